@@ -774,6 +774,30 @@ def verify_step(ctx, x, ids, kind, pipelined=False):
             "streams": S, "kernel_path": path, "what": "sha256 of every stream's whole frame stream of one step"}
 
 
+DUMP_BUDGET = 48 << 20  # bytes of float32 frames written by --dump-outputs
+
+
+def dump_outputs(out_dir, view, ids, suffix=""):
+    """--dump-outputs: the frames the last timed step returned (S, F, 128 + nb_fec, 512 bytes), as float32.  A whole step is
+    ~85 MB of bytes at the headline geometry, so at most DUMP_BUDGET bytes of whole frames are written: a fixed (seed 0)
+    sample of the S * F frames, in (stream, frame) order.
+      frames<suffix>.npy     (k, 128 + nb_fec, 512) float32: the sampled frames, byte for byte
+      frame_ids<suffix>.npy  (k, 3) float64: stream id, stream index in the bank, frame index in the step of every row
+      frame_counts<suffix>.npy (S,) float64: frames every stream's view held"""
+    fr = view.torch()
+    S, F = fr.shape[0], fr.shape[1]
+    per = fr.shape[2] * fr.shape[3] * 4
+    k = min(S * F, DUMP_BUDGET // per)
+    pick = np.sort(np.random.RandomState(0).choice(S * F, k, replace=False)) if k < S * F else np.arange(S * F)
+    sel = fr.reshape(S * F, fr.shape[2], fr.shape[3]).index_select(0, torch.from_numpy(pick).to(fr.device))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "frames%s.npy" % suffix), sel.cpu().numpy().astype(np.float32))
+    s_idx, f_idx = pick // max(F, 1), pick % max(F, 1)
+    np.save(os.path.join(out_dir, "frame_ids%s.npy" % suffix),
+            np.stack([np.asarray(ids, np.float64)[s_idx], s_idx.astype(np.float64), f_idx.astype(np.float64)], axis=1))
+    np.save(os.path.join(out_dir, "frame_counts%s.npy" % suffix), np.full(S, F, np.float64))
+
+
 def relaunch_under_torchrun(args):
     """`python bench.py --gpus N` with N > 1 and no launcher around it: re-execute the same command line under
     torch.distributed.run, one rank per GPU on this node, rendezvous on 127.0.0.1 (the container's host name may not resolve).
@@ -828,7 +852,13 @@ def main():
                          "executes the nccl = RCCL branch on a one-GPU box")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to dry-run the N > 1 path on a box with fewer GPUs than ranks)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frames of the last timed step as DIR/*.npy (float32, a fixed seeded "
+                         "sample of at most %d MiB; see dump_outputs()).  The streams then start from fresh handles after the "
+                         "preroll, so that the same arguments give the same outputs from run to run" % (DUMP_BUDGET >> 20))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.timer_stride <= 0:
         args.timer_stride = 1 if args.steps < 50 else 4
     if args.streams is None:
@@ -900,6 +930,12 @@ def main():
             step(0)
         torch.cuda.synchronize()
         preroll += 10
+    if args.dump_outputs:
+        # the preroll runs for a time, not a number of steps, and the streams carry state from call to call: restart them from
+        # the constructor state so that the timed steps (and the dumped frames) depend on the arguments alone
+        rx.close()
+        rx = sd.RxPipe(ctx, S, log2decim=LOG2DECIM, fcpos=sd.FC_CEN, hb_variant=sd.HB_EO1, sample_bits=16, nb_fec=NB_FEC,
+                       center_frequency_khz=435000, sample_rate=625000)
     for i in range(args.warmup):
         step(i)
     torch.cuda.synchronize()
@@ -914,11 +950,15 @@ def main():
     t0 = time.perf_counter()
     frames = 0
     for i in range(args.steps):
-        frames += step(args.warmup + i).shape[1]
+        last = step(args.warmup + i)
+        frames += last.shape[1]
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        # (the view is valid until the next call: taken before the box-state steps below)
+        dump_outputs(args.dump_outputs, last, ids, "" if world == 1 else "_rank%d" % rank)
     dec_ms, dec_n = ctx.kernel_timing_read(K_DECIMATE)
     fec_ms, fec_n = ctx.kernel_timing_read(K_FEC_ENCODE)
     ctx.kernel_timing(False)

@@ -1,5 +1,5 @@
 // ref_fecbuf_shim.cpp -- C entry points around the REAL reference class SDRdaemonFECBuffer
-// (include/SDRdaemonFECBuffer.h, sdmnbase/SDRdaemonFECBuffer.cpp), compiled where it lies by tests/cxx/Makefile
+// (include/SDRdaemonFECBuffer.h, sdmnbase/SDRdaemonFECBuffer.cpp), compiled where it lies by oracle/Makefile
 // against the product's cm256.h adapter (CM256 = libsdrhip.so on the GPU): the reference's own decoder call site
 // running on the product.  An integration test of the drop-in boundary, not an oracle.
 #include <cstddef>

@@ -1,4 +1,4 @@
-"""The reference's OWN SDRdaemonFECBuffer.cpp, compiled where it lies (tests/cxx/Makefile) against the product's
+"""The reference's OWN SDRdaemonFECBuffer.cpp, compiled where it lies (oracle/Makefile, into oracle/_ref) against the product's
 drop-in cm256.h adapter = libsdrhip.so: the reference's decoder call site (SDRdaemonFECBuffer.cpp:148-213: block
 collection, first-128 policy, decode call, fix-up loop, frame change emission, stats) runs unchanged on the GPU and
 gives what the oracle's restatement of the same chain gives.  (Round 1 also built that class over the ORACLE's CM256
@@ -14,7 +14,7 @@ import signals
 
 
 def _load(name):
-    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cxx", "_build", name)
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", name)
     if not os.path.exists(path):
         pytest.skip("%s not built" % name)
     L = C.CDLL(path)
