@@ -353,6 +353,53 @@ int sdrhip_tx_submit(sdrhip_tx *tx, const uint8_t *rx, const uint8_t *indices, s
 int sdrhip_tx_collect(sdrhip_tx *tx, int16_t *iq_out, size_t out_stride, size_t max_samples, uint8_t *block0_out, size_t *n_out,
                       size_t *n_frames, int wait);
 
+/* ------------------------------------------------------------ FEC buffer bank -- */
+/* A bank of `nstreams` independent SDRdaemonFECBuffer instances (SDRdaemonFECBuffer.h, SDRdaemonFECBuffer.cpp:112-250) fed raw
+ * datagrams: the collecting half of sdrdaemontx's receive path (frame change, first-128 policy, decode at the 128th block,
+ * statistics) on the GPU, for many streams at once.  Each stream behaves exactly like one reference object fed the same datagrams
+ * one at a time, whatever way its datagrams are cut into calls (a frame may begin in one call and end several calls later).
+ * Differences: the initial slot (m_frameHead = -1) released by a stream's first datagram reads zero (the reference hands out
+ * uninitialised memory); context option dec_strict applies as in sdrhip_fec_decode_frames (0, the default: every restored block
+ * is delivered; 1: the reference's copy-back holes), dec_path and dec_plan apply, dec_max_rows does NOT: the bank passes the
+ * decoder a bound it collected itself (the highest recovery row among the first 128 blocks of the batch's frames), so
+ * "dec_rows_exceeded" never grows because of it.  A frame with a repeated original among its first 128 blocks is delivered as
+ * received, the LAST copy of a repeated original in place (cm256_decode fails on such a frame; SDRHIP_FECBUF_DECODE_ERROR). */
+typedef struct sdrhip_fecbuf sdrhip_fecbuf;
+int sdrhip_fecbuf_create(sdrhip_ctx *ctx, int nstreams, sdrhip_fecbuf **out);
+void sdrhip_fecbuf_destroy(sdrhip_fecbuf *b);
+/* back to the constructor's state (m_frameHead = -1, min blocks 256, max recovery 0, zero meta) */
+int sdrhip_fecbuf_reset(sdrhip_fecbuf *b);
+
+#define SDRHIP_FECBUF_DECODED 1      /* m_decoded: the frame reached 128 blocks */
+#define SDRHIP_FECBUF_META 2         /* m_metaRetrieved: block 0 was among its first 128 blocks */
+#define SDRHIP_FECBUF_REPAIRED 4     /* decoded with recovery blocks: erased originals restored */
+#define SDRHIP_FECBUF_DECODE_ERROR 8 /* decoded with recovery blocks, but an original arrived twice: left as received */
+typedef struct {
+    int32_t frame_index;    /* header.frameIndex of the released slot; -1 = the collector's initial slot */
+    int32_t block_count;    /* m_blockCount: every datagram of the frame, not only the first 128 */
+    int32_t recovery_count; /* m_recoveryCount: recovery blocks among the first 128 */
+    uint32_t flags;         /* SDRHIP_FECBUF_* */
+} sdrhip_fecbuf_frame;
+
+/* SDRdaemonFECBuffer::writeAndRead over a batch: stream s gives n_dgrams[s] (host array) datagrams of 512 bytes, in arrival order,
+ * at dgrams + s * dgram_stride_bytes.  Every frame those datagrams release is written, in release order, to
+ * data_out + s * data_stride_bytes (127 x 508 bytes each = getSlotData, frame after frame), its block 0 (508 bytes: the meta
+ * block) to block0_out + (s * max_frames + k) * 508 (block0_out may be NULL), and its record to info_out[s * max_frames + k]
+ * (host).  n_frames[s] (host) receives the count of stream s.  A stream that releases more than max_frames frames: the call
+ * returns SDRHIP_EINVAL with every stream's count in n_frames and consumes NOTHING (call again with room).  dgrams / data_out /
+ * block0_out are in `mem` memory: SDRHIP_MEM_HOST (staged through pinned memory; used in place when the datagrams lie in
+ * sdrhip_host_alloc memory; returns with the outputs written) or SDRHIP_MEM_DEVICE (dgrams and dgram_stride_bytes 16-byte
+ * aligned, data_out / block0_out and data_stride_bytes 4-byte aligned; the outputs are enqueued on the context's stream and not
+ * synchronised).  Either way the call synchronises once, to read back the frame counts. */
+int sdrhip_fecbuf_write_and_read(sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes,
+                                 uint8_t *data_out, size_t data_stride_bytes, uint8_t *block0_out, size_t max_frames,
+                                 sdrhip_fecbuf_frame *info_out, size_t *n_frames, int mem);
+/* The getters of SDRdaemonFECBuffer.h:107-126 for one stream (any pointer may be NULL): getCurNbBlocks, getCurNbRecovery,
+ * getMinNbBlocks, getMaxNbRecovery (the last two reset when read, like the reference's), getCurrentMeta, getOutputMeta (20-byte
+ * MetaDataFEC, zero-padded to 24).  Synchronises the context's stream. */
+int sdrhip_fecbuf_stats(sdrhip_fecbuf *b, int stream, int *cur_nb_blocks, int *cur_nb_recovery, int *min_nb_blocks,
+                        int *max_nb_recovery, uint8_t current_meta[24], uint8_t output_meta[24]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,7 +86,8 @@ bool fec_decode_gather_ok(const sdrhip_ctx *c)
 }
 
 int fec_decode_device(sdrhip_ctx *c, const uint8_t *rx, size_t rx_frame_bytes, const uint8_t *indices, size_t nframes,
-                      uint8_t *payload_out, size_t payload_frame_bytes, uint8_t *block0_out, const DecodeSide *side, const DecodeGather *gather)
+                      uint8_t *payload_out, size_t payload_frame_bytes, uint8_t *block0_out, const DecodeSide *side, const DecodeGather *gather,
+                      int max_rows)
 {
     if (gather && !fec_decode_gather_ok(c)) return fail(SDRHIP_EINVAL, "internal: no-copy decode without the fused-plan decoder");
     // (side: a pipelined Tx pipe decodes on the context's second stream with work buffers of its own, so that the context's
@@ -130,7 +131,8 @@ int fec_decode_device(sdrhip_ctx *c, const uint8_t *rx, size_t rx_frame_bytes, c
     {
         KTimer kt(c, SDRHIP_K_FEC_DECODE, side ? st : nullptr);
         e = launch_fec_decode_device_plan(d, rx, rx_frame_bytes, idx_dev, c->gf_explog, c->gf_tab, (int)nframes, payload_out,
-                                          payload_frame_bytes, block0_out, c->opt.dec_max_rows, c->opt.dec_strict, c->dec_stats, st);
+                                          payload_frame_bytes, block0_out, max_rows > 0 ? max_rows : c->opt.dec_max_rows, c->opt.dec_strict,
+                                          c->dec_stats, st);
     }
     if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "fec decode launch: %s", hipGetErrorString(e));
     return SDRHIP_OK;

@@ -1,0 +1,275 @@
+// sdrhip_fecbuf.cpp -- host side of the FEC buffer bank (include/sdrhip.h, sdrhip_fecbuf_*): nstreams SDRdaemonFECBuffer
+// collectors fed raw datagrams.  A call: upload of the per-stream datagram counts, the classify pass (fecbuf_kernels.hip), ONE
+// read-back of the per-stream frame counts and the batch's highest recovery row (they size the grids and pick the decoder),
+// then the scatter pass, the batched decoder on the frames that need it (sdrhip_fec.cpp, unchanged) and the copy of its output
+// to the frames' places.  The collector state is double-buffered on the device: a call reads state[cur], writes
+// state[cur ^ 1], and only a call that got past every check flips `cur` (an SDRHIP_EINVAL call consumes nothing).
+#include "sdrhip_host.h"
+
+#include <cstring>
+#include <new>
+#include <vector>
+
+using namespace sdrhip;
+
+struct sdrhip_fecbuf {
+    sdrhip_ctx *ctx;
+    int nstreams;
+    int cur = 0;                 // state[cur] is the committed collector state
+    FecBufState *state[2] = {nullptr, nullptr};
+    uint8_t *carry = nullptr;    // [2][S][128][512] the open slots' first 128 super blocks
+    DevBuf small;                // ndg [S], job_off [S + 1], dbase [S], rec_base [S] (int64), counts [S][FB_COUNTS], pub [S][max_frames]
+    DevBuf rec, stage, dmap, dec_out, dec_b0;
+    DevBuf hin, hout, hb0;       // SDRHIP_MEM_HOST staging on the device
+    PinnedBuf pin_up, pin_down, pin_in;
+};
+
+namespace {
+constexpr size_t PAYLOAD = (size_t)127 * SDRHIP_BLOCK_BYTES;
+
+int fecbuf_init_state(sdrhip_fecbuf *b)
+{
+    std::vector<FecBufState> st((size_t)b->nstreams);
+    for (FecBufState &x : st) {
+        memset(&x, 0, sizeof(x));
+        x.head = -1; x.maxrow = -1; x.b0 = -1;
+        x.min_blocks = 256;
+        // MetaDataFEC::init(): zero, m_nbFECBlocks = -1 (byte 11)
+        x.cur_meta[2] = x.out_meta[2] = 0xff000000u;
+    }
+    b->cur = 0;
+    HIP_TRY(hipMemcpyAsync(b->state[0], st.data(), st.size() * sizeof(FecBufState), hipMemcpyHostToDevice, b->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+    return SDRHIP_OK;
+}
+
+// the device-pointer core: dgrams / data_out / block0_out on the device
+int fecbuf_device(sdrhip_fecbuf *b, const uint8_t *dg, const size_t *n_dgrams, size_t dg_stride, uint8_t *data_out, size_t data_stride,
+                  uint8_t *block0_out, size_t max_frames, sdrhip_fecbuf_frame *info_out, size_t *n_frames)
+{
+    sdrhip_ctx *c = b->ctx;
+    const int S = b->nstreams;
+    int rc;
+    // small per-call arrays: [ndg S][job_off S + 1][dbase S][pad] ints, then rec_base (int64), counts, public records
+    const size_t ints = ((size_t)3 * S + 2 + 3) & ~(size_t)3;
+    const size_t off_rb = ints * 4, off_cnt = off_rb + (size_t)S * 8, off_pub = off_cnt + (size_t)S * FB_COUNTS * 4;
+    const size_t small_bytes = off_pub + (size_t)S * max_frames * sizeof(FecBufPub);
+    if ((rc = b->small.reserve(small_bytes))) return rc;
+    if ((rc = b->pin_up.reserve(off_cnt))) return rc;
+    if ((rc = b->pin_down.reserve(small_bytes - off_cnt))) return rc;
+    int *up = b->pin_up.as<int>();
+    long long *rb = reinterpret_cast<long long *>(b->pin_up.as<uint8_t>() + off_rb);
+    long long nrec = 0;
+    for (int s = 0; s < S; ++s) {
+        up[s] = (int)n_dgrams[s];
+        rb[s] = nrec;
+        nrec += (long long)n_dgrams[s] + 1;
+    }
+    if ((rc = b->rec.reserve((size_t)nrec * sizeof(FecBufRec)))) return rc;
+    uint8_t *sm = b->small.as<uint8_t>();
+    HIP_TRY(hipMemcpyAsync(sm, b->pin_up.p, off_cnt, hipMemcpyHostToDevice, c->stream));
+    b->pin_up.mark(c->stream);
+
+    FecBufArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dg = dg; a.dg_stride = dg_stride;
+    a.ndg = reinterpret_cast<const int *>(sm);
+    a.job_off = reinterpret_cast<const int *>(sm) + S;
+    a.dbase = reinterpret_cast<const int *>(sm) + 2 * S + 1;
+    a.rec_base = reinterpret_cast<const long long *>(sm + off_rb);
+    a.counts = reinterpret_cast<int *>(sm + off_cnt);
+    a.pub = reinterpret_cast<FecBufPub *>(sm + off_pub);
+    a.rec = b->rec.as<FecBufRec>();
+    a.max_frames = (int)max_frames;
+    a.st_cur = b->state[b->cur]; a.st_next = b->state[b->cur ^ 1];
+    a.carry_cur_base = b->carry; a.carry_base = b->carry;
+    a.nstreams = S;
+    a.data_out = data_out; a.data_stride = data_stride; a.block0_out = block0_out;
+    hipError_t e = launch_fecbuf_classify(a, c->stream);
+    if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "fecbuf classify launch: %s", hipGetErrorString(e));
+    // the one read-back: counts + public records
+    HIP_TRY(hipMemcpyAsync(b->pin_down.p, sm + off_cnt, small_bytes - off_cnt, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const int *cnt = b->pin_down.as<int>();
+    const FecBufPub *pub = reinterpret_cast<const FecBufPub *>(b->pin_down.as<uint8_t>() + (off_pub - off_cnt));
+    bool room = true;
+    int njobs = 0, nslots = 0, maxrow = -1, maxrec = 0;
+    for (int s = 0; s < S; ++s) {
+        const int *x = cnt + (size_t)s * FB_COUNTS;
+        n_frames[s] = (size_t)x[FB_K];
+        if ((size_t)x[FB_K] > max_frames) room = false;
+        up[S + s] = njobs;
+        up[2 * S + 1 + s] = nslots;
+        njobs += x[FB_K] + 1;
+        nslots += x[FB_D];
+        if (x[FB_MAXROW] > maxrow) maxrow = x[FB_MAXROW];
+        if (x[FB_MAXREC] > maxrec) maxrec = x[FB_MAXREC];
+    }
+    up[2 * S] = njobs;
+    if (!room) return fail(SDRHIP_EINVAL, "fecbuf_write_and_read: a stream releases more than max_frames = %zu frames (n_frames has the counts; nothing was consumed)", max_frames);
+    // everything that can fail for want of memory before the state moves on
+    if (nslots > 0) {
+        if ((rc = b->stage.reserve((size_t)nslots * 128 * SDRHIP_UDPSIZE))) return rc;
+        if ((rc = b->dmap.reserve((size_t)nslots * 2 * sizeof(int)))) return rc;
+        if ((rc = b->dec_out.reserve((size_t)nslots * PAYLOAD))) return rc;
+        if (block0_out && (rc = b->dec_b0.reserve((size_t)nslots * SDRHIP_BLOCK_BYTES))) return rc;
+    }
+    for (int s = 0; s < S; ++s) {
+        const FecBufPub *p = pub + (size_t)s * max_frames;
+        for (size_t k = 0; k < n_frames[s]; ++k) {
+            sdrhip_fecbuf_frame &o = info_out[(size_t)s * max_frames + k];
+            o.frame_index = p[k].frame_index; o.block_count = p[k].block_count; o.recovery_count = p[k].recovery_count; o.flags = p[k].flags;
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(sm + (size_t)S * 4, up + S, ((size_t)2 * S + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    b->pin_up.mark(c->stream);
+    a.stage = b->stage.as<uint8_t>(); a.dmap = b->dmap.as<int>();
+    a.dec_out = b->dec_out.as<uint8_t>(); a.dec_b0 = block0_out ? b->dec_b0.as<uint8_t>() : nullptr;
+    if ((e = launch_fecbuf_scatter(a, njobs, c->stream)) != hipSuccess) return fail(SDRHIP_EDEVICE, "fecbuf scatter launch: %s", hipGetErrorString(e));
+    b->cur ^= 1; // (committed: the scatter pass has written the new carry slots)
+    if (nslots > 0) {
+        // the promise is the batch's highest collected row, never a count: <= 32 rows (indices 0..31) take the one-launch decoder
+        const int max_rows = (maxrow < 32 && maxrec <= 32) ? 32 : 128;
+        if ((rc = fec_decode_device(c, b->stage.as<uint8_t>(), (size_t)128 * SDRHIP_UDPSIZE, nullptr, (size_t)nslots, b->dec_out.as<uint8_t>(), PAYLOAD,
+                                    block0_out ? b->dec_b0.as<uint8_t>() : nullptr, nullptr, nullptr, max_rows)))
+            return rc;
+        if ((e = launch_fecbuf_copy(a, nslots, c->stream)) != hipSuccess) return fail(SDRHIP_EDEVICE, "fecbuf copy launch: %s", hipGetErrorString(e));
+    }
+    return SDRHIP_OK;
+}
+} // namespace
+
+extern "C" int sdrhip_fecbuf_create(sdrhip_ctx *ctx, int nstreams, sdrhip_fecbuf **out)
+{
+    if (!ctx || !out || nstreams <= 0 || nstreams > 65535) return fail(SDRHIP_EINVAL, "fecbuf_create: bad argument");
+    sdrhip::CtxLock lock_(ctx);
+    if (sdrhip_device_count() <= 0) return fail(SDRHIP_EDEVICE, "fecbuf_create: no GPU");
+    HIP_TRY(hipSetDevice(ctx->device));
+    sdrhip_fecbuf *b = new (std::nothrow) sdrhip_fecbuf();
+    if (!b) return fail(SDRHIP_ENOMEM, "out of host memory");
+    b->ctx = ctx; b->nstreams = nstreams;
+    const size_t sb = (size_t)nstreams * sizeof(FecBufState), cb = (size_t)2 * nstreams * 128 * SDRHIP_UDPSIZE;
+    if (hipMalloc(reinterpret_cast<void **>(&b->state[0]), sb) != hipSuccess || hipMalloc(reinterpret_cast<void **>(&b->state[1]), sb) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void **>(&b->carry), cb) != hipSuccess) {
+        if (b->state[0]) (void)hipFree(b->state[0]);
+        if (b->state[1]) (void)hipFree(b->state[1]);
+        delete b;
+        return fail(SDRHIP_ENOMEM, "hipMalloc fecbuf state");
+    }
+    ctx_retain(ctx);
+    int rc = fecbuf_init_state(b);
+    if (rc) { sdrhip_fecbuf_destroy(b); return rc; }
+    *out = b;
+    return SDRHIP_OK;
+}
+
+extern "C" void sdrhip_fecbuf_destroy(sdrhip_fecbuf *b)
+{
+    if (!b) return;
+    sdrhip_ctx *c = b->ctx;
+    {
+        sdrhip::CtxLock lock_(c);
+        (void)hipSetDevice(c->device);
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipFree(b->state[0]); (void)hipFree(b->state[1]); (void)hipFree(b->carry);
+        b->small.release(); b->rec.release(); b->stage.release(); b->dmap.release(); b->dec_out.release(); b->dec_b0.release();
+        b->hin.release(); b->hout.release(); b->hb0.release();
+        b->pin_up.release(); b->pin_down.release(); b->pin_in.release();
+    }
+    delete b;
+    ctx_release(c);
+}
+
+extern "C" int sdrhip_fecbuf_reset(sdrhip_fecbuf *b)
+{
+    if (!b) return fail(SDRHIP_EINVAL, "fecbuf is NULL");
+    sdrhip::CtxLock lock_(b->ctx);
+    HIP_TRY(hipSetDevice(b->ctx->device));
+    return fecbuf_init_state(b);
+}
+
+extern "C" int sdrhip_fecbuf_write_and_read(sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes,
+                                            uint8_t *data_out, size_t data_stride_bytes, uint8_t *block0_out, size_t max_frames,
+                                            sdrhip_fecbuf_frame *info_out, size_t *n_frames, int mem)
+{
+    if (!b) return fail(SDRHIP_EINVAL, "fecbuf is NULL");
+    sdrhip_ctx *c = b->ctx;
+    sdrhip::CtxLock lock_(c);
+    const int S = b->nstreams;
+    if (!n_dgrams || !n_frames) return fail(SDRHIP_EINVAL, "fecbuf_write_and_read: NULL n_dgrams / n_frames");
+    if (mem != SDRHIP_MEM_HOST && mem != SDRHIP_MEM_DEVICE) return fail(SDRHIP_EINVAL, "mem must be SDRHIP_MEM_HOST or SDRHIP_MEM_DEVICE");
+    size_t nmax = 0;
+    for (int s = 0; s < S; ++s) {
+        if (n_dgrams[s] > 0x3fffffffu) return fail(SDRHIP_EINVAL, "fecbuf_write_and_read: too many datagrams in one call");
+        nmax = n_dgrams[s] > nmax ? n_dgrams[s] : nmax;
+    }
+    if (nmax > 0 && !dgrams) return fail(SDRHIP_EINVAL, "fecbuf_write_and_read: NULL dgrams");
+    if (S > 1 && nmax > 0 && dgram_stride_bytes < nmax * SDRHIP_UDPSIZE) return fail(SDRHIP_EINVAL, "fecbuf_write_and_read: dgram_stride_bytes below n_dgrams x 512");
+    if (max_frames > 0 && (!data_out || !info_out)) return fail(SDRHIP_EINVAL, "fecbuf_write_and_read: NULL data_out / info_out");
+    if (max_frames > 0x3fffffffu) return fail(SDRHIP_EINVAL, "fecbuf_write_and_read: max_frames too large");
+    if (S > 1 && max_frames > 0 && data_stride_bytes < max_frames * PAYLOAD) return fail(SDRHIP_EINVAL, "fecbuf_write_and_read: data_stride_bytes below max_frames x 127 x 508");
+    HIP_TRY(hipSetDevice(c->device));
+    if (mem == SDRHIP_MEM_DEVICE) {
+        if ((nmax > 0 && !aligned16(dgrams)) || (S > 1 && dgram_stride_bytes % 16))
+            return fail(SDRHIP_EALIGN, "fecbuf_write_and_read: dgrams / dgram_stride_bytes must be 16-byte aligned");
+        if ((reinterpret_cast<uintptr_t>(data_out) & 3u) || (reinterpret_cast<uintptr_t>(block0_out) & 3u) || (S > 1 && data_stride_bytes % 4))
+            return fail(SDRHIP_EALIGN, "fecbuf_write_and_read: data_out / block0_out / data_stride_bytes must be 4-byte aligned");
+        return fecbuf_device(b, dgrams, n_dgrams, dgram_stride_bytes, data_out, data_stride_bytes, block0_out, max_frames, info_out, n_frames);
+    }
+    // host memory: the datagrams go up as one 2-D copy (from sdrhip_host_alloc memory in place, else through a pinned buffer)
+    int rc;
+    const size_t row = nmax * SDRHIP_UDPSIZE, drow = max_frames * PAYLOAD;
+    if (row && (rc = b->hin.reserve((size_t)S * row))) return rc;
+    if (drow && (rc = b->hout.reserve((size_t)S * drow + 4))) return rc;
+    if (block0_out && max_frames && (rc = b->hb0.reserve((size_t)S * max_frames * SDRHIP_BLOCK_BYTES))) return rc;
+    if (row) {
+        const uint8_t *src = dgrams;
+        size_t sstride = S > 1 ? dgram_stride_bytes : row;
+        if (!host_is_pinned(dgrams, (size_t)(S - 1) * sstride + row)) {
+            if ((rc = b->pin_in.reserve((size_t)S * row))) return rc;
+            for (int s = 0; s < S; ++s) memcpy(b->pin_in.as<uint8_t>() + (size_t)s * row, dgrams + (size_t)s * sstride, n_dgrams[s] * SDRHIP_UDPSIZE);
+            src = b->pin_in.as<uint8_t>(); sstride = row;
+        }
+        HIP_TRY(hipMemcpy2DAsync(b->hin.p, row, src, sstride, row, (size_t)S, hipMemcpyHostToDevice, c->stream));
+        if (src != dgrams) b->pin_in.mark(c->stream);
+    }
+    if ((rc = fecbuf_device(b, b->hin.as<uint8_t>(), n_dgrams, row, b->hout.as<uint8_t>(), drow, block0_out ? b->hb0.as<uint8_t>() : nullptr,
+                            max_frames, info_out, n_frames)))
+        return rc;
+    for (int s = 0; s < S; ++s) {
+        if (!n_frames[s]) continue;
+        HIP_TRY(hipMemcpyAsync(data_out + (size_t)s * data_stride_bytes, b->hout.as<uint8_t>() + (size_t)s * drow, n_frames[s] * PAYLOAD,
+                               hipMemcpyDeviceToHost, c->stream));
+        if (block0_out)
+            HIP_TRY(hipMemcpyAsync(block0_out + (size_t)s * max_frames * SDRHIP_BLOCK_BYTES, b->hb0.as<uint8_t>() + (size_t)s * max_frames * SDRHIP_BLOCK_BYTES,
+                                   n_frames[s] * SDRHIP_BLOCK_BYTES, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_fecbuf_stats(sdrhip_fecbuf *b, int stream, int *cur_nb_blocks, int *cur_nb_recovery, int *min_nb_blocks, int *max_nb_recovery,
+                                   uint8_t current_meta[24], uint8_t output_meta[24])
+{
+    if (!b) return fail(SDRHIP_EINVAL, "fecbuf is NULL");
+    sdrhip::CtxLock lock_(b->ctx);
+    if (stream < 0 || stream >= b->nstreams) return fail(SDRHIP_EINVAL, "fecbuf_stats: stream out of range");
+    HIP_TRY(hipSetDevice(b->ctx->device));
+    FecBufState x;
+    FecBufState *d = b->state[b->cur] + stream;
+    HIP_TRY(hipMemcpyAsync(&x, d, sizeof(x), hipMemcpyDeviceToHost, b->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+    if (cur_nb_blocks) *cur_nb_blocks = x.cur_blocks;
+    if (cur_nb_recovery) *cur_nb_recovery = x.cur_recov;
+    if (current_meta) memcpy(current_meta, x.cur_meta, 24);
+    if (output_meta) memcpy(output_meta, x.out_meta, 24);
+    // getMinNbBlocks / getMaxNbRecovery reset what they read (SDRdaemonFECBuffer.h:115-126)
+    int upd[4] = {x.cur_blocks, x.cur_recov, x.min_blocks, x.max_recov};
+    if (min_nb_blocks) { *min_nb_blocks = x.min_blocks; upd[2] = 256; }
+    if (max_nb_recovery) { *max_nb_recovery = x.max_recov; upd[3] = 0; }
+    if (min_nb_blocks || max_nb_recovery) {
+        HIP_TRY(hipMemcpyAsync(&d->cur_blocks, upd, sizeof(upd), hipMemcpyHostToDevice, b->ctx->stream));
+        HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+    }
+    return SDRHIP_OK;
+}

@@ -120,9 +120,12 @@ struct DecodeGather {
     int rows;
 };
 bool fec_decode_gather_ok(const sdrhip_ctx *c);
+// max_rows > 0: the promise for this batch instead of the context option dec_max_rows (the FEC buffer bank knows the rows it collected)
 int fec_decode_device(sdrhip_ctx *ctx, const uint8_t *rx, size_t rx_frame_bytes, const uint8_t *indices, size_t nframes,
                       uint8_t *payload_out, size_t payload_frame_bytes, uint8_t *block0_out, const DecodeSide *side = nullptr,
-                      const DecodeGather *gather = nullptr);
+                      const DecodeGather *gather = nullptr, int max_rows = 0);
+// sdrhip_host_alloc memory: pinned, usable in place
+bool host_is_pinned(const void *p, size_t n);
 
 } // namespace sdrhip
 

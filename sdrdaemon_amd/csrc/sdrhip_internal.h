@@ -349,4 +349,61 @@ hipError_t launch_fec_decode_device_plan(const DecodeBuffers &d, const uint8_t *
                                          const uint8_t *explog, const uint8_t *tab, int nframes, uint8_t *payload_out,
                                          size_t payload_frame_bytes, uint8_t *block0_out, int max_rows, int strict, unsigned *stats, hipStream_t stream);
 
+
+// SDRdaemonFECBuffer bank (fecbuf_kernels.hip, sdrhip_fecbuf.cpp): nstreams independent collectors fed raw datagrams
+// per-stream collector state, double-buffered (a call reads [cur], writes [cur ^ 1]; the host flips cur when the call commits)
+struct FecBufState {
+    int head;              // m_frameHead: frame index of the open slot, -1 = the constructor's
+    int count;             // m_blockCount of the open slot (every arrival)
+    int recov;             // m_recoveryCount (among the first 128)
+    int maxrow;            // highest recovery row (blockIndex - 128) among the first 128, -1 = none
+    unsigned pres[4];      // originals present among the first 128 (bit b = blockIndex b)
+    int dup;               // an original arrived twice among the first 128
+    int cbuf;              // carry buffer (0 / 1) that holds the open slot's first 128 super blocks
+    int cur_blocks, cur_recov, min_blocks, max_recov; // getCurNbBlocks, getCurNbRecovery, m_minNbBlocks, m_maxNbRecovery
+    unsigned cur_meta[6], out_meta[6];                // m_currentMeta, m_outputMeta (MetaDataFEC: 20 bytes, then zero)
+    int b0;                // rank of the last block 0 among the open slot's first 128, -1 = none (m_metaRetrieved)
+    int pad;
+};
+// a frame of the call, internal form: rank r of its first 128 arrivals is datagram start + r of the call, or (start + r < 0) super
+// block r of the carry buffer st_cur.cbuf
+struct FecBufRec {
+    int start, count, dslot, flags; // dslot: index among the stream's frames that go to the decoder (-1: written straight)
+};
+// public record (sdrhip_fecbuf_frame)
+struct FecBufPub {
+    int frame_index, block_count, recovery_count;
+    unsigned flags;
+};
+// per-stream results of the classify pass read back by the host
+enum { FB_K = 0, FB_D, FB_MAXROW, FB_MAXREC, FB_COUNTS = 8 };
+struct FecBufArgs {
+    const uint8_t *dg;           // stream s: datagram i at dg + s * dg_stride + i * 512
+    size_t dg_stride;
+    const int *ndg;              // [S] datagrams per stream in this call
+    const long long *rec_base;   // [S] first internal record of the stream (prefix of ndg + 1)
+    FecBufRec *rec;
+    FecBufPub *pub;              // [S][max_frames] public records (released frames only, k < max_frames)
+    int *counts;                 // [S][FB_COUNTS]
+    int max_frames;
+    const FecBufState *st_cur;
+    FecBufState *st_next;
+    const uint8_t *carry_cur_base; // carry buffers: [2][S][128][512]
+    uint8_t *carry_base;
+    int nstreams;
+    // scatter pass
+    const int *job_off;          // [S + 1] prefix of K_s + 1 (the released frames and the open slot of every stream)
+    const int *dbase;            // [S] first staging slot of the stream's frames that go to the decoder
+    uint8_t *stage;              // [D][128][512] arrival-order super blocks for the decoder
+    int *dmap;                   // [D][2] stream, frame of every staging slot
+    uint8_t *data_out;           // stream s, frame k: data_out + s * data_stride + k * 127 * 508
+    size_t data_stride;
+    uint8_t *block0_out;         // stream s, frame k: block0_out + (s * max_frames + k) * 508 (may be NULL)
+    const uint8_t *dec_out, *dec_b0; // the decoder's output of staging slot j: dec_out + j * 127 * 508, dec_b0 + j * 508
+};
+enum { FB_DECODED = 1, FB_META = 2, FB_REPAIRED = 4, FB_DECODE_ERROR = 8 };
+hipError_t launch_fecbuf_classify(const FecBufArgs &a, hipStream_t stream);
+hipError_t launch_fecbuf_scatter(const FecBufArgs &a, int njobs, hipStream_t stream);
+hipError_t launch_fecbuf_copy(const FecBufArgs &a, int nslots, hipStream_t stream);
+
 } // namespace sdrhip

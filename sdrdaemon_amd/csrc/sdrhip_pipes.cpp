@@ -629,6 +629,8 @@ namespace {
 struct HostRange { const char *p; size_t n; };
 std::mutex g_host_mtx;
 std::vector<HostRange> g_host_ranges;
+} // namespace
+namespace sdrhip {
 bool host_is_pinned(const void *p, size_t n)
 {
     std::lock_guard<std::mutex> g(g_host_mtx);
@@ -637,6 +639,8 @@ bool host_is_pinned(const void *p, size_t n)
         if (c >= r.p && c + n <= r.p + r.n) return true;
     return false;
 }
+} // namespace sdrhip
+namespace {
 int rx_launch_batch(sdrhip_rx *rx, sdrhip_rx::Batch &b)
 {
     sdrhip_ctx *c = rx->ctx;

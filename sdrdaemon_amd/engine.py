@@ -773,3 +773,84 @@ class TxPipe:
             self.close()
         except Exception:
             pass
+
+
+class FECBufferFrame(C.Structure):
+    """sdrhip_fecbuf_frame"""
+    _fields_ = [("frame_index", C.c_int32), ("block_count", C.c_int32), ("recovery_count", C.c_int32), ("flags", C.c_uint32)]
+
+
+FECBUF_DECODED, FECBUF_META, FECBUF_REPAIRED, FECBUF_DECODE_ERROR = 1, 2, 4, 8
+
+
+class FECBufferBank:
+    """nstreams independent SDRdaemonFECBuffer collectors fed raw 512-byte datagrams (sdrhip_fecbuf).  write_and_read() takes one
+    (n_s, 512) uint8 array per stream -- numpy (host memory) or torch device tensors -- and returns per stream the frames the
+    datagrams released: (data (F, 127 * 508) uint8 = getSlotData, block0 (F, 508) uint8 = the meta block, records: a list of
+    dicts frame_index / block_count / recovery_count / flags)."""
+
+    def __init__(self, ctx, nstreams=1):
+        self.ctx, self.nstreams = ctx, nstreams
+        self.h = C.c_void_p()
+        check(ctx.lib.sdrhip_fecbuf_create(ctx.h, nstreams, C.byref(self.h)))
+
+    def __del__(self):
+        h = getattr(self, "h", None)
+        if h is not None and h.value:
+            self.ctx.lib.sdrhip_fecbuf_destroy(h)
+            self.h = C.c_void_p()
+
+    def reset(self):
+        check(self.ctx.lib.sdrhip_fecbuf_reset(self.h))
+
+    def write_and_read(self, dgrams_per_stream, max_frames=None):
+        S = self.nstreams
+        if len(dgrams_per_stream) != S:
+            raise ValueError("one datagram array per stream")
+        is_t = any(_is_torch(d) for d in dgrams_per_stream)
+        counts = [int(d.shape[0]) for d in dgrams_per_stream]
+        nmax = max(counts + [0])
+        if is_t:
+            dev = next(d.device for d in dgrams_per_stream if _is_torch(d))
+            buf = torch.zeros((S, max(nmax, 1), UDPSIZE), dtype=torch.uint8, device=dev)
+            for s, d in enumerate(dgrams_per_stream):
+                if counts[s]:
+                    buf[s, :counts[s]] = d.reshape(counts[s], UDPSIZE)
+        else:
+            buf = np.zeros((S, max(nmax, 1), UDPSIZE), np.uint8)
+            for s, d in enumerate(dgrams_per_stream):
+                if counts[s]:
+                    buf[s, :counts[s]] = np.asarray(d, np.uint8).reshape(counts[s], UDPSIZE)
+        if max_frames is None:
+            max_frames = nmax  # (a call releases at most one frame per datagram)
+        F = max(max_frames, 1)
+        pb = 127 * BLOCK_BYTES
+        if is_t:
+            data = torch.empty((S, F, pb), dtype=torch.uint8, device=buf.device)
+            b0 = torch.empty((S, F, BLOCK_BYTES), dtype=torch.uint8, device=buf.device)
+        else:
+            data = np.empty((S, F, pb), np.uint8)
+            b0 = np.empty((S, F, BLOCK_BYTES), np.uint8)
+        info = (FECBufferFrame * (S * F))()
+        nd = (C.c_size_t * S)(*counts)
+        nf = (C.c_size_t * S)()
+        rc = self.ctx.lib.sdrhip_fecbuf_write_and_read(self.h, _ptr(buf), nd, buf.shape[1] * UDPSIZE, _ptr(data), F * pb, _ptr(b0),
+                                                       max_frames, info, nf, MEM_DEVICE if is_t else MEM_HOST)
+        self.last_n_frames = [int(x) for x in nf]
+        check(rc)
+        out = []
+        for s in range(S):
+            k = int(nf[s])
+            recs = [dict(frame_index=info[s * F + j].frame_index, block_count=info[s * F + j].block_count,
+                         recovery_count=info[s * F + j].recovery_count, flags=info[s * F + j].flags) for j in range(k)]
+            out.append((data[s, :k], b0[s, :k], recs))
+        return out
+
+    def stats(self, stream):
+        """getCurNbBlocks, getCurNbRecovery, getMinNbBlocks, getMaxNbRecovery (these two reset when read), getCurrentMeta,
+        getOutputMeta (24 bytes: the 20-byte MetaDataFEC, zero padded) of one stream, as a dict"""
+        v = [C.c_int() for _ in range(4)]
+        cm, om = (C.c_uint8 * 24)(), (C.c_uint8 * 24)()
+        check(self.ctx.lib.sdrhip_fecbuf_stats(self.h, stream, *[C.byref(x) for x in v], cm, om))
+        return dict(cur_nb_blocks=v[0].value, cur_nb_recovery=v[1].value, min_nb_blocks=v[2].value, max_nb_recovery=v[3].value,
+                    current_meta=bytes(cm), output_meta=bytes(om))
