@@ -400,6 +400,25 @@ int sdrhip_fecbuf_write_and_read(sdrhip_fecbuf *b, const uint8_t *dgrams, const 
 int sdrhip_fecbuf_stats(sdrhip_fecbuf *b, int stream, int *cur_nb_blocks, int *cur_nb_recovery, int *min_nb_blocks,
                         int *max_nb_recovery, uint8_t current_meta[24], uint8_t output_meta[24]);
 
+/* ------------------------------------------------------------ Tx pipe fed datagrams -- */
+/* sdrdaemontx's receive chain for every stream of the bank (UDPSourceFEC::read -> SDRdaemonFECBuffer::writeAndRead ->
+ * Upsampler::process): datagrams in, interpolated samples out.  dgrams, n_dgrams, dgram_stride_bytes, max_frames, block0_out,
+ * info_out, n_frames and mem mean what they mean for sdrhip_fecbuf_write_and_read; the handle's collector (one
+ * SDRdaemonFECBuffer per stream, created on the first call) behaves exactly like the bank.  Stream s gets
+ * n_frames[s] * 16129 << log2interp samples at iq_out + 2 * s * out_stride (room for max_frames * 16129 << log2interp per stream;
+ * samples past a stream's count are unspecified).  Each stream keeps one set of interpolator histories, shared with
+ * sdrhip_tx_process (a stream of the handle is one Upsampler); a stream that releases no frame keeps them as they are, and
+ * sdrhip_tx_reconfigure applies to the next call of either entry.  SDRHIP_EINVAL with nothing consumed (neither the collector
+ * nor any history moves; n_frames holds every stream's count) when a stream would release more than max_frames, and while the
+ * handle is pipelined or asynchronous batches are in flight.  Device memory: iq_out 16-byte aligned and out_stride a multiple
+ * of 4 samples (as sdrhip_tx_process), block0_out 4-byte aligned; the call synchronises once, for the bank's read-back of the
+ * frame counts.  Host memory: the call returns with the outputs written. */
+int sdrhip_tx_process_datagrams(sdrhip_tx *tx, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes,
+                                int16_t *iq_out, size_t out_stride, size_t max_frames, uint8_t *block0_out,
+                                sdrhip_fecbuf_frame *info_out, size_t *n_frames, int mem);
+/* the handle's collector (borrowed; destroyed with the handle) for sdrhip_fecbuf_stats / sdrhip_fecbuf_reset */
+int sdrhip_tx_collector(sdrhip_tx *tx, sdrhip_fecbuf **out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,7 @@ EXPORTS = [
     "sdrhip_rx_max_frames", "sdrhip_rx_frames_view", "sdrhip_tx_create", "sdrhip_tx_destroy", "sdrhip_tx_reconfigure", "sdrhip_tx_process", "sdrhip_tx_set_pipelined", "sdrhip_tx_flush", "sdrhip_tx_pending_samples", "sdrhip_tx_set_async", "sdrhip_tx_submit", "sdrhip_tx_collect",
     "sdrhip_testsource_create", "sdrhip_testsource_destroy", "sdrhip_testsource_configure", "sdrhip_testsource_get", "sdrhip_testsource_read",
     "sdrhip_fecbuf_create", "sdrhip_fecbuf_destroy", "sdrhip_fecbuf_reset", "sdrhip_fecbuf_write_and_read", "sdrhip_fecbuf_stats",
+    "sdrhip_tx_process_datagrams", "sdrhip_tx_collector",
 ]
 
 
@@ -128,6 +129,8 @@ def load():
     lib.sdrhip_fecbuf_reset.argtypes = [vp]
     lib.sdrhip_fecbuf_write_and_read.argtypes = [vp, vp, C.POINTER(sz), sz, vp, sz, vp, sz, vp, C.POINTER(sz), i]
     lib.sdrhip_fecbuf_stats.argtypes = [vp, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i), vp, vp]
+    lib.sdrhip_tx_process_datagrams.argtypes = [vp, vp, C.POINTER(sz), sz, vp, sz, sz, vp, vp, C.POINTER(sz), i]
+    lib.sdrhip_tx_collector.argtypes = [vp, C.POINTER(vp)]
     lib.sdrhip_testsource_create.argtypes = [vp, i, C.POINTER(vp)]
     lib.sdrhip_testsource_destroy.argtypes = [vp]
     lib.sdrhip_testsource_destroy.restype = None

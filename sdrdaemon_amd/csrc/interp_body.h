@@ -4,6 +4,7 @@
 #include "sdrhip_internal.h"
 
 #include <cstring>
+#include <type_traits>
 
 namespace sdrhip {
 namespace {
@@ -39,6 +40,10 @@ template <int NS_> struct IGeo {
     static constexpr int base(int s) { return s == 0 ? 0 : base(s - 1) + 2 * stride(s - 1); }
     static constexpr int ldsDw = base(NS);
 };
+
+// the geometry of the ragged instantiation (interp_ragged_kernel): the same, as a type of its own, so that every helper templated on
+// it is instantiated apart from the uniform kernel's -- sharing them changed how hipcc compiled the uniform kernel
+template <int NS_> struct IGeoRagged : IGeo<NS_> {};
 
 struct IOut {
     unsigned *out;
@@ -170,10 +175,11 @@ template <class G, int S = 0> __device__ __forceinline__ void state_store(const 
 
 // L = log2 interpolation (6 = the reference's 5-stage + zero stuffing variant)
 // one segment (seg of a.nseg, a.nsub_per_seg macro-cycles each) of one stream; lds: IGeo<NS>::ldsDw dwords
-template <int L> __device__ __forceinline__ void interp_segment(const InterpArgs &a, int seg, int stream, int *lds)
+// (RAGGED: the same code, instantiated apart for interp_ragged_kernel, which has set a.n_in / a.nseg for the stream)
+template <int L, bool RAGGED = false> __device__ __forceinline__ void interp_segment(const InterpArgs &a, int seg, int stream, int *lds)
 {
     constexpr int NS = (L == 6) ? 5 : L;
-    using G = IGeo<NS>;
+    using G = typename std::conditional<RAGGED, IGeoRagged<NS>, IGeo<NS>>::type;
     constexpr int CI = G::mc;
     static_assert(G::ldsDw * 4 <= 64 * 1024, "LDS budget");
 

@@ -56,6 +56,39 @@ template <int L, int WPW> __global__ __launch_bounds__(WNT * WPW) void interp_wa
     interp_wave_segment<L, true>(a, seg, blockIdx.y, lds[w]);
 }
 
+// Ragged launches (InterpArgs::count): the grid is planned for the largest stream, every (stream, segment) finds its stream's
+// own end.  The count is wave-uniform (one stream per workgroup row): a scalar load.  A segment past its stream's last returns at
+// once; the last one (segment 0 of a stream without input: it copies state_cur through) writes state_next, as seg == nseg - 1
+// does in a uniform launch.  -> false: nothing to do; else `a` holds the stream's n_in and an nseg whose last segment is its own.
+__device__ __forceinline__ bool ragged_args(InterpArgs &a, int seg, int stream, size_t seg_len)
+{
+    const int k = __builtin_amdgcn_readfirstlane(a.count[(size_t)stream * (size_t)a.count_stride]);
+    size_t n = (size_t)(unsigned)k * (size_t)(unsigned)a.count_unit;
+    if (n > a.n_in) n = a.n_in; // (never beyond what the grid and the buffers were planned for)
+    const size_t start = (size_t)seg * seg_len;
+    if (seg != 0 && start >= n) return false;
+    if (start + seg_len >= n) a.nseg = seg + 1;
+    a.n_in = n;
+    return true;
+}
+
+template <int L> __global__ __launch_bounds__(NT) void interp_ragged_kernel(InterpArgs a)
+{
+    __shared__ __attribute__((aligned(16))) int lds[IGeo<(L == 6) ? 5 : L>::ldsDw];
+    if (!ragged_args(a, (int)blockIdx.x, (int)blockIdx.y, (size_t)a.nsub_per_seg * IGeo<(L == 6) ? 5 : L>::mc)) return;
+    interp_segment<L, true>(a, blockIdx.x, blockIdx.y, lds);
+}
+
+template <int L, int WPW> __global__ __launch_bounds__(WNT * WPW) void interp_wave_ragged_kernel(InterpArgs a)
+{
+    __shared__ __attribute__((aligned(16))) int lds[WPW][WGeo<(L == 6) ? 5 : L>::ldsDw];
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int seg = (int)blockIdx.x * WPW + w;
+    if (seg >= a.nseg) return;
+    if (!ragged_args(a, seg, (int)blockIdx.y, (size_t)a.nsub_per_seg * WB)) return;
+    interp_wave_segment<L>(a, seg, blockIdx.y, lds[w]);
+}
+
 template <int L> hipError_t launch_w(const InterpArgs &a, hipStream_t stream)
 {
     constexpr int WPW = 4;
@@ -73,6 +106,23 @@ template <int L> hipError_t launch_w(const InterpArgs &a, hipStream_t stream)
 template <int L> hipError_t launch_l(const InterpArgs &a, hipStream_t stream)
 {
     hipLaunchKernelGGL((interp_kernel<L>), dim3(a.nseg, a.nstreams), dim3(NT), 0, stream, a);
+    return hipGetLastError();
+}
+
+// (the same workgroup shapes as launch_w / launch_l, decided on the planned -- largest -- grid)
+template <int L> hipError_t launch_w_ragged(const InterpArgs &a, hipStream_t stream)
+{
+    constexpr int WPW = 4;
+    if ((size_t)a.nseg * (size_t)a.nstreams >= 4096)
+        hipLaunchKernelGGL((interp_wave_ragged_kernel<L, WPW>), dim3((a.nseg + WPW - 1) / WPW, a.nstreams), dim3(WNT * WPW), 0, stream, a);
+    else
+        hipLaunchKernelGGL((interp_wave_ragged_kernel<L, 1>), dim3(a.nseg, a.nstreams), dim3(WNT), 0, stream, a);
+    return hipGetLastError();
+}
+
+template <int L> hipError_t launch_l_ragged(const InterpArgs &a, hipStream_t stream)
+{
+    hipLaunchKernelGGL((interp_ragged_kernel<L>), dim3(a.nseg, a.nstreams), dim3(NT), 0, stream, a);
     return hipGetLastError();
 }
 
@@ -126,6 +176,33 @@ hipError_t launch_interpolate(int log2interp, const InterpArgs &a, hipStream_t s
     case 4: return launch_l<4>(a, stream);
     case 5: return launch_l<5>(a, stream);
     case 6: return launch_l<6>(a, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_interpolate_wave_ragged(int log2interp, const InterpArgs &a, hipStream_t stream)
+{
+    if (!a.count || a.gmap) return hipErrorInvalidValue;
+    switch (log2interp) {
+    case 2: return launch_w_ragged<2>(a, stream);
+    case 3: return launch_w_ragged<3>(a, stream);
+    case 4: return launch_w_ragged<4>(a, stream);
+    case 5: return launch_w_ragged<5>(a, stream);
+    case 6: return launch_w_ragged<6>(a, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_interpolate_ragged(int log2interp, const InterpArgs &a, hipStream_t stream)
+{
+    if (!a.count) return hipErrorInvalidValue;
+    switch (log2interp) {
+    case 1: return launch_l_ragged<1>(a, stream);
+    case 2: return launch_l_ragged<2>(a, stream);
+    case 3: return launch_l_ragged<3>(a, stream);
+    case 4: return launch_l_ragged<4>(a, stream);
+    case 5: return launch_l_ragged<5>(a, stream);
+    case 6: return launch_l_ragged<6>(a, stream);
     }
     return hipErrorInvalidValue;
 }

@@ -27,6 +27,9 @@ struct sdrhip_fecbuf {
 namespace {
 constexpr size_t PAYLOAD = (size_t)127 * SDRHIP_BLOCK_BYTES;
 
+// byte offset of the per-stream counts ([S][FB_COUNTS]) in `small`, behind [ndg S][job_off S + 1][dbase S][pad] ints and rec_base (int64)
+size_t counts_offset(int S) { return (((size_t)3 * S + 2 + 3) & ~(size_t)3) * 4 + (size_t)S * 8; }
+
 int fecbuf_init_state(sdrhip_fecbuf *b)
 {
     std::vector<FecBufState> st((size_t)b->nstreams);
@@ -52,7 +55,7 @@ int fecbuf_device(sdrhip_fecbuf *b, const uint8_t *dg, const size_t *n_dgrams, s
     int rc;
     // small per-call arrays: [ndg S][job_off S + 1][dbase S][pad] ints, then rec_base (int64), counts, public records
     const size_t ints = ((size_t)3 * S + 2 + 3) & ~(size_t)3;
-    const size_t off_rb = ints * 4, off_cnt = off_rb + (size_t)S * 8, off_pub = off_cnt + (size_t)S * FB_COUNTS * 4;
+    const size_t off_rb = ints * 4, off_cnt = counts_offset(S), off_pub = off_cnt + (size_t)S * FB_COUNTS * 4;
     const size_t small_bytes = off_pub + (size_t)S * max_frames * sizeof(FecBufPub);
     if ((rc = b->small.reserve(small_bytes))) return rc;
     if ((rc = b->pin_up.reserve(off_cnt))) return rc;
@@ -188,6 +191,43 @@ extern "C" int sdrhip_fecbuf_reset(sdrhip_fecbuf *b)
     return fecbuf_init_state(b);
 }
 
+namespace {
+// the datagram arguments of a call (sdrhip_fecbuf_write_and_read, sdrhip_tx_process_datagrams); *nmax = the most datagrams of a stream
+int check_dgrams(int S, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes, int mem, const char *who, size_t *nmax)
+{
+    if (mem != SDRHIP_MEM_HOST && mem != SDRHIP_MEM_DEVICE) return fail(SDRHIP_EINVAL, "mem must be SDRHIP_MEM_HOST or SDRHIP_MEM_DEVICE");
+    *nmax = 0;
+    for (int s = 0; s < S; ++s) {
+        if (n_dgrams[s] > 0x3fffffffu) return fail(SDRHIP_EINVAL, "%s: too many datagrams in one call", who);
+        *nmax = n_dgrams[s] > *nmax ? n_dgrams[s] : *nmax;
+    }
+    if (*nmax > 0 && !dgrams) return fail(SDRHIP_EINVAL, "%s: NULL dgrams", who);
+    if (S > 1 && *nmax > 0 && dgram_stride_bytes < *nmax * SDRHIP_UDPSIZE) return fail(SDRHIP_EINVAL, "%s: dgram_stride_bytes below n_dgrams x 512", who);
+    return SDRHIP_OK;
+}
+
+// host memory: the datagrams go up as one 2-D copy (from sdrhip_host_alloc memory in place, else through a pinned buffer) to
+// b->hin, `row` bytes per stream
+int upload_dgrams(sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes, size_t row)
+{
+    sdrhip_ctx *c = b->ctx;
+    const int S = b->nstreams;
+    int rc;
+    if (!row) return SDRHIP_OK;
+    if ((rc = b->hin.reserve((size_t)S * row))) return rc;
+    const uint8_t *src = dgrams;
+    size_t sstride = S > 1 ? dgram_stride_bytes : row;
+    if (!host_is_pinned(dgrams, (size_t)(S - 1) * sstride + row)) {
+        if ((rc = b->pin_in.reserve((size_t)S * row))) return rc;
+        for (int s = 0; s < S; ++s) memcpy(b->pin_in.as<uint8_t>() + (size_t)s * row, dgrams + (size_t)s * sstride, n_dgrams[s] * SDRHIP_UDPSIZE);
+        src = b->pin_in.as<uint8_t>(); sstride = row;
+    }
+    HIP_TRY(hipMemcpy2DAsync(b->hin.p, row, src, sstride, row, (size_t)S, hipMemcpyHostToDevice, c->stream));
+    if (src != dgrams) b->pin_in.mark(c->stream);
+    return SDRHIP_OK;
+}
+} // namespace
+
 extern "C" int sdrhip_fecbuf_write_and_read(sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes,
                                             uint8_t *data_out, size_t data_stride_bytes, uint8_t *block0_out, size_t max_frames,
                                             sdrhip_fecbuf_frame *info_out, size_t *n_frames, int mem)
@@ -197,14 +237,9 @@ extern "C" int sdrhip_fecbuf_write_and_read(sdrhip_fecbuf *b, const uint8_t *dgr
     sdrhip::CtxLock lock_(c);
     const int S = b->nstreams;
     if (!n_dgrams || !n_frames) return fail(SDRHIP_EINVAL, "fecbuf_write_and_read: NULL n_dgrams / n_frames");
-    if (mem != SDRHIP_MEM_HOST && mem != SDRHIP_MEM_DEVICE) return fail(SDRHIP_EINVAL, "mem must be SDRHIP_MEM_HOST or SDRHIP_MEM_DEVICE");
     size_t nmax = 0;
-    for (int s = 0; s < S; ++s) {
-        if (n_dgrams[s] > 0x3fffffffu) return fail(SDRHIP_EINVAL, "fecbuf_write_and_read: too many datagrams in one call");
-        nmax = n_dgrams[s] > nmax ? n_dgrams[s] : nmax;
-    }
-    if (nmax > 0 && !dgrams) return fail(SDRHIP_EINVAL, "fecbuf_write_and_read: NULL dgrams");
-    if (S > 1 && nmax > 0 && dgram_stride_bytes < nmax * SDRHIP_UDPSIZE) return fail(SDRHIP_EINVAL, "fecbuf_write_and_read: dgram_stride_bytes below n_dgrams x 512");
+    int rc;
+    if ((rc = check_dgrams(S, dgrams, n_dgrams, dgram_stride_bytes, mem, "fecbuf_write_and_read", &nmax))) return rc;
     if (max_frames > 0 && (!data_out || !info_out)) return fail(SDRHIP_EINVAL, "fecbuf_write_and_read: NULL data_out / info_out");
     if (max_frames > 0x3fffffffu) return fail(SDRHIP_EINVAL, "fecbuf_write_and_read: max_frames too large");
     if (S > 1 && max_frames > 0 && data_stride_bytes < max_frames * PAYLOAD) return fail(SDRHIP_EINVAL, "fecbuf_write_and_read: data_stride_bytes below max_frames x 127 x 508");
@@ -217,22 +252,10 @@ extern "C" int sdrhip_fecbuf_write_and_read(sdrhip_fecbuf *b, const uint8_t *dgr
         return fecbuf_device(b, dgrams, n_dgrams, dgram_stride_bytes, data_out, data_stride_bytes, block0_out, max_frames, info_out, n_frames);
     }
     // host memory: the datagrams go up as one 2-D copy (from sdrhip_host_alloc memory in place, else through a pinned buffer)
-    int rc;
     const size_t row = nmax * SDRHIP_UDPSIZE, drow = max_frames * PAYLOAD;
-    if (row && (rc = b->hin.reserve((size_t)S * row))) return rc;
     if (drow && (rc = b->hout.reserve((size_t)S * drow + 4))) return rc;
     if (block0_out && max_frames && (rc = b->hb0.reserve((size_t)S * max_frames * SDRHIP_BLOCK_BYTES))) return rc;
-    if (row) {
-        const uint8_t *src = dgrams;
-        size_t sstride = S > 1 ? dgram_stride_bytes : row;
-        if (!host_is_pinned(dgrams, (size_t)(S - 1) * sstride + row)) {
-            if ((rc = b->pin_in.reserve((size_t)S * row))) return rc;
-            for (int s = 0; s < S; ++s) memcpy(b->pin_in.as<uint8_t>() + (size_t)s * row, dgrams + (size_t)s * sstride, n_dgrams[s] * SDRHIP_UDPSIZE);
-            src = b->pin_in.as<uint8_t>(); sstride = row;
-        }
-        HIP_TRY(hipMemcpy2DAsync(b->hin.p, row, src, sstride, row, (size_t)S, hipMemcpyHostToDevice, c->stream));
-        if (src != dgrams) b->pin_in.mark(c->stream);
-    }
+    if ((rc = upload_dgrams(b, dgrams, n_dgrams, dgram_stride_bytes, row))) return rc;
     if ((rc = fecbuf_device(b, b->hin.as<uint8_t>(), n_dgrams, row, b->hout.as<uint8_t>(), drow, block0_out ? b->hb0.as<uint8_t>() : nullptr,
                             max_frames, info_out, n_frames)))
         return rc;
@@ -247,6 +270,46 @@ extern "C" int sdrhip_fecbuf_write_and_read(sdrhip_fecbuf *b, const uint8_t *dgr
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SDRHIP_OK;
 }
+
+namespace sdrhip {
+int fecbuf_check_dgrams(const sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes, int mem, const char *who)
+{
+    size_t nmax = 0;
+    int rc = check_dgrams(b->nstreams, dgrams, n_dgrams, dgram_stride_bytes, mem, who, &nmax);
+    if (rc) return rc;
+    if (mem == SDRHIP_MEM_DEVICE && ((nmax > 0 && !aligned16(dgrams)) || (b->nstreams > 1 && dgram_stride_bytes % 16)))
+        return fail(SDRHIP_EALIGN, "%s: dgrams / dgram_stride_bytes must be 16-byte aligned", who);
+    return SDRHIP_OK;
+}
+
+int fecbuf_collect(sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes, int mem, uint8_t *data_out,
+                   size_t data_stride_bytes, uint8_t *block0_out, size_t max_frames, sdrhip_fecbuf_frame *info_out, size_t *n_frames,
+                   const int **counts)
+{
+    sdrhip_ctx *c = b->ctx;
+    const int S = b->nstreams;
+    int rc;
+    if (mem == SDRHIP_MEM_DEVICE)
+        rc = fecbuf_device(b, dgrams, n_dgrams, dgram_stride_bytes, data_out, data_stride_bytes, block0_out, max_frames, info_out, n_frames);
+    else {
+        size_t nmax = 0;
+        for (int s = 0; s < S; ++s) nmax = n_dgrams[s] > nmax ? n_dgrams[s] : nmax;
+        const size_t row = nmax * SDRHIP_UDPSIZE;
+        if (block0_out && max_frames && (rc = b->hb0.reserve((size_t)S * max_frames * SDRHIP_BLOCK_BYTES))) return rc;
+        if ((rc = upload_dgrams(b, dgrams, n_dgrams, dgram_stride_bytes, row))) return rc;
+        rc = fecbuf_device(b, b->hin.as<uint8_t>(), n_dgrams, row, data_out, data_stride_bytes, block0_out ? b->hb0.as<uint8_t>() : nullptr,
+                           max_frames, info_out, n_frames);
+        if (!rc && block0_out)
+            for (int s = 0; s < S; ++s)
+                if (n_frames[s])
+                    HIP_TRY(hipMemcpyAsync(block0_out + (size_t)s * max_frames * SDRHIP_BLOCK_BYTES, b->hb0.as<uint8_t>() + (size_t)s * max_frames * SDRHIP_BLOCK_BYTES,
+                                           n_frames[s] * SDRHIP_BLOCK_BYTES, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (rc) return rc;
+    *counts = reinterpret_cast<const int *>(b->small.as<uint8_t>() + counts_offset(S));
+    return SDRHIP_OK;
+}
+} // namespace sdrhip
 
 extern "C" int sdrhip_fecbuf_stats(sdrhip_fecbuf *b, int stream, int *cur_nb_blocks, int *cur_nb_recovery, int *min_nb_blocks, int *max_nb_recovery,
                                    uint8_t current_meta[24], uint8_t output_meta[24])

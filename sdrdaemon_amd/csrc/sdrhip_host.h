@@ -83,8 +83,20 @@ struct InterpGather { // InterpArgs::gmap / grx / grest / gframes
     int frames;
 };
 bool interpolate_gather_ok(const sdrhip_ctx *c, int log2interp); // K5w serves this ratio (interpolate4 .. 64, interp_path != valu)
+struct InterpCount { // InterpArgs::count / count_stride / count_unit: per-stream input counts on the device (ragged launch)
+    const int *count;
+    int stride, unit;
+};
+// count (optional): stream s takes count[s * stride] * unit inputs, at most n_in (the grid is planned for n_in, the largest)
 int interpolate_device(sdrhip_interpolators *p, int log2interp, const int16_t *in, size_t n_in, size_t in_stride, int16_t *out,
-                       size_t out_stride, size_t *n_out, const InterpGather *gather = nullptr);
+                       size_t out_stride, size_t *n_out, const InterpGather *gather = nullptr, const InterpCount *count = nullptr);
+// FEC buffer bank (sdrhip_fecbuf.cpp) for the Tx pipe fed datagrams: the datagram arguments of sdrhip_fecbuf_write_and_read, then
+// the bank's call with data_out on the device and dgrams / block0_out in `mem` memory (host: staged; block0_out downloaded on the
+// context's stream, not synchronised); *counts (device) = the per-stream counts [S][FB_COUNTS] the classify pass left (FB_K: frames)
+int fecbuf_check_dgrams(const sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes, int mem, const char *who);
+int fecbuf_collect(sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes, int mem, uint8_t *data_out,
+                   size_t data_stride_bytes, uint8_t *block0_out, size_t max_frames, sdrhip_fecbuf_frame *info_out, size_t *n_frames,
+                   const int **counts);
 // frames/recovery on the device; recovery slots may be interleaved with the frames
 // (rec_frame_bytes = stride between the recovery areas of consecutive frames)
 // frame_list_dev (optional, device): groups of GF_FRAMES_PER_GROUP frame indices (-1 = none), ngroups of them

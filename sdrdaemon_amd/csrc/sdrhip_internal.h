@@ -206,12 +206,20 @@ struct InterpArgs {
     const unsigned *gmap;
     const uint8_t *grx, *grest;
     int gframes;
+    // Ragged launches (the Tx pipe fed datagrams; launch_interpolate*_ragged): stream s takes count[s * count_stride] *
+    // count_unit inputs, read on the device where the FEC buffer bank's classify pass left the count; n_in / nseg are the
+    // largest stream's (the grid).  NULL: every stream takes n_in.
+    const int *count;
+    int count_stride, count_unit;
 };
 hipError_t launch_interpolate(int log2interp, const InterpArgs &a, hipStream_t stream);
 void plan_interpolate(int log2interp, size_t n_in, int nstreams, int *nsub_per_seg, int *nseg);
 // K5w (interp_wave.h): wave-private pipelines (workgroups of one or four independent waves), blocks of 128 inputs; log2interp 2..6
 void plan_interpolate_wave(int log2interp, size_t n_in, int nstreams, int n_cu, size_t seg_override, int *nsub_per_seg, int *nseg);
 hipError_t launch_interpolate_wave(int log2interp, const InterpArgs &a, hipStream_t stream);
+// ... with per-stream input counts (InterpArgs::count), planned like the uniform launch of the largest
+hipError_t launch_interpolate_ragged(int log2interp, const InterpArgs &a, hipStream_t stream);
+hipError_t launch_interpolate_wave_ragged(int log2interp, const InterpArgs &a, hipStream_t stream);
 
 // frames are processed in groups that share one coefficient matrix (one frame per half-wave)
 constexpr int GF_FRAMES_PER_GROUP = 2;

@@ -63,12 +63,13 @@ namespace sdrhip {
 bool interpolate_gather_ok(const sdrhip_ctx *c, int log2interp) { return c->opt.interp_wave && log2interp >= 2; }
 
 int interpolate_device(sdrhip_interpolators *p, int log2interp, const int16_t *in, size_t n_in, size_t in_stride, int16_t *out,
-                       size_t out_stride, size_t *n_out, const InterpGather *gather)
+                       size_t out_stride, size_t *n_out, const InterpGather *gather, const InterpCount *count)
 {
     sdrhip_ctx *c = p->ctx;
     if (n_out) *n_out = n_in << log2interp;
     if (n_in == 0) return SDRHIP_OK;
     if (gather && !interpolate_gather_ok(p->ctx, log2interp)) return fail(SDRHIP_EINVAL, "internal: gathered input needs the wave interpolator");
+    if (gather && count) return fail(SDRHIP_EINVAL, "internal: no ragged gather");
     if (log2interp == 0) { // Upsampler::process m_interp == 0: samples_out = samples_in (Upsampler.cpp:54-57)
         HIP_TRY(hipMemcpy2DAsync(out, out_stride * 4, in, in_stride * 4, n_in * 4, p->nstreams, hipMemcpyDeviceToDevice, c->stream));
         return SDRHIP_OK;
@@ -79,6 +80,7 @@ int interpolate_device(sdrhip_interpolators *p, int log2interp, const int16_t *i
     a.state_cur = p->state[p->cur]; a.state_next = p->state[p->cur ^ 1];
     a.nstreams = p->nstreams;
     if (gather) { a.gmap = gather->map; a.grx = gather->rx; a.grest = gather->restored; a.gframes = gather->frames; }
+    if (count) { a.count = count->count; a.count_stride = count->stride; a.count_unit = count->unit; }
     // SDRHIP_INTERP_PATH = wave (K5w, default) | valu (K5); SDRHIP_INTERP_SPAN = segment length in inputs (tests)
     const bool use_wave = c->opt.interp_wave && log2interp >= 2;
     if (use_wave) plan_interpolate_wave(log2interp, n_in, p->nstreams, c->n_cu, c->opt.interp_span, &a.nsub_per_seg, &a.nseg);
@@ -86,7 +88,8 @@ int interpolate_device(sdrhip_interpolators *p, int log2interp, const int16_t *i
     hipError_t e;
     {
         KTimer kt(c, SDRHIP_K_INTERPOLATE);
-        e = use_wave ? launch_interpolate_wave(log2interp, a, c->stream) : launch_interpolate(log2interp, a, c->stream);
+        if (count) e = use_wave ? launch_interpolate_wave_ragged(log2interp, a, c->stream) : launch_interpolate_ragged(log2interp, a, c->stream);
+        else e = use_wave ? launch_interpolate_wave(log2interp, a, c->stream) : launch_interpolate(log2interp, a, c->stream);
     }
     if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "interpolate launch: %s", hipGetErrorString(e));
     p->cur ^= 1;
@@ -870,6 +873,9 @@ struct sdrhip_tx {
     };
     std::vector<ABatch> abatch;
     size_t a_head = 0, a_tail = 0;
+    // ---- datagram entry (sdrhip_tx_process_datagrams): one SDRdaemonFECBuffer per stream, created on first use; the frames it
+    // releases go to payload[0] (or straight to the caller's device iq_out when log2interp = 0), the interpolator reads them there
+    sdrhip_fecbuf *fb = nullptr;
 };
 
 extern "C" int sdrhip_tx_create(sdrhip_ctx *ctx, int nstreams, int log2interp, sdrhip_tx **out)
@@ -904,6 +910,7 @@ extern "C" void sdrhip_tx_destroy(sdrhip_tx *tx)
     (void)hipSetDevice(tx->ctx->device);
     if (tx->ctx->stream2) (void)hipStreamSynchronize(tx->ctx->stream2); // (a decode of the pipelined mode may still run there)
     sdrhip_interpolators_destroy(tx->itp); // (synchronises the first stream)
+    sdrhip_fecbuf_destroy(tx->fb);
     tx->rxbuf.release(); tx->payload[0].release(); tx->payload[1].release(); tx->outbuf.release();
     tx->srcmap.release(); tx->restored.release();
     tx->plan_own.release(); tx->idx_own.release(); tx->pin_own.release();
@@ -1257,5 +1264,84 @@ extern "C" int sdrhip_tx_collect(sdrhip_tx *tx, int16_t *iq_out, size_t out_stri
     if (n_frames) *n_frames = b.nframes;
     b.state = 0;
     ++tx->a_head;
+    return SDRHIP_OK;
+}
+
+// --------------------------------------------------------------------------- Tx pipe fed datagrams
+// UDPSourceFEC::read -> SDRdaemonFECBuffer::writeAndRead -> Upsampler::process for every stream (sdrdaemontx.cpp:449-498,
+// UDPSourceFEC.cpp:52-78): the FEC buffer bank collects and decodes into payload[0] ([stream][pitch] samples, every stream 16-byte
+// aligned: one frame is 64 516 bytes = 4 mod 16, and K5w's paired loads want aligned streams), then ONE ragged interpolator launch
+// takes each stream's own count from where the bank's classify pass left it.  The grid is planned from the largest count, which
+// the host holds after the bank's one read-back.
+namespace {
+int tx_collector(sdrhip_tx *tx)
+{
+    return tx->fb ? SDRHIP_OK : sdrhip_fecbuf_create(tx->ctx, tx->nstreams, &tx->fb);
+}
+} // namespace
+
+extern "C" int sdrhip_tx_collector(sdrhip_tx *tx, sdrhip_fecbuf **out)
+{
+    if (!tx || !out) return fail(SDRHIP_EINVAL, "tx_collector: NULL argument");
+    sdrhip::CtxLock lock_(tx->ctx);
+    int rc = tx_collector(tx);
+    if (rc) return rc;
+    *out = tx->fb;
+    return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_tx_process_datagrams(sdrhip_tx *tx, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes,
+                                           int16_t *iq_out, size_t out_stride, size_t max_frames, uint8_t *block0_out,
+                                           sdrhip_fecbuf_frame *info_out, size_t *n_frames, int mem)
+{
+    if (!tx) return fail(SDRHIP_EINVAL, "tx is NULL");
+    sdrhip::CtxLock lock_(tx->ctx);
+    if (!n_dgrams || !n_frames) return fail(SDRHIP_EINVAL, "tx_process_datagrams: NULL n_dgrams / n_frames");
+    if (mem != SDRHIP_MEM_HOST && mem != SDRHIP_MEM_DEVICE) return fail(SDRHIP_EINVAL, "mem must be SDRHIP_MEM_HOST or SDRHIP_MEM_DEVICE");
+    if (tx->pipelined) return fail(SDRHIP_EINVAL, "tx_process_datagrams: the handle is in pipelined mode");
+    for (const auto &b : tx->abatch)
+        if (b.state != 0) return fail(SDRHIP_EINVAL, "tx_process_datagrams: asynchronous batches are in flight: collect them first");
+    sdrhip_ctx *c = tx->ctx;
+    const int S = tx->nstreams, L = tx->log2interp;
+    if (max_frames > 0x3fffffffu) return fail(SDRHIP_EINVAL, "tx_process_datagrams: max_frames too large");
+    if (max_frames > 0 && (!iq_out || !info_out)) return fail(SDRHIP_EINVAL, "tx_process_datagrams: NULL iq_out / info_out");
+    const size_t per = max_frames * SDRHIP_SAMPLES_PER_FRAME, n_res_max = per << L;
+    if (S == 1) out_stride = (n_res_max + 3) & ~(size_t)3;
+    if (out_stride < n_res_max) return fail(SDRHIP_EINVAL, "tx_process_datagrams: out_stride below max_frames x 16129 << log2interp");
+    if (mem == SDRHIP_MEM_DEVICE && max_frames > 0 && (!aligned16(iq_out) || (out_stride & 3) || (reinterpret_cast<uintptr_t>(block0_out) & 3u)))
+        return fail(SDRHIP_EALIGN, "tx_process_datagrams: device iq_out must be 16-byte aligned, out_stride a multiple of 4 samples, block0_out 4-byte aligned");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = tx_collector(tx))) return rc;
+    if ((rc = fecbuf_check_dgrams(tx->fb, dgrams, n_dgrams, dgram_stride_bytes, mem, "tx_process_datagrams"))) return rc;
+    // where the collector writes getSlotData: the caller's device iq_out (Upsampler's m_interp == 0 pass-through, Upsampler.cpp:54-57)
+    // or payload[0]; host memory: outbuf / payload[0], downloaded below
+    const size_t pitch = (per + 3) & ~(size_t)3, n_res_pitch = (n_res_max + 3) & ~(size_t)3;
+    int16_t *dout = iq_out;
+    size_t dos = out_stride;
+    if (max_frames > 0 && mem == SDRHIP_MEM_HOST) {
+        if ((rc = tx->outbuf.reserve((size_t)S * n_res_pitch * 4 + 16))) return rc;
+        dout = tx->outbuf.as<int16_t>(); dos = n_res_pitch;
+    }
+    if (max_frames > 0 && L > 0 && (rc = tx->payload[0].reserve((size_t)S * pitch * 4 + 16))) return rc;
+    uint8_t *data = L == 0 ? reinterpret_cast<uint8_t *>(dout) : tx->payload[0].as<uint8_t>();
+    const size_t data_stride = L == 0 ? dos * 4 : pitch * 4;
+    const int *counts = nullptr;
+    if ((rc = fecbuf_collect(tx->fb, dgrams, n_dgrams, dgram_stride_bytes, mem, max_frames ? data : nullptr, data_stride, block0_out, max_frames,
+                             info_out, n_frames, &counts)))
+        return rc; // (SDRHIP_EINVAL for want of room: nothing consumed, the interpolator has not run)
+    size_t kmax = 0;
+    for (int s = 0; s < S; ++s) kmax = n_frames[s] > kmax ? n_frames[s] : kmax;
+    const size_t n_max = kmax * SDRHIP_SAMPLES_PER_FRAME;
+    if (L > 0 && kmax > 0) {
+        // (the collector's state has moved on: from here a failure loses the call's frames, it is never replayed)
+        const InterpCount cnt = {counts + FB_K, FB_COUNTS, (int)SDRHIP_SAMPLES_PER_FRAME};
+        if ((rc = interpolate_device(tx->itp, L, tx->payload[0].as<int16_t>(), n_max, pitch, dout, dos, nullptr, nullptr, &cnt))) return rc;
+    }
+    if (mem == SDRHIP_MEM_HOST) {
+        if (kmax > 0)
+            HIP_TRY(hipMemcpy2DAsync(iq_out, out_stride * 4, dout, dos * 4, (n_max << L) * 4, (size_t)S, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
     return SDRHIP_OK;
 }

@@ -763,6 +763,47 @@ class TxPipe:
         check(self.ctx.lib.sdrhip_tx_flush(self.h, _ptr(out), pad, C.byref(n_out), MEM_DEVICE if device is not None else MEM_HOST))
         return out[:, :n_out.value]
 
+    # ---- datagram entry (sdrhip_tx_process_datagrams)
+    def process_datagrams(self, dgrams_per_stream, max_frames=None):
+        """one (n_s, 512) uint8 array of raw datagrams per stream -- numpy (host memory) or torch device tensors, as
+        FECBufferBank.write_and_read -- through the handle's collector and interpolators; -> per stream (iq (n, 2) int16 with
+        n = frames * 16129 << log2interp, block0 (frames, 508) uint8, records)"""
+        S = self.nstreams
+        if len(dgrams_per_stream) != S:
+            raise ValueError("one datagram array per stream")
+        buf, counts, is_t = _datagram_batch(dgrams_per_stream)
+        if max_frames is None:
+            max_frames = max(counts + [0])  # (a call releases at most one frame per datagram)
+        F = max(max_frames, 1)
+        n_cap = (F * SAMPLES_PER_FRAME) << self.log2interp
+        pad = (n_cap + 3) & ~3
+        if is_t:
+            out = torch.empty((S, pad, 2), dtype=torch.int16, device=buf.device)
+            b0 = torch.empty((S, F, BLOCK_BYTES), dtype=torch.uint8, device=buf.device)
+        else:
+            out = np.empty((S, pad, 2), np.int16)
+            b0 = np.empty((S, F, BLOCK_BYTES), np.uint8)
+        info = (FECBufferFrame * (S * F))()
+        nd = (C.c_size_t * S)(*counts)
+        nf = (C.c_size_t * S)()
+        rc = self.ctx.lib.sdrhip_tx_process_datagrams(self.h, _ptr(buf), nd, buf.shape[1] * UDPSIZE, _ptr(out), pad, max_frames, _ptr(b0),
+                                                      info, nf, MEM_DEVICE if is_t else MEM_HOST)
+        self.last_n_frames = [int(x) for x in nf]
+        check(rc)
+        res = []
+        for s in range(S):
+            k = int(nf[s])
+            recs = [dict(frame_index=info[s * F + j].frame_index, block_count=info[s * F + j].block_count,
+                         recovery_count=info[s * F + j].recovery_count, flags=info[s * F + j].flags) for j in range(k)]
+            res.append((out[s, :(k * SAMPLES_PER_FRAME) << self.log2interp], b0[s, :k], recs))
+        return res
+
+    def collector_stats(self, stream):
+        """the statistics of one stream's collector (sdrhip_tx_collector + sdrhip_fecbuf_stats): the dict of FECBufferBank.stats"""
+        h = C.c_void_p()
+        check(self.ctx.lib.sdrhip_tx_collector(self.h, C.byref(h)))
+        return _fecbuf_stats(self.ctx, h, stream)
+
     def close(self):
         if self.h:
             self.ctx.lib.sdrhip_tx_destroy(self.h)
@@ -807,20 +848,8 @@ class FECBufferBank:
         S = self.nstreams
         if len(dgrams_per_stream) != S:
             raise ValueError("one datagram array per stream")
-        is_t = any(_is_torch(d) for d in dgrams_per_stream)
-        counts = [int(d.shape[0]) for d in dgrams_per_stream]
+        buf, counts, is_t = _datagram_batch(dgrams_per_stream)
         nmax = max(counts + [0])
-        if is_t:
-            dev = next(d.device for d in dgrams_per_stream if _is_torch(d))
-            buf = torch.zeros((S, max(nmax, 1), UDPSIZE), dtype=torch.uint8, device=dev)
-            for s, d in enumerate(dgrams_per_stream):
-                if counts[s]:
-                    buf[s, :counts[s]] = d.reshape(counts[s], UDPSIZE)
-        else:
-            buf = np.zeros((S, max(nmax, 1), UDPSIZE), np.uint8)
-            for s, d in enumerate(dgrams_per_stream):
-                if counts[s]:
-                    buf[s, :counts[s]] = np.asarray(d, np.uint8).reshape(counts[s], UDPSIZE)
         if max_frames is None:
             max_frames = nmax  # (a call releases at most one frame per datagram)
         F = max(max_frames, 1)
@@ -849,8 +878,33 @@ class FECBufferBank:
     def stats(self, stream):
         """getCurNbBlocks, getCurNbRecovery, getMinNbBlocks, getMaxNbRecovery (these two reset when read), getCurrentMeta,
         getOutputMeta (24 bytes: the 20-byte MetaDataFEC, zero padded) of one stream, as a dict"""
-        v = [C.c_int() for _ in range(4)]
-        cm, om = (C.c_uint8 * 24)(), (C.c_uint8 * 24)()
-        check(self.ctx.lib.sdrhip_fecbuf_stats(self.h, stream, *[C.byref(x) for x in v], cm, om))
-        return dict(cur_nb_blocks=v[0].value, cur_nb_recovery=v[1].value, min_nb_blocks=v[2].value, max_nb_recovery=v[3].value,
-                    current_meta=bytes(cm), output_meta=bytes(om))
+        return _fecbuf_stats(self.ctx, self.h, stream)
+
+
+def _datagram_batch(dgrams_per_stream):
+    """one (n_s, 512) uint8 array per stream -> (S, max n_s, 512) batch (torch on the device when any input is a torch tensor,
+    else numpy), the counts, is_torch"""
+    S = len(dgrams_per_stream)
+    is_t = any(_is_torch(d) for d in dgrams_per_stream)
+    counts = [int(d.shape[0]) for d in dgrams_per_stream]
+    nmax = max(counts + [0])
+    if is_t:
+        dev = next(d.device for d in dgrams_per_stream if _is_torch(d))
+        buf = torch.zeros((S, max(nmax, 1), UDPSIZE), dtype=torch.uint8, device=dev)
+        for s, d in enumerate(dgrams_per_stream):
+            if counts[s]:
+                buf[s, :counts[s]] = d.reshape(counts[s], UDPSIZE)
+    else:
+        buf = np.zeros((S, max(nmax, 1), UDPSIZE), np.uint8)
+        for s, d in enumerate(dgrams_per_stream):
+            if counts[s]:
+                buf[s, :counts[s]] = np.asarray(d, np.uint8).reshape(counts[s], UDPSIZE)
+    return buf, counts, is_t
+
+
+def _fecbuf_stats(ctx, h, stream):
+    v = [C.c_int() for _ in range(4)]
+    cm, om = (C.c_uint8 * 24)(), (C.c_uint8 * 24)()
+    check(ctx.lib.sdrhip_fecbuf_stats(h, stream, *[C.byref(x) for x in v], cm, om))
+    return dict(cur_nb_blocks=v[0].value, cur_nb_recovery=v[1].value, min_nb_blocks=v[2].value, max_nb_recovery=v[3].value,
+                current_meta=bytes(cm), output_meta=bytes(om))
