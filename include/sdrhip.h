@@ -95,9 +95,14 @@ int sdrhip_ctx_synchronize(sdrhip_ctx *ctx);
  * and stays a hole; by default the batched decoder delivers every restored block (a superset), with dec_strict = 1 exactly the
  * reference's frames, holes included. */
 int sdrhip_ctx_set_option(sdrhip_ctx *ctx, const char *key, const char *value);
-/* Event counters of the context, kept on the device (reading one synchronises the context's stream).  Keys:
+/* Event counters of the context.  Keys:
  * "dec_rows_exceeded" = frames, since the context was created, that the batched decoder (sdrhip_fec_decode_frames,
- * sdrhip_tx_process) left unrepaired because they carried more recovery blocks than the dec_max_rows option allows. */
+ * sdrhip_tx_process) left unrepaired because they carried more recovery blocks than the dec_max_rows option allows (kept on the
+ * device: reading it synchronises the context's stream);
+ * "h2d_bytes" / "d2h_bytes" = bytes that the context's entry points have copied from host to device / device to host since the
+ * context was created (staging copies of host-memory calls, including the kernels' direct reads of pinned staging memory for
+ * small calls; not the constant tables of sdrhip_ctx_create).  Counted on the host when the copy is enqueued: reading them does
+ * not synchronise. */
 int sdrhip_ctx_get_counter(sdrhip_ctx *ctx, const char *key, uint64_t *value);
 /* Average duration in milliseconds of the kernels launched between timing_begin and
  * timing_end on the context's stream, measured with hipEvents on that stream (what
@@ -113,6 +118,7 @@ int sdrhip_ctx_timing_end(sdrhip_ctx *ctx, float *elapsed_ms);
 #define SDRHIP_K_INTERPOLATE 1 /* half-band interpolator cascade kernel */
 #define SDRHIP_K_FEC_ENCODE 2  /* GF(256) matrix apply, encoder rows */
 #define SDRHIP_K_FEC_DECODE 3  /* GF(256) matrix apply, decode matrices */
+#define SDRHIP_K_CONVERT 4     /* 8-bit IQ widening pass of the Rx pipe (sdrhip_rx_set_input_format) */
 int sdrhip_ctx_kernel_timing(sdrhip_ctx *ctx, int enable);
 int sdrhip_ctx_kernel_timing_read(sdrhip_ctx *ctx, int kernel_class, double *total_ms, unsigned *launches);
 
@@ -223,6 +229,15 @@ int sdrhip_testsource_get(const sdrhip_testsource *ts, int stream, uint32_t *sam
 /* the next n samples of every stream (stream s at iq_out + 2*s*out_stride), phase continuous across calls */
 int sdrhip_testsource_read(sdrhip_testsource *ts, int16_t *iq_out, size_t n, size_t out_stride, int mem);
 
+/* ---------------------------------------------------------- IQ sample formats -- */
+/* What the data entries of an Rx / Tx pipe take or give per IQ sample (sdrhip_rx_set_input_format, sdrhip_tx_set_output_format).
+ * The pointer parameters keep their declared types: with an 8-bit format they point at 2-byte samples and the caller casts.
+ * Sample counts and strides stay in samples. */
+#define SDRHIP_IQ_S16 0 /* IQSample {int16 re, int16 im} (SDRDaemon.h:52-70): every entry's format by default */
+#define SDRHIP_IQ_U8 1  /* RTL-SDR: {uint8 re, uint8 im} offset binary, widened to IQSample(b - 128) (RtlSdrSource.cpp:542-553) */
+#define SDRHIP_IQ_S8 2  /* HackRF: {int8 re, int8 im}; in: IQSample(b) (HackRFSource.cpp:661-674), out: (int8)(v >> 8)
+                         * of each component (HackRFSink.cpp:671-672) */
+
 /* ------------------------------------------------------------ fused Rx pipe -- */
 /* Bank of Rx chains: Downsampler::process (Downsampler.cpp:74-162) -> UDPSinkFEC::write
  * framing (UDPSinkFEC.cpp:79-191) -> encode section of transmitUDP (:228-256), i.e. what
@@ -274,6 +289,16 @@ size_t sdrhip_rx_max_frames(const sdrhip_rx *rx, size_t n_in);
  * headline bank against 0.260-0.276 in the default, immediate mode); a pipelined pipe also keeps the stream-order arrangement
  * (context option "rx_direct" applies to immediate pipes). */
 int sdrhip_rx_set_pipelined(sdrhip_rx *rx, int on);
+/* Input format of every later sdrhip_rx_process (host and device memory, immediate and pipelined) and sdrhip_rx_submit:
+ * SDRHIP_IQ_S16 (the default), SDRHIP_IQ_U8 or SDRHIP_IQ_S8.  The RTL-SDR / HackRF sources widen their bytes on a host core
+ * (RtlSdrSource.cpp:542-553, HackRFSource.cpp:661-674) and report get_sample_bits() = 8, which sdrdaemonrx hands to
+ * Downsampler::process (sdrdaemonrx.cpp:619-643); here the bytes cross the host link as they are (2 bytes per sample instead of 4)
+ * and a gfx950 kernel widens them into the decimator's int16 input on the device.  sample_bits stays the caller's choice in
+ * sdrhip_rx_config (an RTL-SDR caller configures 8): the format does not imply a value.  8-bit device input: 16-byte aligned, the
+ * stream stride a multiple of 8 samples (else SDRHIP_EALIGN); the caller's memory is only read.  Refused with SDRHIP_EINVAL,
+ * nothing changed: an unknown format, asynchronous batches being filled or in flight, a pipelined pipe with undelivered frames
+ * (sdrhip_rx_flush first). */
+int sdrhip_rx_set_input_format(sdrhip_rx *rx, int fmt);
 int sdrhip_rx_flush(sdrhip_rx *rx, uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem);
 /* the decimator launch of the last sdrhip_rx_process call (see sdrhip_decimators_last_plan) */
 int sdrhip_rx_last_plan(const sdrhip_rx *rx, sdrhip_decim_plan *out);
@@ -333,6 +358,14 @@ int sdrhip_tx_process(sdrhip_tx *tx, const uint8_t *rx, const uint8_t *indices, 
  * sdrhip_tx_process / sdrhip_tx_flush on this handle has returned.  (Context option "tx_overlap" = 0: the same one-call-late
  * delivery with both kernels on the first stream, the A / B partner.) */
 int sdrhip_tx_set_pipelined(sdrhip_tx *tx, int on);
+/* Output format of every later sdrhip_tx_process, sdrhip_tx_flush, sdrhip_tx_collect and sdrhip_tx_process_datagrams:
+ * SDRHIP_IQ_S16 (the default) or SDRHIP_IQ_S8, the HackRF sink's bytes (HackRFSink.cpp:671-672: buf[2i] = real() >> 8,
+ * buf[2i + 1] = imag() >> 8).  The interpolator's last stage narrows and stores 2 bytes per sample; host outputs download 2 bytes
+ * per sample; block0_out is unchanged.  8-bit device output: 16-byte aligned, the stream stride a multiple of 8 samples (else
+ * SDRHIP_EALIGN).  A batch takes the format in force when it is handed in (sdrhip_tx_process, sdrhip_tx_submit).  Refused with
+ * SDRHIP_EINVAL, nothing changed: an unknown format, SDRHIP_IQ_U8 (no Tx radio takes it), asynchronous batches in flight, a
+ * pipelined batch waiting (sdrhip_tx_flush first). */
+int sdrhip_tx_set_output_format(sdrhip_tx *tx, int fmt);
 int sdrhip_tx_flush(sdrhip_tx *tx, int16_t *iq_out, size_t out_stride, size_t *n_out, int mem);
 size_t sdrhip_tx_pending_samples(const sdrhip_tx *tx);
 /* Asynchronous host-pointer entry, the Tx twin of sdrhip_rx_submit / sdrhip_rx_collect.  sdrdaemontx receives on a reader thread

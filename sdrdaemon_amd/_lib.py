@@ -21,6 +21,7 @@ LIB_PATH = os.environ.get("SDRHIP_LIB_PATH") or os.path.join(HERE, "libsdrhip.so
 MEM_HOST, MEM_DEVICE = 0, 1
 FC_INF, FC_SUP, FC_CEN = 0, 1, 2
 HB_EO1, HB_DB = 0, 1
+IQ_S16, IQ_U8, IQ_S8 = 0, 1, 2
 UDPSIZE, NB_ORIGINAL, BLOCK_BYTES, SAMPLES_PER_BLOCK, SAMPLES_PER_FRAME = 512, 128, 508, 127, 16129
 
 EXPORTS = [
@@ -33,6 +34,7 @@ EXPORTS = [
     "sdrhip_testsource_create", "sdrhip_testsource_destroy", "sdrhip_testsource_configure", "sdrhip_testsource_get", "sdrhip_testsource_read",
     "sdrhip_fecbuf_create", "sdrhip_fecbuf_destroy", "sdrhip_fecbuf_reset", "sdrhip_fecbuf_write_and_read", "sdrhip_fecbuf_stats",
     "sdrhip_tx_process_datagrams", "sdrhip_tx_collector",
+    "sdrhip_rx_set_input_format", "sdrhip_tx_set_output_format",
 ]
 
 
@@ -131,6 +133,8 @@ def load():
     lib.sdrhip_fecbuf_stats.argtypes = [vp, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i), vp, vp]
     lib.sdrhip_tx_process_datagrams.argtypes = [vp, vp, C.POINTER(sz), sz, vp, sz, sz, vp, vp, C.POINTER(sz), i]
     lib.sdrhip_tx_collector.argtypes = [vp, C.POINTER(vp)]
+    lib.sdrhip_rx_set_input_format.argtypes = [vp, i]
+    lib.sdrhip_tx_set_output_format.argtypes = [vp, i]
     lib.sdrhip_testsource_create.argtypes = [vp, i, C.POINTER(vp)]
     lib.sdrhip_testsource_destroy.argtypes = [vp]
     lib.sdrhip_testsource_destroy.restype = None

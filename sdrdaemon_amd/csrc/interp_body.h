@@ -44,6 +44,8 @@ template <int NS_> struct IGeo {
 // the geometry of the ragged instantiation (interp_ragged_kernel): the same, as a type of its own, so that every helper templated on
 // it is instantiated apart from the uniform kernel's -- sharing them changed how hipcc compiled the uniform kernel
 template <int NS_> struct IGeoRagged : IGeo<NS_> {};
+// ... and of the 8-bit output instantiations (interp_s8_kernel, interp_s8_count_kernel), for the same reason
+template <int NS_, bool RAGGED> struct IGeoS8 : IGeo<NS_> {};
 
 struct IOut {
     unsigned *out;
@@ -81,8 +83,9 @@ template <class G, int S> __device__ __forceinline__ void istage(int *lds, int t
     *reinterpret_cast<int4_t *>(nx + 4) = (int4_t){o[4], o[5], o[6], o[7]};
 }
 
-// the last stage: both components per thread, int16 packing, 2 x 16-byte stores
-template <class G, int S> __device__ __forceinline__ void istage_last(int *lds, int tid, int in_off, int valid, const IOut &oc)
+// the last stage: both components per thread, int16 packing, 2 x 16-byte stores (OF = IQF_S8: byte 1 of each component, the
+// HackRF sink's v >> 8 (HackRFSink.cpp:671-672), one 16-byte store; oc.out then points at 2-byte samples)
+template <class G, int S, int OF = IQF_S16> __device__ __forceinline__ void istage_last(int *lds, int tid, int in_off, int valid, const IOut &oc)
 {
     constexpr int O = stage_order(S), K = O / 4, S2 = O / 2, R = 4;
     const int m0 = tid * R;
@@ -105,6 +108,30 @@ template <class G, int S> __device__ __forceinline__ void istage_last(int *lds, 
             o[comp][2 * r] = w[r + K];
             o[comp][2 * r + 1] = acc >> 13;
         }
+    }
+    if constexpr (OF == IQF_S8) {
+        unsigned pk[R]; // (I hi8, Q hi8) of outputs 2r, 2r + 1
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const unsigned e = __builtin_amdgcn_perm((unsigned)o[1][2 * r], (unsigned)o[0][2 * r], 0x05010501u);
+            const unsigned d = __builtin_amdgcn_perm((unsigned)o[1][2 * r + 1], (unsigned)o[0][2 * r + 1], 0x05010501u);
+            pk[r] = __builtin_amdgcn_perm(d, e, 0x05040100u);
+        }
+        size_t idx = oc.out_pos + 2 * (size_t)m0; // chain output index (even: input m0 + r gives outputs idx + 2r, idx + 2r + 1 = dword r)
+        if (oc.stuff64) idx = (idx >> 5) * 64 + (idx & 31);
+        unsigned *dst = oc.out + (idx >> 1); // (2-byte samples: dword r holds the pair of outputs of input m0 + r)
+        if (m0 + R <= valid) {
+            *reinterpret_cast<uint4_t *>(dst) = (uint4_t){pk[0], pk[1], pk[2], pk[3]};
+            if (oc.stuff64) *reinterpret_cast<uint4_t *>(dst + 16) = (uint4_t){0u, 0u, 0u, 0u};
+        } else {
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                if (m0 + r < valid) {
+                    dst[r] = pk[r];
+                    if (oc.stuff64) dst[16 + r] = 0u;
+                }
+        }
+        return;
     }
     unsigned pk[2 * R];
 #pragma unroll
@@ -141,10 +168,10 @@ template <class G, int S> __device__ __forceinline__ void slide(int *lds, int ti
 }
 
 // depth-first walk: stage S consumes `valid` inputs at in_off of its buffer
-template <class G, int S> __device__ __forceinline__ void descend(int *lds, int tid, int in_off, int valid, IOut &oc)
+template <class G, int S, int OF = IQF_S16> __device__ __forceinline__ void descend(int *lds, int tid, int in_off, int valid, IOut &oc)
 {
     if constexpr (S == G::NS - 1) {
-        istage_last<G, S>(lds, tid, in_off, valid, oc);
+        istage_last<G, S, OF>(lds, tid, in_off, valid, oc);
         if (oc.store) oc.out_pos += 2 * (size_t)valid;
         __syncthreads();
     } else {
@@ -152,10 +179,10 @@ template <class G, int S> __device__ __forceinline__ void descend(int *lds, int 
         __syncthreads();
         const int n = 2 * valid;
         if constexpr (S + 1 == G::NS - 1) {
-            descend<G, S + 1>(lds, tid, 0, n, oc);
+            descend<G, S + 1, OF>(lds, tid, 0, n, oc);
         } else {
-            descend<G, S + 1>(lds, tid, 0, n < MC ? n : MC, oc);
-            if (n > MC) descend<G, S + 1>(lds, tid, MC, n - MC, oc);
+            descend<G, S + 1, OF>(lds, tid, 0, n < MC ? n : MC, oc);
+            if (n > MC) descend<G, S + 1, OF>(lds, tid, MC, n - MC, oc);
         }
         slide<G, S + 1>(lds, tid, n);
         __syncthreads();
@@ -175,11 +202,13 @@ template <class G, int S = 0> __device__ __forceinline__ void state_store(const 
 
 // L = log2 interpolation (6 = the reference's 5-stage + zero stuffing variant)
 // one segment (seg of a.nseg, a.nsub_per_seg macro-cycles each) of one stream; lds: IGeo<NS>::ldsDw dwords
-// (RAGGED: the same code, instantiated apart for interp_ragged_kernel, which has set a.n_in / a.nseg for the stream)
-template <int L, bool RAGGED = false> __device__ __forceinline__ void interp_segment(const InterpArgs &a, int seg, int stream, int *lds)
+// (RAGGED: the same code, instantiated apart for interp_ragged_kernel, which has set a.n_in / a.nseg for the stream; OF: the output
+// format, IQF_S16 or IQF_S8 -- a.out then points at 2-byte samples and a.out_stride counts them)
+template <int L, bool RAGGED = false, int OF = IQF_S16> __device__ __forceinline__ void interp_segment(const InterpArgs &a, int seg, int stream, int *lds)
 {
     constexpr int NS = (L == 6) ? 5 : L;
-    using G = typename std::conditional<RAGGED, IGeoRagged<NS>, IGeo<NS>>::type;
+    using G = typename std::conditional<OF == IQF_S8, IGeoS8<NS, RAGGED>,
+                                        typename std::conditional<RAGGED, IGeoRagged<NS>, IGeo<NS>>::type>::type;
     constexpr int CI = G::mc;
     static_assert(G::ldsDw * 4 <= 64 * 1024, "LDS budget");
 
@@ -194,7 +223,8 @@ template <int L, bool RAGGED = false> __device__ __forceinline__ void interp_seg
     state_load<G>(lds, tid, stc, seg != 0);
 
     IOut oc;
-    oc.out = reinterpret_cast<unsigned *>(a.out) + (size_t)stream * a.out_stride;
+    if constexpr (OF == IQF_S8) oc.out = reinterpret_cast<unsigned *>(reinterpret_cast<unsigned short *>(a.out) + (size_t)stream * a.out_stride);
+    else oc.out = reinterpret_cast<unsigned *>(a.out) + (size_t)stream * a.out_stride;
     oc.stuff64 = (L == 6);
     oc.out_pos = seg_start << NS;
 
@@ -227,7 +257,7 @@ template <int L, bool RAGGED = false> __device__ __forceinline__ void interp_seg
         }
         __syncthreads();
         oc.store = !warm;
-        descend<G, 0>(lds, tid, 0, cnt, oc);
+        descend<G, 0, OF>(lds, tid, 0, cnt, oc);
         slide<G, 0>(lds, tid, cnt);
         __syncthreads();
         if (!more) break;

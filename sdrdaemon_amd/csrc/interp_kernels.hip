@@ -89,6 +89,37 @@ template <int L, int WPW> __global__ __launch_bounds__(WNT * WPW) void interp_wa
     interp_wave_segment<L>(a, seg, blockIdx.y, lds[w]);
 }
 
+// 8-bit output (IQF_S8: the HackRF sink's bytes), uniform and per-stream counts.  (Kernel names without "ragged": that word names
+// the int16 ragged kernels.)
+template <int L, int WPW> __global__ __launch_bounds__(WNT * WPW) void interp_wave_s8_kernel(InterpArgs a)
+{
+    __shared__ __attribute__((aligned(16))) int lds[WPW][WGeo<(L == 6) ? 5 : L>::ldsDw];
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int seg = (int)blockIdx.x * WPW + w;
+    if (seg >= a.nseg) return;
+    interp_wave_segment<L, false, IQF_S8>(a, seg, blockIdx.y, lds[w]);
+}
+template <int L, int WPW> __global__ __launch_bounds__(WNT * WPW) void interp_wave_s8_count_kernel(InterpArgs a)
+{
+    __shared__ __attribute__((aligned(16))) int lds[WPW][WGeo<(L == 6) ? 5 : L>::ldsDw];
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int seg = (int)blockIdx.x * WPW + w;
+    if (seg >= a.nseg) return;
+    if (!ragged_args(a, seg, (int)blockIdx.y, (size_t)a.nsub_per_seg * WB)) return;
+    interp_wave_segment<L, false, IQF_S8>(a, seg, blockIdx.y, lds[w]);
+}
+template <int L> __global__ __launch_bounds__(NT) void interp_s8_kernel(InterpArgs a)
+{
+    __shared__ __attribute__((aligned(16))) int lds[IGeo<(L == 6) ? 5 : L>::ldsDw];
+    interp_segment<L, false, IQF_S8>(a, blockIdx.x, blockIdx.y, lds);
+}
+template <int L> __global__ __launch_bounds__(NT) void interp_s8_count_kernel(InterpArgs a)
+{
+    __shared__ __attribute__((aligned(16))) int lds[IGeo<(L == 6) ? 5 : L>::ldsDw];
+    if (!ragged_args(a, (int)blockIdx.x, (int)blockIdx.y, (size_t)a.nsub_per_seg * IGeo<(L == 6) ? 5 : L>::mc)) return;
+    interp_segment<L, true, IQF_S8>(a, blockIdx.x, blockIdx.y, lds);
+}
+
 template <int L> hipError_t launch_w(const InterpArgs &a, hipStream_t stream)
 {
     constexpr int WPW = 4;
@@ -123,6 +154,28 @@ template <int L> hipError_t launch_w_ragged(const InterpArgs &a, hipStream_t str
 template <int L> hipError_t launch_l_ragged(const InterpArgs &a, hipStream_t stream)
 {
     hipLaunchKernelGGL((interp_ragged_kernel<L>), dim3(a.nseg, a.nstreams), dim3(NT), 0, stream, a);
+    return hipGetLastError();
+}
+
+// (8-bit output: the workgroup shapes of the int16 launches)
+template <int L> hipError_t launch_w_s8(const InterpArgs &a, hipStream_t stream)
+{
+    constexpr int WPW = 4;
+    const bool four = (size_t)a.nseg * (size_t)a.nstreams >= 4096;
+    if (a.count) {
+        if (four) hipLaunchKernelGGL((interp_wave_s8_count_kernel<L, WPW>), dim3((a.nseg + WPW - 1) / WPW, a.nstreams), dim3(WNT * WPW), 0, stream, a);
+        else hipLaunchKernelGGL((interp_wave_s8_count_kernel<L, 1>), dim3(a.nseg, a.nstreams), dim3(WNT), 0, stream, a);
+    } else if (four)
+        hipLaunchKernelGGL((interp_wave_s8_kernel<L, WPW>), dim3((a.nseg + WPW - 1) / WPW, a.nstreams), dim3(WNT * WPW), 0, stream, a);
+    else
+        hipLaunchKernelGGL((interp_wave_s8_kernel<L, 1>), dim3(a.nseg, a.nstreams), dim3(WNT), 0, stream, a);
+    return hipGetLastError();
+}
+
+template <int L> hipError_t launch_l_s8(const InterpArgs &a, hipStream_t stream)
+{
+    if (a.count) hipLaunchKernelGGL((interp_s8_count_kernel<L>), dim3(a.nseg, a.nstreams), dim3(NT), 0, stream, a);
+    else hipLaunchKernelGGL((interp_s8_kernel<L>), dim3(a.nseg, a.nstreams), dim3(NT), 0, stream, a);
     return hipGetLastError();
 }
 
@@ -205,6 +258,58 @@ hipError_t launch_interpolate_ragged(int log2interp, const InterpArgs &a, hipStr
     case 6: return launch_l_ragged<6>(a, stream);
     }
     return hipErrorInvalidValue;
+}
+
+// 8-bit output: no gathered input (the no-copy Tx mode stays on int16 output)
+hipError_t launch_interpolate_wave_s8(int log2interp, const InterpArgs &a, hipStream_t stream)
+{
+    if (a.gmap || a.count) return hipErrorInvalidValue;
+    switch (log2interp) {
+    case 2: return launch_w_s8<2>(a, stream);
+    case 3: return launch_w_s8<3>(a, stream);
+    case 4: return launch_w_s8<4>(a, stream);
+    case 5: return launch_w_s8<5>(a, stream);
+    case 6: return launch_w_s8<6>(a, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_interpolate_wave_ragged_s8(int log2interp, const InterpArgs &a, hipStream_t stream)
+{
+    if (!a.count || a.gmap) return hipErrorInvalidValue;
+    switch (log2interp) {
+    case 2: return launch_w_s8<2>(a, stream);
+    case 3: return launch_w_s8<3>(a, stream);
+    case 4: return launch_w_s8<4>(a, stream);
+    case 5: return launch_w_s8<5>(a, stream);
+    case 6: return launch_w_s8<6>(a, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+static hipError_t launch_l_s8_any(int log2interp, const InterpArgs &a, hipStream_t stream)
+{
+    switch (log2interp) {
+    case 1: return launch_l_s8<1>(a, stream);
+    case 2: return launch_l_s8<2>(a, stream);
+    case 3: return launch_l_s8<3>(a, stream);
+    case 4: return launch_l_s8<4>(a, stream);
+    case 5: return launch_l_s8<5>(a, stream);
+    case 6: return launch_l_s8<6>(a, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_interpolate_s8(int log2interp, const InterpArgs &a, hipStream_t stream)
+{
+    if (a.gmap || a.count) return hipErrorInvalidValue;
+    return launch_l_s8_any(log2interp, a, stream);
+}
+
+hipError_t launch_interpolate_ragged_s8(int log2interp, const InterpArgs &a, hipStream_t stream)
+{
+    if (!a.count || a.gmap) return hipErrorInvalidValue;
+    return launch_l_s8_any(log2interp, a, stream);
 }
 
 } // namespace sdrhip

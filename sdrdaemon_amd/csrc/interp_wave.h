@@ -11,6 +11,8 @@
 //    output instead of 16 adds + 16 multiply-adds (the raw samples are int16; every later stage sees 19-bit values);
 //  * the last stage multiplies by 8 x tap: (acc >> 13) & 0xffff is then the HIGH half of the accumulator, and one v_perm_b32 both
 //    shifts and packs I/Q (the truncation to int16 drops everything above bit 28 anyway);
+//  * 8-bit output (OF = IQF_S8, the HackRF sink's (int8)(v >> 8), HackRFSink.cpp:671-672): the same accumulators, byte 1 of the even
+//    and byte 3 of the odd outputs, three v_perm_b32 per output pair and ONE 16-byte store per lane instead of two;
 #ifndef SDRHIP_INTERP_WAVE_H
 #define SDRHIP_INTERP_WAVE_H
 #include "interp_body.h"
@@ -158,7 +160,7 @@ template <class G, int S, bool FULL> __device__ __forceinline__ void wstage(int 
 }
 
 // the last stage: both components per lane, taps x 8 (the int16 result is the accumulator's high half), 2 x 16-byte stores
-template <class G, int S, bool FULL> __device__ __forceinline__ void wstage_last(int *lds, int lane, int in_off, int valid, const IOut &oc)
+template <class G, int S, bool FULL, int OF = IQF_S16> __device__ __forceinline__ void wstage_last(int *lds, int lane, int in_off, int valid, const IOut &oc)
 {
     constexpr int O = stage_order(S), K = O / 4, S2 = O / 2, R = 4;
     const int m0 = lane * R;
@@ -182,6 +184,30 @@ template <class G, int S, bool FULL> __device__ __forceinline__ void wstage_last
             ev[comp][r] = w[r + K];
             od[comp][r] = acc; // (acc >> 13) & 0xffff == bits 16..31 of 8 * sum
         }
+    }
+    if constexpr (OF == IQF_S8) {
+        unsigned pk[R]; // outputs 2r, 2r + 1: (I, Q) = byte 1 of the even values, byte 3 of the odd accumulators
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const unsigned e = __builtin_amdgcn_perm((unsigned)ev[1][r], (unsigned)ev[0][r], 0x05010501u);
+            const unsigned d = __builtin_amdgcn_perm((unsigned)od[1][r], (unsigned)od[0][r], 0x07030703u);
+            pk[r] = __builtin_amdgcn_perm(d, e, 0x05040100u);
+        }
+        size_t idx = oc.out_pos + 2 * (size_t)m0; // chain output index
+        if (oc.stuff64) idx = (idx >> 5) * 64 + (idx & 31);
+        unsigned short *dst = reinterpret_cast<unsigned short *>(oc.out) + idx;
+        if (FULL || m0 + R <= valid) {
+            *reinterpret_cast<uint4_t *>(dst) = (uint4_t){pk[0], pk[1], pk[2], pk[3]};
+            if (oc.stuff64) *reinterpret_cast<uint4_t *>(dst + 32) = (uint4_t){0u, 0u, 0u, 0u};
+        } else {
+#pragma unroll
+            for (int q = 0; q < 2 * R; ++q)
+                if (m0 + q / 2 < valid) {
+                    dst[q] = (unsigned short)(pk[q / 2] >> (16 * (q & 1)));
+                    if (oc.stuff64) dst[32 + q] = 0;
+                }
+        }
+        return;
     }
     unsigned pk[2 * R];
 #pragma unroll
@@ -226,11 +252,11 @@ template <class G, int S> __device__ __forceinline__ void whist(int *lds, int la
 // FULL: a whole block with its stores (valid = 128 per stage invocation, 256 in the last stage): every guard is a compile-time
 // constant and the walk is straight-line code apart from the LDS-only history writes -- which is what lets hipcc count the
 // block's eight stores behind the prefetch load exactly (s_waitcnt vmcnt(8) instead of a drain of the stores, see the loop)
-template <class G, int S, bool FULL> __device__ __forceinline__ void wdescend(int *lds, int lane, int in_off, int valid_rt, IOut &oc)
+template <class G, int S, bool FULL, int OF = IQF_S16> __device__ __forceinline__ void wdescend(int *lds, int lane, int in_off, int valid_rt, IOut &oc)
 {
     const int valid = FULL ? (S == G::NS - 1 ? WCAP : WB) : valid_rt;
     if constexpr (S == G::NS - 1) {
-        wstage_last<G, S, FULL>(lds, lane, in_off, valid, oc);
+        wstage_last<G, S, FULL, OF>(lds, lane, in_off, valid, oc);
         if (FULL || oc.store) oc.out_pos += 2 * (size_t)valid;
     } else {
         int o[8];
@@ -239,13 +265,13 @@ template <class G, int S, bool FULL> __device__ __forceinline__ void wdescend(in
         wave_sync(); // the stage's outputs, written by all lanes, are read by other lanes next
         const int n = 2 * valid;
         if constexpr (S + 1 == G::NS - 1) {
-            wdescend<G, S + 1, FULL>(lds, lane, 0, n, oc);
+            wdescend<G, S + 1, FULL, OF>(lds, lane, 0, n, oc);
         } else if constexpr (FULL) {
-            wdescend<G, S + 1, true>(lds, lane, 0, WB, oc);
-            wdescend<G, S + 1, true>(lds, lane, WB, WB, oc);
+            wdescend<G, S + 1, true, OF>(lds, lane, 0, WB, oc);
+            wdescend<G, S + 1, true, OF>(lds, lane, WB, WB, oc);
         } else {
-            wdescend<G, S + 1, false>(lds, lane, 0, n < WB ? n : WB, oc);
-            if (n > WB) wdescend<G, S + 1, false>(lds, lane, WB, n - WB, oc);
+            wdescend<G, S + 1, false, OF>(lds, lane, 0, n < WB ? n : WB, oc);
+            if (n > WB) wdescend<G, S + 1, false, OF>(lds, lane, WB, n - WB, oc);
         }
         wave_sync(); // (the consumers' reads of the old history stay in front of its rewrite)
         whist<G, S + 1>(lds, lane, n);
@@ -339,7 +365,8 @@ template <> struct WSrc<true> {
 // segment (<= 16 blocks = 8 KiB: eight global_load_dwordx4) in front of everything else, parks it in 32 accumulation registers
 // (nothing else uses them, so nothing moves them) and issues nothing but stores from then on; a pair of blocks at a time comes
 // back through v_accvgpr_read, is de-interleaved into packed I / Q pairs and staged in LDS.
-template <int L, bool GATHER = false> __device__ __forceinline__ void interp_wave_segment(const InterpArgs &a, int seg, int stream, int *lds)
+// OF: output format, IQF_S16 or IQF_S8 (a.out then points at 2-byte samples and a.out_stride counts them)
+template <int L, bool GATHER = false, int OF = IQF_S16> __device__ __forceinline__ void interp_wave_segment(const InterpArgs &a, int seg, int stream, int *lds)
 {
     constexpr int NS = (L == 6) ? 5 : L;
     static_assert(NS >= 2, "interpolate2 has a single stage: K5");
@@ -385,7 +412,8 @@ template <int L, bool GATHER = false> __device__ __forceinline__ void interp_wav
     wave_sync();
 
     IOut oc;
-    oc.out = reinterpret_cast<unsigned *>(a.out) + (size_t)stream * a.out_stride;
+    if constexpr (OF == IQF_S8) oc.out = reinterpret_cast<unsigned *>(reinterpret_cast<unsigned short *>(a.out) + (size_t)stream * a.out_stride);
+    else oc.out = reinterpret_cast<unsigned *>(a.out) + (size_t)stream * a.out_stride;
     oc.stuff64 = (L == 6);
     oc.out_pos = seg_start << NS;
     oc.store = true;
@@ -407,7 +435,7 @@ template <int L, bool GATHER = false> __device__ __forceinline__ void interp_wav
         p0[W0STR + W0HIST + lane] = __builtin_amdgcn_perm(v.y, v.x, 0x07060302u);
         wave_sync();
         oc.store = store;
-        wdescend<G, 0, false>(lds, lane, 0, cnt, oc);
+        wdescend<G, 0, false, OF>(lds, lane, 0, cnt, oc);
         hist0(cnt);
     };
     auto single = [&](size_t pos, int cnt, bool store) {
@@ -437,8 +465,8 @@ template <int L, bool GATHER = false> __device__ __forceinline__ void interp_wav
         *reinterpret_cast<uint2_t *>(p0 + W0HIST + 2 * lane) = pi;
         *reinterpret_cast<uint2_t *>(p0 + W0STR + W0HIST + 2 * lane) = pq;
         wave_sync();
-        wdescend<G, 0, true>(lds, lane, 0, WB, oc);
-        wdescend<G, 0, true>(lds, lane, 1, WB, oc);
+        wdescend<G, 0, true, OF>(lds, lane, 0, WB, oc);
+        wdescend<G, 0, true, OF>(lds, lane, 1, WB, oc);
         // history of stage 0: the pair's last 32 samples, straight from the registers of lanes 56 .. 63
         wave_sync();
         if (lane >= 56) {

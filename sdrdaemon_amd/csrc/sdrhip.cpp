@@ -94,7 +94,7 @@ static void drop_kernel_events(sdrhip_ctx *c)
 {
     (void)hipStreamSynchronize(c->stream);
     if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < SDRHIP_KCLASSES; ++k) {
         for (auto &pr : c->kev[k]) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
         c->kev[k].clear();
     }
@@ -238,25 +238,27 @@ extern "C" int sdrhip_ctx_set_option(sdrhip_ctx *c, const char *key, const char 
         else return fail(SDRHIP_EINVAL, "ctx_set_option: dec_path must be syndrome or dense");
     } else if (k == "dec_max_rows" && isnum && num >= 1 && num <= 128) c->opt.dec_max_rows = (int)num;
     else if (k == "dec_strict" && isnum && num <= 1) c->opt.dec_strict = (int)num;
-    else if (k == "ktime_stride" && isnum && num >= 1 && num <= 1024) { c->ktime_stride = (int)num; for (int i = 0; i < 4; ++i) c->ktime_stride_cls[i] = 0; }
+    else if (k == "ktime_stride" && isnum && num >= 1 && num <= 1024) { c->ktime_stride = (int)num; for (int i = 0; i < SDRHIP_KCLASSES; ++i) c->ktime_stride_cls[i] = 0; }
     else if (k == "ktime_stride_class") { // "<class>:<stride>": this kernel class only (e.g. the roofline kernel on every launch, the others on every 4th)
         int cls = -1, st = 0;
-        if (sscanf(value, "%d:%d", &cls, &st) != 2 || cls < 0 || cls > 3 || st < 1 || st > 1024) return fail(SDRHIP_EINVAL, "ctx_set_option: ktime_stride_class takes <class 0..3>:<stride 1..1024>");
+        if (sscanf(value, "%d:%d", &cls, &st) != 2 || cls < 0 || cls >= SDRHIP_KCLASSES || st < 1 || st > 1024) return fail(SDRHIP_EINVAL, "ctx_set_option: ktime_stride_class takes <class 0..4>:<stride 1..1024>");
         c->ktime_stride_cls[cls] = st;
     }
     else return fail(SDRHIP_EINVAL, "ctx_set_option: unknown key or malformed value: %s=%s", key, value);
     return SDRHIP_OK;
 }
 
-// Event counters kept on the device (read = one stream synchronisation + a 4-byte copy).
+// Event counters: kept on the device (read = one stream synchronisation + a 4-byte copy), the host-link byte counts on the host.
 extern "C" int sdrhip_ctx_get_counter(sdrhip_ctx *c, const char *key, uint64_t *value)
 {
     if (!c || !key || !value) return fail(SDRHIP_EINVAL, "ctx_get_counter: NULL argument");
     sdrhip::CtxLock lock_(c);
+    if (std::string(key) == "h2d_bytes") { *value = c->h2d_bytes; return SDRHIP_OK; }
+    if (std::string(key) == "d2h_bytes") { *value = c->d2h_bytes; return SDRHIP_OK; }
     if (std::string(key) != "dec_rows_exceeded") return fail(SDRHIP_EINVAL, "ctx_get_counter: unknown key: %s", key);
     HIP_TRY(hipSetDevice(c->device));
     unsigned v = 0;
-    HIP_TRY(hipMemcpyAsync(&v, c->dec_stats, sizeof(v), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(link_copy(c, &v, c->dec_stats, sizeof(v), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     *value = v;
     return SDRHIP_OK;
@@ -317,14 +319,14 @@ extern "C" int sdrhip_ctx_kernel_timing(sdrhip_ctx *c, int enable)
     if (!c) return fail(SDRHIP_EINVAL, "ctx is NULL");
     sdrhip::CtxLock lock_(c);
     c->ktime_on = enable != 0;
-    for (int i = 0; i < 4; ++i) c->ktime_seen[i] = 0;
+    for (int i = 0; i < SDRHIP_KCLASSES; ++i) c->ktime_seen[i] = 0;
     if (!enable) drop_kernel_events(c); // pairs nobody read
     return SDRHIP_OK;
 }
 
 extern "C" int sdrhip_ctx_kernel_timing_read(sdrhip_ctx *c, int cls, double *total_ms, unsigned *launches)
 {
-    if (!c || cls < 0 || cls > 3 || !total_ms || !launches) return fail(SDRHIP_EINVAL, "kernel_timing_read: bad argument");
+    if (!c || cls < 0 || cls >= SDRHIP_KCLASSES || !total_ms || !launches) return fail(SDRHIP_EINVAL, "kernel_timing_read: bad argument");
     sdrhip::CtxLock lock_(c);
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->stream2) HIP_TRY(hipStreamSynchronize(c->stream2));
@@ -564,6 +566,8 @@ extern "C" int sdrhip_decimate(sdrhip_decimators *d, int log2decim, int fcpos, u
         if ((rc = c->zin.reserve((size_t)S * dis * 4 + 16))) return rc;
         if ((rc = c->zout.reserve((size_t)S * dos * 4 + 16))) return rc;
         for (int s = 0; s < S; ++s) memcpy(c->zin.as<int16_t>() + (size_t)s * dis * 2, iq_in + (size_t)s * in_stride * 2, n_in * 4);
+        link_bytes(c, hipMemcpyHostToDevice, (size_t)S * n_in * 4);  // (read by the kernel over the link)
+        link_bytes(c, hipMemcpyDeviceToHost, (size_t)S * n_res * 4); // (written by it)
         rc = decimate_device(d, log2decim, fcpos, sampleSize, c->zin.as<int16_t>(), n_in, dis, c->zout.as<int16_t>(), dos, n_out, 0, 0, 0);
         if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -572,11 +576,11 @@ extern "C" int sdrhip_decimate(sdrhip_decimators *d, int log2decim, int fcpos, u
     }
     if ((rc = c->in.reserve((size_t)S * dis * 4 + 16))) return rc;
     if ((rc = c->out.reserve((size_t)S * dos * 4 + 16))) return rc;
-    HIP_TRY(hipMemcpy2DAsync(c->in.p, dis * 4, iq_in, in_stride * 4, n_in * 4, S, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(link_copy2d(c, c->in.p, dis * 4, iq_in, in_stride * 4, n_in * 4, S, hipMemcpyHostToDevice, c->stream));
     rc = decimate_device(d, log2decim, fcpos, sampleSize, static_cast<const int16_t *>(c->in.p), n_in, dis,
                          static_cast<int16_t *>(c->out.p), dos, n_out, 0, 0, 0);
     if (rc) return rc;
-    if (n_res) HIP_TRY(hipMemcpy2DAsync(iq_out, out_stride * 4, c->out.p, dos * 4, n_res * 4, S, hipMemcpyDeviceToHost, c->stream));
+    if (n_res) HIP_TRY(link_copy2d(c, iq_out, out_stride * 4, c->out.p, dos * 4, n_res * 4, S, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SDRHIP_OK;
 }

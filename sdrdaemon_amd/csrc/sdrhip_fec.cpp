@@ -123,7 +123,7 @@ int fec_decode_device(sdrhip_ctx *c, const uint8_t *rx, size_t rx_frame_bytes, c
         if ((rc = pinbuf.reserve(nb))) return rc;
         if ((rc = idxbuf.reserve(nb))) return rc;
         memcpy(pinbuf.p, indices, nb);
-        HIP_TRY(hipMemcpyAsync(idxbuf.p, pinbuf.p, nb, hipMemcpyHostToDevice, st));
+        HIP_TRY(link_copy(c, idxbuf.p, pinbuf.p, nb, hipMemcpyHostToDevice, st));
         pinbuf.mark(st);
         idx_dev = idxbuf.as<uint8_t>();
     }
@@ -156,9 +156,9 @@ extern "C" int sdrhip_fec_encode_frames(sdrhip_ctx *c, const uint8_t *frames, si
     int rc;
     if ((rc = c->in.reserve(nframes * fb))) return rc;
     if ((rc = c->out.reserve(nframes * rb))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->in.p, frames, nframes * fb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(link_copy(c, c->in.p, frames, nframes * fb, hipMemcpyHostToDevice, c->stream));
     if ((rc = fec_encode_device(c, c->in.as<uint8_t>(), fb, nframes, nb_fec, c->out.as<uint8_t>(), rb))) return rc;
-    HIP_TRY(hipMemcpyAsync(recovery_out, c->out.p, nframes * rb, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(link_copy(c, recovery_out, c->out.p, nframes * rb, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SDRHIP_OK;
 }
@@ -178,11 +178,11 @@ extern "C" int sdrhip_fec_decode_frames(sdrhip_ctx *c, const uint8_t *rx, const 
     if ((rc = c->in.reserve(nframes * fb))) return rc;
     if ((rc = c->out.reserve(nframes * pb))) return rc;
     if (block0_out && (rc = c->aux3.reserve(nframes * SDRHIP_BLOCK_BYTES))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->in.p, rx, nframes * fb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(link_copy(c, c->in.p, rx, nframes * fb, hipMemcpyHostToDevice, c->stream));
     if ((rc = fec_decode_device(c, c->in.as<uint8_t>(), fb, indices, nframes, c->out.as<uint8_t>(), pb, block0_out ? c->aux3.as<uint8_t>() : nullptr)))
         return rc;
-    HIP_TRY(hipMemcpyAsync(payload_out, c->out.p, nframes * pb, hipMemcpyDeviceToHost, c->stream));
-    if (block0_out) HIP_TRY(hipMemcpyAsync(block0_out, c->aux3.p, nframes * SDRHIP_BLOCK_BYTES, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(link_copy(c, payload_out, c->out.p, nframes * pb, hipMemcpyDeviceToHost, c->stream));
+    if (block0_out) HIP_TRY(link_copy(c, block0_out, c->aux3.p, nframes * SDRHIP_BLOCK_BYTES, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SDRHIP_OK;
 }
@@ -215,8 +215,8 @@ extern "C" int sdrhip_cm256_encode(sdrhip_ctx *c, sdrhip_cm256_params p, const s
     if ((rc = c->in.reserve(hin.size()))) return rc;
     if ((rc = c->out.reserve(hout.size()))) return rc;
     if ((rc = c->aux.reserve(mat.size()))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->in.p, hin.data(), hin.size(), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->aux.p, mat.data(), mat.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(link_copy(c, c->in.p, hin.data(), hin.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(link_copy(c, c->aux.p, mat.data(), mat.size(), hipMemcpyHostToDevice, c->stream));
     GfArgs a;
     memset(&a, 0, sizeof(a));
     a.in = c->in.as<uint8_t>(); a.out = c->out.as<uint8_t>(); a.coef = c->aux.as<uint8_t>(); a.tab = c->gf_tab;
@@ -225,7 +225,7 @@ extern "C" int sdrhip_cm256_encode(sdrhip_ctx *c, sdrhip_cm256_params p, const s
     a.rows = m; a.cols = k; a.nframes = nslab;
     hipError_t e = launch_gf_apply(a, c->stream);
     if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "cm256 encode launch: %s", hipGetErrorString(e));
-    HIP_TRY(hipMemcpyAsync(hout.data(), c->out.p, hout.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(link_copy(c, hout.data(), c->out.p, hout.size(), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (int s = 0; s < nslab; ++s) {
         const int off = s * SDRHIP_BLOCK_BYTES, len = (bb - off) < SDRHIP_BLOCK_BYTES ? (bb - off) : SDRHIP_BLOCK_BYTES;
@@ -263,8 +263,8 @@ extern "C" int sdrhip_cm256_decode(sdrhip_ctx *c, sdrhip_cm256_params p, sdrhip_
     if ((rc = c->in.reserve(hin.size()))) return rc;
     if ((rc = c->out.reserve(hout.size()))) return rc;
     if ((rc = c->aux.reserve((size_t)n_rec * k))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->in.p, hin.data(), hin.size(), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->aux.p, coef.data(), (size_t)n_rec * k, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(link_copy(c, c->in.p, hin.data(), hin.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(link_copy(c, c->aux.p, coef.data(), (size_t)n_rec * k, hipMemcpyHostToDevice, c->stream));
     GfArgs a;
     memset(&a, 0, sizeof(a));
     a.in = c->in.as<uint8_t>(); a.out = c->out.as<uint8_t>(); a.coef = c->aux.as<uint8_t>(); a.tab = c->gf_tab;
@@ -273,7 +273,7 @@ extern "C" int sdrhip_cm256_decode(sdrhip_ctx *c, sdrhip_cm256_params p, sdrhip_
     a.rows = n_rec; a.cols = k; a.nframes = nslab;
     hipError_t e = launch_gf_apply(a, c->stream);
     if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "cm256 decode launch: %s", hipGetErrorString(e));
-    HIP_TRY(hipMemcpyAsync(hout.data(), c->out.p, hout.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(link_copy(c, hout.data(), c->out.p, hout.size(), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (int i = 0; i < n_rec; ++i) {
         sdrhip_cm256_block &b = blocks[rec_pos[i]];

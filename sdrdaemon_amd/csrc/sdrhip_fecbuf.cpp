@@ -41,7 +41,7 @@ int fecbuf_init_state(sdrhip_fecbuf *b)
         x.cur_meta[2] = x.out_meta[2] = 0xff000000u;
     }
     b->cur = 0;
-    HIP_TRY(hipMemcpyAsync(b->state[0], st.data(), st.size() * sizeof(FecBufState), hipMemcpyHostToDevice, b->ctx->stream));
+    HIP_TRY(link_copy(b->ctx, b->state[0], st.data(), st.size() * sizeof(FecBufState), hipMemcpyHostToDevice, b->ctx->stream));
     HIP_TRY(hipStreamSynchronize(b->ctx->stream));
     return SDRHIP_OK;
 }
@@ -70,7 +70,7 @@ int fecbuf_device(sdrhip_fecbuf *b, const uint8_t *dg, const size_t *n_dgrams, s
     }
     if ((rc = b->rec.reserve((size_t)nrec * sizeof(FecBufRec)))) return rc;
     uint8_t *sm = b->small.as<uint8_t>();
-    HIP_TRY(hipMemcpyAsync(sm, b->pin_up.p, off_cnt, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(link_copy(c, sm, b->pin_up.p, off_cnt, hipMemcpyHostToDevice, c->stream));
     b->pin_up.mark(c->stream);
 
     FecBufArgs a;
@@ -91,7 +91,7 @@ int fecbuf_device(sdrhip_fecbuf *b, const uint8_t *dg, const size_t *n_dgrams, s
     hipError_t e = launch_fecbuf_classify(a, c->stream);
     if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "fecbuf classify launch: %s", hipGetErrorString(e));
     // the one read-back: counts + public records
-    HIP_TRY(hipMemcpyAsync(b->pin_down.p, sm + off_cnt, small_bytes - off_cnt, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(link_copy(c, b->pin_down.p, sm + off_cnt, small_bytes - off_cnt, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const int *cnt = b->pin_down.as<int>();
     const FecBufPub *pub = reinterpret_cast<const FecBufPub *>(b->pin_down.as<uint8_t>() + (off_pub - off_cnt));
@@ -124,7 +124,7 @@ int fecbuf_device(sdrhip_fecbuf *b, const uint8_t *dg, const size_t *n_dgrams, s
             o.frame_index = p[k].frame_index; o.block_count = p[k].block_count; o.recovery_count = p[k].recovery_count; o.flags = p[k].flags;
         }
     }
-    HIP_TRY(hipMemcpyAsync(sm + (size_t)S * 4, up + S, ((size_t)2 * S + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(link_copy(c, sm + (size_t)S * 4, up + S, ((size_t)2 * S + 1) * 4, hipMemcpyHostToDevice, c->stream));
     b->pin_up.mark(c->stream);
     a.stage = b->stage.as<uint8_t>(); a.dmap = b->dmap.as<int>();
     a.dec_out = b->dec_out.as<uint8_t>(); a.dec_b0 = block0_out ? b->dec_b0.as<uint8_t>() : nullptr;
@@ -222,7 +222,7 @@ int upload_dgrams(sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgram
         for (int s = 0; s < S; ++s) memcpy(b->pin_in.as<uint8_t>() + (size_t)s * row, dgrams + (size_t)s * sstride, n_dgrams[s] * SDRHIP_UDPSIZE);
         src = b->pin_in.as<uint8_t>(); sstride = row;
     }
-    HIP_TRY(hipMemcpy2DAsync(b->hin.p, row, src, sstride, row, (size_t)S, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(link_copy2d(c, b->hin.p, row, src, sstride, row, (size_t)S, hipMemcpyHostToDevice, c->stream));
     if (src != dgrams) b->pin_in.mark(c->stream);
     return SDRHIP_OK;
 }
@@ -261,11 +261,11 @@ extern "C" int sdrhip_fecbuf_write_and_read(sdrhip_fecbuf *b, const uint8_t *dgr
         return rc;
     for (int s = 0; s < S; ++s) {
         if (!n_frames[s]) continue;
-        HIP_TRY(hipMemcpyAsync(data_out + (size_t)s * data_stride_bytes, b->hout.as<uint8_t>() + (size_t)s * drow, n_frames[s] * PAYLOAD,
-                               hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(link_copy(c, data_out + (size_t)s * data_stride_bytes, b->hout.as<uint8_t>() + (size_t)s * drow,
+                          n_frames[s] * PAYLOAD, hipMemcpyDeviceToHost, c->stream));
         if (block0_out)
-            HIP_TRY(hipMemcpyAsync(block0_out + (size_t)s * max_frames * SDRHIP_BLOCK_BYTES, b->hb0.as<uint8_t>() + (size_t)s * max_frames * SDRHIP_BLOCK_BYTES,
-                                   n_frames[s] * SDRHIP_BLOCK_BYTES, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(link_copy(c, block0_out + (size_t)s * max_frames * SDRHIP_BLOCK_BYTES, b->hb0.as<uint8_t>() + (size_t)s * max_frames * SDRHIP_BLOCK_BYTES,
+                              n_frames[s] * SDRHIP_BLOCK_BYTES, hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SDRHIP_OK;
@@ -302,8 +302,8 @@ int fecbuf_collect(sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgra
         if (!rc && block0_out)
             for (int s = 0; s < S; ++s)
                 if (n_frames[s])
-                    HIP_TRY(hipMemcpyAsync(block0_out + (size_t)s * max_frames * SDRHIP_BLOCK_BYTES, b->hb0.as<uint8_t>() + (size_t)s * max_frames * SDRHIP_BLOCK_BYTES,
-                                           n_frames[s] * SDRHIP_BLOCK_BYTES, hipMemcpyDeviceToHost, c->stream));
+                    HIP_TRY(link_copy(c, block0_out + (size_t)s * max_frames * SDRHIP_BLOCK_BYTES, b->hb0.as<uint8_t>() + (size_t)s * max_frames * SDRHIP_BLOCK_BYTES,
+                                      n_frames[s] * SDRHIP_BLOCK_BYTES, hipMemcpyDeviceToHost, c->stream));
     }
     if (rc) return rc;
     *counts = reinterpret_cast<const int *>(b->small.as<uint8_t>() + counts_offset(S));
@@ -320,7 +320,7 @@ extern "C" int sdrhip_fecbuf_stats(sdrhip_fecbuf *b, int stream, int *cur_nb_blo
     HIP_TRY(hipSetDevice(b->ctx->device));
     FecBufState x;
     FecBufState *d = b->state[b->cur] + stream;
-    HIP_TRY(hipMemcpyAsync(&x, d, sizeof(x), hipMemcpyDeviceToHost, b->ctx->stream));
+    HIP_TRY(link_copy(b->ctx, &x, d, sizeof(x), hipMemcpyDeviceToHost, b->ctx->stream));
     HIP_TRY(hipStreamSynchronize(b->ctx->stream));
     if (cur_nb_blocks) *cur_nb_blocks = x.cur_blocks;
     if (cur_nb_recovery) *cur_nb_recovery = x.cur_recov;
@@ -331,7 +331,7 @@ extern "C" int sdrhip_fecbuf_stats(sdrhip_fecbuf *b, int stream, int *cur_nb_blo
     if (min_nb_blocks) { *min_nb_blocks = x.min_blocks; upd[2] = 256; }
     if (max_nb_recovery) { *max_nb_recovery = x.max_recov; upd[3] = 0; }
     if (min_nb_blocks || max_nb_recovery) {
-        HIP_TRY(hipMemcpyAsync(&d->cur_blocks, upd, sizeof(upd), hipMemcpyHostToDevice, b->ctx->stream));
+        HIP_TRY(link_copy(b->ctx, &d->cur_blocks, upd, sizeof(upd), hipMemcpyHostToDevice, b->ctx->stream));
         HIP_TRY(hipStreamSynchronize(b->ctx->stream));
     }
     return SDRHIP_OK;

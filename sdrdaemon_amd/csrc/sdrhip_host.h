@@ -89,7 +89,8 @@ struct InterpCount { // InterpArgs::count / count_stride / count_unit: per-strea
 };
 // count (optional): stream s takes count[s * stride] * unit inputs, at most n_in (the grid is planned for n_in, the largest)
 int interpolate_device(sdrhip_interpolators *p, int log2interp, const int16_t *in, size_t n_in, size_t in_stride, int16_t *out,
-                       size_t out_stride, size_t *n_out, const InterpGather *gather = nullptr, const InterpCount *count = nullptr);
+                       size_t out_stride, size_t *n_out, const InterpGather *gather = nullptr, const InterpCount *count = nullptr,
+                       int out_fmt = IQF_S16); // IQF_S8: `out` holds 2-byte samples, out_stride counts them (multiple of 8 for streams > 1)
 // FEC buffer bank (sdrhip_fecbuf.cpp) for the Tx pipe fed datagrams: the datagram arguments of sdrhip_fecbuf_write_and_read, then
 // the bank's call with data_out on the device and dgrams / block0_out in `mem` memory (host: staged; block0_out downloaded on the
 // context's stream, not synchronised); *counts (device) = the per-stream counts [S][FB_COUNTS] the classify pass left (FB_K: frames)
@@ -141,6 +142,7 @@ bool host_is_pinned(const void *p, size_t n);
 
 } // namespace sdrhip
 
+#define SDRHIP_KCLASSES 5 // SDRHIP_K_DECIMATE .. SDRHIP_K_CONVERT
 namespace sdrhip {
 enum { DECIM_PATH_AUTO = 0, DECIM_PATH_VALU = 1, DECIM_PATH_MFMA = 2 };
 // Kernel-path knobs of a context.  Read ONCE from the environment when the context is created (SDRHIP_DECIM_PATH =
@@ -213,9 +215,11 @@ struct sdrhip_ctx {
     // per-kernel-class timing with hipEvents on `stream` (sdrhip_ctx_kernel_timing)
     bool ktime_on = false;
     int ktime_stride = 1;                     // kernel-class timers bracket every ktime_stride-th launch of a class (option "ktime_stride")
-    int ktime_stride_cls[4] = {0, 0, 0, 0};   // ... per class when > 0 (option "ktime_stride_class" = "<class>:<stride>"; "ktime_stride" resets them)
-    unsigned ktime_seen[4] = {0, 0, 0, 0};
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> kev[4];
+    int ktime_stride_cls[SDRHIP_KCLASSES] = {0, 0, 0, 0, 0}; // ... per class when > 0 (option "ktime_stride_class" = "<class>:<stride>"; "ktime_stride" resets them)
+    unsigned ktime_seen[SDRHIP_KCLASSES] = {0, 0, 0, 0, 0};
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> kev[SDRHIP_KCLASSES];
+    // bytes the entry points copied across the host link (sdrhip_ctx_get_counter "h2d_bytes" / "d2h_bytes"), counted when enqueued
+    uint64_t h2d_bytes = 0, d2h_bytes = 0;
 };
 
 namespace sdrhip {
@@ -233,7 +237,7 @@ struct KTimer {
     {
         if (!c->ktime_on) return;
         // (an event pair around a launch costs the stream ~2.5 us: timing every launch of a two-launch step took 3 % off the step)
-        if (cls >= 0 && cls < 4) {
+        if (cls >= 0 && cls < SDRHIP_KCLASSES) {
             const int stride = c->ktime_stride_cls[cls] > 0 ? c->ktime_stride_cls[cls] : c->ktime_stride;
             if (stride > 1 && (c->ktime_seen[cls]++ % (unsigned)stride) != 0) return;
         }
@@ -248,4 +252,25 @@ struct KTimer {
         if (e1) (void)hipEventRecord(e1, st);
     }
 };
+// a copy across the host link of `bytes` (hipMemcpyHostToDevice / DeviceToHost; anything else is not counted)
+inline void link_bytes(sdrhip_ctx *c, hipMemcpyKind kind, size_t bytes)
+{
+    if (kind == hipMemcpyHostToDevice) c->h2d_bytes += bytes;
+    else if (kind == hipMemcpyDeviceToHost) c->d2h_bytes += bytes;
+}
+// hipMemcpyAsync / hipMemcpy2DAsync on the context's behalf: the bytes of a copy across the host link are counted (link_bytes)
+// when it was enqueued
+inline hipError_t link_copy(sdrhip_ctx *c, void *dst, const void *src, size_t bytes, hipMemcpyKind kind, hipStream_t stream)
+{
+    const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, stream);
+    if (e == hipSuccess) link_bytes(c, kind, bytes);
+    return e;
+}
+inline hipError_t link_copy2d(sdrhip_ctx *c, void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t height,
+                              hipMemcpyKind kind, hipStream_t stream)
+{
+    const hipError_t e = hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height, kind, stream);
+    if (e == hipSuccess) link_bytes(c, kind, width * height);
+    return e;
+}
 } // namespace sdrhip

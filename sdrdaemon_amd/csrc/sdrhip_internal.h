@@ -212,14 +212,29 @@ struct InterpArgs {
     const int *count;
     int count_stride, count_unit;
 };
+// IQ sample formats of the pipes' edges (= SDRHIP_IQ_* of include/sdrhip.h)
+enum { IQF_S16 = 0, IQF_U8 = 1, IQF_S8 = 2 };
+// K0 (convert_kernels.hip): 8-bit IQ rows (stream s at in + 2 * s * in_stride bytes, in_stride a multiple of 8 samples) -> int16 rows
+// (stream s at out + 2 * s * out_stride, out_stride a multiple of 4); fmt IQF_U8 / IQF_S8
+hipError_t launch_iq8_widen(int fmt, const uint8_t *in, size_t in_stride, int16_t *out, size_t out_stride, size_t n, int nstreams,
+                            hipStream_t stream);
+// K6n: int16 rows -> int8 rows of byte 1 of every component (interpolate1 with IQF_S8 output)
+hipError_t launch_iq8_narrow(const int16_t *in, size_t in_stride, uint8_t *out, size_t out_stride, size_t n, int nstreams, hipStream_t stream);
+
+// out_fmt IQF_S8 (interpolators below): InterpArgs::out points at 2-byte samples {int8 re, int8 im} and out_stride counts them; the
+// last stage stores (int8)(v >> 8) of each component (own kernel instantiations; IQF_S16 launches the kernels as they were)
 hipError_t launch_interpolate(int log2interp, const InterpArgs &a, hipStream_t stream);
 void plan_interpolate(int log2interp, size_t n_in, int nstreams, int *nsub_per_seg, int *nseg);
 // K5w (interp_wave.h): wave-private pipelines (workgroups of one or four independent waves), blocks of 128 inputs; log2interp 2..6
 void plan_interpolate_wave(int log2interp, size_t n_in, int nstreams, int n_cu, size_t seg_override, int *nsub_per_seg, int *nseg);
 hipError_t launch_interpolate_wave(int log2interp, const InterpArgs &a, hipStream_t stream);
+hipError_t launch_interpolate_s8(int log2interp, const InterpArgs &a, hipStream_t stream);
+hipError_t launch_interpolate_wave_s8(int log2interp, const InterpArgs &a, hipStream_t stream);
 // ... with per-stream input counts (InterpArgs::count), planned like the uniform launch of the largest
 hipError_t launch_interpolate_ragged(int log2interp, const InterpArgs &a, hipStream_t stream);
 hipError_t launch_interpolate_wave_ragged(int log2interp, const InterpArgs &a, hipStream_t stream);
+hipError_t launch_interpolate_ragged_s8(int log2interp, const InterpArgs &a, hipStream_t stream);
+hipError_t launch_interpolate_wave_ragged_s8(int log2interp, const InterpArgs &a, hipStream_t stream);
 
 // frames are processed in groups that share one coefficient matrix (one frame per half-wave)
 constexpr int GF_FRAMES_PER_GROUP = 2;

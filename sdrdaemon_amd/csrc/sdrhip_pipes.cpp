@@ -63,13 +63,23 @@ namespace sdrhip {
 bool interpolate_gather_ok(const sdrhip_ctx *c, int log2interp) { return c->opt.interp_wave && log2interp >= 2; }
 
 int interpolate_device(sdrhip_interpolators *p, int log2interp, const int16_t *in, size_t n_in, size_t in_stride, int16_t *out,
-                       size_t out_stride, size_t *n_out, const InterpGather *gather, const InterpCount *count)
+                       size_t out_stride, size_t *n_out, const InterpGather *gather, const InterpCount *count, int out_fmt)
 {
     sdrhip_ctx *c = p->ctx;
     if (n_out) *n_out = n_in << log2interp;
     if (n_in == 0) return SDRHIP_OK;
     if (gather && !interpolate_gather_ok(p->ctx, log2interp)) return fail(SDRHIP_EINVAL, "internal: gathered input needs the wave interpolator");
     if (gather && count) return fail(SDRHIP_EINVAL, "internal: no ragged gather");
+    if (gather && out_fmt != IQF_S16) return fail(SDRHIP_EINVAL, "internal: gathered input has int16 output only");
+    if (log2interp == 0 && out_fmt == IQF_S8) { // the copy, narrowed (K6n)
+        hipError_t e;
+        {
+            KTimer kt(c, SDRHIP_K_INTERPOLATE);
+            e = launch_iq8_narrow(in, in_stride, reinterpret_cast<uint8_t *>(out), out_stride, n_in, p->nstreams, c->stream);
+        }
+        if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "narrow launch: %s", hipGetErrorString(e));
+        return SDRHIP_OK;
+    }
     if (log2interp == 0) { // Upsampler::process m_interp == 0: samples_out = samples_in (Upsampler.cpp:54-57)
         HIP_TRY(hipMemcpy2DAsync(out, out_stride * 4, in, in_stride * 4, n_in * 4, p->nstreams, hipMemcpyDeviceToDevice, c->stream));
         return SDRHIP_OK;
@@ -88,7 +98,10 @@ int interpolate_device(sdrhip_interpolators *p, int log2interp, const int16_t *i
     hipError_t e;
     {
         KTimer kt(c, SDRHIP_K_INTERPOLATE);
-        if (count) e = use_wave ? launch_interpolate_wave_ragged(log2interp, a, c->stream) : launch_interpolate_ragged(log2interp, a, c->stream);
+        if (out_fmt == IQF_S8) {
+            if (count) e = use_wave ? launch_interpolate_wave_ragged_s8(log2interp, a, c->stream) : launch_interpolate_ragged_s8(log2interp, a, c->stream);
+            else e = use_wave ? launch_interpolate_wave_s8(log2interp, a, c->stream) : launch_interpolate_s8(log2interp, a, c->stream);
+        } else if (count) e = use_wave ? launch_interpolate_wave_ragged(log2interp, a, c->stream) : launch_interpolate_ragged(log2interp, a, c->stream);
         else e = use_wave ? launch_interpolate_wave(log2interp, a, c->stream) : launch_interpolate(log2interp, a, c->stream);
     }
     if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "interpolate launch: %s", hipGetErrorString(e));
@@ -121,9 +134,9 @@ extern "C" int sdrhip_interpolate(sdrhip_interpolators *p, int log2interp, const
     int rc;
     if ((rc = c->in.reserve((size_t)S * dis * 4 + 16))) return rc;
     if ((rc = c->out.reserve((size_t)S * dos * 4 + 16))) return rc;
-    HIP_TRY(hipMemcpy2DAsync(c->in.p, dis * 4, iq_in, in_stride * 4, n_in * 4, S, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(link_copy2d(c, c->in.p, dis * 4, iq_in, in_stride * 4, n_in * 4, S, hipMemcpyHostToDevice, c->stream));
     if ((rc = interpolate_device(p, log2interp, c->in.as<int16_t>(), n_in, dis, c->out.as<int16_t>(), dos, n_out))) return rc;
-    HIP_TRY(hipMemcpy2DAsync(iq_out, out_stride * 4, c->out.p, dos * 4, n_res * 4, S, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(link_copy2d(c, iq_out, out_stride * 4, c->out.p, dos * 4, n_res * 4, S, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SDRHIP_OK;
 }
@@ -186,6 +199,9 @@ struct sdrhip_rx {
     int a_blocks = 1;             // blocks per launch
     bool consumed = false;        // set by sdrhip_rx_process once the decimator launch of the call went out (the filter state advanced)
     size_t a_head = 0, a_tail = 0; // next batch to collect / batch being filled
+    // ---- input format (sdrhip_rx_set_input_format): 8-bit input is widened by K0 into `wide`, the decimator's int16 input
+    int in_fmt = IQF_S16;
+    DevBuf wide;
 };
 
 static int rx_check_config(const sdrhip_rx_config *cfg);
@@ -246,6 +262,34 @@ extern "C" int sdrhip_rx_set_pipelined(sdrhip_rx *rx, int on)
     return SDRHIP_OK;
 }
 
+extern "C" int sdrhip_rx_set_input_format(sdrhip_rx *rx, int fmt)
+{
+    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
+    sdrhip::CtxLock lock_(rx->ctx);
+    if (fmt != SDRHIP_IQ_S16 && fmt != SDRHIP_IQ_U8 && fmt != SDRHIP_IQ_S8) return fail(SDRHIP_EINVAL, "rx_set_input_format: unknown format %d", fmt);
+    for (const auto &b : rx->abatch)
+        if (b.state != 0) return fail(SDRHIP_EINVAL, "rx_set_input_format: asynchronous batches are being filled or in flight: collect them first");
+    if (rx->late.have) return fail(SDRHIP_EINVAL, "rx_set_input_format: frames of the previous call wait for delivery (pipelined mode): sdrhip_rx_flush them first");
+    rx->in_fmt = fmt;
+    return SDRHIP_OK;
+}
+
+// K0: 8-bit rows (in_stride a multiple of 8 samples, or one stream) -> rx->wide [stream][dstride] int16, ahead of the decimator
+static int rx_widen(sdrhip_rx *rx, const uint8_t *in, size_t in_stride, size_t n_in, size_t dstride, const int16_t **din)
+{
+    sdrhip_ctx *c = rx->ctx;
+    int rc = rx->wide.reserve((size_t)rx->nstreams * dstride * 4 + 16);
+    if (rc) return rc;
+    hipError_t e;
+    {
+        KTimer kt(c, SDRHIP_K_CONVERT);
+        e = launch_iq8_widen(rx->in_fmt, in, in_stride, rx->wide.as<int16_t>(), dstride, n_in, rx->nstreams, c->stream);
+    }
+    if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "widen launch: %s", hipGetErrorString(e));
+    *din = rx->wide.as<int16_t>();
+    return SDRHIP_OK;
+}
+
 extern "C" int sdrhip_rx_reconfigure(sdrhip_rx *rx, const sdrhip_rx_config *cfg)
 {
     if (!rx || !cfg) return fail(SDRHIP_EINVAL, "rx_reconfigure: NULL argument");
@@ -292,6 +336,7 @@ extern "C" void sdrhip_rx_destroy(sdrhip_rx *rx)
     rx->lin[0].release();
     rx->lin[1].release();
     rx->flist.release();
+    rx->wide.release();
     if (rx->ev_framed) (void)hipEventDestroy(rx->ev_framed);
     if (rx->ev_enc) (void)hipEventDestroy(rx->ev_enc);
     for (auto &b : rx->abatch) {
@@ -334,8 +379,8 @@ static int rx_deliver(sdrhip_rx *rx, const uint8_t *base, size_t stride, size_t 
     const int S = rx->nstreams;
     if (frames && frames_out) {
         if (S > 1 && frame_stride_bytes < frames * frame_bytes) return fail(SDRHIP_EINVAL, "rx_process: frame stride too small");
-        HIP_TRY(hipMemcpy2DAsync(frames_out, S > 1 ? frame_stride_bytes : frames * frame_bytes, base, stride, frames * frame_bytes, S,
-                                 mem == SDRHIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(link_copy2d(c, frames_out, S > 1 ? frame_stride_bytes : frames * frame_bytes, base, stride, frames * frame_bytes, S,
+                            mem == SDRHIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
     } else if (frames && mem != SDRHIP_MEM_DEVICE) {
         return fail(SDRHIP_EINVAL, "rx_process: NULL frames_out");
     }
@@ -393,17 +438,40 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
     const int16_t *din = iq_in;
     size_t dstride = in_stride;
     int rc;
-    if (mem == SDRHIP_MEM_HOST) {
+    if (rx->in_fmt != IQF_S16 && (mem == SDRHIP_MEM_HOST || mem == SDRHIP_MEM_DEVICE)) {
+        // 8-bit input: 2 bytes per sample cross the link (rows of a multiple of 8 samples: K0's 16-byte loads), K0 widens them into
+        // rx->wide, which the decimator reads as it reads int16 input
+        const uint8_t *src = reinterpret_cast<const uint8_t *>(iq_in), *d8 = src;
+        size_t sstride = in_stride;
+        if (mem == SDRHIP_MEM_HOST) {
+            sstride = (n_in + 7) & ~(size_t)7;
+            if ((size_t)S * sstride * 2 <= SDRHIP_ZEROCOPY_MAX) { // (small call: K0 reads the pinned rows itself, as the decimator does for int16)
+                if ((rc = c->zin.reserve((size_t)S * sstride * 2 + 16))) return rc;
+                for (int s = 0; s < S; ++s) memcpy(c->zin.as<uint8_t>() + (size_t)s * sstride * 2, src + (size_t)s * in_stride * 2, n_in * 2);
+                link_bytes(c, hipMemcpyHostToDevice, (size_t)S * n_in * 2);
+                d8 = c->zin.as<uint8_t>();
+            } else {
+                if ((rc = c->in.reserve((size_t)S * sstride * 2 + 16))) return rc;
+                HIP_TRY(link_copy2d(c, c->in.p, sstride * 2, src, in_stride * 2, n_in * 2, S, hipMemcpyHostToDevice, c->stream));
+                d8 = c->in.as<uint8_t>();
+            }
+        } else if (!aligned16(iq_in) || (S > 1 && (in_stride & 7))) {
+            return fail(SDRHIP_EALIGN, "rx_process: 8-bit device input must be 16-byte aligned, its stride a multiple of 8 samples");
+        }
+        dstride = (n_in + 3) & ~(size_t)3;
+        if ((rc = rx_widen(rx, d8, sstride, n_in, dstride, &din))) return rc;
+    } else if (mem == SDRHIP_MEM_HOST) {
         dstride = (n_in + 3) & ~(size_t)3;
         if ((size_t)S * dstride * 4 <= SDRHIP_ZEROCOPY_MAX) {
             // small call: the decimator reads pinned host memory itself (no copy engine in front of the launch); the buffer is
             // free again when this call returns (host-pointer calls end with a stream synchronisation)
             if ((rc = c->zin.reserve((size_t)S * dstride * 4 + 16))) return rc;
             for (int s = 0; s < S; ++s) memcpy(c->zin.as<int16_t>() + (size_t)s * dstride * 2, iq_in + (size_t)s * in_stride * 2, n_in * 4);
+            link_bytes(c, hipMemcpyHostToDevice, (size_t)S * n_in * 4); // (read by the decimator over the link)
             din = c->zin.as<int16_t>();
         } else {
             if ((rc = c->in.reserve((size_t)S * dstride * 4 + 16))) return rc;
-            HIP_TRY(hipMemcpy2DAsync(c->in.p, dstride * 4, iq_in, in_stride * 4, n_in * 4, S, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(link_copy2d(c, c->in.p, dstride * 4, iq_in, in_stride * 4, n_in * 4, S, hipMemcpyHostToDevice, c->stream));
             din = c->in.as<int16_t>();
         }
     } else if (mem == SDRHIP_MEM_DEVICE) {
@@ -585,7 +653,7 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
                     for (size_t f = 0; f < done; ++f) rx->flist_host.push_back((int32_t)(s * rx->cap_frames + f));
                 while (rx->flist_host.size() % GF_FRAMES_PER_GROUP) rx->flist_host.push_back(-1);
                 if ((rc = rx->flist.reserve(rx->flist_host.size() * 4))) return rc;
-                HIP_TRY(hipMemcpyAsync(rx->flist.p, rx->flist_host.data(), rx->flist_host.size() * 4, hipMemcpyHostToDevice, c->stream));
+                HIP_TRY(link_copy(c, rx->flist.p, rx->flist_host.data(), rx->flist_host.size() * 4, hipMemcpyHostToDevice, c->stream));
                 rx->flist_done = done; rx->flist_cap = rx->cap_frames;
             }
             if ((rc = fec_encode_device(c, work, frame_bytes, (size_t)S * rx->cap_frames, R, work + (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE,
@@ -648,24 +716,26 @@ int rx_launch_batch(sdrhip_rx *rx, sdrhip_rx::Batch &b)
 {
     sdrhip_ctx *c = rx->ctx;
     const int S = rx->nstreams;
-    const size_t dstride = (b.n_in + 3) & ~(size_t)3;
+    // (8-bit input: the batch goes up as bytes, rows of a multiple of 8 samples; sdrhip_rx_process widens it on the device)
+    const size_t esz = rx->in_fmt == IQF_S16 ? 4 : 2;
+    const size_t dstride = esz == 4 ? (b.n_in + 3) & ~(size_t)3 : (b.n_in + 7) & ~(size_t)7;
     int rc;
-    if ((rc = b.din.reserve((size_t)S * dstride * 4 + 16))) return rc;
+    if ((rc = b.din.reserve((size_t)S * dstride * esz + 16))) return rc;
     // uploads: runs of blocks that are adjacent in host memory go out as ONE 2-D copy (a run of staged blocks -- stream-major in
     // the pinned arena -- or of in-place blocks cut from one buffer)
     size_t off = 0;
     for (size_t i = 0; i < b.blocks.size();) {
-        const int16_t *src = b.blocks[i].first;
+        const char *src = reinterpret_cast<const char *>(b.blocks[i].first);
         size_t sstride = b.strides[i], n = b.blocks[i].second, j = i + 1;
         if (!src) { // staged: [stream][in_cap] at sample offset `off` of every row (all staged blocks of a batch are one run)
-            src = b.in.as<int16_t>() + off * 2;
+            src = b.in.as<char>() + off * esz;
             sstride = b.in_cap;
             while (j < b.blocks.size() && !b.blocks[j].first) n += b.blocks[j++].second;
         } else {
-            while (j < b.blocks.size() && b.blocks[j].first == src + n * 2 && b.strides[j] == sstride) n += b.blocks[j++].second;
+            while (j < b.blocks.size() && reinterpret_cast<const char *>(b.blocks[j].first) == src + n * esz && b.strides[j] == sstride) n += b.blocks[j++].second;
         }
-        if (S == 1) HIP_TRY(hipMemcpyAsync(b.din.as<char>() + off * 4, src, n * 4, hipMemcpyHostToDevice, c->stream)); // (no pitch limits)
-        else HIP_TRY(hipMemcpy2DAsync(b.din.as<char>() + off * 4, dstride * 4, src, sstride * 4, n * 4, S, hipMemcpyHostToDevice, c->stream));
+        if (S == 1) HIP_TRY(link_copy(c, b.din.as<char>() + off * esz, src, n * esz, hipMemcpyHostToDevice, c->stream)); // (no pitch limits)
+        else HIP_TRY(link_copy2d(c, b.din.as<char>() + off * esz, dstride * esz, src, sstride * esz, n * esz, S, hipMemcpyHostToDevice, c->stream));
         off += n;
         i = j;
     }
@@ -687,8 +757,8 @@ int rx_launch_batch(sdrhip_rx *rx, sdrhip_rx::Batch &b)
     b.frames = nf;
     hipError_t e = hipSuccess;
     if (nf > nf_max) e = hipErrorInvalidValue; // (cannot happen: rx_max_frames is the pipe's own bound)
-    else if (nf && S == 1) e = hipMemcpyAsync(b.out.p, rx->view_base, nf * b.frame_bytes, hipMemcpyDeviceToHost, c->stream);
-    else if (nf) e = hipMemcpy2DAsync(b.out.p, nf * b.frame_bytes, rx->view_base, rx->view_stride, nf * b.frame_bytes, S, hipMemcpyDeviceToHost, c->stream);
+    else if (nf && S == 1) e = link_copy(c, b.out.p, rx->view_base, nf * b.frame_bytes, hipMemcpyDeviceToHost, c->stream);
+    else if (nf) e = link_copy2d(c, b.out.p, nf * b.frame_bytes, rx->view_base, rx->view_stride, nf * b.frame_bytes, S, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipEventRecord(b.done, c->stream);
     if (e != hipSuccess) {
         b.state = 0; // consumed and lost: never replayed
@@ -751,7 +821,9 @@ extern "C" int sdrhip_rx_submit(sdrhip_rx *rx, const int16_t *iq_in, size_t n_in
         b.blocks.clear(); b.strides.clear(); b.n_in = 0; b.tv_sec = tv_sec; b.tv_usec = tv_usec; b.state = 1;
         b.in_cap = 0; // no staged rows yet: the first pageable block of this batch (re)claims the arena
     }
-    if (host_is_pinned(iq_in, ((size_t)(S - 1) * in_stride + n_in) * 4)) {
+    const size_t esz = rx->in_fmt == IQF_S16 ? 4 : 2; // bytes per sample (sdrhip_rx_set_input_format)
+    const char *src = reinterpret_cast<const char *>(iq_in);
+    if (host_is_pinned(iq_in, ((size_t)(S - 1) * in_stride + n_in) * esz)) {
         b.blocks.push_back(std::make_pair(iq_in, n_in)); // in place: the caller keeps it untouched until the batch is collected
         b.strides.push_back(in_stride);
     } else {
@@ -760,20 +832,20 @@ extern "C" int sdrhip_rx_submit(sdrhip_rx *rx, const int16_t *iq_in, size_t n_in
         const size_t need = b.n_in + n_in;
         if (b.in_cap == 0) { // first staged block of the batch, whatever came before it in place
             const size_t cap = (size_t)rx->a_blocks * n_in > need ? (size_t)rx->a_blocks * n_in : need;
-            int rc = b.in.reserve((size_t)S * cap * 4); // (waits for the upload of the batch that used this buffer last)
+            int rc = b.in.reserve((size_t)S * cap * esz); // (waits for the upload of the batch that used this buffer last)
             if (rc) return rc;
             b.in_cap = cap;
         } else if (need > b.in_cap) { // blocks longer than the first one: re-lay the rows out in a bigger arena
             PinnedBuf bigger;
             const size_t ncap = 2 * need;
-            int rc = bigger.reserve((size_t)S * ncap * 4);
+            int rc = bigger.reserve((size_t)S * ncap * esz);
             if (rc) return rc;
-            for (int s = 0; s < S; ++s) memcpy(bigger.as<char>() + (size_t)s * ncap * 4, b.in.as<char>() + (size_t)s * b.in_cap * 4, b.n_in * 4);
+            for (int s = 0; s < S; ++s) memcpy(bigger.as<char>() + (size_t)s * ncap * esz, b.in.as<char>() + (size_t)s * b.in_cap * esz, b.n_in * esz);
             b.in.release();
             b.in = bigger;
             b.in_cap = ncap;
         }
-        for (int s = 0; s < S; ++s) memcpy(b.in.as<char>() + ((size_t)s * b.in_cap + b.n_in) * 4, iq_in + (size_t)s * in_stride * 2, n_in * 4);
+        for (int s = 0; s < S; ++s) memcpy(b.in.as<char>() + ((size_t)s * b.in_cap + b.n_in) * esz, src + (size_t)s * in_stride * esz, n_in * esz);
         b.blocks.push_back(std::make_pair((const int16_t *)nullptr, n_in));
         b.strides.push_back(n_in);
     }
@@ -876,7 +948,17 @@ struct sdrhip_tx {
     // ---- datagram entry (sdrhip_tx_process_datagrams): one SDRdaemonFECBuffer per stream, created on first use; the frames it
     // releases go to payload[0] (or straight to the caller's device iq_out when log2interp = 0), the interpolator reads them there
     sdrhip_fecbuf *fb = nullptr;
+    // ---- output format (sdrhip_tx_set_output_format): IQF_S8 = 2-byte samples from the interpolator's last stage (or K6n for x1)
+    int out_fmt = IQF_S16;
 };
+
+namespace {
+// bytes per output sample, and the row pitch (samples) of the library's own output buffers: 16-byte rows either way
+inline size_t tx_esz(const sdrhip_tx *tx) { return tx->out_fmt == IQF_S8 ? 2 : 4; }
+inline size_t tx_pitch(const sdrhip_tx *tx, size_t n) { return tx->out_fmt == IQF_S8 ? (n + 7) & ~(size_t)7 : (n + 3) & ~(size_t)3; }
+// a device output the interpolator may store to with 16-byte stores: aligned, the stride a multiple of 4 (int16) / 8 (8-bit) samples
+inline bool tx_out_aligned(const sdrhip_tx *tx, const void *p, size_t stride) { return aligned16(p) && (tx->nstreams == 1 || (stride & (tx->out_fmt == IQF_S8 ? 7 : 3)) == 0); }
+} // namespace
 
 extern "C" int sdrhip_tx_create(sdrhip_ctx *ctx, int nstreams, int log2interp, sdrhip_tx **out)
 {
@@ -941,6 +1023,19 @@ extern "C" int sdrhip_tx_set_pipelined(sdrhip_tx *tx, int on)
     return SDRHIP_OK;
 }
 
+extern "C" int sdrhip_tx_set_output_format(sdrhip_tx *tx, int fmt)
+{
+    if (!tx) return fail(SDRHIP_EINVAL, "tx is NULL");
+    sdrhip::CtxLock lock_(tx->ctx);
+    if (fmt == SDRHIP_IQ_U8) return fail(SDRHIP_EINVAL, "tx_set_output_format: SDRHIP_IQ_U8 is an input format (RTL-SDR); the Tx side gives S16 or S8");
+    if (fmt != SDRHIP_IQ_S16 && fmt != SDRHIP_IQ_S8) return fail(SDRHIP_EINVAL, "tx_set_output_format: unknown format %d", fmt);
+    for (const auto &b : tx->abatch)
+        if (b.state != 0) return fail(SDRHIP_EINVAL, "tx_set_output_format: asynchronous batches are in flight: collect them first");
+    if (tx->late.have) return fail(SDRHIP_EINVAL, "tx_set_output_format: a pipelined batch waits: sdrhip_tx_flush it first");
+    tx->out_fmt = fmt;
+    return SDRHIP_OK;
+}
+
 namespace {
 // decode S x nframes frames into `pay` ([S][pstride] samples): one batch, or one call per stream when the rows are padded
 int tx_decode(sdrhip_tx *tx, const uint8_t *drx, const uint8_t *indices, size_t nframes, DevBuf &pay, size_t pstride, const DecodeSide *side,
@@ -966,7 +1061,7 @@ int tx_decode(sdrhip_tx *tx, const uint8_t *drx, const uint8_t *indices, size_t 
 bool tx_gather_applies(const sdrhip_tx *tx, int log2interp)
 {
     const sdrhip_ctx *c = tx->ctx;
-    return c->opt.tx_gather && !tx->pipelined && interpolate_gather_ok(c, log2interp) && fec_decode_gather_ok(c);
+    return c->opt.tx_gather && !tx->pipelined && tx->out_fmt == IQF_S16 && interpolate_gather_ok(c, log2interp) && fec_decode_gather_ok(c);
 }
 int tx_decode_gather(sdrhip_tx *tx, const uint8_t *drx, const uint8_t *indices, size_t nframes, InterpGather *g, uint8_t *block0 = nullptr)
 {
@@ -998,14 +1093,15 @@ int tx_interpolate(sdrhip_tx *tx, int log2interp, const DevBuf &pay, size_t n_pa
     int16_t *dout = iq_out;
     size_t dos = out_stride;
     int rc;
+    const size_t esz = tx_esz(tx);
     if (mem == SDRHIP_MEM_HOST) {
-        dos = (n_res + 3) & ~(size_t)3;
-        if ((rc = tx->outbuf.reserve((size_t)S * dos * 4 + 16))) return rc;
+        dos = tx_pitch(tx, n_res);
+        if ((rc = tx->outbuf.reserve((size_t)S * dos * esz + 16))) return rc;
         dout = tx->outbuf.as<int16_t>();
     }
-    if ((rc = interpolate_device(tx->itp, log2interp, gather ? nullptr : pay.as<int16_t>(), n_payload, pstride, dout, dos, nullptr, gather))) return rc;
+    if ((rc = interpolate_device(tx->itp, log2interp, gather ? nullptr : pay.as<int16_t>(), n_payload, pstride, dout, dos, nullptr, gather, nullptr, tx->out_fmt))) return rc;
     if (mem == SDRHIP_MEM_HOST)
-        HIP_TRY(hipMemcpy2DAsync(iq_out, out_stride * 4, dout, dos * 4, n_res * 4, S, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(link_copy2d(c, iq_out, out_stride * esz, dout, dos * esz, n_res * esz, S, hipMemcpyDeviceToHost, c->stream));
     return SDRHIP_OK;
 }
 
@@ -1018,7 +1114,7 @@ int tx_deliver_late(sdrhip_tx *tx, int16_t *iq_out, size_t out_stride, size_t *n
     if (S == 1) out_stride = n_res;
     if (!iq_out) return fail(SDRHIP_EINVAL, "tx: NULL output buffer for the waiting batch");
     if (out_stride < n_res) return fail(SDRHIP_EINVAL, "tx: out_stride smaller than the waiting batch (%zu samples per stream)", n_res);
-    if (mem == SDRHIP_MEM_DEVICE && (!aligned16(iq_out) || (S > 1 && (out_stride & 3)))) return fail(SDRHIP_EALIGN, "tx_process: device output must be 16-byte aligned");
+    if (mem == SDRHIP_MEM_DEVICE && !tx_out_aligned(tx, iq_out, out_stride)) return fail(SDRHIP_EALIGN, "tx_process: device output must be 16-byte aligned, its stride a multiple of 4 (8-bit: 8) samples");
     const int sel = tx->psel ^ 1; // (psel already points at the buffer the NEXT decode fills)
     HIP_TRY(hipStreamWaitEvent(c->stream, tx->ev_dec, 0));
     int rc = tx_interpolate(tx, tx->late.log2interp, tx->payload[sel], tx->late.n_payload, tx->late.pstride, iq_out, out_stride, mem);
@@ -1098,7 +1194,7 @@ extern "C" int sdrhip_tx_process(sdrhip_tx *tx, const uint8_t *rx, const uint8_t
         if (mem == SDRHIP_MEM_HOST) {
             if (overlap) HIP_TRY(hipStreamSynchronize(s2)); // (the previous decode may still read rxbuf; it ran beside the previous call's interpolator)
             if ((rc = tx->rxbuf.reserve((size_t)S * nframes * fb))) return rc;
-            HIP_TRY(hipMemcpy2DAsync(tx->rxbuf.p, nframes * fb, rx, rx_stride_bytes, nframes * fb, S, hipMemcpyHostToDevice, s2));
+            HIP_TRY(link_copy2d(c, tx->rxbuf.p, nframes * fb, rx, rx_stride_bytes, nframes * fb, S, hipMemcpyHostToDevice, s2));
             // (pinned caller memory makes this copy truly asynchronous, and it runs on the SECOND stream: the call must not return
             // before it has read `rx` -- the host-pointer contract is "the buffer is yours again when the call returns")
             if (overlap) HIP_TRY(hipEventRecord(tx->ev_up, s2));
@@ -1123,10 +1219,10 @@ extern "C" int sdrhip_tx_process(sdrhip_tx *tx, const uint8_t *rx, const uint8_t
     const uint8_t *drx = rx;
     if (mem == SDRHIP_MEM_HOST) {
         if ((rc = tx->rxbuf.reserve((size_t)S * nframes * fb))) return rc;
-        HIP_TRY(hipMemcpy2DAsync(tx->rxbuf.p, nframes * fb, rx, rx_stride_bytes, nframes * fb, S, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(link_copy2d(c, tx->rxbuf.p, nframes * fb, rx, rx_stride_bytes, nframes * fb, S, hipMemcpyHostToDevice, c->stream));
         drx = tx->rxbuf.as<uint8_t>();
     } else {
-        if (!aligned16(iq_out) || (S > 1 && (out_stride & 3))) return fail(SDRHIP_EALIGN, "tx_process: device output must be 16-byte aligned");
+        if (!tx_out_aligned(tx, iq_out, out_stride)) return fail(SDRHIP_EALIGN, "tx_process: device output must be 16-byte aligned, its stride a multiple of 4 (8-bit: 8) samples");
     }
     if (tx_gather_applies(tx, tx->log2interp)) {
         // no-copy: decode (restored blocks + map only), then the interpolator reads the received frames through the map
@@ -1180,14 +1276,14 @@ extern "C" int sdrhip_tx_submit(sdrhip_tx *tx, const uint8_t *rx, const uint8_t 
     sdrhip_tx::ABatch &b = tx->abatch[tx->a_tail % tx->abatch.size()];
     if (b.state == 2) return fail(SDRHIP_EBUSY, "tx_submit: every batch of the ring is in flight: sdrhip_tx_collect first");
     const size_t n_payload = nframes * SDRHIP_SAMPLES_PER_FRAME, n_res = n_payload << tx->log2interp;
-    const size_t pstride = (n_payload + 3) & ~(size_t)3, dos = (n_res + 3) & ~(size_t)3;
+    const size_t pstride = (n_payload + 3) & ~(size_t)3, dos = tx_pitch(tx, n_res), esz = tx_esz(tx);
     const size_t b0_bytes = (size_t)S * nframes * SDRHIP_BLOCK_BYTES;
     int rc;
     // everything that can fail for want of memory comes first
     if ((rc = b.din.reserve((size_t)S * row))) return rc;
-    if ((rc = b.dout.reserve((size_t)S * dos * 4 + 16))) return rc;
+    if ((rc = b.dout.reserve((size_t)S * dos * esz + 16))) return rc;
     if ((rc = b.db0.reserve(b0_bytes))) return rc;
-    if ((rc = b.out.reserve((size_t)S * dos * 4 + b0_bytes))) return rc;
+    if ((rc = b.out.reserve((size_t)S * dos * esz + b0_bytes))) return rc;
     const bool gather = tx_gather_applies(tx, tx->log2interp);
     if (!gather && (rc = tx->payload[0].reserve((size_t)S * pstride * 4 + 16))) return rc;
     if (!b.done && hipEventCreateWithFlags(&b.done, hipEventDisableTiming) != hipSuccess) { b.done = nullptr; return fail(SDRHIP_EDEVICE, "hipEventCreate"); }
@@ -1198,8 +1294,8 @@ extern "C" int sdrhip_tx_submit(sdrhip_tx *tx, const uint8_t *rx, const uint8_t 
         for (int s = 0; s < S; ++s) memcpy(b.in.as<char>() + (size_t)s * row, rx + (size_t)s * rx_stride_bytes, row);
         src = b.in.as<uint8_t>(); sstride = row;
     }
-    if (S == 1) HIP_TRY(hipMemcpyAsync(b.din.p, src, row, hipMemcpyHostToDevice, c->stream));
-    else HIP_TRY(hipMemcpy2DAsync(b.din.p, row, src, sstride, row, S, hipMemcpyHostToDevice, c->stream));
+    if (S == 1) HIP_TRY(link_copy(c, b.din.p, src, row, hipMemcpyHostToDevice, c->stream));
+    else HIP_TRY(link_copy2d(c, b.din.p, row, src, sstride, row, S, hipMemcpyHostToDevice, c->stream));
     if (src != rx) b.in.mark(c->stream);
     if (gather) {
         // (the batch's received frames live in b.din until it is collected: the interpolator reads them in place)
@@ -1208,11 +1304,13 @@ extern "C" int sdrhip_tx_submit(sdrhip_tx *tx, const uint8_t *rx, const uint8_t 
         if ((rc = interpolate_device(tx->itp, tx->log2interp, nullptr, n_payload, pstride, b.dout.as<int16_t>(), dos, nullptr, &g))) return rc;
     } else {
         if ((rc = tx_decode(tx, b.din.as<uint8_t>(), indices, nframes, tx->payload[0], pstride, nullptr, b.db0.as<uint8_t>()))) return rc;
-        if ((rc = interpolate_device(tx->itp, tx->log2interp, tx->payload[0].as<int16_t>(), n_payload, pstride, b.dout.as<int16_t>(), dos, nullptr))) return rc;
+        if ((rc = interpolate_device(tx->itp, tx->log2interp, tx->payload[0].as<int16_t>(), n_payload, pstride, b.dout.as<int16_t>(), dos, nullptr,
+                                     nullptr, nullptr, tx->out_fmt)))
+            return rc;
     }
     // (from here on the interpolator's state has advanced: a failure loses the batch, it is never replayed)
-    hipError_t e = hipMemcpyAsync(b.out.p, b.dout.p, (size_t)S * dos * 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(b.out.as<char>() + (size_t)S * dos * 4, b.db0.p, b0_bytes, hipMemcpyDeviceToHost, c->stream);
+    hipError_t e = link_copy(c, b.out.p, b.dout.p, (size_t)S * dos * esz, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = link_copy(c, b.out.as<char>() + (size_t)S * dos * esz, b.db0.p, b0_bytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipEventRecord(b.done, c->stream);
     if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "tx batch download: %s (the batch's %zu frames per stream are lost)", hipGetErrorString(e), nframes);
     b.nframes = nframes; b.n_res = n_res; b.dos = dos;
@@ -1248,6 +1346,7 @@ extern "C" int sdrhip_tx_collect(sdrhip_tx *tx, int16_t *iq_out, size_t out_stri
     }
     sdrhip_tx::ABatch &b = *bp;
     const int S = tx->nstreams;
+    const size_t esz = tx_esz(tx); // (the format cannot change while a batch is in flight)
     if (b.n_res > max_samples) { // (the batch stays where it is: call again with room for *n_out samples per stream)
         *n_out = b.n_res;
         if (n_frames) *n_frames = b.nframes;
@@ -1257,9 +1356,9 @@ extern "C" int sdrhip_tx_collect(sdrhip_tx *tx, int16_t *iq_out, size_t out_stri
         if (!iq_out) return fail(SDRHIP_EINVAL, "tx_collect: NULL iq_out");
         if (S == 1) out_stride = b.n_res;
         if (out_stride < b.n_res) return fail(SDRHIP_EINVAL, "tx_collect: out_stride too small");
-        for (int s = 0; s < S; ++s) memcpy(iq_out + (size_t)s * out_stride * 2, b.out.as<char>() + (size_t)s * b.dos * 4, b.n_res * 4);
+        for (int s = 0; s < S; ++s) memcpy(reinterpret_cast<char *>(iq_out) + (size_t)s * out_stride * esz, b.out.as<char>() + (size_t)s * b.dos * esz, b.n_res * esz);
     }
-    if (block0_out) memcpy(block0_out, b.out.as<char>() + (size_t)S * b.dos * 4, (size_t)S * b.nframes * SDRHIP_BLOCK_BYTES);
+    if (block0_out) memcpy(block0_out, b.out.as<char>() + (size_t)S * b.dos * esz, (size_t)S * b.nframes * SDRHIP_BLOCK_BYTES);
     *n_out = b.n_res;
     if (n_frames) *n_frames = b.nframes;
     b.state = 0;
@@ -1306,26 +1405,30 @@ extern "C" int sdrhip_tx_process_datagrams(sdrhip_tx *tx, const uint8_t *dgrams,
     if (max_frames > 0x3fffffffu) return fail(SDRHIP_EINVAL, "tx_process_datagrams: max_frames too large");
     if (max_frames > 0 && (!iq_out || !info_out)) return fail(SDRHIP_EINVAL, "tx_process_datagrams: NULL iq_out / info_out");
     const size_t per = max_frames * SDRHIP_SAMPLES_PER_FRAME, n_res_max = per << L;
-    if (S == 1) out_stride = (n_res_max + 3) & ~(size_t)3;
+    const bool s8 = tx->out_fmt == IQF_S8;
+    const size_t esz = tx_esz(tx);
+    if (S == 1) out_stride = tx_pitch(tx, n_res_max);
     if (out_stride < n_res_max) return fail(SDRHIP_EINVAL, "tx_process_datagrams: out_stride below max_frames x 16129 << log2interp");
-    if (mem == SDRHIP_MEM_DEVICE && max_frames > 0 && (!aligned16(iq_out) || (out_stride & 3) || (reinterpret_cast<uintptr_t>(block0_out) & 3u)))
-        return fail(SDRHIP_EALIGN, "tx_process_datagrams: device iq_out must be 16-byte aligned, out_stride a multiple of 4 samples, block0_out 4-byte aligned");
+    if (mem == SDRHIP_MEM_DEVICE && max_frames > 0 && (!aligned16(iq_out) || (out_stride & (s8 ? 7 : 3)) || (reinterpret_cast<uintptr_t>(block0_out) & 3u)))
+        return fail(SDRHIP_EALIGN, "tx_process_datagrams: device iq_out must be 16-byte aligned, out_stride a multiple of 4 (8-bit: 8) samples, block0_out 4-byte aligned");
     HIP_TRY(hipSetDevice(c->device));
     int rc;
     if ((rc = tx_collector(tx))) return rc;
     if ((rc = fecbuf_check_dgrams(tx->fb, dgrams, n_dgrams, dgram_stride_bytes, mem, "tx_process_datagrams"))) return rc;
     // where the collector writes getSlotData: the caller's device iq_out (Upsampler's m_interp == 0 pass-through, Upsampler.cpp:54-57)
     // or payload[0]; host memory: outbuf / payload[0], downloaded below
-    const size_t pitch = (per + 3) & ~(size_t)3, n_res_pitch = (n_res_max + 3) & ~(size_t)3;
+    // (8-bit output with x1: the collector writes int16 to payload[0] as for the other ratios, K6n narrows it into dout)
+    const size_t pitch = (per + 3) & ~(size_t)3, n_res_pitch = tx_pitch(tx, n_res_max);
+    const bool direct = L == 0 && !s8;
     int16_t *dout = iq_out;
     size_t dos = out_stride;
     if (max_frames > 0 && mem == SDRHIP_MEM_HOST) {
-        if ((rc = tx->outbuf.reserve((size_t)S * n_res_pitch * 4 + 16))) return rc;
+        if ((rc = tx->outbuf.reserve((size_t)S * n_res_pitch * esz + 16))) return rc;
         dout = tx->outbuf.as<int16_t>(); dos = n_res_pitch;
     }
-    if (max_frames > 0 && L > 0 && (rc = tx->payload[0].reserve((size_t)S * pitch * 4 + 16))) return rc;
-    uint8_t *data = L == 0 ? reinterpret_cast<uint8_t *>(dout) : tx->payload[0].as<uint8_t>();
-    const size_t data_stride = L == 0 ? dos * 4 : pitch * 4;
+    if (max_frames > 0 && !direct && (rc = tx->payload[0].reserve((size_t)S * pitch * 4 + 16))) return rc;
+    uint8_t *data = direct ? reinterpret_cast<uint8_t *>(dout) : tx->payload[0].as<uint8_t>();
+    const size_t data_stride = direct ? dos * 4 : pitch * 4;
     const int *counts = nullptr;
     if ((rc = fecbuf_collect(tx->fb, dgrams, n_dgrams, dgram_stride_bytes, mem, max_frames ? data : nullptr, data_stride, block0_out, max_frames,
                              info_out, n_frames, &counts)))
@@ -1333,14 +1436,17 @@ extern "C" int sdrhip_tx_process_datagrams(sdrhip_tx *tx, const uint8_t *dgrams,
     size_t kmax = 0;
     for (int s = 0; s < S; ++s) kmax = n_frames[s] > kmax ? n_frames[s] : kmax;
     const size_t n_max = kmax * SDRHIP_SAMPLES_PER_FRAME;
-    if (L > 0 && kmax > 0) {
+    if (L == 0 && s8 && kmax > 0) {
+        // (x1 has no count-aware kernel: K6n narrows the largest stream's length; past a stream's own count the samples are unspecified)
+        if ((rc = interpolate_device(tx->itp, 0, tx->payload[0].as<int16_t>(), n_max, pitch, dout, dos, nullptr, nullptr, nullptr, IQF_S8))) return rc;
+    } else if (L > 0 && kmax > 0) {
         // (the collector's state has moved on: from here a failure loses the call's frames, it is never replayed)
         const InterpCount cnt = {counts + FB_K, FB_COUNTS, (int)SDRHIP_SAMPLES_PER_FRAME};
-        if ((rc = interpolate_device(tx->itp, L, tx->payload[0].as<int16_t>(), n_max, pitch, dout, dos, nullptr, nullptr, &cnt))) return rc;
+        if ((rc = interpolate_device(tx->itp, L, tx->payload[0].as<int16_t>(), n_max, pitch, dout, dos, nullptr, nullptr, &cnt, tx->out_fmt))) return rc;
     }
     if (mem == SDRHIP_MEM_HOST) {
         if (kmax > 0)
-            HIP_TRY(hipMemcpy2DAsync(iq_out, out_stride * 4, dout, dos * 4, (n_max << L) * 4, (size_t)S, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(link_copy2d(c, iq_out, out_stride * esz, dout, dos * esz, (n_max << L) * esz, (size_t)S, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     return SDRHIP_OK;

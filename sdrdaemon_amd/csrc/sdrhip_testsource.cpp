@@ -246,7 +246,7 @@ extern "C" int sdrhip_testsource_read(sdrhip_testsource *t, int16_t *iq_out, siz
         hp[s].phase0 = g.phase; hp[s].inc = g.inc; hp[s].amp = g.amp;
         g.phase += (unsigned)n * g.inc; // mod 2^32
     }
-    HIP_TRY(hipMemcpyAsync(t->par, hp, (size_t)S * sizeof(TestSourceParams), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(link_copy(c, t->par, hp, (size_t)S * sizeof(TestSourceParams), hipMemcpyHostToDevice, c->stream));
     t->pin.mark(c->stream);
     int16_t *dout = iq_out;
     size_t dstride = out_stride;
@@ -262,7 +262,7 @@ extern "C" int sdrhip_testsource_read(sdrhip_testsource *t, int16_t *iq_out, siz
     hipError_t e = launch_testsource(t->table, t->par, dout, dstride, n, S, c->stream);
     if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "testsource launch: %s", hipGetErrorString(e));
     if (mem == SDRHIP_MEM_HOST) {
-        HIP_TRY(hipMemcpy2DAsync(iq_out, out_stride * 4, dout, dstride * 4, n * 4, S, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(link_copy2d(c, iq_out, out_stride * 4, dout, dstride * 4, n * 4, S, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     return SDRHIP_OK;

@@ -8,6 +8,9 @@ reference.  Every method accepts
   * numpy int16 arrays  -> SDRHIP_MEM_HOST (staged through the GPU, synchronous), or
   * torch int16 CUDA tensors -> SDRHIP_MEM_DEVICE (zero-copy, enqueued on the context stream).
 
+The Rx / Tx pipes also take / give 8-bit IQ (RxPipe input_format "u8" = RTL-SDR offset binary as uint8, "s8" = HackRF int8;
+TxPipe output_format "s8" = HackRF int8), with the same shapes.
+
 Shapes: one stream (n, 2); a bank of S streams (S, n, 2).  There is no CPU implementation
 behind these classes: without libsdrhip.so or without a GPU they raise.
 """
@@ -26,7 +29,16 @@ except Exception:  # pragma: no cover
     torch = None
 
 
-K_DECIMATE, K_INTERPOLATE, K_FEC_ENCODE, K_FEC_DECODE = 0, 1, 2, 3
+K_DECIMATE, K_INTERPOLATE, K_FEC_ENCODE, K_FEC_DECODE, K_CONVERT = 0, 1, 2, 3, 4
+
+# IQ sample formats (SDRHIP_IQ_*): code and element dtype
+_IQ_FORMATS = {"s16": (0, np.int16), "u8": (1, np.uint8), "s8": (2, np.int8)}
+
+
+def _iq_format(fmt, allowed):
+    if fmt not in allowed:
+        raise ValueError("IQ format must be one of %s, not %r" % (", ".join(allowed), fmt))
+    return _IQ_FORMATS[fmt]
 
 
 def _is_torch(x):
@@ -88,8 +100,9 @@ class Context:
             self.lib.sdrhip_host_free(self.h, C.c_void_p(p))
 
     def counter(self, key):
-        """device-side event counters (sdrhip_ctx_get_counter; synchronises): "dec_rows_exceeded" = frames the batched decoder
-        left unrepaired because they carried more recovery blocks than the dec_max_rows option promises"""
+        """event counters (sdrhip_ctx_get_counter): "dec_rows_exceeded" = frames the batched decoder left unrepaired because they
+        carried more recovery blocks than the dec_max_rows option promises (device-side: synchronises); "h2d_bytes" / "d2h_bytes" =
+        bytes the context's calls copied across the host link since it was created (host-side: no synchronisation)"""
         v = C.c_uint64(0)
         check(self.lib.sdrhip_ctx_get_counter(self.h, str(key).encode(), C.byref(v)))
         return v.value
@@ -123,12 +136,19 @@ class Context:
             pass
 
 
-def _bank_view(iq, nstreams):
-    """-> (array (S, n, 2) contiguous-per-stream, is_torch, squeeze)"""
+def _bank_view(iq, nstreams, dtype=np.int16):
+    """-> (array (S, n, 2) contiguous-per-stream, is_torch, squeeze).  dtype: the element type the call takes (np.int16, or for
+    8-bit IQ np.uint8 / np.int8, which may also come flat interleaved: (2n,) or (S, 2n))"""
     squeeze = False
+    eight = dtype != np.int16
     if _is_torch(iq):
-        if iq.dtype != torch.int16 or not iq.is_cuda:
-            raise TypeError("torch input must be an int16 CUDA tensor")
+        tdt = {np.int16: torch.int16, np.uint8: torch.uint8, np.int8: torch.int8}[dtype]
+        if iq.dtype != tdt or not iq.is_cuda:
+            raise TypeError("torch input must be a %s CUDA tensor" % str(tdt).replace("torch.", ""))
+        if eight and iq.dim() == 1:
+            iq = iq.reshape(-1, 2)
+        elif eight and iq.dim() == 2 and iq.shape[1] != 2:
+            iq = iq.reshape(iq.shape[0], -1, 2)
         if iq.dim() == 2:
             iq, squeeze = iq.unsqueeze(0), True
         if iq.dim() != 3 or iq.shape[2] != 2 or iq.shape[0] != nstreams:
@@ -137,8 +157,12 @@ def _bank_view(iq, nstreams):
             iq = iq.contiguous()
         return iq, True, squeeze
     a = np.asarray(iq)
-    if a.dtype != np.int16:
-        raise TypeError("numpy input must be int16")
+    if a.dtype != dtype:
+        raise TypeError("numpy input must be %s" % np.dtype(dtype).name)
+    if eight and a.ndim == 1:
+        a = a.reshape(-1, 2)
+    elif eight and a.ndim == 2 and a.shape[1] != 2:
+        a = a.reshape(a.shape[0], -1, 2)
     if a.ndim == 2:
         a, squeeze = a[None], True
     if a.ndim != 3 or a.shape[2] != 2 or a.shape[0] != nstreams:
@@ -151,7 +175,7 @@ def _ptr(x):
 
 
 def _stride_samples(x):
-    return (x.stride(0) // 2) if _is_torch(x) else (x.strides[0] // 4)
+    return (x.stride(0) // 2) if _is_torch(x) else (x.strides[0] // (2 * x.itemsize))
 
 
 def _alloc_like(x, shape, dtype_np=np.int16):
@@ -473,9 +497,10 @@ class RxPipe:
     """Downsampler -> UDPSinkFEC framing -> CM256 encode for a bank of streams (sdrhip_rx)."""
 
     def __init__(self, ctx, nstreams=1, log2decim=4, fcpos=FC_CEN, hb_variant=HB_EO1, sample_bits=16, nb_fec=32,
-                 center_frequency_khz=435000, sample_rate=625000, pipelined=False):
+                 center_frequency_khz=435000, sample_rate=625000, pipelined=False, input_format="s16"):
         """pipelined: a process() call returns the frames the PREVIOUS call completed (their recovery blocks are computed inside
-        this call's decimator launch, sdrhip_rx_set_pipelined); flush() / flush_view() return the last call's at the end."""
+        this call's decimator launch, sdrhip_rx_set_pipelined); flush() / flush_view() return the last call's at the end.
+        input_format: "s16" (int16 IQ), "u8" (RTL-SDR uint8 offset binary) or "s8" (HackRF int8), see set_input_format."""
         self.ctx, self.nstreams, self.nb_fec = ctx, nstreams, nb_fec
         self.cfg = RxConfig(log2decim, fcpos, hb_variant, sample_bits, nb_fec, center_frequency_khz, sample_rate)
         self.h = C.c_void_p()
@@ -485,6 +510,27 @@ class RxPipe:
         self.pipelined = bool(pipelined)
         if pipelined:
             check(ctx.lib.sdrhip_rx_set_pipelined(self.h, 1))
+        self.input_format, self._in_dtype = "s16", np.int16
+        if input_format != "s16":
+            self.set_input_format(input_format)
+
+    def set_input_format(self, fmt):
+        """"s16" | "u8" | "s8" for every later process() / submit() (sdrhip_rx_set_input_format): 8-bit input crosses the host link
+        as bytes and is widened on the GPU.  Refused (SdrHipError) while async batches are filling or in flight or pipelined frames
+        wait for delivery."""
+        code, dt = _iq_format(fmt, ("s16", "u8", "s8"))
+        check(self.ctx.lib.sdrhip_rx_set_input_format(self.h, code))
+        self.input_format, self._in_dtype = fmt, dt
+
+    def _input(self, iq):
+        """the (S, n, 2) view of a process() input; 8-bit device rows padded to a multiple of 8 samples (the library's stride rule)"""
+        x, is_t, squeeze = _bank_view(iq, self.nstreams, self._in_dtype)
+        if is_t and self._in_dtype != np.int16 and x.shape[0] > 1 and (x.stride(0) // 2) % 8:
+            n = x.shape[1]
+            buf = torch.empty((x.shape[0], (n + 7) & ~7, 2), dtype=x.dtype, device=x.device)
+            buf[:, :n].copy_(x)
+            x = buf[:, :n]
+        return x, is_t, squeeze
 
     def error(self):
         e, self.m_error = self.m_error, ""
@@ -574,10 +620,12 @@ class RxPipe:
         if _is_torch(iq):
             raise TypeError("submit takes host memory")
         a = np.asarray(iq)
-        if a.ndim == 3 and a.dtype == np.int16 and a.shape[0] == self.nstreams and a.shape[2] == 2 and a.strides[2] == 2 and a.strides[1] == 4 and a.strides[0] % 4 == 0:
+        it = np.dtype(self._in_dtype).itemsize
+        if (a.ndim == 3 and a.dtype == self._in_dtype and a.shape[0] == self.nstreams and a.shape[2] == 2 and a.strides[2] == it
+                and a.strides[1] == 2 * it and a.strides[0] % (2 * it) == 0):
             x = a  # rows of a bigger array (e.g. a pinned buffer): passed in place with their stride
         else:
-            x, _, _ = _bank_view(iq, self.nstreams)
+            x, _, _ = _bank_view(iq, self.nstreams, self._in_dtype)
         if not hasattr(self, "_async_batches"):  # (sdrhip_rx_submit's default ring: 4 batches of one block)
             self._async_blocks, self._async_batches, self._async_fill, self._async_last = 1, [], [0, 0], 0
         check(self.ctx.lib.sdrhip_rx_submit(self.h, _ptr(x), x.shape[1], _stride_samples(x), tv_sec, tv_usec))
@@ -616,7 +664,7 @@ class RxPipe:
 
     def process(self, iq, tv_sec=0, tv_usec=0, out=None):
         """-> frames (S, n_frames, 128 + nb_fec, 512) uint8 (squeezed for one stream)"""
-        x, is_t, squeeze = _bank_view(iq, self.nstreams)
+        x, is_t, squeeze = self._input(iq)
         S, n = x.shape[0], x.shape[1]
         cap = max(self.max_frames(n), 1)
         fb = (NB_ORIGINAL + self.nb_fec) * UDPSIZE
@@ -635,7 +683,7 @@ class RxPipe:
     def process_view(self, iq, tv_sec=0, tv_usec=0):
         """Zero-copy variant for CUDA tensors: the finished frames stay in the library's frame area.
         -> uint8 CUDA tensor view (S, n_frames, 128 + nb_fec, 512), valid until the next process call."""
-        x, is_t, squeeze = _bank_view(iq, self.nstreams)
+        x, is_t, squeeze = self._input(iq)
         if not is_t:
             raise TypeError("process_view needs a CUDA tensor")
         S, n = x.shape[0], x.shape[1]
@@ -662,7 +710,8 @@ class TxPipe:
     (sdrhip_tx_set_pipelined); flush() returns the last batch's at the end.  A device-memory rx batch must stay untouched until
     the next process() / flush() has returned."""
 
-    def __init__(self, ctx, nstreams=1, log2interp=4, pipelined=False):
+    def __init__(self, ctx, nstreams=1, log2interp=4, pipelined=False, output_format="s16"):
+        """output_format: "s16" (int16 IQ) or "s8" (HackRF int8), see set_output_format"""
         self.ctx, self.nstreams, self.log2interp = ctx, nstreams, log2interp
         self.h = C.c_void_p()
         self.m_error = ""
@@ -670,6 +719,25 @@ class TxPipe:
         check(ctx.lib.sdrhip_tx_create(ctx.h, nstreams, log2interp, C.byref(self.h)))
         if pipelined:
             check(ctx.lib.sdrhip_tx_set_pipelined(self.h, 1))
+        self.output_format, self._out_dtype = "s16", np.int16
+        if output_format != "s16":
+            self.set_output_format(output_format)
+
+    def set_output_format(self, fmt):
+        """"s16" | "s8" for every later process() / flush() / collect() / process_datagrams() (sdrhip_tx_set_output_format): with
+        "s8" the samples come back as int8 (v >> 8 of each component, narrowed on the GPU).  Refused (SdrHipError) while async
+        batches are in flight or a pipelined batch waits."""
+        code, dt = _iq_format(fmt, ("s16", "s8"))
+        check(self.ctx.lib.sdrhip_tx_set_output_format(self.h, code))
+        self.output_format, self._out_dtype = fmt, dt
+
+    def _out(self, S, n_res, device=None):
+        """output buffer of (S, pitch, 2) samples: rows of a multiple of 4 (int16) / 8 (int8) samples, the library's stride rule"""
+        if self._out_dtype == np.int16:
+            pad = max((n_res + 3) & ~3, 4)
+            return (torch.empty((S, pad, 2), dtype=torch.int16, device=device) if device is not None else np.empty((S, pad, 2), np.int16)), pad
+        pad = max((n_res + 7) & ~7, 8)
+        return (torch.empty((S, pad, 2), dtype=torch.int8, device=device) if device is not None else np.empty((S, pad, 2), np.int8)), pad
 
     def configure(self, m):
         """The `interp` key of a control message (Upsampler::configure, Upsampler.cpp:31-50) between two batches;
@@ -703,8 +771,7 @@ class TxPipe:
         n_res = (F * SAMPLES_PER_FRAME) << self.log2interp
         if self.pipelined:  # (the call delivers the batch the PREVIOUS call decoded)
             n_res = self.ctx.lib.sdrhip_tx_pending_samples(self.h)
-        pad = max((n_res + 3) & ~3, 4)
-        out = (torch.empty((S, pad, 2), dtype=torch.int16, device=rx.device) if is_t else np.empty((S, pad, 2), np.int16))
+        out, pad = self._out(S, n_res, rx.device if is_t else None)
         n_out = C.c_size_t(0)
         check(self.ctx.lib.sdrhip_tx_process(self.h, _ptr(rx), C.c_void_p(indices.ctypes.data if indices is not None else 0), F, F * NB_ORIGINAL * UDPSIZE,
                                              _ptr(out), pad, C.byref(n_out), MEM_DEVICE if is_t else MEM_HOST))
@@ -741,7 +808,7 @@ class TxPipe:
         pend = getattr(self, "_async_frames", [])
         F, L = pend[0] if pend else (0, self.log2interp)
         cap = max((F * SAMPLES_PER_FRAME) << L, 4)
-        out = np.empty((self.nstreams, cap, 2), np.int16)
+        out = np.empty((self.nstreams, cap, 2), self._out_dtype)
         b0 = np.empty((self.nstreams, max(F, 1), BLOCK_BYTES), np.uint8)
         n_out, nf = C.c_size_t(0), C.c_size_t(0)
         rc = self.ctx.lib.sdrhip_tx_collect(self.h, _ptr(out), cap, cap, _ptr(b0) if block0 else C.c_void_p(0), C.byref(n_out), C.byref(nf), 1 if wait else 0)
@@ -757,8 +824,7 @@ class TxPipe:
         waits.  device: a torch device for a device-memory result, None for numpy"""
         S = self.nstreams
         n_res = self.ctx.lib.sdrhip_tx_pending_samples(self.h)
-        pad = max((n_res + 3) & ~3, 4)
-        out = torch.empty((S, pad, 2), dtype=torch.int16, device=device) if device is not None else np.empty((S, pad, 2), np.int16)
+        out, pad = self._out(S, n_res, device)
         n_out = C.c_size_t(0)
         check(self.ctx.lib.sdrhip_tx_flush(self.h, _ptr(out), pad, C.byref(n_out), MEM_DEVICE if device is not None else MEM_HOST))
         return out[:, :n_out.value]
@@ -776,12 +842,10 @@ class TxPipe:
             max_frames = max(counts + [0])  # (a call releases at most one frame per datagram)
         F = max(max_frames, 1)
         n_cap = (F * SAMPLES_PER_FRAME) << self.log2interp
-        pad = (n_cap + 3) & ~3
+        out, pad = self._out(S, n_cap, buf.device if is_t else None)
         if is_t:
-            out = torch.empty((S, pad, 2), dtype=torch.int16, device=buf.device)
             b0 = torch.empty((S, F, BLOCK_BYTES), dtype=torch.uint8, device=buf.device)
         else:
-            out = np.empty((S, pad, 2), np.int16)
             b0 = np.empty((S, F, BLOCK_BYTES), np.uint8)
         info = (FECBufferFrame * (S * F))()
         nd = (C.c_size_t * S)(*counts)
