@@ -152,6 +152,17 @@ int sdrhip_decimators_last_plan(const sdrhip_decimators *d, sdrhip_decim_plan *o
  * remainder never enters the filter history. */
 int sdrhip_decimate(sdrhip_decimators *d, int log2decim, int fcpos, unsigned *sampleSize, const int16_t *iq_in,
                     size_t n_in, size_t in_stride, int16_t *iq_out, size_t out_stride, size_t *n_out, int mem);
+/* Decimators bank, ragged: stream s consumes n_in[s] samples (remainder below 2^log2decim dropped per stream, as
+ * sdrhip_decimate drops it for all); n_out[s] = n_in[s] >> log2decim. in_stride / out_stride >= the largest count.
+ * n_in and n_out are host arrays of nstreams entries.  A stream with n_in[s] < 2^log2decim keeps its filter history as it was.
+ * Host memory: only n_in[s] samples of row s are read and n_out[s] written.  Device memory: the alignment rules of
+ * sdrhip_decimate; the kernels read no sample of stream s past n_in[s] (the last row may be exactly n_in[nstreams - 1] long).
+ * One launch serves every stream, chosen as for sdrhip_decimate (context option decim_path, mfma_min of the call's total samples):
+ * the matrix-core cascade with per-stream wave groups and pieces (sdrhip_decimators_last_plan: path 2, span / head shared, wps /
+ * npieces = the launch's totals) or the VALU cascade with a per-call work table (path 1, nseg = the launch's workgroups).
+ * *sampleSize advances as in sdrhip_decimate. */
+int sdrhip_decimate_ragged(sdrhip_decimators *d, int log2decim, int fcpos, unsigned *sampleSize, const int16_t *iq_in,
+                           const size_t *n_in, size_t in_stride, int16_t *iq_out, size_t out_stride, size_t *n_out, int mem);
 
 /* ------------------------------------------------------------ interpolators -- */
 /* Bank of `Interpolators` objects (Interpolators.h:35-61): HB64, HB32, 4 x HB16 states. */
@@ -308,6 +319,30 @@ int sdrhip_rx_last_plan(const sdrhip_rx *rx, sdrhip_decim_plan *out);
  * base + s * stream_stride_bytes (device memory, frame after frame).  The view stays valid until
  * the next sdrhip_rx_process / sdrhip_rx_destroy on this handle. */
 int sdrhip_rx_frames_view(const sdrhip_rx *rx, const uint8_t **base, size_t *stream_stride_bytes, size_t *n_frames);
+
+/* Rx pipe, ragged: stream s takes n_in[s] device-rate samples whose first sample was taken at tv_sec[s] / tv_usec[s];
+ * n_frames[s] = frames stream s completed; they land at frames_out + s * frame_stride_bytes as today.
+ * n_in, tv_sec, tv_usec and n_frames are host arrays of nstreams entries.  Per stream the result is byte for byte what a one-stream
+ * sdrhip_rx with the same config produces when it is fed stream s's samples with stream s's stamps, call after call: frames,
+ * recovery blocks, meta blocks and frameIndex (each stream's m_frameCount wraps on its own).  A stream with n_in[s] below
+ * 2^log2decim keeps its filter history, open frame and frame counter.  Input: as sdrhip_rx_process (host memory: only n_in[s]
+ * samples of row s are read; device memory: its alignment rules, no sample past n_in[s] is read; sdrhip_rx_set_input_format
+ * applies).  frame_stride_bytes >= (largest n_frames) * (128 + nb_fec) * 512 when frames_out is given.  Once ragged calls leave the
+ * streams at different frame positions: sdrhip_rx_process runs as a ragged call with equal counts and stamps (its *n_frames = the
+ * largest per-stream count), sdrhip_rx_max_frames returns the maximum over the streams, sdrhip_rx_frames_view returns SDRHIP_EINVAL
+ * while the delivered windows differ, sdrhip_rx_reconfigure moves each stream's open frame (the old-meta / new-fecblk rule applies per
+ * stream), and sdrhip_rx_set_pipelined(on) / sdrhip_rx_submit return SDRHIP_EINVAL.  The decimator launch is chosen as for
+ * sdrhip_decimate_ragged; on the matrix cores it stores straight into each stream's frame window (context option rx_direct, the
+ * default; 0: stream order and a framing pass).  Refused with SDRHIP_EINVAL, nothing consumed (the next call continues
+ * as if the refused one never happened): a NULL count, stamp or n_frames array, in_stride below the largest count, a frame stride
+ * too small for the stream with the most frames, pipelined mode, asynchronous batches being filled or in flight. */
+int sdrhip_rx_process_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, size_t in_stride,
+                             const uint32_t *tv_sec, const uint32_t *tv_usec, uint8_t *frames_out,
+                             size_t frame_stride_bytes, size_t *n_frames, int mem);
+/* zero-copy view after a ragged call: stream s's n_frames[s] frames start at base + s * stride + first_slot[s] * frame bytes
+ * (first_slot and n_frames: host arrays of nstreams entries; valid until the next data call on the handle) */
+int sdrhip_rx_frames_view_ragged(const sdrhip_rx *rx, const uint8_t **base, size_t *stream_stride_bytes,
+                                 size_t *first_slot, size_t *n_frames);
 
 /* Asynchronous host-pointer entry.  The reference's Rx chain is asynchronous end to end (source thread -> source_buffer ->
  * Downsampler::process -> output_buffer -> writer -> transmit thread, sdrdaemonrx.cpp:555-663): the frames of a block leave the

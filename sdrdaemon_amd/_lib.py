@@ -35,6 +35,7 @@ EXPORTS = [
     "sdrhip_fecbuf_create", "sdrhip_fecbuf_destroy", "sdrhip_fecbuf_reset", "sdrhip_fecbuf_write_and_read", "sdrhip_fecbuf_stats",
     "sdrhip_tx_process_datagrams", "sdrhip_tx_collector",
     "sdrhip_rx_set_input_format", "sdrhip_tx_set_output_format",
+    "sdrhip_decimate_ragged", "sdrhip_rx_process_ragged", "sdrhip_rx_frames_view_ragged",
 ]
 
 
@@ -135,6 +136,10 @@ def load():
     lib.sdrhip_tx_collector.argtypes = [vp, C.POINTER(vp)]
     lib.sdrhip_rx_set_input_format.argtypes = [vp, i]
     lib.sdrhip_tx_set_output_format.argtypes = [vp, i]
+    lib.sdrhip_decimate_ragged.argtypes = [vp, i, i, C.POINTER(u), vp, C.POINTER(sz), sz, vp, sz, C.POINTER(sz), i]
+    lib.sdrhip_rx_process_ragged.argtypes = [vp, vp, C.POINTER(sz), sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp, sz,
+                                             C.POINTER(sz), i]
+    lib.sdrhip_rx_frames_view_ragged.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     lib.sdrhip_testsource_create.argtypes = [vp, i, C.POINTER(vp)]
     lib.sdrhip_testsource_destroy.argtypes = [vp]
     lib.sdrhip_testsource_destroy.restype = None

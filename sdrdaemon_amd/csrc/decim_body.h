@@ -446,5 +446,47 @@ template <int L, int FC, bool PACK16> struct DecimLds {
     static_assert(dwords * 4 <= 64 * 1024, "LDS budget");
 };
 
+// filter-less variants (decimate1, decimate2 / 4 inf / sup), one row: n_in samples of `stream`; one thread per group of four inputs.
+// The ragged kernel's body (rx_ragged_kernels.hip); decim_kernels.hip's uniform decim_simple_kernel keeps its own copy of these lines,
+// so that its instructions stay as they were.
+__device__ __forceinline__ void decim_simple_row(int log2decim, int fcpos, const int16_t *in, size_t in_stride, int16_t *out,
+                                                 size_t out_stride, size_t n_in, int norm, int trunk, int stream)
+{
+    const unsigned *src = reinterpret_cast<const unsigned *>(in) + (size_t)stream * in_stride;
+    unsigned *dst = reinterpret_cast<unsigned *>(out) + (size_t)stream * out_stride;
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (log2decim == 0) {
+        for (size_t i = g; i < n_in; i += (size_t)gridDim.x * blockDim.x) {
+            unsigned v = SDRHIP_STREAM_LOAD(src + i);
+            int a = (short)(v & 0xffff), b = (int)v >> 16;
+            dst[i] = (((unsigned)a << norm) & 0xffffu) | (((unsigned)b << norm) << 16);
+        }
+        return;
+    }
+    const size_t n_resize = n_in >> log2decim;
+    const size_t ngroups = n_in / 4;
+    for (size_t q = g; q < (n_in + 3) / 4; q += (size_t)gridDim.x * blockDim.x) {
+        if (q >= ngroups) { // out.resize() elements the loop never writes stay zero (fresh vector)
+            if (log2decim == 1 && 2 * q < n_resize) dst[2 * q] = 0;
+            continue;
+        }
+        const unsigned v0 = SDRHIP_STREAM_LOAD(src + 4 * q), v1 = SDRHIP_STREAM_LOAD(src + 4 * q + 1), v2 = SDRHIP_STREAM_LOAD(src + 4 * q + 2), v3 = SDRHIP_STREAM_LOAD(src + 4 * q + 3);
+        const int I0 = (short)(v0 & 0xffff), Q0 = (int)v0 >> 16, I1 = (short)(v1 & 0xffff), Q1 = (int)v1 >> 16;
+        const int I2 = (short)(v2 & 0xffff), Q2 = (int)v2 >> 16, I3 = (short)(v3 & 0xffff), Q3 = (int)v3 >> 16;
+        if (log2decim == 1) {
+            int xa, ya, xb, yb;
+            if (fcpos == 0) { xa = I0 - Q1; ya = Q0 + I1; xb = Q3 - I2; yb = -Q2 - I3; }
+            else { xa = Q0 - I1; ya = -I0 - Q1; xb = I3 - Q2; yb = I2 + Q3; }
+            dst[2 * q] = final_pack(xa, ya, norm, trunk);
+            dst[2 * q + 1] = final_pack(xb, yb, norm, trunk);
+        } else {
+            int x, y;
+            if (fcpos == 0) { x = I0 - Q1 + Q3 - I2; y = Q0 - Q2 + I1 - I3; }
+            else { x = Q0 - I1 - Q2 + I3; y = -I0 - Q1 + I2 + Q3; }
+            dst[q] = final_pack(x, y, norm, trunk);
+        }
+    }
+}
+
 } // namespace
 } // namespace sdrhip

@@ -633,6 +633,75 @@ template <int L, bool PACK16, int NG, bool FR> __global__ __launch_bounds__(mf_b
     mf_wave<L, NG, FR>(a, gw, (unsigned)(size_t)(__attribute__((address_space(3))) char *)lds);
     MF_STAMP(gw, 7);
 }
+// K1mr: the same launch for a ragged call (sdrhip_rx_process_ragged, sdrhip_decimate_ragged).  The streams share the span, the head and
+// the piece length; each has its own count of wave groups and pieces, dealt through prefix sums of the per-call table (RaggedRow
+// mf_w0 / mf_p0: a binary search per workgroup).  a.mf_wps = the launch's matrix-core waves, a.mf_npieces = its pieces.  In frame
+// mode each stream stores into its own window (RaggedRow out_off) with its own frame base and meta record.
+__device__ __forceinline__ int mf_ragged_find(const RaggedRow *rows, int nstreams, int x, bool waves)
+{
+    // the last stream whose first wave (piece) is <= x: streams without waves share their first index with the next one
+    int lo = 0, hi = nstreams - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if ((waves ? rows[mid].mf_w0 : rows[mid].mf_p0) <= x) lo = mid;
+        else hi = mid - 1;
+    }
+    return __builtin_amdgcn_readfirstlane(lo); // (workgroup-uniform: keeps the row's fields in scalar registers)
+}
+// the stream's view of the launch's arguments: its own window, frame base and meta record (frame mode), its wave count
+__device__ __forceinline__ DecimArgs mf_ragged_args(const DecimArgs &a, const RaggedRow &r)
+{
+    DecimArgs b = a;
+    b.n_used = (size_t)r.n_used;
+    b.mf_wps = r.mf_wps;
+    if (a.frame_mode) {
+        b.out = reinterpret_cast<int16_t *>(reinterpret_cast<unsigned *>(a.out) + r.out_off);
+        b.frame_sample_base = r.frame_sample_base;
+        b.meta_first = r.meta_first; b.meta_count = r.meta_count; b.meta_frame_count0 = r.frame_count0;
+        b.meta_w[3] = r.tv_sec; b.meta_w[4] = r.tv_usec;
+        b.meta_idx0 = r.meta_idx0;
+    }
+    return b;
+}
+
+template <int L, bool PACK16, int NG, bool FR> __global__ __launch_bounds__(mf_block_threads(L), mf_dma_applies(L) && NG != 2 ? 1 : MF_WAVES) void decim_mfma_ragged_kernel(DecimArgs a, const RaggedRow *rows)
+{
+    constexpr int LDSDW = mf_dma_applies(L) && mf_wave_ring(NG) > DecimLds<L, 2, PACK16>::dwords ? mf_wave_ring(NG) : DecimLds<L, 2, PACK16>::dwords;
+    __shared__ __attribute__((aligned(16))) int lds[LDSDW];
+    const int nmf = (a.mf_wps + 3) / 4;
+    const int bx = blockIdx.x;
+    if (bx >= nmf) { // VALU pieces, dealt as in decim_mfma_kernel (early workgroups take mf_piece_share pieces each)
+        const int nitems = a.mf_npieces, j = bx - nmf, nearly = a.mf_piece_early * a.mf_piece_share;
+        const int nmine = j < a.mf_piece_early ? a.mf_piece_share : 1;
+        for (int k = 0; k < nmine; ++k) {
+            const int lx = j < a.mf_piece_early ? j + k * a.mf_piece_early : nearly + (j - a.mf_piece_early);
+            if (lx >= nitems || (j < a.mf_piece_early && lx >= nearly)) break; // (workgroup-uniform)
+            const int stream = mf_ragged_find(rows, a.nstreams, lx, false);
+            const RaggedRow &r = rows[stream];
+            const DecimArgs b = mf_ragged_args(a, r);
+            const int piece = lx - r.mf_p0;
+            const size_t n_used = (size_t)r.n_used;
+            if (piece == 0) {
+                decim_piece<L, 2, PACK16>(b, lds, stream, 0, (size_t)r.mf_head, true, r.mf_np == 1, piece, r.mf_np);
+            } else {
+                const size_t s0 = (size_t)r.mf_tail_start + (size_t)(piece - 1) * a.mf_tail_seg;
+                size_t s1 = s0 + a.mf_tail_seg;
+                if (s1 > n_used || piece == r.mf_np - 1) s1 = n_used;
+                decim_piece<L, 2, PACK16>(b, lds, stream, s0, s1, false, piece == r.mf_np - 1, piece, r.mf_np);
+            }
+            __syncthreads(); // (the next piece reuses the stage buffers)
+        }
+        return;
+    }
+    const int gw = __builtin_amdgcn_readfirstlane(bx * 4 + (int)(threadIdx.x >> 6));
+    if (gw >= a.mf_wps) return;
+    const int stream = mf_ragged_find(rows, a.nstreams, gw, true);
+    const RaggedRow &r = rows[stream];
+    const DecimArgs b = mf_ragged_args(a, r);
+    // mf_wave finds its stream as gw / mf_wps: hand it the stream's own numbering
+    mf_wave<L, NG, FR>(b, stream * r.mf_wps + (gw - r.mf_w0), (unsigned)(size_t)(__attribute__((address_space(3))) char *)lds);
+}
+
 #ifdef MF_STAMPS
 } // namespace
 extern "C" int sdrhip_debug_mf_stamps(unsigned long long *dst) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_mf_stamps), sizeof(g_mf_stamps)); }
@@ -746,6 +815,28 @@ template <int L> hipError_t launch_mf(bool pack16, const DecimArgs &a, hipStream
     }
     if (a.frame_mode) launch_mf2<L, 4, true>(pack16, a, grid, block, stream);
     else launch_mf2<L, 4, false>(pack16, a, grid, block, stream);
+    return hipGetLastError();
+}
+
+template <int L, int NG, bool FR> void launch_mfr2(bool pack16, const DecimArgs &a, const RaggedRow *rows, dim3 grid, dim3 block, hipStream_t stream)
+{
+    if (pack16) hipLaunchKernelGGL((decim_mfma_ragged_kernel<L, true, NG, FR>), grid, block, 0, stream, a, rows);
+    else hipLaunchKernelGGL((decim_mfma_ragged_kernel<L, false, NG, FR>), grid, block, 0, stream, a, rows);
+}
+
+template <int L> hipError_t launch_mfr(bool pack16, const DecimArgs &a, const RaggedRow *rows, hipStream_t stream)
+{
+    const int nmf = (a.mf_wps + 3) / 4;
+    const dim3 grid(a.mf_piece_wgs + nmf), block(mf_block_threads(L));
+    if constexpr (mf_dma_applies(L)) {
+        if (a.mf_ring == 3) {
+            if (a.frame_mode) launch_mfr2<L, 3, true>(pack16, a, rows, grid, block, stream);
+            else launch_mfr2<L, 3, false>(pack16, a, rows, grid, block, stream);
+            return hipGetLastError();
+        }
+    }
+    if (a.frame_mode) launch_mfr2<L, 4, true>(pack16, a, rows, grid, block, stream);
+    else launch_mfr2<L, 4, false>(pack16, a, rows, grid, block, stream);
     return hipGetLastError();
 }
 
@@ -865,6 +956,68 @@ hipError_t launch_decimate_mfma(int log2decim, bool pack16, const DecimArgs &a, 
     case 4: return launch_mf<4>(pack16, a, stream);
     case 5: return launch_mf<5>(pack16, a, stream);
     case 6: return launch_mf<6>(pack16, a, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+bool plan_decimate_mfma_ragged(int log2decim, int fcpos, RaggedRow *rows, int nstreams, size_t span_override, int n_cu, DecimArgs *a)
+{
+    // the span and head the uniform planner picks for the mean stream: equal counts get the uniform launch's geometry
+    size_t total = 0;
+    for (int s = 0; s < nstreams; ++s) total += (size_t)rows[s].n_used;
+    const int L = log2decim;
+    const size_t mean = total / (size_t)nstreams / ((size_t)1 << L) * ((size_t)1 << L);
+    DecimArgs u = *a;
+    if (!plan_decimate_mfma(L, fcpos, mean, nstreams, span_override, n_cu, &u)) return false;
+    const size_t S = u.mf_span, head = u.mf_head, seg = u.mf_tail_seg;
+    long long waves = 0, pieces = 0;
+    for (int s = 0; s < nstreams; ++s) {
+        RaggedRow &r = rows[s];
+        const size_t n = (size_t)r.n_used;
+        size_t wps = n > head ? (n - head) / (8 * S) : 0;
+        size_t tail_start = head + wps * 8 * S;
+        if (wps && n - tail_start < 256u) { --wps; tail_start = head + wps * 8 * S; } // (the register ring reads 256 samples ahead)
+        size_t h = head;
+        if (!wps) { h = n < seg ? n : seg; tail_start = h; } // (no span: pieces alone, the first one from the state)
+        const size_t tail = n - tail_start;
+        const size_t np = 1 + (tail + seg - 1) / seg;
+        r.mf_w0 = (int)waves; r.mf_wps = (int)wps;
+        r.mf_p0 = (int)pieces; r.mf_np = (int)np;
+        r.mf_head = h; r.mf_tail_start = tail_start;
+        waves += (long long)wps;
+        pieces += (long long)np;
+        if (waves > 0x7fffffff || pieces > 0x7fffffff) return false;
+    }
+    if (waves == 0) return false;
+    a->mf_head = head; a->mf_span = S; a->mf_tail_seg = seg; a->mf_tail_start = 0;
+    a->mf_wps = (int)waves; a->mf_npieces = (int)pieces;
+    {
+        // the piece workgroups, as plan_decimate_mfma deals them
+        const int items = (int)pieces, nmf = (int)((waves + 3) / 4);
+        const size_t W = (size_t)64 << L;
+        a->mf_piece_early = 0; a->mf_piece_share = 0;
+        if (mf_dma_applies(L) && n_cu > nmf) {
+            int early = n_cu - nmf;
+            if (early > items) early = items;
+            int share = (int)((W + S) / 6720);
+            if (share < 3) share = 3;
+            if (share > (items + early - 1) / early) share = (items + early - 1) / early;
+            a->mf_piece_early = early; a->mf_piece_share = share;
+        }
+        const int rest = items - a->mf_piece_early * a->mf_piece_share;
+        a->mf_piece_wgs = a->mf_piece_early + (rest > 0 ? rest : 0);
+    }
+    return true;
+}
+
+hipError_t launch_decimate_mfma_ragged(int log2decim, bool pack16, const DecimArgs &a, const RaggedRow *rows, hipStream_t stream)
+{
+    switch (log2decim) {
+    case 2: return launch_mfr<2>(pack16, a, rows, stream);
+    case 3: return launch_mfr<3>(pack16, a, rows, stream);
+    case 4: return launch_mfr<4>(pack16, a, rows, stream);
+    case 5: return launch_mfr<5>(pack16, a, rows, stream);
+    case 6: return launch_mfr<6>(pack16, a, rows, stream);
     }
     return hipErrorInvalidValue;
 }

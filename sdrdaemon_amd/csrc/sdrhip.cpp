@@ -353,6 +353,12 @@ struct sdrhip_decimators {
     int cur;
     bool stage0_int16; // history of m_decimator2 fits int16 (it last saw raw samples or nothing)
     sdrhip::DecimPlanInfo last; // what the last call launched
+    // ragged calls: the per-call table (host staging, device copy), K1r's segment length and grid, staging of host rows
+    sdrhip::PinnedBuf rows_pin, stage_pin, out_pin;
+    sdrhip::DevBuf rows_dev;
+    int r_nsub = 0, r_grid = 0;
+    bool r_mfma = false;     // the last ragged_prepare planned the matrix-core launch (K1mr), r_mf holds its shared fields
+    sdrhip::DecimArgs r_mf;
 };
 
 extern "C" int sdrhip_decimators_last_plan(const sdrhip_decimators *d, sdrhip_decim_plan *out)
@@ -392,6 +398,7 @@ extern "C" void sdrhip_decimators_destroy(sdrhip_decimators *d)
     (void)hipStreamSynchronize(d->ctx->stream);
     (void)hipFree(d->state[0]);
     (void)hipFree(d->state[1]);
+    d->rows_pin.release(); d->stage_pin.release(); d->out_pin.release(); d->rows_dev.release();
     ctx_release(d->ctx);
     delete d;
 }
@@ -582,5 +589,198 @@ extern "C" int sdrhip_decimate(sdrhip_decimators *d, int log2decim, int fcpos, u
     if (rc) return rc;
     if (n_res) HIP_TRY(link_copy2d(c, iq_out, out_stride * 4, c->out.p, dos * 4, n_res * 4, S, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return SDRHIP_OK;
+}
+
+// ------------------------------------------------------------------------------ ragged decimator calls
+namespace sdrhip {
+int ragged_prepare(sdrhip_decimators *d, int log2decim, int fcpos, const size_t *n_in, RaggedRow *rows, const RaggedRow **rows_dev)
+{
+    sdrhip_ctx *c = d->ctx;
+    const int S = d->nstreams;
+    const unsigned L = (unsigned)log2decim;
+    size_t total = 0;
+    for (int s = 0; s < S; ++s) {
+        rows[s].n_raw = n_in[s];
+        rows[s].n_dec = n_in[s] >> L;
+        rows[s].n_used = (uint64_t)(n_in[s] >> L) << L;
+        total += (size_t)rows[s].n_used;
+    }
+    // K1r: one segment length for the call, sized as the uniform planner sizes it for the mean stream; each stream gets the
+    // segments its own count needs (at least one: its state), so the grid follows the total, not the largest stream
+    const bool cen = fcpos == SDRHIP_FC_CEN;
+    d->r_nsub = 0; d->r_grid = 0;
+    if (L >= 1 && (cen || L >= 3)) {
+        int nseg = 0;
+        plan_decimate((int)L, fcpos, (total + (size_t)S - 1) / (size_t)S, S, &d->r_nsub, &nseg);
+        const size_t seg_raw = (size_t)d->r_nsub * (size_t)(cen ? 2048 : 8192);
+        size_t acc = 0;
+        for (int s = 0; s < S; ++s) {
+            rows[s].seg0 = (int)acc;
+            acc += rows[s].n_used ? (size_t)((rows[s].n_used + seg_raw - 1) / seg_raw) : 1;
+        }
+        if (acc > 0x7fffffffu) return fail(SDRHIP_EINVAL, "ragged call: too many segments");
+        d->r_grid = (int)acc;
+    }
+    // K1mr: the matrix-core launch with per-stream wave groups and pieces, under the rules of the uniform call (decim_path, mfma_min
+    // of the call's total samples, a stream long enough for a span)
+    d->r_mfma = false;
+    const CtxOptions &env = c->opt;
+    if (cen && L >= 2 && env.decim_path != DECIM_PATH_VALU && (env.decim_path == DECIM_PATH_MFMA || total >= mfma_min_samples(env, (int)L))) {
+        memset(&d->r_mf, 0, sizeof(d->r_mf));
+        d->r_mf.mf_ring = env.mfma_ring == 3 ? 3 : 4;
+        d->r_mfma = plan_decimate_mfma_ragged((int)L, fcpos, rows, S, env.mfma_span, c->n_cu, &d->r_mf);
+    }
+    const size_t bytes = (size_t)S * sizeof(RaggedRow);
+    int rc;
+    if ((rc = d->rows_pin.reserve(bytes))) return rc; // (waits for the upload of the previous table)
+    if ((rc = d->rows_dev.reserve(bytes))) return rc;
+    memcpy(d->rows_pin.p, rows, bytes);
+    HIP_TRY(hipMemcpyAsync(d->rows_dev.p, d->rows_pin.p, bytes, hipMemcpyHostToDevice, c->stream));
+    d->rows_pin.mark(c->stream);
+    *rows_dev = d->rows_dev.as<RaggedRow>();
+    return SDRHIP_OK;
+}
+
+bool ragged_mfma_planned(const sdrhip_decimators *d) { return d->r_mfma; }
+
+int decimate_ragged_device(sdrhip_decimators *d, int log2decim, int fcpos, unsigned *sampleSize, const int16_t *in, size_t in_stride,
+                           int16_t *out, size_t out_stride, const RaggedRow *rows, const RaggedRow *rows_dev, int frame_mode,
+                           int frame_blocks, const unsigned *meta_w, unsigned meta_rate)
+{
+    sdrhip_ctx *c = d->ctx;
+    const int S = d->nstreams;
+    const unsigned L = (unsigned)log2decim;
+    const unsigned ss = *sampleSize;
+    size_t max_raw = 0, max_dec = 0, min_used = SIZE_MAX;
+    for (int s = 0; s < S; ++s) {
+        if (rows[s].n_raw > max_raw) max_raw = (size_t)rows[s].n_raw;
+        if (rows[s].n_dec > max_dec) max_dec = (size_t)rows[s].n_dec;
+        if (rows[s].n_used < min_used) min_used = (size_t)rows[s].n_used;
+    }
+    d->last = DecimPlanInfo();
+    if (L == 0) {
+        if (max_raw == 0) return SDRHIP_OK;
+        const int norm = ss < 16 ? (int)(16 - ss) : 0;
+        hipError_t e = launch_decimate_simple_ragged(0, fcpos, in, in_stride, out, out_stride, max_raw, S, norm, 0, rows_dev, c->stream);
+        if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "decimate1 launch: %s", hipGetErrorString(e));
+        return SDRHIP_OK;
+    }
+    const unsigned target = 16 - L;
+    const unsigned trunk = ss < target ? 0 : ss - target;
+    const unsigned norm = ss < target ? target - ss : 0;
+    *sampleSize = ss + L - trunk;
+    if (max_dec == 0) return SDRHIP_OK; // (no stream has a whole output sample: nothing enters any history)
+    if (fcpos != SDRHIP_FC_CEN && L <= 2) {
+        hipError_t e = launch_decimate_simple_ragged((int)L, fcpos, in, in_stride, out, out_stride, max_raw, S, (int)norm, (int)trunk, rows_dev, c->stream);
+        if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "decimate%u launch: %s", 1u << L, hipGetErrorString(e));
+        return SDRHIP_OK;
+    }
+    if (frame_mode && !d->r_mfma) return fail(SDRHIP_EINVAL, "internal: ragged frame mode needs the matrix-core launch");
+    DecimArgs a;
+    if (d->r_mfma) a = d->r_mf;
+    else memset(&a, 0, sizeof(a));
+    a.in = in; a.out = out; a.in_stride = in_stride; a.out_stride = out_stride;
+    a.state_cur = d->state[d->cur]; a.state_next = d->state[d->cur ^ 1];
+    a.nstreams = S;
+    a.bias = d->bias; a.norm = (int)norm; a.trunk = (int)trunk;
+    a.nsub_per_seg = d->r_nsub; a.nseg = d->r_grid;
+    a.frame_mode = frame_mode; a.frame_blocks = frame_blocks; a.meta_rate = meta_rate;
+    if (meta_w) memcpy(a.meta_w, meta_w, sizeof(a.meta_w));
+    a.mf_dump = c->decim_dump;
+    const bool cen = fcpos == SDRHIP_FC_CEN;
+    hipError_t e;
+    {
+        KTimer kt(c, SDRHIP_K_DECIMATE);
+        e = d->r_mfma ? launch_decimate_mfma_ragged((int)L, cen && d->stage0_int16, a, rows_dev, c->stream)
+                      : launch_decimate_ragged((int)L, fcpos, cen && d->stage0_int16, a, rows_dev, c->stream);
+    }
+    if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "decimate launch: %s", hipGetErrorString(e));
+    d->last.path = d->r_mfma ? DECIM_PATH_MFMA : DECIM_PATH_VALU;
+    if (d->r_mfma) {
+        d->last.span = a.mf_span; d->last.head = a.mf_head; d->last.wps = a.mf_wps; d->last.npieces = a.mf_npieces;
+    } else {
+        d->last.nseg = d->r_grid;
+    }
+    d->cur ^= 1;
+    // every stream's first-stage history holds raw int16 samples when every stream either saw a whole history of them now or held
+    // only such before (a stream that got nothing keeps what it had)
+    d->stage0_int16 = cen && (d->stage0_int16 || min_used >= (size_t)2 * DEC_HIST);
+    return SDRHIP_OK;
+}
+
+int ragged_stage_in(sdrhip_ctx *c, PinnedBuf &pin, DevBuf &dev, const void *src, size_t in_stride, const size_t *n_in, int S, size_t esz,
+                    size_t dstride, const void **out)
+{
+    int rc;
+    size_t total = 0, max_n = 0;
+    for (int s = 0; s < S; ++s) { total += n_in[s]; if (n_in[s] > max_n) max_n = n_in[s]; }
+    const char *p = static_cast<const char *>(src);
+    if ((size_t)S * dstride * esz <= SDRHIP_ZEROCOPY_MAX) { // (small call: the kernel reads the pinned rows itself)
+        if ((rc = c->zin.reserve((size_t)S * dstride * esz + 16))) return rc;
+        for (int s = 0; s < S; ++s)
+            if (n_in[s]) memcpy(c->zin.as<char>() + (size_t)s * dstride * esz, p + (size_t)s * in_stride * esz, n_in[s] * esz);
+        link_bytes(c, hipMemcpyHostToDevice, total * esz);
+        *out = c->zin.p;
+        return SDRHIP_OK;
+    }
+    if ((rc = pin.reserve((size_t)S * dstride * esz))) return rc;
+    if ((rc = dev.reserve((size_t)S * dstride * esz + 16))) return rc;
+    for (int s = 0; s < S; ++s)
+        if (n_in[s]) memcpy(pin.as<char>() + (size_t)s * dstride * esz, p + (size_t)s * in_stride * esz, n_in[s] * esz);
+    HIP_TRY(link_copy2d(c, dev.p, dstride * esz, pin.p, dstride * esz, max_n * esz, S, hipMemcpyHostToDevice, c->stream));
+    pin.mark(c->stream);
+    *out = dev.p;
+    return SDRHIP_OK;
+}
+} // namespace sdrhip
+
+extern "C" int sdrhip_decimate_ragged(sdrhip_decimators *d, int log2decim, int fcpos, unsigned *sampleSize, const int16_t *iq_in,
+                                      const size_t *n_in, size_t in_stride, int16_t *iq_out, size_t out_stride, size_t *n_out, int mem)
+{
+    if (!d || !sampleSize || !n_in || !n_out) return fail(SDRHIP_EINVAL, "decimate_ragged: NULL handle, sampleSize or count array");
+    sdrhip::CtxLock lock_(d->ctx);
+    if (log2decim < 0 || log2decim > 6) return fail(SDRHIP_EINVAL, "Invalid log2 decimation factor");
+    if (fcpos < SDRHIP_FC_INF || fcpos > SDRHIP_FC_CEN) return fail(SDRHIP_EINVAL, "Invalid Fc position index");
+    if (*sampleSize < 1 || *sampleSize > 16) return fail(SDRHIP_EINVAL, "sampleSize must be 1..16");
+    if (mem != SDRHIP_MEM_HOST && mem != SDRHIP_MEM_DEVICE) return fail(SDRHIP_EINVAL, "mem must be SDRHIP_MEM_HOST or SDRHIP_MEM_DEVICE");
+    sdrhip_ctx *c = d->ctx;
+    const int S = d->nstreams;
+    size_t max_in = 0;
+    for (int s = 0; s < S; ++s) if (n_in[s] > max_in) max_in = n_in[s];
+    const size_t max_res = max_in >> log2decim;
+    if (max_in && (!iq_in || (!iq_out && max_res))) return fail(SDRHIP_EINVAL, "decimate_ragged: NULL buffer");
+    if (S == 1) { in_stride = max_in; out_stride = max_res; }
+    if (S > 1 && (in_stride < max_in || out_stride < max_res)) return fail(SDRHIP_EINVAL, "decimate_ragged: stride smaller than the largest count");
+    if (mem == SDRHIP_MEM_DEVICE && max_in && (!aligned16(iq_in) || !aligned16(iq_out) || (S > 1 && ((in_stride & 3) || (out_stride & 3)))))
+        return fail(SDRHIP_EALIGN, "decimate_ragged: device pointers must be 16-byte aligned and strides multiples of 4 samples");
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<RaggedRow> rows((size_t)S);
+    memset(rows.data(), 0, rows.size() * sizeof(RaggedRow));
+    for (int s = 0; s < S; ++s) n_out[s] = n_in[s] >> log2decim;
+    if (max_in == 0) { // nothing to stage; sampleSize advances as in sdrhip_decimate
+        d->last = DecimPlanInfo();
+        if (log2decim > 0) { const unsigned t = 16u - (unsigned)log2decim, ss = *sampleSize; *sampleSize = ss + (unsigned)log2decim - (ss < t ? 0 : ss - t); }
+        return SDRHIP_OK;
+    }
+    const RaggedRow *rdev = nullptr;
+    int rc = ragged_prepare(d, log2decim, fcpos, n_in, rows.data(), &rdev);
+    if (rc) return rc;
+    if (mem == SDRHIP_MEM_DEVICE)
+        return decimate_ragged_device(d, log2decim, fcpos, sampleSize, iq_in, in_stride, iq_out, out_stride, rows.data(), rdev);
+    const size_t dis = (max_in + 3) & ~(size_t)3, dos = (max_res + 3) & ~(size_t)3;
+    const void *din = nullptr;
+    if ((rc = ragged_stage_in(c, d->stage_pin, c->in, iq_in, in_stride, n_in, S, 4, dis, &din))) return rc;
+    if ((rc = c->out.reserve((size_t)S * dos * 4 + 16))) return rc;
+    if ((rc = decimate_ragged_device(d, log2decim, fcpos, sampleSize, static_cast<const int16_t *>(din), dis, c->out.as<int16_t>(), dos,
+                                     rows.data(), rdev)))
+        return rc;
+    if (max_res) {
+        if ((rc = d->out_pin.reserve((size_t)S * dos * 4))) return rc;
+        HIP_TRY(link_copy2d(c, d->out_pin.p, dos * 4, c->out.p, dos * 4, max_res * 4, S, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int s = 0; s < S; ++s)
+        if (n_out[s]) memcpy(iq_out + (size_t)s * out_stride * 2, d->out_pin.as<char>() + (size_t)s * dos * 4, n_out[s] * 4);
     return SDRHIP_OK;
 }

@@ -74,6 +74,21 @@ int decimate_device(sdrhip_decimators *d, int log2decim, int fcpos, unsigned *sa
                     size_t in_stride, int16_t *out, size_t out_stride, size_t *n_out, int frame_mode, int frame_blocks,
                     uint64_t frame_sample_base, const RxMeta *meta = nullptr, const Enc128Args *fuse = nullptr, bool *fused = nullptr,
                     bool coresident = false); // coresident: another kernel's workgroups share the CUs (ring depth 3, raised wave priority)
+// ragged calls (sdrhip_decimate_ragged, sdrhip_rx_process_ragged): ragged_prepare fills the decimator fields of rows[0..S) (the
+// caller's framing fields are kept), plans K1r and uploads the table (the decimators' own device copy, valid until the next ragged
+// call on them); decimate_ragged_device then runs the cascade with it
+int ragged_prepare(sdrhip_decimators *d, int log2decim, int fcpos, const size_t *n_in, RaggedRow *rows, const RaggedRow **rows_dev);
+// frame_mode != 0 (only when ragged_mfma_planned): the matrix-core launch stores straight into the frame layout, `out` = the frame
+// area (stream s at out + s * out_stride dwords, its window at RaggedRow out_off), meta_w / meta_rate = the shared meta words
+int decimate_ragged_device(sdrhip_decimators *d, int log2decim, int fcpos, unsigned *sampleSize, const int16_t *in, size_t in_stride,
+                           int16_t *out, size_t out_stride, const RaggedRow *rows, const RaggedRow *rows_dev, int frame_mode = 0,
+                           int frame_blocks = 0, const unsigned *meta_w = nullptr, unsigned meta_rate = 0);
+// the last ragged_prepare planned the matrix-core launch (K1mr): decimate_ragged_device will run it
+bool ragged_mfma_planned(const sdrhip_decimators *d);
+// host rows of n_in[s] samples of esz bytes -> [S][dstride] rows the kernels read (pinned zero-copy memory for small calls, else
+// `dev` through the pinned `pin`); only n_in[s] samples of row s are read
+int ragged_stage_in(sdrhip_ctx *c, PinnedBuf &pin, DevBuf &dev, const void *src, size_t in_stride, const size_t *n_in, int S, size_t esz,
+                    size_t dstride, const void **out);
 // the context's second stream (created on first use; non-blocking, so that it never synchronises with a NULL caller stream)
 int ctx_stream2(sdrhip_ctx *c, hipStream_t *out);
 bool decimate_mfma_applies(const sdrhip_decimators *d, int log2decim, int fcpos, size_t n_in);

@@ -163,6 +163,39 @@ hipError_t launch_decimate_simple(int log2decim, int fcpos, const int16_t *in, s
                                   size_t out_stride, size_t n_in, int nstreams, int norm, int trunk,
                                   hipStream_t stream);
 
+// Ragged calls (sdrhip_decimate_ragged, sdrhip_rx_process_ragged): one row per stream, uploaded per call.  K1r reads
+// n_used / seg0, K0r and the filter-less kernel n_raw, K2r the framing fields.
+struct RaggedRow {
+    uint64_t n_raw;             // samples of the stream in this call (K0r, filter-less kernel: the count itself)
+    uint64_t n_used;            // raw samples the cascade consumes (multiple of 2^log2decim)
+    uint64_t n_dec;             // decimated samples (K2r)
+    uint64_t out_off;           // K2r: dwords from the stream's frame area to slot 0 of its window
+    uint64_t frame_sample_base; // K2r: samples already in that slot
+    uint64_t meta_idx0;         // K2r: decimated-sample index (from the stream's first sample of the call) of frame meta_first
+    int seg0;                   // K1r: first workgroup of the stream (prefix sum of the per-stream segment counts)
+    int meta_first, meta_count; // K2r: as FrameArgs::meta_*, per stream
+    unsigned frame_count0;
+    unsigned tv_sec, tv_usec;   // K2r: the stamp of the stream's first sample (meta_w[3..4])
+    // K1mr (the matrix-core launch of ragged calls): the stream's matrix-core waves mf_w0 .. mf_w0 + mf_wps - 1 (mf_wps groups of 8
+    // spans from the shared head on), its VALU pieces mf_p0 .. mf_p0 + mf_np - 1: piece 0 = [0, mf_head) from the state, pieces
+    // 1.. = mf_tail_seg-long pieces from mf_tail_start, the last one storing the state.  A stream too short for a span
+    // (mf_wps = 0) runs on pieces alone (mf_head = min(n_used, mf_tail_seg)).
+    int mf_w0, mf_wps, mf_p0, mf_np;
+    uint64_t mf_head, mf_tail_start;
+};
+// K1mr: plans the matrix-core launch of a ragged call (per-stream fields of `rows`, shared span / grid in `a`: a->mf_wps = the
+// launch's matrix-core waves, a->mf_npieces = its VALU pieces); false when no stream is long enough for a span
+bool plan_decimate_mfma_ragged(int log2decim, int fcpos, RaggedRow *rows, int nstreams, size_t span_override, int n_cu, DecimArgs *a);
+hipError_t launch_decimate_mfma_ragged(int log2decim, bool pack16, const DecimArgs &a, const RaggedRow *rows, hipStream_t stream);
+// K1r: the VALU cascade with a 1-D grid of sum_s max(1, ceil(n_used_s / segment)) workgroups; workgroup b serves the stream
+// whose seg0 range holds it (binary search over `rows`).  A stream with n_used = 0 copies its state.  a.nsub_per_seg is the
+// segment length; a.n_used / a.nseg are ignored, a.nseg carries the grid size.
+hipError_t launch_decimate_ragged(int log2decim, int fcpos, bool pack16, const DecimArgs &a, const RaggedRow *rows, hipStream_t stream);
+// filter-less kernel with per-stream counts n_raw (grid planned for the largest, n_in)
+hipError_t launch_decimate_simple_ragged(int log2decim, int fcpos, const int16_t *in, size_t in_stride, int16_t *out,
+                                         size_t out_stride, size_t n_in, int nstreams, int norm, int trunk, const RaggedRow *rows,
+                                         hipStream_t stream);
+
 // TestSource bank (testsource_kernels.hip): one record per stream and call
 struct TestSourceParams {
     unsigned phase0; // NCO phase of the call's first sample (2^32 = one turn)
@@ -188,6 +221,9 @@ struct FrameArgs {
     unsigned meta_rate;
 };
 hipError_t launch_frame_pack(const FrameArgs &a, int nstreams, hipStream_t stream);
+// K2r: the same with per-stream n / window / frame base / meta record from `rows` (a.n = the largest count: the grid;
+// a.meta_w[3..4] are replaced by each row's stamp; skip_* unused)
+hipError_t launch_frame_pack_ragged(const FrameArgs &a, const RaggedRow *rows, int nstreams, hipStream_t stream);
 
 struct InterpArgs {
     const int16_t *in;
@@ -218,6 +254,9 @@ enum { IQF_S16 = 0, IQF_U8 = 1, IQF_S8 = 2 };
 // (stream s at out + 2 * s * out_stride, out_stride a multiple of 4); fmt IQF_U8 / IQF_S8
 hipError_t launch_iq8_widen(int fmt, const uint8_t *in, size_t in_stride, int16_t *out, size_t out_stride, size_t n, int nstreams,
                             hipStream_t stream);
+// K0r: the same, stream s widening rows[s].n_raw samples (n = the largest: the grid)
+hipError_t launch_iq8_widen_ragged(int fmt, const uint8_t *in, size_t in_stride, int16_t *out, size_t out_stride, size_t n, int nstreams,
+                                   const struct RaggedRow *rows, hipStream_t stream);
 // K6n: int16 rows -> int8 rows of byte 1 of every component (interpolate1 with IQF_S8 output)
 hipError_t launch_iq8_narrow(const int16_t *in, size_t in_stride, uint8_t *out, size_t out_stride, size_t n, int nstreams, hipStream_t stream);
 

@@ -202,6 +202,18 @@ struct sdrhip_rx {
     // ---- input format (sdrhip_rx_set_input_format): 8-bit input is widened by K0 into `wide`, the decimator's int16 input
     int in_fmt = IQF_S16;
     DevBuf wide;
+    // ---- ragged calls (sdrhip_rx_process_ragged): per-stream framing state.  While `diverged` the vectors hold it (the scalars
+    // above are stale) and every Rx call takes the ragged path; when a call leaves every stream at the same position the scalars
+    // take over again
+    bool diverged = false;
+    std::vector<size_t> r_base;        // base_slot per stream
+    std::vector<uint64_t> r_pending;   // pending_samples per stream
+    std::vector<uint8_t> r_open;       // frame_open per stream
+    std::vector<uint16_t> r_count;     // frame_count per stream
+    std::vector<size_t> r_view_first, r_view_frames; // sdrhip_rx_frames_view_ragged: the frames the last call delivered
+    bool view_ragged = false;          // the last call's windows differ between streams: sdrhip_rx_frames_view refuses
+    PinnedBuf r_pin, r_flist_pin;      // host-row staging and the encoder's frame list
+    DevBuf r_flist;
 };
 
 static int rx_check_config(const sdrhip_rx_config *cfg);
@@ -258,6 +270,7 @@ extern "C" int sdrhip_rx_set_pipelined(sdrhip_rx *rx, int on)
     if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
     sdrhip::CtxLock lock_(rx->ctx);
     if (!on && rx->late.have) return fail(SDRHIP_EINVAL, "rx_set_pipelined: sdrhip_rx_flush the waiting frames first");
+    if (on && rx->diverged) return fail(SDRHIP_EINVAL, "rx_set_pipelined: ragged calls left the streams at different frame positions");
     rx->pipelined = on ? 1 : 0;
     return SDRHIP_OK;
 }
@@ -310,7 +323,15 @@ extern "C" int sdrhip_rx_reconfigure(sdrhip_rx *rx, const sdrhip_rx_config *cfg)
         const size_t new_fb = (size_t)(SDRHIP_NB_ORIGINAL + cfg->nb_fec) * SDRHIP_UDPSIZE;
         DevBuf fresh;
         if ((rc = fresh.reserve((size_t)S * rx->cap_frames * new_fb))) return rc;
-        if (rx->frame_open)
+        if (rx->diverged) { // (per-stream windows: each open frame moves to slot 0 of its stream)
+            for (int s = 0; s < S; ++s) {
+                if (rx->r_open[(size_t)s])
+                    HIP_TRY(hipMemcpyAsync(fresh.as<uint8_t>() + (size_t)s * rx->cap_frames * new_fb,
+                                           rx->work.as<uint8_t>() + (size_t)s * rx->cap_frames * old_fb + rx->r_base[(size_t)s] * old_fb,
+                                           (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE, hipMemcpyDeviceToDevice, c->stream));
+                rx->r_base[(size_t)s] = 0;
+            }
+        } else if (rx->frame_open)
             HIP_TRY(hipMemcpy2DAsync(fresh.p, rx->cap_frames * new_fb, rx->work.as<uint8_t>() + rx->base_slot * old_fb,
                                      rx->cap_frames * old_fb, (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE, S, hipMemcpyDeviceToDevice,
                                      c->stream));
@@ -322,6 +343,7 @@ extern "C" int sdrhip_rx_reconfigure(sdrhip_rx *rx, const sdrhip_rx_config *cfg)
         rx->base_slot = 0;
         rx->view_base = nullptr;
         rx->view_frames = 0;
+        rx->view_ragged = false;
     }
     rx->cfg = *cfg;
     return SDRHIP_OK;
@@ -337,6 +359,7 @@ extern "C" void sdrhip_rx_destroy(sdrhip_rx *rx)
     rx->lin[1].release();
     rx->flist.release();
     rx->wide.release();
+    rx->r_pin.release(); rx->r_flist_pin.release(); rx->r_flist.release();
     if (rx->ev_framed) (void)hipEventDestroy(rx->ev_framed);
     if (rx->ev_enc) (void)hipEventDestroy(rx->ev_enc);
     for (auto &b : rx->abatch) {
@@ -350,9 +373,32 @@ extern "C" int sdrhip_rx_frames_view(const sdrhip_rx *rx, const uint8_t **base, 
 {
     if (!rx || !base || !stream_stride_bytes || !n_frames) return fail(SDRHIP_EINVAL, "rx_frames_view: NULL argument");
     sdrhip::CtxLock lock_(rx->ctx);
+    if (rx->view_ragged) return fail(SDRHIP_EINVAL, "rx_frames_view: the last call's windows differ between streams: use sdrhip_rx_frames_view_ragged");
     *base = rx->view_base;
     *stream_stride_bytes = rx->view_stride;
     *n_frames = rx->view_frames;
+    return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_rx_frames_view_ragged(const sdrhip_rx *rx, const uint8_t **base, size_t *stream_stride_bytes, size_t *first_slot,
+                                            size_t *n_frames)
+{
+    if (!rx || !base || !stream_stride_bytes || !first_slot || !n_frames) return fail(SDRHIP_EINVAL, "rx_frames_view_ragged: NULL argument");
+    sdrhip::CtxLock lock_(rx->ctx);
+    const int S = rx->nstreams;
+    const size_t fb = (size_t)(SDRHIP_NB_ORIGINAL + rx->cfg.nb_fec) * SDRHIP_UDPSIZE;
+    if (rx->view_ragged) {
+        *base = rx->work.as<uint8_t>();
+        *stream_stride_bytes = rx->cap_frames * fb;
+        for (int s = 0; s < S; ++s) { first_slot[s] = rx->r_view_first[(size_t)s]; n_frames[s] = rx->r_view_frames[(size_t)s]; }
+        return SDRHIP_OK;
+    }
+    // (the last call delivered the same window of every stream: the uniform view, as slot offsets from the area)
+    const size_t slot = rx->view_base && rx->work.p && rx->view_base >= rx->work.as<uint8_t>() && rx->view_stride == rx->cap_frames * fb
+                            ? (size_t)(rx->view_base - rx->work.as<uint8_t>()) / fb : 0;
+    *base = rx->view_base ? rx->view_base - slot * fb : nullptr;
+    *stream_stride_bytes = rx->view_stride;
+    for (int s = 0; s < S; ++s) { first_slot[s] = slot; n_frames[s] = rx->view_frames; }
     return SDRHIP_OK;
 }
 
@@ -366,6 +412,14 @@ extern "C" size_t sdrhip_rx_max_frames(const sdrhip_rx *rx, size_t n_in)
 {
     if (!rx) return 0;
     sdrhip::CtxLock lock_(rx->ctx);
+    if (rx->diverged) { // (ragged calls left the streams at different positions: the stream that completes the most)
+        size_t most = 0;
+        for (size_t s = 0; s < rx->r_pending.size(); ++s) {
+            const size_t f = (size_t)((rx->r_pending[s] + (n_in >> rx->cfg.log2decim)) / SDRHIP_SAMPLES_PER_FRAME);
+            if (f > most) most = f;
+        }
+        return most;
+    }
     const size_t now = (size_t)((rx->pending_samples + (n_in >> rx->cfg.log2decim)) / SDRHIP_SAMPLES_PER_FRAME);
     if (!rx->pipelined) return now;
     return rx->late.have && rx->late.frames > now ? rx->late.frames : now; // (a pipelined call delivers the previous call's frames)
@@ -385,6 +439,7 @@ static int rx_deliver(sdrhip_rx *rx, const uint8_t *base, size_t stride, size_t 
         return fail(SDRHIP_EINVAL, "rx_process: NULL frames_out");
     }
     rx->view_base = base; rx->view_stride = stride; rx->view_frames = frames;
+    rx->view_ragged = false;
     if (n_frames) *n_frames = frames;
     return SDRHIP_OK;
 }
@@ -405,17 +460,34 @@ extern "C" int sdrhip_rx_flush(sdrhip_rx *rx, uint8_t *frames_out, size_t frame_
     return SDRHIP_OK;
 }
 
+static int rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, size_t in_stride, const uint32_t *tv_sec,
+                     const uint32_t *tv_usec, uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem);
+
 extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_in, size_t in_stride, uint32_t tv_sec, uint32_t tv_usec,
                                  uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem)
 {
     if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
     sdrhip::CtxLock lock_(rx->ctx);
     if (n_frames) *n_frames = 0;
+    if (rx->diverged && n_in) {
+        // ragged calls left the streams at different frame positions: a ragged call with equal counts and stamps; *n_frames = the
+        // largest per-stream count (sdrhip_rx_frames_view_ragged has each)
+        const size_t S = (size_t)rx->nstreams;
+        std::vector<size_t> cnt(S, n_in), nf(S, 0);
+        std::vector<uint32_t> sec(S, tv_sec), usec(S, tv_usec);
+        const int rc = rx_ragged(rx, iq_in, cnt.data(), in_stride, sec.data(), usec.data(), frames_out, frame_stride_bytes, nf.data(), mem);
+        if (rc) return rc;
+        size_t most = 0;
+        for (size_t s = 0; s < S; ++s) if (nf[s] > most) most = nf[s];
+        if (n_frames) *n_frames = most;
+        return SDRHIP_OK;
+    }
     if (n_in == 0) {
         // an empty call completes nothing; in pipelined mode it still DELIVERS what the previous call completed (the header's
         // contract: every call delivers the frames of the one before it)
         if (rx->pipelined && rx->late.have) return sdrhip_rx_flush(rx, frames_out, frame_stride_bytes, n_frames, mem);
         rx->view_frames = 0;
+        rx->view_ragged = false;
         return SDRHIP_OK;
     }
     if (!iq_in) return fail(SDRHIP_EINVAL, "rx_process: NULL input");
@@ -666,7 +738,7 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
         if (rx->late.have) {
             if ((rc = rx_deliver(rx, rx->late.base, rx->late.stride, rx->late.frames, rx->late.frame_bytes, frames_out, frame_stride_bytes, n_frames, mem))) return rc;
         } else {
-            rx->view_base = nullptr; rx->view_frames = 0;
+            rx->view_base = nullptr; rx->view_frames = 0; rx->view_ragged = false;
         }
         rx->late.have = done > 0;
         rx->late.encode = encode_later;
@@ -686,6 +758,286 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
     rx->frame_count = (uint16_t)(rx->frame_count + done);
     if (mem == SDRHIP_MEM_HOST) HIP_TRY(hipStreamSynchronize(c->stream));
     return SDRHIP_OK;
+}
+
+// --------------------------------------------------------------------------- ragged Rx calls
+// Every stream takes its own count: K0r (8-bit input) -> K1r / filter-less kernel into stream order -> K2r into each stream's
+// own window -> one encoder launch over the list of every stream's completed frames.  The per-stream framing state lives in the
+// r_* vectors while the streams differ, in the scalars otherwise.
+static void rx_split(sdrhip_rx *rx)
+{
+    if (rx->diverged) return;
+    const size_t S = (size_t)rx->nstreams;
+    rx->r_base.assign(S, rx->base_slot);
+    rx->r_pending.assign(S, rx->pending_samples);
+    rx->r_open.assign(S, rx->frame_open ? 1 : 0);
+    rx->r_count.assign(S, rx->frame_count);
+}
+
+static void rx_join(sdrhip_rx *rx)
+{
+    const size_t S = (size_t)rx->nstreams;
+    for (size_t s = 1; s < S; ++s)
+        if (rx->r_base[s] != rx->r_base[0] || rx->r_pending[s] != rx->r_pending[0] || rx->r_open[s] != rx->r_open[0] ||
+            rx->r_count[s] != rx->r_count[0]) {
+            rx->diverged = true;
+            return;
+        }
+    rx->diverged = false;
+    rx->base_slot = rx->r_base[0];
+    rx->pending_samples = rx->r_pending[0];
+    rx->frame_open = rx->r_open[0] != 0;
+    rx->frame_count = rx->r_count[0];
+}
+
+// a HIP failure inside a ragged call: the per-stream state goes back to the scalars where the streams agree (the windows may have
+// moved already), then the error
+#define RX_TRY(expr)                                                                                                   \
+    do {                                                                                                               \
+        hipError_t e_ = (expr);                                                                                        \
+        if (e_ != hipSuccess) { rx_join(rx); return ::sdrhip::fail(SDRHIP_EDEVICE, "%s: %s", #expr, hipGetErrorString(e_)); } \
+    } while (0)
+
+static int rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, size_t in_stride, const uint32_t *tv_sec,
+                     const uint32_t *tv_usec, uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem)
+{
+    sdrhip_ctx *c = rx->ctx;
+    const int S = rx->nstreams, L = rx->cfg.log2decim, R = rx->cfg.nb_fec;
+    const size_t FB = (size_t)SDRHIP_NB_ORIGINAL + (size_t)R;
+    const size_t frame_bytes = FB * SDRHIP_UDPSIZE;
+    for (int s = 0; s < S; ++s) n_frames[s] = 0;
+    // ---- everything that can be refused is checked before anything is consumed
+    if (mem != SDRHIP_MEM_HOST && mem != SDRHIP_MEM_DEVICE) return fail(SDRHIP_EINVAL, "mem must be SDRHIP_MEM_HOST or SDRHIP_MEM_DEVICE");
+    if (rx->pipelined) return fail(SDRHIP_EINVAL, "rx_process_ragged: not available in pipelined mode");
+    for (const auto &b : rx->abatch)
+        if (b.state != 0) return fail(SDRHIP_EINVAL, "rx_process_ragged: asynchronous batches are being filled or in flight: collect them first");
+    size_t max_in = 0;
+    for (int s = 0; s < S; ++s) if (n_in[s] > max_in) max_in = n_in[s];
+    if (S == 1) in_stride = max_in;
+    if (S > 1 && in_stride < max_in) return fail(SDRHIP_EINVAL, "rx_process_ragged: in_stride smaller than the largest count");
+    if (max_in && !iq_in) return fail(SDRHIP_EINVAL, "rx_process_ragged: NULL input");
+    const bool wide8 = rx->in_fmt != IQF_S16;
+    if (max_in && mem == SDRHIP_MEM_DEVICE && (!aligned16(iq_in) || (S > 1 && (in_stride & (wide8 ? 7 : 3)))))
+        return fail(SDRHIP_EALIGN, "rx_process_ragged: device input must be 16-byte aligned, its stride a multiple of %d samples", wide8 ? 8 : 4);
+    rx_split(rx);
+    std::vector<size_t> done((size_t)S);
+    std::vector<uint64_t> rest((size_t)S);
+    size_t max_done = 0, sum_done = 0, max_dec = 0;
+    for (int s = 0; s < S; ++s) {
+        const size_t n_dec = n_in[s] >> L;
+        const uint64_t total = rx->r_pending[(size_t)s] + n_dec;
+        done[(size_t)s] = (size_t)(total / SDRHIP_SAMPLES_PER_FRAME);
+        rest[(size_t)s] = total - (uint64_t)done[(size_t)s] * SDRHIP_SAMPLES_PER_FRAME;
+        if (done[(size_t)s] > max_done) max_done = done[(size_t)s];
+        if (n_dec > max_dec) max_dec = n_dec;
+        sum_done += done[(size_t)s];
+    }
+    if (max_done && !frames_out && mem != SDRHIP_MEM_DEVICE) { rx_join(rx); return fail(SDRHIP_EINVAL, "rx_process_ragged: NULL frames_out"); }
+    if (frames_out && S > 1 && max_done && frame_stride_bytes < max_done * frame_bytes) {
+        rx_join(rx);
+        return fail(SDRHIP_EINVAL, "rx_process_ragged: frame stride too small for the stream with the most frames (%zu)", max_done);
+    }
+    RX_TRY(hipSetDevice(c->device));
+    rx->consumed = false;
+    if (max_in == 0) { // nothing arrives: nothing changes, nothing is delivered
+        rx->view_frames = 0; rx->view_ragged = false;
+        rx_join(rx);
+        return SDRHIP_OK;
+    }
+    int rc;
+    // ---- windows: stream s fills slots r_base[s] .. r_base[s] + done[s] of its area; a window that would pass the end of the area
+    // moves that stream's open frame to slot 0 (the others stay where they are); a call that needs more slots than the area has
+    // gets a new area, every open frame at slot 0
+    size_t need_max = 0;
+    for (int s = 0; s < S; ++s) if (done[(size_t)s] + 1 > need_max) need_max = done[(size_t)s] + 1;
+    if (rx->old_work.p && !rx->late.have) {
+        RX_TRY(hipStreamSynchronize(c->stream));
+        rx->old_work.release();
+    }
+    if (need_max > rx->cap_frames) {
+        const size_t wmul = c->opt.rx_window ? (size_t)c->opt.rx_window : 2;
+        const size_t ncap = wmul * need_max;
+        DevBuf bigger;
+        if ((rc = bigger.reserve((size_t)S * ncap * frame_bytes))) { rx_join(rx); return rc; }
+        // (the old area and every window stay as they were until the copies have completed: a failure leaves the handle untouched)
+        hipError_t e = hipSuccess;
+        for (int s = 0; s < S && e == hipSuccess; ++s)
+            if (rx->r_open[(size_t)s])
+                e = hipMemcpyAsync(bigger.as<uint8_t>() + (size_t)s * ncap * frame_bytes,
+                                   rx->work.as<uint8_t>() + ((size_t)s * rx->cap_frames + rx->r_base[(size_t)s]) * frame_bytes, frame_bytes,
+                                   hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // earlier launches may still use the old area
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(c->stream);
+            bigger.release();
+            rx_join(rx);
+            return fail(SDRHIP_EDEVICE, "rx_process_ragged: moving the open frames: %s", hipGetErrorString(e));
+        }
+        for (int s = 0; s < S; ++s) rx->r_base[(size_t)s] = 0;
+        rx->work.release();
+        rx->work = bigger;
+        rx->cap_frames = ncap;
+    } else {
+        for (int s = 0; s < S; ++s) {
+            if (rx->r_base[(size_t)s] + done[(size_t)s] + 1 <= rx->cap_frames) continue;
+            uint8_t *a0 = rx->work.as<uint8_t>() + (size_t)s * rx->cap_frames * frame_bytes;
+            if (rx->r_open[(size_t)s])
+                RX_TRY(hipMemcpyAsync(a0, a0 + rx->r_base[(size_t)s] * frame_bytes, frame_bytes, hipMemcpyDeviceToDevice, c->stream));
+            rx->r_base[(size_t)s] = 0;
+        }
+    }
+    const size_t stream_bytes = rx->cap_frames * frame_bytes;
+    uint8_t *area = rx->work.as<uint8_t>();
+
+    // ---- the per-call table: counts (decimator), windows and meta records (K2r)
+    unsigned ss = rx->cfg.sample_bits;
+    const unsigned ssd = decimated_sample_size((unsigned)L, ss);
+    unsigned mw[6];
+    {
+        uint8_t m[24];
+        const uint32_t fc = rx->cfg.center_frequency_khz, sr = rx->cfg.sample_rate;
+        memcpy(m + 0, &fc, 4); memcpy(m + 4, &sr, 4);
+        m[8] = (uint8_t)((ssd - 1) / 8 + 1); m[9] = (uint8_t)ssd;
+        m[10] = SDRHIP_NB_ORIGINAL; m[11] = (uint8_t)R;
+        memset(m + 12, 0, 8);
+        uint32_t crc = 0xFFFFFFFFu; // (the CRC of the record with a zero stamp: shared, the config is)
+        for (int i = 0; i < 20; ++i) {
+            crc ^= m[i];
+            for (int k = 0; k < 8; ++k) crc = (crc & 1) ? 0xEDB88320u ^ (crc >> 1) : crc >> 1;
+        }
+        crc ^= 0xFFFFFFFFu;
+        memcpy(m + 20, &crc, 4);
+        memcpy(mw, m, 24);
+    }
+    std::vector<RaggedRow> rows((size_t)S);
+    memset(rows.data(), 0, rows.size() * sizeof(RaggedRow));
+    for (int s = 0; s < S; ++s) {
+        RaggedRow &r = rows[(size_t)s];
+        const int first_new = rx->r_open[(size_t)s] ? 1 : 0;
+        const int started = (int)(done[(size_t)s] + (rest[(size_t)s] > 0 ? 1 : 0)) - first_new;
+        r.out_off = rx->r_base[(size_t)s] * frame_bytes / 4;
+        r.frame_sample_base = rx->r_pending[(size_t)s];
+        if (started > 0 && (n_in[s] >> L)) {
+            r.meta_first = first_new; r.meta_count = started;
+            r.frame_count0 = (unsigned)rx->r_count[(size_t)s] + (unsigned)first_new;
+            r.meta_idx0 = first_new ? (uint64_t)SDRHIP_SAMPLES_PER_FRAME - rx->r_pending[(size_t)s] : 0;
+            r.tv_sec = tv_sec[s]; r.tv_usec = tv_usec[s];
+        }
+    }
+    const RaggedRow *rdev = nullptr;
+    if ((rc = ragged_prepare(rx->dec, L, rx->cfg.fcpos, n_in, rows.data(), &rdev))) { rx_join(rx); return rc; }
+
+    // ---- input: host rows staged stream by stream (n_in[s] samples each), 8-bit rows widened by K0r
+    const int16_t *din = iq_in;
+    size_t dstride = in_stride;
+    if (wide8) {
+        const uint8_t *d8 = reinterpret_cast<const uint8_t *>(iq_in);
+        size_t sstride = in_stride;
+        if (mem == SDRHIP_MEM_HOST) {
+            sstride = (max_in + 7) & ~(size_t)7;
+            const void *p = nullptr;
+            if ((rc = ragged_stage_in(c, rx->r_pin, c->in, iq_in, in_stride, n_in, S, 2, sstride, &p))) { rx_join(rx); return rc; }
+            d8 = static_cast<const uint8_t *>(p);
+        }
+        dstride = (max_in + 3) & ~(size_t)3;
+        if ((rc = rx->wide.reserve((size_t)S * dstride * 4 + 16))) { rx_join(rx); return rc; }
+        hipError_t e;
+        {
+            KTimer kt(c, SDRHIP_K_CONVERT);
+            e = launch_iq8_widen_ragged(rx->in_fmt, d8, sstride, rx->wide.as<int16_t>(), dstride, max_in, S, rdev, c->stream);
+        }
+        if (e != hipSuccess) { rx_join(rx); return fail(SDRHIP_EDEVICE, "widen launch: %s", hipGetErrorString(e)); }
+        din = rx->wide.as<int16_t>();
+    } else if (mem == SDRHIP_MEM_HOST) {
+        dstride = (max_in + 3) & ~(size_t)3;
+        const void *p = nullptr;
+        if ((rc = ragged_stage_in(c, rx->r_pin, c->in, iq_in, in_stride, n_in, S, 4, dstride, &p))) { rx_join(rx); return rc; }
+        din = static_cast<const int16_t *>(p);
+    }
+
+    // ---- decimate: the matrix-core launch (K1mr) stores straight into each stream's window (context option rx_direct, the
+    // default), its VALU pieces write the meta blocks; otherwise stream order, and K2r lays each stream's samples into its window
+    const bool direct = ragged_mfma_planned(rx->dec) && c->opt.rx_direct && stream_bytes < 0x3fffffffu;
+    const size_t lstride = (max_dec + 3) & ~(size_t)3;
+    DevBuf &lin = rx->lin[0];
+    if (direct) {
+        rc = decimate_ragged_device(rx->dec, L, rx->cfg.fcpos, &ss, din, dstride, reinterpret_cast<int16_t *>(area), stream_bytes / 4,
+                                    rows.data(), rdev, 1, (int)FB, mw, rx->cfg.sample_rate);
+    } else {
+        if ((rc = lin.reserve((size_t)S * lstride * 4 + 16))) { rx_join(rx); return rc; }
+        rc = decimate_ragged_device(rx->dec, L, rx->cfg.fcpos, &ss, din, dstride, lin.as<int16_t>(), lstride, rows.data(), rdev);
+    }
+    if (rc) { rx_join(rx); return rc; }
+    rx->consumed = true;
+    if (max_dec && !direct) {
+        FrameArgs fa;
+        memset(&fa, 0, sizeof(fa));
+        fa.in = lin.as<unsigned>(); fa.out = reinterpret_cast<unsigned *>(area);
+        fa.in_stride = lstride; fa.out_stride = stream_bytes / 4;
+        fa.n = max_dec; fa.frame_blocks = (int)FB;
+        memcpy(fa.meta_w, mw, sizeof(fa.meta_w));
+        fa.meta_rate = rx->cfg.sample_rate;
+        hipError_t e = launch_frame_pack_ragged(fa, rdev, S, c->stream);
+        if (e != hipSuccess) { rx_join(rx); return fail(SDRHIP_EDEVICE, "frame pack launch: %s", hipGetErrorString(e)); }
+    }
+
+    // ---- FEC: one launch over the completed frames of every stream (a dense list: frame f of stream s = area frame s * cap + slot)
+    if (sum_done && R > 0) {
+        const size_t nl = (sum_done + GF_FRAMES_PER_GROUP - 1) / GF_FRAMES_PER_GROUP * GF_FRAMES_PER_GROUP;
+        if ((rc = rx->r_flist_pin.reserve(nl * 4))) { rx_join(rx); return rc; }
+        if ((rc = rx->r_flist.reserve(nl * 4))) { rx_join(rx); return rc; }
+        int32_t *fl = rx->r_flist_pin.as<int32_t>();
+        size_t k = 0;
+        for (int s = 0; s < S; ++s)
+            for (size_t f = 0; f < done[(size_t)s]; ++f) fl[k++] = (int32_t)((size_t)s * rx->cap_frames + rx->r_base[(size_t)s] + f);
+        while (k < nl) fl[k++] = -1;
+        RX_TRY(hipMemcpyAsync(rx->r_flist.p, fl, nl * 4, hipMemcpyHostToDevice, c->stream));
+        rx->r_flist_pin.mark(c->stream);
+        if ((rc = fec_encode_device(c, area, frame_bytes, (size_t)S * rx->cap_frames, R, area + (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE,
+                                    frame_bytes, rx->r_flist.as<int32_t>(), (int)(nl / GF_FRAMES_PER_GROUP))))
+            { rx_join(rx); return rc; }
+    }
+
+    // ---- delivery: every stream's window (one 2-D copy when the windows line up, else a copy per stream)
+    bool same_base = true;
+    for (int s = 1; s < S; ++s) same_base = same_base && rx->r_base[(size_t)s] == rx->r_base[0];
+    if (frames_out && max_done) {
+        const hipMemcpyKind kind = mem == SDRHIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        if (same_base) {
+            RX_TRY(link_copy2d(c, frames_out, S > 1 ? frame_stride_bytes : max_done * frame_bytes, area + rx->r_base[0] * frame_bytes, stream_bytes,
+                                max_done * frame_bytes, S, kind, c->stream));
+        } else {
+            for (int s = 0; s < S; ++s)
+                if (done[(size_t)s])
+                    RX_TRY(link_copy(c, frames_out + (size_t)s * frame_stride_bytes, area + (size_t)s * stream_bytes + rx->r_base[(size_t)s] * frame_bytes,
+                                      done[(size_t)s] * frame_bytes, kind, c->stream));
+        }
+    }
+    rx->r_view_first.assign(rx->r_base.begin(), rx->r_base.end());
+    rx->r_view_frames.assign(done.begin(), done.end());
+    bool same_frames = true;
+    for (int s = 1; s < S; ++s) same_frames = same_frames && done[(size_t)s] == done[0];
+    rx->view_ragged = !(same_base && same_frames);
+    if (!rx->view_ragged) { rx->view_base = area + rx->r_base[0] * frame_bytes; rx->view_stride = stream_bytes; rx->view_frames = done[0]; }
+    for (int s = 0; s < S; ++s) {
+        n_frames[s] = done[(size_t)s];
+        rx->r_base[(size_t)s] += done[(size_t)s];
+        rx->r_pending[(size_t)s] = rest[(size_t)s];
+        rx->r_open[(size_t)s] = rest[(size_t)s] > 0 ? 1 : 0;
+        rx->r_count[(size_t)s] = (uint16_t)(rx->r_count[(size_t)s] + done[(size_t)s]);
+    }
+    rx_join(rx);
+    if (mem == SDRHIP_MEM_HOST) RX_TRY(hipStreamSynchronize(c->stream));
+    return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_rx_process_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, size_t in_stride, const uint32_t *tv_sec,
+                                        const uint32_t *tv_usec, uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem)
+{
+    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
+    if (!n_in || !tv_sec || !tv_usec || !n_frames) return fail(SDRHIP_EINVAL, "rx_process_ragged: NULL count, stamp or n_frames array");
+    sdrhip::CtxLock lock_(rx->ctx);
+    return rx_ragged(rx, iq_in, n_in, in_stride, tv_sec, tv_usec, frames_out, frame_stride_bytes, n_frames, mem);
 }
 
 // --------------------------------------------------------------------------- asynchronous host-pointer Rx entry
@@ -811,6 +1163,7 @@ extern "C" int sdrhip_rx_submit(sdrhip_rx *rx, const int16_t *iq_in, size_t n_in
     sdrhip::CtxLock lock_(rx->ctx);
     if (n_in == 0) return SDRHIP_OK;
     if (!iq_in) return fail(SDRHIP_EINVAL, "rx_submit: NULL input");
+    if (rx->diverged) return fail(SDRHIP_EINVAL, "rx_submit: ragged calls left the streams at different frame positions");
     if (rx->abatch.empty()) { rx->abatch.assign(4, sdrhip_rx::Batch()); rx->a_blocks = 1; }
     HIP_TRY(hipSetDevice(rx->ctx->device));
     const int S = rx->nstreams;

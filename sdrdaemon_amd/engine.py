@@ -186,6 +186,14 @@ def _alloc_like(x, shape, dtype_np=np.int16):
     return np.empty(shape, dtype=dtype_np)
 
 
+def _counts(counts, S, n):
+    """per-stream sample counts of a ragged call as a numpy int64 vector, each <= the rows' length n"""
+    cnt = np.asarray(counts.cpu() if _is_torch(counts) else counts, dtype=np.int64).reshape(-1)
+    if cnt.shape[0] != S or (S and (cnt.min() < 0 or cnt.max() > n)):
+        raise ValueError("counts: %d values in 0..%d expected" % (S, n))
+    return cnt
+
+
 def _plan_dict(fn, h):
     p = _lib.DecimPlan()
     check(fn(h, C.byref(p)))
@@ -225,6 +233,29 @@ class Decimators:
                                            _stride_samples(out) if S > 1 else n_res, C.byref(n_out),
                                            MEM_DEVICE if is_t else MEM_HOST))
         return (out[0] if squeeze else out), ss.value
+
+    def decimate_ragged(self, log2decim, fcpos, sample_size, iq, counts, out=None):
+        """sdrhip_decimate_ragged: stream s decimates counts[s] samples of row s of iq (S, >= max(counts), 2).
+        Returns (out (S, max(counts) >> log2decim, 2) -- row s valid up to n_out[s] --, n_out (numpy, S), new_sample_size)."""
+        x, is_t, _ = _bank_view(iq, self.nstreams)
+        S, n = x.shape[0], x.shape[1]
+        cnt = _counts(counts, S, n)
+        mx = int(cnt.max()) if S else 0
+        n_res = (mx >> log2decim) if 0 <= log2decim <= 6 else 0
+        if out is None:
+            if is_t:
+                buf = torch.zeros((S, max((n_res + 3) & ~3, 4), 2), dtype=torch.int16, device=x.device)
+                out = buf[:, :n_res]
+            else:
+                out = np.zeros((S, n_res, 2), dtype=np.int16)
+        if is_t and S > 1 and (x.stride(0) // 2) % 4:
+            raise ValueError("device bank input: per-stream stride must be a multiple of 4 samples")
+        ss = C.c_uint(sample_size)
+        n_out = (C.c_size_t * S)()
+        check(self.ctx.lib.sdrhip_decimate_ragged(self.h, log2decim, fcpos, C.byref(ss), _ptr(x), (C.c_size_t * S)(*cnt.tolist()),
+                                                  _stride_samples(x), _ptr(out), _stride_samples(out) if S > 1 else n_res, n_out,
+                                                  MEM_DEVICE if is_t else MEM_HOST))
+        return out, np.array(n_out[:], dtype=np.int64), ss.value
 
     def last_plan(self):
         """what the last cascade launch was (sdrhip_decimators_last_plan): dict with path ('valu' / 'mfma' / None), span, wps, ..."""
@@ -691,6 +722,70 @@ class RxPipe:
         check(self.ctx.lib.sdrhip_rx_process(self.h, _ptr(x), n, _stride_samples(x), tv_sec, tv_usec, C.c_void_p(0), 0,
                                              C.byref(nf), MEM_DEVICE))
         return self._view(x.device)
+
+    def _ragged_input(self, iq):
+        """_input, with int16 device rows padded to a multiple of 4 samples as well (the library's stride rule).  NOTE: a CUDA
+        tensor whose row stride is not a multiple of 4 samples is COPIED whole into a padded buffer on every call; pass rows
+        allocated with such a stride to avoid the copy."""
+        x, is_t, squeeze = self._input(iq)
+        if is_t and x.shape[0] > 1 and (x.stride(0) // 2) % 4:
+            n = x.shape[1]
+            buf = torch.empty((x.shape[0], (n + 3) & ~3, 2), dtype=x.dtype, device=x.device)
+            buf[:, :n].copy_(x)
+            x = buf[:, :n]
+        return x, is_t, squeeze
+
+    def _ragged_args(self, x, counts, tv_sec, tv_usec):
+        S = x.shape[0]
+        cnt = _counts(counts, S, x.shape[1])
+        sec = np.broadcast_to(np.asarray(tv_sec, dtype=np.uint32), (S,))
+        usec = np.broadcast_to(np.asarray(tv_usec, dtype=np.uint32), (S,))
+        return (cnt, (C.c_size_t * S)(*cnt.tolist()), (C.c_uint32 * S)(*[int(v) for v in sec]), (C.c_uint32 * S)(*[int(v) for v in usec]))
+
+    def process_ragged(self, iq, counts, tv_sec=0, tv_usec=0, out=None):
+        """sdrhip_rx_process_ragged: stream s takes counts[s] samples of row s of iq (S, >= max(counts), 2), stamped tv_sec[s] /
+        tv_usec[s] (scalars apply to every stream).  -> (frames (S, max_frames, 128 + nb_fec, 512) uint8, n_frames numpy (S,)):
+        stream s's frames are frames[s, :n_frames[s]]."""
+        x, is_t, _ = self._ragged_input(iq)
+        S = x.shape[0]
+        cnt, c_cnt, c_sec, c_usec = self._ragged_args(x, counts, tv_sec, tv_usec)
+        cap = max(self.max_frames(int(cnt.max()) if S else 0), 1)
+        fb = (NB_ORIGINAL + self.nb_fec) * UDPSIZE
+        if out is None:
+            out = (torch.empty((S, cap, NB_ORIGINAL + self.nb_fec, UDPSIZE), dtype=torch.uint8, device=x.device) if is_t
+                   else np.empty((S, cap, NB_ORIGINAL + self.nb_fec, UDPSIZE), np.uint8))
+        if out.shape[1] < cap or out.shape[0] != S:
+            raise ValueError("out must hold (S, >= %d, %d, 512) bytes" % (cap, NB_ORIGINAL + self.nb_fec))
+        nf = (C.c_size_t * S)()
+        check(self.ctx.lib.sdrhip_rx_process_ragged(self.h, _ptr(x), c_cnt, _stride_samples(x), c_sec, c_usec, _ptr(out),
+                                                    out.shape[1] * fb, nf, MEM_DEVICE if is_t else MEM_HOST))
+        n_frames = np.array(nf[:], dtype=np.int64)
+        return out[:, :int(n_frames.max()) if S else 0], n_frames
+
+    def frames_view_ragged(self, device="cuda"):
+        """the frames the last call delivered (sdrhip_rx_frames_view_ragged): a list of S uint8 CUDA tensors (n_frames[s], 128 + nb_fec,
+        512) sharing the library's frame area, valid until the next call on this pipe"""
+        S = self.nstreams
+        base, stride = C.c_void_p(0), C.c_size_t(0)
+        first, cnt = (C.c_size_t * S)(), (C.c_size_t * S)()
+        check(self.ctx.lib.sdrhip_rx_frames_view_ragged(self.h, C.byref(base), C.byref(stride), first, cnt))
+        fb = (NB_ORIGINAL + self.nb_fec) * UDPSIZE
+        dev = torch.device(device)
+        return [_DeviceView((base.value or 0) + s * stride.value + first[s] * fb, (cnt[s], NB_ORIGINAL + self.nb_fec, UDPSIZE),
+                            (fb, UDPSIZE, 1), dev, owner=self).torch() if cnt[s] else
+                torch.empty((0, NB_ORIGINAL + self.nb_fec, UDPSIZE), dtype=torch.uint8, device=dev) for s in range(S)]
+
+    def process_view_ragged(self, iq, counts, tv_sec=0, tv_usec=0):
+        """Zero-copy ragged call for CUDA tensors: -> (list of S frame tensors as frames_view_ragged, n_frames numpy (S,))"""
+        x, is_t, _ = self._ragged_input(iq)
+        if not is_t:
+            raise TypeError("process_view_ragged needs a CUDA tensor")
+        S = x.shape[0]
+        _, c_cnt, c_sec, c_usec = self._ragged_args(x, counts, tv_sec, tv_usec)
+        nf = (C.c_size_t * S)()
+        check(self.ctx.lib.sdrhip_rx_process_ragged(self.h, _ptr(x), c_cnt, _stride_samples(x), c_sec, c_usec, C.c_void_p(0), 0, nf,
+                                                    MEM_DEVICE))
+        return self.frames_view_ragged(x.device), np.array(nf[:], dtype=np.int64)
 
     def close(self):
         if self.h:
