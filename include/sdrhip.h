@@ -363,6 +363,38 @@ int sdrhip_rx_frames_view_ragged(const sdrhip_rx *rx, const uint8_t **base, size
 int sdrhip_rx_set_async(sdrhip_rx *rx, int depth, int blocks);
 int sdrhip_rx_submit(sdrhip_rx *rx, const int16_t *iq_in, size_t n_in, size_t in_stride, uint32_t tv_sec, uint32_t tv_usec);
 int sdrhip_rx_collect(sdrhip_rx *rx, uint8_t *frames_out, size_t frame_stride_bytes, size_t max_frames, size_t *n_frames, int wait);
+
+/* Asynchronous ragged entry: the host-fed mode of a host with N sources, each delivering its own block size at its own rate.
+ * sdrhip_rx_submit_ragged appends one block per stream to the batch being filled: stream s contributes n_in[s] samples (0 is
+ * allowed, and so are counts below 2^log2decim).  The ring and the batch size are those of sdrhip_rx_set_async(depth, blocks);
+ * it returns SDRHIP_EBUSY when every batch of the ring is in flight.  Rows: in_stride-strided (in_stride >= the largest count),
+ * or SDRHIP_PACKED: back to back, row s starting at sample sum_{t<s} n_in[t].  sdrhip_rx_set_input_format applies; the counts
+ * stay in samples (an 8-bit sample is 2 bytes).  Packed input that lies wholly inside sdrhip_host_alloc memory is used IN PLACE
+ * (the caller leaves it untouched until the batch is collected); anything else is copied into the pinned staging arena packed:
+ * one memcpy per non-empty row, never the padding between a short row and the stride.
+ * Per stream a batch is exactly one sdrhip_rx_process_ragged call: its count is the sum of the stream's counts over the batch's
+ * blocks, its stamp is the stream's tv_sec[s] / tv_usec[s] of the batch's FIRST block.  Frames, recovery blocks, meta blocks,
+ * frameIndex and the carried filter, frame and counter state are byte for byte what that sequence of synchronous ragged calls
+ * produces (and so what one one-stream pipe per stream produces).  A batch moves what it carries: host to device the packed
+ * sample bytes (sum of the counts x 4, or x 2 for 8-bit input), one copy per run of adjacent memory; device to host
+ * sum_s n_frames[s] x (128 + nb_fec) x 512 bytes in one copy.  Both are counted in "h2d_bytes" / "d2h_bytes".  The per-batch
+ * tables on top are NOT counted: at most 16 x (nstreams + 1) + 16 x (blocks x nstreams) + 16 + 4 x (frames of the batch) bytes
+ * host to device (the packing table, the download's frame list).
+ * sdrhip_rx_collect_ragged returns the OLDEST batch: stream s's n_frames[s] frames (host array of nstreams entries) at
+ * frames_out + s * frame_stride_bytes, frame_stride_bytes >= (largest n_frames) x (128 + nb_fec) x 512 for more than one stream.
+ * Its contract is sdrhip_rx_collect's: SDRHIP_OK = one batch collected (possibly with no frames); SDRHIP_EBUSY = none was
+ * (nothing submitted, or with wait = 0 the oldest batch is still being filled or in flight); wait = 1 blocks outside the context
+ * lock and launches a partly filled batch as it is; a stream with more than max_frames frames leaves the batch uncollected with
+ * n_frames[] filled in and returns SDRHIP_EINVAL.
+ * Refused with SDRHIP_EINVAL, nothing consumed (the next call continues as if the refused one never happened): a NULL count or
+ * stamp array, an in_stride that is neither SDRHIP_PACKED nor >= the largest count, pipelined mode, a ragged submit / collect while
+ * uniform batches are being filled or in flight, sdrhip_rx_submit / sdrhip_rx_collect / sdrhip_rx_process[_ragged] while ragged
+ * batches are (a batch holds one kind; once they are collected the state carries over both ways).  A batch that fails before its
+ * decimator launch is launched again by the next submit / collect; one that fails behind it is dropped, never replayed. */
+#define SDRHIP_PACKED 0 /* in_stride value: rows back to back, row s starts at sample sum_{t<s} n_in[t] */
+int sdrhip_rx_submit_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, size_t in_stride, const uint32_t *tv_sec,
+                            const uint32_t *tv_usec);
+int sdrhip_rx_collect_ragged(sdrhip_rx *rx, uint8_t *frames_out, size_t frame_stride_bytes, size_t max_frames, size_t *n_frames, int wait);
 /* Pinned host memory for the source side (the buffers a DeviceSource pushes): blocks submitted from it skip the staging copy. */
 void *sdrhip_host_alloc(sdrhip_ctx *ctx, size_t bytes);
 void sdrhip_host_free(sdrhip_ctx *ctx, void *p);

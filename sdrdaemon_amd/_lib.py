@@ -36,6 +36,7 @@ EXPORTS = [
     "sdrhip_tx_process_datagrams", "sdrhip_tx_collector",
     "sdrhip_rx_set_input_format", "sdrhip_tx_set_output_format",
     "sdrhip_decimate_ragged", "sdrhip_rx_process_ragged", "sdrhip_rx_frames_view_ragged",
+    "sdrhip_rx_submit_ragged", "sdrhip_rx_collect_ragged",
 ]
 
 
@@ -140,6 +141,8 @@ def load():
     lib.sdrhip_rx_process_ragged.argtypes = [vp, vp, C.POINTER(sz), sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp, sz,
                                              C.POINTER(sz), i]
     lib.sdrhip_rx_frames_view_ragged.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
+    lib.sdrhip_rx_submit_ragged.argtypes = [vp, vp, C.POINTER(sz), sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    lib.sdrhip_rx_collect_ragged.argtypes = [vp, vp, sz, sz, C.POINTER(sz), i]
     lib.sdrhip_testsource_create.argtypes = [vp, i, C.POINTER(vp)]
     lib.sdrhip_testsource_destroy.argtypes = [vp]
     lib.sdrhip_testsource_destroy.restype = None

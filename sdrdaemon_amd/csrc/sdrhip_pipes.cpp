@@ -194,8 +194,19 @@ struct sdrhip_rx {
         uint32_t tv_sec = 0, tv_usec = 0;
         size_t frames = 0, frame_bytes = 0;
         int state = 0;            // 0 free, 1 filling, 2 in flight
+        // ---- a ragged batch (sdrhip_rx_submit_ragged; a batch holds one kind only): blocks of per-stream counts, packed
+        bool ragged = false;
+        struct Run { const char *p; size_t off, bytes; }; // packed bytes of one block: in place at p, or staged at `in` + off (p NULL)
+        std::vector<Run> r_runs;
+        std::vector<size_t> r_cnt;            // [block][stream] counts
+        std::vector<size_t> r_tot;            // per-stream samples so far
+        std::vector<uint32_t> r_sec, r_usec;  // the stamps of the batch's first block
+        size_t r_used = 0;                    // staged bytes in `in`
+        std::vector<size_t> r_frames;         // frames per stream of the launched batch, in stream order in `out`
+        PinnedBuf r_tab;                      // K0p's table, then the frame list of the download
     };
     std::vector<Batch> abatch;
+    DevBuf a_pk, a_din, a_tab, a_frames;      // ragged batches on the device: packed upload, K0p's rows, tables, compacted frames
     int a_blocks = 1;             // blocks per launch
     bool consumed = false;        // set by sdrhip_rx_process once the decimator launch of the call went out (the filter state advanced)
     size_t a_head = 0, a_tail = 0; // next batch to collect / batch being filled
@@ -364,8 +375,9 @@ extern "C" void sdrhip_rx_destroy(sdrhip_rx *rx)
     if (rx->ev_enc) (void)hipEventDestroy(rx->ev_enc);
     for (auto &b : rx->abatch) {
         if (b.done) { (void)hipEventSynchronize(b.done); (void)hipEventDestroy(b.done); }
-        b.in.release(); b.din.release(); b.out.release();
+        b.in.release(); b.din.release(); b.out.release(); b.r_tab.release();
     }
+    rx->a_pk.release(); rx->a_din.release(); rx->a_tab.release(); rx->a_frames.release();
     delete rx;
 }
 
@@ -461,7 +473,15 @@ extern "C" int sdrhip_rx_flush(sdrhip_rx *rx, uint8_t *frames_out, size_t frame_
 }
 
 static int rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, size_t in_stride, const uint32_t *tv_sec,
-                     const uint32_t *tv_usec, uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem);
+                     const uint32_t *tv_usec, uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem, bool batch = false);
+
+// batches of the ring that are being filled or in flight, of the ragged (or the uniform) kind
+static bool rx_has_batches(const sdrhip_rx *rx, bool ragged)
+{
+    for (const auto &b : rx->abatch)
+        if (b.state != 0 && b.ragged == ragged) return true;
+    return false;
+}
 
 extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_in, size_t in_stride, uint32_t tv_sec, uint32_t tv_usec,
                                  uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem)
@@ -469,6 +489,7 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
     if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
     sdrhip::CtxLock lock_(rx->ctx);
     if (n_frames) *n_frames = 0;
+    if (rx_has_batches(rx, true)) return fail(SDRHIP_EINVAL, "rx_process: ragged batches are being filled or in flight: collect them first");
     if (rx->diverged && n_in) {
         // ragged calls left the streams at different frame positions: a ragged call with equal counts and stamps; *n_frames = the
         // largest per-stream count (sdrhip_rx_frames_view_ragged has each)
@@ -798,8 +819,9 @@ static void rx_join(sdrhip_rx *rx)
         if (e_ != hipSuccess) { rx_join(rx); return ::sdrhip::fail(SDRHIP_EDEVICE, "%s: %s", #expr, hipGetErrorString(e_)); } \
     } while (0)
 
+// batch: a ragged asynchronous batch (rx_launch_ragged): int16 device rows that K0p laid out, whatever the input format
 static int rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, size_t in_stride, const uint32_t *tv_sec,
-                     const uint32_t *tv_usec, uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem)
+                     const uint32_t *tv_usec, uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem, bool batch)
 {
     sdrhip_ctx *c = rx->ctx;
     const int S = rx->nstreams, L = rx->cfg.log2decim, R = rx->cfg.nb_fec;
@@ -809,14 +831,15 @@ static int rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, si
     // ---- everything that can be refused is checked before anything is consumed
     if (mem != SDRHIP_MEM_HOST && mem != SDRHIP_MEM_DEVICE) return fail(SDRHIP_EINVAL, "mem must be SDRHIP_MEM_HOST or SDRHIP_MEM_DEVICE");
     if (rx->pipelined) return fail(SDRHIP_EINVAL, "rx_process_ragged: not available in pipelined mode");
-    for (const auto &b : rx->abatch)
-        if (b.state != 0) return fail(SDRHIP_EINVAL, "rx_process_ragged: asynchronous batches are being filled or in flight: collect them first");
+    if (!batch)
+        for (const auto &b : rx->abatch)
+            if (b.state != 0) return fail(SDRHIP_EINVAL, "rx_process_ragged: asynchronous batches are being filled or in flight: collect them first");
     size_t max_in = 0;
     for (int s = 0; s < S; ++s) if (n_in[s] > max_in) max_in = n_in[s];
     if (S == 1) in_stride = max_in;
     if (S > 1 && in_stride < max_in) return fail(SDRHIP_EINVAL, "rx_process_ragged: in_stride smaller than the largest count");
     if (max_in && !iq_in) return fail(SDRHIP_EINVAL, "rx_process_ragged: NULL input");
-    const bool wide8 = rx->in_fmt != IQF_S16;
+    const bool wide8 = rx->in_fmt != IQF_S16 && !batch;
     if (max_in && mem == SDRHIP_MEM_DEVICE && (!aligned16(iq_in) || (S > 1 && (in_stride & (wide8 ? 7 : 3)))))
         return fail(SDRHIP_EALIGN, "rx_process_ragged: device input must be 16-byte aligned, its stride a multiple of %d samples", wide8 ? 8 : 4);
     rx_split(rx);
@@ -1119,6 +1142,129 @@ int rx_launch_batch(sdrhip_rx *rx, sdrhip_rx::Batch &b)
     b.state = 2;
     return SDRHIP_OK;
 }
+
+// a ragged batch: ONE upload per run of adjacent packed memory -> K0p lays the rows out (and widens 8-bit input) -> per stream one
+// sdrhip_rx_process_ragged step of the batch's summed counts with its first block's stamps -> the frames every stream delivered,
+// compacted in stream order -> ONE download of exactly those frames.  Failure rules of rx_launch_batch: everything that can fail
+// for want of memory happens before the decimator launch (the batch is launched again later); a failure behind it (rx->consumed)
+// drops the batch.
+int rx_launch_ragged(sdrhip_rx *rx, sdrhip_rx::Batch &b)
+{
+    sdrhip_ctx *c = rx->ctx;
+    const int S = rx->nstreams, L = rx->cfg.log2decim;
+    const size_t esz = rx->in_fmt == IQF_S16 ? 4 : 2;
+    const size_t nblk = b.r_cnt.size() / (size_t)S;
+    size_t max_t = 0, nseg = 0, packed = 0, sum_done = 0;
+    for (size_t i = 0; i < b.r_cnt.size(); ++i) { packed += b.r_cnt[i]; nseg += b.r_cnt[i] ? 1 : 0; }
+    for (int s = 0; s < S; ++s) if (b.r_tot[(size_t)s] > max_t) max_t = b.r_tot[(size_t)s];
+    const size_t dstride = (max_t + 7) & ~(size_t)7;
+    const size_t fb = (size_t)(SDRHIP_NB_ORIGINAL + rx->cfg.nb_fec) * SDRHIP_UDPSIZE;
+    // (the frames every stream completes, counted as rx_ragged counts them: the buffers are sized before anything is consumed)
+    for (int s = 0; s < S; ++s) {
+        const uint64_t pend = rx->diverged ? rx->r_pending[(size_t)s] : rx->pending_samples;
+        sum_done += (size_t)((pend + (b.r_tot[(size_t)s] >> L)) / SDRHIP_SAMPLES_PER_FRAME);
+    }
+    const size_t rows_bytes = (size_t)(S + 1) * sizeof(PackRow), segs_bytes = nseg * sizeof(PackSeg);
+    const size_t list_off = (rows_bytes + segs_bytes + 15) & ~(size_t)15;
+    int rc;
+    if ((rc = b.r_tab.reserve(list_off + sum_done * 4 + 16))) return rc; // (waits for the table upload of this batch's last use)
+    if (list_off + sum_done * 4 + 16 > rx->a_tab.cap || packed * esz + 64 > rx->a_pk.cap || (size_t)S * dstride * 4 + 16 > rx->a_din.cap ||
+        sum_done * fb > rx->a_frames.cap)
+        HIP_TRY(hipStreamSynchronize(c->stream)); // (a device buffer grows: batches in flight may still use the old one)
+    if ((rc = rx->a_tab.reserve(list_off + sum_done * 4 + 16))) return rc;
+    if ((rc = rx->a_pk.reserve(packed * esz + 64))) return rc;
+    if ((rc = rx->a_din.reserve((size_t)S * dstride * 4 + 16))) return rc;
+    if (sum_done && (rc = b.out.reserve(sum_done * fb))) return rc;
+    if (sum_done && (rc = rx->a_frames.reserve(sum_done * fb))) return rc;
+    if (!b.done && hipEventCreateWithFlags(&b.done, hipEventDisableTiming) != hipSuccess) { b.done = nullptr; return fail(SDRHIP_EDEVICE, "hipEventCreate"); }
+
+    // ---- K0p's table: segments stream by stream (block order inside), sources at their packed offsets (block-major, stream-minor)
+    PackRow *rows = b.r_tab.as<PackRow>();
+    PackSeg *segs = reinterpret_cast<PackSeg *>(b.r_tab.as<char>() + rows_bytes);
+    std::vector<uint64_t> src(b.r_cnt.size());
+    {
+        uint64_t acc = 0;
+        for (size_t i = 0; i < b.r_cnt.size(); ++i) { src[i] = acc; acc += b.r_cnt[i]; }
+    }
+    uint32_t k = 0;
+    uint64_t wg = 0;
+    for (int s = 0; s < S; ++s) {
+        PackRow &r = rows[s];
+        r.seg0 = k; r.wg0 = (uint32_t)wg; r.total = (uint32_t)b.r_tot[(size_t)s];
+        uint32_t dst = 0;
+        for (size_t blk = 0; blk < nblk; ++blk) {
+            const size_t i = blk * (size_t)S + (size_t)s, n = b.r_cnt[i];
+            if (!n) continue;
+            segs[k].src = src[i]; segs[k].dst = dst; segs[k].n = (uint32_t)n;
+            dst += (uint32_t)n;
+            ++k;
+        }
+        r.nseg = k - r.seg0;
+        wg += (b.r_tot[(size_t)s] + UNPACK_WG_SAMPLES - 1) / UNPACK_WG_SAMPLES;
+    }
+    rows[S].seg0 = k; rows[S].nseg = 0; rows[S].wg0 = (uint32_t)wg; rows[S].total = 0;
+    if (wg > 0x7fffffffu) return fail(SDRHIP_EINVAL, "rx batch: too many samples for one launch");
+
+    // ---- uploads: the packed samples, one copy per run of adjacent memory (staged runs are adjacent in the arena), then the table
+    uint8_t *pk = rx->a_pk.as<uint8_t>();
+    size_t off = 0;
+    for (size_t i = 0; i < b.r_runs.size();) {
+        const char *p0 = b.r_runs[i].p ? b.r_runs[i].p : b.in.as<char>() + b.r_runs[i].off;
+        size_t n = b.r_runs[i].bytes, j = i + 1;
+        for (; j < b.r_runs.size(); ++j) {
+            const char *pj = b.r_runs[j].p ? b.r_runs[j].p : b.in.as<char>() + b.r_runs[j].off;
+            if ((b.r_runs[j].p == nullptr) != (b.r_runs[i].p == nullptr) || pj != p0 + n) break;
+            n += b.r_runs[j].bytes;
+        }
+        HIP_TRY(link_copy(c, pk + off, p0, n, hipMemcpyHostToDevice, c->stream));
+        off += n;
+        i = j;
+    }
+    b.in.mark(c->stream);
+    HIP_TRY(hipMemcpyAsync(rx->a_tab.p, b.r_tab.p, rows_bytes + segs_bytes, hipMemcpyHostToDevice, c->stream)); // (not counted: a table)
+    b.r_tab.mark(c->stream);
+    const PackRow *rows_dev = rx->a_tab.as<PackRow>();
+    const PackSeg *segs_dev = reinterpret_cast<const PackSeg *>(rx->a_tab.as<char>() + rows_bytes);
+    {
+        KTimer kt(c, SDRHIP_K_CONVERT);
+        const hipError_t e = launch_unpack_packed(rx->in_fmt, pk, rx->a_din.as<int16_t>(), dstride, rows_dev, segs_dev, S, (unsigned)wg, c->stream);
+        if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "unpack launch: %s", hipGetErrorString(e));
+    }
+
+    // ---- the batch as one ragged step
+    std::vector<size_t> nf((size_t)S, 0);
+    rc = rx_ragged(rx, rx->a_din.as<int16_t>(), b.r_tot.data(), dstride, b.r_sec.data(), b.r_usec.data(), nullptr, 0, nf.data(),
+                   SDRHIP_MEM_DEVICE, true);
+    if (rc) {
+        if (rx->consumed) b.state = 0; // consumed and lost: never replayed (the pipe's own error stands)
+        return rc;
+    }
+
+    // ---- download: the delivered frames of every stream, compacted in stream order, in ONE copy
+    int32_t *list = reinterpret_cast<int32_t *>(b.r_tab.as<char>() + list_off);
+    size_t nl = 0;
+    hipError_t e = hipSuccess;
+    for (int s = 0; s < S && e == hipSuccess; ++s) {
+        if (nl + nf[(size_t)s] > sum_done) { e = hipErrorInvalidValue; break; } // (cannot happen: the count above is the pipe's own)
+        for (size_t f = 0; f < nf[(size_t)s]; ++f) list[nl++] = (int32_t)((size_t)s * rx->cap_frames + rx->r_view_first[(size_t)s] + f);
+    }
+    if (e == hipSuccess && nl) e = hipMemcpyAsync(rx->a_tab.as<char>() + list_off, list, nl * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && nl) {
+        b.r_tab.mark(c->stream);
+        e = launch_frame_gather(rx->work.as<uint8_t>(), fb, reinterpret_cast<const int32_t *>(rx->a_tab.as<char>() + list_off), nl,
+                                rx->a_frames.as<uint8_t>(), c->stream);
+    }
+    if (e == hipSuccess && nl) e = link_copy(c, b.out.p, rx->a_frames.p, nl * fb, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipEventRecord(b.done, c->stream);
+    if (e != hipSuccess) {
+        b.state = 0; // consumed and lost: never replayed
+        return fail(SDRHIP_EDEVICE, "rx ragged batch download: %s (the batch's %zu frames are lost)", hipGetErrorString(e), nl);
+    }
+    b.r_frames.assign(nf.begin(), nf.end());
+    b.frame_bytes = fb;
+    b.state = 2;
+    return SDRHIP_OK;
+}
 } // namespace
 
 extern "C" void *sdrhip_host_alloc(sdrhip_ctx *c, size_t bytes)
@@ -1151,7 +1297,7 @@ extern "C" int sdrhip_rx_set_async(sdrhip_rx *rx, int depth, int blocks)
     if (depth < 1 || depth > 64 || blocks < 1 || blocks > 1024) return fail(SDRHIP_EINVAL, "rx_set_async: depth 1..64, blocks 1..1024");
     for (auto &b : rx->abatch)
         if (b.state != 0) return fail(SDRHIP_EINVAL, "rx_set_async: batches are in flight: collect them first");
-    for (auto &b : rx->abatch) { if (b.done) (void)hipEventDestroy(b.done); b.in.release(); b.din.release(); b.out.release(); }
+    for (auto &b : rx->abatch) { if (b.done) (void)hipEventDestroy(b.done); b.in.release(); b.din.release(); b.out.release(); b.r_tab.release(); }
     rx->abatch.assign((size_t)depth, sdrhip_rx::Batch());
     rx->a_blocks = blocks; rx->a_head = rx->a_tail = 0;
     return SDRHIP_OK;
@@ -1164,6 +1310,7 @@ extern "C" int sdrhip_rx_submit(sdrhip_rx *rx, const int16_t *iq_in, size_t n_in
     if (n_in == 0) return SDRHIP_OK;
     if (!iq_in) return fail(SDRHIP_EINVAL, "rx_submit: NULL input");
     if (rx->diverged) return fail(SDRHIP_EINVAL, "rx_submit: ragged calls left the streams at different frame positions");
+    if (rx_has_batches(rx, true)) return fail(SDRHIP_EINVAL, "rx_submit: ragged batches are being filled or in flight: collect them first");
     if (rx->abatch.empty()) { rx->abatch.assign(4, sdrhip_rx::Batch()); rx->a_blocks = 1; }
     HIP_TRY(hipSetDevice(rx->ctx->device));
     const int S = rx->nstreams;
@@ -1171,7 +1318,7 @@ extern "C" int sdrhip_rx_submit(sdrhip_rx *rx, const int16_t *iq_in, size_t n_in
     sdrhip_rx::Batch &b = rx->abatch[rx->a_tail % rx->abatch.size()];
     if (b.state == 2) return fail(SDRHIP_EBUSY, "rx_submit: every batch of the ring is in flight: sdrhip_rx_collect first");
     if (b.state == 0) {
-        b.blocks.clear(); b.strides.clear(); b.n_in = 0; b.tv_sec = tv_sec; b.tv_usec = tv_usec; b.state = 1;
+        b.blocks.clear(); b.strides.clear(); b.n_in = 0; b.tv_sec = tv_sec; b.tv_usec = tv_usec; b.state = 1; b.ragged = false;
         b.in_cap = 0; // no staged rows yet: the first pageable block of this batch (re)claims the arena
     }
     const size_t esz = rx->in_fmt == IQF_S16 ? 4 : 2; // bytes per sample (sdrhip_rx_set_input_format)
@@ -1211,38 +1358,47 @@ extern "C" int sdrhip_rx_submit(sdrhip_rx *rx, const int16_t *iq_in, size_t n_in
     return SDRHIP_OK;
 }
 
-extern "C" int sdrhip_rx_collect(sdrhip_rx *rx, uint8_t *frames_out, size_t frame_stride_bytes, size_t max_frames, size_t *n_frames, int wait)
+// the oldest batch of the ring once it has finished (wait = 1: launches it when it is still being filled, then waits OUTSIDE the
+// context lock: the submitting thread -- the reference's source / main thread -- keeps feeding the ring while the collecting thread
+// -- its transmit thread -- sleeps on the oldest batch's event)
+static int rx_wait_oldest(sdrhip_rx *rx, std::unique_lock<std::recursive_mutex> &lock_, int wait, const char *who, sdrhip_rx::Batch **bp)
 {
-    if (!rx || !n_frames) return fail(SDRHIP_EINVAL, "rx_collect: NULL argument");
-    // (the wait for a batch happens OUTSIDE the context lock: the submitting thread -- the reference's source / main thread -- keeps
-    // feeding the ring while the collecting thread -- its transmit thread -- sleeps on the oldest batch's event)
-    std::unique_lock<std::recursive_mutex> lock_(rx->ctx->mtx);
-    *n_frames = 0;
-    if (rx->abatch.empty()) return fail(SDRHIP_EBUSY, "rx_collect: nothing was submitted");
-    HIP_TRY(hipSetDevice(rx->ctx->device));
-    sdrhip_rx::Batch *bp = nullptr;
     for (;;) {
         sdrhip_rx::Batch &h = rx->abatch[rx->a_head % rx->abatch.size()];
-        if (h.state == 0) return fail(SDRHIP_EBUSY, "rx_collect: nothing was submitted"); // (SDRHIP_OK always means: one batch collected, *n_frames of it -- possibly 0)
+        if (h.state == 0) return fail(SDRHIP_EBUSY, "%s: nothing was submitted", who); // (SDRHIP_OK always means: one batch collected, *n_frames of it -- possibly 0)
         if (h.state == 1) {
-            if (!wait) return fail(SDRHIP_EBUSY, "rx_collect: the oldest batch is still being filled (wait = 1 launches it as it is)");
-            int rc = rx_launch_batch(rx, h); // a partly filled batch goes out as it is (end of stream)
+            if (!wait) return fail(SDRHIP_EBUSY, "%s: the oldest batch is still being filled (wait = 1 launches it as it is)", who);
+            int rc = h.ragged ? rx_launch_ragged(rx, h) : rx_launch_batch(rx, h); // a partly filled batch goes out as it is (end of stream)
             if (rc) return rc;
             ++rx->a_tail;
         }
         const hipError_t q = hipEventQuery(h.done);
-        if (q == hipSuccess) { bp = &h; break; }
+        if (q == hipSuccess) { *bp = &h; break; }
         if (q != hipErrorNotReady) return fail(SDRHIP_EDEVICE, "hipEventQuery: %s", hipGetErrorString(q));
-        if (!wait) return fail(SDRHIP_EBUSY, "rx_collect: the oldest batch is still in flight");
+        if (!wait) return fail(SDRHIP_EBUSY, "%s: the oldest batch is still in flight", who);
         const size_t head = rx->a_head;
         hipEvent_t ev = h.done;
         lock_.unlock();
         const hipError_t w = hipEventSynchronize(ev);
         lock_.lock();
         if (w != hipSuccess) return fail(SDRHIP_EDEVICE, "hipEventSynchronize: %s", hipGetErrorString(w));
-        if (rx->a_head == head) { bp = &rx->abatch[head % rx->abatch.size()]; break; }
+        if (rx->a_head == head) { *bp = &rx->abatch[head % rx->abatch.size()]; break; }
         // (another thread collected that batch meanwhile: look at the new head)
     }
+    return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_rx_collect(sdrhip_rx *rx, uint8_t *frames_out, size_t frame_stride_bytes, size_t max_frames, size_t *n_frames, int wait)
+{
+    if (!rx || !n_frames) return fail(SDRHIP_EINVAL, "rx_collect: NULL argument");
+    std::unique_lock<std::recursive_mutex> lock_(rx->ctx->mtx);
+    *n_frames = 0;
+    if (rx->abatch.empty()) return fail(SDRHIP_EBUSY, "rx_collect: nothing was submitted");
+    if (rx_has_batches(rx, true)) return fail(SDRHIP_EINVAL, "rx_collect: ragged batches are being filled or in flight: use sdrhip_rx_collect_ragged");
+    HIP_TRY(hipSetDevice(rx->ctx->device));
+    sdrhip_rx::Batch *bp = nullptr;
+    int rc = rx_wait_oldest(rx, lock_, wait, "rx_collect", &bp);
+    if (rc) return rc;
     sdrhip_rx::Batch &b = *bp;
     const int S = rx->nstreams;
     if (b.frames > max_frames) { // (the batch stays where it is: call again with room for *n_frames frames per stream)
@@ -1256,6 +1412,113 @@ extern "C" int sdrhip_rx_collect(sdrhip_rx *rx, uint8_t *frames_out, size_t fram
         for (int s = 0; s < S; ++s) memcpy(frames_out + (size_t)s * (S > 1 ? frame_stride_bytes : row), b.out.as<char>() + (size_t)s * row, row);
     }
     *n_frames = b.frames;
+    b.state = 0;
+    ++rx->a_head;
+    return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_rx_submit_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, size_t in_stride, const uint32_t *tv_sec,
+                                       const uint32_t *tv_usec)
+{
+    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
+    if (!n_in || !tv_sec || !tv_usec) return fail(SDRHIP_EINVAL, "rx_submit_ragged: NULL count or stamp array");
+    sdrhip::CtxLock lock_(rx->ctx);
+    // ---- everything that can be refused is checked before anything is consumed
+    const int S = rx->nstreams;
+    size_t max_in = 0, sum = 0;
+    for (int s = 0; s < S; ++s) { sum += n_in[s]; if (n_in[s] > max_in) max_in = n_in[s]; }
+    if (in_stride != SDRHIP_PACKED && in_stride < max_in)
+        return fail(SDRHIP_EINVAL, "rx_submit_ragged: in_stride is neither SDRHIP_PACKED nor at least the largest count");
+    if (sum && !iq_in) return fail(SDRHIP_EINVAL, "rx_submit_ragged: NULL input");
+    if (rx->pipelined) return fail(SDRHIP_EINVAL, "rx_submit_ragged: not available in pipelined mode");
+    if (rx_has_batches(rx, false)) return fail(SDRHIP_EINVAL, "rx_submit_ragged: uniform batches are being filled or in flight: collect them first");
+    if (rx->abatch.empty()) { rx->abatch.assign(4, sdrhip_rx::Batch()); rx->a_blocks = 1; }
+    sdrhip_rx::Batch &b = rx->abatch[rx->a_tail % rx->abatch.size()];
+    if (b.state == 2) return fail(SDRHIP_EBUSY, "rx_submit_ragged: every batch of the ring is in flight: sdrhip_rx_collect_ragged first");
+    for (int s = 0; s < S; ++s) // (K0p's table holds 32-bit row positions)
+        if ((b.state == 1 ? b.r_tot[(size_t)s] : 0) + n_in[s] > (size_t)0xffffffffu - UNPACK_WG_SAMPLES)
+            return fail(SDRHIP_EINVAL, "rx_submit_ragged: a stream's batch would exceed 2^32 - 4096 samples");
+    HIP_TRY(hipSetDevice(rx->ctx->device));
+    const size_t esz = rx->in_fmt == IQF_S16 ? 4 : 2; // bytes per sample (sdrhip_rx_set_input_format)
+    const char *src = reinterpret_cast<const char *>(iq_in);
+    const bool inplace = in_stride == SDRHIP_PACKED && sum && host_is_pinned(iq_in, sum * esz);
+    if (sum && !inplace) { // (the arena: the staged blocks of the batch back to back, packed)
+        const size_t used = b.state == 1 ? b.r_used : 0, need = used + sum * esz;
+        if (used == 0) {
+            const size_t cap = (size_t)rx->a_blocks * sum * esz > need ? (size_t)rx->a_blocks * sum * esz : need;
+            int rc = b.in.reserve(cap); // (waits for the upload of the batch that used this buffer last)
+            if (rc) return rc;
+        } else if (need > b.in.cap) {
+            PinnedBuf bigger;
+            int rc = bigger.reserve(2 * need);
+            if (rc) return rc;
+            memcpy(bigger.p, b.in.p, used);
+            b.in.release();
+            b.in = bigger;
+        }
+    }
+    if (b.state == 0) { // the batch's first block: its stamps are the batch's
+        b.ragged = true; b.state = 1;
+        b.r_runs.clear(); b.r_cnt.clear(); b.r_used = 0;
+        b.r_tot.assign((size_t)S, 0);
+        b.r_sec.assign(tv_sec, tv_sec + S); b.r_usec.assign(tv_usec, tv_usec + S);
+    }
+    if (inplace) { // in place: the caller keeps it untouched until the batch is collected
+        b.r_runs.push_back(sdrhip_rx::Batch::Run{src, 0, sum * esz});
+    } else if (sum) { // staged packed: one memcpy per non-empty row, never the padding of a strided row
+        char *dst = b.in.as<char>() + b.r_used;
+        size_t soff = 0;
+        for (int s = 0; s < S; ++s) {
+            const size_t n = n_in[s];
+            const char *row = in_stride == SDRHIP_PACKED ? src + soff : src + (size_t)s * in_stride * esz;
+            if (n) memcpy(dst, row, n * esz);
+            dst += n * esz;
+            soff += n * esz;
+        }
+        b.r_runs.push_back(sdrhip_rx::Batch::Run{nullptr, b.r_used, sum * esz});
+        b.r_used += sum * esz;
+    }
+    b.r_cnt.insert(b.r_cnt.end(), n_in, n_in + S);
+    for (int s = 0; s < S; ++s) b.r_tot[(size_t)s] += n_in[s];
+    if ((int)(b.r_cnt.size() / (size_t)S) >= rx->a_blocks) {
+        int rc = rx_launch_ragged(rx, b);
+        if (rc) return rc;
+        ++rx->a_tail;
+    }
+    return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_rx_collect_ragged(sdrhip_rx *rx, uint8_t *frames_out, size_t frame_stride_bytes, size_t max_frames, size_t *n_frames,
+                                        int wait)
+{
+    if (!rx || !n_frames) return fail(SDRHIP_EINVAL, "rx_collect_ragged: NULL argument");
+    std::unique_lock<std::recursive_mutex> lock_(rx->ctx->mtx);
+    const int S = rx->nstreams;
+    for (int s = 0; s < S; ++s) n_frames[s] = 0;
+    if (rx->abatch.empty()) return fail(SDRHIP_EBUSY, "rx_collect_ragged: nothing was submitted");
+    if (rx_has_batches(rx, false)) return fail(SDRHIP_EINVAL, "rx_collect_ragged: uniform batches are being filled or in flight: use sdrhip_rx_collect");
+    HIP_TRY(hipSetDevice(rx->ctx->device));
+    sdrhip_rx::Batch *bp = nullptr;
+    int rc = rx_wait_oldest(rx, lock_, wait, "rx_collect_ragged", &bp);
+    if (rc) return rc;
+    sdrhip_rx::Batch &b = *bp;
+    size_t most = 0;
+    for (int s = 0; s < S; ++s) if (b.r_frames[(size_t)s] > most) most = b.r_frames[(size_t)s];
+    if (most > max_frames) { // (the batch stays where it is: call again with room for the largest n_frames[s])
+        for (int s = 0; s < S; ++s) n_frames[s] = b.r_frames[(size_t)s];
+        return fail(SDRHIP_EINVAL, "rx_collect_ragged: a stream of the batch holds %zu frames, frames_out has room for %zu", most, max_frames);
+    }
+    if (most) {
+        if (!frames_out) return fail(SDRHIP_EINVAL, "rx_collect_ragged: NULL frames_out");
+        if (S > 1 && frame_stride_bytes < most * b.frame_bytes) return fail(SDRHIP_EINVAL, "rx_collect_ragged: frame stride too small");
+        size_t off = 0;
+        for (int s = 0; s < S; ++s) {
+            const size_t row = b.r_frames[(size_t)s] * b.frame_bytes;
+            if (row) memcpy(frames_out + (size_t)s * frame_stride_bytes, b.out.as<char>() + off, row);
+            off += row;
+        }
+    }
+    for (int s = 0; s < S; ++s) n_frames[s] = b.r_frames[(size_t)s];
     b.state = 0;
     ++rx->a_head;
     return SDRHIP_OK;

@@ -644,6 +644,7 @@ class RxPipe:
         self._async_batches = []
         self._async_fill = [0, 0]
         self._async_last = 0
+        self._rg_batches, self._rg_fill = [], [np.zeros(self.nstreams, np.int64), 0]  # (the same for ragged batches, per stream)
 
     def submit(self, iq, tv_sec=0, tv_usec=0):
         """one block of host samples per stream (numpy; memory from Context.host_alloc is used in place); returns at once.
@@ -692,6 +693,81 @@ class RxPipe:
             self._async_last = fill[0]
             self._async_fill = [0, 0]
         return out[:, :nf.value]
+
+    # ---- asynchronous ragged entry (sdrhip_rx_submit_ragged / sdrhip_rx_collect_ragged)
+    def submit_ragged(self, iq, counts, tv_sec=None, tv_usec=None):
+        """one block per stream with its own count, returns at once.  iq: numpy rows (S, >= max(counts), 2) -- stream s takes
+        counts[s] samples of row s -- or the packed samples, 1-D or (sum(counts), 2), stream after stream (memory from
+        Context.host_alloc is used in place; keep it untouched until the batch is collected).  tv_sec / tv_usec: per stream or
+        scalars (None = 0).  Raises SdrHipError(code SDRHIP_EBUSY = -6) when every batch of the ring is in flight."""
+        if _is_torch(iq):
+            raise TypeError("submit_ragged takes host memory")
+        S = self.nstreams
+        a = np.asarray(iq)
+        it = np.dtype(self._in_dtype).itemsize
+        if a.dtype != self._in_dtype:
+            raise TypeError("numpy input must be %s" % np.dtype(self._in_dtype).name)
+        if a.ndim == 3:  # rows, with their stride (rows of a bigger array are passed in place)
+            if not (a.shape[0] == S and a.shape[2] == 2 and a.strides[2] == it and a.strides[1] == 2 * it and a.strides[0] % (2 * it) == 0
+                    and a.strides[0] > 0):
+                a = np.ascontiguousarray(a)
+                if a.shape[0] != S or a.shape[2] != 2:
+                    raise ValueError("expected shape (%d, n, 2)" % S)
+            cnt = _counts(counts, S, a.shape[1])
+            stride = a.strides[0] // (2 * it) if a.shape[1] else 0
+            if stride < (int(cnt.max()) if S else 0):
+                raise ValueError("rows shorter than the largest count")
+            stride = max(stride, 1)
+        elif a.ndim in (1, 2):  # packed
+            if a.ndim == 2 and a.shape[1] != 2:
+                raise ValueError("packed input: (sum(counts), 2) or 1-D")
+            a = np.ascontiguousarray(a)
+            cnt = _counts(counts, S, a.size // 2)
+            if int(cnt.sum()) * 2 != a.size:
+                raise ValueError("packed input holds %d samples, the counts sum to %d" % (a.size // 2, int(cnt.sum())))
+            stride = 0  # SDRHIP_PACKED
+        else:
+            raise ValueError("expected rows (%d, n, 2) or packed samples" % S)
+        sec = np.broadcast_to(np.asarray(0 if tv_sec is None else tv_sec, dtype=np.uint32), (S,))
+        usec = np.broadcast_to(np.asarray(0 if tv_usec is None else tv_usec, dtype=np.uint32), (S,))
+        if not hasattr(self, "_async_batches"):  # (the library's default ring: 4 batches of one block)
+            self._async_blocks, self._async_batches, self._async_fill, self._async_last = 1, [], [0, 0], 0
+        if not hasattr(self, "_rg_fill"):
+            self._rg_batches, self._rg_fill = [], [np.zeros(S, np.int64), 0]
+        check(self.ctx.lib.sdrhip_rx_submit_ragged(self.h, _ptr(a), (C.c_size_t * S)(*cnt.tolist()), stride,
+                                                   (C.c_uint32 * S)(*[int(v) for v in sec]), (C.c_uint32 * S)(*[int(v) for v in usec])))
+        self._rg_fill[0] = self._rg_fill[0] + cnt
+        self._rg_fill[1] += 1
+        if self._rg_fill[1] >= self._async_blocks:  # (the library launched the batch)
+            self._rg_batches.append(self._rg_fill[0])
+            self._rg_fill = [np.zeros(S, np.int64), 0]
+
+    def collect_ragged(self, wait=True, max_frames=None):
+        """-> the frames of the oldest ragged batch: a list of S arrays (n_s, 128 + nb_fec, 512), n_s possibly 0; None when no
+        batch was collected (nothing submitted, or with wait = False the oldest batch is still in flight / being filled)"""
+        S = self.nstreams
+        batches = getattr(self, "_rg_batches", [])
+        fill = getattr(self, "_rg_fill", [np.zeros(S, np.int64), 0])
+        oldest = batches[0] if batches else fill[0]
+        cap = max_frames if max_frames is not None else int(oldest.max() if S else 0) // (SAMPLES_PER_FRAME << self.cfg.log2decim) + 2
+        cap = max(cap, 1)
+        fb = (NB_ORIGINAL + self.nb_fec) * UDPSIZE
+        nf = (C.c_size_t * S)()
+        for _ in range(2):  # (a batch bigger than the guess is asked for again with room for its largest stream)
+            out = np.empty((S, cap, NB_ORIGINAL + self.nb_fec, UDPSIZE), np.uint8)
+            rc = self.ctx.lib.sdrhip_rx_collect_ragged(self.h, _ptr(out), cap * fb, cap, nf, 1 if wait else 0)
+            if rc == -1 and max_frames is None and S and max(nf[:]) > cap:
+                cap = max(nf[:])
+                continue
+            break
+        if rc == -6:
+            return None
+        check(rc)
+        if batches:
+            batches.pop(0)
+        elif fill[1]:  # (wait = True sent the partly filled batch out as it was)
+            self._rg_fill = [np.zeros(S, np.int64), 0]
+        return [out[s, :nf[s]] for s in range(S)]
 
     def process(self, iq, tv_sec=0, tv_usec=0, out=None):
         """-> frames (S, n_frames, 128 + nb_fec, 512) uint8 (squeezed for one stream)"""
