@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- headline metric of BASELINE.json on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N > 1: either under python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ..., or as the
      plain command above: without WORLD_SIZE in the environment it launches the N ranks itself)
+
+A plain run does what the headline figure needs and no more: set-up, pre-roll, the W warm-up steps, the K timed steps,
+--dump-outputs if given, and the result line (its `roofline` comes from the HIP events of the timed steps and the committed
+PMC passes).  --full adds everything that takes runs of its own: `verified` (the output check behind the timed region),
+`box` (socket power / shader clock over more steps of the same call), at N = 1 the `configs` lines and the CPU baselines.
 
 Workload (config.workload): BASELINE.json configs[2] -- TestSource-shaped 16-bit IQ streams,
 decimate by 16 centred (Decimators::decimate16_cen over IntHalfbandFilterEO1) + UDPSinkFEC
@@ -16,7 +21,7 @@ streams are continuous across steps (filter state and partial frames carry over)
 --streams N fixes the TOTAL number of streams of the job (the same 64 streams at
 2 / 4 / 8 GPUs, stream s on rank s mod G): "scaling" is then "strong"; that is the default for
 --gpus > 1 (64 streams = configs[4]); --streams 0 gives every rank 8 streams ("weak"), which is
-also what the one-GPU headline run does.  At N = 1 the line also carries `configs`: the other single-GPU
+also what the one-GPU headline run does.  At N = 1 a --full line also carries `configs`: the other single-GPU
 configurations of BASELINE.json measured in the same run (configs[1] decimate16_cen alone,
 configs[2] as ONE stream of 2^27 samples, configs[3] the Tx pipe with a different random
 24-erasure pattern in every frame), each with its own roofline object.
@@ -831,12 +836,15 @@ def main():
                          "whenever --gpus > 1 (SURVEY.md 8e: the same 64 streams at 2 / 4 / 8 GPUs), 8 streams on the one GPU at "
                          "--gpus 1 (the headline step); 0 = 8 streams per GPU whatever N (weak scaling); the environment variable "
                          "SDRHIP_BENCH_STREAMS sets the default for a driver that cannot add flags")
-    ap.add_argument("--no-configs", action="store_true", help="skip the extra single-GPU configurations of the `configs` key")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, run everything that takes runs of its own: the output check behind the timed region "
+                         "(`verified`), the power / clock sample (`box`), at N = 1 the other configurations (`configs`) and the CPU baselines")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the extra single-GPU configurations of the `configs` key")
     ap.add_argument("--input", choices=["hash", "noise", "testsource"], default="hash",
                     help="hash: counter-based full-scale uniform noise (tests/signals.py) -- the input of the committed reference digests, "
                          "so the run can verify its own output; noise: torch.randint; testsource: the library's GPU TestSource bank")
-    ap.add_argument("--no-verify", action="store_true", help="skip the output check behind the timed region")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg (0 = skip)")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the output check behind the timed region")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: budget of the cpu_baseline leg (0 = skip)")
     ap.add_argument("--preroll-seconds", type=float, default=0.25,
                     help="untimed run-in of the same step before the W warm-up steps (the GPU's clocks ramp over the first "
                          "~60 ms of load: with a small W the timed steps would measure that ramp)")
@@ -846,7 +854,7 @@ def main():
                          "the encoder's timers stay on every 4th step (an event pair costs the stream ~3.5 us: tools/experiments_r06/timer_cost.py)")
     ap.add_argument("--no-kernel-timing", action="store_true",
                     help="diagnostic: leave the per-kernel HIP events out of the timed region (roofline fields become null)")
-    ap.add_argument("--no-box-state", action="store_true", help="do not sample socket power / shader clock (amdsmi) beside the timed region")
+    ap.add_argument("--no-box-state", action="store_true", help="--full: do not sample socket power / shader clock (amdsmi) behind the timed region")
     ap.add_argument("--force-dist", action="store_true",
                     help="N = 1 only: go through the N > 1 code path anyway (init_process_group, barriers, device-tensor all_reduce) -- "
                          "executes the nccl = RCCL branch on a one-GPU box")
@@ -967,7 +975,7 @@ def main():
     # region: the SMU's socket power is a filtered value that takes ~0.4 s of load to settle (a 60-ms timed region reads the ramp:
     # 680 W on a box that settles at 1370 W), and the queries themselves should not sit beside the measurement.
     box_state = None
-    if rank == 0 and not args.no_box_state:
+    if rank == 0 and args.full and not args.no_box_state:
         box = BoxState(local, period_s=0.01).start()
         t_s = time.perf_counter()
         while time.perf_counter() - t_s < 0.8:
@@ -981,7 +989,7 @@ def main():
             box_state["over"] = "the second half of 0.8 s of the same step, back to back, right behind the timed region (untimed)"
     plan = rx.last_plan()
     kname = decim_kernel_name(plan)
-    verified = None if args.no_verify else verify_step(ctx, x, ids, args.input)
+    verified = verify_step(ctx, x, ids, args.input) if args.full and not args.no_verify else None
     # the only collectives of the job: MAX of the elapsed time, SUM of the samples (8 bytes each, reporting only)
     elapsed, total_samples = sharding.aggregate(elapsed, float(S) * n * args.steps, dist,
                                                 dev if args.backend == "nccl" else torch.device("cpu"), force=args.force_dist)
@@ -1038,12 +1046,12 @@ def main():
             tl = lane_ops / (avg_ms * 1e-3) / 1e12
             res["roofline"]["valu"] = {"achieved": round(tl, 2), "peak": round(VALU_PEAK_TLANEOPS, 2), "unit": "T lane-ops/s",
                                        "frac": round(tl / VALU_PEAK_TLANEOPS, 4), "lane_ops_per_sample": round(lane_ops / per_launch_samples, 2)}
-        if world == 1 and not args.no_configs:
+        if args.full and world == 1 and not args.no_configs:
             res["configs"] = extra_configs(ctx, dev, x, args.input, ids)
             if not args.streams:
                 del x
                 res["configs"].append(strong_layout_at_one_gpu(ctx, dev, n, args.input))
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             res["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
             res["gpu_over_cpu_1core"] = round(value / res["cpu_baseline"]["value"], 1)
             allc = cpu_all_cores(min(4.0, args.cpu_seconds / 3.0))

@@ -123,7 +123,7 @@ def test_bench_gpus_2_as_a_plain_process():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "SDRHIP_BENCH_STREAMS")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1",
-           "--cpu-seconds", "0", "--preroll-seconds", "0.05", "--log2-samples", "21"]
+           "--cpu-seconds", "0", "--preroll-seconds", "0.05", "--log2-samples", "21", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -145,7 +145,7 @@ def test_bench_n1_names_the_same_64_streams_as_n2():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "SDRHIP_BENCH_STREAMS", "SDRHIP_BENCH_SCALE")}
     base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0",
-            "--preroll-seconds", "0.05", "--log2-samples", "22"]
+            "--preroll-seconds", "0.05", "--log2-samples", "22", "--full"]
     r = subprocess.run(base, capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -162,6 +162,28 @@ def test_bench_n1_names_the_same_64_streams_as_n2():
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert res["n_gpus"] == 1 and res["scaling"] == "strong" and res["config"]["streams_total"] == 64
     assert res["config"]["stream_ids_by_rank"] == [list(range(64))] and res["verified"]["ok"] is True
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_carries_the_headline_alone():
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the headline figure and nothing that takes runs of its own
+    (no output check, no power / clock sample, no `configs` lines, no CPU baselines: --full, tested above)"""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "SDRHIP_BENCH_STREAMS", "SDRHIP_BENCH_SCALE")}
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--preroll-seconds", "0.05",
+           "--log2-samples", "22"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert res["higher_is_better"] is True and res["unit"] == "Msamples/s" and res["dtype"] == "int32" and res["steps"] == 3
+    assert res["value"] == pytest.approx(8 * (1 << 22) * 3 / (res["ms_per_step"] * 3e-3) / 1e6, rel=1e-3)
+    assert res["roofline"]["launches"] > 0 and res["roofline"]["avg_launch_ms"] > 0
+    assert res["verified"] is None and res["box"] is None
+    assert not {"configs", "cpu_baseline", "gpu_over_cpu_1core", "cpu_baseline_all_cores"} & set(res)
 
 
 def test_bench_gpus_n_without_enough_gpus_refuses_cleanly():

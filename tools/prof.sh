@@ -1,3 +1,3 @@
 #!/bin/bash
-# Runs on the GPU box (via gpurun): profile of the default bench command -> gpurun_out/prof_bench/summary.txt
-exec bash tools/prof_cmd.sh bench python $PWD/bench.py --cpu-seconds 0 $BENCH_ARGS
+# Runs on the GPU box: profile of the full bench command (every line of `bench.py --full`) -> prof_bench/summary.txt (tools/prof_cmd.sh)
+exec bash tools/prof_cmd.sh bench python $PWD/bench.py --full --cpu-seconds 0 $BENCH_ARGS

@@ -6,6 +6,7 @@ export TMPDIR=/tmp
 ROOT=$PWD
 TAG=$1; shift
 OUT=$ROOT/gpurun_out/prof_$TAG
+[ -n "$PROF_ROOT" ] && OUT=$PROF_ROOT/prof_$TAG  # (a caller that collects its results elsewhere)
 rm -rf $OUT; mkdir -p $OUT
 CMD="$@"
 cd /tmp
