@@ -161,6 +161,17 @@ __global__ __launch_bounds__(GF_NT, FFT_WAVES_PER_EU) void gf_encode128_fft_kern
     gf_encode128_fft_unit(a, (int)blockIdx.x, ldsraw);
 }
 
+// ... with its middle stages bit-sliced (Enc128Args::bitslice, context option enc_form = bitslice): same grid, same bytes
+#include "gf_encode128_bs.h"
+#ifndef BS_WAVES_PER_EU
+#define BS_WAVES_PER_EU 5 // (102 registers: five waves per SIMD, as the table form's 96 allow)
+#endif
+__global__ __launch_bounds__(GF_NT, BS_WAVES_PER_EU) void gf_encode128_bs_kernel(Enc128Args a)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char ldsraw[ENC128_FFT_KERNEL_LDS];
+    gf_encode128_bs_wg(a, (int)blockIdx.x, ldsraw);
+}
+
 // ... in half-frame workgroups (Enc128Args::half_units): grid = 2 x frames, 128 threads
 __global__ __launch_bounds__(128, FFT_WAVES_PER_EU) void gf_encode128_fft_half_kernel(Enc128Args a)
 {
@@ -191,6 +202,18 @@ __global__ __launch_bounds__(GF_NT, FFT_WAVES_PER_EU) void gf_encode128_fft_pack
     const unsigned nenc = (unsigned)a.nlist;
     if (blockIdx.x < nenc) {
         gf_encode128_fft_unit(a, (int)blockIdx.x, ldsraw);
+    } else {
+        const unsigned u = blockIdx.x - nenc;
+        frame_pack_wg(f, (int)(u / pack_bx), u % pack_bx, pack_bx);
+    }
+}
+// ... and with the bit-sliced encoder
+__global__ __launch_bounds__(GF_NT, BS_WAVES_PER_EU) void gf_encode128_bs_pack_kernel(Enc128Args a, FrameArgs f, unsigned pack_bx)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char ldsraw[ENC128_FFT_KERNEL_LDS];
+    const unsigned nenc = (unsigned)a.nlist;
+    if (blockIdx.x < nenc) {
+        gf_encode128_bs_wg(a, (int)blockIdx.x, ldsraw);
     } else {
         const unsigned u = blockIdx.x - nenc;
         frame_pack_wg(f, (int)(u / pack_bx), u % pack_bx, pack_bx);
@@ -800,6 +823,7 @@ hipError_t launch_gf_encode128(const Enc128Args &a, hipStream_t stream)
 {
     if (a.nlist <= 0 || a.rows <= 0) return hipSuccess;
     if (a.use_fft && a.fft_tables && a.rows <= FFT_MAX_ROWS && a.half_units) hipLaunchKernelGGL(gf_encode128_fft_half_kernel, dim3(2 * a.nlist), dim3(128), 0, stream, a);
+    else if (a.use_fft && a.fft_tables && a.rows <= FFT_MAX_ROWS && a.bitslice) hipLaunchKernelGGL(gf_encode128_bs_kernel, dim3(a.nlist), dim3(GF_NT), 0, stream, a);
     else if (a.use_fft && a.fft_tables && a.rows <= FFT_MAX_ROWS) hipLaunchKernelGGL(gf_encode128_fft_kernel, dim3(a.nlist), dim3(GF_NT), 0, stream, a);
     else hipLaunchKernelGGL(gf_encode128_kernel, dim3(2 * a.nlist), dim3(GF_NT), 0, stream, a);
     return hipGetLastError();
@@ -811,7 +835,9 @@ hipError_t launch_gf_encode128_pack(const Enc128Args &a, const FrameArgs &f, int
     if (blocks > 256) blocks = 256;
     if (blocks < 1) blocks = 1;
     const unsigned units = a.rows > 0 ? 2u * (unsigned)(a.nlist > 0 ? a.nlist : 0) : 0u;
-    if (a.use_fft && a.fft_tables && a.rows > 0 && a.rows <= FFT_MAX_ROWS)
+    if (a.use_fft && a.fft_tables && a.rows > 0 && a.rows <= FFT_MAX_ROWS && a.bitslice)
+        hipLaunchKernelGGL(gf_encode128_bs_pack_kernel, dim3(units / 2u + (unsigned)blocks * (unsigned)nstreams), dim3(GF_NT), 0, stream, a, f, (unsigned)blocks);
+    else if (a.use_fft && a.fft_tables && a.rows > 0 && a.rows <= FFT_MAX_ROWS)
         hipLaunchKernelGGL(gf_encode128_fft_pack_kernel, dim3(units / 2u + (unsigned)blocks * (unsigned)nstreams), dim3(GF_NT), 0, stream, a, f, (unsigned)blocks);
     else
         hipLaunchKernelGGL(gf_encode128_pack_kernel, dim3(units + (unsigned)blocks * (unsigned)nstreams), dim3(GF_NT), 0, stream, a, f, (unsigned)blocks);

@@ -364,6 +364,8 @@ struct Enc128Args {
     // in different phases.  0 = off.
     int stagger, stagger_div;
     int half_units;                 // 1: the FFT encoder runs in half-frame workgroups (gf_encode128_fft_half_kernel; context option enc_units)
+    int bitslice;                   // 1: the FFT encoder's middle stages as bit-sliced XOR trees (gf_encode128_bs.h; context option
+                                    // enc_form); whole-frame workgroups only: half_units = 1 runs the table form
 };
 // the sleep in front of a workgroup's loads (Enc128Args::stagger, DecodeBuffers::stagger)
 #if defined(__HIPCC__)
