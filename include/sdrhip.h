@@ -101,6 +101,8 @@ int sdrhip_ctx_set_option(sdrhip_ctx *ctx, const char *key, const char *value);
  * "dec_rows_exceeded" = frames, since the context was created, that the batched decoder (sdrhip_fec_decode_frames,
  * sdrhip_tx_process) left unrepaired because they carried more recovery blocks than the dec_max_rows option allows (kept on the
  * device: reading it synchronises the context's stream);
+ * "fecbuf_shadow_mismatch" = streams of asynchronous datagram batches (sdrhip_tx_submit_datagrams) whose collector counts on the
+ * device disagreed with the host's shadow that sized the batch's grids; 0 unless the library is broken (on the device, as above);
  * "h2d_bytes" / "d2h_bytes" = bytes that the context's entry points have copied from host to device / device to host since the
  * context was created (staging copies of host-memory calls, including the kernels' direct reads of pinned staging memory for
  * small calls; not the constant tables of sdrhip_ctx_create).  Counted on the host when the copy is enqueued: reading them does
@@ -520,6 +522,32 @@ int sdrhip_tx_process_datagrams(sdrhip_tx *tx, const uint8_t *dgrams, const size
                                 sdrhip_fecbuf_frame *info_out, size_t *n_frames, int mem);
 /* the handle's collector (borrowed; destroyed with the handle) for sdrhip_fecbuf_stats / sdrhip_fecbuf_reset */
 int sdrhip_tx_collector(sdrhip_tx *tx, sdrhip_fecbuf **out);
+/* Asynchronous datagram batches, the datagram twin of sdrhip_tx_submit / sdrhip_tx_collect: sdrdaemontx's reader thread receives
+ * while its main loop interpolates (sdrdaemontx.cpp:449-498).  sdrhip_tx_submit_datagrams takes ONE batch from host memory:
+ * stream s gives n_dgrams[s] datagrams of 512 bytes (counts may differ and may be 0) at dgrams + s * dgram_stride_bytes, or, with
+ * dgram_stride_bytes = SDRHIP_PACKED, back to back (stream s at dgrams + 512 * sum_{t<s} n_dgrams[t]).  The datagrams are staged
+ * into pinned memory (the buffer is the caller's again on return) or, when they lie in sdrhip_host_alloc memory, uploaded in
+ * place (leave them untouched until the batch is collected).  The call enqueues upload, collection, decode, interpolation at the
+ * factor in force and download in the output format in force, and returns with NO synchronisation (the first batch after the
+ * handle's collector was created, reset or fed by sdrhip_tx_process_datagrams reads its state back once).  The batch keeps that
+ * factor and format.  sdrhip_tx_collect_datagrams returns the OLDEST batch, meaning what sdrhip_tx_process_datagrams means for
+ * the same datagrams: stream s gets n_frames[s] * 16129 << log2interp samples at iq_out + 2 * s * out_stride (8-bit output:
+ * byte addressing as for sdrhip_tx_collect), the released frames' meta blocks at block0_out + (s * max_frames + k) * 508
+ * (block0_out may be NULL) and records at info_out[s * max_frames + k].  A stream that released more than max_frames, or an
+ * out_stride below the batch's largest stream: SDRHIP_EINVAL with every stream's count in n_frames, the batch stays (call again
+ * with room).  SDRHIP_EBUSY: nothing submitted, or (wait = 0) the oldest batch is still in flight; wait = 1 blocks outside the
+ * context lock.  The ring depth is sdrhip_tx_set_async's (default 4); a full ring makes the submit return SDRHIP_EBUSY.  The
+ * collector and the histories are the handle's (sdrhip_tx_collector, sdrhip_tx_process_datagrams, sdrhip_tx_process):
+ * synchronous calls before and after a run of batches continue the same streams, and sdrhip_fecbuf_stats reports the state after
+ * every batch submitted so far.  While datagram batches are in flight, SDRHIP_EINVAL with nothing consumed from
+ * sdrhip_tx_submit / _collect, sdrhip_tx_process, sdrhip_tx_process_datagrams, sdrhip_tx_set_output_format, sdrhip_tx_set_async,
+ * sdrhip_tx_set_pipelined(1), and sdrhip_fecbuf_reset / sdrhip_fecbuf_write_and_read on the handle's collector; the datagram
+ * entries refuse the same way while batches of received frames are in flight, in pipelined mode and while a pipelined batch
+ * waits.  sdrhip_tx_reconfigure applies to later submits.  A submit that fails before the collector's scatter launch consumes
+ * nothing; one that fails behind it loses the batch (never replayed). */
+int sdrhip_tx_submit_datagrams(sdrhip_tx *tx, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes);
+int sdrhip_tx_collect_datagrams(sdrhip_tx *tx, int16_t *iq_out, size_t out_stride, size_t max_frames, uint8_t *block0_out,
+                                sdrhip_fecbuf_frame *info_out, size_t *n_frames, int wait);
 
 #ifdef __cplusplus
 }

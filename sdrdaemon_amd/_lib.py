@@ -37,6 +37,7 @@ EXPORTS = [
     "sdrhip_rx_set_input_format", "sdrhip_tx_set_output_format",
     "sdrhip_decimate_ragged", "sdrhip_rx_process_ragged", "sdrhip_rx_frames_view_ragged",
     "sdrhip_rx_submit_ragged", "sdrhip_rx_collect_ragged",
+    "sdrhip_tx_submit_datagrams", "sdrhip_tx_collect_datagrams",
 ]
 
 
@@ -135,6 +136,8 @@ def load():
     lib.sdrhip_fecbuf_stats.argtypes = [vp, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i), vp, vp]
     lib.sdrhip_tx_process_datagrams.argtypes = [vp, vp, C.POINTER(sz), sz, vp, sz, sz, vp, vp, C.POINTER(sz), i]
     lib.sdrhip_tx_collector.argtypes = [vp, C.POINTER(vp)]
+    lib.sdrhip_tx_submit_datagrams.argtypes = [vp, vp, C.POINTER(sz), sz]
+    lib.sdrhip_tx_collect_datagrams.argtypes = [vp, vp, sz, sz, vp, vp, C.POINTER(sz), i]
     lib.sdrhip_rx_set_input_format.argtypes = [vp, i]
     lib.sdrhip_tx_set_output_format.argtypes = [vp, i]
     lib.sdrhip_decimate_ragged.argtypes = [vp, i, i, C.POINTER(u), vp, C.POINTER(sz), sz, vp, sz, C.POINTER(sz), i]

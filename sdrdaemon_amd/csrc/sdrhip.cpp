@@ -256,10 +256,11 @@ extern "C" int sdrhip_ctx_get_counter(sdrhip_ctx *c, const char *key, uint64_t *
     sdrhip::CtxLock lock_(c);
     if (std::string(key) == "h2d_bytes") { *value = c->h2d_bytes; return SDRHIP_OK; }
     if (std::string(key) == "d2h_bytes") { *value = c->d2h_bytes; return SDRHIP_OK; }
-    if (std::string(key) != "dec_rows_exceeded") return fail(SDRHIP_EINVAL, "ctx_get_counter: unknown key: %s", key);
+    const bool shadow = std::string(key) == "fecbuf_shadow_mismatch"; // (streams whose classify pass disagreed with the host's shadow)
+    if (std::string(key) != "dec_rows_exceeded" && !shadow) return fail(SDRHIP_EINVAL, "ctx_get_counter: unknown key: %s", key);
     HIP_TRY(hipSetDevice(c->device));
     unsigned v = 0;
-    HIP_TRY(link_copy(c, &v, c->dec_stats, sizeof(v), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(link_copy(c, &v, c->dec_stats + (shadow ? DEC_STATS_SHADOW_MISMATCH : 0), sizeof(v), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     *value = v;
     return SDRHIP_OK;

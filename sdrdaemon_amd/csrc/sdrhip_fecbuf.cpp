@@ -22,6 +22,11 @@ struct sdrhip_fecbuf {
     DevBuf rec, stage, dmap, dec_out, dec_b0;
     DevBuf hin, hout, hb0;       // SDRHIP_MEM_HOST staging on the device
     PinnedBuf pin_up, pin_down, pin_in;
+    // ---- asynchronous Tx batches (sdrhip_tx_submit_datagrams): the host's shadow of the classification part of state[cur]
+    std::vector<FecBufShadow> shadow;
+    bool shadow_ok = false;      // false: refreshed from the device before the next asynchronous batch (creation, reset, a synchronous call)
+    int async_busy = 0;          // the owning Tx handle has asynchronous batches in flight: reset and write_and_read are refused
+    DevBuf atab;                 // their tables, counts and public records (fecbuf_packed)
 };
 
 namespace {
@@ -41,6 +46,7 @@ int fecbuf_init_state(sdrhip_fecbuf *b)
         x.cur_meta[2] = x.out_meta[2] = 0xff000000u;
     }
     b->cur = 0;
+    b->shadow_ok = false;
     HIP_TRY(link_copy(b->ctx, b->state[0], st.data(), st.size() * sizeof(FecBufState), hipMemcpyHostToDevice, b->ctx->stream));
     HIP_TRY(hipStreamSynchronize(b->ctx->stream));
     return SDRHIP_OK;
@@ -53,6 +59,7 @@ int fecbuf_device(sdrhip_fecbuf *b, const uint8_t *dg, const size_t *n_dgrams, s
     sdrhip_ctx *c = b->ctx;
     const int S = b->nstreams;
     int rc;
+    b->shadow_ok = false; // (the collector moves without the host's shadow)
     // small per-call arrays: [ndg S][job_off S + 1][dbase S][pad] ints, then rec_base (int64), counts, public records
     const size_t ints = ((size_t)3 * S + 2 + 3) & ~(size_t)3;
     const size_t off_rb = ints * 4, off_cnt = counts_offset(S), off_pub = off_cnt + (size_t)S * FB_COUNTS * 4;
@@ -178,6 +185,7 @@ extern "C" void sdrhip_fecbuf_destroy(sdrhip_fecbuf *b)
         b->small.release(); b->rec.release(); b->stage.release(); b->dmap.release(); b->dec_out.release(); b->dec_b0.release();
         b->hin.release(); b->hout.release(); b->hb0.release();
         b->pin_up.release(); b->pin_down.release(); b->pin_in.release();
+        b->atab.release();
     }
     delete b;
     ctx_release(c);
@@ -187,6 +195,7 @@ extern "C" int sdrhip_fecbuf_reset(sdrhip_fecbuf *b)
 {
     if (!b) return fail(SDRHIP_EINVAL, "fecbuf is NULL");
     sdrhip::CtxLock lock_(b->ctx);
+    if (b->async_busy) return fail(SDRHIP_EINVAL, "fecbuf_reset: the Tx handle's asynchronous datagram batches are in flight: collect them first");
     HIP_TRY(hipSetDevice(b->ctx->device));
     return fecbuf_init_state(b);
 }
@@ -237,6 +246,7 @@ extern "C" int sdrhip_fecbuf_write_and_read(sdrhip_fecbuf *b, const uint8_t *dgr
     sdrhip::CtxLock lock_(c);
     const int S = b->nstreams;
     if (!n_dgrams || !n_frames) return fail(SDRHIP_EINVAL, "fecbuf_write_and_read: NULL n_dgrams / n_frames");
+    if (b->async_busy) return fail(SDRHIP_EINVAL, "fecbuf_write_and_read: the Tx handle's asynchronous datagram batches are in flight: collect them first");
     size_t nmax = 0;
     int rc;
     if ((rc = check_dgrams(S, dgrams, n_dgrams, dgram_stride_bytes, mem, "fecbuf_write_and_read", &nmax))) return rc;
@@ -309,6 +319,150 @@ int fecbuf_collect(sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgra
     *counts = reinterpret_cast<const int *>(b->small.as<uint8_t>() + counts_offset(S));
     return SDRHIP_OK;
 }
+} // namespace sdrhip
+
+// --------------------------------------------------------------------------- asynchronous Tx batches: no read-back
+// sdrhip_tx_submit_datagrams sizes the grids and picks the decoder from the host's own run of the classify pass's rule over the
+// headers it stages anyway (4 bytes per 512): a per-stream shadow of head, count, recov, maxrow, pres, dup gives every number the
+// bank's read-back gives (SDRdaemonFECBuffer.cpp:112-170).  The classify pass still writes its own counts (the interpolator reads
+// them); a check kernel compares the two and raises "fecbuf_shadow_mismatch".
+namespace sdrhip {
+int fecbuf_shadow(sdrhip_fecbuf *b, std::vector<FecBufShadow> *out)
+{
+    const int S = b->nstreams;
+    if (!b->shadow_ok) { // (the first batch after anything else moved the collector: one copy + one synchronisation)
+        std::vector<FecBufState> st((size_t)S);
+        HIP_TRY(hipMemcpyAsync(st.data(), b->state[b->cur], st.size() * sizeof(FecBufState), hipMemcpyDeviceToHost, b->ctx->stream));
+        HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+        b->shadow.assign((size_t)S, FecBufShadow());
+        for (int s = 0; s < S; ++s) {
+            FecBufShadow &h = b->shadow[(size_t)s];
+            const FecBufState &x = st[(size_t)s];
+            h.head = x.head; h.count = x.count; h.recov = x.recov; h.maxrow = x.maxrow; h.dup = x.dup;
+            for (int q = 0; q < 4; ++q) h.pres[q] = x.pres[q];
+        }
+        b->shadow_ok = true;
+    }
+    *out = b->shadow;
+    return SDRHIP_OK;
+}
+
+void fecbuf_shadow_run(FecBufShadow &h, const uint8_t *dg, size_t n, int res[4])
+{
+    int K = 0, D = 0, maxrow = -1, maxrec = 0;
+    for (size_t i = 0; i < n; ++i) {
+        uint32_t hd;
+        memcpy(&hd, dg + i * SDRHIP_UDPSIZE, 4);
+        const int fi = (int)(hd & 0xffffu), bi = (int)((hd >> 16) & 0xffu);
+        if (fi != h.head) { // another frame index releases the open slot (the first datagram: the initial one)
+            ++K;
+            if (h.count >= 128 && h.recov > 0 && !h.dup) { // (to the decoder: the frames cm256_decode repairs)
+                ++D;
+                maxrow = h.maxrow > maxrow ? h.maxrow : maxrow;
+                maxrec = h.recov > maxrec ? h.recov : maxrec;
+            }
+            h.head = fi; h.count = 0; h.recov = 0; h.maxrow = -1; h.dup = 0;
+            h.pres[0] = h.pres[1] = h.pres[2] = h.pres[3] = 0u;
+        }
+        if (h.count < 128) { // (the first 128 arrivals)
+            if (bi >= 128) {
+                ++h.recov;
+                h.maxrow = bi - 128 > h.maxrow ? bi - 128 : h.maxrow;
+            } else {
+                const unsigned bit = 1u << (bi & 31);
+                if (h.pres[bi >> 5] & bit) h.dup = 1;
+                h.pres[bi >> 5] |= bit;
+            }
+        }
+        ++h.count;
+    }
+    res[0] = K; res[1] = D; res[2] = maxrow; res[3] = maxrec;
+}
+
+int fecbuf_packed(sdrhip_fecbuf *b, const uint8_t *dg, const size_t *n_dgrams, const int *res, const std::vector<FecBufShadow> &next,
+                  PinnedBuf &tab, uint8_t *data_out, size_t data_stride, uint8_t *block0_out, size_t max_frames, unsigned *mismatch,
+                  bool *committed, const int **counts, const FecBufPub **pub)
+{
+    sdrhip_ctx *c = b->ctx;
+    const int S = b->nstreams;
+    int rc;
+    *committed = false;
+    // tables: [ndg S][job_off S + 1][dbase S][expect S x 4][pad] ints, rec_base [S], dg_off [S] (int64); on the device the counts
+    // [S][FB_COUNTS] and the public records [S][max_frames] follow
+    const size_t ints = ((size_t)7 * S + 1 + 3) & ~(size_t)3;
+    const size_t off_rb = ints * 4, off_do = off_rb + (size_t)S * 8, off_cnt = off_do + (size_t)S * 8;
+    const size_t off_pub = off_cnt + (size_t)S * FB_COUNTS * 4, bytes = off_pub + (size_t)S * max_frames * sizeof(FecBufPub);
+    if ((rc = tab.reserve(off_cnt))) return rc; // (waits for the upload of this batch slot's last use)
+    int *ndg = tab.as<int>(), *job_off = ndg + S, *dbase = job_off + S + 1, *expect = dbase + S;
+    long long *rb = reinterpret_cast<long long *>(tab.as<uint8_t>() + off_rb), *doff = reinterpret_cast<long long *>(tab.as<uint8_t>() + off_do);
+    long long nrec = 0, off = 0;
+    int njobs = 0, nslots = 0, maxrow = -1, maxrec = 0;
+    for (int s = 0; s < S; ++s) {
+        const int *x = res + 4 * s;
+        ndg[s] = (int)n_dgrams[s];
+        rb[s] = nrec; nrec += (long long)n_dgrams[s] + 1;
+        doff[s] = off; off += (long long)(n_dgrams[s] * SDRHIP_UDPSIZE);
+        job_off[s] = njobs; njobs += x[0] + 1;
+        dbase[s] = nslots; nslots += x[1];
+        for (int q = 0; q < 4; ++q) expect[4 * s + q] = x[q];
+        maxrow = x[2] > maxrow ? x[2] : maxrow;
+        maxrec = x[3] > maxrec ? x[3] : maxrec;
+    }
+    job_off[S] = njobs;
+    // everything that can fail for want of memory before the state moves on (a buffer that grows waits for the batches in flight)
+    if ((rc = reserve_settled(c, b->atab, bytes))) return rc;
+    if ((rc = reserve_settled(c, b->rec, (size_t)nrec * sizeof(FecBufRec)))) return rc;
+    if (nslots > 0) {
+        if ((rc = reserve_settled(c, b->stage, (size_t)nslots * 128 * SDRHIP_UDPSIZE))) return rc;
+        if ((rc = reserve_settled(c, b->dmap, (size_t)nslots * 2 * sizeof(int)))) return rc;
+        if ((rc = reserve_settled(c, b->dec_out, (size_t)nslots * PAYLOAD))) return rc;
+        if (block0_out && (rc = reserve_settled(c, b->dec_b0, (size_t)nslots * SDRHIP_BLOCK_BYTES))) return rc;
+    }
+    uint8_t *t = b->atab.as<uint8_t>();
+    HIP_TRY(hipMemcpyAsync(t, tab.p, off_cnt, hipMemcpyHostToDevice, c->stream)); // (not counted: a table)
+    tab.mark(c->stream);
+    FecBufArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dg = dg; a.dg_stride = 0;
+    a.ndg = reinterpret_cast<const int *>(t);
+    a.job_off = a.ndg + S;
+    a.dbase = a.job_off + S + 1;
+    a.rec_base = reinterpret_cast<const long long *>(t + off_rb);
+    a.counts = reinterpret_cast<int *>(t + off_cnt);
+    a.pub = reinterpret_cast<FecBufPub *>(t + off_pub);
+    a.rec = b->rec.as<FecBufRec>();
+    a.max_frames = (int)max_frames;
+    a.st_cur = b->state[b->cur]; a.st_next = b->state[b->cur ^ 1];
+    a.carry_cur_base = b->carry; a.carry_base = b->carry;
+    a.nstreams = S;
+    a.data_out = data_out; a.data_stride = data_stride; a.block0_out = block0_out;
+    a.stage = nslots ? b->stage.as<uint8_t>() : nullptr; a.dmap = nslots ? b->dmap.as<int>() : nullptr;
+    a.dec_out = nslots ? b->dec_out.as<uint8_t>() : nullptr; a.dec_b0 = nslots && block0_out ? b->dec_b0.as<uint8_t>() : nullptr;
+    const long long *dg_off = reinterpret_cast<const long long *>(t + off_do);
+    hipError_t e = launch_fecbuf_classify_packed(a, dg_off, c->stream);
+    if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "fecbuf classify launch: %s", hipGetErrorString(e));
+    if ((e = launch_fecbuf_shadow_check(a.counts, reinterpret_cast<const int *>(t) + 3 * S + 1, S, mismatch, c->stream)) != hipSuccess)
+        return fail(SDRHIP_EDEVICE, "fecbuf shadow check launch: %s", hipGetErrorString(e));
+    if (nslots > 0) HIP_TRY(hipMemsetAsync(a.dmap, 0xff, (size_t)nslots * 2 * sizeof(int), c->stream)); // (the guarded copy skips what stays -1)
+    if ((e = launch_fecbuf_scatter_packed(a, dg_off, njobs, nslots, c->stream)) != hipSuccess)
+        return fail(SDRHIP_EDEVICE, "fecbuf scatter launch: %s", hipGetErrorString(e));
+    b->cur ^= 1; // (committed: the scatter pass has written the new carry slots)
+    b->shadow = next;
+    *committed = true;
+    if (nslots > 0) {
+        // the promise is the batch's highest collected row, never a count (as fecbuf_device)
+        const int max_rows = (maxrow < 32 && maxrec <= 32) ? 32 : 128;
+        if ((rc = fec_decode_device(c, b->stage.as<uint8_t>(), (size_t)128 * SDRHIP_UDPSIZE, nullptr, (size_t)nslots, b->dec_out.as<uint8_t>(), PAYLOAD,
+                                    block0_out ? b->dec_b0.as<uint8_t>() : nullptr, nullptr, nullptr, max_rows)))
+            return rc;
+        if ((e = launch_fecbuf_copy_guarded(a, nslots, c->stream)) != hipSuccess) return fail(SDRHIP_EDEVICE, "fecbuf copy launch: %s", hipGetErrorString(e));
+    }
+    *counts = a.counts;
+    *pub = a.pub;
+    return SDRHIP_OK;
+}
+
+void fecbuf_set_async_busy(sdrhip_fecbuf *b, bool busy) { b->async_busy = busy ? 1 : 0; }
 } // namespace sdrhip
 
 extern "C" int sdrhip_fecbuf_stats(sdrhip_fecbuf *b, int stream, int *cur_nb_blocks, int *cur_nb_recovery, int *min_nb_blocks, int *max_nb_recovery,

@@ -113,6 +113,32 @@ int fecbuf_check_dgrams(const sdrhip_fecbuf *b, const uint8_t *dgrams, const siz
 int fecbuf_collect(sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes, int mem, uint8_t *data_out,
                    size_t data_stride_bytes, uint8_t *block0_out, size_t max_frames, sdrhip_fecbuf_frame *info_out, size_t *n_frames,
                    const int **counts);
+// asynchronous Tx batches (sdrhip_tx_submit_datagrams): the host's shadow of the classification part of a stream's FecBufState
+struct FecBufShadow {
+    int head, count, recov, maxrow, dup;
+    unsigned pres[4];
+};
+// the shadow of the committed state (refreshed from the device -- one copy + one synchronisation -- when something else moved the
+// collector since the last asynchronous batch)
+int fecbuf_shadow(sdrhip_fecbuf *b, std::vector<FecBufShadow> *out);
+// the classify pass's rule over n datagrams of one stream (datagram i at dg + 512 i, host): advances h; res = what the pass reports
+// for the stream, {FB_K, FB_D, FB_MAXROW, FB_MAXREC}
+void fecbuf_shadow_run(FecBufShadow &h, const uint8_t *dg, size_t n, int res[4]);
+// one batch on the device without a read-back: stream s's datagrams back to back at dg + sum_{t<s} n_dgrams[t] * 512 (device),
+// grids and decoder bound from res ([S][4], fecbuf_shadow_run); tab = the batch's pinned table buffer; data_out / block0_out on
+// the device, max_frames >= every res[s][0]; +1 on *mismatch (device) per stream whose classify pass disagrees with res.
+// *committed: the state has moved on (to `next`; a failure after it loses the batch); *counts / *pub = the pass's counts
+// [S][FB_COUNTS] and public records [S][max_frames] on the device (valid until the next batch)
+int fecbuf_packed(sdrhip_fecbuf *b, const uint8_t *dg, const size_t *n_dgrams, const int *res, const std::vector<FecBufShadow> &next,
+                  PinnedBuf &tab, uint8_t *data_out, size_t data_stride, uint8_t *block0_out, size_t max_frames, unsigned *mismatch,
+                  bool *committed, const int **counts, const FecBufPub **pub);
+// DevBuf::reserve behind a synchronisation of the context's stream when the buffer grows (it frees the old one, which batches in
+// flight may still use)
+inline int reserve_settled(sdrhip_ctx *c, DevBuf &b, size_t n);
+// the word of sdrhip_ctx::dec_stats the shadow check counts in (sdrhip_ctx_get_counter "fecbuf_shadow_mismatch")
+constexpr int DEC_STATS_SHADOW_MISMATCH = 1;
+// while set, sdrhip_fecbuf_reset / sdrhip_fecbuf_write_and_read on the collector are refused (SDRHIP_EINVAL)
+void fecbuf_set_async_busy(sdrhip_fecbuf *b, bool busy);
 // frames/recovery on the device; recovery slots may be interleaved with the frames
 // (rec_frame_bytes = stride between the recovery areas of consecutive frames)
 // frame_list_dev (optional, device): groups of GF_FRAMES_PER_GROUP frame indices (-1 = none), ngroups of them
@@ -268,6 +294,11 @@ struct KTimer {
         if (e1) (void)hipEventRecord(e1, st);
     }
 };
+inline int reserve_settled(sdrhip_ctx *c, DevBuf &b, size_t n)
+{
+    if (n > b.cap && b.p && hipStreamSynchronize(c->stream) != hipSuccess) return fail(SDRHIP_EDEVICE, "hipStreamSynchronize");
+    return b.reserve(n);
+}
 // a copy across the host link of `bytes` (hipMemcpyHostToDevice / DeviceToHost; anything else is not counted)
 inline void link_bytes(sdrhip_ctx *c, hipMemcpyKind kind, size_t bytes)
 {

@@ -491,5 +491,24 @@ enum { FB_DECODED = 1, FB_META = 2, FB_REPAIRED = 4, FB_DECODE_ERROR = 8 };
 hipError_t launch_fecbuf_classify(const FecBufArgs &a, hipStream_t stream);
 hipError_t launch_fecbuf_scatter(const FecBufArgs &a, int njobs, hipStream_t stream);
 hipError_t launch_fecbuf_copy(const FecBufArgs &a, int nslots, hipStream_t stream);
+// asynchronous Tx batches (sdrhip_tx_submit_datagrams): stream s's datagrams back to back at a.dg + dg_off[s] (device); njobs /
+// nslots come from the host's shadow of the classification; the scatter pass skips what lies past the classify pass's own counts,
+// max_frames or nslots, the guarded copy a slot whose dmap entry is still -1 (preset by the caller)
+hipError_t launch_fecbuf_classify_packed(const FecBufArgs &a, const long long *dg_off, hipStream_t stream);
+hipError_t launch_fecbuf_scatter_packed(const FecBufArgs &a, const long long *dg_off, int njobs, int nslots, hipStream_t stream);
+hipError_t launch_fecbuf_copy_guarded(const FecBufArgs &a, int nslots, hipStream_t stream);
+// counts [S][FB_COUNTS] against the shadow's expect [S][4] = {K, D, maxrow, maxrec}: +1 on *mismatch per
+// stream that differs
+hipError_t launch_fecbuf_shadow_check(const int *counts, const int *expect, int nstreams, unsigned *mismatch, hipStream_t stream);
+// delivery gather: segment i = bytes (a multiple of 2) from src (dword-aligned, readable 2 bytes past the end) to out + dst
+struct GatherSeg {
+    const uint8_t *src;
+    uint64_t dst, bytes;
+    uint32_t wg0, pad; // first workgroup (gather_plan)
+};
+constexpr uint64_t GATHER_WG_BYTES = 16384; // 16-byte-aligned output bytes per workgroup (256 lanes x 4 chunks of 16 bytes)
+// fills every segment's wg0, returns the grid (0: more than 2^31 workgroups)
+uint32_t gather_plan(GatherSeg *segs, int nseg);
+hipError_t launch_delivery_gather(const GatherSeg *segs, int nseg, uint32_t grid, uint8_t *out, hipStream_t stream);
 
 } // namespace sdrhip

@@ -1033,6 +1033,81 @@ class TxPipe:
             res.append((out[s, :(k * SAMPLES_PER_FRAME) << self.log2interp], b0[s, :k], recs))
         return res
 
+    # ---- asynchronous datagram batches (sdrhip_tx_submit_datagrams / sdrhip_tx_collect_datagrams)
+    def submit_datagrams(self, dgrams_per_stream):
+        """one batch of raw datagrams from host memory: one (n_s, 512) uint8 numpy array per stream (counts may differ, may be 0),
+        or ONE (sum n_s, 512) array of them back to back with a list of counts as (array, counts) -- such an array in
+        sdrhip_host_alloc memory goes up in place and must stay untouched until the batch is collected.  Returns at once; raises
+        SdrHipError(code SDRHIP_EBUSY = -6) when every batch of the ring is in flight."""
+        S = self.nstreams
+        if isinstance(dgrams_per_stream, tuple):
+            buf, counts = dgrams_per_stream
+            counts = [int(x) for x in counts]
+            if len(counts) != S:
+                raise ValueError("one count per stream")
+        else:
+            if len(dgrams_per_stream) != S:
+                raise ValueError("one datagram array per stream")
+            if any(_is_torch(d) for d in dgrams_per_stream):
+                raise TypeError("submit_datagrams takes host memory")
+            counts = [int(np.asarray(d).shape[0]) for d in dgrams_per_stream]
+            nz = [np.asarray(d, np.uint8).reshape(-1, UDPSIZE) for d in dgrams_per_stream if len(d)]
+            buf = np.concatenate(nz) if nz else np.zeros((0, UDPSIZE), np.uint8)
+        if _is_torch(buf):
+            raise TypeError("submit_datagrams takes host memory")
+        buf = np.ascontiguousarray(buf, np.uint8)
+        if buf.size != sum(counts) * UDPSIZE:
+            raise ValueError("the datagrams do not match the counts")
+        nd = (C.c_size_t * S)(*counts)
+        pend = self.__dict__.setdefault("_dg_pending", [])
+        pend.append(self.log2interp)  # (the batch keeps the factor in force; collect_datagrams sizes its buffers with it)
+        try:
+            check(self.ctx.lib.sdrhip_tx_submit_datagrams(self.h, _ptr(buf), nd, 0))  # (0 = SDRHIP_PACKED)
+        except SdrHipError:
+            pend.pop()
+            raise
+
+    def collect_datagrams(self, wait=True, max_frames=None):
+        """the oldest datagram batch: per stream (iq (n, 2) with n = frames * 16129 << the batch's log2interp, block0 (frames, 508)
+        uint8, records) as process_datagrams returns them, or None when no batch was collected (nothing submitted, or wait=False
+        and the oldest one is in flight).  max_frames=None: room for exactly what the batch released (one call that learns the
+        counts, one that collects)."""
+        S = self.nstreams
+        nf = (C.c_size_t * S)()
+        if max_frames is None:
+            rc = self.ctx.lib.sdrhip_tx_collect_datagrams(self.h, None, 0, 0, None, None, nf, 1 if wait else 0)
+            if rc == -6:
+                return None
+            if rc == 0:  # (a batch that released nothing: collected)
+                pend = self.__dict__.get("_dg_pending")
+                if pend:
+                    pend.pop(0)
+                return [(np.zeros((0, 2), self._out_dtype), np.zeros((0, BLOCK_BYTES), np.uint8), []) for _ in range(S)]
+            if rc != -1:
+                check(rc)
+            max_frames = max(int(x) for x in nf)
+        pend = self.__dict__.setdefault("_dg_pending", [])
+        L = pend[0] if pend else self.log2interp
+        F = max(max_frames, 1)
+        out, pad = self._out(S, (F * SAMPLES_PER_FRAME) << L)
+        b0 = np.empty((S, F, BLOCK_BYTES), np.uint8)
+        info = (FECBufferFrame * (S * F))()
+        rc = self.ctx.lib.sdrhip_tx_collect_datagrams(self.h, _ptr(out), pad, max_frames, _ptr(b0), info, nf, 1 if wait else 0)
+        self.last_n_frames = [int(x) for x in nf]
+        if rc == -6:
+            return None
+        check(rc)
+        if pend:
+            pend.pop(0)
+        res = []
+        for s in range(S):
+            k = int(nf[s])
+            n = (k * SAMPLES_PER_FRAME) << L
+            recs = [dict(frame_index=info[s * F + j].frame_index, block_count=info[s * F + j].block_count,
+                         recovery_count=info[s * F + j].recovery_count, flags=info[s * F + j].flags) for j in range(k)]
+            res.append((out[s, :n], b0[s, :k], recs))
+        return res
+
     def collector_stats(self, stream):
         """the statistics of one stream's collector (sdrhip_tx_collector + sdrhip_fecbuf_stats): the dict of FECBufferBank.stats"""
         h = C.c_void_p()
