@@ -334,7 +334,7 @@ template <int NS, int I> __device__ __forceinline__ void mf_front2(MfState<NS> &
 constexpr int MF_GROUP_BYTES = 9216;             // 8 blocks of 1 KiB + their skew
 // Ring depth NG (groups per wave): 4 = 36 KiB per wave, 147 KiB per workgroup -- the workgroup owns its CU; 3 = 27 KiB per wave,
 // 108 KiB per workgroup, which leaves 52 KiB of the CU's 160 KiB for two workgroups of ANOTHER kernel (the CM256 encoder of the
-// previous call on a second stream: sdrhip_pipes.cpp, "overlap" mode).  The DMAs run NG - 1 groups (8 (NG - 1) steps) ahead.
+// previous call on a second stream: sdrhip_rx.cpp, "overlap" mode).  The DMAs run NG - 1 groups (8 (NG - 1) steps) ahead.
 constexpr int mf_wave_ring(int ng) { return ng * MF_GROUP_BYTES; } // bytes of LDS per wave
 // decimate16 only: measured with 3 interleaved rounds (tools/experiments_r03/exp24.sh), register ring against LDS-DMA ring: decimate16 0.2445 / 0.2363 ms,
 // decimate32 0.2512 / 0.2537, decimate64 0.2693 / 0.2947 (their warm-up and the ring's run-ahead past the span grow with the ratio)
@@ -712,7 +712,7 @@ namespace {
 // The matrix-core waves run one per SIMD and leave ~40 % of their SIMD's issue slots empty (memory waits, dependent issue);
 // a kernel boundary cannot fill them, co-resident encoder workgroups can: first the decimator's workgroups (as in
 // decim_mfma_kernel, register ring: its 34 KB of static LDS leave room for three encoder workgroups per CU), then one
-// encoder workgroup per (frame, half block).  No dependency between the two roles inside the launch (sdrhip_pipes.cpp).
+// encoder workgroup per (frame, half block).  No dependency between the two roles inside the launch (sdrhip_rx.cpp).
 #include "gf_encode128_body.h"
 // Roles are claimed at run time, not by blockIdx: the decimator's workgroups must sit ONE per CU (a launch lasts as long as
 // its fullest CU), but every workgroup of a kernel has the same resource footprint, and with 2 000 encoder workgroups in the

@@ -346,6 +346,47 @@ extern "C" int sdrhip_ctx_kernel_timing_read(sdrhip_ctx *c, int cls, double *tot
     return SDRHIP_OK;
 }
 
+// ------------------------------------------------------------------------------ pinned host memory
+namespace {
+// memory handed out by sdrhip_host_alloc: pinned, usable in place
+struct HostRange { const char *p; size_t n; };
+std::mutex g_host_mtx;
+std::vector<HostRange> g_host_ranges;
+} // namespace
+namespace sdrhip {
+bool host_is_pinned(const void *p, size_t n)
+{
+    std::lock_guard<std::mutex> g(g_host_mtx);
+    const char *c = static_cast<const char *>(p);
+    for (const HostRange &r : g_host_ranges)
+        if (c >= r.p && c + n <= r.p + r.n) return true;
+    return false;
+}
+} // namespace sdrhip
+
+extern "C" void *sdrhip_host_alloc(sdrhip_ctx *c, size_t bytes)
+{
+    if (!c || bytes == 0) return nullptr;
+    if (hipSetDevice(c->device) != hipSuccess) return nullptr;
+    void *p = nullptr;
+    if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) { (void)fail(SDRHIP_ENOMEM, "hipHostMalloc(%zu) failed", bytes); return nullptr; }
+    std::lock_guard<std::mutex> g(g_host_mtx);
+    g_host_ranges.push_back(HostRange{static_cast<const char *>(p), bytes});
+    return p;
+}
+
+extern "C" void sdrhip_host_free(sdrhip_ctx *c, void *p)
+{
+    if (!p) return;
+    (void)c;
+    {
+        std::lock_guard<std::mutex> g(g_host_mtx);
+        for (size_t i = 0; i < g_host_ranges.size(); ++i)
+            if (g_host_ranges[i].p == p) { g_host_ranges.erase(g_host_ranges.begin() + (long)i); break; }
+    }
+    (void)hipHostFree(p);
+}
+
 // ------------------------------------------------------------------------------ decimators
 struct sdrhip_decimators {
     sdrhip_ctx *ctx;
@@ -563,7 +604,7 @@ extern "C" int sdrhip_decimate(sdrhip_decimators *d, int log2decim, int fcpos, u
             return fail(SDRHIP_EALIGN, "decimate: device pointers must be 16-byte aligned and strides multiples of 4 samples");
         return decimate_device(d, log2decim, fcpos, sampleSize, iq_in, n_in, in_stride, iq_out, out_stride, n_out, 0, 0, 0);
     }
-    if (mem != SDRHIP_MEM_HOST) return fail(SDRHIP_EINVAL, "mem must be SDRHIP_MEM_HOST or SDRHIP_MEM_DEVICE");
+    if (int e = check_mem(mem)) return e;
 
     // host buffers: stage through device memory with padded (16-byte aligned) per-stream strides
     const size_t dis = (n_in + 3) & ~(size_t)3, dos = (n_res + 3) & ~(size_t)3;
@@ -745,7 +786,7 @@ extern "C" int sdrhip_decimate_ragged(sdrhip_decimators *d, int log2decim, int f
     if (log2decim < 0 || log2decim > 6) return fail(SDRHIP_EINVAL, "Invalid log2 decimation factor");
     if (fcpos < SDRHIP_FC_INF || fcpos > SDRHIP_FC_CEN) return fail(SDRHIP_EINVAL, "Invalid Fc position index");
     if (*sampleSize < 1 || *sampleSize > 16) return fail(SDRHIP_EINVAL, "sampleSize must be 1..16");
-    if (mem != SDRHIP_MEM_HOST && mem != SDRHIP_MEM_DEVICE) return fail(SDRHIP_EINVAL, "mem must be SDRHIP_MEM_HOST or SDRHIP_MEM_DEVICE");
+    if (int e = check_mem(mem)) return e;
     sdrhip_ctx *c = d->ctx;
     const int S = d->nstreams;
     size_t max_in = 0;

@@ -154,7 +154,7 @@ extern "C" int sdrhip_fec_encode_frames(sdrhip_ctx *c, const uint8_t *frames, si
     HIP_TRY(hipSetDevice(c->device));
     const size_t fb = (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE, rb = (size_t)nb_fec * SDRHIP_UDPSIZE;
     if (mem == SDRHIP_MEM_DEVICE) return fec_encode_device(c, frames, fb, nframes, nb_fec, recovery_out, rb);
-    if (mem != SDRHIP_MEM_HOST) return fail(SDRHIP_EINVAL, "mem must be SDRHIP_MEM_HOST or SDRHIP_MEM_DEVICE");
+    if (int e = check_mem(mem)) return e;
     int rc;
     if ((rc = c->in.reserve(nframes * fb))) return rc;
     if ((rc = c->out.reserve(nframes * rb))) return rc;
@@ -175,7 +175,7 @@ extern "C" int sdrhip_fec_decode_frames(sdrhip_ctx *c, const uint8_t *rx, const 
     HIP_TRY(hipSetDevice(c->device));
     const size_t fb = (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE, pb = (size_t)127 * SDRHIP_BLOCK_BYTES;
     if (mem == SDRHIP_MEM_DEVICE) return fec_decode_device(c, rx, fb, indices, nframes, payload_out, pb, block0_out);
-    if (mem != SDRHIP_MEM_HOST) return fail(SDRHIP_EINVAL, "mem must be SDRHIP_MEM_HOST or SDRHIP_MEM_DEVICE");
+    if (int e = check_mem(mem)) return e;
     int rc;
     if ((rc = c->in.reserve(nframes * fb))) return rc;
     if ((rc = c->out.reserve(nframes * pb))) return rc;

@@ -204,7 +204,7 @@ namespace {
 // the datagram arguments of a call (sdrhip_fecbuf_write_and_read, sdrhip_tx_process_datagrams); *nmax = the most datagrams of a stream
 int check_dgrams(int S, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes, int mem, const char *who, size_t *nmax)
 {
-    if (mem != SDRHIP_MEM_HOST && mem != SDRHIP_MEM_DEVICE) return fail(SDRHIP_EINVAL, "mem must be SDRHIP_MEM_HOST or SDRHIP_MEM_DEVICE");
+    if (int e = check_mem(mem)) return e;
     *nmax = 0;
     for (int s = 0; s < S; ++s) {
         if (n_dgrams[s] > 0x3fffffffu) return fail(SDRHIP_EINVAL, "%s: too many datagrams in one call", who);

@@ -48,6 +48,11 @@ struct PinnedBuf {
 constexpr size_t SDRHIP_ZEROCOPY_MAX = (size_t)384 << 10; // (measured: 256 KiB calls 42 -> 29 us, 1 MiB calls 59 -> 77 us: the copy engine wins from there)
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// the `mem` argument of an entry point
+inline int check_mem(int mem)
+{
+    return mem == SDRHIP_MEM_HOST || mem == SDRHIP_MEM_DEVICE ? SDRHIP_OK : fail(SDRHIP_EINVAL, "mem must be SDRHIP_MEM_HOST or SDRHIP_MEM_DEVICE");
+}
 
 void ctx_retain(sdrhip_ctx *c);
 void ctx_release(sdrhip_ctx *c);

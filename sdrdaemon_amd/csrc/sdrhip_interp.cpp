@@ -1,0 +1,139 @@
+// sdrhip_interp.cpp -- the interpolator bank of include/sdrhip.h.
+#include "sdrhip_host.h"
+
+#include <cstring>
+#include <new>
+
+using namespace sdrhip;
+
+// --------------------------------------------------------------------------- interpolators
+struct sdrhip_interpolators {
+    sdrhip_ctx *ctx;
+    int nstreams;
+    int32_t *state[2]; // [nstreams][INT_STATE_WORDS]
+    int cur;
+};
+
+extern "C" int sdrhip_interpolators_create(sdrhip_ctx *ctx, int nstreams, sdrhip_interpolators **out)
+{
+    if (!ctx || !out || nstreams <= 0 || nstreams > 65535) return fail(SDRHIP_EINVAL, "interpolators_create: bad argument");
+    HIP_TRY(hipSetDevice(ctx->device));
+    sdrhip_interpolators *p = new (std::nothrow) sdrhip_interpolators();
+    if (!p) return fail(SDRHIP_ENOMEM, "out of host memory");
+    p->ctx = ctx; p->nstreams = nstreams; p->cur = 0;
+    size_t bytes = (size_t)nstreams * INT_STATE_WORDS * sizeof(int32_t);
+    p->state[0] = p->state[1] = nullptr;
+    if (hipMalloc(reinterpret_cast<void **>(&p->state[0]), bytes) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void **>(&p->state[1]), bytes) != hipSuccess) {
+        if (p->state[0]) (void)hipFree(p->state[0]);
+        delete p;
+        return fail(SDRHIP_ENOMEM, "hipMalloc interpolator state");
+    }
+    ctx_retain(ctx);
+    *out = p;
+    return sdrhip_interpolators_reset(p);
+}
+
+extern "C" void sdrhip_interpolators_destroy(sdrhip_interpolators *p)
+{
+    if (!p) return;
+    (void)hipSetDevice(p->ctx->device);
+    (void)hipStreamSynchronize(p->ctx->stream);
+    (void)hipFree(p->state[0]);
+    (void)hipFree(p->state[1]);
+    ctx_release(p->ctx);
+    delete p;
+}
+
+extern "C" int sdrhip_interpolators_reset(sdrhip_interpolators *p)
+{
+    if (!p) return fail(SDRHIP_EINVAL, "interpolators is NULL");
+    sdrhip::CtxLock lock_(p->ctx);
+    size_t bytes = (size_t)p->nstreams * INT_STATE_WORDS * sizeof(int32_t);
+    HIP_TRY(hipMemsetAsync(p->state[0], 0, bytes, p->ctx->stream));
+    HIP_TRY(hipMemsetAsync(p->state[1], 0, bytes, p->ctx->stream));
+    p->cur = 0;
+    return SDRHIP_OK;
+}
+
+namespace sdrhip {
+bool interpolate_gather_ok(const sdrhip_ctx *c, int log2interp) { return c->opt.interp_wave && log2interp >= 2; }
+
+int interpolate_device(sdrhip_interpolators *p, int log2interp, const int16_t *in, size_t n_in, size_t in_stride, int16_t *out,
+                       size_t out_stride, size_t *n_out, const InterpGather *gather, const InterpCount *count, int out_fmt)
+{
+    sdrhip_ctx *c = p->ctx;
+    if (n_out) *n_out = n_in << log2interp;
+    if (n_in == 0) return SDRHIP_OK;
+    if (gather && !interpolate_gather_ok(p->ctx, log2interp)) return fail(SDRHIP_EINVAL, "internal: gathered input needs the wave interpolator");
+    if (gather && count) return fail(SDRHIP_EINVAL, "internal: no ragged gather");
+    if (gather && out_fmt != IQF_S16) return fail(SDRHIP_EINVAL, "internal: gathered input has int16 output only");
+    if (log2interp == 0 && out_fmt == IQF_S8) { // the copy, narrowed (K6n)
+        hipError_t e;
+        {
+            KTimer kt(c, SDRHIP_K_INTERPOLATE);
+            e = launch_iq8_narrow(in, in_stride, reinterpret_cast<uint8_t *>(out), out_stride, n_in, p->nstreams, c->stream);
+        }
+        if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "narrow launch: %s", hipGetErrorString(e));
+        return SDRHIP_OK;
+    }
+    if (log2interp == 0) { // Upsampler::process m_interp == 0: samples_out = samples_in (Upsampler.cpp:54-57)
+        HIP_TRY(hipMemcpy2DAsync(out, out_stride * 4, in, in_stride * 4, n_in * 4, p->nstreams, hipMemcpyDeviceToDevice, c->stream));
+        return SDRHIP_OK;
+    }
+    InterpArgs a;
+    memset(&a, 0, sizeof(a));
+    a.in = in; a.out = out; a.in_stride = in_stride; a.out_stride = out_stride; a.n_in = n_in;
+    a.state_cur = p->state[p->cur]; a.state_next = p->state[p->cur ^ 1];
+    a.nstreams = p->nstreams;
+    if (gather) { a.gmap = gather->map; a.grx = gather->rx; a.grest = gather->restored; a.gframes = gather->frames; }
+    if (count) { a.count = count->count; a.count_stride = count->stride; a.count_unit = count->unit; }
+    // SDRHIP_INTERP_PATH = wave (K5w, default) | valu (K5); SDRHIP_INTERP_SPAN = segment length in inputs (tests)
+    const bool use_wave = c->opt.interp_wave && log2interp >= 2;
+    if (use_wave) plan_interpolate_wave(log2interp, n_in, p->nstreams, c->n_cu, c->opt.interp_span, &a.nsub_per_seg, &a.nseg);
+    else plan_interpolate(log2interp, n_in, p->nstreams, &a.nsub_per_seg, &a.nseg);
+    hipError_t e;
+    {
+        KTimer kt(c, SDRHIP_K_INTERPOLATE);
+        if (out_fmt == IQF_S8) {
+            if (count) e = use_wave ? launch_interpolate_wave_ragged_s8(log2interp, a, c->stream) : launch_interpolate_ragged_s8(log2interp, a, c->stream);
+            else e = use_wave ? launch_interpolate_wave_s8(log2interp, a, c->stream) : launch_interpolate_s8(log2interp, a, c->stream);
+        } else if (count) e = use_wave ? launch_interpolate_wave_ragged(log2interp, a, c->stream) : launch_interpolate_ragged(log2interp, a, c->stream);
+        else e = use_wave ? launch_interpolate_wave(log2interp, a, c->stream) : launch_interpolate(log2interp, a, c->stream);
+    }
+    if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "interpolate launch: %s", hipGetErrorString(e));
+    p->cur ^= 1;
+    return SDRHIP_OK;
+}
+} // namespace sdrhip
+
+extern "C" int sdrhip_interpolate(sdrhip_interpolators *p, int log2interp, const int16_t *iq_in, size_t n_in, size_t in_stride,
+                                  int16_t *iq_out, size_t out_stride, size_t *n_out, int mem)
+{
+    if (!p) return fail(SDRHIP_EINVAL, "interpolate: NULL handle");
+    sdrhip::CtxLock lock_(p->ctx);
+    if (log2interp < 0 || log2interp > 6) return fail(SDRHIP_EINVAL, "Invalid log2 interpolation factor"); // Upsampler.cpp:38-42
+    if (n_in && (!iq_in || !iq_out)) return fail(SDRHIP_EINVAL, "interpolate: NULL buffer");
+    sdrhip_ctx *c = p->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const int S = p->nstreams;
+    const size_t n_res = n_in << log2interp;
+    if (S == 1) { in_stride = n_in; out_stride = n_res; }
+    if (S > 1 && (in_stride < n_in || out_stride < n_res)) return fail(SDRHIP_EINVAL, "interpolate: stride smaller than the per-stream length");
+    if (mem == SDRHIP_MEM_DEVICE) {
+        if (n_in && (!aligned16(iq_in) || !aligned16(iq_out) || (S > 1 && ((in_stride & 3) || (out_stride & 3)))))
+            return fail(SDRHIP_EALIGN, "interpolate: device pointers must be 16-byte aligned and strides multiples of 4 samples");
+        return interpolate_device(p, log2interp, iq_in, n_in, in_stride, iq_out, out_stride, n_out);
+    }
+    if (int e = check_mem(mem)) return e;
+    if (n_in == 0) { if (n_out) *n_out = 0; return SDRHIP_OK; }
+    const size_t dis = (n_in + 3) & ~(size_t)3, dos = (n_res + 3) & ~(size_t)3;
+    int rc;
+    if ((rc = c->in.reserve((size_t)S * dis * 4 + 16))) return rc;
+    if ((rc = c->out.reserve((size_t)S * dos * 4 + 16))) return rc;
+    HIP_TRY(link_copy2d(c, c->in.p, dis * 4, iq_in, in_stride * 4, n_in * 4, S, hipMemcpyHostToDevice, c->stream));
+    if ((rc = interpolate_device(p, log2interp, c->in.as<int16_t>(), n_in, dis, c->out.as<int16_t>(), dos, n_out))) return rc;
+    HIP_TRY(link_copy2d(c, iq_out, out_stride * 4, c->out.p, dos * 4, n_res * 4, S, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SDRHIP_OK;
+}

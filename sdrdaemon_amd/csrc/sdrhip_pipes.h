@@ -1,0 +1,253 @@
+// sdrhip_pipes.h -- the fused Rx / Tx pipes of include/sdrhip.h: their handles, the ring of asynchronous batches and what the
+// units sdrhip_rx.cpp, sdrhip_rx_async.cpp, sdrhip_tx.cpp and sdrhip_tx_async.cpp share
+#pragma once
+#include "sdrhip_host.h"
+
+#include <cstring>
+#include <new>
+
+namespace sdrhip {
+// The ring of batches behind a pipe's submit / collect entries, created on first use with depth 4.  B has `state` (0 free, 1 being
+// filled, 2 in flight), the event `done` and release().  tail = the batch being filled, head = the next one to collect.
+template <class B> struct BatchRing {
+    std::vector<B> v;
+    size_t head = 0, tail = 0;
+
+    void release(bool wait) // wait: for the events of batches that may still be in flight (destruction)
+    {
+        for (auto &b : v) {
+            if (wait && b.done) (void)hipEventSynchronize(b.done);
+            b.release();
+        }
+    }
+    void reset(size_t depth) { release(false); v.assign(depth, B()); head = tail = 0; } // (the caller refuses while anything is in flight)
+    B &tail_batch() { if (v.empty()) v.assign(4, B()); return v[tail % v.size()]; }
+    // a batch that is being filled or in flight and satisfies pred
+    template <class P> bool any(P pred) const
+    {
+        for (const auto &b : v)
+            if (b.state != 0 && pred(b)) return true;
+        return false;
+    }
+    bool busy() const { return any([](const B &) { return true; }); }
+    static int ensure_event(B &b)
+    {
+        if (!b.done && hipEventCreateWithFlags(&b.done, hipEventDisableTiming) != hipSuccess) { b.done = nullptr; return fail(SDRHIP_EDEVICE, "hipEventCreate"); }
+        return SDRHIP_OK;
+    }
+    // the oldest batch once it has finished.  wait = 1: a batch that is still being filled goes out as it is (launch_filling, the
+    // end of a stream), then the wait happens OUTSIDE the context lock: the submitting thread -- the reference's source / reader
+    // thread -- keeps feeding the ring while the collecting thread sleeps on the oldest batch's event
+    template <class F> int wait_oldest(std::unique_lock<std::recursive_mutex> &lock_, int wait, const char *who, F launch_filling, B **bp)
+    {
+        if (v.empty()) return fail(SDRHIP_EBUSY, "%s: nothing was submitted", who);
+        for (;;) {
+            B &h = v[head % v.size()];
+            if (h.state == 0) return fail(SDRHIP_EBUSY, "%s: nothing was submitted", who); // (SDRHIP_OK always means: one batch collected -- possibly empty)
+            if (h.state == 1) {
+                if (!wait) return fail(SDRHIP_EBUSY, "%s: the oldest batch is still being filled (wait = 1 launches it as it is)", who);
+                int rc = launch_filling(h);
+                if (rc) return rc;
+                ++tail;
+            }
+            const hipError_t q = hipEventQuery(h.done);
+            if (q == hipSuccess) { *bp = &h; break; }
+            if (q != hipErrorNotReady) return fail(SDRHIP_EDEVICE, "hipEventQuery: %s", hipGetErrorString(q));
+            if (!wait) return fail(SDRHIP_EBUSY, "%s: the oldest batch is still in flight", who);
+            const size_t at = head;
+            hipEvent_t ev = h.done;
+            lock_.unlock();
+            const hipError_t w = hipEventSynchronize(ev);
+            lock_.lock();
+            if (w != hipSuccess) return fail(SDRHIP_EDEVICE, "hipEventSynchronize: %s", hipGetErrorString(w));
+            if (head == at) { *bp = &v[at % v.size()]; break; }
+            // (another thread collected that batch meanwhile: look at the new head)
+        }
+        return SDRHIP_OK;
+    }
+};
+} // namespace sdrhip
+
+// --------------------------------------------------------------------------- fused Rx pipe
+struct sdrhip_rx {
+    sdrhip_ctx *ctx;
+    int nstreams;
+    sdrhip_rx_config cfg;
+    sdrhip_decimators *dec;
+    // [nstreams][cap_frames][128 + nb_fec][512].  A call fills slots r_base[s] .. r_base[s] + done of stream s; slot
+    // r_base[s] + done (the frame still being filled) is slot r_base[s] of the next call, so the window slides and nothing is
+    // copied until it reaches the end of the area.
+    sdrhip::DevBuf work;
+    size_t cap_frames;        // frame slots per stream in `work`
+    // the framing state, per stream.  The uniform step (sdrhip_rx_process) runs while every stream stands at the same position
+    // (rx_aligned) and moves them together; ragged calls move each by its own count
+    std::vector<size_t> r_base;        // slot of the frame being filled
+    std::vector<uint64_t> r_pending;   // decimated samples sitting in that slot (the partial frame)
+    std::vector<uint8_t> r_open;       // it has its meta block (a frame was started)
+    std::vector<uint16_t> r_count;     // its m_frameCount
+    // what sdrhip_rx_frames_view shows: the frames the last call DELIVERED
+    const uint8_t *view_base = nullptr; // slot 0 of the delivered window of stream 0
+    size_t view_stride = 0;             // bytes between streams
+    size_t view_frames = 0;
+    sdrhip::DevBuf lin[2];    // stream-order decimator output of a call that is framed by K2 (two: pipelined mode)
+    int lin_sel = 0;
+    sdrhip::DevBuf flist;     // frame list of the generic encode launch (device), relative to the window
+    std::vector<int32_t> flist_host;
+    size_t flist_done = 0, flist_cap = 0;
+    // ---- pipelined mode (sdrhip_rx_set_pipelined): a call delivers the frames the PREVIOUS call completed; their
+    // recovery blocks are computed by encoder workgroups inside this call's decimator launch (rx_fused_kernel)
+    int pipelined = 0;
+    struct Late {
+        bool have = false;          // frames completed by the previous call wait for delivery
+        bool encode = false;        // ... and still have to be encoded (k)
+        sdrhip::Enc128Args k;
+        const uint8_t *base = nullptr;
+        size_t stride = 0, frames = 0, frame_bytes = 0;
+        size_t slot0 = 0;           // window position inside `work` (overlap check of the sliding window), SIZE_MAX = other area
+    } late;
+    sdrhip::DevBuf old_work;  // the previous frame area after a re-allocation, kept while `late` points into it
+    // overlap mode (option rx_fused = 3): the waiting encode runs on the context's second stream beside the next call's decimator.
+    // ev_framed: recorded on the first stream when a call has written everything its deferred encode reads (decimator + K2);
+    // ev_enc: recorded on the second stream behind the encode, the first stream waits for it before the frames are delivered
+    hipEvent_t ev_framed = nullptr, ev_enc = nullptr;
+    // ---- asynchronous host-pointer entry (sdrhip_rx_submit / sdrhip_rx_collect): a ring of batches
+    struct Batch {
+        sdrhip::PinnedBuf in;     // the submitted blocks, appended: [block][stream][n] (unless the caller's memory is pinned by us)
+        sdrhip::DevBuf din;       // [stream][dstride] on the device
+        sdrhip::PinnedBuf out;    // the batch's finished frames [stream][frames][128 + R][512]
+        hipEvent_t done = nullptr;
+        std::vector<std::pair<const int16_t *, size_t> > blocks; // source of each block (host address, samples per stream) and
+        std::vector<size_t> strides;                             // its stream stride in samples
+        size_t n_in = 0;          // samples per stream so far
+        size_t in_cap = 0;        // row length of `in` in samples: staged blocks lie stream-major, [stream][in_cap], at their batch offset
+        uint32_t tv_sec = 0, tv_usec = 0;
+        size_t frames = 0, frame_bytes = 0;
+        int state = 0;            // 0 free, 1 filling, 2 in flight
+        // ---- a ragged batch (sdrhip_rx_submit_ragged; a batch holds one kind only): blocks of per-stream counts, packed
+        bool ragged = false;
+        struct Run { const char *p; size_t off, bytes; }; // packed bytes of one block: in place at p, or staged at `in` + off (p NULL)
+        std::vector<Run> r_runs;
+        std::vector<size_t> r_cnt;            // [block][stream] counts
+        std::vector<size_t> r_tot;            // per-stream samples so far
+        std::vector<uint32_t> r_sec, r_usec;  // the stamps of the batch's first block
+        size_t r_used = 0;                    // staged bytes in `in`
+        std::vector<size_t> r_frames;         // frames per stream of the launched batch, in stream order in `out`
+        sdrhip::PinnedBuf r_tab;              // K0p's table, then the frame list of the download
+        void release()
+        {
+            if (done) (void)hipEventDestroy(done);
+            done = nullptr;
+            in.release(); din.release(); out.release(); r_tab.release();
+        }
+    };
+    sdrhip::BatchRing<Batch> ring;
+    sdrhip::DevBuf a_pk, a_din, a_tab, a_frames; // ragged batches on the device: packed upload, K0p's rows, tables, compacted frames
+    int a_blocks = 1;             // blocks per launch
+    bool consumed = false;        // set by sdrhip_rx_process once the decimator launch of the call went out (the filter state advanced)
+    // ---- input format (sdrhip_rx_set_input_format): 8-bit input is widened by K0 into `wide`, the decimator's int16 input
+    int in_fmt = sdrhip::IQF_S16;
+    sdrhip::DevBuf wide;
+    // ---- ragged calls (sdrhip_rx_process_ragged)
+    std::vector<size_t> r_view_first, r_view_frames; // sdrhip_rx_frames_view_ragged: the frames the last call delivered
+    bool view_ragged = false;          // the last call's windows differ between streams: sdrhip_rx_frames_view refuses
+    sdrhip::PinnedBuf r_pin, r_flist_pin; // host-row staging and the encoder's frame list
+    sdrhip::DevBuf r_flist;
+};
+
+// --------------------------------------------------------------------------- fused Tx pipe
+struct sdrhip_tx {
+    sdrhip_ctx *ctx;
+    int nstreams;
+    int log2interp;
+    sdrhip_interpolators *itp;
+    sdrhip::DevBuf rxbuf, payload[2], outbuf;
+    sdrhip::DevBuf srcmap, restored; // no-copy mode (tx_gather): the decoder's position map and restored blocks, read by K5w's gather variant
+    size_t restored_slots = 0; // slots `restored` was zero-terminated for (its last slot must read zero)
+    // ---- pipelined mode (sdrhip_tx_set_pipelined): a call decodes ITS batch into payload[psel] -- on the context's second stream,
+    // with work buffers of its own -- while the first stream interpolates the batch the PREVIOUS call decoded (payload[psel ^ 1]);
+    // the samples are delivered one call late, like SDRdaemonFECBuffer delivers a frame when the next one begins (.cpp:133-139)
+    int pipelined = 0;
+    int psel = 0;
+    struct Late {
+        bool have = false;
+        size_t n_payload = 0, pstride = 0;
+        int log2interp = 0; // the factor in force when the batch was handed in
+    } late;
+    sdrhip::DevBuf plan_own, idx_own;
+    sdrhip::PinnedBuf pin_own;
+    hipEvent_t ev_in = nullptr;              // first stream: the caller's device rx buffer is ready
+    hipEvent_t ev_up = nullptr;              // second stream: the upload of the caller's HOST rx buffer has read it (the call returns behind it)
+    hipEvent_t ev_dec = nullptr;             // second stream: the waiting batch is decoded
+    hipEvent_t ev_itp[2] = {nullptr, nullptr}; // first stream: the interpolator has read payload[i]
+    bool itp_pending[2] = {false, false};
+    // ---- asynchronous host-pointer entry (sdrhip_tx_submit / sdrhip_tx_collect): a ring of batches of received frames
+    struct ABatch {
+        sdrhip::PinnedBuf in;        // the batch's received super blocks [stream][frame][128][512] (staged; sdrhip_host_alloc memory is used in place)
+        sdrhip::DevBuf din, dout, db0; // ... on the device; its samples [stream][dos]; its meta blocks [stream * nframes][508]
+        sdrhip::PinnedBuf out;       // samples, then meta blocks, downloaded
+        hipEvent_t done = nullptr;
+        size_t nframes = 0, n_res = 0, dos = 0;
+        int state = 0;            // 0 free, 2 in flight
+        // a batch of raw datagrams (sdrhip_tx_submit_datagrams): `in` holds them packed, `out` the gathered delivery (every
+        // stream's samples, then the records, then the meta blocks); tab / seg = its collector tables and gather segments
+        bool dg = false;
+        sdrhip::PinnedBuf tab, seg;
+        std::vector<size_t> frames; // released frames per stream
+        int log2interp = 0;
+        size_t esz = 4;
+        void release()
+        {
+            if (done) (void)hipEventDestroy(done);
+            done = nullptr;
+            in.release(); din.release(); dout.release(); db0.release(); out.release(); tab.release(); seg.release();
+        }
+    };
+    sdrhip::BatchRing<ABatch> ring;
+    // device buffers of the datagram batches, shared by the ring (the context's stream orders the batches): the packed datagrams,
+    // the collector's [stream][pitch] rows, the interpolator's output rows, the meta blocks, the gathered delivery, its segments
+    sdrhip::DevBuf a_pk, a_pay, a_out, a_b0, a_gat, a_seg;
+    // ---- datagram entry (sdrhip_tx_process_datagrams): one SDRdaemonFECBuffer per stream, created on first use; the frames it
+    // releases go to payload[0] (or straight to the caller's device iq_out when log2interp = 0), the interpolator reads them there
+    sdrhip_fecbuf *fb = nullptr;
+    // ---- output format (sdrhip_tx_set_output_format): IQF_S8 = 2-byte samples from the interpolator's last stage (or K6n for x1)
+    int out_fmt = sdrhip::IQF_S16;
+};
+
+namespace sdrhip {
+// ---- Rx: every stream stands at the same frame position (what the uniform step, pipelined mode and uniform batches need)
+inline bool rx_aligned(const sdrhip_rx *rx)
+{
+    for (size_t s = 1; s < (size_t)rx->nstreams; ++s)
+        if (rx->r_base[s] != rx->r_base[0] || rx->r_pending[s] != rx->r_pending[0] || rx->r_open[s] != rx->r_open[0] ||
+            rx->r_count[s] != rx->r_count[0])
+            return false;
+    return true;
+}
+// batches of the ring that are being filled or in flight, of the ragged (or the uniform) kind
+inline bool rx_has_batches(const sdrhip_rx *rx, bool ragged)
+{
+    return rx->ring.any([ragged](const sdrhip_rx::Batch &b) { return b.ragged == ragged; });
+}
+// the ragged step (sdrhip_rx_process_ragged).  batch: a ragged asynchronous batch (rx_launch_ragged): int16 device rows that K0p
+// laid out, whatever the input format
+int rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, size_t in_stride, const uint32_t *tv_sec, const uint32_t *tv_usec,
+              uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem, bool batch = false);
+
+// ---- Tx: bytes per output sample, and the row pitch (samples) of the library's own output buffers: 16-byte rows either way
+inline size_t tx_esz(const sdrhip_tx *tx) { return tx->out_fmt == IQF_S8 ? 2 : 4; }
+inline size_t tx_pitch(const sdrhip_tx *tx, size_t n) { return tx->out_fmt == IQF_S8 ? (n + 7) & ~(size_t)7 : (n + 3) & ~(size_t)3; }
+// asynchronous batches of one kind in flight: raw datagrams (dg) or received frames
+inline bool tx_in_flight(const sdrhip_tx *tx, bool dg)
+{
+    return tx->ring.any([dg](const sdrhip_tx::ABatch &b) { return b.dg == dg; });
+}
+// decode S x nframes frames into `pay` ([S][pstride] samples): one batch, or one call per stream when the rows are padded
+int tx_decode(sdrhip_tx *tx, const uint8_t *drx, const uint8_t *indices, size_t nframes, DevBuf &pay, size_t pstride, const DecodeSide *side,
+              uint8_t *block0 = nullptr); // block0 (optional, device): [stream * nframes][508], the frames' meta blocks
+bool tx_gather_applies(const sdrhip_tx *tx, int log2interp);
+int tx_decode_gather(sdrhip_tx *tx, const uint8_t *drx, const uint8_t *indices, size_t nframes, InterpGather *g, uint8_t *block0 = nullptr);
+int tx_collector(sdrhip_tx *tx); // the datagram collector, created on first use
+// the interpolator behind the collector of a datagram call, each stream's own count (device, the classify pass's) of n_max at most:
+// x1 to 8-bit = K6n narrows; x2 .. x64 = one ragged launch; x1 int16 = nothing, the collector wrote the samples where they go
+int tx_interpolate_counts(sdrhip_tx *tx, const int16_t *pay, size_t n_max, size_t pitch, int16_t *dout, size_t dos, const int *counts);
+} // namespace sdrhip

@@ -1,0 +1,762 @@
+// sdrhip_rx.cpp -- the fused Rx pipe of include/sdrhip.h: life cycle, configuration, the uniform and the ragged step.
+#include "sdrhip_pipes.h"
+
+using namespace sdrhip;
+
+static int rx_check_config(const sdrhip_rx_config *cfg);
+
+extern "C" int sdrhip_rx_create(sdrhip_ctx *ctx, int nstreams, const sdrhip_rx_config *cfg, sdrhip_rx **out)
+{
+    if (!ctx || !cfg || !out || nstreams <= 0) return fail(SDRHIP_EINVAL, "rx_create: bad argument");
+    {
+        const int rcc = rx_check_config(cfg);
+        if (rcc) return rcc;
+    }
+    sdrhip_rx *rx = new (std::nothrow) sdrhip_rx();
+    if (!rx) return fail(SDRHIP_ENOMEM, "out of host memory");
+    rx->ctx = ctx; rx->nstreams = nstreams; rx->cfg = *cfg; rx->dec = nullptr;
+    rx->cap_frames = 0;
+    rx->r_base.assign((size_t)nstreams, 0); rx->r_pending.assign((size_t)nstreams, 0);
+    rx->r_open.assign((size_t)nstreams, 0); rx->r_count.assign((size_t)nstreams, 0);
+    int rc = sdrhip_decimators_create(ctx, nstreams, cfg->hb_variant, &rx->dec);
+    if (rc) { delete rx; return rc; }
+    *out = rx;
+    return SDRHIP_OK;
+}
+
+static int rx_check_config(const sdrhip_rx_config *cfg)
+{
+    if (cfg->log2decim < 0 || cfg->log2decim > 6) return fail(SDRHIP_EINVAL, "Invalid log2 decimation factor");
+    if (cfg->fcpos < 0 || cfg->fcpos > 2) return fail(SDRHIP_EINVAL, "Invalid Fc position index");
+    if (cfg->nb_fec < 0 || cfg->nb_fec > 128) return fail(SDRHIP_EINVAL, "nb_fec must be 0..128");
+    if (cfg->sample_bits < 1 || cfg->sample_bits > 16) return fail(SDRHIP_EINVAL, "sample_bits must be 1..16");
+    return SDRHIP_OK;
+}
+
+// the encode that a pipelined call left for the next launch, now (flush, reconfiguration, a call that cannot fuse it)
+static int rx_settle(sdrhip_rx *rx)
+{
+    if (!rx->late.encode) return SDRHIP_OK;
+    rx->late.encode = false;
+    sdrhip_ctx *c = rx->ctx;
+    if (c->opt.rx_fused != 3 || !rx->ev_framed) return fec_encode128_launch(c, rx->late.k);
+    // overlap mode: the encode goes to the second stream -- behind everything the call that left it had enqueued (ev_framed), beside
+    // whatever the first stream runs now (the decimator of the current call, enqueued just before) -- and the first stream picks
+    // up behind it: the frames are delivered, and the buffers reused, in first-stream order
+    hipStream_t s2 = nullptr;
+    int rc = ctx_stream2(c, &s2);
+    if (rc) return rc;
+    if (!rx->ev_enc) HIP_TRY(hipEventCreateWithFlags(&rx->ev_enc, hipEventDisableTiming));
+    HIP_TRY(hipStreamWaitEvent(s2, rx->ev_framed, 0));
+    if ((rc = fec_encode128_launch(c, rx->late.k, s2))) return rc;
+    HIP_TRY(hipEventRecord(rx->ev_enc, s2));
+    HIP_TRY(hipStreamWaitEvent(c->stream, rx->ev_enc, 0));
+    return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_rx_set_pipelined(sdrhip_rx *rx, int on)
+{
+    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
+    sdrhip::CtxLock lock_(rx->ctx);
+    if (!on && rx->late.have) return fail(SDRHIP_EINVAL, "rx_set_pipelined: sdrhip_rx_flush the waiting frames first");
+    if (on && !rx_aligned(rx)) return fail(SDRHIP_EINVAL, "rx_set_pipelined: ragged calls left the streams at different frame positions");
+    rx->pipelined = on ? 1 : 0;
+    return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_rx_set_input_format(sdrhip_rx *rx, int fmt)
+{
+    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
+    sdrhip::CtxLock lock_(rx->ctx);
+    if (fmt != SDRHIP_IQ_S16 && fmt != SDRHIP_IQ_U8 && fmt != SDRHIP_IQ_S8) return fail(SDRHIP_EINVAL, "rx_set_input_format: unknown format %d", fmt);
+    if (rx->ring.busy()) return fail(SDRHIP_EINVAL, "rx_set_input_format: asynchronous batches are being filled or in flight: collect them first");
+    if (rx->late.have) return fail(SDRHIP_EINVAL, "rx_set_input_format: frames of the previous call wait for delivery (pipelined mode): sdrhip_rx_flush them first");
+    rx->in_fmt = fmt;
+    return SDRHIP_OK;
+}
+
+// K0: 8-bit rows (in_stride a multiple of 8 samples, or one stream) -> rx->wide [stream][dstride] int16, ahead of the decimator
+static int rx_widen(sdrhip_rx *rx, const uint8_t *in, size_t in_stride, size_t n_in, size_t dstride, const int16_t **din)
+{
+    sdrhip_ctx *c = rx->ctx;
+    int rc = rx->wide.reserve((size_t)rx->nstreams * dstride * 4 + 16);
+    if (rc) return rc;
+    hipError_t e;
+    {
+        KTimer kt(c, SDRHIP_K_CONVERT);
+        e = launch_iq8_widen(rx->in_fmt, in, in_stride, rx->wide.as<int16_t>(), dstride, n_in, rx->nstreams, c->stream);
+    }
+    if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "widen launch: %s", hipGetErrorString(e));
+    *din = rx->wide.as<int16_t>();
+    return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_rx_reconfigure(sdrhip_rx *rx, const sdrhip_rx_config *cfg)
+{
+    if (!rx || !cfg) return fail(SDRHIP_EINVAL, "rx_reconfigure: NULL argument");
+    sdrhip::CtxLock lock_(rx->ctx);
+    int rc = rx_check_config(cfg);
+    if (rc) return rc;
+    if (cfg->hb_variant != rx->cfg.hb_variant) return fail(SDRHIP_EINVAL, "rx_reconfigure: hb_variant is fixed at creation");
+    sdrhip_ctx *c = rx->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    if (cfg->nb_fec != rx->cfg.nb_fec && rx->late.have)
+        return fail(SDRHIP_EINVAL, "rx_reconfigure: frames of the previous call wait for delivery (pipelined mode): sdrhip_rx_flush them "
+                                   "before changing fecblk (they carry the old frame size)");
+    if (cfg->nb_fec != rx->cfg.nb_fec && rx->cap_frames) {
+        // the slots change size: the frame being filled (its 128 original super blocks) moves to slot 0 of a new area
+        if ((rc = rx_settle(rx))) return rc;
+        const int S = rx->nstreams;
+        const size_t old_fb = (size_t)(SDRHIP_NB_ORIGINAL + rx->cfg.nb_fec) * SDRHIP_UDPSIZE;
+        const size_t new_fb = (size_t)(SDRHIP_NB_ORIGINAL + cfg->nb_fec) * SDRHIP_UDPSIZE;
+        DevBuf fresh;
+        if ((rc = fresh.reserve((size_t)S * rx->cap_frames * new_fb))) return rc;
+        if (!rx_aligned(rx)) { // (per-stream windows: each open frame moves to slot 0 of its stream)
+            for (int s = 0; s < S; ++s)
+                if (rx->r_open[(size_t)s])
+                    HIP_TRY(hipMemcpyAsync(fresh.as<uint8_t>() + (size_t)s * rx->cap_frames * new_fb,
+                                           rx->work.as<uint8_t>() + (size_t)s * rx->cap_frames * old_fb + rx->r_base[(size_t)s] * old_fb,
+                                           (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE, hipMemcpyDeviceToDevice, c->stream));
+        } else if (rx->r_open[0])
+            HIP_TRY(hipMemcpy2DAsync(fresh.p, rx->cap_frames * new_fb, rx->work.as<uint8_t>() + rx->r_base[0] * old_fb,
+                                     rx->cap_frames * old_fb, (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE, S, hipMemcpyDeviceToDevice,
+                                     c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream)); // earlier launches may still use the old area
+        // (no frames wait for delivery here: a fecblk change with late.have set was refused above)
+        rx->old_work.release();
+        rx->work.release();
+        rx->work = fresh;
+        rx->r_base.assign((size_t)S, 0);
+        rx->view_base = nullptr;
+        rx->view_frames = 0;
+        rx->view_ragged = false;
+    }
+    rx->cfg = *cfg;
+    return SDRHIP_OK;
+}
+
+extern "C" void sdrhip_rx_destroy(sdrhip_rx *rx)
+{
+    if (!rx) return;
+    sdrhip_decimators_destroy(rx->dec);
+    rx->work.release();
+    rx->old_work.release();
+    rx->lin[0].release();
+    rx->lin[1].release();
+    rx->flist.release();
+    rx->wide.release();
+    rx->r_pin.release(); rx->r_flist_pin.release(); rx->r_flist.release();
+    if (rx->ev_framed) (void)hipEventDestroy(rx->ev_framed);
+    if (rx->ev_enc) (void)hipEventDestroy(rx->ev_enc);
+    rx->ring.release(true);
+    rx->a_pk.release(); rx->a_din.release(); rx->a_tab.release(); rx->a_frames.release();
+    delete rx;
+}
+
+extern "C" int sdrhip_rx_frames_view(const sdrhip_rx *rx, const uint8_t **base, size_t *stream_stride_bytes, size_t *n_frames)
+{
+    if (!rx || !base || !stream_stride_bytes || !n_frames) return fail(SDRHIP_EINVAL, "rx_frames_view: NULL argument");
+    sdrhip::CtxLock lock_(rx->ctx);
+    if (rx->view_ragged) return fail(SDRHIP_EINVAL, "rx_frames_view: the last call's windows differ between streams: use sdrhip_rx_frames_view_ragged");
+    *base = rx->view_base;
+    *stream_stride_bytes = rx->view_stride;
+    *n_frames = rx->view_frames;
+    return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_rx_frames_view_ragged(const sdrhip_rx *rx, const uint8_t **base, size_t *stream_stride_bytes, size_t *first_slot,
+                                            size_t *n_frames)
+{
+    if (!rx || !base || !stream_stride_bytes || !first_slot || !n_frames) return fail(SDRHIP_EINVAL, "rx_frames_view_ragged: NULL argument");
+    sdrhip::CtxLock lock_(rx->ctx);
+    const int S = rx->nstreams;
+    const size_t fb = (size_t)(SDRHIP_NB_ORIGINAL + rx->cfg.nb_fec) * SDRHIP_UDPSIZE;
+    if (rx->view_ragged) {
+        *base = rx->work.as<uint8_t>();
+        *stream_stride_bytes = rx->cap_frames * fb;
+        for (int s = 0; s < S; ++s) { first_slot[s] = rx->r_view_first[(size_t)s]; n_frames[s] = rx->r_view_frames[(size_t)s]; }
+        return SDRHIP_OK;
+    }
+    // (the last call delivered the same window of every stream: the uniform view, as slot offsets from the area)
+    const size_t slot = rx->view_base && rx->work.p && rx->view_base >= rx->work.as<uint8_t>() && rx->view_stride == rx->cap_frames * fb
+                            ? (size_t)(rx->view_base - rx->work.as<uint8_t>()) / fb : 0;
+    *base = rx->view_base ? rx->view_base - slot * fb : nullptr;
+    *stream_stride_bytes = rx->view_stride;
+    for (int s = 0; s < S; ++s) { first_slot[s] = slot; n_frames[s] = rx->view_frames; }
+    return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_rx_last_plan(const sdrhip_rx *rx, sdrhip_decim_plan *out)
+{
+    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
+    return sdrhip_decimators_last_plan(rx->dec, out);
+}
+
+extern "C" size_t sdrhip_rx_max_frames(const sdrhip_rx *rx, size_t n_in)
+{
+    if (!rx) return 0;
+    sdrhip::CtxLock lock_(rx->ctx);
+    size_t now = 0; // (the stream that completes the most: every stream, while they stand at the same position)
+    for (size_t s = 0; s < (size_t)rx->nstreams; ++s) {
+        const size_t f = (size_t)((rx->r_pending[s] + (n_in >> rx->cfg.log2decim)) / SDRHIP_SAMPLES_PER_FRAME);
+        if (f > now) now = f;
+    }
+    if (!rx->pipelined) return now;
+    return rx->late.have && rx->late.frames > now ? rx->late.frames : now; // (a pipelined call delivers the previous call's frames)
+}
+
+// delivery of a finished window: optional copy to the caller's buffer, and the zero-copy view
+static int rx_deliver(sdrhip_rx *rx, const uint8_t *base, size_t stride, size_t frames, size_t frame_bytes, uint8_t *frames_out,
+                      size_t frame_stride_bytes, size_t *n_frames, int mem)
+{
+    sdrhip_ctx *c = rx->ctx;
+    const int S = rx->nstreams;
+    if (frames && frames_out) {
+        if (S > 1 && frame_stride_bytes < frames * frame_bytes) return fail(SDRHIP_EINVAL, "rx_process: frame stride too small");
+        HIP_TRY(link_copy2d(c, frames_out, S > 1 ? frame_stride_bytes : frames * frame_bytes, base, stride, frames * frame_bytes, S,
+                            mem == SDRHIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+    } else if (frames && mem != SDRHIP_MEM_DEVICE) {
+        return fail(SDRHIP_EINVAL, "rx_process: NULL frames_out");
+    }
+    rx->view_base = base; rx->view_stride = stride; rx->view_frames = frames;
+    rx->view_ragged = false;
+    if (n_frames) *n_frames = frames;
+    return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_rx_flush(sdrhip_rx *rx, uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem)
+{
+    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
+    sdrhip::CtxLock lock_(rx->ctx);
+    if (n_frames) *n_frames = 0;
+    if (int e = check_mem(mem)) return e;
+    if (!rx->late.have) { rx->view_frames = 0; return SDRHIP_OK; }
+    HIP_TRY(hipSetDevice(rx->ctx->device));
+    int rc;
+    if ((rc = rx_settle(rx))) return rc;
+    if ((rc = rx_deliver(rx, rx->late.base, rx->late.stride, rx->late.frames, rx->late.frame_bytes, frames_out, frame_stride_bytes, n_frames, mem))) return rc;
+    rx->late.have = false;
+    if (mem == SDRHIP_MEM_HOST) HIP_TRY(hipStreamSynchronize(rx->ctx->stream));
+    return SDRHIP_OK;
+}
+
+// the 24-byte MetaDataFEC record (UDPSinkFEC.cpp:87-132) with a ZERO stamp, and in w[5] the boost::crc_32_type over its first 20
+// bytes (:106-109): the affine part of every frame's CRC.  A frame's own stamp (the reference calls gettimeofday when it opens the
+// frame, :90-104) is the call's plus its first sample's offset on the sample clock: w[3], w[4] and the CRC follow per frame on the
+// device (frame_meta_words)
+static void rx_meta_base(const sdrhip_rx_config &cfg, unsigned ssd, unsigned w[6])
+{
+    uint8_t m[24];
+    const uint32_t fc = cfg.center_frequency_khz, sr = cfg.sample_rate;
+    memcpy(m + 0, &fc, 4); memcpy(m + 4, &sr, 4);
+    m[8] = (uint8_t)((ssd - 1) / 8 + 1); // setSampleBytes((sampleSize - 1) / 8 + 1), sdrdaemonrx.cpp:643
+    m[9] = (uint8_t)ssd;                 // setSampleBits(sampleSize), :642
+    m[10] = SDRHIP_NB_ORIGINAL; m[11] = (uint8_t)cfg.nb_fec;
+    memset(m + 12, 0, 8);
+    uint32_t crc = 0xFFFFFFFFu;
+    for (int i = 0; i < 20; ++i) {
+        crc ^= m[i];
+        for (int k = 0; k < 8; ++k) crc = (crc & 1) ? 0xEDB88320u ^ (crc >> 1) : crc >> 1;
+    }
+    crc ^= 0xFFFFFFFFu;
+    memcpy(m + 20, &crc, 4);
+    memcpy(w, m, 24);
+}
+
+// host input of the uniform step: S rows of n_in samples of esz bytes -> [S][dstride] rows the first kernel reads.  A small call
+// skips the copy engine: the kernel reads pinned host memory over the link itself, and the buffer is free again when the call
+// returns (host-pointer calls end with a stream synchronisation); a large one goes to c->in in one 2-D copy
+static int rx_stage_in(sdrhip_ctx *c, const void *src, size_t in_stride, size_t n_in, int S, size_t esz, size_t dstride, const void **out)
+{
+    int rc;
+    if ((size_t)S * dstride * esz <= SDRHIP_ZEROCOPY_MAX) {
+        if ((rc = c->zin.reserve((size_t)S * dstride * esz + 16))) return rc;
+        for (int s = 0; s < S; ++s) memcpy(c->zin.as<char>() + (size_t)s * dstride * esz, static_cast<const char *>(src) + (size_t)s * in_stride * esz, n_in * esz);
+        link_bytes(c, hipMemcpyHostToDevice, (size_t)S * n_in * esz); // (read by the kernel over the link)
+        *out = c->zin.p;
+    } else {
+        if ((rc = c->in.reserve((size_t)S * dstride * esz + 16))) return rc;
+        HIP_TRY(link_copy2d(c, c->in.p, dstride * esz, src, in_stride * esz, n_in * esz, S, hipMemcpyHostToDevice, c->stream));
+        *out = c->in.p;
+    }
+    return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_in, size_t in_stride, uint32_t tv_sec, uint32_t tv_usec,
+                                 uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem)
+{
+    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
+    sdrhip::CtxLock lock_(rx->ctx);
+    if (n_frames) *n_frames = 0;
+    if (rx_has_batches(rx, true)) return fail(SDRHIP_EINVAL, "rx_process: ragged batches are being filled or in flight: collect them first");
+    if (n_in && !rx_aligned(rx)) {
+        // ragged calls left the streams at different frame positions: a ragged call with equal counts and stamps; *n_frames = the
+        // largest per-stream count (sdrhip_rx_frames_view_ragged has each)
+        const size_t S = (size_t)rx->nstreams;
+        std::vector<size_t> cnt(S, n_in), nf(S, 0);
+        std::vector<uint32_t> sec(S, tv_sec), usec(S, tv_usec);
+        const int rc = rx_ragged(rx, iq_in, cnt.data(), in_stride, sec.data(), usec.data(), frames_out, frame_stride_bytes, nf.data(), mem);
+        if (rc) return rc;
+        size_t most = 0;
+        for (size_t s = 0; s < S; ++s) if (nf[s] > most) most = nf[s];
+        if (n_frames) *n_frames = most;
+        return SDRHIP_OK;
+    }
+    if (n_in == 0) {
+        // an empty call completes nothing; in pipelined mode it still DELIVERS what the previous call completed (the header's
+        // contract: every call delivers the frames of the one before it)
+        if (rx->pipelined && rx->late.have) return sdrhip_rx_flush(rx, frames_out, frame_stride_bytes, n_frames, mem);
+        rx->view_frames = 0;
+        rx->view_ragged = false;
+        return SDRHIP_OK;
+    }
+    if (!iq_in) return fail(SDRHIP_EINVAL, "rx_process: NULL input");
+    sdrhip_ctx *c = rx->ctx;
+    rx->consumed = false;
+    HIP_TRY(hipSetDevice(c->device));
+    const int S = rx->nstreams, L = rx->cfg.log2decim, R = rx->cfg.nb_fec;
+    const int FB = SDRHIP_NB_ORIGINAL + R;
+    const size_t frame_bytes = (size_t)FB * SDRHIP_UDPSIZE;
+    const size_t n_dec = n_in >> L;
+    const uint64_t pending = rx->r_pending[0]; // (every stream stands here: rx_aligned)
+    const bool frame_open = rx->r_open[0] != 0;
+    const uint64_t total = pending + n_dec;
+    const size_t done = (size_t)(total / SDRHIP_SAMPLES_PER_FRAME);
+    const uint64_t rest = total - (uint64_t)done * SDRHIP_SAMPLES_PER_FRAME;
+    if (S == 1) in_stride = n_in;
+    const size_t deliver_now = rx->pipelined ? (rx->late.have ? rx->late.frames : 0) : done;
+    const size_t deliver_fb = rx->pipelined && rx->late.have ? rx->late.frame_bytes : frame_bytes;
+    if (deliver_now && !frames_out && mem != SDRHIP_MEM_DEVICE) return fail(SDRHIP_EINVAL, "rx_process: NULL frames_out");
+    if (frames_out && S > 1 && deliver_now && frame_stride_bytes < deliver_now * deliver_fb) return fail(SDRHIP_EINVAL, "rx_process: frame stride too small");
+
+    const int16_t *din = iq_in;
+    size_t dstride = in_stride;
+    int rc;
+    // 8-bit input: 2 bytes per sample cross the link (rows of a multiple of 8 samples: K0's 16-byte loads), K0 widens them into
+    // rx->wide, which the decimator reads as it reads int16 input
+    const bool wide8 = rx->in_fmt != IQF_S16;
+    const void *src = iq_in;
+    if ((rc = check_mem(mem))) return rc;
+    if (mem == SDRHIP_MEM_HOST) {
+        dstride = wide8 ? (n_in + 7) & ~(size_t)7 : (n_in + 3) & ~(size_t)3;
+        if ((rc = rx_stage_in(c, iq_in, in_stride, n_in, S, wide8 ? 2 : 4, dstride, &src))) return rc;
+    } else if (!aligned16(iq_in) || (S > 1 && (in_stride & (wide8 ? 7 : 3)))) {
+        return wide8 ? fail(SDRHIP_EALIGN, "rx_process: 8-bit device input must be 16-byte aligned, its stride a multiple of 8 samples")
+                     : fail(SDRHIP_EALIGN, "rx_process: device input must be 16-byte aligned");
+    }
+    din = static_cast<const int16_t *>(src);
+    if (wide8) {
+        const size_t sstride = dstride;
+        dstride = (n_in + 3) & ~(size_t)3;
+        if ((rc = rx_widen(rx, static_cast<const uint8_t *>(src), sstride, n_in, dstride, &din))) return rc;
+    }
+
+    // ---- work area [stream][slot][128 + R][512]: this call fills slots r_base .. r_base + done.  The
+    // finished frames stay readable in place until the next call (sdrhip_rx_frames_view); the frame still
+    // being filled is the first slot of the next call.  At the end of the area the window wraps: the open
+    // frame moves to slot 0 (one strided copy every few calls instead of a save + restore per call).  Frames that
+    // wait for delivery (pipelined mode) are never overwritten: a window that would reach them gets a new area.
+    const size_t need = done + 1;
+    if (rx->old_work.p && !(rx->late.have && rx->late.slot0 == SIZE_MAX)) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        rx->old_work.release();
+    }
+    if (rx->r_base[0] + need > rx->cap_frames) {
+        const bool late_here = rx->late.have && rx->late.slot0 != SIZE_MAX;
+        const bool wrap_hits_late = late_here && need > rx->late.slot0; // the wrapped window [0, need) against [slot0, slot0 + frames)
+        if (need > rx->cap_frames || wrap_hits_late) {
+            DevBuf bigger;
+            // the window: TWO calls' frames (round 5; four until then).  The step rewrites what it wrote two calls ago: 2 x 84 MB per
+            // 8-stream bank stay in the 256 MB of Infinity Cache, and on this memory system a write stream that stays there
+            // costs the read stream beside it less (profiles/r05_rx_direct.txt: decimator launch 0.2435 -> 0.2335 ms, encoder
+            // launch 0.052 -> 0.049 ms; a window of one call wraps -- a copy of the open frames -- on every call).  option rx_window (SDRHIP_RX_WINDOW at context creation, 1..8) = A / B
+            // (pipelined pipes keep the previous call's frames until they are delivered: four calls, as before)
+            const size_t wmul = c->opt.rx_window ? (size_t)c->opt.rx_window : rx->pipelined ? 4 : 2;
+            const size_t ncap = need > rx->cap_frames ? wmul * need : rx->cap_frames;
+            if ((rc = bigger.reserve((size_t)S * ncap * frame_bytes))) return rc;
+            if (frame_open)
+                HIP_TRY(hipMemcpy2DAsync(bigger.p, ncap * frame_bytes, rx->work.as<uint8_t>() + rx->r_base[0] * frame_bytes,
+                                         rx->cap_frames * frame_bytes, frame_bytes, S, hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream)); // earlier launches may still use the old area
+            if (late_here) { rx->old_work.release(); rx->old_work = rx->work; rx->late.slot0 = SIZE_MAX; }
+            else rx->work.release();
+            rx->work = bigger;
+            rx->cap_frames = ncap;
+        } else if (frame_open) {
+            uint8_t *w0 = rx->work.as<uint8_t>();
+            HIP_TRY(hipMemcpy2DAsync(w0, rx->cap_frames * frame_bytes, w0 + rx->r_base[0] * frame_bytes, rx->cap_frames * frame_bytes,
+                                     frame_bytes, S, hipMemcpyDeviceToDevice, c->stream));
+        }
+        rx->r_base.assign((size_t)S, 0);
+    }
+    const size_t stream_bytes = rx->cap_frames * frame_bytes;
+    uint8_t *work = rx->work.as<uint8_t>() + rx->r_base[0] * frame_bytes; // slot 0 of the window
+
+    // ---- meta record of the frames started by this call (UDPSinkFEC.cpp:87-132); the decimator kernel writes
+    // their meta blocks and super block headers on its way
+    unsigned ss = rx->cfg.sample_bits;
+    const int first_new = frame_open ? 1 : 0;
+    const int started = (int)(done + (rest > 0 ? 1 : 0)) - first_new; // frames whose first sample arrives now
+    RxMeta meta;
+    memset(&meta, 0, sizeof(meta));
+    if (started > 0) {
+        // tv_sec / tv_usec = the stamp of the call's first sample
+        rx_meta_base(rx->cfg, decimated_sample_size((unsigned)L, ss), meta.w);
+        meta.w[3] = tv_sec; meta.w[4] = tv_usec;
+        meta.first = first_new; meta.count = started; meta.frame_count0 = (unsigned)rx->r_count[0] + first_new;
+        meta.idx0 = first_new ? (uint64_t)SDRHIP_SAMPLES_PER_FRAME - pending : 0;
+        meta.rate = rx->cfg.sample_rate;
+    }
+
+    size_t n_out = 0;
+    EncodeLin elin;
+    bool use_lin = false, pack_with_encoder = false;
+    FrameArgs fa;
+    memset(&fa, 0, sizeof(fa));
+    const bool structured = R >= enc128_min_rows(c) && frame_bytes % 4 == 0; // gf_encode128_kernel serves this setting
+    const bool filterless = L == 0 || (rx->cfg.fcpos != SDRHIP_FC_CEN && L <= 2); // Decimators.cpp:22-91,127-170: no cascade kernel
+    const Enc128Args *fuse = rx->late.encode && (c->opt.rx_fused == 1 || c->opt.rx_fused == 2) ? &rx->late.k : nullptr;
+    // overlap mode: the waiting encode will run on the second stream BESIDE this call's decimator (rx_settle below), which therefore
+    // leaves room on its CUs (ring depth 3) and raises its waves' priority
+    const bool coresident = rx->late.encode && c->opt.rx_fused == 3 && rx->ev_framed;
+    bool fused = false;
+    // (matrix-core decimator: stream order + K2 + the encoder's fused copy, unless its waves frame their output themselves)
+    const bool direct = c->opt.rx_direct && !rx->pipelined && stream_bytes < 0x3fffffffu;
+    if (filterless || (!direct && decimate_mfma_applies(rx->dec, L, rx->cfg.fcpos, n_in))) {
+        // ---- decimate in stream order, then K2 lays the samples out as super blocks (+ meta blocks and headers)
+        const size_t lstride = (n_dec + 3) & ~(size_t)3;
+        if (rx->pipelined) rx->lin_sel ^= 1; // (the deferred encoder of the previous call still reads the other one)
+        DevBuf &lin = rx->lin[rx->lin_sel];
+        if (lin.cap < (size_t)S * lstride * 4 + 16 && rx->late.encode) { if ((rc = rx_settle(rx))) return rc; fuse = nullptr; HIP_TRY(hipStreamSynchronize(c->stream)); }
+        if ((rc = lin.reserve((size_t)S * lstride * 4 + 16))) return rc;
+        rc = decimate_device(rx->dec, L, rx->cfg.fcpos, &ss, din, n_in, dstride, lin.as<int16_t>(), lstride, &n_out, 0, 0, 0, nullptr, fuse, &fused, coresident);
+        if (rc) return rc;
+        rx->consumed = true;
+        if (fused) rx->late.encode = false;
+        // the frames that lie entirely inside this call's samples are laid out by the encoder (fused copy); K2 does
+        // the frame that was open when the call began, the one left open at its end, meta blocks and headers
+        if (fec_encode_fuses_framing(c, R)) {
+            const size_t first = pending ? 1 : 0;
+            if (done > first && frame_bytes % 4 == 0) {
+                elin.lin = lin.as<unsigned>(); elin.stride = lstride; elin.cap = (int)rx->cap_frames;
+                elin.first = (int)first; elin.pending = (int)pending;
+                use_lin = true;
+            }
+        }
+        if (use_lin) {
+            fa.skip_from = (size_t)elin.first * SDRHIP_SAMPLES_PER_FRAME - (size_t)elin.pending;
+            fa.skip_to = done * SDRHIP_SAMPLES_PER_FRAME - (size_t)elin.pending;
+        }
+        fa.in = lin.as<unsigned>(); fa.out = reinterpret_cast<unsigned *>(work);
+        fa.in_stride = lstride; fa.out_stride = stream_bytes / 4;
+        fa.n = n_dec; fa.frame_sample_base = pending; fa.frame_blocks = FB;
+        fa.meta_first = meta.first; fa.meta_count = meta.count; fa.meta_frame_count0 = meta.frame_count0;
+        memcpy(fa.meta_w, meta.w, sizeof(fa.meta_w));
+        fa.meta_idx0 = meta.idx0; fa.meta_rate = meta.rate;
+        // K2 rides in the encoder's launch when this call's frames are encoded right away by the structured encoder (one launch
+        // less per step); otherwise it goes out now
+        pack_with_encoder = !rx->pipelined && c->opt.rx_fused && structured && R > 0 && use_lin;
+        if (!pack_with_encoder) {
+            hipError_t e = launch_frame_pack(fa, S, c->stream);
+            if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "frame pack launch: %s", hipGetErrorString(e));
+        }
+    } else {
+        // ---- decimate straight into the frame layout (VALU cascade kernel with the framing epilogue, or the matrix-core kernel
+        // with its frame-layout stores and the VALU pieces' epilogue for meta blocks and headers)
+        rc = decimate_device(rx->dec, L, rx->cfg.fcpos, &ss, din, n_in, dstride, reinterpret_cast<int16_t *>(work), stream_bytes / 4, &n_out, 1,
+                             FB, pending, &meta);
+        if (rc) return rc;
+        rx->consumed = true;
+    }
+    if ((rc = rx_settle(rx))) return rc; // (a waiting encode that this call's launch could not take along)
+
+    // ---- FEC over the completed frames of every stream, recovery blocks land behind block 127
+    bool encode_later = false;
+    Enc128Args k;
+    memset(&k, 0, sizeof(k));
+    if (done && R > 0) {
+        if (structured) {
+            // structured encoder, one workgroup per (frame, half block); frame (s, f) of the window is frame s * cap_frames + f
+            k.in = work; k.out = work + (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE; k.tab = c->gf_tab; k.leaf_tables = c->enc_leaves; k.fft_tables = c->enc_fft; k.use_fft = c->opt.enc_fft;
+            k.bitslice = c->opt.enc_bitslice;
+            k.in_frame_bytes = frame_bytes; k.out_frame_bytes = frame_bytes;
+            k.rows = R; k.nframes = (int)((size_t)S * rx->cap_frames);
+            k.nlist = (int)((size_t)S * done); k.gen_done = (int)done; k.gen_cap = (int)rx->cap_frames;
+            if (use_lin) { k.lin = elin.lin; k.lin_stride = elin.stride; k.lin_cap = elin.cap; k.lin_first = elin.first; k.lin_pending = elin.pending; }
+            if (rx->pipelined) {
+                encode_later = true; // rides in the next call's decimator launch (or sdrhip_rx_flush)
+            } else if (pack_with_encoder) {
+                // encoder + K2 in one launch: the encoder derives the meta blocks of the frames this call starts itself and
+                // completes the frame that was open (its tail comes from the stream-order buffer), K2 leaves both alone
+                k.meta_first = meta.first; k.meta_count = meta.count; k.meta_frame_count0 = meta.frame_count0;
+                memcpy(k.meta_w, meta.w, sizeof(k.meta_w));
+                k.meta_idx0 = meta.idx0; k.meta_rate = meta.rate;
+                if (elin.first == 1) { k.lin_straddle = 1; fa.skip_from = 0; }
+                hipError_t e;
+                {
+                    KTimer kt(c, SDRHIP_K_FEC_ENCODE);
+                    e = launch_gf_encode128_pack(k, fa, S, c->stream);
+                }
+                if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "encode + frame pack launch: %s", hipGetErrorString(e));
+            } else if ((rc = fec_encode128_launch(c, k))) return rc;
+        } else {
+            // generic matrix kernel: one launch for every stream, frame list in groups of GF_FRAMES_PER_GROUP
+            if (rx->flist_done != done || rx->flist_cap != rx->cap_frames) {
+                HIP_TRY(hipStreamSynchronize(c->stream)); // a previous upload may still read flist_host
+                rx->flist_host.clear();
+                for (int s = 0; s < S; ++s)
+                    for (size_t f = 0; f < done; ++f) rx->flist_host.push_back((int32_t)(s * rx->cap_frames + f));
+                while (rx->flist_host.size() % GF_FRAMES_PER_GROUP) rx->flist_host.push_back(-1);
+                if ((rc = rx->flist.reserve(rx->flist_host.size() * 4))) return rc;
+                HIP_TRY(link_copy(c, rx->flist.p, rx->flist_host.data(), rx->flist_host.size() * 4, hipMemcpyHostToDevice, c->stream));
+                rx->flist_done = done; rx->flist_cap = rx->cap_frames;
+            }
+            if ((rc = fec_encode_device(c, work, frame_bytes, (size_t)S * rx->cap_frames, R, work + (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE,
+                                        frame_bytes, rx->flist.as<int32_t>(), (int)(rx->flist_host.size() / GF_FRAMES_PER_GROUP), nullptr)))
+                return rc;
+        }
+    }
+    // ---- delivery: this call's frames, or (pipelined) the previous call's, whose encode went out above
+    if (rx->pipelined) {
+        if (rx->late.have) {
+            if ((rc = rx_deliver(rx, rx->late.base, rx->late.stride, rx->late.frames, rx->late.frame_bytes, frames_out, frame_stride_bytes, n_frames, mem))) return rc;
+        } else {
+            rx->view_base = nullptr; rx->view_frames = 0; rx->view_ragged = false;
+        }
+        rx->late.have = done > 0;
+        rx->late.encode = encode_later;
+        if (encode_later && c->opt.rx_fused == 3) { // (everything the deferred encode reads has been enqueued on the first stream by now)
+            if (!rx->ev_framed) HIP_TRY(hipEventCreateWithFlags(&rx->ev_framed, hipEventDisableTiming));
+            HIP_TRY(hipEventRecord(rx->ev_framed, c->stream));
+        }
+        rx->late.k = k;
+        rx->late.base = work; rx->late.stride = stream_bytes; rx->late.frames = done; rx->late.frame_bytes = frame_bytes;
+        rx->late.slot0 = rx->r_base[0];
+    } else {
+        if ((rc = rx_deliver(rx, work, stream_bytes, done, frame_bytes, frames_out, frame_stride_bytes, n_frames, mem))) return rc;
+    }
+    // every stream moves on together; the frame still being filled opens the next call's window
+    rx->r_base.assign((size_t)S, rx->r_base[0] + done);
+    rx->r_pending.assign((size_t)S, rest);
+    rx->r_open.assign((size_t)S, rest > 0 ? 1 : 0);
+    rx->r_count.assign((size_t)S, (uint16_t)(rx->r_count[0] + done));
+    if (mem == SDRHIP_MEM_HOST) HIP_TRY(hipStreamSynchronize(c->stream));
+    return SDRHIP_OK;
+}
+
+// --------------------------------------------------------------------------- ragged Rx calls
+// Every stream takes its own count: K0r (8-bit input) -> K1r / filter-less kernel into stream order -> K2r into each stream's
+// own window -> one encoder launch over the list of every stream's completed frames.  A call that fails after it moved windows
+// leaves r_base moved (the open frames lie there now) and the rest of the framing state untouched.
+int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, size_t in_stride, const uint32_t *tv_sec, const uint32_t *tv_usec,
+                      uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem, bool batch)
+{
+    sdrhip_ctx *c = rx->ctx;
+    const int S = rx->nstreams, L = rx->cfg.log2decim, R = rx->cfg.nb_fec;
+    const size_t FB = (size_t)SDRHIP_NB_ORIGINAL + (size_t)R;
+    const size_t frame_bytes = FB * SDRHIP_UDPSIZE;
+    for (int s = 0; s < S; ++s) n_frames[s] = 0;
+    // ---- everything that can be refused is checked before anything is consumed
+    if (int e = check_mem(mem)) return e;
+    if (rx->pipelined) return fail(SDRHIP_EINVAL, "rx_process_ragged: not available in pipelined mode");
+    if (!batch && rx->ring.busy()) return fail(SDRHIP_EINVAL, "rx_process_ragged: asynchronous batches are being filled or in flight: collect them first");
+    size_t max_in = 0;
+    for (int s = 0; s < S; ++s) if (n_in[s] > max_in) max_in = n_in[s];
+    if (S == 1) in_stride = max_in;
+    if (S > 1 && in_stride < max_in) return fail(SDRHIP_EINVAL, "rx_process_ragged: in_stride smaller than the largest count");
+    if (max_in && !iq_in) return fail(SDRHIP_EINVAL, "rx_process_ragged: NULL input");
+    const bool wide8 = rx->in_fmt != IQF_S16 && !batch;
+    if (max_in && mem == SDRHIP_MEM_DEVICE && (!aligned16(iq_in) || (S > 1 && (in_stride & (wide8 ? 7 : 3)))))
+        return fail(SDRHIP_EALIGN, "rx_process_ragged: device input must be 16-byte aligned, its stride a multiple of %d samples", wide8 ? 8 : 4);
+    std::vector<size_t> done((size_t)S);
+    std::vector<uint64_t> rest((size_t)S);
+    size_t max_done = 0, sum_done = 0, max_dec = 0;
+    for (int s = 0; s < S; ++s) {
+        const size_t n_dec = n_in[s] >> L;
+        const uint64_t total = rx->r_pending[(size_t)s] + n_dec;
+        done[(size_t)s] = (size_t)(total / SDRHIP_SAMPLES_PER_FRAME);
+        rest[(size_t)s] = total - (uint64_t)done[(size_t)s] * SDRHIP_SAMPLES_PER_FRAME;
+        if (done[(size_t)s] > max_done) max_done = done[(size_t)s];
+        if (n_dec > max_dec) max_dec = n_dec;
+        sum_done += done[(size_t)s];
+    }
+    if (max_done && !frames_out && mem != SDRHIP_MEM_DEVICE) return fail(SDRHIP_EINVAL, "rx_process_ragged: NULL frames_out");
+    if (frames_out && S > 1 && max_done && frame_stride_bytes < max_done * frame_bytes)
+        return fail(SDRHIP_EINVAL, "rx_process_ragged: frame stride too small for the stream with the most frames (%zu)", max_done);
+    HIP_TRY(hipSetDevice(c->device));
+    rx->consumed = false;
+    if (max_in == 0) { // nothing arrives: nothing changes, nothing is delivered
+        rx->view_frames = 0; rx->view_ragged = false;
+        return SDRHIP_OK;
+    }
+    int rc;
+    // ---- windows: stream s fills slots r_base[s] .. r_base[s] + done[s] of its area; a window that would pass the end of the area
+    // moves that stream's open frame to slot 0 (the others stay where they are); a call that needs more slots than the area has
+    // gets a new area, every open frame at slot 0
+    size_t need_max = 0;
+    for (int s = 0; s < S; ++s) if (done[(size_t)s] + 1 > need_max) need_max = done[(size_t)s] + 1;
+    if (rx->old_work.p && !rx->late.have) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        rx->old_work.release();
+    }
+    if (need_max > rx->cap_frames) {
+        const size_t wmul = c->opt.rx_window ? (size_t)c->opt.rx_window : 2;
+        const size_t ncap = wmul * need_max;
+        DevBuf bigger;
+        if ((rc = bigger.reserve((size_t)S * ncap * frame_bytes))) return rc;
+        // (the old area and every window stay as they were until the copies have completed: a failure leaves the handle untouched)
+        hipError_t e = hipSuccess;
+        for (int s = 0; s < S && e == hipSuccess; ++s)
+            if (rx->r_open[(size_t)s])
+                e = hipMemcpyAsync(bigger.as<uint8_t>() + (size_t)s * ncap * frame_bytes,
+                                   rx->work.as<uint8_t>() + ((size_t)s * rx->cap_frames + rx->r_base[(size_t)s]) * frame_bytes, frame_bytes,
+                                   hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // earlier launches may still use the old area
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(c->stream);
+            bigger.release();
+            return fail(SDRHIP_EDEVICE, "rx_process_ragged: moving the open frames: %s", hipGetErrorString(e));
+        }
+        for (int s = 0; s < S; ++s) rx->r_base[(size_t)s] = 0;
+        rx->work.release();
+        rx->work = bigger;
+        rx->cap_frames = ncap;
+    } else {
+        for (int s = 0; s < S; ++s) {
+            if (rx->r_base[(size_t)s] + done[(size_t)s] + 1 <= rx->cap_frames) continue;
+            uint8_t *a0 = rx->work.as<uint8_t>() + (size_t)s * rx->cap_frames * frame_bytes;
+            if (rx->r_open[(size_t)s])
+                HIP_TRY(hipMemcpyAsync(a0, a0 + rx->r_base[(size_t)s] * frame_bytes, frame_bytes, hipMemcpyDeviceToDevice, c->stream));
+            rx->r_base[(size_t)s] = 0;
+        }
+    }
+    const size_t stream_bytes = rx->cap_frames * frame_bytes;
+    uint8_t *area = rx->work.as<uint8_t>();
+
+    // ---- the per-call table: counts (decimator), windows and meta records (K2r)
+    unsigned ss = rx->cfg.sample_bits;
+    unsigned mw[6]; // (the record with a zero stamp: shared, the config is; the stamps go per row)
+    rx_meta_base(rx->cfg, decimated_sample_size((unsigned)L, ss), mw);
+    std::vector<RaggedRow> rows((size_t)S);
+    memset(rows.data(), 0, rows.size() * sizeof(RaggedRow));
+    for (int s = 0; s < S; ++s) {
+        RaggedRow &r = rows[(size_t)s];
+        const int first_new = rx->r_open[(size_t)s] ? 1 : 0;
+        const int started = (int)(done[(size_t)s] + (rest[(size_t)s] > 0 ? 1 : 0)) - first_new;
+        r.out_off = rx->r_base[(size_t)s] * frame_bytes / 4;
+        r.frame_sample_base = rx->r_pending[(size_t)s];
+        if (started > 0 && (n_in[s] >> L)) {
+            r.meta_first = first_new; r.meta_count = started;
+            r.frame_count0 = (unsigned)rx->r_count[(size_t)s] + (unsigned)first_new;
+            r.meta_idx0 = first_new ? (uint64_t)SDRHIP_SAMPLES_PER_FRAME - rx->r_pending[(size_t)s] : 0;
+            r.tv_sec = tv_sec[s]; r.tv_usec = tv_usec[s];
+        }
+    }
+    const RaggedRow *rdev = nullptr;
+    if ((rc = ragged_prepare(rx->dec, L, rx->cfg.fcpos, n_in, rows.data(), &rdev))) return rc;
+
+    // ---- input: host rows staged stream by stream (n_in[s] samples each), 8-bit rows widened by K0r
+    const int16_t *din = iq_in;
+    size_t dstride = in_stride;
+    const void *src = iq_in;
+    if (mem == SDRHIP_MEM_HOST) {
+        dstride = wide8 ? (max_in + 7) & ~(size_t)7 : (max_in + 3) & ~(size_t)3;
+        if ((rc = ragged_stage_in(c, rx->r_pin, c->in, iq_in, in_stride, n_in, S, wide8 ? 2 : 4, dstride, &src))) return rc;
+        din = static_cast<const int16_t *>(src);
+    }
+    if (wide8) {
+        const size_t sstride = dstride;
+        dstride = (max_in + 3) & ~(size_t)3;
+        if ((rc = rx->wide.reserve((size_t)S * dstride * 4 + 16))) return rc;
+        hipError_t e;
+        {
+            KTimer kt(c, SDRHIP_K_CONVERT);
+            e = launch_iq8_widen_ragged(rx->in_fmt, static_cast<const uint8_t *>(src), sstride, rx->wide.as<int16_t>(), dstride, max_in, S, rdev, c->stream);
+        }
+        if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "widen launch: %s", hipGetErrorString(e));
+        din = rx->wide.as<int16_t>();
+    }
+
+    // ---- decimate: the matrix-core launch (K1mr) stores straight into each stream's window (context option rx_direct, the
+    // default), its VALU pieces write the meta blocks; otherwise stream order, and K2r lays each stream's samples into its window
+    const bool direct = ragged_mfma_planned(rx->dec) && c->opt.rx_direct && stream_bytes < 0x3fffffffu;
+    const size_t lstride = (max_dec + 3) & ~(size_t)3;
+    DevBuf &lin = rx->lin[0];
+    if (direct) {
+        rc = decimate_ragged_device(rx->dec, L, rx->cfg.fcpos, &ss, din, dstride, reinterpret_cast<int16_t *>(area), stream_bytes / 4,
+                                    rows.data(), rdev, 1, (int)FB, mw, rx->cfg.sample_rate);
+    } else {
+        if ((rc = lin.reserve((size_t)S * lstride * 4 + 16))) return rc;
+        rc = decimate_ragged_device(rx->dec, L, rx->cfg.fcpos, &ss, din, dstride, lin.as<int16_t>(), lstride, rows.data(), rdev);
+    }
+    if (rc) return rc;
+    rx->consumed = true;
+    if (max_dec && !direct) {
+        FrameArgs fa;
+        memset(&fa, 0, sizeof(fa));
+        fa.in = lin.as<unsigned>(); fa.out = reinterpret_cast<unsigned *>(area);
+        fa.in_stride = lstride; fa.out_stride = stream_bytes / 4;
+        fa.n = max_dec; fa.frame_blocks = (int)FB;
+        memcpy(fa.meta_w, mw, sizeof(fa.meta_w));
+        fa.meta_rate = rx->cfg.sample_rate;
+        hipError_t e = launch_frame_pack_ragged(fa, rdev, S, c->stream);
+        if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "frame pack launch: %s", hipGetErrorString(e));
+    }
+
+    // ---- FEC: one launch over the completed frames of every stream (a dense list: frame f of stream s = area frame s * cap + slot)
+    if (sum_done && R > 0) {
+        const size_t nl = (sum_done + GF_FRAMES_PER_GROUP - 1) / GF_FRAMES_PER_GROUP * GF_FRAMES_PER_GROUP;
+        if ((rc = rx->r_flist_pin.reserve(nl * 4))) return rc;
+        if ((rc = rx->r_flist.reserve(nl * 4))) return rc;
+        int32_t *fl = rx->r_flist_pin.as<int32_t>();
+        size_t k = 0;
+        for (int s = 0; s < S; ++s)
+            for (size_t f = 0; f < done[(size_t)s]; ++f) fl[k++] = (int32_t)((size_t)s * rx->cap_frames + rx->r_base[(size_t)s] + f);
+        while (k < nl) fl[k++] = -1;
+        HIP_TRY(hipMemcpyAsync(rx->r_flist.p, fl, nl * 4, hipMemcpyHostToDevice, c->stream));
+        rx->r_flist_pin.mark(c->stream);
+        if ((rc = fec_encode_device(c, area, frame_bytes, (size_t)S * rx->cap_frames, R, area + (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE,
+                                    frame_bytes, rx->r_flist.as<int32_t>(), (int)(nl / GF_FRAMES_PER_GROUP))))
+            return rc;
+    }
+
+    // ---- delivery: every stream's window (one 2-D copy when the windows line up, else a copy per stream)
+    bool same_base = true;
+    for (int s = 1; s < S; ++s) same_base = same_base && rx->r_base[(size_t)s] == rx->r_base[0];
+    if (frames_out && max_done) {
+        const hipMemcpyKind kind = mem == SDRHIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        if (same_base) {
+            HIP_TRY(link_copy2d(c, frames_out, S > 1 ? frame_stride_bytes : max_done * frame_bytes, area + rx->r_base[0] * frame_bytes, stream_bytes,
+                                max_done * frame_bytes, S, kind, c->stream));
+        } else {
+            for (int s = 0; s < S; ++s)
+                if (done[(size_t)s])
+                    HIP_TRY(link_copy(c, frames_out + (size_t)s * frame_stride_bytes, area + (size_t)s * stream_bytes + rx->r_base[(size_t)s] * frame_bytes,
+                                      done[(size_t)s] * frame_bytes, kind, c->stream));
+        }
+    }
+    rx->r_view_first.assign(rx->r_base.begin(), rx->r_base.end());
+    rx->r_view_frames.assign(done.begin(), done.end());
+    bool same_frames = true;
+    for (int s = 1; s < S; ++s) same_frames = same_frames && done[(size_t)s] == done[0];
+    rx->view_ragged = !(same_base && same_frames);
+    if (!rx->view_ragged) { rx->view_base = area + rx->r_base[0] * frame_bytes; rx->view_stride = stream_bytes; rx->view_frames = done[0]; }
+    for (int s = 0; s < S; ++s) {
+        n_frames[s] = done[(size_t)s];
+        rx->r_base[(size_t)s] += done[(size_t)s];
+        rx->r_pending[(size_t)s] = rest[(size_t)s];
+        rx->r_open[(size_t)s] = rest[(size_t)s] > 0 ? 1 : 0;
+        rx->r_count[(size_t)s] = (uint16_t)(rx->r_count[(size_t)s] + done[(size_t)s]);
+    }
+    if (mem == SDRHIP_MEM_HOST) HIP_TRY(hipStreamSynchronize(c->stream));
+    return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_rx_process_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, size_t in_stride, const uint32_t *tv_sec,
+                                        const uint32_t *tv_usec, uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem)
+{
+    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
+    if (!n_in || !tv_sec || !tv_usec || !n_frames) return fail(SDRHIP_EINVAL, "rx_process_ragged: NULL count, stamp or n_frames array");
+    sdrhip::CtxLock lock_(rx->ctx);
+    return rx_ragged(rx, iq_in, n_in, in_stride, tv_sec, tv_usec, frames_out, frame_stride_bytes, n_frames, mem);
+}

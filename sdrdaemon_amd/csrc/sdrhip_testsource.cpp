@@ -257,7 +257,7 @@ extern "C" int sdrhip_testsource_read(sdrhip_testsource *t, int16_t *iq_out, siz
     } else if (mem == SDRHIP_MEM_DEVICE) {
         if (!aligned16(iq_out) || (S > 1 && (out_stride & 3))) return fail(SDRHIP_EALIGN, "testsource_read: device output must be 16-byte aligned");
     } else {
-        return fail(SDRHIP_EINVAL, "mem must be SDRHIP_MEM_HOST or SDRHIP_MEM_DEVICE");
+        return check_mem(mem);
     }
     hipError_t e = launch_testsource(t->table, t->par, dout, dstride, n, S, c->stream);
     if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "testsource launch: %s", hipGetErrorString(e));
