@@ -549,6 +549,44 @@ int sdrhip_tx_submit_datagrams(sdrhip_tx *tx, const uint8_t *dgrams, const size_
 int sdrhip_tx_collect_datagrams(sdrhip_tx *tx, int16_t *iq_out, size_t out_stride, size_t max_frames, uint8_t *block0_out,
                                 sdrhip_fecbuf_frame *info_out, size_t *n_frames, int wait);
 
+/* ------------------------------------------------------------ Rx pipe fed datagrams -- */
+/* A hub between a fast link and a slow one: per stream, sdrdaemontx's receive half (UDPSourceFEC::read ->
+ * SDRdaemonFECBuffer::writeAndRead, sdrdaemontx.cpp:449-498) chained to sdrdaemonrx's send half (Downsampler::process ->
+ * UDPSinkFEC::write, sdrdaemonrx.cpp:619-644).  Radio heads that cannot afford the half-band cascades send undecimated IQSample
+ * streams as FEC-protected datagrams; this call repairs the losses, decimates, re-frames and re-protects them.
+ * Collect: dgrams, n_dgrams, dgram_stride_bytes, info_out and mem mean what they mean for sdrhip_fecbuf_write_and_read;
+ * info_out[s * max_released + k] is the record of the k-th frame stream s released, n_released[s] (host) their count.  The
+ * handle's collector (one SDRdaemonFECBuffer per stream, created on the first call) behaves exactly like the bank (dec_strict,
+ * dec_path, dec_plan apply; the initial slot's zero payload is a released frame like any other: sdrdaemontx hands it to its
+ * Upsampler too).
+ * Join: the released payloads of stream s (16129 samples each), in release order, go behind the samples the stream holds back
+ * from earlier calls (its carry).  Of carry + 16129 * n_released[s] samples the largest multiple of U is decimated, the rest --
+ * 63 samples at the most -- is the new carry.  U = 2^log2decim, but 4 for log2decim = 1 with fcpos inf / sup (decimate2_inf /
+ * _sup walk the input in fours, Decimators.cpp:48,76).  The carry is the remainder buffer a host loop would keep between
+ * Downsampler::process calls, not decimator state: it survives sdrhip_rx_reconfigure (a new U applies to the next call),
+ * sdrhip_rx_process[_ragged] neither read nor clear it, sdrhip_fecbuf_reset on the handle's collector clears it together with
+ * the collector.
+ * Decimate, frame, encode: one sdrhip_rx_process_ragged step with those counts; tv_sec[s] / tv_usec[s] (host arrays) stamp the
+ * first sample fed.  Its rules apply unchanged: a stream fed nothing keeps its filter history, open frame and counter; frames
+ * land at frames_out + s * frame_stride_bytes, n_frames[s] (host) of them; frames_out = NULL with SDRHIP_MEM_DEVICE leaves them
+ * to sdrhip_rx_frames_view_ragged; sdrhip_rx_last_plan reports the launch; streams stand at different frame positions
+ * afterwards.  sdrhip_rx_set_input_format does not apply (the wire carries IQSample).  Size frames_out with
+ * sdrhip_rx_max_frames(rx, 16129 * max_released + 63).
+ * SDRHIP_EINVAL with nothing consumed (collector, carry, histories, open frames and counters stay as they were): a stream that
+ * would release more than max_released (n_released holds every stream's count), NULL count or stamp arrays, a frame stride too
+ * small for the stream with the most frames, pipelined mode, asynchronous batches being filled or in flight.
+ * Device memory: dgrams as sdrhip_fecbuf_write_and_read, frames_out as sdrhip_rx_process_ragged; the call synchronises once, for
+ * the collector's read-back of the release counts.  Host memory: the call returns with the frames written; only datagrams,
+ * frames, records and counts cross the link, the samples between collector and decimator stay on the device. */
+int sdrhip_rx_process_datagrams(sdrhip_rx *rx, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes,
+                                const uint32_t *tv_sec, const uint32_t *tv_usec, size_t max_released,
+                                uint8_t *frames_out, size_t frame_stride_bytes, sdrhip_fecbuf_frame *info_out,
+                                size_t *n_released, size_t *n_frames, int mem);
+/* the handle's collector (borrowed; destroyed with the handle) for sdrhip_fecbuf_stats / sdrhip_fecbuf_reset */
+int sdrhip_rx_collector(sdrhip_rx *rx, sdrhip_fecbuf **out);
+/* carry: host array of nstreams entries, the samples each stream holds back (0 .. 63) */
+int sdrhip_rx_carry(const sdrhip_rx *rx, size_t *carry);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,7 @@ EXPORTS = [
     "sdrhip_decimate_ragged", "sdrhip_rx_process_ragged", "sdrhip_rx_frames_view_ragged",
     "sdrhip_rx_submit_ragged", "sdrhip_rx_collect_ragged",
     "sdrhip_tx_submit_datagrams", "sdrhip_tx_collect_datagrams",
+    "sdrhip_rx_process_datagrams", "sdrhip_rx_collector", "sdrhip_rx_carry",
 ]
 
 
@@ -146,6 +147,10 @@ def load():
     lib.sdrhip_rx_frames_view_ragged.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     lib.sdrhip_rx_submit_ragged.argtypes = [vp, vp, C.POINTER(sz), sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.sdrhip_rx_collect_ragged.argtypes = [vp, vp, sz, sz, C.POINTER(sz), i]
+    lib.sdrhip_rx_process_datagrams.argtypes = [vp, vp, C.POINTER(sz), sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), sz, vp, sz, vp,
+                                                C.POINTER(sz), C.POINTER(sz), i]
+    lib.sdrhip_rx_collector.argtypes = [vp, C.POINTER(vp)]
+    lib.sdrhip_rx_carry.argtypes = [vp, C.POINTER(sz)]
     lib.sdrhip_testsource_create.argtypes = [vp, i, C.POINTER(vp)]
     lib.sdrhip_testsource_destroy.argtypes = [vp]
     lib.sdrhip_testsource_destroy.restype = None

@@ -5,6 +5,12 @@
 // max_frames and a staging slot at or past nslots are skipped, and the copy skips a slot the scatter pass did not fill (dmap preset
 // to -1), so that counts that disagree with the shadow (the shadow check counts them) never write outside the buffers.  (One text
 // for both: the bank's kernels compile to the instructions they had.)
+// With FB_ROWS 1 (and FB_PACKED 0) by rx_join_kernels.hip: the scatter and copy passes alone, for the Rx pipe fed datagrams
+// (sdrhip_rx_process_datagrams): stream s's payloads go row_off[s] samples behind a.data_out + s * a.data_stride, behind the
+// samples the stream's row holds back from earlier calls.
+#ifndef FB_ROWS
+#define FB_ROWS 0
+#endif
 #ifndef SDRHIP_FECBUF_PASSES_COMMON
 #define SDRHIP_FECBUF_PASSES_COMMON
 typedef unsigned uint4_t __attribute__((ext_vector_type(4)));
@@ -56,7 +62,13 @@ __device__ __forceinline__ void copy_dwords(unsigned *dst, const unsigned *src, 
 #else
 #define FB_STREAM_DG(s) (a.dg + (size_t)(s) * a.dg_stride)
 #endif
+#if FB_ROWS
+#define FB_STREAM_OUT(s) (a.data_out + (size_t)(s) * a.data_stride + (size_t)row_off[s] * 4)
+#else
+#define FB_STREAM_OUT(s) (a.data_out + (size_t)(s) * a.data_stride)
+#endif
 
+#if !FB_ROWS
 #if FB_PACKED
 __global__ __launch_bounds__(CL_NT) void fecbuf_classify_packed_kernel(FecBufArgs a, const long long *dg_off)
 #else
@@ -252,9 +264,12 @@ __global__ __launch_bounds__(CL_NT) void fecbuf_classify_kernel(FecBufArgs a)
         c[6] = c[7] = 0;
     }
 }
+#endif // !FB_ROWS
 
 #if FB_PACKED
 __global__ __launch_bounds__(SC_NT) void fecbuf_scatter_packed_kernel(FecBufArgs a, const long long *dg_off, int nslots)
+#elif FB_ROWS
+__global__ __launch_bounds__(SC_NT) void fecbuf_scatter_rows_kernel(FecBufArgs a, const unsigned *row_off)
 #else
 __global__ __launch_bounds__(SC_NT) void fecbuf_scatter_kernel(FecBufArgs a)
 #endif
@@ -323,7 +338,7 @@ __global__ __launch_bounds__(SC_NT) void fecbuf_scatter_kernel(FecBufArgs a)
     }
 
     // straight to the output: getSlotData (blocks 1..127 in place, 16129 dwords) and block 0
-    unsigned *out = reinterpret_cast<unsigned *>(a.data_out + (size_t)s * a.data_stride + (size_t)k * PAYLOAD);
+    unsigned *out = reinterpret_cast<unsigned *>(FB_STREAM_OUT(s) + (size_t)k * PAYLOAD);
     for (int j = t; j < 127 * 127; j += SC_NT) {
         const int b = 1 + j / 127, w = j % 127;
         const int win = s_win[b];
@@ -337,6 +352,8 @@ __global__ __launch_bounds__(SC_NT) void fecbuf_scatter_kernel(FecBufArgs a)
 
 #if FB_PACKED
 __global__ __launch_bounds__(SC_NT) void fecbuf_copy_guarded_kernel(FecBufArgs a)
+#elif FB_ROWS
+__global__ __launch_bounds__(SC_NT) void fecbuf_copy_rows_kernel(FecBufArgs a, const unsigned *row_off)
 #else
 __global__ __launch_bounds__(SC_NT) void fecbuf_copy_kernel(FecBufArgs a)
 #endif
@@ -346,7 +363,7 @@ __global__ __launch_bounds__(SC_NT) void fecbuf_copy_kernel(FecBufArgs a)
 #if FB_PACKED
     if (s < 0 || s >= a.nstreams || k < 0 || k >= a.max_frames) return;
 #endif
-    copy_dwords(reinterpret_cast<unsigned *>(a.data_out + (size_t)s * a.data_stride + (size_t)k * PAYLOAD),
+    copy_dwords(reinterpret_cast<unsigned *>(FB_STREAM_OUT(s) + (size_t)k * PAYLOAD),
                 reinterpret_cast<const unsigned *>(a.dec_out + (size_t)slot * PAYLOAD), 127 * 127);
     if (a.block0_out && threadIdx.x < 127)
         reinterpret_cast<unsigned *>(a.block0_out + ((size_t)s * a.max_frames + k) * 508)[threadIdx.x] =
@@ -354,3 +371,5 @@ __global__ __launch_bounds__(SC_NT) void fecbuf_copy_kernel(FecBufArgs a)
 }
 
 #undef FB_STREAM_DG
+#undef FB_STREAM_OUT
+#undef FB_ROWS

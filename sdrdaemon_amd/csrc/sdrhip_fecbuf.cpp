@@ -27,6 +27,9 @@ struct sdrhip_fecbuf {
     bool shadow_ok = false;      // false: refreshed from the device before the next asynchronous batch (creation, reset, a synchronous call)
     int async_busy = 0;          // the owning Tx handle has asynchronous batches in flight: reset and write_and_read are refused
     DevBuf atab;                 // their tables, counts and public records (fecbuf_packed)
+    // ---- the Rx pipe fed datagrams (sdrhip_rx_process_datagrams): samples each stream holds back between calls (fecbuf_join_carry)
+    DevBuf join_carry;
+    std::vector<size_t> join_carry_host;
 };
 
 namespace {
@@ -47,6 +50,10 @@ int fecbuf_init_state(sdrhip_fecbuf *b)
     }
     b->cur = 0;
     b->shadow_ok = false;
+    if (b->join_carry.p) { // (the remainder rows go with the collector)
+        HIP_TRY(hipMemsetAsync(b->join_carry.p, 0, (size_t)b->nstreams * sizeof(unsigned), b->ctx->stream));
+        b->join_carry_host.assign((size_t)b->nstreams, 0);
+    }
     HIP_TRY(link_copy(b->ctx, b->state[0], st.data(), st.size() * sizeof(FecBufState), hipMemcpyHostToDevice, b->ctx->stream));
     HIP_TRY(hipStreamSynchronize(b->ctx->stream));
     return SDRHIP_OK;
@@ -54,7 +61,7 @@ int fecbuf_init_state(sdrhip_fecbuf *b)
 
 // the device-pointer core: dgrams / data_out / block0_out on the device
 int fecbuf_device(sdrhip_fecbuf *b, const uint8_t *dg, const size_t *n_dgrams, size_t dg_stride, uint8_t *data_out, size_t data_stride,
-                  uint8_t *block0_out, size_t max_frames, sdrhip_fecbuf_frame *info_out, size_t *n_frames)
+                  uint8_t *block0_out, size_t max_frames, sdrhip_fecbuf_frame *info_out, size_t *n_frames, const FecBufJoin *join = nullptr)
 {
     sdrhip_ctx *c = b->ctx;
     const int S = b->nstreams;
@@ -117,6 +124,7 @@ int fecbuf_device(sdrhip_fecbuf *b, const uint8_t *dg, const size_t *n_dgrams, s
     }
     up[2 * S] = njobs;
     if (!room) return fail(SDRHIP_EINVAL, "fecbuf_write_and_read: a stream releases more than max_frames = %zu frames (n_frames has the counts; nothing was consumed)", max_frames);
+    if (join && join->admit && (rc = join->admit(join->arg, n_frames))) return rc;
     // everything that can fail for want of memory before the state moves on
     if (nslots > 0) {
         if ((rc = b->stage.reserve((size_t)nslots * 128 * SDRHIP_UDPSIZE))) return rc;
@@ -135,7 +143,8 @@ int fecbuf_device(sdrhip_fecbuf *b, const uint8_t *dg, const size_t *n_dgrams, s
     b->pin_up.mark(c->stream);
     a.stage = b->stage.as<uint8_t>(); a.dmap = b->dmap.as<int>();
     a.dec_out = b->dec_out.as<uint8_t>(); a.dec_b0 = block0_out ? b->dec_b0.as<uint8_t>() : nullptr;
-    if ((e = launch_fecbuf_scatter(a, njobs, c->stream)) != hipSuccess) return fail(SDRHIP_EDEVICE, "fecbuf scatter launch: %s", hipGetErrorString(e));
+    e = join ? launch_fecbuf_scatter_rows(a, join->row_off, njobs, c->stream) : launch_fecbuf_scatter(a, njobs, c->stream);
+    if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "fecbuf scatter launch: %s", hipGetErrorString(e));
     b->cur ^= 1; // (committed: the scatter pass has written the new carry slots)
     if (nslots > 0) {
         // the promise is the batch's highest collected row, never a count: <= 32 rows (indices 0..31) take the one-launch decoder
@@ -143,7 +152,8 @@ int fecbuf_device(sdrhip_fecbuf *b, const uint8_t *dg, const size_t *n_dgrams, s
         if ((rc = fec_decode_device(c, b->stage.as<uint8_t>(), (size_t)128 * SDRHIP_UDPSIZE, nullptr, (size_t)nslots, b->dec_out.as<uint8_t>(), PAYLOAD,
                                     block0_out ? b->dec_b0.as<uint8_t>() : nullptr, nullptr, nullptr, max_rows)))
             return rc;
-        if ((e = launch_fecbuf_copy(a, nslots, c->stream)) != hipSuccess) return fail(SDRHIP_EDEVICE, "fecbuf copy launch: %s", hipGetErrorString(e));
+        e = join ? launch_fecbuf_copy_rows(a, join->row_off, nslots, c->stream) : launch_fecbuf_copy(a, nslots, c->stream);
+        if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "fecbuf copy launch: %s", hipGetErrorString(e));
     }
     return SDRHIP_OK;
 }
@@ -186,6 +196,7 @@ extern "C" void sdrhip_fecbuf_destroy(sdrhip_fecbuf *b)
         b->hin.release(); b->hout.release(); b->hb0.release();
         b->pin_up.release(); b->pin_down.release(); b->pin_in.release();
         b->atab.release();
+        b->join_carry.release();
     }
     delete b;
     ctx_release(c);
@@ -216,8 +227,9 @@ int check_dgrams(int S, const uint8_t *dgrams, const size_t *n_dgrams, size_t dg
 }
 
 // host memory: the datagrams go up as one 2-D copy (from sdrhip_host_alloc memory in place, else through a pinned buffer) to
-// b->hin, `row` bytes per stream
-int upload_dgrams(sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes, size_t row)
+// b->hin, `row` bytes per stream.  exact (the Rx pipe's join: its link traffic is bounded by the datagrams themselves): streams
+// with fewer datagrams than the longest go up one by one, n_dgrams[s] x 512 bytes each
+int upload_dgrams(sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes, size_t row, bool exact = false)
 {
     sdrhip_ctx *c = b->ctx;
     const int S = b->nstreams;
@@ -231,7 +243,15 @@ int upload_dgrams(sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgram
         for (int s = 0; s < S; ++s) memcpy(b->pin_in.as<uint8_t>() + (size_t)s * row, dgrams + (size_t)s * sstride, n_dgrams[s] * SDRHIP_UDPSIZE);
         src = b->pin_in.as<uint8_t>(); sstride = row;
     }
-    HIP_TRY(link_copy2d(c, b->hin.p, row, src, sstride, row, (size_t)S, hipMemcpyHostToDevice, c->stream));
+    bool ragged = false;
+    for (int s = 0; s < S; ++s) ragged = ragged || n_dgrams[s] * SDRHIP_UDPSIZE != row;
+    if (exact && ragged) {
+        for (int s = 0; s < S; ++s)
+            if (n_dgrams[s])
+                HIP_TRY(link_copy(c, b->hin.as<uint8_t>() + (size_t)s * row, src + (size_t)s * sstride, n_dgrams[s] * SDRHIP_UDPSIZE,
+                                  hipMemcpyHostToDevice, c->stream));
+    } else
+        HIP_TRY(link_copy2d(c, b->hin.p, row, src, sstride, row, (size_t)S, hipMemcpyHostToDevice, c->stream));
     if (src != dgrams) b->pin_in.mark(c->stream);
     return SDRHIP_OK;
 }
@@ -294,21 +314,21 @@ int fecbuf_check_dgrams(const sdrhip_fecbuf *b, const uint8_t *dgrams, const siz
 
 int fecbuf_collect(sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes, int mem, uint8_t *data_out,
                    size_t data_stride_bytes, uint8_t *block0_out, size_t max_frames, sdrhip_fecbuf_frame *info_out, size_t *n_frames,
-                   const int **counts)
+                   const int **counts, const FecBufJoin *join)
 {
     sdrhip_ctx *c = b->ctx;
     const int S = b->nstreams;
     int rc;
     if (mem == SDRHIP_MEM_DEVICE)
-        rc = fecbuf_device(b, dgrams, n_dgrams, dgram_stride_bytes, data_out, data_stride_bytes, block0_out, max_frames, info_out, n_frames);
+        rc = fecbuf_device(b, dgrams, n_dgrams, dgram_stride_bytes, data_out, data_stride_bytes, block0_out, max_frames, info_out, n_frames, join);
     else {
         size_t nmax = 0;
         for (int s = 0; s < S; ++s) nmax = n_dgrams[s] > nmax ? n_dgrams[s] : nmax;
         const size_t row = nmax * SDRHIP_UDPSIZE;
         if (block0_out && max_frames && (rc = b->hb0.reserve((size_t)S * max_frames * SDRHIP_BLOCK_BYTES))) return rc;
-        if ((rc = upload_dgrams(b, dgrams, n_dgrams, dgram_stride_bytes, row))) return rc;
+        if ((rc = upload_dgrams(b, dgrams, n_dgrams, dgram_stride_bytes, row, join != nullptr))) return rc;
         rc = fecbuf_device(b, b->hin.as<uint8_t>(), n_dgrams, row, data_out, data_stride_bytes, block0_out ? b->hb0.as<uint8_t>() : nullptr,
-                           max_frames, info_out, n_frames);
+                           max_frames, info_out, n_frames, join);
         if (!rc && block0_out)
             for (int s = 0; s < S; ++s)
                 if (n_frames[s])
@@ -463,6 +483,19 @@ int fecbuf_packed(sdrhip_fecbuf *b, const uint8_t *dg, const size_t *n_dgrams, c
 }
 
 void fecbuf_set_async_busy(sdrhip_fecbuf *b, bool busy) { b->async_busy = busy ? 1 : 0; }
+
+int fecbuf_join_carry(sdrhip_fecbuf *b, unsigned **dev, std::vector<size_t> **host)
+{
+    if (!b->join_carry.p) {
+        int rc = b->join_carry.reserve((size_t)b->nstreams * sizeof(unsigned));
+        if (rc) return rc;
+        HIP_TRY(hipMemsetAsync(b->join_carry.p, 0, (size_t)b->nstreams * sizeof(unsigned), b->ctx->stream));
+        b->join_carry_host.assign((size_t)b->nstreams, 0);
+    }
+    *dev = b->join_carry.as<unsigned>();
+    *host = &b->join_carry_host;
+    return SDRHIP_OK;
+}
 } // namespace sdrhip
 
 extern "C" int sdrhip_fecbuf_stats(sdrhip_fecbuf *b, int stream, int *cur_nb_blocks, int *cur_nb_recovery, int *min_nb_blocks, int *max_nb_recovery,

@@ -115,9 +115,20 @@ int interpolate_device(sdrhip_interpolators *p, int log2interp, const int16_t *i
 // the bank's call with data_out on the device and dgrams / block0_out in `mem` memory (host: staged; block0_out downloaded on the
 // context's stream, not synchronised); *counts (device) = the per-stream counts [S][FB_COUNTS] the classify pass left (FB_K: frames)
 int fecbuf_check_dgrams(const sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes, int mem, const char *who);
+// join (the Rx pipe fed datagrams): stream s's payloads go row_off[s] samples (device) behind its data_out row; admit is called
+// with the call's release counts behind the read-back, while nothing is committed: what it returns other than SDRHIP_OK refuses
+// the call (nothing consumed)
+struct FecBufJoin {
+    const unsigned *row_off;
+    int (*admit)(void *arg, const size_t *n_frames);
+    void *arg;
+};
 int fecbuf_collect(sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes, int mem, uint8_t *data_out,
                    size_t data_stride_bytes, uint8_t *block0_out, size_t max_frames, sdrhip_fecbuf_frame *info_out, size_t *n_frames,
-                   const int **counts);
+                   const int **counts, const FecBufJoin *join = nullptr);
+// the samples every stream of the collector's owner (an Rx handle) holds back between datagram calls: [nstreams] on the device
+// (KJ keeps it) and the host's copy; created zero on first use, zeroed by sdrhip_fecbuf_reset
+int fecbuf_join_carry(sdrhip_fecbuf *b, unsigned **dev, std::vector<size_t> **host);
 // asynchronous Tx batches (sdrhip_tx_submit_datagrams): the host's shadow of the classification part of a stream's FecBufState
 struct FecBufShadow {
     int head, count, recov, maxrow, dup;

@@ -491,6 +491,14 @@ enum { FB_DECODED = 1, FB_META = 2, FB_REPAIRED = 4, FB_DECODE_ERROR = 8 };
 hipError_t launch_fecbuf_classify(const FecBufArgs &a, hipStream_t stream);
 hipError_t launch_fecbuf_scatter(const FecBufArgs &a, int njobs, hipStream_t stream);
 hipError_t launch_fecbuf_copy(const FecBufArgs &a, int nslots, hipStream_t stream);
+// the Rx pipe fed datagrams (sdrhip_rx_process_datagrams, rx_join_kernels.hip): the scatter and copy passes with stream s's
+// payloads row_off[s] samples (device) behind a.data_out + s * a.data_stride, and KJ, which moves what the decimator left of
+// every stream's row (carry[s] + 16129 x counts[s][FB_K] samples, less their largest multiple of `unit` <= 64) to the row's head
+// and writes the new carry[s]; rows = [nstreams][row_len] samples
+hipError_t launch_fecbuf_scatter_rows(const FecBufArgs &a, const unsigned *row_off, int njobs, hipStream_t stream);
+hipError_t launch_fecbuf_copy_rows(const FecBufArgs &a, const unsigned *row_off, int nslots, hipStream_t stream);
+hipError_t launch_rx_join_carry(int16_t *rows, size_t row_len, unsigned *carry, const int *counts, unsigned unit, int nstreams,
+                                hipStream_t stream);
 // asynchronous Tx batches (sdrhip_tx_submit_datagrams): stream s's datagrams back to back at a.dg + dg_off[s] (device); njobs /
 // nslots come from the host's shadow of the classification; the scatter pass skips what lies past the classify pass's own counts,
 // max_frames or nslots, the guarded copy a slot whose dmap entry is still -1 (preset by the caller)

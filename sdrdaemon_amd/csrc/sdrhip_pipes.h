@@ -152,6 +152,12 @@ struct sdrhip_rx {
     bool view_ragged = false;          // the last call's windows differ between streams: sdrhip_rx_frames_view refuses
     sdrhip::PinnedBuf r_pin, r_flist_pin; // host-row staging and the encoder's frame list
     sdrhip::DevBuf r_flist;
+    // ---- datagram entry (sdrhip_rx_process_datagrams): one SDRdaemonFECBuffer per stream, created on first use; it delivers into
+    // j_rows ([nstreams][j_row_len] samples, the ragged step's input), behind the samples each row holds back from earlier calls
+    // (their counts live with the collector: fecbuf_join_carry)
+    sdrhip_fecbuf *fb = nullptr;
+    sdrhip::DevBuf j_rows;
+    size_t j_row_len = 0;
 };
 
 // --------------------------------------------------------------------------- fused Tx pipe
@@ -229,9 +235,11 @@ inline bool rx_has_batches(const sdrhip_rx *rx, bool ragged)
     return rx->ring.any([ragged](const sdrhip_rx::Batch &b) { return b.ragged == ragged; });
 }
 // the ragged step (sdrhip_rx_process_ragged).  batch: a ragged asynchronous batch (rx_launch_ragged): int16 device rows that K0p
-// laid out, whatever the input format
+// laid out, whatever the input format.  dev_rows: iq_in is int16 device rows whatever `mem` and the input format are (the datagram
+// entry's rows); `mem` then speaks of frames_out alone
 int rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, size_t in_stride, const uint32_t *tv_sec, const uint32_t *tv_usec,
-              uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem, bool batch = false);
+              uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem, bool batch = false, bool dev_rows = false);
+int rx_collector(sdrhip_rx *rx); // the datagram collector, created on first use
 
 // ---- Tx: bytes per output sample, and the row pitch (samples) of the library's own output buffers: 16-byte rows either way
 inline size_t tx_esz(const sdrhip_tx *tx) { return tx->out_fmt == IQF_S8 ? 2 : 4; }

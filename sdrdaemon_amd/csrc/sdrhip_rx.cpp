@@ -1,4 +1,5 @@
-// sdrhip_rx.cpp -- the fused Rx pipe of include/sdrhip.h: life cycle, configuration, the uniform and the ragged step.
+// sdrhip_rx.cpp -- the fused Rx pipe of include/sdrhip.h: life cycle, configuration, the uniform and the ragged step (the
+// datagram-fed call in front of it: sdrhip_rx_datagrams.cpp).
 #include "sdrhip_pipes.h"
 
 using namespace sdrhip;
@@ -150,6 +151,8 @@ extern "C" void sdrhip_rx_destroy(sdrhip_rx *rx)
     if (rx->ev_enc) (void)hipEventDestroy(rx->ev_enc);
     rx->ring.release(true);
     rx->a_pk.release(); rx->a_din.release(); rx->a_tab.release(); rx->a_frames.release();
+    sdrhip_fecbuf_destroy(rx->fb); // (synchronises the stream)
+    rx->j_rows.release();
     delete rx;
 }
 
@@ -549,7 +552,7 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
 // own window -> one encoder launch over the list of every stream's completed frames.  A call that fails after it moved windows
 // leaves r_base moved (the open frames lie there now) and the rest of the framing state untouched.
 int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, size_t in_stride, const uint32_t *tv_sec, const uint32_t *tv_usec,
-                      uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem, bool batch)
+                      uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem, bool batch, bool dev_rows)
 {
     sdrhip_ctx *c = rx->ctx;
     const int S = rx->nstreams, L = rx->cfg.log2decim, R = rx->cfg.nb_fec;
@@ -565,8 +568,9 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
     if (S == 1) in_stride = max_in;
     if (S > 1 && in_stride < max_in) return fail(SDRHIP_EINVAL, "rx_process_ragged: in_stride smaller than the largest count");
     if (max_in && !iq_in) return fail(SDRHIP_EINVAL, "rx_process_ragged: NULL input");
-    const bool wide8 = rx->in_fmt != IQF_S16 && !batch;
-    if (max_in && mem == SDRHIP_MEM_DEVICE && (!aligned16(iq_in) || (S > 1 && (in_stride & (wide8 ? 7 : 3)))))
+    const bool wide8 = rx->in_fmt != IQF_S16 && !batch && !dev_rows;
+    const bool in_dev = mem == SDRHIP_MEM_DEVICE || dev_rows;
+    if (max_in && in_dev && (!aligned16(iq_in) || (S > 1 && (in_stride & (wide8 ? 7 : 3)))))
         return fail(SDRHIP_EALIGN, "rx_process_ragged: device input must be 16-byte aligned, its stride a multiple of %d samples", wide8 ? 8 : 4);
     std::vector<size_t> done((size_t)S);
     std::vector<uint64_t> rest((size_t)S);
@@ -659,7 +663,7 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
     const int16_t *din = iq_in;
     size_t dstride = in_stride;
     const void *src = iq_in;
-    if (mem == SDRHIP_MEM_HOST) {
+    if (!in_dev) {
         dstride = wide8 ? (max_in + 7) & ~(size_t)7 : (max_in + 3) & ~(size_t)3;
         if ((rc = ragged_stage_in(c, rx->r_pin, c->in, iq_in, in_stride, n_in, S, wide8 ? 2 : 4, dstride, &src))) return rc;
         din = static_cast<const int16_t *>(src);
@@ -725,7 +729,10 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
     for (int s = 1; s < S; ++s) same_base = same_base && rx->r_base[(size_t)s] == rx->r_base[0];
     if (frames_out && max_done) {
         const hipMemcpyKind kind = mem == SDRHIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-        if (same_base) {
+        // (the datagram entry's host callers get each stream's own frames and no more: its link traffic is datagrams up, frames down)
+        bool same_done = true;
+        for (int s = 1; s < S; ++s) same_done = same_done && done[(size_t)s] == done[0];
+        if (same_base && (same_done || !(dev_rows && mem == SDRHIP_MEM_HOST))) {
             HIP_TRY(link_copy2d(c, frames_out, S > 1 ? frame_stride_bytes : max_done * frame_bytes, area + rx->r_base[0] * frame_bytes, stream_bytes,
                                 max_done * frame_bytes, S, kind, c->stream));
         } else {

@@ -1,0 +1,147 @@
+// sdrhip_rx_datagrams.cpp -- the Rx pipe fed raw FEC datagrams (sdrhip_rx_process_datagrams): sdrdaemontx's receive half chained
+// to sdrdaemonrx's send half for every stream.  UDPSourceFEC::read -> SDRdaemonFECBuffer::writeAndRead (sdrdaemontx.cpp:449-498)
+// collects and repairs what an undecimated radio head sent; the released payloads go behind the samples the stream held back,
+// the largest multiple of the decimation unit goes through Downsampler::process -> UDPSinkFEC::write (sdrdaemonrx.cpp:619-644)
+// as ONE ragged step (rx_ragged), and KJ (rx_join_kernels.hip) moves every stream's new remainder to the head of its row.  The
+// samples between collector and decimator stay on the device.
+#include "sdrhip_pipes.h"
+
+using namespace sdrhip;
+
+namespace {
+// samples a call feeds the decimator in one piece: 2^log2decim, but 4 for decimate2_inf / _sup, which walk their input in fours
+// (Decimators.cpp:48,76) -- this entry never hands them a tail of 2
+size_t join_unit(const sdrhip_rx_config &cfg)
+{
+    return cfg.log2decim == 1 && cfg.fcpos != SDRHIP_FC_CEN ? 4 : (size_t)1 << cfg.log2decim;
+}
+
+// what the ragged step would refuse, asked while the collector has not moved: the counts it will get from these releases
+struct Admit {
+    const sdrhip_rx *rx;
+    const std::vector<size_t> *carry;
+    const uint8_t *frames_out;
+    size_t frame_stride_bytes;
+    int mem;
+};
+int admit(void *arg, const size_t *n_released)
+{
+    const Admit &a = *static_cast<const Admit *>(arg);
+    const sdrhip_rx *rx = a.rx;
+    const size_t U = join_unit(rx->cfg), frame_bytes = (size_t)(SDRHIP_NB_ORIGINAL + rx->cfg.nb_fec) * SDRHIP_UDPSIZE;
+    size_t max_done = 0;
+    for (int s = 0; s < rx->nstreams; ++s) {
+        const size_t fed = ((*a.carry)[(size_t)s] + n_released[s] * SDRHIP_SAMPLES_PER_FRAME) / U * U;
+        const size_t done = (size_t)((rx->r_pending[(size_t)s] + (fed >> rx->cfg.log2decim)) / SDRHIP_SAMPLES_PER_FRAME);
+        if (done > max_done) max_done = done;
+    }
+    if (max_done && !a.frames_out && a.mem != SDRHIP_MEM_DEVICE) return fail(SDRHIP_EINVAL, "rx_process_datagrams: NULL frames_out");
+    if (a.frames_out && rx->nstreams > 1 && max_done && a.frame_stride_bytes < max_done * frame_bytes)
+        return fail(SDRHIP_EINVAL, "rx_process_datagrams: frame stride too small for the stream with the most frames (%zu; nothing was consumed)", max_done);
+    return SDRHIP_OK;
+}
+} // namespace
+
+int sdrhip::rx_collector(sdrhip_rx *rx)
+{
+    return rx->fb ? SDRHIP_OK : sdrhip_fecbuf_create(rx->ctx, rx->nstreams, &rx->fb);
+}
+
+extern "C" int sdrhip_rx_collector(sdrhip_rx *rx, sdrhip_fecbuf **out)
+{
+    if (!rx || !out) return fail(SDRHIP_EINVAL, "rx_collector: NULL argument");
+    sdrhip::CtxLock lock_(rx->ctx);
+    int rc = rx_collector(rx);
+    if (rc) return rc;
+    *out = rx->fb;
+    return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_rx_carry(const sdrhip_rx *rx, size_t *carry)
+{
+    if (!rx || !carry) return fail(SDRHIP_EINVAL, "rx_carry: NULL argument");
+    sdrhip::CtxLock lock_(rx->ctx);
+    unsigned *dev = nullptr;
+    std::vector<size_t> *host = nullptr;
+    if (rx->fb) {
+        HIP_TRY(hipSetDevice(rx->ctx->device));
+        int rc = fecbuf_join_carry(rx->fb, &dev, &host);
+        if (rc) return rc;
+    }
+    for (int s = 0; s < rx->nstreams; ++s) carry[s] = host ? (*host)[(size_t)s] : 0;
+    return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_rx_process_datagrams(sdrhip_rx *rx, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes,
+                                           const uint32_t *tv_sec, const uint32_t *tv_usec, size_t max_released, uint8_t *frames_out,
+                                           size_t frame_stride_bytes, sdrhip_fecbuf_frame *info_out, size_t *n_released, size_t *n_frames,
+                                           int mem)
+{
+    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
+    if (!n_dgrams || !tv_sec || !tv_usec || !n_released || !n_frames)
+        return fail(SDRHIP_EINVAL, "rx_process_datagrams: NULL count, stamp, n_released or n_frames array");
+    sdrhip::CtxLock lock_(rx->ctx);
+    sdrhip_ctx *c = rx->ctx;
+    const int S = rx->nstreams;
+    for (int s = 0; s < S; ++s) n_released[s] = n_frames[s] = 0;
+    // ---- everything that can be refused is checked before the collector moves
+    if (int e = check_mem(mem)) return e;
+    if (rx->pipelined) return fail(SDRHIP_EINVAL, "rx_process_datagrams: not available in pipelined mode");
+    if (rx->ring.busy()) return fail(SDRHIP_EINVAL, "rx_process_datagrams: asynchronous batches are being filled or in flight: collect them first");
+    if (max_released > 0x3fffffffu) return fail(SDRHIP_EINVAL, "rx_process_datagrams: max_released too large");
+    if (max_released > 0 && !info_out) return fail(SDRHIP_EINVAL, "rx_process_datagrams: NULL info_out");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = rx_collector(rx))) return rc;
+    if ((rc = fecbuf_check_dgrams(rx->fb, dgrams, n_dgrams, dgram_stride_bytes, mem, "rx_process_datagrams"))) return rc;
+    unsigned *carry_dev = nullptr;
+    std::vector<size_t> *carry = nullptr;
+    if ((rc = fecbuf_join_carry(rx->fb, &carry_dev, &carry))) return rc;
+    // ---- the rows: 63 samples held back at the most, max_released payloads behind them; rows that grow keep their heads
+    if (max_released > 0) {
+        const size_t row_len = (63 + max_released * SDRHIP_SAMPLES_PER_FRAME + 3) & ~(size_t)3;
+        if (row_len > rx->j_row_len) {
+            DevBuf bigger;
+            if ((rc = bigger.reserve((size_t)S * row_len * 4))) return rc;
+            hipError_t e = hipSuccess;
+            if (rx->j_rows.p)
+                e = hipMemcpy2DAsync(bigger.p, row_len * 4, rx->j_rows.p, rx->j_row_len * 4, 64 * 4, (size_t)S, hipMemcpyDeviceToDevice, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // (earlier launches may still use the old rows)
+            if (e != hipSuccess) {
+                (void)hipStreamSynchronize(c->stream);
+                bigger.release();
+                return fail(SDRHIP_EDEVICE, "rx_process_datagrams: moving the rows: %s", hipGetErrorString(e));
+            }
+            rx->j_rows.release();
+            rx->j_rows = bigger;
+            rx->j_row_len = row_len;
+        }
+    }
+    const size_t U = join_unit(rx->cfg);
+    Admit ad = {rx, carry, frames_out, frame_stride_bytes, mem};
+    const FecBufJoin join = {carry_dev, admit, &ad};
+    const int *counts = nullptr;
+    if ((rc = fecbuf_collect(rx->fb, dgrams, n_dgrams, dgram_stride_bytes, mem, max_released ? rx->j_rows.as<uint8_t>() : nullptr,
+                             rx->j_row_len * 4, nullptr, max_released, info_out, n_released, &counts, &join)))
+        return rc; // (SDRHIP_EINVAL: nothing consumed, nothing has run behind the classify pass)
+    // ---- the collector's state has moved on: from here a failure loses the call's samples, it is never replayed
+    std::vector<size_t> fed((size_t)S), left((size_t)S);
+    bool any = false;
+    for (int s = 0; s < S; ++s) {
+        const size_t total = (*carry)[(size_t)s] + n_released[s] * SDRHIP_SAMPLES_PER_FRAME;
+        fed[(size_t)s] = total / U * U;
+        left[(size_t)s] = total - fed[(size_t)s];
+        any = any || fed[(size_t)s] != 0;
+    }
+    if (!any) { // (nothing released, and no row holds a whole unit: rows and remainders stay)
+        rx->view_frames = 0; rx->view_ragged = false;
+        return SDRHIP_OK;
+    }
+    if ((rc = rx_ragged(rx, rx->j_rows.as<int16_t>(), fed.data(), rx->j_row_len, tv_sec, tv_usec, frames_out, frame_stride_bytes, n_frames, mem,
+                        false, true)))
+        return rc;
+    hipError_t e = launch_rx_join_carry(rx->j_rows.as<int16_t>(), rx->j_row_len, carry_dev, counts, (unsigned)U, S, c->stream);
+    if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "rx join launch: %s", hipGetErrorString(e));
+    *carry = left;
+    return SDRHIP_OK;
+}

@@ -863,6 +863,61 @@ class RxPipe:
                                                     MEM_DEVICE))
         return self.frames_view_ragged(x.device), np.array(nf[:], dtype=np.int64)
 
+    # ---- datagram entry (sdrhip_rx_process_datagrams)
+    def process_datagrams(self, dgrams_per_stream, tv_sec=0, tv_usec=0, max_released=None):
+        """one (n_s, 512) uint8 array of raw FEC datagrams per stream -- numpy (host memory) or torch device tensors, as
+        TxPipe.process_datagrams -- through the handle's collector, the remainder rows, the decimators, the framer and the
+        encoder; tv_sec / tv_usec (scalars or one per stream) stamp the first sample each stream feeds its decimator.  -> per
+        stream (frames (n, 128 + nb_fec, 512) uint8, records of the frames the collector released).  A stream that would release
+        more than max_released (default: room for anything the datagrams can release) raises SdrHipError, nothing consumed;
+        last_n_released has the counts."""
+        S = self.nstreams
+        if len(dgrams_per_stream) != S:
+            raise ValueError("one datagram array per stream")
+        buf, counts, is_t = _datagram_batch(dgrams_per_stream)
+        if max_released is None:
+            max_released = max(counts + [0])  # (a call releases at most one frame per datagram)
+        F = max(max_released, 1)
+        cap = max(self.max_frames(SAMPLES_PER_FRAME * max_released + 63), 1)
+        rows, fb = NB_ORIGINAL + self.nb_fec, (NB_ORIGINAL + self.nb_fec) * UDPSIZE
+        out = (torch.empty((S, cap, rows, UDPSIZE), dtype=torch.uint8, device=buf.device) if is_t
+               else np.empty((S, cap, rows, UDPSIZE), np.uint8))
+        sec = np.broadcast_to(np.asarray(tv_sec, dtype=np.uint32), (S,))
+        usec = np.broadcast_to(np.asarray(tv_usec, dtype=np.uint32), (S,))
+        info = (FECBufferFrame * (S * F))()
+        nd = (C.c_size_t * S)(*counts)
+        nr, nf = (C.c_size_t * S)(), (C.c_size_t * S)()
+        rc = self.ctx.lib.sdrhip_rx_process_datagrams(self.h, _ptr(buf), nd, buf.shape[1] * UDPSIZE, (C.c_uint32 * S)(*[int(v) for v in sec]),
+                                                      (C.c_uint32 * S)(*[int(v) for v in usec]), max_released, _ptr(out), cap * fb, info, nr, nf,
+                                                      MEM_DEVICE if is_t else MEM_HOST)
+        self.last_n_released = [int(x) for x in nr]
+        check(rc)
+        res = []
+        for s in range(S):
+            recs = [dict(frame_index=info[s * F + j].frame_index, block_count=info[s * F + j].block_count,
+                         recovery_count=info[s * F + j].recovery_count, flags=info[s * F + j].flags) for j in range(int(nr[s]))]
+            res.append((out[s, :int(nf[s])], recs))
+        return res
+
+    def collector_stats(self, stream):
+        """the statistics of one stream's collector (sdrhip_rx_collector + sdrhip_fecbuf_stats): the dict of FECBufferBank.stats"""
+        return _fecbuf_stats(self.ctx, self._collector(), stream)
+
+    def reset_collector(self):
+        """sdrhip_fecbuf_reset on the handle's collector: the constructor's state, and every stream's carry cleared"""
+        check(self.ctx.lib.sdrhip_fecbuf_reset(self._collector()))
+
+    def _collector(self):
+        h = C.c_void_p()
+        check(self.ctx.lib.sdrhip_rx_collector(self.h, C.byref(h)))
+        return h
+
+    def carry(self):
+        """samples each stream holds back between process_datagrams calls (sdrhip_rx_carry): numpy (S,)"""
+        c = (C.c_size_t * self.nstreams)()
+        check(self.ctx.lib.sdrhip_rx_carry(self.h, c))
+        return np.array(c[:], dtype=np.int64)
+
     def close(self):
         if self.h:
             self.ctx.lib.sdrhip_rx_destroy(self.h)
