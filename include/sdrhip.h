@@ -101,7 +101,8 @@ int sdrhip_ctx_set_option(sdrhip_ctx *ctx, const char *key, const char *value);
  * "dec_rows_exceeded" = frames, since the context was created, that the batched decoder (sdrhip_fec_decode_frames,
  * sdrhip_tx_process) left unrepaired because they carried more recovery blocks than the dec_max_rows option allows (kept on the
  * device: reading it synchronises the context's stream);
- * "fecbuf_shadow_mismatch" = streams of asynchronous datagram batches (sdrhip_tx_submit_datagrams) whose collector counts on the
+ * "fecbuf_shadow_mismatch" = streams of asynchronous datagram batches of either pipe (sdrhip_tx_submit_datagrams,
+ * sdrhip_rx_submit_datagrams) whose collector counts on the
  * device disagreed with the host's shadow that sized the batch's grids; 0 unless the library is broken (on the device, as above);
  * "h2d_bytes" / "d2h_bytes" = bytes that the context's entry points have copied from host to device / device to host since the
  * context was created (staging copies of host-memory calls, including the kernels' direct reads of pinned staging memory for
@@ -586,6 +587,43 @@ int sdrhip_rx_process_datagrams(sdrhip_rx *rx, const uint8_t *dgrams, const size
 int sdrhip_rx_collector(sdrhip_rx *rx, sdrhip_fecbuf **out);
 /* carry: host array of nstreams entries, the samples each stream holds back (0 .. 63) */
 int sdrhip_rx_carry(const sdrhip_rx *rx, size_t *carry);
+/* Asynchronous datagram batches, the datagram twin of sdrhip_rx_submit_ragged / sdrhip_rx_collect_ragged and the Rx twin of
+ * sdrhip_tx_submit_datagrams: a hub's reader thread keeps receiving while its main loop works (sdrdaemontx.cpp:449-498), and
+ * UDPSinkFEC::write returns at once (UDPSinkFEC.cpp:193-211).  sdrhip_rx_submit_datagrams takes ONE batch from host memory:
+ * stream s gives n_dgrams[s] datagrams of 512 bytes (counts may differ and may be 0) at dgrams + s * dgram_stride_bytes, or, with
+ * dgram_stride_bytes = SDRHIP_PACKED, back to back (stream s at dgrams + 512 * sum_{t<s} n_dgrams[t]); tv_sec[s] / tv_usec[s]
+ * (host arrays) stamp the first sample stream s feeds its decimator in this batch.  The datagrams are staged into pinned memory
+ * (the buffer is the caller's again on return) or, when they lie in sdrhip_host_alloc memory, uploaded in place (leave them
+ * untouched until the batch is collected).  The call enqueues upload, collection, decode, the join behind the carry, the ragged
+ * decimate / frame / encode step at the configuration in force, the delivery and ONE download, and returns with NO
+ * synchronisation: every count comes from the host's shadow of the classification (the first batch after the handle's collector
+ * was created, reset or fed by sdrhip_rx_process_datagrams reads its state back once; rows or frame areas that grow synchronise
+ * once; every pinned table of a batch belongs to its ring slot, so a submit waits for no earlier batch).  A batch means exactly one sdrhip_rx_process_datagrams call with the same datagrams and stamps: frames, recovery blocks,
+ * meta blocks, frameIndex, records, and the collector state, carry, filter histories, open frames and counters left behind are
+ * byte for byte those of that sequence of synchronous calls; synchronous calls before and after a run of batches continue the same
+ * streams, and sdrhip_rx_carry / sdrhip_fecbuf_stats report the state after every batch submitted so far.
+ * sdrhip_rx_collect_datagrams returns the OLDEST batch: stream s's n_frames[s] frames of (128 + nb_fec) x 512 bytes at
+ * frames_out + s * frame_stride_bytes and its n_released[s] records at info_out[s * max_released + k] (both counts: host arrays
+ * of nstreams entries).  SDRHIP_OK: one batch collected, possibly with no frames.  SDRHIP_EBUSY: none was -- nothing submitted,
+ * or (wait = 0) the oldest batch is still in flight; wait = 1 blocks outside the context lock.  A stream with more than max_frames
+ * frames or more than max_released records, or a frame stride below the stream with the most frames: SDRHIP_EINVAL with both
+ * count arrays filled in, the batch stays (call again with room).  The ring depth is sdrhip_rx_set_async's (default 4; its
+ * `blocks` does not apply: one submit is one batch); a full ring makes the submit return SDRHIP_EBUSY with nothing consumed.
+ * One kind of batch at a time: the datagram submit is refused (SDRHIP_EINVAL, nothing consumed) in pipelined mode, while uniform
+ * or ragged batches are being filled or in flight, for NULL count or stamp arrays and for a stride that is neither SDRHIP_PACKED
+ * nor at least the largest count x 512.  While datagram batches are in flight, SDRHIP_EINVAL with nothing consumed from
+ * sdrhip_rx_submit[_ragged], sdrhip_rx_collect[_ragged], sdrhip_rx_process[_ragged], sdrhip_rx_process_datagrams,
+ * sdrhip_rx_set_input_format, sdrhip_rx_set_async, sdrhip_rx_set_pipelined(1), and sdrhip_fecbuf_reset /
+ * sdrhip_fecbuf_write_and_read on the handle's collector.  sdrhip_rx_reconfigure is allowed at any time and applies to later
+ * submits: batches in flight keep the configuration (and frame size) they were submitted with; a fecblk change waits for them to
+ * finish on the device (they are still collected as usual).  A submit that fails before the collector's scatter launch consumes
+ * nothing, and everything the batch needs is allocated before that launch (but the decimator's stream-order rows, should a
+ * matrix-core launch the sizes counted on not apply); one that fails behind it loses the batch (never replayed).  Link traffic ("h2d_bytes" / "d2h_bytes"): up exactly
+ * sum n_dgrams x 512, down exactly sum n_frames x (128 + nb_fec) x 512 + sum n_released x 16 in one copy. */
+int sdrhip_rx_submit_datagrams(sdrhip_rx *rx, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes,
+                               const uint32_t *tv_sec, const uint32_t *tv_usec);
+int sdrhip_rx_collect_datagrams(sdrhip_rx *rx, uint8_t *frames_out, size_t frame_stride_bytes, size_t max_frames,
+                                size_t max_released, sdrhip_fecbuf_frame *info_out, size_t *n_released, size_t *n_frames, int wait);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,9 @@
 // With FB_ROWS 1 (and FB_PACKED 0) by rx_join_kernels.hip: the scatter and copy passes alone, for the Rx pipe fed datagrams
 // (sdrhip_rx_process_datagrams): stream s's payloads go row_off[s] samples behind a.data_out + s * a.data_stride, behind the
 // samples the stream's row holds back from earlier calls.
+// With FB_PACKED 1 and FB_ROWS 1 by rx_dgram_async_kernels.hip: the scatter and the guarded copy pass of asynchronous datagram-fed Rx
+// batches (sdrhip_rx_submit_datagrams): packed datagrams in, payloads behind row_off[s]; on top of the packed guards a frame whose
+// payload would end past the stream's row (a.data_stride bytes) is skipped.
 #ifndef FB_ROWS
 #define FB_ROWS 0
 #endif
@@ -66,6 +69,9 @@ __device__ __forceinline__ void copy_dwords(unsigned *dst, const unsigned *src, 
 #define FB_STREAM_OUT(s) (a.data_out + (size_t)(s) * a.data_stride + (size_t)row_off[s] * 4)
 #else
 #define FB_STREAM_OUT(s) (a.data_out + (size_t)(s) * a.data_stride)
+#endif
+#if FB_PACKED && FB_ROWS
+#define FB_PAST_ROW(s, k) ((size_t)row_off[s] * 4 + (size_t)((k) + 1) * PAYLOAD > a.data_stride)
 #endif
 
 #if !FB_ROWS
@@ -266,7 +272,9 @@ __global__ __launch_bounds__(CL_NT) void fecbuf_classify_kernel(FecBufArgs a)
 }
 #endif // !FB_ROWS
 
-#if FB_PACKED
+#if FB_PACKED && FB_ROWS
+__global__ __launch_bounds__(SC_NT) void fecbuf_scatter_packed_rows_kernel(FecBufArgs a, const long long *dg_off, int nslots, const unsigned *row_off)
+#elif FB_PACKED
 __global__ __launch_bounds__(SC_NT) void fecbuf_scatter_packed_kernel(FecBufArgs a, const long long *dg_off, int nslots)
 #elif FB_ROWS
 __global__ __launch_bounds__(SC_NT) void fecbuf_scatter_rows_kernel(FecBufArgs a, const unsigned *row_off)
@@ -338,6 +346,9 @@ __global__ __launch_bounds__(SC_NT) void fecbuf_scatter_kernel(FecBufArgs a)
     }
 
     // straight to the output: getSlotData (blocks 1..127 in place, 16129 dwords) and block 0
+#if FB_PACKED && FB_ROWS
+    if (FB_PAST_ROW(s, k)) return;
+#endif
     unsigned *out = reinterpret_cast<unsigned *>(FB_STREAM_OUT(s) + (size_t)k * PAYLOAD);
     for (int j = t; j < 127 * 127; j += SC_NT) {
         const int b = 1 + j / 127, w = j % 127;
@@ -350,7 +361,9 @@ __global__ __launch_bounds__(SC_NT) void fecbuf_scatter_kernel(FecBufArgs a)
     }
 }
 
-#if FB_PACKED
+#if FB_PACKED && FB_ROWS
+__global__ __launch_bounds__(SC_NT) void fecbuf_copy_guarded_rows_kernel(FecBufArgs a, const unsigned *row_off)
+#elif FB_PACKED
 __global__ __launch_bounds__(SC_NT) void fecbuf_copy_guarded_kernel(FecBufArgs a)
 #elif FB_ROWS
 __global__ __launch_bounds__(SC_NT) void fecbuf_copy_rows_kernel(FecBufArgs a, const unsigned *row_off)
@@ -363,6 +376,9 @@ __global__ __launch_bounds__(SC_NT) void fecbuf_copy_kernel(FecBufArgs a)
 #if FB_PACKED
     if (s < 0 || s >= a.nstreams || k < 0 || k >= a.max_frames) return;
 #endif
+#if FB_PACKED && FB_ROWS
+    if (FB_PAST_ROW(s, k)) return;
+#endif
     copy_dwords(reinterpret_cast<unsigned *>(FB_STREAM_OUT(s) + (size_t)k * PAYLOAD),
                 reinterpret_cast<const unsigned *>(a.dec_out + (size_t)slot * PAYLOAD), 127 * 127);
     if (a.block0_out && threadIdx.x < 127)
@@ -372,4 +388,5 @@ __global__ __launch_bounds__(SC_NT) void fecbuf_copy_kernel(FecBufArgs a)
 
 #undef FB_STREAM_DG
 #undef FB_STREAM_OUT
+#undef FB_PAST_ROW
 #undef FB_ROWS

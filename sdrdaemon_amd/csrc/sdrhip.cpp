@@ -637,7 +637,8 @@ extern "C" int sdrhip_decimate(sdrhip_decimators *d, int log2decim, int fcpos, u
 
 // ------------------------------------------------------------------------------ ragged decimator calls
 namespace sdrhip {
-int ragged_prepare(sdrhip_decimators *d, int log2decim, int fcpos, const size_t *n_in, RaggedRow *rows, const RaggedRow **rows_dev)
+int ragged_prepare(sdrhip_decimators *d, int log2decim, int fcpos, const size_t *n_in, RaggedRow *rows, const RaggedRow **rows_dev,
+                   PinnedBuf *pin)
 {
     sdrhip_ctx *c = d->ctx;
     const int S = d->nstreams;
@@ -676,13 +677,21 @@ int ragged_prepare(sdrhip_decimators *d, int log2decim, int fcpos, const size_t 
     }
     const size_t bytes = (size_t)S * sizeof(RaggedRow);
     int rc;
-    if ((rc = d->rows_pin.reserve(bytes))) return rc; // (waits for the upload of the previous table)
+    PinnedBuf &tab = pin ? *pin : d->rows_pin;
+    if ((rc = tab.reserve(bytes))) return rc; // (waits for the last upload from this staging: the previous table's, or the ring slot's)
     if ((rc = d->rows_dev.reserve(bytes))) return rc;
-    memcpy(d->rows_pin.p, rows, bytes);
-    HIP_TRY(hipMemcpyAsync(d->rows_dev.p, d->rows_pin.p, bytes, hipMemcpyHostToDevice, c->stream));
-    d->rows_pin.mark(c->stream);
+    memcpy(tab.p, rows, bytes);
+    HIP_TRY(hipMemcpyAsync(d->rows_dev.p, tab.p, bytes, hipMemcpyHostToDevice, c->stream));
+    tab.mark(c->stream);
     *rows_dev = d->rows_dev.as<RaggedRow>();
     return SDRHIP_OK;
+}
+
+int ragged_reserve(sdrhip_decimators *d, PinnedBuf *pin)
+{
+    const size_t bytes = (size_t)d->nstreams * sizeof(RaggedRow);
+    if (int rc = (pin ? *pin : d->rows_pin).reserve(bytes)) return rc;
+    return d->rows_dev.reserve(bytes);
 }
 
 bool ragged_mfma_planned(const sdrhip_decimators *d) { return d->r_mfma; }

@@ -25,7 +25,7 @@ struct sdrhip_fecbuf {
     // ---- asynchronous Tx batches (sdrhip_tx_submit_datagrams): the host's shadow of the classification part of state[cur]
     std::vector<FecBufShadow> shadow;
     bool shadow_ok = false;      // false: refreshed from the device before the next asynchronous batch (creation, reset, a synchronous call)
-    int async_busy = 0;          // the owning Tx handle has asynchronous batches in flight: reset and write_and_read are refused
+    int async_busy = 0;          // the owning Tx / Rx handle has asynchronous datagram batches in flight: reset and write_and_read are refused
     DevBuf atab;                 // their tables, counts and public records (fecbuf_packed)
     // ---- the Rx pipe fed datagrams (sdrhip_rx_process_datagrams): samples each stream holds back between calls (fecbuf_join_carry)
     DevBuf join_carry;
@@ -206,7 +206,7 @@ extern "C" int sdrhip_fecbuf_reset(sdrhip_fecbuf *b)
 {
     if (!b) return fail(SDRHIP_EINVAL, "fecbuf is NULL");
     sdrhip::CtxLock lock_(b->ctx);
-    if (b->async_busy) return fail(SDRHIP_EINVAL, "fecbuf_reset: the Tx handle's asynchronous datagram batches are in flight: collect them first");
+    if (b->async_busy) return fail(SDRHIP_EINVAL, "fecbuf_reset: the owning pipe's asynchronous datagram batches are in flight: collect them first");
     HIP_TRY(hipSetDevice(b->ctx->device));
     return fecbuf_init_state(b);
 }
@@ -266,7 +266,7 @@ extern "C" int sdrhip_fecbuf_write_and_read(sdrhip_fecbuf *b, const uint8_t *dgr
     sdrhip::CtxLock lock_(c);
     const int S = b->nstreams;
     if (!n_dgrams || !n_frames) return fail(SDRHIP_EINVAL, "fecbuf_write_and_read: NULL n_dgrams / n_frames");
-    if (b->async_busy) return fail(SDRHIP_EINVAL, "fecbuf_write_and_read: the Tx handle's asynchronous datagram batches are in flight: collect them first");
+    if (b->async_busy) return fail(SDRHIP_EINVAL, "fecbuf_write_and_read: the owning pipe's asynchronous datagram batches are in flight: collect them first");
     size_t nmax = 0;
     int rc;
     if ((rc = check_dgrams(S, dgrams, n_dgrams, dgram_stride_bytes, mem, "fecbuf_write_and_read", &nmax))) return rc;
@@ -401,7 +401,7 @@ void fecbuf_shadow_run(FecBufShadow &h, const uint8_t *dg, size_t n, int res[4])
 
 int fecbuf_packed(sdrhip_fecbuf *b, const uint8_t *dg, const size_t *n_dgrams, const int *res, const std::vector<FecBufShadow> &next,
                   PinnedBuf &tab, uint8_t *data_out, size_t data_stride, uint8_t *block0_out, size_t max_frames, unsigned *mismatch,
-                  bool *committed, const int **counts, const FecBufPub **pub)
+                  bool *committed, const int **counts, const FecBufPub **pub, const FecBufJoin *join)
 {
     sdrhip_ctx *c = b->ctx;
     const int S = b->nstreams;
@@ -464,7 +464,9 @@ int fecbuf_packed(sdrhip_fecbuf *b, const uint8_t *dg, const size_t *n_dgrams, c
     if ((e = launch_fecbuf_shadow_check(a.counts, reinterpret_cast<const int *>(t) + 3 * S + 1, S, mismatch, c->stream)) != hipSuccess)
         return fail(SDRHIP_EDEVICE, "fecbuf shadow check launch: %s", hipGetErrorString(e));
     if (nslots > 0) HIP_TRY(hipMemsetAsync(a.dmap, 0xff, (size_t)nslots * 2 * sizeof(int), c->stream)); // (the guarded copy skips what stays -1)
-    if ((e = launch_fecbuf_scatter_packed(a, dg_off, njobs, nslots, c->stream)) != hipSuccess)
+    e = join ? launch_fecbuf_scatter_packed_rows(a, dg_off, join->row_off, njobs, nslots, c->stream)
+             : launch_fecbuf_scatter_packed(a, dg_off, njobs, nslots, c->stream);
+    if (e != hipSuccess)
         return fail(SDRHIP_EDEVICE, "fecbuf scatter launch: %s", hipGetErrorString(e));
     b->cur ^= 1; // (committed: the scatter pass has written the new carry slots)
     b->shadow = next;
@@ -475,7 +477,8 @@ int fecbuf_packed(sdrhip_fecbuf *b, const uint8_t *dg, const size_t *n_dgrams, c
         if ((rc = fec_decode_device(c, b->stage.as<uint8_t>(), (size_t)128 * SDRHIP_UDPSIZE, nullptr, (size_t)nslots, b->dec_out.as<uint8_t>(), PAYLOAD,
                                     block0_out ? b->dec_b0.as<uint8_t>() : nullptr, nullptr, nullptr, max_rows)))
             return rc;
-        if ((e = launch_fecbuf_copy_guarded(a, nslots, c->stream)) != hipSuccess) return fail(SDRHIP_EDEVICE, "fecbuf copy launch: %s", hipGetErrorString(e));
+        e = join ? launch_fecbuf_copy_guarded_rows(a, join->row_off, nslots, c->stream) : launch_fecbuf_copy_guarded(a, nslots, c->stream);
+        if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "fecbuf copy launch: %s", hipGetErrorString(e));
     }
     *counts = a.counts;
     *pub = a.pub;

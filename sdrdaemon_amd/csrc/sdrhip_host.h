@@ -82,7 +82,11 @@ int decimate_device(sdrhip_decimators *d, int log2decim, int fcpos, unsigned *sa
 // ragged calls (sdrhip_decimate_ragged, sdrhip_rx_process_ragged): ragged_prepare fills the decimator fields of rows[0..S) (the
 // caller's framing fields are kept), plans K1r and uploads the table (the decimators' own device copy, valid until the next ragged
 // call on them); decimate_ragged_device then runs the cascade with it
-int ragged_prepare(sdrhip_decimators *d, int log2decim, int fcpos, const size_t *n_in, RaggedRow *rows, const RaggedRow **rows_dev);
+// pin (optional): the caller's own pinned staging for the table instead of the handle's one -- an asynchronous batch passes its
+// ring slot's, so that the call waits for that slot's last upload, not for the previous call's
+int ragged_prepare(sdrhip_decimators *d, int log2decim, int fcpos, const size_t *n_in, RaggedRow *rows, const RaggedRow **rows_dev,
+                   PinnedBuf *pin = nullptr);
+int ragged_reserve(sdrhip_decimators *d, PinnedBuf *pin); // the table's storage alone: nothing left to allocate in ragged_prepare
 // frame_mode != 0 (only when ragged_mfma_planned): the matrix-core launch stores straight into the frame layout, `out` = the frame
 // area (stream s at out + s * out_stride dwords, its window at RaggedRow out_off), meta_w / meta_rate = the shared meta words
 int decimate_ragged_device(sdrhip_decimators *d, int log2decim, int fcpos, unsigned *sampleSize, const int16_t *in, size_t in_stride,
@@ -129,7 +133,8 @@ int fecbuf_collect(sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgra
 // the samples every stream of the collector's owner (an Rx handle) holds back between datagram calls: [nstreams] on the device
 // (KJ keeps it) and the host's copy; created zero on first use, zeroed by sdrhip_fecbuf_reset
 int fecbuf_join_carry(sdrhip_fecbuf *b, unsigned **dev, std::vector<size_t> **host);
-// asynchronous Tx batches (sdrhip_tx_submit_datagrams): the host's shadow of the classification part of a stream's FecBufState
+// asynchronous Tx / Rx batches (sdrhip_tx_submit_datagrams, sdrhip_rx_submit_datagrams): the host's shadow of the classification part
+// of a stream's FecBufState
 struct FecBufShadow {
     int head, count, recov, maxrow, dup;
     unsigned pres[4];
@@ -144,10 +149,12 @@ void fecbuf_shadow_run(FecBufShadow &h, const uint8_t *dg, size_t n, int res[4])
 // grids and decoder bound from res ([S][4], fecbuf_shadow_run); tab = the batch's pinned table buffer; data_out / block0_out on
 // the device, max_frames >= every res[s][0]; +1 on *mismatch (device) per stream whose classify pass disagrees with res.
 // *committed: the state has moved on (to `next`; a failure after it loses the batch); *counts / *pub = the pass's counts
-// [S][FB_COUNTS] and public records [S][max_frames] on the device (valid until the next batch)
+// [S][FB_COUNTS] and public records [S][max_frames] on the device (valid until the next batch).  join (asynchronous Rx batches):
+// stream s's payloads go join->row_off[s] samples (device) behind its data_out row, never past the row's data_stride bytes (admit
+// is not used: nothing is read back)
 int fecbuf_packed(sdrhip_fecbuf *b, const uint8_t *dg, const size_t *n_dgrams, const int *res, const std::vector<FecBufShadow> &next,
                   PinnedBuf &tab, uint8_t *data_out, size_t data_stride, uint8_t *block0_out, size_t max_frames, unsigned *mismatch,
-                  bool *committed, const int **counts, const FecBufPub **pub);
+                  bool *committed, const int **counts, const FecBufPub **pub, const FecBufJoin *join = nullptr);
 // DevBuf::reserve behind a synchronisation of the context's stream when the buffer grows (it frees the old one, which batches in
 // flight may still use)
 inline int reserve_settled(sdrhip_ctx *c, DevBuf &b, size_t n);

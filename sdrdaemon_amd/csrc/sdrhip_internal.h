@@ -505,6 +505,23 @@ hipError_t launch_rx_join_carry(int16_t *rows, size_t row_len, unsigned *carry, 
 hipError_t launch_fecbuf_classify_packed(const FecBufArgs &a, const long long *dg_off, hipStream_t stream);
 hipError_t launch_fecbuf_scatter_packed(const FecBufArgs &a, const long long *dg_off, int njobs, int nslots, hipStream_t stream);
 hipError_t launch_fecbuf_copy_guarded(const FecBufArgs &a, int nslots, hipStream_t stream);
+// asynchronous Rx batches (sdrhip_rx_submit_datagrams, rx_dgram_async_kernels.hip): the packed scatter and guarded copy passes with
+// stream s's payloads row_off[s] samples (device) behind a.data_out + s * a.data_stride; on top of the packed guards they skip a
+// frame whose payload would end past the stream's row (a.data_stride bytes)
+hipError_t launch_fecbuf_scatter_packed_rows(const FecBufArgs &a, const long long *dg_off, const unsigned *row_off, int njobs, int nslots,
+                                             hipStream_t stream);
+hipError_t launch_fecbuf_copy_guarded_rows(const FecBufArgs &a, const unsigned *row_off, int nslots, hipStream_t stream);
+// their delivery, KD: segment i = bytes from (from_records ? records : frames) + src to out + dst; src, dst and bytes are multiples
+// of 16, the three bases 16-byte aligned
+struct RxDeliverSeg {
+    uint64_t src, dst, bytes;
+    uint32_t wg0, from_records; // first workgroup (rx_deliver_plan)
+};
+constexpr uint64_t RX_DELIVER_WG_BYTES = 16384; // bytes per workgroup (256 lanes x 4 chunks of 16 bytes)
+// fills every segment's wg0, returns the grid (0: an empty or misaligned segment, one of 32 GiB or more, or more than 2^31 workgroups)
+uint32_t rx_deliver_plan(RxDeliverSeg *segs, int nseg);
+hipError_t launch_rx_deliver(const RxDeliverSeg *segs, int nseg, uint32_t grid, const uint8_t *frames, const uint8_t *records, uint8_t *out,
+                             hipStream_t stream);
 // counts [S][FB_COUNTS] against the shadow's expect [S][4] = {K, D, maxrow, maxrec}: +1 on *mismatch per
 // stream that differs
 hipError_t launch_fecbuf_shadow_check(const int *counts, const int *expect, int nstreams, unsigned *mismatch, hipStream_t stream);

@@ -1,5 +1,6 @@
 // sdrhip_pipes.h -- the fused Rx / Tx pipes of include/sdrhip.h: their handles, the ring of asynchronous batches and what the
-// units sdrhip_rx.cpp, sdrhip_rx_async.cpp, sdrhip_tx.cpp and sdrhip_tx_async.cpp share
+// units sdrhip_rx.cpp, sdrhip_rx_async.cpp, sdrhip_rx_datagrams.cpp, sdrhip_rx_datagrams_async.cpp, sdrhip_tx.cpp and
+// sdrhip_tx_async.cpp share
 #pragma once
 #include "sdrhip_host.h"
 
@@ -69,6 +70,11 @@ template <class B> struct BatchRing {
 } // namespace sdrhip
 
 // --------------------------------------------------------------------------- fused Rx pipe
+namespace sdrhip {
+// pinned staging of the ragged step's two host tables (the decimator's rows, the encoder's frame list).  The handle owns one pair,
+// whose reuse waits for the previous call's upload; a datagram batch brings its ring slot's pair (rx_ragged's `tabs`)
+struct RxTabs { PinnedBuf rows, flist; };
+} // namespace sdrhip
 struct sdrhip_rx {
     sdrhip_ctx *ctx;
     int nstreams;
@@ -133,15 +139,26 @@ struct sdrhip_rx {
         size_t r_used = 0;                    // staged bytes in `in`
         std::vector<size_t> r_frames;         // frames per stream of the launched batch, in stream order in `out`
         sdrhip::PinnedBuf r_tab;              // K0p's table, then the frame list of the download
+        // ---- a batch of raw datagrams (sdrhip_rx_submit_datagrams; the third kind, never being filled: one submit is one batch):
+        // `in` holds them packed, r_tab the collector's tables, d_seg the delivery's segments, `out` the gathered delivery (every
+        // stream's r_frames[s] frames, then every stream's d_rel[s] records)
+        // d_tabs = the ragged step's row table and frame list, per slot: a submit waits for its own slot's last use, never for
+        // the previous batch
+        bool dg = false;
+        sdrhip::PinnedBuf d_seg;
+        sdrhip::RxTabs d_tabs;
+        std::vector<size_t> d_rel;            // released frames (records) per stream
         void release()
         {
             if (done) (void)hipEventDestroy(done);
             done = nullptr;
-            in.release(); din.release(); out.release(); r_tab.release();
+            in.release(); din.release(); out.release(); r_tab.release(); d_seg.release(); d_tabs.rows.release(); d_tabs.flist.release();
         }
     };
     sdrhip::BatchRing<Batch> ring;
-    sdrhip::DevBuf a_pk, a_din, a_tab, a_frames; // ragged batches on the device: packed upload, K0p's rows, tables, compacted frames
+    // ragged batches on the device: packed upload, K0p's rows, tables, compacted frames (datagram batches: the packed datagrams in
+    // a_pk, the delivery's segments in a_tab, the gathered delivery in a_frames)
+    sdrhip::DevBuf a_pk, a_din, a_tab, a_frames;
     int a_blocks = 1;             // blocks per launch
     bool consumed = false;        // set by sdrhip_rx_process once the decimator launch of the call went out (the filter state advanced)
     // ---- input format (sdrhip_rx_set_input_format): 8-bit input is widened by K0 into `wide`, the decimator's int16 input
@@ -232,13 +249,32 @@ inline bool rx_aligned(const sdrhip_rx *rx)
 // batches of the ring that are being filled or in flight, of the ragged (or the uniform) kind
 inline bool rx_has_batches(const sdrhip_rx *rx, bool ragged)
 {
-    return rx->ring.any([ragged](const sdrhip_rx::Batch &b) { return b.ragged == ragged; });
+    return rx->ring.any([ragged](const sdrhip_rx::Batch &b) { return !b.dg && b.ragged == ragged; });
 }
+// ... of the datagram kind (sdrhip_rx_submit_datagrams): every other entry that moves the pipe is refused meanwhile
+inline bool rx_dgrams_in_flight(const sdrhip_rx *rx)
+{
+    return rx->ring.any([](const sdrhip_rx::Batch &b) { return b.dg; });
+}
+// samples a datagram call feeds the decimator in one piece: 2^log2decim, but 4 for decimate2_inf / _sup, which walk their input in
+// fours (Decimators.cpp:48,76) -- the datagram entries never hand them a tail of 2
+inline size_t rx_join_unit(const sdrhip_rx_config &cfg)
+{
+    return cfg.log2decim == 1 && cfg.fcpos != SDRHIP_FC_CEN ? 4 : (size_t)1 << cfg.log2decim;
+}
+// the datagram entries' rows (j_rows): room for 63 samples held back and max_released payloads behind them.  Rows that grow keep
+// their heads and grow behind a synchronisation (earlier launches may still use the old rows)
+int rx_join_rows(sdrhip_rx *rx, size_t max_released, const char *who);
 // the ragged step (sdrhip_rx_process_ragged).  batch: a ragged asynchronous batch (rx_launch_ragged): int16 device rows that K0p
 // laid out, whatever the input format.  dev_rows: iq_in is int16 device rows whatever `mem` and the input format are (the datagram
 // entry's rows); `mem` then speaks of frames_out alone
 int rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, size_t in_stride, const uint32_t *tv_sec, const uint32_t *tv_usec,
-              uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem, bool batch = false, bool dev_rows = false);
+              uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem, bool batch = false, bool dev_rows = false,
+              RxTabs *tabs = nullptr);
+// everything the ragged step allocates for these counts, ahead of it (a caller that must not fail between two launches): the frame
+// area (grown behind a synchronisation), the tables, the frame list, and the stream-order rows when the decimator cannot store
+// straight into the windows.  rx_ragged itself then allocates nothing, unless a matrix-core plan it counted on does not apply
+int rx_ragged_room(sdrhip_rx *rx, const size_t *n_in, RxTabs *tabs);
 int rx_collector(sdrhip_rx *rx); // the datagram collector, created on first use
 
 // ---- Tx: bytes per output sample, and the row pitch (samples) of the library's own output buffers: 16-byte rows either way

@@ -60,6 +60,7 @@ extern "C" int sdrhip_rx_set_pipelined(sdrhip_rx *rx, int on)
     if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
     sdrhip::CtxLock lock_(rx->ctx);
     if (!on && rx->late.have) return fail(SDRHIP_EINVAL, "rx_set_pipelined: sdrhip_rx_flush the waiting frames first");
+    if (on && rx_dgrams_in_flight(rx)) return fail(SDRHIP_EINVAL, "rx_set_pipelined: asynchronous datagram batches are in flight: collect them first");
     if (on && !rx_aligned(rx)) return fail(SDRHIP_EINVAL, "rx_set_pipelined: ragged calls left the streams at different frame positions");
     rx->pipelined = on ? 1 : 0;
     return SDRHIP_OK;
@@ -292,6 +293,7 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
     sdrhip::CtxLock lock_(rx->ctx);
     if (n_frames) *n_frames = 0;
     if (rx_has_batches(rx, true)) return fail(SDRHIP_EINVAL, "rx_process: ragged batches are being filled or in flight: collect them first");
+    if (rx_dgrams_in_flight(rx)) return fail(SDRHIP_EINVAL, "rx_process: asynchronous datagram batches are in flight: collect them first");
     if (n_in && !rx_aligned(rx)) {
         // ragged calls left the streams at different frame positions: a ragged call with equal counts and stamps; *n_frames = the
         // largest per-stream count (sdrhip_rx_frames_view_ragged has each)
@@ -548,11 +550,70 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
 }
 
 // --------------------------------------------------------------------------- ragged Rx calls
+// a new frame area of more slots per stream (a ragged call needs more than the area has): every open frame moves to its slot 0
+static int rx_grow_area(sdrhip_rx *rx, size_t need_max)
+{
+    sdrhip_ctx *c = rx->ctx;
+    const int S = rx->nstreams;
+    const size_t frame_bytes = ((size_t)SDRHIP_NB_ORIGINAL + (size_t)rx->cfg.nb_fec) * SDRHIP_UDPSIZE;
+    const size_t wmul = c->opt.rx_window ? (size_t)c->opt.rx_window : 2;
+    const size_t ncap = wmul * need_max;
+    DevBuf bigger;
+    if (int rc = bigger.reserve((size_t)S * ncap * frame_bytes)) return rc;
+    // (the old area and every window stay as they were until the copies have completed: a failure leaves the handle untouched)
+    hipError_t e = hipSuccess;
+    for (int s = 0; s < S && e == hipSuccess; ++s)
+        if (rx->r_open[(size_t)s])
+            e = hipMemcpyAsync(bigger.as<uint8_t>() + (size_t)s * ncap * frame_bytes,
+                               rx->work.as<uint8_t>() + ((size_t)s * rx->cap_frames + rx->r_base[(size_t)s]) * frame_bytes, frame_bytes,
+                               hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // earlier launches may still use the old area
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);
+        bigger.release();
+        return fail(SDRHIP_EDEVICE, "rx_process_ragged: moving the open frames: %s", hipGetErrorString(e));
+    }
+    for (int s = 0; s < S; ++s) rx->r_base[(size_t)s] = 0;
+    rx->work.release();
+    rx->work = bigger;
+    rx->cap_frames = ncap;
+    return SDRHIP_OK;
+}
+
+int sdrhip::rx_ragged_room(sdrhip_rx *rx, const size_t *n_in, RxTabs *tabs)
+{
+    const int S = rx->nstreams, L = rx->cfg.log2decim;
+    size_t need_max = 0, sum_done = 0, max_dec = 0;
+    for (int s = 0; s < S; ++s) {
+        const size_t n_dec = n_in[s] >> L, done = (size_t)((rx->r_pending[(size_t)s] + n_dec) / SDRHIP_SAMPLES_PER_FRAME);
+        need_max = done + 1 > need_max ? done + 1 : need_max;
+        max_dec = n_dec > max_dec ? n_dec : max_dec;
+        sum_done += done;
+    }
+    int rc;
+    // (the view of the last call's frames does not outlive the area it points into)
+    if (need_max > rx->cap_frames) {
+        if ((rc = rx_grow_area(rx, need_max))) return rc;
+        rx->view_frames = 0; rx->view_ragged = false;
+        rx->r_view_frames.assign((size_t)S, 0);
+    }
+    if ((rc = ragged_reserve(rx->dec, tabs ? &tabs->rows : nullptr))) return rc;
+    // (only the matrix-core launch of a centred decimation by 4 or more stores straight into the windows)
+    const bool may_direct = rx->cfg.fcpos == SDRHIP_FC_CEN && L >= 2 && rx->ctx->opt.rx_direct;
+    if (!may_direct && (rc = rx->lin[0].reserve((size_t)S * ((max_dec + 3) & ~(size_t)3) * 4 + 16))) return rc;
+    if (sum_done && rx->cfg.nb_fec > 0) {
+        const size_t nl = (sum_done + GF_FRAMES_PER_GROUP - 1) / GF_FRAMES_PER_GROUP * GF_FRAMES_PER_GROUP;
+        if ((rc = (tabs ? tabs->flist : rx->r_flist_pin).reserve(nl * 4))) return rc;
+        if ((rc = rx->r_flist.reserve(nl * 4))) return rc;
+    }
+    return SDRHIP_OK;
+}
+
 // Every stream takes its own count: K0r (8-bit input) -> K1r / filter-less kernel into stream order -> K2r into each stream's
 // own window -> one encoder launch over the list of every stream's completed frames.  A call that fails after it moved windows
 // leaves r_base moved (the open frames lie there now) and the rest of the framing state untouched.
 int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, size_t in_stride, const uint32_t *tv_sec, const uint32_t *tv_usec,
-                      uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem, bool batch, bool dev_rows)
+                      uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem, bool batch, bool dev_rows, RxTabs *tabs)
 {
     sdrhip_ctx *c = rx->ctx;
     const int S = rx->nstreams, L = rx->cfg.log2decim, R = rx->cfg.nb_fec;
@@ -604,27 +665,7 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
         rx->old_work.release();
     }
     if (need_max > rx->cap_frames) {
-        const size_t wmul = c->opt.rx_window ? (size_t)c->opt.rx_window : 2;
-        const size_t ncap = wmul * need_max;
-        DevBuf bigger;
-        if ((rc = bigger.reserve((size_t)S * ncap * frame_bytes))) return rc;
-        // (the old area and every window stay as they were until the copies have completed: a failure leaves the handle untouched)
-        hipError_t e = hipSuccess;
-        for (int s = 0; s < S && e == hipSuccess; ++s)
-            if (rx->r_open[(size_t)s])
-                e = hipMemcpyAsync(bigger.as<uint8_t>() + (size_t)s * ncap * frame_bytes,
-                                   rx->work.as<uint8_t>() + ((size_t)s * rx->cap_frames + rx->r_base[(size_t)s]) * frame_bytes, frame_bytes,
-                                   hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // earlier launches may still use the old area
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(c->stream);
-            bigger.release();
-            return fail(SDRHIP_EDEVICE, "rx_process_ragged: moving the open frames: %s", hipGetErrorString(e));
-        }
-        for (int s = 0; s < S; ++s) rx->r_base[(size_t)s] = 0;
-        rx->work.release();
-        rx->work = bigger;
-        rx->cap_frames = ncap;
+        if ((rc = rx_grow_area(rx, need_max))) return rc;
     } else {
         for (int s = 0; s < S; ++s) {
             if (rx->r_base[(size_t)s] + done[(size_t)s] + 1 <= rx->cap_frames) continue;
@@ -657,7 +698,7 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
         }
     }
     const RaggedRow *rdev = nullptr;
-    if ((rc = ragged_prepare(rx->dec, L, rx->cfg.fcpos, n_in, rows.data(), &rdev))) return rc;
+    if ((rc = ragged_prepare(rx->dec, L, rx->cfg.fcpos, n_in, rows.data(), &rdev, tabs ? &tabs->rows : nullptr))) return rc;
 
     // ---- input: host rows staged stream by stream (n_in[s] samples each), 8-bit rows widened by K0r
     const int16_t *din = iq_in;
@@ -710,15 +751,16 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
     // ---- FEC: one launch over the completed frames of every stream (a dense list: frame f of stream s = area frame s * cap + slot)
     if (sum_done && R > 0) {
         const size_t nl = (sum_done + GF_FRAMES_PER_GROUP - 1) / GF_FRAMES_PER_GROUP * GF_FRAMES_PER_GROUP;
-        if ((rc = rx->r_flist_pin.reserve(nl * 4))) return rc;
+        PinnedBuf &fpin = tabs ? tabs->flist : rx->r_flist_pin;
+        if ((rc = fpin.reserve(nl * 4))) return rc;
         if ((rc = rx->r_flist.reserve(nl * 4))) return rc;
-        int32_t *fl = rx->r_flist_pin.as<int32_t>();
+        int32_t *fl = fpin.as<int32_t>();
         size_t k = 0;
         for (int s = 0; s < S; ++s)
             for (size_t f = 0; f < done[(size_t)s]; ++f) fl[k++] = (int32_t)((size_t)s * rx->cap_frames + rx->r_base[(size_t)s] + f);
         while (k < nl) fl[k++] = -1;
         HIP_TRY(hipMemcpyAsync(rx->r_flist.p, fl, nl * 4, hipMemcpyHostToDevice, c->stream));
-        rx->r_flist_pin.mark(c->stream);
+        fpin.mark(c->stream);
         if ((rc = fec_encode_device(c, area, frame_bytes, (size_t)S * rx->cap_frames, R, area + (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE,
                                     frame_bytes, rx->r_flist.as<int32_t>(), (int)(nl / GF_FRAMES_PER_GROUP))))
             return rc;

@@ -206,6 +206,7 @@ extern "C" int sdrhip_rx_submit(sdrhip_rx *rx, const int16_t *iq_in, size_t n_in
     sdrhip::CtxLock lock_(rx->ctx);
     if (n_in == 0) return SDRHIP_OK;
     if (!iq_in) return fail(SDRHIP_EINVAL, "rx_submit: NULL input");
+    if (rx_dgrams_in_flight(rx)) return fail(SDRHIP_EINVAL, "rx_submit: asynchronous datagram batches are in flight: sdrhip_rx_collect_datagrams them first");
     if (!rx_aligned(rx)) return fail(SDRHIP_EINVAL, "rx_submit: ragged calls left the streams at different frame positions");
     if (rx_has_batches(rx, true)) return fail(SDRHIP_EINVAL, "rx_submit: ragged batches are being filled or in flight: collect them first");
     HIP_TRY(hipSetDevice(rx->ctx->device));
@@ -265,6 +266,7 @@ extern "C" int sdrhip_rx_collect(sdrhip_rx *rx, uint8_t *frames_out, size_t fram
     if (!rx || !n_frames) return fail(SDRHIP_EINVAL, "rx_collect: NULL argument");
     std::unique_lock<std::recursive_mutex> lock_(rx->ctx->mtx);
     *n_frames = 0;
+    if (rx_dgrams_in_flight(rx)) return fail(SDRHIP_EINVAL, "rx_collect: asynchronous datagram batches are in flight: sdrhip_rx_collect_datagrams them first");
     if (rx_has_batches(rx, true)) return fail(SDRHIP_EINVAL, "rx_collect: ragged batches are being filled or in flight: use sdrhip_rx_collect_ragged");
     HIP_TRY(hipSetDevice(rx->ctx->device));
     sdrhip_rx::Batch *bp = nullptr;
@@ -302,6 +304,7 @@ extern "C" int sdrhip_rx_submit_ragged(sdrhip_rx *rx, const int16_t *iq_in, cons
         return fail(SDRHIP_EINVAL, "rx_submit_ragged: in_stride is neither SDRHIP_PACKED nor at least the largest count");
     if (sum && !iq_in) return fail(SDRHIP_EINVAL, "rx_submit_ragged: NULL input");
     if (rx->pipelined) return fail(SDRHIP_EINVAL, "rx_submit_ragged: not available in pipelined mode");
+    if (rx_dgrams_in_flight(rx)) return fail(SDRHIP_EINVAL, "rx_submit_ragged: asynchronous datagram batches are in flight: sdrhip_rx_collect_datagrams them first");
     if (rx_has_batches(rx, false)) return fail(SDRHIP_EINVAL, "rx_submit_ragged: uniform batches are being filled or in flight: collect them first");
     sdrhip_rx::Batch &b = rx->ring.tail_batch();
     if (b.state == 2) return fail(SDRHIP_EBUSY, "rx_submit_ragged: every batch of the ring is in flight: sdrhip_rx_collect_ragged first");
@@ -365,6 +368,7 @@ extern "C" int sdrhip_rx_collect_ragged(sdrhip_rx *rx, uint8_t *frames_out, size
     std::unique_lock<std::recursive_mutex> lock_(rx->ctx->mtx);
     const int S = rx->nstreams;
     for (int s = 0; s < S; ++s) n_frames[s] = 0;
+    if (rx_dgrams_in_flight(rx)) return fail(SDRHIP_EINVAL, "rx_collect_ragged: asynchronous datagram batches are in flight: use sdrhip_rx_collect_datagrams");
     if (rx_has_batches(rx, false)) return fail(SDRHIP_EINVAL, "rx_collect_ragged: uniform batches are being filled or in flight: use sdrhip_rx_collect");
     HIP_TRY(hipSetDevice(rx->ctx->device));
     sdrhip_rx::Batch *bp = nullptr;

@@ -9,13 +9,6 @@
 using namespace sdrhip;
 
 namespace {
-// samples a call feeds the decimator in one piece: 2^log2decim, but 4 for decimate2_inf / _sup, which walk their input in fours
-// (Decimators.cpp:48,76) -- this entry never hands them a tail of 2
-size_t join_unit(const sdrhip_rx_config &cfg)
-{
-    return cfg.log2decim == 1 && cfg.fcpos != SDRHIP_FC_CEN ? 4 : (size_t)1 << cfg.log2decim;
-}
-
 // what the ragged step would refuse, asked while the collector has not moved: the counts it will get from these releases
 struct Admit {
     const sdrhip_rx *rx;
@@ -28,7 +21,7 @@ int admit(void *arg, const size_t *n_released)
 {
     const Admit &a = *static_cast<const Admit *>(arg);
     const sdrhip_rx *rx = a.rx;
-    const size_t U = join_unit(rx->cfg), frame_bytes = (size_t)(SDRHIP_NB_ORIGINAL + rx->cfg.nb_fec) * SDRHIP_UDPSIZE;
+    const size_t U = rx_join_unit(rx->cfg), frame_bytes = (size_t)(SDRHIP_NB_ORIGINAL + rx->cfg.nb_fec) * SDRHIP_UDPSIZE;
     size_t max_done = 0;
     for (int s = 0; s < rx->nstreams; ++s) {
         const size_t fed = ((*a.carry)[(size_t)s] + n_released[s] * SDRHIP_SAMPLES_PER_FRAME) / U * U;
@@ -45,6 +38,30 @@ int admit(void *arg, const size_t *n_released)
 int sdrhip::rx_collector(sdrhip_rx *rx)
 {
     return rx->fb ? SDRHIP_OK : sdrhip_fecbuf_create(rx->ctx, rx->nstreams, &rx->fb);
+}
+
+int sdrhip::rx_join_rows(sdrhip_rx *rx, size_t max_released, const char *who)
+{
+    sdrhip_ctx *c = rx->ctx;
+    const int S = rx->nstreams;
+    const size_t row_len = (63 + max_released * SDRHIP_SAMPLES_PER_FRAME + 3) & ~(size_t)3;
+    if (row_len <= rx->j_row_len) return SDRHIP_OK;
+    DevBuf bigger;
+    int rc;
+    if ((rc = bigger.reserve((size_t)S * row_len * 4))) return rc;
+    hipError_t e = hipSuccess;
+    if (rx->j_rows.p)
+        e = hipMemcpy2DAsync(bigger.p, row_len * 4, rx->j_rows.p, rx->j_row_len * 4, 64 * 4, (size_t)S, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // (earlier launches may still use the old rows)
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);
+        bigger.release();
+        return fail(SDRHIP_EDEVICE, "%s: moving the rows: %s", who, hipGetErrorString(e));
+    }
+    rx->j_rows.release();
+    rx->j_rows = bigger;
+    rx->j_row_len = row_len;
+    return SDRHIP_OK;
 }
 
 extern "C" int sdrhip_rx_collector(sdrhip_rx *rx, sdrhip_fecbuf **out)
@@ -97,27 +114,8 @@ extern "C" int sdrhip_rx_process_datagrams(sdrhip_rx *rx, const uint8_t *dgrams,
     unsigned *carry_dev = nullptr;
     std::vector<size_t> *carry = nullptr;
     if ((rc = fecbuf_join_carry(rx->fb, &carry_dev, &carry))) return rc;
-    // ---- the rows: 63 samples held back at the most, max_released payloads behind them; rows that grow keep their heads
-    if (max_released > 0) {
-        const size_t row_len = (63 + max_released * SDRHIP_SAMPLES_PER_FRAME + 3) & ~(size_t)3;
-        if (row_len > rx->j_row_len) {
-            DevBuf bigger;
-            if ((rc = bigger.reserve((size_t)S * row_len * 4))) return rc;
-            hipError_t e = hipSuccess;
-            if (rx->j_rows.p)
-                e = hipMemcpy2DAsync(bigger.p, row_len * 4, rx->j_rows.p, rx->j_row_len * 4, 64 * 4, (size_t)S, hipMemcpyDeviceToDevice, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // (earlier launches may still use the old rows)
-            if (e != hipSuccess) {
-                (void)hipStreamSynchronize(c->stream);
-                bigger.release();
-                return fail(SDRHIP_EDEVICE, "rx_process_datagrams: moving the rows: %s", hipGetErrorString(e));
-            }
-            rx->j_rows.release();
-            rx->j_rows = bigger;
-            rx->j_row_len = row_len;
-        }
-    }
-    const size_t U = join_unit(rx->cfg);
+    if (max_released > 0 && (rc = rx_join_rows(rx, max_released, "rx_process_datagrams"))) return rc;
+    const size_t U = rx_join_unit(rx->cfg);
     Admit ad = {rx, carry, frames_out, frame_stride_bytes, mem};
     const FecBufJoin join = {carry_dev, admit, &ad};
     const int *counts = nullptr;

@@ -1,0 +1,237 @@
+// sdrhip_rx_datagrams_async.cpp -- asynchronous batches of the Rx pipe fed raw FEC datagrams (sdrhip_rx_submit_datagrams /
+// sdrhip_rx_collect_datagrams).  A hub's reader thread receives while its main loop works (sdrdaemontx.cpp:449-498) and
+// UDPSinkFEC::write returns at once (UDPSinkFEC.cpp:193-211); sdrhip_rx_process_datagrams synchronises for the collector's
+// read-back and again at its end.  A batch goes out with no synchronisation: its datagrams up packed (one memcpy per stream into
+// the batch's pinned arena, or in place from sdrhip_host_alloc memory), the collector's passes with grids from the host's shadow
+// of the classification (fecbuf_packed with the join: packed datagrams in, payloads behind each row's carry), the decoder, ONE
+// ragged decimate / frame / encode step (rx_ragged) with counts the host derives from the shadow's release counts and its copy of
+// the carry, KJ, the delivery KD (frames, then records: one launch), ONE download of exactly the delivered bytes.  The collector, the
+// rows, the carry, the histories and the framing state are the ones sdrhip_rx_process_datagrams uses.
+#include "sdrhip_pipes.h"
+
+using namespace sdrhip;
+
+namespace {
+constexpr size_t DG_REC = sizeof(sdrhip_fecbuf_frame);
+static_assert(sizeof(sdrhip_fecbuf_frame) == sizeof(FecBufPub), "public record layout");
+// a failure behind the collector's scatter launch: the batch is consumed and lost, never replayed
+int rx_batch_lost(int rc)
+{
+    const std::string m = sdrhip_last_error();
+    return fail(rc, "rx_submit_datagrams: %s (the batch is lost)", m.c_str());
+}
+} // namespace
+
+extern "C" int sdrhip_rx_submit_datagrams(sdrhip_rx *rx, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes,
+                                          const uint32_t *tv_sec, const uint32_t *tv_usec)
+{
+    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
+    if (!n_dgrams || !tv_sec || !tv_usec) return fail(SDRHIP_EINVAL, "rx_submit_datagrams: NULL count or stamp array");
+    sdrhip::CtxLock lock_(rx->ctx);
+    // ---- everything that can be refused is checked before anything is consumed
+    const int S = rx->nstreams, L = rx->cfg.log2decim;
+    size_t sum = 0, nmax = 0;
+    for (int s = 0; s < S; ++s) {
+        if (n_dgrams[s] > 0x3fffffffu) return fail(SDRHIP_EINVAL, "rx_submit_datagrams: too many datagrams in one batch");
+        sum += n_dgrams[s];
+        nmax = n_dgrams[s] > nmax ? n_dgrams[s] : nmax;
+    }
+    const bool packed = dgram_stride_bytes == SDRHIP_PACKED || S == 1;
+    if (sum && !dgrams) return fail(SDRHIP_EINVAL, "rx_submit_datagrams: NULL dgrams");
+    if (!packed && dgram_stride_bytes < nmax * SDRHIP_UDPSIZE)
+        return fail(SDRHIP_EINVAL, "rx_submit_datagrams: dgram_stride_bytes is neither SDRHIP_PACKED nor at least the largest count x 512");
+    if (rx->pipelined) return fail(SDRHIP_EINVAL, "rx_submit_datagrams: not available in pipelined mode");
+    if (rx_has_batches(rx, false) || rx_has_batches(rx, true))
+        return fail(SDRHIP_EINVAL, "rx_submit_datagrams: uniform or ragged batches are being filled or in flight: collect them first");
+    sdrhip_rx::Batch &b = rx->ring.tail_batch();
+    if (b.state == 2) return fail(SDRHIP_EBUSY, "rx_submit_datagrams: every batch of the ring is in flight: sdrhip_rx_collect_datagrams first");
+    sdrhip_ctx *c = rx->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = rx_collector(rx))) return rc;
+    unsigned *carry_dev = nullptr;
+    std::vector<size_t> *carry = nullptr;
+    if ((rc = fecbuf_join_carry(rx->fb, &carry_dev, &carry))) return rc;
+    std::vector<FecBufShadow> sh;
+    if ((rc = fecbuf_shadow(rx->fb, &sh))) return rc;
+
+    // ---- staging: packed, one memcpy per non-empty stream (in place: the caller's pinned memory); the shadow runs over the headers
+    const size_t bytes_in = sum * SDRHIP_UDPSIZE;
+    auto row_of = [&](int s, size_t off) { return packed ? dgrams + off : dgrams + (size_t)s * dgram_stride_bytes; };
+    const bool inplace = sum && (packed ? host_is_pinned(dgrams, bytes_in) : host_is_pinned(dgrams, (size_t)(S - 1) * dgram_stride_bytes + nmax * SDRHIP_UDPSIZE));
+    if (sum && !inplace && (rc = b.in.reserve(bytes_in))) return rc; // (waits for the upload of this slot's last batch)
+    std::vector<int> res((size_t)S * 4);
+    {
+        size_t off = 0;
+        for (int s = 0; s < S; ++s) {
+            const size_t nb = n_dgrams[s] * SDRHIP_UDPSIZE;
+            const uint8_t *src = row_of(s, off);
+            if (nb && !inplace) {
+                memcpy(b.in.as<uint8_t>() + off, src, nb);
+                src = b.in.as<uint8_t>() + off;
+            }
+            fecbuf_shadow_run(sh[(size_t)s], src, n_dgrams[s], &res[(size_t)s * 4]);
+            off += nb;
+        }
+    }
+    // ---- every count of the batch, from the shadow's release counts and the host's copy of the carry: what each stream feeds its
+    // decimator, what it holds back, the frames it completes (as rx_ragged counts them)
+    const size_t U = rx_join_unit(rx->cfg), fb = (size_t)(SDRHIP_NB_ORIGINAL + rx->cfg.nb_fec) * SDRHIP_UDPSIZE;
+    std::vector<size_t> fed((size_t)S), left((size_t)S), nf((size_t)S, 0);
+    size_t kmax = 0, kall = 0, sum_done = 0;
+    bool any = false;
+    for (int s = 0; s < S; ++s) {
+        const size_t k = (size_t)res[(size_t)s * 4];
+        kmax = k > kmax ? k : kmax;
+        kall += k;
+        const size_t total = (*carry)[(size_t)s] + k * SDRHIP_SAMPLES_PER_FRAME;
+        fed[(size_t)s] = total / U * U;
+        left[(size_t)s] = total - fed[(size_t)s];
+        any = any || fed[(size_t)s] != 0;
+        sum_done += (size_t)((rx->r_pending[(size_t)s] + (fed[(size_t)s] >> L)) / SDRHIP_SAMPLES_PER_FRAME);
+    }
+    const size_t b_frames = sum_done * fb, b_total = b_frames + kall * DG_REC;
+    const size_t seg_bytes = (size_t)2 * S * sizeof(RxDeliverSeg);
+    // everything that can fail for want of memory comes before the collector moves (a device buffer that grows waits for the
+    // batches in flight; the rows keep their heads): the batch's own buffers, then what the ragged step takes for these counts
+    // (rx_ragged_room: frame area, tables, frame list; it names the one allocation it cannot foresee).  The pinned tables are the ring slot's own, so that what a submit waits
+    // for is this slot's previous batch -- which the caller has collected -- and never the batch before it
+    if (sum && (rc = reserve_settled(c, rx->a_pk, bytes_in + 16))) return rc;
+    if (kmax && (rc = rx_join_rows(rx, kmax, "rx_submit_datagrams"))) return rc;
+    if (b_total && (rc = reserve_settled(c, rx->a_frames, b_total + 16))) return rc;
+    if ((rc = reserve_settled(c, rx->a_tab, seg_bytes))) return rc;
+    if (b_total && (rc = b.out.reserve(b_total))) return rc;
+    if ((rc = b.d_seg.reserve(seg_bytes))) return rc;
+    if ((rc = rx->ring.ensure_event(b))) return rc;
+    if (any && (rc = rx_ragged_room(rx, fed.data(), &b.d_tabs))) return rc;
+
+    // ---- upload: exactly the datagrams (staged: one copy; in place: one per run of adjacent rows)
+    uint8_t *pk = rx->a_pk.as<uint8_t>();
+    if (sum && !inplace) {
+        HIP_TRY(link_copy(c, pk, b.in.p, bytes_in, hipMemcpyHostToDevice, c->stream));
+        b.in.mark(c->stream);
+    } else if (sum) {
+        size_t off = 0;
+        for (int s = 0; s < S;) {
+            const uint8_t *p0 = row_of(s, off);
+            size_t n = n_dgrams[s] * SDRHIP_UDPSIZE;
+            int j = s + 1;
+            // (packed input is one run; a strided row joins the next one when it fills its stride)
+            for (; j < S && p0 + n == row_of(j, off + n); ++j) n += n_dgrams[j] * SDRHIP_UDPSIZE;
+            if (n) HIP_TRY(link_copy(c, pk + off, p0, n, hipMemcpyHostToDevice, c->stream));
+            off += n;
+            s = j;
+        }
+    }
+
+    // ---- the collector's passes, no read-back, the payloads behind each row's carry (from the scatter launch on, the batch is
+    // consumed: a failure loses it)
+    bool committed = false;
+    const int *counts = nullptr;
+    const FecBufPub *pub = nullptr;
+    const FecBufJoin join = {carry_dev, nullptr, nullptr};
+    rc = fecbuf_packed(rx->fb, pk, n_dgrams, res.data(), sh, b.r_tab, kmax ? rx->j_rows.as<uint8_t>() : nullptr, rx->j_row_len * 4, nullptr, kmax,
+                       c->dec_stats + DEC_STATS_SHADOW_MISMATCH, &committed, &counts, &pub, &join);
+    if (rc && !committed) return rc; // (nothing consumed)
+    if (rc) return rx_batch_lost(rc);
+    // ---- decimate, frame, encode: one ragged step; KJ moves every row's remainder to its head (the device's own counts)
+    if (any) {
+        if ((rc = rx_ragged(rx, rx->j_rows.as<int16_t>(), fed.data(), rx->j_row_len, tv_sec, tv_usec, nullptr, 0, nf.data(), SDRHIP_MEM_DEVICE,
+                            true, true, &b.d_tabs)))
+            return rx_batch_lost(rc);
+        hipError_t e = launch_rx_join_carry(rx->j_rows.as<int16_t>(), rx->j_row_len, carry_dev, counts, (unsigned)U, S, c->stream);
+        if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "rx join launch: %s (the batch is lost)", hipGetErrorString(e));
+        *carry = left;
+    } else { // (nothing released, and no row holds a whole unit: rows and remainders stay)
+        rx->view_frames = 0; rx->view_ragged = false;
+    }
+    // ---- the delivery: every stream's frames (its sliding window in `work`), then the records, gathered and downloaded in ONE copy
+    RxDeliverSeg *seg = b.d_seg.as<RxDeliverSeg>();
+    int nseg = 0;
+    uint64_t dst = 0;
+    for (int s = 0; s < S; ++s) {
+        if (!nf[(size_t)s]) continue;
+        RxDeliverSeg &g = seg[nseg++];
+        g.src = ((size_t)s * rx->cap_frames + rx->r_view_first[(size_t)s]) * fb;
+        g.bytes = nf[(size_t)s] * fb; g.dst = dst; g.from_records = 0;
+        dst += g.bytes;
+    }
+    hipError_t e = dst == b_frames ? hipSuccess : hipErrorInvalidValue; // (cannot differ: the count above is the pipe's own)
+    for (int s = 0; s < S; ++s) {
+        const size_t k = (size_t)res[(size_t)s * 4];
+        if (!k) continue;
+        RxDeliverSeg &g = seg[nseg++];
+        g.src = (size_t)s * kmax * DG_REC;
+        g.bytes = k * DG_REC; g.dst = dst; g.from_records = 1;
+        dst += g.bytes;
+    }
+    const uint32_t grid = rx_deliver_plan(seg, nseg);
+    if (e == hipSuccess && nseg && (!grid || !aligned16(pub))) e = hipErrorInvalidValue;
+    if (e == hipSuccess && nseg) e = hipMemcpyAsync(rx->a_tab.p, seg, (size_t)nseg * sizeof(RxDeliverSeg), hipMemcpyHostToDevice, c->stream); // (not counted: a table)
+    if (e == hipSuccess && nseg) {
+        b.d_seg.mark(c->stream);
+        KTimer kt(c, SDRHIP_K_CONVERT);
+        e = launch_rx_deliver(rx->a_tab.as<RxDeliverSeg>(), nseg, grid, rx->work.as<uint8_t>(), reinterpret_cast<const uint8_t *>(pub),
+                              rx->a_frames.as<uint8_t>(), c->stream);
+    }
+    if (e == hipSuccess && b_total) e = link_copy(c, b.out.p, rx->a_frames.p, b_total, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipEventRecord(b.done, c->stream);
+    if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "rx datagram batch delivery: %s (the batch is lost)", hipGetErrorString(e));
+    b.r_frames.assign(nf.begin(), nf.end());
+    b.d_rel.resize((size_t)S);
+    for (int s = 0; s < S; ++s) b.d_rel[(size_t)s] = (size_t)res[(size_t)s * 4];
+    b.frame_bytes = fb;
+    b.dg = true; b.ragged = false;
+    b.state = 2;
+    ++rx->ring.tail;
+    fecbuf_set_async_busy(rx->fb, true);
+    return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_rx_collect_datagrams(sdrhip_rx *rx, uint8_t *frames_out, size_t frame_stride_bytes, size_t max_frames,
+                                           size_t max_released, sdrhip_fecbuf_frame *info_out, size_t *n_released, size_t *n_frames, int wait)
+{
+    if (!rx || !n_released || !n_frames) return fail(SDRHIP_EINVAL, "rx_collect_datagrams: NULL argument");
+    // (the wait happens outside the context lock: the submitting thread -- the hub's reader thread -- keeps feeding the ring)
+    std::unique_lock<std::recursive_mutex> lock_(rx->ctx->mtx);
+    const int S = rx->nstreams;
+    for (int s = 0; s < S; ++s) n_released[s] = n_frames[s] = 0;
+    if (rx_has_batches(rx, false) || rx_has_batches(rx, true))
+        return fail(SDRHIP_EINVAL, "rx_collect_datagrams: uniform or ragged batches are being filled or in flight: use sdrhip_rx_collect[_ragged]");
+    HIP_TRY(hipSetDevice(rx->ctx->device));
+    sdrhip_rx::Batch *bp = nullptr;
+    // (a datagram batch goes out when it is submitted: none is ever being filled)
+    int rc = rx->ring.wait_oldest(lock_, wait, "rx_collect_datagrams", [](sdrhip_rx::Batch &) { return SDRHIP_OK; }, &bp);
+    if (rc) return rc;
+    sdrhip_rx::Batch &b = *bp;
+    size_t most = 0, most_rel = 0, all = 0;
+    for (int s = 0; s < S; ++s) {
+        most = b.r_frames[(size_t)s] > most ? b.r_frames[(size_t)s] : most;
+        most_rel = b.d_rel[(size_t)s] > most_rel ? b.d_rel[(size_t)s] : most_rel;
+        all += b.r_frames[(size_t)s];
+    }
+    // (the batch stays where it is while the caller lacks room: the counts say how much it needs)
+    const char *why = nullptr;
+    if (most > max_frames) why = "a stream of the batch holds more frames than max_frames";
+    else if (most_rel > max_released) why = "a stream of the batch released more frames than max_released";
+    else if (most && S > 1 && frame_stride_bytes < most * b.frame_bytes) why = "frame stride too small for the stream with the most frames";
+    else if (most && !frames_out) why = "NULL frames_out";
+    else if (most_rel && !info_out) why = "NULL info_out";
+    if (why) {
+        for (int s = 0; s < S; ++s) { n_released[s] = b.d_rel[(size_t)s]; n_frames[s] = b.r_frames[(size_t)s]; }
+        return fail(SDRHIP_EINVAL, "rx_collect_datagrams: %s (most frames %zu, most records %zu; the batch stays)", why, most, most_rel);
+    }
+    const uint8_t *src = b.out.as<uint8_t>(), *rec = src + all * b.frame_bytes;
+    for (int s = 0; s < S; ++s) {
+        const size_t row = b.r_frames[(size_t)s] * b.frame_bytes, k = b.d_rel[(size_t)s];
+        if (row) memcpy(frames_out + (size_t)s * frame_stride_bytes, src, row);
+        if (k) memcpy(info_out + (size_t)s * max_released, rec, k * DG_REC);
+        src += row; rec += k * DG_REC;
+        n_released[s] = k; n_frames[s] = b.r_frames[(size_t)s];
+    }
+    b.state = 0;
+    b.dg = false;
+    ++rx->ring.head;
+    fecbuf_set_async_busy(rx->fb, rx_dgrams_in_flight(rx));
+    return SDRHIP_OK;
+}

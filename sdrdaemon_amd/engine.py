@@ -533,6 +533,7 @@ class RxPipe:
         this call's decimator launch, sdrhip_rx_set_pipelined); flush() / flush_view() return the last call's at the end.
         input_format: "s16" (int16 IQ), "u8" (RTL-SDR uint8 offset binary) or "s8" (HackRF int8), see set_input_format."""
         self.ctx, self.nstreams, self.nb_fec = ctx, nstreams, nb_fec
+        self._dg_pending = []  # nb_fec of every datagram batch in flight, oldest first (collect_datagrams sizes its frames with it)
         self.cfg = RxConfig(log2decim, fcpos, hb_variant, sample_bits, nb_fec, center_frequency_khz, sample_rate)
         self.h = C.c_void_p()
         self.m_error = ""
@@ -892,6 +893,86 @@ class RxPipe:
                                                       MEM_DEVICE if is_t else MEM_HOST)
         self.last_n_released = [int(x) for x in nr]
         check(rc)
+        res = []
+        for s in range(S):
+            recs = [dict(frame_index=info[s * F + j].frame_index, block_count=info[s * F + j].block_count,
+                         recovery_count=info[s * F + j].recovery_count, flags=info[s * F + j].flags) for j in range(int(nr[s]))]
+            res.append((out[s, :int(nf[s])], recs))
+        return res
+
+    # ---- asynchronous datagram batches (sdrhip_rx_submit_datagrams / sdrhip_rx_collect_datagrams)
+    def submit_datagrams(self, dgrams_per_stream, tv_sec=0, tv_usec=0):
+        """one batch of raw datagrams from host memory, as TxPipe.submit_datagrams takes them: one (n_s, 512) uint8 numpy array per
+        stream (counts may differ, may be 0), or ONE (sum n_s, 512) array of them back to back with a list of counts as (array,
+        counts) -- such an array in sdrhip_host_alloc memory goes up in place and must stay untouched until the batch is collected.
+        tv_sec / tv_usec (scalars or one per stream) stamp the first sample each stream feeds its decimator in this batch.  Returns
+        at once; raises SdrHipError(code SDRHIP_EBUSY = -6) when every batch of the ring is in flight."""
+        S = self.nstreams
+        if isinstance(dgrams_per_stream, tuple):
+            buf, counts = dgrams_per_stream
+            counts = [int(x) for x in counts]
+            if len(counts) != S:
+                raise ValueError("one count per stream")
+        else:
+            if len(dgrams_per_stream) != S:
+                raise ValueError("one datagram array per stream")
+            if any(_is_torch(d) for d in dgrams_per_stream):
+                raise TypeError("submit_datagrams takes host memory")
+            counts = [int(np.asarray(d).shape[0]) for d in dgrams_per_stream]
+            nz = [np.asarray(d, np.uint8).reshape(-1, UDPSIZE) for d in dgrams_per_stream if len(d)]
+            buf = np.concatenate(nz) if nz else np.zeros((0, UDPSIZE), np.uint8)
+        if _is_torch(buf):
+            raise TypeError("submit_datagrams takes host memory")
+        buf = np.ascontiguousarray(buf, np.uint8)
+        if buf.size != sum(counts) * UDPSIZE:
+            raise ValueError("the datagrams do not match the counts")
+        sec = np.broadcast_to(np.asarray(tv_sec, dtype=np.uint32), (S,))
+        usec = np.broadcast_to(np.asarray(tv_usec, dtype=np.uint32), (S,))
+        nd = (C.c_size_t * S)(*counts)
+        check(self.ctx.lib.sdrhip_rx_submit_datagrams(self.h, _ptr(buf), nd, 0, (C.c_uint32 * S)(*[int(v) for v in sec]),
+                                                      (C.c_uint32 * S)(*[int(v) for v in usec])))  # (0 = SDRHIP_PACKED)
+        self._dg_submitted()
+
+    def _dg_submitted(self):
+        """bookkeeping behind a successful sdrhip_rx_submit_datagrams (also for callers of the C entry itself): the batch keeps the
+        frame size in force at its submit"""
+        self._dg_pending.append(self.nb_fec)
+
+    def collect_datagrams(self, wait=True, max_frames=None, max_released=None):
+        """the oldest datagram batch: per stream (frames (n, 128 + nb_fec, 512) uint8, records) as process_datagrams returns them, or
+        None when no batch was collected (nothing submitted, or wait=False and the oldest one is in flight).  max_frames /
+        max_released = None: room for exactly what the batch holds (one call that learns the counts, one that collects); a batch
+        that holds more than a given bound raises SdrHipError and stays (last_n_frames / last_n_released have the counts)."""
+        S = self.nstreams
+        nr, nf = (C.c_size_t * S)(), (C.c_size_t * S)()
+        w = 1 if wait else 0
+        pend = self._dg_pending
+        if max_frames is None or max_released is None:
+            rc = self.ctx.lib.sdrhip_rx_collect_datagrams(self.h, None, 0, 0, 0, None, nr, nf, w)
+            if rc == -6:
+                return None
+            if rc == 0:  # (a batch that released and completed nothing: collected)
+                rows = NB_ORIGINAL + (pend.pop(0) if pend else self.nb_fec)
+                self.last_n_released, self.last_n_frames = [0] * S, [0] * S
+                return [(np.zeros((0, rows, UDPSIZE), np.uint8), []) for _ in range(S)]
+            if rc != -1:
+                check(rc)
+            if max_frames is None:
+                max_frames = max(int(x) for x in nf)
+            if max_released is None:
+                max_released = max(int(x) for x in nr)
+        rows = NB_ORIGINAL + (pend[0] if pend else self.nb_fec)
+        fb = rows * UDPSIZE
+        cap, F = max(max_frames, 1), max(max_released, 1)
+        out = np.empty((S, cap, rows, UDPSIZE), np.uint8)
+        info = (FECBufferFrame * (S * F))()
+        rc = self.ctx.lib.sdrhip_rx_collect_datagrams(self.h, _ptr(out), cap * fb, max_frames, max_released, info, nr, nf, w)
+        self.last_n_released, self.last_n_frames = [int(x) for x in nr], [int(x) for x in nf]
+        if rc == -6:
+            return None
+        check(rc)
+        if pend:
+            pend.pop(0)
         res = []
         for s in range(S):
             recs = [dict(frame_index=info[s * F + j].frame_index, block_count=info[s * F + j].block_count,
