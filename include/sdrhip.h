@@ -278,6 +278,25 @@ void sdrhip_rx_destroy(sdrhip_rx *rx);
  * frame being filled keeps the meta block it was started with and is encoded with the fecblk value
  * in force when it completes (UDPSinkFEC.cpp:160-165).  hb_variant cannot change. */
 int sdrhip_rx_reconfigure(sdrhip_rx *rx, const sdrhip_rx_config *cfg);
+/* Per-stream UDPSink::setCenterFrequency / setSampleRate (UDPSink.h:93-96; sdrdaemonrx.cpp:597,624,644: every sdrdaemonrx sets them
+ * from its own source).  Host arrays of nstreams entries; NULL = that field is bank-wide again (sdrhip_rx_config's value).
+ * A frame of stream s takes, when it is opened: center_frequency_khz[s] and sample_rate[s] in bytes 0..7 of its meta block
+ * (UDPSinkFEC.cpp:97-98), the CRC-32 over its own 20 bytes, and a time stamp advanced by ITS OWN sample clock: floor(p * 10^6 /
+ * sample_rate[s]) microseconds for a frame that starts p decimated samples into the call (sample_rate[s] = 0: no advance).  Per
+ * stream the result is byte for byte that of a one-stream sdrhip_rx whose config carries that stream's two values -- meta block and
+ * the recovery blocks computed over it -- through every entry: sdrhip_rx_process (immediate and pipelined, sdrhip_rx_flush),
+ * sdrhip_rx_process_ragged, sdrhip_rx_submit / _collect, sdrhip_rx_submit_ragged / _collect_ragged, sdrhip_rx_process_datagrams
+ * and sdrhip_rx_submit_datagrams / _collect_datagrams.
+ * While an array is set for a field, the config's value of that field is unused; sdrhip_rx_reconfigure does not clear the arrays.
+ * sample_rate stays "the rate AFTER decimation", the caller's business as in the config.
+ * Allowed at any time, never synchronises: it applies to frames opened by later launches.  A batch takes the values at the moment
+ * it takes its sdrhip_rx_config: a datagram batch at submit, a uniform or ragged batch when it is launched.  The frame being filled
+ * keeps the meta block it was started with (UDPSinkFEC.cpp:160-165), batches in flight keep theirs, and frames a pipelined call
+ * left for the next launch keep the values of the call that opened them.  A handle on which this was never called launches what it
+ * launched before the call existed.  SDRHIP_EINVAL, nothing changed: a NULL handle. */
+int sdrhip_rx_set_stream_meta(sdrhip_rx *rx, const uint32_t *center_frequency_khz, const uint32_t *sample_rate);
+/* what stream s's next opened frame will carry (either pointer may be NULL); SDRHIP_EINVAL: a NULL handle, a stream outside the bank */
+int sdrhip_rx_get_stream_meta(const sdrhip_rx *rx, int stream, uint32_t *center_frequency_khz, uint32_t *sample_rate);
 /* Feeds n_in device-rate samples per stream.  Completed frames of stream s are written to
  * frames_out + s*frame_stride_bytes as (128 + nb_fec) super blocks of 512 bytes each,
  * frame after frame; *n_frames (per stream, identical for all streams) is the number of

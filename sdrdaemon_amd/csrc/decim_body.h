@@ -298,7 +298,8 @@ template <class G, int S> __device__ __forceinline__ void later_stages(int *lds,
 // end of the call).  from_state: the piece starts where the bank state was saved (no warm-up), otherwise the
 // histories are rebuilt from the WRAW preceding raw samples.  store_state: the piece ends the call.
 // meta_id / meta_n: this workgroup writes the meta blocks of frames meta_id, meta_id + meta_n, ...
-template <int L, int FC, bool PACK16>
+// TAB = false (the ragged launches): a.meta_tab is not looked at, the shared record serves every stream
+template <int L, int FC, bool PACK16, bool TAB = true>
 __device__ __forceinline__ void decim_piece(const DecimArgs &a, int *lds, int stream, size_t seg_start, size_t seg_end, bool from_state,
                                             bool store_state, int meta_id, int meta_n)
 {
@@ -327,9 +328,11 @@ __device__ __forceinline__ void decim_piece(const DecimArgs &a, int *lds, int st
         // (i) the 24-byte records, a frame per THREAD: two 64-bit divisions and a CRC each -- one frame at a time, with the record
         // formed by a whole wave, this loop took ~1.2 us per frame, and the matrix-core launch leaves it to three workgroups per
         // stream: 130 frames = the launch's tail (profiles/r05_rx_direct.txt); (ii) zero fill and block headers, a frame per pass
+        unsigned base[6], rate;
+        stream_meta_base(a.meta_w, a.meta_rate, TAB ? a.meta_tab : nullptr, stream, base, rate);
         for (int fi = meta_id + tid * meta_n; fi < a.meta_count; fi += NT * meta_n) {
             unsigned w[6];
-            frame_meta_words_thread(a.meta_w, a.meta_idx0, a.meta_rate, fi, w);
+            frame_meta_words_thread(base, a.meta_idx0, rate, fi, w);
             unsigned *fr = oc.out + (size_t)(a.meta_first + fi) * a.frame_blocks * 128u;
             fr[0] = (a.meta_frame_count0 + (unsigned)fi) & 0xffffu;
 #pragma unroll

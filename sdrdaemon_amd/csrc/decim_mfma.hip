@@ -636,7 +636,10 @@ template <int L, bool PACK16, int NG, bool FR> __global__ __launch_bounds__(mf_b
 // K1mr: the same launch for a ragged call (sdrhip_rx_process_ragged, sdrhip_decimate_ragged).  The streams share the span, the head and
 // the piece length; each has its own count of wave groups and pieces, dealt through prefix sums of the per-call table (RaggedRow
 // mf_w0 / mf_p0: a binary search per workgroup).  a.mf_wps = the launch's matrix-core waves, a.mf_npieces = its pieces.  In frame
-// mode each stream stores into its own window (RaggedRow out_off) with its own frame base and meta record.
+// mode each stream stores into its own window (RaggedRow out_off) with its own frame base and meta record.  (The record's
+// per-stream words -- RaggedRow fc / rate / crc0 -- are NOT read here: this kernel has no scalar register to spare, its 64 spilled
+// SGPRs fill one VGPR to the last lane.  Its pieces write the launch's shared record, decim_piece<.., TAB = false>; when the
+// streams' values differ, K2r rewrites the meta blocks behind this launch: launch_frame_meta_ragged.)
 __device__ __forceinline__ int mf_ragged_find(const RaggedRow *rows, int nstreams, int x, bool waves)
 {
     // the last stream whose first wave (piece) is <= x: streams without waves share their first index with the next one
@@ -682,12 +685,12 @@ template <int L, bool PACK16, int NG, bool FR> __global__ __launch_bounds__(mf_b
             const int piece = lx - r.mf_p0;
             const size_t n_used = (size_t)r.n_used;
             if (piece == 0) {
-                decim_piece<L, 2, PACK16>(b, lds, stream, 0, (size_t)r.mf_head, true, r.mf_np == 1, piece, r.mf_np);
+                decim_piece<L, 2, PACK16, false>(b, lds, stream, 0, (size_t)r.mf_head, true, r.mf_np == 1, piece, r.mf_np);
             } else {
                 const size_t s0 = (size_t)r.mf_tail_start + (size_t)(piece - 1) * a.mf_tail_seg;
                 size_t s1 = s0 + a.mf_tail_seg;
                 if (s1 > n_used || piece == r.mf_np - 1) s1 = n_used;
-                decim_piece<L, 2, PACK16>(b, lds, stream, s0, s1, false, piece == r.mf_np - 1, piece, r.mf_np);
+                decim_piece<L, 2, PACK16, false>(b, lds, stream, s0, s1, false, piece == r.mf_np - 1, piece, r.mf_np);
             }
             __syncthreads(); // (the next piece reuses the stage buffers)
         }

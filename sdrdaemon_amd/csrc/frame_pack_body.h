@@ -2,7 +2,8 @@
 // Include inside namespace sdrhip { namespace { ... } }.
 #pragma once
 // one workgroup of K2: block bx of nbx of stream `stream` (a device function: gf_kernels.hip runs it in the encoder's launch too)
-__device__ __forceinline__ void frame_pack_wg(const FrameArgs &a, int stream, unsigned bx, unsigned nbx)
+// ROWMETA (a ragged launch): meta_row = the stream's {fc, rate, crc0} (stream_meta_base<true>), else a.meta_tab or the shared record
+template <bool ROWMETA = false> __device__ __forceinline__ void frame_pack_wg(const FrameArgs &a, int stream, unsigned bx, unsigned nbx, const unsigned *meta_row = nullptr)
 {
     const unsigned *src = a.in + (size_t)stream * a.in_stride;
     unsigned *dst = a.out + (size_t)stream * a.out_stride;
@@ -20,9 +21,11 @@ __device__ __forceinline__ void frame_pack_wg(const FrameArgs &a, int stream, un
     // meta block + super block headers of the frames this call starts: frame fi by workgroup fi mod nbx
     if (threadIdx.x < 128) {
         const unsigned t = threadIdx.x;
+        unsigned base[6], rate;
+        stream_meta_base<ROWMETA>(a.meta_w, a.meta_rate, ROWMETA ? meta_row : a.meta_tab, stream, base, rate);
         for (int fi = (int)bx; fi < a.meta_count; fi += (int)nbx) {
             unsigned w[6];
-            frame_meta_words(a.meta_w, a.meta_idx0, a.meta_rate, fi, w); // per-frame time stamp + CRC (wave-uniform)
+            frame_meta_words(base, a.meta_idx0, rate, fi, w); // per-frame time stamp + CRC (wave-uniform)
             unsigned mw = 0u; // dword t of block 0 behind the header: the 24-byte MetaDataFEC, then zeros
 #pragma unroll
             for (int k = 0; k < 6; ++k)

@@ -214,8 +214,9 @@ __device__ __forceinline__ void gf_encode128_wg(const Enc128Args &a, int bx, uns
     if (a.meta_count > 0 && a.gen_done > 0) {
         const int f = fr % a.gen_cap, fi = f - a.meta_first;
         if (fr >= 0 && fi >= 0 && fi < a.meta_count) { // (workgroup-uniform: the shuffle inside frame_meta_words sees whole waves)
-            unsigned w[6];
-            frame_meta_words(a.meta_w, a.meta_idx0, a.meta_rate, fi, w);
+            unsigned w[6], base[6], rate;
+            stream_meta_base(a.meta_w, a.meta_rate, a.meta_tab, fr / a.gen_cap, base, rate);
+            frame_meta_words(base, a.meta_idx0, rate, fi, w);
             own0 = true;
             hdr0 = (a.meta_frame_count0 + (unsigned)fi) & 0xffffu;
 #pragma unroll

@@ -182,8 +182,9 @@ template <int HF> __device__ __forceinline__ void gf_encode128_bs_wave(const Enc
     if (a.meta_count > 0 && a.gen_done > 0) {
         const int f = fr % a.gen_cap, mi = f - a.meta_first;
         if (mi >= 0 && mi < a.meta_count) {
-            unsigned w[6];
-            frame_meta_words(a.meta_w, a.meta_idx0, a.meta_rate, mi, w);
+            unsigned w[6], base[6], rate;
+            stream_meta_base(a.meta_w, a.meta_rate, a.meta_tab, fr / a.gen_cap, base, rate);
+            frame_meta_words(base, a.meta_idx0, rate, mi, w);
             own0 = true;
             hdr0 = (a.meta_frame_count0 + (unsigned)mi) & 0xffffu;
 #pragma unroll

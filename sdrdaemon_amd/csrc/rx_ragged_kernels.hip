@@ -38,7 +38,7 @@ template <int L, int FC, bool PACK16> __global__ __launch_bounds__(NT) void deci
     const size_t seg_start = (size_t)seg * seg_raw;
     size_t seg_end = seg_start + seg_raw;
     if (seg_end > n_used) seg_end = n_used;
-    decim_piece<L, FC, PACK16>(a, lds, s, seg_start, seg_end, seg == 0, seg == nseg - 1, seg, nseg);
+    decim_piece<L, FC, PACK16, false>(a, lds, s, seg_start, seg_end, seg == 0, seg == nseg - 1, seg, nseg);
 }
 
 template <int L, int FC, bool PACK16> hipError_t launch_ragged_variant(const DecimArgs &a, const RaggedRow *rows, hipStream_t stream)
@@ -60,13 +60,13 @@ __global__ __launch_bounds__(256) void frame_pack_ragged_kernel(FrameArgs a, con
 {
     const int s = (int)blockIdx.y;
     const RaggedRow &r = rows[s];
-    a.n = (size_t)r.n_dec;
+    a.n = a.in ? (size_t)r.n_dec : 0; // (a.in == NULL: no samples, the meta blocks alone -- launch_frame_meta_ragged)
     a.out += r.out_off;
     a.frame_sample_base = r.frame_sample_base;
     a.meta_first = r.meta_first; a.meta_count = r.meta_count; a.meta_frame_count0 = r.frame_count0;
     a.meta_w[3] = r.tv_sec; a.meta_w[4] = r.tv_usec;
     a.meta_idx0 = r.meta_idx0;
-    frame_pack_wg(a, s, blockIdx.x, gridDim.x);
+    frame_pack_wg<true>(a, s, blockIdx.x, gridDim.x, &r.fc);
 }
 
 // K0r: two samples {re, im, re, im} of one dword -> two IQSample dwords (convert_kernels.hip's rule: U8 = S8 behind one XOR)
@@ -149,6 +149,15 @@ hipError_t launch_frame_pack_ragged(const FrameArgs &a, const RaggedRow *rows, i
     size_t blocks = (a.n + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(frame_pack_ragged_kernel, dim3((unsigned)blocks, nstreams), dim3(256), 0, stream, a, rows);
+    return hipGetLastError();
+}
+
+hipError_t launch_frame_meta_ragged(const FrameArgs &a0, const RaggedRow *rows, int max_started, int nstreams, hipStream_t stream)
+{
+    FrameArgs a = a0;
+    a.in = nullptr;
+    const int blocks = max_started < 1 ? 1 : max_started > 2048 ? 2048 : max_started; // (frame fi of a stream by workgroup fi mod blocks)
     hipLaunchKernelGGL(frame_pack_ragged_kernel, dim3((unsigned)blocks, nstreams), dim3(256), 0, stream, a, rows);
     return hipGetLastError();
 }

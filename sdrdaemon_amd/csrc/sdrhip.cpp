@@ -513,7 +513,7 @@ int decimate_device(sdrhip_decimators *d, int log2decim, int fcpos, unsigned *sa
     if (meta) {
         a.meta_first = meta->first; a.meta_count = meta->count; a.meta_frame_count0 = meta->frame_count0;
         memcpy(a.meta_w, meta->w, sizeof(a.meta_w));
-        a.meta_idx0 = meta->idx0; a.meta_rate = meta->rate;
+        a.meta_idx0 = meta->idx0; a.meta_rate = meta->rate; a.meta_tab = meta->tab;
     }
     plan_decimate((int)L, fcpos, a.n_used, d->nstreams, &a.nsub_per_seg, &a.nseg);
     const bool cen = (fcpos == SDRHIP_FC_CEN);

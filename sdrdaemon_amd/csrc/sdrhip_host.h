@@ -64,6 +64,7 @@ struct RxMeta {
     unsigned w[6]; // MetaDataFEC, 24 bytes: w[3], w[4] = time stamp of the call's first sample; the kernels advance it per frame and add the CRC
     uint64_t idx0; // call-relative decimated-sample index of the first started frame's first sample
     unsigned rate; // sample rate the stamps advance with (Hz, 0 = none)
+    const unsigned *tab; // per-stream {fc, rate, zero-stamp CRC} on the device (DecimArgs::meta_tab), NULL: w / rate serve every stream
 };
 
 // sampleSize after decimateN (Decimators.cpp:43-44, 112-113 ...): grows by log2decim, capped at 16 bits

@@ -70,6 +70,9 @@ struct DecimArgs {
     unsigned *mf_dump;   // >= 1 KiB of device memory that swallows the stores of the warm-up period
     int mf_ring;         // LDS-DMA ring depth of the decimate16 kernel in groups: 4 (147 KiB per workgroup), 3 (108 KiB: room for another kernel)
     int mf_prio;         // 1: the matrix-core waves raise their issue priority (they share their SIMDs with another kernel's waves)
+    // (behind everything else: the kernels' argument offsets are part of their register allocation, decim_mfma.hip sits on the edge)
+    const unsigned *meta_tab; // per-stream {fc, rate, zero-stamp CRC}, STREAM_META_WORDS each (stream_meta_base()); NULL: meta_w / meta_rate
+                              // serve every stream.  (Ragged launches leave it NULL: each stream's three words come with its RaggedRow, for K2r)
 };
 
 // MetaDataFEC of the fi-th frame a call starts (UDPSinkFEC.cpp:90-115: the reference takes gettimeofday() when it opens a
@@ -82,6 +85,7 @@ struct DecimArgs {
 // of a wave looks at bit k, six DPP / swizzle steps XOR-reduce: ~25 instructions per frame instead of a 160-step bit-serial
 // loop (which doubled the framing kernel's time).  Must be called by whole waves.  (The test-side framer applies the same
 // rule: DESIGN.md K2.)
+constexpr int STREAM_META_WORDS = 3; // words per stream of DecimArgs::meta_tab (stream_meta_base)
 #if defined(__HIPCC__) && __cplusplus >= 201703L // (the kernels' translation units: C++17; the host files are C++11)
 struct CrcBitTable { unsigned c[64]; };
 constexpr CrcBitTable make_crc_bit_table()
@@ -141,6 +145,25 @@ __device__ __forceinline__ void frame_meta_words_thread(const unsigned (&base)[6
     }
     w[5] = base[5] ^ x;
 }
+// Per-stream UDPSink::setCenterFrequency / setSampleRate (sdrhip_rx_set_stream_meta): of the six words of a launch's zero-stamp record
+// three differ between the streams of a bank: w[0] = centre frequency, w[1] = sample rate (also the clock of the stamps) and
+// w[5] = the record's CRC (host-computed: the affine part, see above).  ROW = false (uniform launches): `p` is the Rx handle's
+// table, stream s at p + s * STREAM_META_WORDS, NULL: the shared record serves every stream.  ROW = true (ragged launches): `p` is
+// the stream's own three words, RaggedRow::fc ...  `stream` and `p` are wave-uniform: three scalar loads where a workgroup starts
+// on a stream's frames.
+template <bool ROW = false>
+__device__ __forceinline__ void stream_meta_base(const unsigned (&shared)[6], unsigned shared_rate, const unsigned *p, int stream,
+                                                 unsigned (&base)[6], unsigned &rate)
+{
+#pragma unroll
+    for (int k = 0; k < 6; ++k) base[k] = shared[k];
+    rate = shared_rate;
+    if (ROW || p) {
+        const unsigned *t = ROW ? p : p + (size_t)STREAM_META_WORDS * (size_t)__builtin_amdgcn_readfirstlane(stream);
+        base[0] = t[0]; base[1] = t[1]; base[5] = t[2];
+        rate = t[1];
+    }
+}
 #endif
 
 // returns hipSuccess or the launch error
@@ -182,6 +205,8 @@ struct RaggedRow {
     // (mf_wps = 0) runs on pieces alone (mf_head = min(n_used, mf_tail_seg)).
     int mf_w0, mf_wps, mf_p0, mf_np;
     uint64_t mf_head, mf_tail_start;
+    unsigned fc, rate, crc0;    // K2r: the stream's centre frequency, sample rate and zero-stamp CRC (stream_meta_base<true>)
+    unsigned pad;
 };
 // K1mr: plans the matrix-core launch of a ragged call (per-stream fields of `rows`, shared span / grid in `a`: a->mf_wps = the
 // launch's matrix-core waves, a->mf_npieces = its VALU pieces); false when no stream is long enough for a span
@@ -219,11 +244,15 @@ struct FrameArgs {
     unsigned meta_w[6];
     uint64_t meta_idx0;
     unsigned meta_rate;
+    const unsigned *meta_tab; // as DecimArgs::meta_tab
 };
 hipError_t launch_frame_pack(const FrameArgs &a, int nstreams, hipStream_t stream);
 // K2r: the same with per-stream n / window / frame base / meta record from `rows` (a.n = the largest count: the grid;
-// a.meta_w[3..4] are replaced by each row's stamp; skip_* unused)
+// a.meta_w[3..4] are replaced by each row's stamp, {fc, rate, crc0} come from the row too; skip_* unused)
 hipError_t launch_frame_pack_ragged(const FrameArgs &a, const RaggedRow *rows, int nstreams, hipStream_t stream);
+// K2r without samples: block 0 (header, meta record, zero fill) and the headers of blocks 1..127 of the frames every stream starts,
+// rewritten behind a K1mr launch whose pieces wrote them with the shared record; max_started = the largest meta_count of the rows
+hipError_t launch_frame_meta_ragged(const FrameArgs &a, const RaggedRow *rows, int max_started, int nstreams, hipStream_t stream);
 
 struct InterpArgs {
     const int16_t *in;
@@ -358,6 +387,7 @@ struct Enc128Args {
     unsigned meta_w[6];
     uint64_t meta_idx0;
     unsigned meta_rate;
+    const unsigned *meta_tab;       // as DecimArgs::meta_tab : the frame's stream is fr / gen_cap
     // staggered start (round 6): the launch is ONE round of resident workgroups that all load first and compute afterwards -- the
     // memory phase and the VALU phase do not overlap.  Workgroup i sleeps (i / stagger_div) * stagger units of 1024 clocks before
     // its loads (stagger_div = the number of CUs: the i-th workgroup a CU receives), so that the co-resident workgroups of a CU are

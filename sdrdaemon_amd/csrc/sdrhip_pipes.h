@@ -169,6 +169,19 @@ struct sdrhip_rx {
     bool view_ragged = false;          // the last call's windows differ between streams: sdrhip_rx_frames_view refuses
     sdrhip::PinnedBuf r_pin, r_flist_pin; // host-row staging and the encoder's frame list
     sdrhip::DevBuf r_flist;
+    // ---- per-stream centre frequency / sample rate (sdrhip_rx_set_stream_meta).  The setter touches the host arrays alone; the
+    // next launch forms the streams' records (sm_words: {fc, rate, zero-stamp CRC} per stream, for the configuration in sm_key).
+    // Ragged launches carry them in their row table.  Uniform launches read a device table: a change goes up in front of the
+    // launch, on the context's stream, from the next of four pinned versions into the device table the previous version does
+    // NOT occupy -- launches in flight keep the table they were enqueued with, a deferred encode (late.k) keeps its pointer
+    std::vector<uint32_t> sm_fc, sm_rate; // empty: the field is bank-wide (cfg's value)
+    uint64_t sm_version = 0;              // counts the setter's calls
+    struct SmKey { uint64_t version; unsigned w2, fc, rate; } sm_key = {~(uint64_t)0, 0, 0, 0};
+    std::vector<unsigned> sm_words;
+    bool sm_uploaded = false;             // sm_dev[sm_dev_sel] holds sm_words
+    sdrhip::PinnedBuf sm_pin[4];
+    sdrhip::DevBuf sm_dev[2];
+    int sm_pin_sel = 0, sm_dev_sel = 0;
     // ---- datagram entry (sdrhip_rx_process_datagrams): one SDRdaemonFECBuffer per stream, created on first use; it delivers into
     // j_rows ([nstreams][j_row_len] samples, the ragged step's input), behind the samples each row holds back from earlier calls
     // (their counts live with the collector: fecbuf_join_carry)

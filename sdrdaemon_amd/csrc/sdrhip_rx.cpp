@@ -154,6 +154,8 @@ extern "C" void sdrhip_rx_destroy(sdrhip_rx *rx)
     rx->a_pk.release(); rx->a_din.release(); rx->a_tab.release(); rx->a_frames.release();
     sdrhip_fecbuf_destroy(rx->fb); // (synchronises the stream)
     rx->j_rows.release();
+    for (auto &b : rx->sm_pin) b.release();
+    for (auto &b : rx->sm_dev) b.release();
     delete rx;
 }
 
@@ -248,14 +250,13 @@ extern "C" int sdrhip_rx_flush(sdrhip_rx *rx, uint8_t *frames_out, size_t frame_
 // bytes (:106-109): the affine part of every frame's CRC.  A frame's own stamp (the reference calls gettimeofday when it opens the
 // frame, :90-104) is the call's plus its first sample's offset on the sample clock: w[3], w[4] and the CRC follow per frame on the
 // device (frame_meta_words)
-static void rx_meta_base(const sdrhip_rx_config &cfg, unsigned ssd, unsigned w[6])
+static void rx_meta_record(uint32_t fc, uint32_t sr, int nb_fec, unsigned ssd, unsigned w[6])
 {
     uint8_t m[24];
-    const uint32_t fc = cfg.center_frequency_khz, sr = cfg.sample_rate;
     memcpy(m + 0, &fc, 4); memcpy(m + 4, &sr, 4);
     m[8] = (uint8_t)((ssd - 1) / 8 + 1); // setSampleBytes((sampleSize - 1) / 8 + 1), sdrdaemonrx.cpp:643
     m[9] = (uint8_t)ssd;                 // setSampleBits(sampleSize), :642
-    m[10] = SDRHIP_NB_ORIGINAL; m[11] = (uint8_t)cfg.nb_fec;
+    m[10] = SDRHIP_NB_ORIGINAL; m[11] = (uint8_t)nb_fec;
     memset(m + 12, 0, 8);
     uint32_t crc = 0xFFFFFFFFu;
     for (int i = 0; i < 20; ++i) {
@@ -265,6 +266,86 @@ static void rx_meta_base(const sdrhip_rx_config &cfg, unsigned ssd, unsigned w[6
     crc ^= 0xFFFFFFFFu;
     memcpy(m + 20, &crc, 4);
     memcpy(w, m, 24);
+}
+static void rx_meta_base(const sdrhip_rx_config &cfg, unsigned ssd, unsigned w[6])
+{
+    rx_meta_record(cfg.center_frequency_khz, cfg.sample_rate, cfg.nb_fec, ssd, w);
+}
+
+// ---- per-stream centre frequency / sample rate (UDPSink.h:93-96: every sdrdaemonrx sets them on its own sink)
+extern "C" int sdrhip_rx_set_stream_meta(sdrhip_rx *rx, const uint32_t *center_frequency_khz, const uint32_t *sample_rate)
+{
+    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
+    sdrhip::CtxLock lock_(rx->ctx);
+    const size_t S = (size_t)rx->nstreams;
+    // (host arrays alone: the next launch takes them, nothing is enqueued and nothing waited for here)
+    if (center_frequency_khz) rx->sm_fc.assign(center_frequency_khz, center_frequency_khz + S);
+    else rx->sm_fc.clear();
+    if (sample_rate) rx->sm_rate.assign(sample_rate, sample_rate + S);
+    else rx->sm_rate.clear();
+    ++rx->sm_version;
+    return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_rx_get_stream_meta(const sdrhip_rx *rx, int stream, uint32_t *center_frequency_khz, uint32_t *sample_rate)
+{
+    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
+    sdrhip::CtxLock lock_(rx->ctx);
+    if (stream < 0 || stream >= rx->nstreams) return fail(SDRHIP_EINVAL, "rx_get_stream_meta: stream %d of %d", stream, rx->nstreams);
+    if (center_frequency_khz) *center_frequency_khz = rx->sm_fc.empty() ? rx->cfg.center_frequency_khz : rx->sm_fc[(size_t)stream];
+    if (sample_rate) *sample_rate = rx->sm_rate.empty() ? rx->cfg.sample_rate : rx->sm_rate[(size_t)stream];
+    return SDRHIP_OK;
+}
+
+// the streams' records for the frames the next launch opens: [nstreams][STREAM_META_WORDS] = {fc, rate, CRC of the zero-stamp
+// record}; NULL while neither array is set (the shared record of rx_meta_base serves every stream).  Formed again only when the
+// arrays or the configuration words that enter the record have changed
+static const unsigned *rx_stream_words(sdrhip_rx *rx, unsigned ssd)
+{
+    if (rx->sm_fc.empty() && rx->sm_rate.empty()) return nullptr;
+    unsigned w[6];
+    rx_meta_base(rx->cfg, ssd, w);
+    const sdrhip_rx::SmKey key = {rx->sm_version, w[2], w[0], w[1]};
+    const sdrhip_rx::SmKey &old = rx->sm_key;
+    if (key.version != old.version || key.w2 != old.w2 || key.fc != old.fc || key.rate != old.rate) {
+        const size_t S = (size_t)rx->nstreams;
+        rx->sm_words.resize(S * STREAM_META_WORDS);
+        for (size_t s = 0; s < S; ++s) {
+            rx_meta_record(rx->sm_fc.empty() ? rx->cfg.center_frequency_khz : rx->sm_fc[s],
+                           rx->sm_rate.empty() ? rx->cfg.sample_rate : rx->sm_rate[s], rx->cfg.nb_fec, ssd, w);
+            unsigned *t = &rx->sm_words[s * STREAM_META_WORDS];
+            t[0] = w[0]; t[1] = w[1]; t[2] = w[5];
+        }
+        rx->sm_key = key;
+        rx->sm_uploaded = false;
+    }
+    return rx->sm_words.data();
+}
+
+// ... on the device, for a uniform launch (*dev = NULL: shared record).  A new version is copied in front of the launch on the
+// context's stream: from a pinned buffer of its own (four rotate; reuse waits for that buffer's own upload, four versions back)
+// into the device table that the previous version does not occupy, so that a deferred encode keeps reading the one it was given
+static int rx_stream_table(sdrhip_rx *rx, unsigned ssd, const unsigned **dev)
+{
+    *dev = nullptr;
+    const unsigned *w = rx_stream_words(rx, ssd);
+    if (!w) return SDRHIP_OK;
+    if (!rx->sm_uploaded) {
+        const size_t bytes = rx->sm_words.size() * sizeof(unsigned);
+        PinnedBuf &pin = rx->sm_pin[(rx->sm_pin_sel + 1) & 3];
+        DevBuf &tab = rx->sm_dev[rx->sm_dev_sel ^ 1];
+        int rc;
+        if ((rc = pin.reserve(bytes))) return rc;
+        if ((rc = tab.reserve(bytes))) return rc;
+        memcpy(pin.p, w, bytes);
+        HIP_TRY(hipMemcpyAsync(tab.p, pin.p, bytes, hipMemcpyHostToDevice, rx->ctx->stream)); // (not counted: a table)
+        pin.mark(rx->ctx->stream);
+        rx->sm_pin_sel = (rx->sm_pin_sel + 1) & 3;
+        rx->sm_dev_sel ^= 1;
+        rx->sm_uploaded = true;
+    }
+    *dev = rx->sm_dev[rx->sm_dev_sel].as<unsigned>();
+    return SDRHIP_OK;
 }
 
 // host input of the uniform step: S rows of n_in samples of esz bytes -> [S][dstride] rows the first kernel reads.  A small call
@@ -407,6 +488,7 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
     if (started > 0) {
         // tv_sec / tv_usec = the stamp of the call's first sample
         rx_meta_base(rx->cfg, decimated_sample_size((unsigned)L, ss), meta.w);
+        if ((rc = rx_stream_table(rx, decimated_sample_size((unsigned)L, ss), &meta.tab))) return rc;
         meta.w[3] = tv_sec; meta.w[4] = tv_usec;
         meta.first = first_new; meta.count = started; meta.frame_count0 = (unsigned)rx->r_count[0] + first_new;
         meta.idx0 = first_new ? (uint64_t)SDRHIP_SAMPLES_PER_FRAME - pending : 0;
@@ -457,7 +539,7 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
         fa.n = n_dec; fa.frame_sample_base = pending; fa.frame_blocks = FB;
         fa.meta_first = meta.first; fa.meta_count = meta.count; fa.meta_frame_count0 = meta.frame_count0;
         memcpy(fa.meta_w, meta.w, sizeof(fa.meta_w));
-        fa.meta_idx0 = meta.idx0; fa.meta_rate = meta.rate;
+        fa.meta_idx0 = meta.idx0; fa.meta_rate = meta.rate; fa.meta_tab = meta.tab;
         // K2 rides in the encoder's launch when this call's frames are encoded right away by the structured encoder (one launch
         // less per step); otherwise it goes out now
         pack_with_encoder = !rx->pipelined && c->opt.rx_fused && structured && R > 0 && use_lin;
@@ -495,7 +577,7 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
                 // completes the frame that was open (its tail comes from the stream-order buffer), K2 leaves both alone
                 k.meta_first = meta.first; k.meta_count = meta.count; k.meta_frame_count0 = meta.frame_count0;
                 memcpy(k.meta_w, meta.w, sizeof(k.meta_w));
-                k.meta_idx0 = meta.idx0; k.meta_rate = meta.rate;
+                k.meta_idx0 = meta.idx0; k.meta_rate = meta.rate; k.meta_tab = meta.tab;
                 if (elin.first == 1) { k.lin_straddle = 1; fa.skip_from = 0; }
                 hipError_t e;
                 {
@@ -680,8 +762,9 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
 
     // ---- the per-call table: counts (decimator), windows and meta records (K2r)
     unsigned ss = rx->cfg.sample_bits;
-    unsigned mw[6]; // (the record with a zero stamp: shared, the config is; the stamps go per row)
+    unsigned mw[6]; // (the record with a zero stamp; the stamps go per row, and so do fc, rate and the CRC: sdrhip_rx_set_stream_meta)
     rx_meta_base(rx->cfg, decimated_sample_size((unsigned)L, ss), mw);
+    const unsigned *sw = rx_stream_words(rx, decimated_sample_size((unsigned)L, ss));
     std::vector<RaggedRow> rows((size_t)S);
     memset(rows.data(), 0, rows.size() * sizeof(RaggedRow));
     for (int s = 0; s < S; ++s) {
@@ -690,6 +773,8 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
         const int started = (int)(done[(size_t)s] + (rest[(size_t)s] > 0 ? 1 : 0)) - first_new;
         r.out_off = rx->r_base[(size_t)s] * frame_bytes / 4;
         r.frame_sample_base = rx->r_pending[(size_t)s];
+        r.fc = sw ? sw[s * STREAM_META_WORDS] : mw[0]; r.rate = sw ? sw[s * STREAM_META_WORDS + 1] : mw[1];
+        r.crc0 = sw ? sw[s * STREAM_META_WORDS + 2] : mw[5];
         if (started > 0 && (n_in[s] >> L)) {
             r.meta_first = first_new; r.meta_count = started;
             r.frame_count0 = (unsigned)rx->r_count[(size_t)s] + (unsigned)first_new;
@@ -736,7 +821,7 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
     }
     if (rc) return rc;
     rx->consumed = true;
-    if (max_dec && !direct) {
+    if (max_dec && (!direct || sw)) {
         FrameArgs fa;
         memset(&fa, 0, sizeof(fa));
         fa.in = lin.as<unsigned>(); fa.out = reinterpret_cast<unsigned *>(area);
@@ -744,7 +829,15 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
         fa.n = max_dec; fa.frame_blocks = (int)FB;
         memcpy(fa.meta_w, mw, sizeof(fa.meta_w));
         fa.meta_rate = rx->cfg.sample_rate;
-        hipError_t e = launch_frame_pack_ragged(fa, rdev, S, c->stream);
+        hipError_t e;
+        if (direct) {
+            // K1mr's pieces wrote the meta blocks with the shared record (that kernel has no register to spare for the streams'
+            // words): K2r, without samples, writes them again with each stream's own values
+            int max_started = 0;
+            for (int s = 0; s < S; ++s) if (rows[(size_t)s].meta_count > max_started) max_started = rows[(size_t)s].meta_count;
+            e = max_started ? launch_frame_meta_ragged(fa, rdev, max_started, S, c->stream) : hipSuccess;
+        } else
+            e = launch_frame_pack_ragged(fa, rdev, S, c->stream);
         if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "frame pack launch: %s", hipGetErrorString(e));
     }
 

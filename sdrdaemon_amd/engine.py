@@ -605,6 +605,34 @@ class RxPipe:
         check(self.ctx.lib.sdrhip_rx_reconfigure(self.h, C.byref(cfg)))
         self.cfg, self.nb_fec = cfg, cfg.nb_fec
 
+    def set_stream_meta(self, center_frequency_khz=None, sample_rate=None):
+        """Per-stream UDPSink::setCenterFrequency / setSampleRate (sdrhip_rx_set_stream_meta): sequences of nstreams values for
+        the frames that later launches open; None = that field is bank-wide again (the config's value).  Never synchronises."""
+        arrs = []
+        for name, v in (("center_frequency_khz", center_frequency_khz), ("sample_rate", sample_rate)):
+            if v is None:
+                arrs.append(None)
+                continue
+            v = [int(x) for x in v]
+            if len(v) != self.nstreams or any(x < 0 or x > 0xffffffff for x in v):
+                raise ValueError("%s: %d values of 32 bits, one per stream" % (name, self.nstreams))
+            arrs.append((C.c_uint32 * self.nstreams)(*v))
+        check(self.ctx.lib.sdrhip_rx_set_stream_meta(self.h, arrs[0], arrs[1]))
+
+    def stream_meta(self, stream):
+        """-> {"center_frequency_khz", "sample_rate"}: what the stream's next opened frame will carry"""
+        fc, sr = C.c_uint32(0), C.c_uint32(0)
+        check(self.ctx.lib.sdrhip_rx_get_stream_meta(self.h, int(stream), C.byref(fc), C.byref(sr)))
+        return {"center_frequency_khz": fc.value, "sample_rate": sr.value}
+
+    def follow_testsource(self, ts):
+        """What sdrdaemonrx's loop does with its source, per stream of a TestSource bank: setCenterFrequency(frequency / 1000)
+        and setSampleRate(srate >> decim) (sdrdaemonrx.cpp:597,624,644)"""
+        if ts.nstreams != self.nstreams:
+            raise ValueError("the TestSource bank has %d streams, the pipe %d" % (ts.nstreams, self.nstreams))
+        g = [ts.get(s) for s in range(self.nstreams)]
+        self.set_stream_meta([x["frequency"] // 1000 for x in g], [x["sample_rate"] >> self.cfg.log2decim for x in g])
+
     def configure(self, m):
         """The control-message keys of sdrdaemonrx (parsekv pairs): decim, fcpos (Downsampler.cpp:32-67),
         fecblk (UDPSink::setNbBlocksFEC), freq in Hz (setCenterFrequency: kHz on the wire), srate
