@@ -167,20 +167,24 @@ def test_reference_class_whole_and_cut(oracle, ctx, seed):
 
 
 def _hostile(oracle, rs, R=32, fi0=0, nframes=8):
-    fr = make_frames(oracle, rs, nframes, R, fi0)
+    """nframes frames (a multiple of 8), every eight of them the seven hostile patterns below"""
+    assert nframes % 8 == 0
+    frames = make_frames(oracle, rs, nframes, R, fi0)
     out = []
-    out += lossy(rs, fr[0], 20)                                  # plain
-    f1 = lossy(rs, fr[1], 24)
-    out += f1[:10] + f1[:10] + f1[10:]                            # identical duplicates among the first 128
-    a, b = lossy(rs, fr[2], 10), lossy(rs, fr[3], 10)
-    out += a[:60] + b[:30] + a[60:] + b[30:]                      # A B A interleaving
-    f4 = lossy(rs, fr[4], 16)
-    rs.shuffle(f4)
-    out += f4                                                     # reordered inside the frame
-    out += list(fr[5]) + list(fr[5][:40])                         # more than 128 arrivals
-    f6 = [x for x in fr[6] if x[2] != 0]
-    out += lossy(rs, f6, 20)                                      # block 0 lost (restored: no META)
-    out += lossy(rs, fr[7], R + 20)[:100]                         # incomplete, with recovery blocks
+    for g in range(0, nframes, 8):
+        fr = frames[g:g + 8]
+        out += lossy(rs, fr[0], 20)                                  # plain
+        f1 = lossy(rs, fr[1], 24)
+        out += f1[:10] + f1[:10] + f1[10:]                            # identical duplicates among the first 128
+        a, b = lossy(rs, fr[2], 10), lossy(rs, fr[3], 10)
+        out += a[:60] + b[:30] + a[60:] + b[30:]                      # A B A interleaving
+        f4 = lossy(rs, fr[4], 16)
+        rs.shuffle(f4)
+        out += f4                                                     # reordered inside the frame
+        out += list(fr[5]) + list(fr[5][:40])                         # more than 128 arrivals
+        f6 = [x for x in fr[6] if x[2] != 0]
+        out += lossy(rs, f6, 20)                                      # block 0 lost (restored: no META)
+        out += lossy(rs, fr[7], R + 20)[:100]                         # incomplete, with recovery blocks
     return out
 
 
@@ -194,6 +198,16 @@ def test_hostile_sequences(oracle, ctx, R):
     m = Model(oracle).run(dg)
     bank = sd.FECBufferBank(ctx, 1)
     got = run_bank(bank, [dg], _cuts(len(dg), 0, rs))
+    check_against_model(bank, got, [m])
+    assert any(r["flags"] & sd.engine.FECBUF_DECODE_ERROR for r in got[0][2]) or R < 32
+    # the same patterns three times over in ONE call: the classify pass walks them in chunks of 1024 datagrams
+    rs = np.random.RandomState(200 + R)
+    dg = _hostile(oracle, rs, R, fi0=65519, nframes=24)
+    dg.append(np.full(512, 0xEE, np.uint8))
+    assert len(dg) >= 2100
+    m = Model(oracle).run(dg)
+    bank = sd.FECBufferBank(ctx, 1)
+    got = run_bank(bank, [dg])
     check_against_model(bank, got, [m])
     assert any(r["flags"] & sd.engine.FECBUF_DECODE_ERROR for r in got[0][2]) or R < 32
 
