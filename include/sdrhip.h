@@ -295,8 +295,35 @@ int sdrhip_rx_reconfigure(sdrhip_rx *rx, const sdrhip_rx_config *cfg);
  * left for the next launch keep the values of the call that opened them.  A handle on which this was never called launches what it
  * launched before the call existed.  SDRHIP_EINVAL, nothing changed: a NULL handle. */
 int sdrhip_rx_set_stream_meta(sdrhip_rx *rx, const uint32_t *center_frequency_khz, const uint32_t *sample_rate);
-/* what stream s's next opened frame will carry (either pointer may be NULL); SDRHIP_EINVAL: a NULL handle, a stream outside the bank */
+/* what stream s's next opened frame will carry (either pointer may be NULL); SDRHIP_EINVAL: a NULL handle, a stream outside the bank.
+ * The host's values: the arrays above, else the config.  Values followed from the incoming meta blocks (sdrhip_rx_set_follow_meta) are
+ * never brought to the host: read them from the delivered frames, or through sdrhip_fecbuf_stats on sdrhip_rx_collector. */
 int sdrhip_rx_get_stream_meta(const sdrhip_rx *rx, int stream, uint32_t *center_frequency_khz, uint32_t *sample_rate);
+/* Outgoing meta from the incoming meta blocks, for the entries fed raw FEC datagrams (sdrhip_rx_process_datagrams,
+ * sdrhip_rx_submit_datagrams / _collect_datagrams).  sdrdaemonrx announces the frequency and the rate of its own source
+ * (sdrdaemonrx.cpp:622-631,644); a hub's source is the radio head, whose values arrive in the meta block of its frames.  on = 0 is
+ * the default.  The call sets a host-side flag only: nothing is enqueued, nothing is waited for.  Allowed at any time: it applies to
+ * later sdrhip_rx_process_datagrams calls and later sdrhip_rx_submit_datagrams submits; a batch in flight keeps the mode it was
+ * submitted with.  The sample-fed entries (sdrhip_rx_process, _ragged, _submit*) have no incoming meta and ignore the flag.
+ * With on != 0, for every datagram call or batch and every stream s:
+ *  1. the stream's m_outputMeta is taken as it stands after this call's collection: the state the call commits, what
+ *     sdrhip_fecbuf_stats(..., output_meta) reports after the call.  It is the meta block of the last frame released in this or an
+ *     earlier call whose block 0 was among its first 128 arrivals (SDRdaemonFECBuffer.cpp:72-85); a frame whose block 0 was lost and
+ *     restored by the decoder does not set it (m_metaRetrieved, SDRdaemonFECBuffer.cpp:150-153).
+ *  2. m_outputMeta.m_sampleRate != 0: the stream has incoming meta.  Every frame that this call's step opens carries
+ *     m_centerFrequency unchanged and m_sampleRate >> log2decim, with the log2decim of the configuration the call or batch runs with
+ *     (sdrdaemonrx.cpp:622-631,644).  The shifted rate is also the clock that advances the frame stamps (a shifted rate of 0: every
+ *     frame carries the call's stamp), and the CRC is that of the resulting 20-byte record.
+ *  3. otherwise (no frame released with its block 0 yet, or a sender that says rate 0) the stream keeps the values it has with the
+ *     flag off: the sdrhip_rx_set_stream_meta arrays, else the configuration.
+ *  4. a frame left open by an earlier call keeps the block 0 it was opened with (UDPSinkFEC.cpp:160-165).
+ *  5. sampleBytes, sampleBits, nbOriginalBlocks, nbFECBlocks and the stamps stay the hub's own: the reference stamps a frame with
+ *     gettimeofday where it is opened (UDPSinkFEC.cpp:90-104), so the caller's tv_sec / tv_usec arrays remain right.
+ *  6. sdrhip_rx_get_stream_meta keeps reporting the host's values.
+ * The values are formed on the device between the collector and the step (one small launch per call or batch); nothing about them
+ * comes back to the host, and a submit still synchronises nothing.  With the flag off every entry launches exactly what it launched
+ * before the call existed.  SDRHIP_EINVAL, nothing changed: a NULL handle. */
+int sdrhip_rx_set_follow_meta(sdrhip_rx *rx, int on);
 /* Feeds n_in device-rate samples per stream.  Completed frames of stream s are written to
  * frames_out + s*frame_stride_bytes as (128 + nb_fec) super blocks of 512 bytes each,
  * frame after frame; *n_frames (per stream, identical for all streams) is the number of

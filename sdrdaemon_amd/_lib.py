@@ -41,6 +41,7 @@ EXPORTS = [
     "sdrhip_rx_process_datagrams", "sdrhip_rx_collector", "sdrhip_rx_carry",
     "sdrhip_rx_submit_datagrams", "sdrhip_rx_collect_datagrams",
     "sdrhip_rx_set_stream_meta", "sdrhip_rx_get_stream_meta",
+    "sdrhip_rx_set_follow_meta",
 ]
 
 
@@ -157,6 +158,7 @@ def load():
     lib.sdrhip_rx_collect_datagrams.argtypes = [vp, vp, sz, sz, sz, vp, C.POINTER(sz), C.POINTER(sz), i]
     lib.sdrhip_rx_set_stream_meta.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.sdrhip_rx_get_stream_meta.argtypes = [vp, i, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    lib.sdrhip_rx_set_follow_meta.argtypes = [vp, i]
     lib.sdrhip_testsource_create.argtypes = [vp, i, C.POINTER(vp)]
     lib.sdrhip_testsource_destroy.argtypes = [vp]
     lib.sdrhip_testsource_destroy.restype = None

@@ -499,6 +499,8 @@ int fecbuf_join_carry(sdrhip_fecbuf *b, unsigned **dev, std::vector<size_t> **ho
     *host = &b->join_carry_host;
     return SDRHIP_OK;
 }
+
+const FecBufState *fecbuf_committed_state(const sdrhip_fecbuf *b) { return b->state[b->cur]; }
 } // namespace sdrhip
 
 extern "C" int sdrhip_fecbuf_stats(sdrhip_fecbuf *b, int stream, int *cur_nb_blocks, int *cur_nb_recovery, int *min_nb_blocks, int *max_nb_recovery,

@@ -134,6 +134,9 @@ int fecbuf_collect(sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgra
 // the samples every stream of the collector's owner (an Rx handle) holds back between datagram calls: [nstreams] on the device
 // (KJ keeps it) and the host's copy; created zero on first use, zeroed by sdrhip_fecbuf_reset
 int fecbuf_join_carry(sdrhip_fecbuf *b, unsigned **dev, std::vector<size_t> **host);
+// the committed half of the collector's double-buffered state, [nstreams] on the device: what launches enqueued behind the
+// collector's passes of a call read (KF: m_outputMeta); the next call writes the other half
+const FecBufState *fecbuf_committed_state(const sdrhip_fecbuf *b);
 // asynchronous Tx / Rx batches (sdrhip_tx_submit_datagrams, sdrhip_rx_submit_datagrams): the host's shadow of the classification part
 // of a stream's FecBufState
 struct FecBufShadow {

@@ -529,6 +529,10 @@ hipError_t launch_fecbuf_scatter_rows(const FecBufArgs &a, const unsigned *row_o
 hipError_t launch_fecbuf_copy_rows(const FecBufArgs &a, const unsigned *row_off, int nslots, hipStream_t stream);
 hipError_t launch_rx_join_carry(int16_t *rows, size_t row_len, unsigned *carry, const int *counts, unsigned unit, int nstreams,
                                 hipStream_t stream);
+// KF (rx_follow_kernels.hip, sdrhip_rx_set_follow_meta): one lane per stream; a stream whose committed m_outputMeta (state[s].out_meta)
+// carries a sample rate other than 0 gets {fc, rate >> log2decim, CRC of the zero-stamp record with third word w2} in rows[s]
+// (device: the per-call table, behind its upload); the others keep their row
+hipError_t launch_rx_follow_meta(const FecBufState *state, RaggedRow *rows, unsigned w2, int log2decim, int nstreams, hipStream_t stream);
 // asynchronous Tx batches (sdrhip_tx_submit_datagrams): stream s's datagrams back to back at a.dg + dg_off[s] (device); njobs /
 // nslots come from the host's shadow of the classification; the scatter pass skips what lies past the classify pass's own counts,
 // max_frames or nslots, the guarded copy a slot whose dmap entry is still -1 (preset by the caller)

@@ -188,6 +188,9 @@ struct sdrhip_rx {
     sdrhip_fecbuf *fb = nullptr;
     sdrhip::DevBuf j_rows;
     size_t j_row_len = 0;
+    // ---- outgoing meta from the incoming meta blocks (sdrhip_rx_set_follow_meta): a host flag, read by the datagram entries per call
+    // and per batch at its submit; KF (rx_follow_kernels.hip) then rewrites the rows of the streams that have incoming meta
+    int follow_meta = 0;
 };
 
 // --------------------------------------------------------------------------- fused Tx pipe
@@ -280,10 +283,11 @@ inline size_t rx_join_unit(const sdrhip_rx_config &cfg)
 int rx_join_rows(sdrhip_rx *rx, size_t max_released, const char *who);
 // the ragged step (sdrhip_rx_process_ragged).  batch: a ragged asynchronous batch (rx_launch_ragged): int16 device rows that K0p
 // laid out, whatever the input format.  dev_rows: iq_in is int16 device rows whatever `mem` and the input format are (the datagram
-// entry's rows); `mem` then speaks of frames_out alone
+// entry's rows); `mem` then speaks of frames_out alone.  follow (the datagram entries with sdrhip_rx_set_follow_meta on): the collector's
+// committed state on the device; KF forms the meta words of the streams that have incoming meta from it, behind the table's upload
 int rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, size_t in_stride, const uint32_t *tv_sec, const uint32_t *tv_usec,
               uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem, bool batch = false, bool dev_rows = false,
-              RxTabs *tabs = nullptr);
+              RxTabs *tabs = nullptr, const FecBufState *follow = nullptr);
 // everything the ragged step allocates for these counts, ahead of it (a caller that must not fail between two launches): the frame
 // area (grown behind a synchronisation), the tables, the frame list, and the stream-order rows when the decimator cannot store
 // straight into the windows.  rx_ragged itself then allocates nothing, unless a matrix-core plan it counted on does not apply

@@ -287,6 +287,15 @@ extern "C" int sdrhip_rx_set_stream_meta(sdrhip_rx *rx, const uint32_t *center_f
     return SDRHIP_OK;
 }
 
+// ---- outgoing meta from the incoming meta blocks: the flag alone (the datagram entries read it per call / per submit)
+extern "C" int sdrhip_rx_set_follow_meta(sdrhip_rx *rx, int on)
+{
+    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
+    sdrhip::CtxLock lock_(rx->ctx);
+    rx->follow_meta = on ? 1 : 0;
+    return SDRHIP_OK;
+}
+
 extern "C" int sdrhip_rx_get_stream_meta(const sdrhip_rx *rx, int stream, uint32_t *center_frequency_khz, uint32_t *sample_rate)
 {
     if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
@@ -695,7 +704,8 @@ int sdrhip::rx_ragged_room(sdrhip_rx *rx, const size_t *n_in, RxTabs *tabs)
 // own window -> one encoder launch over the list of every stream's completed frames.  A call that fails after it moved windows
 // leaves r_base moved (the open frames lie there now) and the rest of the framing state untouched.
 int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, size_t in_stride, const uint32_t *tv_sec, const uint32_t *tv_usec,
-                      uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem, bool batch, bool dev_rows, RxTabs *tabs)
+                      uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem, bool batch, bool dev_rows, RxTabs *tabs,
+                      const FecBufState *follow)
 {
     sdrhip_ctx *c = rx->ctx;
     const int S = rx->nstreams, L = rx->cfg.log2decim, R = rx->cfg.nb_fec;
@@ -784,6 +794,13 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
     }
     const RaggedRow *rdev = nullptr;
     if ((rc = ragged_prepare(rx->dec, L, rx->cfg.fcpos, n_in, rows.data(), &rdev, tabs ? &tabs->rows : nullptr))) return rc;
+    if (follow) {
+        // KF: the streams that have incoming meta get {fc, rate >> L, CRC} from the collector's committed m_outputMeta, in the device
+        // table, behind its upload and in front of K2r, the one kernel that reads a row's three words (the host's rows, `mw` and the
+        // rate handed to the decimator launch stay the configuration's)
+        hipError_t e = launch_rx_follow_meta(follow, const_cast<RaggedRow *>(rdev), mw[2], L, S, c->stream);
+        if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "follow meta launch: %s", hipGetErrorString(e));
+    }
 
     // ---- input: host rows staged stream by stream (n_in[s] samples each), 8-bit rows widened by K0r
     const int16_t *din = iq_in;
@@ -821,7 +838,7 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
     }
     if (rc) return rc;
     rx->consumed = true;
-    if (max_dec && (!direct || sw)) {
+    if (max_dec && (!direct || sw || follow)) {
         FrameArgs fa;
         memset(&fa, 0, sizeof(fa));
         fa.in = lin.as<unsigned>(); fa.out = reinterpret_cast<unsigned *>(area);
@@ -832,7 +849,7 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
         hipError_t e;
         if (direct) {
             // K1mr's pieces wrote the meta blocks with the shared record (that kernel has no register to spare for the streams'
-            // words): K2r, without samples, writes them again with each stream's own values
+            // words): K2r, without samples, writes them again with each stream's own values (the host's arrays, or KF's)
             int max_started = 0;
             for (int s = 0; s < S; ++s) if (rows[(size_t)s].meta_count > max_started) max_started = rows[(size_t)s].meta_count;
             e = max_started ? launch_frame_meta_ragged(fa, rdev, max_started, S, c->stream) : hipSuccess;

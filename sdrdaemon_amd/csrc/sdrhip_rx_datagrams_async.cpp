@@ -137,7 +137,7 @@ extern "C" int sdrhip_rx_submit_datagrams(sdrhip_rx *rx, const uint8_t *dgrams, 
     // ---- decimate, frame, encode: one ragged step; KJ moves every row's remainder to its head (the device's own counts)
     if (any) {
         if ((rc = rx_ragged(rx, rx->j_rows.as<int16_t>(), fed.data(), rx->j_row_len, tv_sec, tv_usec, nullptr, 0, nf.data(), SDRHIP_MEM_DEVICE,
-                            true, true, &b.d_tabs)))
+                            true, true, &b.d_tabs, rx->follow_meta ? fecbuf_committed_state(rx->fb) : nullptr))) // (the flag as it stands at this submit)
             return rx_batch_lost(rc);
         hipError_t e = launch_rx_join_carry(rx->j_rows.as<int16_t>(), rx->j_row_len, carry_dev, counts, (unsigned)U, S, c->stream);
         if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "rx join launch: %s (the batch is lost)", hipGetErrorString(e));

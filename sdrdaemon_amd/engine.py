@@ -625,6 +625,14 @@ class RxPipe:
         check(self.ctx.lib.sdrhip_rx_get_stream_meta(self.h, int(stream), C.byref(fc), C.byref(sr)))
         return {"center_frequency_khz": fc.value, "sample_rate": sr.value}
 
+    def set_follow_meta(self, on=True):
+        """Outgoing meta from the incoming meta blocks (sdrhip_rx_set_follow_meta), for process_datagrams / submit_datagrams: a
+        stream whose collector holds a meta block with a sample rate other than 0 announces that block's centre frequency and its
+        rate >> log2decim in the frames later calls and submits open; the others keep the host's values.  A host flag: never
+        synchronises, a batch in flight keeps the mode of its submit.  stream_meta() keeps reporting the host's values: the
+        followed ones are in the delivered frames, and in collector_stats(s)["output_meta"]."""
+        check(self.ctx.lib.sdrhip_rx_set_follow_meta(self.h, 1 if on else 0))
+
     def follow_testsource(self, ts):
         """What sdrdaemonrx's loop does with its source, per stream of a TestSource bank: setCenterFrequency(frequency / 1000)
         and setSampleRate(srate >> decim) (sdrdaemonrx.cpp:597,624,644)"""
