@@ -188,7 +188,7 @@ int cm256_decode_plan(int k, int recovery_count_param, const uint8_t *indices, i
             row[rec_pos[i]] = a;
             if (!a) continue;
             const uint8_t *ma = g.mul[a];
-            const uint8_t *e = &E[(size_t)i * orig_pos.size()];
+            const uint8_t *e = E.data() + (size_t)i * orig_pos.size(); // (E is empty when every original is lost: no operator[] on it)
             for (size_t q = 0; q < orig_pos.size(); ++q) row[orig_pos[q]] ^= ma[e[q]];
         }
     }

@@ -13,90 +13,12 @@ not on this machine (FEC parity stays "unpinned": tests/test_oracle_vs_ref_cm256
 import numpy as np
 import pytest
 
-
-def _clmul_mod(a, b, poly):
-    r = 0
-    while b:
-        if b & 1:
-            r ^= a
-        a <<= 1
-        if a & 0x100:
-            a ^= poly
-        b >>= 1
-    return r
-
-
-def _x_is_primitive(poly):
-    # x generates the multiplicative group iff its order is 255 (then the polynomial is irreducible as well)
-    v, n = 2, 1
-    while v != 1:
-        v = _clmul_mod(v, 2, poly)
-        n += 1
-        if n > 255:
-            return False
-    return n == 255
+from cm256_spec import GEOMETRIES, _clmul_mod, _encode, _matrix, _solve, _x_is_primitive, arrival, field, pick  # noqa: F401  (the derivation itself: tests/cm256_spec.py)
 
 
 @pytest.fixture(scope="module")
 def spec():
-    prim = [p for p in range(0x101, 0x200, 2) if _x_is_primitive(p)]
-    assert len(prim) == 16  # phi(255) / 8
-    poly = prim[3]          # fact (A)
-    mul = np.zeros((256, 256), np.uint8)
-    for a in range(256):
-        for b in range(a, 256):
-            mul[a, b] = mul[b, a] = _clmul_mod(a, b, poly)
-    inv = np.zeros(256, np.uint8)
-    for a in range(1, 256):
-        inv[a] = int(np.nonzero(mul[a] == 1)[0][0])
-    return poly, mul, inv
-
-
-def _matrix(spec, k, m):
-    _, mul, inv = spec
-    a = np.zeros((m, k), np.uint8)
-    for i in range(m):
-        for j in range(k):
-            a[i, j] = mul[j ^ k, inv[(k + i) ^ j]]  # fact (B)
-    return a
-
-
-def _encode(spec, x, m):
-    _, mul, _ = spec
-    a = _matrix(spec, x.shape[0], m)
-    rec = np.zeros((m, x.shape[1]), np.uint8)
-    for i in range(m):
-        for j in range(x.shape[0]):
-            rec[i] ^= mul[a[i, j]][x[j]]
-    return rec
-
-
-def _solve(spec, k, rows, data):
-    """originals from any k of the k + m blocks: rows[t] = block index (< k: original, >= k: recovery row - k), data[t] its bytes."""
-    _, mul, inv = spec
-    m = max([r - k + 1 for r in rows if r >= k] + [1])
-    a = _matrix(spec, k, m)
-    g = np.zeros((k, k), np.uint8)
-    for t, r in enumerate(rows):
-        if r < k:
-            g[t, r] = 1
-        else:
-            g[t] = a[r - k]
-    g, d = g.copy(), data.copy()
-    for c in range(k):  # Gauss-Jordan over GF(2^8)
-        p = next(t for t in range(c, k) if g[t, c])
-        if p != c:
-            g[[c, p]] = g[[p, c]]
-            d[[c, p]] = d[[p, c]]
-        s = inv[g[c, c]]
-        g[c] = mul[s][g[c]]
-        d[c] = mul[s][d[c]]
-        for t in range(k):
-            if t != c and g[t, c]:
-                f = g[t, c]
-                g[t] ^= mul[f][g[c]]
-                d[t] ^= mul[f][d[c]]
-    return d
+    return field()
 
 
 def test_polynomial_is_the_fourth_primitive_one(spec, oracle):
@@ -232,3 +154,84 @@ def test_product_decode_plan_solves_the_specification_s_system(spec, product_hos
                 v ^= mul[c[i, p]][data[p]]
         assert np.array_equal(v, x[er[i]]), (case, i)
         assert idx[rec_pos[i]] >= k  # restored INTO a recovery descriptor (cm256_decode's in-place contract)
+
+
+def _plan(product_host, k, m, idx):
+    """cm256_decode_plan with buffers of exactly the sizes sdrhip_cm256_decode gives it -> (rc, n_rec, rec_pos, erased, coef)"""
+    import ctypes as C
+
+    idx = np.ascontiguousarray(idx, np.uint8)
+    assert idx.shape == (k,)
+    n_rec = C.c_int(-1)
+    rec_pos, er, coef = np.full(k, 0xEE, np.uint8), np.full(256, 0xEE, np.uint8), np.full((k, k), 0xEE, np.uint8)
+    rc = product_host["plan"](k, m, idx.ctypes.data, C.byref(n_rec), rec_pos.ctypes.data, er.ctypes.data, coef.ctypes.data)
+    return rc, n_rec.value, rec_pos, er, coef
+
+
+def _apply(spec, coef_row, data):
+    _, mul, _ = spec
+    v = np.zeros(data.shape[1], np.uint8)
+    for p in range(data.shape[0]):
+        if coef_row[p]:
+            v ^= mul[coef_row[p]][data[p]]
+    return v
+
+
+@pytest.mark.parametrize("k,m,n", GEOMETRIES, ids=["%d+%d_lose%d" % g for g in GEOMETRIES])
+def test_product_decode_plan_at_generic_geometry(spec, product_host, k, m, n):
+    """The plan behind sdrhip_cm256_decode at every OriginalCount the test above leaves out (it stays at 128): recovery rows from
+    anywhere in 0 .. m - 1, arrival order fully shuffled, blocks encoded by the SPECIFICATION.  erased[] is the ascending list of the
+    missing originals, rec_pos[] lists the recovery descriptors in arrival order (cm256_decode's in-place contract: the i-th of them
+    ends holding erased[i]), and coefficient row i applied with the specification's multiplication gives back original erased[i]."""
+    rs = np.random.RandomState(9000 + 300 * k + m)
+    bb = 5
+    x = rs.randint(0, 256, size=(k, bb)).astype(np.uint8)
+    allb = np.concatenate([x, _encode(spec, x, m)])
+    erased, rows = pick(rs, k, m, n, include=(0, k - 1) if n >= 2 and (k + m) % 2 else ())
+    idx = arrival(rs, k, erased, rows, "shuffled")
+    data = allb[idx]
+    rc, n_rec, rec_pos, er, coef = _plan(product_host, k, m, idx)
+    assert rc == 0 and n_rec == n
+    assert er[:n].tolist() == erased
+    assert rec_pos[:n].tolist() == [p for p in range(k) if idx[p] >= k]
+    c = coef.reshape(-1)[: n * k].reshape(n, k)
+    for i in range(n):
+        assert np.array_equal(_apply(spec, c[i], data), x[er[i]]), (k, m, i)
+    assert np.all(coef.reshape(-1)[n * k:] == 0xEE) and np.all(rec_pos[n:] == 0xEE) and np.all(er[n:] == 0xEE)  # nothing written behind
+
+
+@pytest.mark.parametrize("k", [10, 200])
+@pytest.mark.parametrize("row", [0, 2])
+def test_product_decode_plan_recovery_count_one(spec, product_host, k, row):
+    """recovery_count_param == 1 is upstream's DecodeM1: one coefficient row of ones over the received originals and the recovery
+    block, whatever that block's row (only row 0, the parity row, then gives back the original)."""
+    rs = np.random.RandomState(40 + k + row)
+    x = rs.randint(0, 256, size=(k, 7)).astype(np.uint8)
+    allb = np.concatenate([x, _encode(spec, x, row + 1)])
+    lost = int(rs.randint(k))
+    idx = arrival(rs, k, [lost], [row], "shuffled")
+    rc, n_rec, rec_pos, er, coef = _plan(product_host, k, 1, idx)
+    assert rc == 0 and n_rec == 1 and er[0] == lost and idx[rec_pos[0]] == k + row
+    assert np.all(coef[0] == 1) and np.all(coef[1:] == 0xEE)
+    assert np.array_equal(_apply(spec, coef[0], allb[idx]), x[lost]) == (row == 0)
+
+
+@pytest.mark.parametrize("k,m", [(7, 3), (200, 56)])
+def test_product_decode_plan_without_erasures(product_host, k, m):
+    idx = np.random.RandomState(k).permutation(k)
+    rc, n_rec, rec_pos, er, coef = _plan(product_host, k, m, idx)
+    assert rc == 0 and n_rec == 0
+    assert np.all(coef == 0xEE) and np.all(rec_pos == 0xEE) and np.all(er == 0xEE)
+
+
+def test_product_decode_plan_refuses_what_it_cannot_solve(product_host):
+    """a repeated original is upstream's Initialize() failure; the same recovery row twice makes the Cauchy block singular (upstream
+    does not notice, the plan does)"""
+    k, m = 10, 4
+    idx = np.arange(k)
+    idx[3] = 2
+    idx[9] = k + 1
+    assert _plan(product_host, k, m, idx)[0] == -5
+    idx = np.arange(k)
+    idx[4] = idx[8] = k + 3
+    assert _plan(product_host, k, m, idx)[0] == -5
