@@ -35,8 +35,136 @@ struct sdrhip_fecbuf {
 namespace {
 constexpr size_t PAYLOAD = (size_t)127 * SDRHIP_BLOCK_BYTES;
 
-// byte offset of the per-stream counts ([S][FB_COUNTS]) in `small`, behind [ndg S][job_off S + 1][dbase S][pad] ints and rec_base (int64)
-size_t counts_offset(int S) { return (((size_t)3 * S + 2 + 3) & ~(size_t)3) * 4 + (size_t)S * 8; }
+// the per-call table of a driver, as byte offsets that hold for the host's copy and the device's alike.  The host fills and
+// uploads [0, upload): ints [ndg S][job_off S + 1][dbase S] (packed: [expect S x 4]) [pad], then int64 rec_base [S] (packed:
+// dg_off [S]).  Behind them the device alone has the counts [S][FB_COUNTS] and the public records [S][max_frames]
+struct FecBufTable {
+    bool packed;
+    size_t ndg, job_off, dbase, expect, rec_base, dg_off, counts, pub;
+    size_t upload, total;
+};
+FecBufTable fecbuf_table(int S, size_t max_frames, bool packed)
+{
+    const size_t n = (size_t)S;
+    FecBufTable t;
+    t.packed = packed;
+    t.ndg = 0; t.job_off = n * 4; t.dbase = (2 * n + 1) * 4; t.expect = (3 * n + 1) * 4;
+    // (the synchronous table has neither expect nor dg_off; it keeps the one spare int it always had in front of its padding)
+    t.rec_base = (((packed ? 7 * n + 1 : 3 * n + 2) + 3) & ~(size_t)3) * 4;
+    t.dg_off = t.rec_base + n * 8;
+    t.counts = t.dg_off + (packed ? n * 8 : 0);
+    t.pub = t.counts + n * FB_COUNTS * 4;
+    t.upload = t.counts;
+    t.total = t.pub + n * max_frames * sizeof(FecBufPub);
+    return t;
+}
+template <class T> T *at(void *base, size_t off) { return reinterpret_cast<T *>(static_cast<uint8_t *>(base) + off); }
+
+// what a call brings, into the host's table: ndg, rec_base, packed: dg_off; returns the internal records the call needs
+long long table_inputs(const FecBufTable &t, void *host, const size_t *n_dgrams, int S)
+{
+    int *ndg = at<int>(host, t.ndg);
+    long long *rb = at<long long>(host, t.rec_base), *doff = at<long long>(host, t.dg_off);
+    long long nrec = 0, off = 0;
+    for (int s = 0; s < S; ++s) {
+        ndg[s] = (int)n_dgrams[s];
+        rb[s] = nrec; nrec += (long long)n_dgrams[s] + 1;
+        if (t.packed) { doff[s] = off; off += (long long)(n_dgrams[s] * SDRHIP_UDPSIZE); }
+    }
+    return nrec;
+}
+
+// what the classification gives, into the host's table: the prefix sums job_off and dbase (packed: expect, for the shadow check)
+// over stream s's {K, D, maxrow, maxrec} at x + s * stride (the read-back counts, or the shadow's res); returns the grids and
+// the batch's highest recovery row and count
+struct FecBufSums {
+    int njobs, nslots, maxrow, maxrec;
+};
+FecBufSums table_sums(const FecBufTable &t, void *host, const int *x, size_t stride, int S)
+{
+    int *job_off = at<int>(host, t.job_off), *dbase = at<int>(host, t.dbase), *expect = at<int>(host, t.expect);
+    FecBufSums n = {0, 0, -1, 0};
+    for (int s = 0; s < S; ++s, x += stride) {
+        job_off[s] = n.njobs; n.njobs += x[FB_K] + 1;
+        dbase[s] = n.nslots; n.nslots += x[FB_D];
+        for (int q = 0; t.packed && q < 4; ++q) expect[4 * s + q] = x[q];
+        n.maxrow = x[FB_MAXROW] > n.maxrow ? x[FB_MAXROW] : n.maxrow;
+        n.maxrec = x[FB_MAXREC] > n.maxrec ? x[FB_MAXREC] : n.maxrec;
+    }
+    job_off[S] = n.njobs;
+    return n;
+}
+
+// the kernels' arguments but the decoder's scratch (fecbuf_scratch): the table at `dev`, the records, the state and the carry
+FecBufArgs fecbuf_args(const sdrhip_fecbuf *b, const FecBufTable &t, uint8_t *dev, const uint8_t *dg, size_t dg_stride, uint8_t *data_out,
+                       size_t data_stride, uint8_t *block0_out, size_t max_frames)
+{
+    FecBufArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dg = dg; a.dg_stride = dg_stride;
+    a.ndg = at<const int>(dev, t.ndg);
+    a.job_off = at<const int>(dev, t.job_off);
+    a.dbase = at<const int>(dev, t.dbase);
+    a.rec_base = at<const long long>(dev, t.rec_base);
+    a.counts = at<int>(dev, t.counts);
+    a.pub = at<FecBufPub>(dev, t.pub);
+    a.rec = b->rec.as<FecBufRec>();
+    a.max_frames = (int)max_frames;
+    a.st_cur = b->state[b->cur]; a.st_next = b->state[b->cur ^ 1];
+    a.carry_cur_base = b->carry; a.carry_base = b->carry;
+    a.nstreams = b->nstreams;
+    a.data_out = data_out; a.data_stride = data_stride; a.block0_out = block0_out;
+    return a;
+}
+
+// everything that can fail for want of memory before the state moves on: staging, map and decoder output of nslots frames
+// (settled, asynchronous batches: a buffer that grows waits for the batches in flight)
+int fecbuf_scratch(sdrhip_fecbuf *b, FecBufArgs &a, int nslots, bool settled)
+{
+    if (nslots <= 0) return SDRHIP_OK; // (a.stage .. a.dec_b0 stay NULL: no job has a staging slot)
+    sdrhip_ctx *c = b->ctx;
+    const size_t n = (size_t)nslots;
+    auto grow = [&](DevBuf &d, size_t bytes) { return settled ? reserve_settled(c, d, bytes) : d.reserve(bytes); };
+    int rc;
+    if ((rc = grow(b->stage, n * 128 * SDRHIP_UDPSIZE))) return rc;
+    if ((rc = grow(b->dmap, n * 2 * sizeof(int)))) return rc;
+    if ((rc = grow(b->dec_out, n * PAYLOAD))) return rc;
+    if (a.block0_out && (rc = grow(b->dec_b0, n * SDRHIP_BLOCK_BYTES))) return rc;
+    a.stage = b->stage.as<uint8_t>(); a.dmap = b->dmap.as<int>();
+    a.dec_out = b->dec_out.as<uint8_t>(); a.dec_b0 = a.block0_out ? b->dec_b0.as<uint8_t>() : nullptr;
+    return SDRHIP_OK;
+}
+
+// tables known, scratch reserved: the scatter pass, the commit, the batched decoder on the frames that need it and the copy of
+// its output to the frames' places.  dg_off (device): the packed passes (else the strided ones); join: their row forms.  next /
+// committed (asynchronous batches): the shadow the commit moves to, and whether it happened (a failure behind it loses the batch)
+int fecbuf_passes(sdrhip_fecbuf *b, const FecBufArgs &a, const long long *dg_off, const FecBufJoin *join, const FecBufSums &n,
+                  const std::vector<FecBufShadow> *next, bool *committed)
+{
+    sdrhip_ctx *c = b->ctx;
+    const unsigned *row_off = join ? join->row_off : nullptr;
+    const int kind = (dg_off ? 2 : 0) | (join ? 1 : 0);
+    hipError_t e = kind == 3   ? launch_fecbuf_scatter_packed_rows(a, dg_off, row_off, n.njobs, n.nslots, c->stream)
+                   : kind == 2 ? launch_fecbuf_scatter_packed(a, dg_off, n.njobs, n.nslots, c->stream)
+                   : kind == 1 ? launch_fecbuf_scatter_rows(a, row_off, n.njobs, c->stream)
+                               : launch_fecbuf_scatter(a, n.njobs, c->stream);
+    if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "fecbuf scatter launch: %s", hipGetErrorString(e));
+    b->cur ^= 1; // (committed: the scatter pass has written the new carry slots)
+    if (next) b->shadow = *next;
+    if (committed) *committed = true;
+    if (n.nslots <= 0) return SDRHIP_OK;
+    // the promise is the batch's highest collected row, never a count: <= 32 rows (indices 0..31) take the one-launch decoder
+    const int max_rows = (n.maxrow < 32 && n.maxrec <= 32) ? 32 : 128;
+    if (int rc = fec_decode_device(c, b->stage.as<uint8_t>(), (size_t)128 * SDRHIP_UDPSIZE, nullptr, (size_t)n.nslots, b->dec_out.as<uint8_t>(), PAYLOAD,
+                                   a.block0_out ? b->dec_b0.as<uint8_t>() : nullptr, nullptr, nullptr, max_rows))
+        return rc;
+    e = kind == 3   ? launch_fecbuf_copy_guarded_rows(a, row_off, n.nslots, c->stream)
+        : kind == 2 ? launch_fecbuf_copy_guarded(a, n.nslots, c->stream)
+        : kind == 1 ? launch_fecbuf_copy_rows(a, row_off, n.nslots, c->stream)
+                    : launch_fecbuf_copy(a, n.nslots, c->stream);
+    if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "fecbuf copy launch: %s", hipGetErrorString(e));
+    return SDRHIP_OK;
+}
 
 int fecbuf_init_state(sdrhip_fecbuf *b)
 {
@@ -67,71 +195,33 @@ int fecbuf_device(sdrhip_fecbuf *b, const uint8_t *dg, const size_t *n_dgrams, s
     const int S = b->nstreams;
     int rc;
     b->shadow_ok = false; // (the collector moves without the host's shadow)
-    // small per-call arrays: [ndg S][job_off S + 1][dbase S][pad] ints, then rec_base (int64), counts, public records
-    const size_t ints = ((size_t)3 * S + 2 + 3) & ~(size_t)3;
-    const size_t off_rb = ints * 4, off_cnt = counts_offset(S), off_pub = off_cnt + (size_t)S * FB_COUNTS * 4;
-    const size_t small_bytes = off_pub + (size_t)S * max_frames * sizeof(FecBufPub);
-    if ((rc = b->small.reserve(small_bytes))) return rc;
-    if ((rc = b->pin_up.reserve(off_cnt))) return rc;
-    if ((rc = b->pin_down.reserve(small_bytes - off_cnt))) return rc;
-    int *up = b->pin_up.as<int>();
-    long long *rb = reinterpret_cast<long long *>(b->pin_up.as<uint8_t>() + off_rb);
-    long long nrec = 0;
-    for (int s = 0; s < S; ++s) {
-        up[s] = (int)n_dgrams[s];
-        rb[s] = nrec;
-        nrec += (long long)n_dgrams[s] + 1;
-    }
+    const FecBufTable t = fecbuf_table(S, max_frames, false);
+    if ((rc = b->small.reserve(t.total))) return rc;
+    if ((rc = b->pin_up.reserve(t.upload))) return rc;
+    if ((rc = b->pin_down.reserve(t.total - t.counts))) return rc;
+    const long long nrec = table_inputs(t, b->pin_up.p, n_dgrams, S);
     if ((rc = b->rec.reserve((size_t)nrec * sizeof(FecBufRec)))) return rc;
     uint8_t *sm = b->small.as<uint8_t>();
-    HIP_TRY(link_copy(c, sm, b->pin_up.p, off_cnt, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(link_copy(c, sm, b->pin_up.p, t.upload, hipMemcpyHostToDevice, c->stream));
     b->pin_up.mark(c->stream);
 
-    FecBufArgs a;
-    memset(&a, 0, sizeof(a));
-    a.dg = dg; a.dg_stride = dg_stride;
-    a.ndg = reinterpret_cast<const int *>(sm);
-    a.job_off = reinterpret_cast<const int *>(sm) + S;
-    a.dbase = reinterpret_cast<const int *>(sm) + 2 * S + 1;
-    a.rec_base = reinterpret_cast<const long long *>(sm + off_rb);
-    a.counts = reinterpret_cast<int *>(sm + off_cnt);
-    a.pub = reinterpret_cast<FecBufPub *>(sm + off_pub);
-    a.rec = b->rec.as<FecBufRec>();
-    a.max_frames = (int)max_frames;
-    a.st_cur = b->state[b->cur]; a.st_next = b->state[b->cur ^ 1];
-    a.carry_cur_base = b->carry; a.carry_base = b->carry;
-    a.nstreams = S;
-    a.data_out = data_out; a.data_stride = data_stride; a.block0_out = block0_out;
+    FecBufArgs a = fecbuf_args(b, t, sm, dg, dg_stride, data_out, data_stride, block0_out, max_frames);
     hipError_t e = launch_fecbuf_classify(a, c->stream);
     if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "fecbuf classify launch: %s", hipGetErrorString(e));
     // the one read-back: counts + public records
-    HIP_TRY(link_copy(c, b->pin_down.p, sm + off_cnt, small_bytes - off_cnt, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(link_copy(c, b->pin_down.p, sm + t.counts, t.total - t.counts, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const int *cnt = b->pin_down.as<int>();
-    const FecBufPub *pub = reinterpret_cast<const FecBufPub *>(b->pin_down.as<uint8_t>() + (off_pub - off_cnt));
+    const FecBufPub *pub = at<const FecBufPub>(b->pin_down.p, t.pub - t.counts);
     bool room = true;
-    int njobs = 0, nslots = 0, maxrow = -1, maxrec = 0;
     for (int s = 0; s < S; ++s) {
-        const int *x = cnt + (size_t)s * FB_COUNTS;
-        n_frames[s] = (size_t)x[FB_K];
-        if ((size_t)x[FB_K] > max_frames) room = false;
-        up[S + s] = njobs;
-        up[2 * S + 1 + s] = nslots;
-        njobs += x[FB_K] + 1;
-        nslots += x[FB_D];
-        if (x[FB_MAXROW] > maxrow) maxrow = x[FB_MAXROW];
-        if (x[FB_MAXREC] > maxrec) maxrec = x[FB_MAXREC];
+        n_frames[s] = (size_t)cnt[(size_t)s * FB_COUNTS + FB_K];
+        if (n_frames[s] > max_frames) room = false;
     }
-    up[2 * S] = njobs;
+    const FecBufSums n = table_sums(t, b->pin_up.p, cnt, FB_COUNTS, S);
     if (!room) return fail(SDRHIP_EINVAL, "fecbuf_write_and_read: a stream releases more than max_frames = %zu frames (n_frames has the counts; nothing was consumed)", max_frames);
     if (join && join->admit && (rc = join->admit(join->arg, n_frames))) return rc;
-    // everything that can fail for want of memory before the state moves on
-    if (nslots > 0) {
-        if ((rc = b->stage.reserve((size_t)nslots * 128 * SDRHIP_UDPSIZE))) return rc;
-        if ((rc = b->dmap.reserve((size_t)nslots * 2 * sizeof(int)))) return rc;
-        if ((rc = b->dec_out.reserve((size_t)nslots * PAYLOAD))) return rc;
-        if (block0_out && (rc = b->dec_b0.reserve((size_t)nslots * SDRHIP_BLOCK_BYTES))) return rc;
-    }
+    if ((rc = fecbuf_scratch(b, a, n.nslots, false))) return rc;
     for (int s = 0; s < S; ++s) {
         const FecBufPub *p = pub + (size_t)s * max_frames;
         for (size_t k = 0; k < n_frames[s]; ++k) {
@@ -139,23 +229,10 @@ int fecbuf_device(sdrhip_fecbuf *b, const uint8_t *dg, const size_t *n_dgrams, s
             o.frame_index = p[k].frame_index; o.block_count = p[k].block_count; o.recovery_count = p[k].recovery_count; o.flags = p[k].flags;
         }
     }
-    HIP_TRY(link_copy(c, sm + (size_t)S * 4, up + S, ((size_t)2 * S + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    // (job_off and dbase: the columns the read-back filled)
+    HIP_TRY(link_copy(c, sm + t.job_off, b->pin_up.as<uint8_t>() + t.job_off, t.expect - t.job_off, hipMemcpyHostToDevice, c->stream));
     b->pin_up.mark(c->stream);
-    a.stage = b->stage.as<uint8_t>(); a.dmap = b->dmap.as<int>();
-    a.dec_out = b->dec_out.as<uint8_t>(); a.dec_b0 = block0_out ? b->dec_b0.as<uint8_t>() : nullptr;
-    e = join ? launch_fecbuf_scatter_rows(a, join->row_off, njobs, c->stream) : launch_fecbuf_scatter(a, njobs, c->stream);
-    if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "fecbuf scatter launch: %s", hipGetErrorString(e));
-    b->cur ^= 1; // (committed: the scatter pass has written the new carry slots)
-    if (nslots > 0) {
-        // the promise is the batch's highest collected row, never a count: <= 32 rows (indices 0..31) take the one-launch decoder
-        const int max_rows = (maxrow < 32 && maxrec <= 32) ? 32 : 128;
-        if ((rc = fec_decode_device(c, b->stage.as<uint8_t>(), (size_t)128 * SDRHIP_UDPSIZE, nullptr, (size_t)nslots, b->dec_out.as<uint8_t>(), PAYLOAD,
-                                    block0_out ? b->dec_b0.as<uint8_t>() : nullptr, nullptr, nullptr, max_rows)))
-            return rc;
-        e = join ? launch_fecbuf_copy_rows(a, join->row_off, nslots, c->stream) : launch_fecbuf_copy(a, nslots, c->stream);
-        if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "fecbuf copy launch: %s", hipGetErrorString(e));
-    }
-    return SDRHIP_OK;
+    return fecbuf_passes(b, a, nullptr, join, n, nullptr, nullptr);
 }
 } // namespace
 
@@ -212,15 +289,24 @@ extern "C" int sdrhip_fecbuf_reset(sdrhip_fecbuf *b)
 }
 
 namespace {
+// the counts of one call / batch (`unit` names it in the message): *sum = all datagrams, *nmax = the most of a stream
+int count_dgrams(int S, const size_t *n_dgrams, const char *who, const char *unit, size_t *sum, size_t *nmax)
+{
+    *sum = *nmax = 0;
+    for (int s = 0; s < S; ++s) {
+        if (n_dgrams[s] > 0x3fffffffu) return fail(SDRHIP_EINVAL, "%s: too many datagrams in one %s", who, unit);
+        *sum += n_dgrams[s];
+        *nmax = n_dgrams[s] > *nmax ? n_dgrams[s] : *nmax;
+    }
+    return SDRHIP_OK;
+}
+
 // the datagram arguments of a call (sdrhip_fecbuf_write_and_read, sdrhip_tx_process_datagrams); *nmax = the most datagrams of a stream
 int check_dgrams(int S, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes, int mem, const char *who, size_t *nmax)
 {
     if (int e = check_mem(mem)) return e;
-    *nmax = 0;
-    for (int s = 0; s < S; ++s) {
-        if (n_dgrams[s] > 0x3fffffffu) return fail(SDRHIP_EINVAL, "%s: too many datagrams in one call", who);
-        *nmax = n_dgrams[s] > *nmax ? n_dgrams[s] : *nmax;
-    }
+    size_t sum = 0;
+    if (int e = count_dgrams(S, n_dgrams, who, "call", &sum, nmax)) return e;
     if (*nmax > 0 && !dgrams) return fail(SDRHIP_EINVAL, "%s: NULL dgrams", who);
     if (S > 1 && *nmax > 0 && dgram_stride_bytes < *nmax * SDRHIP_UDPSIZE) return fail(SDRHIP_EINVAL, "%s: dgram_stride_bytes below n_dgrams x 512", who);
     return SDRHIP_OK;
@@ -279,24 +365,20 @@ extern "C" int sdrhip_fecbuf_write_and_read(sdrhip_fecbuf *b, const uint8_t *dgr
             return fail(SDRHIP_EALIGN, "fecbuf_write_and_read: dgrams / dgram_stride_bytes must be 16-byte aligned");
         if ((reinterpret_cast<uintptr_t>(data_out) & 3u) || (reinterpret_cast<uintptr_t>(block0_out) & 3u) || (S > 1 && data_stride_bytes % 4))
             return fail(SDRHIP_EALIGN, "fecbuf_write_and_read: data_out / block0_out / data_stride_bytes must be 4-byte aligned");
-        return fecbuf_device(b, dgrams, n_dgrams, dgram_stride_bytes, data_out, data_stride_bytes, block0_out, max_frames, info_out, n_frames);
     }
-    // host memory: the datagrams go up as one 2-D copy (from sdrhip_host_alloc memory in place, else through a pinned buffer)
-    const size_t row = nmax * SDRHIP_UDPSIZE, drow = max_frames * PAYLOAD;
-    if (drow && (rc = b->hout.reserve((size_t)S * drow + 4))) return rc;
-    if (block0_out && max_frames && (rc = b->hb0.reserve((size_t)S * max_frames * SDRHIP_BLOCK_BYTES))) return rc;
-    if ((rc = upload_dgrams(b, dgrams, n_dgrams, dgram_stride_bytes, row))) return rc;
-    if ((rc = fecbuf_device(b, b->hin.as<uint8_t>(), n_dgrams, row, b->hout.as<uint8_t>(), drow, block0_out ? b->hb0.as<uint8_t>() : nullptr,
-                            max_frames, info_out, n_frames)))
-        return rc;
-    for (int s = 0; s < S; ++s) {
-        if (!n_frames[s]) continue;
-        HIP_TRY(link_copy(c, data_out + (size_t)s * data_stride_bytes, b->hout.as<uint8_t>() + (size_t)s * drow,
-                          n_frames[s] * PAYLOAD, hipMemcpyDeviceToHost, c->stream));
-        if (block0_out)
-            HIP_TRY(link_copy(c, block0_out + (size_t)s * max_frames * SDRHIP_BLOCK_BYTES, b->hb0.as<uint8_t>() + (size_t)s * max_frames * SDRHIP_BLOCK_BYTES,
-                              n_frames[s] * SDRHIP_BLOCK_BYTES, hipMemcpyDeviceToHost, c->stream));
-    }
+    // both memories go through fecbuf_collect (host: it stages the datagrams and downloads block 0).  Host memory adds only what its
+    // other callers do not need, their data staying on the device: the frames go to b->hout and come down from there below
+    const bool host = mem == SDRHIP_MEM_HOST;
+    const size_t drow = max_frames * PAYLOAD;
+    if (host && drow && (rc = b->hout.reserve((size_t)S * drow + 4))) return rc;
+    const int *counts = nullptr;
+    rc = fecbuf_collect(b, dgrams, n_dgrams, dgram_stride_bytes, mem, host ? b->hout.as<uint8_t>() : data_out, host ? drow : data_stride_bytes,
+                        block0_out, max_frames, info_out, n_frames, &counts);
+    if (rc || !host) return rc;
+    for (int s = 0; s < S; ++s)
+        if (n_frames[s])
+            HIP_TRY(link_copy(c, data_out + (size_t)s * data_stride_bytes, b->hout.as<uint8_t>() + (size_t)s * drow, n_frames[s] * PAYLOAD,
+                              hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SDRHIP_OK;
 }
@@ -336,7 +418,7 @@ int fecbuf_collect(sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgra
                                       n_frames[s] * SDRHIP_BLOCK_BYTES, hipMemcpyDeviceToHost, c->stream));
     }
     if (rc) return rc;
-    *counts = reinterpret_cast<const int *>(b->small.as<uint8_t>() + counts_offset(S));
+    *counts = at<const int>(b->small.p, fecbuf_table(S, max_frames, false).counts);
     return SDRHIP_OK;
 }
 } // namespace sdrhip
@@ -399,6 +481,73 @@ void fecbuf_shadow_run(FecBufShadow &h, const uint8_t *dg, size_t n, int res[4])
     res[0] = K; res[1] = D; res[2] = maxrow; res[3] = maxrec;
 }
 
+// ---- a batch of sdrhip_tx_submit_datagrams / sdrhip_rx_submit_datagrams (`who`) on its way up
+int fecbuf_batch_check(FecBufBatch *in, int S, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes, const char *who)
+{
+    in->S = S; in->dgrams = dgrams; in->n_dgrams = n_dgrams; in->stride = dgram_stride_bytes;
+    if (int e = count_dgrams(S, n_dgrams, who, "batch", &in->sum, &in->nmax)) return e;
+    in->packed = dgram_stride_bytes == SDRHIP_PACKED || S == 1;
+    in->bytes_in = in->sum * SDRHIP_UDPSIZE;
+    in->inplace = false;
+    if (in->sum && !dgrams) return fail(SDRHIP_EINVAL, "%s: NULL dgrams", who);
+    if (!in->packed && dgram_stride_bytes < in->nmax * SDRHIP_UDPSIZE)
+        return fail(SDRHIP_EINVAL, "%s: dgram_stride_bytes is neither SDRHIP_PACKED nor at least the largest count x 512", who);
+    return SDRHIP_OK;
+}
+
+// stream s's row in the caller's memory; off = the bytes of the streams in front of it
+static const uint8_t *row_of(const FecBufBatch &in, int s, size_t off)
+{
+    return in.packed ? in.dgrams + off : in.dgrams + (size_t)s * in.stride;
+}
+
+int fecbuf_batch_stage(FecBufBatch *in, PinnedBuf &arena, std::vector<FecBufShadow> &sh, int *res)
+{
+    const int S = in->S;
+    in->inplace = in->sum && host_is_pinned(in->dgrams, in->packed ? in->bytes_in : (size_t)(S - 1) * in->stride + in->nmax * SDRHIP_UDPSIZE);
+    if (in->sum && !in->inplace)
+        if (int rc = arena.reserve(in->bytes_in)) return rc; // (waits for the upload of this slot's last batch)
+    size_t off = 0;
+    for (int s = 0; s < S; ++s) {
+        const size_t nb = in->n_dgrams[s] * SDRHIP_UDPSIZE;
+        const uint8_t *src = row_of(*in, s, off);
+        if (nb && !in->inplace) {
+            memcpy(arena.as<uint8_t>() + off, src, nb);
+            src = arena.as<uint8_t>() + off;
+        }
+        fecbuf_shadow_run(sh[(size_t)s], src, in->n_dgrams[s], res + (size_t)s * 4);
+        off += nb;
+    }
+    return SDRHIP_OK;
+}
+
+int fecbuf_batch_upload(sdrhip_ctx *c, const FecBufBatch &in, PinnedBuf &arena, uint8_t *pk)
+{
+    if (in.sum && !in.inplace) {
+        HIP_TRY(link_copy(c, pk, arena.p, in.bytes_in, hipMemcpyHostToDevice, c->stream));
+        arena.mark(c->stream);
+    } else if (in.sum) {
+        size_t off = 0;
+        for (int s = 0; s < in.S;) {
+            const uint8_t *p0 = row_of(in, s, off);
+            size_t n = in.n_dgrams[s] * SDRHIP_UDPSIZE;
+            int j = s + 1;
+            // (packed input is one run; a strided row joins the next one when it fills its stride)
+            for (; j < in.S && p0 + n == row_of(in, j, off + n); ++j) n += in.n_dgrams[j] * SDRHIP_UDPSIZE;
+            if (n) HIP_TRY(link_copy(c, pk + off, p0, n, hipMemcpyHostToDevice, c->stream));
+            off += n;
+            s = j;
+        }
+    }
+    return SDRHIP_OK;
+}
+
+int fecbuf_batch_lost(const char *who, int rc)
+{
+    const std::string m = sdrhip_last_error();
+    return fail(rc, "%s: %s (the batch is lost)", who, m.c_str());
+}
+
 int fecbuf_packed(sdrhip_fecbuf *b, const uint8_t *dg, const size_t *n_dgrams, const int *res, const std::vector<FecBufShadow> &next,
                   PinnedBuf &tab, uint8_t *data_out, size_t data_stride, uint8_t *block0_out, size_t max_frames, unsigned *mismatch,
                   bool *committed, const int **counts, const FecBufPub **pub, const FecBufJoin *join)
@@ -407,79 +556,25 @@ int fecbuf_packed(sdrhip_fecbuf *b, const uint8_t *dg, const size_t *n_dgrams, c
     const int S = b->nstreams;
     int rc;
     *committed = false;
-    // tables: [ndg S][job_off S + 1][dbase S][expect S x 4][pad] ints, rec_base [S], dg_off [S] (int64); on the device the counts
-    // [S][FB_COUNTS] and the public records [S][max_frames] follow
-    const size_t ints = ((size_t)7 * S + 1 + 3) & ~(size_t)3;
-    const size_t off_rb = ints * 4, off_do = off_rb + (size_t)S * 8, off_cnt = off_do + (size_t)S * 8;
-    const size_t off_pub = off_cnt + (size_t)S * FB_COUNTS * 4, bytes = off_pub + (size_t)S * max_frames * sizeof(FecBufPub);
-    if ((rc = tab.reserve(off_cnt))) return rc; // (waits for the upload of this batch slot's last use)
-    int *ndg = tab.as<int>(), *job_off = ndg + S, *dbase = job_off + S + 1, *expect = dbase + S;
-    long long *rb = reinterpret_cast<long long *>(tab.as<uint8_t>() + off_rb), *doff = reinterpret_cast<long long *>(tab.as<uint8_t>() + off_do);
-    long long nrec = 0, off = 0;
-    int njobs = 0, nslots = 0, maxrow = -1, maxrec = 0;
-    for (int s = 0; s < S; ++s) {
-        const int *x = res + 4 * s;
-        ndg[s] = (int)n_dgrams[s];
-        rb[s] = nrec; nrec += (long long)n_dgrams[s] + 1;
-        doff[s] = off; off += (long long)(n_dgrams[s] * SDRHIP_UDPSIZE);
-        job_off[s] = njobs; njobs += x[0] + 1;
-        dbase[s] = nslots; nslots += x[1];
-        for (int q = 0; q < 4; ++q) expect[4 * s + q] = x[q];
-        maxrow = x[2] > maxrow ? x[2] : maxrow;
-        maxrec = x[3] > maxrec ? x[3] : maxrec;
-    }
-    job_off[S] = njobs;
-    // everything that can fail for want of memory before the state moves on (a buffer that grows waits for the batches in flight)
-    if ((rc = reserve_settled(c, b->atab, bytes))) return rc;
+    const FecBufTable t = fecbuf_table(S, max_frames, true);
+    if ((rc = tab.reserve(t.upload))) return rc; // (waits for the upload of this batch slot's last use)
+    const long long nrec = table_inputs(t, tab.p, n_dgrams, S);
+    const FecBufSums n = table_sums(t, tab.p, res, 4, S);
+    // (a buffer that grows waits for the batches in flight)
+    if ((rc = reserve_settled(c, b->atab, t.total))) return rc;
     if ((rc = reserve_settled(c, b->rec, (size_t)nrec * sizeof(FecBufRec)))) return rc;
-    if (nslots > 0) {
-        if ((rc = reserve_settled(c, b->stage, (size_t)nslots * 128 * SDRHIP_UDPSIZE))) return rc;
-        if ((rc = reserve_settled(c, b->dmap, (size_t)nslots * 2 * sizeof(int)))) return rc;
-        if ((rc = reserve_settled(c, b->dec_out, (size_t)nslots * PAYLOAD))) return rc;
-        if (block0_out && (rc = reserve_settled(c, b->dec_b0, (size_t)nslots * SDRHIP_BLOCK_BYTES))) return rc;
-    }
-    uint8_t *t = b->atab.as<uint8_t>();
-    HIP_TRY(hipMemcpyAsync(t, tab.p, off_cnt, hipMemcpyHostToDevice, c->stream)); // (not counted: a table)
+    uint8_t *dev = b->atab.as<uint8_t>();
+    FecBufArgs a = fecbuf_args(b, t, dev, dg, 0, data_out, data_stride, block0_out, max_frames);
+    if ((rc = fecbuf_scratch(b, a, n.nslots, true))) return rc;
+    HIP_TRY(hipMemcpyAsync(dev, tab.p, t.upload, hipMemcpyHostToDevice, c->stream)); // (not counted: a table)
     tab.mark(c->stream);
-    FecBufArgs a;
-    memset(&a, 0, sizeof(a));
-    a.dg = dg; a.dg_stride = 0;
-    a.ndg = reinterpret_cast<const int *>(t);
-    a.job_off = a.ndg + S;
-    a.dbase = a.job_off + S + 1;
-    a.rec_base = reinterpret_cast<const long long *>(t + off_rb);
-    a.counts = reinterpret_cast<int *>(t + off_cnt);
-    a.pub = reinterpret_cast<FecBufPub *>(t + off_pub);
-    a.rec = b->rec.as<FecBufRec>();
-    a.max_frames = (int)max_frames;
-    a.st_cur = b->state[b->cur]; a.st_next = b->state[b->cur ^ 1];
-    a.carry_cur_base = b->carry; a.carry_base = b->carry;
-    a.nstreams = S;
-    a.data_out = data_out; a.data_stride = data_stride; a.block0_out = block0_out;
-    a.stage = nslots ? b->stage.as<uint8_t>() : nullptr; a.dmap = nslots ? b->dmap.as<int>() : nullptr;
-    a.dec_out = nslots ? b->dec_out.as<uint8_t>() : nullptr; a.dec_b0 = nslots && block0_out ? b->dec_b0.as<uint8_t>() : nullptr;
-    const long long *dg_off = reinterpret_cast<const long long *>(t + off_do);
+    const long long *dg_off = at<const long long>(dev, t.dg_off);
     hipError_t e = launch_fecbuf_classify_packed(a, dg_off, c->stream);
     if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "fecbuf classify launch: %s", hipGetErrorString(e));
-    if ((e = launch_fecbuf_shadow_check(a.counts, reinterpret_cast<const int *>(t) + 3 * S + 1, S, mismatch, c->stream)) != hipSuccess)
+    if ((e = launch_fecbuf_shadow_check(a.counts, at<const int>(dev, t.expect), S, mismatch, c->stream)) != hipSuccess)
         return fail(SDRHIP_EDEVICE, "fecbuf shadow check launch: %s", hipGetErrorString(e));
-    if (nslots > 0) HIP_TRY(hipMemsetAsync(a.dmap, 0xff, (size_t)nslots * 2 * sizeof(int), c->stream)); // (the guarded copy skips what stays -1)
-    e = join ? launch_fecbuf_scatter_packed_rows(a, dg_off, join->row_off, njobs, nslots, c->stream)
-             : launch_fecbuf_scatter_packed(a, dg_off, njobs, nslots, c->stream);
-    if (e != hipSuccess)
-        return fail(SDRHIP_EDEVICE, "fecbuf scatter launch: %s", hipGetErrorString(e));
-    b->cur ^= 1; // (committed: the scatter pass has written the new carry slots)
-    b->shadow = next;
-    *committed = true;
-    if (nslots > 0) {
-        // the promise is the batch's highest collected row, never a count (as fecbuf_device)
-        const int max_rows = (maxrow < 32 && maxrec <= 32) ? 32 : 128;
-        if ((rc = fec_decode_device(c, b->stage.as<uint8_t>(), (size_t)128 * SDRHIP_UDPSIZE, nullptr, (size_t)nslots, b->dec_out.as<uint8_t>(), PAYLOAD,
-                                    block0_out ? b->dec_b0.as<uint8_t>() : nullptr, nullptr, nullptr, max_rows)))
-            return rc;
-        e = join ? launch_fecbuf_copy_guarded_rows(a, join->row_off, nslots, c->stream) : launch_fecbuf_copy_guarded(a, nslots, c->stream);
-        if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "fecbuf copy launch: %s", hipGetErrorString(e));
-    }
+    if (n.nslots > 0) HIP_TRY(hipMemsetAsync(a.dmap, 0xff, (size_t)n.nslots * 2 * sizeof(int), c->stream)); // (the guarded copy skips what stays -1)
+    if ((rc = fecbuf_passes(b, a, dg_off, join, n, &next, committed))) return rc;
     *counts = a.counts;
     *pub = a.pub;
     return SDRHIP_OK;

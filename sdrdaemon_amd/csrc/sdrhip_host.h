@@ -159,6 +159,27 @@ void fecbuf_shadow_run(FecBufShadow &h, const uint8_t *dg, size_t n, int res[4])
 int fecbuf_packed(sdrhip_fecbuf *b, const uint8_t *dg, const size_t *n_dgrams, const int *res, const std::vector<FecBufShadow> &next,
                   PinnedBuf &tab, uint8_t *data_out, size_t data_stride, uint8_t *block0_out, size_t max_frames, unsigned *mismatch,
                   bool *committed, const int **counts, const FecBufPub **pub, const FecBufJoin *join = nullptr);
+// a batch of an asynchronous datagram-fed pipe on its way up (sdrhip_tx_submit_datagrams, sdrhip_rx_submit_datagrams; `who` in the
+// messages).  fecbuf_batch_check: the count limit, NULL dgrams and the SDRHIP_PACKED / stride rule; it fills `in` (nothing consumed).
+// fecbuf_batch_stage: one memcpy per non-empty stream into the batch's pinned `arena`, packed (not at all where the caller's memory
+// is pinned: in->inplace), and the shadow `sh` run over every stream's headers: res [S][4].  fecbuf_batch_upload: exactly the
+// datagrams to pk (device), packed -- staged: one copy; in place: one per run of adjacent rows
+struct FecBufBatch {
+    int S;
+    const uint8_t *dgrams;
+    const size_t *n_dgrams;
+    size_t stride;
+    bool packed, inplace;       // packed: the rows lie back to back (SDRHIP_PACKED, or one stream), else row s at dgrams + s * stride
+    size_t sum, nmax, bytes_in; // all datagrams, the most of a stream, sum x 512
+};
+int fecbuf_batch_check(FecBufBatch *in, int S, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes, const char *who);
+int fecbuf_batch_stage(FecBufBatch *in, PinnedBuf &arena, std::vector<FecBufShadow> &sh, int *res);
+int fecbuf_batch_upload(sdrhip_ctx *c, const FecBufBatch &in, PinnedBuf &arena, uint8_t *pk);
+// a failure behind the collector's scatter launch: the batch is consumed and lost, never replayed
+int fecbuf_batch_lost(const char *who, int rc);
+// a public record as a batch delivers it
+constexpr size_t DG_REC = sizeof(sdrhip_fecbuf_frame);
+static_assert(sizeof(sdrhip_fecbuf_frame) == sizeof(FecBufPub), "public record layout");
 // DevBuf::reserve behind a synchronisation of the context's stream when the buffer grows (it frees the old one, which batches in
 // flight may still use)
 inline int reserve_settled(sdrhip_ctx *c, DevBuf &b, size_t n);

@@ -11,17 +11,6 @@
 
 using namespace sdrhip;
 
-namespace {
-constexpr size_t DG_REC = sizeof(sdrhip_fecbuf_frame);
-static_assert(sizeof(sdrhip_fecbuf_frame) == sizeof(FecBufPub), "public record layout");
-// a failure behind the collector's scatter launch: the batch is consumed and lost, never replayed
-int rx_batch_lost(int rc)
-{
-    const std::string m = sdrhip_last_error();
-    return fail(rc, "rx_submit_datagrams: %s (the batch is lost)", m.c_str());
-}
-} // namespace
-
 extern "C" int sdrhip_rx_submit_datagrams(sdrhip_rx *rx, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes,
                                           const uint32_t *tv_sec, const uint32_t *tv_usec)
 {
@@ -30,16 +19,9 @@ extern "C" int sdrhip_rx_submit_datagrams(sdrhip_rx *rx, const uint8_t *dgrams, 
     sdrhip::CtxLock lock_(rx->ctx);
     // ---- everything that can be refused is checked before anything is consumed
     const int S = rx->nstreams, L = rx->cfg.log2decim;
-    size_t sum = 0, nmax = 0;
-    for (int s = 0; s < S; ++s) {
-        if (n_dgrams[s] > 0x3fffffffu) return fail(SDRHIP_EINVAL, "rx_submit_datagrams: too many datagrams in one batch");
-        sum += n_dgrams[s];
-        nmax = n_dgrams[s] > nmax ? n_dgrams[s] : nmax;
-    }
-    const bool packed = dgram_stride_bytes == SDRHIP_PACKED || S == 1;
-    if (sum && !dgrams) return fail(SDRHIP_EINVAL, "rx_submit_datagrams: NULL dgrams");
-    if (!packed && dgram_stride_bytes < nmax * SDRHIP_UDPSIZE)
-        return fail(SDRHIP_EINVAL, "rx_submit_datagrams: dgram_stride_bytes is neither SDRHIP_PACKED nor at least the largest count x 512");
+    const char *who = "rx_submit_datagrams";
+    FecBufBatch in;
+    if (int e = fecbuf_batch_check(&in, S, dgrams, n_dgrams, dgram_stride_bytes, who)) return e;
     if (rx->pipelined) return fail(SDRHIP_EINVAL, "rx_submit_datagrams: not available in pipelined mode");
     if (rx_has_batches(rx, false) || rx_has_batches(rx, true))
         return fail(SDRHIP_EINVAL, "rx_submit_datagrams: uniform or ragged batches are being filled or in flight: collect them first");
@@ -56,24 +38,8 @@ extern "C" int sdrhip_rx_submit_datagrams(sdrhip_rx *rx, const uint8_t *dgrams, 
     if ((rc = fecbuf_shadow(rx->fb, &sh))) return rc;
 
     // ---- staging: packed, one memcpy per non-empty stream (in place: the caller's pinned memory); the shadow runs over the headers
-    const size_t bytes_in = sum * SDRHIP_UDPSIZE;
-    auto row_of = [&](int s, size_t off) { return packed ? dgrams + off : dgrams + (size_t)s * dgram_stride_bytes; };
-    const bool inplace = sum && (packed ? host_is_pinned(dgrams, bytes_in) : host_is_pinned(dgrams, (size_t)(S - 1) * dgram_stride_bytes + nmax * SDRHIP_UDPSIZE));
-    if (sum && !inplace && (rc = b.in.reserve(bytes_in))) return rc; // (waits for the upload of this slot's last batch)
     std::vector<int> res((size_t)S * 4);
-    {
-        size_t off = 0;
-        for (int s = 0; s < S; ++s) {
-            const size_t nb = n_dgrams[s] * SDRHIP_UDPSIZE;
-            const uint8_t *src = row_of(s, off);
-            if (nb && !inplace) {
-                memcpy(b.in.as<uint8_t>() + off, src, nb);
-                src = b.in.as<uint8_t>() + off;
-            }
-            fecbuf_shadow_run(sh[(size_t)s], src, n_dgrams[s], &res[(size_t)s * 4]);
-            off += nb;
-        }
-    }
+    if ((rc = fecbuf_batch_stage(&in, b.in, sh, res.data()))) return rc;
     // ---- every count of the batch, from the shadow's release counts and the host's copy of the carry: what each stream feeds its
     // decimator, what it holds back, the frames it completes (as rx_ragged counts them)
     const size_t U = rx_join_unit(rx->cfg), fb = (size_t)(SDRHIP_NB_ORIGINAL + rx->cfg.nb_fec) * SDRHIP_UDPSIZE;
@@ -96,8 +62,8 @@ extern "C" int sdrhip_rx_submit_datagrams(sdrhip_rx *rx, const uint8_t *dgrams, 
     // batches in flight; the rows keep their heads): the batch's own buffers, then what the ragged step takes for these counts
     // (rx_ragged_room: frame area, tables, frame list; it names the one allocation it cannot foresee).  The pinned tables are the ring slot's own, so that what a submit waits
     // for is this slot's previous batch -- which the caller has collected -- and never the batch before it
-    if (sum && (rc = reserve_settled(c, rx->a_pk, bytes_in + 16))) return rc;
-    if (kmax && (rc = rx_join_rows(rx, kmax, "rx_submit_datagrams"))) return rc;
+    if (in.sum && (rc = reserve_settled(c, rx->a_pk, in.bytes_in + 16))) return rc;
+    if (kmax && (rc = rx_join_rows(rx, kmax, who))) return rc;
     if (b_total && (rc = reserve_settled(c, rx->a_frames, b_total + 16))) return rc;
     if ((rc = reserve_settled(c, rx->a_tab, seg_bytes))) return rc;
     if (b_total && (rc = b.out.reserve(b_total))) return rc;
@@ -107,22 +73,7 @@ extern "C" int sdrhip_rx_submit_datagrams(sdrhip_rx *rx, const uint8_t *dgrams, 
 
     // ---- upload: exactly the datagrams (staged: one copy; in place: one per run of adjacent rows)
     uint8_t *pk = rx->a_pk.as<uint8_t>();
-    if (sum && !inplace) {
-        HIP_TRY(link_copy(c, pk, b.in.p, bytes_in, hipMemcpyHostToDevice, c->stream));
-        b.in.mark(c->stream);
-    } else if (sum) {
-        size_t off = 0;
-        for (int s = 0; s < S;) {
-            const uint8_t *p0 = row_of(s, off);
-            size_t n = n_dgrams[s] * SDRHIP_UDPSIZE;
-            int j = s + 1;
-            // (packed input is one run; a strided row joins the next one when it fills its stride)
-            for (; j < S && p0 + n == row_of(j, off + n); ++j) n += n_dgrams[j] * SDRHIP_UDPSIZE;
-            if (n) HIP_TRY(link_copy(c, pk + off, p0, n, hipMemcpyHostToDevice, c->stream));
-            off += n;
-            s = j;
-        }
-    }
+    if ((rc = fecbuf_batch_upload(c, in, b.in, pk))) return rc;
 
     // ---- the collector's passes, no read-back, the payloads behind each row's carry (from the scatter launch on, the batch is
     // consumed: a failure loses it)
@@ -133,12 +84,12 @@ extern "C" int sdrhip_rx_submit_datagrams(sdrhip_rx *rx, const uint8_t *dgrams, 
     rc = fecbuf_packed(rx->fb, pk, n_dgrams, res.data(), sh, b.r_tab, kmax ? rx->j_rows.as<uint8_t>() : nullptr, rx->j_row_len * 4, nullptr, kmax,
                        c->dec_stats + DEC_STATS_SHADOW_MISMATCH, &committed, &counts, &pub, &join);
     if (rc && !committed) return rc; // (nothing consumed)
-    if (rc) return rx_batch_lost(rc);
+    if (rc) return fecbuf_batch_lost(who, rc);
     // ---- decimate, frame, encode: one ragged step; KJ moves every row's remainder to its head (the device's own counts)
     if (any) {
         if ((rc = rx_ragged(rx, rx->j_rows.as<int16_t>(), fed.data(), rx->j_row_len, tv_sec, tv_usec, nullptr, 0, nf.data(), SDRHIP_MEM_DEVICE,
                             true, true, &b.d_tabs, rx->follow_meta ? fecbuf_committed_state(rx->fb) : nullptr))) // (the flag as it stands at this submit)
-            return rx_batch_lost(rc);
+            return fecbuf_batch_lost(who, rc);
         hipError_t e = launch_rx_join_carry(rx->j_rows.as<int16_t>(), rx->j_row_len, carry_dev, counts, (unsigned)U, S, c->stream);
         if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "rx join launch: %s (the batch is lost)", hipGetErrorString(e));
         *carry = left;

@@ -125,17 +125,6 @@ extern "C" int sdrhip_tx_collect(sdrhip_tx *tx, int16_t *iq_out, size_t out_stri
 // sdrhip_host_alloc memory), the collector's passes with grids from the host's shadow of the classification (fecbuf_packed: no
 // read-back), the decoder, the interpolator at the factor in force, the delivery gather, ONE download of exactly the delivered
 // bytes.  The collector and the histories are the ones sdrhip_tx_process_datagrams and sdrhip_tx_process use.
-namespace {
-constexpr size_t DG_REC = sizeof(sdrhip_fecbuf_frame);
-static_assert(sizeof(sdrhip_fecbuf_frame) == sizeof(FecBufPub), "public record layout");
-// a failure behind the collector's scatter launch: the batch is consumed and lost, never replayed
-int tx_batch_lost(int rc)
-{
-    const std::string m = sdrhip_last_error();
-    return fail(rc, "tx_submit_datagrams: %s (the batch is lost)", m.c_str());
-}
-} // namespace
-
 extern "C" int sdrhip_tx_submit_datagrams(sdrhip_tx *tx, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes)
 {
     if (!tx) return fail(SDRHIP_EINVAL, "tx is NULL");
@@ -143,16 +132,9 @@ extern "C" int sdrhip_tx_submit_datagrams(sdrhip_tx *tx, const uint8_t *dgrams, 
     sdrhip::CtxLock lock_(tx->ctx);
     // ---- everything that can be refused is checked before anything is consumed
     const int S = tx->nstreams;
-    size_t sum = 0, nmax = 0;
-    for (int s = 0; s < S; ++s) {
-        if (n_dgrams[s] > 0x3fffffffu) return fail(SDRHIP_EINVAL, "tx_submit_datagrams: too many datagrams in one batch");
-        sum += n_dgrams[s];
-        nmax = n_dgrams[s] > nmax ? n_dgrams[s] : nmax;
-    }
-    const bool packed = dgram_stride_bytes == SDRHIP_PACKED || S == 1;
-    if (sum && !dgrams) return fail(SDRHIP_EINVAL, "tx_submit_datagrams: NULL dgrams");
-    if (!packed && dgram_stride_bytes < nmax * SDRHIP_UDPSIZE)
-        return fail(SDRHIP_EINVAL, "tx_submit_datagrams: dgram_stride_bytes is neither SDRHIP_PACKED nor at least the largest count x 512");
+    const char *who = "tx_submit_datagrams";
+    FecBufBatch in;
+    if (int e = fecbuf_batch_check(&in, S, dgrams, n_dgrams, dgram_stride_bytes, who)) return e;
     if (tx->pipelined) return fail(SDRHIP_EINVAL, "tx_submit_datagrams: the handle is in pipelined mode");
     if (tx->late.have) return fail(SDRHIP_EINVAL, "tx_submit_datagrams: a pipelined batch waits: sdrhip_tx_flush it first");
     if (tx_in_flight(tx, false)) return fail(SDRHIP_EINVAL, "tx_submit_datagrams: batches of received frames are in flight: sdrhip_tx_collect them first");
@@ -166,24 +148,8 @@ extern "C" int sdrhip_tx_submit_datagrams(sdrhip_tx *tx, const uint8_t *dgrams, 
     if ((rc = fecbuf_shadow(tx->fb, &sh))) return rc;
 
     // ---- staging: packed, one memcpy per non-empty stream (in place: the caller's pinned memory); the shadow runs over the headers
-    const size_t bytes_in = sum * SDRHIP_UDPSIZE;
-    auto row_of = [&](int s, size_t off) { return packed ? dgrams + off : dgrams + (size_t)s * dgram_stride_bytes; };
-    const bool inplace = sum && (packed ? host_is_pinned(dgrams, bytes_in) : host_is_pinned(dgrams, (size_t)(S - 1) * dgram_stride_bytes + nmax * SDRHIP_UDPSIZE));
-    if (sum && !inplace && (rc = b.in.reserve(bytes_in))) return rc; // (waits for the upload of this slot's last batch)
     std::vector<int> res((size_t)S * 4);
-    {
-        size_t off = 0;
-        for (int s = 0; s < S; ++s) {
-            const size_t nb = n_dgrams[s] * SDRHIP_UDPSIZE;
-            const uint8_t *src = row_of(s, off);
-            if (nb && !inplace) {
-                memcpy(b.in.as<uint8_t>() + off, src, nb);
-                src = b.in.as<uint8_t>() + off;
-            }
-            fecbuf_shadow_run(sh[(size_t)s], src, n_dgrams[s], &res[(size_t)s * 4]);
-            off += nb;
-        }
-    }
+    if ((rc = fecbuf_batch_stage(&in, b.in, sh, res.data()))) return rc;
     size_t kmax = 0, kall = 0;
     for (int s = 0; s < S; ++s) {
         kmax = (size_t)res[(size_t)s * 4] > kmax ? (size_t)res[(size_t)s * 4] : kmax;
@@ -196,7 +162,7 @@ extern "C" int sdrhip_tx_submit_datagrams(sdrhip_tx *tx, const uint8_t *dgrams, 
     const size_t b_samples = kall * n_one * esz, b_total = b_samples + kall * (DG_REC + SDRHIP_BLOCK_BYTES);
     // everything that can fail for want of memory comes before the collector moves (a device buffer that grows waits for the
     // batches in flight)
-    if (sum && (rc = reserve_settled(c, tx->a_pk, bytes_in + 16))) return rc;
+    if (in.sum && (rc = reserve_settled(c, tx->a_pk, in.bytes_in + 16))) return rc;
     if (kmax && !direct && (rc = reserve_settled(c, tx->a_pay, (size_t)S * pitch * 4 + 16))) return rc;
     if (kmax && (rc = reserve_settled(c, tx->a_out, (size_t)S * dos * esz + 16))) return rc;
     if (kmax && (rc = reserve_settled(c, tx->a_b0, (size_t)S * kmax * SDRHIP_BLOCK_BYTES + 16))) return rc;
@@ -208,22 +174,7 @@ extern "C" int sdrhip_tx_submit_datagrams(sdrhip_tx *tx, const uint8_t *dgrams, 
 
     // ---- upload: exactly the datagrams (staged: one copy; in place: one per run of adjacent rows)
     uint8_t *pk = tx->a_pk.as<uint8_t>();
-    if (sum && !inplace) {
-        HIP_TRY(link_copy(c, pk, b.in.p, bytes_in, hipMemcpyHostToDevice, c->stream));
-        b.in.mark(c->stream);
-    } else if (sum) {
-        size_t off = 0;
-        for (int s = 0; s < S;) {
-            const uint8_t *p0 = row_of(s, off);
-            size_t n = n_dgrams[s] * SDRHIP_UDPSIZE;
-            int j = s + 1;
-            // (packed input is one run; a strided row joins the next one when it fills its stride)
-            for (; j < S && p0 + n == row_of(j, off + n); ++j) n += n_dgrams[j] * SDRHIP_UDPSIZE;
-            if (n) HIP_TRY(link_copy(c, pk + off, p0, n, hipMemcpyHostToDevice, c->stream));
-            off += n;
-            s = j;
-        }
-    }
+    if ((rc = fecbuf_batch_upload(c, in, b.in, pk))) return rc;
 
     // ---- the collector's passes, no read-back (from the scatter launch on, the batch is consumed: a failure loses it)
     uint8_t *data = direct ? tx->a_out.as<uint8_t>() : tx->a_pay.as<uint8_t>();
@@ -234,9 +185,9 @@ extern "C" int sdrhip_tx_submit_datagrams(sdrhip_tx *tx, const uint8_t *dgrams, 
     rc = fecbuf_packed(tx->fb, pk, n_dgrams, res.data(), sh, b.tab, kmax ? data : nullptr, data_stride, kmax ? tx->a_b0.as<uint8_t>() : nullptr, kmax,
                        c->dec_stats + DEC_STATS_SHADOW_MISMATCH, &committed, &counts, &pub);
     if (rc && !committed) return rc; // (nothing consumed)
-    if (rc) return tx_batch_lost(rc);
+    if (rc) return fecbuf_batch_lost(who, rc);
     // ---- the interpolator (x1: the collector wrote the samples where the gather reads them; 8-bit x1: K6n narrows them)
-    if ((rc = tx_interpolate_counts(tx, tx->a_pay.as<int16_t>(), per, pitch, tx->a_out.as<int16_t>(), dos, counts))) return tx_batch_lost(rc);
+    if ((rc = tx_interpolate_counts(tx, tx->a_pay.as<int16_t>(), per, pitch, tx->a_out.as<int16_t>(), dos, counts))) return fecbuf_batch_lost(who, rc);
     // ---- the delivery: every stream's samples, then the records, then the meta blocks, gathered and downloaded in ONE copy
     GatherSeg *seg = b.seg.as<GatherSeg>();
     int nseg = 0;

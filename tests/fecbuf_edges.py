@@ -286,17 +286,56 @@ def sequences(oracle, carry):
     return [np.concatenate([c[s] for c in calls(oracle, carry)]) for s in range(len(streams(oracle)))]
 
 
-def models(oracle, carry):
-    """per stream the oracle's restatement fed the whole sequence (fresh: check_against_model resets its statistics), and per
-    call, per stream the number of frames the call releases"""
-    ms = [tg.Model(oracle) for _ in streams(oracle)]
+def models_of(oracle, the_calls):
+    """per stream the oracle's restatement fed every call (fresh: check_against_model resets its statistics), and per call, per
+    stream the number of frames the call releases"""
+    ms = [tg.Model(oracle) for _ in the_calls[0]]
     counts = []
-    for chunk in calls(oracle, carry):
+    for chunk in the_calls:
         before = [len(m.recs) for m in ms]
         for m, c in zip(ms, chunk):
             m.run(list(c))
         counts.append([len(m.recs) - b for m, b in zip(ms, before)])
     return ms, counts
+
+
+def models(oracle, carry):
+    return models_of(oracle, calls(oracle, carry))
+
+
+TABLE_SIZES = (1, 3, 5)  # bank sizes 1 and 3 mod 4 (the main bank has 14 streams, the other datagram tests mostly 4, 8, 32 or 64)
+
+
+def table_calls(oracle, S):
+    """two calls that fill every column of the drivers' per-call table at a bank size of S: its 64-bit arrays lie behind a padded
+    run of ints, so their offsets move with S mod 4.  The smallest such input, fecblk 4.  Call 1, per stream: a frame with one
+    original lost (it goes to the decoder: dbase, a staging slot), then the first five datagrams of the next frame (an open
+    slot in the carry buffer).  Call 2: the rest of that frame, nothing lost (the straight path), and one datagram of another
+    frame that releases it.  Stream 1 (a bank of one has none) gets nothing in call 1 and both parts in call 2."""
+    if ("table", S) not in _BUILT:
+        rs = np.random.RandomState(4000 + S)
+        one, two = [], []
+        for s in range(S):
+            a, b = tg.make_frames(oracle, rs, 2, 4, 500 * s + 11)
+            lost = 1 + int(rs.randint(127))
+            c1 = [a[i] for i in range(132) if i != lost] + list(b[:5])
+            c2 = list(b[5:]) + [ee()]
+            if s == 1:
+                c1, c2 = [], c1 + c2
+            one.append(_arr(c1))
+            two.append(_arr(c2))
+        _BUILT[("table", S)] = [one, two]
+    return _BUILT[("table", S)]
+
+
+def check_table_events(recs, counts):
+    """recs[s]: every record stream s got back.  Every stream released its initial slot, a repaired frame and a complete one;
+    all but stream 1 the first two in call 1"""
+    S = len(recs)
+    assert counts == [[0 if s == 1 else 2 for s in range(S)], [3 if s == 1 else 1 for s in range(S)]], counts
+    for r in recs:
+        assert [x["block_count"] for x in r] == [0, 131, 132] and [x["recovery_count"] for x in r[1:]] == [1, 0], r
+        assert r[1]["flags"] & REPAIRED and not r[2]["flags"] & (REPAIRED | ERROR), r
 
 
 def event(oracle, name, kind):

@@ -242,3 +242,22 @@ def test_the_events_happen_in_the_restatement(oracle, carry):
     """what the GPU tests assert of the records they get back (fecbuf_edges.check_events) holds for the restatement's"""
     ms, counts = fe.models(oracle, carry)
     fe.check_events(oracle, [m.recs for m in ms], counts, lambda s: dict(output_meta=ms[s].out_meta, current_meta=ms[s].cur_meta))
+
+
+@pytest.mark.parametrize("S", fe.TABLE_SIZES)
+def test_table_calls(oracle, reference, S):
+    """the small banks' two calls (fecbuf_edges.table_calls): what the GPU tests assert of their records holds for the
+    restatement's, and the reference class releases the restatement's frames"""
+    L, decoder = reference
+    calls = fe.table_calls(oracle, S)
+    assert len(calls) == 2 and len(calls[0]) == len(calls[1]) == S
+    assert [len(c) for c in calls[0]] == [0 if s == 1 else 136 for s in range(S)]
+    assert [len(c) for c in calls[1]] == [264 if s == 1 else 128 for s in range(S)]
+    ms, counts = fe.models_of(oracle, calls)
+    fe.check_table_events([m.recs for m in ms], counts)
+    for s, m in enumerate(ms):
+        ro, rstats, _ = tr._run_ref(L, list(np.concatenate([c[s] for c in calls])))
+        assert rstats[1:] == [(r["block_count"], r["recovery_count"]) for r in m.recs][1:], s
+        assert np.array_equal(ro[2], m.frames[2]), s
+        if decoder:
+            assert np.array_equal(ro[1], m.frames[1]), s

@@ -11,6 +11,10 @@ calls above 1024 were benign.  test_gpu_tx_datagrams.test_bench_shape and test_g
 they are: their fixed 136-datagram frames are the benchmark's shape, which is why their boundaries at 1024 and 2048 never moved
 from ranks 72 and 8 of a frame.
 
+The bank above has 14 streams, and the other datagram tests reach a bank of 1, 3 or 5 streams at some entries only: the
+test_table_* cases at the end put banks of 1, 3 and 5 streams through all five entries on the smallest input that fills every column of the
+drivers' per-call table (fecbuf_edges.table_calls), whose 64-bit arrays lie behind a padded run of ints.
+
 Yardsticks: the reference's own SDRdaemonFECBuffer fed datagram by datagram (RefChain / HubChain) and the oracle's restatement
 (test_gpu_fecbuf.Model); every released frame of every stream is compared, byte for byte."""
 import numpy as np
@@ -209,4 +213,127 @@ def test_rx_submit_collect_datagrams(oracle, ctx, reflib, rx_expected, carry):
             tr.check_frames(got[i][s][0], exp[i][s], (carry, i, s))
             recs[s] += got[i][s][1]
     check_events(oracle, recs, counts, rx.collector_stats)
+    assert tra.mismatches(ctx) == 0
+
+
+# ---- banks of 1, 3 and 5 streams: every column of the per-call table, whose offsets move with the bank size mod 4
+@pytest.fixture(scope="module")
+def table_expected(oracle, reflib):
+    """per bank size: the calls, the frame counts per call, and per call, per stream the reference chains' results: the Tx
+    chain's samples at TABLE_L, the hub chain's frames and remainders; computed once for the entries that share them"""
+    kept = {}
+
+    def get(S):
+        if S not in kept:
+            calls = fe.table_calls(oracle, S)
+            _, counts = fe.models_of(oracle, calls)
+            txc, hub = [tt.RefChain(reflib, oracle) for _ in range(S)], [tr.HubChain(reflib, oracle) for _ in range(S)]
+            samples, frames, rems = [], [], []
+            for i, chunk in enumerate(calls):
+                sec, usec = tra.stamps(i, S)
+                samples.append([txc[s].feed(chunk[s], TABLE_L) for s in range(S)])
+                frames.append([hub[s].dgrams(chunk[s], TABLE_RX["L"], TABLE_RX["fcpos"], TABLE_RX["R"], sec[s], usec[s]) for s in range(S)])
+                rems.append([len(c.rem) for c in hub])
+            kept[S] = (calls, counts, samples, frames, rems)
+        return kept[S]
+
+    yield get
+    kept.clear()
+
+
+TABLE_L = 1                           # interpolate2
+TABLE_RX = dict(L=1, fcpos=2, R=8)    # decimate2_cen: three frames of 16129 samples leave one behind in every row
+
+
+@pytest.mark.parametrize("device", [True, False])
+@pytest.mark.parametrize("S", fe.TABLE_SIZES)
+def test_table_bank(oracle, ctx, reflib, table_expected, S, device):
+    """FECBufferBank.write_and_read, device and host memory: as test_bank"""
+    import sdrdaemon_amd as sd
+
+    calls, counts = table_expected(S)[:2]
+    models, _ = fe.models_of(oracle, calls)
+    bank = sd.FECBufferBank(ctx, S)
+    got, n = fe.run_bank(bank, calls, device)
+    assert n == counts
+    tg.check_against_model(bank, got, models)
+    for s in range(S):
+        ref = tt.RefChain(reflib, oracle).collect(list(np.concatenate([c[s] for c in calls])))
+        assert len(got[s][0]) == len(ref), s
+        for k in range(len(ref)):
+            assert np.array_equal(got[s][0][k], ref[k]), (s, k, got[s][2][k])
+    fe.check_table_events([g[2] for g in got], counts)
+
+
+@pytest.mark.parametrize("S", fe.TABLE_SIZES)
+def test_table_tx_process_datagrams(oracle, ctx, table_expected, S):
+    """TxPipe.process_datagrams: as test_tx_process_datagrams"""
+    import sdrdaemon_amd as sd
+
+    calls, counts, samples = table_expected(S)[:3]
+    tx, bank = sd.TxPipe(ctx, S, TABLE_L), sd.FECBufferBank(ctx, S)
+    got = tt.run_calls(tx, calls, bank=bank)
+    assert [[len(g[2]) for g in call] for call in got] == counts
+    check_samples(got, samples)
+    fe.check_table_events([sum((call[s][2] for call in got), []) for s in range(S)], counts)
+
+
+@pytest.mark.parametrize("S", fe.TABLE_SIZES)
+def test_table_tx_submit_collect_datagrams(oracle, ctx, table_expected, S):
+    """TxPipe.submit_datagrams / collect_datagrams at depth 2: as test_tx_submit_collect_datagrams"""
+    import sdrdaemon_amd as sd
+
+    calls, counts, samples = table_expected(S)[:3]
+    tx = sd.TxPipe(ctx, S, TABLE_L)
+    got = ta.run_async(tx, calls, 2)
+    assert [[len(g[2]) for g in call] for call in got] == counts
+    ta.check_bank(ctx, got, calls)
+    check_samples(got, samples)
+    fe.check_table_events([sum((call[s][2] for call in got), []) for s in range(S)], counts)
+    assert ta.mismatches(ctx) == 0
+
+
+@pytest.mark.parametrize("S", fe.TABLE_SIZES)
+def test_table_rx_process_datagrams(oracle, ctx, table_expected, S):
+    """RxPipe.process_datagrams: as test_rx_process_datagrams"""
+    import sdrdaemon_amd as sd
+
+    calls, counts, _, exp, rems = table_expected(S)
+    rx = sd.RxPipe(ctx, S, log2decim=TABLE_RX["L"], fcpos=TABLE_RX["fcpos"], nb_fec=TABLE_RX["R"])
+    bank = sd.FECBufferBank(ctx, S)
+    recs = [[] for _ in range(S)]
+    for i, chunk in enumerate(calls):
+        sec, usec = tra.stamps(i, S)
+        got = tr.run_call(rx, chunk, sec, usec, bank=bank)
+        assert rx.last_n_released == counts[i], i
+        for s in range(S):
+            tr.check_frames(got[s][0], exp[i][s], (S, i, s))
+            recs[s] += got[s][1]
+        assert list(rx.carry()) == rems[i], i
+    assert sum(len(f) for call in exp for f in call) == S and rems[-1] == [1] * S
+    fe.check_table_events(recs, counts)
+
+
+@pytest.mark.parametrize("S", fe.TABLE_SIZES)
+def test_table_rx_submit_collect_datagrams(oracle, ctx, table_expected, S):
+    """RxPipe.submit_datagrams / collect_datagrams at depth 2: as test_rx_submit_collect_datagrams"""
+    import sdrdaemon_amd as sd
+
+    calls, counts, _, exp, rems = table_expected(S)
+    rx = sd.RxPipe(ctx, S, log2decim=TABLE_RX["L"], fcpos=TABLE_RX["fcpos"], nb_fec=TABLE_RX["R"])
+
+    def carry_is_the_chains(i):
+        assert list(rx.carry()) == rems[i], i
+
+    got = tra.run_async(rx, calls, 2, after_submit=carry_is_the_chains)
+    bank = sd.FECBufferBank(ctx, S)
+    recs = [[] for _ in range(S)]
+    for i, chunk in enumerate(calls):
+        ref = bank.write_and_read(chunk)
+        assert [len(g[1]) for g in got[i]] == bank.last_n_frames == counts[i], i
+        for s in range(S):
+            assert got[i][s][1] == ref[s][2], (i, s)
+            tr.check_frames(got[i][s][0], exp[i][s], (S, i, s))
+            recs[s] += got[i][s][1]
+    fe.check_table_events(recs, counts)
     assert tra.mismatches(ctx) == 0
