@@ -86,12 +86,21 @@ int sdrhip_ctx_synchronize(sdrhip_ctx *ctx);
  * workgroup, the default, or by the planning kernel in a launch of its own), "rx_window" = 0 | 1..8 (frame window of the Rx pipe in
  * calls; 0 = the default: 2, pipelined pipes 4), "fec_stagger" / "fec_stagger_mod" (experiment: staggered start of the FFT encoder's /
  * decoder's workgroups, default off; mod 0: phase = resident round, 1..16: workgroup mod m, 100 + m: the workgroup's arrival rank on its CU mod m), "ktime_stride" = 1..1024 / "ktime_stride_class" = "<class>:<stride>" (the kernel-class timers
- * of sdrhip_ctx_kernel_timing bracket every n-th launch, of all classes / of one).  Every setting computes the same bytes.  One knob is a promise, not a path: "dec_max_rows" = 1..128 (default 128), the most recovery
- * blocks a received frame can carry (the sender's fecblk, known from the meta block; a collector that counted the recovery blocks
- * of a batch -- adapters/UDPSourceFEC.h -- passes that count); <= 32 makes the batched decode ONE launch (the plan inside the
- * decoder, no fallback kernel).  The promise is checked on the device: a frame that carries MORE recovery blocks than
+ * of sdrhip_ctx_kernel_timing bracket every n-th launch, of all classes / of one).  Every setting computes the same bytes.  One knob is a promise, not a path: "dec_max_rows" = 1..128 | auto (default 128).  A number is the most recovery
+ * blocks a received frame can carry AND bounds their row indices: it is the sender's fecblk (known from the meta block), every
+ * recovery block of every frame has a row below it -- not a count of the recovery blocks that happened to arrive (a fecblk-64
+ * sender's frame can hold five of them and a row of 40); <= 32 makes the batched decode ONE launch (the plan inside the
+ * decoder, no fallback kernel).  The count is checked on the device: a frame that carries MORE recovery blocks than
  * dec_max_rows is left as received (like an undecodable frame: missing originals read zero) and counted, see
- * sdrhip_ctx_get_counter("dec_rows_exceeded").  One knob selects behaviour: "dec_strict" = 0 | 1 (default 0).  The reference copies
+ * sdrhip_ctx_get_counter("dec_rows_exceeded"); the rows are the caller's word.  "auto" is a mode, not a promise: the library
+ * decides per frame from the frame's own block indices (header byte 2, or the `indices` array when one is given).  With N the number of
+ * indices >= 128 among the frame's 128 received blocks and maxrow the highest of them minus 128, a frame is DEFERRED iff N > 32 or
+ * maxrow >= 32 (whatever else is true of it), every other frame is served by the one-launch decoder exactly as under dec_max_rows =
+ * 32; the deferred frames are listed on the device and decoded by the launches behind it exactly as under dec_max_rows = 128 (no
+ * host read-back in between), and counted in sdrhip_ctx_get_counter("dec_deferred").  Under auto every batch -- dec_strict 0 or 1, header
+ * indices or the `indices` array -- is delivered byte for byte as under dec_max_rows = 128, and "dec_rows_exceeded" does not grow.
+ * Where the one-launch decoder is not in play (dec_plan = kernel, dec_path = dense, enc_path = karatsuba) auto reads as 128 and
+ * defers nothing; "tx_gather" keeps requiring a number <= 32.  One knob selects behaviour: "dec_strict" = 0 | 1 (default 0).  The reference copies
  * back only the descriptors [128 - recoveryCount, 128) after cm256_decode (SDRdaemonFECBuffer.cpp:204-211: it relies on the
  * recovery blocks arriving last), so a block restored into a recovery block that arrived BEFORE some original is never copied
  * and stays a hole; by default the batched decoder delivers every restored block (a superset), with dec_strict = 1 exactly the
@@ -100,7 +109,9 @@ int sdrhip_ctx_set_option(sdrhip_ctx *ctx, const char *key, const char *value);
 /* Event counters of the context.  Keys:
  * "dec_rows_exceeded" = frames, since the context was created, that the batched decoder (sdrhip_fec_decode_frames,
  * sdrhip_tx_process) left unrepaired because they carried more recovery blocks than the dec_max_rows option allows (kept on the
- * device: reading it synchronises the context's stream);
+ * device: reading it synchronises the context's stream); it does not grow under dec_max_rows = auto;
+ * "dec_deferred" = frames, since the context was created, that the one-launch decoder handed to the launches behind it under
+ * dec_max_rows = auto (more than 32 recovery blocks, or a recovery row >= 32, among the frame's 128 blocks; on the device, as above);
  * "fecbuf_shadow_mismatch" = streams of asynchronous datagram batches of either pipe (sdrhip_tx_submit_datagrams,
  * sdrhip_rx_submit_datagrams) whose collector counts on the
  * device disagreed with the host's shadow that sized the batch's grids; 0 unless the library is broken (on the device, as above);

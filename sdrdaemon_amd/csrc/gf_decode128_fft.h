@@ -43,7 +43,7 @@ struct Dec128Scratch {
     int cnt[256];              // how often block index b arrived
     uint8_t x[128], y[128], rpos[128], idx[128];
     int lpx[DEC128_MAXN], lqx[DEC128_MAXN], lpy[DEC128_MAXN], lqy[DEC128_MAXN];
-    unsigned long long mask[2][3];
+    unsigned long long mask[2][4];
 };
 static_assert(sizeof(Dec128Scratch) % 16 == 0, "scratch size");
 static_assert(offsetof(Dec128Scratch, lqx) == offsetof(Dec128Scratch, lpx) + 4 * DEC128_MAXN && offsetof(Dec128Scratch, lpy) == offsetof(Dec128Scratch, lpx) + 8 * DEC128_MAXN &&
@@ -96,14 +96,24 @@ __device__ __forceinline__ void dec128_plan(const Dec128Args &a, int fr, Dec128P
         br = __ballot(is_rec);
         bm = __ballot(s->cnt[tid] == 0);
         const unsigned long long bd = __ballot(s->cnt[tid] > 1 || s->cnt[K + tid] > 1); // an original, or a recovery block, more than once
-        if (ln == 0) { s->mask[wv][0] = br; s->mask[wv][1] = bm; s->mask[wv][2] = bd; }
+        const unsigned long long bh = __ballot(b >= K + DEC128_MAXN); // a recovery row the syndrome stage cannot serve (it reads rowidx[0..31])
+        if (ln == 0) { s->mask[wv][0] = br; s->mask[wv][1] = bm; s->mask[wv][2] = bd; s->mask[wv][3] = bh; }
     }
     __syncthreads();
     const int nrec = __popcll(s->mask[0][0]) + __popcll(s->mask[1][0]), nmiss = __popcll(s->mask[0][1]) + __popcll(s->mask[1][1]);
     const bool dup = (s->mask[0][2] | s->mask[1][2]) != 0ull;
     const int N = nrec;
     bool ok = N > 0 && !dup;
-    if (N > a.max_rows) { // more recovery blocks than the caller promised: left as received and COUNTED (gf_decode_plan_kernel)
+    if (a.defer_count && (N > DEC128_MAXN || (s->mask[0][3] | s->mask[1][3]) != 0ull)) {
+        // dec_max_rows = auto: a frame this kernel cannot serve (more than 32 recovery blocks, or a row >= 32 among them, whatever else is
+        // true of it) is left as received HERE and listed for the safe chain behind this launch (launch_fec_decode_device_plan), which
+        // does the whole frame again; nothing is counted as a broken promise
+        ok = false;
+        if (tid == 0) {
+            a.defer_list[atomicAdd(a.defer_count, 1)] = fr;
+            atomicAdd(a.stats + DEC_STATS_DEFERRED, 1u);
+        }
+    } else if (N > a.max_rows) { // more recovery blocks than the caller promised: left as received and COUNTED (gf_decode_plan_kernel)
         ok = false;
         if (tid == 0) atomicAdd(a.stats, 1u);
     }

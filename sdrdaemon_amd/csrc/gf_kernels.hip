@@ -284,6 +284,9 @@ struct DecPlanArgs {
     int strict;                // ctx option dec_strict: deliver only what the reference's copy-back loop delivers (see the planner)
     int max_rows;              // the caller's promise (ctx option dec_max_rows): no frame carries more recovery blocks
     unsigned *stats;           // [0] += frames that broke the promise (they stay as received; sdrhip_ctx_get_counter)
+    // optional (dec_max_rows = auto, stage B): workgroup i takes frame list[i], workgroups at or past *count leave at once;
+    // every per-frame buffer stays indexed by the real frame number.  NULL: workgroup i takes frame i
+    const int *list, *count;
 };
 
 // Per-frame record of the syndrome decoder (gf_decode128_kernel): where every original lies in the received array, which
@@ -316,7 +319,12 @@ __global__ __launch_bounds__(128) void gf_decode_plan_kernel(DecPlanArgs a)
     __shared__ uint8_t s_le[K * K];   // log of (y'_p ^ x_0) / (x_i ^ y'_p) at [i][p]
     __shared__ int s_bad;
     __shared__ unsigned long long s_mask[2][3];
-    const int f = blockIdx.x, p = threadIdx.x;
+    int f = blockIdx.x;
+    const int p = threadIdx.x;
+    if (a.list) {
+        if (f >= *a.count) return; // (workgroup-uniform, in front of every barrier)
+        f = a.list[f];
+    }
     // (one 16-byte load per thread, issued with the header byte: as two copy loops of bytes / halfwords the table arrived in six
     // global round trips one after the other)
     uint4_t el = {0u, 0u, 0u, 0u};
@@ -479,6 +487,7 @@ struct DecApplyArgs {
     const uint8_t *tab;
     int which;
     int nframes;
+    const int *list, *count;   // optional (DecPlanArgs::list): group g works on frames list[2 g] and list[2 g + 1]
 };
 
 template <int RB> __global__ __launch_bounds__(GF_NT) void gf_decode_apply_kernel(DecApplyArgs a)
@@ -489,19 +498,28 @@ template <int RB> __global__ __launch_bounds__(GF_NT) void gf_decode_apply_kerne
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, h = lane >> 5, l = lane & 31;
     const int row0 = blockIdx.y * ROWS_PER_WG;
     const int f0 = blockIdx.x * 2;
-    int rows[2];
+    int rows[2], frs[2]; // (frs: the pair's frame numbers, -1 = none)
+    if (a.list) {
+        const int cnt = *a.count;
+        if (f0 >= cnt) return; // (uniform)
+        frs[0] = a.list[f0];
+        frs[1] = f0 + 1 < cnt ? a.list[f0 + 1] : -1;
+    } else {
+        frs[0] = f0;
+        frs[1] = f0 + 1 < a.nframes ? f0 + 1 : -1;
+    }
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-        const int fr = f0 + u;
+        const int fr = frs[u];
         int n = 0;
-        if (fr < a.nframes) n = a.which ? (a.nrec[(size_t)fr * 2 + 1] ? 1 : 0) : a.nrec[(size_t)fr * 2];
+        if (fr >= 0) n = a.which ? (a.nrec[(size_t)fr * 2 + 1] ? 1 : 0) : a.nrec[(size_t)fr * 2];
         rows[u] = n;
     }
     if (row0 >= rows[0] && row0 >= rows[1]) return; // (uniform: nothing to recover here)
     for (int i = tid; i < 256 * 8; i += GF_NT) tab[i] = reinterpret_cast<const unsigned *>(a.tab)[i];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-        const uint8_t *cg = a.coef + ((size_t)(f0 + u) * K + row0) * K;
+        const uint8_t *cg = a.coef + ((size_t)(frs[u] < 0 ? 0 : frs[u]) * K + row0) * K;
         const int nr = rows[u] - row0;
         for (int i = tid; i < ROWS_PER_WG * K / 4; i += GF_NT) {
             const int r = (i * 4) / K;
@@ -509,7 +527,7 @@ template <int RB> __global__ __launch_bounds__(GF_NT) void gf_decode_apply_kerne
         }
     }
     __syncthreads();
-    const int fr = f0 + h;
+    const int fr = h ? frs[1] : frs[0];
     const int myrows = rows[h];
     const int r0 = wave * RB;
     if (row0 + r0 >= rows[0] && row0 + r0 >= rows[1]) return;
@@ -517,8 +535,8 @@ template <int RB> __global__ __launch_bounds__(GF_NT) void gf_decode_apply_kerne
     uint4_t acc[RB];
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) acc[rb] = (uint4_t){0u, 0u, 0u, 0u};
-    const bool live = fr < a.nframes && row0 + r0 < myrows;
-    const uint8_t *fbase = a.in + (size_t)(fr < a.nframes ? fr : 0) * a.in_frame_bytes + 4;
+    const bool live = fr >= 0 && row0 + r0 < myrows;
+    const uint8_t *fbase = a.in + (size_t)(fr >= 0 ? fr : 0) * a.in_frame_bytes + 4;
     const uint8_t *cw = coef[h] + r0 * K;
     uint4_t xn = (uint4_t){0u, 0u, 0u, 0u};
     if (live) xn = load_slab(fbase, l);
@@ -578,6 +596,10 @@ struct Dec128Args {
     unsigned *srcmap;           // [nframes][128]: where original j of frame f lies (gf_decode128_fft.h: dec128_plan)
     uint8_t *restored;          // [nframes * restored_rows + 1] slots of 508 bytes: row t of frame f -> slot f * restored_rows + t; the last slot stays zero
     int restored_rows;
+    // dec_max_rows = auto (NULL otherwise).  Stage A, gf_decode128_fft_plan_kernel: a frame with more than DEC128_MAXN recovery blocks or
+    // a recovery row >= DEC128_MAXN is appended here (dec128_plan).  Stage B, gf_decode128_fft_kernel: workgroup i takes frame
+    // defer_list[i], workgroups at or past *defer_count leave at once
+    int *defer_count, *defer_list;
 };
 constexpr int DEC128_LDS_BYTES = 8 * KLEAVES * 20 + 256 * 32 + 33 * 64 * 4 + DEC128_MAXN * 64 * 4 + DEC128_PLAN_BYTES;
 
@@ -780,7 +802,11 @@ __global__ __launch_bounds__(GF_NT, 4) void gf_decode128_fft_kernel(Dec128Args a
 {
     constexpr int LDSB = DEC128_FFT_LDS_BYTES > DEC128_LDS_BYTES ? DEC128_FFT_LDS_BYTES : DEC128_LDS_BYTES;
     __shared__ __attribute__((aligned(16))) unsigned char ldsraw[LDSB];
-    const int fr = (int)blockIdx.x;
+    int fr = (int)blockIdx.x;
+    if (a.defer_list) {
+        if (fr >= *a.defer_count) return; // (workgroup-uniform, in front of every barrier)
+        fr = a.defer_list[fr];
+    }
     const Dec128Plan *gp = reinterpret_cast<const Dec128Plan *>(a.plan + (size_t)fr * DEC128_PLAN_BYTES);
     if (gp->n > 0 && !gp->m1 && gp->maxrow >= FFT_MAX_ROWS) { // (workgroup-uniform)
 #pragma unroll 1
@@ -877,6 +903,15 @@ hipError_t launch_fec_decode_device_plan(const DecodeBuffers &d, const uint8_t *
     if (nframes <= 0) return hipSuccess;
     if (max_rows < 1) max_rows = 1;
     if (max_rows > 128) max_rows = 128;
+    // dec_max_rows = auto (d.defer_count): stage A is the one-launch decoder under a bound of 32; the frames it cannot serve are
+    // listed on the device and stage B -- the chain below at a bound of 128 -- takes frame list[i] in workgroup i.  The host never
+    // learns the count: stage B's grids are sized as for nframes, workgroups at or past the count leave at once.
+    const bool defer = d.defer_count && d.defer_list && d.plan2 && d.use_fft && d.fft_tables && d.fused_plan && !d.srcmap;
+    if (defer) {
+        hipError_t e = hipMemsetAsync(d.defer_count, 0, sizeof(int), stream);
+        if (e != hipSuccess) return e;
+        max_rows = DEC128_MAXN;
+    }
     if (d.plan2 && d.use_fft && d.fft_tables && d.fused_plan && max_rows <= DEC128_MAXN) {
         // one launch: every workgroup plans its own frame (gf_decode128_fft.h: dec128_plan_front / _back)
         Dec128Args k;
@@ -885,9 +920,12 @@ hipError_t launch_fec_decode_device_plan(const DecodeBuffers &d, const uint8_t *
         k.stagger = d.stagger; k.stagger_div = d.stagger_div;
         k.indices = indices_dev; k.explog = explog; k.max_rows = max_rows; k.strict = strict; k.stats = stats;
         k.srcmap = d.srcmap; k.restored = d.restored; k.restored_rows = d.restored_rows;
+        k.defer_count = defer ? d.defer_count : nullptr; k.defer_list = defer ? d.defer_list : nullptr;
         if (k.srcmap) hipLaunchKernelGGL(gf_decode128_fft_plan_kernel<true>, dim3(nframes), dim3(GF_NT), 0, stream, k);
         else hipLaunchKernelGGL(gf_decode128_fft_plan_kernel<false>, dim3(nframes), dim3(GF_NT), 0, stream, k);
-        return hipGetLastError();
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess || !defer) return e;
+        max_rows = 128;
     }
     DecPlanArgs p;
     p.max_rows = max_rows; p.stats = stats; p.strict = strict;
@@ -895,6 +933,7 @@ hipError_t launch_fec_decode_device_plan(const DecodeBuffers &d, const uint8_t *
     p.coef = d.coef; p.pmap = d.pmap; p.zmap = d.zmap; p.pdst = d.pdst; p.zdst = d.zdst; p.nrec = d.nrec;
     p.payload_out = payload_out; p.payload_frame_bytes = payload_frame_bytes; p.block0_out = block0_out; p.nframes = nframes;
     p.plan2 = d.plan2;
+    p.list = defer ? d.defer_list : nullptr; p.count = defer ? d.defer_count : nullptr;
     hipLaunchKernelGGL(gf_decode_plan_kernel, dim3(nframes), dim3(128), 0, stream, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -907,6 +946,7 @@ hipError_t launch_fec_decode_device_plan(const DecodeBuffers &d, const uint8_t *
         k.stagger = d.stagger; k.stagger_div = d.stagger_div;
         k.indices = nullptr; k.explog = nullptr; k.max_rows = max_rows; k.strict = strict; k.stats = stats;
         k.srcmap = nullptr; k.restored = nullptr; k.restored_rows = 0;
+        k.defer_count = defer ? d.defer_count : nullptr; k.defer_list = defer ? d.defer_list : nullptr;
         if (d.use_fft && d.fft_tables) hipLaunchKernelGGL(gf_decode128_fft_kernel, dim3(nframes), dim3(GF_NT), 0, stream, k);
         else hipLaunchKernelGGL(gf_decode128_kernel, dim3(2 * nframes), dim3(GF_NT), 0, stream, k);
         e = hipGetLastError();
@@ -925,6 +965,7 @@ hipError_t launch_fec_decode_device_plan(const DecodeBuffers &d, const uint8_t *
     DecApplyArgs a;
     a.in = rx; a.in_frame_bytes = rx_frame_bytes; a.out = payload_out; a.out_frame_bytes = payload_frame_bytes; a.out_pitch = 508;
     a.coef = d.coef; a.dst = d.pdst; a.nrec = d.nrec; a.tab = tab; a.which = 0; a.nframes = nframes;
+    a.list = p.list; a.count = p.count;
     const int groups = (nframes + 1) / 2;
     if (max_rows <= 16) hipLaunchKernelGGL(gf_decode_apply_kernel<4>, dim3(groups, 1), dim3(GF_NT), 0, stream, a);
     else hipLaunchKernelGGL(gf_decode_apply_kernel<6>, dim3(groups, (max_rows + 23) / 24), dim3(GF_NT), 0, stream, a);

@@ -237,7 +237,8 @@ extern "C" int sdrhip_ctx_set_option(sdrhip_ctx *c, const char *key, const char 
         if (v == "syndrome") c->opt.dec_syndrome = 1;
         else if (v == "dense") c->opt.dec_syndrome = 0;
         else return fail(SDRHIP_EINVAL, "ctx_set_option: dec_path must be syndrome or dense");
-    } else if (k == "dec_max_rows" && isnum && num >= 1 && num <= 128) c->opt.dec_max_rows = (int)num;
+    } else if (k == "dec_max_rows" && isnum && num >= 1 && num <= 128) { c->opt.dec_max_rows = (int)num; c->opt.dec_auto = 0; }
+    else if (k == "dec_max_rows" && v == "auto") { c->opt.dec_max_rows = 128; c->opt.dec_auto = 1; } // (whoever reads the number sees 128: auto is decided per frame, fec_decode_device)
     else if (k == "dec_strict" && isnum && num <= 1) c->opt.dec_strict = (int)num;
     else if (k == "ktime_stride" && isnum && num >= 1 && num <= 1024) { c->ktime_stride = (int)num; for (int i = 0; i < SDRHIP_KCLASSES; ++i) c->ktime_stride_cls[i] = 0; }
     else if (k == "ktime_stride_class") { // "<class>:<stride>": this kernel class only (e.g. the roofline kernel on every launch, the others on every 4th)
@@ -257,10 +258,11 @@ extern "C" int sdrhip_ctx_get_counter(sdrhip_ctx *c, const char *key, uint64_t *
     if (std::string(key) == "h2d_bytes") { *value = c->h2d_bytes; return SDRHIP_OK; }
     if (std::string(key) == "d2h_bytes") { *value = c->d2h_bytes; return SDRHIP_OK; }
     const bool shadow = std::string(key) == "fecbuf_shadow_mismatch"; // (streams whose classify pass disagreed with the host's shadow)
-    if (std::string(key) != "dec_rows_exceeded" && !shadow) return fail(SDRHIP_EINVAL, "ctx_get_counter: unknown key: %s", key);
+    const bool deferred = std::string(key) == "dec_deferred"; // (frames the one-launch decoder handed to the safe chain under dec_max_rows = auto)
+    if (std::string(key) != "dec_rows_exceeded" && !shadow && !deferred) return fail(SDRHIP_EINVAL, "ctx_get_counter: unknown key: %s", key);
     HIP_TRY(hipSetDevice(c->device));
     unsigned v = 0;
-    HIP_TRY(link_copy(c, &v, c->dec_stats + (shadow ? DEC_STATS_SHADOW_MISMATCH : 0), sizeof(v), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(link_copy(c, &v, c->dec_stats + (shadow ? DEC_STATS_SHADOW_MISMATCH : deferred ? DEC_STATS_DEFERRED : 0), sizeof(v), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     *value = v;
     return SDRHIP_OK;

@@ -84,7 +84,8 @@ int fec_encode_device(sdrhip_ctx *c, const uint8_t *frames, size_t frame_bytes, 
 bool fec_decode_gather_ok(const sdrhip_ctx *c)
 {
     // (the conditions under which launch_fec_decode_device_plan takes its one-launch branch)
-    return c->opt.dec_syndrome && c->opt.enc_fft && c->enc_fft && c->opt.dec_fused_plan && c->opt.dec_max_rows <= 32;
+    // (dec_max_rows = auto is no promise: the no-copy variant has no second stage to hand a frame to)
+    return c->opt.dec_syndrome && c->opt.enc_fft && c->enc_fft && c->opt.dec_fused_plan && !c->opt.dec_auto && c->opt.dec_max_rows <= 32;
 }
 
 int fec_decode_device(sdrhip_ctx *c, const uint8_t *rx, size_t rx_frame_bytes, const uint8_t *indices, size_t nframes,
@@ -103,7 +104,10 @@ int fec_decode_device(sdrhip_ctx *c, const uint8_t *rx, size_t rx_frame_bytes, c
     // (the dense path's scatter pass puts the frame index in gridDim.y: 65535 at most; the default syndrome path has no such pass)
     if (!c->opt.dec_syndrome && nframes > 65535) return fail(SDRHIP_EINVAL, "fec decode (dec_path = dense): at most 65535 frames per call");
     int rc;
-    if ((rc = planbuf.reserve(DecodeBuffers::bytes(nframes)))) return rc;
+    // dec_max_rows = auto: per frame on the device, where the one-launch decoder is in play and the caller brought no bound of its own;
+    // everywhere else the option reads as 128 (CtxOptions::dec_max_rows holds 128 while dec_auto is set)
+    const bool defer = c->opt.dec_auto && max_rows <= 0 && !gather && c->opt.dec_syndrome && c->opt.enc_fft && c->enc_fft && c->opt.dec_fused_plan;
+    if ((rc = planbuf.reserve(DecodeBuffers::bytes(nframes, defer)))) return rc;
     DecodeBuffers d;
     uint8_t *base = planbuf.as<uint8_t>();
     d.coef = base; base += nframes * (size_t)128 * 128;
@@ -114,6 +118,9 @@ int fec_decode_device(sdrhip_ctx *c, const uint8_t *rx, size_t rx_frame_bytes, c
     d.nrec = reinterpret_cast<int32_t *>(base); base += (nframes * 2 * sizeof(int32_t) + 15) & ~(size_t)15;
     // syndrome decoder (default) or the dense matrix kernel alone (ctx option dec_path = dense: A / B and fallback)
     d.plan2 = c->opt.dec_syndrome ? base : nullptr;
+    base += nframes * DECODE_PLAN2_BYTES;
+    d.defer_count = defer ? reinterpret_cast<int *>(base) : nullptr;
+    d.defer_list = defer ? reinterpret_cast<int *>(base + 16) : nullptr;
     d.leaf_tables = c->enc_leaves;
     d.fft_tables = c->enc_fft; d.use_fft = c->opt.enc_fft;
     d.stagger = c->opt.fec_stagger; d.stagger_div = c->opt.fec_stagger_mod ? -c->opt.fec_stagger_mod : c->n_cu;

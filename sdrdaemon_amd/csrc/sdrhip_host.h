@@ -267,6 +267,7 @@ struct CtxOptions {
     int dec_syndrome = 1;                  // batched CM256 decode: syndrome kernel (1) or the dense matrix kernel alone (0)
     int dec_strict = 0;                    // batched decode delivers only what the reference's copy-back loop delivers (SDRdaemonFECBuffer.cpp:204-211)
     int dec_max_rows = 128;                // upper bound of the recovery blocks a received frame can have used (the sender's fecblk)
+    int dec_auto = 0;                      // dec_max_rows = auto: no promise, the one-launch decoder defers per frame (fec_decode_device); dec_max_rows holds 128 meanwhile
 };
 // what the last decimate / rx call of a bank actually launched (sdrhip_decimators_last_plan)
 struct DecimPlanInfo {
@@ -299,7 +300,7 @@ struct sdrhip_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     uint8_t *gf_explog = nullptr;             // exp[512] + log[256] (uint16) of GF(256) for the decode planner (device)
     sdrhip::DevBuf dec_plan;                  // per-frame decode plans of the current batch (DecodeBuffers)
-    unsigned *dec_stats = nullptr;            // device counters of the batched decoder: [0] frames that broke the dec_max_rows promise
+    unsigned *dec_stats = nullptr;            // device counters of the batched decoder: [0] frames that broke the dec_max_rows promise, [1] DEC_STATS_SHADOW_MISMATCH, [2] DEC_STATS_DEFERRED
     sdrhip::PinnedBuf pin;                       // per-call upload staging (maps, frame lists)
     sdrhip::PinnedBuf zin, zout;                 // zero-copy staging of small host-pointer calls (the kernels read / write pinned host memory)
     // per-kernel-class timing with hipEvents on `stream` (sdrhip_ctx_kernel_timing)

@@ -457,10 +457,20 @@ struct DecodeBuffers {
     unsigned *srcmap;
     uint8_t *restored;
     int restored_rows;
-    static size_t bytes(size_t nframes) { return nframes * (128 * 128 + 4 * 128 * sizeof(int16_t) + 2 * sizeof(int32_t) + DECODE_PLAN2_BYTES) + 64; }
+    // dec_max_rows = auto (NULL otherwise): the frames the one-launch decoder hands to the chain behind it -- a counter the launch
+    // clears on its stream and [nframes] frame numbers, part of THIS plan buffer (a pipelined Tx call's second stream has its own)
+    int *defer_count, *defer_list;
+    static size_t bytes(size_t nframes, bool defer = false)
+    {
+        return nframes * (128 * 128 + 4 * 128 * sizeof(int16_t) + 2 * sizeof(int32_t) + DECODE_PLAN2_BYTES) + 64 + (defer ? 16 + nframes * sizeof(int) : 0);
+    }
 };
+// words of sdrhip_ctx::dec_stats the decoder's kernels count in: [0] frames that broke the dec_max_rows promise, [2] frames the
+// one-launch decoder handed to the safe chain under dec_max_rows = auto ([1]: DEC_STATS_SHADOW_MISMATCH, sdrhip_host.h)
+constexpr int DEC_STATS_DEFERRED = 2;
 // plan + scatter + apply, all on the stream, no host synchronisation; max_rows = upper bound of the recovery blocks a
-// frame can have used (128 when unknown); a frame that carries more is left as received and counted in stats[0]
+// frame can have used (128 when unknown); a frame that carries more is left as received and counted in stats[0].
+// d.defer_count != NULL (dec_max_rows = auto): max_rows is not read -- 32 for the one-launch decoder, 128 for the listed frames
 hipError_t launch_fec_decode_device_plan(const DecodeBuffers &d, const uint8_t *rx, size_t rx_frame_bytes, const uint8_t *indices_dev,
                                          const uint8_t *explog, const uint8_t *tab, int nframes, uint8_t *payload_out,
                                          size_t payload_frame_bytes, uint8_t *block0_out, int max_rows, int strict, unsigned *stats, hipStream_t stream);

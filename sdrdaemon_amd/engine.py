@@ -70,7 +70,11 @@ class Context:
 
     def set_option(self, key, value):
         """kernel-path knobs for tests and tools (sdrhip_ctx_set_option): decim_path, mfma_span, mfma_min, interp_path,
-        interp_span, rx_fused; the defaults were read from the SDRHIP_* environment when the context was created"""
+        interp_span, rx_fused; the defaults were read from the SDRHIP_* environment when the context was created.
+        "dec_max_rows" = 1..128 is a promise about the sender's fecblk (it bounds the recovery blocks' row indices, not only their
+        count); "auto" is no promise: the batched decoder decides per frame from its block indices -- at most 32 recovery blocks, all
+        of rows 0..31: repaired in the one launch that plans it; any other frame is deferred to the general chain behind that launch
+        -- and delivers the bytes of dec_max_rows = 128"""
         check(self.lib.sdrhip_ctx_set_option(self.h, str(key).encode(), str(value).encode()))
         self.options[str(key)] = str(value)
 
@@ -101,7 +105,8 @@ class Context:
 
     def counter(self, key):
         """event counters (sdrhip_ctx_get_counter): "dec_rows_exceeded" = frames the batched decoder left unrepaired because they
-        carried more recovery blocks than the dec_max_rows option promises (device-side: synchronises); "h2d_bytes" / "d2h_bytes" =
+        carried more recovery blocks than the dec_max_rows option promises (device-side: synchronises; does not grow under
+        dec_max_rows = auto); "dec_deferred" = frames the one-launch decoder deferred under dec_max_rows = auto (device-side); "h2d_bytes" / "d2h_bytes" =
         bytes the context's calls copied across the host link since it was created (host-side: no synchronisation)"""
         v = C.c_uint64(0)
         check(self.lib.sdrhip_ctx_get_counter(self.h, str(key).encode(), C.byref(v)))
