@@ -682,6 +682,73 @@ int sdrhip_rx_submit_datagrams(sdrhip_rx *rx, const uint8_t *dgrams, const size_
 int sdrhip_rx_collect_datagrams(sdrhip_rx *rx, uint8_t *frames_out, size_t frame_stride_bytes, size_t max_frames,
                                 size_t max_released, sdrhip_fecbuf_frame *info_out, size_t *n_released, size_t *n_frames, int wait);
 
+/* ---- Per-stream lifecycle: one stream of a bank begins again while the others run on.
+ * In the reference one stream is one sdrdaemonrx / sdrdaemontx process, and restarting that process gives the stream what the
+ * constructors leave: zero half-band histories (Decimators.h:56-70, Interpolators.h:47-52: EO1.h:171-188 / IntHalfbandFilterDB's
+ * zero fill), no open frame and m_frameCount 0 (UDPSinkFEC.cpp:28-60), an SDRdaemonFECBuffer with frame head -1, empty slots,
+ * statistics 256 / 0 and MetaDataFEC::init() in m_currentMeta and m_outputMeta (SDRdaemonFECBuffer.cpp:28-52).
+ * mask: host array of nstreams bytes, nonzero = reset that stream; NULL = every stream (for the pipes: the whole-pipe reset).
+ * Afterwards stream s behaves, byte for byte, like stream s of a freshly created handle with the present configuration; every
+ * other stream behaves as if the call had not happened.
+ *  - sdrhip_decimators_reset_streams / sdrhip_interpolators_reset_streams: the streams' filter histories.
+ *  - sdrhip_fecbuf_reset_streams: the streams' collector state and statistics (and, on an Rx handle's collector, the samples the
+ *    stream holds back in front of its decimator: sdrhip_rx_carry reads 0).
+ *  - sdrhip_rx_reset_streams: the six decimator histories; the open frame, which is discarded and never delivered (its window
+ *    slot may keep stale bytes); m_frameCount, back to 0; with a datagram collector also what sdrhip_fecbuf_reset_streams covers,
+ *    so that m_outputMeta reads "no incoming meta" for sdrhip_rx_set_follow_meta until the stream's next block 0 is released.
+ *  - sdrhip_tx_reset_streams: the interpolator histories, and the collector if there is one.
+ * What survives: the configuration, the sdrhip_rx_set_stream_meta arrays, the follow flag, the input / output format, the
+ * asynchronous ring.
+ * Ordering: the call takes the context lock and enqueues ONE small launch on the context's stream behind everything submitted so
+ * far; it never synchronises and reads nothing back (the mask goes up from a pinned version of its own: a launch in flight never
+ * sees a later call's mask; an all-zero mask launches nothing).  On a collector whose host shadow is valid the host writes the
+ * constructor's values into the shadow itself: the next sdrhip_*_submit_datagrams still reads nothing back.  Allowed between any
+ * two calls, also between two submits while batches are in flight: those keep what they were enqueued with.  After a partial
+ * sdrhip_rx_reset_streams the streams stand at different frame positions: sdrhip_rx_process takes its ragged step, and
+ * sdrhip_rx_set_pipelined(1) / sdrhip_rx_submit refuse as they do after ragged calls (a pipe that IS pipelined cannot take the
+ * ragged step: leave pipelined mode, or reset the whole pipe, before the next sdrhip_rx_process).  A reset of EVERY stream (NULL,
+ * or a mask that names them all) also puts every stream's frame window back to the start of the frame area, whatever ragged
+ * calls moved the windows apart before: the streams stand at the same position again, and the uniform step, pipelined mode and
+ * uniform batches are available as on a fresh handle.
+ * SDRHIP_EINVAL, nothing changed: a NULL handle; on a pipe, a uniform or ragged batch that is being filled (collect it first), and
+ * frames or a batch of a pipelined pipe that wait for delivery (sdrhip_*_flush first).
+ * A handle on which none of these was called launches exactly what it launched before they existed. */
+int sdrhip_decimators_reset_streams(sdrhip_decimators *d, const uint8_t *mask);
+int sdrhip_interpolators_reset_streams(sdrhip_interpolators *p, const uint8_t *mask);
+int sdrhip_fecbuf_reset_streams(sdrhip_fecbuf *b, const uint8_t *mask);
+int sdrhip_rx_reset_streams(sdrhip_rx *rx, const uint8_t *mask);
+int sdrhip_tx_reset_streams(sdrhip_tx *tx, const uint8_t *mask);
+/* Export and import of ONE stream: what carries a live stream from one bank to another (a hub rebalancing "stream s on rank
+ * s mod N", a process replaced without a glitch), the way a checkpointed sdrdaemonrx / sdrdaemontx would be carried.
+ * The blob is host memory, opaque, sdrhip_*_stream_state_bytes() long: fixed per kind, independent of the configuration (0 for a
+ * NULL handle).  It starts with a 16-byte header {magic "SDRS", version 1, kind 1 = rx / 2 = tx, total bytes}.  An Rx blob holds
+ * hb_variant; the stream's decimator row (the six histories of Decimators.h:56-70) and whether its first-stage history fits int16;
+ * r_pending, r_open and r_count (UDPSinkFEC's sample index, open frame and m_frameCount); the 128 super blocks of the open frame with
+ * the meta block it was opened with (UDPSinkFEC.cpp:160-165); a "has collector" flag and, with a collector, the stream's
+ * SDRdaemonFECBuffer state, the 128 super blocks of its current carry buffer, and its held-back samples (at most 63) with their
+ * count.  A Tx blob holds the interpolator row (Interpolators.h:47-52) and the same collector part.
+ * Export leaves the source untouched; it synchronises once (one gather launch, one copy of the packed bytes, one wait).
+ * Import makes stream `stream` of the destination -- any Rx or Tx bank, on any context, of any nstreams -- continue exactly where
+ * the source stream stood: it enqueues ONE upload and ONE scatter launch on the context's stream and does not synchronise (the
+ * upload is staged in the next of four pinned buffers of the handle: only a fifth import in a row waits, for the upload of the
+ * first; the
+ * first import that must create the bank's collector, its rows or its frame area allocates them, as a first call does).  The
+ * destination's own log2decim, fcpos, nb_fec, meta arrays and log2interp apply from then on, as after sdrhip_*_reconfigure: the open
+ * frame keeps its meta block and is encoded with the fecblk in force when it completes.  A blob without a collector leaves the
+ * stream of a bank that has one with the constructor's collector state.  Import clears the bank-wide "first-stage history fits
+ * int16" shortcut when the blob says so, and patches a valid collector shadow as the reset does.  The other streams of both banks
+ * run on undisturbed.
+ * SDRHIP_EINVAL, nothing changed: a NULL handle or blob; a wrong size, magic, version or kind; a blob of another hb_variant; a
+ * stream outside the bank; a blob whose fields no stream can be in; any asynchronous batch being filled or in flight; a
+ * pipelined pipe with frames or a batch waiting (flush first).
+ * A handle on which none of these was called launches exactly what it launched before they existed. */
+size_t sdrhip_rx_stream_state_bytes(const sdrhip_rx *rx);
+size_t sdrhip_tx_stream_state_bytes(const sdrhip_tx *tx);
+int sdrhip_rx_export_stream(sdrhip_rx *rx, int stream, void *blob, size_t bytes);
+int sdrhip_rx_import_stream(sdrhip_rx *rx, int stream, const void *blob, size_t bytes);
+int sdrhip_tx_export_stream(sdrhip_tx *tx, int stream, void *blob, size_t bytes);
+int sdrhip_tx_import_stream(sdrhip_tx *tx, int stream, const void *blob, size_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

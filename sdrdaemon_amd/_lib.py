@@ -42,6 +42,10 @@ EXPORTS = [
     "sdrhip_rx_submit_datagrams", "sdrhip_rx_collect_datagrams",
     "sdrhip_rx_set_stream_meta", "sdrhip_rx_get_stream_meta",
     "sdrhip_rx_set_follow_meta",
+    "sdrhip_decimators_reset_streams", "sdrhip_interpolators_reset_streams", "sdrhip_fecbuf_reset_streams",
+    "sdrhip_rx_reset_streams", "sdrhip_tx_reset_streams",
+    "sdrhip_rx_stream_state_bytes", "sdrhip_tx_stream_state_bytes", "sdrhip_rx_export_stream", "sdrhip_rx_import_stream",
+    "sdrhip_tx_export_stream", "sdrhip_tx_import_stream",
 ]
 
 
@@ -159,6 +163,13 @@ def load():
     lib.sdrhip_rx_set_stream_meta.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.sdrhip_rx_get_stream_meta.argtypes = [vp, i, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.sdrhip_rx_set_follow_meta.argtypes = [vp, i]
+    for name in ("decimators", "interpolators", "fecbuf", "rx", "tx"):
+        getattr(lib, "sdrhip_%s_reset_streams" % name).argtypes = [vp, C.POINTER(C.c_uint8)]
+    for name in ("rx", "tx"):
+        getattr(lib, "sdrhip_%s_stream_state_bytes" % name).argtypes = [vp]
+        getattr(lib, "sdrhip_%s_stream_state_bytes" % name).restype = sz
+        getattr(lib, "sdrhip_%s_export_stream" % name).argtypes = [vp, i, vp, sz]
+        getattr(lib, "sdrhip_%s_import_stream" % name).argtypes = [vp, i, vp, sz]
     lib.sdrhip_testsource_create.argtypes = [vp, i, C.POINTER(vp)]
     lib.sdrhip_testsource_destroy.argtypes = [vp]
     lib.sdrhip_testsource_destroy.restype = None

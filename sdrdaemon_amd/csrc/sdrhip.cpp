@@ -404,6 +404,7 @@ struct sdrhip_decimators {
     int r_nsub = 0, r_grid = 0;
     bool r_mfma = false;     // the last ragged_prepare planned the matrix-core launch (K1mr), r_mf holds its shared fields
     sdrhip::DecimArgs r_mf;
+    sdrhip::StreamMask reset_mask; // sdrhip_decimators_reset_streams
 };
 
 extern "C" int sdrhip_decimators_last_plan(const sdrhip_decimators *d, sdrhip_decim_plan *out)
@@ -444,6 +445,7 @@ extern "C" void sdrhip_decimators_destroy(sdrhip_decimators *d)
     (void)hipFree(d->state[0]);
     (void)hipFree(d->state[1]);
     d->rows_pin.release(); d->stage_pin.release(); d->out_pin.release(); d->rows_dev.release();
+    d->reset_mask.release();
     ctx_release(d->ctx);
     delete d;
 }
@@ -458,6 +460,31 @@ extern "C" int sdrhip_decimators_reset(sdrhip_decimators *d)
     d->cur = 0;
     d->stage0_int16 = true;
     return SDRHIP_OK;
+}
+
+namespace sdrhip {
+void decimators_reset_part(sdrhip_decimators *d, StreamResetArgs *a)
+{
+    a->rows[0] = d->state[0]; a->rows[1] = d->state[1];
+    a->row_words = DEC_STATE_WORDS;
+}
+void decimators_reset_done(sdrhip_decimators *d, bool all)
+{
+    // (bank-wide: the streams that were not reset may still hold rotate-sums in m_decimator2's history)
+    if (all) d->stage0_int16 = true;
+}
+int32_t *decimators_row(sdrhip_decimators *d, int s, int half) { return d->state[d->cur ^ (half & 1)] + (size_t)s * DEC_STATE_WORDS; }
+bool decimators_stage0_int16(const sdrhip_decimators *d) { return d->stage0_int16; }
+void decimators_clear_stage0_int16(sdrhip_decimators *d) { d->stage0_int16 = false; }
+} // namespace sdrhip
+
+extern "C" int sdrhip_decimators_reset_streams(sdrhip_decimators *d, const uint8_t *mask)
+{
+    if (!d) return fail(SDRHIP_EINVAL, "decimators is NULL");
+    sdrhip::CtxLock lock_(d->ctx);
+    return stream_reset_bank(d->ctx, d->reset_mask, mask, d->nstreams,
+                             [d](StreamResetArgs *a) { decimators_reset_part(d, a); },
+                             [d](const uint8_t *m) { decimators_reset_done(d, m == nullptr); });
 }
 
 namespace {

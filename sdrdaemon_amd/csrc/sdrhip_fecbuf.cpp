@@ -30,7 +30,55 @@ struct sdrhip_fecbuf {
     // ---- the Rx pipe fed datagrams (sdrhip_rx_process_datagrams): samples each stream holds back between calls (fecbuf_join_carry)
     DevBuf join_carry;
     std::vector<size_t> join_carry_host;
+    StreamMask reset_mask;       // sdrhip_fecbuf_reset_streams
 };
+
+namespace sdrhip {
+void fecbuf_fresh_state(FecBufState *x)
+{
+    memset(x, 0, sizeof(*x));
+    x->head = -1; x->maxrow = -1; x->b0 = -1;
+    x->min_blocks = 256;
+    // MetaDataFEC::init(): zero, m_nbFECBlocks = -1 (byte 11)
+    x->cur_meta[2] = x->out_meta[2] = 0xff000000u;
+}
+
+void fecbuf_reset_part(sdrhip_fecbuf *b, StreamResetArgs *a)
+{
+    a->fb[0] = b->state[0]; a->fb[1] = b->state[1];
+    a->carry = b->join_carry.as<unsigned>(); // (NULL while no datagram entry of an Rx pipe has run: nothing is held back)
+    fecbuf_fresh_state(&a->fb_init.st);
+}
+
+void fecbuf_reset_done(sdrhip_fecbuf *b, const uint8_t *mask)
+{
+    // the host's copies follow by themselves: no read-back, and the shadow stays valid for the next asynchronous batch
+    FecBufShadow fresh = FecBufShadow();
+    fresh.head = -1; fresh.maxrow = -1;
+    for (int s = 0; s < b->nstreams; ++s) {
+        if (mask && !mask[s]) continue;
+        if (b->shadow_ok) b->shadow[(size_t)s] = fresh;
+        if (b->join_carry.p) b->join_carry_host[(size_t)s] = 0;
+    }
+}
+
+void fecbuf_stream_ref(sdrhip_fecbuf *b, int s, FecBufStreamRef *out)
+{
+    out->st[0] = b->state[b->cur] + s; out->st[1] = b->state[b->cur ^ 1] + s;
+    out->carry = b->carry + (size_t)s * 128 * SDRHIP_UDPSIZE;
+    out->carry_half = (size_t)b->nstreams * 128 * SDRHIP_UDPSIZE;
+}
+
+void fecbuf_import_host(sdrhip_fecbuf *b, int s, const FecBufState &st, size_t carry)
+{
+    if (b->shadow_ok) {
+        FecBufShadow &h = b->shadow[(size_t)s];
+        h.head = st.head; h.count = st.count; h.recov = st.recov; h.maxrow = st.maxrow; h.dup = st.dup;
+        for (int q = 0; q < 4; ++q) h.pres[q] = st.pres[q];
+    }
+    if (b->join_carry.p) b->join_carry_host[(size_t)s] = carry;
+}
+} // namespace sdrhip
 
 namespace {
 constexpr size_t PAYLOAD = (size_t)127 * SDRHIP_BLOCK_BYTES;
@@ -169,13 +217,7 @@ int fecbuf_passes(sdrhip_fecbuf *b, const FecBufArgs &a, const long long *dg_off
 int fecbuf_init_state(sdrhip_fecbuf *b)
 {
     std::vector<FecBufState> st((size_t)b->nstreams);
-    for (FecBufState &x : st) {
-        memset(&x, 0, sizeof(x));
-        x.head = -1; x.maxrow = -1; x.b0 = -1;
-        x.min_blocks = 256;
-        // MetaDataFEC::init(): zero, m_nbFECBlocks = -1 (byte 11)
-        x.cur_meta[2] = x.out_meta[2] = 0xff000000u;
-    }
+    for (FecBufState &x : st) fecbuf_fresh_state(&x);
     b->cur = 0;
     b->shadow_ok = false;
     if (b->join_carry.p) { // (the remainder rows go with the collector)
@@ -274,6 +316,7 @@ extern "C" void sdrhip_fecbuf_destroy(sdrhip_fecbuf *b)
         b->pin_up.release(); b->pin_down.release(); b->pin_in.release();
         b->atab.release();
         b->join_carry.release();
+        b->reset_mask.release();
     }
     delete b;
     ctx_release(c);
@@ -286,6 +329,16 @@ extern "C" int sdrhip_fecbuf_reset(sdrhip_fecbuf *b)
     if (b->async_busy) return fail(SDRHIP_EINVAL, "fecbuf_reset: the owning pipe's asynchronous datagram batches are in flight: collect them first");
     HIP_TRY(hipSetDevice(b->ctx->device));
     return fecbuf_init_state(b);
+}
+
+// (on a pipe's own collector this is allowed while the pipe's datagram batches are in flight: they keep what they were enqueued
+// with, the launch goes behind them and the shadow already stands behind the last submit)
+extern "C" int sdrhip_fecbuf_reset_streams(sdrhip_fecbuf *b, const uint8_t *mask)
+{
+    if (!b) return fail(SDRHIP_EINVAL, "fecbuf is NULL");
+    sdrhip::CtxLock lock_(b->ctx);
+    return stream_reset_bank(b->ctx, b->reset_mask, mask, b->nstreams,
+                             [b](StreamResetArgs *a) { fecbuf_reset_part(b, a); }, [b](const uint8_t *m) { fecbuf_reset_done(b, m); });
 }
 
 namespace {

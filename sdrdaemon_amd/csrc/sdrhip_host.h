@@ -4,6 +4,7 @@
 #include "sdrhip_internal.h"
 
 #include <cstdint>
+#include <cstring>
 #include <atomic>
 #include <map>
 #include <mutex>
@@ -229,6 +230,45 @@ int fec_decode_device(sdrhip_ctx *ctx, const uint8_t *rx, size_t rx_frame_bytes,
 // sdrhip_host_alloc memory: pinned, usable in place
 bool host_is_pinned(const void *p, size_t n);
 
+// ---- per-stream lifecycle (sdrhip_*_reset_streams, sdrhip_stream_state.cpp).  The mask of a call goes up like the Rx pipe's
+// stream-meta table: from the next of four pinned versions (reuse waits for that version's own upload, four calls back) into the
+// device copy the previous call does not occupy -- a launch in flight never sees a later call's mask
+struct StreamMask {
+    PinnedBuf pin[4];
+    DevBuf dev[2];
+    int pin_sel = 0, dev_sel = 0;
+    void release();
+};
+// counts the streams `mask` names (NULL: all S) into *n_set.  *dev = NULL when it names none or all of them (nothing is enqueued),
+// else the device copy, enqueued on the context's stream
+int stream_mask_upload(sdrhip_ctx *c, StreamMask &m, const uint8_t *mask, int S, const uint8_t **dev, int *n_set);
+// the handles' parts of KR's arguments (*_reset_part: they change nothing), and the host side of the reset, once the launch is out
+// (*_reset_done; all: every stream was reset, else `mask` names them): decimators: stage0_int16 becomes true only when every
+// stream was reset; collector: a valid shadow gets the constructor's values for the streams reset (it stays valid: the next
+// asynchronous batch reads nothing back), and so does the host's copy of the carry
+void decimators_reset_part(sdrhip_decimators *d, StreamResetArgs *a);
+void decimators_reset_done(sdrhip_decimators *d, bool all);
+void interpolators_reset_part(sdrhip_interpolators *p, StreamResetArgs *a);
+void fecbuf_reset_part(sdrhip_fecbuf *b, StreamResetArgs *a);
+void fecbuf_reset_done(sdrhip_fecbuf *b, const uint8_t *mask); // mask NULL: every stream
+void fecbuf_fresh_state(FecBufState *x); // what SDRdaemonFECBuffer's constructor leaves
+int stream_reset_launch(sdrhip_ctx *c, const StreamResetArgs &a);
+// ---- export / import of one stream (sdrhip_*_export_stream / _import_stream): where the handles keep stream s
+// the stream's history row in the current half (half = 0: what the next call reads) or the other one
+int32_t *decimators_row(sdrhip_decimators *d, int s, int half);
+int32_t *interpolators_row(sdrhip_interpolators *p, int s, int half);
+bool decimators_stage0_int16(const sdrhip_decimators *d);
+void decimators_clear_stage0_int16(sdrhip_decimators *d); // an imported history may hold rotate-sums
+struct FecBufStreamRef {
+    FecBufState *st[2];   // [0]: the committed half
+    uint8_t *carry;       // the stream's 128 super blocks in carry buffer 0; buffer 1 lies carry_half bytes behind
+    size_t carry_half;
+};
+void fecbuf_stream_ref(sdrhip_fecbuf *b, int s, FecBufStreamRef *out);
+// the host side of an import: a valid shadow takes the stream's classification part of `st` (it stays valid), the host's copy of
+// the carry takes `carry`
+void fecbuf_import_host(sdrhip_fecbuf *b, int s, const FecBufState &st, size_t carry);
+
 } // namespace sdrhip
 
 #define SDRHIP_KCLASSES 5 // SDRHIP_K_DECIMATE .. SDRHIP_K_CONVERT
@@ -368,5 +408,21 @@ inline hipError_t link_copy2d(sdrhip_ctx *c, void *dst, size_t dpitch, const voi
     const hipError_t e = hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height, kind, stream);
     if (e == hipSuccess) link_bytes(c, kind, width * height);
     return e;
+}
+// the whole call of every reset entry, banks and pipes alike: mask up, `fill` the handle's parts of the arguments, KR, and only
+// behind a launch that went out `done(mask)`, the host's bookkeeping (mask NULL: every stream was reset)
+template <class F, class D> int stream_reset_bank(sdrhip_ctx *c, StreamMask &m, const uint8_t *mask, int S, F fill, D done)
+{
+    HIP_TRY(hipSetDevice(c->device));
+    StreamResetArgs a;
+    memset(&a, 0, sizeof(a));
+    int n_set = 0;
+    if (int rc = stream_mask_upload(c, m, mask, S, &a.mask, &n_set)) return rc;
+    if (n_set == 0) return SDRHIP_OK; // (an all-zero mask launches nothing)
+    a.nstreams = S;
+    fill(&a);
+    if (int rc = stream_reset_launch(c, a)) return rc;
+    done(n_set == S ? nullptr : mask);
+    return SDRHIP_OK;
 }
 } // namespace sdrhip

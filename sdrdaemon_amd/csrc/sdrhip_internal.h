@@ -580,4 +580,44 @@ constexpr uint64_t GATHER_WG_BYTES = 16384; // 16-byte-aligned output bytes per 
 uint32_t gather_plan(GatherSeg *segs, int nseg);
 hipError_t launch_delivery_gather(const GatherSeg *segs, int nseg, uint32_t grid, uint8_t *out, hipStream_t stream);
 
+// KR (stream_state_kernels.hip, sdrhip_*_reset_streams): the streams whose mask byte is set go back to constructor state, in one
+// launch over (stream, piece of state).  Every part is optional: a bank's handle fills in its own, a pipe's handle those of its
+// filter bank and of its collector
+struct StreamResetArgs {
+    const uint8_t *mask;   // [nstreams] on the device; NULL: every stream
+    int nstreams;
+    int row_words;         // int32 words per stream of a history row (DEC_STATE_WORDS / INT_STATE_WORDS), a multiple of 4
+    int32_t *rows[2];      // both halves of the double-buffered filter histories (zero filled); NULL: none
+    FecBufState *fb[2];    // both halves of the collector state (set to fb_init); NULL: none
+    unsigned *carry;       // the samples every stream holds back in front of its decimator (zeroed); NULL: none
+    union { FecBufState st; unsigned w[sizeof(FecBufState) / sizeof(unsigned)]; } fb_init; // the constructor's state (fecbuf_fresh_state)
+};
+hipError_t launch_stream_reset(const StreamResetArgs &a, hipStream_t stream);
+// KG / KS (sdrhip_*_export_stream / _import_stream): the scattered pieces of one stream's state <-> one contiguous device blob, as KD
+// packs a delivery: segment i = `bytes` (a multiple of 16) from src to dst, both 16-byte aligned; the segments travel in the
+// kernel's arguments (no table to upload).  Workgroup w serves the segment whose wg0 range holds it (stream_copy_plan)
+constexpr int STREAM_COPY_MAX_SEGS = 8;
+constexpr uint32_t STREAM_COPY_WG_BYTES = 16384; // bytes per workgroup (256 lanes x 4 chunks of 16 bytes)
+struct StreamCopySeg {
+    const uint8_t *src;
+    uint8_t *dst;
+    uint32_t bytes, wg0;
+};
+struct StreamCopyArgs {
+    StreamCopySeg seg[STREAM_COPY_MAX_SEGS];
+    int nseg;
+    // KG: which of the two carry buffers holds the collector's open slot stands in the stream's state on the device:
+    // seg[carry_seg].src += cbuf_from->cbuf * carry_half bytes (carry_seg = -1: no such segment)
+    int carry_seg;
+    const FecBufState *cbuf_from;
+    size_t carry_half;
+    // KS: the stream's count of held-back samples, one word beside the segments (NULL: none)
+    unsigned *word_dst;
+    unsigned word_val;
+};
+// fills every segment's wg0, returns the grid (0: no segment, a misaligned or empty one)
+uint32_t stream_copy_plan(StreamCopyArgs *a);
+hipError_t launch_stream_gather(const StreamCopyArgs &a, uint32_t grid, hipStream_t stream);
+hipError_t launch_stream_scatter(const StreamCopyArgs &a, uint32_t grid, hipStream_t stream);
+
 } // namespace sdrhip

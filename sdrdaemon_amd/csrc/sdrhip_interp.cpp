@@ -12,6 +12,7 @@ struct sdrhip_interpolators {
     int nstreams;
     int32_t *state[2]; // [nstreams][INT_STATE_WORDS]
     int cur;
+    sdrhip::StreamMask reset_mask; // sdrhip_interpolators_reset_streams
 };
 
 extern "C" int sdrhip_interpolators_create(sdrhip_ctx *ctx, int nstreams, sdrhip_interpolators **out)
@@ -41,6 +42,7 @@ extern "C" void sdrhip_interpolators_destroy(sdrhip_interpolators *p)
     (void)hipStreamSynchronize(p->ctx->stream);
     (void)hipFree(p->state[0]);
     (void)hipFree(p->state[1]);
+    p->reset_mask.release();
     ctx_release(p->ctx);
     delete p;
 }
@@ -54,6 +56,23 @@ extern "C" int sdrhip_interpolators_reset(sdrhip_interpolators *p)
     HIP_TRY(hipMemsetAsync(p->state[1], 0, bytes, p->ctx->stream));
     p->cur = 0;
     return SDRHIP_OK;
+}
+
+namespace sdrhip {
+void interpolators_reset_part(sdrhip_interpolators *p, StreamResetArgs *a)
+{
+    a->rows[0] = p->state[0]; a->rows[1] = p->state[1];
+    a->row_words = INT_STATE_WORDS;
+}
+int32_t *interpolators_row(sdrhip_interpolators *p, int s, int half) { return p->state[p->cur ^ (half & 1)] + (size_t)s * INT_STATE_WORDS; }
+} // namespace sdrhip
+
+extern "C" int sdrhip_interpolators_reset_streams(sdrhip_interpolators *p, const uint8_t *mask)
+{
+    if (!p) return fail(SDRHIP_EINVAL, "interpolators is NULL");
+    sdrhip::CtxLock lock_(p->ctx);
+    return stream_reset_bank(p->ctx, p->reset_mask, mask, p->nstreams,
+                             [p](StreamResetArgs *a) { interpolators_reset_part(p, a); }, [](const uint8_t *) {});
 }
 
 namespace sdrhip {

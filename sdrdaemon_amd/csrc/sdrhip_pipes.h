@@ -191,6 +191,12 @@ struct sdrhip_rx {
     // ---- outgoing meta from the incoming meta blocks (sdrhip_rx_set_follow_meta): a host flag, read by the datagram entries per call
     // and per batch at its submit; KF (rx_follow_kernels.hip) then rewrites the rows of the streams that have incoming meta
     int follow_meta = 0;
+    // ---- per-stream lifecycle (sdrhip_rx_reset_streams): the mask's versions on their way up; sdrhip_rx_export_stream /
+    // _import_stream: the contiguous device blob KG packs / KS unpacks, and the pinned staging of an import's upload
+    sdrhip::StreamMask reset_mask;
+    sdrhip::DevBuf x_blob;
+    sdrhip::PinnedBuf x_pin[4]; // (four versions: an import waits for the upload four imports back, not for the previous one)
+    int x_pin_sel = 0;
 };
 
 // --------------------------------------------------------------------------- fused Tx pipe
@@ -250,6 +256,12 @@ struct sdrhip_tx {
     sdrhip_fecbuf *fb = nullptr;
     // ---- output format (sdrhip_tx_set_output_format): IQF_S8 = 2-byte samples from the interpolator's last stage (or K6n for x1)
     int out_fmt = sdrhip::IQF_S16;
+    // ---- per-stream lifecycle (sdrhip_tx_reset_streams): the mask's versions on their way up; sdrhip_tx_export_stream /
+    // _import_stream: the contiguous device blob KG packs / KS unpacks, and the pinned staging of an import's upload
+    sdrhip::StreamMask reset_mask;
+    sdrhip::DevBuf x_blob;
+    sdrhip::PinnedBuf x_pin[4]; // (four versions: an import waits for the upload four imports back, not for the previous one)
+    int x_pin_sel = 0;
 };
 
 namespace sdrhip {
@@ -293,6 +305,7 @@ int rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, size_t in
 // straight into the windows.  rx_ragged itself then allocates nothing, unless a matrix-core plan it counted on does not apply
 int rx_ragged_room(sdrhip_rx *rx, const size_t *n_in, RxTabs *tabs);
 int rx_collector(sdrhip_rx *rx); // the datagram collector, created on first use
+int rx_area_room(sdrhip_rx *rx); // a frame area with at least one slot per stream (sdrhip_rx_import_stream into a bank that never ran)
 
 // ---- Tx: bytes per output sample, and the row pitch (samples) of the library's own output buffers: 16-byte rows either way
 inline size_t tx_esz(const sdrhip_tx *tx) { return tx->out_fmt == IQF_S8 ? 2 : 4; }

@@ -156,6 +156,9 @@ extern "C" void sdrhip_rx_destroy(sdrhip_rx *rx)
     rx->j_rows.release();
     for (auto &b : rx->sm_pin) b.release();
     for (auto &b : rx->sm_dev) b.release();
+    rx->reset_mask.release();
+    rx->x_blob.release();
+    for (auto &b : rx->x_pin) b.release();
     delete rx;
 }
 
@@ -670,6 +673,8 @@ static int rx_grow_area(sdrhip_rx *rx, size_t need_max)
     rx->cap_frames = ncap;
     return SDRHIP_OK;
 }
+
+int sdrhip::rx_area_room(sdrhip_rx *rx) { return rx->cap_frames ? SDRHIP_OK : rx_grow_area(rx, 1); }
 
 int sdrhip::rx_ragged_room(sdrhip_rx *rx, const size_t *n_in, RxTabs *tabs)
 {

@@ -49,6 +49,9 @@ extern "C" void sdrhip_tx_destroy(sdrhip_tx *tx)
     tx->plan_own.release(); tx->idx_own.release(); tx->pin_own.release();
     tx->ring.release(true);
     tx->a_pk.release(); tx->a_pay.release(); tx->a_out.release(); tx->a_b0.release(); tx->a_gat.release(); tx->a_seg.release();
+    tx->reset_mask.release();
+    tx->x_blob.release();
+    for (auto &b : tx->x_pin) b.release();
     if (tx->ev_in) (void)hipEventDestroy(tx->ev_in);
     if (tx->ev_up) (void)hipEventDestroy(tx->ev_up);
     if (tx->ev_dec) (void)hipEventDestroy(tx->ev_dec);

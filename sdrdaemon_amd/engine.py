@@ -199,6 +199,31 @@ def _counts(counts, S, n):
     return cnt
 
 
+def _stream_mask(streams, S):
+    """the mask argument of the sdrhip_*_reset_streams entries: None = NULL (every stream), else one byte per stream"""
+    if streams is None:
+        return None
+    m = (C.c_uint8 * S)()
+    for s in streams:
+        s = int(s)
+        if not 0 <= s < S:
+            raise ValueError("stream %d of %d" % (s, S))
+        m[s] = 1
+    return m
+
+
+def _export_stream(ctx, kind, h, stream):
+    n = getattr(ctx.lib, "sdrhip_%s_stream_state_bytes" % kind)(h)
+    buf = C.create_string_buffer(n)
+    check(getattr(ctx.lib, "sdrhip_%s_export_stream" % kind)(h, int(stream), buf, n))
+    return buf.raw
+
+
+def _import_stream(ctx, kind, h, stream, blob):
+    blob = bytes(blob)
+    check(getattr(ctx.lib, "sdrhip_%s_import_stream" % kind)(h, int(stream), blob, len(blob)))
+
+
 def _plan_dict(fn, h):
     p = _lib.DecimPlan()
     check(fn(h, C.byref(p)))
@@ -214,8 +239,13 @@ class Decimators:
         self.h = C.c_void_p()
         check(ctx.lib.sdrhip_decimators_create(ctx.h, nstreams, hb_variant, C.byref(self.h)))
 
-    def reset(self):
-        check(self.ctx.lib.sdrhip_decimators_reset(self.h))
+    def reset(self, streams=None):
+        """constructor state: every stream (sdrhip_decimators_reset), or the streams listed (sdrhip_decimators_reset_streams:
+        on the device, no synchronisation, the others run on)"""
+        if streams is None:
+            check(self.ctx.lib.sdrhip_decimators_reset(self.h))
+        else:
+            check(self.ctx.lib.sdrhip_decimators_reset_streams(self.h, _stream_mask(streams, self.nstreams)))
 
     def decimate(self, log2decim, fcpos, sample_size, iq, out=None):
         """Decimators::decimate<2^log2decim>_{inf,sup,cen}(sampleSize, in, out).
@@ -388,8 +418,12 @@ class Interpolators:
         self.h = C.c_void_p()
         check(ctx.lib.sdrhip_interpolators_create(ctx.h, nstreams, C.byref(self.h)))
 
-    def reset(self):
-        check(self.ctx.lib.sdrhip_interpolators_reset(self.h))
+    def reset(self, streams=None):
+        """constructor state: every stream (sdrhip_interpolators_reset), or the streams listed (sdrhip_interpolators_reset_streams)"""
+        if streams is None:
+            check(self.ctx.lib.sdrhip_interpolators_reset(self.h))
+        else:
+            check(self.ctx.lib.sdrhip_interpolators_reset_streams(self.h, _stream_mask(streams, self.nstreams)))
 
     def interpolate(self, log2interp, iq, out=None):
         """Interpolators::interpolate<2^log2interp>_cen(in, out)."""
@@ -1025,6 +1059,22 @@ class RxPipe:
         """the statistics of one stream's collector (sdrhip_rx_collector + sdrhip_fecbuf_stats): the dict of FECBufferBank.stats"""
         return _fecbuf_stats(self.ctx, self._collector(), stream)
 
+    def reset_streams(self, streams=None):
+        """sdrhip_rx_reset_streams: the streams listed (None: every stream, the whole-pipe reset) begin again as a restarted
+        sdrdaemonrx does -- zero decimator histories, the open frame dropped, m_frameCount 0, a fresh collector and no carry --
+        while the others run on.  One small launch, no synchronisation."""
+        check(self.ctx.lib.sdrhip_rx_reset_streams(self.h, _stream_mask(streams, self.nstreams)))
+
+    def export_stream(self, stream):
+        """sdrhip_rx_export_stream: the state of one stream as opaque bytes (histories, open frame, collector, held-back samples);
+        the source is left untouched.  Synchronises once."""
+        return _export_stream(self.ctx, "rx", self.h, stream)
+
+    def import_stream(self, stream, blob):
+        """sdrhip_rx_import_stream: stream `stream` of this bank continues where the exported stream stood, under this bank's
+        own configuration; the bank's other streams run on.  One upload, one launch, no synchronisation."""
+        _import_stream(self.ctx, "rx", self.h, stream, blob)
+
     def reset_collector(self):
         """sdrhip_fecbuf_reset on the handle's collector: the constructor's state, and every stream's carry cleared"""
         check(self.ctx.lib.sdrhip_fecbuf_reset(self._collector()))
@@ -1285,6 +1335,21 @@ class TxPipe:
             res.append((out[s, :n], b0[s, :k], recs))
         return res
 
+    def reset_streams(self, streams=None):
+        """sdrhip_tx_reset_streams: the streams listed (None: every stream) begin again as a restarted sdrdaemontx does -- zero
+        interpolator histories and a fresh collector -- while the others run on.  One small launch, no synchronisation."""
+        check(self.ctx.lib.sdrhip_tx_reset_streams(self.h, _stream_mask(streams, self.nstreams)))
+
+    def export_stream(self, stream):
+        """sdrhip_tx_export_stream: the state of one stream as opaque bytes (interpolator histories, collector); the source is
+        left untouched.  Synchronises once."""
+        return _export_stream(self.ctx, "tx", self.h, stream)
+
+    def import_stream(self, stream, blob):
+        """sdrhip_tx_import_stream: stream `stream` of this bank continues where the exported stream stood; the bank's other
+        streams run on.  One upload, one launch, no synchronisation."""
+        _import_stream(self.ctx, "tx", self.h, stream, blob)
+
     def collector_stats(self, stream):
         """the statistics of one stream's collector (sdrhip_tx_collector + sdrhip_fecbuf_stats): the dict of FECBufferBank.stats"""
         h = C.c_void_p()
@@ -1328,8 +1393,13 @@ class FECBufferBank:
             self.ctx.lib.sdrhip_fecbuf_destroy(h)
             self.h = C.c_void_p()
 
-    def reset(self):
-        check(self.ctx.lib.sdrhip_fecbuf_reset(self.h))
+    def reset(self, streams=None):
+        """constructor state: every stream (sdrhip_fecbuf_reset), or the streams listed (sdrhip_fecbuf_reset_streams: on the
+        device, no synchronisation, the others collect on)"""
+        if streams is None:
+            check(self.ctx.lib.sdrhip_fecbuf_reset(self.h))
+        else:
+            check(self.ctx.lib.sdrhip_fecbuf_reset_streams(self.h, _stream_mask(streams, self.nstreams)))
 
     def write_and_read(self, dgrams_per_stream, max_frames=None):
         S = self.nstreams
