@@ -682,6 +682,37 @@ int sdrhip_rx_submit_datagrams(sdrhip_rx *rx, const uint8_t *dgrams, const size_
 int sdrhip_rx_collect_datagrams(sdrhip_rx *rx, uint8_t *frames_out, size_t frame_stride_bytes, size_t max_frames,
                                 size_t max_released, sdrhip_fecbuf_frame *info_out, size_t *n_released, size_t *n_frames, int wait);
 
+/* ------------------------------------------------------------ Tagged datagram batches -- */
+/* A hub receives on ONE socket (recvmmsg): one array of 512-byte datagrams from all its radio heads, interleaved in arrival order.
+ * The datagram header (frameIndex, blockIndex, filler) does not name the stream; the source address does, and only the host sees
+ * it.  The tagged entries take that array as it is: dgrams holds n_total datagrams of 512 bytes back to back, in arrival order;
+ * stream_of[i] (host array) is the stream of datagram i, or SDRHIP_DGRAM_SKIP for one that belongs to no stream of the bank
+ * (unknown peer, wrong length).
+ * Meaning: a tagged call is the untagged call of the same name with SDRHIP_PACKED input in which stream s's row is the subsequence
+ * of the datagrams tagged s, in arrival order; skipped datagrams are in no row.  Everything else -- outputs, records, counts,
+ * collector state, carry, histories, open frames, counters, the host's shadow, the refusals with nothing consumed -- is byte for
+ * byte what the untagged call gives for those rows and leaves behind.  A batch submitted tagged is collected with
+ * sdrhip_tx_collect_datagrams / sdrhip_rx_collect_datagrams; tagged and untagged calls may alternate on one handle.
+ * How: the host walks the tags and the 4-byte headers once, in arrival order (the headers feed its shadow of the classification,
+ * as they do for an untagged batch), and gives every datagram its place among its stream's; the array goes up unsorted with that
+ * table, and one kernel (KX) puts it in the order the collector's passes read.  No host core touches a payload.
+ * SDRHIP_EINVAL with nothing consumed, on top of everything the untagged twin refuses: a tag that is >= nstreams and not
+ * SDRHIP_DGRAM_SKIP, stream_of == NULL with n_total > 0, a bank of more than 65535 streams.  The tags are checked before anything
+ * is staged or moved.
+ * Memory: for the two submits dgrams is host memory, used in place when it lies in sdrhip_host_alloc memory (recvmmsg straight
+ * into it; leave it untouched until the batch is collected) and staged with ONE memcpy otherwise (the buffer is the caller's again
+ * on return).  For the bank call mem means what it means for sdrhip_fecbuf_write_and_read; stream_of is always host memory; with
+ * SDRHIP_MEM_DEVICE dgrams must be 16-byte aligned.
+ * Link traffic of a submit ("h2d_bytes"): 512 bytes per datagram, skipped ones included, and 4 bytes per datagram for the table
+ * of places; nothing per stream.  Down ("d2h_bytes"): what the untagged twin brings down. */
+#define SDRHIP_DGRAM_SKIP 0xffffu   /* a datagram that belongs to no stream of the bank (unknown peer, wrong length) */
+int sdrhip_fecbuf_write_and_read_tagged(sdrhip_fecbuf *b, const uint8_t *dgrams, const uint16_t *stream_of, size_t n_total,
+                                        uint8_t *data_out, size_t data_stride_bytes, uint8_t *block0_out, size_t max_frames,
+                                        sdrhip_fecbuf_frame *info_out, size_t *n_frames, int mem);
+int sdrhip_tx_submit_datagrams_tagged(sdrhip_tx *tx, const uint8_t *dgrams, const uint16_t *stream_of, size_t n_total);
+int sdrhip_rx_submit_datagrams_tagged(sdrhip_rx *rx, const uint8_t *dgrams, const uint16_t *stream_of, size_t n_total,
+                                      const uint32_t *tv_sec, const uint32_t *tv_usec);
+
 /* ---- Per-stream lifecycle: one stream of a bank begins again while the others run on.
  * In the reference one stream is one sdrdaemonrx / sdrdaemontx process, and restarting that process gives the stream what the
  * constructors leave: zero half-band histories (Decimators.h:56-70, Interpolators.h:47-52: EO1.h:171-188 / IntHalfbandFilterDB's

@@ -19,6 +19,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SDRHIP_LIB_PATH") or os.path.join(HERE, "libsdrhip.so")
 
 MEM_HOST, MEM_DEVICE = 0, 1
+DGRAM_SKIP = 0xffff  # SDRHIP_DGRAM_SKIP
 FC_INF, FC_SUP, FC_CEN = 0, 1, 2
 HB_EO1, HB_DB = 0, 1
 IQ_S16, IQ_U8, IQ_S8 = 0, 1, 2
@@ -46,6 +47,7 @@ EXPORTS = [
     "sdrhip_rx_reset_streams", "sdrhip_tx_reset_streams",
     "sdrhip_rx_stream_state_bytes", "sdrhip_tx_stream_state_bytes", "sdrhip_rx_export_stream", "sdrhip_rx_import_stream",
     "sdrhip_tx_export_stream", "sdrhip_tx_import_stream",
+    "sdrhip_fecbuf_write_and_read_tagged", "sdrhip_tx_submit_datagrams_tagged", "sdrhip_rx_submit_datagrams_tagged",
 ]
 
 
@@ -160,6 +162,10 @@ def load():
     lib.sdrhip_rx_carry.argtypes = [vp, C.POINTER(sz)]
     lib.sdrhip_rx_submit_datagrams.argtypes = [vp, vp, C.POINTER(sz), sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.sdrhip_rx_collect_datagrams.argtypes = [vp, vp, sz, sz, sz, vp, C.POINTER(sz), C.POINTER(sz), i]
+    u16p = C.POINTER(C.c_uint16)
+    lib.sdrhip_fecbuf_write_and_read_tagged.argtypes = [vp, vp, u16p, sz, vp, sz, vp, sz, vp, C.POINTER(sz), i]
+    lib.sdrhip_tx_submit_datagrams_tagged.argtypes = [vp, vp, u16p, sz]
+    lib.sdrhip_rx_submit_datagrams_tagged.argtypes = [vp, vp, u16p, sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.sdrhip_rx_set_stream_meta.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.sdrhip_rx_get_stream_meta.argtypes = [vp, i, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.sdrhip_rx_set_follow_meta.argtypes = [vp, i]

@@ -21,6 +21,7 @@ struct sdrhip_fecbuf {
     DevBuf small;                // ndg [S], job_off [S + 1], dbase [S], rec_base [S] (int64), counts [S][FB_COUNTS], pub [S][max_frames]
     DevBuf rec, stage, dmap, dec_out, dec_b0;
     DevBuf hin, hout, hb0;       // SDRHIP_MEM_HOST staging on the device
+    DevBuf demux;                // sdrhip_fecbuf_write_and_read_tagged: the places of the datagrams, then the rows KX sorted them into
     PinnedBuf pin_up, pin_down, pin_in;
     // ---- asynchronous Tx batches (sdrhip_tx_submit_datagrams): the host's shadow of the classification part of state[cur]
     std::vector<FecBufShadow> shadow;
@@ -312,7 +313,7 @@ extern "C" void sdrhip_fecbuf_destroy(sdrhip_fecbuf *b)
         (void)hipStreamSynchronize(c->stream);
         (void)hipFree(b->state[0]); (void)hipFree(b->state[1]); (void)hipFree(b->carry);
         b->small.release(); b->rec.release(); b->stage.release(); b->dmap.release(); b->dec_out.release(); b->dec_b0.release();
-        b->hin.release(); b->hout.release(); b->hb0.release();
+        b->hin.release(); b->hout.release(); b->hb0.release(); b->demux.release();
         b->pin_up.release(); b->pin_down.release(); b->pin_in.release();
         b->atab.release();
         b->join_carry.release();
@@ -394,6 +395,25 @@ int upload_dgrams(sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgram
     if (src != dgrams) b->pin_in.mark(c->stream);
     return SDRHIP_OK;
 }
+
+// the output arguments of the bank's call (`who`: sdrhip_fecbuf_write_and_read and its tagged twin), and their alignment on the device
+int check_outputs(int S, const uint8_t *data_out, size_t data_stride_bytes, size_t max_frames, const sdrhip_fecbuf_frame *info_out, const char *who)
+{
+    if (max_frames > 0 && (!data_out || !info_out)) return fail(SDRHIP_EINVAL, "%s: NULL data_out / info_out", who);
+    if (max_frames > 0x3fffffffu) return fail(SDRHIP_EINVAL, "%s: max_frames too large", who);
+    if (S > 1 && max_frames > 0 && data_stride_bytes < max_frames * PAYLOAD) return fail(SDRHIP_EINVAL, "%s: data_stride_bytes below max_frames x 127 x 508", who);
+    return SDRHIP_OK;
+}
+int check_outputs_aligned(int S, const uint8_t *data_out, size_t data_stride_bytes, const uint8_t *block0_out, const char *who)
+{
+    if ((reinterpret_cast<uintptr_t>(data_out) & 3u) || (reinterpret_cast<uintptr_t>(block0_out) & 3u) || (S > 1 && data_stride_bytes % 4))
+        return fail(SDRHIP_EALIGN, "%s: data_out / block0_out / data_stride_bytes must be 4-byte aligned", who);
+    return SDRHIP_OK;
+}
+// the call behind its checks.  staged (host memory): the datagrams are on the device already (fecbuf_collect)
+int write_and_read_checked(sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes, uint8_t *data_out,
+                           size_t data_stride_bytes, uint8_t *block0_out, size_t max_frames, sdrhip_fecbuf_frame *info_out, size_t *n_frames,
+                           int mem, const uint8_t *staged);
 } // namespace
 
 extern "C" int sdrhip_fecbuf_write_and_read(sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes,
@@ -409,16 +429,25 @@ extern "C" int sdrhip_fecbuf_write_and_read(sdrhip_fecbuf *b, const uint8_t *dgr
     size_t nmax = 0;
     int rc;
     if ((rc = check_dgrams(S, dgrams, n_dgrams, dgram_stride_bytes, mem, "fecbuf_write_and_read", &nmax))) return rc;
-    if (max_frames > 0 && (!data_out || !info_out)) return fail(SDRHIP_EINVAL, "fecbuf_write_and_read: NULL data_out / info_out");
-    if (max_frames > 0x3fffffffu) return fail(SDRHIP_EINVAL, "fecbuf_write_and_read: max_frames too large");
-    if (S > 1 && max_frames > 0 && data_stride_bytes < max_frames * PAYLOAD) return fail(SDRHIP_EINVAL, "fecbuf_write_and_read: data_stride_bytes below max_frames x 127 x 508");
+    if ((rc = check_outputs(S, data_out, data_stride_bytes, max_frames, info_out, "fecbuf_write_and_read"))) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if (mem == SDRHIP_MEM_DEVICE) {
         if ((nmax > 0 && !aligned16(dgrams)) || (S > 1 && dgram_stride_bytes % 16))
             return fail(SDRHIP_EALIGN, "fecbuf_write_and_read: dgrams / dgram_stride_bytes must be 16-byte aligned");
-        if ((reinterpret_cast<uintptr_t>(data_out) & 3u) || (reinterpret_cast<uintptr_t>(block0_out) & 3u) || (S > 1 && data_stride_bytes % 4))
-            return fail(SDRHIP_EALIGN, "fecbuf_write_and_read: data_out / block0_out / data_stride_bytes must be 4-byte aligned");
+        if ((rc = check_outputs_aligned(S, data_out, data_stride_bytes, block0_out, "fecbuf_write_and_read"))) return rc;
     }
+    return write_and_read_checked(b, dgrams, n_dgrams, dgram_stride_bytes, data_out, data_stride_bytes, block0_out, max_frames, info_out, n_frames, mem,
+                                  nullptr);
+}
+
+namespace {
+int write_and_read_checked(sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes, uint8_t *data_out,
+                           size_t data_stride_bytes, uint8_t *block0_out, size_t max_frames, sdrhip_fecbuf_frame *info_out, size_t *n_frames,
+                           int mem, const uint8_t *staged)
+{
+    sdrhip_ctx *c = b->ctx;
+    const int S = b->nstreams;
+    int rc;
     // both memories go through fecbuf_collect (host: it stages the datagrams and downloads block 0).  Host memory adds only what its
     // other callers do not need, their data staying on the device: the frames go to b->hout and come down from there below
     const bool host = mem == SDRHIP_MEM_HOST;
@@ -426,7 +455,7 @@ extern "C" int sdrhip_fecbuf_write_and_read(sdrhip_fecbuf *b, const uint8_t *dgr
     if (host && drow && (rc = b->hout.reserve((size_t)S * drow + 4))) return rc;
     const int *counts = nullptr;
     rc = fecbuf_collect(b, dgrams, n_dgrams, dgram_stride_bytes, mem, host ? b->hout.as<uint8_t>() : data_out, host ? drow : data_stride_bytes,
-                        block0_out, max_frames, info_out, n_frames, &counts);
+                        block0_out, max_frames, info_out, n_frames, &counts, nullptr, staged);
     if (rc || !host) return rc;
     for (int s = 0; s < S; ++s)
         if (n_frames[s])
@@ -435,6 +464,7 @@ extern "C" int sdrhip_fecbuf_write_and_read(sdrhip_fecbuf *b, const uint8_t *dgr
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SDRHIP_OK;
 }
+} // namespace
 
 namespace sdrhip {
 int fecbuf_check_dgrams(const sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes, int mem, const char *who)
@@ -449,7 +479,7 @@ int fecbuf_check_dgrams(const sdrhip_fecbuf *b, const uint8_t *dgrams, const siz
 
 int fecbuf_collect(sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes, int mem, uint8_t *data_out,
                    size_t data_stride_bytes, uint8_t *block0_out, size_t max_frames, sdrhip_fecbuf_frame *info_out, size_t *n_frames,
-                   const int **counts, const FecBufJoin *join)
+                   const int **counts, const FecBufJoin *join, const uint8_t *staged)
 {
     sdrhip_ctx *c = b->ctx;
     const int S = b->nstreams;
@@ -461,8 +491,8 @@ int fecbuf_collect(sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgra
         for (int s = 0; s < S; ++s) nmax = n_dgrams[s] > nmax ? n_dgrams[s] : nmax;
         const size_t row = nmax * SDRHIP_UDPSIZE;
         if (block0_out && max_frames && (rc = b->hb0.reserve((size_t)S * max_frames * SDRHIP_BLOCK_BYTES))) return rc;
-        if ((rc = upload_dgrams(b, dgrams, n_dgrams, dgram_stride_bytes, row, join != nullptr))) return rc;
-        rc = fecbuf_device(b, b->hin.as<uint8_t>(), n_dgrams, row, data_out, data_stride_bytes, block0_out ? b->hb0.as<uint8_t>() : nullptr,
+        if (!staged && (rc = upload_dgrams(b, dgrams, n_dgrams, dgram_stride_bytes, row, join != nullptr))) return rc;
+        rc = fecbuf_device(b, staged ? staged : b->hin.as<uint8_t>(), n_dgrams, row, data_out, data_stride_bytes, block0_out ? b->hb0.as<uint8_t>() : nullptr,
                            max_frames, info_out, n_frames, join);
         if (!rc && block0_out)
             for (int s = 0; s < S; ++s)
@@ -502,36 +532,69 @@ int fecbuf_shadow(sdrhip_fecbuf *b, std::vector<FecBufShadow> *out)
     return SDRHIP_OK;
 }
 
+void fecbuf_shadow_step(FecBufShadow &h, uint32_t hd, int res[4])
+{
+    const int fi = (int)(hd & 0xffffu), bi = (int)((hd >> 16) & 0xffu);
+    if (fi != h.head) { // another frame index releases the open slot (the first datagram: the initial one)
+        ++res[0];
+        if (h.count >= 128 && h.recov > 0 && !h.dup) { // (to the decoder: the frames cm256_decode repairs)
+            ++res[1];
+            res[2] = h.maxrow > res[2] ? h.maxrow : res[2];
+            res[3] = h.recov > res[3] ? h.recov : res[3];
+        }
+        h.head = fi; h.count = 0; h.recov = 0; h.maxrow = -1; h.dup = 0;
+        h.pres[0] = h.pres[1] = h.pres[2] = h.pres[3] = 0u;
+    }
+    if (h.count < 128) { // (the first 128 arrivals)
+        if (bi >= 128) {
+            ++h.recov;
+            h.maxrow = bi - 128 > h.maxrow ? bi - 128 : h.maxrow;
+        } else {
+            const unsigned bit = 1u << (bi & 31);
+            if (h.pres[bi >> 5] & bit) h.dup = 1;
+            h.pres[bi >> 5] |= bit;
+        }
+    }
+    ++h.count;
+}
+
 void fecbuf_shadow_run(FecBufShadow &h, const uint8_t *dg, size_t n, int res[4])
 {
-    int K = 0, D = 0, maxrow = -1, maxrec = 0;
+    int r[4] = {0, 0, -1, 0}; // K, D, maxrow, maxrec
     for (size_t i = 0; i < n; ++i) {
         uint32_t hd;
         memcpy(&hd, dg + i * SDRHIP_UDPSIZE, 4);
-        const int fi = (int)(hd & 0xffffu), bi = (int)((hd >> 16) & 0xffu);
-        if (fi != h.head) { // another frame index releases the open slot (the first datagram: the initial one)
-            ++K;
-            if (h.count >= 128 && h.recov > 0 && !h.dup) { // (to the decoder: the frames cm256_decode repairs)
-                ++D;
-                maxrow = h.maxrow > maxrow ? h.maxrow : maxrow;
-                maxrec = h.recov > maxrec ? h.recov : maxrec;
-            }
-            h.head = fi; h.count = 0; h.recov = 0; h.maxrow = -1; h.dup = 0;
-            h.pres[0] = h.pres[1] = h.pres[2] = h.pres[3] = 0u;
-        }
-        if (h.count < 128) { // (the first 128 arrivals)
-            if (bi >= 128) {
-                ++h.recov;
-                h.maxrow = bi - 128 > h.maxrow ? bi - 128 : h.maxrow;
-            } else {
-                const unsigned bit = 1u << (bi & 31);
-                if (h.pres[bi >> 5] & bit) h.dup = 1;
-                h.pres[bi >> 5] |= bit;
-            }
-        }
-        ++h.count;
+        fecbuf_shadow_step(h, hd, r);
     }
-    res[0] = K; res[1] = D; res[2] = maxrow; res[3] = maxrec;
+    res[0] = r[0]; res[1] = r[1]; res[2] = r[2]; res[3] = r[3];
+}
+
+int fecbuf_tag_counts(int S, const uint8_t *dgrams, const uint16_t *stream_of, size_t n_total, const char *who, size_t *counts, size_t *sum,
+                      size_t *nmax)
+{
+    *sum = *nmax = 0;
+    for (int s = 0; s < S; ++s) counts[s] = 0;
+    if (S > 65535) return fail(SDRHIP_EINVAL, "%s: a bank of more than 65535 streams has no 16-bit tags", who);
+    if (n_total > 0x3fffffffu) return fail(SDRHIP_EINVAL, "%s: too many datagrams in one batch", who);
+    if (n_total && !stream_of) return fail(SDRHIP_EINVAL, "%s: NULL stream_of", who);
+    if (n_total && !dgrams) return fail(SDRHIP_EINVAL, "%s: NULL dgrams", who);
+    for (size_t i = 0; i < n_total; ++i) {
+        const unsigned t = stream_of[i];
+        if (t == SDRHIP_DGRAM_SKIP) continue;
+        if (t >= (unsigned)S) return fail(SDRHIP_EINVAL, "%s: stream_of[%zu] = %u is neither a stream of the bank nor SDRHIP_DGRAM_SKIP", who, i, t);
+        ++counts[t];
+    }
+    for (int s = 0; s < S; ++s) {
+        *sum += counts[s];
+        *nmax = counts[s] > *nmax ? counts[s] : *nmax;
+    }
+    return SDRHIP_OK;
+}
+
+// the places of a tagged array's datagrams: dest[i] = next[tag]++ (next[s] = stream s's first place on entry), 0xffffffff: skipped
+static void tag_dest(const uint16_t *tags, size_t n_total, size_t *next, uint32_t *dest)
+{
+    for (size_t i = 0; i < n_total; ++i) dest[i] = tags[i] == SDRHIP_DGRAM_SKIP ? 0xffffffffu : (uint32_t)next[tags[i]]++;
 }
 
 // ---- a batch of sdrhip_tx_submit_datagrams / sdrhip_rx_submit_datagrams (`who`) on its way up
@@ -540,11 +603,24 @@ int fecbuf_batch_check(FecBufBatch *in, int S, const uint8_t *dgrams, const size
     in->S = S; in->dgrams = dgrams; in->n_dgrams = n_dgrams; in->stride = dgram_stride_bytes;
     if (int e = count_dgrams(S, n_dgrams, who, "batch", &in->sum, &in->nmax)) return e;
     in->packed = dgram_stride_bytes == SDRHIP_PACKED || S == 1;
-    in->bytes_in = in->sum * SDRHIP_UDPSIZE;
+    in->bytes_in = in->dev_bytes = in->sum * SDRHIP_UDPSIZE;
     in->inplace = false;
     if (in->sum && !dgrams) return fail(SDRHIP_EINVAL, "%s: NULL dgrams", who);
     if (!in->packed && dgram_stride_bytes < in->nmax * SDRHIP_UDPSIZE)
         return fail(SDRHIP_EINVAL, "%s: dgram_stride_bytes is neither SDRHIP_PACKED nor at least the largest count x 512", who);
+    return SDRHIP_OK;
+}
+
+int fecbuf_batch_check_tagged(FecBufBatch *in, int S, const uint8_t *dgrams, const uint16_t *stream_of, size_t n_total, const char *who)
+{
+    in->S = S; in->dgrams = dgrams; in->stride = SDRHIP_PACKED;
+    in->packed = true; in->inplace = false;
+    in->tags = stream_of; in->n_total = n_total;
+    in->counts.assign((size_t)S, 0);
+    in->n_dgrams = in->counts.data();
+    if (int e = fecbuf_tag_counts(S, dgrams, stream_of, n_total, who, in->counts.data(), &in->sum, &in->nmax)) return e;
+    in->bytes_in = n_total * SDRHIP_UDPSIZE;
+    in->dev_bytes = in->sum * SDRHIP_UDPSIZE + n_total * (SDRHIP_UDPSIZE + sizeof(uint32_t));
     return SDRHIP_OK;
 }
 
@@ -554,8 +630,43 @@ static const uint8_t *row_of(const FecBufBatch &in, int s, size_t off)
     return in.packed ? in.dgrams + off : in.dgrams + (size_t)s * in.stride;
 }
 
-int fecbuf_batch_stage(FecBufBatch *in, PinnedBuf &arena, std::vector<FecBufShadow> &sh, int *res)
+// the tagged form: one memcpy, one walk in arrival order (the shadow's step and the datagram's place)
+static int batch_stage_tagged(FecBufBatch *in, PinnedBuf &arena, PinnedBuf &tab, std::vector<FecBufShadow> &sh, int *res)
 {
+    const int S = in->S;
+    const size_t n = in->n_total;
+    in->inplace = n && host_is_pinned(in->dgrams, in->bytes_in);
+    const uint8_t *src = in->dgrams;
+    if (n && !in->inplace) {
+        if (int rc = arena.reserve(in->bytes_in)) return rc; // (waits for the upload of this slot's last batch)
+        memcpy(arena.p, in->dgrams, in->bytes_in);
+        src = arena.as<uint8_t>();
+    }
+    // (dest lies behind the table fecbuf_packed fills: its reserve of the smaller size keeps the buffer)
+    const size_t tab_bytes = fecbuf_table(S, 0, true).upload;
+    if (int rc = tab.reserve(tab_bytes + n * sizeof(uint32_t))) return rc;
+    in->dest = at<uint32_t>(tab.p, tab_bytes);
+    std::vector<size_t> next((size_t)S);
+    size_t first = 0;
+    for (int s = 0; s < S; ++s) {
+        next[(size_t)s] = first; first += in->counts[(size_t)s];
+        int *r = res + (size_t)s * 4;
+        r[0] = 0; r[1] = 0; r[2] = -1; r[3] = 0;
+    }
+    for (size_t i = 0; i < n; ++i) {
+        const unsigned t = in->tags[i];
+        if (t == SDRHIP_DGRAM_SKIP) { in->dest[i] = 0xffffffffu; continue; }
+        in->dest[i] = (uint32_t)next[t]++;
+        uint32_t hd;
+        memcpy(&hd, src + i * SDRHIP_UDPSIZE, 4);
+        fecbuf_shadow_step(sh[t], hd, res + (size_t)t * 4);
+    }
+    return SDRHIP_OK;
+}
+
+int fecbuf_batch_stage(FecBufBatch *in, PinnedBuf &arena, PinnedBuf &tab, std::vector<FecBufShadow> &sh, int *res)
+{
+    if (in->n_total) return batch_stage_tagged(in, arena, tab, sh, res);
     const int S = in->S;
     in->inplace = in->sum && host_is_pinned(in->dgrams, in->packed ? in->bytes_in : (size_t)(S - 1) * in->stride + in->nmax * SDRHIP_UDPSIZE);
     if (in->sum && !in->inplace)
@@ -576,6 +687,16 @@ int fecbuf_batch_stage(FecBufBatch *in, PinnedBuf &arena, std::vector<FecBufShad
 
 int fecbuf_batch_upload(sdrhip_ctx *c, const FecBufBatch &in, PinnedBuf &arena, uint8_t *pk)
 {
+    if (in.n_total) { // tagged: the arrival array and its places behind the packed area, then KX
+        uint8_t *raw = pk + in.sum * SDRHIP_UDPSIZE;
+        uint32_t *dest = reinterpret_cast<uint32_t *>(raw + in.bytes_in);
+        HIP_TRY(link_copy(c, raw, in.inplace ? static_cast<const void *>(in.dgrams) : arena.p, in.bytes_in, hipMemcpyHostToDevice, c->stream));
+        if (!in.inplace) arena.mark(c->stream);
+        HIP_TRY(link_copy(c, dest, in.dest, in.n_total * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        const hipError_t e = in.sum ? launch_dgram_demux(raw, dest, in.n_total, pk, c->stream) : hipSuccess;
+        if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "datagram demultiplexer launch: %s", hipGetErrorString(e));
+        return SDRHIP_OK;
+    }
     if (in.sum && !in.inplace) {
         HIP_TRY(link_copy(c, pk, arena.p, in.bytes_in, hipMemcpyHostToDevice, c->stream));
         arena.mark(c->stream);
@@ -650,6 +771,62 @@ int fecbuf_join_carry(sdrhip_fecbuf *b, unsigned **dev, std::vector<size_t> **ho
 
 const FecBufState *fecbuf_committed_state(const sdrhip_fecbuf *b) { return b->state[b->cur]; }
 } // namespace sdrhip
+
+// --------------------------------------------------------------------------- the bank's call on an arrival-order array
+// One walk over the tags for the counts (it refuses a bad tag before anything moves), one for the places: the bank's kernels read
+// stream s's row at s * nmax * 512, so datagram i goes to row-start + its rank within the stream.  The array goes up as it is (host
+// memory: in place or through ONE memcpy), KX sorts it into the handle's own rows, and the call goes on as the untagged one does.
+extern "C" int sdrhip_fecbuf_write_and_read_tagged(sdrhip_fecbuf *b, const uint8_t *dgrams, const uint16_t *stream_of, size_t n_total,
+                                                   uint8_t *data_out, size_t data_stride_bytes, uint8_t *block0_out, size_t max_frames,
+                                                   sdrhip_fecbuf_frame *info_out, size_t *n_frames, int mem)
+{
+    const char *who = "fecbuf_write_and_read_tagged";
+    if (!b) return fail(SDRHIP_EINVAL, "fecbuf is NULL");
+    sdrhip_ctx *c = b->ctx;
+    sdrhip::CtxLock lock_(c);
+    const int S = b->nstreams;
+    if (!n_frames) return fail(SDRHIP_EINVAL, "%s: NULL n_frames", who);
+    if (b->async_busy) return fail(SDRHIP_EINVAL, "%s: the owning pipe's asynchronous datagram batches are in flight: collect them first", who);
+    int rc;
+    if ((rc = check_mem(mem))) return rc;
+    std::vector<size_t> counts((size_t)S);
+    size_t sum = 0, nmax = 0;
+    if ((rc = fecbuf_tag_counts(S, dgrams, stream_of, n_total, who, counts.data(), &sum, &nmax))) return rc;
+    if ((rc = check_outputs(S, data_out, data_stride_bytes, max_frames, info_out, who))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const bool host = mem == SDRHIP_MEM_HOST;
+    if (!host) {
+        if (n_total && !aligned16(dgrams)) return fail(SDRHIP_EALIGN, "%s: dgrams must be 16-byte aligned", who);
+        if ((rc = check_outputs_aligned(S, data_out, data_stride_bytes, block0_out, who))) return rc;
+    }
+    const size_t row = nmax * SDRHIP_UDPSIZE;
+    if (sum) {
+        const size_t bytes = n_total * SDRHIP_UDPSIZE, rows_bytes = (size_t)S * row, dest_bytes = n_total * sizeof(uint32_t);
+        const bool pinned = host && host_is_pinned(dgrams, bytes);
+        const size_t staged_bytes = host && !pinned ? bytes : 0;
+        if ((rc = b->pin_in.reserve(staged_bytes + dest_bytes))) return rc;
+        if ((rc = b->demux.reserve(rows_bytes + dest_bytes))) return rc;
+        if (host && (rc = b->hin.reserve(bytes))) return rc;
+        uint32_t *dest = at<uint32_t>(b->pin_in.p, staged_bytes);
+        std::vector<size_t> next((size_t)S);
+        for (int s = 0; s < S; ++s) next[(size_t)s] = (size_t)s * nmax;
+        tag_dest(stream_of, n_total, next.data(), dest);
+        const uint8_t *src = dgrams;
+        if (host) {
+            const void *from = dgrams;
+            if (!pinned) { memcpy(b->pin_in.p, dgrams, bytes); from = b->pin_in.p; }
+            HIP_TRY(link_copy(c, b->hin.p, from, bytes, hipMemcpyHostToDevice, c->stream));
+            src = b->hin.as<uint8_t>();
+        }
+        uint32_t *dest_dev = at<uint32_t>(b->demux.p, rows_bytes);
+        HIP_TRY(link_copy(c, dest_dev, dest, dest_bytes, hipMemcpyHostToDevice, c->stream));
+        b->pin_in.mark(c->stream);
+        const hipError_t e = launch_dgram_demux(src, dest_dev, n_total, b->demux.as<uint8_t>(), c->stream);
+        if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "datagram demultiplexer launch: %s", hipGetErrorString(e));
+    }
+    return write_and_read_checked(b, b->demux.as<uint8_t>(), counts.data(), row, data_out, data_stride_bytes, block0_out, max_frames, info_out,
+                                  n_frames, mem, sum && host ? b->demux.as<uint8_t>() : nullptr);
+}
 
 extern "C" int sdrhip_fecbuf_stats(sdrhip_fecbuf *b, int stream, int *cur_nb_blocks, int *cur_nb_recovery, int *min_nb_blocks, int *max_nb_recovery,
                                    uint8_t current_meta[24], uint8_t output_meta[24])

@@ -131,7 +131,8 @@ struct FecBufJoin {
 };
 int fecbuf_collect(sdrhip_fecbuf *b, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes, int mem, uint8_t *data_out,
                    size_t data_stride_bytes, uint8_t *block0_out, size_t max_frames, sdrhip_fecbuf_frame *info_out, size_t *n_frames,
-                   const int **counts, const FecBufJoin *join = nullptr);
+                   const int **counts, const FecBufJoin *join = nullptr, const uint8_t *staged = nullptr);
+// (staged, host memory: the datagrams are already on the device, stream s's row at staged + s * nmax * 512 -- the tagged bank call)
 // the samples every stream of the collector's owner (an Rx handle) holds back between datagram calls: [nstreams] on the device
 // (KJ keeps it) and the host's copy; created zero on first use, zeroed by sdrhip_fecbuf_reset
 int fecbuf_join_carry(sdrhip_fecbuf *b, unsigned **dev, std::vector<size_t> **host);
@@ -150,6 +151,9 @@ int fecbuf_shadow(sdrhip_fecbuf *b, std::vector<FecBufShadow> *out);
 // the classify pass's rule over n datagrams of one stream (datagram i at dg + 512 i, host): advances h; res = what the pass reports
 // for the stream, {FB_K, FB_D, FB_MAXROW, FB_MAXREC}
 void fecbuf_shadow_run(FecBufShadow &h, const uint8_t *dg, size_t n, int res[4]);
+// one datagram of that rule: header word hd (frameIndex | blockIndex << 16 | filler << 24) advances h and adds to res, which the
+// caller starts at {0, 0, -1, 0}.  fecbuf_shadow_run is this step over a row; the walk of a tagged batch calls it in arrival order
+void fecbuf_shadow_step(FecBufShadow &h, uint32_t hd, int res[4]);
 // one batch on the device without a read-back: stream s's datagrams back to back at dg + sum_{t<s} n_dgrams[t] * 512 (device),
 // grids and decoder bound from res ([S][4], fecbuf_shadow_run); tab = the batch's pinned table buffer; data_out / block0_out on
 // the device, max_frames >= every res[s][0]; +1 on *mismatch (device) per stream whose classify pass disagrees with res.
@@ -165,17 +169,37 @@ int fecbuf_packed(sdrhip_fecbuf *b, const uint8_t *dg, const size_t *n_dgrams, c
 // fecbuf_batch_stage: one memcpy per non-empty stream into the batch's pinned `arena`, packed (not at all where the caller's memory
 // is pinned: in->inplace), and the shadow `sh` run over every stream's headers: res [S][4].  fecbuf_batch_upload: exactly the
 // datagrams to pk (device), packed -- staged: one copy; in place: one per run of adjacent rows
+// The tagged form (sdrhip_*_submit_datagrams_tagged; tags != NULL): n_total datagrams in arrival order, tags[i] = the stream of
+// datagram i or SDRHIP_DGRAM_SKIP.  fecbuf_batch_check_tagged walks the tags once (a tag that names no stream refuses the batch;
+// the per-stream counts, which n_dgrams then points at).  fecbuf_batch_stage: ONE memcpy of the whole array (none in place), then
+// one walk in arrival order over the tags and the headers: the shadow's step for the datagram's stream and its place
+// dest[i] = first datagram of its stream in packed order + its rank within the stream (0xffffffff: skipped), written into `tab`,
+// the batch's pinned table buffer, behind the table fecbuf_packed fills.  fecbuf_batch_upload: the arrival array (bytes_in,
+// skipped datagrams included) and dest (4 n_total bytes) go up behind the packed area of pk, and KX (launch_dgram_demux) moves
+// every datagram to its place at pk: from there on the batch is an SDRHIP_PACKED one.  (`tab` is not marked: fecbuf_packed, which
+// uploads its own part of it behind, does that; a caller that returns before it marks the buffer itself.)
 struct FecBufBatch {
     int S;
     const uint8_t *dgrams;
     const size_t *n_dgrams;
     size_t stride;
     bool packed, inplace;       // packed: the rows lie back to back (SDRHIP_PACKED, or one stream), else row s at dgrams + s * stride
-    size_t sum, nmax, bytes_in; // all datagrams, the most of a stream, sum x 512
+    size_t sum, nmax, bytes_in; // the streams' datagrams, the most of a stream, the bytes that go up (sum x 512; tagged: n_total x 512)
+    size_t dev_bytes;           // what the device arena pk holds: bytes_in; tagged: sum x 512 packed + n_total x (512 + 4)
+    // ---- the tagged form
+    const uint16_t *tags = nullptr;
+    size_t n_total = 0;
+    std::vector<size_t> counts; // [S]
+    uint32_t *dest = nullptr;   // [n_total] in the batch's pinned table buffer (fecbuf_batch_stage)
 };
 int fecbuf_batch_check(FecBufBatch *in, int S, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes, const char *who);
-int fecbuf_batch_stage(FecBufBatch *in, PinnedBuf &arena, std::vector<FecBufShadow> &sh, int *res);
+int fecbuf_batch_check_tagged(FecBufBatch *in, int S, const uint8_t *dgrams, const uint16_t *stream_of, size_t n_total, const char *who);
+int fecbuf_batch_stage(FecBufBatch *in, PinnedBuf &arena, PinnedBuf &tab, std::vector<FecBufShadow> &sh, int *res);
 int fecbuf_batch_upload(sdrhip_ctx *c, const FecBufBatch &in, PinnedBuf &arena, uint8_t *pk);
+// the per-stream counts of a tagged array into counts [S] (zeroed here); SDRHIP_EINVAL for a tag that is neither a stream of the
+// bank nor SDRHIP_DGRAM_SKIP, for NULL tags or datagrams with n_total > 0, for more than 65535 streams; *sum / *nmax as count_dgrams
+int fecbuf_tag_counts(int S, const uint8_t *dgrams, const uint16_t *stream_of, size_t n_total, const char *who, size_t *counts, size_t *sum,
+                      size_t *nmax);
 // a failure behind the collector's scatter launch: the batch is consumed and lost, never replayed
 int fecbuf_batch_lost(const char *who, int rc);
 // a public record as a batch delivers it

@@ -569,6 +569,10 @@ hipError_t launch_rx_deliver(const RxDeliverSeg *segs, int nseg, uint32_t grid, 
 // counts [S][FB_COUNTS] against the shadow's expect [S][4] = {K, D, maxrow, maxrec}: +1 on *mismatch per
 // stream that differs
 hipError_t launch_fecbuf_shadow_check(const int *counts, const int *expect, int nstreams, unsigned *mismatch, hipStream_t stream);
+// KX (dgram_demux_kernels.hip), tagged datagram batches: datagram i of the arrival-order array src goes to dst + 512 * dest[i]
+// (device table, n_total entries; 0xffffffff: the datagram is moved nowhere).  src and dst 16-byte aligned, n_total below 2^30;
+// the host that made dest vouches for every entry lying inside dst
+hipError_t launch_dgram_demux(const uint8_t *src, const uint32_t *dest, size_t n_total, uint8_t *dst, hipStream_t stream);
 // delivery gather: segment i = bytes (a multiple of 2) from src (dword-aligned, readable 2 bytes past the end) to out + dst
 struct GatherSeg {
     const uint8_t *src;

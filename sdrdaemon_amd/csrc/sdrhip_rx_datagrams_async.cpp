@@ -7,26 +7,22 @@
 // ragged decimate / frame / encode step (rx_ragged) with counts the host derives from the shadow's release counts and its copy of
 // the carry, KJ, the delivery KD (frames, then records: one launch), ONE download of exactly the delivered bytes.  The collector, the
 // rows, the carry, the histories and the framing state are the ones sdrhip_rx_process_datagrams uses.
+// sdrhip_rx_submit_datagrams_tagged is the same submit on an arrival-order array with a stream tag per datagram: the staging path
+// (fecbuf_batch_*) walks the tags, uploads the array unsorted and has KX put it in packed order; nothing behind it differs.
 #include "sdrhip_pipes.h"
 
 using namespace sdrhip;
 
-extern "C" int sdrhip_rx_submit_datagrams(sdrhip_rx *rx, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes,
-                                          const uint32_t *tv_sec, const uint32_t *tv_usec)
+// one batch behind fecbuf_batch_check[_tagged] (`in`; the context lock is held): the rest of the refusals, then the submit
+static int rx_submit_batch(sdrhip_rx *rx, FecBufBatch &in, const uint32_t *tv_sec, const uint32_t *tv_usec, const char *who)
 {
-    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
-    if (!n_dgrams || !tv_sec || !tv_usec) return fail(SDRHIP_EINVAL, "rx_submit_datagrams: NULL count or stamp array");
-    sdrhip::CtxLock lock_(rx->ctx);
-    // ---- everything that can be refused is checked before anything is consumed
     const int S = rx->nstreams, L = rx->cfg.log2decim;
-    const char *who = "rx_submit_datagrams";
-    FecBufBatch in;
-    if (int e = fecbuf_batch_check(&in, S, dgrams, n_dgrams, dgram_stride_bytes, who)) return e;
-    if (rx->pipelined) return fail(SDRHIP_EINVAL, "rx_submit_datagrams: not available in pipelined mode");
+    const size_t *n_dgrams = in.n_dgrams;
+    if (rx->pipelined) return fail(SDRHIP_EINVAL, "%s: not available in pipelined mode", who);
     if (rx_has_batches(rx, false) || rx_has_batches(rx, true))
-        return fail(SDRHIP_EINVAL, "rx_submit_datagrams: uniform or ragged batches are being filled or in flight: collect them first");
+        return fail(SDRHIP_EINVAL, "%s: uniform or ragged batches are being filled or in flight: collect them first", who);
     sdrhip_rx::Batch &b = rx->ring.tail_batch();
-    if (b.state == 2) return fail(SDRHIP_EBUSY, "rx_submit_datagrams: every batch of the ring is in flight: sdrhip_rx_collect_datagrams first");
+    if (b.state == 2) return fail(SDRHIP_EBUSY, "%s: every batch of the ring is in flight: sdrhip_rx_collect_datagrams first", who);
     sdrhip_ctx *c = rx->ctx;
     HIP_TRY(hipSetDevice(c->device));
     int rc;
@@ -39,7 +35,7 @@ extern "C" int sdrhip_rx_submit_datagrams(sdrhip_rx *rx, const uint8_t *dgrams, 
 
     // ---- staging: packed, one memcpy per non-empty stream (in place: the caller's pinned memory); the shadow runs over the headers
     std::vector<int> res((size_t)S * 4);
-    if ((rc = fecbuf_batch_stage(&in, b.in, sh, res.data()))) return rc;
+    if ((rc = fecbuf_batch_stage(&in, b.in, b.r_tab, sh, res.data()))) return rc;
     // ---- every count of the batch, from the shadow's release counts and the host's copy of the carry: what each stream feeds its
     // decimator, what it holds back, the frames it completes (as rx_ragged counts them)
     const size_t U = rx_join_unit(rx->cfg), fb = (size_t)(SDRHIP_NB_ORIGINAL + rx->cfg.nb_fec) * SDRHIP_UDPSIZE;
@@ -62,7 +58,7 @@ extern "C" int sdrhip_rx_submit_datagrams(sdrhip_rx *rx, const uint8_t *dgrams, 
     // batches in flight; the rows keep their heads): the batch's own buffers, then what the ragged step takes for these counts
     // (rx_ragged_room: frame area, tables, frame list; it names the one allocation it cannot foresee).  The pinned tables are the ring slot's own, so that what a submit waits
     // for is this slot's previous batch -- which the caller has collected -- and never the batch before it
-    if (in.sum && (rc = reserve_settled(c, rx->a_pk, in.bytes_in + 16))) return rc;
+    if (in.dev_bytes && (rc = reserve_settled(c, rx->a_pk, in.dev_bytes + 16))) return rc;
     if (kmax && (rc = rx_join_rows(rx, kmax, who))) return rc;
     if (b_total && (rc = reserve_settled(c, rx->a_frames, b_total + 16))) return rc;
     if ((rc = reserve_settled(c, rx->a_tab, seg_bytes))) return rc;
@@ -83,7 +79,10 @@ extern "C" int sdrhip_rx_submit_datagrams(sdrhip_rx *rx, const uint8_t *dgrams, 
     const FecBufJoin join = {carry_dev, nullptr, nullptr};
     rc = fecbuf_packed(rx->fb, pk, n_dgrams, res.data(), sh, b.r_tab, kmax ? rx->j_rows.as<uint8_t>() : nullptr, rx->j_row_len * 4, nullptr, kmax,
                        c->dec_stats + DEC_STATS_SHADOW_MISMATCH, &committed, &counts, &pub, &join);
-    if (rc && !committed) return rc; // (nothing consumed)
+    if (rc && !committed) { // (nothing consumed)
+        if (in.n_total) b.r_tab.mark(c->stream); // (the places of a tagged batch went up from it)
+        return rc;
+    }
     if (rc) return fecbuf_batch_lost(who, rc);
     // ---- decimate, frame, encode: one ragged step; KJ moves every row's remainder to its head (the device's own counts)
     if (any) {
@@ -137,6 +136,32 @@ extern "C" int sdrhip_rx_submit_datagrams(sdrhip_rx *rx, const uint8_t *dgrams, 
     ++rx->ring.tail;
     fecbuf_set_async_busy(rx->fb, true);
     return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_rx_submit_datagrams(sdrhip_rx *rx, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes,
+                                          const uint32_t *tv_sec, const uint32_t *tv_usec)
+{
+    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
+    if (!n_dgrams || !tv_sec || !tv_usec) return fail(SDRHIP_EINVAL, "rx_submit_datagrams: NULL count or stamp array");
+    sdrhip::CtxLock lock_(rx->ctx);
+    // ---- everything that can be refused is checked before anything is consumed
+    const char *who = "rx_submit_datagrams";
+    FecBufBatch in;
+    if (int e = fecbuf_batch_check(&in, rx->nstreams, dgrams, n_dgrams, dgram_stride_bytes, who)) return e;
+    return rx_submit_batch(rx, in, tv_sec, tv_usec, who);
+}
+
+// the same batch from an arrival-order array: the tags are walked (and refused) first, KX sorts the upload on the device
+extern "C" int sdrhip_rx_submit_datagrams_tagged(sdrhip_rx *rx, const uint8_t *dgrams, const uint16_t *stream_of, size_t n_total,
+                                                 const uint32_t *tv_sec, const uint32_t *tv_usec)
+{
+    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
+    if (!tv_sec || !tv_usec) return fail(SDRHIP_EINVAL, "rx_submit_datagrams_tagged: NULL stamp array");
+    sdrhip::CtxLock lock_(rx->ctx);
+    const char *who = "rx_submit_datagrams_tagged";
+    FecBufBatch in;
+    if (int e = fecbuf_batch_check_tagged(&in, rx->nstreams, dgrams, stream_of, n_total, who)) return e;
+    return rx_submit_batch(rx, in, tv_sec, tv_usec, who);
 }
 
 extern "C" int sdrhip_rx_collect_datagrams(sdrhip_rx *rx, uint8_t *frames_out, size_t frame_stride_bytes, size_t max_frames,

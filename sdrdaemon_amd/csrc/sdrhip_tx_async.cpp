@@ -125,21 +125,16 @@ extern "C" int sdrhip_tx_collect(sdrhip_tx *tx, int16_t *iq_out, size_t out_stri
 // sdrhip_host_alloc memory), the collector's passes with grids from the host's shadow of the classification (fecbuf_packed: no
 // read-back), the decoder, the interpolator at the factor in force, the delivery gather, ONE download of exactly the delivered
 // bytes.  The collector and the histories are the ones sdrhip_tx_process_datagrams and sdrhip_tx_process use.
-extern "C" int sdrhip_tx_submit_datagrams(sdrhip_tx *tx, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes)
+// one batch behind fecbuf_batch_check[_tagged] (`in`; the context lock is held): the rest of the refusals, then the submit
+static int tx_submit_batch(sdrhip_tx *tx, FecBufBatch &in, const char *who)
 {
-    if (!tx) return fail(SDRHIP_EINVAL, "tx is NULL");
-    if (!n_dgrams) return fail(SDRHIP_EINVAL, "tx_submit_datagrams: NULL n_dgrams");
-    sdrhip::CtxLock lock_(tx->ctx);
-    // ---- everything that can be refused is checked before anything is consumed
     const int S = tx->nstreams;
-    const char *who = "tx_submit_datagrams";
-    FecBufBatch in;
-    if (int e = fecbuf_batch_check(&in, S, dgrams, n_dgrams, dgram_stride_bytes, who)) return e;
-    if (tx->pipelined) return fail(SDRHIP_EINVAL, "tx_submit_datagrams: the handle is in pipelined mode");
-    if (tx->late.have) return fail(SDRHIP_EINVAL, "tx_submit_datagrams: a pipelined batch waits: sdrhip_tx_flush it first");
-    if (tx_in_flight(tx, false)) return fail(SDRHIP_EINVAL, "tx_submit_datagrams: batches of received frames are in flight: sdrhip_tx_collect them first");
+    const size_t *n_dgrams = in.n_dgrams;
+    if (tx->pipelined) return fail(SDRHIP_EINVAL, "%s: the handle is in pipelined mode", who);
+    if (tx->late.have) return fail(SDRHIP_EINVAL, "%s: a pipelined batch waits: sdrhip_tx_flush it first", who);
+    if (tx_in_flight(tx, false)) return fail(SDRHIP_EINVAL, "%s: batches of received frames are in flight: sdrhip_tx_collect them first", who);
     sdrhip_tx::ABatch &b = tx->ring.tail_batch();
-    if (b.state == 2) return fail(SDRHIP_EBUSY, "tx_submit_datagrams: every batch of the ring is in flight: sdrhip_tx_collect_datagrams first");
+    if (b.state == 2) return fail(SDRHIP_EBUSY, "%s: every batch of the ring is in flight: sdrhip_tx_collect_datagrams first", who);
     sdrhip_ctx *c = tx->ctx;
     HIP_TRY(hipSetDevice(c->device));
     int rc;
@@ -149,7 +144,7 @@ extern "C" int sdrhip_tx_submit_datagrams(sdrhip_tx *tx, const uint8_t *dgrams, 
 
     // ---- staging: packed, one memcpy per non-empty stream (in place: the caller's pinned memory); the shadow runs over the headers
     std::vector<int> res((size_t)S * 4);
-    if ((rc = fecbuf_batch_stage(&in, b.in, sh, res.data()))) return rc;
+    if ((rc = fecbuf_batch_stage(&in, b.in, b.tab, sh, res.data()))) return rc;
     size_t kmax = 0, kall = 0;
     for (int s = 0; s < S; ++s) {
         kmax = (size_t)res[(size_t)s * 4] > kmax ? (size_t)res[(size_t)s * 4] : kmax;
@@ -162,7 +157,7 @@ extern "C" int sdrhip_tx_submit_datagrams(sdrhip_tx *tx, const uint8_t *dgrams, 
     const size_t b_samples = kall * n_one * esz, b_total = b_samples + kall * (DG_REC + SDRHIP_BLOCK_BYTES);
     // everything that can fail for want of memory comes before the collector moves (a device buffer that grows waits for the
     // batches in flight)
-    if (in.sum && (rc = reserve_settled(c, tx->a_pk, in.bytes_in + 16))) return rc;
+    if (in.dev_bytes && (rc = reserve_settled(c, tx->a_pk, in.dev_bytes + 16))) return rc;
     if (kmax && !direct && (rc = reserve_settled(c, tx->a_pay, (size_t)S * pitch * 4 + 16))) return rc;
     if (kmax && (rc = reserve_settled(c, tx->a_out, (size_t)S * dos * esz + 16))) return rc;
     if (kmax && (rc = reserve_settled(c, tx->a_b0, (size_t)S * kmax * SDRHIP_BLOCK_BYTES + 16))) return rc;
@@ -184,7 +179,10 @@ extern "C" int sdrhip_tx_submit_datagrams(sdrhip_tx *tx, const uint8_t *dgrams, 
     const FecBufPub *pub = nullptr;
     rc = fecbuf_packed(tx->fb, pk, n_dgrams, res.data(), sh, b.tab, kmax ? data : nullptr, data_stride, kmax ? tx->a_b0.as<uint8_t>() : nullptr, kmax,
                        c->dec_stats + DEC_STATS_SHADOW_MISMATCH, &committed, &counts, &pub);
-    if (rc && !committed) return rc; // (nothing consumed)
+    if (rc && !committed) { // (nothing consumed)
+        if (in.n_total) b.tab.mark(c->stream); // (the places of a tagged batch went up from it)
+        return rc;
+    }
     if (rc) return fecbuf_batch_lost(who, rc);
     // ---- the interpolator (x1: the collector wrote the samples where the gather reads them; 8-bit x1: K6n narrows them)
     if ((rc = tx_interpolate_counts(tx, tx->a_pay.as<int16_t>(), per, pitch, tx->a_out.as<int16_t>(), dos, counts))) return fecbuf_batch_lost(who, rc);
@@ -222,6 +220,29 @@ extern "C" int sdrhip_tx_submit_datagrams(sdrhip_tx *tx, const uint8_t *dgrams, 
     ++tx->ring.tail;
     fecbuf_set_async_busy(tx->fb, true);
     return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_tx_submit_datagrams(sdrhip_tx *tx, const uint8_t *dgrams, const size_t *n_dgrams, size_t dgram_stride_bytes)
+{
+    if (!tx) return fail(SDRHIP_EINVAL, "tx is NULL");
+    if (!n_dgrams) return fail(SDRHIP_EINVAL, "tx_submit_datagrams: NULL n_dgrams");
+    sdrhip::CtxLock lock_(tx->ctx);
+    // ---- everything that can be refused is checked before anything is consumed
+    const char *who = "tx_submit_datagrams";
+    FecBufBatch in;
+    if (int e = fecbuf_batch_check(&in, tx->nstreams, dgrams, n_dgrams, dgram_stride_bytes, who)) return e;
+    return tx_submit_batch(tx, in, who);
+}
+
+// the same batch from an arrival-order array: the tags are walked (and refused) first, KX sorts the upload on the device
+extern "C" int sdrhip_tx_submit_datagrams_tagged(sdrhip_tx *tx, const uint8_t *dgrams, const uint16_t *stream_of, size_t n_total)
+{
+    if (!tx) return fail(SDRHIP_EINVAL, "tx is NULL");
+    sdrhip::CtxLock lock_(tx->ctx);
+    const char *who = "tx_submit_datagrams_tagged";
+    FecBufBatch in;
+    if (int e = fecbuf_batch_check_tagged(&in, tx->nstreams, dgrams, stream_of, n_total, who)) return e;
+    return tx_submit_batch(tx, in, who);
 }
 
 extern "C" int sdrhip_tx_collect_datagrams(sdrhip_tx *tx, int16_t *iq_out, size_t out_stride, size_t max_frames, uint8_t *block0_out,

@@ -20,7 +20,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import (BLOCK_BYTES, FC_CEN, FC_INF, FC_SUP, HB_DB, HB_EO1, MEM_DEVICE, MEM_HOST, NB_ORIGINAL,  # noqa: F401
+from ._lib import (BLOCK_BYTES, DGRAM_SKIP, FC_CEN, FC_INF, FC_SUP, HB_DB, HB_EO1, MEM_DEVICE, MEM_HOST, NB_ORIGINAL,  # noqa: F401
                    SAMPLES_PER_FRAME, UDPSIZE, CM256Block, CM256Params, RxConfig, SdrHipError, check)
 
 try:
@@ -1008,6 +1008,19 @@ class RxPipe:
                                                       (C.c_uint32 * S)(*[int(v) for v in usec])))  # (0 = SDRHIP_PACKED)
         self._dg_submitted()
 
+    def submit_datagrams_tagged(self, dgrams, stream_of, tv_sec=0, tv_usec=0):
+        """one batch as a hub's socket delivers it (sdrhip_rx_submit_datagrams_tagged): dgrams (n, 512) uint8 in arrival order,
+        stream_of (n,) uint16 = the stream of every datagram or DGRAM_SKIP.  It means submit_datagrams of the per-stream
+        subsequences; the array goes up unsorted (from Context.host_alloc memory in place: keep it untouched until the batch is
+        collected) and is demultiplexed on the device.  Collected with collect_datagrams."""
+        S = self.nstreams
+        buf, tags, tp = _tagged_batch(dgrams, stream_of)
+        sec = np.broadcast_to(np.asarray(tv_sec, dtype=np.uint32), (S,))
+        usec = np.broadcast_to(np.asarray(tv_usec, dtype=np.uint32), (S,))
+        check(self.ctx.lib.sdrhip_rx_submit_datagrams_tagged(self.h, _ptr(buf), tp, buf.shape[0], (C.c_uint32 * S)(*[int(v) for v in sec]),
+                                                             (C.c_uint32 * S)(*[int(v) for v in usec])))
+        self._dg_submitted()
+
     def _dg_submitted(self):
         """bookkeeping behind a successful sdrhip_rx_submit_datagrams (also for callers of the C entry itself): the batch keeps the
         frame size in force at its submit"""
@@ -1294,6 +1307,20 @@ class TxPipe:
             pend.pop()
             raise
 
+    def submit_datagrams_tagged(self, dgrams, stream_of):
+        """one batch as a hub's socket delivers it (sdrhip_tx_submit_datagrams_tagged): dgrams (n, 512) uint8 in arrival order,
+        stream_of (n,) uint16 = the stream of every datagram or DGRAM_SKIP.  It means submit_datagrams of the per-stream
+        subsequences; the array goes up unsorted (from Context.host_alloc memory in place) and is demultiplexed on the device.
+        Collected with collect_datagrams."""
+        buf, tags, tp = _tagged_batch(dgrams, stream_of)
+        pend = self.__dict__.setdefault("_dg_pending", [])
+        pend.append(self.log2interp)  # (as submit_datagrams)
+        try:
+            check(self.ctx.lib.sdrhip_tx_submit_datagrams_tagged(self.h, _ptr(buf), tp, buf.shape[0]))
+        except SdrHipError:
+            pend.pop()
+            raise
+
     def collect_datagrams(self, wait=True, max_frames=None):
         """the oldest datagram batch: per stream (iq (n, 2) with n = frames * 16129 << the batch's log2interp, block0 (frames, 508)
         uint8, records) as process_datagrams returns them, or None when no batch was collected (nothing submitted, or wait=False
@@ -1432,10 +1459,58 @@ class FECBufferBank:
             out.append((data[s, :k], b0[s, :k], recs))
         return out
 
+    def write_and_read_tagged(self, dgrams, stream_of, max_frames=None):
+        """write_and_read of an arrival-order array (sdrhip_fecbuf_write_and_read_tagged): dgrams (n, 512) uint8 -- numpy or a torch
+        device tensor --, stream_of (n,) uint16 = the stream of every datagram or DGRAM_SKIP.  Returns what write_and_read returns
+        for the per-stream subsequences."""
+        S = self.nstreams
+        buf, tags, tp = _tagged_batch(dgrams, stream_of, allow_torch=True)
+        is_t = _is_torch(buf)
+        if max_frames is None:  # (a call releases at most one frame per datagram)
+            max_frames = int(np.bincount(tags[tags != DGRAM_SKIP], minlength=1).max()) if tags.size else 0
+        F = max(max_frames, 1)
+        pb = 127 * BLOCK_BYTES
+        if is_t:
+            data = torch.empty((S, F, pb), dtype=torch.uint8, device=buf.device)
+            b0 = torch.empty((S, F, BLOCK_BYTES), dtype=torch.uint8, device=buf.device)
+        else:
+            data = np.empty((S, F, pb), np.uint8)
+            b0 = np.empty((S, F, BLOCK_BYTES), np.uint8)
+        info = (FECBufferFrame * (S * F))()
+        nf = (C.c_size_t * S)()
+        rc = self.ctx.lib.sdrhip_fecbuf_write_and_read_tagged(self.h, _ptr(buf), tp, buf.shape[0], _ptr(data), F * pb, _ptr(b0), max_frames,
+                                                              info, nf, MEM_DEVICE if is_t else MEM_HOST)
+        self.last_n_frames = [int(x) for x in nf]
+        check(rc)
+        out = []
+        for s in range(S):
+            k = int(nf[s])
+            recs = [dict(frame_index=info[s * F + j].frame_index, block_count=info[s * F + j].block_count,
+                         recovery_count=info[s * F + j].recovery_count, flags=info[s * F + j].flags) for j in range(k)]
+            out.append((data[s, :k], b0[s, :k], recs))
+        return out
+
     def stats(self, stream):
         """getCurNbBlocks, getCurNbRecovery, getMinNbBlocks, getMaxNbRecovery (these two reset when read), getCurrentMeta,
         getOutputMeta (24 bytes: the 20-byte MetaDataFEC, zero padded) of one stream, as a dict"""
         return _fecbuf_stats(self.ctx, self.h, stream)
+
+
+def _tagged_batch(dgrams, stream_of, allow_torch=False):
+    """an arrival-order array and its tags as the tagged entries take them: (n, 512) uint8 (numpy, used where it lies when it is
+    contiguous; a torch device tensor only for the bank), (n,) uint16 numpy tags (SDRHIP_DGRAM_SKIP = 0xffff: no stream)"""
+    if _is_torch(dgrams):
+        if not allow_torch:
+            raise TypeError("submit_datagrams_tagged takes host memory")
+        buf = dgrams.reshape(-1, UDPSIZE).contiguous()
+        if buf.dtype != torch.uint8:
+            raise TypeError("datagrams must be uint8")
+    else:
+        buf = np.ascontiguousarray(np.asarray(dgrams, np.uint8).reshape(-1, UDPSIZE))
+    tags = np.ascontiguousarray(np.asarray(stream_of).reshape(-1), np.uint16)
+    if tags.shape[0] != buf.shape[0]:
+        raise ValueError("one tag per datagram")
+    return buf, tags, tags.ctypes.data_as(C.POINTER(C.c_uint16))
 
 
 def _datagram_batch(dgrams_per_stream):
