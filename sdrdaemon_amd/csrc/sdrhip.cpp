@@ -539,11 +539,7 @@ int decimate_device(sdrhip_decimators *d, int log2decim, int fcpos, unsigned *sa
     a.nstreams = d->nstreams;
     a.bias = d->bias; a.norm = (int)norm; a.trunk = (int)trunk;
     a.frame_mode = frame_mode; a.frame_blocks = frame_blocks; a.frame_sample_base = frame_sample_base;
-    if (meta) {
-        a.meta_first = meta->first; a.meta_count = meta->count; a.meta_frame_count0 = meta->frame_count0;
-        memcpy(a.meta_w, meta->w, sizeof(a.meta_w));
-        a.meta_idx0 = meta->idx0; a.meta_rate = meta->rate; a.meta_tab = meta->tab;
-    }
+    if (meta) set_meta_args(a, *meta);
     plan_decimate((int)L, fcpos, a.n_used, d->nstreams, &a.nsub_per_seg, &a.nseg);
     const bool cen = (fcpos == SDRHIP_FC_CEN);
     const bool pack16 = cen && d->stage0_int16;

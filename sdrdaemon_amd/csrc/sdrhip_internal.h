@@ -74,6 +74,13 @@ struct DecimArgs {
     const unsigned *meta_tab; // per-stream {fc, rate, zero-stamp CRC}, STREAM_META_WORDS each (stream_meta_base()); NULL: meta_w / meta_rate
                               // serve every stream.  (Ragged launches leave it NULL: each stream's three words come with its RaggedRow, for K2r)
 };
+// host: the meta_* fields of DecimArgs, FrameArgs or Enc128Args from the call's record (RxMeta, sdrhip_host.h)
+template <class Args, class Meta> inline void set_meta_args(Args &a, const Meta &m)
+{
+    a.meta_first = m.first; a.meta_count = m.count; a.meta_frame_count0 = m.frame_count0;
+    for (int i = 0; i < 6; ++i) a.meta_w[i] = m.w[i];
+    a.meta_idx0 = m.idx0; a.meta_rate = m.rate; a.meta_tab = m.tab;
+}
 
 // MetaDataFEC of the fi-th frame a call starts (UDPSinkFEC.cpp:90-115: the reference takes gettimeofday() when it opens a
 // frame and CRCs the first 20 bytes).  A batched call opens all its frames "at once", so the stamp of a frame is the

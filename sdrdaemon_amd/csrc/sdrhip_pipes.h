@@ -2,6 +2,7 @@
 // units sdrhip_rx.cpp, sdrhip_rx_async.cpp, sdrhip_rx_datagrams.cpp, sdrhip_rx_datagrams_async.cpp, sdrhip_tx.cpp and
 // sdrhip_tx_async.cpp share
 #pragma once
+#include "rx_frame_area.h"
 #include "sdrhip_host.h"
 
 #include <cstring>
@@ -80,21 +81,12 @@ struct sdrhip_rx {
     int nstreams;
     sdrhip_rx_config cfg;
     sdrhip_decimators *dec;
-    // [nstreams][cap_frames][128 + nb_fec][512].  A call fills slots r_base[s] .. r_base[s] + done of stream s; slot
-    // r_base[s] + done (the frame still being filled) is slot r_base[s] of the next call, so the window slides and nothing is
-    // copied until it reaches the end of the area.
+    // [nstreams][area.cap()][128 + nb_fec][512].  A call fills slots area.slot(s) .. area.slot(s) + done of stream s; the frame
+    // still being filled is the first slot of the next call, so the window slides and nothing is copied until it reaches the end
+    // of the area.  `area` decides where the windows go (rx_frame_area.h), rx_run_plan moves the open frames there
     sdrhip::DevBuf work;
-    size_t cap_frames;        // frame slots per stream in `work`
-    // the framing state, per stream.  The uniform step (sdrhip_rx_process) runs while every stream stands at the same position
-    // (rx_aligned) and moves them together; ragged calls move each by its own count
-    std::vector<size_t> r_base;        // slot of the frame being filled
-    std::vector<uint64_t> r_pending;   // decimated samples sitting in that slot (the partial frame)
-    std::vector<uint8_t> r_open;       // it has its meta block (a frame was started)
-    std::vector<uint16_t> r_count;     // its m_frameCount
-    // what sdrhip_rx_frames_view shows: the frames the last call DELIVERED
-    const uint8_t *view_base = nullptr; // slot 0 of the delivered window of stream 0
-    size_t view_stride = 0;             // bytes between streams
-    size_t view_frames = 0;
+    sdrhip::RxFrameArea area;
+    sdrhip::RxView view;      // what sdrhip_rx_frames_view / _ragged show: the frames the last call DELIVERED
     sdrhip::DevBuf lin[2];    // stream-order decimator output of a call that is framed by K2 (two: pipelined mode)
     int lin_sel = 0;
     sdrhip::DevBuf flist;     // frame list of the generic encode launch (device), relative to the window
@@ -107,9 +99,9 @@ struct sdrhip_rx {
         bool have = false;          // frames completed by the previous call wait for delivery
         bool encode = false;        // ... and still have to be encoded (k)
         sdrhip::Enc128Args k;
-        const uint8_t *base = nullptr;
-        size_t stride = 0, frames = 0, frame_bytes = 0;
-        size_t slot0 = 0;           // window position inside `work` (overlap check of the sliding window), SIZE_MAX = other area
+        const uint8_t *area = nullptr; // the area they lie in, from slot `first` of every stream on
+        size_t first = 0, stride = 0, frames = 0, frame_bytes = 0;
+        bool in_old = false;        // that area is old_work (the windows got a new one meanwhile)
     } late;
     sdrhip::DevBuf old_work;  // the previous frame area after a re-allocation, kept while `late` points into it
     // overlap mode (option rx_fused = 3): the waiting encode runs on the context's second stream beside the next call's decimator.
@@ -165,8 +157,6 @@ struct sdrhip_rx {
     int in_fmt = sdrhip::IQF_S16;
     sdrhip::DevBuf wide;
     // ---- ragged calls (sdrhip_rx_process_ragged)
-    std::vector<size_t> r_view_first, r_view_frames; // sdrhip_rx_frames_view_ragged: the frames the last call delivered
-    bool view_ragged = false;          // the last call's windows differ between streams: sdrhip_rx_frames_view refuses
     sdrhip::PinnedBuf r_pin, r_flist_pin; // host-row staging and the encoder's frame list
     sdrhip::DevBuf r_flist;
     // ---- per-stream centre frequency / sample rate (sdrhip_rx_set_stream_meta).  The setter touches the host arrays alone; the
@@ -265,15 +255,8 @@ struct sdrhip_tx {
 };
 
 namespace sdrhip {
-// ---- Rx: every stream stands at the same frame position (what the uniform step, pipelined mode and uniform batches need)
-inline bool rx_aligned(const sdrhip_rx *rx)
-{
-    for (size_t s = 1; s < (size_t)rx->nstreams; ++s)
-        if (rx->r_base[s] != rx->r_base[0] || rx->r_pending[s] != rx->r_pending[0] || rx->r_open[s] != rx->r_open[0] ||
-            rx->r_count[s] != rx->r_count[0])
-            return false;
-    return true;
-}
+static_assert(RX_FRAME_SAMPLES == SDRHIP_SAMPLES_PER_FRAME, "rx_frame_area.h frames the header's frame");
+inline size_t rx_frame_bytes(const sdrhip_rx *rx) { return (size_t)(SDRHIP_NB_ORIGINAL + rx->cfg.nb_fec) * SDRHIP_UDPSIZE; }
 // batches of the ring that are being filled or in flight, of the ragged (or the uniform) kind
 inline bool rx_has_batches(const sdrhip_rx *rx, bool ragged)
 {
@@ -305,7 +288,9 @@ int rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, size_t in
 // straight into the windows.  rx_ragged itself then allocates nothing, unless a matrix-core plan it counted on does not apply
 int rx_ragged_room(sdrhip_rx *rx, const size_t *n_in, RxTabs *tabs);
 int rx_collector(sdrhip_rx *rx); // the datagram collector, created on first use
-int rx_area_room(sdrhip_rx *rx); // a frame area with at least one slot per stream (sdrhip_rx_import_stream into a bank that never ran)
+// the frame area made ready for a ragged step that completes done[s] frames of stream s (NULL: none -- a slot per stream for
+// sdrhip_rx_import_stream into a bank that never ran): plan, new area or in-place moves
+int rx_area_room(sdrhip_rx *rx, const size_t *done);
 
 // ---- Tx: bytes per output sample, and the row pitch (samples) of the library's own output buffers: 16-byte rows either way
 inline size_t tx_esz(const sdrhip_tx *tx) { return tx->out_fmt == IQF_S8 ? 2 : 4; }

@@ -16,9 +16,8 @@ extern "C" int sdrhip_rx_create(sdrhip_ctx *ctx, int nstreams, const sdrhip_rx_c
     sdrhip_rx *rx = new (std::nothrow) sdrhip_rx();
     if (!rx) return fail(SDRHIP_ENOMEM, "out of host memory");
     rx->ctx = ctx; rx->nstreams = nstreams; rx->cfg = *cfg; rx->dec = nullptr;
-    rx->cap_frames = 0;
-    rx->r_base.assign((size_t)nstreams, 0); rx->r_pending.assign((size_t)nstreams, 0);
-    rx->r_open.assign((size_t)nstreams, 0); rx->r_count.assign((size_t)nstreams, 0);
+    rx->area.init((size_t)nstreams);
+    rx->view.init((size_t)nstreams);
     int rc = sdrhip_decimators_create(ctx, nstreams, cfg->hb_variant, &rx->dec);
     if (rc) { delete rx; return rc; }
     *out = rx;
@@ -61,7 +60,7 @@ extern "C" int sdrhip_rx_set_pipelined(sdrhip_rx *rx, int on)
     sdrhip::CtxLock lock_(rx->ctx);
     if (!on && rx->late.have) return fail(SDRHIP_EINVAL, "rx_set_pipelined: sdrhip_rx_flush the waiting frames first");
     if (on && rx_dgrams_in_flight(rx)) return fail(SDRHIP_EINVAL, "rx_set_pipelined: asynchronous datagram batches are in flight: collect them first");
-    if (on && !rx_aligned(rx)) return fail(SDRHIP_EINVAL, "rx_set_pipelined: ragged calls left the streams at different frame positions");
+    if (on && !rx->area.aligned()) return fail(SDRHIP_EINVAL, "rx_set_pipelined: ragged calls left the streams at different frame positions");
     rx->pipelined = on ? 1 : 0;
     return SDRHIP_OK;
 }
@@ -93,6 +92,71 @@ static int rx_widen(sdrhip_rx *rx, const uint8_t *in, size_t in_stride, size_t n
     return SDRHIP_OK;
 }
 
+// the old frame area of a pipelined pipe, kept while frames wait for delivery in it
+static int rx_release_old(sdrhip_rx *rx)
+{
+    if (rx->old_work.p && !(rx->late.have && rx->late.in_old)) {
+        HIP_TRY(hipStreamSynchronize(rx->ctx->stream));
+        rx->old_work.release();
+    }
+    return SDRHIP_OK;
+}
+
+// Carries a plan out: `bytes` of every open frame whose window moves go to slot 0 of its stream -- of `fresh` (slots of dst_pitch
+// bytes; it becomes the area behind a synchronisation: earlier launches may still use the old one) or, fresh = NULL, in place.
+// One strided copy when every stream moves from the same slot, else one copy per stream.  A failure releases `fresh` and leaves
+// the handle as it was.
+static int rx_run_plan(sdrhip_rx *rx, const RxAreaPlan &p, DevBuf *fresh, size_t src_pitch, size_t dst_pitch, size_t bytes, const char *who)
+{
+    sdrhip_ctx *c = rx->ctx;
+    const RxFrameArea &A = rx->area;
+    const size_t S = A.streams(), dcap = fresh ? p.new_cap : A.cap();
+    const uint8_t *src = rx->work.as<uint8_t>();
+    uint8_t *dst = fresh ? fresh->as<uint8_t>() : rx->work.as<uint8_t>();
+    bool together = true;
+    for (size_t s = 0; s < S; ++s) together = together && p.to_slot0[s] && A.open(s) && A.slot(s) == A.slot(0);
+    hipError_t e = hipSuccess;
+    if (together)
+        e = hipMemcpy2DAsync(dst, dcap * dst_pitch, src + A.slot(0) * src_pitch, A.cap() * src_pitch, bytes, S, hipMemcpyDeviceToDevice, c->stream);
+    else
+        for (size_t s = 0; s < S && e == hipSuccess; ++s)
+            if (p.to_slot0[s] && A.open(s))
+                e = hipMemcpyAsync(dst + s * dcap * dst_pitch, src + A.index(s) * src_pitch, bytes, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess && fresh) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        if (fresh) { (void)hipStreamSynchronize(c->stream); fresh->release(); }
+        return fail(SDRHIP_EDEVICE, "%s: moving the open frames: %s", who, hipGetErrorString(e));
+    }
+    if (fresh) {
+        if (p.keep_old) { rx->old_work.release(); rx->old_work = rx->work; rx->late.in_old = true; }
+        else rx->work.release();
+        rx->work = *fresh;
+        rx->view.clear(); // (the view of the last call's frames does not outlive the area it points into)
+    }
+    rx->area.moved(p);
+    return SDRHIP_OK;
+}
+
+// the windows where a call that completes done[s] frames of stream s can write: plan, new area if the plan asks for one, moves
+// (grow_only: ahead of the call, nothing moves in place yet)
+static int rx_make_room(sdrhip_rx *rx, const size_t *done, bool pipelined, const char *who, bool grow_only = false)
+{
+    sdrhip_ctx *c = rx->ctx;
+    // the window: TWO calls' frames (round 5; four until then).  The step rewrites what it wrote two calls ago: 2 x 84 MB per
+    // 8-stream bank stay in the 256 MB of Infinity Cache, and on this memory system a write stream that stays there
+    // costs the read stream beside it less (profiles/r05_rx_direct.txt: decimator launch 0.2435 -> 0.2335 ms, encoder
+    // launch 0.052 -> 0.049 ms; a window of one call wraps -- a copy of the open frames -- on every call).  option rx_window (SDRHIP_RX_WINDOW at context creation, 1..8) = A / B
+    // (pipelined pipes keep the previous call's frames until they are delivered: four calls, as before)
+    const size_t wmul = c->opt.rx_window ? (size_t)c->opt.rx_window : pipelined ? 4 : 2;
+    const RxAreaPlan p = rx->area.plan(done, rx->late.have && !rx->late.in_old ? rx->late.first : RX_NO_LATE, wmul);
+    if (!p.new_cap && (grow_only || !p.moves())) return SDRHIP_OK;
+    const size_t fb = rx_frame_bytes(rx);
+    DevBuf fresh;
+    if (p.new_cap)
+        if (int rc = fresh.reserve(rx->area.streams() * p.new_cap * fb)) return rc;
+    return rx_run_plan(rx, p, p.new_cap ? &fresh : nullptr, fb, fb, fb, who);
+}
+
 extern "C" int sdrhip_rx_reconfigure(sdrhip_rx *rx, const sdrhip_rx_config *cfg)
 {
     if (!rx || !cfg) return fail(SDRHIP_EINVAL, "rx_reconfigure: NULL argument");
@@ -105,33 +169,16 @@ extern "C" int sdrhip_rx_reconfigure(sdrhip_rx *rx, const sdrhip_rx_config *cfg)
     if (cfg->nb_fec != rx->cfg.nb_fec && rx->late.have)
         return fail(SDRHIP_EINVAL, "rx_reconfigure: frames of the previous call wait for delivery (pipelined mode): sdrhip_rx_flush them "
                                    "before changing fecblk (they carry the old frame size)");
-    if (cfg->nb_fec != rx->cfg.nb_fec && rx->cap_frames) {
+    if (cfg->nb_fec != rx->cfg.nb_fec && rx->area.cap()) {
         // the slots change size: the frame being filled (its 128 original super blocks) moves to slot 0 of a new area
         if ((rc = rx_settle(rx))) return rc;
-        const int S = rx->nstreams;
-        const size_t old_fb = (size_t)(SDRHIP_NB_ORIGINAL + rx->cfg.nb_fec) * SDRHIP_UDPSIZE;
         const size_t new_fb = (size_t)(SDRHIP_NB_ORIGINAL + cfg->nb_fec) * SDRHIP_UDPSIZE;
         DevBuf fresh;
-        if ((rc = fresh.reserve((size_t)S * rx->cap_frames * new_fb))) return rc;
-        if (!rx_aligned(rx)) { // (per-stream windows: each open frame moves to slot 0 of its stream)
-            for (int s = 0; s < S; ++s)
-                if (rx->r_open[(size_t)s])
-                    HIP_TRY(hipMemcpyAsync(fresh.as<uint8_t>() + (size_t)s * rx->cap_frames * new_fb,
-                                           rx->work.as<uint8_t>() + (size_t)s * rx->cap_frames * old_fb + rx->r_base[(size_t)s] * old_fb,
-                                           (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE, hipMemcpyDeviceToDevice, c->stream));
-        } else if (rx->r_open[0])
-            HIP_TRY(hipMemcpy2DAsync(fresh.p, rx->cap_frames * new_fb, rx->work.as<uint8_t>() + rx->r_base[0] * old_fb,
-                                     rx->cap_frames * old_fb, (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE, S, hipMemcpyDeviceToDevice,
-                                     c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream)); // earlier launches may still use the old area
+        if ((rc = fresh.reserve(rx->area.streams() * rx->area.cap() * new_fb))) return rc;
+        if ((rc = rx_run_plan(rx, rx->area.replan(), &fresh, rx_frame_bytes(rx), new_fb, (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE, "rx_reconfigure")))
+            return rc;
         // (no frames wait for delivery here: a fecblk change with late.have set was refused above)
         rx->old_work.release();
-        rx->work.release();
-        rx->work = fresh;
-        rx->r_base.assign((size_t)S, 0);
-        rx->view_base = nullptr;
-        rx->view_frames = 0;
-        rx->view_ragged = false;
     }
     rx->cfg = *cfg;
     return SDRHIP_OK;
@@ -166,10 +213,10 @@ extern "C" int sdrhip_rx_frames_view(const sdrhip_rx *rx, const uint8_t **base, 
 {
     if (!rx || !base || !stream_stride_bytes || !n_frames) return fail(SDRHIP_EINVAL, "rx_frames_view: NULL argument");
     sdrhip::CtxLock lock_(rx->ctx);
-    if (rx->view_ragged) return fail(SDRHIP_EINVAL, "rx_frames_view: the last call's windows differ between streams: use sdrhip_rx_frames_view_ragged");
-    *base = rx->view_base;
-    *stream_stride_bytes = rx->view_stride;
-    *n_frames = rx->view_frames;
+    if (!rx->view.uniform()) return fail(SDRHIP_EINVAL, "rx_frames_view: the last call's windows differ between streams: use sdrhip_rx_frames_view_ragged");
+    *base = rx->view.window(0, rx_frame_bytes(rx));
+    *stream_stride_bytes = rx->view.stride();
+    *n_frames = rx->view.frames(0);
     return SDRHIP_OK;
 }
 
@@ -178,20 +225,9 @@ extern "C" int sdrhip_rx_frames_view_ragged(const sdrhip_rx *rx, const uint8_t *
 {
     if (!rx || !base || !stream_stride_bytes || !first_slot || !n_frames) return fail(SDRHIP_EINVAL, "rx_frames_view_ragged: NULL argument");
     sdrhip::CtxLock lock_(rx->ctx);
-    const int S = rx->nstreams;
-    const size_t fb = (size_t)(SDRHIP_NB_ORIGINAL + rx->cfg.nb_fec) * SDRHIP_UDPSIZE;
-    if (rx->view_ragged) {
-        *base = rx->work.as<uint8_t>();
-        *stream_stride_bytes = rx->cap_frames * fb;
-        for (int s = 0; s < S; ++s) { first_slot[s] = rx->r_view_first[(size_t)s]; n_frames[s] = rx->r_view_frames[(size_t)s]; }
-        return SDRHIP_OK;
-    }
-    // (the last call delivered the same window of every stream: the uniform view, as slot offsets from the area)
-    const size_t slot = rx->view_base && rx->work.p && rx->view_base >= rx->work.as<uint8_t>() && rx->view_stride == rx->cap_frames * fb
-                            ? (size_t)(rx->view_base - rx->work.as<uint8_t>()) / fb : 0;
-    *base = rx->view_base ? rx->view_base - slot * fb : nullptr;
-    *stream_stride_bytes = rx->view_stride;
-    for (int s = 0; s < S; ++s) { first_slot[s] = slot; n_frames[s] = rx->view_frames; }
+    *base = rx->view.base();
+    *stream_stride_bytes = rx->view.stride();
+    for (size_t s = 0; s < (size_t)rx->nstreams; ++s) { first_slot[s] = rx->view.first(s); n_frames[s] = rx->view.frames(s); }
     return SDRHIP_OK;
 }
 
@@ -207,7 +243,7 @@ extern "C" size_t sdrhip_rx_max_frames(const sdrhip_rx *rx, size_t n_in)
     sdrhip::CtxLock lock_(rx->ctx);
     size_t now = 0; // (the stream that completes the most: every stream, while they stand at the same position)
     for (size_t s = 0; s < (size_t)rx->nstreams; ++s) {
-        const size_t f = (size_t)((rx->r_pending[s] + (n_in >> rx->cfg.log2decim)) / SDRHIP_SAMPLES_PER_FRAME);
+        const size_t f = rx->area.advance(s, n_in >> rx->cfg.log2decim).done;
         if (f > now) now = f;
     }
     if (!rx->pipelined) return now;
@@ -215,11 +251,12 @@ extern "C" size_t sdrhip_rx_max_frames(const sdrhip_rx *rx, size_t n_in)
 }
 
 // delivery of a finished window: optional copy to the caller's buffer, and the zero-copy view
-static int rx_deliver(sdrhip_rx *rx, const uint8_t *base, size_t stride, size_t frames, size_t frame_bytes, uint8_t *frames_out,
+static int rx_deliver(sdrhip_rx *rx, const uint8_t *area, size_t first, size_t stride, size_t frames, size_t frame_bytes, uint8_t *frames_out,
                       size_t frame_stride_bytes, size_t *n_frames, int mem)
 {
     sdrhip_ctx *c = rx->ctx;
     const int S = rx->nstreams;
+    const uint8_t *base = area + first * frame_bytes; // the window of stream 0
     if (frames && frames_out) {
         if (S > 1 && frame_stride_bytes < frames * frame_bytes) return fail(SDRHIP_EINVAL, "rx_process: frame stride too small");
         HIP_TRY(link_copy2d(c, frames_out, S > 1 ? frame_stride_bytes : frames * frame_bytes, base, stride, frames * frame_bytes, S,
@@ -227,8 +264,7 @@ static int rx_deliver(sdrhip_rx *rx, const uint8_t *base, size_t stride, size_t 
     } else if (frames && mem != SDRHIP_MEM_DEVICE) {
         return fail(SDRHIP_EINVAL, "rx_process: NULL frames_out");
     }
-    rx->view_base = base; rx->view_stride = stride; rx->view_frames = frames;
-    rx->view_ragged = false;
+    rx->view.set(area, stride, (size_t)S, first, frames);
     if (n_frames) *n_frames = frames;
     return SDRHIP_OK;
 }
@@ -239,11 +275,11 @@ extern "C" int sdrhip_rx_flush(sdrhip_rx *rx, uint8_t *frames_out, size_t frame_
     sdrhip::CtxLock lock_(rx->ctx);
     if (n_frames) *n_frames = 0;
     if (int e = check_mem(mem)) return e;
-    if (!rx->late.have) { rx->view_frames = 0; return SDRHIP_OK; }
+    if (!rx->late.have) { rx->view.clear(); return SDRHIP_OK; }
     HIP_TRY(hipSetDevice(rx->ctx->device));
     int rc;
     if ((rc = rx_settle(rx))) return rc;
-    if ((rc = rx_deliver(rx, rx->late.base, rx->late.stride, rx->late.frames, rx->late.frame_bytes, frames_out, frame_stride_bytes, n_frames, mem))) return rc;
+    if ((rc = rx_deliver(rx, rx->late.area, rx->late.first, rx->late.stride, rx->late.frames, rx->late.frame_bytes, frames_out, frame_stride_bytes, n_frames, mem))) return rc;
     rx->late.have = false;
     if (mem == SDRHIP_MEM_HOST) HIP_TRY(hipStreamSynchronize(rx->ctx->stream));
     return SDRHIP_OK;
@@ -387,7 +423,7 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
     if (n_frames) *n_frames = 0;
     if (rx_has_batches(rx, true)) return fail(SDRHIP_EINVAL, "rx_process: ragged batches are being filled or in flight: collect them first");
     if (rx_dgrams_in_flight(rx)) return fail(SDRHIP_EINVAL, "rx_process: asynchronous datagram batches are in flight: collect them first");
-    if (n_in && !rx_aligned(rx)) {
+    if (n_in && !rx->area.aligned()) {
         // ragged calls left the streams at different frame positions: a ragged call with equal counts and stamps; *n_frames = the
         // largest per-stream count (sdrhip_rx_frames_view_ragged has each)
         const size_t S = (size_t)rx->nstreams;
@@ -404,8 +440,7 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
         // an empty call completes nothing; in pipelined mode it still DELIVERS what the previous call completed (the header's
         // contract: every call delivers the frames of the one before it)
         if (rx->pipelined && rx->late.have) return sdrhip_rx_flush(rx, frames_out, frame_stride_bytes, n_frames, mem);
-        rx->view_frames = 0;
-        rx->view_ragged = false;
+        rx->view.clear();
         return SDRHIP_OK;
     }
     if (!iq_in) return fail(SDRHIP_EINVAL, "rx_process: NULL input");
@@ -416,11 +451,9 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
     const int FB = SDRHIP_NB_ORIGINAL + R;
     const size_t frame_bytes = (size_t)FB * SDRHIP_UDPSIZE;
     const size_t n_dec = n_in >> L;
-    const uint64_t pending = rx->r_pending[0]; // (every stream stands here: rx_aligned)
-    const bool frame_open = rx->r_open[0] != 0;
-    const uint64_t total = pending + n_dec;
-    const size_t done = (size_t)(total / SDRHIP_SAMPLES_PER_FRAME);
-    const uint64_t rest = total - (uint64_t)done * SDRHIP_SAMPLES_PER_FRAME;
+    const uint64_t pending = rx->area.pending(0); // (every stream stands here: aligned)
+    const RxAdvance adv = rx->area.advance(0, n_dec);
+    const size_t done = adv.done;
     if (S == 1) in_stride = n_in;
     const size_t deliver_now = rx->pipelined ? (rx->late.have ? rx->late.frames : 0) : done;
     const size_t deliver_fb = rx->pipelined && rx->late.have ? rx->late.frame_bytes : frame_bytes;
@@ -449,61 +482,30 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
         if ((rc = rx_widen(rx, static_cast<const uint8_t *>(src), sstride, n_in, dstride, &din))) return rc;
     }
 
-    // ---- work area [stream][slot][128 + R][512]: this call fills slots r_base .. r_base + done.  The
+    // ---- work area [stream][slot][128 + R][512]: this call fills slots slot .. slot + done.  The
     // finished frames stay readable in place until the next call (sdrhip_rx_frames_view); the frame still
     // being filled is the first slot of the next call.  At the end of the area the window wraps: the open
     // frame moves to slot 0 (one strided copy every few calls instead of a save + restore per call).  Frames that
     // wait for delivery (pipelined mode) are never overwritten: a window that would reach them gets a new area.
-    const size_t need = done + 1;
-    if (rx->old_work.p && !(rx->late.have && rx->late.slot0 == SIZE_MAX)) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        rx->old_work.release();
-    }
-    if (rx->r_base[0] + need > rx->cap_frames) {
-        const bool late_here = rx->late.have && rx->late.slot0 != SIZE_MAX;
-        const bool wrap_hits_late = late_here && need > rx->late.slot0; // the wrapped window [0, need) against [slot0, slot0 + frames)
-        if (need > rx->cap_frames || wrap_hits_late) {
-            DevBuf bigger;
-            // the window: TWO calls' frames (round 5; four until then).  The step rewrites what it wrote two calls ago: 2 x 84 MB per
-            // 8-stream bank stay in the 256 MB of Infinity Cache, and on this memory system a write stream that stays there
-            // costs the read stream beside it less (profiles/r05_rx_direct.txt: decimator launch 0.2435 -> 0.2335 ms, encoder
-            // launch 0.052 -> 0.049 ms; a window of one call wraps -- a copy of the open frames -- on every call).  option rx_window (SDRHIP_RX_WINDOW at context creation, 1..8) = A / B
-            // (pipelined pipes keep the previous call's frames until they are delivered: four calls, as before)
-            const size_t wmul = c->opt.rx_window ? (size_t)c->opt.rx_window : rx->pipelined ? 4 : 2;
-            const size_t ncap = need > rx->cap_frames ? wmul * need : rx->cap_frames;
-            if ((rc = bigger.reserve((size_t)S * ncap * frame_bytes))) return rc;
-            if (frame_open)
-                HIP_TRY(hipMemcpy2DAsync(bigger.p, ncap * frame_bytes, rx->work.as<uint8_t>() + rx->r_base[0] * frame_bytes,
-                                         rx->cap_frames * frame_bytes, frame_bytes, S, hipMemcpyDeviceToDevice, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream)); // earlier launches may still use the old area
-            if (late_here) { rx->old_work.release(); rx->old_work = rx->work; rx->late.slot0 = SIZE_MAX; }
-            else rx->work.release();
-            rx->work = bigger;
-            rx->cap_frames = ncap;
-        } else if (frame_open) {
-            uint8_t *w0 = rx->work.as<uint8_t>();
-            HIP_TRY(hipMemcpy2DAsync(w0, rx->cap_frames * frame_bytes, w0 + rx->r_base[0] * frame_bytes, rx->cap_frames * frame_bytes,
-                                     frame_bytes, S, hipMemcpyDeviceToDevice, c->stream));
-        }
-        rx->r_base.assign((size_t)S, 0);
-    }
-    const size_t stream_bytes = rx->cap_frames * frame_bytes;
-    uint8_t *work = rx->work.as<uint8_t>() + rx->r_base[0] * frame_bytes; // slot 0 of the window
+    const std::vector<size_t> dones((size_t)S, done);
+    if ((rc = rx_release_old(rx))) return rc;
+    if ((rc = rx_make_room(rx, dones.data(), rx->pipelined != 0, "rx_process"))) return rc;
+    const size_t cap = rx->area.cap(), slot0 = rx->area.slot(0);
+    const size_t stream_bytes = cap * frame_bytes;
+    uint8_t *work = rx->work.as<uint8_t>() + slot0 * frame_bytes; // slot 0 of the window
 
     // ---- meta record of the frames started by this call (UDPSinkFEC.cpp:87-132); the decimator kernel writes
     // their meta blocks and super block headers on its way
     unsigned ss = rx->cfg.sample_bits;
-    const int first_new = frame_open ? 1 : 0;
-    const int started = (int)(done + (rest > 0 ? 1 : 0)) - first_new; // frames whose first sample arrives now
     RxMeta meta;
     memset(&meta, 0, sizeof(meta));
-    if (started > 0) {
+    if (adv.started > 0) {
         // tv_sec / tv_usec = the stamp of the call's first sample
         rx_meta_base(rx->cfg, decimated_sample_size((unsigned)L, ss), meta.w);
         if ((rc = rx_stream_table(rx, decimated_sample_size((unsigned)L, ss), &meta.tab))) return rc;
         meta.w[3] = tv_sec; meta.w[4] = tv_usec;
-        meta.first = first_new; meta.count = started; meta.frame_count0 = (unsigned)rx->r_count[0] + first_new;
-        meta.idx0 = first_new ? (uint64_t)SDRHIP_SAMPLES_PER_FRAME - pending : 0;
+        meta.first = adv.first_new; meta.count = adv.started; meta.frame_count0 = adv.frame_count0;
+        meta.idx0 = adv.idx0;
         meta.rate = rx->cfg.sample_rate;
     }
 
@@ -537,7 +539,7 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
         if (fec_encode_fuses_framing(c, R)) {
             const size_t first = pending ? 1 : 0;
             if (done > first && frame_bytes % 4 == 0) {
-                elin.lin = lin.as<unsigned>(); elin.stride = lstride; elin.cap = (int)rx->cap_frames;
+                elin.lin = lin.as<unsigned>(); elin.stride = lstride; elin.cap = (int)cap;
                 elin.first = (int)first; elin.pending = (int)pending;
                 use_lin = true;
             }
@@ -549,9 +551,7 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
         fa.in = lin.as<unsigned>(); fa.out = reinterpret_cast<unsigned *>(work);
         fa.in_stride = lstride; fa.out_stride = stream_bytes / 4;
         fa.n = n_dec; fa.frame_sample_base = pending; fa.frame_blocks = FB;
-        fa.meta_first = meta.first; fa.meta_count = meta.count; fa.meta_frame_count0 = meta.frame_count0;
-        memcpy(fa.meta_w, meta.w, sizeof(fa.meta_w));
-        fa.meta_idx0 = meta.idx0; fa.meta_rate = meta.rate; fa.meta_tab = meta.tab;
+        set_meta_args(fa, meta);
         // K2 rides in the encoder's launch when this call's frames are encoded right away by the structured encoder (one launch
         // less per step); otherwise it goes out now
         pack_with_encoder = !rx->pipelined && c->opt.rx_fused && structured && R > 0 && use_lin;
@@ -575,21 +575,19 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
     memset(&k, 0, sizeof(k));
     if (done && R > 0) {
         if (structured) {
-            // structured encoder, one workgroup per (frame, half block); frame (s, f) of the window is frame s * cap_frames + f
+            // structured encoder, one workgroup per (frame, half block); frame (s, f) of the window is frame s * cap + f
             k.in = work; k.out = work + (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE; k.tab = c->gf_tab; k.leaf_tables = c->enc_leaves; k.fft_tables = c->enc_fft; k.use_fft = c->opt.enc_fft;
             k.bitslice = c->opt.enc_bitslice;
             k.in_frame_bytes = frame_bytes; k.out_frame_bytes = frame_bytes;
-            k.rows = R; k.nframes = (int)((size_t)S * rx->cap_frames);
-            k.nlist = (int)((size_t)S * done); k.gen_done = (int)done; k.gen_cap = (int)rx->cap_frames;
+            k.rows = R; k.nframes = (int)((size_t)S * cap);
+            k.nlist = (int)((size_t)S * done); k.gen_done = (int)done; k.gen_cap = (int)cap;
             if (use_lin) { k.lin = elin.lin; k.lin_stride = elin.stride; k.lin_cap = elin.cap; k.lin_first = elin.first; k.lin_pending = elin.pending; }
             if (rx->pipelined) {
                 encode_later = true; // rides in the next call's decimator launch (or sdrhip_rx_flush)
             } else if (pack_with_encoder) {
                 // encoder + K2 in one launch: the encoder derives the meta blocks of the frames this call starts itself and
                 // completes the frame that was open (its tail comes from the stream-order buffer), K2 leaves both alone
-                k.meta_first = meta.first; k.meta_count = meta.count; k.meta_frame_count0 = meta.frame_count0;
-                memcpy(k.meta_w, meta.w, sizeof(k.meta_w));
-                k.meta_idx0 = meta.idx0; k.meta_rate = meta.rate; k.meta_tab = meta.tab;
+                set_meta_args(k, meta);
                 if (elin.first == 1) { k.lin_straddle = 1; fa.skip_from = 0; }
                 hipError_t e;
                 {
@@ -600,17 +598,17 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
             } else if ((rc = fec_encode128_launch(c, k))) return rc;
         } else {
             // generic matrix kernel: one launch for every stream, frame list in groups of GF_FRAMES_PER_GROUP
-            if (rx->flist_done != done || rx->flist_cap != rx->cap_frames) {
+            if (rx->flist_done != done || rx->flist_cap != cap) {
                 HIP_TRY(hipStreamSynchronize(c->stream)); // a previous upload may still read flist_host
                 rx->flist_host.clear();
                 for (int s = 0; s < S; ++s)
-                    for (size_t f = 0; f < done; ++f) rx->flist_host.push_back((int32_t)(s * rx->cap_frames + f));
+                    for (size_t f = 0; f < done; ++f) rx->flist_host.push_back((int32_t)(s * cap + f));
                 while (rx->flist_host.size() % GF_FRAMES_PER_GROUP) rx->flist_host.push_back(-1);
                 if ((rc = rx->flist.reserve(rx->flist_host.size() * 4))) return rc;
                 HIP_TRY(link_copy(c, rx->flist.p, rx->flist_host.data(), rx->flist_host.size() * 4, hipMemcpyHostToDevice, c->stream));
-                rx->flist_done = done; rx->flist_cap = rx->cap_frames;
+                rx->flist_done = done; rx->flist_cap = cap;
             }
-            if ((rc = fec_encode_device(c, work, frame_bytes, (size_t)S * rx->cap_frames, R, work + (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE,
+            if ((rc = fec_encode_device(c, work, frame_bytes, (size_t)S * cap, R, work + (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE,
                                         frame_bytes, rx->flist.as<int32_t>(), (int)(rx->flist_host.size() / GF_FRAMES_PER_GROUP), nullptr)))
                 return rc;
         }
@@ -618,9 +616,9 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
     // ---- delivery: this call's frames, or (pipelined) the previous call's, whose encode went out above
     if (rx->pipelined) {
         if (rx->late.have) {
-            if ((rc = rx_deliver(rx, rx->late.base, rx->late.stride, rx->late.frames, rx->late.frame_bytes, frames_out, frame_stride_bytes, n_frames, mem))) return rc;
+            if ((rc = rx_deliver(rx, rx->late.area, rx->late.first, rx->late.stride, rx->late.frames, rx->late.frame_bytes, frames_out, frame_stride_bytes, n_frames, mem))) return rc;
         } else {
-            rx->view_base = nullptr; rx->view_frames = 0; rx->view_ragged = false;
+            rx->view.clear();
         }
         rx->late.have = done > 0;
         rx->late.encode = encode_later;
@@ -629,70 +627,36 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
             HIP_TRY(hipEventRecord(rx->ev_framed, c->stream));
         }
         rx->late.k = k;
-        rx->late.base = work; rx->late.stride = stream_bytes; rx->late.frames = done; rx->late.frame_bytes = frame_bytes;
-        rx->late.slot0 = rx->r_base[0];
+        rx->late.area = rx->work.as<uint8_t>(); rx->late.first = slot0; rx->late.in_old = false;
+        rx->late.stride = stream_bytes; rx->late.frames = done; rx->late.frame_bytes = frame_bytes;
     } else {
-        if ((rc = rx_deliver(rx, work, stream_bytes, done, frame_bytes, frames_out, frame_stride_bytes, n_frames, mem))) return rc;
+        if ((rc = rx_deliver(rx, rx->work.as<uint8_t>(), slot0, stream_bytes, done, frame_bytes, frames_out, frame_stride_bytes, n_frames, mem))) return rc;
     }
     // every stream moves on together; the frame still being filled opens the next call's window
-    rx->r_base.assign((size_t)S, rx->r_base[0] + done);
-    rx->r_pending.assign((size_t)S, rest);
-    rx->r_open.assign((size_t)S, rest > 0 ? 1 : 0);
-    rx->r_count.assign((size_t)S, (uint16_t)(rx->r_count[0] + done));
+    rx->area.commit(dones.data(), std::vector<uint64_t>((size_t)S, adv.rest).data());
     if (mem == SDRHIP_MEM_HOST) HIP_TRY(hipStreamSynchronize(c->stream));
     return SDRHIP_OK;
 }
 
 // --------------------------------------------------------------------------- ragged Rx calls
-// a new frame area of more slots per stream (a ragged call needs more than the area has): every open frame moves to its slot 0
-static int rx_grow_area(sdrhip_rx *rx, size_t need_max)
+int sdrhip::rx_area_room(sdrhip_rx *rx, const size_t *done)
 {
-    sdrhip_ctx *c = rx->ctx;
-    const int S = rx->nstreams;
-    const size_t frame_bytes = ((size_t)SDRHIP_NB_ORIGINAL + (size_t)rx->cfg.nb_fec) * SDRHIP_UDPSIZE;
-    const size_t wmul = c->opt.rx_window ? (size_t)c->opt.rx_window : 2;
-    const size_t ncap = wmul * need_max;
-    DevBuf bigger;
-    if (int rc = bigger.reserve((size_t)S * ncap * frame_bytes)) return rc;
-    // (the old area and every window stay as they were until the copies have completed: a failure leaves the handle untouched)
-    hipError_t e = hipSuccess;
-    for (int s = 0; s < S && e == hipSuccess; ++s)
-        if (rx->r_open[(size_t)s])
-            e = hipMemcpyAsync(bigger.as<uint8_t>() + (size_t)s * ncap * frame_bytes,
-                               rx->work.as<uint8_t>() + ((size_t)s * rx->cap_frames + rx->r_base[(size_t)s]) * frame_bytes, frame_bytes,
-                               hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // earlier launches may still use the old area
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(c->stream);
-        bigger.release();
-        return fail(SDRHIP_EDEVICE, "rx_process_ragged: moving the open frames: %s", hipGetErrorString(e));
-    }
-    for (int s = 0; s < S; ++s) rx->r_base[(size_t)s] = 0;
-    rx->work.release();
-    rx->work = bigger;
-    rx->cap_frames = ncap;
-    return SDRHIP_OK;
+    return rx_make_room(rx, done ? done : std::vector<size_t>(rx->area.streams(), 0).data(), false, "rx_process_ragged", true);
 }
-
-int sdrhip::rx_area_room(sdrhip_rx *rx) { return rx->cap_frames ? SDRHIP_OK : rx_grow_area(rx, 1); }
 
 int sdrhip::rx_ragged_room(sdrhip_rx *rx, const size_t *n_in, RxTabs *tabs)
 {
     const int S = rx->nstreams, L = rx->cfg.log2decim;
-    size_t need_max = 0, sum_done = 0, max_dec = 0;
+    size_t sum_done = 0, max_dec = 0;
+    std::vector<size_t> done((size_t)S);
     for (int s = 0; s < S; ++s) {
-        const size_t n_dec = n_in[s] >> L, done = (size_t)((rx->r_pending[(size_t)s] + n_dec) / SDRHIP_SAMPLES_PER_FRAME);
-        need_max = done + 1 > need_max ? done + 1 : need_max;
+        const size_t n_dec = n_in[s] >> L;
+        done[(size_t)s] = rx->area.advance((size_t)s, n_dec).done;
         max_dec = n_dec > max_dec ? n_dec : max_dec;
-        sum_done += done;
+        sum_done += done[(size_t)s];
     }
     int rc;
-    // (the view of the last call's frames does not outlive the area it points into)
-    if (need_max > rx->cap_frames) {
-        if ((rc = rx_grow_area(rx, need_max))) return rc;
-        rx->view_frames = 0; rx->view_ragged = false;
-        rx->r_view_frames.assign((size_t)S, 0);
-    }
+    if ((rc = rx_area_room(rx, done.data()))) return rc;
     if ((rc = ragged_reserve(rx->dec, tabs ? &tabs->rows : nullptr))) return rc;
     // (only the matrix-core launch of a centred decimation by 4 or more stores straight into the windows)
     const bool may_direct = rx->cfg.fcpos == SDRHIP_FC_CEN && L >= 2 && rx->ctx->opt.rx_direct;
@@ -707,7 +671,7 @@ int sdrhip::rx_ragged_room(sdrhip_rx *rx, const size_t *n_in, RxTabs *tabs)
 
 // Every stream takes its own count: K0r (8-bit input) -> K1r / filter-less kernel into stream order -> K2r into each stream's
 // own window -> one encoder launch over the list of every stream's completed frames.  A call that fails after it moved windows
-// leaves r_base moved (the open frames lie there now) and the rest of the framing state untouched.
+// leaves the windows moved (the open frames lie there now) and the rest of the framing state untouched.
 int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, size_t in_stride, const uint32_t *tv_sec, const uint32_t *tv_usec,
                       uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem, bool batch, bool dev_rows, RxTabs *tabs,
                       const FecBufState *follow)
@@ -730,14 +694,15 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
     const bool in_dev = mem == SDRHIP_MEM_DEVICE || dev_rows;
     if (max_in && in_dev && (!aligned16(iq_in) || (S > 1 && (in_stride & (wide8 ? 7 : 3)))))
         return fail(SDRHIP_EALIGN, "rx_process_ragged: device input must be 16-byte aligned, its stride a multiple of %d samples", wide8 ? 8 : 4);
+    std::vector<RxAdvance> adv((size_t)S);
     std::vector<size_t> done((size_t)S);
     std::vector<uint64_t> rest((size_t)S);
     size_t max_done = 0, sum_done = 0, max_dec = 0;
     for (int s = 0; s < S; ++s) {
         const size_t n_dec = n_in[s] >> L;
-        const uint64_t total = rx->r_pending[(size_t)s] + n_dec;
-        done[(size_t)s] = (size_t)(total / SDRHIP_SAMPLES_PER_FRAME);
-        rest[(size_t)s] = total - (uint64_t)done[(size_t)s] * SDRHIP_SAMPLES_PER_FRAME;
+        adv[(size_t)s] = rx->area.advance((size_t)s, n_dec);
+        done[(size_t)s] = adv[(size_t)s].done;
+        rest[(size_t)s] = adv[(size_t)s].rest;
         if (done[(size_t)s] > max_done) max_done = done[(size_t)s];
         if (n_dec > max_dec) max_dec = n_dec;
         sum_done += done[(size_t)s];
@@ -748,31 +713,17 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
     HIP_TRY(hipSetDevice(c->device));
     rx->consumed = false;
     if (max_in == 0) { // nothing arrives: nothing changes, nothing is delivered
-        rx->view_frames = 0; rx->view_ragged = false;
+        rx->view.clear();
         return SDRHIP_OK;
     }
     int rc;
-    // ---- windows: stream s fills slots r_base[s] .. r_base[s] + done[s] of its area; a window that would pass the end of the area
+    // ---- windows: stream s fills slots slot(s) .. slot(s) + done[s] of its area; a window that would pass the end of the area
     // moves that stream's open frame to slot 0 (the others stay where they are); a call that needs more slots than the area has
     // gets a new area, every open frame at slot 0
-    size_t need_max = 0;
-    for (int s = 0; s < S; ++s) if (done[(size_t)s] + 1 > need_max) need_max = done[(size_t)s] + 1;
-    if (rx->old_work.p && !rx->late.have) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        rx->old_work.release();
-    }
-    if (need_max > rx->cap_frames) {
-        if ((rc = rx_grow_area(rx, need_max))) return rc;
-    } else {
-        for (int s = 0; s < S; ++s) {
-            if (rx->r_base[(size_t)s] + done[(size_t)s] + 1 <= rx->cap_frames) continue;
-            uint8_t *a0 = rx->work.as<uint8_t>() + (size_t)s * rx->cap_frames * frame_bytes;
-            if (rx->r_open[(size_t)s])
-                HIP_TRY(hipMemcpyAsync(a0, a0 + rx->r_base[(size_t)s] * frame_bytes, frame_bytes, hipMemcpyDeviceToDevice, c->stream));
-            rx->r_base[(size_t)s] = 0;
-        }
-    }
-    const size_t stream_bytes = rx->cap_frames * frame_bytes;
+    if ((rc = rx_release_old(rx))) return rc;
+    if ((rc = rx_make_room(rx, done.data(), false, "rx_process_ragged"))) return rc;
+    const RxFrameArea &A = rx->area;
+    const size_t stream_bytes = A.cap() * frame_bytes;
     uint8_t *area = rx->work.as<uint8_t>();
 
     // ---- the per-call table: counts (decimator), windows and meta records (K2r)
@@ -784,16 +735,15 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
     memset(rows.data(), 0, rows.size() * sizeof(RaggedRow));
     for (int s = 0; s < S; ++s) {
         RaggedRow &r = rows[(size_t)s];
-        const int first_new = rx->r_open[(size_t)s] ? 1 : 0;
-        const int started = (int)(done[(size_t)s] + (rest[(size_t)s] > 0 ? 1 : 0)) - first_new;
-        r.out_off = rx->r_base[(size_t)s] * frame_bytes / 4;
-        r.frame_sample_base = rx->r_pending[(size_t)s];
+        const RxAdvance &a = adv[(size_t)s];
+        r.out_off = A.slot((size_t)s) * frame_bytes / 4;
+        r.frame_sample_base = A.pending((size_t)s);
         r.fc = sw ? sw[s * STREAM_META_WORDS] : mw[0]; r.rate = sw ? sw[s * STREAM_META_WORDS + 1] : mw[1];
         r.crc0 = sw ? sw[s * STREAM_META_WORDS + 2] : mw[5];
-        if (started > 0 && (n_in[s] >> L)) {
-            r.meta_first = first_new; r.meta_count = started;
-            r.frame_count0 = (unsigned)rx->r_count[(size_t)s] + (unsigned)first_new;
-            r.meta_idx0 = first_new ? (uint64_t)SDRHIP_SAMPLES_PER_FRAME - rx->r_pending[(size_t)s] : 0;
+        if (a.started > 0 && (n_in[s] >> L)) {
+            r.meta_first = a.first_new; r.meta_count = a.started;
+            r.frame_count0 = a.frame_count0;
+            r.meta_idx0 = a.idx0;
             r.tv_sec = tv_sec[s]; r.tv_usec = tv_usec[s];
         }
     }
@@ -872,46 +822,36 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
         int32_t *fl = fpin.as<int32_t>();
         size_t k = 0;
         for (int s = 0; s < S; ++s)
-            for (size_t f = 0; f < done[(size_t)s]; ++f) fl[k++] = (int32_t)((size_t)s * rx->cap_frames + rx->r_base[(size_t)s] + f);
+            for (size_t f = 0; f < done[(size_t)s]; ++f) fl[k++] = (int32_t)A.index((size_t)s, f);
         while (k < nl) fl[k++] = -1;
         HIP_TRY(hipMemcpyAsync(rx->r_flist.p, fl, nl * 4, hipMemcpyHostToDevice, c->stream));
         fpin.mark(c->stream);
-        if ((rc = fec_encode_device(c, area, frame_bytes, (size_t)S * rx->cap_frames, R, area + (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE,
+        if ((rc = fec_encode_device(c, area, frame_bytes, (size_t)S * A.cap(), R, area + (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE,
                                     frame_bytes, rx->r_flist.as<int32_t>(), (int)(nl / GF_FRAMES_PER_GROUP))))
             return rc;
     }
 
     // ---- delivery: every stream's window (one 2-D copy when the windows line up, else a copy per stream)
     bool same_base = true;
-    for (int s = 1; s < S; ++s) same_base = same_base && rx->r_base[(size_t)s] == rx->r_base[0];
+    for (int s = 1; s < S; ++s) same_base = same_base && A.slot((size_t)s) == A.slot(0);
     if (frames_out && max_done) {
         const hipMemcpyKind kind = mem == SDRHIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
         // (the datagram entry's host callers get each stream's own frames and no more: its link traffic is datagrams up, frames down)
         bool same_done = true;
         for (int s = 1; s < S; ++s) same_done = same_done && done[(size_t)s] == done[0];
         if (same_base && (same_done || !(dev_rows && mem == SDRHIP_MEM_HOST))) {
-            HIP_TRY(link_copy2d(c, frames_out, S > 1 ? frame_stride_bytes : max_done * frame_bytes, area + rx->r_base[0] * frame_bytes, stream_bytes,
+            HIP_TRY(link_copy2d(c, frames_out, S > 1 ? frame_stride_bytes : max_done * frame_bytes, area + A.slot(0) * frame_bytes, stream_bytes,
                                 max_done * frame_bytes, S, kind, c->stream));
         } else {
             for (int s = 0; s < S; ++s)
                 if (done[(size_t)s])
-                    HIP_TRY(link_copy(c, frames_out + (size_t)s * frame_stride_bytes, area + (size_t)s * stream_bytes + rx->r_base[(size_t)s] * frame_bytes,
+                    HIP_TRY(link_copy(c, frames_out + (size_t)s * frame_stride_bytes, area + A.index((size_t)s) * frame_bytes,
                                       done[(size_t)s] * frame_bytes, kind, c->stream));
         }
     }
-    rx->r_view_first.assign(rx->r_base.begin(), rx->r_base.end());
-    rx->r_view_frames.assign(done.begin(), done.end());
-    bool same_frames = true;
-    for (int s = 1; s < S; ++s) same_frames = same_frames && done[(size_t)s] == done[0];
-    rx->view_ragged = !(same_base && same_frames);
-    if (!rx->view_ragged) { rx->view_base = area + rx->r_base[0] * frame_bytes; rx->view_stride = stream_bytes; rx->view_frames = done[0]; }
-    for (int s = 0; s < S; ++s) {
-        n_frames[s] = done[(size_t)s];
-        rx->r_base[(size_t)s] += done[(size_t)s];
-        rx->r_pending[(size_t)s] = rest[(size_t)s];
-        rx->r_open[(size_t)s] = rest[(size_t)s] > 0 ? 1 : 0;
-        rx->r_count[(size_t)s] = (uint16_t)(rx->r_count[(size_t)s] + done[(size_t)s]);
-    }
+    rx->view.set_each(area, stream_bytes, (size_t)S, A.slots(), done.data());
+    for (int s = 0; s < S; ++s) n_frames[s] = done[(size_t)s];
+    rx->area.commit(done.data(), rest.data());
     if (mem == SDRHIP_MEM_HOST) HIP_TRY(hipStreamSynchronize(c->stream));
     return SDRHIP_OK;
 }

@@ -56,8 +56,8 @@ int rx_launch_batch(sdrhip_rx *rx, sdrhip_rx::Batch &b)
     b.frames = nf;
     hipError_t e = hipSuccess;
     if (nf > nf_max) e = hipErrorInvalidValue; // (cannot happen: rx_max_frames is the pipe's own bound)
-    else if (nf && S == 1) e = link_copy(c, b.out.p, rx->view_base, nf * b.frame_bytes, hipMemcpyDeviceToHost, c->stream);
-    else if (nf) e = link_copy2d(c, b.out.p, nf * b.frame_bytes, rx->view_base, rx->view_stride, nf * b.frame_bytes, S, hipMemcpyDeviceToHost, c->stream);
+    else if (nf && S == 1) e = link_copy(c, b.out.p, rx->view.window(0, b.frame_bytes), nf * b.frame_bytes, hipMemcpyDeviceToHost, c->stream);
+    else if (nf) e = link_copy2d(c, b.out.p, nf * b.frame_bytes, rx->view.window(0, b.frame_bytes), rx->view.stride(), nf * b.frame_bytes, S, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipEventRecord(b.done, c->stream);
     if (e != hipSuccess) {
         b.state = 0; // consumed and lost: never replayed
@@ -85,7 +85,7 @@ int rx_launch_ragged(sdrhip_rx *rx, sdrhip_rx::Batch &b)
     const size_t fb = (size_t)(SDRHIP_NB_ORIGINAL + rx->cfg.nb_fec) * SDRHIP_UDPSIZE;
     // (the frames every stream completes, counted as rx_ragged counts them: the buffers are sized before anything is consumed)
     for (int s = 0; s < S; ++s)
-        sum_done += (size_t)((rx->r_pending[(size_t)s] + (b.r_tot[(size_t)s] >> L)) / SDRHIP_SAMPLES_PER_FRAME);
+        sum_done += rx->area.advance((size_t)s, b.r_tot[(size_t)s] >> L).done;
     const size_t rows_bytes = (size_t)(S + 1) * sizeof(PackRow), segs_bytes = nseg * sizeof(PackSeg);
     const size_t list_off = (rows_bytes + segs_bytes + 15) & ~(size_t)15;
     int rc;
@@ -168,7 +168,7 @@ int rx_launch_ragged(sdrhip_rx *rx, sdrhip_rx::Batch &b)
     hipError_t e = hipSuccess;
     for (int s = 0; s < S && e == hipSuccess; ++s) {
         if (nl + nf[(size_t)s] > sum_done) { e = hipErrorInvalidValue; break; } // (cannot happen: the count above is the pipe's own)
-        for (size_t f = 0; f < nf[(size_t)s]; ++f) list[nl++] = (int32_t)((size_t)s * rx->cap_frames + rx->r_view_first[(size_t)s] + f);
+        for (size_t f = 0; f < nf[(size_t)s]; ++f) list[nl++] = (int32_t)(rx->view.offset((size_t)s, fb) / fb + f);
     }
     if (e == hipSuccess && nl) e = hipMemcpyAsync(rx->a_tab.as<char>() + list_off, list, nl * 4, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && nl) {
@@ -207,7 +207,7 @@ extern "C" int sdrhip_rx_submit(sdrhip_rx *rx, const int16_t *iq_in, size_t n_in
     if (n_in == 0) return SDRHIP_OK;
     if (!iq_in) return fail(SDRHIP_EINVAL, "rx_submit: NULL input");
     if (rx_dgrams_in_flight(rx)) return fail(SDRHIP_EINVAL, "rx_submit: asynchronous datagram batches are in flight: sdrhip_rx_collect_datagrams them first");
-    if (!rx_aligned(rx)) return fail(SDRHIP_EINVAL, "rx_submit: ragged calls left the streams at different frame positions");
+    if (!rx->area.aligned()) return fail(SDRHIP_EINVAL, "rx_submit: ragged calls left the streams at different frame positions");
     if (rx_has_batches(rx, true)) return fail(SDRHIP_EINVAL, "rx_submit: ragged batches are being filled or in flight: collect them first");
     HIP_TRY(hipSetDevice(rx->ctx->device));
     const int S = rx->nstreams;

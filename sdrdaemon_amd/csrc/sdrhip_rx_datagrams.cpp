@@ -25,7 +25,7 @@ int admit(void *arg, const size_t *n_released)
     size_t max_done = 0;
     for (int s = 0; s < rx->nstreams; ++s) {
         const size_t fed = ((*a.carry)[(size_t)s] + n_released[s] * SDRHIP_SAMPLES_PER_FRAME) / U * U;
-        const size_t done = (size_t)((rx->r_pending[(size_t)s] + (fed >> rx->cfg.log2decim)) / SDRHIP_SAMPLES_PER_FRAME);
+        const size_t done = rx->area.advance((size_t)s, fed >> rx->cfg.log2decim).done;
         if (done > max_done) max_done = done;
     }
     if (max_done && !a.frames_out && a.mem != SDRHIP_MEM_DEVICE) return fail(SDRHIP_EINVAL, "rx_process_datagrams: NULL frames_out");
@@ -132,7 +132,7 @@ extern "C" int sdrhip_rx_process_datagrams(sdrhip_rx *rx, const uint8_t *dgrams,
         any = any || fed[(size_t)s] != 0;
     }
     if (!any) { // (nothing released, and no row holds a whole unit: rows and remainders stay)
-        rx->view_frames = 0; rx->view_ragged = false;
+        rx->view.clear();
         return SDRHIP_OK;
     }
     // (follow: the state this call's collection committed -- fecbuf_collect has flipped the double buffer)

@@ -50,7 +50,7 @@ static int rx_submit_batch(sdrhip_rx *rx, FecBufBatch &in, const uint32_t *tv_se
         fed[(size_t)s] = total / U * U;
         left[(size_t)s] = total - fed[(size_t)s];
         any = any || fed[(size_t)s] != 0;
-        sum_done += (size_t)((rx->r_pending[(size_t)s] + (fed[(size_t)s] >> L)) / SDRHIP_SAMPLES_PER_FRAME);
+        sum_done += rx->area.advance((size_t)s, fed[(size_t)s] >> L).done;
     }
     const size_t b_frames = sum_done * fb, b_total = b_frames + kall * DG_REC;
     const size_t seg_bytes = (size_t)2 * S * sizeof(RxDeliverSeg);
@@ -93,7 +93,7 @@ static int rx_submit_batch(sdrhip_rx *rx, FecBufBatch &in, const uint32_t *tv_se
         if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "rx join launch: %s (the batch is lost)", hipGetErrorString(e));
         *carry = left;
     } else { // (nothing released, and no row holds a whole unit: rows and remainders stay)
-        rx->view_frames = 0; rx->view_ragged = false;
+        rx->view.clear();
     }
     // ---- the delivery: every stream's frames (its sliding window in `work`), then the records, gathered and downloaded in ONE copy
     RxDeliverSeg *seg = b.d_seg.as<RxDeliverSeg>();
@@ -102,7 +102,7 @@ static int rx_submit_batch(sdrhip_rx *rx, FecBufBatch &in, const uint32_t *tv_se
     for (int s = 0; s < S; ++s) {
         if (!nf[(size_t)s]) continue;
         RxDeliverSeg &g = seg[nseg++];
-        g.src = ((size_t)s * rx->cap_frames + rx->r_view_first[(size_t)s]) * fb;
+        g.src = rx->view.offset((size_t)s, fb);
         g.bytes = nf[(size_t)s] * fb; g.dst = dst; g.from_records = 0;
         dst += g.bytes;
     }

@@ -65,16 +65,10 @@ extern "C" int sdrhip_rx_reset_streams(sdrhip_rx *rx, const uint8_t *mask)
             if (rx->fb) fecbuf_reset_done(rx->fb, m);
             // the open frame is dropped where it lies (its slot keeps the stale bytes: the next frame the stream opens writes every
             // block).  When every stream was reset no frame is open anywhere, so every window goes back to slot 0 as well: the
-            // streams stand at the same position again (rx_aligned) whatever ragged steps moved their windows apart before, and the
+            // streams stand at the same position again (aligned) whatever ragged steps moved their windows apart before, and the
             // uniform step, pipelined mode and uniform batches are available as on a fresh handle.  (Launches in flight that read
             // the old windows are ahead of the next call's on the context's stream.)
-            for (size_t s = 0; s < (size_t)rx->nstreams; ++s) {
-                if (m && !m[s]) continue;
-                rx->r_pending[s] = 0;
-                rx->r_open[s] = 0;
-                rx->r_count[s] = 0;
-                if (!m) rx->r_base[s] = 0;
-            }
+            rx->area.reset(m);
         });
 }
 
@@ -230,15 +224,14 @@ extern "C" int sdrhip_rx_export_stream(sdrhip_rx *rx, int stream, void *blob, si
     RxBlobHost h;
     memset(&h, 0, sizeof(h));
     h.hb_variant = (uint32_t)rx->cfg.hb_variant; h.stage0_int16 = decimators_stage0_int16(rx->dec) ? 1 : 0;
-    h.r_open = rx->r_open[s]; h.r_count = rx->r_count[s]; h.r_pending = rx->r_pending[s];
+    h.r_open = rx->area.open(s); h.r_count = rx->area.count(s); h.r_pending = rx->area.pending(s);
     HIP_TRY(hipMemsetAsync(dev, 0, RX_DEV_BYTES, c->stream)); // (the pieces the stream does not have)
     StreamCopyArgs a;
     memset(&a, 0, sizeof(a));
     a.carry_seg = -1;
     add_seg(&a, decimators_row(rx->dec, stream, 0), dev + RX_ROW, DEC_STATE_WORDS * 4);
     if (h.r_open) {
-        const size_t frame_bytes = (size_t)(SDRHIP_NB_ORIGINAL + rx->cfg.nb_fec) * SDRHIP_UDPSIZE;
-        add_seg(&a, rx->work.as<uint8_t>() + (s * rx->cap_frames + rx->r_base[s]) * frame_bytes, dev + RX_FRAME, SLOT_BYTES);
+        add_seg(&a, rx->work.as<uint8_t>() + rx->area.index(s) * rx_frame_bytes(rx), dev + RX_FRAME, SLOT_BYTES);
     }
     if (rx->fb) {
         unsigned *carry_dev = nullptr;
@@ -270,7 +263,7 @@ extern "C" int sdrhip_rx_import_stream(sdrhip_rx *rx, int stream, const void *bl
     memcpy(&h, in + sizeof(BlobHead), sizeof(h));
     memcpy(&st, in + RX_HOST_BYTES + RX_ST, sizeof(st));
     if ((int)h.hb_variant != rx->cfg.hb_variant) return fail(SDRHIP_EINVAL, "%s: the blob's histories belong to hb_variant %u, the bank runs %d", who, h.hb_variant, rx->cfg.hb_variant);
-    if (h.r_open > 1 || h.r_pending >= SDRHIP_SAMPLES_PER_FRAME || (!h.r_open && h.r_pending) || h.r_count > 0xffffu || h.carry > 63 || h.has_collector > 1 ||
+    if (!RxFrameArea::importable(h.r_pending, h.r_open, h.r_count) || h.carry > 63 || h.has_collector > 1 ||
         (!h.has_collector && h.carry))
         return fail(SDRHIP_EINVAL, "%s: the blob's framing state is not one a stream can be in", who);
     if (h.has_collector && (rc = check_state(st, who))) return rc;
@@ -283,7 +276,7 @@ extern "C" int sdrhip_rx_import_stream(sdrhip_rx *rx, int stream, const void *bl
     std::vector<size_t> *carry = nullptr;
     if (rx->fb && (rc = fecbuf_join_carry(rx->fb, &carry_dev, &carry))) return rc;
     if (h.carry && (rc = rx_join_rows(rx, 0, who))) return rc;
-    if (h.r_open && (rc = rx_area_room(rx))) return rc;
+    if (h.r_open && (rc = rx_area_room(rx, nullptr))) return rc;
     if ((rc = reserve_settled(c, rx->x_blob, RX_DEV_BYTES))) return rc;
     PinnedBuf &pin = import_pin(rx);
     if ((rc = pin.reserve(RX_DEV_BYTES))) return rc;
@@ -299,8 +292,7 @@ extern "C" int sdrhip_rx_import_stream(sdrhip_rx *rx, int stream, const void *bl
     add_seg(&a, dev + RX_ROW, decimators_row(rx->dec, stream, 0), DEC_STATE_WORDS * 4);
     add_seg(&a, dev + RX_ROW, decimators_row(rx->dec, stream, 1), DEC_STATE_WORDS * 4);
     if (h.r_open) { // (its 128 original blocks, the meta block it was opened with among them; encoded with the fecblk in force when it completes)
-        const size_t frame_bytes = (size_t)(SDRHIP_NB_ORIGINAL + rx->cfg.nb_fec) * SDRHIP_UDPSIZE;
-        add_seg(&a, dev + RX_FRAME, rx->work.as<uint8_t>() + (s * rx->cap_frames + rx->r_base[s]) * frame_bytes, SLOT_BYTES);
+        add_seg(&a, dev + RX_FRAME, rx->work.as<uint8_t>() + rx->area.index(s) * rx_frame_bytes(rx), SLOT_BYTES);
     }
     if (rx->fb) {
         scatter_collector(rx->fb, stream, dev, RX_ST, RX_CARRY, st, h.has_collector != 0, &a);
@@ -308,7 +300,7 @@ extern "C" int sdrhip_rx_import_stream(sdrhip_rx *rx, int stream, const void *bl
         a.word_dst = carry_dev + s; a.word_val = h.carry;
     }
     if ((rc = import_run(c, a, pin, rx->x_blob, RX_DEV_BYTES))) return rc;
-    rx->r_pending[s] = h.r_pending; rx->r_open[s] = (uint8_t)h.r_open; rx->r_count[s] = (uint16_t)h.r_count;
+    rx->area.import_stream(s, h.r_pending, h.r_open, h.r_count);
     if (!h.stage0_int16) decimators_clear_stage0_int16(rx->dec);
     if (rx->fb) fecbuf_import_host(rx->fb, stream, st, h.carry);
     return SDRHIP_OK;

@@ -248,6 +248,95 @@ def test_mixed_uniform_ragged_and_reconfigure(ctx):
     uniform((2 * F) << L, 9)
 
 
+def test_ragged_wrap_of_some_streams_only(ctx):
+    """A window of one call (rx_window = 1): stream 0's window passes the end of the area on calls where the other two stay, and its
+    open frame moves to slot 0 in place, alone; then a uniform call on the unaligned bank (the ragged route).  Against twin pipes."""
+    rs = np.random.RandomState(21)
+    S, L = 3, 1
+    cfg = dict(log2decim=L, nb_fec=8)
+    ctx.set_option("rx_window", 1)
+    try:
+        bank, twins = sd.RxPipe(ctx, S, **cfg), Twins(ctx, S, **cfg)
+        n = (F // 2) << L  # half a frame everywhere: one slot per stream, every stream keeps an open frame
+        x = rand_iq(rs, S, n)
+        g = bank.process(x, 1, 2)
+        assert g.shape[1] == 0 and all(e.shape[0] == 0 for e in twins.process(x, [n] * S, [1] * S, [2] * S))
+        counts = [(9 * F // 4) << L, (F // 4) << L, 0]
+        total = np.zeros(S, np.int64)
+        for k in range(8):
+            x = rand_iq(rs, S, max(counts))
+            secs, usecs = [10 + k + s for s in range(S)], [5 * s for s in range(S)]
+            g, nf = bank.process_ragged(x, counts, secs, usecs)
+            check_call(g, nf, twins.process(x, counts, secs, usecs), k)
+            total += nf
+        assert list(total) == [(F // 2 + 8 * (9 * F // 4)) // F, (F // 2 + 8 * (F // 4)) // F, 0]
+        n = (F << L) + 300
+        x = rand_iq(rs, S, n)
+        g = bank.process(x, 30, 4)
+        exp = twins.process(x, [n] * S, [30] * S, [4] * S)
+        assert g.shape[1] == max(e.shape[0] for e in exp)
+        for s in range(S):
+            assert np.array_equal(g[s, :exp[s].shape[0]], exp[s]), s
+    finally:
+        ctx.set_option("rx_window", 0)
+
+
+def test_fecblk_change_on_unaligned_bank_with_open_frames(ctx):
+    """ragged calls leave three streams at three positions, each with an open frame; the frame size changes (every open frame moves
+    to slot 0 of a new area, 128 original blocks each); two more ragged calls.  Against twin pipes reconfigured at the same points."""
+    rs = np.random.RandomState(22)
+    S, L = 3, 1
+    cfg = dict(log2decim=L, nb_fec=8)
+    bank, twins = sd.RxPipe(ctx, S, **cfg), Twins(ctx, S, **cfg)
+
+    def ragged(counts, sec):
+        x = rand_iq(rs, S, max(counts))
+        secs, usecs = [sec + s for s in range(S)], [7 * s for s in range(S)]
+        g, nf = bank.process_ragged(x, counts, secs, usecs)
+        check_call(g, nf, twins.process(x, counts, secs, usecs), counts)
+        return nf
+
+    assert list(ragged([(2 * F + F // 3) << L, (F + F // 2) << L, (F // 4) << L], 1)) == [2, 1, 0]
+    assert list(ragged([(F // 3) << L, (F + 100) << L, 6], 2)) == [0, 1, 0]  # (windows at slots 2, 2 and 0 -- samples 2 F / 3, F / 2 + 100, F / 4 + 3)
+    bank.reconfigure(nb_fec=40)
+    twins.reconfigure(nb_fec=40)
+    assert list(ragged([(F // 2) << L, (F // 2) << L, F << L], 3)) == [1, 1, 1]
+    assert list(ragged([(2 * F) << L, 0, (3 * F) << L], 4)) == [2, 0, 3]
+
+
+def test_frames_view_ragged_after_uniform_and_pipelined_calls(ctx):
+    """sdrhip_rx_frames_view_ragged describes what a uniform call delivered too: after a uniform call, after pipelined calls -- the one
+    whose frames lie in the old area included (a wrapped window that would reach the waiting frames gets a new area) -- and after
+    flush_view.  The tensors formed from (base, stride, first, count) are the frames process() copied out."""
+    rs = np.random.RandomState(23)
+    S, L, R = 2, 1, 8
+
+    def same(views, frames, where):
+        ctx.synchronize()
+        for s in range(S):
+            assert views[s].shape[0] == frames.shape[1], (where, s)
+            assert np.array_equal(views[s].cpu().numpy(), np.asarray(frames[s].cpu() if torch.is_tensor(frames) else frames[s])), (where, s)
+
+    a = sd.RxPipe(ctx, S, log2decim=L, nb_fec=R)
+    p = sd.RxPipe(ctx, S, log2decim=L, nb_fec=R, pipelined=True)
+    # (decimated counts of test_pipelined_many_calls_wrap_the_frame_window up to its first call that keeps the old area: the last one)
+    sizes = [64516, 16129, 64516, 5000, 5000, 16129, 700, 0, 5000, 64516, 48387, 64516, 48387, 48387, 64516, 150000]
+    prev = np.zeros((S, 0, 128 + R, 512), np.uint8)
+    for i, c in enumerate(sizes):
+        x = rand_iq(rs, S, c << L)[:, :c << L]
+        e = a.process(x, 100 + i, 3 * i) if c else np.zeros((S, 0, 128 + R, 512), np.uint8)
+        if c:
+            same(a.frames_view_ragged(), e, ("uniform", i))
+        g = p.process(x, 100 + i, 3 * i)
+        assert np.array_equal(g, prev), i
+        same(p.frames_view_ragged(), g, ("pipelined", i))
+        prev = e
+    assert prev.shape[1] == 10 and g.shape[1] == 4
+    last = p.flush_view()
+    same(p.frames_view_ragged(), last.torch(), "flush_view")
+    assert np.array_equal(last.torch().cpu().numpy(), prev)
+
+
 @pytest.mark.parametrize("fmt", ["u8", "s8"])
 @pytest.mark.parametrize("device", [False, True])
 def test_iq8_input(ctx, fmt, device):
