@@ -713,6 +713,58 @@ int sdrhip_tx_submit_datagrams_tagged(sdrhip_tx *tx, const uint8_t *dgrams, cons
 int sdrhip_rx_submit_datagrams_tagged(sdrhip_rx *rx, const uint8_t *dgrams, const uint16_t *stream_of, size_t n_total,
                                       const uint32_t *tv_sec, const uint32_t *tv_usec);
 
+/* ------------------------------------------------------------ Rx egress: one departure-order array -- */
+/* The mirror of the tagged submit.  sdrhip_rx_collect_ragged / sdrhip_rx_collect_datagrams hand a batch back per stream, stream
+ * after stream, one memcpy per stream; a hub that sends what it was handed puts stream 0's n_frames x (128 + nb_fec) datagrams on
+ * the wire back to back, then stream 1's.  The reference never does that to a receiver: UDPSinkFEC::transmitUDP sleeps txDelay
+ * between any two datagrams of a stream (UDPSinkFEC.cpp:259-282; the control channel's txdelay key, sdrdaemonrx.cpp:607-613),
+ * because receivers with small socket buffers drop bursts.  A bank of N streams gives every receiver that gap for free: datagram
+ * j of every stream before datagram j + 1 of any.
+ * sdrhip_rx_set_egress sets a host-side mode (nothing is enqueued, nothing waited for) for the batches launched LATER by
+ * sdrhip_rx_submit_ragged, sdrhip_rx_submit_datagrams and sdrhip_rx_submit_datagrams_tagged; a batch keeps the order it was
+ * launched with.  SDRHIP_EINVAL, nothing changed: an unknown order, a NULL handle, a batch being filled, a bank of more than 65535
+ * streams.  While the order is not SDRHIP_EGRESS_OFF, sdrhip_rx_submit (uniform batches) returns SDRHIP_EINVAL with nothing
+ * consumed: a ragged submit with equal counts does that job.  With SDRHIP_EGRESS_OFF, the default, every entry launches and
+ * returns exactly what it did before this mode existed.
+ * Departure order (SDRHIP_EGRESS_ROUND_ROBIN).  B = blocks_per_frame = 128 + the nb_fec the batch was submitted with; stream s
+ * delivered F_s = n_frames[s] frames, that is D_s = F_s B datagrams in the reference's wire order (frame after frame, blocks
+ * 0 .. B - 1 inside a frame, UDPSinkFEC.cpp:259).  The array is rounds j = 0, 1, 2, ... concatenated; round j holds datagram j of
+ * every stream with D_s > j, streams in ascending order; stream_of[i] names the stream of entry i.  Per stream, the subsequence is
+ * byte for byte what the stream-order collect returns for that stream; collector state, carry, histories, open frames, counters
+ * and records are those of the same batch in stream order.
+ * sdrhip_rx_collect_egress returns the OLDEST batch, of either kind, that was launched with an order.  n_frames: host array of
+ * nstreams entries, required.  A datagram batch: n_released is required and the records land at info_out[s * max_released + k];
+ * a stream with more than max_released records: SDRHIP_EINVAL with both count arrays filled, the batch stays.  A ragged batch:
+ * info_out and n_released may be NULL; n_released, when given, is zero-filled.  SDRHIP_OK: one batch collected (one that
+ * completed no frame: n_dgrams = 0).  SDRHIP_EBUSY: none was -- nothing submitted, or (wait = 0) the oldest batch is still in
+ * flight; wait = 1 launches a ragged batch that is still being filled and blocks outside the context lock.  One kind of collect
+ * per batch: sdrhip_rx_collect_ragged / sdrhip_rx_collect_datagrams on a batch launched with an order, and
+ * sdrhip_rx_collect_egress on a stream-order batch, return SDRHIP_EINVAL and the batch stays.
+ * Lending: out->dgrams and out->stream_of point into the batch's own ring slot -- its pinned download buffer and its tag array.
+ * No host core copies a payload byte.  They stay valid and unchanged until sdrhip_rx_release_egress, the next successful
+ * sdrhip_rx_collect_egress (which releases implicitly) or sdrhip_rx_destroy.  A lent batch occupies its ring slot: a submit that
+ * finds every slot in flight or lent returns SDRHIP_EBUSY with nothing consumed (at depth 1: release before the next submit), and
+ * sdrhip_rx_set_async and sdrhip_rx_set_input_format are refused while a batch is lent.  A lent batch is not in flight: once every
+ * batch has been collected, lent or not, the synchronous entries and sdrhip_fecbuf_* on the collector work as after the last
+ * stream-order collect.  sdrhip_rx_release_egress with nothing lent returns SDRHIP_OK.
+ * How: one kernel (KE) in the place of the stream-order delivery writes the batch's one download buffer in departure order, from
+ * a table of one entry per delivered frame that the host derives from its own counts; the host writes the tags from the same
+ * counts, they never cross the link.  Everything the order needs is allocated before the batch consumes anything.  Link traffic
+ * is the stream-order batch's: down ("d2h_bytes") exactly sum n_frames x B x 512 + sum n_released x 16 in one copy.
+ * Not covered: uniform batches, the synchronous entries, a device-resident view of the array, other orders, the Tx pipe. */
+#define SDRHIP_EGRESS_OFF 0          /* default: frames per stream, sdrhip_rx_collect_ragged / _datagrams */
+#define SDRHIP_EGRESS_ROUND_ROBIN 1  /* one departure-order array per batch, sdrhip_rx_collect_egress */
+typedef struct {
+    const uint8_t *dgrams;      /* n_dgrams x 512 bytes in departure order (lent) */
+    const uint16_t *stream_of;  /* n_dgrams tags: the stream of datagram i (lent) */
+    size_t n_dgrams;            /* = blocks_per_frame x sum n_frames[s] */
+    size_t blocks_per_frame;    /* 128 + the nb_fec the batch was submitted with */
+} sdrhip_rx_egress;
+int sdrhip_rx_set_egress(sdrhip_rx *rx, int order);
+int sdrhip_rx_collect_egress(sdrhip_rx *rx, sdrhip_rx_egress *out, size_t *n_frames, size_t max_released,
+                             sdrhip_fecbuf_frame *info_out, size_t *n_released, int wait);
+int sdrhip_rx_release_egress(sdrhip_rx *rx);
+
 /* ---- Per-stream lifecycle: one stream of a bank begins again while the others run on.
  * In the reference one stream is one sdrdaemonrx / sdrdaemontx process, and restarting that process gives the stream what the
  * constructors leave: zero half-band histories (Decimators.h:56-70, Interpolators.h:47-52: EO1.h:171-188 / IntHalfbandFilterDB's

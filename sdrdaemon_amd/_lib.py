@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get("SDRHIP_LIB_PATH") or os.path.join(HERE, "libsdrhip.so
 
 MEM_HOST, MEM_DEVICE = 0, 1
 DGRAM_SKIP = 0xffff  # SDRHIP_DGRAM_SKIP
+EGRESS_OFF, EGRESS_ROUND_ROBIN = 0, 1
 FC_INF, FC_SUP, FC_CEN = 0, 1, 2
 HB_EO1, HB_DB = 0, 1
 IQ_S16, IQ_U8, IQ_S8 = 0, 1, 2
@@ -48,6 +49,7 @@ EXPORTS = [
     "sdrhip_rx_stream_state_bytes", "sdrhip_tx_stream_state_bytes", "sdrhip_rx_export_stream", "sdrhip_rx_import_stream",
     "sdrhip_tx_export_stream", "sdrhip_tx_import_stream",
     "sdrhip_fecbuf_write_and_read_tagged", "sdrhip_tx_submit_datagrams_tagged", "sdrhip_rx_submit_datagrams_tagged",
+    "sdrhip_rx_set_egress", "sdrhip_rx_collect_egress", "sdrhip_rx_release_egress",
 ]
 
 
@@ -68,6 +70,10 @@ class CM256Block(C.Structure):
 class DecimPlan(C.Structure):
     _fields_ = [("path", C.c_int), ("wps", C.c_int), ("npieces", C.c_int), ("nseg", C.c_int),
                 ("span", C.c_size_t), ("head", C.c_size_t), ("tail_start", C.c_size_t)]
+
+
+class RxEgress(C.Structure):  # sdrhip_rx_egress
+    _fields_ = [("dgrams", C.c_void_p), ("stream_of", C.c_void_p), ("n_dgrams", C.c_size_t), ("blocks_per_frame", C.c_size_t)]
 
 
 class RxConfig(C.Structure):
@@ -166,6 +172,9 @@ def load():
     lib.sdrhip_fecbuf_write_and_read_tagged.argtypes = [vp, vp, u16p, sz, vp, sz, vp, sz, vp, C.POINTER(sz), i]
     lib.sdrhip_tx_submit_datagrams_tagged.argtypes = [vp, vp, u16p, sz]
     lib.sdrhip_rx_submit_datagrams_tagged.argtypes = [vp, vp, u16p, sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    lib.sdrhip_rx_set_egress.argtypes = [vp, i]
+    lib.sdrhip_rx_collect_egress.argtypes = [vp, C.POINTER(RxEgress), C.POINTER(sz), sz, vp, C.POINTER(sz), i]
+    lib.sdrhip_rx_release_egress.argtypes = [vp]
     lib.sdrhip_rx_set_stream_meta.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.sdrhip_rx_get_stream_meta.argtypes = [vp, i, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.sdrhip_rx_set_follow_meta.argtypes = [vp, i]

@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "rx_egress_order.h"
+
 // loads of data that is streamed through once (IQ input, frames): non-temporal.  tools/dma_probe.hip on MI355X: 7.1 TB/s with
 // `nt` against 6.2 TB/s with the default cache policy, register loads and LDS-DMA alike (stores: no difference).
 #ifndef SDRHIP_NT
@@ -576,6 +578,22 @@ hipError_t launch_rx_deliver(const RxDeliverSeg *segs, int nseg, uint32_t grid, 
 // counts [S][FB_COUNTS] against the shadow's expect [S][4] = {K, D, maxrow, maxrec}: +1 on *mismatch per
 // stream that differs
 hipError_t launch_fecbuf_shadow_check(const int *counts, const int *expect, int nstreams, unsigned *mismatch, hipStream_t stream);
+// KE (rx_egress_kernels.hip), departure-order batches (sdrhip_rx_set_egress): run k = one delivered frame, blocks_per_frame datagrams
+// from frames + src to out + dst + b * stride (rx_egress_order.h; wg_per_frame = its wg_per_frame()), then the records of a datagram
+// batch: record k < place[s].cnt of stream s from records + 16 (s kmax + k) to out + dst + 16 (place[s].pre + k); nslots = streams x
+// kmax (0: no records), records readable for all of them.  Bases and offsets 16-byte aligned; the host that made the tables vouches
+// for every piece lying inside `out`
+struct RxEgressRecPlace {
+    uint32_t pre, cnt, pad[2]; // records of the streams before this one, and its own (16 bytes: KE reads an entry with one dwordx4)
+};
+struct RxEgressRecords {
+    const RxEgressRecPlace *place; // [streams] (device)
+    const uint8_t *records;
+    uint64_t dst;
+    uint32_t kmax, nslots;
+};
+hipError_t launch_rx_egress(const RxEgressRun *runs, uint64_t nruns, uint32_t wg_per_frame, uint32_t blocks_per_frame, const uint8_t *frames,
+                            uint8_t *out, const RxEgressRecords &rec, hipStream_t stream);
 // KX (dgram_demux_kernels.hip), tagged datagram batches: datagram i of the arrival-order array src goes to dst + 512 * dest[i]
 // (device table, n_total entries; 0xffffffff: the datagram is moved nowhere).  src and dst 16-byte aligned, n_total below 2^30;
 // the host that made dest vouches for every entry lying inside dst

@@ -10,7 +10,8 @@
 
 namespace sdrhip {
 // The ring of batches behind a pipe's submit / collect entries, created on first use with depth 4.  B has `state` (0 free, 1 being
-// filled, 2 in flight), the event `done` and release().  tail = the batch being filled, head = the next one to collect.
+// filled, 2 in flight, 3 collected and lent to the caller: sdrhip_rx_collect_egress), the event `done` and release().  tail = the
+// batch being filled, head = the next one to collect.  A lent batch lies behind head and keeps its slot until it is released.
 template <class B> struct BatchRing {
     std::vector<B> v;
     size_t head = 0, tail = 0;
@@ -24,7 +25,7 @@ template <class B> struct BatchRing {
     }
     void reset(size_t depth) { release(false); v.assign(depth, B()); head = tail = 0; } // (the caller refuses while anything is in flight)
     B &tail_batch() { if (v.empty()) v.assign(4, B()); return v[tail % v.size()]; }
-    // a batch that is being filled or in flight and satisfies pred
+    // a batch that is being filled, in flight or lent and satisfies pred
     template <class P> bool any(P pred) const
     {
         for (const auto &b : v)
@@ -45,7 +46,8 @@ template <class B> struct BatchRing {
         if (v.empty()) return fail(SDRHIP_EBUSY, "%s: nothing was submitted", who);
         for (;;) {
             B &h = v[head % v.size()];
-            if (h.state == 0) return fail(SDRHIP_EBUSY, "%s: nothing was submitted", who); // (SDRHIP_OK always means: one batch collected -- possibly empty)
+            // (SDRHIP_OK always means: one batch collected -- possibly empty; a lent batch at the head of a ring it fills was collected)
+            if (h.state == 0 || h.state == 3) return fail(SDRHIP_EBUSY, "%s: nothing was submitted", who);
             if (h.state == 1) {
                 if (!wait) return fail(SDRHIP_EBUSY, "%s: the oldest batch is still being filled (wait = 1 launches it as it is)", who);
                 int rc = launch_filling(h);
@@ -120,7 +122,7 @@ struct sdrhip_rx {
         size_t in_cap = 0;        // row length of `in` in samples: staged blocks lie stream-major, [stream][in_cap], at their batch offset
         uint32_t tv_sec = 0, tv_usec = 0;
         size_t frames = 0, frame_bytes = 0;
-        int state = 0;            // 0 free, 1 filling, 2 in flight
+        int state = 0;            // 0 free, 1 filling, 2 in flight, 3 lent (collected by sdrhip_rx_collect_egress, not yet released)
         // ---- a ragged batch (sdrhip_rx_submit_ragged; a batch holds one kind only): blocks of per-stream counts, packed
         bool ragged = false;
         struct Run { const char *p; size_t off, bytes; }; // packed bytes of one block: in place at p, or staged at `in` + off (p NULL)
@@ -140,11 +142,17 @@ struct sdrhip_rx {
         sdrhip::PinnedBuf d_seg;
         sdrhip::RxTabs d_tabs;
         std::vector<size_t> d_rel;            // released frames (records) per stream
+        // ---- departure-order egress (sdrhip_rx_set_egress; a ragged or a datagram batch): the order the batch was launched with,
+        // KE's table (one run per delivered frame, then the record places), and the tags the collect lends beside `out`
+        int egress = 0;
+        sdrhip::PinnedBuf e_tab;
+        std::vector<uint16_t> e_tags;
         void release()
         {
             if (done) (void)hipEventDestroy(done);
             done = nullptr;
             in.release(); din.release(); out.release(); r_tab.release(); d_seg.release(); d_tabs.rows.release(); d_tabs.flist.release();
+            e_tab.release();
         }
     };
     sdrhip::BatchRing<Batch> ring;
@@ -152,6 +160,10 @@ struct sdrhip_rx {
     // a_pk, the delivery's segments in a_tab, the gathered delivery in a_frames)
     sdrhip::DevBuf a_pk, a_din, a_tab, a_frames;
     int a_blocks = 1;             // blocks per launch
+    // ---- departure-order egress (sdrhip_rx_set_egress): the order later launches get, and KE's table on the device
+    int egress = 0;
+    sdrhip::DevBuf e_tab;
+    sdrhip::RxEgressOrder e_order;
     bool consumed = false;        // set by sdrhip_rx_process once the decimator launch of the call went out (the filter state advanced)
     // ---- input format (sdrhip_rx_set_input_format): 8-bit input is widened by K0 into `wide`, the decimator's int16 input
     int in_fmt = sdrhip::IQF_S16;
@@ -257,15 +269,21 @@ struct sdrhip_tx {
 namespace sdrhip {
 static_assert(RX_FRAME_SAMPLES == SDRHIP_SAMPLES_PER_FRAME, "rx_frame_area.h frames the header's frame");
 inline size_t rx_frame_bytes(const sdrhip_rx *rx) { return (size_t)(SDRHIP_NB_ORIGINAL + rx->cfg.nb_fec) * SDRHIP_UDPSIZE; }
-// batches of the ring that are being filled or in flight, of the ragged (or the uniform) kind
+// batches of the ring that are being filled or in flight, of the ragged (or the uniform) kind.  (A lent batch -- state 3 -- is
+// neither: it was collected, and only its slot is still taken.)
 inline bool rx_has_batches(const sdrhip_rx *rx, bool ragged)
 {
-    return rx->ring.any([ragged](const sdrhip_rx::Batch &b) { return !b.dg && b.ragged == ragged; });
+    return rx->ring.any([ragged](const sdrhip_rx::Batch &b) { return b.state != 3 && !b.dg && b.ragged == ragged; });
 }
 // ... of the datagram kind (sdrhip_rx_submit_datagrams): every other entry that moves the pipe is refused meanwhile
 inline bool rx_dgrams_in_flight(const sdrhip_rx *rx)
 {
-    return rx->ring.any([](const sdrhip_rx::Batch &b) { return b.dg; });
+    return rx->ring.any([](const sdrhip_rx::Batch &b) { return b.state != 3 && b.dg; });
+}
+// ... of any kind: what the synchronous entries wait for (ring.busy() counts lent batches as well: the slots are taken)
+inline bool rx_batches_active(const sdrhip_rx *rx)
+{
+    return rx->ring.any([](const sdrhip_rx::Batch &b) { return b.state != 3; });
 }
 // samples a datagram call feeds the decimator in one piece: 2^log2decim, but 4 for decimate2_inf / _sup, which walk their input in
 // fours (Decimators.cpp:48,76) -- the datagram entries never hand them a tail of 2
@@ -288,6 +306,19 @@ int rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, size_t in
 // straight into the windows.  rx_ragged itself then allocates nothing, unless a matrix-core plan it counted on does not apply
 int rx_ragged_room(sdrhip_rx *rx, const size_t *n_in, RxTabs *tabs);
 int rx_collector(sdrhip_rx *rx); // the datagram collector, created on first use
+// a uniform or ragged batch that is still being filled goes out as it is (wait_oldest's launch_filling; sdrhip_rx_async.cpp)
+int rx_launch_filling(sdrhip_rx *rx, sdrhip_rx::Batch &b);
+// ---- departure-order egress (sdrhip_rx_egress.cpp), for a launch path whose batch has an order (b.egress).  rx_egress_room:
+// everything KE's launch needs for a batch of at most `frames` delivered frames of blocks_per_frame datagrams -- the slot's pinned
+// table and tags, the device table -- ahead of anything that consumes input (a device table that grows synchronises once).
+// rx_egress_launch: the runs, the record places and the tags from the delivered counts n_frames[s] (each stream's frames contiguous
+// in `work` from view.offset(s, frame_bytes)), the table's upload, and KE into a_frames: the datagrams in departure order, then --
+// a datagram batch: released = the collector's [S][4] results, records = its public records [S][kmax] -- the records as KD lays
+// them out.  The table, the tags and the device table are rx_egress_room's; the order's own vectors (one entry per frame) are the
+// handle's and keep their capacity.
+int rx_egress_room(sdrhip_rx *rx, sdrhip_rx::Batch &b, size_t frames, size_t blocks_per_frame);
+hipError_t rx_egress_launch(sdrhip_rx *rx, sdrhip_rx::Batch &b, const size_t *n_frames, size_t frame_bytes, const int *released, size_t kmax,
+                            const uint8_t *records);
 // the frame area made ready for a ragged step that completes done[s] frames of stream s (NULL: none -- a slot per stream for
 // sdrhip_rx_import_stream into a bank that never ran): plan, new area or in-place moves
 int rx_area_room(sdrhip_rx *rx, const size_t *done);

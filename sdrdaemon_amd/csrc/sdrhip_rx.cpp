@@ -198,7 +198,7 @@ extern "C" void sdrhip_rx_destroy(sdrhip_rx *rx)
     if (rx->ev_framed) (void)hipEventDestroy(rx->ev_framed);
     if (rx->ev_enc) (void)hipEventDestroy(rx->ev_enc);
     rx->ring.release(true);
-    rx->a_pk.release(); rx->a_din.release(); rx->a_tab.release(); rx->a_frames.release();
+    rx->a_pk.release(); rx->a_din.release(); rx->a_tab.release(); rx->a_frames.release(); rx->e_tab.release();
     sdrhip_fecbuf_destroy(rx->fb); // (synchronises the stream)
     rx->j_rows.release();
     for (auto &b : rx->sm_pin) b.release();
@@ -684,7 +684,7 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
     // ---- everything that can be refused is checked before anything is consumed
     if (int e = check_mem(mem)) return e;
     if (rx->pipelined) return fail(SDRHIP_EINVAL, "rx_process_ragged: not available in pipelined mode");
-    if (!batch && rx->ring.busy()) return fail(SDRHIP_EINVAL, "rx_process_ragged: asynchronous batches are being filled or in flight: collect them first");
+    if (!batch && rx_batches_active(rx)) return fail(SDRHIP_EINVAL, "rx_process_ragged: asynchronous batches are being filled or in flight: collect them first");
     size_t max_in = 0;
     for (int s = 0; s < S; ++s) if (n_in[s] > max_in) max_in = n_in[s];
     if (S == 1) in_stride = max_in;

@@ -44,6 +44,7 @@ int rx_launch_batch(sdrhip_rx *rx, sdrhip_rx::Batch &b)
     // behind the decimator launch (rx->consumed) is dropped: its samples are in the filter state already, replaying them would
     // duplicate samples and shift every later stamp
     b.frame_bytes = (size_t)(SDRHIP_NB_ORIGINAL + rx->cfg.nb_fec) * SDRHIP_UDPSIZE;
+    b.egress = 0;
     const size_t nf_max = sdrhip_rx_max_frames(rx, b.n_in);
     if (nf_max && (rc = b.out.reserve((size_t)S * nf_max * b.frame_bytes))) return rc;
     if ((rc = rx->ring.ensure_event(b))) return rc;
@@ -99,6 +100,8 @@ int rx_launch_ragged(sdrhip_rx *rx, sdrhip_rx::Batch &b)
     if (sum_done && (rc = b.out.reserve(sum_done * fb))) return rc;
     if (sum_done && (rc = rx->a_frames.reserve(sum_done * fb))) return rc;
     if ((rc = rx->ring.ensure_event(b))) return rc;
+    b.egress = rx->egress; // (set_egress is refused while a batch is being filled: the order of the batch's first block)
+    if (b.egress && (rc = rx_egress_room(rx, b, sum_done, fb / SDRHIP_UDPSIZE))) return rc;
 
     // ---- K0p's table: segments stream by stream (block order inside), sources at their packed offsets (block-major, stream-minor)
     PackRow *rows = b.r_tab.as<PackRow>();
@@ -170,8 +173,10 @@ int rx_launch_ragged(sdrhip_rx *rx, sdrhip_rx::Batch &b)
         if (nl + nf[(size_t)s] > sum_done) { e = hipErrorInvalidValue; break; } // (cannot happen: the count above is the pipe's own)
         for (size_t f = 0; f < nf[(size_t)s]; ++f) list[nl++] = (int32_t)(rx->view.offset((size_t)s, fb) / fb + f);
     }
-    if (e == hipSuccess && nl) e = hipMemcpyAsync(rx->a_tab.as<char>() + list_off, list, nl * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && nl) {
+    // (departure order: KE in the gather's place writes the same buffer, sdrhip_rx_egress.cpp)
+    if (e == hipSuccess && nl && b.egress) e = rx_egress_launch(rx, b, nf.data(), fb, nullptr, 0, nullptr);
+    else if (e == hipSuccess && nl) e = hipMemcpyAsync(rx->a_tab.as<char>() + list_off, list, nl * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && nl && !b.egress) {
         b.r_tab.mark(c->stream);
         e = launch_frame_gather(rx->work.as<uint8_t>(), fb, reinterpret_cast<const int32_t *>(rx->a_tab.as<char>() + list_off), nl,
                                 rx->a_frames.as<uint8_t>(), c->stream);
@@ -189,12 +194,14 @@ int rx_launch_ragged(sdrhip_rx *rx, sdrhip_rx::Batch &b)
 }
 } // namespace
 
+int sdrhip::rx_launch_filling(sdrhip_rx *rx, sdrhip_rx::Batch &b) { return b.ragged ? rx_launch_ragged(rx, b) : rx_launch_batch(rx, b); }
+
 extern "C" int sdrhip_rx_set_async(sdrhip_rx *rx, int depth, int blocks)
 {
     if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
     sdrhip::CtxLock lock_(rx->ctx);
     if (depth < 1 || depth > 64 || blocks < 1 || blocks > 1024) return fail(SDRHIP_EINVAL, "rx_set_async: depth 1..64, blocks 1..1024");
-    if (rx->ring.busy()) return fail(SDRHIP_EINVAL, "rx_set_async: batches are in flight: collect them first");
+    if (rx->ring.busy()) return fail(SDRHIP_EINVAL, "rx_set_async: batches are in flight or lent: collect and release them first");
     rx->ring.reset((size_t)depth);
     rx->a_blocks = blocks;
     return SDRHIP_OK;
@@ -204,6 +211,7 @@ extern "C" int sdrhip_rx_submit(sdrhip_rx *rx, const int16_t *iq_in, size_t n_in
 {
     if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
     sdrhip::CtxLock lock_(rx->ctx);
+    if (rx->egress) return fail(SDRHIP_EINVAL, "rx_submit: uniform batches have no departure order (sdrhip_rx_set_egress): use sdrhip_rx_submit_ragged with equal counts");
     if (n_in == 0) return SDRHIP_OK;
     if (!iq_in) return fail(SDRHIP_EINVAL, "rx_submit: NULL input");
     if (rx_dgrams_in_flight(rx)) return fail(SDRHIP_EINVAL, "rx_submit: asynchronous datagram batches are in flight: sdrhip_rx_collect_datagrams them first");
@@ -213,7 +221,7 @@ extern "C" int sdrhip_rx_submit(sdrhip_rx *rx, const int16_t *iq_in, size_t n_in
     const int S = rx->nstreams;
     if (S == 1) in_stride = n_in;
     sdrhip_rx::Batch &b = rx->ring.tail_batch();
-    if (b.state == 2) return fail(SDRHIP_EBUSY, "rx_submit: every batch of the ring is in flight: sdrhip_rx_collect first");
+    if (b.state >= 2) return fail(SDRHIP_EBUSY, "rx_submit: every batch of the ring is in flight or lent: sdrhip_rx_collect first");
     if (b.state == 0) {
         b.blocks.clear(); b.strides.clear(); b.n_in = 0; b.tv_sec = tv_sec; b.tv_usec = tv_usec; b.state = 1; b.ragged = false;
         b.in_cap = 0; // no staged rows yet: the first pageable block of this batch (re)claims the arena
@@ -258,7 +266,7 @@ extern "C" int sdrhip_rx_submit(sdrhip_rx *rx, const int16_t *iq_in, size_t n_in
 // the oldest batch of the ring once it has finished; wait = 1 launches a partly filled one as it is (the end of a stream)
 static int rx_oldest(sdrhip_rx *rx, std::unique_lock<std::recursive_mutex> &lock_, int wait, const char *who, sdrhip_rx::Batch **bp)
 {
-    return rx->ring.wait_oldest(lock_, wait, who, [rx](sdrhip_rx::Batch &b) { return b.ragged ? rx_launch_ragged(rx, b) : rx_launch_batch(rx, b); }, bp);
+    return rx->ring.wait_oldest(lock_, wait, who, [rx](sdrhip_rx::Batch &b) { return rx_launch_filling(rx, b); }, bp);
 }
 
 extern "C" int sdrhip_rx_collect(sdrhip_rx *rx, uint8_t *frames_out, size_t frame_stride_bytes, size_t max_frames, size_t *n_frames, int wait)
@@ -307,7 +315,7 @@ extern "C" int sdrhip_rx_submit_ragged(sdrhip_rx *rx, const int16_t *iq_in, cons
     if (rx_dgrams_in_flight(rx)) return fail(SDRHIP_EINVAL, "rx_submit_ragged: asynchronous datagram batches are in flight: sdrhip_rx_collect_datagrams them first");
     if (rx_has_batches(rx, false)) return fail(SDRHIP_EINVAL, "rx_submit_ragged: uniform batches are being filled or in flight: collect them first");
     sdrhip_rx::Batch &b = rx->ring.tail_batch();
-    if (b.state == 2) return fail(SDRHIP_EBUSY, "rx_submit_ragged: every batch of the ring is in flight: sdrhip_rx_collect_ragged first");
+    if (b.state >= 2) return fail(SDRHIP_EBUSY, "rx_submit_ragged: every batch of the ring is in flight or lent: collect or release one first");
     for (int s = 0; s < S; ++s) // (K0p's table holds 32-bit row positions)
         if ((b.state == 1 ? b.r_tot[(size_t)s] : 0) + n_in[s] > (size_t)0xffffffffu - UNPACK_WG_SAMPLES)
             return fail(SDRHIP_EINVAL, "rx_submit_ragged: a stream's batch would exceed 2^32 - 4096 samples");
@@ -375,6 +383,7 @@ extern "C" int sdrhip_rx_collect_ragged(sdrhip_rx *rx, uint8_t *frames_out, size
     int rc = rx_oldest(rx, lock_, wait, "rx_collect_ragged", &bp);
     if (rc) return rc;
     sdrhip_rx::Batch &b = *bp;
+    if (b.egress) return fail(SDRHIP_EINVAL, "rx_collect_ragged: the batch was launched in departure order: use sdrhip_rx_collect_egress (the batch stays)");
     size_t most = 0;
     for (int s = 0; s < S; ++s) if (b.r_frames[(size_t)s] > most) most = b.r_frames[(size_t)s];
     if (most > max_frames) { // (the batch stays where it is: call again with room for the largest n_frames[s])

@@ -104,7 +104,7 @@ extern "C" int sdrhip_rx_process_datagrams(sdrhip_rx *rx, const uint8_t *dgrams,
     // ---- everything that can be refused is checked before the collector moves
     if (int e = check_mem(mem)) return e;
     if (rx->pipelined) return fail(SDRHIP_EINVAL, "rx_process_datagrams: not available in pipelined mode");
-    if (rx->ring.busy()) return fail(SDRHIP_EINVAL, "rx_process_datagrams: asynchronous batches are being filled or in flight: collect them first");
+    if (rx_batches_active(rx)) return fail(SDRHIP_EINVAL, "rx_process_datagrams: asynchronous batches are being filled or in flight: collect them first");
     if (max_released > 0x3fffffffu) return fail(SDRHIP_EINVAL, "rx_process_datagrams: max_released too large");
     if (max_released > 0 && !info_out) return fail(SDRHIP_EINVAL, "rx_process_datagrams: NULL info_out");
     HIP_TRY(hipSetDevice(c->device));

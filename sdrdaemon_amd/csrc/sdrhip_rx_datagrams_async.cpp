@@ -22,7 +22,7 @@ static int rx_submit_batch(sdrhip_rx *rx, FecBufBatch &in, const uint32_t *tv_se
     if (rx_has_batches(rx, false) || rx_has_batches(rx, true))
         return fail(SDRHIP_EINVAL, "%s: uniform or ragged batches are being filled or in flight: collect them first", who);
     sdrhip_rx::Batch &b = rx->ring.tail_batch();
-    if (b.state == 2) return fail(SDRHIP_EBUSY, "%s: every batch of the ring is in flight: sdrhip_rx_collect_datagrams first", who);
+    if (b.state >= 2) return fail(SDRHIP_EBUSY, "%s: every batch of the ring is in flight or lent: collect or release one first", who);
     sdrhip_ctx *c = rx->ctx;
     HIP_TRY(hipSetDevice(c->device));
     int rc;
@@ -65,6 +65,8 @@ static int rx_submit_batch(sdrhip_rx *rx, FecBufBatch &in, const uint32_t *tv_se
     if (b_total && (rc = b.out.reserve(b_total))) return rc;
     if ((rc = b.d_seg.reserve(seg_bytes))) return rc;
     if ((rc = rx->ring.ensure_event(b))) return rc;
+    b.egress = rx->egress; // (departure order: KE's table and the tags, like everything else, before the collector moves)
+    if (b.egress && (rc = rx_egress_room(rx, b, sum_done, fb / SDRHIP_UDPSIZE))) return rc;
     if (any && (rc = rx_ragged_room(rx, fed.data(), &b.d_tabs))) return rc;
 
     // ---- upload: exactly the datagrams (staged: one copy; in place: one per run of adjacent rows)
@@ -114,6 +116,10 @@ static int rx_submit_batch(sdrhip_rx *rx, FecBufBatch &in, const uint32_t *tv_se
         g.src = (size_t)s * kmax * DG_REC;
         g.bytes = k * DG_REC; g.dst = dst; g.from_records = 1;
         dst += g.bytes;
+    }
+    if (b.egress) { // departure order: KE in KD's place writes the same buffer (sdrhip_rx_egress.cpp); KD's table stays unused
+        nseg = 0;
+        if (e == hipSuccess) e = rx_egress_launch(rx, b, nf.data(), fb, res.data(), kmax, reinterpret_cast<const uint8_t *>(pub));
     }
     const uint32_t grid = rx_deliver_plan(seg, nseg);
     if (e == hipSuccess && nseg && (!grid || !aligned16(pub))) e = hipErrorInvalidValue;
@@ -180,6 +186,7 @@ extern "C" int sdrhip_rx_collect_datagrams(sdrhip_rx *rx, uint8_t *frames_out, s
     int rc = rx->ring.wait_oldest(lock_, wait, "rx_collect_datagrams", [](sdrhip_rx::Batch &) { return SDRHIP_OK; }, &bp);
     if (rc) return rc;
     sdrhip_rx::Batch &b = *bp;
+    if (b.egress) return fail(SDRHIP_EINVAL, "rx_collect_datagrams: the batch was launched in departure order: use sdrhip_rx_collect_egress (the batch stays)");
     size_t most = 0, most_rel = 0, all = 0;
     for (int s = 0; s < S; ++s) {
         most = b.r_frames[(size_t)s] > most ? b.r_frames[(size_t)s] : most;

@@ -1,0 +1,163 @@
+// sdrhip_rx_egress.cpp -- departure-order egress of the Rx pipe's asynchronous batches (sdrhip_rx_set_egress /
+// sdrhip_rx_collect_egress / sdrhip_rx_release_egress).  A hub that sends what the stream-order collects hand it puts a burst per
+// stream on the wire; the reference never does that to a receiver (UDPSinkFEC::transmitUDP sleeps txDelay between two datagrams of
+// a stream, UDPSinkFEC.cpp:259-282).  With the order on, a batch's delivery is ONE array: datagram j of every stream before
+// datagram j + 1 of any (rx_egress_order.h), with a stream tag per datagram -- the mirror of the tagged submit.  KE
+// (rx_egress_kernels.hip) writes the batch's one download buffer in that order in KD's / the frame gather's place; the collect
+// lends the ring slot's pinned download buffer and its tags instead of copying frames out of it.  The two launch paths
+// (rx_submit_batch, rx_launch_ragged) call rx_egress_room ahead of everything that consumes input and rx_egress_launch where their
+// stream-order delivery would go; nothing else of them differs.
+#include "sdrhip_pipes.h"
+
+using namespace sdrhip;
+
+namespace {
+// KE's table: the record places (16 bytes each) in front, so that they are 16-byte aligned whatever the number of runs behind them
+size_t egress_table_bytes(size_t frames, size_t S) { return S * sizeof(RxEgressRecPlace) + frames * sizeof(RxEgressRun); }
+
+// the batch the caller holds (state 3) is free again
+void release_lent(sdrhip_rx *rx)
+{
+    for (auto &b : rx->ring.v)
+        if (b.state == 3) b.state = 0;
+}
+} // namespace
+
+int sdrhip::rx_egress_room(sdrhip_rx *rx, sdrhip_rx::Batch &b, size_t frames, size_t blocks_per_frame)
+{
+    const size_t S = (size_t)rx->nstreams, bytes = egress_table_bytes(frames, S) + 16;
+    int rc;
+    if ((rc = b.e_tab.reserve(bytes))) return rc; // (waits for the table upload of this slot's last use)
+    if ((rc = reserve_settled(rx->ctx, rx->e_tab, bytes))) return rc;
+    try {
+        b.e_tags.resize(frames * blocks_per_frame);
+    } catch (const std::bad_alloc &) {
+        return fail(SDRHIP_ENOMEM, "rx egress: %zu tags", frames * blocks_per_frame);
+    }
+    return SDRHIP_OK;
+}
+
+hipError_t sdrhip::rx_egress_launch(sdrhip_rx *rx, sdrhip_rx::Batch &b, const size_t *n_frames, size_t frame_bytes, const int *released,
+                                    size_t kmax, const uint8_t *records)
+{
+    sdrhip_ctx *c = rx->ctx;
+    const size_t S = (size_t)rx->nstreams, B = frame_bytes / SDRHIP_UDPSIZE;
+    RxEgressOrder &o = rx->e_order;
+    std::vector<uint64_t> src0;
+    try {
+        src0.assign(S, 0);
+        if (!o.plan(n_frames, S, B)) return hipErrorInvalidValue; // (a batch KE's index types cannot hold: refused, never truncated)
+    } catch (const std::bad_alloc &) {
+        return hipErrorOutOfMemory;
+    }
+    // (cannot differ: rx_egress_room was given the pipe's own count of these frames)
+    if (egress_table_bytes(o.frames(), S) > b.e_tab.cap || o.dgrams() > b.e_tags.size()) return hipErrorInvalidValue;
+    for (size_t s = 0; s < S; ++s)
+        if (n_frames[s]) src0[s] = rx->view.offset(s, frame_bytes);
+    RxEgressRecPlace *place = b.e_tab.as<RxEgressRecPlace>();
+    RxEgressRun *runs = reinterpret_cast<RxEgressRun *>(place + S);
+    if (!o.runs(src0.data(), runs)) return hipErrorInvalidValue;
+    b.e_tags.resize((size_t)o.dgrams()); // (never grows)
+    o.tags(b.e_tags.data());
+    uint32_t pre = 0;
+    for (size_t s = 0; s < S; ++s) {
+        place[s].pre = pre;
+        place[s].cnt = released && kmax ? (uint32_t)released[s * 4] : 0;
+        place[s].pad[0] = place[s].pad[1] = 0;
+        pre += place[s].cnt;
+    }
+    if (!o.frames() && !pre) return hipSuccess;
+    if (kmax > 0xffffffffu / S) return hipErrorInvalidValue;
+    const size_t bytes = egress_table_bytes(o.frames(), S);
+    hipError_t e = hipMemcpyAsync(rx->e_tab.p, b.e_tab.p, bytes, hipMemcpyHostToDevice, c->stream); // (not counted: a table)
+    if (e != hipSuccess) return e;
+    b.e_tab.mark(c->stream);
+    RxEgressRecords rec;
+    rec.place = rx->e_tab.as<RxEgressRecPlace>();
+    const RxEgressRun *runs_dev = reinterpret_cast<const RxEgressRun *>(rec.place + S);
+    rec.records = records;
+    rec.dst = o.dgrams() * SDRHIP_UDPSIZE;
+    rec.kmax = (uint32_t)kmax;
+    rec.nslots = pre ? (uint32_t)(S * kmax) : 0;
+    KTimer kt(c, SDRHIP_K_CONVERT);
+    return launch_rx_egress(runs_dev, o.frames(), o.wg_per_frame(), (uint32_t)B, rx->work.as<uint8_t>(), rx->a_frames.as<uint8_t>(), rec, c->stream);
+}
+
+extern "C" int sdrhip_rx_set_egress(sdrhip_rx *rx, int order)
+{
+    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
+    sdrhip::CtxLock lock_(rx->ctx);
+    if (order != SDRHIP_EGRESS_OFF && order != SDRHIP_EGRESS_ROUND_ROBIN) return fail(SDRHIP_EINVAL, "rx_set_egress: unknown order %d", order);
+    if ((size_t)rx->nstreams > RX_EGRESS_MAX_STREAMS) return fail(SDRHIP_EINVAL, "rx_set_egress: a tag names at most 65535 streams");
+    if (rx->ring.any([](const sdrhip_rx::Batch &b) { return b.state == 1; }))
+        return fail(SDRHIP_EINVAL, "rx_set_egress: a batch is being filled: collect it first");
+    rx->egress = order;
+    return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_rx_collect_egress(sdrhip_rx *rx, sdrhip_rx_egress *out, size_t *n_frames, size_t max_released,
+                                        sdrhip_fecbuf_frame *info_out, size_t *n_released, int wait)
+{
+    if (!rx || !out || !n_frames) return fail(SDRHIP_EINVAL, "rx_collect_egress: NULL argument");
+    // (the wait happens outside the context lock: the submitting thread keeps feeding the ring)
+    std::unique_lock<std::recursive_mutex> lock_(rx->ctx->mtx);
+    const int S = rx->nstreams;
+    for (int s = 0; s < S; ++s) {
+        n_frames[s] = 0;
+        if (n_released) n_released[s] = 0;
+    }
+    if (rx_has_batches(rx, false)) return fail(SDRHIP_EINVAL, "rx_collect_egress: uniform batches are being filled or in flight: use sdrhip_rx_collect");
+    HIP_TRY(hipSetDevice(rx->ctx->device));
+    sdrhip_rx::Batch *bp = nullptr;
+    int rc = rx->ring.wait_oldest(lock_, wait, "rx_collect_egress", [rx](sdrhip_rx::Batch &f) { return rx_launch_filling(rx, f); }, &bp);
+    if (rc) return rc;
+    sdrhip_rx::Batch &b = *bp;
+    if (!b.egress)
+        return fail(SDRHIP_EINVAL, "rx_collect_egress: the batch was launched in stream order: use sdrhip_rx_collect_%s (the batch stays)",
+                    b.dg ? "datagrams" : "ragged");
+    size_t all = 0, most_rel = 0;
+    for (int s = 0; s < S; ++s) {
+        all += b.r_frames[(size_t)s];
+        if (b.dg && b.d_rel[(size_t)s] > most_rel) most_rel = b.d_rel[(size_t)s];
+    }
+    const char *why = nullptr;
+    if (b.dg && !n_released) why = "NULL n_released for a datagram batch";
+    else if (most_rel > max_released) why = "a stream of the batch released more frames than max_released";
+    else if (most_rel && !info_out) why = "NULL info_out";
+    if (why) { // (the batch stays where it is: the counts say how much room it needs)
+        for (int s = 0; s < S; ++s) {
+            n_frames[s] = b.r_frames[(size_t)s];
+            if (n_released) n_released[s] = b.dg ? b.d_rel[(size_t)s] : 0;
+        }
+        return fail(SDRHIP_EINVAL, "rx_collect_egress: %s (most records %zu; the batch stays)", why, most_rel);
+    }
+    const size_t B = b.frame_bytes / SDRHIP_UDPSIZE, n = all * B;
+    // the records alone are copied (16 bytes per released frame); the datagrams and the tags are lent where they lie
+    const uint8_t *rec = b.out.as<uint8_t>() + n * SDRHIP_UDPSIZE;
+    for (int s = 0; s < S; ++s) {
+        const size_t k = b.dg ? b.d_rel[(size_t)s] : 0;
+        if (k) memcpy(info_out + (size_t)s * max_released, rec, k * DG_REC);
+        rec += k * DG_REC;
+        n_frames[s] = b.r_frames[(size_t)s];
+        if (n_released) n_released[s] = k;
+    }
+    release_lent(rx); // (a successful collect releases what the previous one lent)
+    out->dgrams = n ? b.out.as<uint8_t>() : nullptr;
+    out->stream_of = n ? b.e_tags.data() : nullptr;
+    out->n_dgrams = n;
+    out->blocks_per_frame = B;
+    const bool was_dg = b.dg;
+    b.state = 3;
+    b.dg = false;
+    ++rx->ring.head;
+    if (was_dg) fecbuf_set_async_busy(rx->fb, rx_dgrams_in_flight(rx));
+    return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_rx_release_egress(sdrhip_rx *rx)
+{
+    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
+    sdrhip::CtxLock lock_(rx->ctx);
+    release_lent(rx);
+    return SDRHIP_OK;
+}

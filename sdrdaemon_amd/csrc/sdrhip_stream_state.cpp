@@ -192,7 +192,7 @@ int import_run(sdrhip_ctx *c, StreamCopyArgs &a, PinnedBuf &pin, DevBuf &dev, si
 int rx_movable(const sdrhip_rx *rx, int stream, const char *who)
 {
     if (stream < 0 || stream >= rx->nstreams) return fail(SDRHIP_EINVAL, "%s: stream %d of %d", who, stream, rx->nstreams);
-    if (rx->ring.busy()) return fail(SDRHIP_EINVAL, "%s: asynchronous batches are being filled or in flight: collect them first", who);
+    if (rx_batches_active(rx)) return fail(SDRHIP_EINVAL, "%s: asynchronous batches are being filled or in flight: collect them first", who);
     if (rx->late.have) return fail(SDRHIP_EINVAL, "%s: frames of the previous call wait for delivery (pipelined mode): sdrhip_rx_flush them first", who);
     return SDRHIP_OK;
 }

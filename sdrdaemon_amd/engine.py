@@ -1068,6 +1068,64 @@ class RxPipe:
             res.append((out[s, :int(nf[s])], recs))
         return res
 
+    # ---- departure-order egress (sdrhip_rx_set_egress / sdrhip_rx_collect_egress / sdrhip_rx_release_egress)
+    def set_egress(self, order="round_robin"):
+        """the order later ragged and datagram batches are delivered in: "round_robin" = one array per batch, datagram j of every
+        stream before datagram j + 1 of any (collect_egress); None or "off" = frames per stream (collect_ragged /
+        collect_datagrams), the default.  A batch keeps the order it was launched with."""
+        orders = {None: _lib.EGRESS_OFF, "off": _lib.EGRESS_OFF, "round_robin": _lib.EGRESS_ROUND_ROBIN}
+        check(self.ctx.lib.sdrhip_rx_set_egress(self.h, orders[order] if order in orders else int(order)))
+
+    def collect_egress(self, wait=True, max_released=None, copy=True):
+        """the oldest batch launched with an egress order -> (dgrams (n, 512) uint8 in departure order, stream_of (n,) uint16,
+        n_frames numpy (S,), records), or None when no batch was collected (nothing submitted, or wait=False and the oldest one is
+        in flight).  records: per stream the records of the frames its collector released, as collect_datagrams returns them;
+        None for a ragged batch.  blocks per frame of the batch: last_blocks_per_frame.  copy=False returns views of the memory
+        the library lends -- the batch's pinned download buffer and its tags -- valid until release_egress, the next
+        collect_egress or the pipe's destruction; the batch keeps its ring slot meanwhile.  copy=True copies and releases."""
+        S = self.nstreams
+        is_dg = bool(self._dg_pending)
+        eg = _lib.RxEgress()
+        nf, nr = (C.c_size_t * S)(), (C.c_size_t * S)()
+        F, info = (max_released or 0), None
+        for _ in range(2):  # (max_released=None: one call that learns the counts, one that collects)
+            info = (FECBufferFrame * (S * F))() if F else None
+            rc = self.ctx.lib.sdrhip_rx_collect_egress(self.h, C.byref(eg), nf, F, info, nr, 1 if wait else 0)
+            if rc == -1 and max_released is None and S and max(nr[:]) > F:
+                F = max(nr[:])
+                continue
+            break
+        self.last_n_released, self.last_n_frames = [int(x) for x in nr], [int(x) for x in nf]
+        if rc == -6:
+            return None
+        check(rc)
+        if is_dg:
+            self._dg_pending.pop(0)
+        elif getattr(self, "_rg_batches", []):
+            self._rg_batches.pop(0)
+        elif hasattr(self, "_rg_fill") and self._rg_fill[1]:  # (wait = True sent the partly filled batch out as it was)
+            self._rg_fill = [np.zeros(S, np.int64), 0]
+        n = int(eg.n_dgrams)
+        self.last_blocks_per_frame = int(eg.blocks_per_frame)
+        if n:
+            dg = np.ctypeslib.as_array((C.c_uint8 * (n * UDPSIZE)).from_address(eg.dgrams)).reshape(n, UDPSIZE)
+            tags = np.ctypeslib.as_array((C.c_uint16 * n).from_address(eg.stream_of))
+        else:
+            dg, tags = np.zeros((0, UDPSIZE), np.uint8), np.zeros(0, np.uint16)
+        if copy:
+            dg, tags = dg.copy(), tags.copy()
+            self.release_egress()
+        records = None
+        if is_dg:
+            records = [[dict(frame_index=info[s * F + j].frame_index, block_count=info[s * F + j].block_count,
+                             recovery_count=info[s * F + j].recovery_count, flags=info[s * F + j].flags) for j in range(int(nr[s]))]
+                       for s in range(S)]
+        return dg, tags, np.array(nf[:], dtype=np.int64), records
+
+    def release_egress(self):
+        """sdrhip_rx_release_egress: the batch collect_egress(copy=False) lent is free again (its views are dead)"""
+        check(self.ctx.lib.sdrhip_rx_release_egress(self.h))
+
     def collector_stats(self, stream):
         """the statistics of one stream's collector (sdrhip_rx_collector + sdrhip_fecbuf_stats): the dict of FECBufferBank.stats"""
         return _fecbuf_stats(self.ctx, self._collector(), stream)
