@@ -49,20 +49,43 @@ def device_count():
     return _lib.lib().sdrhip_device_count()
 
 
-class Context:
+class _Handle:
+    """A library handle its object owns: self.h, given back once by close() -- the class's `_destroy` entry -- at the latest
+    when the object dies."""
+
+    _destroy = None
+
+    def __init__(self, lib):
+        self.lib, self.h = lib, C.c_void_p()
+
+    def close(self):
+        if getattr(self, "h", None):  # (an object whose constructor raised early has none)
+            getattr(self.lib, self._destroy)(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Context(_Handle):
     """One per GPU (sdrhip_ctx).  stream: a torch.cuda.Stream, a raw hipStream_t int, or None
     (torch's current stream when torch sees the device, else the null stream)."""
 
+    _destroy = "sdrhip_ctx_destroy"
+
     def __init__(self, device=0, stream=None):
-        self.lib = _lib.lib()
+        _Handle.__init__(self, _lib.lib())
         self.device = device
         if stream is None and torch is not None and torch.cuda.is_available():
             with torch.cuda.device(device):
                 stream = torch.cuda.current_stream().cuda_stream
         elif stream is not None and hasattr(stream, "cuda_stream"):
             stream = stream.cuda_stream
-        self.h = C.c_void_p()
         self.options = {}
+        self._host_allocs = {}  # address of every host_alloc array -> the pointer to free
         check(self.lib.sdrhip_ctx_create(device, C.c_void_p(stream or 0), C.byref(self.h)))
 
     def synchronize(self):
@@ -94,12 +117,11 @@ class Context:
             raise MemoryError("sdrhip_host_alloc(%d) failed" % n)
         buf = (C.c_char * n).from_address(p)
         a = np.frombuffer(buf, dtype=dtype).reshape(shape)
-        self._host_allocs = getattr(self, "_host_allocs", {})
         self._host_allocs[a.ctypes.data] = p
         return a
 
     def host_free(self, a):
-        p = getattr(self, "_host_allocs", {}).pop(a.ctypes.data, None)
+        p = self._host_allocs.pop(a.ctypes.data, None)
         if p:
             self.lib.sdrhip_host_free(self.h, C.c_void_p(p))
 
@@ -128,17 +150,6 @@ class Context:
         ms, n = C.c_double(0), C.c_uint(0)
         check(self.lib.sdrhip_ctx_kernel_timing_read(self.h, kernel_class, C.byref(ms), C.byref(n)))
         return ms.value, n.value
-
-    def close(self):
-        if self.h:
-            self.lib.sdrhip_ctx_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _bank_view(iq, nstreams, dtype=np.int16):
@@ -183,12 +194,141 @@ def _stride_samples(x):
     return (x.stride(0) // 2) if _is_torch(x) else (x.strides[0] // (2 * x.itemsize))
 
 
-def _alloc_like(x, shape, dtype_np=np.int16):
-    if _is_torch(x):
-        tdt = {np.int16: torch.int16, np.uint8: torch.uint8}[dtype_np]
-        # rows padded to 16 bytes so that every stream starts aligned
-        return torch.empty(shape, dtype=tdt, device=x.device)
-    return np.empty(shape, dtype=dtype_np)
+def _padded_rows(S, n, m, dtype, device, src=None, zero=False):
+    """torch rows (S, n, 2) of a buffer whose rows are a multiple of m samples long (and not empty): the library's stride rule
+    for device banks, 16-byte aligned rows.  src: a tensor (S, n, 2) copied into them."""
+    buf = (torch.zeros if zero else torch.empty)((S, max((n + m - 1) & ~(m - 1), m), 2), dtype=dtype, device=device)
+    if src is not None:
+        buf[:, :n].copy_(src)
+    return buf[:, :n]
+
+
+def _rows_in_place(a, S, dtype):
+    """whether the rows of a host array are usable where they lie, with their stride: (S, n, 2) of dtype, samples contiguous, the
+    rows a whole number of samples apart (rows of a bigger array, e.g. a pinned buffer)"""
+    it = np.dtype(dtype).itemsize
+    return (a.ndim == 3 and a.dtype == dtype and a.shape[0] == S and a.shape[2] == 2 and a.strides[2] == it
+            and a.strides[1] == 2 * it and a.strides[0] % (2 * it) == 0 and a.strides[0] > 0)
+
+
+def _stamps(v, S):
+    """a time stamp field -- a scalar, None (= 0) or one value per stream -- as the (C.c_uint32 * S) the per-stream entries take"""
+    v = np.broadcast_to(np.asarray(0 if v is None else v, dtype=np.uint32), (S,))
+    return (C.c_uint32 * S)(*[int(x) for x in v])
+
+
+def _frame_buffer(S, cap, nb_fec, device=None, out=None):
+    """-> (the frame output buffer (S, cap, 128 + nb_fec, 512) uint8 -- torch on `device`, numpy without one, or the caller's
+    `out` if it has the room --, its stride in bytes per stream)"""
+    rows = NB_ORIGINAL + nb_fec
+    if out is None:
+        shape = (S, cap, rows, UDPSIZE)
+        out = torch.empty(shape, dtype=torch.uint8, device=device) if device is not None else np.empty(shape, np.uint8)
+    if out.shape[1] < cap or out.shape[0] != S:
+        raise ValueError("out must hold (S, >= %d, %d, 512) bytes" % (cap, rows))
+    return out, out.shape[1] * rows * UDPSIZE
+
+
+def _records(info, F, n):
+    """the sdrhip_fecbuf_frame records a call filled in, F slots per stream (info may be None when every n[s] is 0): per stream
+    the list of dicts of its first n[s]"""
+    return [[dict(frame_index=r.frame_index, block_count=r.block_count, recovery_count=r.recovery_count, flags=r.flags)
+             for r in (info[s * F:s * F + int(n[s])] if n[s] else ())] for s in range(len(n))]
+
+
+def _packed_datagrams(dgrams_per_stream, S):
+    """what the submit_datagrams methods take -- one (n_s, 512) uint8 host array per stream, or (array, counts) of them back to
+    back -- as (packed contiguous uint8 array, used where it lies when it is one already; counts)"""
+    if isinstance(dgrams_per_stream, tuple):
+        buf, counts = dgrams_per_stream
+        counts = [int(x) for x in counts]
+        if len(counts) != S:
+            raise ValueError("one count per stream")
+    else:
+        if len(dgrams_per_stream) != S:
+            raise ValueError("one datagram array per stream")
+        if any(_is_torch(d) for d in dgrams_per_stream):
+            raise TypeError("submit_datagrams takes host memory")
+        counts = [int(np.asarray(d).shape[0]) for d in dgrams_per_stream]
+        nz = [np.asarray(d, np.uint8).reshape(-1, UDPSIZE) for d in dgrams_per_stream if len(d)]
+        buf = np.concatenate(nz) if nz else np.zeros((0, UDPSIZE), np.uint8)
+    if _is_torch(buf):
+        raise TypeError("submit_datagrams takes host memory")
+    buf = np.ascontiguousarray(buf, np.uint8)
+    if buf.size != sum(counts) * UDPSIZE:
+        raise ValueError("the datagrams do not match the counts")
+    return buf, counts
+
+
+class _BatchLog:
+    """What a pipe knows about the batches its library handle holds (the asynchronous entries): the batches launched and not
+    collected yet, oldest first, and the one still being filled.  Pure bookkeeping: collects size and shape their buffers from
+    the head record, since a batch in flight keeps the configuration it was launched with.  A record has
+      kind  "uniform" | "ragged" | "datagram" (Rx), "frames" | "datagram" (Tx)
+      size  the hint the collects size with: samples per stream, per-stream counts (numpy), frames; None for datagrams
+      cfg   the setting the batch keeps: nb_fec (Rx), log2interp (Tx), as it stood when the batch was launched
+    A fresh log is the library's default ring: 4 batches of one block."""
+
+    class Batch:
+        def __init__(self, kind, size, cfg=None):
+            self.kind, self.size, self.cfg, self.nblocks = kind, size, cfg, 1
+
+        @property
+        def most(self):
+            """the largest count of a stream (0 for a size of None)"""
+            if isinstance(self.size, np.ndarray):
+                return int(self.size.max()) if self.size.size else 0
+            return self.size or 0
+
+    def __init__(self, blocks=1):
+        self.reset(blocks)
+
+    def reset(self, blocks=1):
+        """set_async: an empty ring whose batches take `blocks` submitted blocks each"""
+        self.blocks, self.batches, self.filling = blocks, [], None
+        self.last = 0  # size of the uniform batch collected last: a pipelined pipe delivers the PREVIOUS batch's frames
+
+    def block(self, kind, size, cfg):
+        """after a successful submit of one block of `size`: it joins the batch being filled, which the library launches -- under
+        the cfg of this submit -- once it has `blocks` blocks"""
+        if self.filling is None:
+            self.filling = self.Batch(kind, size)
+        else:
+            self.filling.size = self.filling.size + size
+            self.filling.nblocks += 1
+        if self.filling.nblocks >= self.blocks:
+            self._launch(cfg)
+
+    def batch(self, kind, size, cfg):
+        """after a successful submit that is a batch of its own, launched at once (datagram batches, Tx frames)"""
+        self.batches.append(self.Batch(kind, size, cfg))
+
+    def _launch(self, cfg):
+        b, self.filling = self.filling, None
+        b.cfg = cfg
+        self.batches.append(b)
+
+    def head(self, cfg, wait_kind=None):
+        """-> (the record of the oldest launched batch or None, the cfg that batch keeps), for a collect; cfg: the pipe's setting
+        at this moment, assumed for a batch the log was not told of.  wait_kind: the kind a collect with wait = True takes: with
+        nothing in front of it the library sends the partly filled batch of that kind out as it is, under the cfg of this moment"""
+        if not self.batches and self.filling is not None and self.filling.kind == wait_kind:
+            self._launch(cfg)
+        rec = self.batches[0] if self.batches else None
+        return rec, (rec.cfg if rec is not None else cfg)
+
+    def pop(self):
+        """the oldest batch was collected (rc 0: not the -1 of a call that learns the counts, not SDRHIP_EBUSY).  A log that was
+        not told of a submit (a caller of the C entry itself) has nothing to forget."""
+        if self.batches:
+            b = self.batches.pop(0)
+            if b.kind == "uniform":
+                self.last = b.size
+
+    def sample_room(self):
+        """samples per stream that bound what the next collect can deliver: the oldest batch, the one being filled, or -- a
+        pipelined pipe -- the uniform batch collected last"""
+        return max([self.last] + [b.most for b in (self.filling, self.batches[0] if self.batches else None) if b is not None])
 
 
 def _counts(counts, S, n):
@@ -231,12 +371,14 @@ def _plan_dict(fn, h):
             "head": p.head, "tail_start": p.tail_start}
 
 
-class Decimators:
+class Decimators(_Handle):
     """Bank of reference `Decimators` objects (Decimators.h:32-71)."""
 
+    _destroy = "sdrhip_decimators_destroy"
+
     def __init__(self, ctx, nstreams=1, hb_variant=HB_EO1):
+        _Handle.__init__(self, ctx.lib)
         self.ctx, self.nstreams = ctx, nstreams
-        self.h = C.c_void_p()
         check(ctx.lib.sdrhip_decimators_create(ctx.h, nstreams, hb_variant, C.byref(self.h)))
 
     def reset(self, streams=None):
@@ -254,12 +396,7 @@ class Decimators:
         S, n = x.shape[0], x.shape[1]
         n_res = (n >> log2decim) if 0 <= log2decim <= 6 else 0  # out-of-range factors are rejected by the library
         if out is None:
-            if is_t:  # per-stream rows padded to a multiple of 4 samples (16-byte aligned rows)
-                pad = (n_res + 3) & ~3
-                buf = torch.empty((S, max(pad, 4), 2), dtype=torch.int16, device=x.device)
-                out = buf[:, :n_res]
-            else:
-                out = np.empty((S, n_res, 2), dtype=np.int16)
+            out = _padded_rows(S, n_res, 4, torch.int16, x.device) if is_t else np.empty((S, n_res, 2), dtype=np.int16)
         if is_t and S > 1 and (x.stride(0) // 2) % 4:
             raise ValueError("device bank input: per-stream stride must be a multiple of 4 samples")
         ss = C.c_uint(sample_size)
@@ -278,11 +415,7 @@ class Decimators:
         mx = int(cnt.max()) if S else 0
         n_res = (mx >> log2decim) if 0 <= log2decim <= 6 else 0
         if out is None:
-            if is_t:
-                buf = torch.zeros((S, max((n_res + 3) & ~3, 4), 2), dtype=torch.int16, device=x.device)
-                out = buf[:, :n_res]
-            else:
-                out = np.zeros((S, n_res, 2), dtype=np.int16)
+            out = _padded_rows(S, n_res, 4, torch.int16, x.device, zero=True) if is_t else np.zeros((S, n_res, 2), dtype=np.int16)
         if is_t and S > 1 and (x.stride(0) // 2) % 4:
             raise ValueError("device bank input: per-stream stride must be a multiple of 4 samples")
         ss = C.c_uint(sample_size)
@@ -295,17 +428,6 @@ class Decimators:
     def last_plan(self):
         """what the last cascade launch was (sdrhip_decimators_last_plan): dict with path ('valu' / 'mfma' / None), span, wps, ..."""
         return _plan_dict(self.ctx.lib.sdrhip_decimators_last_plan, self.h)
-
-    def close(self):
-        if self.h:
-            self.ctx.lib.sdrhip_decimators_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Downsampler:
@@ -352,14 +474,16 @@ class Downsampler:
         return self.m_decimators.decimate(0, self.m_fcPos, sample_size, samples_inout)
 
 
-class TestSource:
+class TestSource(_Handle):
     """Bank of the reference's TestSource devices (TestSource.h:29-116) generating on the GPU: configure() takes the
     reference's control string / key-value map (TestSource.cpp:59-215), read() returns the next samples of every
     stream as a CUDA tensor (or numpy with host=True).  The sample arithmetic is the library's integer NCO."""
 
+    _destroy = "sdrhip_testsource_destroy"
+
     def __init__(self, ctx, nstreams=1):
+        _Handle.__init__(self, ctx.lib)
         self.ctx, self.nstreams = ctx, nstreams
-        self.h = C.c_void_p()
         self.m_error = ""
         check(ctx.lib.sdrhip_testsource_create(ctx.h, nstreams, C.byref(self.h)))
 
@@ -398,24 +522,15 @@ class TestSource:
         y = out[:, :n]
         return y[0] if S == 1 else y
 
-    def close(self):
-        if self.h:
-            self.ctx.lib.sdrhip_testsource_destroy(self.h)
-            self.h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Interpolators:
+class Interpolators(_Handle):
     """Bank of reference `Interpolators` objects (Interpolators.h:35-61)."""
 
+    _destroy = "sdrhip_interpolators_destroy"
+
     def __init__(self, ctx, nstreams=1):
+        _Handle.__init__(self, ctx.lib)
         self.ctx, self.nstreams = ctx, nstreams
-        self.h = C.c_void_p()
         check(ctx.lib.sdrhip_interpolators_create(ctx.h, nstreams, C.byref(self.h)))
 
     def reset(self, streams=None):
@@ -431,27 +546,12 @@ class Interpolators:
         S, n = x.shape[0], x.shape[1]
         n_res = (n << log2interp) if 0 <= log2interp <= 6 else 0
         if out is None:
-            if is_t:
-                pad = (n_res + 3) & ~3
-                out = torch.empty((S, max(pad, 4), 2), dtype=torch.int16, device=x.device)[:, :n_res]
-            else:
-                out = np.empty((S, n_res, 2), dtype=np.int16)
+            out = _padded_rows(S, n_res, 4, torch.int16, x.device) if is_t else np.empty((S, n_res, 2), dtype=np.int16)
         n_out = C.c_size_t(0)
         check(self.ctx.lib.sdrhip_interpolate(self.h, log2interp, _ptr(x), n, _stride_samples(x), _ptr(out),
                                               _stride_samples(out) if S > 1 else n_res, C.byref(n_out),
                                               MEM_DEVICE if is_t else MEM_HOST))
         return out[0] if squeeze else out
-
-    def close(self):
-        if self.h:
-            self.ctx.lib.sdrhip_interpolators_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Upsampler:
@@ -563,18 +663,20 @@ class _DeviceView:
         return torch.as_tensor(self, device=self.device)
 
 
-class RxPipe:
+class RxPipe(_Handle):
     """Downsampler -> UDPSinkFEC framing -> CM256 encode for a bank of streams (sdrhip_rx)."""
+
+    _destroy = "sdrhip_rx_destroy"
 
     def __init__(self, ctx, nstreams=1, log2decim=4, fcpos=FC_CEN, hb_variant=HB_EO1, sample_bits=16, nb_fec=32,
                  center_frequency_khz=435000, sample_rate=625000, pipelined=False, input_format="s16"):
         """pipelined: a process() call returns the frames the PREVIOUS call completed (their recovery blocks are computed inside
         this call's decimator launch, sdrhip_rx_set_pipelined); flush() / flush_view() return the last call's at the end.
         input_format: "s16" (int16 IQ), "u8" (RTL-SDR uint8 offset binary) or "s8" (HackRF int8), see set_input_format."""
+        _Handle.__init__(self, ctx.lib)
         self.ctx, self.nstreams, self.nb_fec = ctx, nstreams, nb_fec
-        self._dg_pending = []  # nb_fec of every datagram batch in flight, oldest first (collect_datagrams sizes its frames with it)
+        self._log = _BatchLog()  # the asynchronous batches in flight, each with the nb_fec it keeps (the collects size and shape with it)
         self.cfg = RxConfig(log2decim, fcpos, hb_variant, sample_bits, nb_fec, center_frequency_khz, sample_rate)
-        self.h = C.c_void_p()
         self.m_error = ""
         self.m_device_rate = sample_rate << log2decim  # DeviceSource::get_sample_rate(): the sink gets it >> decim
         check(ctx.lib.sdrhip_rx_create(ctx.h, nstreams, C.byref(self.cfg), C.byref(self.h)))
@@ -597,10 +699,7 @@ class RxPipe:
         """the (S, n, 2) view of a process() input; 8-bit device rows padded to a multiple of 8 samples (the library's stride rule)"""
         x, is_t, squeeze = _bank_view(iq, self.nstreams, self._in_dtype)
         if is_t and self._in_dtype != np.int16 and x.shape[0] > 1 and (x.stride(0) // 2) % 8:
-            n = x.shape[1]
-            buf = torch.empty((x.shape[0], (n + 7) & ~7, 2), dtype=x.dtype, device=x.device)
-            buf[:, :n].copy_(x)
-            x = buf[:, :n]
+            x = _padded_rows(x.shape[0], x.shape[1], 8, x.dtype, x.device, src=x)
         return x, is_t, squeeze
 
     def error(self):
@@ -621,11 +720,9 @@ class RxPipe:
 
     def flush(self):
         """pipelined mode: -> the frames the last process() call completed, as a host array (S, n, 128 + nb_fec, 512)"""
-        cap = max(self.max_frames(0), 1)
-        fb = (NB_ORIGINAL + self.nb_fec) * UDPSIZE
-        out = np.empty((self.nstreams, cap, NB_ORIGINAL + self.nb_fec, UDPSIZE), np.uint8)
+        out, stride_bytes = _frame_buffer(self.nstreams, max(self.max_frames(0), 1), self.nb_fec)
         nf = C.c_size_t(0)
-        check(self.ctx.lib.sdrhip_rx_flush(self.h, _ptr(out), cap * fb, C.byref(nf), MEM_HOST))
+        check(self.ctx.lib.sdrhip_rx_flush(self.h, _ptr(out), stride_bytes, C.byref(nf), MEM_HOST))
         return out[:, :nf.value]
 
     def last_plan(self):
@@ -714,13 +811,7 @@ class RxPipe:
     def set_async(self, depth=4, blocks=1):
         """ring of `depth` batches, `blocks` submitted blocks per upload + launch + download"""
         check(self.ctx.lib.sdrhip_rx_set_async(self.h, depth, blocks))
-        # samples per stream of the batches not collected yet (oldest first), of the batch being filled and of the batch collected
-        # last (a pipelined pipe delivers the PREVIOUS batch's frames): collect() sizes its buffer from them, not from a lifetime total
-        self._async_blocks = blocks
-        self._async_batches = []
-        self._async_fill = [0, 0]
-        self._async_last = 0
-        self._rg_batches, self._rg_fill = [], [np.zeros(self.nstreams, np.int64), 0]  # (the same for ragged batches, per stream)
+        self._log.reset(blocks)
 
     def submit(self, iq, tv_sec=0, tv_usec=0):
         """one block of host samples per stream (numpy; memory from Context.host_alloc is used in place); returns at once.
@@ -728,34 +819,25 @@ class RxPipe:
         if _is_torch(iq):
             raise TypeError("submit takes host memory")
         a = np.asarray(iq)
-        it = np.dtype(self._in_dtype).itemsize
-        if (a.ndim == 3 and a.dtype == self._in_dtype and a.shape[0] == self.nstreams and a.shape[2] == 2 and a.strides[2] == it
-                and a.strides[1] == 2 * it and a.strides[0] % (2 * it) == 0):
-            x = a  # rows of a bigger array (e.g. a pinned buffer): passed in place with their stride
+        if _rows_in_place(a, self.nstreams, self._in_dtype):
+            x = a
         else:
             x, _, _ = _bank_view(iq, self.nstreams, self._in_dtype)
-        if not hasattr(self, "_async_batches"):  # (sdrhip_rx_submit's default ring: 4 batches of one block)
-            self._async_blocks, self._async_batches, self._async_fill, self._async_last = 1, [], [0, 0], 0
         check(self.ctx.lib.sdrhip_rx_submit(self.h, _ptr(x), x.shape[1], _stride_samples(x), tv_sec, tv_usec))
         if x.shape[1]:
-            self._async_fill[0] += x.shape[1]
-            self._async_fill[1] += 1
-            if self._async_fill[1] >= self._async_blocks:  # (the library launched the batch)
-                self._async_batches.append(self._async_fill[0])
-                self._async_fill = [0, 0]
+            self._log.block("uniform", x.shape[1], self.nb_fec)
 
     def collect(self, wait=True, max_frames=None):
         """-> the finished frames of the oldest batch (S, n, 128 + nb_fec, 512; n may be 0), or None when no batch was collected:
         nothing submitted, or (wait = False) the oldest batch is still in flight / being filled"""
-        batches = getattr(self, "_async_batches", [])
-        fill = getattr(self, "_async_fill", [0, 0])
-        biggest = max([getattr(self, "_async_last", 0), fill[0]] + batches[:1])  # the oldest batch, or its predecessor (pipelined)
-        cap = max_frames if max_frames is not None else max(biggest // (SAMPLES_PER_FRAME << self.cfg.log2decim) + 2, 1)
-        fb = (NB_ORIGINAL + self.nb_fec) * UDPSIZE
+        # (the frames have the size in force when the batch was launched, whatever reconfigure() has set since; the buffer is sized
+        # from the batches at hand, not from a lifetime total)
+        _, nb_fec = self._log.head(self.nb_fec, "uniform" if wait else None)
+        cap = max_frames if max_frames is not None else max(self._log.sample_room() // (SAMPLES_PER_FRAME << self.cfg.log2decim) + 2, 1)
         nf = C.c_size_t(0)
         for _ in range(2):  # (a batch bigger than the guess -- pipelined mode delivers the previous batch's frames -- is asked for again)
-            out = np.empty((self.nstreams, cap, NB_ORIGINAL + self.nb_fec, UDPSIZE), np.uint8)
-            rc = self.ctx.lib.sdrhip_rx_collect(self.h, _ptr(out), cap * fb, cap, C.byref(nf), 1 if wait else 0)
+            out, stride_bytes = _frame_buffer(self.nstreams, cap, nb_fec)
+            rc = self.ctx.lib.sdrhip_rx_collect(self.h, _ptr(out), stride_bytes, cap, C.byref(nf), 1 if wait else 0)
             if rc == -1 and nf.value > cap:
                 cap = nf.value
                 continue
@@ -763,11 +845,7 @@ class RxPipe:
         if rc == -6:
             return None
         check(rc)
-        if batches:
-            self._async_last = batches.pop(0)
-        elif fill[1]:  # (wait = True sent the partly filled batch out as it was)
-            self._async_last = fill[0]
-            self._async_fill = [0, 0]
+        self._log.pop()
         return out[:, :nf.value]
 
     # ---- asynchronous ragged entry (sdrhip_rx_submit_ragged / sdrhip_rx_collect_ragged)
@@ -784,8 +862,7 @@ class RxPipe:
         if a.dtype != self._in_dtype:
             raise TypeError("numpy input must be %s" % np.dtype(self._in_dtype).name)
         if a.ndim == 3:  # rows, with their stride (rows of a bigger array are passed in place)
-            if not (a.shape[0] == S and a.shape[2] == 2 and a.strides[2] == it and a.strides[1] == 2 * it and a.strides[0] % (2 * it) == 0
-                    and a.strides[0] > 0):
+            if not _rows_in_place(a, S, self._in_dtype):
                 a = np.ascontiguousarray(a)
                 if a.shape[0] != S or a.shape[2] != 2:
                     raise ValueError("expected shape (%d, n, 2)" % S)
@@ -804,34 +881,22 @@ class RxPipe:
             stride = 0  # SDRHIP_PACKED
         else:
             raise ValueError("expected rows (%d, n, 2) or packed samples" % S)
-        sec = np.broadcast_to(np.asarray(0 if tv_sec is None else tv_sec, dtype=np.uint32), (S,))
-        usec = np.broadcast_to(np.asarray(0 if tv_usec is None else tv_usec, dtype=np.uint32), (S,))
-        if not hasattr(self, "_async_batches"):  # (the library's default ring: 4 batches of one block)
-            self._async_blocks, self._async_batches, self._async_fill, self._async_last = 1, [], [0, 0], 0
-        if not hasattr(self, "_rg_fill"):
-            self._rg_batches, self._rg_fill = [], [np.zeros(S, np.int64), 0]
-        check(self.ctx.lib.sdrhip_rx_submit_ragged(self.h, _ptr(a), (C.c_size_t * S)(*cnt.tolist()), stride,
-                                                   (C.c_uint32 * S)(*[int(v) for v in sec]), (C.c_uint32 * S)(*[int(v) for v in usec])))
-        self._rg_fill[0] = self._rg_fill[0] + cnt
-        self._rg_fill[1] += 1
-        if self._rg_fill[1] >= self._async_blocks:  # (the library launched the batch)
-            self._rg_batches.append(self._rg_fill[0])
-            self._rg_fill = [np.zeros(S, np.int64), 0]
+        check(self.ctx.lib.sdrhip_rx_submit_ragged(self.h, _ptr(a), (C.c_size_t * S)(*cnt.tolist()), stride, _stamps(tv_sec, S),
+                                                   _stamps(tv_usec, S)))
+        self._log.block("ragged", cnt, self.nb_fec)
 
     def collect_ragged(self, wait=True, max_frames=None):
         """-> the frames of the oldest ragged batch: a list of S arrays (n_s, 128 + nb_fec, 512), n_s possibly 0; None when no
         batch was collected (nothing submitted, or with wait = False the oldest batch is still in flight / being filled)"""
         S = self.nstreams
-        batches = getattr(self, "_rg_batches", [])
-        fill = getattr(self, "_rg_fill", [np.zeros(S, np.int64), 0])
-        oldest = batches[0] if batches else fill[0]
-        cap = max_frames if max_frames is not None else int(oldest.max() if S else 0) // (SAMPLES_PER_FRAME << self.cfg.log2decim) + 2
+        rec, nb_fec = self._log.head(self.nb_fec, "ragged" if wait else None)
+        oldest = rec or self._log.filling
+        cap = max_frames if max_frames is not None else (oldest.most if oldest else 0) // (SAMPLES_PER_FRAME << self.cfg.log2decim) + 2
         cap = max(cap, 1)
-        fb = (NB_ORIGINAL + self.nb_fec) * UDPSIZE
         nf = (C.c_size_t * S)()
         for _ in range(2):  # (a batch bigger than the guess is asked for again with room for its largest stream)
-            out = np.empty((S, cap, NB_ORIGINAL + self.nb_fec, UDPSIZE), np.uint8)
-            rc = self.ctx.lib.sdrhip_rx_collect_ragged(self.h, _ptr(out), cap * fb, cap, nf, 1 if wait else 0)
+            out, stride_bytes = _frame_buffer(S, cap, nb_fec)
+            rc = self.ctx.lib.sdrhip_rx_collect_ragged(self.h, _ptr(out), stride_bytes, cap, nf, 1 if wait else 0)
             if rc == -1 and max_frames is None and S and max(nf[:]) > cap:
                 cap = max(nf[:])
                 continue
@@ -839,24 +904,14 @@ class RxPipe:
         if rc == -6:
             return None
         check(rc)
-        if batches:
-            batches.pop(0)
-        elif fill[1]:  # (wait = True sent the partly filled batch out as it was)
-            self._rg_fill = [np.zeros(S, np.int64), 0]
+        self._log.pop()
         return [out[s, :nf[s]] for s in range(S)]
 
     def process(self, iq, tv_sec=0, tv_usec=0, out=None):
         """-> frames (S, n_frames, 128 + nb_fec, 512) uint8 (squeezed for one stream)"""
         x, is_t, squeeze = self._input(iq)
         S, n = x.shape[0], x.shape[1]
-        cap = max(self.max_frames(n), 1)
-        fb = (NB_ORIGINAL + self.nb_fec) * UDPSIZE
-        if out is None:
-            out = (torch.empty((S, cap, NB_ORIGINAL + self.nb_fec, UDPSIZE), dtype=torch.uint8, device=x.device) if is_t
-                   else np.empty((S, cap, NB_ORIGINAL + self.nb_fec, UDPSIZE), np.uint8))
-        if out.shape[1] < cap or out.shape[0] != S:
-            raise ValueError("out must hold (S, >= %d, %d, 512) bytes" % (cap, NB_ORIGINAL + self.nb_fec))
-        stride_bytes = out.shape[1] * fb
+        out, stride_bytes = _frame_buffer(S, max(self.max_frames(n), 1), self.nb_fec, x.device if is_t else None, out)
         nf = C.c_size_t(0)
         check(self.ctx.lib.sdrhip_rx_process(self.h, _ptr(x), n, _stride_samples(x), tv_sec, tv_usec, _ptr(out), stride_bytes,
                                              C.byref(nf), MEM_DEVICE if is_t else MEM_HOST))
@@ -881,18 +936,13 @@ class RxPipe:
         allocated with such a stride to avoid the copy."""
         x, is_t, squeeze = self._input(iq)
         if is_t and x.shape[0] > 1 and (x.stride(0) // 2) % 4:
-            n = x.shape[1]
-            buf = torch.empty((x.shape[0], (n + 3) & ~3, 2), dtype=x.dtype, device=x.device)
-            buf[:, :n].copy_(x)
-            x = buf[:, :n]
+            x = _padded_rows(x.shape[0], x.shape[1], 4, x.dtype, x.device, src=x)
         return x, is_t, squeeze
 
     def _ragged_args(self, x, counts, tv_sec, tv_usec):
         S = x.shape[0]
         cnt = _counts(counts, S, x.shape[1])
-        sec = np.broadcast_to(np.asarray(tv_sec, dtype=np.uint32), (S,))
-        usec = np.broadcast_to(np.asarray(tv_usec, dtype=np.uint32), (S,))
-        return (cnt, (C.c_size_t * S)(*cnt.tolist()), (C.c_uint32 * S)(*[int(v) for v in sec]), (C.c_uint32 * S)(*[int(v) for v in usec]))
+        return cnt, (C.c_size_t * S)(*cnt.tolist()), _stamps(tv_sec, S), _stamps(tv_usec, S)
 
     def process_ragged(self, iq, counts, tv_sec=0, tv_usec=0, out=None):
         """sdrhip_rx_process_ragged: stream s takes counts[s] samples of row s of iq (S, >= max(counts), 2), stamped tv_sec[s] /
@@ -902,15 +952,10 @@ class RxPipe:
         S = x.shape[0]
         cnt, c_cnt, c_sec, c_usec = self._ragged_args(x, counts, tv_sec, tv_usec)
         cap = max(self.max_frames(int(cnt.max()) if S else 0), 1)
-        fb = (NB_ORIGINAL + self.nb_fec) * UDPSIZE
-        if out is None:
-            out = (torch.empty((S, cap, NB_ORIGINAL + self.nb_fec, UDPSIZE), dtype=torch.uint8, device=x.device) if is_t
-                   else np.empty((S, cap, NB_ORIGINAL + self.nb_fec, UDPSIZE), np.uint8))
-        if out.shape[1] < cap or out.shape[0] != S:
-            raise ValueError("out must hold (S, >= %d, %d, 512) bytes" % (cap, NB_ORIGINAL + self.nb_fec))
+        out, stride_bytes = _frame_buffer(S, cap, self.nb_fec, x.device if is_t else None, out)
         nf = (C.c_size_t * S)()
         check(self.ctx.lib.sdrhip_rx_process_ragged(self.h, _ptr(x), c_cnt, _stride_samples(x), c_sec, c_usec, _ptr(out),
-                                                    out.shape[1] * fb, nf, MEM_DEVICE if is_t else MEM_HOST))
+                                                    stride_bytes, nf, MEM_DEVICE if is_t else MEM_HOST))
         n_frames = np.array(nf[:], dtype=np.int64)
         return out[:, :int(n_frames.max()) if S else 0], n_frames
 
@@ -955,25 +1000,15 @@ class RxPipe:
             max_released = max(counts + [0])  # (a call releases at most one frame per datagram)
         F = max(max_released, 1)
         cap = max(self.max_frames(SAMPLES_PER_FRAME * max_released + 63), 1)
-        rows, fb = NB_ORIGINAL + self.nb_fec, (NB_ORIGINAL + self.nb_fec) * UDPSIZE
-        out = (torch.empty((S, cap, rows, UDPSIZE), dtype=torch.uint8, device=buf.device) if is_t
-               else np.empty((S, cap, rows, UDPSIZE), np.uint8))
-        sec = np.broadcast_to(np.asarray(tv_sec, dtype=np.uint32), (S,))
-        usec = np.broadcast_to(np.asarray(tv_usec, dtype=np.uint32), (S,))
+        out, stride_bytes = _frame_buffer(S, cap, self.nb_fec, buf.device if is_t else None)
         info = (FECBufferFrame * (S * F))()
         nd = (C.c_size_t * S)(*counts)
         nr, nf = (C.c_size_t * S)(), (C.c_size_t * S)()
-        rc = self.ctx.lib.sdrhip_rx_process_datagrams(self.h, _ptr(buf), nd, buf.shape[1] * UDPSIZE, (C.c_uint32 * S)(*[int(v) for v in sec]),
-                                                      (C.c_uint32 * S)(*[int(v) for v in usec]), max_released, _ptr(out), cap * fb, info, nr, nf,
-                                                      MEM_DEVICE if is_t else MEM_HOST)
+        rc = self.ctx.lib.sdrhip_rx_process_datagrams(self.h, _ptr(buf), nd, buf.shape[1] * UDPSIZE, _stamps(tv_sec, S), _stamps(tv_usec, S),
+                                                      max_released, _ptr(out), stride_bytes, info, nr, nf, MEM_DEVICE if is_t else MEM_HOST)
         self.last_n_released = [int(x) for x in nr]
         check(rc)
-        res = []
-        for s in range(S):
-            recs = [dict(frame_index=info[s * F + j].frame_index, block_count=info[s * F + j].block_count,
-                         recovery_count=info[s * F + j].recovery_count, flags=info[s * F + j].flags) for j in range(int(nr[s]))]
-            res.append((out[s, :int(nf[s])], recs))
-        return res
+        return [(out[s, :int(nf[s])], recs) for s, recs in enumerate(_records(info, F, nr))]
 
     # ---- asynchronous datagram batches (sdrhip_rx_submit_datagrams / sdrhip_rx_collect_datagrams)
     def submit_datagrams(self, dgrams_per_stream, tv_sec=0, tv_usec=0):
@@ -983,29 +1018,9 @@ class RxPipe:
         tv_sec / tv_usec (scalars or one per stream) stamp the first sample each stream feeds its decimator in this batch.  Returns
         at once; raises SdrHipError(code SDRHIP_EBUSY = -6) when every batch of the ring is in flight."""
         S = self.nstreams
-        if isinstance(dgrams_per_stream, tuple):
-            buf, counts = dgrams_per_stream
-            counts = [int(x) for x in counts]
-            if len(counts) != S:
-                raise ValueError("one count per stream")
-        else:
-            if len(dgrams_per_stream) != S:
-                raise ValueError("one datagram array per stream")
-            if any(_is_torch(d) for d in dgrams_per_stream):
-                raise TypeError("submit_datagrams takes host memory")
-            counts = [int(np.asarray(d).shape[0]) for d in dgrams_per_stream]
-            nz = [np.asarray(d, np.uint8).reshape(-1, UDPSIZE) for d in dgrams_per_stream if len(d)]
-            buf = np.concatenate(nz) if nz else np.zeros((0, UDPSIZE), np.uint8)
-        if _is_torch(buf):
-            raise TypeError("submit_datagrams takes host memory")
-        buf = np.ascontiguousarray(buf, np.uint8)
-        if buf.size != sum(counts) * UDPSIZE:
-            raise ValueError("the datagrams do not match the counts")
-        sec = np.broadcast_to(np.asarray(tv_sec, dtype=np.uint32), (S,))
-        usec = np.broadcast_to(np.asarray(tv_usec, dtype=np.uint32), (S,))
+        buf, counts = _packed_datagrams(dgrams_per_stream, S)
         nd = (C.c_size_t * S)(*counts)
-        check(self.ctx.lib.sdrhip_rx_submit_datagrams(self.h, _ptr(buf), nd, 0, (C.c_uint32 * S)(*[int(v) for v in sec]),
-                                                      (C.c_uint32 * S)(*[int(v) for v in usec])))  # (0 = SDRHIP_PACKED)
+        check(self.ctx.lib.sdrhip_rx_submit_datagrams(self.h, _ptr(buf), nd, 0, _stamps(tv_sec, S), _stamps(tv_usec, S)))  # (0 = SDRHIP_PACKED)
         self._dg_submitted()
 
     def submit_datagrams_tagged(self, dgrams, stream_of, tv_sec=0, tv_usec=0):
@@ -1015,16 +1030,12 @@ class RxPipe:
         collected) and is demultiplexed on the device.  Collected with collect_datagrams."""
         S = self.nstreams
         buf, tags, tp = _tagged_batch(dgrams, stream_of)
-        sec = np.broadcast_to(np.asarray(tv_sec, dtype=np.uint32), (S,))
-        usec = np.broadcast_to(np.asarray(tv_usec, dtype=np.uint32), (S,))
-        check(self.ctx.lib.sdrhip_rx_submit_datagrams_tagged(self.h, _ptr(buf), tp, buf.shape[0], (C.c_uint32 * S)(*[int(v) for v in sec]),
-                                                             (C.c_uint32 * S)(*[int(v) for v in usec])))
+        check(self.ctx.lib.sdrhip_rx_submit_datagrams_tagged(self.h, _ptr(buf), tp, buf.shape[0], _stamps(tv_sec, S), _stamps(tv_usec, S)))
         self._dg_submitted()
 
     def _dg_submitted(self):
-        """bookkeeping behind a successful sdrhip_rx_submit_datagrams (also for callers of the C entry itself): the batch keeps the
-        frame size in force at its submit"""
-        self._dg_pending.append(self.nb_fec)
+        """a datagram batch was submitted (also for callers of the C entry itself): the log's record of it, with the nb_fec it keeps"""
+        self._log.batch("datagram", None, self.nb_fec)
 
     def collect_datagrams(self, wait=True, max_frames=None, max_released=None):
         """the oldest datagram batch: per stream (frames (n, 128 + nb_fec, 512) uint8, records) as process_datagrams returns them, or
@@ -1034,39 +1045,31 @@ class RxPipe:
         S = self.nstreams
         nr, nf = (C.c_size_t * S)(), (C.c_size_t * S)()
         w = 1 if wait else 0
-        pend = self._dg_pending
+        _, nb_fec = self._log.head(self.nb_fec)
         if max_frames is None or max_released is None:
             rc = self.ctx.lib.sdrhip_rx_collect_datagrams(self.h, None, 0, 0, 0, None, nr, nf, w)
             if rc == -6:
                 return None
             if rc == 0:  # (a batch that released and completed nothing: collected)
-                rows = NB_ORIGINAL + (pend.pop(0) if pend else self.nb_fec)
+                self._log.pop()
                 self.last_n_released, self.last_n_frames = [0] * S, [0] * S
-                return [(np.zeros((0, rows, UDPSIZE), np.uint8), []) for _ in range(S)]
+                return [(np.zeros((0, NB_ORIGINAL + nb_fec, UDPSIZE), np.uint8), []) for _ in range(S)]
             if rc != -1:
                 check(rc)
             if max_frames is None:
                 max_frames = max(int(x) for x in nf)
             if max_released is None:
                 max_released = max(int(x) for x in nr)
-        rows = NB_ORIGINAL + (pend[0] if pend else self.nb_fec)
-        fb = rows * UDPSIZE
-        cap, F = max(max_frames, 1), max(max_released, 1)
-        out = np.empty((S, cap, rows, UDPSIZE), np.uint8)
+        F = max(max_released, 1)
+        out, stride_bytes = _frame_buffer(S, max(max_frames, 1), nb_fec)
         info = (FECBufferFrame * (S * F))()
-        rc = self.ctx.lib.sdrhip_rx_collect_datagrams(self.h, _ptr(out), cap * fb, max_frames, max_released, info, nr, nf, w)
+        rc = self.ctx.lib.sdrhip_rx_collect_datagrams(self.h, _ptr(out), stride_bytes, max_frames, max_released, info, nr, nf, w)
         self.last_n_released, self.last_n_frames = [int(x) for x in nr], [int(x) for x in nf]
         if rc == -6:
             return None
         check(rc)
-        if pend:
-            pend.pop(0)
-        res = []
-        for s in range(S):
-            recs = [dict(frame_index=info[s * F + j].frame_index, block_count=info[s * F + j].block_count,
-                         recovery_count=info[s * F + j].recovery_count, flags=info[s * F + j].flags) for j in range(int(nr[s]))]
-            res.append((out[s, :int(nf[s])], recs))
-        return res
+        self._log.pop()
+        return [(out[s, :int(nf[s])], recs) for s, recs in enumerate(_records(info, F, nr))]
 
     # ---- departure-order egress (sdrhip_rx_set_egress / sdrhip_rx_collect_egress / sdrhip_rx_release_egress)
     def set_egress(self, order="round_robin"):
@@ -1084,7 +1087,8 @@ class RxPipe:
         the library lends -- the batch's pinned download buffer and its tags -- valid until release_egress, the next
         collect_egress or the pipe's destruction; the batch keeps its ring slot meanwhile.  copy=True copies and releases."""
         S = self.nstreams
-        is_dg = bool(self._dg_pending)
+        rec, _ = self._log.head(self.nb_fec, "ragged" if wait else None)
+        is_dg = rec is not None and rec.kind == "datagram"
         eg = _lib.RxEgress()
         nf, nr = (C.c_size_t * S)(), (C.c_size_t * S)()
         F, info = (max_released or 0), None
@@ -1099,12 +1103,7 @@ class RxPipe:
         if rc == -6:
             return None
         check(rc)
-        if is_dg:
-            self._dg_pending.pop(0)
-        elif getattr(self, "_rg_batches", []):
-            self._rg_batches.pop(0)
-        elif hasattr(self, "_rg_fill") and self._rg_fill[1]:  # (wait = True sent the partly filled batch out as it was)
-            self._rg_fill = [np.zeros(S, np.int64), 0]
+        self._log.pop()
         n = int(eg.n_dgrams)
         self.last_blocks_per_frame = int(eg.blocks_per_frame)
         if n:
@@ -1115,12 +1114,7 @@ class RxPipe:
         if copy:
             dg, tags = dg.copy(), tags.copy()
             self.release_egress()
-        records = None
-        if is_dg:
-            records = [[dict(frame_index=info[s * F + j].frame_index, block_count=info[s * F + j].block_count,
-                             recovery_count=info[s * F + j].recovery_count, flags=info[s * F + j].flags) for j in range(int(nr[s]))]
-                       for s in range(S)]
-        return dg, tags, np.array(nf[:], dtype=np.int64), records
+        return dg, tags, np.array(nf[:], dtype=np.int64), _records(info, F, nr) if is_dg else None
 
     def release_egress(self):
         """sdrhip_rx_release_egress: the batch collect_egress(copy=False) lent is free again (its views are dead)"""
@@ -1161,28 +1155,20 @@ class RxPipe:
         check(self.ctx.lib.sdrhip_rx_carry(self.h, c))
         return np.array(c[:], dtype=np.int64)
 
-    def close(self):
-        if self.h:
-            self.ctx.lib.sdrhip_rx_destroy(self.h)
-            self.h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class TxPipe:
+class TxPipe(_Handle):
     """SDRdaemonFECBuffer decode -> Upsampler for a bank of streams (sdrhip_tx).  pipelined=True: process() decodes its batch
     on the context's second stream while the previous batch is interpolated, and returns the PREVIOUS batch's samples
     (sdrhip_tx_set_pipelined); flush() returns the last batch's at the end.  A device-memory rx batch must stay untouched until
     the next process() / flush() has returned."""
 
+    _destroy = "sdrhip_tx_destroy"
+
     def __init__(self, ctx, nstreams=1, log2interp=4, pipelined=False, output_format="s16"):
         """output_format: "s16" (int16 IQ) or "s8" (HackRF int8), see set_output_format"""
+        _Handle.__init__(self, ctx.lib)
         self.ctx, self.nstreams, self.log2interp = ctx, nstreams, log2interp
-        self.h = C.c_void_p()
+        self._log = _BatchLog()  # the asynchronous batches in flight, each with the log2interp it keeps (the collects size with it)
         self.m_error = ""
         self.pipelined = bool(pipelined)
         check(ctx.lib.sdrhip_tx_create(ctx.h, nstreams, log2interp, C.byref(self.h)))
@@ -1251,6 +1237,7 @@ class TxPipe:
     def set_async(self, depth=4):
         """ring of `depth` batches in flight"""
         check(self.ctx.lib.sdrhip_tx_set_async(self.h, depth))
+        self._log.reset()
 
     def submit(self, rx, indices=None):
         """one batch of received frames from host memory, (S, F, 128, 512) uint8 (or (F, 128, 512)); returns at once.  Raises
@@ -1266,16 +1253,15 @@ class TxPipe:
             a = np.ascontiguousarray(a)
         if indices is not None:
             indices = np.ascontiguousarray(indices, dtype=np.uint8)
-        self._async_frames = getattr(self, "_async_frames", [])
         check(self.ctx.lib.sdrhip_tx_submit(self.h, _ptr(a), C.c_void_p(indices.ctypes.data if indices is not None else 0), a.shape[1], a.strides[0]))
         if a.shape[1]:
-            self._async_frames.append((a.shape[1], self.log2interp))
+            self._log.batch("frames", a.shape[1], self.log2interp)
 
     def collect(self, wait=True, block0=False):
         """-> the samples of the oldest batch (S, F * 16129 << log2interp, 2) int16 -- with block0=True a pair (samples, meta blocks
         (S, F, 508) uint8) -- or None when no batch was collected (nothing submitted, or wait=False and the oldest one is in flight)"""
-        pend = getattr(self, "_async_frames", [])
-        F, L = pend[0] if pend else (0, self.log2interp)
+        rec, L = self._log.head(self.log2interp)
+        F = rec.most if rec is not None else 0
         cap = max((F * SAMPLES_PER_FRAME) << L, 4)
         out = np.empty((self.nstreams, cap, 2), self._out_dtype)
         b0 = np.empty((self.nstreams, max(F, 1), BLOCK_BYTES), np.uint8)
@@ -1284,8 +1270,7 @@ class TxPipe:
         if rc == -6:
             return None
         check(rc)
-        if pend:
-            pend.pop(0)
+        self._log.pop()
         return (out[:, :n_out.value], b0[:, :nf.value]) if block0 else out[:, :n_out.value]
 
     def flush(self, device=None):
@@ -1323,13 +1308,8 @@ class TxPipe:
                                                       info, nf, MEM_DEVICE if is_t else MEM_HOST)
         self.last_n_frames = [int(x) for x in nf]
         check(rc)
-        res = []
-        for s in range(S):
-            k = int(nf[s])
-            recs = [dict(frame_index=info[s * F + j].frame_index, block_count=info[s * F + j].block_count,
-                         recovery_count=info[s * F + j].recovery_count, flags=info[s * F + j].flags) for j in range(k)]
-            res.append((out[s, :(k * SAMPLES_PER_FRAME) << self.log2interp], b0[s, :k], recs))
-        return res
+        return [(out[s, :(len(recs) * SAMPLES_PER_FRAME) << self.log2interp], b0[s, :len(recs)], recs)
+                for s, recs in enumerate(_records(info, F, nf))]
 
     # ---- asynchronous datagram batches (sdrhip_tx_submit_datagrams / sdrhip_tx_collect_datagrams)
     def submit_datagrams(self, dgrams_per_stream):
@@ -1338,32 +1318,10 @@ class TxPipe:
         sdrhip_host_alloc memory goes up in place and must stay untouched until the batch is collected.  Returns at once; raises
         SdrHipError(code SDRHIP_EBUSY = -6) when every batch of the ring is in flight."""
         S = self.nstreams
-        if isinstance(dgrams_per_stream, tuple):
-            buf, counts = dgrams_per_stream
-            counts = [int(x) for x in counts]
-            if len(counts) != S:
-                raise ValueError("one count per stream")
-        else:
-            if len(dgrams_per_stream) != S:
-                raise ValueError("one datagram array per stream")
-            if any(_is_torch(d) for d in dgrams_per_stream):
-                raise TypeError("submit_datagrams takes host memory")
-            counts = [int(np.asarray(d).shape[0]) for d in dgrams_per_stream]
-            nz = [np.asarray(d, np.uint8).reshape(-1, UDPSIZE) for d in dgrams_per_stream if len(d)]
-            buf = np.concatenate(nz) if nz else np.zeros((0, UDPSIZE), np.uint8)
-        if _is_torch(buf):
-            raise TypeError("submit_datagrams takes host memory")
-        buf = np.ascontiguousarray(buf, np.uint8)
-        if buf.size != sum(counts) * UDPSIZE:
-            raise ValueError("the datagrams do not match the counts")
+        buf, counts = _packed_datagrams(dgrams_per_stream, S)
         nd = (C.c_size_t * S)(*counts)
-        pend = self.__dict__.setdefault("_dg_pending", [])
-        pend.append(self.log2interp)  # (the batch keeps the factor in force; collect_datagrams sizes its buffers with it)
-        try:
-            check(self.ctx.lib.sdrhip_tx_submit_datagrams(self.h, _ptr(buf), nd, 0))  # (0 = SDRHIP_PACKED)
-        except SdrHipError:
-            pend.pop()
-            raise
+        check(self.ctx.lib.sdrhip_tx_submit_datagrams(self.h, _ptr(buf), nd, 0))  # (0 = SDRHIP_PACKED)
+        self._log.batch("datagram", None, self.log2interp)
 
     def submit_datagrams_tagged(self, dgrams, stream_of):
         """one batch as a hub's socket delivers it (sdrhip_tx_submit_datagrams_tagged): dgrams (n, 512) uint8 in arrival order,
@@ -1371,13 +1329,8 @@ class TxPipe:
         subsequences; the array goes up unsorted (from Context.host_alloc memory in place) and is demultiplexed on the device.
         Collected with collect_datagrams."""
         buf, tags, tp = _tagged_batch(dgrams, stream_of)
-        pend = self.__dict__.setdefault("_dg_pending", [])
-        pend.append(self.log2interp)  # (as submit_datagrams)
-        try:
-            check(self.ctx.lib.sdrhip_tx_submit_datagrams_tagged(self.h, _ptr(buf), tp, buf.shape[0]))
-        except SdrHipError:
-            pend.pop()
-            raise
+        check(self.ctx.lib.sdrhip_tx_submit_datagrams_tagged(self.h, _ptr(buf), tp, buf.shape[0]))
+        self._log.batch("datagram", None, self.log2interp)
 
     def collect_datagrams(self, wait=True, max_frames=None):
         """the oldest datagram batch: per stream (iq (n, 2) with n = frames * 16129 << the batch's log2interp, block0 (frames, 508)
@@ -1391,15 +1344,12 @@ class TxPipe:
             if rc == -6:
                 return None
             if rc == 0:  # (a batch that released nothing: collected)
-                pend = self.__dict__.get("_dg_pending")
-                if pend:
-                    pend.pop(0)
+                self._log.pop()
                 return [(np.zeros((0, 2), self._out_dtype), np.zeros((0, BLOCK_BYTES), np.uint8), []) for _ in range(S)]
             if rc != -1:
                 check(rc)
             max_frames = max(int(x) for x in nf)
-        pend = self.__dict__.setdefault("_dg_pending", [])
-        L = pend[0] if pend else self.log2interp
+        _, L = self._log.head(self.log2interp)
         F = max(max_frames, 1)
         out, pad = self._out(S, (F * SAMPLES_PER_FRAME) << L)
         b0 = np.empty((S, F, BLOCK_BYTES), np.uint8)
@@ -1409,16 +1359,8 @@ class TxPipe:
         if rc == -6:
             return None
         check(rc)
-        if pend:
-            pend.pop(0)
-        res = []
-        for s in range(S):
-            k = int(nf[s])
-            n = (k * SAMPLES_PER_FRAME) << L
-            recs = [dict(frame_index=info[s * F + j].frame_index, block_count=info[s * F + j].block_count,
-                         recovery_count=info[s * F + j].recovery_count, flags=info[s * F + j].flags) for j in range(k)]
-            res.append((out[s, :n], b0[s, :k], recs))
-        return res
+        self._log.pop()
+        return [(out[s, :(len(recs) * SAMPLES_PER_FRAME) << L], b0[s, :len(recs)], recs) for s, recs in enumerate(_records(info, F, nf))]
 
     def reset_streams(self, streams=None):
         """sdrhip_tx_reset_streams: the streams listed (None: every stream) begin again as a restarted sdrdaemontx does -- zero
@@ -1441,17 +1383,6 @@ class TxPipe:
         check(self.ctx.lib.sdrhip_tx_collector(self.h, C.byref(h)))
         return _fecbuf_stats(self.ctx, h, stream)
 
-    def close(self):
-        if self.h:
-            self.ctx.lib.sdrhip_tx_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class FECBufferFrame(C.Structure):
     """sdrhip_fecbuf_frame"""
@@ -1461,22 +1392,18 @@ class FECBufferFrame(C.Structure):
 FECBUF_DECODED, FECBUF_META, FECBUF_REPAIRED, FECBUF_DECODE_ERROR = 1, 2, 4, 8
 
 
-class FECBufferBank:
+class FECBufferBank(_Handle):
     """nstreams independent SDRdaemonFECBuffer collectors fed raw 512-byte datagrams (sdrhip_fecbuf).  write_and_read() takes one
     (n_s, 512) uint8 array per stream -- numpy (host memory) or torch device tensors -- and returns per stream the frames the
     datagrams released: (data (F, 127 * 508) uint8 = getSlotData, block0 (F, 508) uint8 = the meta block, records: a list of
     dicts frame_index / block_count / recovery_count / flags)."""
 
-    def __init__(self, ctx, nstreams=1):
-        self.ctx, self.nstreams = ctx, nstreams
-        self.h = C.c_void_p()
-        check(ctx.lib.sdrhip_fecbuf_create(ctx.h, nstreams, C.byref(self.h)))
+    _destroy = "sdrhip_fecbuf_destroy"
 
-    def __del__(self):
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            self.ctx.lib.sdrhip_fecbuf_destroy(h)
-            self.h = C.c_void_p()
+    def __init__(self, ctx, nstreams=1):
+        _Handle.__init__(self, ctx.lib)
+        self.ctx, self.nstreams = ctx, nstreams
+        check(ctx.lib.sdrhip_fecbuf_create(ctx.h, nstreams, C.byref(self.h)))
 
     def reset(self, streams=None):
         """constructor state: every stream (sdrhip_fecbuf_reset), or the streams listed (sdrhip_fecbuf_reset_streams: on the
@@ -1486,16 +1413,11 @@ class FECBufferBank:
         else:
             check(self.ctx.lib.sdrhip_fecbuf_reset_streams(self.h, _stream_mask(streams, self.nstreams)))
 
-    def write_and_read(self, dgrams_per_stream, max_frames=None):
-        S = self.nstreams
-        if len(dgrams_per_stream) != S:
-            raise ValueError("one datagram array per stream")
-        buf, counts, is_t = _datagram_batch(dgrams_per_stream)
-        nmax = max(counts + [0])
-        if max_frames is None:
-            max_frames = nmax  # (a call releases at most one frame per datagram)
-        F = max(max_frames, 1)
-        pb = 127 * BLOCK_BYTES
+    def _read(self, entry, buf, batch_args, max_frames):
+        """the tail of both entries: room for max_frames frames per stream, the call -- entry(handle, buf, *batch_args, outputs) --
+        and per stream the frames it released"""
+        S, F, pb = self.nstreams, max(max_frames, 1), 127 * BLOCK_BYTES
+        is_t = _is_torch(buf)
         if is_t:
             data = torch.empty((S, F, pb), dtype=torch.uint8, device=buf.device)
             b0 = torch.empty((S, F, BLOCK_BYTES), dtype=torch.uint8, device=buf.device)
@@ -1503,50 +1425,29 @@ class FECBufferBank:
             data = np.empty((S, F, pb), np.uint8)
             b0 = np.empty((S, F, BLOCK_BYTES), np.uint8)
         info = (FECBufferFrame * (S * F))()
-        nd = (C.c_size_t * S)(*counts)
         nf = (C.c_size_t * S)()
-        rc = self.ctx.lib.sdrhip_fecbuf_write_and_read(self.h, _ptr(buf), nd, buf.shape[1] * UDPSIZE, _ptr(data), F * pb, _ptr(b0),
-                                                       max_frames, info, nf, MEM_DEVICE if is_t else MEM_HOST)
+        rc = entry(self.h, _ptr(buf), *batch_args, _ptr(data), F * pb, _ptr(b0), max_frames, info, nf, MEM_DEVICE if is_t else MEM_HOST)
         self.last_n_frames = [int(x) for x in nf]
         check(rc)
-        out = []
-        for s in range(S):
-            k = int(nf[s])
-            recs = [dict(frame_index=info[s * F + j].frame_index, block_count=info[s * F + j].block_count,
-                         recovery_count=info[s * F + j].recovery_count, flags=info[s * F + j].flags) for j in range(k)]
-            out.append((data[s, :k], b0[s, :k], recs))
-        return out
+        return [(data[s, :len(recs)], b0[s, :len(recs)], recs) for s, recs in enumerate(_records(info, F, nf))]
+
+    def write_and_read(self, dgrams_per_stream, max_frames=None):
+        S = self.nstreams
+        if len(dgrams_per_stream) != S:
+            raise ValueError("one datagram array per stream")
+        buf, counts, _ = _datagram_batch(dgrams_per_stream)
+        if max_frames is None:
+            max_frames = max(counts + [0])  # (a call releases at most one frame per datagram)
+        return self._read(self.ctx.lib.sdrhip_fecbuf_write_and_read, buf, ((C.c_size_t * S)(*counts), buf.shape[1] * UDPSIZE), max_frames)
 
     def write_and_read_tagged(self, dgrams, stream_of, max_frames=None):
         """write_and_read of an arrival-order array (sdrhip_fecbuf_write_and_read_tagged): dgrams (n, 512) uint8 -- numpy or a torch
         device tensor --, stream_of (n,) uint16 = the stream of every datagram or DGRAM_SKIP.  Returns what write_and_read returns
         for the per-stream subsequences."""
-        S = self.nstreams
         buf, tags, tp = _tagged_batch(dgrams, stream_of, allow_torch=True)
-        is_t = _is_torch(buf)
         if max_frames is None:  # (a call releases at most one frame per datagram)
             max_frames = int(np.bincount(tags[tags != DGRAM_SKIP], minlength=1).max()) if tags.size else 0
-        F = max(max_frames, 1)
-        pb = 127 * BLOCK_BYTES
-        if is_t:
-            data = torch.empty((S, F, pb), dtype=torch.uint8, device=buf.device)
-            b0 = torch.empty((S, F, BLOCK_BYTES), dtype=torch.uint8, device=buf.device)
-        else:
-            data = np.empty((S, F, pb), np.uint8)
-            b0 = np.empty((S, F, BLOCK_BYTES), np.uint8)
-        info = (FECBufferFrame * (S * F))()
-        nf = (C.c_size_t * S)()
-        rc = self.ctx.lib.sdrhip_fecbuf_write_and_read_tagged(self.h, _ptr(buf), tp, buf.shape[0], _ptr(data), F * pb, _ptr(b0), max_frames,
-                                                              info, nf, MEM_DEVICE if is_t else MEM_HOST)
-        self.last_n_frames = [int(x) for x in nf]
-        check(rc)
-        out = []
-        for s in range(S):
-            k = int(nf[s])
-            recs = [dict(frame_index=info[s * F + j].frame_index, block_count=info[s * F + j].block_count,
-                         recovery_count=info[s * F + j].recovery_count, flags=info[s * F + j].flags) for j in range(k)]
-            out.append((data[s, :k], b0[s, :k], recs))
-        return out
+        return self._read(self.ctx.lib.sdrhip_fecbuf_write_and_read_tagged, buf, (tp, buf.shape[0]), max_frames)
 
     def stats(self, stream):
         """getCurNbBlocks, getCurNbRecovery, getMinNbBlocks, getMaxNbRecovery (these two reset when read), getCurrentMeta,
