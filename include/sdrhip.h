@@ -765,6 +765,47 @@ int sdrhip_rx_collect_egress(sdrhip_rx *rx, sdrhip_rx_egress *out, size_t *n_fra
                              sdrhip_fecbuf_frame *info_out, size_t *n_released, int wait);
 int sdrhip_rx_release_egress(sdrhip_rx *rx);
 
+/* ---- Per-stream fecblk: the recovery block count of every stream of a bank, from the meta block to the egress array.
+ * In the reference fecblk is set per process, that is per stream: the control channel's fecblk key calls
+ * UDPSink::setNbBlocksFEC on that process's own sink (sdrdaemonrx.cpp:599-605); the count enters the meta block's nbFECBlocks
+ * byte and the CRC over it (UDPSinkFEC.cpp:160-165) and sizes the frame's encoding (UDPSinkFEC.cpp:228-256).  A hub whose
+ * clients sit behind links of different quality -- fecblk 4 on the LAN, 32 behind a lossy bridge -- keeps them in ONE bank.
+ * sdrhip_rx_set_stream_fec: nb_fec = host array of nstreams entries, each 0..128; NULL = bank-wide again (cfg.nb_fec).
+ * Contract.  Per stream the result is byte for byte that of a one-stream sdrhip_rx whose config carries nb_fec[s]: the meta
+ * block's nbFECBlocks byte, the CRC over it, the recovery blocks computed over that block 0, the recovery headers.  A later call
+ * acts on stream s exactly like sdrhip_rx_reconfigure with the new value on that one-stream pipe at the same point: the frame
+ * being filled keeps the meta block it was opened with and is encoded with the count in force when it completes.
+ * The config: while the array is set cfg.nb_fec is unused; sdrhip_rx_reconfigure does not clear the array, and neither does
+ * sdrhip_rx_reset_streams (it is configuration, like the stream meta arrays); export and import of a stream are untouched.
+ * Layout: the frame area keeps ONE slot pitch, slot_blocks = 128 + max_s nb_fec[s] (a call that changes it moves the open
+ * frames the way a fecblk change of sdrhip_rx_reconfigure does); a frame of stream s holds 128 + nb_fec[s] valid super blocks,
+ * the rest of its slot is unspecified.  sdrhip_rx_frames_view_ragged shows slots at that pitch; sdrhip_rx_get_stream_fec
+ * reports a stream's count and the pitch.
+ * Entries: while the array is set every step is the ragged step: sdrhip_rx_process, sdrhip_rx_submit and
+ * sdrhip_rx_set_pipelined(1) return SDRHIP_EINVAL with nothing consumed.  The setter itself is refused, nothing changed, in
+ * pipelined mode, while batches are being filled or in flight, while a batch is lent, and for a count outside 0..128.  A handle
+ * on which the setter was never called launches exactly what it launched before.  An array of equal entries is allowed and
+ * behaves, layout and delivery, like that bank-wide count.
+ * Synchronous delivery (sdrhip_rx_process_ragged, sdrhip_rx_process_datagrams) with differing counts: stream s's frames land at
+ * frames_out + s * frame_stride_bytes as 128 + nb_fec[s] super blocks each, frame after frame -- dense per stream, the
+ * one-stream pipe's bytes; frame_stride_bytes must hold the largest n_frames[s] * (128 + nb_fec[s]) * 512.
+ * Asynchronous delivery: a batch submitted while the array holds differing values is delivered in departure order only; with
+ * SDRHIP_EGRESS_OFF sdrhip_rx_submit_ragged, sdrhip_rx_submit_datagrams and sdrhip_rx_submit_datagrams_tagged return
+ * SDRHIP_EINVAL with nothing consumed (sdrhip_rx_set_egress first).  A batch keeps the counts it was submitted with.
+ * Egress: the order's definition stands -- round j holds datagram j of every stream with D_s > j, streams ascending -- with
+ * D_s = n_frames[s] * (128 + nb_fec[s]).  For such a batch sdrhip_rx_egress.blocks_per_frame is 0 and
+ * sdrhip_rx_egress_stream_blocks fills `blocks` (nstreams entries) with each stream's 128 + nb_fec[s], valid while the batch is
+ * lent (SDRHIP_EINVAL when none is; for a batch of equal frames every entry is blocks_per_frame).  The download holds exactly
+ * sum n_frames[s] * (128 + nb_fec[s]) * 512 + sum n_released[s] * 16 bytes.
+ * How: the ragged rows carry each stream's third meta word; recovery row r of CM256 does not depend on the count, so the frames
+ * are encoded in at most three launches (one per encoder form) with the largest count of each group; a stream's end can fall
+ * inside another stream's frame, so the delivery kernel (KR) moves runs of constant stride, at most sum n_frames + S (S - 1).
+ * Not covered: the stream-order gather and KD for differing counts (departure order only), the uniform step, pipelined mode,
+ * per-stream decimation, Fc position or sample size, the Tx pipe. */
+int sdrhip_rx_set_stream_fec(sdrhip_rx *rx, const int *nb_fec);
+int sdrhip_rx_get_stream_fec(const sdrhip_rx *rx, int stream, int *nb_fec, int *slot_blocks);
+int sdrhip_rx_egress_stream_blocks(const sdrhip_rx *rx, size_t *blocks);
+
 /* ---- Per-stream lifecycle: one stream of a bank begins again while the others run on.
  * In the reference one stream is one sdrdaemonrx / sdrdaemontx process, and restarting that process gives the stream what the
  * constructors leave: zero half-band histories (Decimators.h:56-70, Interpolators.h:47-52: EO1.h:171-188 / IntHalfbandFilterDB's

@@ -50,6 +50,7 @@ EXPORTS = [
     "sdrhip_tx_export_stream", "sdrhip_tx_import_stream",
     "sdrhip_fecbuf_write_and_read_tagged", "sdrhip_tx_submit_datagrams_tagged", "sdrhip_rx_submit_datagrams_tagged",
     "sdrhip_rx_set_egress", "sdrhip_rx_collect_egress", "sdrhip_rx_release_egress",
+    "sdrhip_rx_set_stream_fec", "sdrhip_rx_get_stream_fec", "sdrhip_rx_egress_stream_blocks",
 ]
 
 
@@ -175,6 +176,9 @@ def load():
     lib.sdrhip_rx_set_egress.argtypes = [vp, i]
     lib.sdrhip_rx_collect_egress.argtypes = [vp, C.POINTER(RxEgress), C.POINTER(sz), sz, vp, C.POINTER(sz), i]
     lib.sdrhip_rx_release_egress.argtypes = [vp]
+    lib.sdrhip_rx_set_stream_fec.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.sdrhip_rx_get_stream_fec.argtypes = [vp, i, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.sdrhip_rx_egress_stream_blocks.argtypes = [vp, C.POINTER(sz)]
     lib.sdrhip_rx_set_stream_meta.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.sdrhip_rx_get_stream_meta.argtypes = [vp, i, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.sdrhip_rx_set_follow_meta.argtypes = [vp, i]

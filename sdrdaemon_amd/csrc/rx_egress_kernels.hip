@@ -21,6 +21,8 @@ namespace {
 
 typedef unsigned uint4_t __attribute__((ext_vector_type(4)));
 
+#include "rx_records_body.h"
+
 constexpr int KE_NT = 256;
 constexpr int KE_PER = 4;                  // 16-byte chunks per lane
 constexpr unsigned KE_CHUNKS = 512 / 16;   // chunks of a datagram = lanes of a half-wave
@@ -56,25 +58,7 @@ __global__ __launch_bounds__(KE_NT) void rx_egress_kernel(const RxEgressRun *__r
         }
         return;
     }
-    // ---- the records: slot i = record i % kmax of stream i / kmax.  The record loads do not wait for the places
-    const unsigned i0 = (wg - frame_wgs) * (unsigned)(KE_NT * KE_PER) + threadIdx.x;
-    const uint4_t *recs = reinterpret_cast<const uint4_t *>(rec.records);
-    unsigned rk[KE_PER];
-    uint4_t p[KE_PER]; // {pre, cnt, -, -} of the slot's stream
-#pragma unroll
-    for (int j = 0; j < KE_PER; ++j) {
-        const unsigned i = i0 + j * KE_NT < rec.nslots ? i0 + j * KE_NT : rec.nslots - 1;
-        const unsigned s = i / rec.kmax;
-        rk[j] = i - s * rec.kmax;
-        v[j] = __builtin_nontemporal_load(recs + i);
-        p[j] = reinterpret_cast<const uint4_t *>(rec.place)[s];
-    }
-#pragma unroll
-    for (int j = 0; j < KE_PER; ++j) asm volatile("" : "+v"(v[j]), "+v"(p[j]));
-    uint4_t *rdst = reinterpret_cast<uint4_t *>(out + rec.dst);
-#pragma unroll
-    for (int j = 0; j < KE_PER; ++j)
-        if (i0 + j * KE_NT < rec.nslots && rk[j] < p[j].y) rdst[(uint64_t)p[j].x + rk[j]] = v[j];
+    deliver_records_wg<KE_NT, KE_PER>(wg - frame_wgs, rec, out); // ---- the records (rx_records_body.h)
 }
 
 } // namespace

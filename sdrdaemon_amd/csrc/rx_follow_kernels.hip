@@ -5,7 +5,7 @@
 //
 // One launch per call or batch for the whole bank, one lane per stream: the lane reads m_outputMeta's frequency and rate from the
 // collector state the call committed, forms the zero-stamp MetaDataFEC record the stream's next frames carry -- frequency unchanged,
-// rate >> log2decim, the hub's own third word -- with its CRC, and writes {fc, rate, crc0} into the stream's row of the per-call
+// rate >> log2decim, the third word the host put into the stream's row (its own nbFECBlocks) -- with its CRC, and writes {fc, rate, crc0} into the stream's row of the per-call
 // table, where K2r takes them (stream_meta_base<true>).  A stream whose incoming rate is 0 (none of its frames released with a
 // block 0 yet, or a sender that says 0) keeps what the host put there.  The launch sits behind the table's upload and in front of
 // the first kernel that reads a row's three words, on the context's stream: nothing is read back.
@@ -26,8 +26,7 @@ __device__ __forceinline__ unsigned kf_crc_word(unsigned crc, unsigned w)
     return crc;
 }
 
-__global__ __launch_bounds__(KF_LANES) void rx_follow_meta_kernel(const FecBufState *state, RaggedRow *rows, unsigned w2, unsigned log2decim,
-                                                                  int nstreams)
+__global__ __launch_bounds__(KF_LANES) void rx_follow_meta_kernel(const FecBufState *state, RaggedRow *rows, unsigned log2decim, int nstreams)
 {
     const int s = (int)blockIdx.x * KF_LANES + (int)threadIdx.x;
     if (s >= nstreams) return;
@@ -37,10 +36,10 @@ __global__ __launch_bounds__(KF_LANES) void rx_follow_meta_kernel(const FecBufSt
     unsigned crc = 0xFFFFFFFFu;
     crc = kf_crc_word(crc, fc);
     crc = kf_crc_word(crc, rate);
-    crc = kf_crc_word(crc, w2);
+    RaggedRow &r = rows[s];
+    crc = kf_crc_word(crc, r.w2);
     crc = kf_crc_word(crc, 0u); // tv_sec
     crc = kf_crc_word(crc, 0u); // tv_usec
-    RaggedRow &r = rows[s];
     r.fc = fc;
     r.rate = rate;
     r.crc0 = crc ^ 0xFFFFFFFFu;
@@ -48,10 +47,10 @@ __global__ __launch_bounds__(KF_LANES) void rx_follow_meta_kernel(const FecBufSt
 
 } // namespace
 
-hipError_t launch_rx_follow_meta(const FecBufState *state, RaggedRow *rows, unsigned w2, int log2decim, int nstreams, hipStream_t stream)
+hipError_t launch_rx_follow_meta(const FecBufState *state, RaggedRow *rows, int log2decim, int nstreams, hipStream_t stream)
 {
     if (!state || !rows || nstreams <= 0 || log2decim < 0 || log2decim > 31) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rx_follow_meta_kernel, dim3((unsigned)((nstreams + KF_LANES - 1) / KF_LANES)), dim3(KF_LANES), 0, stream, state, rows, w2,
+    hipLaunchKernelGGL(rx_follow_meta_kernel, dim3((unsigned)((nstreams + KF_LANES - 1) / KF_LANES)), dim3(KF_LANES), 0, stream, state, rows,
                        (unsigned)log2decim, nstreams);
     return hipGetLastError();
 }

@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "rx_depart_order.h"
 #include "rx_egress_order.h"
 
 // loads of data that is streamed through once (IQ input, frames): non-temporal.  tools/dma_probe.hip on MI355X: 7.1 TB/s with
@@ -158,8 +159,8 @@ __device__ __forceinline__ void frame_meta_words_thread(const unsigned (&base)[6
 // three differ between the streams of a bank: w[0] = centre frequency, w[1] = sample rate (also the clock of the stamps) and
 // w[5] = the record's CRC (host-computed: the affine part, see above).  ROW = false (uniform launches): `p` is the Rx handle's
 // table, stream s at p + s * STREAM_META_WORDS, NULL: the shared record serves every stream.  ROW = true (ragged launches): `p` is
-// the stream's own three words, RaggedRow::fc ...  `stream` and `p` are wave-uniform: three scalar loads where a workgroup starts
-// on a stream's frames.
+// the stream's own words, RaggedRow::fc ... w2 (the fourth, w[2], carries the stream's nbFECBlocks: sdrhip_rx_set_stream_fec).
+// `stream` and `p` are wave-uniform: scalar loads where a workgroup starts on a stream's frames.
 template <bool ROW = false>
 __device__ __forceinline__ void stream_meta_base(const unsigned (&shared)[6], unsigned shared_rate, const unsigned *p, int stream,
                                                  unsigned (&base)[6], unsigned &rate)
@@ -170,6 +171,7 @@ __device__ __forceinline__ void stream_meta_base(const unsigned (&shared)[6], un
     if (ROW || p) {
         const unsigned *t = ROW ? p : p + (size_t)STREAM_META_WORDS * (size_t)__builtin_amdgcn_readfirstlane(stream);
         base[0] = t[0]; base[1] = t[1]; base[5] = t[2];
+        if (ROW) base[2] = t[3]; // (RaggedRow::w2, behind the three: the stream's own nbFECBlocks byte)
         rate = t[1];
     }
 }
@@ -215,7 +217,7 @@ struct RaggedRow {
     int mf_w0, mf_wps, mf_p0, mf_np;
     uint64_t mf_head, mf_tail_start;
     unsigned fc, rate, crc0;    // K2r: the stream's centre frequency, sample rate and zero-stamp CRC (stream_meta_base<true>)
-    unsigned pad;
+    unsigned w2;                // K2r, KF: word 2 of the stream's record -- sampleBytes, sampleBits, 128, nbFECBlocks (per-stream fecblk)
 };
 // K1mr: plans the matrix-core launch of a ragged call (per-stream fields of `rows`, shared span / grid in `a`: a->mf_wps = the
 // launch's matrix-core waves, a->mf_npieces = its VALU pieces); false when no stream is long enough for a span
@@ -551,7 +553,7 @@ hipError_t launch_rx_join_carry(int16_t *rows, size_t row_len, unsigned *carry, 
 // KF (rx_follow_kernels.hip, sdrhip_rx_set_follow_meta): one lane per stream; a stream whose committed m_outputMeta (state[s].out_meta)
 // carries a sample rate other than 0 gets {fc, rate >> log2decim, CRC of the zero-stamp record with third word w2} in rows[s]
 // (device: the per-call table, behind its upload); the others keep their row
-hipError_t launch_rx_follow_meta(const FecBufState *state, RaggedRow *rows, unsigned w2, int log2decim, int nstreams, hipStream_t stream);
+hipError_t launch_rx_follow_meta(const FecBufState *state, RaggedRow *rows, int log2decim, int nstreams, hipStream_t stream);
 // asynchronous Tx batches (sdrhip_tx_submit_datagrams): stream s's datagrams back to back at a.dg + dg_off[s] (device); njobs /
 // nslots come from the host's shadow of the classification; the scatter pass skips what lies past the classify pass's own counts,
 // max_frames or nslots, the guarded copy a slot whose dmap entry is still -1 (preset by the caller)
@@ -594,6 +596,11 @@ struct RxEgressRecords {
 };
 hipError_t launch_rx_egress(const RxEgressRun *runs, uint64_t nruns, uint32_t wg_per_frame, uint32_t blocks_per_frame, const uint8_t *frames,
                             uint8_t *out, const RxEgressRecords &rec, hipStream_t stream);
+// KR (rx_runs_kernels.hip), departure-order batches whose streams' frames differ in length (sdrhip_rx_set_stream_fec): run k =
+// `count` datagrams from frames + src to out + dst + i * stride (rx_depart_order.h; wg_per_run = its wg_per_run()), then the
+// records as KE moves them
+hipError_t launch_rx_runs(const RxDepartRun *runs, uint64_t nruns, uint32_t wg_per_run, const uint8_t *frames, uint8_t *out,
+                          const RxEgressRecords &rec, hipStream_t stream);
 // KX (dgram_demux_kernels.hip), tagged datagram batches: datagram i of the arrival-order array src goes to dst + 512 * dest[i]
 // (device table, n_total entries; 0xffffffff: the datagram is moved nowhere).  src and dst 16-byte aligned, n_total below 2^30;
 // the host that made dest vouches for every entry lying inside dst

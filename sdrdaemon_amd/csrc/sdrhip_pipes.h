@@ -2,6 +2,7 @@
 // units sdrhip_rx.cpp, sdrhip_rx_async.cpp, sdrhip_rx_datagrams.cpp, sdrhip_rx_datagrams_async.cpp, sdrhip_tx.cpp and
 // sdrhip_tx_async.cpp share
 #pragma once
+#include "rx_depart_order.h"
 #include "rx_frame_area.h"
 #include "sdrhip_host.h"
 
@@ -83,7 +84,7 @@ struct sdrhip_rx {
     int nstreams;
     sdrhip_rx_config cfg;
     sdrhip_decimators *dec;
-    // [nstreams][area.cap()][128 + nb_fec][512].  A call fills slots area.slot(s) .. area.slot(s) + done of stream s; the frame
+    // [nstreams][area.cap()][128 + nb_fec][512] (per-stream fecblk: 128 + the largest count, rx_frame_bytes).  A call fills slots area.slot(s) .. area.slot(s) + done of stream s; the frame
     // still being filled is the first slot of the next call, so the window slides and nothing is copied until it reaches the end
     // of the area.  `area` decides where the windows go (rx_frame_area.h), rx_run_plan moves the open frames there
     sdrhip::DevBuf work;
@@ -147,6 +148,10 @@ struct sdrhip_rx {
         int egress = 0;
         sdrhip::PinnedBuf e_tab;
         std::vector<uint16_t> e_tags;
+        // (per-stream fecblk, sdrhip_rx_set_stream_fec with differing counts: the super blocks per frame of every stream the batch
+        // was launched with, and the datagrams of its array; empty: every frame holds frame_bytes / 512)
+        std::vector<size_t> e_blocks;
+        size_t e_dgrams = 0;
         void release()
         {
             if (done) (void)hipEventDestroy(done);
@@ -164,6 +169,7 @@ struct sdrhip_rx {
     int egress = 0;
     sdrhip::DevBuf e_tab;
     sdrhip::RxEgressOrder e_order;
+    sdrhip::RxDepartOrder e_depart; // (batches whose streams' frames differ in length: rx_depart_order.h)
     bool consumed = false;        // set by sdrhip_rx_process once the decimator launch of the call went out (the filter state advanced)
     // ---- input format (sdrhip_rx_set_input_format): 8-bit input is widened by K0 into `wide`, the decimator's int16 input
     int in_fmt = sdrhip::IQF_S16;
@@ -184,6 +190,12 @@ struct sdrhip_rx {
     sdrhip::PinnedBuf sm_pin[4];
     sdrhip::DevBuf sm_dev[2];
     int sm_pin_sel = 0, sm_dev_sel = 0;
+    // ---- per-stream fecblk (sdrhip_rx_set_stream_fec): empty = bank-wide (cfg.nb_fec).  While it is set every step is the ragged
+    // step; the frame area keeps ONE slot pitch, 128 + the largest count (rx_frame_bytes), a frame of stream s holds
+    // rx_stream_blocks(rx, s) valid super blocks at the head of its slot.  sm_w2 = word 2 of each stream's zero-stamp record
+    // (sampleBytes, sampleBits, 128, nbFECBlocks), formed with sm_words
+    std::vector<int> sf_fec;
+    std::vector<unsigned> sm_w2;
     // ---- datagram entry (sdrhip_rx_process_datagrams): one SDRdaemonFECBuffer per stream, created on first use; it delivers into
     // j_rows ([nstreams][j_row_len] samples, the ragged step's input), behind the samples each row holds back from earlier calls
     // (their counts live with the collector: fecbuf_join_carry)
@@ -268,7 +280,25 @@ struct sdrhip_tx {
 
 namespace sdrhip {
 static_assert(RX_FRAME_SAMPLES == SDRHIP_SAMPLES_PER_FRAME, "rx_frame_area.h frames the header's frame");
-inline size_t rx_frame_bytes(const sdrhip_rx *rx) { return (size_t)(SDRHIP_NB_ORIGINAL + rx->cfg.nb_fec) * SDRHIP_UDPSIZE; }
+// per-stream fecblk: the count of stream s, the largest of the bank, and whether two streams differ
+inline int rx_fec_of(const sdrhip_rx *rx, size_t s) { return rx->sf_fec.empty() ? rx->cfg.nb_fec : rx->sf_fec[s]; }
+inline int rx_fec_max(const sdrhip_rx *rx)
+{
+    if (rx->sf_fec.empty()) return rx->cfg.nb_fec;
+    int m = 0;
+    for (size_t s = 0; s < rx->sf_fec.size(); ++s) m = rx->sf_fec[s] > m ? rx->sf_fec[s] : m;
+    return m;
+}
+inline bool rx_fec_mixed(const sdrhip_rx *rx)
+{
+    for (size_t s = 1; s < rx->sf_fec.size(); ++s)
+        if (rx->sf_fec[s] != rx->sf_fec[0]) return true;
+    return false;
+}
+// bytes of a slot of the frame area (the ONE pitch), and of the valid super blocks of a frame of stream s
+inline size_t rx_frame_bytes(const sdrhip_rx *rx) { return (size_t)(SDRHIP_NB_ORIGINAL + rx_fec_max(rx)) * SDRHIP_UDPSIZE; }
+inline size_t rx_stream_blocks(const sdrhip_rx *rx, size_t s) { return (size_t)(SDRHIP_NB_ORIGINAL + rx_fec_of(rx, s)); }
+inline size_t rx_stream_bytes(const sdrhip_rx *rx, size_t s) { return rx_stream_blocks(rx, s) * SDRHIP_UDPSIZE; }
 // batches of the ring that are being filled or in flight, of the ragged (or the uniform) kind.  (A lent batch -- state 3 -- is
 // neither: it was collected, and only its slot is still taken.)
 inline bool rx_has_batches(const sdrhip_rx *rx, bool ragged)
@@ -315,7 +345,8 @@ int rx_launch_filling(sdrhip_rx *rx, sdrhip_rx::Batch &b);
 // in `work` from view.offset(s, frame_bytes)), the table's upload, and KE into a_frames: the datagrams in departure order, then --
 // a datagram batch: released = the collector's [S][4] results, records = its public records [S][kmax] -- the records as KD lays
 // them out.  The table, the tags and the device table are rx_egress_room's; the order's own vectors (one entry per frame) are the
-// handle's and keep their capacity.
+// handle's and keep their capacity.  Per-stream fecblk with differing counts (rx_fec_mixed): frame_bytes / blocks_per_frame are the
+// slot pitch, the runs are rx_depart_order.h's (at most frames + S (S - 1)) and KR moves them; b.e_blocks / b.e_dgrams say so
 int rx_egress_room(sdrhip_rx *rx, sdrhip_rx::Batch &b, size_t frames, size_t blocks_per_frame);
 hipError_t rx_egress_launch(sdrhip_rx *rx, sdrhip_rx::Batch &b, const size_t *n_frames, size_t frame_bytes, const int *released, size_t kmax,
                             const uint8_t *records);

@@ -59,6 +59,7 @@ extern "C" int sdrhip_rx_set_pipelined(sdrhip_rx *rx, int on)
     if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
     sdrhip::CtxLock lock_(rx->ctx);
     if (!on && rx->late.have) return fail(SDRHIP_EINVAL, "rx_set_pipelined: sdrhip_rx_flush the waiting frames first");
+    if (on && !rx->sf_fec.empty()) return fail(SDRHIP_EINVAL, "rx_set_pipelined: per-stream fecblk is set (sdrhip_rx_set_stream_fec): every step is the ragged step");
     if (on && rx_dgrams_in_flight(rx)) return fail(SDRHIP_EINVAL, "rx_set_pipelined: asynchronous datagram batches are in flight: collect them first");
     if (on && !rx->area.aligned()) return fail(SDRHIP_EINVAL, "rx_set_pipelined: ragged calls left the streams at different frame positions");
     rx->pipelined = on ? 1 : 0;
@@ -157,6 +158,20 @@ static int rx_make_room(sdrhip_rx *rx, const size_t *done, bool pipelined, const
     return rx_run_plan(rx, p, p.new_cap ? &fresh : nullptr, fb, fb, fb, who);
 }
 
+// the slots change size (a fecblk change): the frame being filled (its 128 original super blocks) moves to slot 0 of a new area
+static int rx_repitch(sdrhip_rx *rx, size_t new_fb, const char *who)
+{
+    if (!rx->area.cap() || new_fb == rx_frame_bytes(rx)) return SDRHIP_OK;
+    int rc;
+    if ((rc = rx_settle(rx))) return rc;
+    DevBuf fresh;
+    if ((rc = fresh.reserve(rx->area.streams() * rx->area.cap() * new_fb))) return rc;
+    if ((rc = rx_run_plan(rx, rx->area.replan(), &fresh, rx_frame_bytes(rx), new_fb, (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE, who))) return rc;
+    // (no frames wait for delivery here: a fecblk change with late.have set is refused by the callers)
+    rx->old_work.release();
+    return SDRHIP_OK;
+}
+
 extern "C" int sdrhip_rx_reconfigure(sdrhip_rx *rx, const sdrhip_rx_config *cfg)
 {
     if (!rx || !cfg) return fail(SDRHIP_EINVAL, "rx_reconfigure: NULL argument");
@@ -166,20 +181,12 @@ extern "C" int sdrhip_rx_reconfigure(sdrhip_rx *rx, const sdrhip_rx_config *cfg)
     if (cfg->hb_variant != rx->cfg.hb_variant) return fail(SDRHIP_EINVAL, "rx_reconfigure: hb_variant is fixed at creation");
     sdrhip_ctx *c = rx->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    if (cfg->nb_fec != rx->cfg.nb_fec && rx->late.have)
+    // (per-stream fecblk: cfg.nb_fec is unused while the array is set, the slots keep their pitch)
+    const bool fec_changes = rx->sf_fec.empty() && cfg->nb_fec != rx->cfg.nb_fec;
+    if (fec_changes && rx->late.have)
         return fail(SDRHIP_EINVAL, "rx_reconfigure: frames of the previous call wait for delivery (pipelined mode): sdrhip_rx_flush them "
                                    "before changing fecblk (they carry the old frame size)");
-    if (cfg->nb_fec != rx->cfg.nb_fec && rx->area.cap()) {
-        // the slots change size: the frame being filled (its 128 original super blocks) moves to slot 0 of a new area
-        if ((rc = rx_settle(rx))) return rc;
-        const size_t new_fb = (size_t)(SDRHIP_NB_ORIGINAL + cfg->nb_fec) * SDRHIP_UDPSIZE;
-        DevBuf fresh;
-        if ((rc = fresh.reserve(rx->area.streams() * rx->area.cap() * new_fb))) return rc;
-        if ((rc = rx_run_plan(rx, rx->area.replan(), &fresh, rx_frame_bytes(rx), new_fb, (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE, "rx_reconfigure")))
-            return rc;
-        // (no frames wait for delivery here: a fecblk change with late.have set was refused above)
-        rx->old_work.release();
-    }
+    if (fec_changes && (rc = rx_repitch(rx, (size_t)(SDRHIP_NB_ORIGINAL + cfg->nb_fec) * SDRHIP_UDPSIZE, "rx_reconfigure"))) return rc;
     rx->cfg = *cfg;
     return SDRHIP_OK;
 }
@@ -345,12 +352,54 @@ extern "C" int sdrhip_rx_get_stream_meta(const sdrhip_rx *rx, int stream, uint32
     return SDRHIP_OK;
 }
 
+// ---- per-stream fecblk (sdrdaemonrx.cpp:599-605: every sdrdaemonrx sets UDPSink::setNbBlocksFEC on its own sink)
+extern "C" int sdrhip_rx_set_stream_fec(sdrhip_rx *rx, const int *nb_fec)
+{
+    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
+    sdrhip::CtxLock lock_(rx->ctx);
+    const size_t S = (size_t)rx->nstreams;
+    // ---- everything that can be refused, before anything changes
+    if (rx->pipelined || rx->late.have) return fail(SDRHIP_EINVAL, "rx_set_stream_fec: not available in pipelined mode");
+    if (rx_batches_active(rx)) return fail(SDRHIP_EINVAL, "rx_set_stream_fec: asynchronous batches are being filled or in flight: collect them first");
+    if (rx->ring.busy()) return fail(SDRHIP_EINVAL, "rx_set_stream_fec: a batch is lent (sdrhip_rx_collect_egress): sdrhip_rx_release_egress it first");
+    int most = rx->cfg.nb_fec;
+    if (nb_fec) {
+        most = 0;
+        for (size_t s = 0; s < S; ++s) {
+            if (nb_fec[s] < 0 || nb_fec[s] > 128) return fail(SDRHIP_EINVAL, "rx_set_stream_fec: nb_fec[%zu] = %d, must be 0..128", s, nb_fec[s]);
+            most = nb_fec[s] > most ? nb_fec[s] : most;
+        }
+    }
+    try { // (room for the array before anything moves: the assignment below cannot fail)
+        if (nb_fec) rx->sf_fec.reserve(S);
+    } catch (const std::bad_alloc &) {
+        return fail(SDRHIP_ENOMEM, "out of host memory");
+    }
+    HIP_TRY(hipSetDevice(rx->ctx->device));
+    // the slot pitch follows the largest count: a change moves the open frames like a fecblk change of sdrhip_rx_reconfigure
+    if (int rc = rx_repitch(rx, (size_t)(SDRHIP_NB_ORIGINAL + most) * SDRHIP_UDPSIZE, "rx_set_stream_fec")) return rc;
+    if (nb_fec) rx->sf_fec.assign(nb_fec, nb_fec + S);
+    else rx->sf_fec.clear();
+    ++rx->sm_version; // (the streams' records carry the count: formed again by the next launch)
+    return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_rx_get_stream_fec(const sdrhip_rx *rx, int stream, int *nb_fec, int *slot_blocks)
+{
+    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
+    sdrhip::CtxLock lock_(rx->ctx);
+    if (stream < 0 || stream >= rx->nstreams) return fail(SDRHIP_EINVAL, "rx_get_stream_fec: stream %d of %d", stream, rx->nstreams);
+    if (nb_fec) *nb_fec = rx_fec_of(rx, (size_t)stream);
+    if (slot_blocks) *slot_blocks = (int)(rx_frame_bytes(rx) / SDRHIP_UDPSIZE);
+    return SDRHIP_OK;
+}
+
 // the streams' records for the frames the next launch opens: [nstreams][STREAM_META_WORDS] = {fc, rate, CRC of the zero-stamp
 // record}; NULL while neither array is set (the shared record of rx_meta_base serves every stream).  Formed again only when the
 // arrays or the configuration words that enter the record have changed
 static const unsigned *rx_stream_words(sdrhip_rx *rx, unsigned ssd)
 {
-    if (rx->sm_fc.empty() && rx->sm_rate.empty()) return nullptr;
+    if (rx->sm_fc.empty() && rx->sm_rate.empty() && rx->sf_fec.empty()) return nullptr;
     unsigned w[6];
     rx_meta_base(rx->cfg, ssd, w);
     const sdrhip_rx::SmKey key = {rx->sm_version, w[2], w[0], w[1]};
@@ -358,11 +407,13 @@ static const unsigned *rx_stream_words(sdrhip_rx *rx, unsigned ssd)
     if (key.version != old.version || key.w2 != old.w2 || key.fc != old.fc || key.rate != old.rate) {
         const size_t S = (size_t)rx->nstreams;
         rx->sm_words.resize(S * STREAM_META_WORDS);
+        rx->sm_w2.resize(S);
         for (size_t s = 0; s < S; ++s) {
             rx_meta_record(rx->sm_fc.empty() ? rx->cfg.center_frequency_khz : rx->sm_fc[s],
-                           rx->sm_rate.empty() ? rx->cfg.sample_rate : rx->sm_rate[s], rx->cfg.nb_fec, ssd, w);
+                           rx->sm_rate.empty() ? rx->cfg.sample_rate : rx->sm_rate[s], rx_fec_of(rx, s), ssd, w);
             unsigned *t = &rx->sm_words[s * STREAM_META_WORDS];
             t[0] = w[0]; t[1] = w[1]; t[2] = w[5];
+            rx->sm_w2[s] = w[2]; // (the ragged rows' fourth word: the stream's own nbFECBlocks byte)
         }
         rx->sm_key = key;
         rx->sm_uploaded = false;
@@ -421,6 +472,7 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
     if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
     sdrhip::CtxLock lock_(rx->ctx);
     if (n_frames) *n_frames = 0;
+    if (!rx->sf_fec.empty()) return fail(SDRHIP_EINVAL, "rx_process: per-stream fecblk is set (sdrhip_rx_set_stream_fec): use sdrhip_rx_process_ragged");
     if (rx_has_batches(rx, true)) return fail(SDRHIP_EINVAL, "rx_process: ragged batches are being filled or in flight: collect them first");
     if (rx_dgrams_in_flight(rx)) return fail(SDRHIP_EINVAL, "rx_process: asynchronous datagram batches are in flight: collect them first");
     if (n_in && !rx->area.aligned()) {
@@ -644,6 +696,12 @@ int sdrhip::rx_area_room(sdrhip_rx *rx, const size_t *done)
     return rx_make_room(rx, done ? done : std::vector<size_t>(rx->area.streams(), 0).data(), false, "rx_process_ragged", true);
 }
 
+// entries of the ragged step's frame list: up to three sublists (one per encoder form, per-stream fecblk), each padded to a
+// whole group
+static size_t rx_flist_entries(size_t sum_done) { return (sum_done / GF_FRAMES_PER_GROUP + 3) * GF_FRAMES_PER_GROUP; }
+// the form fec_encode_device chooses for `rows` recovery blocks: 0 the generic kernel, 1 the FFT / bit-sliced kernel, 2 the walk
+static int rx_encode_form(const sdrhip_ctx *c, int rows) { return rows < enc128_min_rows(c) ? 0 : rows <= 32 ? 1 : 2; }
+
 int sdrhip::rx_ragged_room(sdrhip_rx *rx, const size_t *n_in, RxTabs *tabs)
 {
     const int S = rx->nstreams, L = rx->cfg.log2decim;
@@ -661,8 +719,8 @@ int sdrhip::rx_ragged_room(sdrhip_rx *rx, const size_t *n_in, RxTabs *tabs)
     // (only the matrix-core launch of a centred decimation by 4 or more stores straight into the windows)
     const bool may_direct = rx->cfg.fcpos == SDRHIP_FC_CEN && L >= 2 && rx->ctx->opt.rx_direct;
     if (!may_direct && (rc = rx->lin[0].reserve((size_t)S * ((max_dec + 3) & ~(size_t)3) * 4 + 16))) return rc;
-    if (sum_done && rx->cfg.nb_fec > 0) {
-        const size_t nl = (sum_done + GF_FRAMES_PER_GROUP - 1) / GF_FRAMES_PER_GROUP * GF_FRAMES_PER_GROUP;
+    if (sum_done && rx_fec_max(rx) > 0) {
+        const size_t nl = rx_flist_entries(sum_done);
         if ((rc = (tabs ? tabs->flist : rx->r_flist_pin).reserve(nl * 4))) return rc;
         if ((rc = rx->r_flist.reserve(nl * 4))) return rc;
     }
@@ -677,9 +735,11 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
                       const FecBufState *follow)
 {
     sdrhip_ctx *c = rx->ctx;
-    const int S = rx->nstreams, L = rx->cfg.log2decim, R = rx->cfg.nb_fec;
+    // (per-stream fecblk: FB = the slot pitch, 128 + the largest count; a frame of stream s holds rx_stream_blocks(rx, s) of them)
+    const int S = rx->nstreams, L = rx->cfg.log2decim, R = rx_fec_max(rx);
     const size_t FB = (size_t)SDRHIP_NB_ORIGINAL + (size_t)R;
     const size_t frame_bytes = FB * SDRHIP_UDPSIZE;
+    const bool mixed = rx_fec_mixed(rx);
     for (int s = 0; s < S; ++s) n_frames[s] = 0;
     // ---- everything that can be refused is checked before anything is consumed
     if (int e = check_mem(mem)) return e;
@@ -697,19 +757,20 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
     std::vector<RxAdvance> adv((size_t)S);
     std::vector<size_t> done((size_t)S);
     std::vector<uint64_t> rest((size_t)S);
-    size_t max_done = 0, sum_done = 0, max_dec = 0;
+    size_t max_done = 0, sum_done = 0, max_dec = 0, max_row = 0; // max_row: the longest dense delivery of a stream
     for (int s = 0; s < S; ++s) {
         const size_t n_dec = n_in[s] >> L;
         adv[(size_t)s] = rx->area.advance((size_t)s, n_dec);
         done[(size_t)s] = adv[(size_t)s].done;
         rest[(size_t)s] = adv[(size_t)s].rest;
         if (done[(size_t)s] > max_done) max_done = done[(size_t)s];
+        if (done[(size_t)s] * rx_stream_bytes(rx, (size_t)s) > max_row) max_row = done[(size_t)s] * rx_stream_bytes(rx, (size_t)s);
         if (n_dec > max_dec) max_dec = n_dec;
         sum_done += done[(size_t)s];
     }
     if (max_done && !frames_out && mem != SDRHIP_MEM_DEVICE) return fail(SDRHIP_EINVAL, "rx_process_ragged: NULL frames_out");
-    if (frames_out && S > 1 && max_done && frame_stride_bytes < max_done * frame_bytes)
-        return fail(SDRHIP_EINVAL, "rx_process_ragged: frame stride too small for the stream with the most frames (%zu)", max_done);
+    if (frames_out && S > 1 && max_done && frame_stride_bytes < max_row)
+        return fail(SDRHIP_EINVAL, "rx_process_ragged: frame stride too small: the longest stream's frames take %zu bytes (%zu frames at most)", max_row, max_done);
     HIP_TRY(hipSetDevice(c->device));
     rx->consumed = false;
     if (max_in == 0) { // nothing arrives: nothing changes, nothing is delivered
@@ -740,6 +801,7 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
         r.frame_sample_base = A.pending((size_t)s);
         r.fc = sw ? sw[s * STREAM_META_WORDS] : mw[0]; r.rate = sw ? sw[s * STREAM_META_WORDS + 1] : mw[1];
         r.crc0 = sw ? sw[s * STREAM_META_WORDS + 2] : mw[5];
+        r.w2 = sw ? rx->sm_w2[(size_t)s] : mw[2];
         if (a.started > 0 && (n_in[s] >> L)) {
             r.meta_first = a.first_new; r.meta_count = a.started;
             r.frame_count0 = a.frame_count0;
@@ -751,9 +813,9 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
     if ((rc = ragged_prepare(rx->dec, L, rx->cfg.fcpos, n_in, rows.data(), &rdev, tabs ? &tabs->rows : nullptr))) return rc;
     if (follow) {
         // KF: the streams that have incoming meta get {fc, rate >> L, CRC} from the collector's committed m_outputMeta, in the device
-        // table, behind its upload and in front of K2r, the one kernel that reads a row's three words (the host's rows, `mw` and the
+        // table (over the row's own third word), behind its upload and in front of K2r, the one kernel that reads a row's words (the host's rows, `mw` and the
         // rate handed to the decimator launch stay the configuration's)
-        hipError_t e = launch_rx_follow_meta(follow, const_cast<RaggedRow *>(rdev), mw[2], L, S, c->stream);
+        hipError_t e = launch_rx_follow_meta(follow, const_cast<RaggedRow *>(rdev), L, S, c->stream);
         if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "follow meta launch: %s", hipGetErrorString(e));
     }
 
@@ -813,22 +875,39 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
         if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "frame pack launch: %s", hipGetErrorString(e));
     }
 
-    // ---- FEC: one launch over the completed frames of every stream (a dense list: frame f of stream s = area frame s * cap + slot)
+    // ---- FEC: one launch over the completed frames of every stream (a dense list: frame f of stream s = area frame s * cap + slot).
+    // Per-stream fecblk: recovery row r of CM256 is Cauchy row 128 + r whatever the count, so a frame encoded with R' >= its own
+    // count carries its own encoding in its first rows: the frames are grouped by the form fec_encode_device chooses for their own
+    // count, each group present is ONE launch with the group's largest count (at most three; the surplus rows land in the
+    // unspecified rest of the slot); streams without recovery blocks are left out
     if (sum_done && R > 0) {
-        const size_t nl = (sum_done + GF_FRAMES_PER_GROUP - 1) / GF_FRAMES_PER_GROUP * GF_FRAMES_PER_GROUP;
+        const size_t nl = rx_flist_entries(sum_done);
         PinnedBuf &fpin = tabs ? tabs->flist : rx->r_flist_pin;
         if ((rc = fpin.reserve(nl * 4))) return rc;
         if ((rc = rx->r_flist.reserve(nl * 4))) return rc;
         int32_t *fl = fpin.as<int32_t>();
-        size_t k = 0;
-        for (int s = 0; s < S; ++s)
-            for (size_t f = 0; f < done[(size_t)s]; ++f) fl[k++] = (int32_t)A.index((size_t)s, f);
-        while (k < nl) fl[k++] = -1;
-        HIP_TRY(hipMemcpyAsync(rx->r_flist.p, fl, nl * 4, hipMemcpyHostToDevice, c->stream));
-        fpin.mark(c->stream);
-        if ((rc = fec_encode_device(c, area, frame_bytes, (size_t)S * A.cap(), R, area + (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE,
-                                    frame_bytes, rx->r_flist.as<int32_t>(), (int)(nl / GF_FRAMES_PER_GROUP))))
-            return rc;
+        size_t k = 0, g_first[3], g_count[3];
+        int g_rows[3] = {0, 0, 0};
+        for (int form = 0; form < 3; ++form) {
+            g_first[form] = k;
+            for (int s = 0; s < S; ++s) {
+                const int rs = rx_fec_of(rx, (size_t)s);
+                if (rs <= 0 || !done[(size_t)s] || rx_encode_form(c, rs) != form) continue;
+                g_rows[form] = rs > g_rows[form] ? rs : g_rows[form];
+                for (size_t f = 0; f < done[(size_t)s]; ++f) fl[k++] = (int32_t)A.index((size_t)s, f);
+            }
+            while (k % GF_FRAMES_PER_GROUP) fl[k++] = -1;
+            g_count[form] = k - g_first[form];
+        }
+        if (k > nl) return fail(SDRHIP_EINVAL, "rx_process_ragged: frame list"); // (cannot happen: rx_flist_entries counts three paddings)
+        if (k) {
+            HIP_TRY(hipMemcpyAsync(rx->r_flist.p, fl, k * 4, hipMemcpyHostToDevice, c->stream));
+            fpin.mark(c->stream);
+        }
+        for (int form = 0; form < 3; ++form)
+            if (g_count[form] && (rc = fec_encode_device(c, area, frame_bytes, (size_t)S * A.cap(), g_rows[form], area + (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE,
+                                                         frame_bytes, rx->r_flist.as<int32_t>() + g_first[form], (int)(g_count[form] / GF_FRAMES_PER_GROUP))))
+                return rc;
     }
 
     // ---- delivery: every stream's window (one 2-D copy when the windows line up, else a copy per stream)
@@ -839,7 +918,13 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
         // (the datagram entry's host callers get each stream's own frames and no more: its link traffic is datagrams up, frames down)
         bool same_done = true;
         for (int s = 1; s < S; ++s) same_done = same_done && done[(size_t)s] == done[0];
-        if (same_base && (same_done || !(dev_rows && mem == SDRHIP_MEM_HOST))) {
+        if (mixed) {
+            // per-stream fecblk: each stream's frames dense, 128 + nb_fec[s] super blocks each -- a 2-D copy per stream from the pitched area
+            for (int s = 0; s < S; ++s)
+                if (done[(size_t)s])
+                    HIP_TRY(link_copy2d(c, frames_out + (size_t)s * frame_stride_bytes, rx_stream_bytes(rx, (size_t)s), area + A.index((size_t)s) * frame_bytes,
+                                        frame_bytes, rx_stream_bytes(rx, (size_t)s), done[(size_t)s], kind, c->stream));
+        } else if (same_base && (same_done || !(dev_rows && mem == SDRHIP_MEM_HOST))) {
             HIP_TRY(link_copy2d(c, frames_out, S > 1 ? frame_stride_bytes : max_done * frame_bytes, area + A.slot(0) * frame_bytes, stream_bytes,
                                 max_done * frame_bytes, S, kind, c->stream));
         } else {

@@ -83,7 +83,7 @@ int rx_launch_ragged(sdrhip_rx *rx, sdrhip_rx::Batch &b)
     for (size_t i = 0; i < b.r_cnt.size(); ++i) { packed += b.r_cnt[i]; nseg += b.r_cnt[i] ? 1 : 0; }
     for (int s = 0; s < S; ++s) if (b.r_tot[(size_t)s] > max_t) max_t = b.r_tot[(size_t)s];
     const size_t dstride = (max_t + 7) & ~(size_t)7;
-    const size_t fb = (size_t)(SDRHIP_NB_ORIGINAL + rx->cfg.nb_fec) * SDRHIP_UDPSIZE;
+    const size_t fb = rx_frame_bytes(rx); // (per-stream fecblk: the slot pitch, a bound on every stream's frame)
     // (the frames every stream completes, counted as rx_ragged counts them: the buffers are sized before anything is consumed)
     for (int s = 0; s < S; ++s)
         sum_done += rx->area.advance((size_t)s, b.r_tot[(size_t)s] >> L).done;
@@ -181,7 +181,9 @@ int rx_launch_ragged(sdrhip_rx *rx, sdrhip_rx::Batch &b)
         e = launch_frame_gather(rx->work.as<uint8_t>(), fb, reinterpret_cast<const int32_t *>(rx->a_tab.as<char>() + list_off), nl,
                                 rx->a_frames.as<uint8_t>(), c->stream);
     }
-    if (e == hipSuccess && nl) e = link_copy(c, b.out.p, rx->a_frames.p, nl * fb, hipMemcpyDeviceToHost, c->stream);
+    // (a departure-order batch of frames of different lengths: exactly its datagrams)
+    const size_t down = b.egress && !b.e_blocks.empty() ? b.e_dgrams * SDRHIP_UDPSIZE : nl * fb;
+    if (e == hipSuccess && nl) e = link_copy(c, b.out.p, rx->a_frames.p, down, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipEventRecord(b.done, c->stream);
     if (e != hipSuccess) {
         b.state = 0; // consumed and lost: never replayed
@@ -211,6 +213,7 @@ extern "C" int sdrhip_rx_submit(sdrhip_rx *rx, const int16_t *iq_in, size_t n_in
 {
     if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
     sdrhip::CtxLock lock_(rx->ctx);
+    if (!rx->sf_fec.empty()) return fail(SDRHIP_EINVAL, "rx_submit: per-stream fecblk is set (sdrhip_rx_set_stream_fec): use sdrhip_rx_submit_ragged");
     if (rx->egress) return fail(SDRHIP_EINVAL, "rx_submit: uniform batches have no departure order (sdrhip_rx_set_egress): use sdrhip_rx_submit_ragged with equal counts");
     if (n_in == 0) return SDRHIP_OK;
     if (!iq_in) return fail(SDRHIP_EINVAL, "rx_submit: NULL input");
@@ -312,6 +315,8 @@ extern "C" int sdrhip_rx_submit_ragged(sdrhip_rx *rx, const int16_t *iq_in, cons
         return fail(SDRHIP_EINVAL, "rx_submit_ragged: in_stride is neither SDRHIP_PACKED nor at least the largest count");
     if (sum && !iq_in) return fail(SDRHIP_EINVAL, "rx_submit_ragged: NULL input");
     if (rx->pipelined) return fail(SDRHIP_EINVAL, "rx_submit_ragged: not available in pipelined mode");
+    if (rx_fec_mixed(rx) && !rx->egress)
+        return fail(SDRHIP_EINVAL, "rx_submit_ragged: the streams' fecblk differ (sdrhip_rx_set_stream_fec): such a batch is delivered in departure order only, sdrhip_rx_set_egress first");
     if (rx_dgrams_in_flight(rx)) return fail(SDRHIP_EINVAL, "rx_submit_ragged: asynchronous datagram batches are in flight: sdrhip_rx_collect_datagrams them first");
     if (rx_has_batches(rx, false)) return fail(SDRHIP_EINVAL, "rx_submit_ragged: uniform batches are being filled or in flight: collect them first");
     sdrhip_rx::Batch &b = rx->ring.tail_batch();

@@ -21,16 +21,17 @@ int admit(void *arg, const size_t *n_released)
 {
     const Admit &a = *static_cast<const Admit *>(arg);
     const sdrhip_rx *rx = a.rx;
-    const size_t U = rx_join_unit(rx->cfg), frame_bytes = (size_t)(SDRHIP_NB_ORIGINAL + rx->cfg.nb_fec) * SDRHIP_UDPSIZE;
-    size_t max_done = 0;
+    const size_t U = rx_join_unit(rx->cfg);
+    size_t max_done = 0, max_row = 0; // (per-stream fecblk: a stream's frames are delivered dense, 128 + nb_fec[s] blocks each)
     for (int s = 0; s < rx->nstreams; ++s) {
         const size_t fed = ((*a.carry)[(size_t)s] + n_released[s] * SDRHIP_SAMPLES_PER_FRAME) / U * U;
         const size_t done = rx->area.advance((size_t)s, fed >> rx->cfg.log2decim).done;
         if (done > max_done) max_done = done;
+        if (done * rx_stream_bytes(rx, (size_t)s) > max_row) max_row = done * rx_stream_bytes(rx, (size_t)s);
     }
     if (max_done && !a.frames_out && a.mem != SDRHIP_MEM_DEVICE) return fail(SDRHIP_EINVAL, "rx_process_datagrams: NULL frames_out");
-    if (a.frames_out && rx->nstreams > 1 && max_done && a.frame_stride_bytes < max_done * frame_bytes)
-        return fail(SDRHIP_EINVAL, "rx_process_datagrams: frame stride too small for the stream with the most frames (%zu; nothing was consumed)", max_done);
+    if (a.frames_out && rx->nstreams > 1 && max_done && a.frame_stride_bytes < max_row)
+        return fail(SDRHIP_EINVAL, "rx_process_datagrams: frame stride too small: the longest stream's frames take %zu bytes (%zu frames at most; nothing was consumed)", max_row, max_done);
     return SDRHIP_OK;
 }
 } // namespace

@@ -19,6 +19,8 @@ static int rx_submit_batch(sdrhip_rx *rx, FecBufBatch &in, const uint32_t *tv_se
     const int S = rx->nstreams, L = rx->cfg.log2decim;
     const size_t *n_dgrams = in.n_dgrams;
     if (rx->pipelined) return fail(SDRHIP_EINVAL, "%s: not available in pipelined mode", who);
+    if (rx_fec_mixed(rx) && !rx->egress)
+        return fail(SDRHIP_EINVAL, "%s: the streams' fecblk differ (sdrhip_rx_set_stream_fec): such a batch is delivered in departure order only, sdrhip_rx_set_egress first", who);
     if (rx_has_batches(rx, false) || rx_has_batches(rx, true))
         return fail(SDRHIP_EINVAL, "%s: uniform or ragged batches are being filled or in flight: collect them first", who);
     sdrhip_rx::Batch &b = rx->ring.tail_batch();
@@ -38,9 +40,9 @@ static int rx_submit_batch(sdrhip_rx *rx, FecBufBatch &in, const uint32_t *tv_se
     if ((rc = fecbuf_batch_stage(&in, b.in, b.r_tab, sh, res.data()))) return rc;
     // ---- every count of the batch, from the shadow's release counts and the host's copy of the carry: what each stream feeds its
     // decimator, what it holds back, the frames it completes (as rx_ragged counts them)
-    const size_t U = rx_join_unit(rx->cfg), fb = (size_t)(SDRHIP_NB_ORIGINAL + rx->cfg.nb_fec) * SDRHIP_UDPSIZE;
+    const size_t U = rx_join_unit(rx->cfg), fb = rx_frame_bytes(rx); // (per-stream fecblk: the slot pitch)
     std::vector<size_t> fed((size_t)S), left((size_t)S), nf((size_t)S, 0);
-    size_t kmax = 0, kall = 0, sum_done = 0;
+    size_t kmax = 0, kall = 0, sum_done = 0, b_frames = 0; // b_frames: exactly the delivered bytes, 128 + nb_fec[s] blocks per frame
     bool any = false;
     for (int s = 0; s < S; ++s) {
         const size_t k = (size_t)res[(size_t)s * 4];
@@ -50,9 +52,11 @@ static int rx_submit_batch(sdrhip_rx *rx, FecBufBatch &in, const uint32_t *tv_se
         fed[(size_t)s] = total / U * U;
         left[(size_t)s] = total - fed[(size_t)s];
         any = any || fed[(size_t)s] != 0;
-        sum_done += rx->area.advance((size_t)s, fed[(size_t)s] >> L).done;
+        const size_t done = rx->area.advance((size_t)s, fed[(size_t)s] >> L).done;
+        sum_done += done;
+        b_frames += done * rx_stream_bytes(rx, (size_t)s);
     }
-    const size_t b_frames = sum_done * fb, b_total = b_frames + kall * DG_REC;
+    const size_t b_total = b_frames + kall * DG_REC;
     const size_t seg_bytes = (size_t)2 * S * sizeof(RxDeliverSeg);
     // everything that can fail for want of memory comes before the collector moves (a device buffer that grows waits for the
     // batches in flight; the rows keep their heads): the batch's own buffers, then what the ragged step takes for these counts
@@ -105,7 +109,7 @@ static int rx_submit_batch(sdrhip_rx *rx, FecBufBatch &in, const uint32_t *tv_se
         if (!nf[(size_t)s]) continue;
         RxDeliverSeg &g = seg[nseg++];
         g.src = rx->view.offset((size_t)s, fb);
-        g.bytes = nf[(size_t)s] * fb; g.dst = dst; g.from_records = 0;
+        g.bytes = nf[(size_t)s] * rx_stream_bytes(rx, (size_t)s); g.dst = dst; g.from_records = 0; // (= fb unless the counts differ: departure order only)
         dst += g.bytes;
     }
     hipError_t e = dst == b_frames ? hipSuccess : hipErrorInvalidValue; // (cannot differ: the count above is the pipe's own)

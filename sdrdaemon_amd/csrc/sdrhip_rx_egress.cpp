@@ -15,6 +15,29 @@ namespace {
 // KE's table: the record places (16 bytes each) in front, so that they are 16-byte aligned whatever the number of runs behind them
 size_t egress_table_bytes(size_t frames, size_t S) { return S * sizeof(RxEgressRecPlace) + frames * sizeof(RxEgressRun); }
 
+// ... KR's, for a batch whose streams' frames differ in length (per-stream fecblk)
+size_t depart_table_bytes(size_t runs, size_t S) { return S * sizeof(RxEgressRecPlace) + runs * sizeof(RxDepartRun); }
+// the runs of such a batch at most: a frame each, and every stream's end cuts at most one frame of each other stream -- of the
+// streams that deliver at all, min(S, frames) of them (quadratic in that number: 24 bytes a run, pinned per ring slot and on the device)
+size_t depart_runs_bound(size_t frames, size_t S)
+{
+    const size_t live = frames < S ? frames : S;
+    return frames + (live ? live * (live - 1) : 0);
+}
+
+// the record places of a datagram batch, in front of either table; returns the records of the batch
+uint32_t record_places(RxEgressRecPlace *place, size_t S, const int *released, size_t kmax)
+{
+    uint32_t pre = 0;
+    for (size_t s = 0; s < S; ++s) {
+        place[s].pre = pre;
+        place[s].cnt = released && kmax ? (uint32_t)released[s * 4] : 0;
+        place[s].pad[0] = place[s].pad[1] = 0;
+        pre += place[s].cnt;
+    }
+    return pre;
+}
+
 // the batch the caller holds (state 3) is free again
 void release_lent(sdrhip_rx *rx)
 {
@@ -25,12 +48,20 @@ void release_lent(sdrhip_rx *rx)
 
 int sdrhip::rx_egress_room(sdrhip_rx *rx, sdrhip_rx::Batch &b, size_t frames, size_t blocks_per_frame)
 {
-    const size_t S = (size_t)rx->nstreams, bytes = egress_table_bytes(frames, S) + 16;
+    // (per-stream fecblk with differing counts: KR's longer table; blocks_per_frame = the slot pitch bounds the tags)
+    const size_t S = (size_t)rx->nstreams;
+    const bool mixed = rx_fec_mixed(rx);
+    const size_t bytes = (mixed ? depart_table_bytes(depart_runs_bound(frames, S), S) : egress_table_bytes(frames, S)) + 16;
     int rc;
     if ((rc = b.e_tab.reserve(bytes))) return rc; // (waits for the table upload of this slot's last use)
     if ((rc = reserve_settled(rx->ctx, rx->e_tab, bytes))) return rc;
     try {
         b.e_tags.resize(frames * blocks_per_frame);
+        // what the slot's previous batch left goes here, where the batch is launched: a batch that completes no frame never reaches
+        // rx_egress_launch.  The batch keeps the counts it is launched with
+        b.e_dgrams = 0;
+        b.e_blocks.resize(mixed ? S : 0);
+        for (size_t s = 0; s < b.e_blocks.size(); ++s) b.e_blocks[s] = rx_stream_blocks(rx, s);
     } catch (const std::bad_alloc &) {
         return fail(SDRHIP_ENOMEM, "rx egress: %zu tags", frames * blocks_per_frame);
     }
@@ -42,6 +73,44 @@ hipError_t sdrhip::rx_egress_launch(sdrhip_rx *rx, sdrhip_rx::Batch &b, const si
 {
     sdrhip_ctx *c = rx->ctx;
     const size_t S = (size_t)rx->nstreams, B = frame_bytes / SDRHIP_UDPSIZE;
+    if (!b.e_blocks.empty()) { // (rx_egress_room: the streams' counts differ)
+        // ---- frames of different lengths: the runs of rx_depart_order.h, moved by KR (frame_bytes = the area's slot pitch)
+        RxDepartOrder &d = rx->e_depart;
+        std::vector<uint64_t> src0;
+        try {
+            src0.assign(S, 0);
+            if (!d.plan(n_frames, b.e_blocks.data(), S)) return hipErrorInvalidValue;
+        } catch (const std::bad_alloc &) {
+            return hipErrorOutOfMemory;
+        }
+        size_t frames = 0;
+        for (size_t s = 0; s < S; ++s) {
+            frames += n_frames[s];
+            if (n_frames[s]) src0[s] = rx->view.offset(s, frame_bytes);
+        }
+        // (cannot differ: rx_egress_room was given the pipe's own count of these frames, and the bound on their runs)
+        if (d.nruns() > depart_runs_bound(frames, S) || depart_table_bytes(d.nruns(), S) > b.e_tab.cap || d.dgrams() > b.e_tags.size()) return hipErrorInvalidValue;
+        RxEgressRecPlace *place = b.e_tab.as<RxEgressRecPlace>();
+        if (!d.runs(src0.data(), frame_bytes, reinterpret_cast<RxDepartRun *>(place + S))) return hipErrorInvalidValue;
+        b.e_tags.resize((size_t)d.dgrams()); // (never grows)
+        d.tags(b.e_tags.data());
+        b.e_dgrams = (size_t)d.dgrams();
+        const uint32_t pre = record_places(place, S, released, kmax);
+        if (!d.nruns() && !pre) return hipSuccess;
+        if (kmax > 0xffffffffu / S) return hipErrorInvalidValue;
+        hipError_t e = hipMemcpyAsync(rx->e_tab.p, b.e_tab.p, depart_table_bytes(d.nruns(), S), hipMemcpyHostToDevice, c->stream); // (not counted: a table)
+        if (e != hipSuccess) return e;
+        b.e_tab.mark(c->stream);
+        RxEgressRecords rec;
+        rec.place = rx->e_tab.as<RxEgressRecPlace>();
+        rec.records = records;
+        rec.dst = d.dgrams() * SDRHIP_UDPSIZE;
+        rec.kmax = (uint32_t)kmax;
+        rec.nslots = pre ? (uint32_t)(S * kmax) : 0;
+        KTimer kt(c, SDRHIP_K_CONVERT);
+        return launch_rx_runs(reinterpret_cast<const RxDepartRun *>(rec.place + S), d.nruns(), d.wg_per_run(), rx->work.as<uint8_t>(),
+                              rx->a_frames.as<uint8_t>(), rec, c->stream);
+    }
     RxEgressOrder &o = rx->e_order;
     std::vector<uint64_t> src0;
     try {
@@ -59,13 +128,8 @@ hipError_t sdrhip::rx_egress_launch(sdrhip_rx *rx, sdrhip_rx::Batch &b, const si
     if (!o.runs(src0.data(), runs)) return hipErrorInvalidValue;
     b.e_tags.resize((size_t)o.dgrams()); // (never grows)
     o.tags(b.e_tags.data());
-    uint32_t pre = 0;
-    for (size_t s = 0; s < S; ++s) {
-        place[s].pre = pre;
-        place[s].cnt = released && kmax ? (uint32_t)released[s * 4] : 0;
-        place[s].pad[0] = place[s].pad[1] = 0;
-        pre += place[s].cnt;
-    }
+    const uint32_t pre = record_places(place, S, released, kmax);
+    b.e_dgrams = (size_t)o.dgrams();
     if (!o.frames() && !pre) return hipSuccess;
     if (kmax > 0xffffffffu / S) return hipErrorInvalidValue;
     const size_t bytes = egress_table_bytes(o.frames(), S);
@@ -131,7 +195,9 @@ extern "C" int sdrhip_rx_collect_egress(sdrhip_rx *rx, sdrhip_rx_egress *out, si
         }
         return fail(SDRHIP_EINVAL, "rx_collect_egress: %s (most records %zu; the batch stays)", why, most_rel);
     }
-    const size_t B = b.frame_bytes / SDRHIP_UDPSIZE, n = all * B;
+    // (per-stream fecblk with differing counts: blocks_per_frame = 0, sdrhip_rx_egress_stream_blocks has each stream's)
+    const bool each = !b.e_blocks.empty();
+    const size_t B = each ? 0 : b.frame_bytes / SDRHIP_UDPSIZE, n = each ? b.e_dgrams : all * B;
     // the records alone are copied (16 bytes per released frame); the datagrams and the tags are lent where they lie
     const uint8_t *rec = b.out.as<uint8_t>() + n * SDRHIP_UDPSIZE;
     for (int s = 0; s < S; ++s) {
@@ -152,6 +218,18 @@ extern "C" int sdrhip_rx_collect_egress(sdrhip_rx *rx, sdrhip_rx_egress *out, si
     ++rx->ring.head;
     if (was_dg) fecbuf_set_async_busy(rx->fb, rx_dgrams_in_flight(rx));
     return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_rx_egress_stream_blocks(const sdrhip_rx *rx, size_t *blocks)
+{
+    if (!rx || !blocks) return fail(SDRHIP_EINVAL, "rx_egress_stream_blocks: NULL argument");
+    sdrhip::CtxLock lock_(rx->ctx);
+    for (const auto &b : rx->ring.v) {
+        if (b.state != 3) continue;
+        for (size_t s = 0; s < (size_t)rx->nstreams; ++s) blocks[s] = b.e_blocks.empty() ? b.frame_bytes / SDRHIP_UDPSIZE : b.e_blocks[s];
+        return SDRHIP_OK;
+    }
+    return fail(SDRHIP_EINVAL, "rx_egress_stream_blocks: no batch is lent (sdrhip_rx_collect_egress)");
 }
 
 extern "C" int sdrhip_rx_release_egress(sdrhip_rx *rx)

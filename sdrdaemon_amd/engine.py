@@ -678,6 +678,8 @@ class RxPipe(_Handle):
         self._log = _BatchLog()  # the asynchronous batches in flight, each with the nb_fec it keeps (the collects size and shape with it)
         self.cfg = RxConfig(log2decim, fcpos, hb_variant, sample_bits, nb_fec, center_frequency_khz, sample_rate)
         self.m_error = ""
+        self._stream_fec = None  # set_stream_fec's array (None: nb_fec is bank-wide)
+        self.last_blocks_per_frame, self.last_stream_blocks = 0, None
         self.m_device_rate = sample_rate << log2decim  # DeviceSource::get_sample_rate(): the sink gets it >> decim
         check(ctx.lib.sdrhip_rx_create(ctx.h, nstreams, C.byref(self.cfg), C.byref(self.h)))
         self.pipelined = bool(pipelined)
@@ -760,6 +762,39 @@ class RxPipe(_Handle):
         fc, sr = C.c_uint32(0), C.c_uint32(0)
         check(self.ctx.lib.sdrhip_rx_get_stream_meta(self.h, int(stream), C.byref(fc), C.byref(sr)))
         return {"center_frequency_khz": fc.value, "sample_rate": sr.value}
+
+    def set_stream_fec(self, nb_fec=None):
+        """Per-stream UDPSink::setNbBlocksFEC (sdrhip_rx_set_stream_fec): a sequence of nstreams counts, each 0..128, for the meta
+        blocks later launches open and the frames they complete; None = bank-wide again (the config's nb_fec).  While it is set
+        process(), submit() and pipelined mode raise, process_ragged / process_datagrams return each stream's frames as its own
+        (n, 128 + nb_fec[s], 512) array, and batches whose counts differ are delivered in departure order only (set_egress).
+        Refused (SdrHipError) in pipelined mode and while batches are being filled, in flight or lent."""
+        arr = None
+        if nb_fec is not None:
+            v = [int(x) for x in nb_fec]
+            if len(v) != self.nstreams:
+                raise ValueError("nb_fec: %d counts, one per stream" % self.nstreams)
+            arr = (C.c_int * self.nstreams)(*v)
+        check(self.ctx.lib.sdrhip_rx_set_stream_fec(self.h, arr))
+        self._stream_fec = None if nb_fec is None else v
+
+    def stream_fec(self, stream):
+        """-> (nb_fec of the stream, slot_blocks = 128 + the largest count: the pitch of the frame area's slots)"""
+        r, sb = C.c_int(0), C.c_int(0)
+        check(self.ctx.lib.sdrhip_rx_get_stream_fec(self.h, int(stream), C.byref(r), C.byref(sb)))
+        return r.value, sb.value
+
+    def _slot_fec(self):
+        """the count that sizes a frame slot and a delivery row: the largest of set_stream_fec's array, else nb_fec"""
+        return max(self._stream_fec) if self._stream_fec else self.nb_fec
+
+    def _stream_frames(self, out, nf):
+        """set_stream_fec's delivery: row s of `out` holds stream s's nf[s] frames dense, 128 + nb_fec[s] super blocks each"""
+        res = []
+        for s, r in enumerate(self._stream_fec):
+            n = int(nf[s]) * (NB_ORIGINAL + r) * UDPSIZE
+            res.append(out[s].reshape(-1)[:n].reshape(int(nf[s]), NB_ORIGINAL + r, UDPSIZE))
+        return res
 
     def set_follow_meta(self, on=True):
         """Outgoing meta from the incoming meta blocks (sdrhip_rx_set_follow_meta), for process_datagrams / submit_datagrams: a
@@ -883,7 +918,7 @@ class RxPipe(_Handle):
             raise ValueError("expected rows (%d, n, 2) or packed samples" % S)
         check(self.ctx.lib.sdrhip_rx_submit_ragged(self.h, _ptr(a), (C.c_size_t * S)(*cnt.tolist()), stride, _stamps(tv_sec, S),
                                                    _stamps(tv_usec, S)))
-        self._log.block("ragged", cnt, self.nb_fec)
+        self._log.block("ragged", cnt, self._slot_fec())
 
     def collect_ragged(self, wait=True, max_frames=None):
         """-> the frames of the oldest ragged batch: a list of S arrays (n_s, 128 + nb_fec, 512), n_s possibly 0; None when no
@@ -947,16 +982,19 @@ class RxPipe(_Handle):
     def process_ragged(self, iq, counts, tv_sec=0, tv_usec=0, out=None):
         """sdrhip_rx_process_ragged: stream s takes counts[s] samples of row s of iq (S, >= max(counts), 2), stamped tv_sec[s] /
         tv_usec[s] (scalars apply to every stream).  -> (frames (S, max_frames, 128 + nb_fec, 512) uint8, n_frames numpy (S,)):
-        stream s's frames are frames[s, :n_frames[s]]."""
+        stream s's frames are frames[s, :n_frames[s]].  With set_stream_fec's array set: (a list of S arrays (n_frames[s],
+        128 + nb_fec[s], 512), n_frames)."""
         x, is_t, _ = self._ragged_input(iq)
         S = x.shape[0]
         cnt, c_cnt, c_sec, c_usec = self._ragged_args(x, counts, tv_sec, tv_usec)
         cap = max(self.max_frames(int(cnt.max()) if S else 0), 1)
-        out, stride_bytes = _frame_buffer(S, cap, self.nb_fec, x.device if is_t else None, out)
+        out, stride_bytes = _frame_buffer(S, cap, self._slot_fec(), x.device if is_t else None, out)
         nf = (C.c_size_t * S)()
         check(self.ctx.lib.sdrhip_rx_process_ragged(self.h, _ptr(x), c_cnt, _stride_samples(x), c_sec, c_usec, _ptr(out),
                                                     stride_bytes, nf, MEM_DEVICE if is_t else MEM_HOST))
         n_frames = np.array(nf[:], dtype=np.int64)
+        if self._stream_fec is not None:
+            return self._stream_frames(out, nf), n_frames
         return out[:, :int(n_frames.max()) if S else 0], n_frames
 
     def frames_view_ragged(self, device="cuda"):
@@ -966,11 +1004,12 @@ class RxPipe(_Handle):
         base, stride = C.c_void_p(0), C.c_size_t(0)
         first, cnt = (C.c_size_t * S)(), (C.c_size_t * S)()
         check(self.ctx.lib.sdrhip_rx_frames_view_ragged(self.h, C.byref(base), C.byref(stride), first, cnt))
-        fb = (NB_ORIGINAL + self.nb_fec) * UDPSIZE
+        fb = (NB_ORIGINAL + self._slot_fec()) * UDPSIZE  # (the slot pitch; with set_stream_fec a frame shows its own 128 + nb_fec[s] blocks)
+        rows = [NB_ORIGINAL + (self._stream_fec[s] if self._stream_fec else self.nb_fec) for s in range(S)]
         dev = torch.device(device)
-        return [_DeviceView((base.value or 0) + s * stride.value + first[s] * fb, (cnt[s], NB_ORIGINAL + self.nb_fec, UDPSIZE),
+        return [_DeviceView((base.value or 0) + s * stride.value + first[s] * fb, (cnt[s], rows[s], UDPSIZE),
                             (fb, UDPSIZE, 1), dev, owner=self).torch() if cnt[s] else
-                torch.empty((0, NB_ORIGINAL + self.nb_fec, UDPSIZE), dtype=torch.uint8, device=dev) for s in range(S)]
+                torch.empty((0, rows[s], UDPSIZE), dtype=torch.uint8, device=dev) for s in range(S)]
 
     def process_view_ragged(self, iq, counts, tv_sec=0, tv_usec=0):
         """Zero-copy ragged call for CUDA tensors: -> (list of S frame tensors as frames_view_ragged, n_frames numpy (S,))"""
@@ -1000,7 +1039,7 @@ class RxPipe(_Handle):
             max_released = max(counts + [0])  # (a call releases at most one frame per datagram)
         F = max(max_released, 1)
         cap = max(self.max_frames(SAMPLES_PER_FRAME * max_released + 63), 1)
-        out, stride_bytes = _frame_buffer(S, cap, self.nb_fec, buf.device if is_t else None)
+        out, stride_bytes = _frame_buffer(S, cap, self._slot_fec(), buf.device if is_t else None)
         info = (FECBufferFrame * (S * F))()
         nd = (C.c_size_t * S)(*counts)
         nr, nf = (C.c_size_t * S)(), (C.c_size_t * S)()
@@ -1008,6 +1047,8 @@ class RxPipe(_Handle):
                                                       max_released, _ptr(out), stride_bytes, info, nr, nf, MEM_DEVICE if is_t else MEM_HOST)
         self.last_n_released = [int(x) for x in nr]
         check(rc)
+        if self._stream_fec is not None:  # (each stream's frames in its own shape, (n, 128 + nb_fec[s], 512))
+            return list(zip(self._stream_frames(out, nf), _records(info, F, nr)))
         return [(out[s, :int(nf[s])], recs) for s, recs in enumerate(_records(info, F, nr))]
 
     # ---- asynchronous datagram batches (sdrhip_rx_submit_datagrams / sdrhip_rx_collect_datagrams)
@@ -1035,7 +1076,7 @@ class RxPipe(_Handle):
 
     def _dg_submitted(self):
         """a datagram batch was submitted (also for callers of the C entry itself): the log's record of it, with the nb_fec it keeps"""
-        self._log.batch("datagram", None, self.nb_fec)
+        self._log.batch("datagram", None, self._slot_fec())
 
     def collect_datagrams(self, wait=True, max_frames=None, max_released=None):
         """the oldest datagram batch: per stream (frames (n, 128 + nb_fec, 512) uint8, records) as process_datagrams returns them, or
@@ -1083,7 +1124,8 @@ class RxPipe(_Handle):
         """the oldest batch launched with an egress order -> (dgrams (n, 512) uint8 in departure order, stream_of (n,) uint16,
         n_frames numpy (S,), records), or None when no batch was collected (nothing submitted, or wait=False and the oldest one is
         in flight).  records: per stream the records of the frames its collector released, as collect_datagrams returns them;
-        None for a ragged batch.  blocks per frame of the batch: last_blocks_per_frame.  copy=False returns views of the memory
+        None for a ragged batch.  blocks per frame of the batch: last_blocks_per_frame -- 0 for a batch whose streams' counts
+        differ (set_stream_fec), last_stream_blocks then lists every stream's (else it is None).  copy=False returns views of the memory
         the library lends -- the batch's pinned download buffer and its tags -- valid until release_egress, the next
         collect_egress or the pipe's destruction; the batch keeps its ring slot meanwhile.  copy=True copies and releases."""
         S = self.nstreams
@@ -1106,6 +1148,11 @@ class RxPipe(_Handle):
         self._log.pop()
         n = int(eg.n_dgrams)
         self.last_blocks_per_frame = int(eg.blocks_per_frame)
+        self.last_stream_blocks = None
+        if n and not self.last_blocks_per_frame:
+            sb = (C.c_size_t * S)()
+            check(self.ctx.lib.sdrhip_rx_egress_stream_blocks(self.h, sb))
+            self.last_stream_blocks = [int(x) for x in sb]
         if n:
             dg = np.ctypeslib.as_array((C.c_uint8 * (n * UDPSIZE)).from_address(eg.dgrams)).reshape(n, UDPSIZE)
             tags = np.ctypeslib.as_array((C.c_uint16 * n).from_address(eg.stream_of))
