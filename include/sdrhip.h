@@ -850,7 +850,9 @@ int sdrhip_tx_reset_streams(sdrhip_tx *tx, const uint8_t *mask);
  * r_pending, r_open and r_count (UDPSinkFEC's sample index, open frame and m_frameCount); the 128 super blocks of the open frame with
  * the meta block it was opened with (UDPSinkFEC.cpp:160-165); a "has collector" flag and, with a collector, the stream's
  * SDRdaemonFECBuffer state, the 128 super blocks of its current carry buffer, and its held-back samples (at most 63) with their
- * count.  A Tx blob holds the interpolator row (Interpolators.h:47-52) and the same collector part.
+ * count.  A Tx blob holds the interpolator row (Interpolators.h:47-52) and the same collector part.  What a stream does not have
+ * is zero -- no open frame, no collector, the carry buffer's rows the open slot has not filled yet, the sample slots behind the
+ * held-back count --: a just-reset stream's blob equals a never-used stream's, byte for byte.
  * Export leaves the source untouched; it synchronises once (one gather launch, one copy of the packed bytes, one wait).
  * Import makes stream `stream` of the destination -- any Rx or Tx bank, on any context, of any nstreams -- continue exactly where
  * the source stream stood: it enqueues ONE upload and ONE scatter launch on the context's stream and does not synchronise (the
@@ -861,7 +863,9 @@ int sdrhip_tx_reset_streams(sdrhip_tx *tx, const uint8_t *mask);
  * frame keeps its meta block and is encoded with the fecblk in force when it completes.  A blob without a collector leaves the
  * stream of a bank that has one with the constructor's collector state.  Import clears the bank-wide "first-stage history fits
  * int16" shortcut when the blob says so, and patches a valid collector shadow as the reset does.  The other streams of both banks
- * run on undisturbed.
+ * run on undisturbed.  An imported stream stands at its own frame position, as a stream does after a partial
+ * sdrhip_rx_reset_streams: unless that position is the other streams' too, sdrhip_rx_process takes its ragged step from then on, and
+ * sdrhip_rx_set_pipelined(1) / sdrhip_rx_submit refuse with SDRHIP_EINVAL, nothing consumed, until a reset of every stream.
  * SDRHIP_EINVAL, nothing changed: a NULL handle or blob; a wrong size, magic, version or kind; a blob of another hb_variant; a
  * stream outside the bank; a blob whose fields no stream can be in; any asynchronous batch being filled or in flight; a
  * pipelined pipe with frames or a batch waiting (flush first).

@@ -151,6 +151,17 @@ int export_run(sdrhip_ctx *c, StreamCopyArgs &a, DevBuf &dev, size_t dev_bytes, 
     return SDRHIP_OK;
 }
 
+// What the open slot has not filled of its carry buffer (ranks from min(count, 128) on) and what lies behind the held-back samples is
+// whatever earlier frames left there: zero in the blob, like every piece the stream does not have -- a reset stream's blob is a
+// never-used stream's, byte for byte.  `part`: the blob's device part, already on the host
+void blank_unused_carry(uint8_t *part, size_t off_st, size_t off_carry)
+{
+    FecBufState st;
+    memcpy(&st, part + off_st, sizeof(st));
+    const size_t n = st.count < 0 ? 0 : st.count > SDRHIP_NB_ORIGINAL ? (size_t)SDRHIP_NB_ORIGINAL : (size_t)st.count;
+    memset(part + off_carry + n * SDRHIP_UDPSIZE, 0, ((size_t)SDRHIP_NB_ORIGINAL - n) * SDRHIP_UDPSIZE);
+}
+
 // the collector's pieces of a gather: the committed state, the carry buffer it names (picked on the device)
 void gather_collector(sdrhip_fecbuf *fb, int s, uint8_t *dev, size_t off_st, size_t off_carry, StreamCopyArgs *a)
 {
@@ -243,6 +254,11 @@ extern "C" int sdrhip_rx_export_stream(sdrhip_rx *rx, int stream, void *blob, si
     }
     uint8_t *out = static_cast<uint8_t *>(blob);
     if ((rc = export_run(c, a, rx->x_blob, RX_DEV_BYTES, out + RX_HOST_BYTES))) return rc;
+    if (h.has_collector) {
+        blank_unused_carry(out + RX_HOST_BYTES, RX_ST, RX_CARRY);
+        const size_t held = h.carry > 63 ? HELD_BYTES : (size_t)h.carry * 4;
+        memset(out + RX_HOST_BYTES + RX_HELD + held, 0, HELD_BYTES - held);
+    }
     const BlobHead head = {BLOB_MAGIC, BLOB_VERSION, BLOB_RX, (uint32_t)RX_BLOB_BYTES};
     memcpy(out, &head, sizeof(head));
     memcpy(out + sizeof(head), &h, sizeof(h));
@@ -331,6 +347,7 @@ extern "C" int sdrhip_tx_export_stream(sdrhip_tx *tx, int stream, void *blob, si
     }
     uint8_t *out = static_cast<uint8_t *>(blob);
     if ((rc = export_run(c, a, tx->x_blob, TX_DEV_BYTES, out + TX_HOST_BYTES))) return rc;
+    if (h.has_collector) blank_unused_carry(out + TX_HOST_BYTES, TX_ST, TX_CARRY);
     const BlobHead head = {BLOB_MAGIC, BLOB_VERSION, BLOB_TX, (uint32_t)TX_BLOB_BYTES};
     memcpy(out, &head, sizeof(head));
     memcpy(out + sizeof(head), &h, sizeof(h));
