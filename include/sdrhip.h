@@ -179,6 +179,14 @@ int sdrhip_decimate(sdrhip_decimators *d, int log2decim, int fcpos, unsigned *sa
  * *sampleSize advances as in sdrhip_decimate. */
 int sdrhip_decimate_ragged(sdrhip_decimators *d, int log2decim, int fcpos, unsigned *sampleSize, const int16_t *iq_in,
                            const size_t *n_in, size_t in_stride, int16_t *iq_out, size_t out_stride, size_t *n_out, int mem);
+/* sdrhip_decimate_ragged with sampleSize an ARRAY of nstreams entries (each 1..16), read and advanced per stream: in the
+ * reference every sdrdaemonrx process hands its own source's get_sample_bits() to Downsampler::process (sdrdaemonrx.cpp:619-620,
+ * 639-640; RtlSdrSource.cpp:549 and HackRFSource.cpp:669 say 8), and the size enters a cascade in one place only, the final
+ * `x << norm_shift >> trunk_shift` in front of the int16 truncation (Decimators.cpp:27-32, 43-44, 52-53, 62 and every decimateN).
+ * Stream s gets the samples of a one-stream bank called with sampleSize[s]; the same launch as sdrhip_decimate_ragged serves the
+ * call (each stream's shift pair travels in its row of the per-call table).  Everything else as sdrhip_decimate_ragged. */
+int sdrhip_decimate_ragged_bits(sdrhip_decimators *d, int log2decim, int fcpos, unsigned *sampleSize, const int16_t *iq_in,
+                                const size_t *n_in, size_t in_stride, int16_t *iq_out, size_t out_stride, size_t *n_out, int mem);
 
 /* ------------------------------------------------------------ interpolators -- */
 /* Bank of `Interpolators` objects (Interpolators.h:35-61): HB64, HB32, 4 x HB16 states. */
@@ -329,7 +337,8 @@ int sdrhip_rx_get_stream_meta(const sdrhip_rx *rx, int stream, uint32_t *center_
  *     flag off: the sdrhip_rx_set_stream_meta arrays, else the configuration.
  *  4. a frame left open by an earlier call keeps the block 0 it was opened with (UDPSinkFEC.cpp:160-165).
  *  5. sampleBytes, sampleBits, nbOriginalBlocks, nbFECBlocks and the stamps stay the hub's own: the reference stamps a frame with
- *     gettimeofday where it is opened (UDPSinkFEC.cpp:90-104), so the caller's tv_sec / tv_usec arrays remain right.
+ *     gettimeofday where it is opened (UDPSinkFEC.cpp:90-104), so the caller's tv_sec / tv_usec arrays remain right.  (With
+ *     sdrhip_rx_set_stream_fec / sdrhip_rx_set_stream_bits arrays "the hub's own" count and sample size are the stream's own.)
  *  6. sdrhip_rx_get_stream_meta keeps reporting the host's values.
  * The values are formed on the device between the collector and the step (one small launch per call or batch); nothing about them
  * comes back to the host, and a submit still synchronises nothing.  With the flag off every entry launches exactly what it launched
@@ -805,6 +814,42 @@ int sdrhip_rx_release_egress(sdrhip_rx *rx);
 int sdrhip_rx_set_stream_fec(sdrhip_rx *rx, const int *nb_fec);
 int sdrhip_rx_get_stream_fec(const sdrhip_rx *rx, int stream, int *nb_fec, int *slot_blocks);
 int sdrhip_rx_egress_stream_blocks(const sdrhip_rx *rx, size_t *blocks);
+
+/* ---- Per-stream sample bits: 8-, 12- and 16-bit radios in one bank.
+ * In the reference the sample size is per process, that is per stream: srcsdr->get_sample_bits() goes into Downsampler::process /
+ * rescale (sdrdaemonrx.cpp:619-620, 639-640) and, as the decimator returns it, into UDPSink::setSampleBits / setSampleBytes
+ * (sdrdaemonrx.cpp:622-623, 642-643).  RTL-SDR and HackRF heads say 8 (RtlSdrSource.cpp:549, HackRFSource.cpp:669), Airspy and
+ * BladeRF 12, the test source 16.  The size changes the last operation of a cascade alone -- `x << norm_shift >> trunk_shift` in
+ * front of the int16 truncation (Decimators.cpp:27-32, 43-44, 52-53, 62 and every decimateN) -- and two bytes of the meta block.
+ * sdrhip_rx_set_stream_bits: sample_bits = host array of nstreams entries, each 1..16; NULL = bank-wide again (cfg.sample_bits).
+ * sdrhip_rx_get_stream_bits: either pointer may be NULL; *sample_bits = the stream's size, *frame_bits = what the next frame the
+ * stream opens says in its sampleBits byte.
+ * Contract.  Per stream the result is byte for byte that of a one-stream sdrhip_rx whose config carries sample_bits[s]: the sample
+ * values, bytes 8 (sampleBytes = (bits' - 1) / 8 + 1) and 9 (sampleBits = bits') of the meta block with bits' the size the
+ * decimator returns for (log2decim, sample_bits[s]), the CRC over them, the recovery blocks computed over that block 0.  A later
+ * call acts on stream s exactly like sdrhip_rx_reconfigure with the new sample_bits on that one-stream pipe at the same point: the
+ * frame being filled keeps the meta block it was opened with (UDPSinkFEC.cpp:160-165), samples decimated from then on take the
+ * new shift.
+ * The config: while the array is set cfg.sample_bits is unused; sdrhip_rx_reconfigure does not clear the array, and neither does
+ * sdrhip_rx_reset_streams; export and import of a stream are untouched (the bits are configuration: the destination's apply).  A
+ * log2decim change through sdrhip_rx_reconfigure changes every stream's frame_bits by the same rule.
+ * Entries: while the array is set every step is the ragged step: sdrhip_rx_process, sdrhip_rx_submit and
+ * sdrhip_rx_set_pipelined(1) return SDRHIP_EINVAL with nothing consumed.  An array of equal entries is allowed and delivers the
+ * bytes of that bank-wide value.  It holds through sdrhip_rx_process_ragged, sdrhip_rx_submit_ragged / _collect_ragged,
+ * sdrhip_rx_process_datagrams, sdrhip_rx_submit_datagrams[_tagged] / _collect_datagrams and sdrhip_rx_collect_egress, and
+ * together with the stream meta arrays, follow meta (whose rule 5 then speaks of the stream's own size) and the fecblk array in
+ * any combination; the rules for differing fecblk (departure order only) stand as they are.
+ * The setter changes host arrays alone: nothing is enqueued, nothing waited for.  It is allowed at any time, also with batches in
+ * flight; a batch takes the values when it takes its sdrhip_rx_config (the rule of sdrhip_rx_set_stream_meta).  It is refused,
+ * nothing changed, for a NULL handle, a value outside 1..16, a pipelined pipe or one with late frames waiting.  A handle on which
+ * the setter was never called launches the same kernels in the same order with the same results.
+ * How: every ragged launch takes the shift pair from its stream's row of the per-call table (one word) instead of the launch
+ * arguments -- the filter-less kernel, K1r and K1mr, which keep their registers and occupancy -- and the row's third meta word
+ * carries sampleBytes / sampleBits per stream, so K2r and KF form block 0 and its CRC as they did.
+ * Not covered: following sampleBits from the incoming meta blocks, a per-stream input format (sdrhip_rx_set_input_format stays
+ * bank-wide), the uniform step and pipelined mode, the Tx pipe. */
+int sdrhip_rx_set_stream_bits(sdrhip_rx *rx, const unsigned *sample_bits);
+int sdrhip_rx_get_stream_bits(const sdrhip_rx *rx, int stream, unsigned *sample_bits, unsigned *frame_bits);
 
 /* ---- Per-stream lifecycle: one stream of a bank begins again while the others run on.
  * In the reference one stream is one sdrdaemonrx / sdrdaemontx process, and restarting that process gives the stream what the

@@ -657,6 +657,10 @@ __device__ __forceinline__ DecimArgs mf_ragged_args(const DecimArgs &a, const Ra
     DecimArgs b = a;
     b.n_used = (size_t)r.n_used;
     b.mf_wps = r.mf_wps;
+    // the stream's own output shift, for its waves and its pieces.  (The readfirstlane pins the pair to scalar registers, where the
+    // uniform kernel's argument words live: without it every instantiation takes two more VGPRs, profiles/rx_stream_bits_ab.txt)
+    const unsigned sh = (unsigned)__builtin_amdgcn_readfirstlane((int)r.shifts);
+    b.norm = (int)(sh & 0xffu); b.trunk = (int)(sh >> 8);
     if (a.frame_mode) {
         b.out = reinterpret_cast<int16_t *>(reinterpret_cast<unsigned *>(a.out) + r.out_off);
         b.frame_sample_base = r.frame_sample_base;

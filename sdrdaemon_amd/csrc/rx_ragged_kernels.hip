@@ -33,6 +33,9 @@ template <int L, int FC, bool PACK16> __global__ __launch_bounds__(NT) void deci
     }
     const int s = lo, seg = b - rows[s].seg0;
     const size_t n_used = (size_t)rows[s].n_used;
+    // the stream's own output shift (RaggedRow::shifts; workgroup-uniform like the row's other fields: scalar registers)
+    const unsigned sh = rows[s].shifts;
+    a.norm = (int)(sh & 0xffu); a.trunk = (int)(sh >> 8);
     const size_t seg_raw = (size_t)a.nsub_per_seg * PRAW;
     const int nseg = n_used ? (int)((n_used + seg_raw - 1) / seg_raw) : 1;
     const size_t seg_start = (size_t)seg * seg_raw;
@@ -47,12 +50,14 @@ template <int L, int FC, bool PACK16> hipError_t launch_ragged_variant(const Dec
     return hipGetLastError();
 }
 
-// ragged calls: stream s takes rows[s].n_raw samples
+// ragged calls: stream s takes rows[s].n_raw samples and shifts its output by its own pair (RaggedRow::shifts; the two shift
+// arguments are kept for the signature and not read)
 __global__ void decim_simple_ragged_kernel(int log2decim, int fcpos, const int16_t *in, size_t in_stride, int16_t *out,
-                                           size_t out_stride, int norm, int trunk, const RaggedRow *rows)
+                                           size_t out_stride, int, int, const RaggedRow *rows)
 {
     const int s = (int)blockIdx.y;
-    decim_simple_row(log2decim, fcpos, in, in_stride, out, out_stride, (size_t)rows[s].n_raw, norm, trunk, s);
+    const unsigned sh = rows[s].shifts;
+    decim_simple_row(log2decim, fcpos, in, in_stride, out, out_stride, (size_t)rows[s].n_raw, (int)(sh & 0xffu), (int)(sh >> 8), s);
 }
 
 // K2r: the stream's own count, window, frame base and meta record from its row of the per-call table

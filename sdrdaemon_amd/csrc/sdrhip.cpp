@@ -510,16 +510,13 @@ int decimate_device(sdrhip_decimators *d, int log2decim, int fcpos, unsigned *sa
         d->last = DecimPlanInfo(); // (no cascade launch: last_plan reports path 0, not the previous call's plan)
         if (n_in == 0) return SDRHIP_OK;
         if (frame_mode) return fail(SDRHIP_EINVAL, "internal: frame mode needs log2decim >= 1");
-        int norm = ss < 16 ? (int)(16 - ss) : 0;
-        hipError_t e = launch_decimate_simple(0, fcpos, in, in_stride, out, out_stride, n_in, d->nstreams, norm, 0, c->stream);
+        hipError_t e = launch_decimate_simple(0, fcpos, in, in_stride, out, out_stride, n_in, d->nstreams, (int)decimated_shifts(0, ss).norm, 0, c->stream);
         if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "decimate1 launch: %s", hipGetErrorString(e));
         return SDRHIP_OK;
     }
-    const unsigned target = 16 - L; // Decimators.cpp:43-44, 132-133, 222-223 ...
-    const unsigned trunk = ss < target ? 0 : ss - target;
-    const unsigned norm = ss < target ? target - ss : 0;
+    const unsigned norm = decimated_shifts(L, ss).norm, trunk = decimated_shifts(L, ss).trunk; // Decimators.cpp:43-44, 132-133, 222-223 ...
     const size_t n_resize = n_in >> L; // out.resize(len / N)
-    *sampleSize = ss + L - trunk;
+    *sampleSize = decimated_sample_size(L, ss);
     if (n_out) *n_out = n_resize;
     d->last = DecimPlanInfo(); // (set below when a cascade kernel is launched; filter-less and empty calls report path 0)
     if (n_resize == 0) return SDRHIP_OK; // (the reference's unsigned loop bound would wrap here)
@@ -728,7 +725,6 @@ int decimate_ragged_device(sdrhip_decimators *d, int log2decim, int fcpos, unsig
     sdrhip_ctx *c = d->ctx;
     const int S = d->nstreams;
     const unsigned L = (unsigned)log2decim;
-    const unsigned ss = *sampleSize;
     size_t max_raw = 0, max_dec = 0, min_used = SIZE_MAX;
     for (int s = 0; s < S; ++s) {
         if (rows[s].n_raw > max_raw) max_raw = (size_t)rows[s].n_raw;
@@ -738,18 +734,15 @@ int decimate_ragged_device(sdrhip_decimators *d, int log2decim, int fcpos, unsig
     d->last = DecimPlanInfo();
     if (L == 0) {
         if (max_raw == 0) return SDRHIP_OK;
-        const int norm = ss < 16 ? (int)(16 - ss) : 0;
-        hipError_t e = launch_decimate_simple_ragged(0, fcpos, in, in_stride, out, out_stride, max_raw, S, norm, 0, rows_dev, c->stream);
+        hipError_t e = launch_decimate_simple_ragged(0, fcpos, in, in_stride, out, out_stride, max_raw, S, 0, 0, rows_dev, c->stream);
         if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "decimate1 launch: %s", hipGetErrorString(e));
         return SDRHIP_OK;
     }
-    const unsigned target = 16 - L;
-    const unsigned trunk = ss < target ? 0 : ss - target;
-    const unsigned norm = ss < target ? target - ss : 0;
-    *sampleSize = ss + L - trunk;
+    // (every stream's size advances as in sdrhip_decimate, whatever its count; the shifts went up with the rows: RaggedRow::shifts)
+    for (int s = 0; s < S; ++s) sampleSize[s] = decimated_sample_size(L, sampleSize[s]);
     if (max_dec == 0) return SDRHIP_OK; // (no stream has a whole output sample: nothing enters any history)
     if (fcpos != SDRHIP_FC_CEN && L <= 2) {
-        hipError_t e = launch_decimate_simple_ragged((int)L, fcpos, in, in_stride, out, out_stride, max_raw, S, (int)norm, (int)trunk, rows_dev, c->stream);
+        hipError_t e = launch_decimate_simple_ragged((int)L, fcpos, in, in_stride, out, out_stride, max_raw, S, 0, 0, rows_dev, c->stream);
         if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "decimate%u launch: %s", 1u << L, hipGetErrorString(e));
         return SDRHIP_OK;
     }
@@ -760,7 +753,7 @@ int decimate_ragged_device(sdrhip_decimators *d, int log2decim, int fcpos, unsig
     a.in = in; a.out = out; a.in_stride = in_stride; a.out_stride = out_stride;
     a.state_cur = d->state[d->cur]; a.state_next = d->state[d->cur ^ 1];
     a.nstreams = S;
-    a.bias = d->bias; a.norm = (int)norm; a.trunk = (int)trunk;
+    a.bias = d->bias; // (a.norm / a.trunk stay 0: the ragged kernels take each stream's pair from its row)
     a.nsub_per_seg = d->r_nsub; a.nseg = d->r_grid;
     a.frame_mode = frame_mode; a.frame_blocks = frame_blocks; a.meta_rate = meta_rate;
     if (meta_w) memcpy(a.meta_w, meta_w, sizeof(a.meta_w));
@@ -812,14 +805,14 @@ int ragged_stage_in(sdrhip_ctx *c, PinnedBuf &pin, DevBuf &dev, const void *src,
 }
 } // namespace sdrhip
 
-extern "C" int sdrhip_decimate_ragged(sdrhip_decimators *d, int log2decim, int fcpos, unsigned *sampleSize, const int16_t *iq_in,
-                                      const size_t *n_in, size_t in_stride, int16_t *iq_out, size_t out_stride, size_t *n_out, int mem)
+// sampleSize: one entry per stream (sdrhip_decimate_ragged hands in nstreams copies of its one value)
+static int decimate_ragged_sizes(sdrhip_decimators *d, int log2decim, int fcpos, unsigned *sampleSize, const int16_t *iq_in,
+                                 const size_t *n_in, size_t in_stride, int16_t *iq_out, size_t out_stride, size_t *n_out, int mem)
 {
-    if (!d || !sampleSize || !n_in || !n_out) return fail(SDRHIP_EINVAL, "decimate_ragged: NULL handle, sampleSize or count array");
-    sdrhip::CtxLock lock_(d->ctx);
     if (log2decim < 0 || log2decim > 6) return fail(SDRHIP_EINVAL, "Invalid log2 decimation factor");
     if (fcpos < SDRHIP_FC_INF || fcpos > SDRHIP_FC_CEN) return fail(SDRHIP_EINVAL, "Invalid Fc position index");
-    if (*sampleSize < 1 || *sampleSize > 16) return fail(SDRHIP_EINVAL, "sampleSize must be 1..16");
+    for (int s = 0; s < d->nstreams; ++s)
+        if (sampleSize[s] < 1 || sampleSize[s] > 16) return fail(SDRHIP_EINVAL, "sampleSize must be 1..16");
     if (int e = check_mem(mem)) return e;
     sdrhip_ctx *c = d->ctx;
     const int S = d->nstreams;
@@ -837,9 +830,10 @@ extern "C" int sdrhip_decimate_ragged(sdrhip_decimators *d, int log2decim, int f
     for (int s = 0; s < S; ++s) n_out[s] = n_in[s] >> log2decim;
     if (max_in == 0) { // nothing to stage; sampleSize advances as in sdrhip_decimate
         d->last = DecimPlanInfo();
-        if (log2decim > 0) { const unsigned t = 16u - (unsigned)log2decim, ss = *sampleSize; *sampleSize = ss + (unsigned)log2decim - (ss < t ? 0 : ss - t); }
+        for (int s = 0; s < S; ++s) sampleSize[s] = decimated_sample_size((unsigned)log2decim, sampleSize[s]);
         return SDRHIP_OK;
     }
+    for (int s = 0; s < S; ++s) rows[(size_t)s].shifts = ragged_shift_word((unsigned)log2decim, sampleSize[s]);
     const RaggedRow *rdev = nullptr;
     int rc = ragged_prepare(d, log2decim, fcpos, n_in, rows.data(), &rdev);
     if (rc) return rc;
@@ -860,4 +854,24 @@ extern "C" int sdrhip_decimate_ragged(sdrhip_decimators *d, int log2decim, int f
     for (int s = 0; s < S; ++s)
         if (n_out[s]) memcpy(iq_out + (size_t)s * out_stride * 2, d->out_pin.as<char>() + (size_t)s * dos * 4, n_out[s] * 4);
     return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_decimate_ragged(sdrhip_decimators *d, int log2decim, int fcpos, unsigned *sampleSize, const int16_t *iq_in,
+                                      const size_t *n_in, size_t in_stride, int16_t *iq_out, size_t out_stride, size_t *n_out, int mem)
+{
+    if (!d || !sampleSize || !n_in || !n_out) return fail(SDRHIP_EINVAL, "decimate_ragged: NULL handle, sampleSize or count array");
+    sdrhip::CtxLock lock_(d->ctx);
+    std::vector<unsigned> sizes((size_t)d->nstreams, *sampleSize);
+    const int rc = decimate_ragged_sizes(d, log2decim, fcpos, sizes.data(), iq_in, n_in, in_stride, iq_out, out_stride, n_out, mem);
+    *sampleSize = sizes[0];
+    return rc;
+}
+
+// every sdrdaemonrx hands ITS source's get_sample_bits() to Downsampler::process (sdrdaemonrx.cpp:619-620, 639-640): a size per stream
+extern "C" int sdrhip_decimate_ragged_bits(sdrhip_decimators *d, int log2decim, int fcpos, unsigned *sampleSize, const int16_t *iq_in,
+                                           const size_t *n_in, size_t in_stride, int16_t *iq_out, size_t out_stride, size_t *n_out, int mem)
+{
+    if (!d || !sampleSize || !n_in || !n_out) return fail(SDRHIP_EINVAL, "decimate_ragged_bits: NULL handle, sampleSize array or count array");
+    sdrhip::CtxLock lock_(d->ctx);
+    return decimate_ragged_sizes(d, log2decim, fcpos, sampleSize, iq_in, n_in, in_stride, iq_out, out_stride, n_out, mem);
 }

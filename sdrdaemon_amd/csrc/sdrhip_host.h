@@ -75,6 +75,22 @@ inline unsigned decimated_sample_size(unsigned log2decim, unsigned ss)
     const unsigned target = 16 - log2decim, trunk = ss < target ? 0 : ss - target;
     return ss + log2decim - trunk;
 }
+// ... and the output shift that gets it there, the one place the sample size enters a cascade: `x << norm >> trunk` in front of the
+// int16 truncation (Decimators.cpp:27-32 decimate1: norm = 16 - ss; :43-44, 52-53, 62 and every decimateN: up to 16 - log2decim bits
+// by norm, beyond them by trunk)
+struct DecimShifts { unsigned norm, trunk; };
+inline DecimShifts decimated_shifts(unsigned log2decim, unsigned ss)
+{
+    const unsigned target = 16 - log2decim;
+    const DecimShifts r = {ss < target ? target - ss : 0, ss < target ? 0 : ss - target};
+    return r;
+}
+// the pair as a ragged launch's rows carry it (RaggedRow::shifts)
+inline unsigned ragged_shift_word(unsigned log2decim, unsigned ss)
+{
+    const DecimShifts sh = decimated_shifts(log2decim, ss);
+    return sh.norm | (sh.trunk << 8);
+}
 
 // device-pointer cores (no argument validation, no staging)
 int decimate_device(sdrhip_decimators *d, int log2decim, int fcpos, unsigned *sampleSize, const int16_t *in, size_t n_in,

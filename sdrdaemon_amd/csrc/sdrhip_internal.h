@@ -218,7 +218,12 @@ struct RaggedRow {
     uint64_t mf_head, mf_tail_start;
     unsigned fc, rate, crc0;    // K2r: the stream's centre frequency, sample rate and zero-stamp CRC (stream_meta_base<true>)
     unsigned w2;                // K2r, KF: word 2 of the stream's record -- sampleBytes, sampleBits, 128, nbFECBlocks (per-stream fecblk)
+    // K1r, K1mr, the filter-less kernel: the stream's final `<< norm >> trunk` (Decimators.cpp:27-32, 43-44), norm | trunk << 8
+    // (ragged_shift_word, sdrhip_host.h).  Every ragged launch reads the pair here, not in DecimArgs: the bank-wide pair in every row
+    // unless the streams' sample sizes differ (sdrhip_rx_set_stream_bits, sdrhip_decimate_ragged_bits).  One word: the row stays 128 bytes
+    unsigned shifts;
 };
+static_assert(sizeof(RaggedRow) == 128, "RaggedRow: one 128-byte row per stream");
 // K1mr: plans the matrix-core launch of a ragged call (per-stream fields of `rows`, shared span / grid in `a`: a->mf_wps = the
 // launch's matrix-core waves, a->mf_npieces = its VALU pieces); false when no stream is long enough for a span
 bool plan_decimate_mfma_ragged(int log2decim, int fcpos, RaggedRow *rows, int nstreams, size_t span_override, int n_cu, DecimArgs *a);
@@ -227,7 +232,8 @@ hipError_t launch_decimate_mfma_ragged(int log2decim, bool pack16, const DecimAr
 // whose seg0 range holds it (binary search over `rows`).  A stream with n_used = 0 copies its state.  a.nsub_per_seg is the
 // segment length; a.n_used / a.nseg are ignored, a.nseg carries the grid size.
 hipError_t launch_decimate_ragged(int log2decim, int fcpos, bool pack16, const DecimArgs &a, const RaggedRow *rows, hipStream_t stream);
-// filter-less kernel with per-stream counts n_raw (grid planned for the largest, n_in)
+// filter-less kernel with per-stream counts n_raw (grid planned for the largest, n_in); norm / trunk are kept for the signature and
+// not read: like K1r and K1mr it shifts each stream by its row's pair (RaggedRow::shifts)
 hipError_t launch_decimate_simple_ragged(int log2decim, int fcpos, const int16_t *in, size_t in_stride, int16_t *out,
                                          size_t out_stride, size_t n_in, int nstreams, int norm, int trunk, const RaggedRow *rows,
                                          hipStream_t stream);

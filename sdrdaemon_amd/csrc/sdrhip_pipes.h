@@ -184,7 +184,7 @@ struct sdrhip_rx {
     // NOT occupy -- launches in flight keep the table they were enqueued with, a deferred encode (late.k) keeps its pointer
     std::vector<uint32_t> sm_fc, sm_rate; // empty: the field is bank-wide (cfg's value)
     uint64_t sm_version = 0;              // counts the setter's calls
-    struct SmKey { uint64_t version; unsigned w2, fc, rate; } sm_key = {~(uint64_t)0, 0, 0, 0};
+    struct SmKey { uint64_t version; unsigned w2, fc, rate; int log2decim; } sm_key = {~(uint64_t)0, 0, 0, 0, 0};
     std::vector<unsigned> sm_words;
     bool sm_uploaded = false;             // sm_dev[sm_dev_sel] holds sm_words
     sdrhip::PinnedBuf sm_pin[4];
@@ -196,6 +196,9 @@ struct sdrhip_rx {
     // (sampleBytes, sampleBits, 128, nbFECBlocks), formed with sm_words
     std::vector<int> sf_fec;
     std::vector<unsigned> sm_w2;
+    // ---- per-stream sample size (sdrhip_rx_set_stream_bits): empty = bank-wide (cfg.sample_bits).  While it is set every step is the
+    // ragged step: a stream's size enters its row's output shift (RaggedRow::shifts) and, decimated, bytes 8 and 9 of its record (sm_w2)
+    std::vector<unsigned> sb_bits;
     // ---- datagram entry (sdrhip_rx_process_datagrams): one SDRdaemonFECBuffer per stream, created on first use; it delivers into
     // j_rows ([nstreams][j_row_len] samples, the ragged step's input), behind the samples each row holds back from earlier calls
     // (their counts live with the collector: fecbuf_join_carry)
@@ -295,6 +298,8 @@ inline bool rx_fec_mixed(const sdrhip_rx *rx)
         if (rx->sf_fec[s] != rx->sf_fec[0]) return true;
     return false;
 }
+// per-stream sample size: the size of stream s as its source delivers it (the decimator's input)
+inline unsigned rx_bits_of(const sdrhip_rx *rx, size_t s) { return rx->sb_bits.empty() ? rx->cfg.sample_bits : rx->sb_bits[s]; }
 // bytes of a slot of the frame area (the ONE pitch), and of the valid super blocks of a frame of stream s
 inline size_t rx_frame_bytes(const sdrhip_rx *rx) { return (size_t)(SDRHIP_NB_ORIGINAL + rx_fec_max(rx)) * SDRHIP_UDPSIZE; }
 inline size_t rx_stream_blocks(const sdrhip_rx *rx, size_t s) { return (size_t)(SDRHIP_NB_ORIGINAL + rx_fec_of(rx, s)); }

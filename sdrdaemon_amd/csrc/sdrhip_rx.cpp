@@ -60,6 +60,7 @@ extern "C" int sdrhip_rx_set_pipelined(sdrhip_rx *rx, int on)
     sdrhip::CtxLock lock_(rx->ctx);
     if (!on && rx->late.have) return fail(SDRHIP_EINVAL, "rx_set_pipelined: sdrhip_rx_flush the waiting frames first");
     if (on && !rx->sf_fec.empty()) return fail(SDRHIP_EINVAL, "rx_set_pipelined: per-stream fecblk is set (sdrhip_rx_set_stream_fec): every step is the ragged step");
+    if (on && !rx->sb_bits.empty()) return fail(SDRHIP_EINVAL, "rx_set_pipelined: per-stream sample bits are set (sdrhip_rx_set_stream_bits): every step is the ragged step");
     if (on && rx_dgrams_in_flight(rx)) return fail(SDRHIP_EINVAL, "rx_set_pipelined: asynchronous datagram batches are in flight: collect them first");
     if (on && !rx->area.aligned()) return fail(SDRHIP_EINVAL, "rx_set_pipelined: ragged calls left the streams at different frame positions");
     rx->pipelined = on ? 1 : 0;
@@ -394,26 +395,60 @@ extern "C" int sdrhip_rx_get_stream_fec(const sdrhip_rx *rx, int stream, int *nb
     return SDRHIP_OK;
 }
 
+// ---- per-stream sample size (sdrdaemonrx.cpp:619-623, 639-643: every sdrdaemonrx hands its own source's get_sample_bits() to its
+// Downsampler and, decimated, to UDPSink::setSampleBits / setSampleBytes).  Host arrays alone, like sdrhip_rx_set_stream_meta
+extern "C" int sdrhip_rx_set_stream_bits(sdrhip_rx *rx, const unsigned *sample_bits)
+{
+    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
+    sdrhip::CtxLock lock_(rx->ctx);
+    const size_t S = (size_t)rx->nstreams;
+    if (rx->pipelined || rx->late.have) return fail(SDRHIP_EINVAL, "rx_set_stream_bits: not available in pipelined mode");
+    if (sample_bits)
+        for (size_t s = 0; s < S; ++s)
+            if (sample_bits[s] < 1 || sample_bits[s] > 16) return fail(SDRHIP_EINVAL, "rx_set_stream_bits: sample_bits[%zu] = %u, must be 1..16", s, sample_bits[s]);
+    try {
+        if (sample_bits) rx->sb_bits.assign(sample_bits, sample_bits + S);
+        else rx->sb_bits.clear();
+    } catch (const std::bad_alloc &) {
+        return fail(SDRHIP_ENOMEM, "out of host memory"); // (assign into too small a vector allocates first: the old values stand)
+    }
+    ++rx->sm_version; // (the streams' records carry the size: formed again by the next launch)
+    return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_rx_get_stream_bits(const sdrhip_rx *rx, int stream, unsigned *sample_bits, unsigned *frame_bits)
+{
+    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
+    sdrhip::CtxLock lock_(rx->ctx);
+    if (stream < 0 || stream >= rx->nstreams) return fail(SDRHIP_EINVAL, "rx_get_stream_bits: stream %d of %d", stream, rx->nstreams);
+    const unsigned b = rx_bits_of(rx, (size_t)stream);
+    if (sample_bits) *sample_bits = b;
+    if (frame_bits) *frame_bits = decimated_sample_size((unsigned)rx->cfg.log2decim, b);
+    return SDRHIP_OK;
+}
+
 // the streams' records for the frames the next launch opens: [nstreams][STREAM_META_WORDS] = {fc, rate, CRC of the zero-stamp
-// record}; NULL while neither array is set (the shared record of rx_meta_base serves every stream).  Formed again only when the
-// arrays or the configuration words that enter the record have changed
+// record}; NULL while no array is set (the shared record of rx_meta_base serves every stream).  Formed again only when the
+// arrays or the configuration words that enter the record have changed.  ssd = the bank-wide decimated sample size; while the
+// sample-size array is set each stream's record carries its own (decimated by cfg.log2decim, which is why the key holds that too)
 static const unsigned *rx_stream_words(sdrhip_rx *rx, unsigned ssd)
 {
-    if (rx->sm_fc.empty() && rx->sm_rate.empty() && rx->sf_fec.empty()) return nullptr;
+    if (rx->sm_fc.empty() && rx->sm_rate.empty() && rx->sf_fec.empty() && rx->sb_bits.empty()) return nullptr;
     unsigned w[6];
     rx_meta_base(rx->cfg, ssd, w);
-    const sdrhip_rx::SmKey key = {rx->sm_version, w[2], w[0], w[1]};
+    const sdrhip_rx::SmKey key = {rx->sm_version, w[2], w[0], w[1], rx->cfg.log2decim};
     const sdrhip_rx::SmKey &old = rx->sm_key;
-    if (key.version != old.version || key.w2 != old.w2 || key.fc != old.fc || key.rate != old.rate) {
+    if (key.version != old.version || key.w2 != old.w2 || key.fc != old.fc || key.rate != old.rate || key.log2decim != old.log2decim) {
         const size_t S = (size_t)rx->nstreams;
         rx->sm_words.resize(S * STREAM_META_WORDS);
         rx->sm_w2.resize(S);
         for (size_t s = 0; s < S; ++s) {
             rx_meta_record(rx->sm_fc.empty() ? rx->cfg.center_frequency_khz : rx->sm_fc[s],
-                           rx->sm_rate.empty() ? rx->cfg.sample_rate : rx->sm_rate[s], rx_fec_of(rx, s), ssd, w);
+                           rx->sm_rate.empty() ? rx->cfg.sample_rate : rx->sm_rate[s], rx_fec_of(rx, s),
+                           rx->sb_bits.empty() ? ssd : decimated_sample_size((unsigned)rx->cfg.log2decim, rx->sb_bits[s]), w);
             unsigned *t = &rx->sm_words[s * STREAM_META_WORDS];
             t[0] = w[0]; t[1] = w[1]; t[2] = w[5];
-            rx->sm_w2[s] = w[2]; // (the ragged rows' fourth word: the stream's own nbFECBlocks byte)
+            rx->sm_w2[s] = w[2]; // (the ragged rows' fourth word: the stream's own sampleBytes, sampleBits and nbFECBlocks bytes)
         }
         rx->sm_key = key;
         rx->sm_uploaded = false;
@@ -473,6 +508,7 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
     sdrhip::CtxLock lock_(rx->ctx);
     if (n_frames) *n_frames = 0;
     if (!rx->sf_fec.empty()) return fail(SDRHIP_EINVAL, "rx_process: per-stream fecblk is set (sdrhip_rx_set_stream_fec): use sdrhip_rx_process_ragged");
+    if (!rx->sb_bits.empty()) return fail(SDRHIP_EINVAL, "rx_process: per-stream sample bits are set (sdrhip_rx_set_stream_bits): use sdrhip_rx_process_ragged");
     if (rx_has_batches(rx, true)) return fail(SDRHIP_EINVAL, "rx_process: ragged batches are being filled or in flight: collect them first");
     if (rx_dgrams_in_flight(rx)) return fail(SDRHIP_EINVAL, "rx_process: asynchronous datagram batches are in flight: collect them first");
     if (n_in && !rx->area.aligned()) {
@@ -788,10 +824,11 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
     uint8_t *area = rx->work.as<uint8_t>();
 
     // ---- the per-call table: counts (decimator), windows and meta records (K2r)
-    unsigned ss = rx->cfg.sample_bits;
+    std::vector<unsigned> ss((size_t)S); // (each stream's own size: sdrhip_rx_set_stream_bits, else the bank's)
+    for (int s = 0; s < S; ++s) ss[(size_t)s] = rx_bits_of(rx, (size_t)s);
     unsigned mw[6]; // (the record with a zero stamp; the stamps go per row, and so do fc, rate and the CRC: sdrhip_rx_set_stream_meta)
-    rx_meta_base(rx->cfg, decimated_sample_size((unsigned)L, ss), mw);
-    const unsigned *sw = rx_stream_words(rx, decimated_sample_size((unsigned)L, ss));
+    rx_meta_base(rx->cfg, decimated_sample_size((unsigned)L, rx->cfg.sample_bits), mw);
+    const unsigned *sw = rx_stream_words(rx, decimated_sample_size((unsigned)L, rx->cfg.sample_bits));
     std::vector<RaggedRow> rows((size_t)S);
     memset(rows.data(), 0, rows.size() * sizeof(RaggedRow));
     for (int s = 0; s < S; ++s) {
@@ -802,6 +839,7 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
         r.fc = sw ? sw[s * STREAM_META_WORDS] : mw[0]; r.rate = sw ? sw[s * STREAM_META_WORDS + 1] : mw[1];
         r.crc0 = sw ? sw[s * STREAM_META_WORDS + 2] : mw[5];
         r.w2 = sw ? rx->sm_w2[(size_t)s] : mw[2];
+        r.shifts = ragged_shift_word((unsigned)L, ss[(size_t)s]);
         if (a.started > 0 && (n_in[s] >> L)) {
             r.meta_first = a.first_new; r.meta_count = a.started;
             r.frame_count0 = a.frame_count0;
@@ -847,11 +885,11 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
     const size_t lstride = (max_dec + 3) & ~(size_t)3;
     DevBuf &lin = rx->lin[0];
     if (direct) {
-        rc = decimate_ragged_device(rx->dec, L, rx->cfg.fcpos, &ss, din, dstride, reinterpret_cast<int16_t *>(area), stream_bytes / 4,
+        rc = decimate_ragged_device(rx->dec, L, rx->cfg.fcpos, ss.data(), din, dstride, reinterpret_cast<int16_t *>(area), stream_bytes / 4,
                                     rows.data(), rdev, 1, (int)FB, mw, rx->cfg.sample_rate);
     } else {
         if ((rc = lin.reserve((size_t)S * lstride * 4 + 16))) return rc;
-        rc = decimate_ragged_device(rx->dec, L, rx->cfg.fcpos, &ss, din, dstride, lin.as<int16_t>(), lstride, rows.data(), rdev);
+        rc = decimate_ragged_device(rx->dec, L, rx->cfg.fcpos, ss.data(), din, dstride, lin.as<int16_t>(), lstride, rows.data(), rdev);
     }
     if (rc) return rc;
     rx->consumed = true;

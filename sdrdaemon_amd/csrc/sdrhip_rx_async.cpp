@@ -214,6 +214,7 @@ extern "C" int sdrhip_rx_submit(sdrhip_rx *rx, const int16_t *iq_in, size_t n_in
     if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
     sdrhip::CtxLock lock_(rx->ctx);
     if (!rx->sf_fec.empty()) return fail(SDRHIP_EINVAL, "rx_submit: per-stream fecblk is set (sdrhip_rx_set_stream_fec): use sdrhip_rx_submit_ragged");
+    if (!rx->sb_bits.empty()) return fail(SDRHIP_EINVAL, "rx_submit: per-stream sample bits are set (sdrhip_rx_set_stream_bits): use sdrhip_rx_submit_ragged");
     if (rx->egress) return fail(SDRHIP_EINVAL, "rx_submit: uniform batches have no departure order (sdrhip_rx_set_egress): use sdrhip_rx_submit_ragged with equal counts");
     if (n_in == 0) return SDRHIP_OK;
     if (!iq_in) return fail(SDRHIP_EINVAL, "rx_submit: NULL input");

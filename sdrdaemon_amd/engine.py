@@ -408,7 +408,9 @@ class Decimators(_Handle):
 
     def decimate_ragged(self, log2decim, fcpos, sample_size, iq, counts, out=None):
         """sdrhip_decimate_ragged: stream s decimates counts[s] samples of row s of iq (S, >= max(counts), 2).
-        Returns (out (S, max(counts) >> log2decim, 2) -- row s valid up to n_out[s] --, n_out (numpy, S), new_sample_size)."""
+        Returns (out (S, max(counts) >> log2decim, 2) -- row s valid up to n_out[s] --, n_out (numpy, S), new_sample_size).
+        sample_size: one size for the bank, or a sequence of one size per stream (sdrhip_decimate_ragged_bits: stream s is
+        shifted for its own size); new_sample_size then is the list of the streams' new sizes."""
         x, is_t, _ = _bank_view(iq, self.nstreams)
         S, n = x.shape[0], x.shape[1]
         cnt = _counts(counts, S, n)
@@ -418,12 +420,20 @@ class Decimators(_Handle):
             out = _padded_rows(S, n_res, 4, torch.int16, x.device, zero=True) if is_t else np.zeros((S, n_res, 2), dtype=np.int16)
         if is_t and S > 1 and (x.stride(0) // 2) % 4:
             raise ValueError("device bank input: per-stream stride must be a multiple of 4 samples")
-        ss = C.c_uint(sample_size)
         n_out = (C.c_size_t * S)()
-        check(self.ctx.lib.sdrhip_decimate_ragged(self.h, log2decim, fcpos, C.byref(ss), _ptr(x), (C.c_size_t * S)(*cnt.tolist()),
-                                                  _stride_samples(x), _ptr(out), _stride_samples(out) if S > 1 else n_res, n_out,
-                                                  MEM_DEVICE if is_t else MEM_HOST))
-        return out, np.array(n_out[:], dtype=np.int64), ss.value
+        per_stream = not isinstance(sample_size, (int, np.integer))
+        if per_stream:
+            sizes = [int(b) for b in sample_size]
+            if len(sizes) != S:
+                raise ValueError("sample_size: %d sizes, one per stream" % S)
+            ss = (C.c_uint * S)(*sizes)
+            entry, ssp = self.ctx.lib.sdrhip_decimate_ragged_bits, ss
+        else:
+            ss = C.c_uint(sample_size)
+            entry, ssp = self.ctx.lib.sdrhip_decimate_ragged, C.byref(ss)
+        check(entry(self.h, log2decim, fcpos, ssp, _ptr(x), (C.c_size_t * S)(*cnt.tolist()), _stride_samples(x), _ptr(out),
+                    _stride_samples(out) if S > 1 else n_res, n_out, MEM_DEVICE if is_t else MEM_HOST))
+        return out, np.array(n_out[:], dtype=np.int64), (list(ss) if per_stream else ss.value)
 
     def last_plan(self):
         """what the last cascade launch was (sdrhip_decimators_last_plan): dict with path ('valu' / 'mfma' / None), span, wps, ..."""
@@ -783,6 +793,25 @@ class RxPipe(_Handle):
         r, sb = C.c_int(0), C.c_int(0)
         check(self.ctx.lib.sdrhip_rx_get_stream_fec(self.h, int(stream), C.byref(r), C.byref(sb)))
         return r.value, sb.value
+
+    def set_stream_bits(self, bits=None):
+        """Per-stream sample size (sdrhip_rx_set_stream_bits): a sequence of nstreams sizes, each 1..16 -- what every stream's
+        source says in get_sample_bits() -- for the samples later launches decimate and the meta blocks they open; None = bank-wide
+        again (the config's sample_bits).  While it is set process(), submit() and pipelined mode raise.  Never synchronises;
+        refused (SdrHipError) in pipelined mode."""
+        arr = None
+        if bits is not None:
+            v = [int(x) for x in bits]
+            if len(v) != self.nstreams or any(x < 0 for x in v):
+                raise ValueError("bits: %d sizes, one per stream" % self.nstreams)
+            arr = (C.c_uint * self.nstreams)(*v)
+        check(self.ctx.lib.sdrhip_rx_set_stream_bits(self.h, arr))
+
+    def stream_bits(self, stream):
+        """-> (bits of the stream, frame_bits = the sampleBits byte of the next frame it opens)"""
+        b, fb = C.c_uint(0), C.c_uint(0)
+        check(self.ctx.lib.sdrhip_rx_get_stream_bits(self.h, int(stream), C.byref(b), C.byref(fb)))
+        return b.value, fb.value
 
     def _slot_fec(self):
         """the count that sizes a frame slot and a delivery row: the largest of set_stream_fec's array, else nb_fec"""
