@@ -1,6 +1,7 @@
 // sdrhip_host.h -- host-side internals shared by the .cpp files of libsdrhip.so
 #pragma once
 #include "../../include/sdrhip.h"
+#include "rx_stream_settings.h" // (the sample-size arithmetic of the decimators lives there: decimated_sample_size, decimated_shifts, ragged_shift_word)
 #include "sdrhip_internal.h"
 
 #include <cstdint>
@@ -67,30 +68,6 @@ struct RxMeta {
     unsigned rate; // sample rate the stamps advance with (Hz, 0 = none)
     const unsigned *tab; // per-stream {fc, rate, zero-stamp CRC} on the device (DecimArgs::meta_tab), NULL: w / rate serve every stream
 };
-
-// sampleSize after decimateN (Decimators.cpp:43-44, 112-113 ...): grows by log2decim, capped at 16 bits
-inline unsigned decimated_sample_size(unsigned log2decim, unsigned ss)
-{
-    if (log2decim == 0) return ss;
-    const unsigned target = 16 - log2decim, trunk = ss < target ? 0 : ss - target;
-    return ss + log2decim - trunk;
-}
-// ... and the output shift that gets it there, the one place the sample size enters a cascade: `x << norm >> trunk` in front of the
-// int16 truncation (Decimators.cpp:27-32 decimate1: norm = 16 - ss; :43-44, 52-53, 62 and every decimateN: up to 16 - log2decim bits
-// by norm, beyond them by trunk)
-struct DecimShifts { unsigned norm, trunk; };
-inline DecimShifts decimated_shifts(unsigned log2decim, unsigned ss)
-{
-    const unsigned target = 16 - log2decim;
-    const DecimShifts r = {ss < target ? target - ss : 0, ss < target ? 0 : ss - target};
-    return r;
-}
-// the pair as a ragged launch's rows carry it (RaggedRow::shifts)
-inline unsigned ragged_shift_word(unsigned log2decim, unsigned ss)
-{
-    const DecimShifts sh = decimated_shifts(log2decim, ss);
-    return sh.norm | (sh.trunk << 8);
-}
 
 // device-pointer cores (no argument validation, no staging)
 int decimate_device(sdrhip_decimators *d, int log2decim, int fcpos, unsigned *sampleSize, const int16_t *in, size_t n_in,

@@ -1,9 +1,11 @@
 // sdrhip_pipes.h -- the fused Rx / Tx pipes of include/sdrhip.h: their handles, the ring of asynchronous batches and what the
 // units sdrhip_rx.cpp, sdrhip_rx_async.cpp, sdrhip_rx_datagrams.cpp, sdrhip_rx_datagrams_async.cpp, sdrhip_tx.cpp and
-// sdrhip_tx_async.cpp share
+// sdrhip_tx_async.cpp share.  The Rx pipe's host decisions live in headers of their own: rx_frame_area.h (windows),
+// rx_stream_settings.h (per-stream settings, the counts of a ragged step and of a join), rx_depart_order.h (departure order)
 #pragma once
 #include "rx_depart_order.h"
 #include "rx_frame_area.h"
+#include "rx_stream_settings.h"
 #include "sdrhip_host.h"
 
 #include <cstring>
@@ -177,28 +179,17 @@ struct sdrhip_rx {
     // ---- ragged calls (sdrhip_rx_process_ragged)
     sdrhip::PinnedBuf r_pin, r_flist_pin; // host-row staging and the encoder's frame list
     sdrhip::DevBuf r_flist;
-    // ---- per-stream centre frequency / sample rate (sdrhip_rx_set_stream_meta).  The setter touches the host arrays alone; the
-    // next launch forms the streams' records (sm_words: {fc, rate, zero-stamp CRC} per stream, for the configuration in sm_key).
-    // Ragged launches carry them in their row table.  Uniform launches read a device table: a change goes up in front of the
-    // launch, on the context's stream, from the next of four pinned versions into the device table the previous version does
-    // NOT occupy -- launches in flight keep the table they were enqueued with, a deferred encode (late.k) keeps its pointer
-    std::vector<uint32_t> sm_fc, sm_rate; // empty: the field is bank-wide (cfg's value)
-    uint64_t sm_version = 0;              // counts the setter's calls
-    struct SmKey { uint64_t version; unsigned w2, fc, rate; int log2decim; } sm_key = {~(uint64_t)0, 0, 0, 0, 0};
-    std::vector<unsigned> sm_words;
-    bool sm_uploaded = false;             // sm_dev[sm_dev_sel] holds sm_words
+    // ---- per-stream centre frequency / sample rate, fecblk and sample size (sdrhip_rx_set_stream_meta / _fec / _bits): the arrays,
+    // what they force and the streams' records are rx_stream_settings.h's; a setter touches the host arrays alone, the next launch
+    // forms the records.  Ragged launches carry them in their row table.  Uniform launches read a device table: a change goes up in
+    // front of the launch, on the context's stream, from the next of four pinned versions into the device table the previous version
+    // does NOT occupy -- launches in flight keep the table they were enqueued with, a deferred encode (late.k) keeps its pointer.
+    // Per-stream fecblk: the frame area keeps ONE slot pitch, 128 + the largest count (rx_frame_bytes), a frame of stream s holds
+    // rx_stream_blocks(rx, s) valid super blocks at the head of its slot
+    sdrhip::RxStreamSettings streams;
     sdrhip::PinnedBuf sm_pin[4];
     sdrhip::DevBuf sm_dev[2];
     int sm_pin_sel = 0, sm_dev_sel = 0;
-    // ---- per-stream fecblk (sdrhip_rx_set_stream_fec): empty = bank-wide (cfg.nb_fec).  While it is set every step is the ragged
-    // step; the frame area keeps ONE slot pitch, 128 + the largest count (rx_frame_bytes), a frame of stream s holds
-    // rx_stream_blocks(rx, s) valid super blocks at the head of its slot.  sm_w2 = word 2 of each stream's zero-stamp record
-    // (sampleBytes, sampleBits, 128, nbFECBlocks), formed with sm_words
-    std::vector<int> sf_fec;
-    std::vector<unsigned> sm_w2;
-    // ---- per-stream sample size (sdrhip_rx_set_stream_bits): empty = bank-wide (cfg.sample_bits).  While it is set every step is the
-    // ragged step: a stream's size enters its row's output shift (RaggedRow::shifts) and, decimated, bytes 8 and 9 of its record (sm_w2)
-    std::vector<unsigned> sb_bits;
     // ---- datagram entry (sdrhip_rx_process_datagrams): one SDRdaemonFECBuffer per stream, created on first use; it delivers into
     // j_rows ([nstreams][j_row_len] samples, the ragged step's input), behind the samples each row holds back from earlier calls
     // (their counts live with the collector: fecbuf_join_carry)
@@ -283,27 +274,40 @@ struct sdrhip_tx {
 
 namespace sdrhip {
 static_assert(RX_FRAME_SAMPLES == SDRHIP_SAMPLES_PER_FRAME, "rx_frame_area.h frames the header's frame");
-// per-stream fecblk: the count of stream s, the largest of the bank, and whether two streams differ
-inline int rx_fec_of(const sdrhip_rx *rx, size_t s) { return rx->sf_fec.empty() ? rx->cfg.nb_fec : rx->sf_fec[s]; }
-inline int rx_fec_max(const sdrhip_rx *rx)
+static_assert(RX_NB_ORIGINAL == SDRHIP_NB_ORIGINAL && RX_UDPSIZE == SDRHIP_UDPSIZE && RX_STREAM_WORDS == STREAM_META_WORDS, "rx_stream_settings.h");
+// the bank-wide values rx_stream_settings.h resolves against, and its answers for this pipe: the count and the sample size of
+// stream s (as its source delivers it: the decimator's input), the largest count, whether two differ; bytes of a slot of the frame
+// area (the ONE pitch) and of the valid super blocks of a frame of stream s
+inline RxBankValues rx_bank(const sdrhip_rx *rx)
 {
-    if (rx->sf_fec.empty()) return rx->cfg.nb_fec;
-    int m = 0;
-    for (size_t s = 0; s < rx->sf_fec.size(); ++s) m = rx->sf_fec[s] > m ? rx->sf_fec[s] : m;
-    return m;
+    const RxBankValues b = {rx->cfg.center_frequency_khz, rx->cfg.sample_rate, rx->cfg.nb_fec, (unsigned)rx->cfg.sample_bits, rx->cfg.log2decim};
+    return b;
 }
-inline bool rx_fec_mixed(const sdrhip_rx *rx)
-{
-    for (size_t s = 1; s < rx->sf_fec.size(); ++s)
-        if (rx->sf_fec[s] != rx->sf_fec[0]) return true;
-    return false;
-}
-// per-stream sample size: the size of stream s as its source delivers it (the decimator's input)
-inline unsigned rx_bits_of(const sdrhip_rx *rx, size_t s) { return rx->sb_bits.empty() ? rx->cfg.sample_bits : rx->sb_bits[s]; }
-// bytes of a slot of the frame area (the ONE pitch), and of the valid super blocks of a frame of stream s
-inline size_t rx_frame_bytes(const sdrhip_rx *rx) { return (size_t)(SDRHIP_NB_ORIGINAL + rx_fec_max(rx)) * SDRHIP_UDPSIZE; }
-inline size_t rx_stream_blocks(const sdrhip_rx *rx, size_t s) { return (size_t)(SDRHIP_NB_ORIGINAL + rx_fec_of(rx, s)); }
+inline int rx_fec_of(const sdrhip_rx *rx, size_t s) { return rx->streams.fec(rx_bank(rx), s); }
+inline int rx_fec_max(const sdrhip_rx *rx) { return rx->streams.fec_max(rx_bank(rx)); }
+inline bool rx_fec_mixed(const sdrhip_rx *rx) { return rx->streams.fec_mixed(); }
+inline unsigned rx_bits_of(const sdrhip_rx *rx, size_t s) { return rx->streams.bits(rx_bank(rx), s); }
+inline size_t rx_frame_bytes(const sdrhip_rx *rx) { return rx->streams.slot_blocks(rx_bank(rx)) * SDRHIP_UDPSIZE; }
+inline size_t rx_stream_blocks(const sdrhip_rx *rx, size_t s) { return rx->streams.stream_blocks(rx_bank(rx), s); }
 inline size_t rx_stream_bytes(const sdrhip_rx *rx, size_t s) { return rx_stream_blocks(rx, s) * SDRHIP_UDPSIZE; }
+// what a ragged step will complete and deliver for the counts n_in[s], as the pipe stands
+inline RxRaggedCounts rx_counts(const sdrhip_rx *rx, const size_t *n_in) { return rx_ragged_counts(rx->area, rx->streams, rx_bank(rx), n_in); }
+// the uniform entries (`who`) while an array forces the ragged step: `instead` = the entry to use (NULL: there is none, pipelined mode)
+inline int rx_refuse_uniform(const char *who, const char *instead, RxSetting forced)
+{
+    if (forced == RX_SET_NONE) return SDRHIP_OK;
+    const char *what = forced == RX_SET_FEC ? "per-stream fecblk is set (sdrhip_rx_set_stream_fec)" : "per-stream sample bits are set (sdrhip_rx_set_stream_bits)";
+    return instead ? fail(SDRHIP_EINVAL, "%s: %s: use %s", who, what, instead) : fail(SDRHIP_EINVAL, "%s: %s: every step is the ragged step", who, what);
+}
+// a delivery of these counts that the caller's frames_out cannot take (`unconsumed`: the entry says that nothing was consumed)
+inline int rx_refuse_delivery(const char *who, const RxRaggedCounts &n, const uint8_t *frames_out, size_t frame_stride_bytes, int mem, bool unconsumed)
+{
+    if (n.max_done && !frames_out && mem != SDRHIP_MEM_DEVICE) return fail(SDRHIP_EINVAL, "%s: NULL frames_out", who);
+    if (frames_out && n.done.size() > 1 && n.max_done && frame_stride_bytes < n.max_row)
+        return fail(SDRHIP_EINVAL, "%s: frame stride too small: the longest stream's frames take %zu bytes (%zu frames at most%s)", who, n.max_row, n.max_done,
+                    unconsumed ? "; nothing was consumed" : "");
+    return SDRHIP_OK;
+}
 // batches of the ring that are being filled or in flight, of the ragged (or the uniform) kind.  (A lent batch -- state 3 -- is
 // neither: it was collected, and only its slot is still taken.)
 inline bool rx_has_batches(const sdrhip_rx *rx, bool ragged)
@@ -333,13 +337,14 @@ int rx_join_rows(sdrhip_rx *rx, size_t max_released, const char *who);
 // laid out, whatever the input format.  dev_rows: iq_in is int16 device rows whatever `mem` and the input format are (the datagram
 // entry's rows); `mem` then speaks of frames_out alone.  follow (the datagram entries with sdrhip_rx_set_follow_meta on): the collector's
 // committed state on the device; KF forms the meta words of the streams that have incoming meta from it, behind the table's upload
-int rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, size_t in_stride, const uint32_t *tv_sec, const uint32_t *tv_usec,
+// n = rx_counts() of the call's counts, taken while the pipe stands where this call finds it
+int rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const RxRaggedCounts &n, size_t in_stride, const uint32_t *tv_sec, const uint32_t *tv_usec,
               uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem, bool batch = false, bool dev_rows = false,
               RxTabs *tabs = nullptr, const FecBufState *follow = nullptr);
 // everything the ragged step allocates for these counts, ahead of it (a caller that must not fail between two launches): the frame
 // area (grown behind a synchronisation), the tables, the frame list, and the stream-order rows when the decimator cannot store
 // straight into the windows.  rx_ragged itself then allocates nothing, unless a matrix-core plan it counted on does not apply
-int rx_ragged_room(sdrhip_rx *rx, const size_t *n_in, RxTabs *tabs);
+int rx_ragged_room(sdrhip_rx *rx, const RxRaggedCounts &n, RxTabs *tabs);
 int rx_collector(sdrhip_rx *rx); // the datagram collector, created on first use
 // a uniform or ragged batch that is still being filled goes out as it is (wait_oldest's launch_filling; sdrhip_rx_async.cpp)
 int rx_launch_filling(sdrhip_rx *rx, sdrhip_rx::Batch &b);

@@ -1,5 +1,6 @@
 // sdrhip_rx.cpp -- the fused Rx pipe of include/sdrhip.h: life cycle, configuration, the uniform and the ragged step (the
-// datagram-fed call in front of it: sdrhip_rx_datagrams.cpp).
+// datagram-fed call in front of it: sdrhip_rx_datagrams.cpp).  The per-stream settings' values and records and the counts of a
+// ragged step are rx_stream_settings.h's; here they meet the device.
 #include "sdrhip_pipes.h"
 
 using namespace sdrhip;
@@ -18,6 +19,7 @@ extern "C" int sdrhip_rx_create(sdrhip_ctx *ctx, int nstreams, const sdrhip_rx_c
     rx->ctx = ctx; rx->nstreams = nstreams; rx->cfg = *cfg; rx->dec = nullptr;
     rx->area.init((size_t)nstreams);
     rx->view.init((size_t)nstreams);
+    rx->streams.init((size_t)nstreams);
     int rc = sdrhip_decimators_create(ctx, nstreams, cfg->hb_variant, &rx->dec);
     if (rc) { delete rx; return rc; }
     *out = rx;
@@ -59,8 +61,7 @@ extern "C" int sdrhip_rx_set_pipelined(sdrhip_rx *rx, int on)
     if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
     sdrhip::CtxLock lock_(rx->ctx);
     if (!on && rx->late.have) return fail(SDRHIP_EINVAL, "rx_set_pipelined: sdrhip_rx_flush the waiting frames first");
-    if (on && !rx->sf_fec.empty()) return fail(SDRHIP_EINVAL, "rx_set_pipelined: per-stream fecblk is set (sdrhip_rx_set_stream_fec): every step is the ragged step");
-    if (on && !rx->sb_bits.empty()) return fail(SDRHIP_EINVAL, "rx_set_pipelined: per-stream sample bits are set (sdrhip_rx_set_stream_bits): every step is the ragged step");
+    if (on && rx_refuse_uniform("rx_set_pipelined", nullptr, rx->streams.forces_ragged())) return SDRHIP_EINVAL;
     if (on && rx_dgrams_in_flight(rx)) return fail(SDRHIP_EINVAL, "rx_set_pipelined: asynchronous datagram batches are in flight: collect them first");
     if (on && !rx->area.aligned()) return fail(SDRHIP_EINVAL, "rx_set_pipelined: ragged calls left the streams at different frame positions");
     rx->pipelined = on ? 1 : 0;
@@ -183,7 +184,7 @@ extern "C" int sdrhip_rx_reconfigure(sdrhip_rx *rx, const sdrhip_rx_config *cfg)
     sdrhip_ctx *c = rx->ctx;
     HIP_TRY(hipSetDevice(c->device));
     // (per-stream fecblk: cfg.nb_fec is unused while the array is set, the slots keep their pitch)
-    const bool fec_changes = rx->sf_fec.empty() && cfg->nb_fec != rx->cfg.nb_fec;
+    const bool fec_changes = rx->streams.forces_ragged() != RX_SET_FEC && cfg->nb_fec != rx->cfg.nb_fec;
     if (fec_changes && rx->late.have)
         return fail(SDRHIP_EINVAL, "rx_reconfigure: frames of the previous call wait for delivery (pipelined mode): sdrhip_rx_flush them "
                                    "before changing fecblk (they carry the old frame size)");
@@ -293,45 +294,31 @@ extern "C" int sdrhip_rx_flush(sdrhip_rx *rx, uint8_t *frames_out, size_t frame_
     return SDRHIP_OK;
 }
 
-// the 24-byte MetaDataFEC record (UDPSinkFEC.cpp:87-132) with a ZERO stamp, and in w[5] the boost::crc_32_type over its first 20
-// bytes (:106-109): the affine part of every frame's CRC.  A frame's own stamp (the reference calls gettimeofday when it opens the
-// frame, :90-104) is the call's plus its first sample's offset on the sample clock: w[3], w[4] and the CRC follow per frame on the
-// device (frame_meta_words)
-static void rx_meta_record(uint32_t fc, uint32_t sr, int nb_fec, unsigned ssd, unsigned w[6])
-{
-    uint8_t m[24];
-    memcpy(m + 0, &fc, 4); memcpy(m + 4, &sr, 4);
-    m[8] = (uint8_t)((ssd - 1) / 8 + 1); // setSampleBytes((sampleSize - 1) / 8 + 1), sdrdaemonrx.cpp:643
-    m[9] = (uint8_t)ssd;                 // setSampleBits(sampleSize), :642
-    m[10] = SDRHIP_NB_ORIGINAL; m[11] = (uint8_t)nb_fec;
-    memset(m + 12, 0, 8);
-    uint32_t crc = 0xFFFFFFFFu;
-    for (int i = 0; i < 20; ++i) {
-        crc ^= m[i];
-        for (int k = 0; k < 8; ++k) crc = (crc & 1) ? 0xEDB88320u ^ (crc >> 1) : crc >> 1;
-    }
-    crc ^= 0xFFFFFFFFu;
-    memcpy(m + 20, &crc, 4);
-    memcpy(w, m, 24);
-}
+// the shared record of the bank-wide values (rx_meta_record: rx_stream_settings.h); ssd = the bank-wide decimated sample size
 static void rx_meta_base(const sdrhip_rx_config &cfg, unsigned ssd, unsigned w[6])
 {
     rx_meta_record(cfg.center_frequency_khz, cfg.sample_rate, cfg.nb_fec, ssd, w);
 }
 
-// ---- per-stream centre frequency / sample rate (UDPSink.h:93-96: every sdrdaemonrx sets them on its own sink)
+// ---- the per-stream setters and getters (rx->streams: rx_stream_settings.h).  A setter: the lock, its own refusals, then the
+// type -- range, room, values, version; whatever fails, the old values stand.  A getter: the lock, the stream, then the type
+static int rx_set_done(const RxSetResult &r, const char *who, const char *what, const char *range)
+{
+    if (r.kind == RxSetResult::RANGE) return fail(SDRHIP_EINVAL, "%s: %s[%zu] = %ld, must be %s", who, what, r.index, r.value, range);
+    return r.kind == RxSetResult::NO_MEMORY ? fail(SDRHIP_ENOMEM, "out of host memory") : SDRHIP_OK;
+}
+static int rx_check_stream(const sdrhip_rx *rx, int stream, const char *who)
+{
+    return stream < 0 || stream >= rx->nstreams ? fail(SDRHIP_EINVAL, "%s: stream %d of %d", who, stream, rx->nstreams) : SDRHIP_OK;
+}
+
+// per-stream centre frequency / sample rate (UDPSink.h:93-96: every sdrdaemonrx sets them on its own sink)
 extern "C" int sdrhip_rx_set_stream_meta(sdrhip_rx *rx, const uint32_t *center_frequency_khz, const uint32_t *sample_rate)
 {
     if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
     sdrhip::CtxLock lock_(rx->ctx);
-    const size_t S = (size_t)rx->nstreams;
     // (host arrays alone: the next launch takes them, nothing is enqueued and nothing waited for here)
-    if (center_frequency_khz) rx->sm_fc.assign(center_frequency_khz, center_frequency_khz + S);
-    else rx->sm_fc.clear();
-    if (sample_rate) rx->sm_rate.assign(sample_rate, sample_rate + S);
-    else rx->sm_rate.clear();
-    ++rx->sm_version;
-    return SDRHIP_OK;
+    return rx_set_done(rx->streams.set_meta(center_frequency_khz, sample_rate), "rx_set_stream_meta", "", "");
 }
 
 // ---- outgoing meta from the incoming meta blocks: the flag alone (the datagram entries read it per call / per submit)
@@ -347,136 +334,81 @@ extern "C" int sdrhip_rx_get_stream_meta(const sdrhip_rx *rx, int stream, uint32
 {
     if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
     sdrhip::CtxLock lock_(rx->ctx);
-    if (stream < 0 || stream >= rx->nstreams) return fail(SDRHIP_EINVAL, "rx_get_stream_meta: stream %d of %d", stream, rx->nstreams);
-    if (center_frequency_khz) *center_frequency_khz = rx->sm_fc.empty() ? rx->cfg.center_frequency_khz : rx->sm_fc[(size_t)stream];
-    if (sample_rate) *sample_rate = rx->sm_rate.empty() ? rx->cfg.sample_rate : rx->sm_rate[(size_t)stream];
+    if (int e = rx_check_stream(rx, stream, "rx_get_stream_meta")) return e;
+    if (center_frequency_khz) *center_frequency_khz = rx->streams.fc(rx_bank(rx), (size_t)stream);
+    if (sample_rate) *sample_rate = rx->streams.rate(rx_bank(rx), (size_t)stream);
     return SDRHIP_OK;
 }
 
-// ---- per-stream fecblk (sdrdaemonrx.cpp:599-605: every sdrdaemonrx sets UDPSink::setNbBlocksFEC on its own sink)
+// per-stream fecblk (sdrdaemonrx.cpp:599-605: every sdrdaemonrx sets UDPSink::setNbBlocksFEC on its own sink)
 extern "C" int sdrhip_rx_set_stream_fec(sdrhip_rx *rx, const int *nb_fec)
 {
     if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
     sdrhip::CtxLock lock_(rx->ctx);
-    const size_t S = (size_t)rx->nstreams;
     // ---- everything that can be refused, before anything changes
     if (rx->pipelined || rx->late.have) return fail(SDRHIP_EINVAL, "rx_set_stream_fec: not available in pipelined mode");
     if (rx_batches_active(rx)) return fail(SDRHIP_EINVAL, "rx_set_stream_fec: asynchronous batches are being filled or in flight: collect them first");
     if (rx->ring.busy()) return fail(SDRHIP_EINVAL, "rx_set_stream_fec: a batch is lent (sdrhip_rx_collect_egress): sdrhip_rx_release_egress it first");
-    int most = rx->cfg.nb_fec;
-    if (nb_fec) {
-        most = 0;
-        for (size_t s = 0; s < S; ++s) {
-            if (nb_fec[s] < 0 || nb_fec[s] > 128) return fail(SDRHIP_EINVAL, "rx_set_stream_fec: nb_fec[%zu] = %d, must be 0..128", s, nb_fec[s]);
-            most = nb_fec[s] > most ? nb_fec[s] : most;
-        }
-    }
-    try { // (room for the array before anything moves: the assignment below cannot fail)
-        if (nb_fec) rx->sf_fec.reserve(S);
-    } catch (const std::bad_alloc &) {
-        return fail(SDRHIP_ENOMEM, "out of host memory");
-    }
+    if (int rc = rx_set_done(rx->streams.admit_fec(nb_fec), "rx_set_stream_fec", "nb_fec", "0..128")) return rc;
     HIP_TRY(hipSetDevice(rx->ctx->device));
     // the slot pitch follows the largest count: a change moves the open frames like a fecblk change of sdrhip_rx_reconfigure
-    if (int rc = rx_repitch(rx, (size_t)(SDRHIP_NB_ORIGINAL + most) * SDRHIP_UDPSIZE, "rx_set_stream_fec")) return rc;
-    if (nb_fec) rx->sf_fec.assign(nb_fec, nb_fec + S);
-    else rx->sf_fec.clear();
-    ++rx->sm_version; // (the streams' records carry the count: formed again by the next launch)
-    return SDRHIP_OK;
+    if (int rc = rx_repitch(rx, rx->streams.slot_blocks_of(nb_fec, rx_bank(rx)) * SDRHIP_UDPSIZE, "rx_set_stream_fec")) return rc;
+    return rx_set_done(rx->streams.set_fec(nb_fec), "rx_set_stream_fec", "nb_fec", "0..128"); // (behind admit_fec: cannot fail)
 }
 
 extern "C" int sdrhip_rx_get_stream_fec(const sdrhip_rx *rx, int stream, int *nb_fec, int *slot_blocks)
 {
     if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
     sdrhip::CtxLock lock_(rx->ctx);
-    if (stream < 0 || stream >= rx->nstreams) return fail(SDRHIP_EINVAL, "rx_get_stream_fec: stream %d of %d", stream, rx->nstreams);
+    if (int e = rx_check_stream(rx, stream, "rx_get_stream_fec")) return e;
     if (nb_fec) *nb_fec = rx_fec_of(rx, (size_t)stream);
     if (slot_blocks) *slot_blocks = (int)(rx_frame_bytes(rx) / SDRHIP_UDPSIZE);
     return SDRHIP_OK;
 }
 
-// ---- per-stream sample size (sdrdaemonrx.cpp:619-623, 639-643: every sdrdaemonrx hands its own source's get_sample_bits() to its
+// per-stream sample size (sdrdaemonrx.cpp:619-623, 639-643: every sdrdaemonrx hands its own source's get_sample_bits() to its
 // Downsampler and, decimated, to UDPSink::setSampleBits / setSampleBytes).  Host arrays alone, like sdrhip_rx_set_stream_meta
 extern "C" int sdrhip_rx_set_stream_bits(sdrhip_rx *rx, const unsigned *sample_bits)
 {
     if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
     sdrhip::CtxLock lock_(rx->ctx);
-    const size_t S = (size_t)rx->nstreams;
     if (rx->pipelined || rx->late.have) return fail(SDRHIP_EINVAL, "rx_set_stream_bits: not available in pipelined mode");
-    if (sample_bits)
-        for (size_t s = 0; s < S; ++s)
-            if (sample_bits[s] < 1 || sample_bits[s] > 16) return fail(SDRHIP_EINVAL, "rx_set_stream_bits: sample_bits[%zu] = %u, must be 1..16", s, sample_bits[s]);
-    try {
-        if (sample_bits) rx->sb_bits.assign(sample_bits, sample_bits + S);
-        else rx->sb_bits.clear();
-    } catch (const std::bad_alloc &) {
-        return fail(SDRHIP_ENOMEM, "out of host memory"); // (assign into too small a vector allocates first: the old values stand)
-    }
-    ++rx->sm_version; // (the streams' records carry the size: formed again by the next launch)
-    return SDRHIP_OK;
+    return rx_set_done(rx->streams.set_bits(sample_bits), "rx_set_stream_bits", "sample_bits", "1..16");
 }
 
 extern "C" int sdrhip_rx_get_stream_bits(const sdrhip_rx *rx, int stream, unsigned *sample_bits, unsigned *frame_bits)
 {
     if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
     sdrhip::CtxLock lock_(rx->ctx);
-    if (stream < 0 || stream >= rx->nstreams) return fail(SDRHIP_EINVAL, "rx_get_stream_bits: stream %d of %d", stream, rx->nstreams);
+    if (int e = rx_check_stream(rx, stream, "rx_get_stream_bits")) return e;
     const unsigned b = rx_bits_of(rx, (size_t)stream);
     if (sample_bits) *sample_bits = b;
     if (frame_bits) *frame_bits = decimated_sample_size((unsigned)rx->cfg.log2decim, b);
     return SDRHIP_OK;
 }
 
-// the streams' records for the frames the next launch opens: [nstreams][STREAM_META_WORDS] = {fc, rate, CRC of the zero-stamp
-// record}; NULL while no array is set (the shared record of rx_meta_base serves every stream).  Formed again only when the
-// arrays or the configuration words that enter the record have changed.  ssd = the bank-wide decimated sample size; while the
-// sample-size array is set each stream's record carries its own (decimated by cfg.log2decim, which is why the key holds that too)
-static const unsigned *rx_stream_words(sdrhip_rx *rx, unsigned ssd)
-{
-    if (rx->sm_fc.empty() && rx->sm_rate.empty() && rx->sf_fec.empty() && rx->sb_bits.empty()) return nullptr;
-    unsigned w[6];
-    rx_meta_base(rx->cfg, ssd, w);
-    const sdrhip_rx::SmKey key = {rx->sm_version, w[2], w[0], w[1], rx->cfg.log2decim};
-    const sdrhip_rx::SmKey &old = rx->sm_key;
-    if (key.version != old.version || key.w2 != old.w2 || key.fc != old.fc || key.rate != old.rate || key.log2decim != old.log2decim) {
-        const size_t S = (size_t)rx->nstreams;
-        rx->sm_words.resize(S * STREAM_META_WORDS);
-        rx->sm_w2.resize(S);
-        for (size_t s = 0; s < S; ++s) {
-            rx_meta_record(rx->sm_fc.empty() ? rx->cfg.center_frequency_khz : rx->sm_fc[s],
-                           rx->sm_rate.empty() ? rx->cfg.sample_rate : rx->sm_rate[s], rx_fec_of(rx, s),
-                           rx->sb_bits.empty() ? ssd : decimated_sample_size((unsigned)rx->cfg.log2decim, rx->sb_bits[s]), w);
-            unsigned *t = &rx->sm_words[s * STREAM_META_WORDS];
-            t[0] = w[0]; t[1] = w[1]; t[2] = w[5];
-            rx->sm_w2[s] = w[2]; // (the ragged rows' fourth word: the stream's own sampleBytes, sampleBits and nbFECBlocks bytes)
-        }
-        rx->sm_key = key;
-        rx->sm_uploaded = false;
-    }
-    return rx->sm_words.data();
-}
-
-// ... on the device, for a uniform launch (*dev = NULL: shared record).  A new version is copied in front of the launch on the
-// context's stream: from a pinned buffer of its own (four rotate; reuse waits for that buffer's own upload, four versions back)
-// into the device table that the previous version does not occupy, so that a deferred encode keeps reading the one it was given
-static int rx_stream_table(sdrhip_rx *rx, unsigned ssd, const unsigned **dev)
+// the streams' records on the device, for a uniform launch (*dev = NULL: no array is set, the shared record serves every stream).
+// A new version is copied in front of the launch on the context's stream: from a pinned buffer of its own (four rotate; reuse
+// waits for that buffer's own upload, four versions back) into the device table that the previous version does not occupy, so
+// that a deferred encode keeps reading the one it was given
+static int rx_stream_table(sdrhip_rx *rx, const unsigned **dev)
 {
     *dev = nullptr;
-    const unsigned *w = rx_stream_words(rx, ssd);
-    if (!w) return SDRHIP_OK;
-    if (!rx->sm_uploaded) {
-        const size_t bytes = rx->sm_words.size() * sizeof(unsigned);
+    const RxStreamRecords *r = rx->streams.records(rx_bank(rx));
+    if (!r) return SDRHIP_OK;
+    if (rx->streams.changed()) {
+        const size_t bytes = r->words.size() * sizeof(unsigned);
         PinnedBuf &pin = rx->sm_pin[(rx->sm_pin_sel + 1) & 3];
         DevBuf &tab = rx->sm_dev[rx->sm_dev_sel ^ 1];
         int rc;
         if ((rc = pin.reserve(bytes))) return rc;
         if ((rc = tab.reserve(bytes))) return rc;
-        memcpy(pin.p, w, bytes);
+        memcpy(pin.p, r->words.data(), bytes);
         HIP_TRY(hipMemcpyAsync(tab.p, pin.p, bytes, hipMemcpyHostToDevice, rx->ctx->stream)); // (not counted: a table)
         pin.mark(rx->ctx->stream);
         rx->sm_pin_sel = (rx->sm_pin_sel + 1) & 3;
         rx->sm_dev_sel ^= 1;
-        rx->sm_uploaded = true;
+        rx->streams.taken();
     }
     *dev = rx->sm_dev[rx->sm_dev_sel].as<unsigned>();
     return SDRHIP_OK;
@@ -507,8 +439,7 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
     if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
     sdrhip::CtxLock lock_(rx->ctx);
     if (n_frames) *n_frames = 0;
-    if (!rx->sf_fec.empty()) return fail(SDRHIP_EINVAL, "rx_process: per-stream fecblk is set (sdrhip_rx_set_stream_fec): use sdrhip_rx_process_ragged");
-    if (!rx->sb_bits.empty()) return fail(SDRHIP_EINVAL, "rx_process: per-stream sample bits are set (sdrhip_rx_set_stream_bits): use sdrhip_rx_process_ragged");
+    if (int e = rx_refuse_uniform("rx_process", "sdrhip_rx_process_ragged", rx->streams.forces_ragged())) return e;
     if (rx_has_batches(rx, true)) return fail(SDRHIP_EINVAL, "rx_process: ragged batches are being filled or in flight: collect them first");
     if (rx_dgrams_in_flight(rx)) return fail(SDRHIP_EINVAL, "rx_process: asynchronous datagram batches are in flight: collect them first");
     if (n_in && !rx->area.aligned()) {
@@ -517,7 +448,7 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
         const size_t S = (size_t)rx->nstreams;
         std::vector<size_t> cnt(S, n_in), nf(S, 0);
         std::vector<uint32_t> sec(S, tv_sec), usec(S, tv_usec);
-        const int rc = rx_ragged(rx, iq_in, cnt.data(), in_stride, sec.data(), usec.data(), frames_out, frame_stride_bytes, nf.data(), mem);
+        const int rc = rx_ragged(rx, iq_in, rx_counts(rx, cnt.data()), in_stride, sec.data(), usec.data(), frames_out, frame_stride_bytes, nf.data(), mem);
         if (rc) return rc;
         size_t most = 0;
         for (size_t s = 0; s < S; ++s) if (nf[s] > most) most = nf[s];
@@ -590,7 +521,7 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
     if (adv.started > 0) {
         // tv_sec / tv_usec = the stamp of the call's first sample
         rx_meta_base(rx->cfg, decimated_sample_size((unsigned)L, ss), meta.w);
-        if ((rc = rx_stream_table(rx, decimated_sample_size((unsigned)L, ss), &meta.tab))) return rc;
+        if ((rc = rx_stream_table(rx, &meta.tab))) return rc;
         meta.w[3] = tv_sec; meta.w[4] = tv_usec;
         meta.first = adv.first_new; meta.count = adv.started; meta.frame_count0 = adv.frame_count0;
         meta.idx0 = adv.idx0;
@@ -738,25 +669,17 @@ static size_t rx_flist_entries(size_t sum_done) { return (sum_done / GF_FRAMES_P
 // the form fec_encode_device chooses for `rows` recovery blocks: 0 the generic kernel, 1 the FFT / bit-sliced kernel, 2 the walk
 static int rx_encode_form(const sdrhip_ctx *c, int rows) { return rows < enc128_min_rows(c) ? 0 : rows <= 32 ? 1 : 2; }
 
-int sdrhip::rx_ragged_room(sdrhip_rx *rx, const size_t *n_in, RxTabs *tabs)
+int sdrhip::rx_ragged_room(sdrhip_rx *rx, const RxRaggedCounts &n, RxTabs *tabs)
 {
     const int S = rx->nstreams, L = rx->cfg.log2decim;
-    size_t sum_done = 0, max_dec = 0;
-    std::vector<size_t> done((size_t)S);
-    for (int s = 0; s < S; ++s) {
-        const size_t n_dec = n_in[s] >> L;
-        done[(size_t)s] = rx->area.advance((size_t)s, n_dec).done;
-        max_dec = n_dec > max_dec ? n_dec : max_dec;
-        sum_done += done[(size_t)s];
-    }
     int rc;
-    if ((rc = rx_area_room(rx, done.data()))) return rc;
+    if ((rc = rx_area_room(rx, n.done.data()))) return rc;
     if ((rc = ragged_reserve(rx->dec, tabs ? &tabs->rows : nullptr))) return rc;
     // (only the matrix-core launch of a centred decimation by 4 or more stores straight into the windows)
     const bool may_direct = rx->cfg.fcpos == SDRHIP_FC_CEN && L >= 2 && rx->ctx->opt.rx_direct;
-    if (!may_direct && (rc = rx->lin[0].reserve((size_t)S * ((max_dec + 3) & ~(size_t)3) * 4 + 16))) return rc;
-    if (sum_done && rx_fec_max(rx) > 0) {
-        const size_t nl = rx_flist_entries(sum_done);
+    if (!may_direct && (rc = rx->lin[0].reserve((size_t)S * ((n.max_dec + 3) & ~(size_t)3) * 4 + 16))) return rc;
+    if (n.sum_done && rx_fec_max(rx) > 0) {
+        const size_t nl = rx_flist_entries(n.sum_done);
         if ((rc = (tabs ? tabs->flist : rx->r_flist_pin).reserve(nl * 4))) return rc;
         if ((rc = rx->r_flist.reserve(nl * 4))) return rc;
     }
@@ -766,7 +689,7 @@ int sdrhip::rx_ragged_room(sdrhip_rx *rx, const size_t *n_in, RxTabs *tabs)
 // Every stream takes its own count: K0r (8-bit input) -> K1r / filter-less kernel into stream order -> K2r into each stream's
 // own window -> one encoder launch over the list of every stream's completed frames.  A call that fails after it moved windows
 // leaves the windows moved (the open frames lie there now) and the rest of the framing state untouched.
-int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, size_t in_stride, const uint32_t *tv_sec, const uint32_t *tv_usec,
+int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const RxRaggedCounts &n, size_t in_stride, const uint32_t *tv_sec, const uint32_t *tv_usec,
                       uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem, bool batch, bool dev_rows, RxTabs *tabs,
                       const FecBufState *follow)
 {
@@ -776,13 +699,13 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
     const size_t FB = (size_t)SDRHIP_NB_ORIGINAL + (size_t)R;
     const size_t frame_bytes = FB * SDRHIP_UDPSIZE;
     const bool mixed = rx_fec_mixed(rx);
+    const size_t *n_in = n.n_in, max_in = n.max_in, max_dec = n.max_dec, max_done = n.max_done, sum_done = n.sum_done;
+    const std::vector<size_t> &done = n.done;
     for (int s = 0; s < S; ++s) n_frames[s] = 0;
     // ---- everything that can be refused is checked before anything is consumed
     if (int e = check_mem(mem)) return e;
     if (rx->pipelined) return fail(SDRHIP_EINVAL, "rx_process_ragged: not available in pipelined mode");
     if (!batch && rx_batches_active(rx)) return fail(SDRHIP_EINVAL, "rx_process_ragged: asynchronous batches are being filled or in flight: collect them first");
-    size_t max_in = 0;
-    for (int s = 0; s < S; ++s) if (n_in[s] > max_in) max_in = n_in[s];
     if (S == 1) in_stride = max_in;
     if (S > 1 && in_stride < max_in) return fail(SDRHIP_EINVAL, "rx_process_ragged: in_stride smaller than the largest count");
     if (max_in && !iq_in) return fail(SDRHIP_EINVAL, "rx_process_ragged: NULL input");
@@ -790,23 +713,7 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
     const bool in_dev = mem == SDRHIP_MEM_DEVICE || dev_rows;
     if (max_in && in_dev && (!aligned16(iq_in) || (S > 1 && (in_stride & (wide8 ? 7 : 3)))))
         return fail(SDRHIP_EALIGN, "rx_process_ragged: device input must be 16-byte aligned, its stride a multiple of %d samples", wide8 ? 8 : 4);
-    std::vector<RxAdvance> adv((size_t)S);
-    std::vector<size_t> done((size_t)S);
-    std::vector<uint64_t> rest((size_t)S);
-    size_t max_done = 0, sum_done = 0, max_dec = 0, max_row = 0; // max_row: the longest dense delivery of a stream
-    for (int s = 0; s < S; ++s) {
-        const size_t n_dec = n_in[s] >> L;
-        adv[(size_t)s] = rx->area.advance((size_t)s, n_dec);
-        done[(size_t)s] = adv[(size_t)s].done;
-        rest[(size_t)s] = adv[(size_t)s].rest;
-        if (done[(size_t)s] > max_done) max_done = done[(size_t)s];
-        if (done[(size_t)s] * rx_stream_bytes(rx, (size_t)s) > max_row) max_row = done[(size_t)s] * rx_stream_bytes(rx, (size_t)s);
-        if (n_dec > max_dec) max_dec = n_dec;
-        sum_done += done[(size_t)s];
-    }
-    if (max_done && !frames_out && mem != SDRHIP_MEM_DEVICE) return fail(SDRHIP_EINVAL, "rx_process_ragged: NULL frames_out");
-    if (frames_out && S > 1 && max_done && frame_stride_bytes < max_row)
-        return fail(SDRHIP_EINVAL, "rx_process_ragged: frame stride too small: the longest stream's frames take %zu bytes (%zu frames at most)", max_row, max_done);
+    if (int e = rx_refuse_delivery("rx_process_ragged", n, frames_out, frame_stride_bytes, mem, false)) return e;
     HIP_TRY(hipSetDevice(c->device));
     rx->consumed = false;
     if (max_in == 0) { // nothing arrives: nothing changes, nothing is delivered
@@ -828,18 +735,19 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
     for (int s = 0; s < S; ++s) ss[(size_t)s] = rx_bits_of(rx, (size_t)s);
     unsigned mw[6]; // (the record with a zero stamp; the stamps go per row, and so do fc, rate and the CRC: sdrhip_rx_set_stream_meta)
     rx_meta_base(rx->cfg, decimated_sample_size((unsigned)L, rx->cfg.sample_bits), mw);
-    const unsigned *sw = rx_stream_words(rx, decimated_sample_size((unsigned)L, rx->cfg.sample_bits));
+    const RxStreamRecords *sw = rx->streams.records(rx_bank(rx)); // (NULL: no array is set, mw serves every stream)
     std::vector<RaggedRow> rows((size_t)S);
     memset(rows.data(), 0, rows.size() * sizeof(RaggedRow));
     for (int s = 0; s < S; ++s) {
         RaggedRow &r = rows[(size_t)s];
-        const RxAdvance &a = adv[(size_t)s];
+        const RxAdvance &a = n.adv[(size_t)s];
         r.out_off = A.slot((size_t)s) * frame_bytes / 4;
         r.frame_sample_base = A.pending((size_t)s);
-        r.fc = sw ? sw[s * STREAM_META_WORDS] : mw[0]; r.rate = sw ? sw[s * STREAM_META_WORDS + 1] : mw[1];
-        r.crc0 = sw ? sw[s * STREAM_META_WORDS + 2] : mw[5];
-        r.w2 = sw ? rx->sm_w2[(size_t)s] : mw[2];
-        r.shifts = ragged_shift_word((unsigned)L, ss[(size_t)s]);
+        const unsigned *t = sw ? &sw->words[(size_t)s * STREAM_META_WORDS] : nullptr;
+        r.fc = t ? t[0] : mw[0]; r.rate = t ? t[1] : mw[1];
+        r.crc0 = t ? t[2] : mw[5];
+        r.w2 = sw ? sw->w2[(size_t)s] : mw[2];
+        r.shifts = sw ? sw->shifts[(size_t)s] : ragged_shift_word((unsigned)L, ss[(size_t)s]);
         if (a.started > 0 && (n_in[s] >> L)) {
             r.meta_first = a.first_new; r.meta_count = a.started;
             r.frame_count0 = a.frame_count0;
@@ -974,7 +882,7 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, s
     }
     rx->view.set_each(area, stream_bytes, (size_t)S, A.slots(), done.data());
     for (int s = 0; s < S; ++s) n_frames[s] = done[(size_t)s];
-    rx->area.commit(done.data(), rest.data());
+    rx->area.commit(done.data(), n.rest.data());
     if (mem == SDRHIP_MEM_HOST) HIP_TRY(hipStreamSynchronize(c->stream));
     return SDRHIP_OK;
 }
@@ -985,5 +893,5 @@ extern "C" int sdrhip_rx_process_ragged(sdrhip_rx *rx, const int16_t *iq_in, con
     if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
     if (!n_in || !tv_sec || !tv_usec || !n_frames) return fail(SDRHIP_EINVAL, "rx_process_ragged: NULL count, stamp or n_frames array");
     sdrhip::CtxLock lock_(rx->ctx);
-    return rx_ragged(rx, iq_in, n_in, in_stride, tv_sec, tv_usec, frames_out, frame_stride_bytes, n_frames, mem);
+    return rx_ragged(rx, iq_in, rx_counts(rx, n_in), in_stride, tv_sec, tv_usec, frames_out, frame_stride_bytes, n_frames, mem);
 }

@@ -76,17 +76,15 @@ int rx_launch_batch(sdrhip_rx *rx, sdrhip_rx::Batch &b)
 int rx_launch_ragged(sdrhip_rx *rx, sdrhip_rx::Batch &b)
 {
     sdrhip_ctx *c = rx->ctx;
-    const int S = rx->nstreams, L = rx->cfg.log2decim;
+    const int S = rx->nstreams;
     const size_t esz = rx->in_fmt == IQF_S16 ? 4 : 2;
     const size_t nblk = b.r_cnt.size() / (size_t)S;
-    size_t max_t = 0, nseg = 0, packed = 0, sum_done = 0;
+    size_t nseg = 0, packed = 0;
     for (size_t i = 0; i < b.r_cnt.size(); ++i) { packed += b.r_cnt[i]; nseg += b.r_cnt[i] ? 1 : 0; }
-    for (int s = 0; s < S; ++s) if (b.r_tot[(size_t)s] > max_t) max_t = b.r_tot[(size_t)s];
-    const size_t dstride = (max_t + 7) & ~(size_t)7;
+    // (what the step below completes: the buffers are sized from it before anything is consumed)
+    const RxRaggedCounts n = rx_counts(rx, b.r_tot.data());
+    const size_t sum_done = n.sum_done, dstride = (n.max_in + 7) & ~(size_t)7;
     const size_t fb = rx_frame_bytes(rx); // (per-stream fecblk: the slot pitch, a bound on every stream's frame)
-    // (the frames every stream completes, counted as rx_ragged counts them: the buffers are sized before anything is consumed)
-    for (int s = 0; s < S; ++s)
-        sum_done += rx->area.advance((size_t)s, b.r_tot[(size_t)s] >> L).done;
     const size_t rows_bytes = (size_t)(S + 1) * sizeof(PackRow), segs_bytes = nseg * sizeof(PackSeg);
     const size_t list_off = (rows_bytes + segs_bytes + 15) & ~(size_t)15;
     int rc;
@@ -158,7 +156,7 @@ int rx_launch_ragged(sdrhip_rx *rx, sdrhip_rx::Batch &b)
 
     // ---- the batch as one ragged step
     std::vector<size_t> nf((size_t)S, 0);
-    rc = rx_ragged(rx, rx->a_din.as<int16_t>(), b.r_tot.data(), dstride, b.r_sec.data(), b.r_usec.data(), nullptr, 0, nf.data(),
+    rc = rx_ragged(rx, rx->a_din.as<int16_t>(), n, dstride, b.r_sec.data(), b.r_usec.data(), nullptr, 0, nf.data(),
                    SDRHIP_MEM_DEVICE, true);
     if (rc) {
         if (rx->consumed) b.state = 0; // consumed and lost: never replayed (the pipe's own error stands)
@@ -169,10 +167,8 @@ int rx_launch_ragged(sdrhip_rx *rx, sdrhip_rx::Batch &b)
     int32_t *list = reinterpret_cast<int32_t *>(b.r_tab.as<char>() + list_off);
     size_t nl = 0;
     hipError_t e = hipSuccess;
-    for (int s = 0; s < S && e == hipSuccess; ++s) {
-        if (nl + nf[(size_t)s] > sum_done) { e = hipErrorInvalidValue; break; } // (cannot happen: the count above is the pipe's own)
+    for (int s = 0; s < S; ++s)
         for (size_t f = 0; f < nf[(size_t)s]; ++f) list[nl++] = (int32_t)(rx->view.offset((size_t)s, fb) / fb + f);
-    }
     // (departure order: KE in the gather's place writes the same buffer, sdrhip_rx_egress.cpp)
     if (e == hipSuccess && nl && b.egress) e = rx_egress_launch(rx, b, nf.data(), fb, nullptr, 0, nullptr);
     else if (e == hipSuccess && nl) e = hipMemcpyAsync(rx->a_tab.as<char>() + list_off, list, nl * 4, hipMemcpyHostToDevice, c->stream);
@@ -213,8 +209,7 @@ extern "C" int sdrhip_rx_submit(sdrhip_rx *rx, const int16_t *iq_in, size_t n_in
 {
     if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
     sdrhip::CtxLock lock_(rx->ctx);
-    if (!rx->sf_fec.empty()) return fail(SDRHIP_EINVAL, "rx_submit: per-stream fecblk is set (sdrhip_rx_set_stream_fec): use sdrhip_rx_submit_ragged");
-    if (!rx->sb_bits.empty()) return fail(SDRHIP_EINVAL, "rx_submit: per-stream sample bits are set (sdrhip_rx_set_stream_bits): use sdrhip_rx_submit_ragged");
+    if (int e = rx_refuse_uniform("rx_submit", "sdrhip_rx_submit_ragged", rx->streams.forces_ragged())) return e;
     if (rx->egress) return fail(SDRHIP_EINVAL, "rx_submit: uniform batches have no departure order (sdrhip_rx_set_egress): use sdrhip_rx_submit_ragged with equal counts");
     if (n_in == 0) return SDRHIP_OK;
     if (!iq_in) return fail(SDRHIP_EINVAL, "rx_submit: NULL input");

@@ -9,30 +9,23 @@
 using namespace sdrhip;
 
 namespace {
-// what the ragged step would refuse, asked while the collector has not moved: the counts it will get from these releases
+// asked with the call's release counts while the collector has not moved: what each stream feeds its decimator and holds back
+// (join), what the ragged step will make of it (n) -- and whether it would refuse the delivery.  The call goes on with both
 struct Admit {
     const sdrhip_rx *rx;
     const std::vector<size_t> *carry;
     const uint8_t *frames_out;
     size_t frame_stride_bytes;
     int mem;
+    RxJoinCounts join;
+    RxRaggedCounts n;
 };
 int admit(void *arg, const size_t *n_released)
 {
-    const Admit &a = *static_cast<const Admit *>(arg);
-    const sdrhip_rx *rx = a.rx;
-    const size_t U = rx_join_unit(rx->cfg);
-    size_t max_done = 0, max_row = 0; // (per-stream fecblk: a stream's frames are delivered dense, 128 + nb_fec[s] blocks each)
-    for (int s = 0; s < rx->nstreams; ++s) {
-        const size_t fed = ((*a.carry)[(size_t)s] + n_released[s] * SDRHIP_SAMPLES_PER_FRAME) / U * U;
-        const size_t done = rx->area.advance((size_t)s, fed >> rx->cfg.log2decim).done;
-        if (done > max_done) max_done = done;
-        if (done * rx_stream_bytes(rx, (size_t)s) > max_row) max_row = done * rx_stream_bytes(rx, (size_t)s);
-    }
-    if (max_done && !a.frames_out && a.mem != SDRHIP_MEM_DEVICE) return fail(SDRHIP_EINVAL, "rx_process_datagrams: NULL frames_out");
-    if (a.frames_out && rx->nstreams > 1 && max_done && a.frame_stride_bytes < max_row)
-        return fail(SDRHIP_EINVAL, "rx_process_datagrams: frame stride too small: the longest stream's frames take %zu bytes (%zu frames at most; nothing was consumed)", max_row, max_done);
-    return SDRHIP_OK;
+    Admit &a = *static_cast<Admit *>(arg);
+    a.join = rx_join_counts(rx_join_unit(a.rx->cfg), *a.carry, n_released);
+    a.n = rx_counts(a.rx, a.join.fed.data());
+    return rx_refuse_delivery("rx_process_datagrams", a.n, a.frames_out, a.frame_stride_bytes, a.mem, true);
 }
 } // namespace
 
@@ -117,31 +110,24 @@ extern "C" int sdrhip_rx_process_datagrams(sdrhip_rx *rx, const uint8_t *dgrams,
     if ((rc = fecbuf_join_carry(rx->fb, &carry_dev, &carry))) return rc;
     if (max_released > 0 && (rc = rx_join_rows(rx, max_released, "rx_process_datagrams"))) return rc;
     const size_t U = rx_join_unit(rx->cfg);
-    Admit ad = {rx, carry, frames_out, frame_stride_bytes, mem};
+    Admit ad = {rx, carry, frames_out, frame_stride_bytes, mem, RxJoinCounts(), RxRaggedCounts()};
     const FecBufJoin join = {carry_dev, admit, &ad};
     const int *counts = nullptr;
     if ((rc = fecbuf_collect(rx->fb, dgrams, n_dgrams, dgram_stride_bytes, mem, max_released ? rx->j_rows.as<uint8_t>() : nullptr,
                              rx->j_row_len * 4, nullptr, max_released, info_out, n_released, &counts, &join)))
         return rc; // (SDRHIP_EINVAL: nothing consumed, nothing has run behind the classify pass)
     // ---- the collector's state has moved on: from here a failure loses the call's samples, it is never replayed
-    std::vector<size_t> fed((size_t)S), left((size_t)S);
-    bool any = false;
-    for (int s = 0; s < S; ++s) {
-        const size_t total = (*carry)[(size_t)s] + n_released[s] * SDRHIP_SAMPLES_PER_FRAME;
-        fed[(size_t)s] = total / U * U;
-        left[(size_t)s] = total - fed[(size_t)s];
-        any = any || fed[(size_t)s] != 0;
-    }
-    if (!any) { // (nothing released, and no row holds a whole unit: rows and remainders stay)
+    // (ad.join / ad.n: admit's, counted from these n_released behind the read-back)
+    if (!ad.join.any) { // (nothing released, and no row holds a whole unit: rows and remainders stay)
         rx->view.clear();
         return SDRHIP_OK;
     }
     // (follow: the state this call's collection committed -- fecbuf_collect has flipped the double buffer)
-    if ((rc = rx_ragged(rx, rx->j_rows.as<int16_t>(), fed.data(), rx->j_row_len, tv_sec, tv_usec, frames_out, frame_stride_bytes, n_frames, mem,
+    if ((rc = rx_ragged(rx, rx->j_rows.as<int16_t>(), ad.n, rx->j_row_len, tv_sec, tv_usec, frames_out, frame_stride_bytes, n_frames, mem,
                         false, true, nullptr, rx->follow_meta ? fecbuf_committed_state(rx->fb) : nullptr)))
         return rc;
     hipError_t e = launch_rx_join_carry(rx->j_rows.as<int16_t>(), rx->j_row_len, carry_dev, counts, (unsigned)U, S, c->stream);
     if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "rx join launch: %s", hipGetErrorString(e));
-    *carry = left;
+    *carry = ad.join.left;
     return SDRHIP_OK;
 }

@@ -16,7 +16,7 @@ using namespace sdrhip;
 // one batch behind fecbuf_batch_check[_tagged] (`in`; the context lock is held): the rest of the refusals, then the submit
 static int rx_submit_batch(sdrhip_rx *rx, FecBufBatch &in, const uint32_t *tv_sec, const uint32_t *tv_usec, const char *who)
 {
-    const int S = rx->nstreams, L = rx->cfg.log2decim;
+    const int S = rx->nstreams;
     const size_t *n_dgrams = in.n_dgrams;
     if (rx->pipelined) return fail(SDRHIP_EINVAL, "%s: not available in pipelined mode", who);
     if (rx_fec_mixed(rx) && !rx->egress)
@@ -39,24 +39,19 @@ static int rx_submit_batch(sdrhip_rx *rx, FecBufBatch &in, const uint32_t *tv_se
     std::vector<int> res((size_t)S * 4);
     if ((rc = fecbuf_batch_stage(&in, b.in, b.r_tab, sh, res.data()))) return rc;
     // ---- every count of the batch, from the shadow's release counts and the host's copy of the carry: what each stream feeds its
-    // decimator, what it holds back, the frames it completes (as rx_ragged counts them)
+    // decimator, what it holds back (fed), the frames the ragged step completes and the bytes it delivers (n)
     const size_t U = rx_join_unit(rx->cfg), fb = rx_frame_bytes(rx); // (per-stream fecblk: the slot pitch)
-    std::vector<size_t> fed((size_t)S), left((size_t)S), nf((size_t)S, 0);
-    size_t kmax = 0, kall = 0, sum_done = 0, b_frames = 0; // b_frames: exactly the delivered bytes, 128 + nb_fec[s] blocks per frame
-    bool any = false;
+    std::vector<size_t> rel((size_t)S), nf((size_t)S, 0);
+    size_t kmax = 0, kall = 0;
     for (int s = 0; s < S; ++s) {
-        const size_t k = (size_t)res[(size_t)s * 4];
+        const size_t k = rel[(size_t)s] = (size_t)res[(size_t)s * 4];
         kmax = k > kmax ? k : kmax;
         kall += k;
-        const size_t total = (*carry)[(size_t)s] + k * SDRHIP_SAMPLES_PER_FRAME;
-        fed[(size_t)s] = total / U * U;
-        left[(size_t)s] = total - fed[(size_t)s];
-        any = any || fed[(size_t)s] != 0;
-        const size_t done = rx->area.advance((size_t)s, fed[(size_t)s] >> L).done;
-        sum_done += done;
-        b_frames += done * rx_stream_bytes(rx, (size_t)s);
     }
-    const size_t b_total = b_frames + kall * DG_REC;
+    const RxJoinCounts fed = rx_join_counts(U, *carry, rel.data());
+    const RxRaggedCounts n = rx_counts(rx, fed.fed.data());
+    const bool any = fed.any;
+    const size_t sum_done = n.sum_done, b_frames = n.bytes, b_total = b_frames + kall * DG_REC;
     const size_t seg_bytes = (size_t)2 * S * sizeof(RxDeliverSeg);
     // everything that can fail for want of memory comes before the collector moves (a device buffer that grows waits for the
     // batches in flight; the rows keep their heads): the batch's own buffers, then what the ragged step takes for these counts
@@ -71,7 +66,7 @@ static int rx_submit_batch(sdrhip_rx *rx, FecBufBatch &in, const uint32_t *tv_se
     if ((rc = rx->ring.ensure_event(b))) return rc;
     b.egress = rx->egress; // (departure order: KE's table and the tags, like everything else, before the collector moves)
     if (b.egress && (rc = rx_egress_room(rx, b, sum_done, fb / SDRHIP_UDPSIZE))) return rc;
-    if (any && (rc = rx_ragged_room(rx, fed.data(), &b.d_tabs))) return rc;
+    if (any && (rc = rx_ragged_room(rx, n, &b.d_tabs))) return rc;
 
     // ---- upload: exactly the datagrams (staged: one copy; in place: one per run of adjacent rows)
     uint8_t *pk = rx->a_pk.as<uint8_t>();
@@ -92,12 +87,12 @@ static int rx_submit_batch(sdrhip_rx *rx, FecBufBatch &in, const uint32_t *tv_se
     if (rc) return fecbuf_batch_lost(who, rc);
     // ---- decimate, frame, encode: one ragged step; KJ moves every row's remainder to its head (the device's own counts)
     if (any) {
-        if ((rc = rx_ragged(rx, rx->j_rows.as<int16_t>(), fed.data(), rx->j_row_len, tv_sec, tv_usec, nullptr, 0, nf.data(), SDRHIP_MEM_DEVICE,
+        if ((rc = rx_ragged(rx, rx->j_rows.as<int16_t>(), n, rx->j_row_len, tv_sec, tv_usec, nullptr, 0, nf.data(), SDRHIP_MEM_DEVICE,
                             true, true, &b.d_tabs, rx->follow_meta ? fecbuf_committed_state(rx->fb) : nullptr))) // (the flag as it stands at this submit)
             return fecbuf_batch_lost(who, rc);
         hipError_t e = launch_rx_join_carry(rx->j_rows.as<int16_t>(), rx->j_row_len, carry_dev, counts, (unsigned)U, S, c->stream);
         if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "rx join launch: %s (the batch is lost)", hipGetErrorString(e));
-        *carry = left;
+        *carry = fed.left;
     } else { // (nothing released, and no row holds a whole unit: rows and remainders stay)
         rx->view.clear();
     }
@@ -112,7 +107,7 @@ static int rx_submit_batch(sdrhip_rx *rx, FecBufBatch &in, const uint32_t *tv_se
         g.bytes = nf[(size_t)s] * rx_stream_bytes(rx, (size_t)s); g.dst = dst; g.from_records = 0; // (= fb unless the counts differ: departure order only)
         dst += g.bytes;
     }
-    hipError_t e = dst == b_frames ? hipSuccess : hipErrorInvalidValue; // (cannot differ: the count above is the pipe's own)
+    hipError_t e = dst == b_frames ? hipSuccess : hipErrorInvalidValue; // (this walk sums what was delivered on its own; the buffers hold what was counted)
     for (int s = 0; s < S; ++s) {
         const size_t k = (size_t)res[(size_t)s * 4];
         if (!k) continue;
@@ -138,8 +133,7 @@ static int rx_submit_batch(sdrhip_rx *rx, FecBufBatch &in, const uint32_t *tv_se
     if (e == hipSuccess) e = hipEventRecord(b.done, c->stream);
     if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "rx datagram batch delivery: %s (the batch is lost)", hipGetErrorString(e));
     b.r_frames.assign(nf.begin(), nf.end());
-    b.d_rel.resize((size_t)S);
-    for (int s = 0; s < S; ++s) b.d_rel[(size_t)s] = (size_t)res[(size_t)s * 4];
+    b.d_rel.assign(rel.begin(), rel.end());
     b.frame_bytes = fb;
     b.dg = true; b.ragged = false;
     b.state = 2;

@@ -756,16 +756,9 @@ class RxPipe(_Handle):
     def set_stream_meta(self, center_frequency_khz=None, sample_rate=None):
         """Per-stream UDPSink::setCenterFrequency / setSampleRate (sdrhip_rx_set_stream_meta): sequences of nstreams values for
         the frames that later launches open; None = that field is bank-wide again (the config's value).  Never synchronises."""
-        arrs = []
-        for name, v in (("center_frequency_khz", center_frequency_khz), ("sample_rate", sample_rate)):
-            if v is None:
-                arrs.append(None)
-                continue
-            v = [int(x) for x in v]
-            if len(v) != self.nstreams or any(x < 0 or x > 0xffffffff for x in v):
-                raise ValueError("%s: %d values of 32 bits, one per stream" % (name, self.nstreams))
-            arrs.append((C.c_uint32 * self.nstreams)(*v))
-        check(self.ctx.lib.sdrhip_rx_set_stream_meta(self.h, arrs[0], arrs[1]))
+        fc, _ = self._stream_ints("center_frequency_khz", center_frequency_khz, C.c_uint32, "values of 32 bits", 0, 0xffffffff)
+        sr, _ = self._stream_ints("sample_rate", sample_rate, C.c_uint32, "values of 32 bits", 0, 0xffffffff)
+        check(self.ctx.lib.sdrhip_rx_set_stream_meta(self.h, fc, sr))
 
     def stream_meta(self, stream):
         """-> {"center_frequency_khz", "sample_rate"}: what the stream's next opened frame will carry"""
@@ -779,14 +772,9 @@ class RxPipe(_Handle):
         process(), submit() and pipelined mode raise, process_ragged / process_datagrams return each stream's frames as its own
         (n, 128 + nb_fec[s], 512) array, and batches whose counts differ are delivered in departure order only (set_egress).
         Refused (SdrHipError) in pipelined mode and while batches are being filled, in flight or lent."""
-        arr = None
-        if nb_fec is not None:
-            v = [int(x) for x in nb_fec]
-            if len(v) != self.nstreams:
-                raise ValueError("nb_fec: %d counts, one per stream" % self.nstreams)
-            arr = (C.c_int * self.nstreams)(*v)
+        arr, v = self._stream_ints("nb_fec", nb_fec, C.c_int, "counts")  # (the range is the library's to refuse)
         check(self.ctx.lib.sdrhip_rx_set_stream_fec(self.h, arr))
-        self._stream_fec = None if nb_fec is None else v
+        self._stream_fec = v
 
     def stream_fec(self, stream):
         """-> (nb_fec of the stream, slot_blocks = 128 + the largest count: the pitch of the frame area's slots)"""
@@ -799,12 +787,7 @@ class RxPipe(_Handle):
         source says in get_sample_bits() -- for the samples later launches decimate and the meta blocks they open; None = bank-wide
         again (the config's sample_bits).  While it is set process(), submit() and pipelined mode raise.  Never synchronises;
         refused (SdrHipError) in pipelined mode."""
-        arr = None
-        if bits is not None:
-            v = [int(x) for x in bits]
-            if len(v) != self.nstreams or any(x < 0 for x in v):
-                raise ValueError("bits: %d sizes, one per stream" % self.nstreams)
-            arr = (C.c_uint * self.nstreams)(*v)
+        arr, _ = self._stream_ints("bits", bits, C.c_uint, "sizes", 0)  # (unsigned in the ABI; 1..16 is the library's to refuse)
         check(self.ctx.lib.sdrhip_rx_set_stream_bits(self.h, arr))
 
     def stream_bits(self, stream):
@@ -812,6 +795,16 @@ class RxPipe(_Handle):
         b, fb = C.c_uint(0), C.c_uint(0)
         check(self.ctx.lib.sdrhip_rx_get_stream_bits(self.h, int(stream), C.byref(b), C.byref(fb)))
         return b.value, fb.value
+
+    def _stream_ints(self, name, values, ctype, what, lo=None, hi=None):
+        """a per-stream setter's argument: a sequence of nstreams ints, each lo..hi where a bound is given -> (its ctypes array, the
+        ints); None (bank-wide again) -> (None, None)"""
+        if values is None:
+            return None, None
+        v = [int(x) for x in values]
+        if len(v) != self.nstreams or any((lo is not None and x < lo) or (hi is not None and x > hi) for x in v):
+            raise ValueError("%s: %d %s, one per stream" % (name, self.nstreams, what))
+        return (ctype * self.nstreams)(*v), v
 
     def _slot_fec(self):
         """the count that sizes a frame slot and a delivery row: the largest of set_stream_fec's array, else nb_fec"""
