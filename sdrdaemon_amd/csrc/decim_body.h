@@ -8,7 +8,7 @@ namespace sdrhip {
 namespace {
 
 constexpr int NT = 256;    // threads per workgroup
-constexpr int P0 = 2048;   // first-stage inputs per pass
+constexpr int P0 = DECIM_PASS; // first-stage inputs per pass (2048; decim_plan.h: the planners size segments and pieces in passes)
 constexpr int FULL = 512;  // fresh entries per plane that trigger a stage s >= 1
 constexpr int HE = 32;     // history entries in front of every plane
 

@@ -55,27 +55,6 @@ template <int L, int FC, bool PACK16> hipError_t launch_variant(const DecimArgs 
 
 } // namespace
 
-void plan_decimate(int log2decim, int fcpos, size_t n_used, int nstreams, int *nsub_per_seg, int *nseg)
-{
-    const bool cen = (fcpos == 2);
-    const size_t praw = cen ? (size_t)P0 : (size_t)P0 * 4;
-    size_t npass = (n_used + praw - 1) / praw;
-    if (npass == 0) npass = 1;
-    // a segment is a whole number of schedule periods (2^(NS-2) passes) so that full-rate
-    // stages never flush early; >= 16 passes keep the warm-up (64 * 2^L samples) below ~3 %.
-    const int ns = cen ? log2decim : log2decim - 2;
-    size_t period = (size_t)1 << (ns > 2 ? ns - 2 : 0);
-    size_t per = period < 32 ? 32 : period; // warm-up = 64 * 2^L of 32 * 2048 samples: 1.6 % at L = 4
-    // fewer passes per segment when the call is too short to fill 256 CUs x 4 workgroups
-    while (per > period && ((npass + per - 1) / per) * (size_t)nstreams < 2048) per >>= 1;
-    while (per > 1 && ((npass + per - 1) / per) * (size_t)nstreams < 256) per >>= 1;
-    // the warm-up region must not reach before the stream start
-    const size_t wraw = (size_t)64 << log2decim;
-    while (per * praw < wraw) per <<= 1;
-    *nsub_per_seg = (int)per;
-    *nseg = (int)((npass + per - 1) / per);
-}
-
 hipError_t launch_decimate(int log2decim, int fcpos, bool pack16, const DecimArgs &a, hipStream_t stream)
 {
 #define SDRHIP_CEN(L_)                                                                                          \

@@ -337,8 +337,9 @@ constexpr int MF_GROUP_BYTES = 9216;             // 8 blocks of 1 KiB + their sk
 // previous call on a second stream: sdrhip_rx.cpp, "overlap" mode).  The DMAs run NG - 1 groups (8 (NG - 1) steps) ahead.
 constexpr int mf_wave_ring(int ng) { return ng * MF_GROUP_BYTES; } // bytes of LDS per wave
 // decimate16 only: measured with 3 interleaved rounds (tools/experiments_r03/exp24.sh), register ring against LDS-DMA ring: decimate16 0.2445 / 0.2363 ms,
-// decimate32 0.2512 / 0.2537, decimate64 0.2693 / 0.2947 (their warm-up and the ring's run-ahead past the span grow with the ratio)
-__host__ __device__ constexpr bool mf_dma_applies(int ns) { return ns == 4; } // (period of 32 steps; one workgroup per CU)
+// decimate32 0.2512 / 0.2537, decimate64 0.2693 / 0.2947 (their warm-up and the ring's run-ahead past the span grow with the ratio):
+// mf_dma_applies(ns), decim_plan.h -- the planner deals the pieces by it
+static_assert(MF_HEAD_MIN % P0 == 0 && MF_TAIL_SEG % P0 == 0, "K1m's head and tail pieces are whole passes of the VALU code");
 __host__ __device__ constexpr int mf_block_units(int p) { return 72 * p + 2 * (p >> 2); }
 
 template <int D> __device__ __forceinline__ void mf_dma_issue(unsigned slot, unsigned voff, unsigned long long span_base)
@@ -489,6 +490,7 @@ template <int NS, int NG = 0, bool FR = false> __device__ __forceinline__ void m
     constexpr size_t W = (size_t)64 << L; // warm-up, raw samples: one, two or four periods
     constexpr int WP = (int)(W / (32 * (size_t)P));
     static_assert(P % D == 0, "prefetch ring");
+    static_assert((size_t)D * 32 <= MF_READ_AHEAD, "the planner leaves the register ring's read-ahead behind a wave's last span (decim_plan.h)");
     const int lane = threadIdx.x & 63;
     const int n = lane & 15, q = lane >> 4, comp = n & 1, p = n >> 1;
     const int stream = gw / a.mf_wps, ws = gw - stream * a.mf_wps;
@@ -849,102 +851,6 @@ template <int L> hipError_t launch_mfr(bool pack16, const DecimArgs &a, const Ra
 
 } // namespace
 
-bool plan_decimate_mfma(int log2decim, int fcpos, size_t n_used, int nstreams, size_t span_override, int n_cu, DecimArgs *a)
-{
-    // one wave per SIMD on all but one CU of every XCD (MI355X: 8 XCDs x 32 CUs -> 31 workgroups per XCD, 992 waves)
-    const int nxcd = n_cu >= 64 && n_cu % 8 == 0 ? 8 : 1;
-    const size_t waves1 = (size_t)4 * (size_t)(n_cu > nxcd ? n_cu - nxcd : n_cu);
-    const size_t waves3 = 3 * waves1 - waves1 / 13; // a round of three waves per SIMD with some slack (2900 on MI355X)
-    if (fcpos != 2 || log2decim < 2 || log2decim > 6) return false; // (decimate2_cen: the VALU kernel is HBM-bound, 63 % against 59 %)
-    const size_t W = (size_t)64 << log2decim;     // one period of the schedule = the warm-up
-    const size_t head = W > 2048 ? W : 2048;      // VALU head piece: whole passes, >= the warm-up of the first span
-    if (n_used <= head) return false;
-    const size_t n = n_used - head;
-    size_t S;
-    if (span_override) {
-        S = (span_override + W - 1) / W * W;
-    } else {
-        const size_t total = n * (size_t)nstreams;
-        if (log2decim <= 3) {
-            // short cascades (decimate4 / 8): TWO waves per SIMD, 62 workgroups per XCD (1984 waves), the spans sized from
-            // the wave count like below (tools/sweep_span.sh: 0.238 / 0.262 ms per 2^28 samples against 0.248 / 0.271 with
-            // one round of three waves per SIMD, 0.250 / 0.318 with one wave per SIMD); three per SIMD for bigger banks
-            S = (total / (waves3 * 8) + W - 1) / W * W;
-            const size_t wps2 = 2 * waves1 / (size_t)nstreams;
-            if (wps2 >= 1) {
-                size_t S2 = n / (8 * wps2) / W * W;
-                if (S2 == 0 || n / (8 * S2) > wps2) S2 += W; // (rounding down must not add a wave)
-                if (S2 <= 256 * W && S2 >= 8 * W) S = S2;
-            }
-        } else {
-            // decimate16 and up: with four and more stages per step a single wave keeps its SIMD as busy as three do
-            // (tools/sweep_span.sh, tools/bench_streams.sh), so the spans can be long and the warm-up small (3 % at 32 Ki
-            // samples and L = 4 against the 9 % of a three-waves-per-SIMD round).  One wave per SIMD: 31 workgroups per XCD
-            // (992 waves; with all 32 CUs of an XCD taken -- 1016 waves -- the launch is 3 % slower, with 1056 it takes
-            // half as long again: the launch lasts as long as its fullest CU), the spans as long as that allows, sized
-            // from the wave count so that the VALU tail stays short.  Banks too big for that (spans beyond the limit of
-            // the planner): spans of 32 Ki samples, the waves are dealt dynamically over many rounds.
-            const size_t SL = 32768 > 8 * W ? 32768 : 8 * W;
-            // (a->mf_ring == 2, decimate16 only: the two-waves-per-SIMD experiment -- 62 workgroups per XCD, spans half as long)
-            const size_t wps1 = (mf_dma_applies(log2decim) && a->mf_ring == 2 ? 2 * waves1 : waves1) / (size_t)nstreams;
-            S = SL;
-            if (wps1 >= 1) {
-                size_t S1 = n / (8 * wps1) / W * W;
-                if (S1 == 0 || n / (8 * S1) > wps1) S1 += W; // (rounding down must not add a wave)
-                // long periods (decimate32 / 64: W = 2048 / 4096) make that rounding coarse: one period less per span and a few
-                // waves more than 31 CUs per XCD hold -- they land on the 32nd -- costs ~3 %, a period more of span + warm-up per
-                // wave costs W / (S + W) (profiles/r04_decim_paths.txt: decimate64 0.2751 -> 0.2533 ms, decimate32 0.2513 -> 0.2447)
-                if (S1 > 8 * W) {
-                    const size_t S0 = S1 - W, wps0 = n / (8 * S0);
-                    if (wps0 * (size_t)nstreams <= (size_t)4 * (size_t)n_cu && (S0 + W) * 105 < (S1 + W) * 100) S1 = S0;
-                }
-                if (S1 <= 256 * W) S = S1;
-            }
-        }
-        // small calls: short spans (the launch lasts (W + S) / 32 steps of ~0.2 us whatever the size of the call)
-        const size_t smin = (log2decim <= 3 ? 8 : 2) * W;
-        if (S < smin) S = smin;
-        if (S > 256 * W) S = 256 * W;
-    }
-    size_t wps = n / (8 * S);
-    if (wps == 0 || wps > 0x7fffffffu / (size_t)nstreams) return false;
-    if (8 * S * 4 >= 0xffffffffu) return false;   // lane offsets inside a wave are 32 bits
-    size_t tail_start = head + wps * 8 * S;
-    // the register-ring waves read up to 8 steps (256 samples) past their last span (the LDS-DMA ring clamps its run-ahead)
-    if (n_used - tail_start < 256u) {
-        if (--wps == 0) return false;
-        tail_start = head + wps * 8 * S;
-    }
-    const size_t tail = n_used - tail_start;
-    const size_t seg = 16384;                     // 8 passes of the VALU code per tail piece
-    size_t ntail = (tail + seg - 1) / seg;
-    if (ntail == 0) ntail = 1;                    // the (possibly empty) last piece stores the bank state
-    a->mf_head = head;
-    a->mf_span = S;
-    a->mf_wps = (int)wps;
-    a->mf_tail_start = tail_start;
-    a->mf_tail_seg = seg;
-    a->mf_npieces = 1 + (int)ntail;
-    {
-        // piece workgroups (see decim_mfma_kernel): one piece each, unless the matrix-core workgroups own their CUs (LDS-DMA ring) and
-        // leave some free: then one EARLY workgroup per free CU with as many pieces as fit beside the matrix part (a piece of 16 Ki
-        // samples takes ~21 us, a step of the matrix-core waves ~0.2 us: half of the matrix part's time), the rest one piece each
-        const int items = nstreams * a->mf_npieces, nmf = (int)(((size_t)nstreams * wps + 3) / 4);
-        a->mf_piece_early = 0; a->mf_piece_share = 0;
-        if (mf_dma_applies(log2decim) && n_cu > nmf) {
-            int early = n_cu - nmf;
-            if (early > items) early = items;
-            int share = (int)((W + S) / 6720);
-            if (share < 3) share = 3;
-            if (share > (items + early - 1) / early) share = (items + early - 1) / early;
-            a->mf_piece_early = early; a->mf_piece_share = share;
-        }
-        const int rest = items - a->mf_piece_early * a->mf_piece_share;
-        a->mf_piece_wgs = a->mf_piece_early + (rest > 0 ? rest : 0);
-    }
-    return true;
-}
-
 hipError_t launch_rx_fused(int log2decim, bool pack16, const DecimArgs &a, const Enc128Args &e, unsigned *roles, unsigned tag, hipStream_t stream)
 {
     switch (log2decim) {
@@ -965,56 +871,6 @@ hipError_t launch_decimate_mfma(int log2decim, bool pack16, const DecimArgs &a, 
     case 6: return launch_mf<6>(pack16, a, stream);
     }
     return hipErrorInvalidValue;
-}
-
-bool plan_decimate_mfma_ragged(int log2decim, int fcpos, RaggedRow *rows, int nstreams, size_t span_override, int n_cu, DecimArgs *a)
-{
-    // the span and head the uniform planner picks for the mean stream: equal counts get the uniform launch's geometry
-    size_t total = 0;
-    for (int s = 0; s < nstreams; ++s) total += (size_t)rows[s].n_used;
-    const int L = log2decim;
-    const size_t mean = total / (size_t)nstreams / ((size_t)1 << L) * ((size_t)1 << L);
-    DecimArgs u = *a;
-    if (!plan_decimate_mfma(L, fcpos, mean, nstreams, span_override, n_cu, &u)) return false;
-    const size_t S = u.mf_span, head = u.mf_head, seg = u.mf_tail_seg;
-    long long waves = 0, pieces = 0;
-    for (int s = 0; s < nstreams; ++s) {
-        RaggedRow &r = rows[s];
-        const size_t n = (size_t)r.n_used;
-        size_t wps = n > head ? (n - head) / (8 * S) : 0;
-        size_t tail_start = head + wps * 8 * S;
-        if (wps && n - tail_start < 256u) { --wps; tail_start = head + wps * 8 * S; } // (the register ring reads 256 samples ahead)
-        size_t h = head;
-        if (!wps) { h = n < seg ? n : seg; tail_start = h; } // (no span: pieces alone, the first one from the state)
-        const size_t tail = n - tail_start;
-        const size_t np = 1 + (tail + seg - 1) / seg;
-        r.mf_w0 = (int)waves; r.mf_wps = (int)wps;
-        r.mf_p0 = (int)pieces; r.mf_np = (int)np;
-        r.mf_head = h; r.mf_tail_start = tail_start;
-        waves += (long long)wps;
-        pieces += (long long)np;
-        if (waves > 0x7fffffff || pieces > 0x7fffffff) return false;
-    }
-    if (waves == 0) return false;
-    a->mf_head = head; a->mf_span = S; a->mf_tail_seg = seg; a->mf_tail_start = 0;
-    a->mf_wps = (int)waves; a->mf_npieces = (int)pieces;
-    {
-        // the piece workgroups, as plan_decimate_mfma deals them
-        const int items = (int)pieces, nmf = (int)((waves + 3) / 4);
-        const size_t W = (size_t)64 << L;
-        a->mf_piece_early = 0; a->mf_piece_share = 0;
-        if (mf_dma_applies(L) && n_cu > nmf) {
-            int early = n_cu - nmf;
-            if (early > items) early = items;
-            int share = (int)((W + S) / 6720);
-            if (share < 3) share = 3;
-            if (share > (items + early - 1) / early) share = (items + early - 1) / early;
-            a->mf_piece_early = early; a->mf_piece_share = share;
-        }
-        const int rest = items - a->mf_piece_early * a->mf_piece_share;
-        a->mf_piece_wgs = a->mf_piece_early + (rest > 0 ? rest : 0);
-    }
-    return true;
 }
 
 hipError_t launch_decimate_mfma_ragged(int log2decim, bool pack16, const DecimArgs &a, const RaggedRow *rows, hipStream_t stream)

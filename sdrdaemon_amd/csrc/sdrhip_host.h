@@ -69,26 +69,26 @@ struct RxMeta {
     const unsigned *tab; // per-stream {fc, rate, zero-stamp CRC} on the device (DecimArgs::meta_tab), NULL: w / rate serve every stream
 };
 
+// ---- the decimator bank (sdrhip_decim.cpp)
 // device-pointer cores (no argument validation, no staging)
 int decimate_device(sdrhip_decimators *d, int log2decim, int fcpos, unsigned *sampleSize, const int16_t *in, size_t n_in,
                     size_t in_stride, int16_t *out, size_t out_stride, size_t *n_out, int frame_mode, int frame_blocks,
                     uint64_t frame_sample_base, const RxMeta *meta = nullptr, const Enc128Args *fuse = nullptr, bool *fused = nullptr,
                     bool coresident = false); // coresident: another kernel's workgroups share the CUs (ring depth 3, raised wave priority)
 // ragged calls (sdrhip_decimate_ragged, sdrhip_rx_process_ragged): ragged_prepare fills the decimator fields of rows[0..S) (the
-// caller's framing fields are kept), plans K1r and uploads the table (the decimators' own device copy, valid until the next ragged
-// call on them); decimate_ragged_device then runs the cascade with it
+// caller's framing fields are kept), plans the launch into *plan (K1r's geometry, and K1mr's when the call goes to the matrix cores:
+// plan->mfma) and uploads the table (the decimators' own device copy, valid until the next ragged call on them);
+// decimate_ragged_device then runs the cascade with the table and that plan
 // pin (optional): the caller's own pinned staging for the table instead of the handle's one -- an asynchronous batch passes its
 // ring slot's, so that the call waits for that slot's last upload, not for the previous call's
 int ragged_prepare(sdrhip_decimators *d, int log2decim, int fcpos, const size_t *n_in, RaggedRow *rows, const RaggedRow **rows_dev,
-                   PinnedBuf *pin = nullptr);
+                   RaggedPlan *plan, PinnedBuf *pin = nullptr);
 int ragged_reserve(sdrhip_decimators *d, PinnedBuf *pin); // the table's storage alone: nothing left to allocate in ragged_prepare
-// frame_mode != 0 (only when ragged_mfma_planned): the matrix-core launch stores straight into the frame layout, `out` = the frame
+// frame_mode != 0 (only when plan.mfma): the matrix-core launch stores straight into the frame layout, `out` = the frame
 // area (stream s at out + s * out_stride dwords, its window at RaggedRow out_off), meta_w / meta_rate = the shared meta words
 int decimate_ragged_device(sdrhip_decimators *d, int log2decim, int fcpos, unsigned *sampleSize, const int16_t *in, size_t in_stride,
-                           int16_t *out, size_t out_stride, const RaggedRow *rows, const RaggedRow *rows_dev, int frame_mode = 0,
-                           int frame_blocks = 0, const unsigned *meta_w = nullptr, unsigned meta_rate = 0);
-// the last ragged_prepare planned the matrix-core launch (K1mr): decimate_ragged_device will run it
-bool ragged_mfma_planned(const sdrhip_decimators *d);
+                           int16_t *out, size_t out_stride, const RaggedRow *rows, const RaggedRow *rows_dev, const RaggedPlan &plan,
+                           int frame_mode = 0, int frame_blocks = 0, const unsigned *meta_w = nullptr, unsigned meta_rate = 0);
 // host rows of n_in[s] samples of esz bytes -> [S][dstride] rows the kernels read (pinned zero-copy memory for small calls, else
 // `dev` through the pinned `pin`); only n_in[s] samples of row s are read
 int ragged_stage_in(sdrhip_ctx *c, PinnedBuf &pin, DevBuf &dev, const void *src, size_t in_stride, const size_t *n_in, int S, size_t esz,
@@ -290,12 +290,11 @@ void fecbuf_import_host(sdrhip_fecbuf *b, int s, const FecBufState &st, size_t c
 
 #define SDRHIP_KCLASSES 5 // SDRHIP_K_DECIMATE .. SDRHIP_K_CONVERT
 namespace sdrhip {
-enum { DECIM_PATH_AUTO = 0, DECIM_PATH_VALU = 1, DECIM_PATH_MFMA = 2 };
 // Kernel-path knobs of a context.  Read ONCE from the environment when the context is created (SDRHIP_DECIM_PATH =
 // valu | mfma | auto, SDRHIP_MFMA_SPAN, SDRHIP_MFMA_MIN, SDRHIP_INTERP_PATH = valu | wave, SDRHIP_INTERP_SPAN); afterwards
 // only sdrhip_ctx_set_option() changes them (tests, tools), under the context's lock.
 struct CtxOptions {
-    int decim_path = DECIM_PATH_AUTO;
+    int decim_path = DECIM_PATH_AUTO;      // DECIM_PATH_*, decim_plan.h
     size_t mfma_span = 0;                  // forced span length of the matrix-core decimator (0 = planner's choice)
     size_t mfma_min = (size_t)1 << 22;     // smallest call (samples over all streams, decimate4 / 8) the matrix cores take in auto mode
     int interp_wave = 1;                   // interpolate4 .. 64: K5w, the barrier-free wave-private pipeline (interp_wave.h); 0 = K5

@@ -1,9 +1,11 @@
-// sdrhip_internal.h -- shared between the host side (sdrhip.cpp) and the gfx950 kernels.
+// sdrhip_internal.h -- shared between the host side (sdrhip*.cpp) and the gfx950 kernels: the kernels' argument structs and launch_*
+// functions.  (What a decimator launch's geometry is decided by lives in decim_plan.h, host-only.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
+#include "decim_plan.h"
 #include "rx_depart_order.h"
 #include "rx_egress_order.h"
 
@@ -179,12 +181,7 @@ __device__ __forceinline__ void stream_meta_base(const unsigned (&shared)[6], un
 
 // returns hipSuccess or the launch error
 hipError_t launch_decimate(int log2decim, int fcpos, bool pack16, const DecimArgs &a, hipStream_t stream);
-// picks nsub_per_seg / nseg for a call (host helper living next to the kernel's geometry)
-void plan_decimate(int log2decim, int fcpos, size_t n_used, int nstreams, int *nsub_per_seg, int *nseg);
-
-// matrix-core variant of the centred cascades: fills the mf_* fields, false when the call is too short (or the
-// mode unsupported); span_override != 0 forces the span length (tests)
-bool plan_decimate_mfma(int log2decim, int fcpos, size_t n_used, int nstreams, size_t span_override, int n_cu, DecimArgs *a);
+// matrix-core variant of the centred cascades, a.mf_* from plan_decimate_mfma (decim_plan.h)
 hipError_t launch_decimate_mfma(int log2decim, bool pack16, const DecimArgs &a, hipStream_t stream);
 struct Enc128Args;
 // the same decimator launch (register-ring variant) with encoder workgroups for `e` behind it in the grid (fused Rx step)
@@ -224,9 +221,8 @@ struct RaggedRow {
     unsigned shifts;
 };
 static_assert(sizeof(RaggedRow) == 128, "RaggedRow: one 128-byte row per stream");
-// K1mr: plans the matrix-core launch of a ragged call (per-stream fields of `rows`, shared span / grid in `a`: a->mf_wps = the
-// launch's matrix-core waves, a->mf_npieces = its VALU pieces); false when no stream is long enough for a span
-bool plan_decimate_mfma_ragged(int log2decim, int fcpos, RaggedRow *rows, int nstreams, size_t span_override, int n_cu, DecimArgs *a);
+// K1mr: the matrix-core launch of a ragged call (plan_decimate_mfma_ragged, decim_plan.h: per-stream fields in the rows, shared span /
+// grid in `a`: a.mf_wps = the launch's matrix-core waves, a.mf_npieces = its VALU pieces)
 hipError_t launch_decimate_mfma_ragged(int log2decim, bool pack16, const DecimArgs &a, const RaggedRow *rows, hipStream_t stream);
 // K1r: the VALU cascade with a 1-D grid of sum_s max(1, ceil(n_used_s / segment)) workgroups; workgroup b serves the stream
 // whose seg0 range holds it (binary search over `rows`).  A stream with n_used = 0 copies its state.  a.nsub_per_seg is the

@@ -756,7 +756,8 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const RxRaggedCounts 
         }
     }
     const RaggedRow *rdev = nullptr;
-    if ((rc = ragged_prepare(rx->dec, L, rx->cfg.fcpos, n_in, rows.data(), &rdev, tabs ? &tabs->rows : nullptr))) return rc;
+    RaggedPlan plan;
+    if ((rc = ragged_prepare(rx->dec, L, rx->cfg.fcpos, n_in, rows.data(), &rdev, &plan, tabs ? &tabs->rows : nullptr))) return rc;
     if (follow) {
         // KF: the streams that have incoming meta get {fc, rate >> L, CRC} from the collector's committed m_outputMeta, in the device
         // table (over the row's own third word), behind its upload and in front of K2r, the one kernel that reads a row's words (the host's rows, `mw` and the
@@ -789,15 +790,15 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const RxRaggedCounts 
 
     // ---- decimate: the matrix-core launch (K1mr) stores straight into each stream's window (context option rx_direct, the
     // default), its VALU pieces write the meta blocks; otherwise stream order, and K2r lays each stream's samples into its window
-    const bool direct = ragged_mfma_planned(rx->dec) && c->opt.rx_direct && stream_bytes < 0x3fffffffu;
+    const bool direct = plan.mfma && c->opt.rx_direct && stream_bytes < 0x3fffffffu;
     const size_t lstride = (max_dec + 3) & ~(size_t)3;
     DevBuf &lin = rx->lin[0];
     if (direct) {
         rc = decimate_ragged_device(rx->dec, L, rx->cfg.fcpos, ss.data(), din, dstride, reinterpret_cast<int16_t *>(area), stream_bytes / 4,
-                                    rows.data(), rdev, 1, (int)FB, mw, rx->cfg.sample_rate);
+                                    rows.data(), rdev, plan, 1, (int)FB, mw, rx->cfg.sample_rate);
     } else {
         if ((rc = lin.reserve((size_t)S * lstride * 4 + 16))) return rc;
-        rc = decimate_ragged_device(rx->dec, L, rx->cfg.fcpos, ss.data(), din, dstride, lin.as<int16_t>(), lstride, rows.data(), rdev);
+        rc = decimate_ragged_device(rx->dec, L, rx->cfg.fcpos, ss.data(), din, dstride, lin.as<int16_t>(), lstride, rows.data(), rdev, plan);
     }
     if (rc) return rc;
     rx->consumed = true;
