@@ -398,7 +398,7 @@ int sdrhip_rx_frames_view(const sdrhip_rx *rx, const uint8_t **base, size_t *str
  * recovery blocks, meta blocks and frameIndex (each stream's m_frameCount wraps on its own).  A stream with n_in[s] below
  * 2^log2decim keeps its filter history, open frame and frame counter.  Input: as sdrhip_rx_process (host memory: only n_in[s]
  * samples of row s are read; device memory: its alignment rules, no sample past n_in[s] is read; sdrhip_rx_set_input_format
- * applies).  frame_stride_bytes >= (largest n_frames) * (128 + nb_fec) * 512 when frames_out is given.  Once ragged calls leave the
+ * applies, or each stream's own format and the 4-byte stride unit of sdrhip_rx_set_stream_format).  frame_stride_bytes >= (largest n_frames) * (128 + nb_fec) * 512 when frames_out is given.  Once ragged calls leave the
  * streams at different frame positions: sdrhip_rx_process runs as a ragged call with equal counts and stamps (its *n_frames = the
  * largest per-stream count), sdrhip_rx_max_frames returns the maximum over the streams, sdrhip_rx_frames_view returns SDRHIP_EINVAL
  * while the delivered windows differ, sdrhip_rx_reconfigure moves each stream's open frame (the old-meta / new-fecblk rule applies per
@@ -440,7 +440,8 @@ int sdrhip_rx_collect(sdrhip_rx *rx, uint8_t *frames_out, size_t frame_stride_by
  * allowed, and so are counts below 2^log2decim).  The ring and the batch size are those of sdrhip_rx_set_async(depth, blocks);
  * it returns SDRHIP_EBUSY when every batch of the ring is in flight.  Rows: in_stride-strided (in_stride >= the largest count),
  * or SDRHIP_PACKED: back to back, row s starting at sample sum_{t<s} n_in[t].  sdrhip_rx_set_input_format applies; the counts
- * stay in samples (an 8-bit sample is 2 bytes).  Packed input that lies wholly inside sdrhip_host_alloc memory is used IN PLACE
+ * stay in samples (an 8-bit sample is 2 bytes).  (With sdrhip_rx_set_stream_format's array set: each stream's own format, packed
+ * rows back to back in bytes, strided rows 4 * in_stride bytes apart.)  Packed input that lies wholly inside sdrhip_host_alloc memory is used IN PLACE
  * (the caller leaves it untouched until the batch is collected); anything else is copied into the pinned staging arena packed:
  * one memcpy per non-empty row, never the padding between a short row and the stride.
  * Per stream a batch is exactly one sdrhip_rx_process_ragged call: its count is the sum of the stream's counts over the batch's
@@ -846,10 +847,46 @@ int sdrhip_rx_egress_stream_blocks(const sdrhip_rx *rx, size_t *blocks);
  * How: every ragged launch takes the shift pair from its stream's row of the per-call table (one word) instead of the launch
  * arguments -- the filter-less kernel, K1r and K1mr, which keep their registers and occupancy -- and the row's third meta word
  * carries sampleBytes / sampleBits per stream, so K2r and KF form block 0 and its CRC as they did.
- * Not covered: following sampleBits from the incoming meta blocks, a per-stream input format (sdrhip_rx_set_input_format stays
- * bank-wide), the uniform step and pipelined mode, the Tx pipe. */
+ * Not covered: following sampleBits from the incoming meta blocks, the uniform step and pipelined mode, the Tx pipe.  (The input
+ * format per stream -- sdrhip_rx_set_input_format is bank-wide -- is sdrhip_rx_set_stream_format, below.) */
 int sdrhip_rx_set_stream_bits(sdrhip_rx *rx, const unsigned *sample_bits);
 int sdrhip_rx_get_stream_bits(const sdrhip_rx *rx, int stream, unsigned *sample_bits, unsigned *frame_bits);
+
+/* ---- Per-stream input format: 8- and 16-bit IQ rows in one call.
+ * In the reference the format belongs to the source object, which is per process and so per stream: RtlSdrSource.cpp:542-553 makes
+ * IQSample(buf[2i] - 128, buf[2i+1] - 128) of its offset-binary bytes, HackRFSource.cpp:661-674 makes IQSample(buf[2i], buf[2i+1])
+ * of its signed bytes, the 12- and 16-bit sources deliver int16, and sdrdaemonrx.cpp:264-374 picks one source per process.
+ * sdrhip_rx_set_stream_format: fmt = host array of nstreams entries, each SDRHIP_IQ_S16, SDRHIP_IQ_U8 or SDRHIP_IQ_S8; NULL =
+ * bank-wide again (the value of sdrhip_rx_set_input_format).  sdrhip_rx_get_stream_format: *fmt = the format in force for the stream.
+ * Contract.  Per stream the result is byte for byte that of a one-stream sdrhip_rx with sdrhip_rx_set_input_format(fmt[s]) fed the
+ * same bytes, call after call: frames, recovery blocks, meta blocks, frameIndex and all carried state.
+ * Sample size: the format implies none.  cfg.sample_bits / sdrhip_rx_set_stream_bits stay the caller's; an RTL-SDR stream sets 8 there.
+ * Entries: the setting holds through sdrhip_rx_process_ragged (host and device memory), sdrhip_rx_submit_ragged,
+ * sdrhip_rx_collect_ragged and sdrhip_rx_collect_egress, together with the stream meta, fecblk and bits arrays in any combination.
+ * While the array is set every step is the ragged step: sdrhip_rx_process, sdrhip_rx_submit and sdrhip_rx_set_pipelined(1) return
+ * SDRHIP_EINVAL with nothing consumed.  The datagram entries ignore the array, as they ignore sdrhip_rx_set_input_format: the wire
+ * carries IQSample.
+ * Addressing while the array is set.  Counts stay in samples.  Strided rows: row s starts at byte 4 * s * in_stride whatever its
+ * format; in_stride counts 4-byte units and is at least the largest count; an 8-bit row occupies the first 2 * n_in[s] bytes of its
+ * row.  Device memory: base 16-byte aligned, in_stride a multiple of 4; nothing outside a row's n_in[s] * bytes(fmt[s]) bytes is
+ * read.  Packed (in_stride = SDRHIP_PACKED, the asynchronous entry): rows back to back in bytes, row s of a block starts at
+ * sum_{t<s} n_in[t] * bytes(fmt[t]) -- an int16 row may start 2 bytes off a dword boundary.  An array of equal entries is allowed:
+ * with packed input it delivers the bytes of that bank-wide format; with strided input the stride unit is the 4-byte unit above
+ * (bank-wide 8-bit strides count 2-byte samples).
+ * The setter changes host state only: nothing is enqueued, nothing waited for.  It is refused, nothing changed, for a NULL handle,
+ * a value outside the three formats, a pipelined pipe or one with late frames waiting, and while asynchronous batches are being
+ * filled or in flight (the rule of sdrhip_rx_set_input_format): a batch has one set of formats.  sdrhip_rx_set_input_format stays
+ * allowed; while the array is set its value is unused.  sdrhip_rx_reconfigure and sdrhip_rx_reset_streams do not clear the array;
+ * export and import of a stream are untouched (the format is configuration).  A handle on which the setter was never called
+ * launches the same kernels in the same order with the same arguments.
+ * Link traffic: a ragged batch uploads exactly sum n_in[s] * bytes(fmt[s]) sample bytes ("h2d_bytes").
+ * How: K0x (rx_unpack_mixed_kernels.hip) is K0p with the format read from the stream's row of the per-call table and segment
+ * sources in 2-byte units; the synchronous call is a K0x launch with one segment per stream, over the staged upload (host memory)
+ * or the caller's rows in place (device memory) -- one pass over the int16 rows more than the bank-wide int16 call.
+ * Not covered: a per-stream decimation or Fc position, following sampleBits from the incoming meta blocks, an output format per
+ * stream of the Tx pipe. */
+int sdrhip_rx_set_stream_format(sdrhip_rx *rx, const int *fmt);
+int sdrhip_rx_get_stream_format(const sdrhip_rx *rx, int stream, int *fmt);
 
 /* ---- Per-stream lifecycle: one stream of a bank begins again while the others run on.
  * In the reference one stream is one sdrdaemonrx / sdrdaemontx process, and restarting that process gives the stream what the

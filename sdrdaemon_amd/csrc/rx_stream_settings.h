@@ -1,4 +1,4 @@
-// rx_stream_settings.h -- the per-stream settings of an Rx bank (sdrhip_rx_set_stream_meta / _fec / _bits): which value is in force
+// rx_stream_settings.h -- the per-stream settings of an Rx bank (sdrhip_rx_set_stream_meta / _fec / _bits / _format): which value is in force
 // for stream s, what a set array forces, the streams' zero-stamp records -- and the counts of a ragged step and of a datagram join:
 // what the streams will complete and deliver for given sample counts.  Pure host arithmetic (no HIP, no library header; the frame
 // area beside it is the only neighbour it sees): sdrhip_rx.cpp and the asynchronous / datagram units ask it,
@@ -79,7 +79,7 @@ struct RxBankValues {
     }
 };
 
-enum RxSetting { RX_SET_NONE = 0, RX_SET_FEC, RX_SET_BITS };
+enum RxSetting { RX_SET_NONE = 0, RX_SET_FEC, RX_SET_BITS, RX_SET_FORMAT };
 // what a setter says.  RANGE: entry `index` = `value` is out of range; NO_MEMORY; either way the old values stand
 struct RxSetResult {
     enum Kind { OK = 0, RANGE, NO_MEMORY } kind;
@@ -110,6 +110,9 @@ public:
     }
     RxSetResult set_fec(const int *nb_fec) { return set(fec_, nb_fec, 0, 128, true); }
     RxSetResult set_bits(const unsigned *sample_bits) { return set(bits_, sample_bits, 1u, 16u, true); }
+    // (the sample-fed entries' input format per stream, 0 / 1 / 2 = SDRHIP_IQ_S16 / _U8 / _S8: configuration of the input side alone,
+    // no part of the streams' records -- the version stays)
+    RxSetResult set_format(const int *fmt) { return set(fmt_, fmt, 0, 2, true, false); }
     // (the frame area's slots follow the largest count: admit_fec is set_fec without the change, for a caller that has to move the
     // open frames to slots of slot_blocks_of(nb_fec, bank) in between -- set_fec behind it cannot fail)
     RxSetResult admit_fec(const int *nb_fec) { return set(fec_, nb_fec, 0, 128, false); }
@@ -120,6 +123,8 @@ public:
     uint32_t rate(const RxBankValues &b, size_t s) const { return rate_.empty() ? b.sample_rate : rate_[s]; }
     int fec(const RxBankValues &b, size_t s) const { return fec_.empty() ? b.nb_fec : fec_[s]; }
     unsigned bits(const RxBankValues &b, size_t s) const { return bits_.empty() ? b.sample_bits : bits_[s]; }
+    int format(int bank_fmt, size_t s) const { return fmt_.empty() ? bank_fmt : fmt_[s]; }
+    const int *formats() const { return fmt_.empty() ? nullptr : fmt_.data(); } // NULL: the bank-wide format serves every stream
     // per-stream fecblk: the largest count of the bank, whether two streams differ, the super blocks of a slot of the frame area (the
     // ONE pitch; slot_blocks_of: once nb_fec is set) and of the valid head of a frame of stream s
     int fec_max(const RxBankValues &b) const { return fec_.empty() ? b.nb_fec : *std::max_element(fec_.begin(), fec_.end()); }
@@ -128,10 +133,10 @@ public:
     size_t slot_blocks_of(const int *nb_fec, const RxBankValues &b) const { return RX_NB_ORIGINAL + (size_t)(nb_fec ? *std::max_element(nb_fec, nb_fec + S_) : b.nb_fec); }
     size_t stream_blocks(const RxBankValues &b, size_t s) const { return RX_NB_ORIGINAL + (size_t)fec(b, s); }
 
-    // ---- what the arrays force: any() = the streams have records of their own; while the fecblk or the sample-size array is set
-    // every step is the ragged step (the one named is the first of the two that is set)
+    // ---- what the arrays force: any() = the streams have records of their own; while the fecblk, the sample-size or the format array
+    // is set every step is the ragged step (the one named is the first of the three that is set)
     bool any() const { return !fc_.empty() || !rate_.empty() || !fec_.empty() || !bits_.empty(); }
-    RxSetting forces_ragged() const { return !fec_.empty() ? RX_SET_FEC : !bits_.empty() ? RX_SET_BITS : RX_SET_NONE; }
+    RxSetting forces_ragged() const { return !fec_.empty() ? RX_SET_FEC : !bits_.empty() ? RX_SET_BITS : !fmt_.empty() ? RX_SET_FORMAT : RX_SET_NONE; }
 
     // ---- the streams' records for the frames the next launch opens; NULL while no array is set (the shared record of the bank-wide
     // values serves every stream).  Formed again only when a setter was called or a bank-wide value has changed since they were formed
@@ -177,13 +182,13 @@ private:
         if (v) to.assign(v, v + S_);
         else to.clear();
     }
-    template <class T> RxSetResult set(std::vector<T> &to, const T *v, T lo, T hi, bool change)
+    template <class T> RxSetResult set(std::vector<T> &to, const T *v, T lo, T hi, bool change, bool versioned = true)
     {
         for (size_t s = 0; v && s < S_; ++s)
             if (v[s] < lo || v[s] > hi) return {RxSetResult::RANGE, s, (long)v[s]};
         if (!room(to, v)) return {RxSetResult::NO_MEMORY, 0, 0};
         if (change) put(to, v);
-        version_ += change ? 1 : 0;
+        version_ += change && versioned ? 1 : 0;
         return {RxSetResult::OK, 0, 0};
     }
 
@@ -191,6 +196,7 @@ private:
     std::vector<uint32_t> fc_, rate_; // empty: the field is bank-wide
     std::vector<int> fec_;
     std::vector<unsigned> bits_;
+    std::vector<int> fmt_;
     uint64_t version_ = 0;            // counts the setters' calls
     std::pair<uint64_t, RxBankValues> key_ = {~(uint64_t)0, RxBankValues()}; // what rec_ was formed for
     RxStreamRecords rec_;

@@ -8,6 +8,7 @@
 #include "decim_plan.h"
 #include "rx_depart_order.h"
 #include "rx_egress_order.h"
+#include "rx_unpack_plan.h"
 
 // loads of data that is streamed through once (IQ input, frames): non-temporal.  tools/dma_probe.hip on MI355X: 7.1 TB/s with
 // `nt` against 6.2 TB/s with the default cache policy, register loads and LDS-DMA alike (stores: no difference).
@@ -321,6 +322,12 @@ constexpr unsigned UNPACK_WG_SAMPLES = 4096; // row samples per K0p workgroup (2
 // samples; `packed` readable 64 bytes past its last sample (the 8-bit loads of an odd segment start read 2 bytes ahead)
 hipError_t launch_unpack_packed(int fmt, const uint8_t *packed, int16_t *out, size_t out_stride, const PackRow *rows, const PackSeg *segs,
                                 int nstreams, unsigned grid, hipStream_t stream);
+// K0x (rx_unpack_mixed_kernels.hip): K0p with the format per stream (rows[s].fmt) and segment sources in 2-byte units of `src`
+// (rx_unpack_plan.h); grid = rows[nstreams].wg0 workgroups; src dword-aligned, out 16-byte aligned, out_stride a multiple of 8
+// samples.  A packed source is readable 64 bytes past its last sample (a realigned chunk reads 2 bytes ahead); strided rows that
+// start on 16 bytes are read inside their own n * bytes(fmt) bytes alone
+hipError_t launch_unpack_mixed(const void *src, int16_t *out, size_t out_stride, const UnpackXRow *rows, const UnpackXSeg *segs, int nstreams,
+                               unsigned grid, hipStream_t stream);
 // frame compaction for the download: frame k of `out` = frame list[k] of `area` (frames of frame_bytes, a multiple of 16)
 hipError_t launch_frame_gather(const uint8_t *area, size_t frame_bytes, const int32_t *list, size_t nframes, uint8_t *out, hipStream_t stream);
 

@@ -176,6 +176,10 @@ struct sdrhip_rx {
     // ---- input format (sdrhip_rx_set_input_format): 8-bit input is widened by K0 into `wide`, the decimator's int16 input
     int in_fmt = sdrhip::IQF_S16;
     sdrhip::DevBuf wide;
+    // ---- per-stream input format (sdrhip_rx_set_stream_format; the array itself is `streams`'): K0x's table of a synchronous ragged
+    // call on its way up, and the staged host rows (packed, each n * bytes(fmt) long) with their upload; K0x writes `wide`
+    sdrhip::PinnedBuf f_tab_pin, f_pin;
+    sdrhip::DevBuf f_tab, f_pk;
     // ---- ragged calls (sdrhip_rx_process_ragged)
     sdrhip::PinnedBuf r_pin, r_flist_pin; // host-row staging and the encoder's frame list
     sdrhip::DevBuf r_flist;
@@ -296,7 +300,9 @@ inline RxRaggedCounts rx_counts(const sdrhip_rx *rx, const size_t *n_in) { retur
 inline int rx_refuse_uniform(const char *who, const char *instead, RxSetting forced)
 {
     if (forced == RX_SET_NONE) return SDRHIP_OK;
-    const char *what = forced == RX_SET_FEC ? "per-stream fecblk is set (sdrhip_rx_set_stream_fec)" : "per-stream sample bits are set (sdrhip_rx_set_stream_bits)";
+    const char *what = forced == RX_SET_FEC    ? "per-stream fecblk is set (sdrhip_rx_set_stream_fec)"
+                       : forced == RX_SET_BITS ? "per-stream sample bits are set (sdrhip_rx_set_stream_bits)"
+                                               : "per-stream input formats are set (sdrhip_rx_set_stream_format)";
     return instead ? fail(SDRHIP_EINVAL, "%s: %s: use %s", who, what, instead) : fail(SDRHIP_EINVAL, "%s: %s: every step is the ragged step", who, what);
 }
 // a delivery of these counts that the caller's frames_out cannot take (`unconsumed`: the entry says that nothing was consumed)

@@ -203,6 +203,7 @@ extern "C" void sdrhip_rx_destroy(sdrhip_rx *rx)
     rx->lin[1].release();
     rx->flist.release();
     rx->wide.release();
+    rx->f_tab_pin.release(); rx->f_pin.release(); rx->f_tab.release(); rx->f_pk.release();
     rx->r_pin.release(); rx->r_flist_pin.release(); rx->r_flist.release();
     if (rx->ev_framed) (void)hipEventDestroy(rx->ev_framed);
     if (rx->ev_enc) (void)hipEventDestroy(rx->ev_enc);
@@ -384,6 +385,27 @@ extern "C" int sdrhip_rx_get_stream_bits(const sdrhip_rx *rx, int stream, unsign
     const unsigned b = rx_bits_of(rx, (size_t)stream);
     if (sample_bits) *sample_bits = b;
     if (frame_bits) *frame_bits = decimated_sample_size((unsigned)rx->cfg.log2decim, b);
+    return SDRHIP_OK;
+}
+
+// per-stream input format (RtlSdrSource.cpp:542-553, HackRFSource.cpp:661-674: the format is the source object's, and
+// sdrdaemonrx.cpp:264-374 picks one source per process).  Host array alone; a batch has ONE set of formats: the rule of
+// sdrhip_rx_set_input_format
+extern "C" int sdrhip_rx_set_stream_format(sdrhip_rx *rx, const int *fmt)
+{
+    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
+    sdrhip::CtxLock lock_(rx->ctx);
+    if (rx->pipelined || rx->late.have) return fail(SDRHIP_EINVAL, "rx_set_stream_format: not available in pipelined mode");
+    if (rx->ring.busy()) return fail(SDRHIP_EINVAL, "rx_set_stream_format: asynchronous batches are being filled or in flight: collect them first");
+    return rx_set_done(rx->streams.set_format(fmt), "rx_set_stream_format", "fmt", "SDRHIP_IQ_S16, SDRHIP_IQ_U8 or SDRHIP_IQ_S8");
+}
+
+extern "C" int sdrhip_rx_get_stream_format(const sdrhip_rx *rx, int stream, int *fmt)
+{
+    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
+    sdrhip::CtxLock lock_(rx->ctx);
+    if (int e = rx_check_stream(rx, stream, "rx_get_stream_format")) return e;
+    if (fmt) *fmt = rx->streams.format(rx->in_fmt, (size_t)stream);
     return SDRHIP_OK;
 }
 
@@ -686,6 +708,55 @@ int sdrhip::rx_ragged_room(sdrhip_rx *rx, const RxRaggedCounts &n, RxTabs *tabs)
     return SDRHIP_OK;
 }
 
+// per-stream input format, the synchronous call: ONE K0x launch with one segment per stream lays the rows out as [S][*dstride] int16
+// in rx->wide.  Host rows are staged packed -- n_in[s] * bytes(fmt[s]) per row, back to back -- and go up in one copy of exactly
+// those bytes; device rows are read in place (row s at byte 4 * s * in_stride), nothing outside a row's own bytes
+static int rx_unpack_rows(sdrhip_rx *rx, const int16_t *iq_in, size_t in_stride, const size_t *n_in, const int *fmts, bool in_dev,
+                          const int16_t **din, size_t *dstride)
+{
+    sdrhip_ctx *c = rx->ctx;
+    const size_t S = (size_t)rx->nstreams;
+    const UnpackXPlan m = unpackx_measure(n_in, 1, S, fmts);
+    size_t max_in = 0;
+    for (size_t s = 0; s < S; ++s) if (n_in[s] > max_in) max_in = n_in[s];
+    const size_t rows_bytes = (S + 1) * sizeof(UnpackXRow), tab_bytes = rows_bytes + (size_t)m.nseg * sizeof(UnpackXSeg);
+    const size_t ds = (max_in + 7) & ~(size_t)7;
+    int rc;
+    if ((rc = rx->f_tab_pin.reserve(tab_bytes))) return rc; // (waits for the upload of the previous call's table)
+    if ((rc = reserve_settled(c, rx->f_tab, tab_bytes))) return rc;
+    if ((rc = rx->wide.reserve(S * ds * 4 + 16))) return rc;
+    const void *src = iq_in;
+    if (!in_dev) {
+        if ((rc = rx->f_pin.reserve((size_t)m.bytes))) return rc; // (waits for the previous call's upload)
+        if ((rc = reserve_settled(c, rx->f_pk, (size_t)m.bytes + 64))) return rc;
+        char *dst = rx->f_pin.as<char>();
+        for (size_t s = 0; s < S; ++s) {
+            const size_t bytes = n_in[s] * unpackx_sample_bytes(fmts[s]);
+            if (bytes) memcpy(dst, reinterpret_cast<const char *>(iq_in) + s * in_stride * 4, bytes);
+            dst += bytes;
+        }
+        HIP_TRY(link_copy(c, rx->f_pk.p, rx->f_pin.p, (size_t)m.bytes, hipMemcpyHostToDevice, c->stream));
+        rx->f_pin.mark(c->stream);
+        src = rx->f_pk.p;
+    }
+    UnpackXRow *rows = rx->f_tab_pin.as<UnpackXRow>();
+    UnpackXSeg *segs = reinterpret_cast<UnpackXSeg *>(rx->f_tab_pin.as<char>() + rows_bytes);
+    if (!unpackx_fill(n_in, 1, S, fmts, in_dev ? 2 * (uint64_t)in_stride : 0, rows, segs).fits)
+        return fail(SDRHIP_EINVAL, "rx_process_ragged: too many samples for one launch");
+    HIP_TRY(hipMemcpyAsync(rx->f_tab.p, rx->f_tab_pin.p, tab_bytes, hipMemcpyHostToDevice, c->stream)); // (not counted: a table)
+    rx->f_tab_pin.mark(c->stream);
+    hipError_t e;
+    {
+        KTimer kt(c, SDRHIP_K_CONVERT);
+        e = launch_unpack_mixed(src, rx->wide.as<int16_t>(), ds, rx->f_tab.as<UnpackXRow>(),
+                                reinterpret_cast<const UnpackXSeg *>(rx->f_tab.as<char>() + rows_bytes), (int)S, (unsigned)m.grid, c->stream);
+    }
+    if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "unpack launch: %s", hipGetErrorString(e));
+    *din = rx->wide.as<int16_t>();
+    *dstride = ds;
+    return SDRHIP_OK;
+}
+
 // Every stream takes its own count: K0r (8-bit input) -> K1r / filter-less kernel into stream order -> K2r into each stream's
 // own window -> one encoder launch over the list of every stream's completed frames.  A call that fails after it moved windows
 // leaves the windows moved (the open frames lie there now) and the rest of the framing state untouched.
@@ -709,8 +780,11 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const RxRaggedCounts 
     if (S == 1) in_stride = max_in;
     if (S > 1 && in_stride < max_in) return fail(SDRHIP_EINVAL, "rx_process_ragged: in_stride smaller than the largest count");
     if (max_in && !iq_in) return fail(SDRHIP_EINVAL, "rx_process_ragged: NULL input");
-    const bool wide8 = rx->in_fmt != IQF_S16 && !batch && !dev_rows;
+    // (per-stream input format: the caller's rows are K0x's source, 4-byte units of stride whatever a row holds)
+    const int *fmts = !batch && !dev_rows ? rx->streams.formats() : nullptr;
+    const bool wide8 = rx->in_fmt != IQF_S16 && !batch && !dev_rows && !fmts;
     const bool in_dev = mem == SDRHIP_MEM_DEVICE || dev_rows;
+    if (fmts && !unpackx_measure(n_in, 1, (size_t)S, fmts).fits) return fail(SDRHIP_EINVAL, "rx_process_ragged: too many samples for one launch");
     if (max_in && in_dev && (!aligned16(iq_in) || (S > 1 && (in_stride & (wide8 ? 7 : 3)))))
         return fail(SDRHIP_EALIGN, "rx_process_ragged: device input must be 16-byte aligned, its stride a multiple of %d samples", wide8 ? 8 : 4);
     if (int e = rx_refuse_delivery("rx_process_ragged", n, frames_out, frame_stride_bytes, mem, false)) return e;
@@ -770,7 +844,9 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const RxRaggedCounts 
     const int16_t *din = iq_in;
     size_t dstride = in_stride;
     const void *src = iq_in;
-    if (!in_dev) {
+    if (fmts) {
+        if ((rc = rx_unpack_rows(rx, iq_in, in_stride, n_in, fmts, in_dev, &din, &dstride))) return rc;
+    } else if (!in_dev) {
         dstride = wide8 ? (max_in + 7) & ~(size_t)7 : (max_in + 3) & ~(size_t)3;
         if ((rc = ragged_stage_in(c, rx->r_pin, c->in, iq_in, in_stride, n_in, S, wide8 ? 2 : 4, dstride, &src))) return rc;
         din = static_cast<const int16_t *>(src);

@@ -689,6 +689,7 @@ class RxPipe(_Handle):
         self.cfg = RxConfig(log2decim, fcpos, hb_variant, sample_bits, nb_fec, center_frequency_khz, sample_rate)
         self.m_error = ""
         self._stream_fec = None  # set_stream_fec's array (None: nb_fec is bank-wide)
+        self._stream_formats = None  # set_stream_formats' names (None: input_format is bank-wide)
         self.last_blocks_per_frame, self.last_stream_blocks = 0, None
         self.m_device_rate = sample_rate << log2decim  # DeviceSource::get_sample_rate(): the sink gets it >> decim
         check(ctx.lib.sdrhip_rx_create(ctx.h, nstreams, C.byref(self.cfg), C.byref(self.h)))
@@ -795,6 +796,74 @@ class RxPipe(_Handle):
         b, fb = C.c_uint(0), C.c_uint(0)
         check(self.ctx.lib.sdrhip_rx_get_stream_bits(self.h, int(stream), C.byref(b), C.byref(fb)))
         return b.value, fb.value
+
+    def set_stream_formats(self, formats=None):
+        """Per-stream input format (sdrhip_rx_set_stream_format): a sequence of nstreams names, each "s16" | "u8" | "s8" -- what
+        every stream's source delivers -- for the sample-fed ragged entries; None = bank-wide again (set_input_format's value).
+        While it is set process(), submit() and pipelined mode raise, and process_ragged / submit_ragged take a list of S arrays
+        (n_s, 2) of each stream's own dtype (packed, or laid into rows of 4-byte units, for the caller), a packed 1-D uint8 buffer
+        (submit_ragged uses one from Context.host_alloc in place) or uint8 rows (S, 4 * in_stride).  The datagram entries ignore
+        it.  Never synchronises; refused (SdrHipError) in pipelined mode and while batches are being filled or in flight."""
+        names = None if formats is None else list(formats)
+        codes = None if names is None else [_iq_format(f, ("s16", "u8", "s8"))[0] for f in names]
+        arr, _ = self._stream_ints("formats", codes, C.c_int, "formats")
+        check(self.ctx.lib.sdrhip_rx_set_stream_format(self.h, arr))
+        self._stream_formats = names
+
+    def stream_format(self, stream):
+        """-> "s16" | "u8" | "s8": the format the sample-fed entries read the stream's rows in"""
+        f = C.c_int(0)
+        check(self.ctx.lib.sdrhip_rx_get_stream_format(self.h, int(stream), C.byref(f)))
+        return [k for k, v in _IQ_FORMATS.items() if v[0] == f.value][0]
+
+    def _formatted_input(self, iq, counts, packed):
+        """an input of the ragged entries while set_stream_formats' array is set -> (uint8 buffer, counts, in_stride in 4-byte
+        units (0 = packed), whether it is a torch tensor).  packed: the entry takes packed rows (submit_ragged); otherwise a
+        list or a packed buffer is laid into rows"""
+        S, fm = self.nstreams, self._stream_formats
+        bps = np.array([4 if f == "s16" else 2 for f in fm], dtype=np.int64)
+        if isinstance(iq, (list, tuple)):
+            if len(iq) != S:
+                raise ValueError("one array per stream")
+            rows = []
+            for s, a in enumerate(iq):
+                a = np.asarray(a)
+                if a.dtype != _IQ_FORMATS[fm[s]][1] or a.ndim != 2 or a.shape[1] != 2:
+                    raise TypeError("stream %d: (n, 2) of %s expected" % (s, np.dtype(_IQ_FORMATS[fm[s]][1]).name))
+                rows.append(np.ascontiguousarray(a))
+            cnt = np.asarray([r.shape[0] for r in rows] if counts is None else counts, dtype=np.int64).reshape(-1)
+            if cnt.shape[0] != S or any(c < 0 or c > r.shape[0] for c, r in zip(cnt, rows)):
+                raise ValueError("counts: one per stream, each within its array")
+            parts = [rows[s][:cnt[s]].reshape(-1).view(np.uint8) for s in range(S)]
+            flat = np.concatenate(parts) if S else np.zeros(0, np.uint8)
+        else:
+            is_t = _is_torch(iq)
+            a = iq if is_t else np.asarray(iq)
+            if a.dtype != (torch.uint8 if is_t else np.uint8) or a.ndim not in (1, 2):
+                raise TypeError("a list of per-stream arrays, a packed 1-D uint8 buffer or uint8 rows (S, 4 * in_stride) expected")
+            if a.ndim == 2:  # rows in place: row s holds counts[s] samples of its format at its start
+                row_bytes = a.stride(0) if is_t else a.strides[0]
+                if a.shape[0] != S or row_bytes % 4 or (a.stride(1) if is_t else a.strides[1]) != 1:
+                    raise ValueError("uint8 rows: (%d, 4 * in_stride), bytes contiguous" % S)
+                cnt = _counts(counts, S, a.shape[1] // 2)
+                if S and int((cnt * bps).max()) > a.shape[1]:
+                    raise ValueError("a row is shorter than its count takes")
+                return a, cnt, max(row_bytes // 4, 1), is_t
+            if is_t:
+                raise TypeError("packed input is host memory")
+            flat = np.ascontiguousarray(a)
+            cnt = _counts(counts, S, flat.size // 2)
+            if int((cnt * bps).sum()) != flat.size:
+                raise ValueError("packed input holds %d bytes, the counts take %d" % (flat.size, int((cnt * bps).sum())))
+        if packed:
+            return flat, cnt, 0, False
+        stride = max((int(cnt.max()) + 3) & ~3, 4) if S else 4
+        buf, off = np.zeros((S, 4 * stride), np.uint8), 0
+        for s in range(S):
+            n = int(cnt[s] * bps[s])
+            buf[s, :n] = flat[off:off + n]
+            off += n
+        return buf, cnt, stride, False
 
     def _stream_ints(self, name, values, ctype, what, lo=None, hi=None):
         """a per-stream setter's argument: a sequence of nstreams ints, each lo..hi where a bound is given -> (its ctypes array, the
@@ -910,10 +979,18 @@ class RxPipe(_Handle):
         """one block per stream with its own count, returns at once.  iq: numpy rows (S, >= max(counts), 2) -- stream s takes
         counts[s] samples of row s -- or the packed samples, 1-D or (sum(counts), 2), stream after stream (memory from
         Context.host_alloc is used in place; keep it untouched until the batch is collected).  tv_sec / tv_usec: per stream or
-        scalars (None = 0).  Raises SdrHipError(code SDRHIP_EBUSY = -6) when every batch of the ring is in flight."""
+        scalars (None = 0).  With set_stream_formats' array set iq is a list of S arrays (n_s, 2) of each stream's own dtype (packed
+        for the caller; counts may be None), a packed 1-D uint8 buffer (used in place when it is Context.host_alloc memory) or uint8
+        rows (S, 4 * in_stride).  Raises SdrHipError(code SDRHIP_EBUSY = -6) when every batch of the ring is in flight."""
         if _is_torch(iq):
             raise TypeError("submit_ragged takes host memory")
         S = self.nstreams
+        if self._stream_formats is not None:  # (set_stream_formats: packed bytes, or uint8 rows of 4-byte units)
+            a, cnt, stride, _ = self._formatted_input(iq, counts, packed=True)
+            check(self.ctx.lib.sdrhip_rx_submit_ragged(self.h, _ptr(a), (C.c_size_t * S)(*cnt.tolist()), stride, _stamps(tv_sec, S),
+                                                       _stamps(tv_usec, S)))
+            self._log.block("ragged", cnt, self._slot_fec())
+            return
         a = np.asarray(iq)
         it = np.dtype(self._in_dtype).itemsize
         if a.dtype != self._in_dtype:
@@ -1005,14 +1082,20 @@ class RxPipe(_Handle):
         """sdrhip_rx_process_ragged: stream s takes counts[s] samples of row s of iq (S, >= max(counts), 2), stamped tv_sec[s] /
         tv_usec[s] (scalars apply to every stream).  -> (frames (S, max_frames, 128 + nb_fec, 512) uint8, n_frames numpy (S,)):
         stream s's frames are frames[s, :n_frames[s]].  With set_stream_fec's array set: (a list of S arrays (n_frames[s],
-        128 + nb_fec[s], 512), n_frames)."""
-        x, is_t, _ = self._ragged_input(iq)
-        S = x.shape[0]
-        cnt, c_cnt, c_sec, c_usec = self._ragged_args(x, counts, tv_sec, tv_usec)
+        128 + nb_fec[s], 512), n_frames).  With set_stream_formats' array set iq is a list of S arrays (n_s, 2) of each stream's own
+        dtype (counts may be None: every array whole), a packed 1-D uint8 buffer, or uint8 rows (S, 4 * in_stride), numpy or CUDA."""
+        if self._stream_formats is not None:  # (set_stream_formats: uint8 rows of 4-byte units, each stream in its own format)
+            x, cnt, in_stride, is_t = self._formatted_input(iq, counts, packed=False)
+            S = self.nstreams
+            c_cnt, c_sec, c_usec = (C.c_size_t * S)(*cnt.tolist()), _stamps(tv_sec, S), _stamps(tv_usec, S)
+        else:
+            x, is_t, _ = self._ragged_input(iq)
+            S, in_stride = x.shape[0], _stride_samples(x)
+            cnt, c_cnt, c_sec, c_usec = self._ragged_args(x, counts, tv_sec, tv_usec)
         cap = max(self.max_frames(int(cnt.max()) if S else 0), 1)
         out, stride_bytes = _frame_buffer(S, cap, self._slot_fec(), x.device if is_t else None, out)
         nf = (C.c_size_t * S)()
-        check(self.ctx.lib.sdrhip_rx_process_ragged(self.h, _ptr(x), c_cnt, _stride_samples(x), c_sec, c_usec, _ptr(out),
+        check(self.ctx.lib.sdrhip_rx_process_ragged(self.h, _ptr(x), c_cnt, in_stride, c_sec, c_usec, _ptr(out),
                                                     stride_bytes, nf, MEM_DEVICE if is_t else MEM_HOST))
         n_frames = np.array(nf[:], dtype=np.int64)
         if self._stream_fec is not None:
@@ -1035,13 +1118,18 @@ class RxPipe(_Handle):
 
     def process_view_ragged(self, iq, counts, tv_sec=0, tv_usec=0):
         """Zero-copy ragged call for CUDA tensors: -> (list of S frame tensors as frames_view_ragged, n_frames numpy (S,))"""
-        x, is_t, _ = self._ragged_input(iq)
+        if self._stream_formats is not None:  # (set_stream_formats: uint8 device rows (S, 4 * in_stride))
+            x, cnt, in_stride, is_t = self._formatted_input(iq, counts, packed=False)
+            S = self.nstreams
+            c_cnt, c_sec, c_usec = (C.c_size_t * S)(*cnt.tolist()), _stamps(tv_sec, S), _stamps(tv_usec, S)
+        else:
+            x, is_t, _ = self._ragged_input(iq)
+            S, in_stride = x.shape[0], _stride_samples(x)
+            _, c_cnt, c_sec, c_usec = self._ragged_args(x, counts, tv_sec, tv_usec)
         if not is_t:
             raise TypeError("process_view_ragged needs a CUDA tensor")
-        S = x.shape[0]
-        _, c_cnt, c_sec, c_usec = self._ragged_args(x, counts, tv_sec, tv_usec)
         nf = (C.c_size_t * S)()
-        check(self.ctx.lib.sdrhip_rx_process_ragged(self.h, _ptr(x), c_cnt, _stride_samples(x), c_sec, c_usec, C.c_void_p(0), 0, nf,
+        check(self.ctx.lib.sdrhip_rx_process_ragged(self.h, _ptr(x), c_cnt, in_stride, c_sec, c_usec, C.c_void_p(0), 0, nf,
                                                     MEM_DEVICE))
         return self.frames_view_ragged(x.device), np.array(nf[:], dtype=np.int64)
 
