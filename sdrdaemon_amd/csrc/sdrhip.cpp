@@ -31,52 +31,6 @@ int fail(int code, const char *fmt, ...)
     return code;
 }
 
-int DevBuf::reserve(size_t n)
-{
-    if (n <= cap) return 0;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = n + n / 4 + 256;
-    if (hipMalloc(&p, want) != hipSuccess) { p = nullptr; return fail(SDRHIP_ENOMEM, "hipMalloc(%zu) failed", want); }
-    cap = want;
-    return 0;
-}
-
-void DevBuf::release()
-{
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-}
-
-int PinnedBuf::reserve(size_t n)
-{
-    if (pending) { (void)hipEventSynchronize(ev); pending = false; }
-    if (n <= cap) return 0;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = n + n / 2 + 4096;
-    if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { p = nullptr; return fail(SDRHIP_ENOMEM, "hipHostMalloc(%zu) failed", want); }
-    cap = want;
-    if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return fail(SDRHIP_EDEVICE, "hipEventCreate");
-    return 0;
-}
-
-void PinnedBuf::mark(hipStream_t s)
-{
-    if (ev && hipEventRecord(ev, s) == hipSuccess) pending = true;
-}
-
-void PinnedBuf::release()
-{
-    if (pending) (void)hipEventSynchronize(ev);
-    if (p) (void)hipHostFree(p);
-    if (ev) (void)hipEventDestroy(ev);
-    p = nullptr; cap = 0; ev = nullptr; pending = false;
-}
-
 } // namespace sdrhip
 
 extern "C" const char *sdrhip_last_error(void) { return g_err.c_str(); }

@@ -10,10 +10,10 @@ using namespace sdrhip;
 
 // ------------------------------------------------------------------------------ decimators
 struct sdrhip_decimators {
-    sdrhip_ctx *ctx;
+    sdrhip::CtxRef ctx; // (first: released last)
     int nstreams;
     int bias;
-    int32_t *state[2]; // double buffered [nstreams][DEC_STATE_WORDS]
+    sdrhip::DevBuf state[2]; // double buffered [nstreams][DEC_STATE_WORDS]
     int cur;
     bool stage0_int16; // history of m_decimator2 fits int16 (it last saw raw samples or nothing)
     sdrhip::DecimPlanInfo last; // what the last call launched
@@ -21,6 +21,7 @@ struct sdrhip_decimators {
     sdrhip::PinnedBuf rows_pin, stage_pin, out_pin;
     sdrhip::DevBuf rows_dev;
     sdrhip::StreamMask reset_mask; // sdrhip_decimators_reset_streams
+    explicit sdrhip_decimators(sdrhip_ctx *c) : ctx(c) {}
 };
 
 extern "C" int sdrhip_decimators_last_plan(const sdrhip_decimators *d, sdrhip_decim_plan *out)
@@ -37,18 +38,14 @@ extern "C" int sdrhip_decimators_create(sdrhip_ctx *ctx, int nstreams, int hb_va
     if (!ctx || !out || nstreams <= 0 || nstreams > 65535) return fail(SDRHIP_EINVAL, "decimators_create: bad argument");
     if (hb_variant != SDRHIP_HB_EO1 && hb_variant != SDRHIP_HB_DB) return fail(SDRHIP_EINVAL, "hb_variant must be SDRHIP_HB_EO1 or SDRHIP_HB_DB");
     HIP_TRY(hipSetDevice(ctx->device));
-    sdrhip_decimators *d = new (std::nothrow) sdrhip_decimators();
+    sdrhip_decimators *d = new (std::nothrow) sdrhip_decimators(ctx);
     if (!d) return fail(SDRHIP_ENOMEM, "out of host memory");
-    d->ctx = ctx; d->nstreams = nstreams; d->bias = hb_variant; d->cur = 0; d->stage0_int16 = true;
+    d->nstreams = nstreams; d->bias = hb_variant; d->cur = 0; d->stage0_int16 = true;
     size_t bytes = (size_t)nstreams * DEC_STATE_WORDS * sizeof(int32_t);
-    d->state[0] = d->state[1] = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&d->state[0]), bytes) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&d->state[1]), bytes) != hipSuccess) {
-        if (d->state[0]) (void)hipFree(d->state[0]);
+    if (d->state[0].alloc_exact(bytes) || d->state[1].alloc_exact(bytes)) {
         delete d;
         return fail(SDRHIP_ENOMEM, "hipMalloc decimator state");
     }
-    ctx_retain(ctx);
     *out = d;
     return sdrhip_decimators_reset(d);
 }
@@ -58,11 +55,6 @@ extern "C" void sdrhip_decimators_destroy(sdrhip_decimators *d)
     if (!d) return;
     (void)hipSetDevice(d->ctx->device);
     (void)hipStreamSynchronize(d->ctx->stream);
-    (void)hipFree(d->state[0]);
-    (void)hipFree(d->state[1]);
-    d->rows_pin.release(); d->stage_pin.release(); d->out_pin.release(); d->rows_dev.release();
-    d->reset_mask.release();
-    ctx_release(d->ctx);
     delete d;
 }
 
@@ -71,8 +63,8 @@ extern "C" int sdrhip_decimators_reset(sdrhip_decimators *d)
     if (!d) return fail(SDRHIP_EINVAL, "decimators is NULL");
     sdrhip::CtxLock lock_(d->ctx);
     size_t bytes = (size_t)d->nstreams * DEC_STATE_WORDS * sizeof(int32_t);
-    HIP_TRY(hipMemsetAsync(d->state[0], 0, bytes, d->ctx->stream)); // ctor zero fill, EO1.h:171-188
-    HIP_TRY(hipMemsetAsync(d->state[1], 0, bytes, d->ctx->stream));
+    HIP_TRY(hipMemsetAsync(d->state[0].p, 0, bytes, d->ctx->stream)); // ctor zero fill, EO1.h:171-188
+    HIP_TRY(hipMemsetAsync(d->state[1].p, 0, bytes, d->ctx->stream));
     d->cur = 0;
     d->stage0_int16 = true;
     return SDRHIP_OK;
@@ -81,7 +73,7 @@ extern "C" int sdrhip_decimators_reset(sdrhip_decimators *d)
 namespace sdrhip {
 void decimators_reset_part(sdrhip_decimators *d, StreamResetArgs *a)
 {
-    a->rows[0] = d->state[0]; a->rows[1] = d->state[1];
+    a->rows[0] = d->state[0].as<int32_t>(); a->rows[1] = d->state[1].as<int32_t>();
     a->row_words = DEC_STATE_WORDS;
 }
 void decimators_reset_done(sdrhip_decimators *d, bool all)
@@ -89,7 +81,7 @@ void decimators_reset_done(sdrhip_decimators *d, bool all)
     // (bank-wide: the streams that were not reset may still hold rotate-sums in m_decimator2's history)
     if (all) d->stage0_int16 = true;
 }
-int32_t *decimators_row(sdrhip_decimators *d, int s, int half) { return d->state[d->cur ^ (half & 1)] + (size_t)s * DEC_STATE_WORDS; }
+int32_t *decimators_row(sdrhip_decimators *d, int s, int half) { return d->state[d->cur ^ (half & 1)].as<int32_t>() + (size_t)s * DEC_STATE_WORDS; }
 bool decimators_stage0_int16(const sdrhip_decimators *d) { return d->stage0_int16; }
 void decimators_clear_stage0_int16(sdrhip_decimators *d) { d->stage0_int16 = false; }
 } // namespace sdrhip
@@ -149,7 +141,7 @@ int decimate_core(sdrhip_decimators *d, unsigned L, int fcpos, const DecimCall &
     DecimArgs a;
     memset(&a, 0, sizeof(a));
     a.in = k.in; a.out = k.out; a.in_stride = k.in_stride; a.out_stride = k.out_stride;
-    a.state_cur = d->state[d->cur]; a.state_next = d->state[d->cur ^ 1];
+    a.state_cur = d->state[d->cur].as<int32_t>(); a.state_next = d->state[d->cur ^ 1].as<int32_t>();
     a.nstreams = d->nstreams;
     a.bias = d->bias;
     a.frame_mode = k.frame_mode; a.frame_blocks = k.frame_blocks;

@@ -7,17 +7,18 @@
 #include "sdrhip_host.h"
 
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
 using namespace sdrhip;
 
 struct sdrhip_fecbuf {
-    sdrhip_ctx *ctx;
+    CtxRef ctx;                  // (first: released last)
     int nstreams;
     int cur = 0;                 // state[cur] is the committed collector state
-    FecBufState *state[2] = {nullptr, nullptr};
-    uint8_t *carry = nullptr;    // [2][S][128][512] the open slots' first 128 super blocks
+    DevBuf state[2];             // [S] FecBufState each
+    DevBuf carry;                // [2][S][128][512] the open slots' first 128 super blocks
     DevBuf small;                // ndg [S], job_off [S + 1], dbase [S], rec_base [S] (int64), counts [S][FB_COUNTS], pub [S][max_frames]
     DevBuf rec, stage, dmap, dec_out, dec_b0;
     DevBuf hin, hout, hb0;       // SDRHIP_MEM_HOST staging on the device
@@ -32,6 +33,8 @@ struct sdrhip_fecbuf {
     DevBuf join_carry;
     std::vector<size_t> join_carry_host;
     StreamMask reset_mask;       // sdrhip_fecbuf_reset_streams
+    explicit sdrhip_fecbuf(sdrhip_ctx *c) : ctx(c) {}
+    FecBufState *st(int half) const { return state[half].as<FecBufState>(); }
 };
 
 namespace sdrhip {
@@ -46,7 +49,7 @@ void fecbuf_fresh_state(FecBufState *x)
 
 void fecbuf_reset_part(sdrhip_fecbuf *b, StreamResetArgs *a)
 {
-    a->fb[0] = b->state[0]; a->fb[1] = b->state[1];
+    a->fb[0] = b->st(0); a->fb[1] = b->st(1);
     a->carry = b->join_carry.as<unsigned>(); // (NULL while no datagram entry of an Rx pipe has run: nothing is held back)
     fecbuf_fresh_state(&a->fb_init.st);
 }
@@ -65,8 +68,8 @@ void fecbuf_reset_done(sdrhip_fecbuf *b, const uint8_t *mask)
 
 void fecbuf_stream_ref(sdrhip_fecbuf *b, int s, FecBufStreamRef *out)
 {
-    out->st[0] = b->state[b->cur] + s; out->st[1] = b->state[b->cur ^ 1] + s;
-    out->carry = b->carry + (size_t)s * 128 * SDRHIP_UDPSIZE;
+    out->st[0] = b->st(b->cur) + s; out->st[1] = b->st(b->cur ^ 1) + s;
+    out->carry = b->carry.as<uint8_t>() + (size_t)s * 128 * SDRHIP_UDPSIZE;
     out->carry_half = (size_t)b->nstreams * 128 * SDRHIP_UDPSIZE;
 }
 
@@ -159,8 +162,8 @@ FecBufArgs fecbuf_args(const sdrhip_fecbuf *b, const FecBufTable &t, uint8_t *de
     a.pub = at<FecBufPub>(dev, t.pub);
     a.rec = b->rec.as<FecBufRec>();
     a.max_frames = (int)max_frames;
-    a.st_cur = b->state[b->cur]; a.st_next = b->state[b->cur ^ 1];
-    a.carry_cur_base = b->carry; a.carry_base = b->carry;
+    a.st_cur = b->st(b->cur); a.st_next = b->st(b->cur ^ 1);
+    a.carry_cur_base = b->carry.as<uint8_t>(); a.carry_base = b->carry.as<uint8_t>();
     a.nstreams = b->nstreams;
     a.data_out = data_out; a.data_stride = data_stride; a.block0_out = block0_out;
     return a;
@@ -225,7 +228,7 @@ int fecbuf_init_state(sdrhip_fecbuf *b)
         HIP_TRY(hipMemsetAsync(b->join_carry.p, 0, (size_t)b->nstreams * sizeof(unsigned), b->ctx->stream));
         b->join_carry_host.assign((size_t)b->nstreams, 0);
     }
-    HIP_TRY(link_copy(b->ctx, b->state[0], st.data(), st.size() * sizeof(FecBufState), hipMemcpyHostToDevice, b->ctx->stream));
+    HIP_TRY(link_copy(b->ctx, b->st(0), st.data(), st.size() * sizeof(FecBufState), hipMemcpyHostToDevice, b->ctx->stream));
     HIP_TRY(hipStreamSynchronize(b->ctx->stream));
     return SDRHIP_OK;
 }
@@ -282,24 +285,18 @@ int fecbuf_device(sdrhip_fecbuf *b, const uint8_t *dg, const size_t *n_dgrams, s
 extern "C" int sdrhip_fecbuf_create(sdrhip_ctx *ctx, int nstreams, sdrhip_fecbuf **out)
 {
     if (!ctx || !out || nstreams <= 0 || nstreams > 65535) return fail(SDRHIP_EINVAL, "fecbuf_create: bad argument");
+    std::unique_ptr<sdrhip_fecbuf> b; // (in front of the lock: a failure deletes it behind the lock's scope)
     sdrhip::CtxLock lock_(ctx);
     if (sdrhip_device_count() <= 0) return fail(SDRHIP_EDEVICE, "fecbuf_create: no GPU");
     HIP_TRY(hipSetDevice(ctx->device));
-    sdrhip_fecbuf *b = new (std::nothrow) sdrhip_fecbuf();
+    b.reset(new (std::nothrow) sdrhip_fecbuf(ctx));
     if (!b) return fail(SDRHIP_ENOMEM, "out of host memory");
-    b->ctx = ctx; b->nstreams = nstreams;
+    b->nstreams = nstreams;
     const size_t sb = (size_t)nstreams * sizeof(FecBufState), cb = (size_t)2 * nstreams * 128 * SDRHIP_UDPSIZE;
-    if (hipMalloc(reinterpret_cast<void **>(&b->state[0]), sb) != hipSuccess || hipMalloc(reinterpret_cast<void **>(&b->state[1]), sb) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&b->carry), cb) != hipSuccess) {
-        if (b->state[0]) (void)hipFree(b->state[0]);
-        if (b->state[1]) (void)hipFree(b->state[1]);
-        delete b;
-        return fail(SDRHIP_ENOMEM, "hipMalloc fecbuf state");
-    }
-    ctx_retain(ctx);
-    int rc = fecbuf_init_state(b);
-    if (rc) { sdrhip_fecbuf_destroy(b); return rc; }
-    *out = b;
+    if (b->state[0].alloc_exact(sb) || b->state[1].alloc_exact(sb) || b->carry.alloc_exact(cb)) return fail(SDRHIP_ENOMEM, "hipMalloc fecbuf state");
+    int rc = fecbuf_init_state(b.get());
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; } // (nothing of the upload stays in flight when the state goes)
+    *out = b.release();
     return SDRHIP_OK;
 }
 
@@ -311,16 +308,8 @@ extern "C" void sdrhip_fecbuf_destroy(sdrhip_fecbuf *b)
         sdrhip::CtxLock lock_(c);
         (void)hipSetDevice(c->device);
         (void)hipStreamSynchronize(c->stream);
-        (void)hipFree(b->state[0]); (void)hipFree(b->state[1]); (void)hipFree(b->carry);
-        b->small.release(); b->rec.release(); b->stage.release(); b->dmap.release(); b->dec_out.release(); b->dec_b0.release();
-        b->hin.release(); b->hout.release(); b->hb0.release(); b->demux.release();
-        b->pin_up.release(); b->pin_down.release(); b->pin_in.release();
-        b->atab.release();
-        b->join_carry.release();
-        b->reset_mask.release();
     }
-    delete b;
-    ctx_release(c);
+    delete b; // (no lock held: the last reference frees the mutex)
 }
 
 extern "C" int sdrhip_fecbuf_reset(sdrhip_fecbuf *b)
@@ -517,7 +506,7 @@ int fecbuf_shadow(sdrhip_fecbuf *b, std::vector<FecBufShadow> *out)
     const int S = b->nstreams;
     if (!b->shadow_ok) { // (the first batch after anything else moved the collector: one copy + one synchronisation)
         std::vector<FecBufState> st((size_t)S);
-        HIP_TRY(hipMemcpyAsync(st.data(), b->state[b->cur], st.size() * sizeof(FecBufState), hipMemcpyDeviceToHost, b->ctx->stream));
+        HIP_TRY(hipMemcpyAsync(st.data(), b->st(b->cur), st.size() * sizeof(FecBufState), hipMemcpyDeviceToHost, b->ctx->stream));
         HIP_TRY(hipStreamSynchronize(b->ctx->stream));
         b->shadow.assign((size_t)S, FecBufShadow());
         for (int s = 0; s < S; ++s) {
@@ -769,7 +758,7 @@ int fecbuf_join_carry(sdrhip_fecbuf *b, unsigned **dev, std::vector<size_t> **ho
     return SDRHIP_OK;
 }
 
-const FecBufState *fecbuf_committed_state(const sdrhip_fecbuf *b) { return b->state[b->cur]; }
+const FecBufState *fecbuf_committed_state(const sdrhip_fecbuf *b) { return b->st(b->cur); }
 } // namespace sdrhip
 
 // --------------------------------------------------------------------------- the bank's call on an arrival-order array
@@ -836,7 +825,7 @@ extern "C" int sdrhip_fecbuf_stats(sdrhip_fecbuf *b, int stream, int *cur_nb_blo
     if (stream < 0 || stream >= b->nstreams) return fail(SDRHIP_EINVAL, "fecbuf_stats: stream out of range");
     HIP_TRY(hipSetDevice(b->ctx->device));
     FecBufState x;
-    FecBufState *d = b->state[b->cur] + stream;
+    FecBufState *d = b->st(b->cur) + stream;
     HIP_TRY(link_copy(b->ctx, &x, d, sizeof(x), hipMemcpyDeviceToHost, b->ctx->stream));
     HIP_TRY(hipStreamSynchronize(b->ctx->stream));
     if (cur_nb_blocks) *cur_nb_blocks = x.cur_blocks;

@@ -1,6 +1,7 @@
 // sdrhip_host.h -- host-side internals shared by the .cpp files of libsdrhip.so
 #pragma once
 #include "../../include/sdrhip.h"
+#include "dev_buffers.h" // (fail, DevBuf, PinnedBuf, DevEvent, TableVersions, CtxRef, BatchRing: who owns what)
 #include "rx_stream_settings.h" // (the sample-size arithmetic of the decimators lives there: decimated_sample_size, decimated_shifts, ragged_shift_word)
 #include "sdrhip_internal.h"
 
@@ -15,34 +16,11 @@
 
 namespace sdrhip {
 
-int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-
 #define HIP_TRY(expr)                                                                                           \
     do {                                                                                                        \
         hipError_t e_ = (expr);                                                                                 \
         if (e_ != hipSuccess) return ::sdrhip::fail(SDRHIP_EDEVICE, "%s: %s", #expr, hipGetErrorString(e_));    \
     } while (0)
-
-// growable device scratch buffer
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    int reserve(size_t n);
-    void release();
-    template <class T> T *as() const { return static_cast<T *>(p); }
-};
-
-// growable pinned host staging buffer; reuse waits for the previous upload that read from it
-struct PinnedBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipEvent_t ev = nullptr;
-    bool pending = false;
-    int reserve(size_t n);                 // also waits for the pending upload
-    void mark(hipStream_t s);              // call after enqueueing the copies that read from p
-    void release();
-    template <class T> T *as() const { return static_cast<T *>(p); }
-};
 
 // host-pointer calls up to this many input bytes skip the copy engine: the input is memcpy'd into pinned host memory that the
 // kernel reads over PCIe itself, small outputs are written the same way (one launch + one sync instead of H2D + launch + D2H + sync:
@@ -55,9 +33,6 @@ inline int check_mem(int mem)
 {
     return mem == SDRHIP_MEM_HOST || mem == SDRHIP_MEM_DEVICE ? SDRHIP_OK : fail(SDRHIP_EINVAL, "mem must be SDRHIP_MEM_HOST or SDRHIP_MEM_DEVICE");
 }
-
-void ctx_retain(sdrhip_ctx *c);
-void ctx_release(sdrhip_ctx *c);
 
 // meta blocks the decimator kernel writes for the fused Rx pipe (DecimArgs::meta_*)
 struct RxMeta {
@@ -248,14 +223,8 @@ int fec_decode_device(sdrhip_ctx *ctx, const uint8_t *rx, size_t rx_frame_bytes,
 bool host_is_pinned(const void *p, size_t n);
 
 // ---- per-stream lifecycle (sdrhip_*_reset_streams, sdrhip_stream_state.cpp).  The mask of a call goes up like the Rx pipe's
-// stream-meta table: from the next of four pinned versions (reuse waits for that version's own upload, four calls back) into the
-// device copy the previous call does not occupy -- a launch in flight never sees a later call's mask
-struct StreamMask {
-    PinnedBuf pin[4];
-    DevBuf dev[2];
-    int pin_sel = 0, dev_sel = 0;
-    void release();
-};
+// stream-meta table, as the next of its TableVersions -- a launch in flight never sees a later call's mask
+typedef TableVersions StreamMask;
 // counts the streams `mask` names (NULL: all S) into *n_set.  *dev = NULL when it names none or all of them (nothing is enqueued),
 // else the device copy, enqueued on the context's stream
 int stream_mask_upload(sdrhip_ctx *c, StreamMask &m, const uint8_t *mask, int S, const uint8_t **dev, int *n_set);

@@ -8,29 +8,26 @@ using namespace sdrhip;
 
 // --------------------------------------------------------------------------- interpolators
 struct sdrhip_interpolators {
-    sdrhip_ctx *ctx;
+    sdrhip::CtxRef ctx; // (first: released last)
     int nstreams;
-    int32_t *state[2]; // [nstreams][INT_STATE_WORDS]
+    sdrhip::DevBuf state[2]; // [nstreams][INT_STATE_WORDS]
     int cur;
     sdrhip::StreamMask reset_mask; // sdrhip_interpolators_reset_streams
+    explicit sdrhip_interpolators(sdrhip_ctx *c) : ctx(c) {}
 };
 
 extern "C" int sdrhip_interpolators_create(sdrhip_ctx *ctx, int nstreams, sdrhip_interpolators **out)
 {
     if (!ctx || !out || nstreams <= 0 || nstreams > 65535) return fail(SDRHIP_EINVAL, "interpolators_create: bad argument");
     HIP_TRY(hipSetDevice(ctx->device));
-    sdrhip_interpolators *p = new (std::nothrow) sdrhip_interpolators();
+    sdrhip_interpolators *p = new (std::nothrow) sdrhip_interpolators(ctx);
     if (!p) return fail(SDRHIP_ENOMEM, "out of host memory");
-    p->ctx = ctx; p->nstreams = nstreams; p->cur = 0;
+    p->nstreams = nstreams; p->cur = 0;
     size_t bytes = (size_t)nstreams * INT_STATE_WORDS * sizeof(int32_t);
-    p->state[0] = p->state[1] = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&p->state[0]), bytes) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&p->state[1]), bytes) != hipSuccess) {
-        if (p->state[0]) (void)hipFree(p->state[0]);
+    if (p->state[0].alloc_exact(bytes) || p->state[1].alloc_exact(bytes)) {
         delete p;
         return fail(SDRHIP_ENOMEM, "hipMalloc interpolator state");
     }
-    ctx_retain(ctx);
     *out = p;
     return sdrhip_interpolators_reset(p);
 }
@@ -40,10 +37,6 @@ extern "C" void sdrhip_interpolators_destroy(sdrhip_interpolators *p)
     if (!p) return;
     (void)hipSetDevice(p->ctx->device);
     (void)hipStreamSynchronize(p->ctx->stream);
-    (void)hipFree(p->state[0]);
-    (void)hipFree(p->state[1]);
-    p->reset_mask.release();
-    ctx_release(p->ctx);
     delete p;
 }
 
@@ -52,8 +45,8 @@ extern "C" int sdrhip_interpolators_reset(sdrhip_interpolators *p)
     if (!p) return fail(SDRHIP_EINVAL, "interpolators is NULL");
     sdrhip::CtxLock lock_(p->ctx);
     size_t bytes = (size_t)p->nstreams * INT_STATE_WORDS * sizeof(int32_t);
-    HIP_TRY(hipMemsetAsync(p->state[0], 0, bytes, p->ctx->stream));
-    HIP_TRY(hipMemsetAsync(p->state[1], 0, bytes, p->ctx->stream));
+    HIP_TRY(hipMemsetAsync(p->state[0].p, 0, bytes, p->ctx->stream));
+    HIP_TRY(hipMemsetAsync(p->state[1].p, 0, bytes, p->ctx->stream));
     p->cur = 0;
     return SDRHIP_OK;
 }
@@ -61,10 +54,10 @@ extern "C" int sdrhip_interpolators_reset(sdrhip_interpolators *p)
 namespace sdrhip {
 void interpolators_reset_part(sdrhip_interpolators *p, StreamResetArgs *a)
 {
-    a->rows[0] = p->state[0]; a->rows[1] = p->state[1];
+    a->rows[0] = p->state[0].as<int32_t>(); a->rows[1] = p->state[1].as<int32_t>();
     a->row_words = INT_STATE_WORDS;
 }
-int32_t *interpolators_row(sdrhip_interpolators *p, int s, int half) { return p->state[p->cur ^ (half & 1)] + (size_t)s * INT_STATE_WORDS; }
+int32_t *interpolators_row(sdrhip_interpolators *p, int s, int half) { return p->state[p->cur ^ (half & 1)].as<int32_t>() + (size_t)s * INT_STATE_WORDS; }
 } // namespace sdrhip
 
 extern "C" int sdrhip_interpolators_reset_streams(sdrhip_interpolators *p, const uint8_t *mask)
@@ -103,7 +96,7 @@ int interpolate_device(sdrhip_interpolators *p, int log2interp, const int16_t *i
     InterpArgs a;
     memset(&a, 0, sizeof(a));
     a.in = in; a.out = out; a.in_stride = in_stride; a.out_stride = out_stride; a.n_in = n_in;
-    a.state_cur = p->state[p->cur]; a.state_next = p->state[p->cur ^ 1];
+    a.state_cur = p->state[p->cur].as<int32_t>(); a.state_next = p->state[p->cur ^ 1].as<int32_t>();
     a.nstreams = p->nstreams;
     if (gather) { a.gmap = gather->map; a.grx = gather->rx; a.grest = gather->restored; a.gframes = gather->frames; }
     if (count) { a.count = count->count; a.count_stride = count->stride; a.count_unit = count->unit; }

@@ -1,5 +1,6 @@
-// sdrhip_pipes.h -- the fused Rx / Tx pipes of include/sdrhip.h: their handles, the ring of asynchronous batches and what the
-// units sdrhip_rx.cpp, sdrhip_rx_async.cpp, sdrhip_rx_datagrams.cpp, sdrhip_rx_datagrams_async.cpp, sdrhip_tx.cpp and
+// sdrhip_pipes.h -- the fused Rx / Tx pipes of include/sdrhip.h: their handles (every buffer, event and ring a member that owns
+// what it holds: dev_buffers.h, the ring of asynchronous batches among them) and what the units sdrhip_rx.cpp, sdrhip_rx_async.cpp,
+// sdrhip_rx_datagrams.cpp, sdrhip_rx_datagrams_async.cpp, sdrhip_tx.cpp and
 // sdrhip_tx_async.cpp share.  The Rx pipe's host decisions live in headers of their own: rx_frame_area.h (windows),
 // rx_stream_settings.h (per-stream settings, the counts of a ragged step and of a join), rx_depart_order.h (departure order)
 #pragma once
@@ -11,70 +12,6 @@
 #include <cstring>
 #include <new>
 
-namespace sdrhip {
-// The ring of batches behind a pipe's submit / collect entries, created on first use with depth 4.  B has `state` (0 free, 1 being
-// filled, 2 in flight, 3 collected and lent to the caller: sdrhip_rx_collect_egress), the event `done` and release().  tail = the
-// batch being filled, head = the next one to collect.  A lent batch lies behind head and keeps its slot until it is released.
-template <class B> struct BatchRing {
-    std::vector<B> v;
-    size_t head = 0, tail = 0;
-
-    void release(bool wait) // wait: for the events of batches that may still be in flight (destruction)
-    {
-        for (auto &b : v) {
-            if (wait && b.done) (void)hipEventSynchronize(b.done);
-            b.release();
-        }
-    }
-    void reset(size_t depth) { release(false); v.assign(depth, B()); head = tail = 0; } // (the caller refuses while anything is in flight)
-    B &tail_batch() { if (v.empty()) v.assign(4, B()); return v[tail % v.size()]; }
-    // a batch that is being filled, in flight or lent and satisfies pred
-    template <class P> bool any(P pred) const
-    {
-        for (const auto &b : v)
-            if (b.state != 0 && pred(b)) return true;
-        return false;
-    }
-    bool busy() const { return any([](const B &) { return true; }); }
-    static int ensure_event(B &b)
-    {
-        if (!b.done && hipEventCreateWithFlags(&b.done, hipEventDisableTiming) != hipSuccess) { b.done = nullptr; return fail(SDRHIP_EDEVICE, "hipEventCreate"); }
-        return SDRHIP_OK;
-    }
-    // the oldest batch once it has finished.  wait = 1: a batch that is still being filled goes out as it is (launch_filling, the
-    // end of a stream), then the wait happens OUTSIDE the context lock: the submitting thread -- the reference's source / reader
-    // thread -- keeps feeding the ring while the collecting thread sleeps on the oldest batch's event
-    template <class F> int wait_oldest(std::unique_lock<std::recursive_mutex> &lock_, int wait, const char *who, F launch_filling, B **bp)
-    {
-        if (v.empty()) return fail(SDRHIP_EBUSY, "%s: nothing was submitted", who);
-        for (;;) {
-            B &h = v[head % v.size()];
-            // (SDRHIP_OK always means: one batch collected -- possibly empty; a lent batch at the head of a ring it fills was collected)
-            if (h.state == 0 || h.state == 3) return fail(SDRHIP_EBUSY, "%s: nothing was submitted", who);
-            if (h.state == 1) {
-                if (!wait) return fail(SDRHIP_EBUSY, "%s: the oldest batch is still being filled (wait = 1 launches it as it is)", who);
-                int rc = launch_filling(h);
-                if (rc) return rc;
-                ++tail;
-            }
-            const hipError_t q = hipEventQuery(h.done);
-            if (q == hipSuccess) { *bp = &h; break; }
-            if (q != hipErrorNotReady) return fail(SDRHIP_EDEVICE, "hipEventQuery: %s", hipGetErrorString(q));
-            if (!wait) return fail(SDRHIP_EBUSY, "%s: the oldest batch is still in flight", who);
-            const size_t at = head;
-            hipEvent_t ev = h.done;
-            lock_.unlock();
-            const hipError_t w = hipEventSynchronize(ev);
-            lock_.lock();
-            if (w != hipSuccess) return fail(SDRHIP_EDEVICE, "hipEventSynchronize: %s", hipGetErrorString(w));
-            if (head == at) { *bp = &v[at % v.size()]; break; }
-            // (another thread collected that batch meanwhile: look at the new head)
-        }
-        return SDRHIP_OK;
-    }
-};
-} // namespace sdrhip
-
 // --------------------------------------------------------------------------- fused Rx pipe
 namespace sdrhip {
 // pinned staging of the ragged step's two host tables (the decimator's rows, the encoder's frame list).  The handle owns one pair,
@@ -82,10 +19,11 @@ namespace sdrhip {
 struct RxTabs { PinnedBuf rows, flist; };
 } // namespace sdrhip
 struct sdrhip_rx {
-    sdrhip_ctx *ctx;
+    sdrhip::CtxRef ctx; // (first: released last -- the pipe's own reference, whatever its banks hold)
     int nstreams;
     sdrhip_rx_config cfg;
-    sdrhip_decimators *dec;
+    sdrhip_decimators *dec = nullptr;
+    explicit sdrhip_rx(sdrhip_ctx *c) : ctx(c) {}
     // [nstreams][area.cap()][128 + nb_fec][512] (per-stream fecblk: 128 + the largest count, rx_frame_bytes).  A call fills slots area.slot(s) .. area.slot(s) + done of stream s; the frame
     // still being filled is the first slot of the next call, so the window slides and nothing is copied until it reaches the end
     // of the area.  `area` decides where the windows go (rx_frame_area.h), rx_run_plan moves the open frames there
@@ -112,13 +50,13 @@ struct sdrhip_rx {
     // overlap mode (option rx_fused = 3): the waiting encode runs on the context's second stream beside the next call's decimator.
     // ev_framed: recorded on the first stream when a call has written everything its deferred encode reads (decimator + K2);
     // ev_enc: recorded on the second stream behind the encode, the first stream waits for it before the frames are delivered
-    hipEvent_t ev_framed = nullptr, ev_enc = nullptr;
+    sdrhip::DevEvent ev_framed, ev_enc;
     // ---- asynchronous host-pointer entry (sdrhip_rx_submit / sdrhip_rx_collect): a ring of batches
     struct Batch {
         sdrhip::PinnedBuf in;     // the submitted blocks, appended: [block][stream][n] (unless the caller's memory is pinned by us)
         sdrhip::DevBuf din;       // [stream][dstride] on the device
         sdrhip::PinnedBuf out;    // the batch's finished frames [stream][frames][128 + R][512]
-        hipEvent_t done = nullptr;
+        sdrhip::DevEvent done;
         std::vector<std::pair<const int16_t *, size_t> > blocks; // source of each block (host address, samples per stream) and
         std::vector<size_t> strides;                             // its stream stride in samples
         size_t n_in = 0;          // samples per stream so far
@@ -154,13 +92,6 @@ struct sdrhip_rx {
         // was launched with, and the datagrams of its array; empty: every frame holds frame_bytes / 512)
         std::vector<size_t> e_blocks;
         size_t e_dgrams = 0;
-        void release()
-        {
-            if (done) (void)hipEventDestroy(done);
-            done = nullptr;
-            in.release(); din.release(); out.release(); r_tab.release(); d_seg.release(); d_tabs.rows.release(); d_tabs.flist.release();
-            e_tab.release();
-        }
     };
     sdrhip::BatchRing<Batch> ring;
     // ragged batches on the device: packed upload, K0p's rows, tables, compacted frames (datagram batches: the packed datagrams in
@@ -191,9 +122,7 @@ struct sdrhip_rx {
     // Per-stream fecblk: the frame area keeps ONE slot pitch, 128 + the largest count (rx_frame_bytes), a frame of stream s holds
     // rx_stream_blocks(rx, s) valid super blocks at the head of its slot
     sdrhip::RxStreamSettings streams;
-    sdrhip::PinnedBuf sm_pin[4];
-    sdrhip::DevBuf sm_dev[2];
-    int sm_pin_sel = 0, sm_dev_sel = 0;
+    sdrhip::TableVersions sm_tab;
     // ---- datagram entry (sdrhip_rx_process_datagrams): one SDRdaemonFECBuffer per stream, created on first use; it delivers into
     // j_rows ([nstreams][j_row_len] samples, the ragged step's input), behind the samples each row holds back from earlier calls
     // (their counts live with the collector: fecbuf_join_carry)
@@ -207,16 +136,16 @@ struct sdrhip_rx {
     // _import_stream: the contiguous device blob KG packs / KS unpacks, and the pinned staging of an import's upload
     sdrhip::StreamMask reset_mask;
     sdrhip::DevBuf x_blob;
-    sdrhip::PinnedBuf x_pin[4]; // (four versions: an import waits for the upload four imports back, not for the previous one)
-    int x_pin_sel = 0;
+    sdrhip::PinnedVersions x_pin; // (four versions: an import waits for the upload four imports back, not for the previous one)
 };
 
 // --------------------------------------------------------------------------- fused Tx pipe
 struct sdrhip_tx {
-    sdrhip_ctx *ctx;
+    sdrhip::CtxRef ctx; // (first: released last -- the pipe's own reference, whatever its banks hold)
     int nstreams;
     int log2interp;
-    sdrhip_interpolators *itp;
+    sdrhip_interpolators *itp = nullptr;
+    explicit sdrhip_tx(sdrhip_ctx *c) : ctx(c) {}
     sdrhip::DevBuf rxbuf, payload[2], outbuf;
     sdrhip::DevBuf srcmap, restored; // no-copy mode (tx_gather): the decoder's position map and restored blocks, read by K5w's gather variant
     size_t restored_slots = 0; // slots `restored` was zero-terminated for (its last slot must read zero)
@@ -232,17 +161,17 @@ struct sdrhip_tx {
     } late;
     sdrhip::DevBuf plan_own, idx_own;
     sdrhip::PinnedBuf pin_own;
-    hipEvent_t ev_in = nullptr;              // first stream: the caller's device rx buffer is ready
-    hipEvent_t ev_up = nullptr;              // second stream: the upload of the caller's HOST rx buffer has read it (the call returns behind it)
-    hipEvent_t ev_dec = nullptr;             // second stream: the waiting batch is decoded
-    hipEvent_t ev_itp[2] = {nullptr, nullptr}; // first stream: the interpolator has read payload[i]
+    sdrhip::DevEvent ev_in;                  // first stream: the caller's device rx buffer is ready
+    sdrhip::DevEvent ev_up;                  // second stream: the upload of the caller's HOST rx buffer has read it (the call returns behind it)
+    sdrhip::DevEvent ev_dec;                 // second stream: the waiting batch is decoded
+    sdrhip::DevEvent ev_itp[2];              // first stream: the interpolator has read payload[i]
     bool itp_pending[2] = {false, false};
     // ---- asynchronous host-pointer entry (sdrhip_tx_submit / sdrhip_tx_collect): a ring of batches of received frames
     struct ABatch {
         sdrhip::PinnedBuf in;        // the batch's received super blocks [stream][frame][128][512] (staged; sdrhip_host_alloc memory is used in place)
         sdrhip::DevBuf din, dout, db0; // ... on the device; its samples [stream][dos]; its meta blocks [stream * nframes][508]
         sdrhip::PinnedBuf out;       // samples, then meta blocks, downloaded
-        hipEvent_t done = nullptr;
+        sdrhip::DevEvent done;
         size_t nframes = 0, n_res = 0, dos = 0;
         int state = 0;            // 0 free, 2 in flight
         // a batch of raw datagrams (sdrhip_tx_submit_datagrams): `in` holds them packed, `out` the gathered delivery (every
@@ -252,12 +181,6 @@ struct sdrhip_tx {
         std::vector<size_t> frames; // released frames per stream
         int log2interp = 0;
         size_t esz = 4;
-        void release()
-        {
-            if (done) (void)hipEventDestroy(done);
-            done = nullptr;
-            in.release(); din.release(); dout.release(); db0.release(); out.release(); tab.release(); seg.release();
-        }
     };
     sdrhip::BatchRing<ABatch> ring;
     // device buffers of the datagram batches, shared by the ring (the context's stream orders the batches): the packed datagrams,
@@ -272,8 +195,7 @@ struct sdrhip_tx {
     // _import_stream: the contiguous device blob KG packs / KS unpacks, and the pinned staging of an import's upload
     sdrhip::StreamMask reset_mask;
     sdrhip::DevBuf x_blob;
-    sdrhip::PinnedBuf x_pin[4]; // (four versions: an import waits for the upload four imports back, not for the previous one)
-    int x_pin_sel = 0;
+    sdrhip::PinnedVersions x_pin; // (four versions: an import waits for the upload four imports back, not for the previous one)
 };
 
 namespace sdrhip {

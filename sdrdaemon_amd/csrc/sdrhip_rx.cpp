@@ -14,9 +14,9 @@ extern "C" int sdrhip_rx_create(sdrhip_ctx *ctx, int nstreams, const sdrhip_rx_c
         const int rcc = rx_check_config(cfg);
         if (rcc) return rcc;
     }
-    sdrhip_rx *rx = new (std::nothrow) sdrhip_rx();
+    sdrhip_rx *rx = new (std::nothrow) sdrhip_rx(ctx);
     if (!rx) return fail(SDRHIP_ENOMEM, "out of host memory");
-    rx->ctx = ctx; rx->nstreams = nstreams; rx->cfg = *cfg; rx->dec = nullptr;
+    rx->nstreams = nstreams; rx->cfg = *cfg;
     rx->area.init((size_t)nstreams);
     rx->view.init((size_t)nstreams);
     rx->streams.init((size_t)nstreams);
@@ -48,7 +48,7 @@ static int rx_settle(sdrhip_rx *rx)
     hipStream_t s2 = nullptr;
     int rc = ctx_stream2(c, &s2);
     if (rc) return rc;
-    if (!rx->ev_enc) HIP_TRY(hipEventCreateWithFlags(&rx->ev_enc, hipEventDisableTiming));
+    if ((rc = rx->ev_enc.ensure())) return rc;
     HIP_TRY(hipStreamWaitEvent(s2, rx->ev_framed, 0));
     if ((rc = fec_encode128_launch(c, rx->late.k, s2))) return rc;
     HIP_TRY(hipEventRecord(rx->ev_enc, s2));
@@ -131,9 +131,8 @@ static int rx_run_plan(sdrhip_rx *rx, const RxAreaPlan &p, DevBuf *fresh, size_t
         return fail(SDRHIP_EDEVICE, "%s: moving the open frames: %s", who, hipGetErrorString(e));
     }
     if (fresh) {
-        if (p.keep_old) { rx->old_work.release(); rx->old_work = rx->work; rx->late.in_old = true; }
-        else rx->work.release();
-        rx->work = *fresh;
+        if (p.keep_old) { rx->old_work = std::move(rx->work); rx->late.in_old = true; } // (frees what old_work held)
+        rx->work = std::move(*fresh); // (frees the area the windows leave, unless old_work took it)
         rx->view.clear(); // (the view of the last call's frames does not outlive the area it points into)
     }
     rx->area.moved(p);
@@ -196,27 +195,14 @@ extern "C" int sdrhip_rx_reconfigure(sdrhip_rx *rx, const sdrhip_rx_config *cfg)
 extern "C" void sdrhip_rx_destroy(sdrhip_rx *rx)
 {
     if (!rx) return;
+    sdrhip_ctx *c = rx->ctx;
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    if (c->stream2) (void)hipStreamSynchronize(c->stream2); // (an encode of the overlap mode may still run there)
+    rx->ring.wait_all();
     sdrhip_decimators_destroy(rx->dec);
-    rx->work.release();
-    rx->old_work.release();
-    rx->lin[0].release();
-    rx->lin[1].release();
-    rx->flist.release();
-    rx->wide.release();
-    rx->f_tab_pin.release(); rx->f_pin.release(); rx->f_tab.release(); rx->f_pk.release();
-    rx->r_pin.release(); rx->r_flist_pin.release(); rx->r_flist.release();
-    if (rx->ev_framed) (void)hipEventDestroy(rx->ev_framed);
-    if (rx->ev_enc) (void)hipEventDestroy(rx->ev_enc);
-    rx->ring.release(true);
-    rx->a_pk.release(); rx->a_din.release(); rx->a_tab.release(); rx->a_frames.release(); rx->e_tab.release();
-    sdrhip_fecbuf_destroy(rx->fb); // (synchronises the stream)
-    rx->j_rows.release();
-    for (auto &b : rx->sm_pin) b.release();
-    for (auto &b : rx->sm_dev) b.release();
-    rx->reset_mask.release();
-    rx->x_blob.release();
-    for (auto &b : rx->x_pin) b.release();
-    delete rx;
+    sdrhip_fecbuf_destroy(rx->fb);
+    delete rx; // (no lock held: the last reference frees the context, its mutex included)
 }
 
 extern "C" int sdrhip_rx_frames_view(const sdrhip_rx *rx, const uint8_t **base, size_t *stream_stride_bytes, size_t *n_frames)
@@ -419,20 +405,11 @@ static int rx_stream_table(sdrhip_rx *rx, const unsigned **dev)
     const RxStreamRecords *r = rx->streams.records(rx_bank(rx));
     if (!r) return SDRHIP_OK;
     if (rx->streams.changed()) {
-        const size_t bytes = r->words.size() * sizeof(unsigned);
-        PinnedBuf &pin = rx->sm_pin[(rx->sm_pin_sel + 1) & 3];
-        DevBuf &tab = rx->sm_dev[rx->sm_dev_sel ^ 1];
-        int rc;
-        if ((rc = pin.reserve(bytes))) return rc;
-        if ((rc = tab.reserve(bytes))) return rc;
-        memcpy(pin.p, r->words.data(), bytes);
-        HIP_TRY(hipMemcpyAsync(tab.p, pin.p, bytes, hipMemcpyHostToDevice, rx->ctx->stream)); // (not counted: a table)
-        pin.mark(rx->ctx->stream);
-        rx->sm_pin_sel = (rx->sm_pin_sel + 1) & 3;
-        rx->sm_dev_sel ^= 1;
+        const void *tab = nullptr;
+        if (int rc = rx->sm_tab.upload(rx->ctx->stream, r->words.data(), r->words.size() * sizeof(unsigned), &tab)) return rc;
         rx->streams.taken();
     }
-    *dev = rx->sm_dev[rx->sm_dev_sel].as<unsigned>();
+    *dev = static_cast<const unsigned *>(rx->sm_tab.current());
     return SDRHIP_OK;
 }
 
@@ -664,7 +641,7 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
         rx->late.have = done > 0;
         rx->late.encode = encode_later;
         if (encode_later && c->opt.rx_fused == 3) { // (everything the deferred encode reads has been enqueued on the first stream by now)
-            if (!rx->ev_framed) HIP_TRY(hipEventCreateWithFlags(&rx->ev_framed, hipEventDisableTiming));
+            if ((rc = rx->ev_framed.ensure())) return rc;
             HIP_TRY(hipEventRecord(rx->ev_framed, c->stream));
         }
         rx->late.k = k;

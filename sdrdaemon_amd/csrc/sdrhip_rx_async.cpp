@@ -47,7 +47,7 @@ int rx_launch_batch(sdrhip_rx *rx, sdrhip_rx::Batch &b)
     b.egress = 0;
     const size_t nf_max = sdrhip_rx_max_frames(rx, b.n_in);
     if (nf_max && (rc = b.out.reserve((size_t)S * nf_max * b.frame_bytes))) return rc;
-    if ((rc = rx->ring.ensure_event(b))) return rc;
+    if ((rc = b.done.ensure())) return rc;
     size_t nf = 0;
     rc = sdrhip_rx_process(rx, b.din.as<int16_t>(), b.n_in, dstride, b.tv_sec, b.tv_usec, nullptr, 0, &nf, SDRHIP_MEM_DEVICE);
     if (rc) {
@@ -103,7 +103,7 @@ int rx_launch_ragged(sdrhip_rx *rx, sdrhip_rx::Batch &b)
     if ((rc = rx->a_din.reserve((size_t)S * dstride * 4 + 16))) return rc;
     if (sum_done && (rc = b.out.reserve(sum_done * fb))) return rc;
     if (sum_done && (rc = rx->a_frames.reserve(sum_done * fb))) return rc;
-    if ((rc = rx->ring.ensure_event(b))) return rc;
+    if ((rc = b.done.ensure())) return rc;
     b.egress = rx->egress; // (set_egress is refused while a batch is being filled: the order of the batch's first block)
     if (b.egress && (rc = rx_egress_room(rx, b, sum_done, fb / SDRHIP_UDPSIZE))) return rc;
 
@@ -261,8 +261,7 @@ extern "C" int sdrhip_rx_submit(sdrhip_rx *rx, const int16_t *iq_in, size_t n_in
             int rc = bigger.reserve((size_t)S * ncap * esz);
             if (rc) return rc;
             for (int s = 0; s < S; ++s) memcpy(bigger.as<char>() + (size_t)s * ncap * esz, b.in.as<char>() + (size_t)s * b.in_cap * esz, b.n_in * esz);
-            b.in.release();
-            b.in = bigger;
+            b.in = std::move(bigger);
             b.in_cap = ncap;
         }
         for (int s = 0; s < S; ++s) memcpy(b.in.as<char>() + ((size_t)s * b.in_cap + b.n_in) * esz, src + (size_t)s * in_stride * esz, n_in * esz);
@@ -356,8 +355,7 @@ extern "C" int sdrhip_rx_submit_ragged(sdrhip_rx *rx, const int16_t *iq_in, cons
             int rc = bigger.reserve(2 * need);
             if (rc) return rc;
             memcpy(bigger.p, b.in.p, used);
-            b.in.release();
-            b.in = bigger;
+            b.in = std::move(bigger);
         }
     }
     if (b.state == 0) { // the batch's first block: its stamps are the batch's

@@ -49,11 +49,9 @@ int sdrhip::rx_join_rows(sdrhip_rx *rx, size_t max_released, const char *who)
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // (earlier launches may still use the old rows)
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(c->stream);
-        bigger.release();
         return fail(SDRHIP_EDEVICE, "%s: moving the rows: %s", who, hipGetErrorString(e));
     }
-    rx->j_rows.release();
-    rx->j_rows = bigger;
+    rx->j_rows = std::move(bigger);
     rx->j_row_len = row_len;
     return SDRHIP_OK;
 }

@@ -63,7 +63,7 @@ static int rx_submit_batch(sdrhip_rx *rx, FecBufBatch &in, const uint32_t *tv_se
     if ((rc = reserve_settled(c, rx->a_tab, seg_bytes))) return rc;
     if (b_total && (rc = b.out.reserve(b_total))) return rc;
     if ((rc = b.d_seg.reserve(seg_bytes))) return rc;
-    if ((rc = rx->ring.ensure_event(b))) return rc;
+    if ((rc = b.done.ensure())) return rc;
     b.egress = rx->egress; // (departure order: KE's table and the tags, like everything else, before the collector moves)
     if (b.egress && (rc = rx_egress_room(rx, b, sum_done, fb / SDRHIP_UDPSIZE))) return rc;
     if (any && (rc = rx_ragged_room(rx, n, &b.d_tabs))) return rc;

@@ -7,12 +7,6 @@
 using namespace sdrhip;
 
 namespace sdrhip {
-void StreamMask::release()
-{
-    for (auto &b : pin) b.release();
-    for (auto &b : dev) b.release();
-}
-
 int stream_mask_upload(sdrhip_ctx *c, StreamMask &m, const uint8_t *mask, int S, const uint8_t **dev, int *n_set)
 {
     *dev = nullptr;
@@ -23,17 +17,9 @@ int stream_mask_upload(sdrhip_ctx *c, StreamMask &m, const uint8_t *mask, int S,
     }
     *n_set = n;
     if (n == 0 || n == S) return SDRHIP_OK;
-    PinnedBuf &pin = m.pin[(m.pin_sel + 1) & 3];
-    DevBuf &tab = m.dev[m.dev_sel ^ 1];
-    int rc;
-    if ((rc = pin.reserve((size_t)S))) return rc;
-    if ((rc = tab.reserve((size_t)S))) return rc;
-    memcpy(pin.p, mask, (size_t)S);
-    HIP_TRY(hipMemcpyAsync(tab.p, pin.p, (size_t)S, hipMemcpyHostToDevice, c->stream)); // (not counted: a table)
-    pin.mark(c->stream);
-    m.pin_sel = (m.pin_sel + 1) & 3;
-    m.dev_sel ^= 1;
-    *dev = tab.as<uint8_t>();
+    const void *tab = nullptr;
+    if (int rc = m.upload(c->stream, mask, (size_t)S, &tab)) return rc;
+    *dev = static_cast<const uint8_t *>(tab);
     return SDRHIP_OK;
 }
 
@@ -181,14 +167,6 @@ void scatter_collector(sdrhip_fecbuf *fb, int s, const uint8_t *dev, size_t off_
     if (carry) add_seg(a, dev + off_carry, r.carry + (st.cbuf ? r.carry_half : 0), SLOT_BYTES);
 }
 
-// the import's staging: the next of the handle's four pinned versions (reuse waits for that version's own upload, four imports
-// back: a run of imports does not wait for the one before it)
-template <class H> PinnedBuf &import_pin(H *h)
-{
-    h->x_pin_sel = (h->x_pin_sel + 1) & 3;
-    return h->x_pin[h->x_pin_sel];
-}
-
 // the import's tail: the device part up from the pinned staging (filled by the caller), then KS
 int import_run(sdrhip_ctx *c, StreamCopyArgs &a, PinnedBuf &pin, DevBuf &dev, size_t dev_bytes)
 {
@@ -294,7 +272,7 @@ extern "C" int sdrhip_rx_import_stream(sdrhip_rx *rx, int stream, const void *bl
     if (h.carry && (rc = rx_join_rows(rx, 0, who))) return rc;
     if (h.r_open && (rc = rx_area_room(rx, nullptr))) return rc;
     if ((rc = reserve_settled(c, rx->x_blob, RX_DEV_BYTES))) return rc;
-    PinnedBuf &pin = import_pin(rx);
+    PinnedBuf &pin = rx->x_pin.next();
     if ((rc = pin.reserve(RX_DEV_BYTES))) return rc;
     memcpy(pin.p, in + RX_HOST_BYTES, RX_DEV_BYTES);
     if (!h.has_collector) { // (the source had no collector: the bank's own begins as the constructor leaves it)
@@ -373,7 +351,7 @@ extern "C" int sdrhip_tx_import_stream(sdrhip_tx *tx, int stream, const void *bl
     HIP_TRY(hipSetDevice(c->device));
     if (h.has_collector && (rc = tx_collector(tx))) return rc;
     if ((rc = reserve_settled(c, tx->x_blob, TX_DEV_BYTES))) return rc;
-    PinnedBuf &pin = import_pin(tx);
+    PinnedBuf &pin = tx->x_pin.next();
     if ((rc = pin.reserve(TX_DEV_BYTES))) return rc;
     memcpy(pin.p, in + TX_HOST_BYTES, TX_DEV_BYTES);
     if (!h.has_collector) {

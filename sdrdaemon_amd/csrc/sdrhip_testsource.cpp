@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -87,34 +88,29 @@ std::map<std::string, std::string> parse_kv(const char *s)
 } // namespace
 
 struct sdrhip_testsource {
-    sdrhip_ctx *ctx;
+    CtxRef ctx; // (first: released last)
     int nstreams;
     std::vector<Gen> gen;
-    int *table = nullptr;              // device: 4096 x int32
-    TestSourceParams *par = nullptr;   // device: [nstreams]
+    DevBuf table;                      // device: 4096 x int32
+    DevBuf par;                        // device: [nstreams] TestSourceParams
     PinnedBuf pin;
+    explicit sdrhip_testsource(sdrhip_ctx *c) : ctx(c) {}
 };
 
 extern "C" int sdrhip_testsource_create(sdrhip_ctx *ctx, int nstreams, sdrhip_testsource **out)
 {
     if (!ctx || !out || nstreams <= 0 || nstreams > 65535) return fail(SDRHIP_EINVAL, "testsource_create: bad argument");
+    std::unique_ptr<sdrhip_testsource> t(new (std::nothrow) sdrhip_testsource(ctx)); // (in front of the lock: a failure deletes it behind the lock's scope)
     CtxLock lock_(ctx);
-    HIP_TRY(hipSetDevice(ctx->device));
-    sdrhip_testsource *t = new (std::nothrow) sdrhip_testsource();
     if (!t) return fail(SDRHIP_ENOMEM, "out of host memory");
-    t->ctx = ctx; t->nstreams = nstreams; t->gen.resize((size_t)nstreams);
+    HIP_TRY(hipSetDevice(ctx->device));
+    t->nstreams = nstreams; t->gen.resize((size_t)nstreams);
     std::vector<int> T(4096);
     nco_table(T.data());
-    if (hipMalloc(reinterpret_cast<void **>(&t->table), 4096 * sizeof(int)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&t->par), (size_t)nstreams * sizeof(TestSourceParams)) != hipSuccess ||
-        hipMemcpy(t->table, T.data(), 4096 * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-        if (t->table) (void)hipFree(t->table);
-        if (t->par) (void)hipFree(t->par);
-        delete t;
+    if (t->table.alloc_exact(4096 * sizeof(int)) || t->par.alloc_exact((size_t)nstreams * sizeof(TestSourceParams)) ||
+        hipMemcpy(t->table.p, T.data(), 4096 * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
         return fail(SDRHIP_ENOMEM, "testsource tables");
-    }
-    ctx_retain(ctx);
-    *out = t;
+    *out = t.release();
     return SDRHIP_OK;
 }
 
@@ -123,10 +119,6 @@ extern "C" void sdrhip_testsource_destroy(sdrhip_testsource *t)
     if (!t) return;
     (void)hipSetDevice(t->ctx->device);
     (void)hipStreamSynchronize(t->ctx->stream);
-    t->pin.release();
-    (void)hipFree(t->table);
-    (void)hipFree(t->par);
-    ctx_release(t->ctx);
     delete t;
 }
 
@@ -246,7 +238,7 @@ extern "C" int sdrhip_testsource_read(sdrhip_testsource *t, int16_t *iq_out, siz
         hp[s].phase0 = g.phase; hp[s].inc = g.inc; hp[s].amp = g.amp;
         g.phase += (unsigned)n * g.inc; // mod 2^32
     }
-    HIP_TRY(link_copy(c, t->par, hp, (size_t)S * sizeof(TestSourceParams), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(link_copy(c, t->par.p, hp, (size_t)S * sizeof(TestSourceParams), hipMemcpyHostToDevice, c->stream));
     t->pin.mark(c->stream);
     int16_t *dout = iq_out;
     size_t dstride = out_stride;
@@ -259,7 +251,7 @@ extern "C" int sdrhip_testsource_read(sdrhip_testsource *t, int16_t *iq_out, siz
     } else {
         return check_mem(mem);
     }
-    hipError_t e = launch_testsource(t->table, t->par, dout, dstride, n, S, c->stream);
+    hipError_t e = launch_testsource(t->table.as<int>(), t->par.as<TestSourceParams>(), dout, dstride, n, S, c->stream);
     if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "testsource launch: %s", hipGetErrorString(e));
     if (mem == SDRHIP_MEM_HOST) {
         HIP_TRY(link_copy2d(c, iq_out, out_stride * 4, dout, dstride * 4, n * 4, S, hipMemcpyDeviceToHost, c->stream));

@@ -15,9 +15,9 @@ extern "C" int sdrhip_tx_create(sdrhip_ctx *ctx, int nstreams, int log2interp, s
 {
     if (!ctx || !out || nstreams <= 0) return fail(SDRHIP_EINVAL, "tx_create: bad argument");
     if (log2interp < 0 || log2interp > 6) return fail(SDRHIP_EINVAL, "Invalid log2 interpolation factor");
-    sdrhip_tx *tx = new (std::nothrow) sdrhip_tx();
+    sdrhip_tx *tx = new (std::nothrow) sdrhip_tx(ctx);
     if (!tx) return fail(SDRHIP_ENOMEM, "out of host memory");
-    tx->ctx = ctx; tx->nstreams = nstreams; tx->log2interp = log2interp; tx->itp = nullptr;
+    tx->nstreams = nstreams; tx->log2interp = log2interp;
     int rc = sdrhip_interpolators_create(ctx, nstreams, &tx->itp);
     if (rc) { delete tx; return rc; }
     *out = tx;
@@ -40,23 +40,14 @@ extern "C" int sdrhip_tx_reconfigure(sdrhip_tx *tx, int log2interp)
 extern "C" void sdrhip_tx_destroy(sdrhip_tx *tx)
 {
     if (!tx) return;
-    (void)hipSetDevice(tx->ctx->device);
-    if (tx->ctx->stream2) (void)hipStreamSynchronize(tx->ctx->stream2); // (a decode of the pipelined mode may still run there)
-    sdrhip_interpolators_destroy(tx->itp); // (synchronises the first stream)
+    sdrhip_ctx *c = tx->ctx;
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    if (c->stream2) (void)hipStreamSynchronize(c->stream2); // (a decode of the pipelined mode may still run there)
+    tx->ring.wait_all();
+    sdrhip_interpolators_destroy(tx->itp);
     sdrhip_fecbuf_destroy(tx->fb);
-    tx->rxbuf.release(); tx->payload[0].release(); tx->payload[1].release(); tx->outbuf.release();
-    tx->srcmap.release(); tx->restored.release();
-    tx->plan_own.release(); tx->idx_own.release(); tx->pin_own.release();
-    tx->ring.release(true);
-    tx->a_pk.release(); tx->a_pay.release(); tx->a_out.release(); tx->a_b0.release(); tx->a_gat.release(); tx->a_seg.release();
-    tx->reset_mask.release();
-    tx->x_blob.release();
-    for (auto &b : tx->x_pin) b.release();
-    if (tx->ev_in) (void)hipEventDestroy(tx->ev_in);
-    if (tx->ev_up) (void)hipEventDestroy(tx->ev_up);
-    if (tx->ev_dec) (void)hipEventDestroy(tx->ev_dec);
-    for (int i = 0; i < 2; ++i) if (tx->ev_itp[i]) (void)hipEventDestroy(tx->ev_itp[i]);
-    delete tx;
+    delete tx; // (no lock held: the last reference frees the context, its mutex included)
 }
 
 extern "C" int sdrhip_tx_set_pipelined(sdrhip_tx *tx, int on)
@@ -67,10 +58,8 @@ extern "C" int sdrhip_tx_set_pipelined(sdrhip_tx *tx, int on)
     if (on && tx_in_flight(tx, true)) return fail(SDRHIP_EINVAL, "tx_set_pipelined: asynchronous datagram batches are in flight: collect them first");
     if (on) {
         HIP_TRY(hipSetDevice(tx->ctx->device));
-        if (!tx->ev_in) HIP_TRY(hipEventCreateWithFlags(&tx->ev_in, hipEventDisableTiming));
-        if (!tx->ev_up) HIP_TRY(hipEventCreateWithFlags(&tx->ev_up, hipEventDisableTiming));
-        if (!tx->ev_dec) HIP_TRY(hipEventCreateWithFlags(&tx->ev_dec, hipEventDisableTiming));
-        for (int i = 0; i < 2; ++i) if (!tx->ev_itp[i]) HIP_TRY(hipEventCreateWithFlags(&tx->ev_itp[i], hipEventDisableTiming));
+        for (DevEvent *e : {&tx->ev_in, &tx->ev_up, &tx->ev_dec, &tx->ev_itp[0], &tx->ev_itp[1]})
+            if (int rc = e->ensure()) return rc;
     }
     tx->pipelined = on ? 1 : 0;
     return SDRHIP_OK;

@@ -46,7 +46,7 @@ extern "C" int sdrhip_tx_submit(sdrhip_tx *tx, const uint8_t *rx, const uint8_t 
     if ((rc = b.out.reserve((size_t)S * dos * esz + b0_bytes))) return rc;
     const bool gather = tx_gather_applies(tx, tx->log2interp);
     if (!gather && (rc = tx->payload[0].reserve((size_t)S * pstride * 4 + 16))) return rc;
-    if ((rc = tx->ring.ensure_event(b))) return rc;
+    if ((rc = b.done.ensure())) return rc;
     const uint8_t *src = rx;
     size_t sstride = rx_stride_bytes;
     if (!host_is_pinned(rx, (size_t)(S - 1) * rx_stride_bytes + row)) {
@@ -165,7 +165,7 @@ static int tx_submit_batch(sdrhip_tx *tx, FecBufBatch &in, const char *who)
     if ((rc = reserve_settled(c, tx->a_seg, (size_t)3 * S * sizeof(GatherSeg)))) return rc;
     if (b_total && (rc = b.out.reserve(b_total))) return rc;
     if ((rc = b.seg.reserve((size_t)3 * S * sizeof(GatherSeg)))) return rc;
-    if ((rc = tx->ring.ensure_event(b))) return rc;
+    if ((rc = b.done.ensure())) return rc;
 
     // ---- upload: exactly the datagrams (staged: one copy; in place: one per run of adjacent rows)
     uint8_t *pk = tx->a_pk.as<uint8_t>();
