@@ -2,9 +2,8 @@
 //
 // K0 (widen): the Rx pipe's 8-bit input -> the int16 IQSample rows the decimator reads.  RtlSdrSource's callback does it on a host
 // core, IQSample(buf[2i] - 128, buf[2i + 1] - 128) (RtlSdrSource.cpp:542-553), HackRFSource's IQSample(buf[2i], buf[2i + 1])
-// (HackRFSource.cpp:661-674); here the bytes cross the host link as they are and one pass on the device widens them.  A lane takes
-// 8 samples: one 16-byte load, two 16-byte stores.  Offset binary is two's complement with the top bit flipped: b - 128 =
-// (int8)(b ^ 0x80), so U8 is S8 behind one XOR per dword.
+// (HackRFSource.cpp:661-674); here the bytes cross the host link as they are and one pass on the device widens them: the row
+// pass of rx_unpack_body.h (a lane takes 8 samples: one 16-byte load, two 16-byte stores), which K0r runs with per-stream counts.
 //
 // K6n (narrow): the Tx pipe's interpolate1 (a copy, Upsampler.cpp:54-57) with 8-bit output, HackRFSink's buf[2i] = real() >> 8,
 // buf[2i + 1] = imag() >> 8 (HackRFSink.cpp:671-672): byte 1 of every int16 component.  A lane takes 8 samples: two 16-byte loads,
@@ -20,40 +19,13 @@ namespace {
 typedef unsigned cvt_uint4_t __attribute__((ext_vector_type(4)));
 constexpr int CVT_NT = 256;
 
-// two samples {re, im, re, im} of one dword -> two IQSample dwords
-template <int FMT> __device__ __forceinline__ void widen2(unsigned x, unsigned &lo, unsigned &hi)
-{
-    if (FMT == IQF_U8) x ^= 0x80808080u;
-    const int b0 = (int)(x << 24) >> 24, b1 = (int)(x << 16) >> 24, b2 = (int)(x << 8) >> 24, b3 = (int)x >> 24;
-    lo = ((unsigned)b0 & 0xffffu) | ((unsigned)b1 << 16);
-    hi = ((unsigned)b2 & 0xffffu) | ((unsigned)b3 << 16);
-}
+#include "rx_unpack_body.h"
 
 template <int FMT> __global__ __launch_bounds__(CVT_NT) void iq8_widen_kernel(const uint8_t *in, size_t in_stride, int16_t *out, size_t out_stride,
                                                                                size_t n)
 {
     const int s = (int)blockIdx.y;
-    const uint8_t *row = in + (size_t)s * in_stride * 2;
-    unsigned *orow = reinterpret_cast<unsigned *>(out) + (size_t)s * out_stride;
-    const size_t groups = n >> 3;
-    for (size_t g = (size_t)blockIdx.x * CVT_NT + threadIdx.x; g < groups; g += (size_t)gridDim.x * CVT_NT) {
-        const cvt_uint4_t v = SDRHIP_STREAM_LOAD(reinterpret_cast<const cvt_uint4_t *>(row) + g);
-        unsigned w[8];
-        widen2<FMT>(v.x, w[0], w[1]);
-        widen2<FMT>(v.y, w[2], w[3]);
-        widen2<FMT>(v.z, w[4], w[5]);
-        widen2<FMT>(v.w, w[6], w[7]);
-        cvt_uint4_t *o = reinterpret_cast<cvt_uint4_t *>(orow + 8 * g);
-        o[0] = (cvt_uint4_t){w[0], w[1], w[2], w[3]};
-        o[1] = (cvt_uint4_t){w[4], w[5], w[6], w[7]};
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 7)) {
-        const size_t i = (groups << 3) + threadIdx.x;
-        const unsigned x = (unsigned)row[2 * i] | ((unsigned)row[2 * i + 1] << 8);
-        unsigned lo, hi;
-        widen2<FMT>(x, lo, hi);
-        orow[i] = lo;
-    }
+    iq8_widen_row<FMT>(in + (size_t)s * in_stride * 2, reinterpret_cast<unsigned *>(out) + (size_t)s * out_stride, n);
 }
 
 __global__ __launch_bounds__(CVT_NT) void iq8_narrow_kernel(const int16_t *in, size_t in_stride, uint8_t *out, size_t out_stride, size_t n)

@@ -16,6 +16,7 @@ namespace sdrhip {
 namespace {
 
 #include "frame_pack_body.h"
+#include "rx_unpack_body.h"
 
 // K1r: ragged calls.  1-D grid: workgroup b serves stream s with rows[s].seg0 <= b < rows[s + 1].seg0 (binary search over
 // the per-call table), segment b - seg0 of that stream; a stream gets max(1, ceil(n_used / segment)) segments, so one with
@@ -74,42 +75,12 @@ __global__ __launch_bounds__(256) void frame_pack_ragged_kernel(FrameArgs a, con
     frame_pack_wg<true>(a, s, blockIdx.x, gridDim.x, &r.fc);
 }
 
-// K0r: two samples {re, im, re, im} of one dword -> two IQSample dwords (convert_kernels.hip's rule: U8 = S8 behind one XOR)
-typedef unsigned rg_uint4_t __attribute__((ext_vector_type(4)));
-template <int FMT> __device__ __forceinline__ void rg_widen2(unsigned x, unsigned &lo, unsigned &hi)
-{
-    if (FMT == IQF_U8) x ^= 0x80808080u;
-    const int b0 = (int)(x << 24) >> 24, b1 = (int)(x << 16) >> 24, b2 = (int)(x << 8) >> 24, b3 = (int)x >> 24;
-    lo = ((unsigned)b0 & 0xffffu) | ((unsigned)b1 << 16);
-    hi = ((unsigned)b2 & 0xffffu) | ((unsigned)b3 << 16);
-}
-
+// K0r: K0's row pass (rx_unpack_body.h), stream s widening its own count
 template <int FMT> __global__ __launch_bounds__(256) void iq8_widen_ragged_kernel(const uint8_t *in, size_t in_stride, int16_t *out,
                                                                                    size_t out_stride, const RaggedRow *rows)
 {
     const int s = (int)blockIdx.y;
-    const size_t n = (size_t)rows[s].n_raw;
-    const uint8_t *row = in + (size_t)s * in_stride * 2;
-    unsigned *orow = reinterpret_cast<unsigned *>(out) + (size_t)s * out_stride;
-    const size_t groups = n >> 3;
-    for (size_t g = (size_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (size_t)gridDim.x * 256) {
-        const rg_uint4_t v = SDRHIP_STREAM_LOAD(reinterpret_cast<const rg_uint4_t *>(row) + g);
-        unsigned w[8];
-        rg_widen2<FMT>(v.x, w[0], w[1]);
-        rg_widen2<FMT>(v.y, w[2], w[3]);
-        rg_widen2<FMT>(v.z, w[4], w[5]);
-        rg_widen2<FMT>(v.w, w[6], w[7]);
-        rg_uint4_t *o = reinterpret_cast<rg_uint4_t *>(orow + 8 * g);
-        o[0] = (rg_uint4_t){w[0], w[1], w[2], w[3]};
-        o[1] = (rg_uint4_t){w[4], w[5], w[6], w[7]};
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 7)) {
-        const size_t i = (groups << 3) + threadIdx.x;
-        const unsigned x = (unsigned)row[2 * i] | ((unsigned)row[2 * i + 1] << 8);
-        unsigned lo, hi;
-        rg_widen2<FMT>(x, lo, hi);
-        orow[i] = lo;
-    }
+    iq8_widen_row<FMT>(in + (size_t)s * in_stride * 2, reinterpret_cast<unsigned *>(out) + (size_t)s * out_stride, (size_t)rows[s].n_raw);
 }
 
 } // namespace

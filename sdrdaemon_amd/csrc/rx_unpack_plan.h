@@ -1,5 +1,6 @@
-// rx_unpack_plan.h -- the table of K0x (rx_unpack_mixed_kernels.hip): a batch of sample-fed blocks whose rows differ in format
-// (sdrhip_rx_set_stream_format) -> the rows and segments the kernel walks.  A segment is the samples of one (block, stream) with a
+// rx_unpack_plan.h -- the table of the unpack kernels (rx_unpack_body.h): a batch of sample-fed blocks -> the rows and segments the
+// kernel walks.  One table serves K0p (rx_async_kernels.hip: every stream in the bank's format, fmt == NULL below) and K0x
+// (rx_unpack_mixed_kernels.hip: each stream in its own, sdrhip_rx_set_stream_format).  A segment is the samples of one (block, stream) with a
 // non-zero count; its source is counted in 2-BYTE UNITS from the start of the upload (an 8-bit sample is one unit, an int16 sample
 // two), so that an int16 row behind an odd number of 8-bit samples starts at an odd unit: 2 bytes off a dword boundary.  The table
 // lists the segments stream by stream, block order inside: a stream's segments tile its row from sample 0 on.  Pure host arithmetic
@@ -9,7 +10,7 @@
 #include <cstdint>
 
 namespace sdrhip {
-constexpr unsigned UNPACKX_WG_SAMPLES = 4096; // row samples per K0x workgroup (K0p's figure: 256 lanes x 16 B of int16 output x 4)
+constexpr unsigned UNPACKX_WG_SAMPLES = 4096; // row samples per workgroup (256 lanes x 16 B of int16 output x 4)
 constexpr int UNPACKX_S16 = 0, UNPACKX_U8 = 1, UNPACKX_S8 = 2; // (= SDRHIP_IQ_* of include/sdrhip.h)
 
 struct UnpackXSeg {
@@ -21,7 +22,7 @@ struct UnpackXRow {      // one per stream, then one sentinel row (wg0 = the gri
     uint32_t seg0, nseg; // the stream's segments in the table
     uint32_t wg0;        // its first workgroup: stream s has ceil(total / UNPACKX_WG_SAMPLES) of them (none for an empty row)
     uint32_t total;      // samples of the row
-    uint32_t fmt;        // the stream's format
+    uint32_t fmt;        // the stream's format (K0x reads it; K0p has the bank's as a template argument)
     uint32_t unused[3];
 };
 
@@ -35,18 +36,20 @@ struct UnpackXPlan {
     bool fits;      // every 32-bit field of the table holds its value and the grid is one launch
 };
 
-// what the table of these counts needs; cnt = nblk x S counts, block-major and stream-minor.  Nothing is written
-inline UnpackXPlan unpackx_measure(const size_t *cnt, size_t nblk, size_t S, const int *fmt)
+// what the table of these counts needs; cnt = nblk x S counts, block-major and stream-minor; fmt = S formats, or NULL: every stream
+// has bank_fmt (which is not looked at while an array is given).  Nothing is written
+inline UnpackXPlan unpackx_measure(const size_t *cnt, size_t nblk, size_t S, const int *fmt, int bank_fmt = UNPACKX_S16)
 {
     UnpackXPlan p = {0, 0, 0, true};
     for (size_t s = 0; s < S; ++s) {
+        const size_t bytes = unpackx_sample_bytes(fmt ? fmt[s] : bank_fmt);
         uint64_t total = 0;
         for (size_t b = 0; b < nblk; ++b) {
             const uint64_t n = cnt[b * S + s];
             if (!n) continue;
             if (n > 0xffffffffu || total + n < total) p.fits = false;
             total += n;
-            p.bytes += n * unpackx_sample_bytes(fmt[s]);
+            p.bytes += n * bytes;
             ++p.nseg;
         }
         if (total > (uint64_t)0xffffffffu - UNPACKX_WG_SAMPLES) p.fits = false;
@@ -58,10 +61,12 @@ inline UnpackXPlan unpackx_measure(const size_t *cnt, size_t nblk, size_t S, con
 
 // the table.  rows: S + 1 entries, segs: unpackx_measure().nseg entries.  stride_units = 0: the source is packed, block after
 // block, stream after stream inside a block, each row n * bytes(fmt) long.  stride_units != 0 (one block): the source is strided
-// rows, row s at 2-byte unit s * stride_units whatever its format.  Returns the measure; writes nothing when it does not fit
-inline UnpackXPlan unpackx_fill(const size_t *cnt, size_t nblk, size_t S, const int *fmt, uint64_t stride_units, UnpackXRow *rows, UnpackXSeg *segs)
+// rows, row s at 2-byte unit s * stride_units whatever its format.  fmt == NULL: every stream has bank_fmt, as in unpackx_measure.
+// Returns the measure; writes nothing when it does not fit
+inline UnpackXPlan unpackx_fill(const size_t *cnt, size_t nblk, size_t S, const int *fmt, uint64_t stride_units, UnpackXRow *rows, UnpackXSeg *segs,
+                                int bank_fmt = UNPACKX_S16)
 {
-    const UnpackXPlan p = unpackx_measure(cnt, nblk, S, fmt);
+    const UnpackXPlan p = unpackx_measure(cnt, nblk, S, fmt, bank_fmt);
     if (!p.fits || (stride_units && nblk != 1)) {
         UnpackXPlan bad = p;
         bad.fits = false;
@@ -71,7 +76,7 @@ inline UnpackXPlan unpackx_fill(const size_t *cnt, size_t nblk, size_t S, const 
     uint32_t k = 0;
     for (size_t s = 0; s < S; ++s) {
         UnpackXRow &r = rows[s];
-        r.seg0 = k; r.nseg = 0; r.wg0 = 0; r.total = 0; r.fmt = (uint32_t)fmt[s];
+        r.seg0 = k; r.nseg = 0; r.wg0 = 0; r.total = 0; r.fmt = (uint32_t)(fmt ? fmt[s] : bank_fmt);
         r.unused[0] = r.unused[1] = r.unused[2] = 0;
         for (size_t b = 0; b < nblk; ++b) k += cnt[b * S + s] ? 1 : 0;
     }
@@ -86,7 +91,7 @@ inline UnpackXPlan unpackx_fill(const size_t *cnt, size_t nblk, size_t S, const 
             g.dst = r.total;
             g.n = (uint32_t)n;
             r.total += (uint32_t)n;
-            at += (uint64_t)n * (unpackx_sample_bytes(fmt[s]) / 2);
+            at += (uint64_t)n * (unpackx_sample_bytes((int)r.fmt) / 2);
         }
     uint64_t wg = 0;
     for (size_t s = 0; s < S; ++s) {

@@ -304,28 +304,17 @@ hipError_t launch_iq8_widen_ragged(int fmt, const uint8_t *in, size_t in_stride,
 hipError_t launch_iq8_narrow(const int16_t *in, size_t in_stride, uint8_t *out, size_t out_stride, size_t n, int nstreams, hipStream_t stream);
 
 // Asynchronous ragged Rx batches (sdrhip_rx_submit_ragged, rx_async_kernels.hip).  A batch's samples go up packed, block-major and
-// stream-minor; K0p lays them out as [stream][out_stride] int16 rows (widening 8-bit input on the way).  Segment = the samples of
-// one (block, stream) with a non-zero count; the table lists them stream by stream, block order inside, so that a stream's
-// segments tile its row from sample 0 on.
-struct PackSeg {
-    uint64_t src;   // first sample of the segment in the packed upload
-    uint32_t dst;   // its first sample in the stream's row
-    uint32_t n;     // samples
-};
-struct PackRow {    // one per stream, then one sentinel row (wg0 = the grid)
-    uint32_t seg0, nseg; // the stream's segments in the table
-    uint32_t wg0;        // its first workgroup: stream s has ceil(total / UNPACK_WG_SAMPLES) of them (none for an empty row)
-    uint32_t total;      // samples of the row
-};
-constexpr unsigned UNPACK_WG_SAMPLES = 4096; // row samples per K0p workgroup (256 lanes x 16 B of int16 output x 4)
-// K0p: grid = rows[nstreams].wg0 workgroups; fmt IQF_S16 / IQF_U8 / IQF_S8; out 16-byte aligned, out_stride a multiple of 8
-// samples; `packed` readable 64 bytes past its last sample (the 8-bit loads of an odd segment start read 2 bytes ahead)
-hipError_t launch_unpack_packed(int fmt, const uint8_t *packed, int16_t *out, size_t out_stride, const PackRow *rows, const PackSeg *segs,
+// stream-minor; K0p lays them out as [stream][out_stride] int16 rows (widening 8-bit input on the way).  The table of rows and
+// segments is rx_unpack_plan.h's, filled for the bank's format (unpackx_fill with fmt == NULL).
+// K0p: grid = rows[nstreams].wg0 workgroups; fmt IQF_S16 / IQF_U8 / IQF_S8 (rows[s].fmt is not read); out 16-byte aligned,
+// out_stride a multiple of 8 samples; `packed` dword-aligned and readable 64 bytes past its last sample (the 8-bit loads of an odd
+// segment start read 2 bytes ahead)
+hipError_t launch_unpack_packed(int fmt, const uint8_t *packed, int16_t *out, size_t out_stride, const UnpackXRow *rows, const UnpackXSeg *segs,
                                 int nstreams, unsigned grid, hipStream_t stream);
-// K0x (rx_unpack_mixed_kernels.hip): K0p with the format per stream (rows[s].fmt) and segment sources in 2-byte units of `src`
-// (rx_unpack_plan.h); grid = rows[nstreams].wg0 workgroups; src dword-aligned, out 16-byte aligned, out_stride a multiple of 8
-// samples.  A packed source is readable 64 bytes past its last sample (a realigned chunk reads 2 bytes ahead); strided rows that
-// start on 16 bytes are read inside their own n * bytes(fmt) bytes alone
+// K0x (rx_unpack_mixed_kernels.hip): the same walk over the same table with the format per stream (rows[s].fmt); grid =
+// rows[nstreams].wg0 workgroups; src dword-aligned, out 16-byte aligned, out_stride a multiple of 8 samples.  A packed source is
+// readable 64 bytes past its last sample (a realigned chunk reads 2 bytes ahead); strided rows that start on 16 bytes are read
+// inside their own n * bytes(fmt) bytes alone
 hipError_t launch_unpack_mixed(const void *src, int16_t *out, size_t out_stride, const UnpackXRow *rows, const UnpackXSeg *segs, int nstreams,
                                unsigned grid, hipStream_t stream);
 // frame compaction for the download: frame k of `out` = frame list[k] of `area` (frames of frame_bytes, a multiple of 16)

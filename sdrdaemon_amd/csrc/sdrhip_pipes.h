@@ -273,6 +273,14 @@ int rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const RxRaggedCounts &n, size
 // area (grown behind a synchronisation), the tables, the frame list, and the stream-order rows when the decimator cannot store
 // straight into the windows.  rx_ragged itself then allocates nothing, unless a matrix-core plan it counted on does not apply
 int rx_ragged_room(sdrhip_rx *rx, const RxRaggedCounts &n, RxTabs *tabs);
+// ---- the unpack pass (K0p / K0x) of the two sample-fed entries that have one: a ragged batch and the synchronous per-stream-format call
+// rx_pack_rows: S rows of n_in[s] * bytes(fmt) bytes back to back at dst, fmt = fmts[s] or (fmts NULL) bank_fmt.  Row s is read at
+// src + s * pitch, or (pitch 0) where the row before it ended: an empty row is skipped, a strided row's padding never read
+void rx_pack_rows(char *dst, const void *src, size_t pitch, const size_t *n_in, const int *fmts, int bank_fmt, size_t S);
+// rx_unpack_launch: the table of rx_unpack_plan.h that stands in `pin` (S + 1 rows, then the segments: tab_bytes in all) goes up into
+// `dev`, then K0x (fmts set) or K0p (NULL: the bank's format) lays `src` out as out[S][dstride] with `grid` workgroups
+int rx_unpack_launch(sdrhip_rx *rx, PinnedBuf &pin, DevBuf &dev, size_t tab_bytes, const int *fmts, const void *src, int16_t *out, size_t dstride,
+                     unsigned grid);
 int rx_collector(sdrhip_rx *rx); // the datagram collector, created on first use
 // a uniform or ragged batch that is still being filled goes out as it is (wait_oldest's launch_filling; sdrhip_rx_async.cpp)
 int rx_launch_filling(sdrhip_rx *rx, sdrhip_rx::Batch &b);

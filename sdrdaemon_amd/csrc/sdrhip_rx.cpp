@@ -685,6 +685,36 @@ int sdrhip::rx_ragged_room(sdrhip_rx *rx, const RxRaggedCounts &n, RxTabs *tabs)
     return SDRHIP_OK;
 }
 
+void sdrhip::rx_pack_rows(char *dst, const void *src, size_t pitch, const size_t *n_in, const int *fmts, int bank_fmt, size_t S)
+{
+    const char *rows = static_cast<const char *>(src), *packed = rows;
+    for (size_t s = 0; s < S; ++s) {
+        const size_t bytes = n_in[s] * unpackx_sample_bytes(fmts ? fmts[s] : bank_fmt);
+        if (bytes) memcpy(dst, pitch ? rows + s * pitch : packed, bytes);
+        dst += bytes;
+        packed += bytes;
+    }
+}
+
+int sdrhip::rx_unpack_launch(sdrhip_rx *rx, PinnedBuf &pin, DevBuf &dev, size_t tab_bytes, const int *fmts, const void *src, int16_t *out,
+                             size_t dstride, unsigned grid)
+{
+    sdrhip_ctx *c = rx->ctx;
+    const int S = rx->nstreams;
+    HIP_TRY(hipMemcpyAsync(dev.p, pin.p, tab_bytes, hipMemcpyHostToDevice, c->stream)); // (not counted: a table)
+    pin.mark(c->stream);
+    const UnpackXRow *rows = dev.as<UnpackXRow>();
+    const UnpackXSeg *segs = reinterpret_cast<const UnpackXSeg *>(rows + S + 1);
+    hipError_t e;
+    {
+        KTimer kt(c, SDRHIP_K_CONVERT);
+        e = fmts ? launch_unpack_mixed(src, out, dstride, rows, segs, S, grid, c->stream)
+                 : launch_unpack_packed(rx->in_fmt, static_cast<const uint8_t *>(src), out, dstride, rows, segs, S, grid, c->stream);
+    }
+    if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "unpack launch: %s", hipGetErrorString(e));
+    return SDRHIP_OK;
+}
+
 // per-stream input format, the synchronous call: ONE K0x launch with one segment per stream lays the rows out as [S][*dstride] int16
 // in rx->wide.  Host rows are staged packed -- n_in[s] * bytes(fmt[s]) per row, back to back -- and go up in one copy of exactly
 // those bytes; device rows are read in place (row s at byte 4 * s * in_stride), nothing outside a row's own bytes
@@ -706,29 +736,15 @@ static int rx_unpack_rows(sdrhip_rx *rx, const int16_t *iq_in, size_t in_stride,
     if (!in_dev) {
         if ((rc = rx->f_pin.reserve((size_t)m.bytes))) return rc; // (waits for the previous call's upload)
         if ((rc = reserve_settled(c, rx->f_pk, (size_t)m.bytes + 64))) return rc;
-        char *dst = rx->f_pin.as<char>();
-        for (size_t s = 0; s < S; ++s) {
-            const size_t bytes = n_in[s] * unpackx_sample_bytes(fmts[s]);
-            if (bytes) memcpy(dst, reinterpret_cast<const char *>(iq_in) + s * in_stride * 4, bytes);
-            dst += bytes;
-        }
+        rx_pack_rows(rx->f_pin.as<char>(), iq_in, in_stride * 4, n_in, fmts, 0, S);
         HIP_TRY(link_copy(c, rx->f_pk.p, rx->f_pin.p, (size_t)m.bytes, hipMemcpyHostToDevice, c->stream));
         rx->f_pin.mark(c->stream);
         src = rx->f_pk.p;
     }
-    UnpackXRow *rows = rx->f_tab_pin.as<UnpackXRow>();
-    UnpackXSeg *segs = reinterpret_cast<UnpackXSeg *>(rx->f_tab_pin.as<char>() + rows_bytes);
-    if (!unpackx_fill(n_in, 1, S, fmts, in_dev ? 2 * (uint64_t)in_stride : 0, rows, segs).fits)
+    if (!unpackx_fill(n_in, 1, S, fmts, in_dev ? 2 * (uint64_t)in_stride : 0, rx->f_tab_pin.as<UnpackXRow>(),
+                      reinterpret_cast<UnpackXSeg *>(rx->f_tab_pin.as<char>() + rows_bytes)).fits)
         return fail(SDRHIP_EINVAL, "rx_process_ragged: too many samples for one launch");
-    HIP_TRY(hipMemcpyAsync(rx->f_tab.p, rx->f_tab_pin.p, tab_bytes, hipMemcpyHostToDevice, c->stream)); // (not counted: a table)
-    rx->f_tab_pin.mark(c->stream);
-    hipError_t e;
-    {
-        KTimer kt(c, SDRHIP_K_CONVERT);
-        e = launch_unpack_mixed(src, rx->wide.as<int16_t>(), ds, rx->f_tab.as<UnpackXRow>(),
-                                reinterpret_cast<const UnpackXSeg *>(rx->f_tab.as<char>() + rows_bytes), (int)S, (unsigned)m.grid, c->stream);
-    }
-    if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "unpack launch: %s", hipGetErrorString(e));
+    if ((rc = rx_unpack_launch(rx, rx->f_tab_pin, rx->f_tab, tab_bytes, fmts, src, rx->wide.as<int16_t>(), ds, (unsigned)m.grid))) return rc;
     *din = rx->wide.as<int16_t>();
     *dstride = ds;
     return SDRHIP_OK;

@@ -77,22 +77,18 @@ int rx_launch_ragged(sdrhip_rx *rx, sdrhip_rx::Batch &b)
 {
     sdrhip_ctx *c = rx->ctx;
     const int S = rx->nstreams;
-    const size_t esz = rx->in_fmt == IQF_S16 ? 4 : 2;
     const size_t nblk = b.r_cnt.size() / (size_t)S;
-    // (per-stream input format, sdrhip_rx_set_stream_format: K0x and its table in K0p's place; the setter is refused while a batch
-    // is being filled or in flight, so the formats are the ones the batch's bytes were staged with)
+    // (per-stream input format, sdrhip_rx_set_stream_format: K0x in K0p's place over the same table, rx_unpack_plan.h; the setter is
+    // refused while a batch is being filled or in flight, so the formats are the ones the batch's bytes were staged with)
     const int *fmts = rx->streams.formats();
-    size_t nseg = 0, pk_bytes = 0;
-    for (size_t i = 0; i < b.r_cnt.size(); ++i) {
-        nseg += b.r_cnt[i] ? 1 : 0;
-        pk_bytes += b.r_cnt[i] * (fmts ? unpackx_sample_bytes(fmts[i % (size_t)S]) : esz);
-    }
+    const UnpackXPlan m = unpackx_measure(b.r_cnt.data(), nblk, (size_t)S, fmts, rx->in_fmt);
+    const size_t pk_bytes = (size_t)m.bytes;
     // (what the step below completes: the buffers are sized from it before anything is consumed)
     const RxRaggedCounts n = rx_counts(rx, b.r_tot.data());
     const size_t sum_done = n.sum_done, dstride = (n.max_in + 7) & ~(size_t)7;
     const size_t fb = rx_frame_bytes(rx); // (per-stream fecblk: the slot pitch, a bound on every stream's frame)
-    const size_t rows_bytes = (size_t)(S + 1) * (fmts ? sizeof(UnpackXRow) : sizeof(PackRow)), segs_bytes = nseg * (fmts ? sizeof(UnpackXSeg) : sizeof(PackSeg));
-    const size_t list_off = (rows_bytes + segs_bytes + 15) & ~(size_t)15;
+    const size_t rows_bytes = (size_t)(S + 1) * sizeof(UnpackXRow), tab_bytes = rows_bytes + (size_t)m.nseg * sizeof(UnpackXSeg);
+    const size_t list_off = (tab_bytes + 15) & ~(size_t)15;
     int rc;
     if ((rc = b.r_tab.reserve(list_off + sum_done * 4 + 16))) return rc; // (waits for the table upload of this batch's last use)
     if (list_off + sum_done * 4 + 16 > rx->a_tab.cap || pk_bytes + 64 > rx->a_pk.cap || (size_t)S * dstride * 4 + 16 > rx->a_din.cap ||
@@ -107,40 +103,10 @@ int rx_launch_ragged(sdrhip_rx *rx, sdrhip_rx::Batch &b)
     b.egress = rx->egress; // (set_egress is refused while a batch is being filled: the order of the batch's first block)
     if (b.egress && (rc = rx_egress_room(rx, b, sum_done, fb / SDRHIP_UDPSIZE))) return rc;
 
-    uint64_t wg = 0;
-    if (fmts) {
-        // ---- K0x's table (rx_unpack_plan.h) from the same counts: sources in 2-byte units, the stream's format in its row
-        const UnpackXPlan m = unpackx_fill(b.r_cnt.data(), nblk, (size_t)S, fmts, 0, b.r_tab.as<UnpackXRow>(),
-                                           reinterpret_cast<UnpackXSeg *>(b.r_tab.as<char>() + rows_bytes));
-        if (!m.fits || m.nseg != nseg || m.bytes != pk_bytes) return fail(SDRHIP_EINVAL, "rx batch: too many samples for one launch");
-        wg = m.grid;
-    } else {
-        // ---- K0p's table: segments stream by stream (block order inside), sources at their packed offsets (block-major, stream-minor)
-        PackRow *rows = b.r_tab.as<PackRow>();
-        PackSeg *segs = reinterpret_cast<PackSeg *>(b.r_tab.as<char>() + rows_bytes);
-        std::vector<uint64_t> src(b.r_cnt.size());
-        {
-            uint64_t acc = 0;
-            for (size_t i = 0; i < b.r_cnt.size(); ++i) { src[i] = acc; acc += b.r_cnt[i]; }
-        }
-        uint32_t k = 0;
-        for (int s = 0; s < S; ++s) {
-            PackRow &r = rows[s];
-            r.seg0 = k; r.wg0 = (uint32_t)wg; r.total = (uint32_t)b.r_tot[(size_t)s];
-            uint32_t dst = 0;
-            for (size_t blk = 0; blk < nblk; ++blk) {
-                const size_t i = blk * (size_t)S + (size_t)s, n = b.r_cnt[i];
-                if (!n) continue;
-                segs[k].src = src[i]; segs[k].dst = dst; segs[k].n = (uint32_t)n;
-                dst += (uint32_t)n;
-                ++k;
-            }
-            r.nseg = k - r.seg0;
-            wg += (b.r_tot[(size_t)s] + UNPACK_WG_SAMPLES - 1) / UNPACK_WG_SAMPLES;
-        }
-        rows[S].seg0 = k; rows[S].nseg = 0; rows[S].wg0 = (uint32_t)wg; rows[S].total = 0;
-    }
-    if (wg > 0x7fffffffu) return fail(SDRHIP_EINVAL, "rx batch: too many samples for one launch");
+    // ---- the table: segments stream by stream (block order inside), sources at their packed offsets (block-major, stream-minor)
+    if (!unpackx_fill(b.r_cnt.data(), nblk, (size_t)S, fmts, 0, b.r_tab.as<UnpackXRow>(),
+                      reinterpret_cast<UnpackXSeg *>(b.r_tab.as<char>() + rows_bytes), rx->in_fmt).fits)
+        return fail(SDRHIP_EINVAL, "rx batch: too many samples for one launch");
 
     // ---- uploads: the packed samples, one copy per run of adjacent memory (staged runs are adjacent in the arena), then the table
     uint8_t *pk = rx->a_pk.as<uint8_t>();
@@ -158,17 +124,7 @@ int rx_launch_ragged(sdrhip_rx *rx, sdrhip_rx::Batch &b)
         i = j;
     }
     b.in.mark(c->stream);
-    HIP_TRY(hipMemcpyAsync(rx->a_tab.p, b.r_tab.p, rows_bytes + segs_bytes, hipMemcpyHostToDevice, c->stream)); // (not counted: a table)
-    b.r_tab.mark(c->stream);
-    const PackRow *rows_dev = rx->a_tab.as<PackRow>();
-    const PackSeg *segs_dev = reinterpret_cast<const PackSeg *>(rx->a_tab.as<char>() + rows_bytes);
-    {
-        KTimer kt(c, SDRHIP_K_CONVERT);
-        const hipError_t e = fmts ? launch_unpack_mixed(pk, rx->a_din.as<int16_t>(), dstride, rx->a_tab.as<UnpackXRow>(),
-                                                        reinterpret_cast<const UnpackXSeg *>(rx->a_tab.as<char>() + rows_bytes), S, (unsigned)wg, c->stream)
-                                  : launch_unpack_packed(rx->in_fmt, pk, rx->a_din.as<int16_t>(), dstride, rows_dev, segs_dev, S, (unsigned)wg, c->stream);
-        if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "unpack launch: %s", hipGetErrorString(e));
-    }
+    if ((rc = rx_unpack_launch(rx, b.r_tab, rx->a_tab, tab_bytes, fmts, pk, rx->a_din.as<int16_t>(), dstride, (unsigned)m.grid))) return rc;
 
     // ---- the batch as one ragged step
     std::vector<size_t> nf((size_t)S, 0);
@@ -332,8 +288,8 @@ extern "C" int sdrhip_rx_submit_ragged(sdrhip_rx *rx, const int16_t *iq_in, cons
     if (rx_has_batches(rx, false)) return fail(SDRHIP_EINVAL, "rx_submit_ragged: uniform batches are being filled or in flight: collect them first");
     sdrhip_rx::Batch &b = rx->ring.tail_batch();
     if (b.state >= 2) return fail(SDRHIP_EBUSY, "rx_submit_ragged: every batch of the ring is in flight or lent: collect or release one first");
-    for (int s = 0; s < S; ++s) // (K0p's table holds 32-bit row positions)
-        if ((b.state == 1 ? b.r_tot[(size_t)s] : 0) + n_in[s] > (size_t)0xffffffffu - UNPACK_WG_SAMPLES)
+    for (int s = 0; s < S; ++s) // (the unpack table holds 32-bit row positions)
+        if ((b.state == 1 ? b.r_tot[(size_t)s] : 0) + n_in[s] > (size_t)0xffffffffu - UNPACKX_WG_SAMPLES)
             return fail(SDRHIP_EINVAL, "rx_submit_ragged: a stream's batch would exceed 2^32 - 4096 samples");
     HIP_TRY(hipSetDevice(rx->ctx->device));
     const size_t esz = rx->in_fmt == IQF_S16 ? 4 : 2; // bytes per sample (sdrhip_rx_set_input_format)
@@ -367,15 +323,7 @@ extern "C" int sdrhip_rx_submit_ragged(sdrhip_rx *rx, const int16_t *iq_in, cons
     if (inplace) { // in place: the caller keeps it untouched until the batch is collected
         b.r_runs.push_back(sdrhip_rx::Batch::Run{src, 0, sum_bytes});
     } else if (sum) { // staged packed: one memcpy per non-empty row, never the padding of a strided row
-        char *dst = b.in.as<char>() + b.r_used;
-        size_t soff = 0;
-        for (int s = 0; s < S; ++s) {
-            const size_t bytes = n_in[s] * (fmts ? unpackx_sample_bytes(fmts[s]) : esz);
-            const char *row = in_stride == SDRHIP_PACKED ? src + soff : src + (size_t)s * in_stride * unit;
-            if (bytes) memcpy(dst, row, bytes);
-            dst += bytes;
-            soff += bytes;
-        }
+        rx_pack_rows(b.in.as<char>() + b.r_used, src, in_stride * unit, n_in, fmts, rx->in_fmt, (size_t)S);
         b.r_runs.push_back(sdrhip_rx::Batch::Run{nullptr, b.r_used, sum_bytes});
         b.r_used += sum_bytes;
     }

@@ -136,18 +136,23 @@ def test_open_device_memory(ctx, oracle):
 
 # ------------------------------------------------------------------------------------------------ 2. packed asynchronous batches
 FMT_B = ["u8", "s16", "u8", "s8", "s16", "s8"]
+# the format sets of this section: the mixed array (K0x), and six streams of one bank-wide format set with set_input_format and no
+# array (K0p: the same chunk walk as its own kernel)
+SETS = {"mixed": FMT_B, "s16": ["s16"] * 6, "u8": ["u8"] * 6, "s8": ["s8"] * 6}
 _BATCH = {}
 
 
-def batch_blocks(oracle):
+def batch_blocks(oracle, fmts=FMT_B):
     """three batches of three blocks.  Batch 0: segments of 1..9 samples (every chunk straddles a boundary), an odd 8-bit row in
     front of an int16 row (block 0: rows 0 -> 1; 5 + 3 + 7 odd in front of row 4), two odd 8-bit rows in front of one (block 1,
     rows 0 and 2 of 3 and 5 in front of row 4: aligned again), zero-count rows between them.  Batch 1: totals that cross W with a
     segment boundary inside the chunk that holds sample W (W + 2, W + 1), inside the last chunk of the first workgroup (W - 3, W - 1),
     a row whose first segment is empty.  Batch 2: long int16 segments behind 4097 and 2049 8-bit samples (whole chunks 2 bytes off a
-    dword), then the block that tops every stream past its frame boundary"""
-    if not _BATCH:
-        S = len(FMT_B)
+    dword), then the block that tops every stream past its frame boundary.  (The rows named are FMT_B's; a bank-wide set runs the same
+    counts: an all-8-bit one has odd rows in front of every other row, an all-int16 one none.)  Made once per format set"""
+    key = tuple(fmts)
+    if key not in _BATCH:
+        S = len(fmts)
         plans = [[[5, 9, 3, 7, 6, 1], [3, 2, 5, 0, 8, 4], [1, 0, 9, 5, 0, 2]],
                  [[W + 2, W + 1, W - 3, W + 2, W - 1, 0], [7, 6, 5, 0, 3, W + 3], [1, 9, W + 1, 3, 8, 5]],
                  [[4097, 5000, 0, 0, 3000, 77], [0, 0, 2049, 1, 4100, 0], None]]
@@ -155,48 +160,73 @@ def batch_blocks(oracle):
         plans[2][2] = [F - tot[s] + 3 + s for s in range(S)]
         assert min(plans[2][2]) > 0
         rs = np.random.RandomState(6)
-        chain = Verbatim(oracle, FMT_B, R_OPEN)
+        chain = Verbatim(oracle, fmts, R_OPEN)
         batches, exp = [], []
         for i, plan in enumerate(plans):
             blocks = []
             for j, counts in enumerate(plan):
                 secs, usecs = stamps(3 * i + j, S)
-                blocks.append(([rand_block(rs, [counts[s]], FMT_B[s])[0] for s in range(S)], counts, secs, usecs))
+                blocks.append(([rand_block(rs, [counts[s]], fmts[s])[0] for s in range(S)], counts, secs, usecs))
             batches.append(blocks)
             both = [np.concatenate([b[0][s] for b in blocks]) for s in range(S)]
             exp.append(chain.step(both, blocks[0][2], blocks[0][3]))  # (a batch is one step with its first block's stamps)
-        _BATCH["batches"], _BATCH["exp"] = batches, exp
         assert [e.shape[0] for e in joined(exp)] == [1] * S
-    return _BATCH["batches"], _BATCH["exp"]
+        _BATCH[key] = (batches, exp)
+    return _BATCH[key]
 
 
-@pytest.mark.parametrize("form", ["staged_packed", "pinned_in_place", "strided"])
-def test_packed_batches(ctx, oracle, form):
+def bank_rows(xs, counts):
+    """a bank-wide block as strided rows of the format's dtype (test_gpu_rx_ragged_async's Feed.arg(b, "strided")): padding behind a
+    short row, and 3 samples of it behind the longest"""
+    rows = np.full((len(xs), max(max(counts), 1) + 3, 2), 0x5A, xs[0].dtype)
+    for s, x in enumerate(xs):
+        rows[s, :counts[s]] = x
+    return rows
+
+
+FORMS = ["staged_packed", "pinned_in_place", "strided"]
+
+
+@pytest.mark.parametrize("form,fset", [(form, fset) for fset in ("mixed", "s16", "u8", "s8") for form in FORMS],
+                         ids=[form if fset == "mixed" else form + "-" + fset for fset in ("mixed", "s16", "u8", "s8") for form in FORMS])
+def test_packed_batches(ctx, oracle, form, fset):
     """blocks = 3 in three input forms: per-stream arrays packed for the caller and staged; one packed buffer of pinned memory used in
-    place (its upload is exactly sum n * bytes(fmt)); strided rows of 4-byte units.  Each form's frames equal numpy's, so each other's"""
-    batches, exp = batch_blocks(oracle)
-    rx = open_pipe(ctx, FMT_B)
+    place (its upload is exactly sum n * bytes(fmt)); strided rows of 4-byte units (a bank-wide set: of samples).  Each form's frames
+    equal numpy's, so each other's.  fset "mixed": the array is set and K0x unpacks; "s16" / "u8" / "s8": set_input_format alone, K0p"""
+    import sdrdaemon_amd as sd
+
+    fmts = SETS[fset]
+    batches, exp = batch_blocks(oracle, fmts)
+    if fset == "mixed":
+        rx = open_pipe(ctx, fmts)
+    else:
+        rx = sd.RxPipe(ctx, len(fmts), log2decim=0, fcpos=sd.FC_CEN, sample_bits=16, nb_fec=R_OPEN)
+        rx.set_input_format(fset)
+        assert [rx.stream_format(s) for s in range(len(fmts))] == fmts
     rx.set_async(depth=2, blocks=3)
     pinned = []
     try:
         for i, blocks in enumerate(batches):
             up0 = ctx.counter("h2d_bytes")
             for xs, counts, secs, usecs in blocks:
+                # (the array set: bytes, or a list that the engine packs; bank-wide: samples of the format's dtype)
+                flat = np.concatenate([raw(x) for x in xs]) if fset == "mixed" else np.concatenate(xs).reshape(-1)
                 if form == "staged_packed":
-                    rx.submit_ragged(xs, counts, secs, usecs)
+                    rx.submit_ragged(xs if fset == "mixed" else flat, counts, secs, usecs)
                 elif form == "pinned_in_place":
-                    flat = np.concatenate([raw(x) for x in xs])
-                    buf = ctx.host_alloc((max(flat.size, 1),), np.uint8)
+                    buf = ctx.host_alloc((max(flat.size, 1),), flat.dtype)
                     pinned.append(buf)
                     buf[:flat.size] = flat
                     rx.submit_ragged(buf[:flat.size], counts, secs, usecs)
-                else:
+                elif fset == "mixed":
                     rx.submit_ragged(device_rows(xs, counts, 0x5A).cpu().numpy(), counts, secs, usecs)
+                else:
+                    rx.submit_ragged(bank_rows(xs, counts), counts, secs, usecs)
             up = ctx.counter("h2d_bytes") - up0
-            want = sum(c * BYTES[f] for _, counts, _, _ in blocks for c, f in zip(counts, FMT_B))
-            print(form, "batch", i, "h2d_bytes", up, "sum n * bytes(fmt)", want)
-            assert up == want, (form, i, up, want)
-            same(rx.collect_ragged(), exp[i], (form, i))
+            want = sum(c * BYTES[f] for _, counts, _, _ in blocks for c, f in zip(counts, fmts))
+            print(fset, form, "batch", i, "h2d_bytes", up, "sum n * bytes(fmt)", want)
+            assert up == want, (fset, form, i, up, want)
+            same(rx.collect_ragged(), exp[i], (fset, form, i))
         assert rx.collect_ragged(wait=False) is None
     finally:
         for b in pinned:

@@ -159,14 +159,16 @@ def test_kernel_compiles_without_scratch_and_lds(tmp_path):
 
 
 def test_lives_in_a_translation_unit_of_its_own():
-    """no other kernel file defines or launches it, the library's Makefile builds the new file, and the two host units that need it
-    launch it once each: the asynchronous batch and the synchronous ragged call"""
+    """no other kernel file defines or launches it, the library's Makefile builds the new file, and the host sources have exactly one
+    call site of K0x's launch and one of K0p's (the helper that the asynchronous batch and the synchronous ragged call share); both
+    of those fill the table"""
     for f in sorted(os.listdir(iq8.CSRC)):
         if f.endswith(".hip") and f != SRC:
             assert "unpack_mixed" not in open(os.path.join(iq8.CSRC, f)).read(), f
     assert SRC in open(os.path.join(iq8.CSRC, "Makefile")).read()
+    hosts = {f: open(os.path.join(iq8.CSRC, f)).read() for f in sorted(os.listdir(iq8.CSRC)) if f.endswith(".cpp")}
+    for launch in ("launch_unpack_mixed(", "launch_unpack_packed("):
+        assert sum(h.count(launch) for h in hosts.values()) == 1, launch
     for unit in ("sdrhip_rx.cpp", "sdrhip_rx_async.cpp"):
-        host = open(os.path.join(iq8.CSRC, unit)).read()
-        assert host.count("launch_unpack_mixed(") == 1, unit
-        assert "unpackx_fill(" in host, unit
+        assert "unpackx_fill(" in hosts[unit] and "rx_unpack_launch(" in hosts[unit], unit
     assert "RX_SET_FORMAT" in open(os.path.join(iq8.CSRC, "rx_stream_settings.h")).read()
