@@ -339,11 +339,49 @@ int sdrhip_rx_get_stream_meta(const sdrhip_rx *rx, int stream, uint32_t *center_
  *  5. sampleBytes, sampleBits, nbOriginalBlocks, nbFECBlocks and the stamps stay the hub's own: the reference stamps a frame with
  *     gettimeofday where it is opened (UDPSinkFEC.cpp:90-104), so the caller's tv_sec / tv_usec arrays remain right.  (With
  *     sdrhip_rx_set_stream_fec / sdrhip_rx_set_stream_bits arrays "the hub's own" count and sample size are the stream's own.)
+ *     sampleBytes and sampleBits stay the hub's own unless sdrhip_rx_set_follow_bits is on: then the record formed here contains the
+ *     followed bytes 8 and 9.
  *  6. sdrhip_rx_get_stream_meta keeps reporting the host's values.
  * The values are formed on the device between the collector and the step (one small launch per call or batch); nothing about them
  * comes back to the host, and a submit still synchronises nothing.  With the flag off every entry launches exactly what it launched
  * before the call existed.  SDRHIP_EINVAL, nothing changed: a NULL handle. */
 int sdrhip_rx_set_follow_meta(sdrhip_rx *rx, int on);
+/* The sample size from the incoming meta blocks, for the same entries (sdrhip_rx_process_datagrams, sdrhip_rx_submit_datagrams[_tagged]
+ * / _collect_datagrams, sdrhip_rx_collect_egress): the twin of sdrhip_rx_set_follow_meta for the one value of a stream's signal
+ * description that it leaves to the operator.  sdrdaemonrx hands its own source's get_sample_bits() to its Downsampler and,
+ * decimated, to its sink (sdrdaemonrx.cpp:619-623, 639-643); a hub's source is the radio head -- 8 for an RTL-SDR or HackRF, 12 for
+ * an Airspy or BladeRF, 16 for a test source -- whose size arrives in byte 9 of the meta block of its frames.  on = 0 is the
+ * default.  The call sets a host-side flag only: nothing is enqueued, nothing is waited for.  Allowed at any time, also with
+ * batches in flight: a datagram call reads the flag per call, a batch at its submit; a batch in flight keeps the mode it was
+ * submitted with.  The sample-fed entries (sdrhip_rx_process, _ragged, _submit*) have no incoming meta and ignore the flag.  It is
+ * independent of sdrhip_rx_set_follow_meta: either flag, both or neither may be on.
+ * With on != 0, for every datagram call or batch and every stream s:
+ *  1. the stream's m_outputMeta is taken as it stands after this call's collection, exactly as in rule 1 of
+ *     sdrhip_rx_set_follow_meta: the state the call commits, what sdrhip_fecbuf_stats(..., output_meta) reports after the call
+ *     (SDRdaemonFECBuffer.cpp:72-85); a block 0 that the decoder restored does not set it (SDRdaemonFECBuffer.cpp:150-153).
+ *  2. b = m_outputMeta.m_sampleBits; 1 <= b <= 16: the stream has an incoming size.  Every sample this call's step decimates for the
+ *     stream -- the samples held back from earlier calls included: the call is the granularity, as for the rate -- takes the shift
+ *     pair of (log2decim, b), `x << norm >> trunk` (Decimators.cpp:27-32, 43-44).  Every frame the step opens carries sampleBits =
+ *     b', the size the decimator returns for (log2decim, b), and sampleBytes = (b' - 1) / 8 + 1; the CRC is that of the resulting
+ *     record, and the recovery blocks are computed over that block 0.  log2decim is that of the configuration the call or batch
+ *     runs with.  Only byte 9 is read: the indicator nibble of the incoming m_sampleBytes is ignored.
+ *  3. otherwise (no frame released with its block 0 yet, a sender that says 0, or a value above 16) the stream keeps the size it
+ *     has with the flag off: its entry of the sdrhip_rx_set_stream_bits array, else cfg.sample_bits.  With the array set and the
+ *     flag on, the followed value wins wherever it exists.
+ *  4. a frame left open by an earlier call keeps the block 0 it was opened with (UDPSinkFEC.cpp:160-165); the samples take the new
+ *     shift at once: the rule sdrhip_rx_set_stream_bits has for a change of its array.
+ *  5. sdrhip_rx_get_stream_bits keeps reporting the host's values: the followed size is never brought to the host.
+ *  6. with both flags on, the record sdrhip_rx_set_follow_meta forms (frequency, rate >> log2decim, CRC) contains the followed
+ *     bytes 8 and 9.
+ *  7. with the flag off, or on a handle where this was never called, every entry launches the kernels it launches today, in the
+ *     same order, with the same arguments.
+ * sdrhip_rx_reconfigure, sdrhip_rx_export_stream and sdrhip_rx_import_stream leave the flag alone: it is configuration of the
+ * handle.  sdrhip_rx_reset_streams resets a stream's collector, which zeroes its m_outputMeta: a reset stream falls back under
+ * rule 3 until its head's first block 0 is released.
+ * The values are formed on the device between the collector and the step (one small launch per call or batch, in front of the one
+ * of sdrhip_rx_set_follow_meta); nothing about them comes back to the host, a submit still synchronises nothing, and the link bytes
+ * of a batch are the same with and without the flag.  SDRHIP_EINVAL, nothing changed: a NULL handle. */
+int sdrhip_rx_set_follow_bits(sdrhip_rx *rx, int on);
 /* Feeds n_in device-rate samples per stream.  Completed frames of stream s are written to
  * frames_out + s*frame_stride_bytes as (128 + nb_fec) super blocks of 512 bytes each,
  * frame after frame; *n_frames (per stream, identical for all streams) is the number of
@@ -847,7 +885,8 @@ int sdrhip_rx_egress_stream_blocks(const sdrhip_rx *rx, size_t *blocks);
  * How: every ragged launch takes the shift pair from its stream's row of the per-call table (one word) instead of the launch
  * arguments -- the filter-less kernel, K1r and K1mr, which keep their registers and occupancy -- and the row's third meta word
  * carries sampleBytes / sampleBits per stream, so K2r and KF form block 0 and its CRC as they did.
- * Not covered: following sampleBits from the incoming meta blocks, the uniform step and pipelined mode, the Tx pipe.  (The input
+ * Not covered: following sampleBits from the incoming meta blocks unless sdrhip_rx_set_follow_bits is on (the datagram entries: the
+ * followed size then wins over the array wherever it exists), the uniform step and pipelined mode, the Tx pipe.  (The input
  * format per stream -- sdrhip_rx_set_input_format is bank-wide -- is sdrhip_rx_set_stream_format, below.) */
 int sdrhip_rx_set_stream_bits(sdrhip_rx *rx, const unsigned *sample_bits);
 int sdrhip_rx_get_stream_bits(const sdrhip_rx *rx, int stream, unsigned *sample_bits, unsigned *frame_bits);
@@ -883,8 +922,8 @@ int sdrhip_rx_get_stream_bits(const sdrhip_rx *rx, int stream, unsigned *sample_
  * How: K0x (rx_unpack_mixed_kernels.hip) is K0p with the format read from the stream's row of the per-call table and segment
  * sources in 2-byte units; the synchronous call is a K0x launch with one segment per stream, over the staged upload (host memory)
  * or the caller's rows in place (device memory) -- one pass over the int16 rows more than the bank-wide int16 call.
- * Not covered: a per-stream decimation or Fc position, following sampleBits from the incoming meta blocks, an output format per
- * stream of the Tx pipe. */
+ * Not covered: a per-stream decimation or Fc position, following sampleBits from the incoming meta blocks unless
+ * sdrhip_rx_set_follow_bits is on (the datagram entries, which ignore this array), an output format per stream of the Tx pipe. */
 int sdrhip_rx_set_stream_format(sdrhip_rx *rx, const int *fmt);
 int sdrhip_rx_get_stream_format(const sdrhip_rx *rx, int stream, int *fmt);
 
@@ -903,7 +942,7 @@ int sdrhip_rx_get_stream_format(const sdrhip_rx *rx, int stream, int *fmt);
  *    slot may keep stale bytes); m_frameCount, back to 0; with a datagram collector also what sdrhip_fecbuf_reset_streams covers,
  *    so that m_outputMeta reads "no incoming meta" for sdrhip_rx_set_follow_meta until the stream's next block 0 is released.
  *  - sdrhip_tx_reset_streams: the interpolator histories, and the collector if there is one.
- * What survives: the configuration, the sdrhip_rx_set_stream_meta arrays, the follow flag, the input / output format, the
+ * What survives: the configuration, the sdrhip_rx_set_stream_meta arrays, the two follow flags, the input / output format, the
  * asynchronous ring.
  * Ordering: the call takes the context lock and enqueues ONE small launch on the context's stream behind everything submitted so
  * far; it never synchronises and reads nothing back (the mask goes up from a pinned version of its own: a launch in flight never

@@ -43,7 +43,7 @@ EXPORTS = [
     "sdrhip_rx_process_datagrams", "sdrhip_rx_collector", "sdrhip_rx_carry",
     "sdrhip_rx_submit_datagrams", "sdrhip_rx_collect_datagrams",
     "sdrhip_rx_set_stream_meta", "sdrhip_rx_get_stream_meta",
-    "sdrhip_rx_set_follow_meta",
+    "sdrhip_rx_set_follow_meta", "sdrhip_rx_set_follow_bits",
     "sdrhip_decimators_reset_streams", "sdrhip_interpolators_reset_streams", "sdrhip_fecbuf_reset_streams",
     "sdrhip_rx_reset_streams", "sdrhip_tx_reset_streams",
     "sdrhip_rx_stream_state_bytes", "sdrhip_tx_stream_state_bytes", "sdrhip_rx_export_stream", "sdrhip_rx_import_stream",
@@ -189,6 +189,7 @@ def load():
     lib.sdrhip_rx_set_stream_meta.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.sdrhip_rx_get_stream_meta.argtypes = [vp, i, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.sdrhip_rx_set_follow_meta.argtypes = [vp, i]
+    lib.sdrhip_rx_set_follow_bits.argtypes = [vp, i]
     for name in ("decimators", "interpolators", "fecbuf", "rx", "tx"):
         getattr(lib, "sdrhip_%s_reset_streams" % name).argtypes = [vp, C.POINTER(C.c_uint8)]
     for name in ("rx", "tx"):

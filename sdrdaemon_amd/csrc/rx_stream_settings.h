@@ -1,8 +1,9 @@
 // rx_stream_settings.h -- the per-stream settings of an Rx bank (sdrhip_rx_set_stream_meta / _fec / _bits / _format): which value is in force
 // for stream s, what a set array forces, the streams' zero-stamp records -- and the counts of a ragged step and of a datagram join:
-// what the streams will complete and deliver for given sample counts.  Pure host arithmetic (no HIP, no library header; the frame
+// what the streams will complete and deliver for given sample counts.  Pure arithmetic (no HIP, no library header; the frame
 // area beside it is the only neighbour it sees): sdrhip_rx.cpp and the asynchronous / datagram units ask it,
-// tests/cxx/rx_stream_settings_test.cpp replays it on a CPU.
+// tests/cxx/rx_stream_settings_test.cpp replays it on a CPU.  Its sample-size functions are marked for both sides under hipcc
+// (RX_HD): KFb, the kernel of sdrhip_rx_set_follow_bits, runs them on the device; tests/cxx/rx_follow_bits_rule_test.cpp on a CPU.
 #pragma once
 #include "rx_frame_area.h"
 
@@ -21,8 +22,16 @@ constexpr size_t RX_NB_ORIGINAL = 128;    // original super blocks of a frame (S
 constexpr size_t RX_UDPSIZE = 512;        // bytes of a super block (SDRHIP_UDPSIZE)
 constexpr size_t RX_STREAM_WORDS = 3;     // words per stream of the uniform step's device table (STREAM_META_WORDS)
 
+// ---- the sample-size arithmetic, ONE text for the host and for KFb (rx_follow_bits_kernels.hip, the one kernel file that includes
+// this header): RX_HD is empty without hipcc, so the CPU programs under tests/cxx run the code the kernel runs
+#if defined(__HIPCC__)
+#define RX_HD __host__ __device__
+#else
+#define RX_HD
+#endif
+
 // sampleSize after decimateN (Decimators.cpp:43-44, 112-113 ...): grows by log2decim, capped at 16 bits
-inline unsigned decimated_sample_size(unsigned log2decim, unsigned ss)
+RX_HD inline unsigned decimated_sample_size(unsigned log2decim, unsigned ss)
 {
     if (log2decim == 0) return ss;
     const unsigned target = 16 - log2decim, trunk = ss < target ? 0 : ss - target;
@@ -32,17 +41,63 @@ inline unsigned decimated_sample_size(unsigned log2decim, unsigned ss)
 // int16 truncation (Decimators.cpp:27-32 decimate1: norm = 16 - ss; :43-44, 52-53, 62 and every decimateN: up to 16 - log2decim bits
 // by norm, beyond them by trunk)
 struct DecimShifts { unsigned norm, trunk; };
-inline DecimShifts decimated_shifts(unsigned log2decim, unsigned ss)
+RX_HD inline DecimShifts decimated_shifts(unsigned log2decim, unsigned ss)
 {
     const unsigned target = 16 - log2decim;
     const DecimShifts r = {ss < target ? target - ss : 0, ss < target ? 0 : ss - target};
     return r;
 }
 // the pair as a ragged launch's rows carry it (RaggedRow::shifts)
-inline unsigned ragged_shift_word(unsigned log2decim, unsigned ss)
+RX_HD inline unsigned ragged_shift_word(unsigned log2decim, unsigned ss)
 {
     const DecimShifts sh = decimated_shifts(log2decim, ss);
     return sh.norm | (sh.trunk << 8);
+}
+
+// ---- the sample size followed from the incoming meta blocks (sdrhip_rx_set_follow_bits).  `in_w2` is the third word of the
+// collector's m_outputMeta: m_sampleBytes, m_sampleBits, m_nbOriginalBlocks, m_nbFECBlocks from byte 0 up.  Only byte 1 is read
+// (the indicator nibble of m_sampleBytes is the sender's business); a size outside 1..16 -- MetaDataFEC::init()'s 0 before the
+// first block 0 is released, a sender that says 0, one that says more than an IQSample holds -- is no incoming size
+RX_HD inline bool followed_sample_bits(unsigned in_w2, unsigned *bits)
+{
+    *bits = (in_w2 >> 8) & 0xffu;
+    return *bits >= 1 && *bits <= 16;
+}
+// the third word of a stream's record with sampleBytes / sampleBits of the decimated size ssd (sdrdaemonrx.cpp:642-643) in bytes 0
+// and 1; bytes 2 and 3 (128 and the stream's own nbFECBlocks) stay
+RX_HD inline unsigned meta_w2_with_size(unsigned w2, unsigned ssd)
+{
+    return (w2 & 0xffff0000u) | ((ssd & 0xffu) << 8) | (((ssd - 1) / 8 + 1) & 0xffu);
+}
+// boost::crc_32_type over the little-endian bytes of `w`, 32 bit steps, and over the zero-stamp record {fc, rate, w2, 0, 0}
+// (UDPSinkFEC.cpp:106-109; the byte-wise statement: rx_meta_record below)
+RX_HD inline unsigned meta_crc_word(unsigned crc, unsigned w)
+{
+    crc ^= w;
+    for (int k = 0; k < 32; ++k) crc = (crc >> 1) ^ (0xEDB88320u & (0u - (crc & 1u)));
+    return crc;
+}
+RX_HD inline unsigned meta_record_crc(unsigned fc, unsigned rate, unsigned w2)
+{
+    unsigned crc = 0xFFFFFFFFu;
+    crc = meta_crc_word(crc, fc);
+    crc = meta_crc_word(crc, rate);
+    crc = meta_crc_word(crc, w2);
+    crc = meta_crc_word(crc, 0u); // tv_sec
+    crc = meta_crc_word(crc, 0u); // tv_usec
+    return crc ^ 0xFFFFFFFFu;
+}
+// what KFb writes into a stream's row: the pair for (log2decim, b), the third word with b' = decimated_sample_size(log2decim, b),
+// and the zero-stamp CRC of {fc, rate, that word}.  false (nothing formed): the stream has no incoming size
+struct FollowedSize { unsigned shifts, w2, crc0; };
+RX_HD inline bool followed_size_words(unsigned in_w2, unsigned log2decim, unsigned fc, unsigned rate, unsigned w2, FollowedSize *f)
+{
+    unsigned b;
+    if (!followed_sample_bits(in_w2, &b)) return false;
+    f->shifts = ragged_shift_word(log2decim, b);
+    f->w2 = meta_w2_with_size(w2, decimated_sample_size(log2decim, b));
+    f->crc0 = meta_record_crc(fc, rate, f->w2);
+    return true;
 }
 
 // the 24-byte MetaDataFEC record (UDPSinkFEC.cpp:87-132) with a ZERO stamp, and in w[5] the boost::crc_32_type over its first 20

@@ -552,6 +552,10 @@ hipError_t launch_rx_join_carry(int16_t *rows, size_t row_len, unsigned *carry, 
 // carries a sample rate other than 0 gets {fc, rate >> log2decim, CRC of the zero-stamp record with third word w2} in rows[s]
 // (device: the per-call table, behind its upload); the others keep their row
 hipError_t launch_rx_follow_meta(const FecBufState *state, RaggedRow *rows, int log2decim, int nstreams, hipStream_t stream);
+// KFb (rx_follow_bits_kernels.hip, sdrhip_rx_set_follow_bits): one lane per stream, in front of KF; a stream whose committed
+// m_outputMeta says a sample size b of 1..16 (byte 1 of state[s].out_meta[2]) gets in rows[s] the shift pair of (log2decim, b), w2 with
+// sampleBytes / sampleBits of the decimated size (bytes 2 and 3 kept) and the CRC of {fc, rate, that w2, 0, 0}; the others keep their row
+hipError_t launch_rx_follow_bits(const FecBufState *state, RaggedRow *rows, int log2decim, int nstreams, hipStream_t stream);
 // asynchronous Tx batches (sdrhip_tx_submit_datagrams): stream s's datagrams back to back at a.dg + dg_off[s] (device); njobs /
 // nslots come from the host's shadow of the classification; the scatter pass skips what lies past the classify pass's own counts,
 // max_frames or nslots, the guarded copy a slot whose dmap entry is still -1 (preset by the caller)

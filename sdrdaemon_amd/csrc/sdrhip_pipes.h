@@ -132,6 +132,9 @@ struct sdrhip_rx {
     // ---- outgoing meta from the incoming meta blocks (sdrhip_rx_set_follow_meta): a host flag, read by the datagram entries per call
     // and per batch at its submit; KF (rx_follow_kernels.hip) then rewrites the rows of the streams that have incoming meta
     int follow_meta = 0;
+    // ---- the sample size from the incoming meta blocks (sdrhip_rx_set_follow_bits): its twin, independent of it; KFb
+    // (rx_follow_bits_kernels.hip) rewrites the shift pair, the third meta word and the CRC of the streams that have an incoming size
+    int follow_bits = 0;
     // ---- per-stream lifecycle (sdrhip_rx_reset_streams): the mask's versions on their way up; sdrhip_rx_export_stream /
     // _import_stream: the contiguous device blob KG packs / KS unpacks, and the pinned staging of an import's upload
     sdrhip::StreamMask reset_mask;
@@ -264,11 +267,13 @@ int rx_join_rows(sdrhip_rx *rx, size_t max_released, const char *who);
 // the ragged step (sdrhip_rx_process_ragged).  batch: a ragged asynchronous batch (rx_launch_ragged): int16 device rows that K0p
 // laid out, whatever the input format.  dev_rows: iq_in is int16 device rows whatever `mem` and the input format are (the datagram
 // entry's rows); `mem` then speaks of frames_out alone.  follow (the datagram entries with sdrhip_rx_set_follow_meta on): the collector's
-// committed state on the device; KF forms the meta words of the streams that have incoming meta from it, behind the table's upload
+// committed state on the device; KF forms the meta words of the streams that have incoming meta from it, behind the table's upload.
+// follow_bits (the same entries with sdrhip_rx_set_follow_bits on): the same state; KFb, in front of KF, forms the shift pair, the
+// third meta word and the CRC of the streams that have an incoming sample size.
 // n = rx_counts() of the call's counts, taken while the pipe stands where this call finds it
 int rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const RxRaggedCounts &n, size_t in_stride, const uint32_t *tv_sec, const uint32_t *tv_usec,
               uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem, bool batch = false, bool dev_rows = false,
-              RxTabs *tabs = nullptr, const FecBufState *follow = nullptr);
+              RxTabs *tabs = nullptr, const FecBufState *follow = nullptr, const FecBufState *follow_bits = nullptr);
 // everything the ragged step allocates for these counts, ahead of it (a caller that must not fail between two launches): the frame
 // area (grown behind a synchronisation), the tables, the frame list, and the stream-order rows when the decimator cannot store
 // straight into the windows.  rx_ragged itself then allocates nothing, unless a matrix-core plan it counted on does not apply

@@ -317,6 +317,15 @@ extern "C" int sdrhip_rx_set_follow_meta(sdrhip_rx *rx, int on)
     return SDRHIP_OK;
 }
 
+// ---- the sample size from the incoming meta blocks: the flag alone, the twin of the one above and independent of it
+extern "C" int sdrhip_rx_set_follow_bits(sdrhip_rx *rx, int on)
+{
+    if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
+    sdrhip::CtxLock lock_(rx->ctx);
+    rx->follow_bits = on ? 1 : 0;
+    return SDRHIP_OK;
+}
+
 extern "C" int sdrhip_rx_get_stream_meta(const sdrhip_rx *rx, int stream, uint32_t *center_frequency_khz, uint32_t *sample_rate)
 {
     if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
@@ -755,7 +764,7 @@ static int rx_unpack_rows(sdrhip_rx *rx, const int16_t *iq_in, size_t in_stride,
 // leaves the windows moved (the open frames lie there now) and the rest of the framing state untouched.
 int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const RxRaggedCounts &n, size_t in_stride, const uint32_t *tv_sec, const uint32_t *tv_usec,
                       uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem, bool batch, bool dev_rows, RxTabs *tabs,
-                      const FecBufState *follow)
+                      const FecBufState *follow, const FecBufState *follow_bits)
 {
     sdrhip_ctx *c = rx->ctx;
     // (per-stream fecblk: FB = the slot pitch, 128 + the largest count; a frame of stream s holds rx_stream_blocks(rx, s) of them)
@@ -825,6 +834,14 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const RxRaggedCounts 
     const RaggedRow *rdev = nullptr;
     RaggedPlan plan;
     if ((rc = ragged_prepare(rx->dec, L, rx->cfg.fcpos, n_in, rows.data(), &rdev, &plan, tabs ? &tabs->rows : nullptr))) return rc;
+    if (follow_bits) {
+        // KFb, in front of KF (which runs its CRC over the row's third word): the streams that have an incoming sample size get the
+        // shift pair, sampleBytes / sampleBits and the CRC from the collector's committed m_outputMeta, in the device table, behind its
+        // upload and in front of every kernel that reads a row.  (The host's rows, `ss` and `mw` stay the host's values: every ragged
+        // decimator launch takes the pair from the device row, and K2r the third word)
+        hipError_t e = launch_rx_follow_bits(follow_bits, const_cast<RaggedRow *>(rdev), L, S, c->stream);
+        if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "follow bits launch: %s", hipGetErrorString(e));
+    }
     if (follow) {
         // KF: the streams that have incoming meta get {fc, rate >> L, CRC} from the collector's committed m_outputMeta, in the device
         // table (over the row's own third word), behind its upload and in front of K2r, the one kernel that reads a row's words (the host's rows, `mw` and the
@@ -871,7 +888,7 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const RxRaggedCounts 
     }
     if (rc) return rc;
     rx->consumed = true;
-    if (max_dec && (!direct || sw || follow)) {
+    if (max_dec && (!direct || sw || follow || follow_bits)) {
         FrameArgs fa;
         memset(&fa, 0, sizeof(fa));
         fa.in = lin.as<unsigned>(); fa.out = reinterpret_cast<unsigned *>(area);
@@ -882,7 +899,7 @@ int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const RxRaggedCounts 
         hipError_t e;
         if (direct) {
             // K1mr's pieces wrote the meta blocks with the shared record (that kernel has no register to spare for the streams'
-            // words): K2r, without samples, writes them again with each stream's own values (the host's arrays, or KF's)
+            // words): K2r, without samples, writes them again with each stream's own values (the host's arrays, KFb's or KF's)
             int max_started = 0;
             for (int s = 0; s < S; ++s) if (rows[(size_t)s].meta_count > max_started) max_started = rows[(size_t)s].meta_count;
             e = max_started ? launch_frame_meta_ragged(fa, rdev, max_started, S, c->stream) : hipSuccess;

@@ -88,7 +88,8 @@ static int rx_submit_batch(sdrhip_rx *rx, FecBufBatch &in, const uint32_t *tv_se
     // ---- decimate, frame, encode: one ragged step; KJ moves every row's remainder to its head (the device's own counts)
     if (any) {
         if ((rc = rx_ragged(rx, rx->j_rows.as<int16_t>(), n, rx->j_row_len, tv_sec, tv_usec, nullptr, 0, nf.data(), SDRHIP_MEM_DEVICE,
-                            true, true, &b.d_tabs, rx->follow_meta ? fecbuf_committed_state(rx->fb) : nullptr))) // (the flag as it stands at this submit)
+                            true, true, &b.d_tabs, rx->follow_meta ? fecbuf_committed_state(rx->fb) : nullptr, // (the flags as they stand at this submit)
+                            rx->follow_bits ? fecbuf_committed_state(rx->fb) : nullptr)))
             return fecbuf_batch_lost(who, rc);
         hipError_t e = launch_rx_join_carry(rx->j_rows.as<int16_t>(), rx->j_row_len, carry_dev, counts, (unsigned)U, S, c->stream);
         if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "rx join launch: %s (the batch is lost)", hipGetErrorString(e));

@@ -895,6 +895,14 @@ class RxPipe(_Handle):
         followed ones are in the delivered frames, and in collector_stats(s)["output_meta"]."""
         check(self.ctx.lib.sdrhip_rx_set_follow_meta(self.h, 1 if on else 0))
 
+    def set_follow_bits(self, on=True):
+        """The sample size from the incoming meta blocks (sdrhip_rx_set_follow_bits), for process_datagrams / submit_datagrams: a
+        stream whose collector holds a meta block that says a sample size b of 1..16 decimates with the shift of (log2decim, b) and
+        announces the decimated size in the frames later calls and submits open; the others keep the host's size (set_stream_bits,
+        else sample_bits).  A host flag, independent of set_follow_meta: never synchronises, a batch in flight keeps the mode of its
+        submit.  stream_bits() keeps reporting the host's values: the followed ones are in the delivered frames."""
+        check(self.ctx.lib.sdrhip_rx_set_follow_bits(self.h, 1 if on else 0))
+
     def follow_testsource(self, ts):
         """What sdrdaemonrx's loop does with its source, per stream of a TestSource bank: setCenterFrequency(frequency / 1000)
         and setSampleRate(srate >> decim) (sdrdaemonrx.cpp:597,624,644)"""
