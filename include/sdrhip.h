@@ -923,9 +923,41 @@ int sdrhip_rx_get_stream_bits(const sdrhip_rx *rx, int stream, unsigned *sample_
  * sources in 2-byte units; the synchronous call is a K0x launch with one segment per stream, over the staged upload (host memory)
  * or the caller's rows in place (device memory) -- one pass over the int16 rows more than the bank-wide int16 call.
  * Not covered: a per-stream decimation or Fc position, following sampleBits from the incoming meta blocks unless
- * sdrhip_rx_set_follow_bits is on (the datagram entries, which ignore this array), an output format per stream of the Tx pipe. */
+ * sdrhip_rx_set_follow_bits is on (the datagram entries, which ignore this array).  (The Tx pipe has an output format per stream
+ * of its own: sdrhip_tx_set_stream_format, below.) */
 int sdrhip_rx_set_stream_format(sdrhip_rx *rx, const int *fmt);
 int sdrhip_rx_get_stream_format(const sdrhip_rx *rx, int stream, int *fmt);
+
+/* ---- Per-stream output format of the Tx pipe: HackRF and int16 sinks in one bank.
+ * In the reference the format belongs to the sink object, which is per process and so per stream: HackRFSink.cpp:671-672 sends
+ * real() >> 8, imag() >> 8, FileSink.cpp:216-277 writes int16 IQ, and sdrdaemontx.cpp:195-255 picks one sink per process.
+ * sdrhip_tx_set_stream_format: fmt = host array of nstreams entries, each SDRHIP_IQ_S16 or SDRHIP_IQ_S8; NULL = bank-wide again
+ * (the value of sdrhip_tx_set_output_format).  sdrhip_tx_get_stream_format: *fmt = the format in force for the stream.
+ * Contract.  Per stream the result is byte for byte that of a one-stream sdrhip_tx with sdrhip_tx_set_output_format(fmt[s]) fed the
+ * same input, call after call: samples, meta blocks, records and all carried histories.
+ * Entries: the array holds through sdrhip_tx_process (host and device memory), pipelined mode and sdrhip_tx_flush, sdrhip_tx_submit /
+ * sdrhip_tx_collect, sdrhip_tx_process_datagrams, sdrhip_tx_submit_datagrams / sdrhip_tx_submit_datagrams_tagged /
+ * sdrhip_tx_collect_datagrams.  A batch takes the formats in force when it is handed in, as it takes the factor.
+ * Addressing while the array is set (the rule of sdrhip_rx_set_stream_format, mirrored).  Counts stay in samples.  out_stride counts
+ * 4-byte units: row s starts at byte 4 * s * out_stride whatever its format; an 8-bit row occupies the first 2 * n bytes of its row,
+ * nothing behind them is written.  Device memory: base 16-byte aligned, out_stride a multiple of 4, else SDRHIP_EALIGN.  An array of
+ * equal entries is allowed: it gives the bytes of that bank-wide format in the 4-byte stride unit (bank-wide 8-bit strides count
+ * 2-byte samples).
+ * The setter changes host state only: nothing is enqueued, nothing waited for.  It is refused, nothing changed, for a NULL handle,
+ * SDRHIP_IQ_U8 or an unknown value in any entry, while asynchronous batches are in flight and while a pipelined batch waits (the
+ * rules of sdrhip_tx_set_output_format).  sdrhip_tx_set_output_format stays allowed; while the array is set its value is unused.
+ * sdrhip_tx_reconfigure and sdrhip_tx_reset_streams do not clear the array; export and import of a stream are untouched (the format
+ * is configuration): an imported stream takes the destination's format.  The no-copy mode (option tx_gather) does not apply while
+ * the array is set.  A handle on which the setter was never called launches the same kernels in the same order with the same
+ * arguments.
+ * Link traffic: every host-memory entry downloads exactly sum_s n[s] * bytes(fmt[s]) sample bytes, plus records and meta blocks as
+ * before ("d2h_bytes").
+ * How: K5x (interp_mixed_kernels.hip) is K5 / K5w with one int per stream read by a scalar load and a wave-uniform branch to the
+ * int16 or the 8-bit last stage; K6x is x1, a copy or the narrowing per stream.  The table of formats goes up on the context's stream
+ * in front of the first launch after a change.
+ * Not covered: a per-stream interpolation factor, SDRHIP_IQ_U8 on Tx, a format argument for the bare sdrhip_interpolate. */
+int sdrhip_tx_set_stream_format(sdrhip_tx *tx, const int *fmt);
+int sdrhip_tx_get_stream_format(const sdrhip_tx *tx, int stream, int *fmt);
 
 /* ---- Per-stream lifecycle: one stream of a bank begins again while the others run on.
  * In the reference one stream is one sdrdaemonrx / sdrdaemontx process, and restarting that process gives the stream what the

@@ -53,6 +53,7 @@ EXPORTS = [
     "sdrhip_rx_set_stream_fec", "sdrhip_rx_get_stream_fec", "sdrhip_rx_egress_stream_blocks",
     "sdrhip_rx_set_stream_bits", "sdrhip_rx_get_stream_bits", "sdrhip_decimate_ragged_bits",
     "sdrhip_rx_set_stream_format", "sdrhip_rx_get_stream_format",
+    "sdrhip_tx_set_stream_format", "sdrhip_tx_get_stream_format",
 ]
 
 
@@ -184,6 +185,8 @@ def load():
     lib.sdrhip_rx_get_stream_bits.argtypes = [vp, i, C.POINTER(u), C.POINTER(u)]
     lib.sdrhip_rx_set_stream_format.argtypes = [vp, C.POINTER(C.c_int)]
     lib.sdrhip_rx_get_stream_format.argtypes = [vp, i, C.POINTER(C.c_int)]
+    lib.sdrhip_tx_set_stream_format.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.sdrhip_tx_get_stream_format.argtypes = [vp, i, C.POINTER(C.c_int)]
     lib.sdrhip_decimate_ragged_bits.argtypes = [vp, i, i, C.POINTER(u), vp, C.POINTER(sz), sz, vp, sz, C.POINTER(sz), i]
     lib.sdrhip_rx_egress_stream_blocks.argtypes = [vp, C.POINTER(sz)]
     lib.sdrhip_rx_set_stream_meta.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]

@@ -21,6 +21,7 @@
 //  * segment 0 takes the histories from the bank state, other segments rebuild them from the
 //    64 preceding inputs (the cascade's memory is 43 inputs) with stores suppressed.
 #include "interp_body.h"
+#include "interp_count.h"
 #include "interp_wave.h"
 
 namespace sdrhip {
@@ -56,22 +57,7 @@ template <int L, int WPW> __global__ __launch_bounds__(WNT * WPW) void interp_wa
     interp_wave_segment<L, true>(a, seg, blockIdx.y, lds[w]);
 }
 
-// Ragged launches (InterpArgs::count): the grid is planned for the largest stream, every (stream, segment) finds its stream's
-// own end.  The count is wave-uniform (one stream per workgroup row): a scalar load.  A segment past its stream's last returns at
-// once; the last one (segment 0 of a stream without input: it copies state_cur through) writes state_next, as seg == nseg - 1
-// does in a uniform launch.  -> false: nothing to do; else `a` holds the stream's n_in and an nseg whose last segment is its own.
-__device__ __forceinline__ bool ragged_args(InterpArgs &a, int seg, int stream, size_t seg_len)
-{
-    const int k = __builtin_amdgcn_readfirstlane(a.count[(size_t)stream * (size_t)a.count_stride]);
-    size_t n = (size_t)(unsigned)k * (size_t)(unsigned)a.count_unit;
-    if (n > a.n_in) n = a.n_in; // (never beyond what the grid and the buffers were planned for)
-    const size_t start = (size_t)seg * seg_len;
-    if (seg != 0 && start >= n) return false;
-    if (start + seg_len >= n) a.nseg = seg + 1;
-    a.n_in = n;
-    return true;
-}
-
+// Ragged launches (InterpArgs::count): ragged_args of interp_count.h finds each (stream, segment)'s own end
 template <int L> __global__ __launch_bounds__(NT) void interp_ragged_kernel(InterpArgs a)
 {
     __shared__ __attribute__((aligned(16))) int lds[IGeo<(L == 6) ? 5 : L>::ldsDw];

@@ -84,7 +84,9 @@ struct InterpCount { // InterpArgs::count / count_stride / count_unit: per-strea
 // count (optional): stream s takes count[s * stride] * unit inputs, at most n_in (the grid is planned for n_in, the largest)
 int interpolate_device(sdrhip_interpolators *p, int log2interp, const int16_t *in, size_t n_in, size_t in_stride, int16_t *out,
                        size_t out_stride, size_t *n_out, const InterpGather *gather = nullptr, const InterpCount *count = nullptr,
-                       int out_fmt = IQF_S16); // IQF_S8: `out` holds 2-byte samples, out_stride counts them (multiple of 8 for streams > 1)
+                       int out_fmt = IQF_S16, // IQF_S8: `out` holds 2-byte samples, out_stride counts them (multiple of 8 for streams > 1)
+                       const int *fmt_dev = nullptr); // the format per stream (device, IQF_S16 | IQF_S8; K5x / K6x): out_fmt is unused, row s
+                                                      // starts at byte 4 * s * out_stride (a multiple of 4 for streams > 1); NULL: the paths above
 // FEC buffer bank (sdrhip_fecbuf.cpp) for the Tx pipe fed datagrams: the datagram arguments of sdrhip_fecbuf_write_and_read, then
 // the bank's call with data_out on the device and dgrams / block0_out in `mem` memory (host: staged; block0_out downloaded on the
 // context's stream, not synchronised); *counts (device) = the per-stream counts [S][FB_COUNTS] the classify pass left (FB_K: frames)

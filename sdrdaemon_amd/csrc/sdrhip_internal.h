@@ -334,6 +334,14 @@ hipError_t launch_interpolate_ragged(int log2interp, const InterpArgs &a, hipStr
 hipError_t launch_interpolate_wave_ragged(int log2interp, const InterpArgs &a, hipStream_t stream);
 hipError_t launch_interpolate_ragged_s8(int log2interp, const InterpArgs &a, hipStream_t stream);
 hipError_t launch_interpolate_wave_ragged_s8(int log2interp, const InterpArgs &a, hipStream_t stream);
+// K5x / K6x (interp_mixed_kernels.hip): the output format per stream, fmt[s] = IQF_S16 | IQF_S8 on the device (a second kernel
+// argument: InterpArgs is as it was).  a.out_stride counts 4-byte units: row s starts at byte 4 * s * out_stride whatever its
+// format, an 8-bit row takes the first 2 * n bytes of it; a.count set = the count variants.  K6x is x1: the copy (int16 rows) or the
+// narrowing (8-bit rows) of n samples per stream, or of count[s * count_stride] * count_unit <= n where count is given
+hipError_t launch_interpolate_mixed(int log2interp, const InterpArgs &a, const int *fmt, hipStream_t stream);
+hipError_t launch_interpolate_wave_mixed(int log2interp, const InterpArgs &a, const int *fmt, hipStream_t stream);
+hipError_t launch_interpolate1_mixed(const int16_t *in, size_t in_stride, uint8_t *out, size_t out_stride, size_t n, int nstreams, const int *fmt,
+                                     const int *count, int count_stride, int count_unit, hipStream_t stream);
 
 // frames are processed in groups that share one coefficient matrix (one frame per half-wave)
 constexpr int GF_FRAMES_PER_GROUP = 2;

@@ -72,14 +72,24 @@ namespace sdrhip {
 bool interpolate_gather_ok(const sdrhip_ctx *c, int log2interp) { return c->opt.interp_wave && log2interp >= 2; }
 
 int interpolate_device(sdrhip_interpolators *p, int log2interp, const int16_t *in, size_t n_in, size_t in_stride, int16_t *out,
-                       size_t out_stride, size_t *n_out, const InterpGather *gather, const InterpCount *count, int out_fmt)
+                       size_t out_stride, size_t *n_out, const InterpGather *gather, const InterpCount *count, int out_fmt, const int *fmt_dev)
 {
     sdrhip_ctx *c = p->ctx;
     if (n_out) *n_out = n_in << log2interp;
     if (n_in == 0) return SDRHIP_OK;
     if (gather && !interpolate_gather_ok(p->ctx, log2interp)) return fail(SDRHIP_EINVAL, "internal: gathered input needs the wave interpolator");
     if (gather && count) return fail(SDRHIP_EINVAL, "internal: no ragged gather");
-    if (gather && out_fmt != IQF_S16) return fail(SDRHIP_EINVAL, "internal: gathered input has int16 output only");
+    if (gather && (out_fmt != IQF_S16 || fmt_dev)) return fail(SDRHIP_EINVAL, "internal: gathered input has int16 output only");
+    if (log2interp == 0 && fmt_dev) { // the copy or its narrowing, stream by stream (K6x)
+        hipError_t e;
+        {
+            KTimer kt(c, SDRHIP_K_INTERPOLATE);
+            e = launch_interpolate1_mixed(in, in_stride, reinterpret_cast<uint8_t *>(out), out_stride, n_in, p->nstreams, fmt_dev, count ? count->count : nullptr,
+                                          count ? count->stride : 0, count ? count->unit : 0, c->stream);
+        }
+        if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "mixed-format copy launch: %s", hipGetErrorString(e));
+        return SDRHIP_OK;
+    }
     if (log2interp == 0 && out_fmt == IQF_S8) { // the copy, narrowed (K6n)
         hipError_t e;
         {
@@ -107,7 +117,8 @@ int interpolate_device(sdrhip_interpolators *p, int log2interp, const int16_t *i
     hipError_t e;
     {
         KTimer kt(c, SDRHIP_K_INTERPOLATE);
-        if (out_fmt == IQF_S8) {
+        if (fmt_dev) e = use_wave ? launch_interpolate_wave_mixed(log2interp, a, fmt_dev, c->stream) : launch_interpolate_mixed(log2interp, a, fmt_dev, c->stream);
+        else if (out_fmt == IQF_S8) {
             if (count) e = use_wave ? launch_interpolate_wave_ragged_s8(log2interp, a, c->stream) : launch_interpolate_ragged_s8(log2interp, a, c->stream);
             else e = use_wave ? launch_interpolate_wave_s8(log2interp, a, c->stream) : launch_interpolate_s8(log2interp, a, c->stream);
         } else if (count) e = use_wave ? launch_interpolate_wave_ragged(log2interp, a, c->stream) : launch_interpolate_ragged(log2interp, a, c->stream);

@@ -183,7 +183,10 @@ struct sdrhip_tx {
         sdrhip::PinnedBuf tab, seg;
         std::vector<size_t> frames; // released frames per stream
         int log2interp = 0;
-        size_t esz = 4;
+        // bytes per output sample of every stream, as the batch was handed in.  rows4 (sdrhip_tx_set_stream_format's array was set):
+        // the caller's row s starts 4 * s * out_stride bytes into iq_out, and a batch of received frames lies packed in `out` too
+        std::vector<uint8_t> esz;
+        bool rows4 = false;
     };
     sdrhip::BatchRing<ABatch> ring;
     // device buffers of the datagram batches, shared by the ring (the context's stream orders the batches): the packed datagrams,
@@ -194,6 +197,12 @@ struct sdrhip_tx {
     sdrhip_fecbuf *fb = nullptr;
     // ---- output format (sdrhip_tx_set_output_format): IQF_S8 = 2-byte samples from the interpolator's last stage (or K6n for x1)
     int out_fmt = sdrhip::IQF_S16;
+    // ---- per-stream output format (sdrhip_tx_set_stream_format): the host array (empty: bank-wide, out_fmt) and its version; K5x /
+    // K6x read one int per stream from a device table, which goes up on the context's stream in front of the first launch that
+    // finds its version changed (tx_format_table).  The setter touches s_fmt / s_fmt_ver alone
+    std::vector<int> s_fmt;
+    uint64_t s_fmt_ver = 0, s_fmt_up = 0; // versions of the array: as set / as uploaded (0: none yet)
+    sdrhip::TableVersions s_fmt_tab;
     // ---- per-stream lifecycle (sdrhip_tx_reset_streams): the mask's versions on their way up; sdrhip_tx_export_stream /
     // _import_stream: the contiguous device blob KG packs / KS unpacks, and the pinned staging of an import's upload
     sdrhip::StreamMask reset_mask;
@@ -308,6 +317,27 @@ int rx_area_room(sdrhip_rx *rx, const size_t *done);
 // ---- Tx: bytes per output sample, and the row pitch (samples) of the library's own output buffers: 16-byte rows either way
 inline size_t tx_esz(const sdrhip_tx *tx) { return tx->out_fmt == IQF_S8 ? 2 : 4; }
 inline size_t tx_pitch(const sdrhip_tx *tx, size_t n) { return tx->out_fmt == IQF_S8 ? (n + 7) & ~(size_t)7 : (n + 3) & ~(size_t)3; }
+// ---- per-stream output format (sdrhip_tx_set_stream_format).  tx_formats: the array is set.  Then: tx_esz(tx, s) = bytes per sample
+// of stream s, and every row -- the caller's and the library's own -- starts 4 * s * stride bytes into its buffer, the stride in
+// 4-byte units; tx_pitch4 = the stride of the library's own rows, a multiple of 4 (16-byte rows).  Unset, tx_esz(tx, s) is tx_esz(tx)
+inline bool tx_formats(const sdrhip_tx *tx) { return !tx->s_fmt.empty(); }
+inline size_t tx_esz(const sdrhip_tx *tx, size_t s) { return tx_formats(tx) ? (tx->s_fmt[s] == IQF_S8 ? 2 : 4) : tx_esz(tx); }
+inline size_t tx_pitch4(size_t n) { return (n + 3) & ~(size_t)3; }
+// row pitch and bytes per pitch unit of the library's own output rows, whichever mode the handle is in
+inline size_t tx_own_pitch(const sdrhip_tx *tx, size_t n) { return tx_formats(tx) ? tx_pitch4(n) : tx_pitch(tx, n); }
+inline size_t tx_unit(const sdrhip_tx *tx) { return tx_formats(tx) ? 4 : tx_esz(tx); }
+// a device output the interpolator may store to with 16-byte stores: aligned, the stride a multiple of 4 (int16) / 8 (8-bit)
+// samples; with the array set, a multiple of 4 of its 4-byte units
+inline bool tx_out_aligned(const sdrhip_tx *tx, const void *p, size_t stride)
+{
+    return aligned16(p) && (tx->nstreams == 1 || (stride & (!tx_formats(tx) && tx->out_fmt == IQF_S8 ? 7 : 3)) == 0);
+}
+// the device table of the array (NULL while it is unset): uploaded on the context's stream when its version changed
+int tx_format_table(sdrhip_tx *tx, const int **fmt_dev);
+// rows of the library's own device buffer `dout` (pitch `dos` units of tx_unit) to the caller's host rows (out_stride units), n[s]
+// samples of stream s (n NULL: n_all each): one link copy per run of adjacent rows of equal format and length -- exactly
+// sum n[s] * tx_esz(tx, s) bytes cross the link
+hipError_t tx_download_rows(sdrhip_tx *tx, void *iq_out, size_t out_stride, const void *dout, size_t dos, const size_t *n, size_t n_all);
 // asynchronous batches of one kind in flight: raw datagrams (dg) or received frames
 inline bool tx_in_flight(const sdrhip_tx *tx, bool dg)
 {
@@ -320,6 +350,7 @@ bool tx_gather_applies(const sdrhip_tx *tx, int log2interp);
 int tx_decode_gather(sdrhip_tx *tx, const uint8_t *drx, const uint8_t *indices, size_t nframes, InterpGather *g, uint8_t *block0 = nullptr);
 int tx_collector(sdrhip_tx *tx); // the datagram collector, created on first use
 // the interpolator behind the collector of a datagram call, each stream's own count (device, the classify pass's) of n_max at most:
-// x1 to 8-bit = K6n narrows; x2 .. x64 = one ragged launch; x1 int16 = nothing, the collector wrote the samples where they go
+// x1 to 8-bit = K6n narrows; x2 .. x64 = one ragged launch; x1 int16 = nothing, the collector wrote the samples where they go.
+// (Per-stream formats: dos counts 4-byte units; x1 is K6x, x2 .. x64 K5x, both up to each stream's own count)
 int tx_interpolate_counts(sdrhip_tx *tx, const int16_t *pay, size_t n_max, size_t pitch, int16_t *dout, size_t dos, const int *counts);
 } // namespace sdrhip

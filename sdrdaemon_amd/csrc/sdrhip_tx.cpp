@@ -77,7 +77,64 @@ extern "C" int sdrhip_tx_set_output_format(sdrhip_tx *tx, int fmt)
     return SDRHIP_OK;
 }
 
+// the sink object is per process and so per stream (sdrdaemontx.cpp:195-255): host state only, the table goes up with the next launch
+extern "C" int sdrhip_tx_set_stream_format(sdrhip_tx *tx, const int *fmt)
+{
+    if (!tx) return fail(SDRHIP_EINVAL, "tx is NULL");
+    sdrhip::CtxLock lock_(tx->ctx);
+    for (int s = 0; fmt && s < tx->nstreams; ++s) {
+        if (fmt[s] == SDRHIP_IQ_U8) return fail(SDRHIP_EINVAL, "tx_set_stream_format: stream %d: SDRHIP_IQ_U8 is an input format (RTL-SDR); the Tx side gives S16 or S8", s);
+        if (fmt[s] != SDRHIP_IQ_S16 && fmt[s] != SDRHIP_IQ_S8) return fail(SDRHIP_EINVAL, "tx_set_stream_format: stream %d: unknown format %d", s, fmt[s]);
+    }
+    if (tx->ring.busy()) return fail(SDRHIP_EINVAL, "tx_set_stream_format: asynchronous batches are in flight: collect them first");
+    if (tx->late.have) return fail(SDRHIP_EINVAL, "tx_set_stream_format: a pipelined batch waits: sdrhip_tx_flush it first");
+    if (fmt) tx->s_fmt.assign(fmt, fmt + tx->nstreams);
+    else tx->s_fmt.clear();
+    ++tx->s_fmt_ver;
+    return SDRHIP_OK;
+}
+
+extern "C" int sdrhip_tx_get_stream_format(const sdrhip_tx *tx, int stream, int *fmt)
+{
+    if (!tx || !fmt) return fail(SDRHIP_EINVAL, "tx_get_stream_format: NULL argument");
+    sdrhip::CtxLock lock_(tx->ctx);
+    if (stream < 0 || stream >= tx->nstreams) return fail(SDRHIP_EINVAL, "tx_get_stream_format: stream %d of %d", stream, tx->nstreams);
+    *fmt = tx_formats(tx) ? tx->s_fmt[(size_t)stream] : tx->out_fmt;
+    return SDRHIP_OK;
+}
+
 namespace sdrhip {
+int tx_format_table(sdrhip_tx *tx, const int **fmt_dev)
+{
+    *fmt_dev = nullptr;
+    if (!tx_formats(tx)) return SDRHIP_OK;
+    if (tx->s_fmt_up != tx->s_fmt_ver) {
+        const void *dev = nullptr;
+        if (int rc = tx->s_fmt_tab.upload(tx->ctx->stream, tx->s_fmt.data(), tx->s_fmt.size() * sizeof(int), &dev)) return rc;
+        tx->s_fmt_up = tx->s_fmt_ver;
+    }
+    *fmt_dev = static_cast<const int *>(tx->s_fmt_tab.current());
+    return SDRHIP_OK;
+}
+
+hipError_t tx_download_rows(sdrhip_tx *tx, void *iq_out, size_t out_stride, const void *dout, size_t dos, const size_t *n, size_t n_all)
+{
+    sdrhip_ctx *c = tx->ctx;
+    const size_t S = (size_t)tx->nstreams, unit = tx_unit(tx);
+    for (size_t s = 0; s < S;) {
+        const size_t len = n ? n[s] : n_all, esz = tx_esz(tx, s);
+        size_t e = s + 1;
+        while (e < S && (n ? n[e] : n_all) == len && tx_esz(tx, e) == esz) ++e;
+        if (len) {
+            const hipError_t err = link_copy2d(c, static_cast<char *>(iq_out) + s * out_stride * unit, out_stride * unit,
+                                               static_cast<const char *>(dout) + s * dos * unit, dos * unit, len * esz, e - s, hipMemcpyDeviceToHost, c->stream);
+            if (err != hipSuccess) return err;
+        }
+        s = e;
+    }
+    return hipSuccess;
+}
+
 int tx_decode(sdrhip_tx *tx, const uint8_t *drx, const uint8_t *indices, size_t nframes, DevBuf &pay, size_t pstride, const DecodeSide *side,
               uint8_t *block0)
 {
@@ -101,7 +158,7 @@ int tx_decode(sdrhip_tx *tx, const uint8_t *drx, const uint8_t *indices, size_t 
 bool tx_gather_applies(const sdrhip_tx *tx, int log2interp)
 {
     const sdrhip_ctx *c = tx->ctx;
-    return c->opt.tx_gather && !tx->pipelined && tx->out_fmt == IQF_S16 && interpolate_gather_ok(c, log2interp) && fec_decode_gather_ok(c);
+    return c->opt.tx_gather && !tx->pipelined && tx->out_fmt == IQF_S16 && !tx_formats(tx) && interpolate_gather_ok(c, log2interp) && fec_decode_gather_ok(c);
 }
 int tx_decode_gather(sdrhip_tx *tx, const uint8_t *drx, const uint8_t *indices, size_t nframes, InterpGather *g, uint8_t *block0)
 {
@@ -123,28 +180,24 @@ int tx_decode_gather(sdrhip_tx *tx, const uint8_t *drx, const uint8_t *indices, 
     return SDRHIP_OK;
 }
 
-// a device output the interpolator may store to with 16-byte stores: aligned, the stride a multiple of 4 (int16) / 8 (8-bit) samples
-static bool tx_out_aligned(const sdrhip_tx *tx, const void *p, size_t stride) { return aligned16(p) && (tx->nstreams == 1 || (stride & (tx->out_fmt == IQF_S8 ? 7 : 3)) == 0); }
-
 // interpolate a decoded batch on the first stream into the caller's buffer (host: through outbuf + a download)
 static int tx_interpolate(sdrhip_tx *tx, int log2interp, const DevBuf &pay, size_t n_payload, size_t pstride, int16_t *iq_out, size_t out_stride, int mem,
                    const InterpGather *gather = nullptr)
 {
-    sdrhip_ctx *c = tx->ctx;
     const int S = tx->nstreams;
     const size_t n_res = n_payload << log2interp;
     int16_t *dout = iq_out;
     size_t dos = out_stride;
     int rc;
-    const size_t esz = tx_esz(tx);
+    const int *fmt_dev = nullptr; // (set: the array of sdrhip_tx_set_stream_format; strides then count 4-byte units)
+    if ((rc = tx_format_table(tx, &fmt_dev))) return rc;
     if (mem == SDRHIP_MEM_HOST) {
-        dos = tx_pitch(tx, n_res);
-        if ((rc = tx->outbuf.reserve((size_t)S * dos * esz + 16))) return rc;
+        dos = tx_own_pitch(tx, n_res);
+        if ((rc = tx->outbuf.reserve((size_t)S * dos * tx_unit(tx) + 16))) return rc;
         dout = tx->outbuf.as<int16_t>();
     }
-    if ((rc = interpolate_device(tx->itp, log2interp, gather ? nullptr : pay.as<int16_t>(), n_payload, pstride, dout, dos, nullptr, gather, nullptr, tx->out_fmt))) return rc;
-    if (mem == SDRHIP_MEM_HOST)
-        HIP_TRY(link_copy2d(c, iq_out, out_stride * esz, dout, dos * esz, n_res * esz, S, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = interpolate_device(tx->itp, log2interp, gather ? nullptr : pay.as<int16_t>(), n_payload, pstride, dout, dos, nullptr, gather, nullptr, tx->out_fmt, fmt_dev))) return rc;
+    if (mem == SDRHIP_MEM_HOST) HIP_TRY(tx_download_rows(tx, iq_out, out_stride, dout, dos, nullptr, n_res));
     return SDRHIP_OK;
 }
 
@@ -157,7 +210,7 @@ static int tx_deliver_late(sdrhip_tx *tx, int16_t *iq_out, size_t out_stride, si
     if (S == 1) out_stride = n_res;
     if (!iq_out) return fail(SDRHIP_EINVAL, "tx: NULL output buffer for the waiting batch");
     if (out_stride < n_res) return fail(SDRHIP_EINVAL, "tx: out_stride smaller than the waiting batch (%zu samples per stream)", n_res);
-    if (mem == SDRHIP_MEM_DEVICE && !tx_out_aligned(tx, iq_out, out_stride)) return fail(SDRHIP_EALIGN, "tx_process: device output must be 16-byte aligned, its stride a multiple of 4 (8-bit: 8) samples");
+    if (mem == SDRHIP_MEM_DEVICE && !tx_out_aligned(tx, iq_out, out_stride)) return fail(SDRHIP_EALIGN, "tx_process: device output must be 16-byte aligned, its stride a multiple of 4 (8-bit: 8) samples (per-stream formats: of 4 4-byte units)");
     const int sel = tx->psel ^ 1; // (psel already points at the buffer the NEXT decode fills)
     HIP_TRY(hipStreamWaitEvent(c->stream, tx->ev_dec, 0));
     int rc = tx_interpolate(tx, tx->late.log2interp, tx->payload[sel], tx->late.n_payload, tx->late.pstride, iq_out, out_stride, mem);
@@ -172,10 +225,14 @@ static int tx_deliver_late(sdrhip_tx *tx, int16_t *iq_out, size_t out_stride, si
 int tx_interpolate_counts(sdrhip_tx *tx, const int16_t *pay, size_t n_max, size_t pitch, int16_t *dout, size_t dos, const int *counts)
 {
     const int L = tx->log2interp;
-    if (n_max == 0 || (L == 0 && tx->out_fmt != IQF_S8)) return SDRHIP_OK;
+    const int *fmt_dev = nullptr;
+    if (int rc = tx_format_table(tx, &fmt_dev)) return rc;
+    if (n_max == 0 || (L == 0 && tx->out_fmt != IQF_S8 && !fmt_dev)) return SDRHIP_OK;
     // (x1 has no count-aware kernel: K6n narrows the largest stream's length; past a stream's own count the samples are unspecified)
-    if (L == 0) return interpolate_device(tx->itp, 0, pay, n_max, pitch, dout, dos, nullptr, nullptr, nullptr, IQF_S8);
     const InterpCount cnt = {counts + FB_K, FB_COUNTS, (int)SDRHIP_SAMPLES_PER_FRAME};
+    // (per-stream formats: K6x at x1 and K5x know each stream's own count; nothing is written past it)
+    if (fmt_dev) return interpolate_device(tx->itp, L, pay, n_max, pitch, dout, dos, nullptr, nullptr, &cnt, tx->out_fmt, fmt_dev);
+    if (L == 0) return interpolate_device(tx->itp, 0, pay, n_max, pitch, dout, dos, nullptr, nullptr, nullptr, IQF_S8);
     return interpolate_device(tx->itp, L, pay, n_max, pitch, dout, dos, nullptr, nullptr, &cnt, tx->out_fmt);
 }
 
@@ -282,7 +339,7 @@ extern "C" int sdrhip_tx_process(sdrhip_tx *tx, const uint8_t *rx, const uint8_t
         HIP_TRY(link_copy2d(c, tx->rxbuf.p, nframes * fb, rx, rx_stride_bytes, nframes * fb, S, hipMemcpyHostToDevice, c->stream));
         drx = tx->rxbuf.as<uint8_t>();
     } else {
-        if (!tx_out_aligned(tx, iq_out, out_stride)) return fail(SDRHIP_EALIGN, "tx_process: device output must be 16-byte aligned, its stride a multiple of 4 (8-bit: 8) samples");
+        if (!tx_out_aligned(tx, iq_out, out_stride)) return fail(SDRHIP_EALIGN, "tx_process: device output must be 16-byte aligned, its stride a multiple of 4 (8-bit: 8) samples (per-stream formats: of 4 4-byte units)");
     }
     // no-copy: decode (restored blocks + map only), then the interpolator reads the received frames through the map; otherwise
     // decode all S * nframes frames in one batch: payload [S][nframes][127 * 508] = [S][n_payload] samples
@@ -327,12 +384,12 @@ extern "C" int sdrhip_tx_process_datagrams(sdrhip_tx *tx, const uint8_t *dgrams,
     if (max_frames > 0x3fffffffu) return fail(SDRHIP_EINVAL, "tx_process_datagrams: max_frames too large");
     if (max_frames > 0 && (!iq_out || !info_out)) return fail(SDRHIP_EINVAL, "tx_process_datagrams: NULL iq_out / info_out");
     const size_t per = max_frames * SDRHIP_SAMPLES_PER_FRAME, n_res_max = per << L;
-    const bool s8 = tx->out_fmt == IQF_S8;
-    const size_t esz = tx_esz(tx);
-    if (S == 1) out_stride = tx_pitch(tx, n_res_max);
+    const bool mixed = tx_formats(tx), s8 = !mixed && tx->out_fmt == IQF_S8; // (mixed: strides count 4-byte units, every x1 is K6x)
+    const size_t unit = tx_unit(tx);
+    if (S == 1) out_stride = tx_own_pitch(tx, n_res_max);
     if (out_stride < n_res_max) return fail(SDRHIP_EINVAL, "tx_process_datagrams: out_stride below max_frames x 16129 << log2interp");
     if (mem == SDRHIP_MEM_DEVICE && max_frames > 0 && (!aligned16(iq_out) || (out_stride & (s8 ? 7 : 3)) || (reinterpret_cast<uintptr_t>(block0_out) & 3u)))
-        return fail(SDRHIP_EALIGN, "tx_process_datagrams: device iq_out must be 16-byte aligned, out_stride a multiple of 4 (8-bit: 8) samples, block0_out 4-byte aligned");
+        return fail(SDRHIP_EALIGN, "tx_process_datagrams: device iq_out must be 16-byte aligned, out_stride a multiple of 4 (8-bit: 8) samples (per-stream formats: of 4 4-byte units), block0_out 4-byte aligned");
     HIP_TRY(hipSetDevice(c->device));
     int rc;
     if ((rc = tx_collector(tx))) return rc;
@@ -340,12 +397,12 @@ extern "C" int sdrhip_tx_process_datagrams(sdrhip_tx *tx, const uint8_t *dgrams,
     // where the collector writes getSlotData: the caller's device iq_out (Upsampler's m_interp == 0 pass-through, Upsampler.cpp:54-57)
     // or payload[0]; host memory: outbuf / payload[0], downloaded below
     // (8-bit output with x1: the collector writes int16 to payload[0] as for the other ratios, K6n narrows it into dout)
-    const size_t pitch = (per + 3) & ~(size_t)3, n_res_pitch = tx_pitch(tx, n_res_max);
-    const bool direct = L == 0 && !s8;
+    const size_t pitch = (per + 3) & ~(size_t)3, n_res_pitch = tx_own_pitch(tx, n_res_max);
+    const bool direct = L == 0 && !s8 && !mixed;
     int16_t *dout = iq_out;
     size_t dos = out_stride;
     if (max_frames > 0 && mem == SDRHIP_MEM_HOST) {
-        if ((rc = tx->outbuf.reserve((size_t)S * n_res_pitch * esz + 16))) return rc;
+        if ((rc = tx->outbuf.reserve((size_t)S * n_res_pitch * unit + 16))) return rc;
         dout = tx->outbuf.as<int16_t>(); dos = n_res_pitch;
     }
     if (max_frames > 0 && !direct && (rc = tx->payload[0].reserve((size_t)S * pitch * 4 + 16))) return rc;
@@ -361,8 +418,10 @@ extern "C" int sdrhip_tx_process_datagrams(sdrhip_tx *tx, const uint8_t *dgrams,
     // (the collector's state has moved on: from here a failure loses the call's frames, it is never replayed)
     if ((rc = tx_interpolate_counts(tx, tx->payload[0].as<int16_t>(), n_max, pitch, dout, dos, counts))) return rc;
     if (mem == SDRHIP_MEM_HOST) {
-        if (kmax > 0)
-            HIP_TRY(link_copy2d(c, iq_out, out_stride * esz, dout, dos * esz, (n_max << L) * esz, (size_t)S, hipMemcpyDeviceToHost, c->stream));
+        // (bank-wide: every row up to the largest count, as one copy; per-stream formats: each stream's own samples)
+        std::vector<size_t> own;
+        for (int s = 0; mixed && s < S; ++s) own.push_back((n_frames[s] * SDRHIP_SAMPLES_PER_FRAME) << L);
+        if (kmax > 0) HIP_TRY(tx_download_rows(tx, iq_out, out_stride, dout, dos, mixed ? own.data() : nullptr, n_max << L));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     return SDRHIP_OK;

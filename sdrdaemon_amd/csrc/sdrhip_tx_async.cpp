@@ -36,14 +36,27 @@ extern "C" int sdrhip_tx_submit(sdrhip_tx *tx, const uint8_t *rx, const uint8_t 
     sdrhip_tx::ABatch &b = tx->ring.tail_batch();
     if (b.state == 2) return fail(SDRHIP_EBUSY, "tx_submit: every batch of the ring is in flight: sdrhip_tx_collect first");
     const size_t n_payload = nframes * SDRHIP_SAMPLES_PER_FRAME, n_res = n_payload << tx->log2interp;
-    const size_t pstride = (n_payload + 3) & ~(size_t)3, dos = tx_pitch(tx, n_res), esz = tx_esz(tx);
+    const bool mixed = tx_formats(tx); // (per-stream formats: rows of 4-byte units, gathered into a download of exactly the delivered bytes)
+    const size_t pstride = (n_payload + 3) & ~(size_t)3, dos = tx_own_pitch(tx, n_res), unit = tx_unit(tx);
     const size_t b0_bytes = (size_t)S * nframes * SDRHIP_BLOCK_BYTES;
+    size_t s_bytes = (size_t)S * dos * unit; // sample bytes of the download
+    if (mixed) {
+        s_bytes = 0;
+        for (int s = 0; s < S; ++s) s_bytes += n_res * tx_esz(tx, (size_t)s);
+    }
     int rc;
+    const int *fmt_dev = nullptr;
     // everything that can fail for want of memory comes first
     if ((rc = b.din.reserve((size_t)S * row))) return rc;
-    if ((rc = b.dout.reserve((size_t)S * dos * esz + 16))) return rc;
+    if ((rc = b.dout.reserve((size_t)S * dos * unit + 16))) return rc;
     if ((rc = b.db0.reserve(b0_bytes))) return rc;
-    if ((rc = b.out.reserve((size_t)S * dos * esz + b0_bytes))) return rc;
+    if ((rc = b.out.reserve(s_bytes + b0_bytes))) return rc;
+    if (mixed) {
+        if ((rc = reserve_settled(c, tx->a_gat, s_bytes + 16))) return rc;
+        if ((rc = reserve_settled(c, tx->a_seg, (size_t)3 * S * sizeof(GatherSeg)))) return rc;
+        if ((rc = b.seg.reserve((size_t)3 * S * sizeof(GatherSeg)))) return rc;
+        if ((rc = tx_format_table(tx, &fmt_dev))) return rc;
+    }
     const bool gather = tx_gather_applies(tx, tx->log2interp);
     if (!gather && (rc = tx->payload[0].reserve((size_t)S * pstride * 4 + 16))) return rc;
     if ((rc = b.done.ensure())) return rc;
@@ -65,15 +78,39 @@ extern "C" int sdrhip_tx_submit(sdrhip_tx *tx, const uint8_t *rx, const uint8_t 
     } else {
         if ((rc = tx_decode(tx, b.din.as<uint8_t>(), indices, nframes, tx->payload[0], pstride, nullptr, b.db0.as<uint8_t>()))) return rc;
         if ((rc = interpolate_device(tx->itp, tx->log2interp, tx->payload[0].as<int16_t>(), n_payload, pstride, b.dout.as<int16_t>(), dos, nullptr,
-                                     nullptr, nullptr, tx->out_fmt)))
+                                     nullptr, nullptr, tx->out_fmt, fmt_dev)))
             return rc;
     }
     // (from here on the interpolator's state has advanced: a failure loses the batch, it is never replayed)
-    hipError_t e = link_copy(c, b.out.p, b.dout.p, (size_t)S * dos * esz, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = link_copy(c, b.out.as<char>() + (size_t)S * dos * esz, b.db0.p, b0_bytes, hipMemcpyDeviceToHost, c->stream);
+    hipError_t e = hipSuccess;
+    const void *samples = b.dout.p;
+    if (mixed) { // each row's n_res * bytes(fmt[s]) bytes, back to back
+        GatherSeg *seg = b.seg.as<GatherSeg>();
+        uint64_t dst = 0;
+        for (int s = 0; s < S; ++s) {
+            GatherSeg &g = seg[s];
+            g.src = b.dout.as<uint8_t>() + (size_t)s * dos * 4; g.bytes = n_res * tx_esz(tx, (size_t)s);
+            g.dst = dst; g.pad = 0;
+            dst += g.bytes;
+        }
+        const uint32_t grid = gather_plan(seg, S);
+        if (!grid) e = hipErrorInvalidValue;
+        if (e == hipSuccess) e = hipMemcpyAsync(tx->a_seg.p, seg, (size_t)S * sizeof(GatherSeg), hipMemcpyHostToDevice, c->stream); // (not counted: a table)
+        if (e == hipSuccess) {
+            b.seg.mark(c->stream);
+            KTimer kt(c, SDRHIP_K_CONVERT);
+            e = launch_delivery_gather(tx->a_seg.as<GatherSeg>(), S, grid, tx->a_gat.as<uint8_t>(), c->stream);
+        }
+        samples = tx->a_gat.p;
+    }
+    if (e == hipSuccess) e = link_copy(c, b.out.p, samples, s_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = link_copy(c, b.out.as<char>() + s_bytes, b.db0.p, b0_bytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipEventRecord(b.done, c->stream);
     if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "tx batch download: %s (the batch's %zu frames per stream are lost)", hipGetErrorString(e), nframes);
     b.nframes = nframes; b.n_res = n_res; b.dos = dos;
+    b.rows4 = mixed;
+    b.esz.resize((size_t)S);
+    for (int s = 0; s < S; ++s) b.esz[(size_t)s] = (uint8_t)tx_esz(tx, (size_t)s);
     b.state = 2;
     ++tx->ring.tail;
     return SDRHIP_OK;
@@ -99,7 +136,9 @@ extern "C" int sdrhip_tx_collect(sdrhip_tx *tx, int16_t *iq_out, size_t out_stri
     if (rc) return rc;
     sdrhip_tx::ABatch &b = *bp;
     const int S = tx->nstreams;
-    const size_t esz = tx_esz(tx); // (the format cannot change while a batch is in flight)
+    // (the formats cannot change while a batch is in flight; the batch holds its own all the same)
+    size_t s_bytes = 0;
+    for (int s = 0; s < S; ++s) s_bytes += (b.rows4 ? b.n_res : b.dos) * b.esz[(size_t)s];
     if (b.n_res > max_samples) { // (the batch stays where it is: call again with room for *n_out samples per stream)
         *n_out = b.n_res;
         if (n_frames) *n_frames = b.nframes;
@@ -109,9 +148,14 @@ extern "C" int sdrhip_tx_collect(sdrhip_tx *tx, int16_t *iq_out, size_t out_stri
         if (!iq_out) return fail(SDRHIP_EINVAL, "tx_collect: NULL iq_out");
         if (S == 1) out_stride = b.n_res;
         if (out_stride < b.n_res) return fail(SDRHIP_EINVAL, "tx_collect: out_stride too small");
-        for (int s = 0; s < S; ++s) memcpy(reinterpret_cast<char *>(iq_out) + (size_t)s * out_stride * esz, b.out.as<char>() + (size_t)s * b.dos * esz, b.n_res * esz);
+        const char *src = b.out.as<char>();
+        for (int s = 0; s < S; ++s) { // (per-stream formats: packed rows in, rows of 4-byte units out)
+            const size_t esz = b.esz[(size_t)s];
+            memcpy(reinterpret_cast<char *>(iq_out) + (size_t)s * out_stride * (b.rows4 ? 4 : esz), src, b.n_res * esz);
+            src += (b.rows4 ? b.n_res : b.dos) * esz;
+        }
     }
-    if (block0_out) memcpy(block0_out, b.out.as<char>() + (size_t)S * b.dos * esz, (size_t)S * b.nframes * SDRHIP_BLOCK_BYTES);
+    if (block0_out) memcpy(block0_out, b.out.as<char>() + s_bytes, (size_t)S * b.nframes * SDRHIP_BLOCK_BYTES);
     *n_out = b.n_res;
     if (n_frames) *n_frames = b.nframes;
     b.state = 0;
@@ -151,15 +195,17 @@ static int tx_submit_batch(sdrhip_tx *tx, FecBufBatch &in, const char *who)
         kall += (size_t)res[(size_t)s * 4];
     }
     const int L = tx->log2interp;
-    const bool s8 = tx->out_fmt == IQF_S8, direct = L == 0 && !s8;
-    const size_t esz = tx_esz(tx), per = kmax * SDRHIP_SAMPLES_PER_FRAME, pitch = (per + 3) & ~(size_t)3;
-    const size_t dos = tx_pitch(tx, per << L), n_one = (size_t)SDRHIP_SAMPLES_PER_FRAME << L;
-    const size_t b_samples = kall * n_one * esz, b_total = b_samples + kall * (DG_REC + SDRHIP_BLOCK_BYTES);
+    const bool mixed = tx_formats(tx), s8 = !mixed && tx->out_fmt == IQF_S8, direct = L == 0 && !s8 && !mixed;
+    const size_t unit = tx_unit(tx), per = kmax * SDRHIP_SAMPLES_PER_FRAME, pitch = (per + 3) & ~(size_t)3;
+    const size_t dos = tx_own_pitch(tx, per << L), n_one = (size_t)SDRHIP_SAMPLES_PER_FRAME << L;
+    size_t b_samples = 0; // (each stream's frames at its own sample size)
+    for (int s = 0; s < S; ++s) b_samples += (size_t)res[(size_t)s * 4] * n_one * tx_esz(tx, (size_t)s);
+    const size_t b_total = b_samples + kall * (DG_REC + SDRHIP_BLOCK_BYTES);
     // everything that can fail for want of memory comes before the collector moves (a device buffer that grows waits for the
     // batches in flight)
     if (in.dev_bytes && (rc = reserve_settled(c, tx->a_pk, in.dev_bytes + 16))) return rc;
     if (kmax && !direct && (rc = reserve_settled(c, tx->a_pay, (size_t)S * pitch * 4 + 16))) return rc;
-    if (kmax && (rc = reserve_settled(c, tx->a_out, (size_t)S * dos * esz + 16))) return rc;
+    if (kmax && (rc = reserve_settled(c, tx->a_out, (size_t)S * dos * unit + 16))) return rc;
     if (kmax && (rc = reserve_settled(c, tx->a_b0, (size_t)S * kmax * SDRHIP_BLOCK_BYTES + 16))) return rc;
     if (b_total && (rc = reserve_settled(c, tx->a_gat, b_total + 16))) return rc;
     if ((rc = reserve_settled(c, tx->a_seg, (size_t)3 * S * sizeof(GatherSeg)))) return rc;
@@ -195,7 +241,7 @@ static int tx_submit_batch(sdrhip_tx *tx, FecBufBatch &in, const char *who)
             const size_t k = (size_t)res[(size_t)s * 4];
             if (!k) continue;
             GatherSeg &g = seg[nseg++];
-            if (part == 0) { g.src = tx->a_out.as<uint8_t>() + (size_t)s * dos * esz; g.bytes = k * n_one * esz; }
+            if (part == 0) { g.src = tx->a_out.as<uint8_t>() + (size_t)s * dos * unit; g.bytes = k * n_one * tx_esz(tx, (size_t)s); }
             else if (part == 1) { g.src = reinterpret_cast<const uint8_t *>(pub + (size_t)s * kmax); g.bytes = k * DG_REC; }
             else { g.src = tx->a_b0.as<uint8_t>() + (size_t)s * kmax * SDRHIP_BLOCK_BYTES; g.bytes = k * SDRHIP_BLOCK_BYTES; }
             g.dst = dst; g.pad = 0;
@@ -214,7 +260,9 @@ static int tx_submit_batch(sdrhip_tx *tx, FecBufBatch &in, const char *who)
     if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "tx datagram batch delivery: %s (the batch is lost)", hipGetErrorString(e));
     b.frames.resize((size_t)S);
     for (int s = 0; s < S; ++s) b.frames[(size_t)s] = (size_t)res[(size_t)s * 4];
-    b.dg = true; b.log2interp = L; b.esz = esz;
+    b.dg = true; b.log2interp = L; b.rows4 = mixed;
+    b.esz.resize((size_t)S);
+    for (int s = 0; s < S; ++s) b.esz[(size_t)s] = (uint8_t)tx_esz(tx, (size_t)s);
     b.nframes = kmax; b.n_res = kmax * n_one; b.dos = 0;
     b.state = 2;
     ++tx->ring.tail;
@@ -270,16 +318,16 @@ extern "C" int sdrhip_tx_collect_datagrams(sdrhip_tx *tx, int16_t *iq_out, size_
             return fail(SDRHIP_EINVAL, "tx_collect_datagrams: out_stride below the batch's %zu samples per stream", kmax * n_one);
         }
         if (!iq_out || !info_out) return fail(SDRHIP_EINVAL, "tx_collect_datagrams: NULL iq_out / info_out");
-        size_t kall = 0;
-        for (int s = 0; s < S; ++s) kall += b.frames[(size_t)s];
-        const uint8_t *src = b.out.as<uint8_t>(), *rec = src + kall * n_one * b.esz, *meta = rec + kall * DG_REC;
+        size_t kall = 0, b_samples = 0;
+        for (int s = 0; s < S; ++s) { kall += b.frames[(size_t)s]; b_samples += b.frames[(size_t)s] * n_one * b.esz[(size_t)s]; }
+        const uint8_t *src = b.out.as<uint8_t>(), *rec = src + b_samples, *meta = rec + kall * DG_REC;
         for (int s = 0; s < S; ++s) {
-            const size_t k = b.frames[(size_t)s];
+            const size_t k = b.frames[(size_t)s], esz = b.esz[(size_t)s];
             if (!k) continue;
-            memcpy(reinterpret_cast<uint8_t *>(iq_out) + (size_t)s * out_stride * b.esz, src, k * n_one * b.esz);
+            memcpy(reinterpret_cast<uint8_t *>(iq_out) + (size_t)s * out_stride * (b.rows4 ? 4 : esz), src, k * n_one * esz);
             memcpy(info_out + (size_t)s * max_frames, rec, k * DG_REC);
             if (block0_out) memcpy(block0_out + (size_t)s * max_frames * SDRHIP_BLOCK_BYTES, meta, k * SDRHIP_BLOCK_BYTES);
-            src += k * n_one * b.esz; rec += k * DG_REC; meta += k * SDRHIP_BLOCK_BYTES;
+            src += k * n_one * esz; rec += k * DG_REC; meta += k * SDRHIP_BLOCK_BYTES;
         }
     }
     for (int s = 0; s < S; ++s) n_frames[s] = b.frames[(size_t)s];

@@ -1340,6 +1340,7 @@ class TxPipe(_Handle):
         if pipelined:
             check(ctx.lib.sdrhip_tx_set_pipelined(self.h, 1))
         self.output_format, self._out_dtype = "s16", np.int16
+        self._stream_formats = None
         if output_format != "s16":
             self.set_output_format(output_format)
 
@@ -1351,8 +1352,49 @@ class TxPipe(_Handle):
         check(self.ctx.lib.sdrhip_tx_set_output_format(self.h, code))
         self.output_format, self._out_dtype = fmt, dt
 
+    def set_stream_formats(self, formats=None):
+        """Per-stream output format (sdrhip_tx_set_stream_format): a sequence of nstreams names, each "s16" | "s8" -- what every
+        stream's sink takes (int16 file / HackRF bytes) -- for every later entry; None = bank-wide again (set_output_format's
+        value).  While it is set every entry returns a LIST with one array per stream, (n, 2) int8 or int16, where the bank-wide
+        handle returns one (S, n, 2) array.  Never synchronises; refused (SdrHipError) while async batches are in flight or a
+        pipelined batch waits."""
+        names = None if formats is None else list(formats)
+        arr = None
+        if names is not None:
+            if len(names) != self.nstreams:
+                raise ValueError("formats: %d names, one per stream" % self.nstreams)
+            arr = (C.c_int * self.nstreams)(*[_iq_format(f, ("s16", "s8"))[0] for f in names])
+        check(self.ctx.lib.sdrhip_tx_set_stream_format(self.h, arr))
+        self._stream_formats = names
+
+    def stream_format(self, stream):
+        """-> "s16" | "s8": the format the stream's samples are delivered in"""
+        f = C.c_int(0)
+        check(self.ctx.lib.sdrhip_tx_get_stream_format(self.h, int(stream), C.byref(f)))
+        return [k for k, v in _IQ_FORMATS.items() if v[0] == f.value][0]
+
+    def _rows(self, out, counts):
+        """what an entry returns for the buffer of _out: bank-wide, out[:, :counts] (counts an int) -- or, with set_stream_formats'
+        array set, the list of every stream's own (counts[s], 2) array of its dtype (counts an int or one per stream)"""
+        fm = self._stream_formats
+        if fm is None:
+            return out[:, :counts]
+        n = [counts] * self.nstreams if isinstance(counts, int) else list(counts)
+        res = []
+        for s, f in enumerate(fm):
+            b = out[s, :n[s] * (4 if f == "s16" else 2)]
+            if _is_torch(out):
+                res.append(b.view(torch.int16 if f == "s16" else torch.int8).reshape(n[s], 2))
+            else:
+                res.append(b.view(_IQ_FORMATS[f][1]).reshape(n[s], 2))
+        return res
+
     def _out(self, S, n_res, device=None):
-        """output buffer of (S, pitch, 2) samples: rows of a multiple of 4 (int16) / 8 (int8) samples, the library's stride rule"""
+        """output buffer of (S, pitch, 2) samples: rows of a multiple of 4 (int16) / 8 (int8) samples, the library's stride rule.
+        (set_stream_formats' array set: (S, 4 * pitch) bytes, the pitch a multiple of 4 of its 4-byte units; _rows reads it)"""
+        if self._stream_formats is not None:
+            pad = max((n_res + 3) & ~3, 4)
+            return (torch.empty((S, 4 * pad), dtype=torch.uint8, device=device) if device is not None else np.empty((S, 4 * pad), np.uint8)), pad
         if self._out_dtype == np.int16:
             pad = max((n_res + 3) & ~3, 4)
             return (torch.empty((S, pad, 2), dtype=torch.int16, device=device) if device is not None else np.empty((S, pad, 2), np.int16)), pad
@@ -1395,7 +1437,7 @@ class TxPipe(_Handle):
         n_out = C.c_size_t(0)
         check(self.ctx.lib.sdrhip_tx_process(self.h, _ptr(rx), C.c_void_p(indices.ctypes.data if indices is not None else 0), F, F * NB_ORIGINAL * UDPSIZE,
                                              _ptr(out), pad, C.byref(n_out), MEM_DEVICE if is_t else MEM_HOST))
-        out = out[:, :n_out.value if self.pipelined else n_res]
+        out = self._rows(out, n_out.value if self.pipelined else n_res)
         return out[0] if squeeze else out
 
     # ---- asynchronous host-pointer entry (sdrhip_tx_submit / sdrhip_tx_collect)
@@ -1428,7 +1470,10 @@ class TxPipe(_Handle):
         rec, L = self._log.head(self.log2interp)
         F = rec.most if rec is not None else 0
         cap = max((F * SAMPLES_PER_FRAME) << L, 4)
-        out = np.empty((self.nstreams, cap, 2), self._out_dtype)
+        if self._stream_formats is not None:
+            out, cap = self._out(self.nstreams, cap)
+        else:
+            out = np.empty((self.nstreams, cap, 2), self._out_dtype)
         b0 = np.empty((self.nstreams, max(F, 1), BLOCK_BYTES), np.uint8)
         n_out, nf = C.c_size_t(0), C.c_size_t(0)
         rc = self.ctx.lib.sdrhip_tx_collect(self.h, _ptr(out), cap, cap, _ptr(b0) if block0 else C.c_void_p(0), C.byref(n_out), C.byref(nf), 1 if wait else 0)
@@ -1436,7 +1481,7 @@ class TxPipe(_Handle):
             return None
         check(rc)
         self._log.pop()
-        return (out[:, :n_out.value], b0[:, :nf.value]) if block0 else out[:, :n_out.value]
+        return (self._rows(out, n_out.value), b0[:, :nf.value]) if block0 else self._rows(out, n_out.value)
 
     def flush(self, device=None):
         """pipelined mode: the samples of the batch the last process() call decoded (sdrhip_tx_flush); (S, 0, 2) when nothing
@@ -1446,7 +1491,7 @@ class TxPipe(_Handle):
         out, pad = self._out(S, n_res, device)
         n_out = C.c_size_t(0)
         check(self.ctx.lib.sdrhip_tx_flush(self.h, _ptr(out), pad, C.byref(n_out), MEM_DEVICE if device is not None else MEM_HOST))
-        return out[:, :n_out.value]
+        return self._rows(out, n_out.value)
 
     # ---- datagram entry (sdrhip_tx_process_datagrams)
     def process_datagrams(self, dgrams_per_stream, max_frames=None):
@@ -1473,8 +1518,13 @@ class TxPipe(_Handle):
                                                       info, nf, MEM_DEVICE if is_t else MEM_HOST)
         self.last_n_frames = [int(x) for x in nf]
         check(rc)
-        return [(out[s, :(len(recs) * SAMPLES_PER_FRAME) << self.log2interp], b0[s, :len(recs)], recs)
-                for s, recs in enumerate(_records(info, F, nf))]
+        return self._dg_result(out, b0, _records(info, F, nf), self.log2interp)
+
+    def _dg_result(self, out, b0, records, L):
+        """per stream (iq, block0, records) of a datagram entry: each stream's own samples, in its own dtype while formats are set"""
+        n = [(len(recs) * SAMPLES_PER_FRAME) << L for recs in records]
+        iq = self._rows(out, n) if self._stream_formats is not None else [out[s, :n[s]] for s in range(len(n))]
+        return [(iq[s], b0[s, :len(recs)], recs) for s, recs in enumerate(records)]
 
     # ---- asynchronous datagram batches (sdrhip_tx_submit_datagrams / sdrhip_tx_collect_datagrams)
     def submit_datagrams(self, dgrams_per_stream):
@@ -1510,7 +1560,8 @@ class TxPipe(_Handle):
                 return None
             if rc == 0:  # (a batch that released nothing: collected)
                 self._log.pop()
-                return [(np.zeros((0, 2), self._out_dtype), np.zeros((0, BLOCK_BYTES), np.uint8), []) for _ in range(S)]
+                dts = [self._out_dtype] * S if self._stream_formats is None else [_IQ_FORMATS[f][1] for f in self._stream_formats]
+                return [(np.zeros((0, 2), dt), np.zeros((0, BLOCK_BYTES), np.uint8), []) for dt in dts]
             if rc != -1:
                 check(rc)
             max_frames = max(int(x) for x in nf)
@@ -1525,7 +1576,7 @@ class TxPipe(_Handle):
             return None
         check(rc)
         self._log.pop()
-        return [(out[s, :(len(recs) * SAMPLES_PER_FRAME) << L], b0[s, :len(recs)], recs) for s, recs in enumerate(_records(info, F, nf))]
+        return self._dg_result(out, b0, _records(info, F, nf), L)
 
     def reset_streams(self, streams=None):
         """sdrhip_tx_reset_streams: the streams listed (None: every stream) begin again as a restarted sdrdaemontx does -- zero
