@@ -52,23 +52,13 @@ __global__ __launch_bounds__(CVT_NT) void iq8_narrow_kernel(const int16_t *in, s
     }
 }
 
-unsigned cvt_blocks(size_t n, int nstreams)
-{
-    size_t blocks = ((n >> 3) + CVT_NT - 1) / CVT_NT;
-    // enough workgroups for the whole chip (256 CUs x 8 per row set), then each lane loops
-    const size_t cap = (size_t)2048 / (size_t)(nstreams > 0 ? nstreams : 1) + 1;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    return (unsigned)blocks;
-}
-
 } // namespace
 
 hipError_t launch_iq8_widen(int fmt, const uint8_t *in, size_t in_stride, int16_t *out, size_t out_stride, size_t n, int nstreams,
                             hipStream_t stream)
 {
     if (n == 0) return hipSuccess;
-    const dim3 grid(cvt_blocks(n, nstreams), (unsigned)nstreams);
+    const dim3 grid(cvt_blocks(n >> 3, nstreams), (unsigned)nstreams);
     if (fmt == IQF_U8) hipLaunchKernelGGL((iq8_widen_kernel<IQF_U8>), grid, dim3(CVT_NT), 0, stream, in, in_stride, out, out_stride, n);
     else if (fmt == IQF_S8) hipLaunchKernelGGL((iq8_widen_kernel<IQF_S8>), grid, dim3(CVT_NT), 0, stream, in, in_stride, out, out_stride, n);
     else return hipErrorInvalidValue;
@@ -78,7 +68,7 @@ hipError_t launch_iq8_widen(int fmt, const uint8_t *in, size_t in_stride, int16_
 hipError_t launch_iq8_narrow(const int16_t *in, size_t in_stride, uint8_t *out, size_t out_stride, size_t n, int nstreams, hipStream_t stream)
 {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(iq8_narrow_kernel, dim3(cvt_blocks(n, nstreams), (unsigned)nstreams), dim3(CVT_NT), 0, stream, in, in_stride, out, out_stride, n);
+    hipLaunchKernelGGL(iq8_narrow_kernel, dim3(cvt_blocks(n >> 3, nstreams), (unsigned)nstreams), dim3(CVT_NT), 0, stream, in, in_stride, out, out_stride, n);
     return hipGetLastError();
 }
 

@@ -1,4 +1,4 @@
-// interp_body.h -- the VALU / LDS interpolator cascade (DESIGN.md "K5") as device code, included by interp_kernels.hip.
+// interp_body.h -- the VALU / LDS interpolator cascade (DESIGN.md "K5") as device code, included by interp_variant.h.
 #ifndef SDRHIP_INTERP_BODY_H
 #define SDRHIP_INTERP_BODY_H
 #include "sdrhip_internal.h"
@@ -41,10 +41,10 @@ template <int NS_> struct IGeo {
     static constexpr int ldsDw = base(NS);
 };
 
-// the geometry of the ragged instantiation (interp_ragged_kernel): the same, as a type of its own, so that every helper templated on
-// it is instantiated apart from the uniform kernel's -- sharing them changed how hipcc compiled the uniform kernel
+// the geometry of the ragged instantiation (the IV_COUNT variants of interp_variant.h): the same, as a type of its own, so that every
+// helper templated on it is instantiated apart from the uniform kernel's -- sharing them changed how hipcc compiled the uniform kernel
 template <int NS_> struct IGeoRagged : IGeo<NS_> {};
-// ... and of the 8-bit output instantiations (interp_s8_kernel, interp_s8_count_kernel), for the same reason
+// ... and of the 8-bit output instantiations (IV_S8, IV_S8 | IV_COUNT and the 8-bit branch of IV_TABLE), for the same reason
 template <int NS_, bool RAGGED> struct IGeoS8 : IGeo<NS_> {};
 
 struct IOut {
@@ -202,7 +202,7 @@ template <class G, int S = 0> __device__ __forceinline__ void state_store(const 
 
 // L = log2 interpolation (6 = the reference's 5-stage + zero stuffing variant)
 // one segment (seg of a.nseg, a.nsub_per_seg macro-cycles each) of one stream; lds: IGeo<NS>::ldsDw dwords
-// (RAGGED: the same code, instantiated apart for interp_ragged_kernel, which has set a.n_in / a.nseg for the stream; OF: the output
+// (RAGGED: the same code, instantiated apart for the IV_COUNT variants, which have set a.n_in / a.nseg for the stream; OF: the output
 // format, IQF_S16 or IQF_S8 -- a.out then points at 2-byte samples and a.out_stride counts them)
 template <int L, bool RAGGED = false, int OF = IQF_S16> __device__ __forceinline__ void interp_segment(const InterpArgs &a, int seg, int stream, int *lds)
 {

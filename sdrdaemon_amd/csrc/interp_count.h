@@ -1,5 +1,5 @@
-// interp_count.h -- the per-stream count of a ragged interpolator launch, shared by the kernel files that launch K5 / K5w with
-// InterpArgs::count (interp_kernels.hip, interp_mixed_kernels.hip).
+// interp_count.h -- the per-stream count of a ragged interpolator launch: what the IV_COUNT variants of interp_variant.h do in front
+// of their segment (InterpArgs::count).
 #pragma once
 #include "sdrhip_internal.h"
 

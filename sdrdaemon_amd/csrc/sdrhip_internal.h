@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "decim_plan.h"
+#include "interp_pick.h"
 #include "rx_depart_order.h"
 #include "rx_egress_order.h"
 #include "rx_unpack_plan.h"
@@ -285,7 +286,7 @@ struct InterpArgs {
     const unsigned *gmap;
     const uint8_t *grx, *grest;
     int gframes;
-    // Ragged launches (the Tx pipe fed datagrams; launch_interpolate*_ragged): stream s takes count[s * count_stride] *
+    // Ragged launches (the Tx pipe fed datagrams; the IV_COUNT variants): stream s takes count[s * count_stride] *
     // count_unit inputs, read on the device where the FEC buffer bank's classify pass left the count; n_in / nseg are the
     // largest stream's (the grid).  NULL: every stream takes n_in.
     const int *count;
@@ -300,6 +301,16 @@ hipError_t launch_iq8_widen(int fmt, const uint8_t *in, size_t in_stride, int16_
 // K0r: the same, stream s widening rows[s].n_raw samples (n = the largest: the grid)
 hipError_t launch_iq8_widen_ragged(int fmt, const uint8_t *in, size_t in_stride, int16_t *out, size_t out_stride, size_t n, int nstreams,
                                    const struct RaggedRow *rows, hipStream_t stream);
+// the grid's x of the row passes K0, K6n (8 samples per lane and step: steps = n >> 3) and K6x (sized for its int16 copy: n >> 2):
+// enough workgroups of 256 lanes for the whole chip (256 CUs x 8 per row set), then each lane loops
+inline unsigned cvt_blocks(size_t steps, int nstreams)
+{
+    size_t blocks = (steps + 255) / 256;
+    const size_t cap = (size_t)2048 / (size_t)(nstreams > 0 ? nstreams : 1) + 1;
+    if (blocks > cap) blocks = cap;
+    if (blocks < 1) blocks = 1;
+    return (unsigned)blocks;
+}
 // K6n: int16 rows -> int8 rows of byte 1 of every component (interpolate1 with IQF_S8 output)
 hipError_t launch_iq8_narrow(const int16_t *in, size_t in_stride, uint8_t *out, size_t out_stride, size_t n, int nstreams, hipStream_t stream);
 
@@ -320,26 +331,23 @@ hipError_t launch_unpack_mixed(const void *src, int16_t *out, size_t out_stride,
 // frame compaction for the download: frame k of `out` = frame list[k] of `area` (frames of frame_bytes, a multiple of 16)
 hipError_t launch_frame_gather(const uint8_t *area, size_t frame_bytes, const int32_t *list, size_t nframes, uint8_t *out, hipStream_t stream);
 
-// out_fmt IQF_S8 (interpolators below): InterpArgs::out points at 2-byte samples {int8 re, int8 im} and out_stride counts them; the
-// last stage stores (int8)(v >> 8) of each component (own kernel instantiations; IQF_S16 launches the kernels as they were)
-hipError_t launch_interpolate(int log2interp, const InterpArgs &a, hipStream_t stream);
+// K5 (interp_body.h; log2interp 1..6) / K5w (interp_wave.h: wave-private pipelines in workgroups of one or four independent waves,
+// blocks of 128 inputs; log2interp 2..6): each plans its own grid, the largest stream's where a.count is given
 void plan_interpolate(int log2interp, size_t n_in, int nstreams, int *nsub_per_seg, int *nseg);
-// K5w (interp_wave.h): wave-private pipelines (workgroups of one or four independent waves), blocks of 128 inputs; log2interp 2..6
 void plan_interpolate_wave(int log2interp, size_t n_in, int nstreams, int n_cu, size_t seg_override, int *nsub_per_seg, int *nseg);
-hipError_t launch_interpolate_wave(int log2interp, const InterpArgs &a, hipStream_t stream);
-hipError_t launch_interpolate_s8(int log2interp, const InterpArgs &a, hipStream_t stream);
-hipError_t launch_interpolate_wave_s8(int log2interp, const InterpArgs &a, hipStream_t stream);
-// ... with per-stream input counts (InterpArgs::count), planned like the uniform launch of the largest
-hipError_t launch_interpolate_ragged(int log2interp, const InterpArgs &a, hipStream_t stream);
-hipError_t launch_interpolate_wave_ragged(int log2interp, const InterpArgs &a, hipStream_t stream);
-hipError_t launch_interpolate_ragged_s8(int log2interp, const InterpArgs &a, hipStream_t stream);
-hipError_t launch_interpolate_wave_ragged_s8(int log2interp, const InterpArgs &a, hipStream_t stream);
-// K5x / K6x (interp_mixed_kernels.hip): the output format per stream, fmt[s] = IQF_S16 | IQF_S8 on the device (a second kernel
-// argument: InterpArgs is as it was).  a.out_stride counts 4-byte units: row s starts at byte 4 * s * out_stride whatever its
-// format, an 8-bit row takes the first 2 * n bytes of it; a.count set = the count variants.  K6x is x1: the copy (int16 rows) or the
-// narrowing (8-bit rows) of n samples per stream, or of count[s * count_stride] * count_unit <= n where count is given
-hipError_t launch_interpolate_mixed(int log2interp, const InterpArgs &a, const int *fmt, hipStream_t stream);
-hipError_t launch_interpolate_wave_mixed(int log2interp, const InterpArgs &a, const int *fmt, hipStream_t stream);
+// The bank's one launch: pick = interp_pick's IR_VALU / IR_WAVE answer for this call, `a` planned for pick.route, a.gmap / a.count set
+// exactly where pick.variant says IV_GATHER / IV_COUNT (else hipErrorInvalidValue, as for a ratio the route does not serve).
+// What `out` holds, by variant:
+//  * plain, IV_GATHER, IV_COUNT: int16 IQ, stream s at a.out + 2 * s * a.out_stride, a.out_stride in samples;
+//  * IV_S8 (bank-wide 8-bit output): a.out points at 2-byte samples {int8 re, int8 im} and a.out_stride counts THEM; the last stage
+//    stores (int8)(v >> 8) of each component;
+//  * IV_TABLE (K5x): fmt[s] = IQF_S16 | IQF_S8 on the device decides per stream, and a.out_stride counts 4-BYTE UNITS: row s starts at
+//    byte 4 * s * a.out_stride whatever its format, an 8-bit row takes the first 2 * n bytes of it.  fmt is not read without IV_TABLE.
+hipError_t launch_interpolate(const InterpPick &pick, int log2interp, const InterpArgs &a, const int *fmt, hipStream_t stream);
+// (behind it: the IV_TABLE variants, instantiated in interp_mixed_kernels.hip alone)
+hipError_t launch_interpolate_table(const InterpPick &pick, int log2interp, const InterpArgs &a, const int *fmt, hipStream_t stream);
+// K6x (interp_mixed_kernels.hip) is x1 with a format table, rows as for IV_TABLE: the copy (int16 rows) or the narrowing (8-bit
+// rows) of n samples per stream, or of count[s * count_stride] * count_unit <= n where count is given
 hipError_t launch_interpolate1_mixed(const int16_t *in, size_t in_stride, uint8_t *out, size_t out_stride, size_t n, int nstreams, const int *fmt,
                                      const int *count, int count_stride, int count_unit, hipStream_t stream);
 

@@ -69,40 +69,47 @@ extern "C" int sdrhip_interpolators_reset_streams(sdrhip_interpolators *p, const
 }
 
 namespace sdrhip {
-bool interpolate_gather_ok(const sdrhip_ctx *c, int log2interp) { return c->opt.interp_wave && log2interp >= 2; }
+bool interpolate_gather_ok(const sdrhip_ctx *c, int log2interp) { return interp_pick_wave(c->opt.interp_wave, log2interp); }
 
+// x1, Upsampler::process m_interp == 0: samples_out = samples_in (Upsampler.cpp:54-57).  No filter, so no state: `cur` stays
+static int interpolate1(sdrhip_interpolators *p, InterpRoute route, const int16_t *in, size_t n_in, size_t in_stride, int16_t *out, size_t out_stride,
+                        const InterpCount *count, const int *fmt_dev)
+{
+    sdrhip_ctx *c = p->ctx;
+    uint8_t *out8 = reinterpret_cast<uint8_t *>(out);
+    hipError_t e = hipErrorInvalidValue;
+    const char *what = "copy";
+    switch (route) {
+    case IR_COPY: e = hipMemcpy2DAsync(out, out_stride * 4, in, in_stride * 4, n_in * 4, p->nstreams, hipMemcpyDeviceToDevice, c->stream); break;
+    case IR_K6N: { // the copy, narrowed
+        KTimer kt(c, SDRHIP_K_INTERPOLATE);
+        e = launch_iq8_narrow(in, in_stride, out8, out_stride, n_in, p->nstreams, c->stream);
+        what = "narrow launch";
+        break;
+    }
+    case IR_K6X: { // the copy or its narrowing, stream by stream
+        KTimer kt(c, SDRHIP_K_INTERPOLATE);
+        e = launch_interpolate1_mixed(in, in_stride, out8, out_stride, n_in, p->nstreams, fmt_dev, count ? count->count : nullptr, count ? count->stride : 0,
+                                      count ? count->unit : 0, c->stream);
+        what = "mixed-format copy launch";
+        break;
+    }
+    default: break;
+    }
+    if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "interpolate1 %s: %s", what, hipGetErrorString(e));
+    return SDRHIP_OK;
+}
+
+// validate and pick, plan, one timed launch, flip `cur`
 int interpolate_device(sdrhip_interpolators *p, int log2interp, const int16_t *in, size_t n_in, size_t in_stride, int16_t *out,
                        size_t out_stride, size_t *n_out, const InterpGather *gather, const InterpCount *count, int out_fmt, const int *fmt_dev)
 {
     sdrhip_ctx *c = p->ctx;
     if (n_out) *n_out = n_in << log2interp;
     if (n_in == 0) return SDRHIP_OK;
-    if (gather && !interpolate_gather_ok(p->ctx, log2interp)) return fail(SDRHIP_EINVAL, "internal: gathered input needs the wave interpolator");
-    if (gather && count) return fail(SDRHIP_EINVAL, "internal: no ragged gather");
-    if (gather && (out_fmt != IQF_S16 || fmt_dev)) return fail(SDRHIP_EINVAL, "internal: gathered input has int16 output only");
-    if (log2interp == 0 && fmt_dev) { // the copy or its narrowing, stream by stream (K6x)
-        hipError_t e;
-        {
-            KTimer kt(c, SDRHIP_K_INTERPOLATE);
-            e = launch_interpolate1_mixed(in, in_stride, reinterpret_cast<uint8_t *>(out), out_stride, n_in, p->nstreams, fmt_dev, count ? count->count : nullptr,
-                                          count ? count->stride : 0, count ? count->unit : 0, c->stream);
-        }
-        if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "mixed-format copy launch: %s", hipGetErrorString(e));
-        return SDRHIP_OK;
-    }
-    if (log2interp == 0 && out_fmt == IQF_S8) { // the copy, narrowed (K6n)
-        hipError_t e;
-        {
-            KTimer kt(c, SDRHIP_K_INTERPOLATE);
-            e = launch_iq8_narrow(in, in_stride, reinterpret_cast<uint8_t *>(out), out_stride, n_in, p->nstreams, c->stream);
-        }
-        if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "narrow launch: %s", hipGetErrorString(e));
-        return SDRHIP_OK;
-    }
-    if (log2interp == 0) { // Upsampler::process m_interp == 0: samples_out = samples_in (Upsampler.cpp:54-57)
-        HIP_TRY(hipMemcpy2DAsync(out, out_stride * 4, in, in_stride * 4, n_in * 4, p->nstreams, hipMemcpyDeviceToDevice, c->stream));
-        return SDRHIP_OK;
-    }
+    InterpPick pick = interp_pick(log2interp, c->opt.interp_wave, gather != nullptr, count != nullptr, out_fmt, fmt_dev != nullptr, 0);
+    if (pick.route == IR_REFUSED) return fail(SDRHIP_EINVAL, "internal: %s", pick.why);
+    if (log2interp == 0) return interpolate1(p, pick.route, in, n_in, in_stride, out, out_stride, count, fmt_dev);
     InterpArgs a;
     memset(&a, 0, sizeof(a));
     a.in = in; a.out = out; a.in_stride = in_stride; a.out_stride = out_stride; a.n_in = n_in;
@@ -111,18 +118,13 @@ int interpolate_device(sdrhip_interpolators *p, int log2interp, const int16_t *i
     if (gather) { a.gmap = gather->map; a.grx = gather->rx; a.grest = gather->restored; a.gframes = gather->frames; }
     if (count) { a.count = count->count; a.count_stride = count->stride; a.count_unit = count->unit; }
     // SDRHIP_INTERP_PATH = wave (K5w, default) | valu (K5); SDRHIP_INTERP_SPAN = segment length in inputs (tests)
-    const bool use_wave = c->opt.interp_wave && log2interp >= 2;
-    if (use_wave) plan_interpolate_wave(log2interp, n_in, p->nstreams, c->n_cu, c->opt.interp_span, &a.nsub_per_seg, &a.nseg);
+    if (pick.route == IR_WAVE) plan_interpolate_wave(log2interp, n_in, p->nstreams, c->n_cu, c->opt.interp_span, &a.nsub_per_seg, &a.nseg);
     else plan_interpolate(log2interp, n_in, p->nstreams, &a.nsub_per_seg, &a.nseg);
+    pick.wpw = interp_pick_wpw(pick.route, (size_t)a.nseg * (size_t)a.nstreams);
     hipError_t e;
     {
         KTimer kt(c, SDRHIP_K_INTERPOLATE);
-        if (fmt_dev) e = use_wave ? launch_interpolate_wave_mixed(log2interp, a, fmt_dev, c->stream) : launch_interpolate_mixed(log2interp, a, fmt_dev, c->stream);
-        else if (out_fmt == IQF_S8) {
-            if (count) e = use_wave ? launch_interpolate_wave_ragged_s8(log2interp, a, c->stream) : launch_interpolate_ragged_s8(log2interp, a, c->stream);
-            else e = use_wave ? launch_interpolate_wave_s8(log2interp, a, c->stream) : launch_interpolate_s8(log2interp, a, c->stream);
-        } else if (count) e = use_wave ? launch_interpolate_wave_ragged(log2interp, a, c->stream) : launch_interpolate_ragged(log2interp, a, c->stream);
-        else e = use_wave ? launch_interpolate_wave(log2interp, a, c->stream) : launch_interpolate(log2interp, a, c->stream);
+        e = launch_interpolate(pick, log2interp, a, fmt_dev, c->stream);
     }
     if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "interpolate launch: %s", hipGetErrorString(e));
     p->cur ^= 1;

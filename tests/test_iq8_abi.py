@@ -10,6 +10,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import interp_kernel_names as ikn
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["sdrhip_rx_set_input_format", "sdrhip_tx_set_output_format"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -124,18 +126,17 @@ def test_convert_kernels_compile_without_scratch(tmp_path):
 
 def test_s8_interpolators_compile_without_scratch(tmp_path):
     res = _compile(tmp_path, "interp_kernels.hip")
-    s8 = {n: v for n, v in res.items() if "_s8_" in n}
+    kernels = ikn.by_meaning(res)  # (path, L, WPW, flags) -> name
+    s8 = {k: n for k, n in kernels.items() if k[3] & ikn.S8}
     # K5 (interpolate2 .. 64) and K5w (interpolate4 .. 64, one or four waves per workgroup), uniform and per-stream counts
-    assert len(s8) == 2 * (6 + 10), sorted(s8)
-    twin = {"27interp_wave_s8_count_kernel": "25interp_wave_ragged_kernel", "21interp_wave_s8_kernel": "18interp_wave_kernel",
-            "22interp_s8_count_kernel": "20interp_ragged_kernel", "16interp_s8_kernel": "13interp_kernel"}
-    for n, (vg, sc, occ) in s8.items():
+    for flags in (ikn.S8, ikn.S8 | ikn.COUNT):
+        assert len([k for k in s8 if k[0] == "valu" and k[3] == flags]) == 6 and len([k for k in s8 if k[0] == "wave" and k[3] == flags]) == 10, flags
+    assert len(s8) == 2 * (6 + 10), sorted(s8.values())
+    for (path, L, wpw, flags), n in s8.items():
+        vg, sc, occ = res[n]
         assert sc == 0, "%s uses %d bytes of scratch" % (n, sc)
-        keys = [k for k in twin if k in n]
-        assert len(keys) == 1, n
-        t = n.replace(keys[0], twin[keys[0]])
-        assert t in res, t
-        if "wave" in n:  # K5w: exact
+        t = kernels[(path, L, wpw, flags & ~ikn.S8)]  # the int16 twin: the plain kernel, or the count variant
+        if path == "wave":  # K5w: exact
             assert vg <= res[t][0], "%s: %d VGPRs, its int16 twin %d" % (n, vg, res[t][0])
         else:  # K5: x64 reports 70 against 68: the same allocation of 8-register units and the same occupancy
             assert (vg + 7) // 8 <= (res[t][0] + 7) // 8, "%s: %d VGPRs, its int16 twin %d" % (n, vg, res[t][0])

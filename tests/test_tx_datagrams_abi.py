@@ -9,6 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import interp_kernel_names as ikn
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["sdrhip_tx_process_datagrams", "sdrhip_tx_collector"]
 
@@ -65,11 +67,11 @@ def test_ragged_kernels_compile_without_scratch(tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
     res = _resources(r.stderr)
     # K5 (interpolate2 .. 64) and K5w (interpolate4 .. 64, one or four waves per workgroup)
-    ragged = {n: v for n, v in res.items() if "ragged" in n}
-    assert len(ragged) == 6 + 10, sorted(ragged)
-    for n, (vg, sc) in ragged.items():
+    kernels = ikn.by_meaning(res)  # (path, L, WPW, flags) -> name
+    ragged = {k: n for k, n in kernels.items() if k[3] == ikn.COUNT}
+    assert len([k for k in ragged if k[0] == "valu"]) == 6 and len([k for k in ragged if k[0] == "wave"]) == 10, sorted(ragged.values())
+    for (path, L, wpw, _), n in ragged.items():
+        vg, sc = res[n]
         assert sc == 0, "%s uses %d bytes of scratch" % (n, sc)
-        uniform = n.replace("interp_wave_ragged_kernel", "interp_wave_kernel").replace("interp_ragged_kernel", "interp_kernel")
-        uniform = uniform.replace("25interp_wave_kernel", "18interp_wave_kernel").replace("20interp_kernel", "13interp_kernel")
-        assert uniform in res, uniform
+        uniform = kernels[(path, L, wpw, 0)]  # the plain kernel of the same ratio and workgroup
         assert vg <= res[uniform][0], "%s: %d VGPRs, the uniform kernel %d" % (n, vg, res[uniform][0])

@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import interp_kernel_names as ikn
 import test_iq8_abi as iq8
 from test_rx_stream_format_abi import _comment, _norm
 
@@ -124,11 +125,15 @@ def _compile(tmp_path, src):
     return {n: v + (l,) for (n, v), l in zip(res.items(), lds)}  # VGPRs, scratch, occupancy, LDS bytes
 
 
-# K5x kernel -> its two bank-wide twins (mangled name fragments: the template arguments behind them are the same)
-TWINS = {"30interp_wave_mixed_count_kernel": ("25interp_wave_ragged_kernel", "27interp_wave_s8_count_kernel"),
-         "24interp_wave_mixed_kernel": ("18interp_wave_kernel", "21interp_wave_s8_kernel"),
-         "25interp_mixed_count_kernel": ("20interp_ragged_kernel", "22interp_s8_count_kernel"),
-         "19interp_mixed_kernel": ("13interp_kernel", "16interp_s8_kernel")}
+# The K5x families: a table variant (path, flags) of interp_variant.h; its two bank-wide twins are the kernels of the same
+# (path, L, WPW) with the table flag taken away (int16) or replaced by the 8-bit flag.  (The case ids are the ones these cases have
+# always had: the name fragments of the four templates the table variants replaced.)
+FAMILIES = {"30interp_wave_mixed_count_kernel": ("wave", ikn.TABLE | ikn.COUNT), "24interp_wave_mixed_kernel": ("wave", ikn.TABLE),
+            "25interp_mixed_count_kernel": ("valu", ikn.TABLE | ikn.COUNT), "19interp_mixed_kernel": ("valu", ikn.TABLE)}
+
+
+def _twins(flags):
+    return (flags & ~ikn.TABLE, (flags & ~ikn.TABLE) | ikn.S8)
 
 
 @pytest.fixture(scope="module")
@@ -140,50 +145,65 @@ def resources(tmp_path_factory):
 
 def test_no_scratch_and_the_kernels_that_are_there(resources):
     res, _ = resources
-    k5x = [n for n in res if any(k in n for k in TWINS)]
+    kernels = ikn.by_meaning(res)
+    k5x = [n for k, n in kernels.items() if k[3] & ikn.TABLE]
     # K5w x4 .. x64 with one or four waves per workgroup, K5 x2 .. x64, each uniform and with per-stream counts; K6x
-    assert len(k5x) == 2 * (10 + 6) and len(res) == len(k5x) + 1, sorted(res)
+    for path, flags in FAMILIES.values():
+        assert len([k for k in kernels if k[0] == path and k[3] == flags]) == (10 if path == "wave" else 6), (path, flags)
+    assert len(k5x) == 2 * (10 + 6) and len(kernels) == len(k5x) and len(res) == len(k5x) + 1, sorted(res)
     for n, (vg, sc, occ, lds) in sorted(res.items()):
         assert sc == 0, "%s uses %d bytes of scratch" % (n, sc)
         if n not in k5x:  # K6x: no LDS, full occupancy
             assert "20interp1_mixed_kernel" in n and lds == 0 and vg <= 64 and occ == 8, (n, vg, lds, occ)
 
 
-@pytest.mark.parametrize("family,L", [(f, L) for f in sorted(TWINS) for L in range(2 if "wave" in f else 1, 7)])
+@pytest.mark.parametrize("family,L", [(f, L) for f in sorted(FAMILIES) for L in range(2 if FAMILIES[f][0] == "wave" else 1, 7)])
 def test_kernels_compile_within_their_twins_resources(resources, family, L):
     """Every K5x kernel reports no more VGPRs and no more LDS than the larger of its two bank-wide twins, at no lower occupancy; the
     reported counts are printed.  (Each branch of a K5x kernel ends in an assembly comment of its own, so that the two bodies do not
     share a tail: with one shared, K5 x64 reported 74 VGPRs against its twins' 68 and 70.)"""
     res, base = resources
+    path, flags = FAMILIES[family]
+    base_kernels = ikn.by_meaning(base)
     missed, seen = [], 0
-    for n, (vg, sc, occ, lds) in sorted(res.items()):
-        if family not in n or "ILi%dE" % L not in n:
+    for (p, l, wpw, f), n in sorted(ikn.by_meaning(res).items(), key=str):
+        if (p, l, f) != (path, L, flags):
             continue
         seen += 1
-        assert n.endswith("PKi"), n  # (the table: the second kernel argument, which the twins do not have)
-        twins = [base[n[:-3].replace(family, t)] for t in TWINS[family]]
+        vg, sc, occ, lds = res[n]
+        assert n.endswith("PKi"), n  # (the table: the last kernel argument)
+        twins = [base[base_kernels[(path, L, wpw, t)]] for t in _twins(flags)]
         tv, tl = max(t[0] for t in twins), max(t[3] for t in twins)
         print(n, "VGPRs", vg, "twins", [t[0] for t in twins], "LDS", lds, "twins", tl, "occupancy", occ, [t[2] for t in twins])
         assert lds <= tl, "%s: %d bytes of LDS, its twins %d" % (n, lds, tl)
         assert occ >= min(t[2] for t in twins), "%s: occupancy %d, its twins %s" % (n, occ, [t[2] for t in twins])
         if vg > tv:
             missed.append("%s: %d VGPRs, the larger of its twins %d" % (n, vg, tv))
-    assert seen == (2 if "wave" in family else 1)  # (K5w: one and four waves per workgroup)
+    assert seen == (2 if path == "wave" else 1)  # (K5w: one and four waves per workgroup)
     assert not missed, missed
 
 
-def test_lives_in_a_translation_unit_of_its_own():
-    """no other kernel file defines or launches the mixed kernels, the library's Makefile builds the new file, InterpArgs did not
-    grow (the table is a second kernel argument), and the host has one call site per launch"""
+def test_lives_in_a_translation_unit_of_its_own(resources):
+    """no other kernel file instantiates a table variant or launches K6x -- by its text and, for interp_kernels.hip, which includes the
+    same templates, by its compile report --, the library's Makefile builds the file, InterpArgs did not grow (the table is a second
+    kernel argument), and the host has one call site of the bank's one launcher and one of the K6x launch"""
+    _, base = resources
+    assert len(ikn.by_meaning(base)) == len(base) == 74 and not [k for k in ikn.by_meaning(base) if k[3] & ikn.TABLE], sorted(base)
     for f in sorted(os.listdir(iq8.CSRC)):
         if f.endswith(".hip") and f != SRC:
-            assert "_mixed(" not in open(os.path.join(iq8.CSRC, f)).read().replace("launch_unpack_mixed(", ""), f
+            text = open(os.path.join(iq8.CSRC, f)).read()
+            assert not re.search(r"variant(_kernel)?<[^>;]*IV_TABLE", text) and "interp1_mixed" not in text, f
+            assert ('#include "interp_variant.h"' in text) == (f == "interp_kernels.hip"), f
     assert SRC in open(os.path.join(iq8.CSRC, "Makefile")).read()
     text = open(os.path.join(iq8.CSRC, SRC)).read()
-    assert "InterpArgs a, const int *fmt" in text and "readfirstlane(fmt[blockIdx.y])" in text
+    assert "launch_variant<IV_TABLE>" in text and "launch_variant<IV_TABLE | IV_COUNT>" in text
+    variant = open(os.path.join(iq8.CSRC, "interp_variant.h")).read()
+    assert variant.count("InterpArgs a, const int *fmt") == 2 and "readfirstlane(fmt[blockIdx.y])" in variant
     internal = open(os.path.join(iq8.CSRC, "sdrhip_internal.h")).read()
     args = internal[internal.index("struct InterpArgs {"):internal.index("};", internal.index("struct InterpArgs {"))]
     assert "fmt" not in args
+    assert len(re.findall(r"^hipError_t launch_interpolate\w*\(", internal, flags=re.M)) == 3  # the launcher, its table half, K6x
     hosts = {f: open(os.path.join(iq8.CSRC, f)).read() for f in sorted(os.listdir(iq8.CSRC)) if f.endswith(".cpp")}
-    for launch in ("launch_interpolate_wave_mixed(", "launch_interpolate_mixed(", "launch_interpolate1_mixed("):
+    for launch in ("launch_interpolate(", "launch_interpolate1_mixed("):
         assert sum(h.count(launch) for h in hosts.values()) == 1, launch
+    assert not any("launch_interpolate_table(" in h for h in hosts.values())  # (reached through the one launcher alone)
