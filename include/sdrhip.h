@@ -799,9 +799,29 @@ int sdrhip_rx_submit_datagrams_tagged(sdrhip_rx *rx, const uint8_t *dgrams, cons
  * a table of one entry per delivered frame that the host derives from its own counts; the host writes the tags from the same
  * counts, they never cross the link.  Everything the order needs is allocated before the batch consumes anything.  Link traffic
  * is the stream-order batch's: down ("d2h_bytes") exactly sum n_frames x B x 512 + sum n_released x 16 in one copy.
- * Not covered: uniform batches, the synchronous entries, a device-resident view of the array, other orders, the Tx pipe. */
+ * Paced order (SDRHIP_EGRESS_PACED).  Round robin keeps "no receiver sees a burst" only while every stream of a batch delivers
+ * the same number of datagrams: a stream with more than the others sends its whole surplus back to back at the array's end (four
+ * streams with 4, 1, 1, 1 frames of 136: 408 consecutive datagrams of stream 0).  The reference never bursts: every sdrdaemonrx
+ * process spaces its OWN datagrams evenly, so N processes side by side put a rate-proportional interleave on the wire.  The paced
+ * order is that interleave.  Stream s delivers D_s datagrams in wire order (D_s = F_s B, or F_s B_s with B_s = 128 + nb_fec[s]
+ * under sdrhip_rx_set_stream_fec with differing counts); datagram j of stream s has the departure key
+ *     k(s, j) = (2 j + 1) / (2 D_s),
+ * the midpoint of its share of the batch period, and the array lists all datagrams by ascending key, ties by ascending stream.
+ * Keys are compared exactly (64-bit cross products, no floating point); a batch with a D_s of 2^31 or more is refused with
+ * SDRHIP_EDEVICE like any batch the index types cannot hold, never truncated.  Guarantee: between two consecutive datagrams of
+ * stream s lie floor(D_t / D_s) or ceil(D_t / D_s) datagrams of every other stream t, never more and never fewer.  Equal counts
+ * give exactly the round-robin array, byte for byte.  A sender that wants the reference's timing sends entry i of n at
+ * (i + 1/2) / n of the batch period.  Everything above holds for it unchanged: it serves sdrhip_rx_submit_ragged,
+ * sdrhip_rx_submit_datagrams and sdrhip_rx_submit_datagrams_tagged, is collected by sdrhip_rx_collect_egress (blocks_per_frame and
+ * sdrhip_rx_egress_stream_blocks as for round robin), lends the same buffers, and batches of both orders may sit in the ring
+ * together, each collected in the order it was launched with.  How: the destinations of a stream are no constant-stride runs, so
+ * one kernel (KP) gathers by destination through a table of 4 bytes per datagram (16 bytes per stream in front) that the host
+ * makes, with the tags, in one merge over the streams; the table's upload is not counted in "h2d_bytes", like KE's and KR's
+ * tables, and "d2h_bytes" is the round-robin batch's.
+ * Not covered: uniform batches, the synchronous entries, a device-resident view of the array, the send itself, the Tx pipe. */
 #define SDRHIP_EGRESS_OFF 0          /* default: frames per stream, sdrhip_rx_collect_ragged / _datagrams */
 #define SDRHIP_EGRESS_ROUND_ROBIN 1  /* one departure-order array per batch, sdrhip_rx_collect_egress */
+#define SDRHIP_EGRESS_PACED 2        /* ... in ascending departure key: streams with unequal counts never burst */
 typedef struct {
     const uint8_t *dgrams;      /* n_dgrams x 512 bytes in departure order (lent) */
     const uint16_t *stream_of;  /* n_dgrams tags: the stream of datagram i (lent) */

@@ -21,6 +21,7 @@ LIB_PATH = os.environ.get("SDRHIP_LIB_PATH") or os.path.join(HERE, "libsdrhip.so
 MEM_HOST, MEM_DEVICE = 0, 1
 DGRAM_SKIP = 0xffff  # SDRHIP_DGRAM_SKIP
 EGRESS_OFF, EGRESS_ROUND_ROBIN = 0, 1
+EGRESS_PACED = 2
 FC_INF, FC_SUP, FC_CEN = 0, 1, 2
 HB_EO1, HB_DB = 0, 1
 IQ_S16, IQ_U8, IQ_S8 = 0, 1, 2

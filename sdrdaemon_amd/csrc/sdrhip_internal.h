@@ -619,6 +619,11 @@ hipError_t launch_rx_egress(const RxEgressRun *runs, uint64_t nruns, uint32_t wg
 // records as KE moves them
 hipError_t launch_rx_runs(const RxDepartRun *runs, uint64_t nruns, uint32_t wg_per_run, const uint8_t *frames, uint8_t *out,
                           const RxEgressRecords &rec, hipStream_t stream);
+// KP (rx_paced_kernels.hip), paced departure-order batches (SDRHIP_EGRESS_PACED), equal frames or not: datagram i of the array
+// comes from frames + 16 * table[i] (device table, n_dgrams entries, rx_paced_order.h) and goes to out + 512 * i, then the records
+// as KE moves them.  The host that made the table vouches for every entry lying inside `frames`
+hipError_t launch_rx_paced(const uint32_t *table, uint64_t n_dgrams, const uint8_t *frames, uint8_t *out, const RxEgressRecords &rec,
+                           hipStream_t stream);
 // KX (dgram_demux_kernels.hip), tagged datagram batches: datagram i of the arrival-order array src goes to dst + 512 * dest[i]
 // (device table, n_total entries; 0xffffffff: the datagram is moved nowhere).  src and dst 16-byte aligned, n_total below 2^30;
 // the host that made dest vouches for every entry lying inside dst

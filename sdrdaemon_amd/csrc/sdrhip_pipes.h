@@ -2,10 +2,12 @@
 // what it holds: dev_buffers.h, the ring of asynchronous batches among them) and what the units sdrhip_rx.cpp, sdrhip_rx_async.cpp,
 // sdrhip_rx_datagrams.cpp, sdrhip_rx_datagrams_async.cpp, sdrhip_tx.cpp and
 // sdrhip_tx_async.cpp share.  The Rx pipe's host decisions live in headers of their own: rx_frame_area.h (windows),
-// rx_stream_settings.h (per-stream settings, the counts of a ragged step and of a join), rx_depart_order.h (departure order)
+// rx_stream_settings.h (per-stream settings, the counts of a ragged step and of a join), rx_depart_order.h and rx_paced_order.h
+// (departure orders)
 #pragma once
 #include "rx_depart_order.h"
 #include "rx_frame_area.h"
+#include "rx_paced_order.h"
 #include "rx_stream_settings.h"
 #include "sdrhip_host.h"
 
@@ -84,7 +86,8 @@ struct sdrhip_rx {
         sdrhip::RxTabs d_tabs;
         std::vector<size_t> d_rel;            // released frames (records) per stream
         // ---- departure-order egress (sdrhip_rx_set_egress; a ragged or a datagram batch): the order the batch was launched with,
-        // KE's table (one run per delivered frame, then the record places), and the tags the collect lends beside `out`
+        // KE's table (one run per delivered frame, then the record places; SDRHIP_EGRESS_PACED: KP's, a dword per datagram), and the
+        // tags the collect lends beside `out`
         int egress = 0;
         sdrhip::PinnedBuf e_tab;
         std::vector<uint16_t> e_tags;
@@ -103,6 +106,7 @@ struct sdrhip_rx {
     sdrhip::DevBuf e_tab;
     sdrhip::RxEgressOrder e_order;
     sdrhip::RxDepartOrder e_depart; // (batches whose streams' frames differ in length: rx_depart_order.h)
+    sdrhip::RxPacedOrder e_paced;   // (SDRHIP_EGRESS_PACED, either kind of batch: rx_paced_order.h)
     bool consumed = false;        // set by sdrhip_rx_process once the decimator launch of the call went out (the filter state advanced)
     // ---- input format (sdrhip_rx_set_input_format): 8-bit input is widened by K0 into `wide`, the decimator's int16 input
     int in_fmt = sdrhip::IQF_S16;
@@ -306,7 +310,9 @@ int rx_launch_filling(sdrhip_rx *rx, sdrhip_rx::Batch &b);
 // a datagram batch: released = the collector's [S][4] results, records = its public records [S][kmax] -- the records as KD lays
 // them out.  The table, the tags and the device table are rx_egress_room's; the order's own vectors (one entry per frame) are the
 // handle's and keep their capacity.  Per-stream fecblk with differing counts (rx_fec_mixed): frame_bytes / blocks_per_frame are the
-// slot pitch, the runs are rx_depart_order.h's (at most frames + S (S - 1)) and KR moves them; b.e_blocks / b.e_dgrams say so
+// slot pitch, the runs are rx_depart_order.h's (at most frames + S (S - 1)) and KR moves them; b.e_blocks / b.e_dgrams say so.
+// SDRHIP_EGRESS_PACED (b.egress, either kind of batch): the table is rx_paced_order.h's -- the record places, then 4 bytes per
+// datagram -- and KP moves the datagrams
 int rx_egress_room(sdrhip_rx *rx, sdrhip_rx::Batch &b, size_t frames, size_t blocks_per_frame);
 hipError_t rx_egress_launch(sdrhip_rx *rx, sdrhip_rx::Batch &b, const size_t *n_frames, size_t frame_bytes, const int *released, size_t kmax,
                             const uint8_t *records);

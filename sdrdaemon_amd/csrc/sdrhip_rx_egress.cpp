@@ -7,6 +7,9 @@
 // lends the ring slot's pinned download buffer and its tags instead of copying frames out of it.  The two launch paths
 // (rx_submit_batch, rx_launch_ragged) call rx_egress_room ahead of everything that consumes input and rx_egress_launch where their
 // stream-order delivery would go; nothing else of them differs.
+// SDRHIP_EGRESS_PACED: the array in ascending departure key (2 j + 1) / (2 D_s) instead (rx_paced_order.h) -- what N senders that
+// each space their own datagrams evenly put on the wire together; streams with unequal counts never burst.  Its destinations are
+// no constant-stride runs, so KP (rx_paced_kernels.hip) gathers by destination through a table of one dword per datagram.
 #include "sdrhip_pipes.h"
 
 using namespace sdrhip;
@@ -25,7 +28,10 @@ size_t depart_runs_bound(size_t frames, size_t S)
     return frames + (live ? live * (live - 1) : 0);
 }
 
-// the record places of a datagram batch, in front of either table; returns the records of the batch
+// ... KP's, for a paced batch of either kind: a source per datagram
+size_t paced_table_bytes(size_t dgrams, size_t S) { return S * sizeof(RxEgressRecPlace) + dgrams * sizeof(uint32_t); }
+
+// the record places of a datagram batch, in front of every table; returns the records of the batch
 uint32_t record_places(RxEgressRecPlace *place, size_t S, const int *released, size_t kmax)
 {
     uint32_t pre = 0;
@@ -51,7 +57,10 @@ int sdrhip::rx_egress_room(sdrhip_rx *rx, sdrhip_rx::Batch &b, size_t frames, si
     // (per-stream fecblk with differing counts: KR's longer table; blocks_per_frame = the slot pitch bounds the tags)
     const size_t S = (size_t)rx->nstreams;
     const bool mixed = rx_fec_mixed(rx);
-    const size_t bytes = (mixed ? depart_table_bytes(depart_runs_bound(frames, S), S) : egress_table_bytes(frames, S)) + 16;
+    // (paced: the slot pitch bounds every frame's datagrams, so frames x blocks_per_frame bounds the table as it does the tags)
+    const size_t bytes = (b.egress == SDRHIP_EGRESS_PACED ? paced_table_bytes(frames * blocks_per_frame, S)
+                          : mixed                         ? depart_table_bytes(depart_runs_bound(frames, S), S)
+                                                          : egress_table_bytes(frames, S)) + 16;
     int rc;
     if ((rc = b.e_tab.reserve(bytes))) return rc; // (waits for the table upload of this slot's last use)
     if ((rc = reserve_settled(rx->ctx, rx->e_tab, bytes))) return rc;
@@ -73,6 +82,45 @@ hipError_t sdrhip::rx_egress_launch(sdrhip_rx *rx, sdrhip_rx::Batch &b, const si
 {
     sdrhip_ctx *c = rx->ctx;
     const size_t S = (size_t)rx->nstreams, B = frame_bytes / SDRHIP_UDPSIZE;
+    if (b.egress == SDRHIP_EGRESS_PACED) {
+        // ---- ascending departure key: one merge over the streams gives the tags and KP's table (frames of different lengths:
+        // frame_bytes = the area's slot pitch, as for KR)
+        RxPacedOrder &p = rx->e_paced;
+        std::vector<uint64_t> src0;
+        try {
+            src0.assign(S, 0);
+            if (!(b.e_blocks.empty() ? p.plan(n_frames, B, S) : p.plan(n_frames, b.e_blocks.data(), S))) return hipErrorInvalidValue;
+        } catch (const std::bad_alloc &) {
+            return hipErrorOutOfMemory;
+        }
+        for (size_t s = 0; s < S; ++s)
+            if (n_frames[s]) src0[s] = rx->view.offset(s, frame_bytes);
+        // (cannot differ: rx_egress_room was given the pipe's own count of these frames)
+        const size_t n = (size_t)p.dgrams(), bytes = paced_table_bytes(n, S);
+        if (bytes > b.e_tab.cap || n > b.e_tags.size()) return hipErrorInvalidValue;
+        RxEgressRecPlace *place = b.e_tab.as<RxEgressRecPlace>();
+        b.e_tags.resize(n); // (never grows)
+        try {
+            if (!p.fill(src0.data(), frame_bytes, b.e_tags.data(), reinterpret_cast<uint32_t *>(place + S))) return hipErrorInvalidValue;
+        } catch (const std::bad_alloc &) {
+            return hipErrorOutOfMemory;
+        }
+        b.e_dgrams = n;
+        const uint32_t pre = record_places(place, S, released, kmax);
+        if (!n && !pre) return hipSuccess;
+        if (kmax > 0xffffffffu / S) return hipErrorInvalidValue;
+        hipError_t e = hipMemcpyAsync(rx->e_tab.p, b.e_tab.p, bytes, hipMemcpyHostToDevice, c->stream); // (not counted: a table)
+        if (e != hipSuccess) return e;
+        b.e_tab.mark(c->stream);
+        RxEgressRecords rec;
+        rec.place = rx->e_tab.as<RxEgressRecPlace>();
+        rec.records = records;
+        rec.dst = (uint64_t)n * SDRHIP_UDPSIZE;
+        rec.kmax = (uint32_t)kmax;
+        rec.nslots = pre ? (uint32_t)(S * kmax) : 0;
+        KTimer kt(c, SDRHIP_K_CONVERT);
+        return launch_rx_paced(reinterpret_cast<const uint32_t *>(rec.place + S), n, rx->work.as<uint8_t>(), rx->a_frames.as<uint8_t>(), rec, c->stream);
+    }
     if (!b.e_blocks.empty()) { // (rx_egress_room: the streams' counts differ)
         // ---- frames of different lengths: the runs of rx_depart_order.h, moved by KR (frame_bytes = the area's slot pitch)
         RxDepartOrder &d = rx->e_depart;
@@ -151,7 +199,8 @@ extern "C" int sdrhip_rx_set_egress(sdrhip_rx *rx, int order)
 {
     if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
     sdrhip::CtxLock lock_(rx->ctx);
-    if (order != SDRHIP_EGRESS_OFF && order != SDRHIP_EGRESS_ROUND_ROBIN) return fail(SDRHIP_EINVAL, "rx_set_egress: unknown order %d", order);
+    if (order != SDRHIP_EGRESS_OFF && order != SDRHIP_EGRESS_ROUND_ROBIN && order != SDRHIP_EGRESS_PACED)
+        return fail(SDRHIP_EINVAL, "rx_set_egress: unknown order %d", order);
     if ((size_t)rx->nstreams > RX_EGRESS_MAX_STREAMS) return fail(SDRHIP_EINVAL, "rx_set_egress: a tag names at most 65535 streams");
     if (rx->ring.any([](const sdrhip_rx::Batch &b) { return b.state == 1; }))
         return fail(SDRHIP_EINVAL, "rx_set_egress: a batch is being filled: collect it first");

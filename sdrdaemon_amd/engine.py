@@ -1233,9 +1233,11 @@ class RxPipe(_Handle):
     # ---- departure-order egress (sdrhip_rx_set_egress / sdrhip_rx_collect_egress / sdrhip_rx_release_egress)
     def set_egress(self, order="round_robin"):
         """the order later ragged and datagram batches are delivered in: "round_robin" = one array per batch, datagram j of every
-        stream before datagram j + 1 of any (collect_egress); None or "off" = frames per stream (collect_ragged /
+        stream before datagram j + 1 of any (collect_egress); "paced" = one array in ascending departure key (2j + 1) / (2 D_s),
+        ties by stream -- what senders that each space their own datagrams evenly put on the wire together, so streams with
+        unequal counts never burst (equal counts: the round-robin array); None or "off" = frames per stream (collect_ragged /
         collect_datagrams), the default.  A batch keeps the order it was launched with."""
-        orders = {None: _lib.EGRESS_OFF, "off": _lib.EGRESS_OFF, "round_robin": _lib.EGRESS_ROUND_ROBIN}
+        orders = {None: _lib.EGRESS_OFF, "off": _lib.EGRESS_OFF, "round_robin": _lib.EGRESS_ROUND_ROBIN, "paced": _lib.EGRESS_PACED}
         check(self.ctx.lib.sdrhip_rx_set_egress(self.h, orders[order] if order in orders else int(order)))
 
     def collect_egress(self, wait=True, max_released=None, copy=True):
