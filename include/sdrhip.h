@@ -201,6 +201,44 @@ int sdrhip_interpolators_reset(sdrhip_interpolators *p);
  * Interpolators.cpp:363-606). */
 int sdrhip_interpolate(sdrhip_interpolators *p, int log2interp, const int16_t *iq_in, size_t n_in,
                        size_t in_stride, int16_t *iq_out, size_t out_stride, size_t *n_out, int mem);
+/* Interpolators bank, ragged: one Interpolators::interpolate<2^log2interp>_cen call per stream (Interpolators.h:38-43;
+ * Upsampler::process, Upsampler.cpp:52-84; Interpolators.cpp:363-606 for log2interp = 6, as sdrhip_interpolate has it) in which
+ * stream s consumes n_in[s] samples at iq_in + 2*s*in_stride and writes n_out[s] = n_in[s] << log2interp samples at
+ * iq_out + 2*s*out_stride.  n_in and n_out are host arrays of nstreams entries; in_stride >= the largest n_in[s], out_stride >=
+ * the largest n_out[s] (strides in samples; ignored for one stream).  log2interp 0..6 (0 copies n_in[s] samples per row).
+ * Per stream, the output and the bank's state afterwards are byte for byte those of a one-stream bank given the same chunks in
+ * the same order: any count is legal, 0, 1 and odd ones included, and a stream with n_in[s] == 0 keeps its six filter histories
+ * exactly.  A call whose counts are all 0 launches nothing.  The entry mixes freely with sdrhip_interpolate on one bank.
+ * One launch serves every stream (K5c): the kernels of sdrhip_interpolate (context options interp_path, interp_span) on a compact
+ * grid, one workgroup (or one wave of a workgroup) per (stream, segment) of a per-call table, sum_s max(1, ceil(n_in[s] / segment))
+ * entries, with one segment length for the launch, taken from the largest count as sdrhip_interpolate takes it from n_in:
+ * the launch's cost follows the samples, not nstreams x the largest count (sdrhip_interpolators_last_plan: compact = 1).
+ * Host memory: only n_in[s] samples of row s are read and only n_out[s] written; the samples go up in one packed copy of exactly
+ * 4 * sum_s n_in[s] bytes and the results come down in one packed copy of exactly 4 * sum_s n_out[s] bytes ("h2d_bytes" /
+ * "d2h_bytes"; log2interp = 1 alone rounds every stream's share of the download up to 16 bytes).
+ * Device memory: the alignment rules of sdrhip_interpolate (pointers 16-byte aligned, strides multiples of 4 samples for more
+ * than one stream).  No byte of row s past n_out[s] samples is written, and the kernels read no sample of stream s past n_in[s]
+ * (every load of either kernel is guarded by the stream's own end; the last row may be exactly n_in[nstreams - 1] long).
+ * Refused with SDRHIP_EINVAL and nothing consumed, enqueued or changed: a NULL handle, NULL n_in or n_out, a NULL buffer with any
+ * count non-zero, a stride below the largest count, a count of 2^31 samples or more, more than 2^31 - 1 table entries (the grid).
+ * Device pointers or strides that break the alignment rules: SDRHIP_EALIGN, likewise nothing consumed. */
+int sdrhip_interpolate_ragged(sdrhip_interpolators *p, int log2interp, const int16_t *iq_in, const size_t *n_in, size_t in_stride,
+                              int16_t *iq_out, size_t out_stride, size_t *n_out, int mem);
+/* What the bank's last launch was (diagnostics, as sdrhip_decimators_last_plan).  path: 0 = the last call launched nothing (none
+ * yet, an empty or a refused-by-the-device call), SDRHIP_INTERP_COPY = the x1 copy, SDRHIP_INTERP_VALU = K5 (workgroups of 256
+ * lanes, segments of whole macro-cycles), SDRHIP_INTERP_WAVE = K5w (wave-private pipelines, segments of 128-input blocks).
+ * seg_len = the segment length in inputs, wpw = waves per workgroup of K5w (1 or 4; 1 elsewhere), entries = the (stream, segment)
+ * pairs the launch served, compact = 1 for sdrhip_interpolate_ragged's grid (one entry per pair that exists), 0 for the
+ * rectangular grids of sdrhip_interpolate and the Tx pipe (entries = segments of the longest stream x nstreams; the x1 copy
+ * reports nstreams entries of n_in samples). */
+#define SDRHIP_INTERP_COPY 1
+#define SDRHIP_INTERP_VALU 2
+#define SDRHIP_INTERP_WAVE 3
+typedef struct sdrhip_interp_plan {
+    int path, wpw, compact, reserved;
+    size_t seg_len, entries;
+} sdrhip_interp_plan;
+int sdrhip_interpolators_last_plan(const sdrhip_interpolators *p, sdrhip_interp_plan *out);
 
 /* -------------------------------------------------------------------- CM256 -- */
 /* CM256::cm256_encoder_params / CM256::cm256_block as used at UDPSinkFEC.cpp:195-246 and

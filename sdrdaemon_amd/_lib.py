@@ -55,6 +55,7 @@ EXPORTS = [
     "sdrhip_rx_set_stream_bits", "sdrhip_rx_get_stream_bits", "sdrhip_decimate_ragged_bits",
     "sdrhip_rx_set_stream_format", "sdrhip_rx_get_stream_format",
     "sdrhip_tx_set_stream_format", "sdrhip_tx_get_stream_format",
+    "sdrhip_interpolate_ragged", "sdrhip_interpolators_last_plan",
 ]
 
 
@@ -75,6 +76,11 @@ class CM256Block(C.Structure):
 class DecimPlan(C.Structure):
     _fields_ = [("path", C.c_int), ("wps", C.c_int), ("npieces", C.c_int), ("nseg", C.c_int),
                 ("span", C.c_size_t), ("head", C.c_size_t), ("tail_start", C.c_size_t)]
+
+
+class InterpPlan(C.Structure):  # sdrhip_interp_plan
+    _fields_ = [("path", C.c_int), ("wpw", C.c_int), ("compact", C.c_int), ("reserved", C.c_int),
+                ("seg_len", C.c_size_t), ("entries", C.c_size_t)]
 
 
 class RxEgress(C.Structure):  # sdrhip_rx_egress
@@ -116,6 +122,8 @@ def load():
     lib.sdrhip_interpolators_destroy.restype = None
     lib.sdrhip_interpolators_reset.argtypes = [vp]
     lib.sdrhip_interpolate.argtypes = [vp, i, vp, sz, sz, vp, sz, C.POINTER(sz), i]
+    lib.sdrhip_interpolate_ragged.argtypes = [vp, i, vp, C.POINTER(sz), sz, vp, sz, C.POINTER(sz), i]
+    lib.sdrhip_interpolators_last_plan.argtypes = [vp, C.POINTER(InterpPlan)]
     lib.sdrhip_cm256_encode.argtypes = [vp, CM256Params, C.POINTER(CM256Block), vp]
     lib.sdrhip_cm256_decode.argtypes = [vp, CM256Params, C.POINTER(CM256Block)]
     lib.sdrhip_fec_encode_frames.argtypes = [vp, vp, sz, i, vp, i]

@@ -27,33 +27,19 @@
 
 namespace sdrhip {
 
+// the segments of a uniform call: interp_ragged_plan.h holds the rules (the ragged entry plans with the same ones)
 void plan_interpolate(int log2interp, size_t n_in, int nstreams, int *nsub_per_seg, int *nseg)
 {
-    const size_t ci = log2interp == 1 ? 1024 : MC;
-    size_t nsub = (n_in + ci - 1) / ci;
-    if (nsub == 0) nsub = 1;
-    size_t per = 16; // warm-up is 64 inputs: 16 macro-cycles per segment keep its cost below 1 %
-    while (per > 1 && ((nsub + per - 1) / per) * (size_t)nstreams < 2048) per >>= 1;
-    *nsub_per_seg = (int)per;
-    *nseg = (int)((nsub + per - 1) / per);
+    static_assert(INTERP_MC == MC, "interp_ragged_plan.h plans with the body's macro-cycle");
+    interp_plan_valu(log2interp, n_in, nstreams, nsub_per_seg, nseg);
 }
 
-// K5w: blocks of 128 inputs, segments of at most 2 x WPAIRS = 16 blocks (the wave parks its whole segment's input in registers at
-// its start), an even number of them (the input comes back a PAIR of blocks at a time; an odd rest runs the guarded path)
 void plan_interpolate_wave(int log2interp, size_t n_in, int nstreams, int n_cu, size_t seg_override, int *nsub_per_seg, int *nseg)
 {
+    static_assert(INTERP_WB == WB && INTERP_WPAIRS == WPAIRS, "interp_ragged_plan.h plans with K5w's block and pair count");
     (void)log2interp; (void)nstreams; (void)n_cu;
-    const size_t maxper = 2 * (size_t)WPAIRS;
-    size_t nsub = (n_in + WB - 1) / WB;
-    if (nsub == 0) nsub = 1;
-    size_t per = seg_override ? (seg_override + WB - 1) / WB : maxper;
-    if (per > maxper) per = maxper;
-    if (per > 1) per &= ~(size_t)1;
-    if (per < 1) per = 1;
-    *nsub_per_seg = (int)per;
-    *nseg = (int)((nsub + per - 1) / per);
+    interp_plan_wave(n_in, seg_override, nsub_per_seg, nseg);
 }
-
 
 // the bank-wide variants live here, the table variants behind launch_interpolate_table
 hipError_t launch_interpolate(const InterpPick &pick, int log2interp, const InterpArgs &a, const int *fmt, hipStream_t stream)

@@ -55,4 +55,21 @@ inline InterpPick interp_pick(int log2interp, bool interp_wave, bool gather, boo
     }
     return p;
 }
+
+// The sample-fed ragged entry (sdrhip_interpolate_ragged, K5c): per-stream counts from the host, a 1-D grid over a per-call table of
+// (stream, segment) entries (interp_ragged_plan.h) and kernels of their own (interp_ragged_kernels.hip).  A flag of its own, never
+// combined with the others and never an answer of interp_pick: int16 output, contiguous input, no format
+constexpr unsigned IV_MAPPED = 16;
+// x1: IR_COPY (a ragged copy kernel, not the strided copy); wpw is settled behind the plan, on the table's real number of entries
+inline InterpPick interp_pick_mapped(int log2interp, bool interp_wave)
+{
+    InterpPick p = {IR_REFUSED, 0, 1, nullptr};
+    if (log2interp < 0 || log2interp > 6) p.why = "log2interp out of range";
+    else if (log2interp == 0) p.route = IR_COPY;
+    else {
+        p.route = interp_pick_wave(interp_wave, log2interp) ? IR_WAVE : IR_VALU;
+        p.variant = IV_MAPPED;
+    }
+    return p;
+}
 } // namespace sdrhip

@@ -7,6 +7,7 @@
 
 #include "decim_plan.h"
 #include "interp_pick.h"
+#include "interp_ragged_plan.h"
 #include "rx_depart_order.h"
 #include "rx_egress_order.h"
 #include "rx_unpack_plan.h"
@@ -346,6 +347,12 @@ void plan_interpolate_wave(int log2interp, size_t n_in, int nstreams, int n_cu, 
 hipError_t launch_interpolate(const InterpPick &pick, int log2interp, const InterpArgs &a, const int *fmt, hipStream_t stream);
 // (behind it: the IV_TABLE variants, instantiated in interp_mixed_kernels.hip alone)
 hipError_t launch_interpolate_table(const InterpPick &pick, int log2interp, const InterpArgs &a, const int *fmt, hipStream_t stream);
+// K5c (interp_ragged_kernels.hip), the sample-fed ragged entry: a 1-D grid over the `nentries` entries of a per-call table (device;
+// interp_ragged_plan.h), pick = interp_pick_mapped's answer with wpw settled on nentries.  The rows carry every stream's offsets,
+// count and segments: a.in_stride / a.out_stride are 0, a.n_in / a.nseg / a.nstreams are not read; x1 (IR_COPY) moves rows[s].n_in
+// samples per row.  Int16 output
+hipError_t launch_interp_mapped(const InterpPick &pick, int log2interp, const InterpArgs &a, const InterpMapRow *rows, const InterpMapEntry *entries,
+                                unsigned nentries, hipStream_t stream);
 // K6x (interp_mixed_kernels.hip) is x1 with a format table, rows as for IV_TABLE: the copy (int16 rows) or the narrowing (8-bit
 // rows) of n samples per stream, or of count[s * count_stride] * count_unit <= n where count is given
 hipError_t launch_interpolate1_mixed(const int16_t *in, size_t in_stride, uint8_t *out, size_t out_stride, size_t n, int nstreams, const int *fmt,

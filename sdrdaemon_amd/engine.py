@@ -563,6 +563,31 @@ class Interpolators(_Handle):
                                               MEM_DEVICE if is_t else MEM_HOST))
         return out[0] if squeeze else out
 
+    def interpolate_ragged(self, log2interp, iq, counts, out=None):
+        """sdrhip_interpolate_ragged: stream s interpolates counts[s] samples of row s of iq (S, >= max(counts), 2) in one launch
+        on a compact grid.  Returns (out (S, max(counts) << log2interp, 2) -- row s valid up to n_out[s] --, n_out (numpy, S))."""
+        x, is_t, _ = _bank_view(iq, self.nstreams)
+        S, n = x.shape[0], x.shape[1]
+        cnt = _counts(counts, S, n)
+        mx = int(cnt.max()) if S else 0
+        n_res = (mx << log2interp) if 0 <= log2interp <= 6 else 0
+        if out is None:
+            out = _padded_rows(S, n_res, 4, torch.int16, x.device, zero=True) if is_t else np.zeros((S, n_res, 2), dtype=np.int16)
+        if is_t and S > 1 and (x.stride(0) // 2) % 4:
+            raise ValueError("device bank input: per-stream stride must be a multiple of 4 samples")
+        n_out = (C.c_size_t * S)()
+        check(self.ctx.lib.sdrhip_interpolate_ragged(self.h, log2interp, _ptr(x), (C.c_size_t * S)(*cnt.tolist()), _stride_samples(x), _ptr(out),
+                                                     _stride_samples(out) if S > 1 else n_res, n_out, MEM_DEVICE if is_t else MEM_HOST))
+        return out, np.array(n_out[:], dtype=np.int64)
+
+    def last_plan(self):
+        """what the last launch was (sdrhip_interpolators_last_plan): dict with path ('copy' / 'valu' / 'wave' / None), seg_len in
+        inputs, wpw, entries = the (stream, segment) pairs served, compact = whether the grid was the ragged entry's"""
+        p = _lib.InterpPlan()
+        check(self.ctx.lib.sdrhip_interpolators_last_plan(self.h, C.byref(p)))
+        return {"path": {0: None, 1: "copy", 2: "valu", 3: "wave"}[p.path], "seg_len": p.seg_len, "wpw": p.wpw, "entries": p.entries,
+                "compact": bool(p.compact)}
+
 
 class Upsampler:
     """Reference `Upsampler` (Upsampler.h:27-70)."""
