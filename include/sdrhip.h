@@ -833,7 +833,7 @@ int sdrhip_rx_submit_datagrams_tagged(sdrhip_rx *rx, const uint8_t *dgrams, cons
  * sdrhip_rx_set_async and sdrhip_rx_set_input_format are refused while a batch is lent.  A lent batch is not in flight: once every
  * batch has been collected, lent or not, the synchronous entries and sdrhip_fecbuf_* on the collector work as after the last
  * stream-order collect.  sdrhip_rx_release_egress with nothing lent returns SDRHIP_OK.
- * How: one kernel (KE) in the place of the stream-order delivery writes the batch's one download buffer in departure order, from
+ * How: one kernel (KR) in the place of the stream-order delivery writes the batch's one download buffer in departure order, from
  * a table of one entry per delivered frame that the host derives from its own counts; the host writes the tags from the same
  * counts, they never cross the link.  Everything the order needs is allocated before the batch consumes anything.  Link traffic
  * is the stream-order batch's: down ("d2h_bytes") exactly sum n_frames x B x 512 + sum n_released x 16 in one copy.
@@ -854,8 +854,8 @@ int sdrhip_rx_submit_datagrams_tagged(sdrhip_rx *rx, const uint8_t *dgrams, cons
  * sdrhip_rx_egress_stream_blocks as for round robin), lends the same buffers, and batches of both orders may sit in the ring
  * together, each collected in the order it was launched with.  How: the destinations of a stream are no constant-stride runs, so
  * one kernel (KP) gathers by destination through a table of 4 bytes per datagram (16 bytes per stream in front) that the host
- * makes, with the tags, in one merge over the streams; the table's upload is not counted in "h2d_bytes", like KE's and KR's
- * tables, and "d2h_bytes" is the round-robin batch's.
+ * makes, with the tags, in one merge over the streams; the table's upload is not counted in "h2d_bytes", like KR's
+ * table, and "d2h_bytes" is the round-robin batch's.
  * Not covered: uniform batches, the synchronous entries, a device-resident view of the array, the send itself, the Tx pipe. */
 #define SDRHIP_EGRESS_OFF 0          /* default: frames per stream, sdrhip_rx_collect_ragged / _datagrams */
 #define SDRHIP_EGRESS_ROUND_ROBIN 1  /* one departure-order array per batch, sdrhip_rx_collect_egress */

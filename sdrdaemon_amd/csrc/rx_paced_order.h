@@ -10,7 +10,7 @@
 //     pos(s, j) = j + sum_{t<s} min(D_t, ((2 j + 1) D_t / D_s + 1) / 2) + sum_{t>s} min(D_t, (((2 j + 1) D_t - 1) / D_s + 1) / 2)
 // (the datagrams i of t with (2 i + 1) D_s <= (2 j + 1) D_t for t < s, < for t > s).
 // What follows from it:
-//   * equal counts give exactly the round-robin array of rx_egress_order.h (all keys of a round coincide, the tie rule orders it);
+//   * equal counts give exactly the round-robin array of rx_depart_order.h (all keys of a round coincide, the tie rule orders it);
 //   * the no-burst guarantee: between two consecutive datagrams of stream s lie floor(D_t / D_s) or ceil(D_t / D_s) datagrams of
 //     every other stream t, never more and never fewer (the keys of s are 1 / D_s apart, those of t 1 / D_t).
 // The destinations of a stream are no constant-stride runs, so KP (rx_paced_kernels.hip) is a gather keyed by destination: table
@@ -25,12 +25,11 @@
 #include <cstdint>
 #include <vector>
 
+#include "rx_egress_limits.h"
+
 namespace sdrhip {
-constexpr uint64_t RX_PACED_DGRAM_BYTES = 512;
-constexpr uint32_t RX_PACED_WG_DGRAMS = 32;    // datagrams a KP workgroup writes (256 lanes x 4 chunks of 16 bytes)
-constexpr size_t RX_PACED_MAX_STREAMS = 65535;  // (a tag is a uint16_t)
 constexpr uint64_t RX_PACED_MAX_STREAM_DGRAMS = 0x7fffffffu; // D_s at most: the cross products fit 64 bits
-constexpr uint64_t RX_PACED_MAX_DGRAMS = (uint64_t)0x7fffffffu * RX_PACED_WG_DGRAMS; // KP's grid has 31 bits
+constexpr uint64_t RX_PACED_MAX_DGRAMS = (uint64_t)0x7fffffffu * RX_EGRESS_WG_DGRAMS; // KP's grid has 31 bits
 
 class RxPacedOrder {
 public:
@@ -45,7 +44,7 @@ public:
     uint64_t dgrams() const { return ok_ ? total_ : 0; }   // entries of the array
     uint64_t dgrams(size_t s) const { return D_[s]; }      // D_s
     size_t blocks(size_t s) const { return B_[s]; }        // B_s
-    uint64_t grid() const { return (dgrams() + RX_PACED_WG_DGRAMS - 1) / RX_PACED_WG_DGRAMS; } // KP's workgroups for the datagrams
+    uint64_t grid() const { return (dgrams() + RX_EGRESS_WG_DGRAMS - 1) / RX_EGRESS_WG_DGRAMS; } // KP's workgroups for the datagrams
 
     // the closed form, evaluated for one datagram (j < D_s)
     uint64_t pos(size_t s, uint64_t j) const
@@ -77,10 +76,10 @@ public:
             for (size_t s = 0; s < D_.size(); ++s) {
                 if (!D_[s]) continue;
                 const uint64_t F = D_[s] / B_[s];
-                if ((src0[s] & 15u) || (uint64_t)B_[s] * RX_PACED_DGRAM_BYTES > pitch_bytes) return false;
+                if ((src0[s] & 15u) || (uint64_t)B_[s] * RX_EGRESS_DGRAM_BYTES > pitch_bytes) return false;
                 const uint64_t most = (uint64_t)0xffffffffu * 16; // (bytes: the sum below cannot wrap)
                 if (src0[s] > most || (F - 1 && F - 1 > most / pitch_bytes)) return false;
-                const uint64_t last = src0[s] + (F - 1) * pitch_bytes + (uint64_t)(B_[s] - 1) * RX_PACED_DGRAM_BYTES;
+                const uint64_t last = src0[s] + (F - 1) * pitch_bytes + (uint64_t)(B_[s] - 1) * RX_EGRESS_DGRAM_BYTES;
                 if (last / 16 > 0xffffffffu) return false;
             }
         }
@@ -108,7 +107,7 @@ private:
     bool plan_(const size_t *F, const size_t *B, size_t B_all, size_t nstreams)
     {
         ok_ = false;
-        if (!nstreams || nstreams > RX_PACED_MAX_STREAMS) return false;
+        if (!nstreams || nstreams > RX_EGRESS_MAX_STREAMS) return false;
         const size_t S = nstreams;
         uint64_t total = 0;
         for (size_t s = 0; s < S; ++s) {
@@ -150,7 +149,7 @@ private:
         if (out)
             for (size_t s = 0; s < S; ++s)
                 if (D_[s]) cur_[s] = src0[s] / 16;
-        const uint64_t step = RX_PACED_DGRAM_BYTES / 16;
+        const uint64_t step = RX_EGRESS_DGRAM_BYTES / 16;
         heap_.clear();
         for (size_t g = 0; g < groups_.size(); ++g) { groups_[g].j = 0; heap_.push_back((uint32_t)g); }
         const Later later = {&groups_, &order_};

@@ -1,4 +1,4 @@
-// rx_records_body.h -- the records half of the departure-order delivery kernels KE and KR as device code shared by both: the
+// rx_records_body.h -- the records half of the departure-order delivery kernels KR and KP as device code shared by both: the
 // collector's public records of a datagram batch lie [stream][kmax], stream s released cnt of them; record k of stream s goes to
 // out + rec.dst + 16 (pre + k), {pre, cnt} per stream (one 16-byte entry) from the host's own counts.  One workgroup takes NT x PER
 // record slots; slot i = record i % kmax of stream i / kmax.  The record loads do not wait for the places.

@@ -9,7 +9,6 @@
 #include "interp_pick.h"
 #include "interp_ragged_plan.h"
 #include "rx_depart_order.h"
-#include "rx_egress_order.h"
 #include "rx_unpack_plan.h"
 
 // loads of data that is streamed through once (IQ input, frames): non-temporal.  tools/dma_probe.hip on MI355X: 7.1 TB/s with
@@ -605,13 +604,12 @@ hipError_t launch_rx_deliver(const RxDeliverSeg *segs, int nseg, uint32_t grid, 
 // counts [S][FB_COUNTS] against the shadow's expect [S][4] = {K, D, maxrow, maxrec}: +1 on *mismatch per
 // stream that differs
 hipError_t launch_fecbuf_shadow_check(const int *counts, const int *expect, int nstreams, unsigned *mismatch, hipStream_t stream);
-// KE (rx_egress_kernels.hip), departure-order batches (sdrhip_rx_set_egress): run k = one delivered frame, blocks_per_frame datagrams
-// from frames + src to out + dst + b * stride (rx_egress_order.h; wg_per_frame = its wg_per_frame()), then the records of a datagram
-// batch: record k < place[s].cnt of stream s from records + 16 (s kmax + k) to out + dst + 16 (place[s].pre + k); nslots = streams x
-// kmax (0: no records), records readable for all of them.  Bases and offsets 16-byte aligned; the host that made the tables vouches
-// for every piece lying inside `out`
+// the records of a datagram batch behind a departure-order array (sdrhip_rx_set_egress; KR and KP move them alike,
+// rx_records_body.h): record k < place[s].cnt of stream s from records + 16 (s kmax + k) to out + dst + 16 (place[s].pre + k);
+// nslots = streams x kmax (0: no records), records readable for all of them.  Bases and offsets 16-byte aligned; the host that made
+// the tables vouches for every piece lying inside `out`
 struct RxEgressRecPlace {
-    uint32_t pre, cnt, pad[2]; // records of the streams before this one, and its own (16 bytes: KE reads an entry with one dwordx4)
+    uint32_t pre, cnt, pad[2]; // records of the streams before this one, and its own (16 bytes: read with one dwordx4)
 };
 struct RxEgressRecords {
     const RxEgressRecPlace *place; // [streams] (device)
@@ -619,16 +617,14 @@ struct RxEgressRecords {
     uint64_t dst;
     uint32_t kmax, nslots;
 };
-hipError_t launch_rx_egress(const RxEgressRun *runs, uint64_t nruns, uint32_t wg_per_frame, uint32_t blocks_per_frame, const uint8_t *frames,
-                            uint8_t *out, const RxEgressRecords &rec, hipStream_t stream);
-// KR (rx_runs_kernels.hip), departure-order batches whose streams' frames differ in length (sdrhip_rx_set_stream_fec): run k =
-// `count` datagrams from frames + src to out + dst + i * stride (rx_depart_order.h; wg_per_run = its wg_per_run()), then the
-// records as KE moves them
+// KR (rx_runs_kernels.hip), round-robin departure-order batches, equal frames (one run per frame) or not (sdrhip_rx_set_stream_fec):
+// run k = `count` datagrams from frames + src to out + dst + i * stride (rx_depart_order.h; wg_per_run = its wg_per_run()), then
+// the records
 hipError_t launch_rx_runs(const RxDepartRun *runs, uint64_t nruns, uint32_t wg_per_run, const uint8_t *frames, uint8_t *out,
                           const RxEgressRecords &rec, hipStream_t stream);
 // KP (rx_paced_kernels.hip), paced departure-order batches (SDRHIP_EGRESS_PACED), equal frames or not: datagram i of the array
 // comes from frames + 16 * table[i] (device table, n_dgrams entries, rx_paced_order.h) and goes to out + 512 * i, then the records
-// as KE moves them.  The host that made the table vouches for every entry lying inside `frames`
+// as KR moves them.  The host that made the table vouches for every entry lying inside `frames`
 hipError_t launch_rx_paced(const uint32_t *table, uint64_t n_dgrams, const uint8_t *frames, uint8_t *out, const RxEgressRecords &rec,
                            hipStream_t stream);
 // KX (dgram_demux_kernels.hip), tagged datagram batches: datagram i of the arrival-order array src goes to dst + 512 * dest[i]

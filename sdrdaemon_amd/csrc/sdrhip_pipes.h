@@ -86,7 +86,7 @@ struct sdrhip_rx {
         sdrhip::RxTabs d_tabs;
         std::vector<size_t> d_rel;            // released frames (records) per stream
         // ---- departure-order egress (sdrhip_rx_set_egress; a ragged or a datagram batch): the order the batch was launched with,
-        // KE's table (one run per delivered frame, then the record places; SDRHIP_EGRESS_PACED: KP's, a dword per datagram), and the
+        // KR's table (the record places, then the runs; SDRHIP_EGRESS_PACED: KP's, a dword per datagram), and the
         // tags the collect lends beside `out`
         int egress = 0;
         sdrhip::PinnedBuf e_tab;
@@ -101,11 +101,10 @@ struct sdrhip_rx {
     // a_pk, the delivery's segments in a_tab, the gathered delivery in a_frames)
     sdrhip::DevBuf a_pk, a_din, a_tab, a_frames;
     int a_blocks = 1;             // blocks per launch
-    // ---- departure-order egress (sdrhip_rx_set_egress): the order later launches get, and KE's table on the device
+    // ---- departure-order egress (sdrhip_rx_set_egress): the order later launches get, and the order's table on the device
     int egress = 0;
     sdrhip::DevBuf e_tab;
-    sdrhip::RxEgressOrder e_order;
-    sdrhip::RxDepartOrder e_depart; // (batches whose streams' frames differ in length: rx_depart_order.h)
+    sdrhip::RxDepartOrder e_depart; // (SDRHIP_EGRESS_ROUND_ROBIN, equal frames or not: rx_depart_order.h)
     sdrhip::RxPacedOrder e_paced;   // (SDRHIP_EGRESS_PACED, either kind of batch: rx_paced_order.h)
     bool consumed = false;        // set by sdrhip_rx_process once the decimator launch of the call went out (the filter state advanced)
     // ---- input format (sdrhip_rx_set_input_format): 8-bit input is widened by K0 into `wide`, the decimator's int16 input
@@ -303,14 +302,14 @@ int rx_collector(sdrhip_rx *rx); // the datagram collector, created on first use
 // a uniform or ragged batch that is still being filled goes out as it is (wait_oldest's launch_filling; sdrhip_rx_async.cpp)
 int rx_launch_filling(sdrhip_rx *rx, sdrhip_rx::Batch &b);
 // ---- departure-order egress (sdrhip_rx_egress.cpp), for a launch path whose batch has an order (b.egress).  rx_egress_room:
-// everything KE's launch needs for a batch of at most `frames` delivered frames of blocks_per_frame datagrams -- the slot's pinned
+// everything the launch needs for a batch of at most `frames` delivered frames of blocks_per_frame datagrams -- the slot's pinned
 // table and tags, the device table -- ahead of anything that consumes input (a device table that grows synchronises once).
 // rx_egress_launch: the runs, the record places and the tags from the delivered counts n_frames[s] (each stream's frames contiguous
-// in `work` from view.offset(s, frame_bytes)), the table's upload, and KE into a_frames: the datagrams in departure order, then --
+// in `work` from view.offset(s, frame_bytes)), the table's upload, and KR into a_frames: the datagrams in departure order, then --
 // a datagram batch: released = the collector's [S][4] results, records = its public records [S][kmax] -- the records as KD lays
-// them out.  The table, the tags and the device table are rx_egress_room's; the order's own vectors (one entry per frame) are the
-// handle's and keep their capacity.  Per-stream fecblk with differing counts (rx_fec_mixed): frame_bytes / blocks_per_frame are the
-// slot pitch, the runs are rx_depart_order.h's (at most frames + S (S - 1)) and KR moves them; b.e_blocks / b.e_dgrams say so.
+// them out.  The table, the tags and the device table are rx_egress_room's; the order's own vectors (one entry per run) are the
+// handle's and keep their capacity.  The runs are rx_depart_order.h's: one per frame, or -- per-stream fecblk with differing counts
+// (rx_fec_mixed): frame_bytes / blocks_per_frame are the slot pitch -- at most frames + S (S - 1); b.e_blocks / b.e_dgrams say so.
 // SDRHIP_EGRESS_PACED (b.egress, either kind of batch): the table is rx_paced_order.h's -- the record places, then 4 bytes per
 // datagram -- and KP moves the datagrams
 int rx_egress_room(sdrhip_rx *rx, sdrhip_rx::Batch &b, size_t frames, size_t blocks_per_frame);

@@ -141,7 +141,7 @@ int rx_launch_ragged(sdrhip_rx *rx, sdrhip_rx::Batch &b)
     hipError_t e = hipSuccess;
     for (int s = 0; s < S; ++s)
         for (size_t f = 0; f < nf[(size_t)s]; ++f) list[nl++] = (int32_t)(rx->view.offset((size_t)s, fb) / fb + f);
-    // (departure order: KE in the gather's place writes the same buffer, sdrhip_rx_egress.cpp)
+    // (departure order: KR / KP in the gather's place writes the same buffer, sdrhip_rx_egress.cpp)
     if (e == hipSuccess && nl && b.egress) e = rx_egress_launch(rx, b, nf.data(), fb, nullptr, 0, nullptr);
     else if (e == hipSuccess && nl) e = hipMemcpyAsync(rx->a_tab.as<char>() + list_off, list, nl * 4, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && nl && !b.egress) {

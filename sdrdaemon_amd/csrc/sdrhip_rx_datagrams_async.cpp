@@ -64,7 +64,7 @@ static int rx_submit_batch(sdrhip_rx *rx, FecBufBatch &in, const uint32_t *tv_se
     if (b_total && (rc = b.out.reserve(b_total))) return rc;
     if ((rc = b.d_seg.reserve(seg_bytes))) return rc;
     if ((rc = b.done.ensure())) return rc;
-    b.egress = rx->egress; // (departure order: KE's table and the tags, like everything else, before the collector moves)
+    b.egress = rx->egress; // (departure order: the table and the tags, like everything else, before the collector moves)
     if (b.egress && (rc = rx_egress_room(rx, b, sum_done, fb / SDRHIP_UDPSIZE))) return rc;
     if (any && (rc = rx_ragged_room(rx, n, &b.d_tabs))) return rc;
 
@@ -117,7 +117,7 @@ static int rx_submit_batch(sdrhip_rx *rx, FecBufBatch &in, const uint32_t *tv_se
         g.bytes = k * DG_REC; g.dst = dst; g.from_records = 1;
         dst += g.bytes;
     }
-    if (b.egress) { // departure order: KE in KD's place writes the same buffer (sdrhip_rx_egress.cpp); KD's table stays unused
+    if (b.egress) { // departure order: KR / KP in KD's place writes the same buffer (sdrhip_rx_egress.cpp); KD's table stays unused
         nseg = 0;
         if (e == hipSuccess) e = rx_egress_launch(rx, b, nf.data(), fb, res.data(), kmax, reinterpret_cast<const uint8_t *>(pub));
     }

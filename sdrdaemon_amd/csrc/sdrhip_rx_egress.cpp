@@ -2,9 +2,10 @@
 // sdrhip_rx_collect_egress / sdrhip_rx_release_egress).  A hub that sends what the stream-order collects hand it puts a burst per
 // stream on the wire; the reference never does that to a receiver (UDPSinkFEC::transmitUDP sleeps txDelay between two datagrams of
 // a stream, UDPSinkFEC.cpp:259-282).  With the order on, a batch's delivery is ONE array: datagram j of every stream before
-// datagram j + 1 of any (rx_egress_order.h), with a stream tag per datagram -- the mirror of the tagged submit.  KE
-// (rx_egress_kernels.hip) writes the batch's one download buffer in that order in KD's / the frame gather's place; the collect
-// lends the ring slot's pinned download buffer and its tags instead of copying frames out of it.  The two launch paths
+// datagram j + 1 of any (rx_depart_order.h), with a stream tag per datagram -- the mirror of the tagged submit.  KR
+// (rx_runs_kernels.hip) writes the batch's one download buffer in that order in KD's / the frame gather's place, run by run: one
+// run per frame, or the pieces of the frames that another stream's end cuts (per-stream fecblk); the collect lends the ring
+// slot's pinned download buffer and its tags instead of copying frames out of it.  The two launch paths
 // (rx_submit_batch, rx_launch_ragged) call rx_egress_room ahead of everything that consumes input and rx_egress_launch where their
 // stream-order delivery would go; nothing else of them differs.
 // SDRHIP_EGRESS_PACED: the array in ascending departure key (2 j + 1) / (2 D_s) instead (rx_paced_order.h) -- what N senders that
@@ -15,13 +16,11 @@
 using namespace sdrhip;
 
 namespace {
-// KE's table: the record places (16 bytes each) in front, so that they are 16-byte aligned whatever the number of runs behind them
-size_t egress_table_bytes(size_t frames, size_t S) { return S * sizeof(RxEgressRecPlace) + frames * sizeof(RxEgressRun); }
-
-// ... KR's, for a batch whose streams' frames differ in length (per-stream fecblk)
-size_t depart_table_bytes(size_t runs, size_t S) { return S * sizeof(RxEgressRecPlace) + runs * sizeof(RxDepartRun); }
-// the runs of such a batch at most: a frame each, and every stream's end cuts at most one frame of each other stream -- of the
-// streams that deliver at all, min(S, frames) of them (quadratic in that number: 24 bytes a run, pinned per ring slot and on the device)
+// KR's table: the record places (16 bytes each) in front, so that they are 16-byte aligned whatever the number of runs behind them
+size_t runs_table_bytes(size_t runs, size_t S) { return S * sizeof(RxEgressRecPlace) + runs * sizeof(RxDepartRun); }
+// the runs of a batch whose streams' frames differ in length (per-stream fecblk) at most: a frame each, and every stream's end cuts
+// at most one frame of each other stream -- of the streams that deliver at all, min(S, frames) of them (quadratic in that number:
+// 24 bytes a run, pinned per ring slot and on the device).  Equal frames: a run each
 size_t depart_runs_bound(size_t frames, size_t S)
 {
     const size_t live = frames < S ? frames : S;
@@ -54,13 +53,13 @@ void release_lent(sdrhip_rx *rx)
 
 int sdrhip::rx_egress_room(sdrhip_rx *rx, sdrhip_rx::Batch &b, size_t frames, size_t blocks_per_frame)
 {
-    // (per-stream fecblk with differing counts: KR's longer table; blocks_per_frame = the slot pitch bounds the tags)
+    // (per-stream fecblk with differing counts: the table of cut frames; blocks_per_frame = the slot pitch bounds the tags)
     const size_t S = (size_t)rx->nstreams;
     const bool mixed = rx_fec_mixed(rx);
     // (paced: the slot pitch bounds every frame's datagrams, so frames x blocks_per_frame bounds the table as it does the tags)
     const size_t bytes = (b.egress == SDRHIP_EGRESS_PACED ? paced_table_bytes(frames * blocks_per_frame, S)
-                          : mixed                         ? depart_table_bytes(depart_runs_bound(frames, S), S)
-                                                          : egress_table_bytes(frames, S)) + 16;
+                          : mixed                         ? runs_table_bytes(depart_runs_bound(frames, S), S)
+                                                          : runs_table_bytes(frames, S)) + 16;
     int rc;
     if ((rc = b.e_tab.reserve(bytes))) return rc; // (waits for the table upload of this slot's last use)
     if ((rc = reserve_settled(rx->ctx, rx->e_tab, bytes))) return rc;
@@ -82,117 +81,52 @@ hipError_t sdrhip::rx_egress_launch(sdrhip_rx *rx, sdrhip_rx::Batch &b, const si
 {
     sdrhip_ctx *c = rx->ctx;
     const size_t S = (size_t)rx->nstreams, B = frame_bytes / SDRHIP_UDPSIZE;
-    if (b.egress == SDRHIP_EGRESS_PACED) {
-        // ---- ascending departure key: one merge over the streams gives the tags and KP's table (frames of different lengths:
-        // frame_bytes = the area's slot pitch, as for KR)
-        RxPacedOrder &p = rx->e_paced;
-        std::vector<uint64_t> src0;
-        try {
-            src0.assign(S, 0);
-            if (!(b.e_blocks.empty() ? p.plan(n_frames, B, S) : p.plan(n_frames, b.e_blocks.data(), S))) return hipErrorInvalidValue;
-        } catch (const std::bad_alloc &) {
-            return hipErrorOutOfMemory;
-        }
+    // the order: round robin (the runs of rx_depart_order.h, moved by KR) or paced (one merge over the streams gives the tags and
+    // KP's table).  each: rx_egress_room saw the streams' counts differ, and frame_bytes is the area's slot pitch
+    const bool paced = b.egress == SDRHIP_EGRESS_PACED;
+    const size_t *each = b.e_blocks.empty() ? nullptr : b.e_blocks.data();
+    RxDepartOrder &d = rx->e_depart;
+    RxPacedOrder &p = rx->e_paced;
+    RxEgressRecPlace *place = b.e_tab.as<RxEgressRecPlace>();
+    size_t n, bytes;
+    try {
+        std::vector<uint64_t> src0(S, 0);
         for (size_t s = 0; s < S; ++s)
             if (n_frames[s]) src0[s] = rx->view.offset(s, frame_bytes);
-        // (cannot differ: rx_egress_room was given the pipe's own count of these frames)
-        const size_t n = (size_t)p.dgrams(), bytes = paced_table_bytes(n, S);
+        // (a batch the order's index types cannot hold: refused, never truncated)
+        if (!(paced ? (each ? p.plan(n_frames, each, S) : p.plan(n_frames, B, S)) : (each ? d.plan(n_frames, each, S) : d.plan(n_frames, B, S))))
+            return hipErrorInvalidValue;
+        n = (size_t)(paced ? p.dgrams() : d.dgrams());
+        bytes = paced ? paced_table_bytes(n, S) : runs_table_bytes(d.nruns(), S);
+        // (cannot differ: rx_egress_room was given the pipe's own count of these frames, and reserved the bound on their runs)
         if (bytes > b.e_tab.cap || n > b.e_tags.size()) return hipErrorInvalidValue;
-        RxEgressRecPlace *place = b.e_tab.as<RxEgressRecPlace>();
         b.e_tags.resize(n); // (never grows)
-        try {
+        if (paced) {
             if (!p.fill(src0.data(), frame_bytes, b.e_tags.data(), reinterpret_cast<uint32_t *>(place + S))) return hipErrorInvalidValue;
-        } catch (const std::bad_alloc &) {
-            return hipErrorOutOfMemory;
+        } else {
+            if (!d.runs(src0.data(), frame_bytes, reinterpret_cast<RxDepartRun *>(place + S))) return hipErrorInvalidValue;
+            d.tags(b.e_tags.data());
         }
-        b.e_dgrams = n;
-        const uint32_t pre = record_places(place, S, released, kmax);
-        if (!n && !pre) return hipSuccess;
-        if (kmax > 0xffffffffu / S) return hipErrorInvalidValue;
-        hipError_t e = hipMemcpyAsync(rx->e_tab.p, b.e_tab.p, bytes, hipMemcpyHostToDevice, c->stream); // (not counted: a table)
-        if (e != hipSuccess) return e;
-        b.e_tab.mark(c->stream);
-        RxEgressRecords rec;
-        rec.place = rx->e_tab.as<RxEgressRecPlace>();
-        rec.records = records;
-        rec.dst = (uint64_t)n * SDRHIP_UDPSIZE;
-        rec.kmax = (uint32_t)kmax;
-        rec.nslots = pre ? (uint32_t)(S * kmax) : 0;
-        KTimer kt(c, SDRHIP_K_CONVERT);
-        return launch_rx_paced(reinterpret_cast<const uint32_t *>(rec.place + S), n, rx->work.as<uint8_t>(), rx->a_frames.as<uint8_t>(), rec, c->stream);
-    }
-    if (!b.e_blocks.empty()) { // (rx_egress_room: the streams' counts differ)
-        // ---- frames of different lengths: the runs of rx_depart_order.h, moved by KR (frame_bytes = the area's slot pitch)
-        RxDepartOrder &d = rx->e_depart;
-        std::vector<uint64_t> src0;
-        try {
-            src0.assign(S, 0);
-            if (!d.plan(n_frames, b.e_blocks.data(), S)) return hipErrorInvalidValue;
-        } catch (const std::bad_alloc &) {
-            return hipErrorOutOfMemory;
-        }
-        size_t frames = 0;
-        for (size_t s = 0; s < S; ++s) {
-            frames += n_frames[s];
-            if (n_frames[s]) src0[s] = rx->view.offset(s, frame_bytes);
-        }
-        // (cannot differ: rx_egress_room was given the pipe's own count of these frames, and the bound on their runs)
-        if (d.nruns() > depart_runs_bound(frames, S) || depart_table_bytes(d.nruns(), S) > b.e_tab.cap || d.dgrams() > b.e_tags.size()) return hipErrorInvalidValue;
-        RxEgressRecPlace *place = b.e_tab.as<RxEgressRecPlace>();
-        if (!d.runs(src0.data(), frame_bytes, reinterpret_cast<RxDepartRun *>(place + S))) return hipErrorInvalidValue;
-        b.e_tags.resize((size_t)d.dgrams()); // (never grows)
-        d.tags(b.e_tags.data());
-        b.e_dgrams = (size_t)d.dgrams();
-        const uint32_t pre = record_places(place, S, released, kmax);
-        if (!d.nruns() && !pre) return hipSuccess;
-        if (kmax > 0xffffffffu / S) return hipErrorInvalidValue;
-        hipError_t e = hipMemcpyAsync(rx->e_tab.p, b.e_tab.p, depart_table_bytes(d.nruns(), S), hipMemcpyHostToDevice, c->stream); // (not counted: a table)
-        if (e != hipSuccess) return e;
-        b.e_tab.mark(c->stream);
-        RxEgressRecords rec;
-        rec.place = rx->e_tab.as<RxEgressRecPlace>();
-        rec.records = records;
-        rec.dst = d.dgrams() * SDRHIP_UDPSIZE;
-        rec.kmax = (uint32_t)kmax;
-        rec.nslots = pre ? (uint32_t)(S * kmax) : 0;
-        KTimer kt(c, SDRHIP_K_CONVERT);
-        return launch_rx_runs(reinterpret_cast<const RxDepartRun *>(rec.place + S), d.nruns(), d.wg_per_run(), rx->work.as<uint8_t>(),
-                              rx->a_frames.as<uint8_t>(), rec, c->stream);
-    }
-    RxEgressOrder &o = rx->e_order;
-    std::vector<uint64_t> src0;
-    try {
-        src0.assign(S, 0);
-        if (!o.plan(n_frames, S, B)) return hipErrorInvalidValue; // (a batch KE's index types cannot hold: refused, never truncated)
     } catch (const std::bad_alloc &) {
         return hipErrorOutOfMemory;
     }
-    // (cannot differ: rx_egress_room was given the pipe's own count of these frames)
-    if (egress_table_bytes(o.frames(), S) > b.e_tab.cap || o.dgrams() > b.e_tags.size()) return hipErrorInvalidValue;
-    for (size_t s = 0; s < S; ++s)
-        if (n_frames[s]) src0[s] = rx->view.offset(s, frame_bytes);
-    RxEgressRecPlace *place = b.e_tab.as<RxEgressRecPlace>();
-    RxEgressRun *runs = reinterpret_cast<RxEgressRun *>(place + S);
-    if (!o.runs(src0.data(), runs)) return hipErrorInvalidValue;
-    b.e_tags.resize((size_t)o.dgrams()); // (never grows)
-    o.tags(b.e_tags.data());
+    b.e_dgrams = n;
     const uint32_t pre = record_places(place, S, released, kmax);
-    b.e_dgrams = (size_t)o.dgrams();
-    if (!o.frames() && !pre) return hipSuccess;
+    if (!n && !pre) return hipSuccess;
     if (kmax > 0xffffffffu / S) return hipErrorInvalidValue;
-    const size_t bytes = egress_table_bytes(o.frames(), S);
     hipError_t e = hipMemcpyAsync(rx->e_tab.p, b.e_tab.p, bytes, hipMemcpyHostToDevice, c->stream); // (not counted: a table)
     if (e != hipSuccess) return e;
     b.e_tab.mark(c->stream);
     RxEgressRecords rec;
     rec.place = rx->e_tab.as<RxEgressRecPlace>();
-    const RxEgressRun *runs_dev = reinterpret_cast<const RxEgressRun *>(rec.place + S);
     rec.records = records;
-    rec.dst = o.dgrams() * SDRHIP_UDPSIZE;
+    rec.dst = (uint64_t)n * SDRHIP_UDPSIZE;
     rec.kmax = (uint32_t)kmax;
     rec.nslots = pre ? (uint32_t)(S * kmax) : 0;
     KTimer kt(c, SDRHIP_K_CONVERT);
-    return launch_rx_egress(runs_dev, o.frames(), o.wg_per_frame(), (uint32_t)B, rx->work.as<uint8_t>(), rx->a_frames.as<uint8_t>(), rec, c->stream);
+    if (paced) return launch_rx_paced(reinterpret_cast<const uint32_t *>(rec.place + S), n, rx->work.as<uint8_t>(), rx->a_frames.as<uint8_t>(), rec, c->stream);
+    return launch_rx_runs(reinterpret_cast<const RxDepartRun *>(rec.place + S), d.nruns(), d.wg_per_run(), rx->work.as<uint8_t>(),
+                          rx->a_frames.as<uint8_t>(), rec, c->stream);
 }
 
 extern "C" int sdrhip_rx_set_egress(sdrhip_rx *rx, int order)

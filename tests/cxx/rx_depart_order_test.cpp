@@ -1,10 +1,9 @@
 // rx_depart_order_test.cpp -- sdrdaemon_amd/csrc/rx_depart_order.h (the departure order of a batch whose streams' frames differ in
 // length: per-stream fecblk) against a literal simulation of the rounds: round j holds datagram j of every stream that still has
 // one, streams in ascending order.  Positions, tags, totals, the run table (every run inside one frame, at most 256 datagrams,
-// at most sum F + S (S - 1) runs, 16-byte aligned) and, for equal lengths, rx_egress_order.h's positions.  Stand-alone
+// at most sum F + S (S - 1) runs, 16-byte aligned) and, for equal lengths, the closed form base_f + b A_f + r_f(s).  Stand-alone
 // (tests/test_rx_stream_fec_abi.py builds it with the address and undefined-behaviour sanitizers); no GPU, no library.
 #include "rx_depart_order.h"
-#include "rx_egress_order.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -108,16 +107,28 @@ void check_case(const std::vector<size_t> &F, const std::vector<size_t> &B)
         CHECK(!o.runs(bad.data(), pitch, runs.data()));
         CHECK(!o.runs(src0.data(), pitch + 8, runs.data()));
     }
-    // equal lengths: rx_egress_order.h's positions, and one run per frame
+    // equal lengths: the closed form base_f + b A_f + r_f(s) (A_f = #{t : F_t > f}, r_f(s) = #{t < s : F_t > f},
+    // base_f = B sum_{g<f} A_g), one run per frame, and the equal-frames plan gives the same table
     bool equal = true;
     for (size_t s = 1; s < S; ++s) equal = equal && B[s] == B[0];
     if (equal) {
-        RxEgressOrder e;
-        CHECK(e.plan(F.data(), S, B[0]));
-        CHECK(e.dgrams() == N && o.nruns() == e.frames());
+        CHECK(o.nruns() == frames);
         for (size_t s = 0; s < S; ++s)
-            for (size_t f = 0; f < F[s]; ++f)
-                for (size_t b = 0; b < B[0]; ++b) CHECK(o.pos(s, f * B[0] + b) == e.pos(s, f, b));
+            for (size_t f = 0; f < F[s]; ++f) {
+                uint64_t A = 0, rank = 0, base = 0;
+                for (size_t t = 0; t < S; ++t) {
+                    A += F[t] > f;
+                    rank += t < s && F[t] > f;
+                    base += (uint64_t)B[0] * (F[t] < f ? F[t] : f);
+                }
+                for (size_t b = 0; b < B[0]; ++b) CHECK(o.pos(s, f * B[0] + b) == base + b * A + rank);
+            }
+        RxDepartOrder e;
+        CHECK(e.plan(F.data(), B[0], S) && e.dgrams() == N && e.nruns() == o.nruns());
+        std::vector<RxDepartRun> same(e.nruns());
+        CHECK(e.runs(src0.data(), pitch, same.data()));
+        for (size_t k = 0; k < e.nruns(); ++k)
+            CHECK(same[k].src == runs[k].src && same[k].dst == runs[k].dst && same[k].stride == runs[k].stride && same[k].count == runs[k].count);
     }
 }
 

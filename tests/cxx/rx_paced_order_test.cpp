@@ -7,7 +7,7 @@
 #include <cstdlib>
 #include <vector>
 
-#include "rx_egress_order.h"
+#include "rx_depart_order.h"
 #include "rx_paced_order.h"
 
 using namespace sdrhip;
@@ -114,8 +114,8 @@ static void equal_counts_are_round_robin(size_t S, size_t F, size_t B)
 {
     const std::vector<size_t> Fs(S, F);
     RxPacedOrder p;
-    RxEgressOrder e;
-    CHECK(p.plan(Fs.data(), B, S) && e.plan(Fs.data(), S, B), "equal: plans");
+    RxDepartOrder e;
+    CHECK(p.plan(Fs.data(), B, S) && e.plan(Fs.data(), B, S), "equal: plans");
     CHECK(p.dgrams() == e.dgrams(), "equal: dgrams");
     std::vector<uint16_t> tp((size_t)p.dgrams()), te((size_t)e.dgrams());
     p.tags(tp.data());
@@ -124,7 +124,7 @@ static void equal_counts_are_round_robin(size_t S, size_t F, size_t B)
     for (size_t s = 0; s < S; ++s)
         for (size_t f = 0; f < F; ++f)
             for (size_t b = 0; b < B; ++b)
-                CHECK(p.pos(s, f * B + b) == e.pos(s, f, b), "equal: pos(%zu, %zu, %zu)", s, f, b);
+                CHECK(p.pos(s, f * B + b) == e.pos(s, f * B + b), "equal: pos(%zu, %zu, %zu)", s, f, b);
 }
 
 static void refusals()

@@ -195,12 +195,14 @@ RAGGED = {
     "equal_counts": dict(S=5, L=1, R=32, plan=[[2] * 5, [1] * 5]),
     "two_blocks": dict(S=5, L=1, R=8, plan=[[1, 0, 2, 1, 0], [1, 0, 1, 0, 1], [0, 2, 0, 1, 1], [2, 1, 1, 0, 0]], blocks=2),
     "u8_input": dict(S=5, L=1, R=127, plan=[[2, 0, 3, 1, 1], [1, 1, 0, 0, 2]], fmt="u8"),
+    "longest_run": dict(S=3, L=1, R=128, plan=[[2, 0, 1], [1, 1, 0]]),  # (B = 256: 8 workgroups per run)
 }
 
 
 @pytest.mark.parametrize("case", sorted(RAGGED))
 def test_ragged_batches(ctx, case):
-    """decimate2_cen with frame counts [2, 0, 3, 1, 1]; S = 1 (the identity order); equal counts; two blocks per batch; 8-bit input"""
+    """decimate2_cen with frame counts [2, 0, 3, 1, 1]; S = 1 (the identity order); equal counts; two blocks per batch; 8-bit input; nb_fec = 128
+    (frames of 256 datagrams, the run kernel's longest run)"""
     import sdrdaemon_amd as sd
 
     c = RAGGED[case]

@@ -1,7 +1,7 @@
 """CPU-side checks of the departure-order egress (sdrhip_rx_set_egress / sdrhip_rx_collect_egress / sdrhip_rx_release_egress):
-declared in include/sdrhip.h with the signatures the issue gives, exported, bound in Python, refused loudly without a GPU; KE
-(rx_egress_kernels.hip) compiles for gfx950 to one kernel without scratch whose global traffic is 16 bytes per lane and
-instruction; the new kernel and its one launch live in the new files alone."""
+declared in include/sdrhip.h with the signatures the issue gives, exported, bound in Python, refused loudly without a GPU; the
+kernel that serves round robin (KR, rx_runs_kernels.hip) compiles for gfx950 to one kernel without scratch whose global traffic is
+16 bytes per lane and instruction; KE is gone, and each remaining delivery kernel has its one launch in sdrhip_rx_egress.cpp."""
 import ctypes as C
 import glob
 import inspect
@@ -72,31 +72,23 @@ def test_null_handle_and_no_gpu(built):
 
 
 def test_ke_compiles_to_one_lean_kernel(tmp_path):
-    res = _compile(tmp_path, "rx_egress_kernels.hip")
-    assert len(res) == 1 and "rx_egress_kernel" in list(res)[0], sorted(res)
-    (_, scratch, occ), = res.values()
-    assert scratch == 0 and occ == 8, res
-    r = subprocess.run([HIPCC, "-std=c++17", "-O3", "--offload-arch=gfx950", "--cuda-device-only", "-S", os.path.join(CSRC, "rx_egress_kernels.hip"),
-                        "-o", str(tmp_path / "k.s")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    code = [ln.split("//")[0].split(";")[0].strip() for ln in open(str(tmp_path / "k.s"))]
-    ops = [ln.split()[0] for ln in code if ln and not ln.startswith(".") and not ln.endswith(":")]
-    assert ops.count("global_load_dwordx4") >= 8 and ops.count("global_store_dwordx4") >= 8  # (four per lane: frames, records)
-    assert {o for o in ops if o.startswith("global_store")} == {"global_store_dwordx4"}
-    assert {o for o in ops if o.startswith("global_load")} == {"global_load_dwordx4"}  # (a frame's run comes through the scalar cache)
-    assert not [o for o in ops if o.startswith(("flat_", "scratch_", "ds_", "buffer_", "s_barrier"))]
-    loads = [ln for ln in code if ln.startswith("global_load_dwordx4")]
-    assert len([ln for ln in loads if " nt" in ln]) >= 8, loads  # (every frame and record load; the record places are a table)
+    """round-robin batches of equal frames are KR's now: one kernel (rx_runs_kernel), no scratch, occupancy 8, dwordx4 global
+    traffic alone, at least 8 nt loads, no flat / scratch / LDS / buffer / barrier instruction -- the list KE was held against"""
+    from test_rx_stream_fec_abi import KR, check_kr_is_one_lean_kernel
+
+    assert KR == "rx_runs_kernels.hip"
+    check_kr_is_one_lean_kernel(tmp_path)
 
 
 def test_the_kernel_and_its_launch_live_in_the_new_files():
-    for path in glob.glob(os.path.join(CSRC, "*.hip")):
-        if os.path.basename(path) != "rx_egress_kernels.hip":
-            assert "rx_egress" not in open(path).read(), path
+    for path in glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.cpp")):
+        text = open(path).read()
+        assert "rx_egress_kernel" not in text and "launch_rx_egress" not in text, path
     mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert "rx_egress_kernels.hip" in mk and "sdrhip_rx_egress.cpp" in mk
-    calls = {os.path.basename(p): open(p).read().count("launch_rx_egress(") for p in glob.glob(os.path.join(CSRC, "*.cpp"))}
-    assert {k: v for k, v in calls.items() if v} == {"sdrhip_rx_egress.cpp": 1}
+    assert "rx_egress_kernels.hip" not in mk and "sdrhip_rx_egress.cpp" in mk
+    for launch in ("launch_rx_runs(", "launch_rx_paced("):
+        calls = {os.path.basename(p): open(p).read().count(launch) for p in glob.glob(os.path.join(CSRC, "*.cpp"))}
+        assert {k: v for k, v in calls.items() if v} == {"sdrhip_rx_egress.cpp": 1}, launch
     # each launch path reaches it through one branch
     for name in ("sdrhip_rx_datagrams_async.cpp", "sdrhip_rx_async.cpp"):
         text = open(os.path.join(CSRC, name)).read()

@@ -1,6 +1,7 @@
-"""The departure order of an egress batch (sdrdaemon_amd/csrc/rx_egress_order.h) on a CPU: tests/cxx/rx_egress_order_test.cpp checks
-the closed form, the tags and KE's run table against a literal simulation of the rounds, as a stand-alone program built with the
-address and undefined-behaviour sanitizers.  No GPU, no library."""
+"""The departure order of an egress batch of equal frames (the equal-frames form of sdrdaemon_amd/csrc/rx_depart_order.h) on a CPU:
+tests/cxx/rx_egress_order_test.cpp checks the closed form, the tags and KR's run table -- one run per delivered frame -- against a
+literal simulation of the rounds, as a stand-alone program built with the address and undefined-behaviour sanitizers.  No GPU, no
+library."""
 import os
 import subprocess
 
@@ -10,12 +11,15 @@ SRC = os.path.join(ROOT, "tests", "cxx", "rx_egress_order_test.cpp")
 
 
 def test_header_stands_alone():
-    """rx_egress_order.h is C++11 and pulls in neither HIP nor a library header: three standard headers and nothing else."""
-    with open(os.path.join(CSRC, "rx_egress_order.h")) as f:
+    """rx_depart_order.h is C++11 and pulls in neither HIP nor a library header: standard headers, and the shared constants of
+    rx_egress_limits.h, which includes two standard headers and nothing else."""
+    with open(os.path.join(CSRC, "rx_depart_order.h")) as f:
         incs = [ln.split()[1] for ln in f if ln.startswith("#include")]
-    assert sorted(incs) == ["<cstddef>", "<cstdint>", "<vector>"]
+    assert sorted(incs) == ['"rx_egress_limits.h"', "<algorithm>", "<cstddef>", "<cstdint>", "<vector>"]
+    with open(os.path.join(CSRC, "rx_egress_limits.h")) as f:
+        assert sorted(ln.split()[1] for ln in f if ln.startswith("#include")) == ["<cstddef>", "<cstdint>"]
     with open(SRC) as f:
-        assert [ln.split()[1] for ln in f if ln.startswith('#include "')] == ['"rx_egress_order.h"']
+        assert [ln.split()[1] for ln in f if ln.startswith('#include "')] == ['"rx_depart_order.h"']
 
 
 def test_order_matches_a_simulation_of_the_rounds(tmp_path):

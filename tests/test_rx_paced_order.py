@@ -16,12 +16,12 @@ def test_header_stands_alone():
     with open(os.path.join(CSRC, "rx_paced_order.h")) as f:
         text = f.read()
     incs = [ln.split()[1] for ln in text.splitlines() if ln.startswith("#include")]
-    assert sorted(incs) == ["<algorithm>", "<cstddef>", "<cstdint>", "<vector>"]
+    assert sorted(incs) == ['"rx_egress_limits.h"', "<algorithm>", "<cstddef>", "<cstdint>", "<vector>"]  # (constants alone)
     code = "\n".join(ln.split("//")[0] for ln in text.splitlines())
     assert "double" not in code and "float" not in code
     assert "floor(D_t / D_s) or ceil(D_t / D_s)" in text and "round-robin array" in text
     with open(SRC) as f:
-        assert [ln.split()[1] for ln in f if ln.startswith('#include "')] == ['"rx_egress_order.h"', '"rx_paced_order.h"']
+        assert [ln.split()[1] for ln in f if ln.startswith('#include "')] == ['"rx_depart_order.h"', '"rx_paced_order.h"']
 
 
 def test_order_matches_a_literal_sort(tmp_path):

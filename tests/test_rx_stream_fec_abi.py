@@ -128,12 +128,15 @@ def test_rounds_is_the_gpu_suites_definition():
 
 
 def test_order_header_stands_alone():
-    """rx_depart_order.h is C++11 and pulls in neither HIP nor a library header"""
+    """rx_depart_order.h is C++11 and pulls in neither HIP nor a library header: standard headers, and the constants it shares with
+    rx_paced_order.h (rx_egress_limits.h, which includes two standard headers and nothing else)"""
     with open(os.path.join(CSRC, "rx_depart_order.h")) as f:
         incs = [ln.split()[1] for ln in f if ln.startswith("#include")]
-    assert sorted(incs) == ["<algorithm>", "<cstddef>", "<cstdint>", "<vector>"]
+    assert sorted(incs) == ['"rx_egress_limits.h"', "<algorithm>", "<cstddef>", "<cstdint>", "<vector>"]
+    with open(os.path.join(CSRC, "rx_egress_limits.h")) as f:
+        assert sorted(ln.split()[1] for ln in f if ln.startswith("#include")) == ["<cstddef>", "<cstdint>"]
     with open(CXX) as f:
-        assert [ln.split()[1] for ln in f if ln.startswith('#include "')] == ['"rx_depart_order.h"', '"rx_egress_order.h"']
+        assert [ln.split()[1] for ln in f if ln.startswith('#include "')] == ['"rx_depart_order.h"']
 
 
 @pytest.fixture(scope="module")
@@ -168,7 +171,7 @@ def test_order_equals_rounds_over_labelled_datagrams(replay):
 
 def test_order_matches_a_simulation_of_the_rounds(replay):
     """positions, tags, totals, run count <= sum F + S (S - 1), every run inside one frame, 16-byte alignment; equal counts
-    reproduce RxEgressOrder; B = [128, 129, 160, 255, 256] over PLAN; F = 0 first / middle / last; one stream; cuts at a frame's
+    reproduce the closed form base_f + b A_f + r_f(s) and the equal-frames plan; B = [128, 129, 160, 255, 256] over PLAN; F = 0 first / middle / last; one stream; cuts at a frame's
     first and last datagram and at offsets 1, 31, 32, 33"""
     src = open(CXX).read()
     plan = re.search(r"PLAN = (\[\[.*?\]\])", open(os.path.join(ROOT, "tests", "test_gpu_rx_egress.py")).read()).group(1)
@@ -178,7 +181,8 @@ def test_order_matches_a_simulation_of_the_rounds(replay):
 
 
 # ------------------------------------------------------------------------------------------------ KR
-def test_kr_compiles_to_one_lean_kernel(tmp_path):
+def check_kr_is_one_lean_kernel(tmp_path):
+    """(tests/test_rx_egress_abi.py holds the kernel that serves round robin against the same list)"""
     res = _compile(tmp_path, KR)
     assert len(res) == 1 and "rx_runs_kernel" in list(res)[0], sorted(res)
     (_, scratch, occ), = res.values()
@@ -196,6 +200,10 @@ def test_kr_compiles_to_one_lean_kernel(tmp_path):
     assert not [o for o in ops if o.startswith(("flat_", "scratch_", "ds_", "buffer_", "s_barrier"))]
     loads = [ln for ln in code if ln.startswith("global_load_dwordx4")]
     assert len([ln for ln in loads if " nt" in ln]) >= 8, loads  # (every frame and record load; the record places are a table)
+
+
+def test_kr_compiles_to_one_lean_kernel(tmp_path):
+    check_kr_is_one_lean_kernel(tmp_path)
 
 
 def test_the_kernel_and_its_launch_live_in_the_new_files():

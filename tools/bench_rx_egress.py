@@ -5,7 +5,7 @@ completes one frame per stream (64 x 160 datagrams delivered).  Variants, altern
   off          order off: sdrhip_rx_collect_datagrams into the caller's rows (one memcpy per stream)
   off_parent   the same calls through a library built from the parent commit (--parent-lib): the yardstick
   on           SDRHIP_EGRESS_ROUND_ROBIN: sdrhip_rx_collect_egress lends the array, the next collect releases it
-1. batch period of each variant; 2. KE against KD per batch (kernel timers, class K_CONVERT: nothing else of these batches runs in
+1. batch period of each variant; 2. KR against KD per batch (kernel timers, class K_CONVERT: nothing else of these batches runs in
 it); 3. host time of the collect call on a batch that has finished: per-stream memcpy against lent.
 
     python tools/bench_rx_egress.py [--rounds N] [--batches B] [--parent-lib libsdrhip.so] [--out profiles/rx_egress_ab.txt]"""
@@ -138,7 +138,7 @@ def main():
             times[k].append((time.perf_counter() - t0) / args.batches)
             assert [int(x) for x in nr] == [F] * S and [int(x) for x in nf] == [1] * S, (k, list(nr), list(nf))
     assert eg.blocks_per_frame == B
-    # 2. the delivery kernel on its own: KD (off) against KE (on)
+    # 2. the delivery kernel on its own: KD (off) against KR (on)
     kern = {}
     for v in ("off", "on"):
         ctx.synchronize()
@@ -178,7 +178,7 @@ def main():
     print(line)
     if args.out:
         with open(args.out, "w") as fh:
-            fh.write("Departure-order egress (KE, sdrhip_rx_collect_egress) against the stream-order collect (KD, sdrhip_rx_collect_datagrams):\n"
+            fh.write("Departure-order egress (KR, sdrhip_rx_collect_egress) against the stream-order collect (KD, sdrhip_rx_collect_datagrams):\n"
                      "tools/bench_rx_egress.py, alternating rounds, medians on the host clock.\n")
             fh.write("box: %s, %s, torch %s\n" % (torch.cuda.get_device_name(0), platform.platform(), torch.__version__))
             fh.write("date: %s\n" % datetime.datetime.now().strftime("%Y-%m-%d %H:%M"))
@@ -193,7 +193,7 @@ def main():
             if parent:
                 fh.write("   off / off_parent = %.4f   on / off_parent = %.4f" % (res["off_over_off_parent"], res["on_over_off_parent"]))
             fh.write("\n2. delivery kernel per batch (kernel timers, K_CONVERT), %d bytes in and out\n" % down)
-            for v, name in (("off", "KD"), ("on", "KE")):
+            for v, name in (("off", "KD"), ("on", "KR")):
                 fh.write("   %s  %.2f us per launch, %.2f launches per batch, %.0f GB/s read + written\n"
                          % (name, kern[v]["us_per_launch"], kern[v]["launches_per_batch"], res["delivery_GBps"][v]))
             fh.write("3. host time of the collect call on a finished batch, us (median / min of %d)\n" % len(collect_s["off"]))

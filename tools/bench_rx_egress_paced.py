@@ -1,4 +1,4 @@
-"""The paced departure order (SDRHIP_EGRESS_PACED, KP) against round robin (KE), every bank driven through the C ABI alone so that a
+"""The paced departure order (SDRHIP_EGRESS_PACED, KP) against round robin (KR), every bank driven through the C ABI alone so that a
 library built from the parent commit (--parent-lib) runs the same calls.  Variants, alternating rounds, medians on the host clock:
   rr_parent   SDRHIP_EGRESS_ROUND_ROBIN through the parent commit's library: the yardstick
   rr          SDRHIP_EGRESS_ROUND_ROBIN through this library
@@ -10,7 +10,7 @@ Shapes:
   unequal  ragged sample batches, 64 streams, decimate2_cen, nb_fec 32, depth 4, packed sdrhip_host_alloc input in place: stream 0
            completes four frames per batch, every other stream one
 Per shape: 1. batch period; 2. the delivery kernel (kernel timers, class K_CONVERT, per batch: nothing else of a datagram batch
-runs in it; a ragged batch's input unpack does, the same launch in all three columns), one figure per round, so that the difference between KP and KE stands next to the spread of KE's own rounds; 3. host time of a submit
+runs in it; a ragged batch's input unpack does, the same launch in all three columns), one figure per round, so that the difference between KP and KR stands next to the spread of KR's own rounds; 3. host time of a submit
 call that found a free slot (it builds the order's table and tags); 4. from the tags alone: the longest run of one stream's
 datagrams, and the most datagrams of one stream among any 64 consecutive entries (one per stream is the even share), under both
 orders.
@@ -267,7 +267,7 @@ def main():
     print(line)
     if args.out:
         with open(args.out, "w") as fh:
-            fh.write("Paced departure order (KP, SDRHIP_EGRESS_PACED) against round robin (KE), and against round robin through the parent\n"
+            fh.write("Paced departure order (KP, SDRHIP_EGRESS_PACED) against round robin (KR), and against round robin through the parent\n"
                      "commit's library: tools/bench_rx_egress_paced.py, alternating rounds, medians on the host clock.\n")
             fh.write("box: %s, %s, torch %s\n" % (torch.cuda.get_device_name(0), platform.platform(), torch.__version__))
             fh.write("date: %s\n" % datetime.datetime.now().strftime("%Y-%m-%d %H:%M"))

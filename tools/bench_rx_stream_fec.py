@@ -5,7 +5,7 @@ submit_datagrams_tagged + collect_egress (departure order, lent buffers), three 
       departure-order arrays per batch)
   A2  the same again, a handle set of its own: the A/A pair, whose spread is the noise floor
   B   one bank of 64 streams with the array (one launch chain, one array; KR delivers)
-  C   one bank of 64 streams at a uniform fecblk 32 (KE delivers; more recovery blocks than B computes and sends)
+  C   one bank of 64 streams at a uniform fecblk 32 (KR delivers, one run per frame; more recovery blocks than B computes and sends)
 Every stream receives --frames whole frames per batch (incoming fecblk 4, nothing lost, decimate1), so every batch releases and
 delivers that many frames per stream; the same arrival-order array is submitted again with its frame indices moved on.
 The variants run interleaved in rounds of at least --window seconds of back-to-back batches (submit, collect, release, move the
