@@ -165,7 +165,11 @@ int sdrhip_decimators_last_plan(const sdrhip_decimators *d, sdrhip_decim_plan *o
  * resizes `out` to) at iq_out + 2*s*out_stride (strides in samples; ignored for one
  * stream).  *sampleSize (effective bits, 8..16) is updated as the reference's by-reference
  * argument.  As in the reference, floor(n_in / N) * N samples are consumed and the
- * remainder never enters the filter history. */
+ * remainder never enters the filter history.  No byte of row s past *n_out samples is
+ * written -- not the gap up to out_stride, nothing in front of the first or behind the
+ * last row --, the input is only read, and neither the result nor the state the call
+ * leaves depends on memory behind n_in samples of a row (the dropped remainder
+ * included), in host and in device memory (tests/test_gpu_bank_bounds.py). */
 int sdrhip_decimate(sdrhip_decimators *d, int log2decim, int fcpos, unsigned *sampleSize, const int16_t *iq_in,
                     size_t n_in, size_t in_stride, int16_t *iq_out, size_t out_stride, size_t *n_out, int mem);
 /* Decimators bank, ragged: stream s consumes n_in[s] samples (remainder below 2^log2decim dropped per stream, as
@@ -198,7 +202,11 @@ int sdrhip_interpolators_reset(sdrhip_interpolators *p);
  * (Interpolators.h:38-43; Upsampler::process, Upsampler.cpp:52-84; log2interp 0 copies).
  * *n_out = n_in << log2interp.  log2interp = 6 reproduces the reference's
  * interpolate64_cen as it is (32 interpolated + 32 zero samples per input,
- * Interpolators.cpp:363-606). */
+ * Interpolators.cpp:363-606).  Stream s reads n_in samples at iq_in + 2*s*in_stride and
+ * writes *n_out at iq_out + 2*s*out_stride (strides in samples; ignored for one stream).
+ * No byte of row s past *n_out samples is written, the input is only read, and neither
+ * the result nor the state the call leaves depends on memory behind n_in samples of a
+ * row, in host and in device memory (tests/test_gpu_bank_bounds.py). */
 int sdrhip_interpolate(sdrhip_interpolators *p, int log2interp, const int16_t *iq_in, size_t n_in,
                        size_t in_stride, int16_t *iq_out, size_t out_stride, size_t *n_out, int mem);
 /* Interpolators bank, ragged: one Interpolators::interpolate<2^log2interp>_cen call per stream (Interpolators.h:38-43;
@@ -299,7 +307,8 @@ int sdrhip_testsource_configure(sdrhip_testsource *ts, int stream, const char *k
 /* get_sample_rate() / get_frequency() (TestSource.cpp:261-270), block length, forwarded decim / fcpos; any pointer may be NULL */
 int sdrhip_testsource_get(const sdrhip_testsource *ts, int stream, uint32_t *sample_rate, uint32_t *frequency, int *block_length,
                           int *log2decim, int *fcpos);
-/* the next n samples of every stream (stream s at iq_out + 2*s*out_stride), phase continuous across calls */
+/* the next n samples of every stream (stream s at iq_out + 2*s*out_stride), phase continuous across calls.  No byte of row s
+ * past n samples is written, in host and in device memory (tests/test_gpu_bank_bounds.py). */
 int sdrhip_testsource_read(sdrhip_testsource *ts, int16_t *iq_out, size_t n, size_t out_stride, int mem);
 
 /* ---------------------------------------------------------- IQ sample formats -- */
