@@ -191,6 +191,45 @@ int sdrhip_decimate_ragged(sdrhip_decimators *d, int log2decim, int fcpos, unsig
  * call (each stream's shift pair travels in its row of the per-call table).  Everything else as sdrhip_decimate_ragged. */
 int sdrhip_decimate_ragged_bits(sdrhip_decimators *d, int log2decim, int fcpos, unsigned *sampleSize, const int16_t *iq_in,
                                 const size_t *n_in, size_t in_stride, int16_t *iq_out, size_t out_stride, size_t *n_out, int mem);
+/* Decimators bank, taps: every rate of a centred cascade in one launch -- one radio head served to several clients at /4, /16 and
+ * /64 reads its samples once and runs the shared stages once.  The reference's centred cascades nest (Decimators.h:38-53):
+ * decimate4_cen is m_decimator2 -> m_decimator4 (Decimators.cpp:173-213), decimate16_cen the same two stages and two more
+ * (Decimators.cpp:403-516), decimate64_cen those four and two more (Decimators.cpp:902-1305); decimate2_cen (Decimators.cpp:94-120)
+ * is the first stage alone.  Every stage is the same HB64 filter, the stages hand each other unshifted int32, and sampleSize enters
+ * in one place only, the final `x << norm_shift >> trunk_shift`.  So stage k of a longer cascade, shifted for decimate<2^k>_cen,
+ * IS that cascade's output (Downsampler::process dispatches to them, Downsampler.cpp:74-162).
+ * tap_mask: bit k set (k = 1..6) = a tap at /2^k; L = the highest set bit.  Bit 0, bits above 6 and an empty mask are refused.
+ * n_in: host array of nstreams counts, which may differ and may be 0.  n_used[s] = (n_in[s] >> L) << L is returned in the host
+ * array n_used; tap k of stream s receives n_used[s] >> k samples at taps->iq_out[k] + 2 * s * taps->out_stride[k], and
+ * taps->sample_size[k] the by-reference sampleSize after decimate<2^k>_cen (slots of taps that are not set are neither read nor
+ * written).  For every set k and every stream the samples and sample_size[k] are byte for byte those of a reference Decimators
+ * object of its own (one-stream EO1 or DB, as the bank) that calls decimate<2^k>_cen(sampleSize, x[0 : n_used[s]]) and continues
+ * from call to call.  The bank's state afterwards is byte for byte that of sdrhip_decimate_ragged(d, L, SDRHIP_FC_CEN, ...) on the
+ * same counts: the entry mixes freely with sdrhip_decimate, _ragged and _ragged_bits on one bank; a stream with n_in[s] < 2^L keeps
+ * its histories exactly; a call whose counts are all below 2^L launches nothing (sdrhip_decimators_last_plan: path 0).
+ * One launch serves every stream and every tap: the VALU cascade with the per-call work table of sdrhip_decimate_ragged and a
+ * store per tapped stage (sdrhip_decimators_last_plan: path 1, nseg = the launch's workgroups), whatever decim_path says -- the
+ * matrix-core kernel does not serve this entry.  A mask with one bit set launches the existing kernels, as sdrhip_decimate_ragged
+ * picks them.
+ * Device memory: the alignment rules of sdrhip_decimate for iq_in and every tapped iq_out[k] / out_stride[k] (pointers 16-byte
+ * aligned, strides multiples of 4 samples); out_stride[k] >= max_s n_used[s] >> k, in_stride >= max n_in.  No byte of a tap's row
+ * past its count is written, and nothing between or around rows; no sample of stream s behind n_in[s] is read, and nothing depends
+ * on the dropped remainder.  Host memory: the samples go up once, exactly 4 * sum_s n_in[s] bytes ("h2d_bytes"), the results come
+ * down as exactly 4 * sum_k sum_s (n_used[s] >> k) bytes ("d2h_bytes"), only those samples of the caller's rows are written, and
+ * the call returns with the outputs written (a call that launches nothing moves nothing).
+ * SDRHIP_EINVAL, with nothing consumed, enqueued or changed: a NULL handle, taps, n_in or n_used; a bad mask; sampleSize outside
+ * 1..16; a NULL buffer of a tapped slot, or a NULL input, while any stream has output; a stride below its largest count; more
+ * segments than a grid holds.  Broken alignment: SDRHIP_EALIGN, likewise with nothing consumed.
+ * Not covered: the inf / sup cascades (they nest from /8 on), a per-stream sampleSize, the matrix-core path, taps inside sdrhip_rx
+ * itself (a fan-out hub composes this entry with one sdrhip_rx bank: INTEGRATION.md), the C++ adapter headers, tools/fuzz_gpu.py. */
+#define SDRHIP_DECIM_TAP_SLOTS 7   /* index k = log2 of a tap's decimation; slot 0 is not used */
+typedef struct sdrhip_decim_taps {
+    int16_t *iq_out[SDRHIP_DECIM_TAP_SLOTS];      /* tap k, stream s: iq_out[k] + 2 * s * out_stride[k] */
+    size_t out_stride[SDRHIP_DECIM_TAP_SLOTS];    /* samples; ignored for one stream */
+    unsigned sample_size[SDRHIP_DECIM_TAP_SLOTS]; /* out: the by-reference sampleSize after decimate<2^k>_cen */
+} sdrhip_decim_taps;
+int sdrhip_decimate_taps(sdrhip_decimators *d, unsigned tap_mask, unsigned sampleSize, const int16_t *iq_in,
+                         const size_t *n_in, size_t in_stride, sdrhip_decim_taps *taps, size_t *n_used, int mem);
 
 /* ------------------------------------------------------------ interpolators -- */
 /* Bank of `Interpolators` objects (Interpolators.h:35-61): HB64, HB32, 4 x HB16 states. */

@@ -56,6 +56,7 @@ EXPORTS = [
     "sdrhip_rx_set_stream_format", "sdrhip_rx_get_stream_format",
     "sdrhip_tx_set_stream_format", "sdrhip_tx_get_stream_format",
     "sdrhip_interpolate_ragged", "sdrhip_interpolators_last_plan",
+    "sdrhip_decimate_taps",
 ]
 
 
@@ -76,6 +77,14 @@ class CM256Block(C.Structure):
 class DecimPlan(C.Structure):
     _fields_ = [("path", C.c_int), ("wps", C.c_int), ("npieces", C.c_int), ("nseg", C.c_int),
                 ("span", C.c_size_t), ("head", C.c_size_t), ("tail_start", C.c_size_t)]
+
+
+DECIM_TAP_SLOTS = 7  # SDRHIP_DECIM_TAP_SLOTS
+
+
+class DecimTaps(C.Structure):  # sdrhip_decim_taps
+    _fields_ = [("iq_out", C.c_void_p * DECIM_TAP_SLOTS), ("out_stride", C.c_size_t * DECIM_TAP_SLOTS),
+                ("sample_size", C.c_uint * DECIM_TAP_SLOTS)]
 
 
 class InterpPlan(C.Structure):  # sdrhip_interp_plan
@@ -197,6 +206,7 @@ def load():
     lib.sdrhip_tx_set_stream_format.argtypes = [vp, C.POINTER(C.c_int)]
     lib.sdrhip_tx_get_stream_format.argtypes = [vp, i, C.POINTER(C.c_int)]
     lib.sdrhip_decimate_ragged_bits.argtypes = [vp, i, i, C.POINTER(u), vp, C.POINTER(sz), sz, vp, sz, C.POINTER(sz), i]
+    lib.sdrhip_decimate_taps.argtypes = [vp, u, u, vp, C.POINTER(sz), sz, C.POINTER(DecimTaps), C.POINTER(sz), i]
     lib.sdrhip_rx_egress_stream_blocks.argtypes = [vp, C.POINTER(sz)]
     lib.sdrhip_rx_set_stream_meta.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.sdrhip_rx_get_stream_meta.argtypes = [vp, i, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]

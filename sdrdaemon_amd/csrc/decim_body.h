@@ -1,6 +1,7 @@
 // decim_body.h -- device code of the VALU half-band decimator cascade (one piece of one stream per workgroup).
 // Included by decim_kernels.hip (the all-VALU kernels) and decim_mfma.hip (the matrix-core kernels, which run
-// the head and the tail of every stream through this code for the bank state's sake).
+// the head and the tail of every stream through this code for the bank state's sake); rx_ragged_kernels.hip (K1r) and
+// decim_taps_kernels.hip (K1t, the one user of the TAPS parameter) instantiate it over a per-call table.
 #pragma once
 #include "sdrhip_internal.h"
 
@@ -95,10 +96,25 @@ __device__ __forceinline__ void store_one(const OutCtx &oc, size_t k, unsigned v
     }
 }
 
+// Taps of a centred cascade (K1t, decim_taps_kernels.hip): stage S < NS - 1 of a /2^L cascade holds, unshifted, what the last
+// stage of decimate<2^(S+1)>_cen holds (Decimators.cpp:173-213 are the first two stages of :403-516, those the first four of
+// :902-1305), so a tap is the last stage's pack and store with the tap's own shift pair, in front of the hand-over to stage S + 1.
+// NoTaps (every other kernel): nothing of it is compiled.
+struct NoTaps { static constexpr bool ON = false; };
+struct StageTaps {
+    static constexpr bool ON = true;
+    const DecimTapArgs &t; // the kernel's argument: the mask and the slots are workgroup-uniform (scalar loads, one scalar branch per stage)
+    int stream;
+    // index of stage S's next output in its stream: from seg_start >> (S + 1) on, advanced by what a run of the stage yields while
+    // oc.store is set, as oc.out_pos is for the last stage
+    size_t pos[6];
+};
+
 // ------------------------------------------------------------------------------------------
 // one invocation of half-band stage S: `valid` outputs exist; results go to the planes of
 // stage S+1 behind `fill_next` fresh entries, or (last stage) to global memory.
-template <class G, int S> __device__ __forceinline__ void run_stage(int *lds, int tid, int valid, int fill_next, int bias, const OutCtx &oc)
+template <class G, int S, class TAPS = NoTaps>
+__device__ __forceinline__ void run_stage(int *lds, int tid, int valid, int fill_next, int bias, const OutCtx &oc, TAPS *taps = nullptr)
 {
     constexpr bool PK = G::PK && S == 0;
     constexpr bool LAST = (S == G::NS - 1);
@@ -219,6 +235,32 @@ template <class G, int S> __device__ __forceinline__ void run_stage(int *lds, in
             *reinterpret_cast<int2_t *>(ne) = (int2_t){res[0], res[2]};
             *reinterpret_cast<int2_t *>(no) = (int2_t){res[1], res[3]};
         }
+        if constexpr (TAPS::ON) {
+            // tap S + 1: what the LAST branch does (partner's value by DPP, the I lane packs and stores), with the tap's own shift
+            // pair, row and position.  Behind the hand-over, where the results are free to be packed in place: in front of it
+            // the K1t kernel <2, int32 first stage> needs 98 VGPRs and loses a wave per SIMD against its K1r twin (96: five waves).
+            // The condition is workgroup-uniform; warm-up stores nothing.
+            if (oc.store && (taps->t.mask & (2u << S))) {
+                const int norm = taps->t.norm[S + 1], trunk = taps->t.trunk[S + 1];
+                unsigned o[R];
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    int other = __builtin_amdgcn_update_dpp(0, res[r], 0xB1 /* quad_perm [1,0,3,2] */, 0xf, 0xf, true);
+                    o[r] = final_pack(res[r], other, norm, trunk);
+                }
+                if (comp == 0) {
+                    unsigned *out = reinterpret_cast<unsigned *>(taps->t.out[S + 1]) + (size_t)taps->stream * taps->t.stride[S + 1] + taps->pos[S] + k0;
+                    if (k0 + R <= valid) {
+#pragma unroll
+                        for (int r = 0; r < R; r += 4) *reinterpret_cast<uint4_t *>(out + r) = (uint4_t){o[r], o[r + 1], o[r + 2], o[r + 3]};
+                    } else { // a flush: exactly `valid` outputs
+#pragma unroll
+                        for (int r = 0; r < R; ++r)
+                            if (k0 + r < valid) out[r] = o[r];
+                    }
+                }
+            }
+        }
     }
 }
 
@@ -273,7 +315,8 @@ template <class G, int S = 0> __device__ __forceinline__ void state_store(const 
 }
 
 // stages 1 .. NS-1 of one pass (each phase = slide of the previous stage + maybe this stage)
-template <class G, int S> __device__ __forceinline__ void later_stages(int *lds, int tid, int (&fill)[6], int consumed_prev, bool flush, int bias, OutCtx &oc)
+template <class G, int S, class TAPS = NoTaps>
+__device__ __forceinline__ void later_stages(int *lds, int tid, int (&fill)[6], int consumed_prev, bool flush, int bias, OutCtx &oc, TAPS *taps = nullptr)
 {
     if constexpr (S < G::NS) {
         slide<G, S - 1>(lds, tid, consumed_prev);
@@ -281,12 +324,15 @@ template <class G, int S> __device__ __forceinline__ void later_stages(int *lds,
         const int have = fill[S];
         const bool run = have > 0 && (have >= FULL || flush);
         if (run) {
-            run_stage<G, S>(lds, tid, have, fill[S + 1 < 6 ? S + 1 : 5], bias, oc);
+            run_stage<G, S, TAPS>(lds, tid, have, fill[S + 1 < 6 ? S + 1 : 5], bias, oc, taps);
             if (S == G::NS - 1 && oc.store) oc.out_pos += have;
+            if constexpr (TAPS::ON && S < G::NS - 1) {
+                if (oc.store) taps->pos[S] += have;
+            }
             fill[S] = 0;
         }
         __syncthreads();
-        if (run) later_stages<G, S + 1>(lds, tid, fill, have, flush, bias, oc);
+        if (run) later_stages<G, S + 1, TAPS>(lds, tid, fill, have, flush, bias, oc, taps);
     } else {
         slide<G, G::NS - 1>(lds, tid, consumed_prev);
         __syncthreads();
@@ -299,9 +345,10 @@ template <class G, int S> __device__ __forceinline__ void later_stages(int *lds,
 // histories are rebuilt from the WRAW preceding raw samples.  store_state: the piece ends the call.
 // meta_id / meta_n: this workgroup writes the meta blocks of frames meta_id, meta_id + meta_n, ...
 // TAB = false (the ragged launches): a.meta_tab is not looked at, the shared record serves every stream
-template <int L, int FC, bool PACK16, bool TAB = true>
+// TAPS = StageTaps (K1t: FC == 2, no frame mode): `taps` names the rows of the stages in front of the last; their positions are set here
+template <int L, int FC, bool PACK16, bool TAB = true, class TAPS = NoTaps>
 __device__ __forceinline__ void decim_piece(const DecimArgs &a, int *lds, int stream, size_t seg_start, size_t seg_end, bool from_state,
-                                            bool store_state, int meta_id, int meta_n)
+                                            bool store_state, int meta_id, int meta_n, TAPS *taps = nullptr)
 {
     constexpr bool CEN = (FC == 2);
     constexpr int NS = CEN ? L : L - 2;
@@ -321,6 +368,11 @@ __device__ __forceinline__ void decim_piece(const DecimArgs &a, int *lds, int st
     oc.frame_mode = a.frame_mode; oc.frame_blocks = a.frame_blocks; oc.frame_sample_base = a.frame_sample_base;
     oc.out = reinterpret_cast<unsigned *>(a.out) + (size_t)stream * a.out_stride;
     oc.out_pos = seg_start >> L;
+    if constexpr (TAPS::ON) {
+        static_assert(CEN, "taps: centred cascades only");
+#pragma unroll
+        for (int k = 0; k < 6; ++k) taps->pos[k] = seg_start >> (k + 1);
+    }
 
     // fused Rx pipe: meta block + super block headers of the frames this call starts, one frame per
     // workgroup (frame i of the stream by segment i mod nseg); nothing else writes those dwords
@@ -424,10 +476,13 @@ __device__ __forceinline__ void decim_piece(const DecimArgs &a, int *lds, int st
 
         oc.store = !warm;
         const int valid0 = cnt0 >> 1;
-        run_stage<G, 0>(lds, tid, valid0, fill[1], a.bias, oc);
+        run_stage<G, 0, TAPS>(lds, tid, valid0, fill[1], a.bias, oc, taps);
         if (NS == 1 && oc.store) oc.out_pos += valid0;
+        if constexpr (TAPS::ON && NS > 1) {
+            if (oc.store) taps->pos[0] += valid0;
+        }
         __syncthreads();
-        later_stages<G, 1>(lds, tid, fill, valid0, flush, a.bias, oc);
+        later_stages<G, 1, TAPS>(lds, tid, fill, valid0, flush, a.bias, oc, taps);
 
         if (!more) break;
         if (flush) { warm = false; region_end = seg_end; }

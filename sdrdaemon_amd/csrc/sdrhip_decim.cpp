@@ -1,5 +1,6 @@
 // sdrhip_decim.cpp -- the decimator bank of include/sdrhip.h: the bank and its state, the uniform and the ragged device cores (shared
-// with the Rx pipe), the host staging of both entries and the ragged table.  The launch geometry is decided in decim_plan.h.
+// with the Rx pipe), the host staging of both entries and the ragged table, and the taps entry (sdrhip_decimate_taps, K1t) on the
+// ragged core's table and plan.  The launch geometry is decided in decim_plan.h.
 #include "sdrhip_host.h"
 
 #include <cstring>
@@ -474,4 +475,159 @@ extern "C" int sdrhip_decimate_ragged_bits(sdrhip_decimators *d, int log2decim, 
     if (!d || !sampleSize || !n_in || !n_out) return fail(SDRHIP_EINVAL, "decimate_ragged_bits: NULL handle, sampleSize array or count array");
     sdrhip::CtxLock lock_(d->ctx);
     return decimate_ragged_sizes(d, log2decim, fcpos, sampleSize, iq_in, n_in, in_stride, iq_out, out_stride, n_out, mem);
+}
+
+// ------------------------------------------------------------------------------ taps of a centred cascade (K1t)
+namespace {
+// One launch for every stream and every tap of `t` (device pointers); L = the highest tap.  Two and more taps: K1t on K1r's grid and
+// rows, through decimate_core like every cascade launch -- never the matrix cores.  One tap is the cascade alone: the launch
+// sdrhip_decimate_ragged picks.
+int decimate_taps_device(sdrhip_decimators *d, int L, unsigned sampleSize, const int16_t *in, size_t in_stride, const DecimTapArgs &t,
+                         const RaggedRow *rows, const RaggedRow *rows_dev, const RaggedPlan &plan)
+{
+    sdrhip_ctx *c = d->ctx;
+    const int S = d->nstreams;
+    if ((t.mask & (t.mask - 1)) == 0) {
+        std::vector<unsigned> sizes((size_t)S, sampleSize);
+        return decimate_ragged_device(d, L, SDRHIP_FC_CEN, sizes.data(), in, in_stride, t.out[L], t.stride[L], rows, rows_dev, plan);
+    }
+    size_t max_raw = 0, max_dec = 0, min_used = SIZE_MAX;
+    for (int s = 0; s < S; ++s) {
+        if (rows[s].n_raw > max_raw) max_raw = (size_t)rows[s].n_raw;
+        if (rows[s].n_dec > max_dec) max_dec = (size_t)rows[s].n_dec;
+        if (rows[s].n_used < min_used) min_used = (size_t)rows[s].n_used;
+    }
+    const DecimCall k = {in, in_stride, t.out[L], t.stride[L], 0, 0, max_raw, max_dec, min_used};
+    return decimate_core(
+        d, (unsigned)L, SDRHIP_FC_CEN, k, [&]() { return hipErrorInvalidValue; }, // (centred, L >= 2: there is no filter-less call)
+        [&](DecimArgs &a, bool *mfma) -> int {
+            a.nsub_per_seg = plan.nsub; a.nseg = plan.grid;
+            *mfma = false;
+            return SDRHIP_OK;
+        },
+        [&](const DecimArgs &a, bool pack16, bool) { return launch_decimate_taps(L, pack16, a, t, rows_dev, c->stream); });
+}
+
+// ragged_stage_in with the link carrying exactly the counts: its copy of a call too big for the kernel to read pinned memory is one
+// rectangle as wide as the largest count, so unequal rows of such a call go up one by one
+int taps_stage_in(sdrhip_decimators *d, const int16_t *src, size_t in_stride, const size_t *n_in, size_t dstride, const void **out)
+{
+    sdrhip_ctx *c = d->ctx;
+    const int S = d->nstreams;
+    bool equal = true;
+    for (int s = 1; s < S; ++s) equal = equal && n_in[s] == n_in[0];
+    if (equal || (size_t)S * dstride * 4 <= SDRHIP_ZEROCOPY_MAX) return ragged_stage_in(c, d->stage_pin, c->in, src, in_stride, n_in, S, 4, dstride, out);
+    int rc;
+    if ((rc = d->stage_pin.reserve((size_t)S * dstride * 4))) return rc;
+    if ((rc = c->in.reserve((size_t)S * dstride * 4 + 16))) return rc;
+    for (int s = 0; s < S; ++s) {
+        if (!n_in[s]) continue;
+        char *row = d->stage_pin.as<char>() + (size_t)s * dstride * 4;
+        memcpy(row, src + (size_t)s * in_stride * 2, n_in[s] * 4);
+        HIP_TRY(link_copy(c, c->in.as<char>() + (size_t)s * dstride * 4, row, n_in[s] * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    d->stage_pin.mark(c->stream);
+    *out = c->in.p;
+    return SDRHIP_OK;
+}
+} // namespace
+
+extern "C" int sdrhip_decimate_taps(sdrhip_decimators *d, unsigned tap_mask, unsigned sampleSize, const int16_t *iq_in,
+                                    const size_t *n_in, size_t in_stride, sdrhip_decim_taps *taps, size_t *n_used, int mem)
+{
+    if (!d || !taps || !n_in || !n_used) return fail(SDRHIP_EINVAL, "decimate_taps: NULL handle, taps or count array");
+    sdrhip::CtxLock lock_(d->ctx);
+    if (tap_mask == 0 || (tap_mask & ~0x7eu)) return fail(SDRHIP_EINVAL, "decimate_taps: tap_mask takes bits 1..6, at least one");
+    if (sampleSize < 1 || sampleSize > 16) return fail(SDRHIP_EINVAL, "sampleSize must be 1..16");
+    if (int e = check_mem(mem)) return e;
+    sdrhip_ctx *c = d->ctx;
+    const int S = d->nstreams;
+    int L = 6;
+    while (!((tap_mask >> L) & 1u)) --L;
+    size_t max_in = 0;
+    for (int s = 0; s < S; ++s) if (n_in[s] > max_in) max_in = n_in[s];
+    const size_t max_used = (max_in >> L) << L;
+    DecimTapArgs t;
+    memset(&t, 0, sizeof(t));
+    t.mask = tap_mask;
+    for (int k = 1; k <= L; ++k) {
+        if (!((tap_mask >> k) & 1u)) continue;
+        const DecimShifts sh = decimated_shifts((unsigned)k, sampleSize); // the pair of decimate<2^k>_cen
+        t.out[k] = taps->iq_out[k];
+        t.stride[k] = S == 1 ? max_used >> k : taps->out_stride[k];
+        t.norm[k] = (int)sh.norm; t.trunk[k] = (int)sh.trunk;
+    }
+    if (S == 1) in_stride = max_in;
+    bool null_out = false, short_out = false, odd_out = false;
+    for (int k = 1; k <= L; ++k) {
+        if (!((tap_mask >> k) & 1u)) continue;
+        null_out = null_out || !t.out[k];
+        short_out = short_out || t.stride[k] < (max_used >> k);
+        odd_out = odd_out || !aligned16(t.out[k]) || (S > 1 && (t.stride[k] & 3));
+    }
+    if (max_used && (!iq_in || null_out)) return fail(SDRHIP_EINVAL, "decimate_taps: NULL buffer");
+    if (S > 1 && (in_stride < max_in || short_out)) return fail(SDRHIP_EINVAL, "decimate_taps: stride smaller than the largest count");
+    if (mem == SDRHIP_MEM_DEVICE && max_used && (!aligned16(iq_in) || odd_out || (S > 1 && (in_stride & 3))))
+        return fail(SDRHIP_EALIGN, "decimate_taps: device pointers must be 16-byte aligned and strides multiples of 4 samples");
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<RaggedRow> rows((size_t)S);
+    memset(rows.data(), 0, rows.size() * sizeof(RaggedRow));
+    const RaggedRow *rdev = nullptr;
+    RaggedPlan plan;
+    int rc;
+    if (max_used == 0) {
+        d->last = DecimPlanInfo(); // no stream has a whole output sample of tap L: nothing enters any history, nothing is launched
+    } else {
+        for (int s = 0; s < S; ++s) rows[(size_t)s].shifts = ragged_shift_word((unsigned)L, sampleSize); // (the one-tap launch reads it)
+        if ((rc = ragged_prepare(d, L, SDRHIP_FC_CEN, n_in, rows.data(), &rdev, &plan))) return rc;
+        if (mem == SDRHIP_MEM_DEVICE) {
+            if ((rc = decimate_taps_device(d, L, sampleSize, iq_in, in_stride, t, rows.data(), rdev, plan))) return rc;
+        } else {
+            // host rows: staged through device memory with padded (16-byte aligned) strides, the taps' banks one behind the other
+            const size_t dis = (max_in + 3) & ~(size_t)3;
+            size_t off[DECIM_TAP_SLOTS] = {0}, dos[DECIM_TAP_SLOTS] = {0}, total = 0;
+            for (int k = 1; k <= L; ++k) {
+                if (!((tap_mask >> k) & 1u)) continue;
+                dos[k] = ((max_used >> k) + 3) & ~(size_t)3;
+                off[k] = total;
+                total += (size_t)S * dos[k] * 4;
+            }
+            const void *din = nullptr;
+            if ((rc = taps_stage_in(d, iq_in, in_stride, n_in, dis, &din))) return rc;
+            if ((rc = c->out.reserve(total + 16))) return rc;
+            if ((rc = d->out_pin.reserve(total))) return rc;
+            DecimTapArgs td = t;
+            for (int k = 1; k <= L; ++k)
+                if ((tap_mask >> k) & 1u) { td.out[k] = reinterpret_cast<int16_t *>(c->out.as<char>() + off[k]); td.stride[k] = dos[k]; }
+            if ((rc = decimate_taps_device(d, L, sampleSize, static_cast<const int16_t *>(din), dis, td, rows.data(), rdev, plan))) return rc;
+            // down: exactly the samples of the results -- one rectangle per tap when the counts agree, else row by row
+            bool equal = true;
+            for (int s = 1; s < S; ++s) equal = equal && rows[(size_t)s].n_used == rows[0].n_used;
+            for (int k = 1; k <= L; ++k) {
+                if (!((tap_mask >> k) & 1u)) continue;
+                char *pin = d->out_pin.as<char>() + off[k];
+                const char *dev = c->out.as<char>() + off[k];
+                if (equal) {
+                    HIP_TRY(link_copy2d(c, pin, dos[k] * 4, dev, dos[k] * 4, (max_used >> k) * 4, S, hipMemcpyDeviceToHost, c->stream));
+                    continue;
+                }
+                for (int s = 0; s < S; ++s) {
+                    const size_t n = (size_t)rows[(size_t)s].n_used >> k;
+                    if (n) HIP_TRY(link_copy(c, pin + (size_t)s * dos[k] * 4, dev + (size_t)s * dos[k] * 4, n * 4, hipMemcpyDeviceToHost, c->stream));
+                }
+            }
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            for (int k = 1; k <= L; ++k) {
+                if (!((tap_mask >> k) & 1u)) continue;
+                for (int s = 0; s < S; ++s) {
+                    const size_t n = (size_t)rows[(size_t)s].n_used >> k;
+                    if (n) memcpy(taps->iq_out[k] + (size_t)s * t.stride[k] * 2, d->out_pin.as<char>() + off[k] + (size_t)s * dos[k] * 4, n * 4);
+                }
+            }
+        }
+    }
+    for (int s = 0; s < S; ++s) n_used[s] = (n_in[s] >> L) << L;
+    for (int k = 1; k <= L; ++k)
+        if ((tap_mask >> k) & 1u) taps->sample_size[k] = decimated_sample_size((unsigned)k, sampleSize);
+    return SDRHIP_OK;
 }

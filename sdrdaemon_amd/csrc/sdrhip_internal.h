@@ -230,6 +230,20 @@ hipError_t launch_decimate_mfma_ragged(int log2decim, bool pack16, const DecimAr
 // whose seg0 range holds it (binary search over `rows`).  A stream with n_used = 0 copies its state.  a.nsub_per_seg is the
 // segment length; a.n_used / a.nseg are ignored, a.nseg carries the grid size.
 hipError_t launch_decimate_ragged(int log2decim, int fcpos, bool pack16, const DecimArgs &a, const RaggedRow *rows, hipStream_t stream);
+// K1t (decim_taps_kernels.hip): the taps of a centred cascade, the second argument of its kernels.  Index k = log2 of a tap's
+// decimation (slot 0 is not used): tap k is the output of half-band stage k - 1 behind its own `<< norm >> trunk`
+// (decimated_shifts(k, sampleSize)), stream s at out[k] + 2 * s * stride[k].  mask: bit k set = tap k is stored; the highest set bit
+// is the cascade's length L, whose slot serves the last stage (DecimArgs::out / out_stride / norm / trunk are not read).
+// (DecimArgs itself stays as it is: see the note on its last field.)
+constexpr int DECIM_TAP_SLOTS = 7;
+struct DecimTapArgs {
+    int16_t *out[DECIM_TAP_SLOTS];
+    size_t stride[DECIM_TAP_SLOTS]; // samples
+    int norm[DECIM_TAP_SLOTS], trunk[DECIM_TAP_SLOTS]; // (whole words: scalar loads, scalar shift operands)
+    unsigned mask;
+};
+// K1r's grid and rows (a.nsub_per_seg, a.nseg = the grid, rows[s].n_used / seg0); log2decim = the highest tap, 2..6
+hipError_t launch_decimate_taps(int log2decim, bool pack16, const DecimArgs &a, const DecimTapArgs &t, const RaggedRow *rows, hipStream_t stream);
 // filter-less kernel with per-stream counts n_raw (grid planned for the largest, n_in); norm / trunk are kept for the signature and
 // not read: like K1r and K1mr it shifts each stream by its row's pair (RaggedRow::shifts)
 hipError_t launch_decimate_simple_ragged(int log2decim, int fcpos, const int16_t *in, size_t in_stride, int16_t *out,

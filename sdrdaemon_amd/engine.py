@@ -435,6 +435,38 @@ class Decimators(_Handle):
                     _stride_samples(out) if S > 1 else n_res, n_out, MEM_DEVICE if is_t else MEM_HOST))
         return out, np.array(n_out[:], dtype=np.int64), (list(ss) if per_stream else ss.value)
 
+    def decimate_taps(self, taps, sample_size, iq, counts=None, out=None):
+        """sdrhip_decimate_taps: every rate of a centred cascade in one launch.  taps: the log2 decimations wanted (1..6); stream s
+        consumes counts[s] samples of row s of iq (S, >= max(counts), 2), None: the full rows; numpy or a device tensor, as
+        decimate_ragged.  Returns ({k: out_k (S, max(n_used) >> k, 2) -- row s valid up to n_used[s] >> k --}, {k: sample size
+        after decimate<2^k>_cen}, n_used (numpy, S)): what Decimators::decimate<2^k>_cen gives on x[:n_used[s]], for every k, and
+        the bank left as by decimate_ragged(max(taps), FC_CEN, ...).  out: {k: buffer} to write into."""
+        x, is_t, _ = _bank_view(iq, self.nstreams)
+        S, n = x.shape[0], x.shape[1]
+        cnt = _counts([n] * S if counts is None else counts, S, n)
+        ks = sorted(set(int(k) for k in taps))
+        if any(not 0 <= k < 32 for k in ks):
+            raise ValueError("taps: log2 decimations expected")
+        mask = sum(1 << k for k in ks)
+        ok = bool(ks) and not mask & ~0x7e  # (anything else: the library refuses the mask; no buffers are needed for that)
+        L = ks[-1] if ok else 0
+        mx = ((int(cnt.max()) if S else 0) >> L) << L
+        if is_t and S > 1 and (x.stride(0) // 2) % 4:
+            raise ValueError("device bank input: per-stream stride must be a multiple of 4 samples")
+        t = _lib.DecimTaps()
+        outs = {}
+        for k in (ks if ok else ()):
+            o = None if out is None else out.get(k)
+            if o is None:
+                o = _padded_rows(S, mx >> k, 4, torch.int16, x.device, zero=True) if is_t else np.zeros((S, mx >> k, 2), dtype=np.int16)
+            outs[k] = o
+            t.iq_out[k] = _ptr(o).value
+            t.out_stride[k] = _stride_samples(o) if S > 1 else mx >> k
+        n_used = (C.c_size_t * S)()
+        check(self.ctx.lib.sdrhip_decimate_taps(self.h, mask, sample_size, _ptr(x), (C.c_size_t * S)(*cnt.tolist()), _stride_samples(x),
+                                                C.byref(t), n_used, MEM_DEVICE if is_t else MEM_HOST))
+        return outs, {k: int(t.sample_size[k]) for k in outs}, np.array(n_used[:], dtype=np.int64)
+
     def last_plan(self):
         """what the last cascade launch was (sdrhip_decimators_last_plan): dict with path ('valu' / 'mfma' / None), span, wps, ..."""
         return _plan_dict(self.ctx.lib.sdrhip_decimators_last_plan, self.h)
