@@ -303,10 +303,9 @@ extern "C" int sdrhip_decimate(sdrhip_decimators *d, int log2decim, int fcpos, u
 
 // ------------------------------------------------------------------------------ ragged decimator calls
 namespace sdrhip {
-int ragged_prepare(sdrhip_decimators *d, int log2decim, int fcpos, const size_t *n_in, RaggedRow *rows, const RaggedRow **rows_dev,
-                   RaggedPlan *plan, PinnedBuf *pin)
+int ragged_plan(const sdrhip_decimators *d, int log2decim, int fcpos, const size_t *n_in, RaggedRow *rows, RaggedPlan *plan)
 {
-    sdrhip_ctx *c = d->ctx;
+    const sdrhip_ctx *c = d->ctx;
     const int S = d->nstreams;
     size_t total = 0;
     for (int s = 0; s < S; ++s) {
@@ -322,8 +321,16 @@ int ragged_prepare(sdrhip_decimators *d, int log2decim, int fcpos, const size_t 
     plan->ring = env.mfma_ring == 3 ? 3 : 4;
     plan->mfma = mfma_admitted(env.decim_path, env.mfma_min, log2decim, total) &&
                  plan_decimate_mfma_ragged(log2decim, fcpos, rows, S, env.mfma_span, c->n_cu, plan->ring, &plan->mf);
-    const size_t bytes = (size_t)S * sizeof(RaggedRow);
+    return SDRHIP_OK;
+}
+
+int ragged_prepare(sdrhip_decimators *d, int log2decim, int fcpos, const size_t *n_in, RaggedRow *rows, const RaggedRow **rows_dev,
+                   RaggedPlan *plan, PinnedBuf *pin)
+{
+    sdrhip_ctx *c = d->ctx;
     int rc;
+    if ((rc = ragged_plan(d, log2decim, fcpos, n_in, rows, plan))) return rc;
+    const size_t bytes = (size_t)d->nstreams * sizeof(RaggedRow);
     PinnedBuf &tab = pin ? *pin : d->rows_pin;
     if ((rc = tab.reserve(bytes))) return rc; // (waits for the last upload from this staging: the previous table's, or the ring slot's)
     if ((rc = d->rows_dev.reserve(bytes))) return rc;

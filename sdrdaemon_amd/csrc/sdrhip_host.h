@@ -58,6 +58,8 @@ int decimate_device(sdrhip_decimators *d, int log2decim, int fcpos, unsigned *sa
 // ring slot's, so that the call waits for that slot's last upload, not for the previous call's
 int ragged_prepare(sdrhip_decimators *d, int log2decim, int fcpos, const size_t *n_in, RaggedRow *rows, const RaggedRow **rows_dev,
                    RaggedPlan *plan, PinnedBuf *pin = nullptr);
+// its planning half alone (no upload, nothing changes): what a step with these counts will launch, for a caller that sizes buffers ahead
+int ragged_plan(const sdrhip_decimators *d, int log2decim, int fcpos, const size_t *n_in, RaggedRow *rows, RaggedPlan *plan);
 int ragged_reserve(sdrhip_decimators *d, PinnedBuf *pin); // the table's storage alone: nothing left to allocate in ragged_prepare
 // frame_mode != 0 (only when plan.mfma): the matrix-core launch stores straight into the frame layout, `out` = the frame
 // area (stream s at out + s * out_stride dwords, its window at RaggedRow out_off), meta_w / meta_rate = the shared meta words

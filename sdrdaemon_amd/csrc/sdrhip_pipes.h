@@ -3,11 +3,12 @@
 // sdrhip_rx_datagrams.cpp, sdrhip_rx_datagrams_async.cpp, sdrhip_tx.cpp and
 // sdrhip_tx_async.cpp share.  The Rx pipe's host decisions live in headers of their own: rx_frame_area.h (windows),
 // rx_stream_settings.h (per-stream settings, the counts of a ragged step and of a join), rx_depart_order.h and rx_paced_order.h
-// (departure orders)
+// (departure orders), rx_step_plan.h (what a step launches)
 #pragma once
 #include "rx_depart_order.h"
 #include "rx_frame_area.h"
 #include "rx_paced_order.h"
+#include "rx_step_plan.h"
 #include "rx_stream_settings.h"
 #include "sdrhip_host.h"
 
@@ -19,6 +20,24 @@ namespace sdrhip {
 // pinned staging of the ragged step's two host tables (the decimator's rows, the encoder's frame list).  The handle owns one pair,
 // whose reuse waits for the previous call's upload; a datagram batch brings its ring slot's pair (rx_ragged's `tabs`)
 struct RxTabs { PinnedBuf rows, flist; };
+// the kind of a ragged step.  batch: a ragged asynchronous batch (rx_launch_ragged): int16 device rows that K0p laid out, whatever
+// the input format.  dev_rows: iq_in is int16 device rows whatever `mem` and the input format are (the datagram entries' rows); `mem`
+// then speaks of frames_out alone.  tabs: the ring slot's staging instead of the handle's.  follow (the datagram entries with
+// sdrhip_rx_set_follow_meta on): the collector's committed state on the device; KF forms the meta words of the streams that have
+// incoming meta from it, behind the table's upload.  follow_bits (sdrhip_rx_set_follow_bits on): the same state; KFb, in front of
+// KF, forms the shift pair, the third meta word and the CRC of the streams that have an incoming sample size
+struct RxRaggedCall {
+    bool batch, dev_rows;
+    RxTabs *tabs;
+    const FecBufState *follow, *follow_bits;
+};
+// where a step delivers: the caller's buffer (`mem` memory; NULL: the view alone) and the per-stream frame counts
+struct RxFramesOut {
+    uint8_t *frames;
+    size_t stride_bytes;
+    size_t *n_frames;
+    int mem;
+};
 } // namespace sdrhip
 struct sdrhip_rx {
     sdrhip::CtxRef ctx; // (first: released last -- the pipe's own reference, whatever its banks hold)
@@ -215,6 +234,7 @@ struct sdrhip_tx {
 
 namespace sdrhip {
 static_assert(RX_FRAME_SAMPLES == SDRHIP_SAMPLES_PER_FRAME, "rx_frame_area.h frames the header's frame");
+static_assert(RX_STEP_FRAME_SAMPLES == SDRHIP_SAMPLES_PER_FRAME && RX_STEP_FC_CEN == SDRHIP_FC_CEN && RX_STEP_GROUP == GF_FRAMES_PER_GROUP, "rx_step_plan.h");
 static_assert(RX_NB_ORIGINAL == SDRHIP_NB_ORIGINAL && RX_UDPSIZE == SDRHIP_UDPSIZE && RX_STREAM_WORDS == STREAM_META_WORDS, "rx_stream_settings.h");
 // the bank-wide values rx_stream_settings.h resolves against, and its answers for this pipe: the count and the sample size of
 // stream s (as its source delivers it: the decimator's input), the largest count, whether two differ; bytes of a slot of the frame
@@ -276,19 +296,13 @@ inline size_t rx_join_unit(const sdrhip_rx_config &cfg)
 // the datagram entries' rows (j_rows): room for 63 samples held back and max_released payloads behind them.  Rows that grow keep
 // their heads and grow behind a synchronisation (earlier launches may still use the old rows)
 int rx_join_rows(sdrhip_rx *rx, size_t max_released, const char *who);
-// the ragged step (sdrhip_rx_process_ragged).  batch: a ragged asynchronous batch (rx_launch_ragged): int16 device rows that K0p
-// laid out, whatever the input format.  dev_rows: iq_in is int16 device rows whatever `mem` and the input format are (the datagram
-// entry's rows); `mem` then speaks of frames_out alone.  follow (the datagram entries with sdrhip_rx_set_follow_meta on): the collector's
-// committed state on the device; KF forms the meta words of the streams that have incoming meta from it, behind the table's upload.
-// follow_bits (the same entries with sdrhip_rx_set_follow_bits on): the same state; KFb, in front of KF, forms the shift pair, the
-// third meta word and the CRC of the streams that have an incoming sample size.
+// the ragged step (sdrhip_rx_process_ragged), of the kind `call` names (none: the caller's own rows, in the pipe's input format).
 // n = rx_counts() of the call's counts, taken while the pipe stands where this call finds it
 int rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const RxRaggedCounts &n, size_t in_stride, const uint32_t *tv_sec, const uint32_t *tv_usec,
-              uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem, bool batch = false, bool dev_rows = false,
-              RxTabs *tabs = nullptr, const FecBufState *follow = nullptr, const FecBufState *follow_bits = nullptr);
+              const RxFramesOut &out, const RxRaggedCall &call = RxRaggedCall());
 // everything the ragged step allocates for these counts, ahead of it (a caller that must not fail between two launches): the frame
-// area (grown behind a synchronisation), the tables, the frame list, and the stream-order rows when the decimator cannot store
-// straight into the windows.  rx_ragged itself then allocates nothing, unless a matrix-core plan it counted on does not apply
+// area (grown behind a synchronisation), the tables, the frame list, and the stream-order rows when the decimator's plan for these
+// counts does not store straight into the windows (the step's own decision: rx_step_plan.h).  rx_ragged itself then allocates nothing
 int rx_ragged_room(sdrhip_rx *rx, const RxRaggedCounts &n, RxTabs *tabs);
 // ---- the unpack pass (K0p / K0x) of the two sample-fed entries that have one: a ragged batch and the synchronous per-stream-format call
 // rx_pack_rows: S rows of n_in[s] * bytes(fmt) bytes back to back at dst, fmt = fmts[s] or (fmts NULL) bank_fmt.  Row s is read at

@@ -1,6 +1,6 @@
 // sdrhip_rx.cpp -- the fused Rx pipe of include/sdrhip.h: life cycle, configuration, the uniform and the ragged step (the
 // datagram-fed call in front of it: sdrhip_rx_datagrams.cpp).  The per-stream settings' values and records and the counts of a
-// ragged step are rx_stream_settings.h's; here they meet the device.
+// ragged step are rx_stream_settings.h's, what a step launches is rx_step_plan.h's; here they meet the device.
 #include "sdrhip_pipes.h"
 
 using namespace sdrhip;
@@ -35,13 +35,27 @@ static int rx_check_config(const sdrhip_rx_config *cfg)
     return SDRHIP_OK;
 }
 
+// the planner's inputs that the handle and the context hold: the ONE place that reads the arrangement options
+static RxStepIn rx_step_inputs(const sdrhip_rx *rx)
+{
+    const sdrhip_ctx *c = rx->ctx;
+    RxStepIn in = RxStepIn();
+    in.L = rx->cfg.log2decim; in.fcpos = rx->cfg.fcpos; in.R = rx->cfg.nb_fec; in.pipelined = rx->pipelined != 0;
+    in.late_have = rx->late.have; in.late_encode = rx->late.encode; in.late_frames = rx->late.frames; in.late_frame_bytes = rx->late.frame_bytes;
+    in.ev_framed = (hipEvent_t)rx->ev_framed != nullptr;
+    in.rx_fused = c->opt.rx_fused; in.rx_direct = c->opt.rx_direct; in.enc_min_rows = enc128_min_rows(c);
+    return in;
+}
+// the ragged step's: K1mr stores straight into the windows of the area as it stands
+static bool rx_stores_direct(const sdrhip_rx *rx, bool plan_mfma) { return rx_ragged_direct(plan_mfma, rx->ctx->opt.rx_direct, rx->area.cap() * rx_frame_bytes(rx)); }
+
 // the encode that a pipelined call left for the next launch, now (flush, reconfiguration, a call that cannot fuse it)
 static int rx_settle(sdrhip_rx *rx)
 {
     if (!rx->late.encode) return SDRHIP_OK;
     rx->late.encode = false;
     sdrhip_ctx *c = rx->ctx;
-    if (c->opt.rx_fused != 3 || !rx->ev_framed) return fec_encode128_launch(c, rx->late.k);
+    if (!rx_late_overlaps(rx_step_inputs(rx))) return fec_encode128_launch(c, rx->late.k);
     // overlap mode: the encode goes to the second stream -- behind everything the call that left it had enqueued (ev_framed), beside
     // whatever the first stream runs now (the decimator of the current call, enqueued just before) -- and the first stream picks
     // up behind it: the frames are delivered, and the buffers reused, in first-stream order
@@ -281,10 +295,10 @@ extern "C" int sdrhip_rx_flush(sdrhip_rx *rx, uint8_t *frames_out, size_t frame_
     return SDRHIP_OK;
 }
 
-// the shared record of the bank-wide values (rx_meta_record: rx_stream_settings.h); ssd = the bank-wide decimated sample size
-static void rx_meta_base(const sdrhip_rx_config &cfg, unsigned ssd, unsigned w[6])
+// the shared record of the bank-wide values (rx_meta_record: rx_stream_settings.h), with the bank-wide decimated sample size
+static void rx_meta_base(const sdrhip_rx_config &cfg, unsigned w[6])
 {
-    rx_meta_record(cfg.center_frequency_khz, cfg.sample_rate, cfg.nb_fec, ssd, w);
+    rx_meta_record(cfg.center_frequency_khz, cfg.sample_rate, cfg.nb_fec, decimated_sample_size((unsigned)cfg.log2decim, cfg.sample_bits), w);
 }
 
 // ---- the per-stream setters and getters (rx->streams: rx_stream_settings.h).  A setter: the lock, its own refusals, then the
@@ -441,6 +455,188 @@ static int rx_stage_in(sdrhip_ctx *c, const void *src, size_t in_stride, size_t 
     return SDRHIP_OK;
 }
 
+// ---- the uniform step: refuse, input, window and table, decimate and frame, encode, deliver and commit.  What the call launches is
+// rx_step_plan.h's answer (asked once, behind rx_make_room); RxStep / RxRagged hold what the phases of a step share
+namespace {
+struct RxStep {
+    sdrhip_rx *rx; sdrhip_ctx *c; int S;
+    size_t n_in, n_dec, frame_bytes; RxAdvance adv;
+    std::vector<size_t> dones;                      // every stream completes adv.done frames
+    RxStepIn in; RxStepPlan plan;
+    const int16_t *din; size_t dstride;             // the decimator's input rows
+    size_t cap, slot0, stream_bytes; uint8_t *work; // the area, and slot 0 of the window
+    RxMeta meta;                                    // meta record of the frames started by this call (UDPSinkFEC.cpp:87-132)
+    const unsigned *lin; size_t lstride;            // stream-order rows (plan.use_lin: the encoder lays frames out from them)
+    FrameArgs fa;                                   // K2's arguments (plan.k2_in_encoder: they ride in the encoder's launch)
+    Enc128Args k;                                   // the structured encode of this call's frames, now or deferred
+    int input(const int16_t *iq_in, size_t in_stride, int mem), window(uint32_t tv_sec, uint32_t tv_usec), decimate(), encode();
+    int deliver(uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem);
+};
+struct RxRagged {
+    sdrhip_rx *rx; sdrhip_ctx *c; int S, L;
+    const RxRaggedCounts &n; const RxRaggedCall &call;
+    RxRaggedInput route;                  // what stands between the caller's rows and the decimator
+    size_t FB, frame_bytes, stream_bytes; uint8_t *area; // (per-stream fecblk: FB = the slot pitch, 128 + the largest count)
+    std::vector<unsigned> ss;             // each stream's own sample size: sdrhip_rx_set_stream_bits, else the bank's
+    unsigned mw[6];                       // the shared record with a zero stamp (stamps, fc, rate and CRC go per row)
+    const RxStreamRecords *sw;            // NULL: no array is set, mw serves every stream
+    std::vector<RaggedRow> rows; const RaggedRow *rdev; RaggedPlan plan; // the per-call table, its upload, the decimator's plan for it
+    const int16_t *din; size_t dstride;   // the decimator's input rows
+    int table(const uint32_t *tv_sec, const uint32_t *tv_usec), input(const int16_t *iq_in, size_t in_stride), decimate(), encode();
+    int deliver(const RxFramesOut &out);
+};
+} // namespace
+
+// input: host rows are staged; 8-bit input crosses the link as 2 bytes per sample (rows of a multiple of 8 samples: K0's 16-byte
+// loads) and K0 widens it into rx->wide, which the decimator reads as it reads int16 input
+int RxStep::input(const int16_t *iq_in, size_t in_stride, int mem)
+{
+    const bool wide8 = rx->in_fmt != IQF_S16;
+    const void *src = iq_in;
+    size_t sstride = in_stride;
+    int rc;
+    if ((rc = check_mem(mem))) return rc;
+    if (mem == SDRHIP_MEM_HOST) {
+        sstride = wide8 ? (n_in + 7) & ~(size_t)7 : (n_in + 3) & ~(size_t)3;
+        if ((rc = rx_stage_in(c, iq_in, in_stride, n_in, S, wide8 ? 2 : 4, sstride, &src))) return rc;
+    } else if (!aligned16(iq_in) || (S > 1 && (in_stride & (wide8 ? 7 : 3)))) {
+        return wide8 ? fail(SDRHIP_EALIGN, "rx_process: 8-bit device input must be 16-byte aligned, its stride a multiple of 8 samples")
+                     : fail(SDRHIP_EALIGN, "rx_process: device input must be 16-byte aligned");
+    }
+    din = static_cast<const int16_t *>(src);
+    dstride = wide8 ? (n_in + 3) & ~(size_t)3 : sstride;
+    return wide8 ? rx_widen(rx, static_cast<const uint8_t *>(src), sstride, n_in, dstride, &din) : SDRHIP_OK;
+}
+
+// window, plan and table.  Work area [stream][slot][128 + R][512]: this call fills slots slot .. slot + done.  The finished frames
+// stay readable in place until the next call (sdrhip_rx_frames_view); the frame still being filled is the first slot of the next
+// call.  At the end of the area the window wraps: the open frame moves to slot 0 (one strided copy every few calls instead of a
+// save + restore per call).  Frames that wait for delivery (pipelined mode) are never overwritten: a window that would reach them
+// gets a new area.  The decimator kernel writes the meta blocks and super block headers of the frames it starts on its way
+int RxStep::window(uint32_t tv_sec, uint32_t tv_usec)
+{
+    int rc;
+    if ((rc = rx_release_old(rx))) return rc;
+    if ((rc = rx_make_room(rx, dones.data(), in.pipelined, "rx_process"))) return rc;
+    cap = rx->area.cap(); slot0 = rx->area.slot(0); stream_bytes = in.stream_bytes = cap * frame_bytes;
+    work = rx->work.as<uint8_t>() + slot0 * frame_bytes;
+    in.mfma_applies = decimate_mfma_applies(rx->dec, in.L, in.fcpos, n_in);
+    plan = rx_step_plan(in, frame_bytes);
+    memset(&meta, 0, sizeof(meta));
+    if (adv.started <= 0) return SDRHIP_OK;
+    rx_meta_base(rx->cfg, meta.w);
+    if ((rc = rx_stream_table(rx, &meta.tab))) return rc;
+    meta.w[3] = tv_sec; meta.w[4] = tv_usec; // (the stamp of the call's first sample)
+    meta.first = adv.first_new; meta.count = adv.started; meta.frame_count0 = adv.frame_count0;
+    meta.idx0 = adv.idx0; meta.rate = rx->cfg.sample_rate;
+    return SDRHIP_OK;
+}
+
+// decimate and frame, by the plan's route: straight into the frame layout, or in stream order, and K2 lays the samples out as super
+// blocks (+ meta blocks and headers) -- now, unless it rides in the encoder's launch
+int RxStep::decimate()
+{
+    const RxStepPlan &p = plan;
+    const int L = in.L, FB = SDRHIP_NB_ORIGINAL + in.R;
+    unsigned ss = rx->cfg.sample_bits;
+    size_t n_out = 0;
+    int rc;
+    if (!p.stream_order()) {
+        if ((rc = decimate_device(rx->dec, L, in.fcpos, &ss, din, n_in, dstride, reinterpret_cast<int16_t *>(work), stream_bytes / 4, &n_out, 1, FB, in.pending, &meta))) return rc;
+        rx->consumed = true;
+        return rx_settle(rx); // (a waiting encode: this launch takes none along)
+    }
+    lstride = (n_dec + 3) & ~(size_t)3;
+    const size_t bytes = (size_t)S * lstride * 4 + 16;
+    if (p.flip_lin) rx->lin_sel ^= 1;
+    DevBuf &rows = rx->lin[rx->lin_sel];
+    const Enc128Args *fuse = p.fuse ? &rx->late.k : nullptr;
+    bool fused = false;
+    // (rows that grow: the waiting encode goes out first, on its own, and the stream drains before the old rows are freed)
+    if (rows.cap < bytes && rx->late.encode) { if ((rc = rx_settle(rx))) return rc; fuse = nullptr; HIP_TRY(hipStreamSynchronize(c->stream)); }
+    if ((rc = rows.reserve(bytes))) return rc;
+    if ((rc = decimate_device(rx->dec, L, in.fcpos, &ss, din, n_in, dstride, rows.as<int16_t>(), lstride, &n_out, 0, 0, 0, nullptr, fuse, &fused, p.coresident))) return rc;
+    rx->consumed = true;
+    if (fused) rx->late.encode = false;
+    lin = rows.as<unsigned>();
+    fa.skip_from = p.skip_from; fa.skip_to = p.skip_to;
+    fa.in = lin; fa.out = reinterpret_cast<unsigned *>(work); fa.in_stride = lstride; fa.out_stride = stream_bytes / 4;
+    fa.n = n_dec; fa.frame_sample_base = in.pending; fa.frame_blocks = FB;
+    set_meta_args(fa, meta);
+    if (!p.k2_in_encoder) {
+        hipError_t e = launch_frame_pack(fa, S, c->stream);
+        if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "frame pack launch: %s", hipGetErrorString(e));
+    }
+    return rx_settle(rx); // (a waiting encode that this call's launch could not take along)
+}
+
+// FEC over the completed frames of every stream, recovery blocks land behind block 127.  The structured encoder (one workgroup per
+// (frame, half block); frame (s, f) of the window is frame s * cap + f) reads and writes whole dwords:
+static_assert(SDRHIP_UDPSIZE % 4 == 0, "gf_encode128_kernel: a frame of (128 + R) super blocks is a whole number of dwords");
+int RxStep::encode()
+{
+    const RxStepPlan &p = plan;
+    const size_t done = in.done, frames = (size_t)S * cap;
+    uint8_t *rec = work + (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE;
+    int rc;
+    if (p.encoder == RX_ENC_NONE) return SDRHIP_OK;
+    if (p.encoder == RX_ENC_GENERIC) {
+        // generic matrix kernel: one launch for every stream, frame list in groups of GF_FRAMES_PER_GROUP
+        if (rx->flist_done != done || rx->flist_cap != cap) {
+            HIP_TRY(hipStreamSynchronize(c->stream)); // a previous upload may still read flist_host
+            rx->flist_host.clear();
+            for (int s = 0; s < S; ++s)
+                for (size_t f = 0; f < done; ++f) rx->flist_host.push_back((int32_t)(s * cap + f));
+            while (rx->flist_host.size() % GF_FRAMES_PER_GROUP) rx->flist_host.push_back(-1);
+            if ((rc = rx->flist.reserve(rx->flist_host.size() * 4))) return rc;
+            HIP_TRY(link_copy(c, rx->flist.p, rx->flist_host.data(), rx->flist_host.size() * 4, hipMemcpyHostToDevice, c->stream));
+            rx->flist_done = done; rx->flist_cap = cap;
+        }
+        return fec_encode_device(c, work, frame_bytes, frames, in.R, rec, frame_bytes, rx->flist.as<int32_t>(), (int)(rx->flist_host.size() / GF_FRAMES_PER_GROUP), nullptr);
+    }
+    k.in = work; k.out = rec; k.tab = c->gf_tab; k.leaf_tables = c->enc_leaves; k.fft_tables = c->enc_fft; k.use_fft = c->opt.enc_fft;
+    k.bitslice = c->opt.enc_bitslice; k.in_frame_bytes = frame_bytes; k.out_frame_bytes = frame_bytes;
+    k.rows = in.R; k.nframes = (int)frames;
+    k.nlist = (int)((size_t)S * done); k.gen_done = (int)done; k.gen_cap = (int)cap;
+    if (p.use_lin) { k.lin = lin; k.lin_stride = lstride; k.lin_cap = (int)cap; k.lin_first = p.lin_first; k.lin_pending = (int)p.lin_pending; }
+    if (p.encoder == RX_ENC_DEFERRED) return SDRHIP_OK; // rides in the next call's decimator launch (or sdrhip_rx_flush)
+    if (!p.k2_in_encoder) return fec_encode128_launch(c, k);
+    set_meta_args(k, meta); // (encoder + K2 in one launch: the encoder derives the meta blocks of the frames this call starts itself)
+    k.lin_straddle = p.lin_straddle ? 1 : 0;
+    hipError_t e;
+    {
+        KTimer kt(c, SDRHIP_K_FEC_ENCODE);
+        e = launch_gf_encode128_pack(k, fa, S, c->stream);
+    }
+    return e == hipSuccess ? SDRHIP_OK : fail(SDRHIP_EDEVICE, "encode + frame pack launch: %s", hipGetErrorString(e));
+}
+
+// delivery: this call's frames, or (pipelined) the previous call's, whose encode went out above; then every stream moves on
+// together, and the frame still being filled opens the next call's window
+int RxStep::deliver(uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem)
+{
+    sdrhip_rx::Late &late = rx->late;
+    const size_t done = in.done;
+    int rc;
+    if (!in.pipelined) {
+        if ((rc = rx_deliver(rx, rx->work.as<uint8_t>(), slot0, stream_bytes, done, frame_bytes, frames_out, frame_stride_bytes, n_frames, mem))) return rc;
+    } else {
+        if (!late.have) rx->view.clear();
+        else if ((rc = rx_deliver(rx, late.area, late.first, late.stride, late.frames, late.frame_bytes, frames_out, frame_stride_bytes, n_frames, mem))) return rc;
+        late.have = done > 0; late.encode = plan.encoder == RX_ENC_DEFERRED;
+        if (plan.record_framed) { // (everything the deferred encode reads has been enqueued on the first stream by now)
+            if ((rc = rx->ev_framed.ensure())) return rc;
+            HIP_TRY(hipEventRecord(rx->ev_framed, c->stream));
+        }
+        late.k = k;
+        late.area = rx->work.as<uint8_t>(); late.first = slot0; late.in_old = false;
+        late.stride = stream_bytes; late.frames = done; late.frame_bytes = frame_bytes;
+    }
+    rx->area.commit(dones.data(), std::vector<uint64_t>(dones.size(), adv.rest).data());
+    if (mem == SDRHIP_MEM_HOST) HIP_TRY(hipStreamSynchronize(c->stream));
+    return SDRHIP_OK;
+}
+
 extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_in, size_t in_stride, uint32_t tv_sec, uint32_t tv_usec,
                                  uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem)
 {
@@ -456,7 +652,8 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
         const size_t S = (size_t)rx->nstreams;
         std::vector<size_t> cnt(S, n_in), nf(S, 0);
         std::vector<uint32_t> sec(S, tv_sec), usec(S, tv_usec);
-        const int rc = rx_ragged(rx, iq_in, rx_counts(rx, cnt.data()), in_stride, sec.data(), usec.data(), frames_out, frame_stride_bytes, nf.data(), mem);
+        const RxFramesOut out = {frames_out, frame_stride_bytes, nf.data(), mem};
+        const int rc = rx_ragged(rx, iq_in, rx_counts(rx, cnt.data()), in_stride, sec.data(), usec.data(), out);
         if (rc) return rc;
         size_t most = 0;
         for (size_t s = 0; s < S; ++s) if (nf[s] > most) most = nf[s];
@@ -467,202 +664,31 @@ extern "C" int sdrhip_rx_process(sdrhip_rx *rx, const int16_t *iq_in, size_t n_i
         // an empty call completes nothing; in pipelined mode it still DELIVERS what the previous call completed (the header's
         // contract: every call delivers the frames of the one before it)
         if (rx->pipelined && rx->late.have) return sdrhip_rx_flush(rx, frames_out, frame_stride_bytes, n_frames, mem);
-        rx->view.clear();
-        return SDRHIP_OK;
+        rx->view.clear(); return SDRHIP_OK;
     }
     if (!iq_in) return fail(SDRHIP_EINVAL, "rx_process: NULL input");
-    sdrhip_ctx *c = rx->ctx;
     rx->consumed = false;
-    HIP_TRY(hipSetDevice(c->device));
-    const int S = rx->nstreams, L = rx->cfg.log2decim, R = rx->cfg.nb_fec;
-    const int FB = SDRHIP_NB_ORIGINAL + R;
-    const size_t frame_bytes = (size_t)FB * SDRHIP_UDPSIZE;
-    const size_t n_dec = n_in >> L;
-    const uint64_t pending = rx->area.pending(0); // (every stream stands here: aligned)
-    const RxAdvance adv = rx->area.advance(0, n_dec);
-    const size_t done = adv.done;
+    HIP_TRY(hipSetDevice(rx->ctx->device));
+    const int S = rx->nstreams;
+    RxStep st;
+    st.rx = rx; st.c = rx->ctx; st.S = S;
+    st.n_in = n_in; st.n_dec = n_in >> rx->cfg.log2decim; st.frame_bytes = (size_t)(SDRHIP_NB_ORIGINAL + rx->cfg.nb_fec) * SDRHIP_UDPSIZE;
+    st.adv = rx->area.advance(0, st.n_dec); st.in = rx_step_inputs(rx);
+    st.in.pending = rx->area.pending(0); st.in.done = st.adv.done; // (every stream stands here: aligned)
+    st.lin = nullptr; st.lstride = 0;
+    memset(&st.fa, 0, sizeof(st.fa)); memset(&st.k, 0, sizeof(st.k));
     if (S == 1) in_stride = n_in;
-    const size_t deliver_now = rx->pipelined ? (rx->late.have ? rx->late.frames : 0) : done;
-    const size_t deliver_fb = rx->pipelined && rx->late.have ? rx->late.frame_bytes : frame_bytes;
-    if (deliver_now && !frames_out && mem != SDRHIP_MEM_DEVICE) return fail(SDRHIP_EINVAL, "rx_process: NULL frames_out");
-    if (frames_out && S > 1 && deliver_now && frame_stride_bytes < deliver_now * deliver_fb) return fail(SDRHIP_EINVAL, "rx_process: frame stride too small");
-
-    const int16_t *din = iq_in;
-    size_t dstride = in_stride;
+    // ---- everything that can be refused is refused before anything is consumed
+    const RxStepDelivery d = rx_step_delivery(st.in, st.frame_bytes);
+    if (d.frames && !frames_out && mem != SDRHIP_MEM_DEVICE) return fail(SDRHIP_EINVAL, "rx_process: NULL frames_out");
+    if (frames_out && S > 1 && d.frames && frame_stride_bytes < d.frames * d.frame_bytes) return fail(SDRHIP_EINVAL, "rx_process: frame stride too small");
     int rc;
-    // 8-bit input: 2 bytes per sample cross the link (rows of a multiple of 8 samples: K0's 16-byte loads), K0 widens them into
-    // rx->wide, which the decimator reads as it reads int16 input
-    const bool wide8 = rx->in_fmt != IQF_S16;
-    const void *src = iq_in;
-    if ((rc = check_mem(mem))) return rc;
-    if (mem == SDRHIP_MEM_HOST) {
-        dstride = wide8 ? (n_in + 7) & ~(size_t)7 : (n_in + 3) & ~(size_t)3;
-        if ((rc = rx_stage_in(c, iq_in, in_stride, n_in, S, wide8 ? 2 : 4, dstride, &src))) return rc;
-    } else if (!aligned16(iq_in) || (S > 1 && (in_stride & (wide8 ? 7 : 3)))) {
-        return wide8 ? fail(SDRHIP_EALIGN, "rx_process: 8-bit device input must be 16-byte aligned, its stride a multiple of 8 samples")
-                     : fail(SDRHIP_EALIGN, "rx_process: device input must be 16-byte aligned");
-    }
-    din = static_cast<const int16_t *>(src);
-    if (wide8) {
-        const size_t sstride = dstride;
-        dstride = (n_in + 3) & ~(size_t)3;
-        if ((rc = rx_widen(rx, static_cast<const uint8_t *>(src), sstride, n_in, dstride, &din))) return rc;
-    }
-
-    // ---- work area [stream][slot][128 + R][512]: this call fills slots slot .. slot + done.  The
-    // finished frames stay readable in place until the next call (sdrhip_rx_frames_view); the frame still
-    // being filled is the first slot of the next call.  At the end of the area the window wraps: the open
-    // frame moves to slot 0 (one strided copy every few calls instead of a save + restore per call).  Frames that
-    // wait for delivery (pipelined mode) are never overwritten: a window that would reach them gets a new area.
-    const std::vector<size_t> dones((size_t)S, done);
-    if ((rc = rx_release_old(rx))) return rc;
-    if ((rc = rx_make_room(rx, dones.data(), rx->pipelined != 0, "rx_process"))) return rc;
-    const size_t cap = rx->area.cap(), slot0 = rx->area.slot(0);
-    const size_t stream_bytes = cap * frame_bytes;
-    uint8_t *work = rx->work.as<uint8_t>() + slot0 * frame_bytes; // slot 0 of the window
-
-    // ---- meta record of the frames started by this call (UDPSinkFEC.cpp:87-132); the decimator kernel writes
-    // their meta blocks and super block headers on its way
-    unsigned ss = rx->cfg.sample_bits;
-    RxMeta meta;
-    memset(&meta, 0, sizeof(meta));
-    if (adv.started > 0) {
-        // tv_sec / tv_usec = the stamp of the call's first sample
-        rx_meta_base(rx->cfg, decimated_sample_size((unsigned)L, ss), meta.w);
-        if ((rc = rx_stream_table(rx, &meta.tab))) return rc;
-        meta.w[3] = tv_sec; meta.w[4] = tv_usec;
-        meta.first = adv.first_new; meta.count = adv.started; meta.frame_count0 = adv.frame_count0;
-        meta.idx0 = adv.idx0;
-        meta.rate = rx->cfg.sample_rate;
-    }
-
-    size_t n_out = 0;
-    EncodeLin elin;
-    bool use_lin = false, pack_with_encoder = false;
-    FrameArgs fa;
-    memset(&fa, 0, sizeof(fa));
-    const bool structured = R >= enc128_min_rows(c) && frame_bytes % 4 == 0; // gf_encode128_kernel serves this setting
-    const bool filterless = L == 0 || (rx->cfg.fcpos != SDRHIP_FC_CEN && L <= 2); // Decimators.cpp:22-91,127-170: no cascade kernel
-    const Enc128Args *fuse = rx->late.encode && (c->opt.rx_fused == 1 || c->opt.rx_fused == 2) ? &rx->late.k : nullptr;
-    // overlap mode: the waiting encode will run on the second stream BESIDE this call's decimator (rx_settle below), which therefore
-    // leaves room on its CUs (ring depth 3) and raises its waves' priority
-    const bool coresident = rx->late.encode && c->opt.rx_fused == 3 && rx->ev_framed;
-    bool fused = false;
-    // (matrix-core decimator: stream order + K2 + the encoder's fused copy, unless its waves frame their output themselves)
-    const bool direct = c->opt.rx_direct && !rx->pipelined && stream_bytes < 0x3fffffffu;
-    if (filterless || (!direct && decimate_mfma_applies(rx->dec, L, rx->cfg.fcpos, n_in))) {
-        // ---- decimate in stream order, then K2 lays the samples out as super blocks (+ meta blocks and headers)
-        const size_t lstride = (n_dec + 3) & ~(size_t)3;
-        if (rx->pipelined) rx->lin_sel ^= 1; // (the deferred encoder of the previous call still reads the other one)
-        DevBuf &lin = rx->lin[rx->lin_sel];
-        if (lin.cap < (size_t)S * lstride * 4 + 16 && rx->late.encode) { if ((rc = rx_settle(rx))) return rc; fuse = nullptr; HIP_TRY(hipStreamSynchronize(c->stream)); }
-        if ((rc = lin.reserve((size_t)S * lstride * 4 + 16))) return rc;
-        rc = decimate_device(rx->dec, L, rx->cfg.fcpos, &ss, din, n_in, dstride, lin.as<int16_t>(), lstride, &n_out, 0, 0, 0, nullptr, fuse, &fused, coresident);
-        if (rc) return rc;
-        rx->consumed = true;
-        if (fused) rx->late.encode = false;
-        // the frames that lie entirely inside this call's samples are laid out by the encoder (fused copy); K2 does
-        // the frame that was open when the call began, the one left open at its end, meta blocks and headers
-        if (fec_encode_fuses_framing(c, R)) {
-            const size_t first = pending ? 1 : 0;
-            if (done > first && frame_bytes % 4 == 0) {
-                elin.lin = lin.as<unsigned>(); elin.stride = lstride; elin.cap = (int)cap;
-                elin.first = (int)first; elin.pending = (int)pending;
-                use_lin = true;
-            }
-        }
-        if (use_lin) {
-            fa.skip_from = (size_t)elin.first * SDRHIP_SAMPLES_PER_FRAME - (size_t)elin.pending;
-            fa.skip_to = done * SDRHIP_SAMPLES_PER_FRAME - (size_t)elin.pending;
-        }
-        fa.in = lin.as<unsigned>(); fa.out = reinterpret_cast<unsigned *>(work);
-        fa.in_stride = lstride; fa.out_stride = stream_bytes / 4;
-        fa.n = n_dec; fa.frame_sample_base = pending; fa.frame_blocks = FB;
-        set_meta_args(fa, meta);
-        // K2 rides in the encoder's launch when this call's frames are encoded right away by the structured encoder (one launch
-        // less per step); otherwise it goes out now
-        pack_with_encoder = !rx->pipelined && c->opt.rx_fused && structured && R > 0 && use_lin;
-        if (!pack_with_encoder) {
-            hipError_t e = launch_frame_pack(fa, S, c->stream);
-            if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "frame pack launch: %s", hipGetErrorString(e));
-        }
-    } else {
-        // ---- decimate straight into the frame layout (VALU cascade kernel with the framing epilogue, or the matrix-core kernel
-        // with its frame-layout stores and the VALU pieces' epilogue for meta blocks and headers)
-        rc = decimate_device(rx->dec, L, rx->cfg.fcpos, &ss, din, n_in, dstride, reinterpret_cast<int16_t *>(work), stream_bytes / 4, &n_out, 1,
-                             FB, pending, &meta);
-        if (rc) return rc;
-        rx->consumed = true;
-    }
-    if ((rc = rx_settle(rx))) return rc; // (a waiting encode that this call's launch could not take along)
-
-    // ---- FEC over the completed frames of every stream, recovery blocks land behind block 127
-    bool encode_later = false;
-    Enc128Args k;
-    memset(&k, 0, sizeof(k));
-    if (done && R > 0) {
-        if (structured) {
-            // structured encoder, one workgroup per (frame, half block); frame (s, f) of the window is frame s * cap + f
-            k.in = work; k.out = work + (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE; k.tab = c->gf_tab; k.leaf_tables = c->enc_leaves; k.fft_tables = c->enc_fft; k.use_fft = c->opt.enc_fft;
-            k.bitslice = c->opt.enc_bitslice;
-            k.in_frame_bytes = frame_bytes; k.out_frame_bytes = frame_bytes;
-            k.rows = R; k.nframes = (int)((size_t)S * cap);
-            k.nlist = (int)((size_t)S * done); k.gen_done = (int)done; k.gen_cap = (int)cap;
-            if (use_lin) { k.lin = elin.lin; k.lin_stride = elin.stride; k.lin_cap = elin.cap; k.lin_first = elin.first; k.lin_pending = elin.pending; }
-            if (rx->pipelined) {
-                encode_later = true; // rides in the next call's decimator launch (or sdrhip_rx_flush)
-            } else if (pack_with_encoder) {
-                // encoder + K2 in one launch: the encoder derives the meta blocks of the frames this call starts itself and
-                // completes the frame that was open (its tail comes from the stream-order buffer), K2 leaves both alone
-                set_meta_args(k, meta);
-                if (elin.first == 1) { k.lin_straddle = 1; fa.skip_from = 0; }
-                hipError_t e;
-                {
-                    KTimer kt(c, SDRHIP_K_FEC_ENCODE);
-                    e = launch_gf_encode128_pack(k, fa, S, c->stream);
-                }
-                if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "encode + frame pack launch: %s", hipGetErrorString(e));
-            } else if ((rc = fec_encode128_launch(c, k))) return rc;
-        } else {
-            // generic matrix kernel: one launch for every stream, frame list in groups of GF_FRAMES_PER_GROUP
-            if (rx->flist_done != done || rx->flist_cap != cap) {
-                HIP_TRY(hipStreamSynchronize(c->stream)); // a previous upload may still read flist_host
-                rx->flist_host.clear();
-                for (int s = 0; s < S; ++s)
-                    for (size_t f = 0; f < done; ++f) rx->flist_host.push_back((int32_t)(s * cap + f));
-                while (rx->flist_host.size() % GF_FRAMES_PER_GROUP) rx->flist_host.push_back(-1);
-                if ((rc = rx->flist.reserve(rx->flist_host.size() * 4))) return rc;
-                HIP_TRY(link_copy(c, rx->flist.p, rx->flist_host.data(), rx->flist_host.size() * 4, hipMemcpyHostToDevice, c->stream));
-                rx->flist_done = done; rx->flist_cap = cap;
-            }
-            if ((rc = fec_encode_device(c, work, frame_bytes, (size_t)S * cap, R, work + (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE,
-                                        frame_bytes, rx->flist.as<int32_t>(), (int)(rx->flist_host.size() / GF_FRAMES_PER_GROUP), nullptr)))
-                return rc;
-        }
-    }
-    // ---- delivery: this call's frames, or (pipelined) the previous call's, whose encode went out above
-    if (rx->pipelined) {
-        if (rx->late.have) {
-            if ((rc = rx_deliver(rx, rx->late.area, rx->late.first, rx->late.stride, rx->late.frames, rx->late.frame_bytes, frames_out, frame_stride_bytes, n_frames, mem))) return rc;
-        } else {
-            rx->view.clear();
-        }
-        rx->late.have = done > 0;
-        rx->late.encode = encode_later;
-        if (encode_later && c->opt.rx_fused == 3) { // (everything the deferred encode reads has been enqueued on the first stream by now)
-            if ((rc = rx->ev_framed.ensure())) return rc;
-            HIP_TRY(hipEventRecord(rx->ev_framed, c->stream));
-        }
-        rx->late.k = k;
-        rx->late.area = rx->work.as<uint8_t>(); rx->late.first = slot0; rx->late.in_old = false;
-        rx->late.stride = stream_bytes; rx->late.frames = done; rx->late.frame_bytes = frame_bytes;
-    } else {
-        if ((rc = rx_deliver(rx, rx->work.as<uint8_t>(), slot0, stream_bytes, done, frame_bytes, frames_out, frame_stride_bytes, n_frames, mem))) return rc;
-    }
-    // every stream moves on together; the frame still being filled opens the next call's window
-    rx->area.commit(dones.data(), std::vector<uint64_t>((size_t)S, adv.rest).data());
-    if (mem == SDRHIP_MEM_HOST) HIP_TRY(hipStreamSynchronize(c->stream));
-    return SDRHIP_OK;
+    if ((rc = st.input(iq_in, in_stride, mem))) return rc;
+    st.dones.assign((size_t)S, st.adv.done);
+    if ((rc = st.window(tv_sec, tv_usec))) return rc;
+    if ((rc = st.decimate())) return rc;
+    if ((rc = st.encode())) return rc;
+    return st.deliver(frames_out, frame_stride_bytes, n_frames, mem);
 }
 
 // --------------------------------------------------------------------------- ragged Rx calls
@@ -671,21 +697,17 @@ int sdrhip::rx_area_room(sdrhip_rx *rx, const size_t *done)
     return rx_make_room(rx, done ? done : std::vector<size_t>(rx->area.streams(), 0).data(), false, "rx_process_ragged", true);
 }
 
-// entries of the ragged step's frame list: up to three sublists (one per encoder form, per-stream fecblk), each padded to a
-// whole group
-static size_t rx_flist_entries(size_t sum_done) { return (sum_done / GF_FRAMES_PER_GROUP + 3) * GF_FRAMES_PER_GROUP; }
-// the form fec_encode_device chooses for `rows` recovery blocks: 0 the generic kernel, 1 the FFT / bit-sliced kernel, 2 the walk
-static int rx_encode_form(const sdrhip_ctx *c, int rows) { return rows < enc128_min_rows(c) ? 0 : rows <= 32 ? 1 : 2; }
-
 int sdrhip::rx_ragged_room(sdrhip_rx *rx, const RxRaggedCounts &n, RxTabs *tabs)
 {
     const int S = rx->nstreams, L = rx->cfg.log2decim;
     int rc;
     if ((rc = rx_area_room(rx, n.done.data()))) return rc;
     if ((rc = ragged_reserve(rx->dec, tabs ? &tabs->rows : nullptr))) return rc;
-    // (only the matrix-core launch of a centred decimation by 4 or more stores straight into the windows)
-    const bool may_direct = rx->cfg.fcpos == SDRHIP_FC_CEN && L >= 2 && rx->ctx->opt.rx_direct;
-    if (!may_direct && (rc = rx->lin[0].reserve((size_t)S * ((n.max_dec + 3) & ~(size_t)3) * 4 + 16))) return rc;
+    // (the stream-order rows, unless the decimator's plan for these counts stores straight into the windows: the step's own rule)
+    std::vector<RaggedRow> rows((size_t)S);
+    RaggedPlan plan;
+    if ((rc = ragged_plan(rx->dec, L, rx->cfg.fcpos, n.n_in, rows.data(), &plan))) return rc;
+    if (!rx_stores_direct(rx, plan.mfma) && (rc = rx->lin[0].reserve((size_t)S * ((n.max_dec + 3) & ~(size_t)3) * 4 + 16))) return rc;
     if (n.sum_done && rx_fec_max(rx) > 0) {
         const size_t nl = rx_flist_entries(n.sum_done);
         if ((rc = (tabs ? tabs->flist : rx->r_flist_pin).reserve(nl * 4))) return rc;
@@ -759,219 +781,196 @@ static int rx_unpack_rows(sdrhip_rx *rx, const int16_t *iq_in, size_t in_stride,
     return SDRHIP_OK;
 }
 
-// Every stream takes its own count: K0r (8-bit input) -> K1r / filter-less kernel into stream order -> K2r into each stream's
-// own window -> one encoder launch over the list of every stream's completed frames.  A call that fails after it moved windows
-// leaves the windows moved (the open frames lie there now) and the rest of the framing state untouched.
-int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const RxRaggedCounts &n, size_t in_stride, const uint32_t *tv_sec, const uint32_t *tv_usec,
-                      uint8_t *frames_out, size_t frame_stride_bytes, size_t *n_frames, int mem, bool batch, bool dev_rows, RxTabs *tabs,
-                      const FecBufState *follow, const FecBufState *follow_bits)
+// ---- the ragged step: every stream takes its own count.  K0x / K0r (input) -> K1mr straight into each stream's window, or K1r /
+// the filter-less kernel into stream order and K2r into the windows -> the encoder over the list of every stream's completed
+// frames; which of these run is rx_step_plan.h's answer.  The per-call table first: counts (decimator), windows and meta records
+// (K2r); then the kernels that rewrite rows of it on the device
+int RxRagged::table(const uint32_t *tv_sec, const uint32_t *tv_usec)
 {
-    sdrhip_ctx *c = rx->ctx;
-    // (per-stream fecblk: FB = the slot pitch, 128 + the largest count; a frame of stream s holds rx_stream_blocks(rx, s) of them)
-    const int S = rx->nstreams, L = rx->cfg.log2decim, R = rx_fec_max(rx);
-    const size_t FB = (size_t)SDRHIP_NB_ORIGINAL + (size_t)R;
-    const size_t frame_bytes = FB * SDRHIP_UDPSIZE;
-    const bool mixed = rx_fec_mixed(rx);
-    const size_t *n_in = n.n_in, max_in = n.max_in, max_dec = n.max_dec, max_done = n.max_done, sum_done = n.sum_done;
-    const std::vector<size_t> &done = n.done;
-    for (int s = 0; s < S; ++s) n_frames[s] = 0;
-    // ---- everything that can be refused is checked before anything is consumed
-    if (int e = check_mem(mem)) return e;
-    if (rx->pipelined) return fail(SDRHIP_EINVAL, "rx_process_ragged: not available in pipelined mode");
-    if (!batch && rx_batches_active(rx)) return fail(SDRHIP_EINVAL, "rx_process_ragged: asynchronous batches are being filled or in flight: collect them first");
-    if (S == 1) in_stride = max_in;
-    if (S > 1 && in_stride < max_in) return fail(SDRHIP_EINVAL, "rx_process_ragged: in_stride smaller than the largest count");
-    if (max_in && !iq_in) return fail(SDRHIP_EINVAL, "rx_process_ragged: NULL input");
-    // (per-stream input format: the caller's rows are K0x's source, 4-byte units of stride whatever a row holds)
-    const int *fmts = !batch && !dev_rows ? rx->streams.formats() : nullptr;
-    const bool wide8 = rx->in_fmt != IQF_S16 && !batch && !dev_rows && !fmts;
-    const bool in_dev = mem == SDRHIP_MEM_DEVICE || dev_rows;
-    if (fmts && !unpackx_measure(n_in, 1, (size_t)S, fmts).fits) return fail(SDRHIP_EINVAL, "rx_process_ragged: too many samples for one launch");
-    if (max_in && in_dev && (!aligned16(iq_in) || (S > 1 && (in_stride & (wide8 ? 7 : 3)))))
-        return fail(SDRHIP_EALIGN, "rx_process_ragged: device input must be 16-byte aligned, its stride a multiple of %d samples", wide8 ? 8 : 4);
-    if (int e = rx_refuse_delivery("rx_process_ragged", n, frames_out, frame_stride_bytes, mem, false)) return e;
-    HIP_TRY(hipSetDevice(c->device));
-    rx->consumed = false;
-    if (max_in == 0) { // nothing arrives: nothing changes, nothing is delivered
-        rx->view.clear();
-        return SDRHIP_OK;
-    }
-    int rc;
-    // ---- windows: stream s fills slots slot(s) .. slot(s) + done[s] of its area; a window that would pass the end of the area
-    // moves that stream's open frame to slot 0 (the others stay where they are); a call that needs more slots than the area has
-    // gets a new area, every open frame at slot 0
-    if ((rc = rx_release_old(rx))) return rc;
-    if ((rc = rx_make_room(rx, done.data(), false, "rx_process_ragged"))) return rc;
     const RxFrameArea &A = rx->area;
-    const size_t stream_bytes = A.cap() * frame_bytes;
-    uint8_t *area = rx->work.as<uint8_t>();
-
-    // ---- the per-call table: counts (decimator), windows and meta records (K2r)
-    std::vector<unsigned> ss((size_t)S); // (each stream's own size: sdrhip_rx_set_stream_bits, else the bank's)
-    for (int s = 0; s < S; ++s) ss[(size_t)s] = rx_bits_of(rx, (size_t)s);
-    unsigned mw[6]; // (the record with a zero stamp; the stamps go per row, and so do fc, rate and the CRC: sdrhip_rx_set_stream_meta)
-    rx_meta_base(rx->cfg, decimated_sample_size((unsigned)L, rx->cfg.sample_bits), mw);
-    const RxStreamRecords *sw = rx->streams.records(rx_bank(rx)); // (NULL: no array is set, mw serves every stream)
-    std::vector<RaggedRow> rows((size_t)S);
     memset(rows.data(), 0, rows.size() * sizeof(RaggedRow));
-    for (int s = 0; s < S; ++s) {
-        RaggedRow &r = rows[(size_t)s];
-        const RxAdvance &a = n.adv[(size_t)s];
-        r.out_off = A.slot((size_t)s) * frame_bytes / 4;
-        r.frame_sample_base = A.pending((size_t)s);
-        const unsigned *t = sw ? &sw->words[(size_t)s * STREAM_META_WORDS] : nullptr;
-        r.fc = t ? t[0] : mw[0]; r.rate = t ? t[1] : mw[1];
-        r.crc0 = t ? t[2] : mw[5];
-        r.w2 = sw ? sw->w2[(size_t)s] : mw[2];
-        r.shifts = sw ? sw->shifts[(size_t)s] : ragged_shift_word((unsigned)L, ss[(size_t)s]);
-        if (a.started > 0 && (n_in[s] >> L)) {
-            r.meta_first = a.first_new; r.meta_count = a.started;
-            r.frame_count0 = a.frame_count0;
-            r.meta_idx0 = a.idx0;
+    for (size_t s = 0; s < (size_t)S; ++s) {
+        RaggedRow &r = rows[s];
+        const RxAdvance &a = n.adv[s];
+        ss[s] = rx_bits_of(rx, s);
+        r.out_off = A.slot(s) * frame_bytes / 4; r.frame_sample_base = A.pending(s);
+        const unsigned *t = sw ? &sw->words[s * STREAM_META_WORDS] : nullptr;
+        r.fc = t ? t[0] : mw[0]; r.rate = t ? t[1] : mw[1]; r.crc0 = t ? t[2] : mw[5];
+        r.w2 = sw ? sw->w2[s] : mw[2];
+        r.shifts = sw ? sw->shifts[s] : ragged_shift_word((unsigned)L, ss[s]);
+        if (a.started > 0 && (n.n_in[s] >> L)) {
+            r.meta_first = a.first_new; r.meta_count = a.started; r.frame_count0 = a.frame_count0; r.meta_idx0 = a.idx0;
             r.tv_sec = tv_sec[s]; r.tv_usec = tv_usec[s];
         }
     }
-    const RaggedRow *rdev = nullptr;
-    RaggedPlan plan;
-    if ((rc = ragged_prepare(rx->dec, L, rx->cfg.fcpos, n_in, rows.data(), &rdev, &plan, tabs ? &tabs->rows : nullptr))) return rc;
-    if (follow_bits) {
-        // KFb, in front of KF (which runs its CRC over the row's third word): the streams that have an incoming sample size get the
-        // shift pair, sampleBytes / sampleBits and the CRC from the collector's committed m_outputMeta, in the device table, behind its
-        // upload and in front of every kernel that reads a row.  (The host's rows, `ss` and `mw` stay the host's values: every ragged
-        // decimator launch takes the pair from the device row, and K2r the third word)
-        hipError_t e = launch_rx_follow_bits(follow_bits, const_cast<RaggedRow *>(rdev), L, S, c->stream);
-        if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "follow bits launch: %s", hipGetErrorString(e));
-    }
-    if (follow) {
-        // KF: the streams that have incoming meta get {fc, rate >> L, CRC} from the collector's committed m_outputMeta, in the device
-        // table (over the row's own third word), behind its upload and in front of K2r, the one kernel that reads a row's words (the host's rows, `mw` and the
-        // rate handed to the decimator launch stay the configuration's)
-        hipError_t e = launch_rx_follow_meta(follow, const_cast<RaggedRow *>(rdev), L, S, c->stream);
-        if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "follow meta launch: %s", hipGetErrorString(e));
-    }
+    if (int rc = ragged_prepare(rx->dec, L, rx->cfg.fcpos, n.n_in, rows.data(), &rdev, &plan, call.tabs ? &call.tabs->rows : nullptr)) return rc;
+    hipError_t e = hipSuccess;
+    // KFb, in front of KF (which runs its CRC over the row's third word): the streams that have an incoming sample size get the
+    // shift pair, sampleBytes / sampleBits and the CRC from the collector's committed m_outputMeta, in the device table, behind its
+    // upload and in front of every kernel that reads a row.  (The host's rows, `ss` and `mw` stay the host's values: every ragged
+    // decimator launch takes the pair from the device row, and K2r the third word)
+    if (call.follow_bits) e = launch_rx_follow_bits(call.follow_bits, const_cast<RaggedRow *>(rdev), L, S, c->stream);
+    if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "follow bits launch: %s", hipGetErrorString(e));
+    // KF: the streams that have incoming meta get {fc, rate >> L, CRC} from the collector's committed m_outputMeta, in the device
+    // table (over the row's own third word), behind its upload and in front of K2r, the one kernel that reads a row's words (the
+    // host's rows, `mw` and the rate handed to the decimator launch stay the configuration's)
+    if (call.follow) e = launch_rx_follow_meta(call.follow, const_cast<RaggedRow *>(rdev), L, S, c->stream);
+    return e == hipSuccess ? SDRHIP_OK : fail(SDRHIP_EDEVICE, "follow meta launch: %s", hipGetErrorString(e));
+}
 
-    // ---- input: host rows staged stream by stream (n_in[s] samples each), 8-bit rows widened by K0r
-    const int16_t *din = iq_in;
-    size_t dstride = in_stride;
+// input: per-stream formats through K0x, host rows staged stream by stream (n_in[s] samples each), 8-bit rows widened by K0r
+int RxRagged::input(const int16_t *iq_in, size_t in_stride)
+{
+    const size_t max_in = n.max_in;
+    const bool wide8 = route.widen;
     const void *src = iq_in;
-    if (fmts) {
-        if ((rc = rx_unpack_rows(rx, iq_in, in_stride, n_in, fmts, in_dev, &din, &dstride))) return rc;
-    } else if (!in_dev) {
+    int rc;
+    din = iq_in; dstride = in_stride;
+    if (route.unpack) return rx_unpack_rows(rx, iq_in, in_stride, n.n_in, rx->streams.formats(), route.in_dev, &din, &dstride);
+    if (route.stage) {
         dstride = wide8 ? (max_in + 7) & ~(size_t)7 : (max_in + 3) & ~(size_t)3;
-        if ((rc = ragged_stage_in(c, rx->r_pin, c->in, iq_in, in_stride, n_in, S, wide8 ? 2 : 4, dstride, &src))) return rc;
+        if ((rc = ragged_stage_in(c, rx->r_pin, c->in, iq_in, in_stride, n.n_in, S, wide8 ? 2 : 4, dstride, &src))) return rc;
         din = static_cast<const int16_t *>(src);
     }
-    if (wide8) {
-        const size_t sstride = dstride;
-        dstride = (max_in + 3) & ~(size_t)3;
-        if ((rc = rx->wide.reserve((size_t)S * dstride * 4 + 16))) return rc;
-        hipError_t e;
-        {
-            KTimer kt(c, SDRHIP_K_CONVERT);
-            e = launch_iq8_widen_ragged(rx->in_fmt, static_cast<const uint8_t *>(src), sstride, rx->wide.as<int16_t>(), dstride, max_in, S, rdev, c->stream);
-        }
-        if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "widen launch: %s", hipGetErrorString(e));
-        din = rx->wide.as<int16_t>();
+    if (!wide8) return SDRHIP_OK;
+    const size_t sstride = dstride;
+    dstride = (max_in + 3) & ~(size_t)3;
+    if ((rc = rx->wide.reserve((size_t)S * dstride * 4 + 16))) return rc;
+    hipError_t e;
+    {
+        KTimer kt(c, SDRHIP_K_CONVERT);
+        e = launch_iq8_widen_ragged(rx->in_fmt, static_cast<const uint8_t *>(src), sstride, rx->wide.as<int16_t>(), dstride, max_in, S, rdev, c->stream);
     }
+    din = rx->wide.as<int16_t>();
+    return e == hipSuccess ? SDRHIP_OK : fail(SDRHIP_EDEVICE, "widen launch: %s", hipGetErrorString(e));
+}
 
-    // ---- decimate: the matrix-core launch (K1mr) stores straight into each stream's window (context option rx_direct, the
-    // default), its VALU pieces write the meta blocks; otherwise stream order, and K2r lays each stream's samples into its window
-    const bool direct = plan.mfma && c->opt.rx_direct && stream_bytes < 0x3fffffffu;
-    const size_t lstride = (max_dec + 3) & ~(size_t)3;
+// decimate and frame: K1mr straight into each stream's window, its VALU pieces write the meta blocks; otherwise stream order + K2r
+int RxRagged::decimate()
+{
+    const bool direct = rx_stores_direct(rx, plan.mfma);
+    const size_t lstride = (n.max_dec + 3) & ~(size_t)3;
     DevBuf &lin = rx->lin[0];
+    int rc;
     if (direct) {
-        rc = decimate_ragged_device(rx->dec, L, rx->cfg.fcpos, ss.data(), din, dstride, reinterpret_cast<int16_t *>(area), stream_bytes / 4,
-                                    rows.data(), rdev, plan, 1, (int)FB, mw, rx->cfg.sample_rate);
+        rc = decimate_ragged_device(rx->dec, L, rx->cfg.fcpos, ss.data(), din, dstride, reinterpret_cast<int16_t *>(area), stream_bytes / 4, rows.data(), rdev, plan, 1,
+                                    (int)FB, mw, rx->cfg.sample_rate);
     } else {
         if ((rc = lin.reserve((size_t)S * lstride * 4 + 16))) return rc;
         rc = decimate_ragged_device(rx->dec, L, rx->cfg.fcpos, ss.data(), din, dstride, lin.as<int16_t>(), lstride, rows.data(), rdev, plan);
     }
     if (rc) return rc;
     rx->consumed = true;
-    if (max_dec && (!direct || sw || follow || follow_bits)) {
-        FrameArgs fa;
-        memset(&fa, 0, sizeof(fa));
-        fa.in = lin.as<unsigned>(); fa.out = reinterpret_cast<unsigned *>(area);
-        fa.in_stride = lstride; fa.out_stride = stream_bytes / 4;
-        fa.n = max_dec; fa.frame_blocks = (int)FB;
-        memcpy(fa.meta_w, mw, sizeof(fa.meta_w));
-        fa.meta_rate = rx->cfg.sample_rate;
-        hipError_t e;
-        if (direct) {
-            // K1mr's pieces wrote the meta blocks with the shared record (that kernel has no register to spare for the streams'
-            // words): K2r, without samples, writes them again with each stream's own values (the host's arrays, KFb's or KF's)
-            int max_started = 0;
-            for (int s = 0; s < S; ++s) if (rows[(size_t)s].meta_count > max_started) max_started = rows[(size_t)s].meta_count;
-            e = max_started ? launch_frame_meta_ragged(fa, rdev, max_started, S, c->stream) : hipSuccess;
-        } else
-            e = launch_frame_pack_ragged(fa, rdev, S, c->stream);
-        if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "frame pack launch: %s", hipGetErrorString(e));
+    const RxK2rJob job = rx_ragged_k2r(n.max_dec != 0, direct, sw != nullptr, call.follow != nullptr, call.follow_bits != nullptr);
+    if (job == RX_K2R_NONE) return SDRHIP_OK;
+    FrameArgs fa;
+    memset(&fa, 0, sizeof(fa));
+    fa.in = lin.as<unsigned>(); fa.out = reinterpret_cast<unsigned *>(area); fa.in_stride = lstride; fa.out_stride = stream_bytes / 4;
+    fa.n = n.max_dec; fa.frame_blocks = (int)FB;
+    memcpy(fa.meta_w, mw, sizeof(fa.meta_w)); fa.meta_rate = rx->cfg.sample_rate;
+    hipError_t e = hipSuccess;
+    if (job == RX_K2R_PACK) e = launch_frame_pack_ragged(fa, rdev, S, c->stream);
+    else { // (without samples: as many frames per stream as the busiest one starts)
+        int max_started = 0;
+        for (int s = 0; s < S; ++s) if (rows[(size_t)s].meta_count > max_started) max_started = rows[(size_t)s].meta_count;
+        if (max_started) e = launch_frame_meta_ragged(fa, rdev, max_started, S, c->stream);
     }
+    return e == hipSuccess ? SDRHIP_OK : fail(SDRHIP_EDEVICE, "frame pack launch: %s", hipGetErrorString(e));
+}
 
-    // ---- FEC: one launch over the completed frames of every stream (a dense list: frame f of stream s = area frame s * cap + slot).
-    // Per-stream fecblk: recovery row r of CM256 is Cauchy row 128 + r whatever the count, so a frame encoded with R' >= its own
-    // count carries its own encoding in its first rows: the frames are grouped by the form fec_encode_device chooses for their own
-    // count, each group present is ONE launch with the group's largest count (at most three; the surplus rows land in the
-    // unspecified rest of the slot); streams without recovery blocks are left out
-    if (sum_done && R > 0) {
-        const size_t nl = rx_flist_entries(sum_done);
-        PinnedBuf &fpin = tabs ? tabs->flist : rx->r_flist_pin;
-        if ((rc = fpin.reserve(nl * 4))) return rc;
-        if ((rc = rx->r_flist.reserve(nl * 4))) return rc;
-        int32_t *fl = fpin.as<int32_t>();
-        size_t k = 0, g_first[3], g_count[3];
-        int g_rows[3] = {0, 0, 0};
-        for (int form = 0; form < 3; ++form) {
-            g_first[form] = k;
-            for (int s = 0; s < S; ++s) {
-                const int rs = rx_fec_of(rx, (size_t)s);
-                if (rs <= 0 || !done[(size_t)s] || rx_encode_form(c, rs) != form) continue;
-                g_rows[form] = rs > g_rows[form] ? rs : g_rows[form];
-                for (size_t f = 0; f < done[(size_t)s]; ++f) fl[k++] = (int32_t)A.index((size_t)s, f);
-            }
-            while (k % GF_FRAMES_PER_GROUP) fl[k++] = -1;
-            g_count[form] = k - g_first[form];
-        }
-        if (k > nl) return fail(SDRHIP_EINVAL, "rx_process_ragged: frame list"); // (cannot happen: rx_flist_entries counts three paddings)
-        if (k) {
-            HIP_TRY(hipMemcpyAsync(rx->r_flist.p, fl, k * 4, hipMemcpyHostToDevice, c->stream));
-            fpin.mark(c->stream);
-        }
-        for (int form = 0; form < 3; ++form)
-            if (g_count[form] && (rc = fec_encode_device(c, area, frame_bytes, (size_t)S * A.cap(), g_rows[form], area + (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE,
-                                                         frame_bytes, rx->r_flist.as<int32_t>() + g_first[form], (int)(g_count[form] / GF_FRAMES_PER_GROUP))))
-                return rc;
+// FEC: the completed frames of every stream as a dense list (frame f of stream s = area frame s * cap + slot), one launch per
+// encoder form present (rx_encode_groups; the surplus rows of a group's largest count land in the unspecified rest of the slot)
+int RxRagged::encode()
+{
+    const RxFrameArea &A = rx->area;
+    int rc;
+    if (!(n.sum_done && FB > (size_t)SDRHIP_NB_ORIGINAL)) return SDRHIP_OK;
+    const size_t nl = rx_flist_entries(n.sum_done);
+    PinnedBuf &fpin = call.tabs ? call.tabs->flist : rx->r_flist_pin;
+    if ((rc = fpin.reserve(nl * 4))) return rc;
+    if ((rc = rx->r_flist.reserve(nl * 4))) return rc;
+    int32_t *fl = fpin.as<int32_t>();
+    const RxEncGroups g = rx_encode_groups((size_t)S, [&](size_t s) { const RxEncStream e = {rx_fec_of(rx, s), n.done[s], A.index(s)}; return e; }, enc128_min_rows(c), fl);
+    if (g.k > nl) return fail(SDRHIP_EINVAL, "rx_process_ragged: frame list"); // (cannot happen: rx_flist_entries counts three paddings)
+    if (g.k) {
+        HIP_TRY(hipMemcpyAsync(rx->r_flist.p, fl, g.k * 4, hipMemcpyHostToDevice, c->stream));
+        fpin.mark(c->stream);
     }
-
-    // ---- delivery: every stream's window (one 2-D copy when the windows line up, else a copy per stream)
-    bool same_base = true;
-    for (int s = 1; s < S; ++s) same_base = same_base && A.slot((size_t)s) == A.slot(0);
-    if (frames_out && max_done) {
-        const hipMemcpyKind kind = mem == SDRHIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-        // (the datagram entry's host callers get each stream's own frames and no more: its link traffic is datagrams up, frames down)
-        bool same_done = true;
-        for (int s = 1; s < S; ++s) same_done = same_done && done[(size_t)s] == done[0];
-        if (mixed) {
-            // per-stream fecblk: each stream's frames dense, 128 + nb_fec[s] super blocks each -- a 2-D copy per stream from the pitched area
-            for (int s = 0; s < S; ++s)
-                if (done[(size_t)s])
-                    HIP_TRY(link_copy2d(c, frames_out + (size_t)s * frame_stride_bytes, rx_stream_bytes(rx, (size_t)s), area + A.index((size_t)s) * frame_bytes,
-                                        frame_bytes, rx_stream_bytes(rx, (size_t)s), done[(size_t)s], kind, c->stream));
-        } else if (same_base && (same_done || !(dev_rows && mem == SDRHIP_MEM_HOST))) {
-            HIP_TRY(link_copy2d(c, frames_out, S > 1 ? frame_stride_bytes : max_done * frame_bytes, area + A.slot(0) * frame_bytes, stream_bytes,
-                                max_done * frame_bytes, S, kind, c->stream));
-        } else {
-            for (int s = 0; s < S; ++s)
-                if (done[(size_t)s])
-                    HIP_TRY(link_copy(c, frames_out + (size_t)s * frame_stride_bytes, area + A.index((size_t)s) * frame_bytes,
-                                      done[(size_t)s] * frame_bytes, kind, c->stream));
-        }
-    }
-    rx->view.set_each(area, stream_bytes, (size_t)S, A.slots(), done.data());
-    for (int s = 0; s < S; ++s) n_frames[s] = done[(size_t)s];
-    rx->area.commit(done.data(), n.rest.data());
-    if (mem == SDRHIP_MEM_HOST) HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int form = 0; form < 3; ++form)
+        if (g.count[form] && (rc = fec_encode_device(c, area, frame_bytes, (size_t)S * A.cap(), g.rows[form], area + (size_t)SDRHIP_NB_ORIGINAL * SDRHIP_UDPSIZE, frame_bytes,
+                                                     rx->r_flist.as<int32_t>() + g.first[form], (int)(g.count[form] / GF_FRAMES_PER_GROUP))))
+            return rc;
     return SDRHIP_OK;
+}
+
+// delivery: every stream's window in the shape rx_ragged_delivery names, the view, and the windows move on
+int RxRagged::deliver(const RxFramesOut &out)
+{
+    const RxFrameArea &A = rx->area;
+    const size_t nS = (size_t)S, max_done = n.max_done;
+    const std::vector<size_t> &done = n.done;
+    if (out.frames && max_done) {
+        const hipMemcpyKind kind = out.mem == SDRHIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        bool same_base = true, same_done = true;
+        for (size_t s = 1; s < nS; ++s) { same_base = same_base && A.slot(s) == A.slot(0); same_done = same_done && done[s] == done[0]; }
+        const RxRaggedDelivery shape = rx_ragged_delivery(rx_fec_mixed(rx), same_base, same_done, call.dev_rows, out.mem == SDRHIP_MEM_HOST);
+        if (shape == RX_DELIVER_RECTANGLE)
+            HIP_TRY(link_copy2d(c, out.frames, S > 1 ? out.stride_bytes : max_done * frame_bytes, area + A.slot(0) * frame_bytes, stream_bytes, max_done * frame_bytes, nS,
+                                kind, c->stream));
+        for (size_t s = 0; s < nS && shape != RX_DELIVER_RECTANGLE; ++s) {
+            uint8_t *to = out.frames + s * out.stride_bytes;
+            const uint8_t *from = area + A.index(s) * frame_bytes;
+            if (!done[s]) continue;
+            if (shape == RX_DELIVER_PITCHED) // (each stream's frames dense, 128 + nb_fec[s] super blocks each)
+                HIP_TRY(link_copy2d(c, to, rx_stream_bytes(rx, s), from, frame_bytes, rx_stream_bytes(rx, s), done[s], kind, c->stream));
+            else
+                HIP_TRY(link_copy(c, to, from, done[s] * frame_bytes, kind, c->stream));
+        }
+    }
+    rx->view.set_each(area, stream_bytes, nS, A.slots(), done.data());
+    for (size_t s = 0; s < nS; ++s) out.n_frames[s] = done[s];
+    rx->area.commit(done.data(), n.rest.data());
+    if (out.mem == SDRHIP_MEM_HOST) HIP_TRY(hipStreamSynchronize(c->stream));
+    return SDRHIP_OK;
+}
+
+// A call that fails after it moved windows leaves the windows moved (the open frames lie there now) and the rest of the framing
+// state untouched.
+int sdrhip::rx_ragged(sdrhip_rx *rx, const int16_t *iq_in, const RxRaggedCounts &n, size_t in_stride, const uint32_t *tv_sec, const uint32_t *tv_usec,
+                      const RxFramesOut &out, const RxRaggedCall &call)
+{
+    const int S = rx->nstreams;
+    const size_t max_in = n.max_in;
+    for (int s = 0; s < S; ++s) out.n_frames[s] = 0;
+    // ---- everything that can be refused is checked before anything is consumed
+    if (int e = check_mem(out.mem)) return e;
+    if (rx->pipelined) return fail(SDRHIP_EINVAL, "rx_process_ragged: not available in pipelined mode");
+    if (!call.batch && rx_batches_active(rx)) return fail(SDRHIP_EINVAL, "rx_process_ragged: asynchronous batches are being filled or in flight: collect them first");
+    if (S == 1) in_stride = max_in;
+    if (S > 1 && in_stride < max_in) return fail(SDRHIP_EINVAL, "rx_process_ragged: in_stride smaller than the largest count");
+    if (max_in && !iq_in) return fail(SDRHIP_EINVAL, "rx_process_ragged: NULL input");
+    // (per-stream input format: the caller's rows are K0x's source, 4-byte units of stride whatever a row holds)
+    const RxRaggedInput input = rx_ragged_input(call.batch, call.dev_rows, rx->streams.formats() != nullptr, rx->in_fmt == IQF_S16, out.mem == SDRHIP_MEM_DEVICE);
+    if (input.unpack && !unpackx_measure(n.n_in, 1, (size_t)S, rx->streams.formats()).fits) return fail(SDRHIP_EINVAL, "rx_process_ragged: too many samples for one launch");
+    if (max_in && input.in_dev && (!aligned16(iq_in) || (S > 1 && (in_stride & (input.widen ? 7 : 3)))))
+        return fail(SDRHIP_EALIGN, "rx_process_ragged: device input must be 16-byte aligned, its stride a multiple of %d samples", input.widen ? 8 : 4);
+    if (int e = rx_refuse_delivery("rx_process_ragged", n, out.frames, out.stride_bytes, out.mem, false)) return e;
+    HIP_TRY(hipSetDevice(rx->ctx->device));
+    rx->consumed = false;
+    if (max_in == 0) { rx->view.clear(); return SDRHIP_OK; } // nothing arrives: nothing changes, nothing is delivered
+    int rc;
+    // ---- windows: stream s fills slots slot(s) .. slot(s) + done[s] of its area (what moves when: RxFrameArea::plan)
+    if ((rc = rx_release_old(rx))) return rc;
+    if ((rc = rx_make_room(rx, n.done.data(), false, "rx_process_ragged"))) return rc;
+    const size_t fb = rx_frame_bytes(rx);
+    RxRagged rg = {rx, rx->ctx, S, rx->cfg.log2decim, n, call, input, fb / SDRHIP_UDPSIZE, fb, rx->area.cap() * fb, rx->work.as<uint8_t>(), std::vector<unsigned>((size_t)S),
+                   {0}, rx->streams.records(rx_bank(rx)), std::vector<RaggedRow>((size_t)S), nullptr, RaggedPlan(), nullptr, 0};
+    rx_meta_base(rx->cfg, rg.mw);
+    if ((rc = rg.table(tv_sec, tv_usec))) return rc;
+    if ((rc = rg.input(iq_in, in_stride))) return rc;
+    if ((rc = rg.decimate())) return rc;
+    if ((rc = rg.encode())) return rc;
+    return rg.deliver(out);
 }
 
 extern "C" int sdrhip_rx_process_ragged(sdrhip_rx *rx, const int16_t *iq_in, const size_t *n_in, size_t in_stride, const uint32_t *tv_sec,
@@ -980,5 +979,6 @@ extern "C" int sdrhip_rx_process_ragged(sdrhip_rx *rx, const int16_t *iq_in, con
     if (!rx) return fail(SDRHIP_EINVAL, "rx is NULL");
     if (!n_in || !tv_sec || !tv_usec || !n_frames) return fail(SDRHIP_EINVAL, "rx_process_ragged: NULL count, stamp or n_frames array");
     sdrhip::CtxLock lock_(rx->ctx);
-    return rx_ragged(rx, iq_in, rx_counts(rx, n_in), in_stride, tv_sec, tv_usec, frames_out, frame_stride_bytes, n_frames, mem);
+    const RxFramesOut out = {frames_out, frame_stride_bytes, n_frames, mem};
+    return rx_ragged(rx, iq_in, rx_counts(rx, n_in), in_stride, tv_sec, tv_usec, out);
 }

@@ -128,8 +128,9 @@ int rx_launch_ragged(sdrhip_rx *rx, sdrhip_rx::Batch &b)
 
     // ---- the batch as one ragged step
     std::vector<size_t> nf((size_t)S, 0);
-    rc = rx_ragged(rx, rx->a_din.as<int16_t>(), n, dstride, b.r_sec.data(), b.r_usec.data(), nullptr, 0, nf.data(),
-                   SDRHIP_MEM_DEVICE, true);
+    const RxFramesOut view_only = {nullptr, 0, nf.data(), SDRHIP_MEM_DEVICE};
+    const RxRaggedCall batch = {true, false, nullptr, nullptr, nullptr};
+    rc = rx_ragged(rx, rx->a_din.as<int16_t>(), n, dstride, b.r_sec.data(), b.r_usec.data(), view_only, batch);
     if (rc) {
         if (rx->consumed) b.state = 0; // consumed and lost: never replayed (the pipe's own error stands)
         return rc;

@@ -121,10 +121,10 @@ extern "C" int sdrhip_rx_process_datagrams(sdrhip_rx *rx, const uint8_t *dgrams,
         return SDRHIP_OK;
     }
     // (follow: the state this call's collection committed -- fecbuf_collect has flipped the double buffer)
-    if ((rc = rx_ragged(rx, rx->j_rows.as<int16_t>(), ad.n, rx->j_row_len, tv_sec, tv_usec, frames_out, frame_stride_bytes, n_frames, mem,
-                        false, true, nullptr, rx->follow_meta ? fecbuf_committed_state(rx->fb) : nullptr,
-                        rx->follow_bits ? fecbuf_committed_state(rx->fb) : nullptr)))
-        return rc;
+    const RxFramesOut out = {frames_out, frame_stride_bytes, n_frames, mem};
+    const RxRaggedCall rows = {false, true, nullptr, rx->follow_meta ? fecbuf_committed_state(rx->fb) : nullptr,
+                               rx->follow_bits ? fecbuf_committed_state(rx->fb) : nullptr};
+    if ((rc = rx_ragged(rx, rx->j_rows.as<int16_t>(), ad.n, rx->j_row_len, tv_sec, tv_usec, out, rows))) return rc;
     hipError_t e = launch_rx_join_carry(rx->j_rows.as<int16_t>(), rx->j_row_len, carry_dev, counts, (unsigned)U, S, c->stream);
     if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "rx join launch: %s", hipGetErrorString(e));
     *carry = ad.join.left;

@@ -55,7 +55,7 @@ static int rx_submit_batch(sdrhip_rx *rx, FecBufBatch &in, const uint32_t *tv_se
     const size_t seg_bytes = (size_t)2 * S * sizeof(RxDeliverSeg);
     // everything that can fail for want of memory comes before the collector moves (a device buffer that grows waits for the
     // batches in flight; the rows keep their heads): the batch's own buffers, then what the ragged step takes for these counts
-    // (rx_ragged_room: frame area, tables, frame list; it names the one allocation it cannot foresee).  The pinned tables are the ring slot's own, so that what a submit waits
+    // (rx_ragged_room: frame area, tables, frame list, stream-order rows).  The pinned tables are the ring slot's own, so that what a submit waits
     // for is this slot's previous batch -- which the caller has collected -- and never the batch before it
     if (in.dev_bytes && (rc = reserve_settled(c, rx->a_pk, in.dev_bytes + 16))) return rc;
     if (kmax && (rc = rx_join_rows(rx, kmax, who))) return rc;
@@ -87,10 +87,10 @@ static int rx_submit_batch(sdrhip_rx *rx, FecBufBatch &in, const uint32_t *tv_se
     if (rc) return fecbuf_batch_lost(who, rc);
     // ---- decimate, frame, encode: one ragged step; KJ moves every row's remainder to its head (the device's own counts)
     if (any) {
-        if ((rc = rx_ragged(rx, rx->j_rows.as<int16_t>(), n, rx->j_row_len, tv_sec, tv_usec, nullptr, 0, nf.data(), SDRHIP_MEM_DEVICE,
-                            true, true, &b.d_tabs, rx->follow_meta ? fecbuf_committed_state(rx->fb) : nullptr, // (the flags as they stand at this submit)
-                            rx->follow_bits ? fecbuf_committed_state(rx->fb) : nullptr)))
-            return fecbuf_batch_lost(who, rc);
+        const RxFramesOut view_only = {nullptr, 0, nf.data(), SDRHIP_MEM_DEVICE};
+        const RxRaggedCall batch = {true, true, &b.d_tabs, rx->follow_meta ? fecbuf_committed_state(rx->fb) : nullptr, // (the flags as they stand at this submit)
+                                    rx->follow_bits ? fecbuf_committed_state(rx->fb) : nullptr};
+        if ((rc = rx_ragged(rx, rx->j_rows.as<int16_t>(), n, rx->j_row_len, tv_sec, tv_usec, view_only, batch))) return fecbuf_batch_lost(who, rc);
         hipError_t e = launch_rx_join_carry(rx->j_rows.as<int16_t>(), rx->j_row_len, carry_dev, counts, (unsigned)U, S, c->stream);
         if (e != hipSuccess) return fail(SDRHIP_EDEVICE, "rx join launch: %s (the batch is lost)", hipGetErrorString(e));
         *carry = fed.left;

@@ -130,7 +130,9 @@ def test_lives_in_a_translation_unit_of_its_own():
     host = open(os.path.join(iq8.CSRC, "sdrhip_rx.cpp")).read()
     assert host.count("launch_rx_follow_bits(") == 1
     assert host.index("ragged_prepare(rx->dec") < host.index("launch_rx_follow_bits(") < host.index("launch_rx_follow_meta(")
-    assert "!direct || sw || follow || follow_bits" in host
+    # (K2r's job is the step planner's decision: the ragged step asks it with the flag, the rule itself stands in rx_step_plan.h)
+    assert "rx_ragged_k2r(" in host and "call.follow_bits != nullptr" in host
+    assert "!direct || sw || follow || follow_bits" in open(os.path.join(iq8.CSRC, "rx_step_plan.h")).read()
 
 
 def test_arithmetic_is_one_text_for_host_and_device():
